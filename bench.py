@@ -15,6 +15,14 @@ Default workload (config.workload): BASELINE.json configs[2] geometry, the one t
 quoted on -- DeiT-tiny-p8 tokens (N = 28x28 = 784, 3 heads, d = 64), per-GPU batch 128.
 `--attn eva|lara|softmax|local|performer|ra|scatterbrain` selects the attention (default: see DEFAULT_ATTN);
 `--attn causal_eva --workload lm` is the wikitext-103 decoder self-attention.
+
+A plain run sets up, warms up, times the K steps and prints the line (`value`, `ms_per_step`, `config`).  `--full` adds
+everything else the line used to carry: the spread over five more blocks, the eager step, per-kernel HIP-event times and
+the roofline, the measured HBM copy bandwidth, the CPU baseline and the other workloads (`other_workloads`).
+`--dump-outputs DIR` writes what the last timed step computed (layer output, input and parameter gradients, updated
+parameters) as DIR/<name>.npy.  The clock pre-warm runs for a time, not a number of steps, so after it the layer's state
+and the random generator are put back to where they were before the first step: the same arguments give the timed steps
+the same inputs from run to run.
 """
 import argparse
 import json
@@ -47,6 +55,29 @@ def _emit(line):
     sys.stdout.flush()
     ctypes.CDLL(None).fflush(None)
     print(json.dumps(line), flush=True)
+
+
+DUMP_SAMPLE = 1 << 20          # elements per array in --dump-outputs: larger arrays are sampled at fixed, seeded positions
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def dump_outputs(out_dir, arrays):
+    """Write {name: tensor} as out_dir/<name>.npy in float32 (float64 stays float64).  An array of more than DUMP_SAMPLE
+    elements is replaced by DUMP_SAMPLE of its (flattened) elements at positions drawn from a generator seeded with 0, so
+    the same shape always gives the same positions."""
+    import numpy as np
+    host = {}
+    for name, t in arrays.items():
+        t = t.detach()
+        if t.numel() > DUMP_SAMPLE:
+            idx = torch.randint(t.numel(), (DUMP_SAMPLE,), generator=torch.Generator().manual_seed(0)).sort().values
+            t = t.reshape(-1)[idx.to(t.device)]
+        host[name] = t.to(torch.float64 if t.dtype == torch.float64 else torch.float32).cpu().numpy()
+    if sum(v.nbytes for v in host.values()) > DUMP_LIMIT_BYTES:
+        raise RuntimeError("--dump-outputs: more than %d MB of outputs" % (DUMP_LIMIT_BYTES >> 20))
+    os.makedirs(out_dir, exist_ok=True)
+    for name, v in host.items():
+        np.save(os.path.join(out_dir, name + ".npy"), v)
 
 
 def attn_args(attn, dim, heads, seq):
@@ -212,7 +243,7 @@ def measure_workload(attn, B, C, H, seq, dev, steps=10, warmup=3, tune=True, ove
     lm = attn == "causal_eva"                                        # fairseq decoder self-attention: time-first, (q, k, v) call
     xshape = (seq[0], B, C) if lm else (B,) + tuple(seq) + (C,)
     x = torch.randn(*xshape, device=dev, requires_grad=True)
-    g = torch.randn(*xshape, device=dev).to(torch.bfloat16)
+    g = (torch.randn(*xshape, device=dev) / (B * N)).to(torch.bfloat16)      # token mean, as in main()
     params = list(layer.parameters())
     big = [prm for prm in params if prm.numel() >= 16384]
     small = [prm for prm in params if prm.numel() < 16384]
@@ -298,6 +329,11 @@ def main():
                     help="skip PyTorch TunableOp selection of the hipBLASLt/rocBLAS projection GEMMs")
     ap.add_argument("--gemm-tune-file", default=None,
                     help="TunableOp results file: read (no tuning) if it exists, else tuned and written at exit")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps, also measure the spread, the eager step, per-kernel times / roofline, the HBM "
+                         "copy bandwidth, the CPU baseline and the other workloads")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step computed as DIR/<name>.npy (float32, <= 64 MB in all)")
     a = ap.parse_args()
     if a.workload.startswith("model_"):
         return main_model(a)
@@ -311,6 +347,9 @@ def main():
     # EA_BENCH_FORCE_DDP=1: dev-only, run the N > 1 code path (process group, DDP wrapper, eager
     # stepping) with a single rank to measure its host-side overhead on one GPU
     ddp = world > 1 or bool(os.environ.get("EA_BENCH_FORCE_DDP"))
+    if ddp and a.dump_outputs:
+        # two schedules are captured and one is chosen by timing: the tensors left behind may be the other one's buffers
+        ap.error("--dump-outputs needs the single-process layer step (not the data-parallel one)")
     if os.environ.get("EA_BENCH_ONE_DEVICE"):
         local = 0
     torch.cuda.set_device(local)                # before the process group: RCCL binds to the current device
@@ -346,7 +385,9 @@ def main():
     LR = 1e-3
     xshape = (seq[0], B, C) if a.attn == "causal_eva" else (B,) + tuple(seq) + (C,)   # fairseq is time-first
     x = torch.randn(*xshape, device=dev, requires_grad=True)
-    g = torch.randn(*xshape, device=dev).to(torch.bfloat16)        # cotangent of y, in y's dtype
+    # cotangent of y, in y's dtype: the gradient of the token MEAN of y . g.  With the plain sum the objective (linear in y)
+    # drives the weights to inf / NaN within ~20 SGD steps at LR, and every later step would compute on NaN.
+    g = (torch.randn(*xshape, device=dev) / (B * N)).to(torch.bfloat16)
     if a.attn == "causal_eva":
         def model(t):
             return layer(t, t, t)[0]
@@ -370,6 +411,8 @@ def main():
             tunable.set_filename(os.path.join(tempfile.gettempdir(), "ea_bench_tunableop_%d.csv" % os.getpid()))
             tunable.tuning_enable(True)
 
+    last = {}                               # the output of the latest step (inside a captured step: the graph's own buffer)
+
     def fwd_bwd():
         for prm in params:
             prm.grad = None
@@ -377,6 +420,7 @@ def main():
         with torch.autocast("cuda", dtype=torch.bfloat16):
             y = model(x)
         y.backward(g)                       # == (y * g).sum().backward() without the loss arithmetic
+        last["y"] = y.detach()
 
     params = [prm for prm in layer.parameters()]
     if not ddp:
@@ -419,6 +463,16 @@ def main():
         if forced:
             schemes = {forced: schemes[forced]}
         parts = schemes.get("three_part", list(schemes.values())[0])
+    # the layer's state before any step: restored after the clock pre-warm (which runs for a time, not a number of steps)
+    initial_state = {k: v.clone() for k, v in layer.state_dict().items()}
+
+    def reset_state():
+        with torch.no_grad():
+            for k, v in layer.state_dict().items():
+                v.copy_(initial_state[k])
+            if ddp:
+                bucket.flat.zero_()
+        torch.manual_seed(1234 + rank)      # the layer's sampling (e.g. LARA's noise) restarts as well, captured steps included
 
     def step():
         for f in parts:
@@ -491,6 +545,7 @@ def main():
         return bool(flag.item())
     from efficient_attention.data_parallel import prewarm_replays
     prewarm_replays(run, prewarm_ms, torch.cuda.synchronize, agree=_agree if world > 1 else None)
+    reset_state()
     for _ in range(a.warmup):
         run()
 
@@ -508,10 +563,15 @@ def main():
         t = torch.tensor([el], device=dev, dtype=torch.float64)
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         el = float(t.item())
+    if rank == 0 and a.dump_outputs:
+        named = list(layer.named_parameters())
+        dump_outputs(a.dump_outputs, dict([("y", last["y"]), ("dx", x.grad)]
+                                          + [("grad." + n, prm.grad) for n, prm in named if prm.grad is not None]
+                                          + [("param." + n, prm) for n, prm in named]))
 
     # ---- spread of the measurement: five more blocks of `steps` steps each (not part of `value`) ----
     blocks_ms = []
-    if world == 1:
+    if world == 1 and a.full:
         for _ in range(5):
             torch.cuda.synchronize()
             tb = time.perf_counter()
@@ -523,31 +583,32 @@ def main():
     # ---- the same step run EAGERLY (the reference's call sites run eagerly, vit/engine.py:47-64) ----
     # Host-bound, so host jitter shows: five blocks, the median is reported (one 20-step block read 0.67 .. 0.93 ms on the
     # same box within a minute), min / max next to it.
-    for _ in range(10):
-        step()
-    eager_blocks = []
-    n_eager = max(min(a.steps, 40), 1)
-    for _ in range(5 if world == 1 else 1):
-        torch.cuda.synchronize()
-        te = time.perf_counter()
-        for _ in range(n_eager):
+    if a.full:
+        for _ in range(10):
+            step()
+        eager_blocks = []
+        n_eager = max(min(a.steps, 40), 1)
+        for _ in range(5 if world == 1 else 1):
+            torch.cuda.synchronize()
+            te = time.perf_counter()
+            for _ in range(n_eager):
+                step()
+            torch.cuda.synchronize()
+            eager_blocks.append((time.perf_counter() - te) / n_eager * 1e3)
+        eager_ms = sorted(eager_blocks)[len(eager_blocks) // 2]
+
+        # ---- instrumented eager pass: HIP events around every launch of the dominant kernel ----
+        _ops.KERNEL_TIMER.enable()
+        for _ in range(min(a.steps, 10)):
             step()
         torch.cuda.synchronize()
-        eager_blocks.append((time.perf_counter() - te) / n_eager * 1e3)
-    eager_ms = sorted(eager_blocks)[len(eager_blocks) // 2]
-
-    # ---- instrumented eager pass: HIP events around every launch of the dominant kernel ----
-    _ops.KERNEL_TIMER.enable()
-    for _ in range(min(a.steps, 10)):
-        step()
-    torch.cuda.synchronize()
-    ktimes = _ops.KERNEL_TIMER.summary()
-    _ops.KERNEL_TIMER.disable()
+        ktimes = _ops.KERNEL_TIMER.summary()
+        _ops.KERNEL_TIMER.disable()
 
     # achievable HBM bandwidth of this GPU, babel-stream style: the library's own 16-byte-per-lane copy kernel
     # over 512 MB (read + write counted), next to the nominal 8 TB/s; torch's copy_ alongside for reference
     copy_gbs = copy_torch_gbs = None
-    if rank == 0:
+    if rank == 0 and a.full:
         from efficient_attention import _native as nv
         src = torch.empty(512 << 20, dtype=torch.uint8, device=dev)
         dst = torch.empty_like(src)
@@ -571,6 +632,7 @@ def main():
     if rank == 0:
         tokens = B * N * world * a.steps
         value = tokens / el
+    if rank == 0 and a.full:
         unit_bytes = B * H * N * d * 2                   # one [B,H,N,D] tensor in the I/O dtype
         # committed counter summaries, used only while they describe THIS build of the library
         # (tools/summarize_profile.py / summarize_sq.py stamp the .so's sha256 into them)
@@ -679,12 +741,11 @@ def main():
                     others[key]["attn"] = attn_o
                 except Exception as ex:          # never let an extra line take the headline measurement down
                     others[key] = {"error": str(ex).split("\n")[0][:200]}
+    if rank == 0:
         line = {
             "metric": "attn fwd+bwd tokens/s per GPU at N=784, d=64; 1/2/4/8-GPU DDP scaling",
             "value": value, "unit": "tokens/s", "n_gpus": world, "steps": a.steps, "warmup": a.warmup,
-            "ms_per_step": el / a.steps * 1e3, "eager_ms_per_step": round(eager_ms, 4),
-            "eager_ms_per_step_blocks": {"n": len(eager_blocks), "steps_each": n_eager, "min": round(min(eager_blocks), 4),
-                                         "median": round(eager_ms, 4), "max": round(max(eager_blocks), 4)},
+            "ms_per_step": el / a.steps * 1e3,
             "higher_is_better": True, "scaling": "weak",
             "vs_baseline": None, "dtype": "bf16", "data": "synthetic",
             "config": {"workload": "%s attention layer fwd+bwd+SGD, x=[%s] per GPU (N=%d, h=%d, d=%d), "
@@ -699,16 +760,23 @@ def main():
             "hbm_roofline_tokens_per_s_per_gpu": HBM_PEAK_GBS * 1e9 / (BYTES_PER_TOKEN_HEAD * H * d / 64),
             # whole layer priced on the op-level q,k,v -> out traffic (1536*h bytes per token at d = 64)
             "layer_algorithmic_gbs": value / world * BYTES_PER_TOKEN_HEAD * H * d / 64 / 1e9,
-            "hbm_measured_copy_gbs": None if copy_gbs is None else round(copy_gbs, 1),
-            "hbm_measured_torch_copy_gbs": None if copy_torch_gbs is None else round(copy_torch_gbs, 1),
-            "step_bytes": step_bytes,
-            "roofline": roof, "cpu_baseline": cpu,
-            "ms_per_step_blocks": None if not blocks_ms else {"n": len(blocks_ms), "steps_each": a.steps, "min": round(min(blocks_ms), 4),
-                                                              "median": round(sorted(blocks_ms)[len(blocks_ms) // 2], 4),
-                                                              "max": round(max(blocks_ms), 4)},
-            "other_workloads": others,
             "prewarm_ms": prewarm_ms,
         }
+        if a.full:
+            line.update({
+                "eager_ms_per_step": round(eager_ms, 4),
+                "eager_ms_per_step_blocks": {"n": len(eager_blocks), "steps_each": n_eager, "min": round(min(eager_blocks), 4),
+                                             "median": round(eager_ms, 4), "max": round(max(eager_blocks), 4)},
+                "hbm_measured_copy_gbs": None if copy_gbs is None else round(copy_gbs, 1),
+                "hbm_measured_torch_copy_gbs": None if copy_torch_gbs is None else round(copy_torch_gbs, 1),
+                "step_bytes": step_bytes,
+                "roofline": roof, "cpu_baseline": cpu,
+                "ms_per_step_blocks": None if not blocks_ms else {"n": len(blocks_ms), "steps_each": a.steps,
+                                                                  "min": round(min(blocks_ms), 4),
+                                                                  "median": round(sorted(blocks_ms)[len(blocks_ms) // 2], 4),
+                                                                  "max": round(max(blocks_ms), 4)},
+                "other_workloads": others,
+            })
     if ddp:
         dist.destroy_process_group()
     if rank == 0:
@@ -762,13 +830,15 @@ def main_model(a):
     if not a.no_gemm_tune:
         tunable.tuning_enable(False)
 
+    last = {}                               # what the latest timed step returned (the loss)
+
     def timed(fn, n):
         if world > 1:
             dist.barrier()
         torch.cuda.synchronize()
         t0 = time.perf_counter()
         for _ in range(n):
-            fn()
+            last["out"] = fn()
         torch.cuda.synchronize()
         if world > 1:
             dist.barrier()
@@ -782,40 +852,50 @@ def main_model(a):
     for _ in range(a.warmup):
         step()
     eager_el = timed(step, a.steps)
+    if rank == 0 and a.dump_outputs:
+        # the loss, and every parameter gradient / updated parameter of the model concatenated in parameters() order
+        prms = [p for p in wl.model.parameters() if p.grad is not None]
+        dump_outputs(a.dump_outputs, {"loss": last["out"],
+                                      "grads": torch.cat([p.grad.detach().reshape(-1).float() for p in prms]),
+                                      "params": torch.cat([p.detach().reshape(-1).float() for p in prms])})
     graph_ms = None
-    if not a.no_graph and not ddp:
-        try:
-            replay = trainer.capture_step(step)
-            for _ in range(3):
-                replay()
-            graph_ms = timed(replay, a.steps) / a.steps * 1e3
-        except Exception as ex:
-            print("graph capture unavailable (%s)" % str(ex).split("\n")[0], file=sys.stderr)
-            torch.cuda.synchronize()
-    _ops.KERNEL_TIMER.enable()
-    for _ in range(min(a.steps, 5)):
-        step()
-    torch.cuda.synchronize()
-    ktimes = _ops.KERNEL_TIMER.summary()
-    _ops.KERNEL_TIMER.disable()
+    if a.full:
+        if not a.no_graph and not ddp:
+            try:
+                replay = trainer.capture_step(step)
+                for _ in range(3):
+                    replay()
+                graph_ms = timed(replay, a.steps) / a.steps * 1e3
+            except Exception as ex:
+                print("graph capture unavailable (%s)" % str(ex).split("\n")[0], file=sys.stderr)
+                torch.cuda.synchronize()
+        _ops.KERNEL_TIMER.enable()
+        for _ in range(min(a.steps, 5)):
+            step()
+        torch.cuda.synchronize()
+        ktimes = _ops.KERNEL_TIMER.summary()
+        _ops.KERNEL_TIMER.disable()
     if rank == 0:
         tokens = wl.tokens * world
-        hip_ms = sum(v["total_ms"] for v in ktimes.values()) / max(min(a.steps, 5), 1)
         line = {
             "metric": "attn fwd+bwd tokens/s per GPU at N=784, d=64; 1/2/4/8-GPU DDP scaling",
             "value": tokens * a.steps / eager_el, "unit": "tokens/s", "n_gpus": world, "steps": a.steps,
             "warmup": a.warmup, "ms_per_step": eager_el / a.steps * 1e3, "eager_ms_per_step": eager_el / a.steps * 1e3,
-            "graph_ms_per_step": graph_ms, "higher_is_better": True, "scaling": "weak", "vs_baseline": None,
+            "higher_is_better": True, "scaling": "weak", "vs_baseline": None,
             "dtype": "bf16", "data": "synthetic",
             "config": {"workload": "%s: %s; whole-model training step (fwd + loss + bwd + SGD momentum), eager, bf16 "
                                    "autocast%s" % (a.workload, wl.desc, ", DistributedDataParallel" if ddp else ""),
                        "tokens_per_step_per_gpu": wl.tokens, "parallelism": "dp%d" % world, "hipgraph": False,
                        "ddp_schedule": ddp_info,
                        "params_M": round(sum(p.numel() for p in wl.model.parameters()) / 1e6, 2)},
-            "attention_core_ms_per_step": round(hip_ms, 4),
-            "attention_kernels_avg_us": {k: round(v["avg_ms"] * 1e3, 2) for k, v in ktimes.items()},
             "roofline": None, "cpu_baseline": None,
         }
+        if a.full:
+            line.update({
+                "graph_ms_per_step": graph_ms,
+                "attention_core_ms_per_step": round(sum(v["total_ms"] for v in ktimes.values()) / max(min(a.steps, 5), 1), 4),
+                "attention_kernels_avg_us": {k: round(v["avg_ms"] * 1e3, 2) for k, v in ktimes.items()},
+            })
     if ddp:
         dist.destroy_process_group()
     if rank == 0:

@@ -5,7 +5,7 @@ export TMPDIR=/tmp
 R=$PWD
 A=$1; shift
 cd /tmp
-rocprofv3 --kernel-trace --output-format csv -d /tmp/prof -o tb -- python $R/bench.py --attn $A "$@" --no-graph --no-cpu-baseline --no-gemm-tune --steps 2 --warmup 1 > /tmp/log.txt 2>&1
+rocprofv3 --kernel-trace --output-format csv -d $TMPDIR/prof -o tb -- python $R/bench.py --full --attn $A "$@" --no-graph --no-cpu-baseline --no-gemm-tune --steps 2 --warmup 1 > $TMPDIR/log.txt 2>&1
 python - <<PY
 import csv,glob
 f=glob.glob("/tmp/prof/**/tb_kernel_trace.csv",recursive=True)
