@@ -19,6 +19,7 @@ int window_bwd_dispatch(const WinP& p, const ea_geom& geom, const T4& outp, cons
 #include "ea_scatter.h"
 #include "ea_rows_mlp.h"
 #include "ea_performer_f32.h"
+#include "ea_kernelized.h"
 #include "ea_f32_attn.h"
 namespace ea {
 int rows_mlp_dispatch(const RowsP& p, int D, int sides, int layer_norm, bool bwd, hipStream_t st);
@@ -78,7 +79,7 @@ static Geo mk_geo(const ea_geom* g) {
 extern "C" {
 
 const char* ea_version(void) { return "ea_hip 0.1.0 gfx950"; }
-int32_t ea_abi_version(void) { return 15; }
+int32_t ea_abi_version(void) { return 16; }
 
 int32_t ea_window_bias_ld(const ea_geom* g) {
   WinTiling t;
@@ -1304,6 +1305,93 @@ int ea_performer_f32_bwd_k(const ea_perf_geom* g, const ea_t4* k, const ea_t4* v
   p.k = pf_mk(k); p.v = pf_mk(v); p.mask = mask; p.W = W; p.p_max = const_cast<float*>(p_max); p.dkv = dkv; p.dksum = dksum;
   p.dk = pf_mk(dk); p.dv = pf_mk(dv);
   return pf32_dispatch(4, p, (hipStream_t)stream);
+}
+
+}  // extern "C"
+
+// ---- kernelized attention, every feature map (ea_kernelized.hip) ----
+static int kz_fill(const ea_kz_geom* g, KzP& p) {
+  if (!g || g->B <= 0 || g->H <= 0 || g->N <= 0 || g->dtype < 0 || g->dtype > EA_F32 || g->map < EA_KZ_FAVORP ||
+      g->map > EA_KZ_DPFP || (g->cos != 0 && g->cos != 1)) return EA_E_BADARG;
+  const bool w = g->map <= EA_KZ_FOURIER;
+  if (g->D != 64 || (w && (g->M <= 0 || g->M > 128 || (g->M & 15))) || (g->map == EA_KZ_DPFP && g->nu < 1))
+    return EA_E_UNSUPPORTED;
+  const int Fb = g->map == EA_KZ_FOURIER ? 2 * g->M : w ? g->M : g->map == EA_KZ_DPFP ? 128 * g->nu : 64;
+  if (g->F != Fb * (g->cos ? 2 : 1) || g->F > 256) return EA_E_UNSUPPORTED;
+  p.B = g->B; p.H = g->H; p.N = g->N; p.M = w ? g->M : 16; p.F = g->F; p.Fb = Fb; p.nu = g->nu; p.cos = g->cos;
+  p.map = g->map; p.dtype = g->dtype;
+  return EA_OK;
+}
+static bool kz_w_ok(const ea_kz_geom* g, const float* W) { return g->map > EA_KZ_FOURIER || W != nullptr; }
+static bool kz_st_ok(const ea_kz_geom* g, const float* p_st) {
+  return (g->map != EA_KZ_FAVORP && g->map != EA_KZ_FOURIER) || p_st != nullptr;
+}
+
+extern "C" {
+
+int32_t ea_kernelized_parts(const ea_kz_geom* g) {
+  KzP p = {};
+  const int rc = kz_fill(g, p);
+  return rc != EA_OK ? rc : kz_slices(g->B * g->H, g->N);
+}
+
+int ea_kernelized_stats(const ea_kz_geom* g, const ea_t4* q, const ea_t4* k, const float* W, float* p_st, void* stream) {
+  KzP p = {};
+  const int rc = kz_fill(g, p);
+  if (rc != EA_OK) return rc;
+  if (g->map != EA_KZ_FAVORP && g->map != EA_KZ_FOURIER) return EA_E_BADARG;
+  if (!pf_t4_ok(k, g->dtype) || (g->map == EA_KZ_FOURIER && !pf_t4_ok(q, g->dtype)) || !kz_w_ok(g, W) || !p_st)
+    return EA_E_BADARG;
+  p.q = pf_mk(q); p.k = pf_mk(k); p.W = W; p.p_st = p_st;
+  return kz_dispatch(0, p, (hipStream_t)stream);
+}
+
+int ea_kernelized_kv(const ea_kz_geom* g, const ea_t4* k, const ea_t4* v, const uint8_t* mask, const float* W,
+                     const float* p_st, float* p_kv, float* p_ksum, void* stream) {
+  KzP p = {};
+  const int rc = kz_fill(g, p);
+  if (rc != EA_OK) return rc;
+  if (!pf_t4_ok(k, g->dtype) || !pf_t4_ok(v, g->dtype) || !kz_w_ok(g, W) || !kz_st_ok(g, p_st) || !p_kv || !p_ksum)
+    return EA_E_BADARG;
+  p.k = pf_mk(k); p.v = pf_mk(v); p.mask = mask; p.W = W; p.p_st = const_cast<float*>(p_st); p.p_kv = p_kv; p.p_ks = p_ksum;
+  return kz_dispatch(1, p, (hipStream_t)stream);
+}
+
+int ea_kernelized_out(const ea_kz_geom* g, const ea_t4* q, const float* W, const float* p_st, const float* kv,
+                      const float* ksum, const ea_t4* out, void* stream) {
+  KzP p = {};
+  const int rc = kz_fill(g, p);
+  if (rc != EA_OK) return rc;
+  if (!pf_t4_ok(q, g->dtype) || !pf_t4_ok(out, g->dtype) || !kz_w_ok(g, W) || !kz_st_ok(g, p_st) || !kv || !ksum)
+    return EA_E_BADARG;
+  p.q = pf_mk(q); p.o = pf_mk(out); p.W = W; p.p_st = const_cast<float*>(p_st); p.kv = kv; p.ksum = ksum;
+  return kz_dispatch(2, p, (hipStream_t)stream);
+}
+
+int ea_kernelized_bwd_q(const ea_kz_geom* g, const ea_t4* q, const ea_t4* dout, const float* W, const float* p_st,
+                        const float* kv, const float* ksum, const ea_t4* dq, float* p_dkv, float* p_dksum, float* p_dw,
+                        void* stream) {
+  KzP p = {};
+  const int rc = kz_fill(g, p);
+  if (rc != EA_OK) return rc;
+  if (!pf_t4_ok(q, g->dtype) || !pf_t4_ok(dout, g->dtype) || !pf_t4_ok(dq, g->dtype) || !kz_w_ok(g, W) || !kz_st_ok(g, p_st) ||
+      !kv || !ksum || !p_dkv || !p_dksum || (p_dw && g->map > EA_KZ_FOURIER)) return EA_E_BADARG;
+  p.q = pf_mk(q); p.dout = pf_mk(dout); p.dq = pf_mk(dq); p.W = W; p.p_st = const_cast<float*>(p_st); p.kv = kv; p.ksum = ksum;
+  p.p_kv = p_dkv; p.p_ks = p_dksum; p.p_dw = p_dw;
+  return kz_dispatch(3, p, (hipStream_t)stream);
+}
+
+int ea_kernelized_bwd_k(const ea_kz_geom* g, const ea_t4* k, const ea_t4* v, const uint8_t* mask, const float* W,
+                        const float* p_st, const float* dkv, const float* dksum, const ea_t4* dk, const ea_t4* dv,
+                        float* p_dw, void* stream) {
+  KzP p = {};
+  const int rc = kz_fill(g, p);
+  if (rc != EA_OK) return rc;
+  if (!pf_t4_ok(k, g->dtype) || !pf_t4_ok(v, g->dtype) || !pf_t4_ok(dk, g->dtype) || !pf_t4_ok(dv, g->dtype) ||
+      !kz_w_ok(g, W) || !kz_st_ok(g, p_st) || !dkv || !dksum || (p_dw && g->map > EA_KZ_FOURIER)) return EA_E_BADARG;
+  p.k = pf_mk(k); p.v = pf_mk(v); p.mask = mask; p.W = W; p.p_st = const_cast<float*>(p_st); p.dkv = dkv; p.dksum = dksum;
+  p.dk = pf_mk(dk); p.dv = pf_mk(dv); p.p_dw = p_dw;
+  return kz_dispatch(4, p, (hipStream_t)stream);
 }
 
 }  // extern "C"

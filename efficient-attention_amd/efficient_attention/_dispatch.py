@@ -12,11 +12,14 @@ implementation (no fallback).  The autograd Functions of _ops.py are thin shells
     ea::eva_fwd / eva_bwd                eva.py:145-227 (and causal_eva.py:666-788)
     ea::lara_fwd / lara_bwd              lara.py:129-175,187-246 (2-D pooled proposals)
     ea::performer_fwd / performer_bwd    kernelized_attention.py:20-56,116-121
+    ea::kernelized_fwd / kernelized_bwd  kernelized_attention.py:13-123,326-346 (every feature map, cos weighting,
+                                         learnable W; _kernelized.py)
     ea::linear / linear_w32              abstract_attention.py:72-78,86-87 (qkv / output projection, streaming kernel;
                                          _w32: straight from the fp32 master weight)
 """
 import torch
 
+from . import _kernelized
 from . import _ops
 
 _LIB = torch.library.Library("ea", "DEF")
@@ -30,6 +33,9 @@ _SCHEMAS = {
     "performer_fwd": "(Tensor qkv, Tensor? mask, Tensor W) -> Tensor[]",
     "performer_bwd": "(Tensor dout, Tensor qkv, Tensor? mask, Tensor W, Tensor stab, Tensor kv, Tensor ksum, "
                      "Tensor out) -> Tensor",
+    "kernelized_fwd": "(Tensor qkv, Tensor? mask, Tensor? W, int[] cfg) -> Tensor[]",
+    "kernelized_bwd": "(Tensor dout, Tensor qkv, Tensor? mask, Tensor? W, Tensor p_st, Tensor kv, Tensor ksum, int[] cfg, "
+                      "bool need_dw) -> Tensor[]",
     "lara_fwd": "(Tensor qkv, Tensor? mask, Tensor? noise, int[] icfg, float[] fcfg, Tensor[] params) -> Tensor[]",
     "lara_bwd": "(Tensor dout, Tensor qkv, Tensor? mask, Tensor? noise, Tensor[] saved, int[] icfg, float[] fcfg, Tensor[] params) "
                 "-> Tensor[]",
@@ -44,6 +50,7 @@ _IMPLS = {
     "softmax_fwd": _ops.softmax_fwd_impl, "softmax_bwd": _ops.softmax_bwd_impl,
     "local_fwd": _ops.local_fwd_impl, "local_bwd": _ops.local_bwd_impl,
     "performer_fwd": _ops.performer_fwd_impl, "performer_bwd": _ops.performer_bwd_impl,
+    "kernelized_fwd": _kernelized.kernelized_fwd_impl, "kernelized_bwd": _kernelized.kernelized_bwd_impl,
     "lara_fwd": _ops.lara_fwd_impl, "lara_bwd": _ops.lara_bwd_impl,
     "eva_fwd": _ops.eva_fwd_impl, "eva_bwd": _ops.eva_bwd_impl,
     "linear": _ops.linear_impl, "linear_w32": _ops.linear_w32_impl,
@@ -115,6 +122,22 @@ def _(qkv, mask, W):
 @torch.library.register_fake("ea::performer_bwd")
 def _(dout, qkv, mask, W, stab, kv, ksum, out):
     return torch.empty_like(qkv)
+
+
+@torch.library.register_fake("ea::kernelized_fwd")
+def _(qkv, mask, W, cfg):
+    B, N, _, h, d = qkv.shape
+    cfg = tuple(int(c) for c in cfg)
+    F = _kernelized._features(cfg)
+    S = _kernelized._parts(_kernelized._geom(qkv, cfg))           # (host-side size query: works on fake tensors)
+    p_st = _f32(qkv, B * h, S, 2) if cfg[0] in _kernelized.STAT_MAPS else _none(qkv)
+    return [qkv.new_empty((B, N, h, d)), p_st, _f32(qkv, B * h, F, d), _f32(qkv, B * h, F)]
+
+
+@torch.library.register_fake("ea::kernelized_bwd")
+def _(dout, qkv, mask, W, p_st, kv, ksum, cfg, need_dw):
+    dW = _f32(qkv, *W.shape) if (need_dw and W is not None) else _none(qkv)
+    return [torch.empty_like(qkv), dW]
 
 
 @torch.library.register_fake("ea::lara_fwd")

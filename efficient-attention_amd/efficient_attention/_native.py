@@ -22,7 +22,7 @@ class ea_t4(ctypes.Structure):
                 ("sn", ctypes.c_int64)]
 
 
-ABI_VERSION = 15         # ea_abi_version() of include/ea_hip.h this file mirrors
+ABI_VERSION = 16         # ea_abi_version() of include/ea_hip.h this file mirrors
 
 
 class ea_geom(ctypes.Structure):
@@ -36,6 +36,12 @@ class ea_geom(ctypes.Structure):
 class ea_perf_geom(ctypes.Structure):
     _fields_ = [("B", ctypes.c_int32), ("H", ctypes.c_int32), ("N", ctypes.c_int32),
                 ("D", ctypes.c_int32), ("dtype", ctypes.c_int32), ("M", ctypes.c_int32)]
+
+
+class ea_kz_geom(ctypes.Structure):
+    _fields_ = [("B", ctypes.c_int32), ("H", ctypes.c_int32), ("N", ctypes.c_int32), ("D", ctypes.c_int32),
+                ("dtype", ctypes.c_int32), ("map", ctypes.c_int32), ("M", ctypes.c_int32), ("F", ctypes.c_int32),
+                ("nu", ctypes.c_int32), ("cos", ctypes.c_int32)]
 
 
 class ea_sb_geom(ctypes.Structure):
@@ -85,6 +91,7 @@ _F = ctypes.c_float
 _G = ctypes.POINTER(ea_geom)
 _LG = ctypes.POINTER(ea_lara_geom)
 _PG = ctypes.POINTER(ea_perf_geom)
+_KG = ctypes.POINTER(ea_kz_geom)
 _MG = ctypes.POINTER(ea_lmk_geom)
 _T = ctypes.POINTER(ea_t4)
 _SG = ctypes.POINTER(ea_sb_geom)
@@ -200,6 +207,12 @@ SIGNATURES = {
     "ea_performer_f32_out": [_PG, _T, _P, _P, _P, _T, _P],
     "ea_performer_f32_bwd_q": [_PG, _T, _T, _P, _P, _P, _T, _P, _P, _P],
     "ea_performer_f32_bwd_k": [_PG, _T, _T, _P, _P, _P, _P, _P, _T, _T, _P],
+    "ea_kernelized_parts": [_KG],
+    "ea_kernelized_stats": [_KG, _T, _T, _P, _P, _P],
+    "ea_kernelized_kv": [_KG, _T, _T, _P, _P, _P, _P, _P, _P],
+    "ea_kernelized_out": [_KG, _T, _P, _P, _P, _P, _T, _P],
+    "ea_kernelized_bwd_q": [_KG, _T, _T, _P, _P, _P, _P, _T, _P, _P, _P, _P],
+    "ea_kernelized_bwd_k": [_KG, _T, _T, _P, _P, _P, _P, _P, _T, _T, _P, _P],
     "ea_softmax_attn_fwd": [_I, _I, _I, _I, _I, _F, _T, _T, _T, _P, _T, _P, _P, _F, _I, _P],
     "ea_softmax_sample": [_I, _I, _I, _I, _I, _F, _T, _T, _P, _P, _P],
     "ea_softmax_attn_bwd": [_I, _I, _I, _I, _I, _F, _T, _T, _T, _P, _T, _T, _P, _P, _T, _T, _T, _P, _F, _I, _P],

@@ -92,6 +92,11 @@ KERNEL_ALGO_UNITS = {
     "ea_performer_f32_out": 2,    # read q; write out
     "ea_performer_f32_bwd_q": 3,  # read q,dout; write dq
     "ea_performer_f32_bwd_k": 4,  # read k,v; write dk,dv
+    "ea_kernelized_stats": 1,     # read k (fourier: q,k -- counted as one: favorp, the common case, reads k only)
+    "ea_kernelized_kv": 2,        # read k,v
+    "ea_kernelized_out": 2,       # read q; write out
+    "ea_kernelized_bwd_q": 3,     # read q,dout; write dq
+    "ea_kernelized_bwd_k": 4,     # read k,v; write dk,dv
     "ea_lara_stats_fwd": 3,       # read q,k,v
     "ea_lara_out_fwd": 2,         # read q; write out
     "ea_lara_bwd_q": 3,           # read q,dout; write dq

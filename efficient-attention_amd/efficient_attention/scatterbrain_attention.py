@@ -33,6 +33,7 @@ from .local_attention import LocalAttention
 
 class ScatterBrain(KernelizedAttention, LocalAttention):
     _F32_CORE = False           # (no fp32-operand kernels for this variant yet: fp32 input is rounded to bf16 with a warning)
+    _FEATURE_MAPS = False       # its feature half is built for favorp only: other proj_method / cos / learnable W are refused
     def __init__(self, *args, **kwargs):
         super().__init__(*args, **kwargs)
         self._slot_cache = {}

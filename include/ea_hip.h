@@ -363,6 +363,56 @@ int ea_performer_f32_bwd_k(const ea_perf_geom* g, const ea_t4* k, const ea_t4* v
                            const float* p_max, const float* dkv, const float* dksum, const ea_t4* dk, const ea_t4* dv,
                            void* stream);
 
+/* ---- Kernelized attention: the reference's feature maps in EXACT fp32 arithmetic (ABI 16; ea_kernelized.hip) ---------
+ * KernelizedAttention (kernelized_attention.py) with proj_method = favorp / relu / fourier / relu-only / sigmoid-only / dpfp,
+ * optionally cos weighting (cosFormer): out_n = phi(q_n) kv / max(phi(q_n).ksum, 1e-2), kv = sum_n phi(k_n)^T v_n,
+ * ksum = sum_n phi(k_n), phi(k) = 0 at padded keys.  c = d^-1/4, c2 = d^-1/2 / 2, r = M^-1/2, W fp32 [H, M, 64]:
+ *   EA_KZ_FAVORP        r exp(c W x - c2|x|^2 - stab) + 1e-4   (stab: row max for queries, max over (tokens, j) for keys)
+ *   EA_KZ_RELU          relu(r c W x) + 1e-3
+ *   EA_KZ_FOURIER       r [sin(c W x), cos(c W x)] exp(c2|x|^2 - max_n c2|x_n|^2)   (max per side over the sequence)
+ *   EA_KZ_RELU_ONLY     relu(x) + 0.1;   EA_KZ_SIGMOID_ONLY  sigmoid(x) + 0.1   (no W)
+ *   EA_KZ_DPFP          x' = [relu(x), relu(-x)];  concat_{j=1..nu} x' * roll(x', j)   (no W)
+ * Stabilisers are detached.  cos = 1 doubles the features to [phi cos t_n, phi sin t_n], t_n = (pi/2) n / N.
+ * Geometry: D = 64; M <= 128, multiple of 16 (maps with W); F = features after cos weighting <= 256 (M, 2M, 64 or 128 nu,
+ * times 2 with cos).  q, k, v, dout of type dtype = EA_BF16 / EA_F16 / EA_F32, fp32 features and products, outputs in dtype.
+ *   S = ea_kernelized_parts(g) sequence slices per (b,h);
+ *   stats (favorp, fourier only): p_st [BH,S,2] = slice maxima (favorp: of the key logits c W_j.k_n, side 0; fourier: of
+ *          c2|k_n|^2, side 0, and c2|q_n|^2, side 1; padded tokens included, as in the reference);
+ *   kv   : p_kv [BH,S,F,64], p_ksum [BH,S,F] partials (added by ea_slice_sum -> kv [BH,F,64], ksum [BH,F]);
+ *   out  : out from the summed kv, ksum;
+ *   bwd_q: dq and the partials of d kv, d ksum (shapes of p_kv, p_ksum);  bwd_k: dk, dv from the summed d kv, d ksum;
+ *   p_dw : NULL, or (learnable W) [H, B, 2, S, M, 64] partials of dW, side 0 written by bwd_q, side 1 by bwd_k -- the
+ *          caller adds the B * 2 * S partials of each head (ea_slice_sum).
+ * p_st is NULL for the maps without statistics.  Replaces the feature maps, (cos_reweighted_)linear_attention and their
+ * autograd (kernelized_attention.py:13-123,326-346). */
+#define EA_KZ_FAVORP        0
+#define EA_KZ_RELU          1
+#define EA_KZ_FOURIER       2
+#define EA_KZ_RELU_ONLY     3
+#define EA_KZ_SIGMOID_ONLY  4
+#define EA_KZ_DPFP          5
+typedef struct {
+  int32_t B, H, N, D;
+  int32_t dtype;             /* EA_BF16 | EA_F16 | EA_F32 */
+  int32_t map;               /* EA_KZ_* */
+  int32_t M;                 /* rows of W (approx_attn_dim); ignored by the maps without W */
+  int32_t F;                 /* features after cos weighting */
+  int32_t nu;                /* dpfp: number of rolls, >= 1 */
+  int32_t cos;               /* 1: cos weighting */
+} ea_kz_geom;
+int32_t ea_kernelized_parts(const ea_kz_geom* g);
+int ea_kernelized_stats(const ea_kz_geom* g, const ea_t4* q, const ea_t4* k, const float* W, float* p_st, void* stream);
+int ea_kernelized_kv(const ea_kz_geom* g, const ea_t4* k, const ea_t4* v, const uint8_t* mask, const float* W,
+                     const float* p_st, float* p_kv, float* p_ksum, void* stream);
+int ea_kernelized_out(const ea_kz_geom* g, const ea_t4* q, const float* W, const float* p_st, const float* kv,
+                      const float* ksum, const ea_t4* out, void* stream);
+int ea_kernelized_bwd_q(const ea_kz_geom* g, const ea_t4* q, const ea_t4* dout, const float* W, const float* p_st,
+                        const float* kv, const float* ksum, const ea_t4* dq, float* p_dkv, float* p_dksum, float* p_dw,
+                        void* stream);
+int ea_kernelized_bwd_k(const ea_kz_geom* g, const ea_t4* k, const ea_t4* v, const uint8_t* mask, const float* W,
+                        const float* p_st, const float* dkv, const float* dksum, const ea_t4* dk, const ea_t4* dv,
+                        float* p_dw, void* stream);
+
 /* ---- LARA landmark pipeline, fused (lara.py:145-198,214-238) -----------------------------------
  * One workgroup per (b,h), all matrices in LDS, exact fp32:
  *   q_bar = LN(pq Wq^T + bq), k0 = LN(pk Wk^T + bk)         (has_mlp; else q_bar = pq, k0 = pk)

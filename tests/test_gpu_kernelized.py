@@ -1,0 +1,229 @@
+"""-m gpu: KernelizedAttention's feature maps on the HIP kernels (ea_kernelized.hip).
+
+  * every fixture of tests/golden/cases_kernelized.py, both modes, under bf16 / fp16 autocast (the Performer tolerance
+    class of tests/gpu_checks.py) and with fp32 activations outside autocast (the fp32-core bound 2e-4 / 1e-4);
+  * the same cases with torch's einsum / exp / sin / cos / relu / sigmoid / roll made to raise: nothing falls back;
+  * favorp through the new entry points against the exact-fp32 Performer kernels (ea_performer_f32_*);
+  * full-size layers against the fp64 restatement (tests/kz_contract.py), every parameter gradient including dW;
+  * torch.library.opcheck of ea::kernelized_fwd / _bwd;  a captured fwd + bwd + SGD step replays like the eager one."""
+import copy
+
+import numpy as np
+import pytest
+import torch
+
+import cases_kernelized
+from gpu_checks import MODULE_TOL, FP16_TOL, ELEM_TOL, ELEM_TOL_VARIANT, CASE_TOL
+from kz_checks import check_module_case
+from util import scaled_err
+
+NAMES = sorted(cases_kernelized.CASES)
+CLAMP = "kz_fourier_2d_clamp"
+F32_TOL = (2e-4, 1e-4)
+# Maps with a KINK -- relu, relu-only, dpfp: the derivative of relu jumps at 0.  Under autocast the qkv projection runs on
+# 16-bit operands, so a q / k entry (or a logit) within its rounding of 0 lands on the other side of the kink than in the fp32
+# reference and its whole gradient contribution differs (the phenomenon of the Performer clamp fixture, tests/gpu_checks.py).
+# y is unaffected (0.6 % bf16, 0.07 % fp16 observed); the gradients are bounded norm-wise at ~1.5x the worst observed on MI355X
+# (bf16 0.17 / 0.040, fp16 0.067 / 0.012) and have no element-wise bound.  In fp32 they hold the fp32-core bound.
+KINKED = ("relu", "relu-only", "dpfp")
+KINK_TOL = {torch.bfloat16: (2.5e-1, 6e-2), torch.float16: (1e-1, 2e-2)}
+# The fourier clamp fixture: 44 % of the queries under the clamp, and fourier normalisers can sit anywhere near it.  In fp16
+# its gradients keep a bound of their own (observed 0.025 / 0.012); in bf16 only y is checked (observed 0.064 / 0.030): the
+# 8-bit qkv moves so many normalisers across 1e-2 (0.54 / 0.19 observed on dx) that a gradient bound there would bound
+# nothing.  Its gradients are pinned by the fp16 and the fp32 runs.
+CLAMP_TOL = {torch.bfloat16: (1e-1, 5e-2), torch.float16: (5e-2, 2.5e-2)}
+
+
+def _tols(name, dtype):
+    """(norm-wise, element-wise) bounds under autocast: the Performer class of tests/gpu_checks.py for the smooth maps."""
+    if name == CLAMP:
+        return CLAMP_TOL[dtype], None
+    if cases_kernelized.CASES[name]["args"]["proj_method"] in KINKED:
+        return KINK_TOL[dtype], None
+    if dtype == torch.float16:
+        return FP16_TOL, ELEM_TOL["fp16"]
+    return MODULE_TOL, ELEM_TOL_VARIANT[("performer", "bf16")]
+
+
+def _check(name, mode, dtype):
+    tol, etol = _tols(name, dtype)
+    return check_module_case(name, mode, dtype, tol, etol, backward=not (name == CLAMP and dtype == torch.bfloat16))
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("dtype", [torch.bfloat16, torch.float16], ids=["bf16", "fp16"])
+@pytest.mark.parametrize("mode", cases_kernelized.MODES)
+@pytest.mark.parametrize("name", NAMES)
+def test_fixture_autocast(name, mode, dtype):
+    errs = _check(name, mode, dtype)
+    print(name, mode, {k: "%.2e/%.2e" % v for k, v in errs.items()})
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("mode", cases_kernelized.MODES)
+@pytest.mark.parametrize("name", NAMES)
+def test_fixture_fp32(name, mode):
+    errs = check_module_case(name, mode, torch.float32, F32_TOL)
+    print(name, mode, {k: "%.2e/%.2e" % v for k, v in errs.items()})
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("mode", cases_kernelized.MODES)
+@pytest.mark.parametrize("name", NAMES)
+def test_feature_maps_stay_on_hip(name, mode, monkeypatch):
+    """Features, linear attention and their gradients run in the HIP kernels: no torch einsum / exp / sin / cos / relu /
+    sigmoid / roll may be reached."""
+    import torch.nn.functional as F
+
+    def banned(*a, **k):
+        raise AssertionError("a torch feature-map op was reached in the kernelized attention path")
+    for mod, fn in ((torch, "einsum"), (torch, "exp"), (torch, "sin"), (torch, "cos"), (torch, "relu"), (torch, "sigmoid"),
+                    (torch, "roll"), (F, "relu"), (F, "sigmoid")):
+        monkeypatch.setattr(mod, fn, banned)
+    _check(name, mode, torch.bfloat16)
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("dtype", [torch.bfloat16, torch.float32])
+@pytest.mark.parametrize("m,mask", [(64, False), (96, True), (32, True)])
+def test_favorp_entry_points_match_the_performer_kernels(m, mask, dtype):
+    """map id favorp without cos through ea_kernelized_* == ea_performer_f32_* (the generalised skeleton against the one it
+    generalises), forward and backward, to 1e-5 relative."""
+    from efficient_attention import _kernelized, _ops
+    torch.manual_seed(0)
+    B, N, h, d = 2, 300, 3, 64
+    qkv5 = (0.5 * torch.randn(B, N, 3, h, d, device="cuda")).to(dtype)
+    W = torch.randn(h, m, d, device="cuda")
+    mk = None
+    if mask:
+        mk = torch.zeros(B, N, dtype=torch.uint8, device="cuda")
+        mk[1, N - 37:] = 1
+    cfg = (0, m, 0, 0)
+    out, p_st, kv, ksum = _kernelized.kernelized_fwd_impl(qkv5, mk, W, cfg)
+    ref, p_max, kv_r, ksum_r = _ops.performer_f32_fwd(qkv5, mk, W)
+    dout = torch.randn_like(out)
+    dqkv, dW = _kernelized.kernelized_bwd_impl(dout, qkv5, mk, W, p_st, kv, ksum, cfg, False)
+    dref = _ops.performer_f32_bwd(dout, qkv5, mk, W, p_max, kv_r, ksum_r)
+    rtol = 1e-5 if dtype == torch.float32 else 8e-3          # (16-bit outputs: one rounding of the same fp32 value)
+    for got, want, what in ((out, ref, "out"), (kv, kv_r, "kv"), (ksum, ksum_r, "ksum"), (dqkv, dref, "dqkv")):
+        err = (got.double() - want.double()).abs().max().item() / max(want.double().abs().max().item(), 1e-30)
+        assert err <= rtol, (what, err)
+
+
+def _fullsize(proj_method, x_shape, heads, m, cos, scheme, mode):
+    import efficient_attention as ea
+    import kz_contract
+    torch.manual_seed(1)
+    C = x_shape[-1]
+    mod = ea.KernelizedAttention(dim=C, num_heads=heads, approx_attn_dim=m, proj_method=proj_method, cos_weighting=cos,
+                                 sample_scheme=scheme).cuda()
+    with torch.no_grad():
+        mod.qkv.weight.normal_(0.0, C ** -0.5)
+        mod.qkv.bias.normal_(0.0, 0.1)
+        mod.proj.weight.normal_(0.0, C ** -0.5)
+    mod.train(mode == "train")
+    x = (0.5 * torch.randn(x_shape, device="cuda")).requires_grad_(True)
+    g = torch.randn(x_shape, device="cuda")
+    mask = None
+    if len(x_shape) == 3:
+        mask = torch.zeros(x_shape[0], x_shape[1], dtype=torch.bool, device="cuda")
+        mask[-1, x_shape[1] - 300:] = True
+    y = mod(x, mask) if mask is not None else mod(x)
+    (y * g).sum().backward()
+    params = {k: v.detach().double().requires_grad_(True) for k, v in mod.state_dict().items()}
+    W = params.get("random_proj", params.get("eval_proj"))
+    xd = x.detach().double().requires_grad_(True)
+    yd = kz_contract.module_forward(xd, params, heads, proj_method, m, cos, W, mask)
+    (yd * g.double()).sum().backward()
+    errs = {"y": scaled_err(y.detach().double().cpu().numpy(), yd.detach().cpu().numpy()),
+            "dx": scaled_err(x.grad.double().cpu().numpy(), xd.grad.cpu().numpy())}
+    for k, p in mod.named_parameters():
+        errs["d" + k] = scaled_err(p.grad.double().cpu().numpy(), params[k].grad.cpu().numpy())
+    return errs
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("proj_method,x_shape,heads,m,cos,scheme,mode", [
+    ("relu", (32, 28, 28, 192), 3, 64, True, "fixed", "eval"),
+    ("fourier", (32, 28, 28, 192), 3, 64, False, "default", "eval"),          # F = 128
+    ("fourier", (32, 28, 28, 192), 3, 128, False, "learnable", "train"),      # F = 256
+    ("fourier", (4, 4096, 512), 8, 64, True, "default", "eval"),              # F = 256, many slices per (b,h)
+    ("relu", (4, 4096, 512), 8, 64, False, "learnable", "train"),
+], ids=["relu_cos_784", "fourier128_784", "fourier256_learn_784", "fourier_cos_4096", "relu_learn_4096"])
+def test_fullsize_against_fp64(proj_method, x_shape, heads, m, cos, scheme, mode):
+    """fp32 activations (no autocast): the layer against the fp64 restatement of the contract."""
+    errs = _fullsize(proj_method, x_shape, heads, m, cos, scheme, mode)
+    print({k: "%.2e/%.2e" % v for k, v in errs.items()})
+    # relu's kink: among the 8 M logits of the 4096-token layer a few lie within fp32 rounding of 0 and take the other branch
+    # than in fp64 (observed dx 1.2e-2 max / 1.6e-4 rms, y 1.6e-6): max-norm bound 5e-2 there, the rms bound of every map
+    tol = (5e-2, 4e-4) if proj_method == "relu" else (1e-3, 2e-4)
+    bad = {k: v for k, v in errs.items() if not (v[0] <= tol[0] and v[1] <= tol[1])}
+    assert not bad, (bad, errs)
+    if scheme == "learnable":
+        assert "drandom_proj" in errs
+
+
+@pytest.mark.gpu
+def test_opcheck_kernelized_ops():
+    import efficient_attention  # noqa: F401
+    torch.manual_seed(0)
+    B, N, h, d = 2, 100, 2, 64
+    qkv = (0.5 * torch.randn(B, N, 3, h, d, device="cuda")).to(torch.bfloat16)
+    mask = torch.zeros(B, N, dtype=torch.uint8, device="cuda")
+    mask[1, 80:] = 1
+    checks = ("test_schema", "test_faketensor")
+    for cfg, W in (([2, 64, 0, 1], torch.randn(h, 64, d, device="cuda")), ([5, 0, 1, 0], None), ([1, 32, 0, 0],
+                                                                                                   torch.randn(h, 32, d, device="cuda"))):
+        torch.library.opcheck(torch.ops.ea.kernelized_fwd.default, (qkv, mask, W, cfg), test_utils=checks)
+        out, p_st, kv, ksum = torch.ops.ea.kernelized_fwd(qkv, mask, W, cfg)
+        dout = torch.randn_like(out)
+        torch.library.opcheck(torch.ops.ea.kernelized_bwd.default, (dout, qkv, mask, W, p_st, kv, ksum, cfg, W is not None),
+                              test_utils=checks)
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("proj_method,cos", [("relu", True), ("fourier", False), ("dpfp", False)])
+def test_captured_step_equals_eager(proj_method, cos):
+    """fwd + bwd + SGD step captured with torch.cuda.graph and replayed == the same step run eagerly (learnable W for the
+    maps with one: its update is part of the captured step)."""
+    import efficient_attention as ea
+    torch.manual_seed(0)
+    m = 128 if proj_method == "dpfp" else 64
+    mod = ea.KernelizedAttention(dim=128, num_heads=2, approx_attn_dim=m, proj_method=proj_method, cos_weighting=cos,
+                                 sample_scheme="learnable").cuda().train()
+    ref = copy.deepcopy(mod)
+    x = torch.randn(2, 14, 14, 128, device="cuda")
+    g = torch.randn_like(x)
+
+    def step(module, opt, xin):
+        opt.zero_grad(set_to_none=False)
+        with torch.autocast("cuda", dtype=torch.bfloat16):
+            y = module(xin)
+        (y.float() * g).sum().backward()
+        opt.step()
+
+    opt = torch.optim.SGD(mod.parameters(), lr=0.1)
+    opt_ref = torch.optim.SGD(ref.parameters(), lr=0.1)
+    for p in mod.parameters():
+        p.grad = torch.zeros_like(p)
+    static_x = x.clone()
+    snapshot = {k: v.clone() for k, v in mod.state_dict().items()}
+    s = torch.cuda.Stream()
+    s.wait_stream(torch.cuda.current_stream())
+    with torch.cuda.stream(s):
+        step(mod, opt, static_x)                       # warm-up (library handles, workspace sizes)
+    torch.cuda.current_stream().wait_stream(s)
+    graph = torch.cuda.CUDAGraph()
+    with torch.cuda.graph(graph):
+        step(mod, opt, static_x)
+    with torch.no_grad():                              # back to the initial state, then one replay
+        for k, v in mod.state_dict().items():
+            v.copy_(snapshot[k])
+    graph.replay()
+    torch.cuda.synchronize()
+    for p in ref.parameters():
+        p.grad = torch.zeros_like(p)
+    step(ref, opt_ref, x)
+    torch.cuda.synchronize()
+    for (k, a), (_, b) in zip(mod.state_dict().items(), ref.state_dict().items()):
+        assert torch.allclose(a, b, rtol=1e-5, atol=1e-7), (k, (a - b).abs().max().item())
