@@ -79,7 +79,7 @@ static Geo mk_geo(const ea_geom* g) {
 extern "C" {
 
 const char* ea_version(void) { return "ea_hip 0.1.0 gfx950"; }
-int32_t ea_abi_version(void) { return 16; }
+int32_t ea_abi_version(void) { return 17; }
 
 int32_t ea_window_bias_ld(const ea_geom* g) {
   WinTiling t;
@@ -2093,6 +2093,64 @@ int ea_layernorm_bwd(int32_t xtype, int32_t rows, int32_t C, const void* x, cons
   ea::LnP p = {};
   p.x = x; p.gamma = gamma; p.stats = const_cast<float*>(stats); p.dy = dy; p.dx = dx; p.part = part; p.rows = rows; p.C = C;
   return ea::layernorm_dispatch(true, p, xtype, (hipStream_t)stream);
+}
+
+}  // extern "C"
+
+// ---- causal EVA, incremental decoding (ea_ceva_decode.hip) ----
+#include "ea_ceva_decode.h"
+static bool dec_t4_ok(const ea_t4* t, int D, int esz) {
+  const int a = 16 / esz;                                 // 16-byte aligned rows
+  return t && t->ptr && ((uintptr_t)t->ptr % 16 == 0) && t->sb % a == 0 && t->sh % a == 0 && t->sn % a == 0 && t->sn >= D;
+}
+static ea::DecT dec_mk(const ea_t4* t) {
+  ea::DecT r;
+  r.p = (const char*)t->ptr; r.sb = t->sb; r.sh = t->sh; r.sn = t->sn;
+  return r;
+}
+static int dec_fill(const ea_ceva_dec_geom* g, const ea_t4* q, const ea_t4* k, const ea_t4* v, const uint8_t* pad,
+                    const ea_t4* lk, const ea_t4* lv, ea::DecP& p) {
+  if (!g || g->B <= 0 || g->H <= 0 || g->window <= 0 || g->chunk <= 0 || g->ext < 0 || g->t0 < 0 || g->T_new <= 0 ||
+      g->cap < g->t0 + g->T_new || (g->dtype != EA_BF16 && g->dtype != EA_F16 && g->dtype != EA_F32)) return EA_E_BADARG;
+  if (g->D != 32 && g->D != 64 && g->D != 128) return EA_E_UNSUPPORTED;
+  const int esz = g->dtype == EA_F32 ? 4 : 2;
+  if (!dec_t4_ok(q, g->D, esz) || !dec_t4_ok(k, g->D, esz) || !dec_t4_ok(v, g->D, esz)) return EA_E_BADARG;
+  if (!dec_t4_ok(lk, g->D, 4) || !dec_t4_ok(lv, g->D, 4) || (g->has_mask && !pad)) return EA_E_BADARG;
+  p.q = dec_mk(q); p.k = dec_mk(k); p.v = dec_mk(v); p.lk = dec_mk(lk); p.lv = dec_mk(lv);
+  p.pad = g->has_mask ? pad : nullptr;
+  p.B = g->B; p.H = g->H; p.D = g->D; p.dtype = g->dtype; p.w = g->window; p.e = g->ext; p.r = g->chunk;
+  p.t0 = g->t0; p.T = g->T_new; p.c_first = g->c_first; p.c_last = g->c_last; p.cap = g->cap; p.adaptive = g->adaptive ? 1 : 0;
+  p.scale = (float)(1.0 / sqrt((double)g->D));
+  return EA_OK;
+}
+
+extern "C" {
+
+int ea_ceva_decode_close(const ea_ceva_dec_geom* g, const ea_t4* q, const ea_t4* k, const ea_t4* v, const uint8_t* pad,
+                         const float* const* mu_params, const ea_t4* rf_k_bar, const ea_t4* beta, void* stream) {
+  ea::DecP p = {};
+  const int rc = dec_fill(g, q, k, v, pad, rf_k_bar, beta, p);
+  if (rc != EA_OK) return rc;
+  // the chunks must be decoded: rows [c_first r, (c_last + 1) r) lie in [0, t0 + T_new)
+  if (!mu_params || g->c_first < 0 || g->c_last < g->c_first || (int64_t)(g->c_last + 1) * g->chunk > g->t0 + g->T_new)
+    return EA_E_BADARG;
+  const int np = g->adaptive ? 8 : 4;
+  for (int i = 0; i < np; ++i) {
+    if (!mu_params[i] || (uintptr_t)mu_params[i] % 16) return EA_E_BADARG;
+    p.mu[i] = mu_params[i];
+  }
+  return ea::ceva_decode_dispatch(true, p, (hipStream_t)stream);
+}
+
+int ea_ceva_decode_attn(const ea_ceva_dec_geom* g, const ea_t4* q, const ea_t4* k, const ea_t4* v, const uint8_t* pad,
+                        const float* bias, const ea_t4* rf_k_bar, const ea_t4* beta, const ea_t4* out, void* stream) {
+  ea::DecP p = {};
+  const int rc = dec_fill(g, q, k, v, pad, rf_k_bar, beta, p);
+  if (rc != EA_OK) return rc;
+  if (!dec_t4_ok(out, g->D, g->dtype == EA_F32 ? 4 : 2) || (g->has_bias && !bias)) return EA_E_BADARG;
+  p.o = dec_mk(out);
+  p.bias = g->has_bias ? bias : nullptr;
+  return ea::ceva_decode_dispatch(false, p, (hipStream_t)stream);
 }
 
 }  // extern "C"

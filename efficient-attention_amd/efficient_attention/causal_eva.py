@@ -15,6 +15,7 @@ there is no CPU fallback.  Quantization noise on the projections (`q_noise > 0`,
 to the parameters in front of the projection kernels exactly as the reference's forward pre-hooks do.  Token-by-token
 decoding with an incremental state (reference :542-665): `_decode`.
 """
+import ctypes
 import math
 import uuid
 
@@ -205,7 +206,7 @@ class CausalEVAttention(_ops.DerivedCacheOwner, nn.Module):
             if N != tgt_len:
                 y = y[:tgt_len]
             return y.contiguous(), None
-        # (the full-sequence path has fp32 cores; decoding does not -- an explicit argument, not module state: forward stays
+        # (fp32 cores, for this path and decoding alike -- an explicit argument, not module state: forward stays
         #  re-entrant)
         if self.self_attention:
             qkv5 = self._project(x, None, None, keep_f32=True)
@@ -328,19 +329,21 @@ class CausalEVAttention(_ops.DerivedCacheOwner, nn.Module):
         extension).  This build therefore defines decoding by PREFIX CONSISTENCY with the pinned full-sequence path: the
         output for token t equals row t of `forward()` on the tokens 0..t (tests/test_gpu_causal_eva.py).  State, all
         batch-first so that `reorder_incremental_state` can index it:
-            qkv       [B, cap, 3, h, d]   projected rows of every token so far (16-bit; the window needs the last w + e,
-                                          a chunk its own rows)
+            qkv       [B, cap, 3, h, d]   projected rows of every token so far (16-bit, or fp32 outside autocast; the
+                                          window needs the last w + e, a chunk its own rows)
             rf_k_bar  [B, h, Lcap, d]     fp32, the landmark keys of the COMPLETED chunks (:588-634)
             beta      [B, h, Lcap, d]     fp32, their control variates
             pos       [B]                 tokens decoded so far
             pad       [B, cap]            uint8, 1 = padded position (`key_padding_mask`, e.g. left-padded prompts of a batch):
                                           handed to the kernels exactly as the full path hands them its mask -- a padded key
                                           is invisible, a padded query sees no local key, a chunk's means skip its padded rows
-        A step projects the new token, closes a chunk when one completes (chunk means -> mu networks -> beta, the same HIP
-        entry points as the full path on the chunk's rows) and runs the window kernel of the training path on the suffix
-        [previous window, current window] against the landmarks of all completed chunks (`ea_geom.lm_base` re-bases the
-        chunk visibility rule of :716-738); rows after the current token are masked.  Past 64 completed chunks (the landmark rows
-        the 16-bit window kernel holds) the same suffix runs on the generic fp32 kernel: no length limit."""
+        A step projects its tokens (fp32 stays fp32 outside autocast when the fp32 cores are usable: the cache dtype is fixed by
+        the first step, a later step of another dtype is cast to it), writes them into the cache, closes every chunk its tokens
+        complete with ONE ea_ceva_decode_close (chunk means -> mu networks -> beta, on the module's fp32 mu parameters) and
+        produces the outputs of all its tokens with ONE ea_ceva_decode_attn (each token against its block window [left
+        extension, block] and the landmarks of the chunks before its own, masked after itself).  Both kernels compute in
+        fp32 on rows of the cache's dtype, so fp32 decoding equals the fp32 full path; which chunks close is decided on the
+        host from the token count, with no read-back.  No limit on the context length or the number of landmarks."""
         if not self.self_attention:
             raise NotImplementedError("incremental decoding of encoder-decoder attention")
         if not self.causal:
@@ -365,7 +368,7 @@ class CausalEVAttention(_ops.DerivedCacheOwner, nn.Module):
                                       "depends on the final sequence length)")
         dev = query.device
         state = self._get_input_buffer(incremental_state)
-        qkv_new = self._project(query, None, None)                 # [T_new, B, 3, h, d]
+        qkv_new = self._project(query, None, None, keep_f32=True)  # [T_new, B, 3, h, d]
         if "qkv" not in state:
             cap = max(2 * w, 64)
             state["qkv"] = torch.zeros((B, cap, 3, h, d), dtype=qkv_new.dtype, device=dev)
@@ -396,9 +399,13 @@ class CausalEVAttention(_ops.DerivedCacheOwner, nn.Module):
                 g2[:, :, :state[name].shape[2]] = state[name]
                 state[name] = g2
         cache = state["qkv"]
+        if qkv_new.dtype != cache.dtype:
+            # the first step fixed the cache's dtype: an fp32 step on a 16-bit cache rounds (with the one-time warning of
+            # _ops.to_io_dtype), a 16-bit step on an fp32 cache widens exactly
+            qkv_new = _ops.to_io_dtype(qkv_new) if cache.dtype != torch.float32 else qkv_new.float()
         cache[:, t0:t0 + T_new] = qkv_new.transpose(0, 1)
-        # (whether a mask was ever given lives on the host: the unpadded case keeps its mask-free chunk kernels without
-        #  reading a flag back from the device)
+        # (whether a mask was ever given lives on the host: the unpadded case passes no mask without reading a flag back
+        #  from the device)
         has_pad = bool(self.get_incremental_state(incremental_state, "attn_has_pad"))
         if key_padding_mask is not None:
             state["pad"][:, t0:t0 + T_new] = key_padding_mask[:, -T_new:].to(device=dev, dtype=torch.uint8)
@@ -406,53 +413,42 @@ class CausalEVAttention(_ops.DerivedCacheOwner, nn.Module):
                 has_pad = True
                 self.set_incremental_state(incremental_state, "attn_has_pad", True)
         pad = state["pad"]
+        cap = cache.shape[1]
         bias = None
         if self.use_t5_rpe:
-            bias = self.rel_pos_bias.dense(w, w + e, dev).expand(h, w, w + e)
-        mlp = self._mu_params()
-        adaptive = "default" if self.adaptive_proj == "qk" else "no-ln"
-        io = _ops.nv.io_dtype(cache)
-        outs = []
-        for i in range(T_new):
-            t = t0 + i
-            # ---- landmarks of the chunks before this token's own (completed at the previous steps) ----
-            nvis = t // r
-            b = t // w
-            b0 = max(b - 1, 0) if e > 0 else b
-            Nc = (b - b0 + 1) * w
-            ctx = cache[:, b0 * w:b0 * w + Nc]                      # [B, Nc, 3, h, d] view
-            mask = pad[:, b0 * w:b0 * w + Nc].clone() if has_pad else torch.zeros((B, Nc), dtype=torch.uint8, device=dev)
-            mask[:, t - b0 * w + 1:] = 1                            # rows after the current token: not decoded yet
-            lk = state["rf_k_bar"][:, :, :nvis].contiguous() if nvis else None
-            lv = state["beta"][:, :, :nvis].contiguous() if nvis else None
-            if nvis <= 64:
-                geom = _ops.nv.make_geom(B, h, Nc, d, io, False, (Nc,), w, e, r, nvis, 2, (b0 * w) // r)
-                bias_p = _ops._bias_padded(bias, geom)
-                out, _ = _ops._window_fwd(geom, ctx, lk, lv, bias_p, mask)
-                outs.append(out[:, t - b0 * w])                     # [B, h, d]
-            else:
-                # more completed chunks than the window kernel holds landmark rows: the same suffix on the generic fp32
-                # kernel (exact on the 16-bit rows; `lm_base` re-bases the visibility rule exactly as ea_geom's does)
-                q32, k32, v32 = [ctx[:, :, i].float().permute(0, 2, 1, 3) for i in range(3)]
-                spec = dict(idx_q=_f32.window_table_1d(Nc, w, 0, dev), idx_k=_f32.window_table_1d(Nc, w, e, dev, left_only=True),
-                            kmask=mask, qmask=mask, scale=d ** -0.5, causal_e=e, chunk=r, lm_base=(b0 * w) // r)
-                with torch.autocast(device_type="cuda", enabled=False):
-                    out, _ = _f32.GatherAttnFn.apply(q32, k32, v32, lk, lv, None if bias is None else bias.float(), spec)
-                outs.append(out[:, :, t - b0 * w].to(cache.dtype))  # [B, h, d]
-            # ---- this token closes chunk c: its landmark becomes visible from the next chunk on ----
-            if (t + 1) % r == 0:
-                c = t // r
-                sub = cache[:, c * r:(c + 1) * r]
-                icfg = [0, r, 0, r, 0, r, 1, 1, 0]
-                cmask = pad[:, c * r:(c + 1) * r].contiguous() if has_pad else None
-                res = torch.ops.ea.eva_fwd(sub, None, None, cmask, None, icfg, [1.0, 1.0], adaptive, list(mlp))
-                state["beta"][:, :, c] = res[6][:, :, 0]
-                state["rf_k_bar"][:, :, c] = res[7][:, :, 0]
+            # the dense single-head [w, w + e] table (already scaled); the module is in eval mode, so it is built once per
+            # weight and reused by every step
+            if not hasattr(self, "_decode_bias_cache"):
+                self._decode_bias_cache = _ops.DerivedCache()
+            rpb = self.rel_pos_bias
+            bias = self._decode_bias_cache.get(self, [rpb.relative_attention_bias.weight],
+                                               lambda: rpb.dense(w, w + e, dev)[0].contiguous())
+        io = _ops.nv.EA_F32 if cache.dtype == torch.float32 else _ops.nv.io_dtype(cache)
+        c_first, c_last = t0 // r, (t0 + T_new) // r - 1            # the chunks this step's tokens complete
+        geom = _ops.nv.ea_ceva_dec_geom(B, h, d, io, w, e, r, t0, T_new, c_first, c_last, cap,
+                                        1 if self.adaptive_proj == "qk" else 0, 0 if bias is None else 1, 1 if has_pad else 0)
+        tq, tk, tv = [_ops.nv.t4(cache[:, :, i].transpose(1, 2)) for i in range(3)]     # [B, h, cap, d] views
+        tl, tb = _ops.nv.t4(state["rf_k_bar"]), _ops.nv.t4(state["beta"])
+        mask_p = _ops.nv.ptr(pad) if has_pad else None
+        st = _ops.nv.stream()
+        if c_last >= c_first:
+            # the kernel reads fp32 parameters: fp32 masters pass through, a module converted with .half() / .bfloat16()
+            # (fairseq's 16-bit generation) hands over fp32 copies, built once per weight as the full path's _f32c does
+            if not hasattr(self, "_decode_mu_cache"):
+                self._decode_mu_cache = _ops.DerivedCache()
+            src = self._mu_params()
+            mlp = self._decode_mu_cache.get(self, src, lambda: [_ops._f32c(p) for p in src])
+            mp = (ctypes.c_void_p * len(mlp))(*[p.data_ptr() for p in mlp])
+            _ops.nv.call("ea_ceva_decode_close", ctypes.byref(geom), ctypes.byref(tq), ctypes.byref(tk), ctypes.byref(tv),
+                         mask_p, mp, ctypes.byref(tl), ctypes.byref(tb), st)
+        out = torch.empty((T_new, B, h, d), dtype=cache.dtype, device=dev)
+        to = _ops.nv.t4(out.permute(1, 2, 0, 3))                   # [B, h, T_new, d] view of the time-first rows
+        _ops.nv.call("ea_ceva_decode_attn", ctypes.byref(geom), ctypes.byref(tq), ctypes.byref(tk), ctypes.byref(tv),
+                     mask_p, _ops.nv.ptr(bias), ctypes.byref(tl), ctypes.byref(tb), ctypes.byref(to), st)
         self.set_incremental_state(incremental_state, "attn_pos", t0 + T_new)
         state["pos"] = state["pos"] + T_new
         self._set_input_buffer(incremental_state, state)
-        o = torch.stack(outs, 0).reshape(T_new, B, C)               # [T_new, B, h*d]
-        y = _ops.linear(o, self.out_proj)
+        y = _ops.linear(out.reshape(T_new, B, C), self.out_proj)
         if not torch.is_autocast_enabled() and y.dtype != query.dtype:
             y = y.to(query.dtype)
         return y.contiguous(), None

@@ -67,9 +67,8 @@ typedef struct {
                               * Masked logits are REPLACED by -5e4 (masked_fill), their gradient is zero. */
   int32_t lm_base;           /* causal == 2 only: landmarks that lie BEFORE the tokens of this call and are visible to
                               * every query -- landmark c is masked unless c < lm_base + token / chunk.  0 for a whole
-                              * sequence; incremental decoding (causal_eva.py:537-665) runs the suffix [previous window,
-                              * current window] against the landmarks of all completed chunks with lm_base = first chunk
-                              * of that suffix. */
+                              * sequence.  No caller of this package sets it any more (ABI 17: incremental decoding has
+                              * its own entry points, ea_ceva_decode_*); kept so that the struct layout stays stable. */
 } ea_geom;
 
 /* ---- library info -------------------------------------------------------------------- */
@@ -749,7 +748,7 @@ typedef struct {
   int32_t B, H, Nq, Nk, D;           /* D in {32, 64, 128} */
   int32_t G, Wq, Wk, L;
   int32_t knorm;                     /* bit 0: the key-norm term; bit 1: masked local keys carry a zero VALUE row (eva.py:167-176) */
-  int32_t neg_inf, causal_e, chunk, lm_base;
+  int32_t neg_inf, causal_e, chunk, lm_base;   /* lm_base: 0 from every caller of this package since ABI 17 (see ea_geom.lm_base) */
   int32_t bias_ld;
   int64_t bias_hs, bias_bs, keep_ld;  /* bias index = b bias_bs + h bias_hs + i bias_ld + j (0 strides: shared) */
   float   keep_scale, scale;
@@ -905,6 +904,40 @@ int ea_scatter_bwd_window(const ea_sb_geom* g, const ea_t4* q, const ea_t4* k, c
 int ea_scatter_bwd_global(const ea_sb_geom* g, const ea_t4* k, const ea_t4* v, const uint8_t* mask, const float* W,
                           const float* mx, const float* dsall, const float* dzall, const ea_t4* dk, const ea_t4* dv,
                           void* stream);
+
+/* ---- causal EVA, incremental decoding (ABI 17; causal_eva.py:537-665; ea_ceva_decode.hip) --------------------------
+ * One decoding step of CausalEVAttention with fairseq's incremental state, defined by prefix consistency with the
+ * full-sequence causal path (the output for token t equals row t of the forward on tokens 0..t).  q, k, v address the
+ * projected rows of the state's cache as [B, H, cap, D] (token n = row n); pad is uint8 [B, cap], 1 = padded position, or
+ * NULL (has_mask = 0); rf_k_bar and beta are the state's fp32 [B, H, Lcap, D] landmark rows, indexed by absolute chunk.
+ * Everything is computed in fp32; rows are read and out is written in `dtype` (EA_BF16 | EA_F16 | EA_F32: with fp32 rows
+ * nothing is rounded to 16 bits).  D = 32, 64 or 128; w, e, r and the number of chunks are not limited.
+ *   ea_ceva_decode_close: for every chunk c in [c_first, c_last] (rows c r .. c r + r - 1, all decoded), one workgroup per
+ *     (c, b, h): qm, km = sum of the unpadded q / k rows / r (eva.py:167-181); rk = mu_k(km), mu = mu_q(qm) + rk with mu_* =
+ *     Linear(D, D) followed (adaptive = 1, 'qk') by LayerNorm(D, eps 1e-5), or not (adaptive = 0, 'no-ln'); mu_params: a
+ *     HOST array of device pointers, the module's fp32 parameters in _mu_params() order (q Linear W, b[, LN w, b], then k);
+ *     beta_c = sum_j softmax_j(s mu.k_j - s|k_j|^2/2) v_j, padded rows -5e4 with a zero value row.  Writes rf_k_bar[c] = rk
+ *     and beta[c].  Eval mode: no sampling noise.
+ *   ea_ceva_decode_attn: the outputs of tokens t0 .. t0 + T_new - 1 (already in the cache), one workgroup per (window block
+ *     touched, b, h).  Token t of block bk = t / w: local slot j < w + e is token bk w - e + j, masked with -5e4 when it is
+ *     absent (< 0), padded, after t, or t itself is padded; its logit is s q.k_j + bias[t - bk w, j] (bias: fp32 [w, w + e]
+ *     dense single-head table, natural-log domain, or NULL when has_bias = 0); landmark c is a column iff c < t / r (every
+ *     chunk before t's own is closed).  One softmax over both, out = P [v ; beta]; out [B, H, T_new, D] row t - t0.
+ * t0 is a kernel argument; nothing is read back to the host.  Replaces the per-token window launches of causal_eva.py:542-665. */
+typedef struct {
+  int32_t B, H, D;
+  int32_t dtype;             /* EA_BF16 | EA_F16 | EA_F32: the cache rows and out */
+  int32_t window, ext, chunk;  /* w, e (left extension, 0 or w), r */
+  int32_t t0, T_new;         /* the step's tokens */
+  int32_t c_first, c_last;   /* close: chunks to build, inclusive */
+  int32_t cap;               /* cache capacity in tokens (row stride of pad) */
+  int32_t adaptive;          /* 1: 'qk' (Linear + LayerNorm), 0: 'no-ln' (Linear) */
+  int32_t has_bias, has_mask;
+} ea_ceva_dec_geom;
+int ea_ceva_decode_close(const ea_ceva_dec_geom* g, const ea_t4* q, const ea_t4* k, const ea_t4* v, const uint8_t* pad,
+                         const float* const* mu_params, const ea_t4* rf_k_bar, const ea_t4* beta, void* stream);
+int ea_ceva_decode_attn(const ea_ceva_dec_geom* g, const ea_t4* q, const ea_t4* k, const ea_t4* v, const uint8_t* pad,
+                        const float* bias, const ea_t4* rf_k_bar, const ea_t4* beta, const ea_t4* out, void* stream);
 
 #ifdef __cplusplus
 }
