@@ -79,7 +79,7 @@ static Geo mk_geo(const ea_geom* g) {
 extern "C" {
 
 const char* ea_version(void) { return "ea_hip 0.1.0 gfx950"; }
-int32_t ea_abi_version(void) { return 17; }
+int32_t ea_abi_version(void) { return 18; }
 
 int32_t ea_window_bias_ld(const ea_geom* g) {
   WinTiling t;
@@ -2151,6 +2151,66 @@ int ea_ceva_decode_attn(const ea_ceva_dec_geom* g, const ea_t4* q, const ea_t4* 
   p.o = dec_mk(out);
   p.bias = g->has_bias ? bias : nullptr;
   return ea::ceva_decode_dispatch(false, p, (hipStream_t)stream);
+}
+
+}  // extern "C"
+
+// static decoding: the geometry of a step whose token count is *g->pos (checked as t0 = 0; the kernels check t0 + T <= cap)
+static int sdec_fill(const ea_ceva_sdec_geom* g, const ea_t4* q, const ea_t4* k, const ea_t4* v, const uint8_t* pad,
+                     const ea_t4* lk, const ea_t4* lv, ea::DecP& p) {
+  if (!g || !g->pos || !g->status || (uintptr_t)g->pos % 4 || (uintptr_t)g->status % 4 || !pad || g->window <= 0 ||
+      g->chunk <= 0 || g->cap % g->window || g->window % g->chunk) return EA_E_BADARG;
+  const ea_ceva_dec_geom d = {g->B, g->H, g->D, g->dtype, g->window, g->ext, g->chunk, 0, g->T_new, 0, -1, g->cap,
+                              g->adaptive, g->has_bias, 1};
+  const int rc = dec_fill(&d, q, k, v, pad, lk, lv, p);
+  p.pos = g->pos;
+  return rc;
+}
+
+extern "C" {
+
+int ea_ceva_sdecode_append(const ea_ceva_sdec_geom* g, const void* qkv_new, const uint8_t* new_pad, void* qkv, uint8_t* pad,
+                           void* stream) {
+  if (!g || !g->pos || !g->status || (uintptr_t)g->pos % 4 || (uintptr_t)g->status % 4 || !pad || !qkv_new || !qkv ||
+      (uintptr_t)qkv_new % 16 || (uintptr_t)qkv % 16 || g->B <= 0 || g->H <= 0 || g->T_new <= 0 || g->cap < g->T_new ||
+      (g->dtype != EA_BF16 && g->dtype != EA_F16 && g->dtype != EA_F32)) return EA_E_BADARG;
+  if (g->D != 32 && g->D != 64 && g->D != 128) return EA_E_UNSUPPORTED;
+  ea::AppP p = {};
+  p.src = (const char*)qkv_new; p.src_pad = new_pad; p.cache = (char*)qkv; p.pad = pad;
+  p.pos = g->pos; p.status = g->status;
+  p.B = g->B; p.T = g->T_new; p.cap = g->cap;
+  p.row_bytes = 3 * g->H * g->D * (g->dtype == EA_F32 ? 4 : 2);
+  return ea::ceva_sdecode_append(p, (hipStream_t)stream);
+}
+
+int ea_ceva_sdecode_close(const ea_ceva_sdec_geom* g, const ea_t4* q, const ea_t4* k, const ea_t4* v, const uint8_t* pad,
+                          const float* const* mu_params, const ea_t4* rf_k_bar, const ea_t4* beta, void* stream) {
+  ea::DecP p = {};
+  const int rc = sdec_fill(g, q, k, v, pad, rf_k_bar, beta, p);
+  if (rc != EA_OK) return rc;
+  if (!mu_params) return EA_E_BADARG;
+  const int np = g->adaptive ? 8 : 4;
+  for (int i = 0; i < np; ++i) {
+    if (!mu_params[i] || (uintptr_t)mu_params[i] % 16) return EA_E_BADARG;
+    p.mu[i] = mu_params[i];
+  }
+  return ea::ceva_sdecode_dispatch(true, p, (hipStream_t)stream);
+}
+
+int ea_ceva_sdecode_attn(const ea_ceva_sdec_geom* g, const ea_t4* q, const ea_t4* k, const ea_t4* v, const uint8_t* pad,
+                         const float* bias, const ea_t4* rf_k_bar, const ea_t4* beta, const ea_t4* out, void* stream) {
+  ea::DecP p = {};
+  const int rc = sdec_fill(g, q, k, v, pad, rf_k_bar, beta, p);
+  if (rc != EA_OK) return rc;
+  if (!dec_t4_ok(out, g->D, g->dtype == EA_F32 ? 4 : 2) || (g->has_bias && !bias)) return EA_E_BADARG;
+  p.o = dec_mk(out);
+  p.bias = g->has_bias ? bias : nullptr;
+  return ea::ceva_sdecode_dispatch(false, p, (hipStream_t)stream);
+}
+
+int ea_ceva_sdecode_advance(const ea_ceva_sdec_geom* g, void* stream) {
+  if (!g || !g->pos || (uintptr_t)g->pos % 4 || g->T_new <= 0 || g->cap < g->T_new) return EA_E_BADARG;
+  return ea::ceva_sdecode_advance(const_cast<int32_t*>(g->pos), g->T_new, g->cap, (hipStream_t)stream);
 }
 
 }  // extern "C"

@@ -19,8 +19,22 @@ struct DecP {
   const float* mu[8];         // close: the mu networks' parameters in _mu_params() order
   int B, H, D, dtype, w, e, r, t0, T, c_first, c_last, cap, adaptive;
   float scale;
+  const int32_t* pos;         // static decoding: the token count in device memory (t0, c_first, c_last unused), or null
+};
+
+struct AppP {                 // static decoding, append: the step's rows into the cache at rows *pos ..
+  const char* src;            // [T, B, 3, H, D] time-first rows of the step (the cache's dtype)
+  const uint8_t* src_pad;     // [B, T] the step's pad flags, or null (zeros)
+  char* cache;                // [B, cap, 3, H, D]
+  uint8_t* pad;               // [B, cap]
+  const int32_t* pos;
+  int32_t* status;            // set to 1 when the step would pass cap (nothing is written)
+  int B, T, cap, row_bytes;   // row_bytes = 3 H D element bytes, a multiple of 16
 };
 
 int ceva_decode_dispatch(bool close, const DecP& p, hipStream_t st);
+int ceva_sdecode_dispatch(bool close, const DecP& p, hipStream_t st);
+int ceva_sdecode_append(const AppP& p, hipStream_t st);
+int ceva_sdecode_advance(int32_t* pos, int T, int cap, hipStream_t st);
 
 }  // namespace ea

@@ -16,6 +16,10 @@
 // The keys are streamed in 64-column tiles (local tiles first, then landmark tiles), one key per lane for the logits and
 // G = D / 4 lanes per value row for P.V.  A wave owns up to QPW queries; when the step holds fewer query groups than
 // waves, the waves split the tiles of each group and merge their (max, sum, acc) partials in LDS.
+//
+// Static decoding (CausalEVAttention.init_static_decoding; ea_ceva_sdecode_*) runs the same two kernels with DEV = true: the
+// step's first token is read from device memory (*p.pos) instead of a kernel argument, so that a captured step replays at
+// the right position.  ceva_append_kernel writes the step's rows into the cache first, ceva_advance_kernel moves *pos last.
 #include "ea_common.h"
 #include "ea_ceva_decode.h"
 
@@ -100,7 +104,21 @@ EA_DEV void pv_rows(const DecT& t, int b, int h, int n0, int nrows, int kg, int 
   }
 }
 
+// every output row of the step is NaN: a static step that would pass the cache's capacity (written by blockIdx.x == 0)
 template <typename E, int D>
+EA_DEV void refuse_out(const DecP& p, int b, int h) {
+  if (blockIdx.x != 0) return;
+  const float nan = __builtin_nanf("");
+  for (int idx = threadIdx.x; idx < p.T * (D / 4); idx += NT) {
+    const int i = idx / (D / 4), c = (idx - i * (D / 4)) * 4;
+    Io<E>::st4(const_cast<char*>(row<E>(p.o, b, h, i)) + (size_t)c * Io<E>::SZ, f32x4{nan, nan, nan, nan});
+  }
+}
+
+// DEV = false: t0 is the kernel argument (ea_ceva_decode_attn).  DEV = true: t0 = *p.pos, read from device memory
+// (ea_ceva_sdecode_attn); the grid holds the most window blocks T tokens can touch, and a block this step does not touch
+// exits at once.  The arithmetic is the same in both.
+template <typename E, int D, bool DEV>
 __global__ __launch_bounds__(NT) void ceva_attn_kernel(const DecP p) {
   static_assert(QPW == 8, "pv_rows reads the probabilities of a row as two float4");
   constexpr int G = D / 4;                         // lanes per value row in P.V
@@ -109,13 +127,19 @@ __global__ __launch_bounds__(NT) void ceva_attn_kernel(const DecP p) {
   __shared__ __attribute__((aligned(16))) float mo[NW][QPW][D];
   __shared__ float ml[NW][QPW][2];
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  const int bk = p.t0 / p.w + (int)blockIdx.x;
   const int b = (int)blockIdx.y / p.H, h = (int)blockIdx.y - b * p.H;
-  const int tq0 = max(p.t0, bk * p.w), tq1 = min(p.t0 + p.T, (bk + 1) * p.w);
+  int t0 = p.t0;
+  if constexpr (DEV) {
+    t0 = *p.pos;                                   // (one value for every thread: the exits below are uniform)
+    if (t0 + p.T > p.cap) { refuse_out<E, D>(p, b, h); return; }
+    if ((t0 / p.w + (int)blockIdx.x) * p.w >= t0 + p.T) return;
+  }
+  const int bk = t0 / p.w + (int)blockIdx.x;
+  const int tq0 = max(t0, bk * p.w), tq1 = min(t0 + p.T, (bk + 1) * p.w);
   const int nqg = (tq1 - tq0 + QPW - 1) / QPW;
   const int nsplit = nqg >= NW ? 1 : NW / nqg;     // waves per query group
   const int Wk = p.w + p.e, nlt = (Wk + KT - 1) / KT;
-  const int tend = p.t0 + p.T;                     // cache rows [0, tend) hold tokens
+  const int tend = t0 + p.T;                       // cache rows [0, tend) hold tokens
   const int kbase = bk * p.w - p.e;                // token of local slot 0
   const int kg = lane / G, dc = (lane % G) * 4;
   for (int g = wave / nsplit; g < nqg; g += NW) {
@@ -194,7 +218,7 @@ __global__ __launch_bounds__(NT) void ceva_attn_kernel(const DecP p) {
       if (lane < G) {
 #pragma unroll
         for (int i = 0; i < QPW; ++i)
-          if (i < nql) Io<E>::st4(const_cast<char*>(row<E>(p.o, b, h, qa + i - p.t0)) + (size_t)dc * Io<E>::SZ, acc[i] * (1.f / l[i]));
+          if (i < nql) Io<E>::st4(const_cast<char*>(row<E>(p.o, b, h, qa + i - t0)) + (size_t)dc * Io<E>::SZ, acc[i] * (1.f / l[i]));
       }
     } else {
       if (lane < G) {
@@ -223,7 +247,7 @@ __global__ __launch_bounds__(NT) void ceva_attn_kernel(const DecP p) {
       lt += f * ml[w][i][1];
       o += f * *reinterpret_cast<const f32x4*>(&mo[w][i][c]);
     }
-    Io<E>::st4(const_cast<char*>(row<E>(p.o, b, h, qa + i - p.t0)) + (size_t)c * Io<E>::SZ, o * (1.f / lt));
+    Io<E>::st4(const_cast<char*>(row<E>(p.o, b, h, qa + i - t0)) + (size_t)c * Io<E>::SZ, o * (1.f / lt));
   }
 }
 
@@ -239,7 +263,10 @@ EA_DEV float block_max(float v, float* red) {
   return r;
 }
 
-template <typename E, int D>
+// DEV = false: chunks c_first .. c_last of the kernel arguments (ea_ceva_decode_close).  DEV = true: the chunks that the
+// step's tokens *p.pos .. *p.pos + T - 1 complete (ea_ceva_sdecode_close); the grid holds ceil(T / r), the most T tokens can
+// complete, and a workgroup whose chunk this step does not complete exits at once.
+template <typename E, int D, bool DEV>
 __global__ __launch_bounds__(NT) void ceva_close_kernel(const DecP p) {
   __shared__ __attribute__((aligned(16))) float xm[2][D];      // chunk means of q, k
   __shared__ __attribute__((aligned(16))) float y[2][D];       // after the Linear layers
@@ -247,7 +274,12 @@ __global__ __launch_bounds__(NT) void ceva_close_kernel(const DecP p) {
   __shared__ float pt[NT];                                      // probabilities of the current row tile
   __shared__ float red[NW];
   const int tid = threadIdx.x;
-  const int c = p.c_first + (int)blockIdx.x;
+  int c = p.c_first + (int)blockIdx.x;
+  if constexpr (DEV) {
+    const int t0 = *p.pos;
+    c = t0 / p.r + (int)blockIdx.x;
+    if (t0 + p.T > p.cap || c > (t0 + p.T) / p.r - 1) return;
+  }
   const int b = (int)blockIdx.y / p.H, h = (int)blockIdx.y - b * p.H;
   const int n0 = c * p.r;
   const uint8_t* pad = p.pad ? p.pad + (size_t)b * p.cap + n0 : nullptr;
@@ -339,37 +371,86 @@ __global__ __launch_bounds__(NT) void ceva_close_kernel(const DecP p) {
   if (tid < D) const_cast<float*>(reinterpret_cast<const float*>(row<float>(p.lv, b, h, c)))[tid] = acc / lrun;
 }
 
-template <typename E, int D>
+// ---- static decoding (ea_ceva_sdecode_*): the token count lives in device memory --------------------------------------
+// A step is append -> close -> attn -> advance on one stream.  Only advance writes *pos, so the three before it read the
+// same count, and each decides from it alone whether the step fits the cache.  A step that does not fit writes no cache
+// byte: append sets *status, close exits, attn writes NaN rows, advance leaves *pos.
+
+// one workgroup per (token t, element b) of the step: the token's [3, H, D] row, 16 bytes per lane and load, and its pad flag
+__global__ __launch_bounds__(NT) void ceva_append_kernel(const AppP p) {
+  const int t0 = *p.pos;
+  const int t = (int)blockIdx.x, b = (int)blockIdx.y;
+  if (t0 + p.T > p.cap) {
+    if (t == 0 && b == 0 && threadIdx.x == 0) *p.status = 1;
+    return;
+  }
+  const u32x4* src = reinterpret_cast<const u32x4*>(p.src + ((size_t)t * p.B + b) * p.row_bytes);
+  u32x4* dst = reinterpret_cast<u32x4*>(p.cache + ((size_t)b * p.cap + t0 + t) * p.row_bytes);
+  for (int i = threadIdx.x; i < p.row_bytes / 16; i += NT) dst[i] = src[i];
+  if (threadIdx.x == 0) p.pad[(size_t)b * p.cap + t0 + t] = p.src_pad ? p.src_pad[(size_t)b * p.T + t] : (uint8_t)0;
+}
+
+// *pos += T, in a launch of its own after attn on the same stream: stream order puts it behind every read of *pos in the
+// step.  (The other way, the last attn workgroup advancing through a completion counter, needs an agent-scope release /
+// acquire pair across XCDs and a counter that every replay must find reset; a dependent launch boundary costs about
+// 1.5 us, eager or in a graph, and leaves no ordering to get wrong.)
+__global__ __launch_bounds__(64) void ceva_advance_kernel(int32_t* pos, int T, int cap) {
+  if (threadIdx.x == 0) {
+    const int t0 = *pos;
+    if (t0 + T <= cap) *pos = t0 + T;
+  }
+}
+
+template <typename E, int D, bool DEV>
 int launch(bool close, const DecP& p, hipStream_t st) {
   if (close) {
-    const dim3 grid((unsigned)(p.c_last - p.c_first + 1), (unsigned)(p.B * p.H));
-    hipLaunchKernelGGL((ceva_close_kernel<E, D>), grid, dim3(NT), 0, st, p);
+    const unsigned nc = DEV ? (unsigned)((p.T + p.r - 1) / p.r) : (unsigned)(p.c_last - p.c_first + 1);
+    hipLaunchKernelGGL((ceva_close_kernel<E, D, DEV>), dim3(nc, (unsigned)(p.B * p.H)), dim3(NT), 0, st, p);
   } else {
-    const dim3 grid((unsigned)((p.t0 + p.T - 1) / p.w - p.t0 / p.w + 1), (unsigned)(p.B * p.H));
-    hipLaunchKernelGGL((ceva_attn_kernel<E, D>), grid, dim3(NT), 0, st, p);
+    // DEV: the most window blocks T tokens can touch, wherever they start
+    const unsigned nb = DEV ? (unsigned)((p.T + p.w - 2) / p.w + 1) : (unsigned)((p.t0 + p.T - 1) / p.w - p.t0 / p.w + 1);
+    hipLaunchKernelGGL((ceva_attn_kernel<E, D, DEV>), dim3(nb, (unsigned)(p.B * p.H)), dim3(NT), 0, st, p);
   }
   return (int)hipGetLastError();
 }
 
-template <typename E>
+template <typename E, bool DEV>
 int launch_d(bool close, const DecP& p, hipStream_t st) {
   switch (p.D) {
-    case 32: return launch<E, 32>(close, p, st);
-    case 64: return launch<E, 64>(close, p, st);
-    default: return launch<E, 128>(close, p, st);
+    case 32: return launch<E, 32, DEV>(close, p, st);
+    case 64: return launch<E, 64, DEV>(close, p, st);
+    default: return launch<E, 128, DEV>(close, p, st);
+  }
+}
+
+template <bool DEV>
+int dispatch(bool close, const DecP& p, hipStream_t st) {
+  if (p.D != 32 && p.D != 64 && p.D != 128) return EA_E_UNSUPPORTED;
+  switch (p.dtype) {
+    case EA_BF16: return launch_d<BF16, DEV>(close, p, st);
+    case EA_F16: return launch_d<F16, DEV>(close, p, st);
+    case EA_F32: return launch_d<float, DEV>(close, p, st);
+    default: return EA_E_BADARG;
   }
 }
 
 }  // namespace
 
-int ceva_decode_dispatch(bool close, const DecP& p, hipStream_t st) {
-  if (p.D != 32 && p.D != 64 && p.D != 128) return EA_E_UNSUPPORTED;
-  switch (p.dtype) {
-    case EA_BF16: return launch_d<BF16>(close, p, st);
-    case EA_F16: return launch_d<F16>(close, p, st);
-    case EA_F32: return launch_d<float>(close, p, st);
-    default: return EA_E_BADARG;
-  }
+int ceva_decode_dispatch(bool close, const DecP& p, hipStream_t st) { return dispatch<false>(close, p, st); }
+
+int ceva_sdecode_dispatch(bool close, const DecP& p, hipStream_t st) {
+  if (!p.pos || !p.pad) return EA_E_BADARG;
+  return dispatch<true>(close, p, st);
+}
+
+int ceva_sdecode_append(const AppP& p, hipStream_t st) {
+  hipLaunchKernelGGL(ceva_append_kernel, dim3((unsigned)p.T, (unsigned)p.B), dim3(NT), 0, st, p);
+  return (int)hipGetLastError();
+}
+
+int ceva_sdecode_advance(int32_t* pos, int T, int cap, hipStream_t st) {
+  hipLaunchKernelGGL(ceva_advance_kernel, dim3(1), dim3(64), 0, st, pos, T, cap);
+  return (int)hipGetLastError();
 }
 
 }  // namespace ea

@@ -22,7 +22,7 @@ class ea_t4(ctypes.Structure):
                 ("sn", ctypes.c_int64)]
 
 
-ABI_VERSION = 17         # ea_abi_version() of include/ea_hip.h this file mirrors
+ABI_VERSION = 18         # ea_abi_version() of include/ea_hip.h this file mirrors
 
 
 class ea_geom(ctypes.Structure):
@@ -79,6 +79,13 @@ class ea_ceva_dec_geom(ctypes.Structure):
                 ("adaptive", ctypes.c_int32), ("has_bias", ctypes.c_int32), ("has_mask", ctypes.c_int32)]
 
 
+class ea_ceva_sdec_geom(ctypes.Structure):
+    _fields_ = [("B", ctypes.c_int32), ("H", ctypes.c_int32), ("D", ctypes.c_int32), ("dtype", ctypes.c_int32),
+                ("window", ctypes.c_int32), ("ext", ctypes.c_int32), ("chunk", ctypes.c_int32), ("T_new", ctypes.c_int32),
+                ("cap", ctypes.c_int32), ("adaptive", ctypes.c_int32), ("has_bias", ctypes.c_int32),
+                ("pos", ctypes.c_void_p), ("status", ctypes.c_void_p)]
+
+
 class ea_eva_layer(ctypes.Structure):
     _fields_ = [("B", ctypes.c_int32), ("H", ctypes.c_int32), ("D", ctypes.c_int32), ("dtype", ctypes.c_int32),
                 ("gh", ctypes.c_int32), ("gw", ctypes.c_int32), ("window", ctypes.c_int32), ("chunk", ctypes.c_int32),
@@ -106,6 +113,7 @@ _LL = ctypes.POINTER(ea_lara_layer)
 _EL = ctypes.POINTER(ea_eva_layer)
 _FA = ctypes.POINTER(ea_f32_attn)
 _DG = ctypes.POINTER(ea_ceva_dec_geom)
+_SDG = ctypes.POINTER(ea_ceva_sdec_geom)
 
 # name -> argtypes; every symbol include/ea_hip.h declares (tests check the list is complete)
 SIGNATURES = {
@@ -223,6 +231,10 @@ SIGNATURES = {
     "ea_kernelized_bwd_k": [_KG, _T, _T, _P, _P, _P, _P, _P, _T, _T, _P, _P],
     "ea_ceva_decode_close": [_DG, _T, _T, _T, _P, _P, _T, _T, _P],
     "ea_ceva_decode_attn": [_DG, _T, _T, _T, _P, _P, _T, _T, _T, _P],
+    "ea_ceva_sdecode_append": [_SDG, _P, _P, _P, _P, _P],
+    "ea_ceva_sdecode_close": [_SDG, _T, _T, _T, _P, _P, _T, _T, _P],
+    "ea_ceva_sdecode_attn": [_SDG, _T, _T, _T, _P, _P, _T, _T, _T, _P],
+    "ea_ceva_sdecode_advance": [_SDG, _P],
     "ea_softmax_attn_fwd": [_I, _I, _I, _I, _I, _F, _T, _T, _T, _P, _T, _P, _P, _F, _I, _P],
     "ea_softmax_sample": [_I, _I, _I, _I, _I, _F, _T, _T, _P, _P, _P],
     "ea_softmax_attn_bwd": [_I, _I, _I, _I, _I, _F, _T, _T, _T, _P, _T, _T, _P, _P, _T, _T, _T, _P, _F, _I, _P],

@@ -33,6 +33,11 @@ def _mu_net(d, with_ln):
     return nn.Sequential(*([nn.Linear(d, d)] + ([nn.LayerNorm(d)] if with_ln else [])))
 
 
+_NEEDS_CHUNK_SIZE = ("incremental decoding needs --chunk-size (with --num-chunks the chunk length depends on the final "
+                     "sequence length)")
+_STATIC_BATCH_FIRST = ("qkv", "rf_k_bar", "beta", "pad")      # the buffers of a static state that a beam reorder permutes
+
+
 class CausalEVAttention(_ops.DerivedCacheOwner, nn.Module):
     def __init__(self, embed_dim, num_heads, kdim=None, vdim=None, dropout=0.0, bias=True,
                  self_attention=False, q_noise=0.0, qn_block_size=8, attn_args=None):
@@ -320,6 +325,120 @@ class CausalEVAttention(_ops.DerivedCacheOwner, nn.Module):
         return y
 
     # ---- incremental decoding (reference :537-665) ------------------------------------------
+    def _refuse_decoding(self):
+        """The cases incremental decoding does not define, dynamic and static state alike."""
+        if not self.self_attention:
+            raise NotImplementedError("incremental decoding of encoder-decoder attention")
+        if not self.causal:
+            raise NotImplementedError("incremental decoding needs --causal: without the causal masks every query of the "
+                                      "training path sees the landmarks of future chunks (causal_eva.py:716-738)")
+        if self.training:
+            raise NotImplementedError("incremental decoding in training mode")
+        if self.adaptive_proj not in ("qk", "no-ln"):
+            raise NotImplementedError("Other adaptive projection methods are not implemented yet.")
+
+    def init_static_decoding(self, incremental_state, batch_size, max_tokens, dtype, device):
+        """Allocate, once, every buffer a decoding step touches and mark this module's incremental state as STATIC: every
+        later `forward(..., incremental_state=incremental_state)` then runs `_decode_static`, a step that can be captured into
+        a graph (`torch.cuda.graph`) and replayed -- the token count lives in device memory and the kernels advance it.
+        State, allocated here (cap = ceil(max_tokens / w) w):
+            qkv       [B, cap, 3, h, d]   `dtype` (bf16, fp16, or fp32 when the fp32 cores are enabled)
+            rf_k_bar  [B, h, cap / r, d]  fp32
+            beta      [B, h, cap / r, d]  fp32
+            pad       [B, cap]            uint8, zeros
+            pos       [1]                 int32 on the device: tokens decoded so far
+            status    [1]                 int32 on the device: 1 once a step would have passed cap
+            bias, mu                      the dense T5 table and fp32 copies of the mu parameters, built here once (a
+                                          capture fixes the weights)
+        A step's token count and the batch are fixed for a given capture; the prompt can go through the same state eagerly.
+        Refuses what dynamic decoding refuses, with the same messages, and CPU devices (there is no CPU fallback)."""
+        self._refuse_decoding()
+        if self.chunk_size is None:
+            raise NotImplementedError(_NEEDS_CHUNK_SIZE)
+        if dtype not in (torch.bfloat16, torch.float16, torch.float32):
+            raise ValueError("static decoding caches bf16, fp16 or fp32 rows, not %s" % (dtype,))
+        if dtype == torch.float32 and not _f32.ENABLED:
+            raise ValueError("an fp32 static decoding cache needs the fp32 cores (EA_F32_CORES=1)")
+        device = torch.device(device)
+        _ops.nv.require_cuda(torch.empty(0, device=device), "the static decoding state")
+        B, T = int(batch_size), int(max_tokens)
+        if B <= 0 or T <= 0:
+            raise ValueError("static decoding needs batch_size > 0 and max_tokens > 0, got %d, %d" % (B, T))
+        w, e, h, d, r = self.window_size, self.ext_size, self.num_heads, self.head_dim, self.chunk_size
+        cap = -(-T // w) * w
+        state = {
+            "qkv": torch.zeros((B, cap, 3, h, d), dtype=dtype, device=device),
+            "rf_k_bar": torch.zeros((B, h, cap // r, d), dtype=torch.float32, device=device),
+            "beta": torch.zeros((B, h, cap // r, d), dtype=torch.float32, device=device),
+            "pad": torch.zeros((B, cap), dtype=torch.uint8, device=device),
+            "pos": torch.zeros((1,), dtype=torch.int32, device=device),
+            "status": torch.zeros((1,), dtype=torch.int32, device=device),
+        }
+        with torch.no_grad():
+            # (what the dynamic path builds lazily through its DerivedCaches, by the same calls)
+            state["bias"] = self.rel_pos_bias.dense(w, w + e, device)[0].contiguous() if self.use_t5_rpe else None
+            state["mu"] = [_ops._f32c(p) for p in self._mu_params()]
+        self._set_input_buffer(incremental_state, state)
+        # host side: the shadow count of EAGER steps (a replay advances only the device count), for the eager overflow check
+        self.set_incremental_state(incremental_state, "attn_static", {"count": 0})
+        return incremental_state
+
+    def static_decoding_overflowed(self, incremental_state):
+        """True once a step on this static state would have passed its capacity (the step wrote nothing; its outputs are
+        NaN).  Reads the device flag back: call it after a replay, not inside a captured step."""
+        return bool(self._get_input_buffer(incremental_state)["status"].item())
+
+    def _decode_static(self, query, key_padding_mask, incremental_state, static):
+        """One decoding step on a state of `init_static_decoding`, safe to capture: four launches of the attention core
+        (ea_ceva_sdecode_append, _close, _attn, _advance) that read the token count from `pos`, no allocation but the step's
+        own outputs, no read-back, no host counter a replay would need.  The arithmetic is `_decode`'s, so the outputs equal
+        its outputs bit for bit."""
+        nv = _ops.nv
+        T_new, B, C = query.shape
+        w, e, h, d, r = self.window_size, self.ext_size, self.num_heads, self.head_dim, self.chunk_size
+        state = self._get_input_buffer(incremental_state)
+        cache, pad = state["qkv"], state["pad"]
+        cap = cache.shape[1]
+        if cache.shape[0] != B:
+            raise RuntimeError("static decoding state holds batch %d, the step has %d" % (cache.shape[0], B))
+        capturing = torch.cuda.is_current_stream_capturing()
+        if not capturing and static["count"] + T_new > cap:
+            raise RuntimeError("static decoding state is full: %d of its %d tokens decoded, the step adds %d "
+                               "(init_static_decoding(max_tokens=...))" % (static["count"], cap, T_new))
+        qkv_new = self._project(query, None, None, keep_f32=True)   # [T_new, B, 3, h, d]
+        if qkv_new.dtype != cache.dtype:
+            # (the dynamic path's rule: an fp32 step on a 16-bit cache rounds with the warning, a 16-bit one on fp32 widens)
+            qkv_new = _ops.to_io_dtype(qkv_new) if cache.dtype != torch.float32 else qkv_new.float()
+            qkv_new = qkv_new.to(cache.dtype)
+        qkv_new = qkv_new.contiguous()
+        new_pad = None
+        if key_padding_mask is not None:
+            new_pad = key_padding_mask[:, -T_new:].to(device=query.device, dtype=torch.uint8).contiguous()
+        bias = state["bias"]
+        io = nv.EA_F32 if cache.dtype == torch.float32 else nv.io_dtype(cache)
+        geom = nv.ea_ceva_sdec_geom(B, h, d, io, w, e, r, T_new, cap, 1 if self.adaptive_proj == "qk" else 0,
+                                    0 if bias is None else 1, state["pos"].data_ptr(), state["status"].data_ptr())
+        g = ctypes.byref(geom)
+        tq, tk, tv = [nv.t4(cache[:, :, i].transpose(1, 2)) for i in range(3)]      # [B, h, cap, d] views
+        tl, tb = nv.t4(state["rf_k_bar"]), nv.t4(state["beta"])
+        mlp = state["mu"]
+        mp = (ctypes.c_void_p * len(mlp))(*[p.data_ptr() for p in mlp])
+        st = nv.stream()
+        nv.call("ea_ceva_sdecode_append", g, nv.ptr(qkv_new), nv.ptr(new_pad), nv.ptr(cache), nv.ptr(pad), st)
+        nv.call("ea_ceva_sdecode_close", g, ctypes.byref(tq), ctypes.byref(tk), ctypes.byref(tv), nv.ptr(pad), mp,
+                ctypes.byref(tl), ctypes.byref(tb), st)
+        out = torch.empty((T_new, B, h, d), dtype=cache.dtype, device=query.device)
+        to = nv.t4(out.permute(1, 2, 0, 3))                         # [B, h, T_new, d] view of the time-first rows
+        nv.call("ea_ceva_sdecode_attn", g, ctypes.byref(tq), ctypes.byref(tk), ctypes.byref(tv), nv.ptr(pad), nv.ptr(bias),
+                ctypes.byref(tl), ctypes.byref(tb), ctypes.byref(to), st)
+        nv.call("ea_ceva_sdecode_advance", g, st)
+        if not capturing:
+            static["count"] += T_new
+        y = _ops.linear(out.reshape(T_new, B, C), self.out_proj)
+        if not torch.is_autocast_enabled() and y.dtype != query.dtype:
+            y = y.to(query.dtype)
+        return y.contiguous(), None
+
     def _decode(self, query, key_padding_mask, incremental_state):
         """Token-by-token decoding with fairseq's incremental state.
 
@@ -343,16 +462,9 @@ class CausalEVAttention(_ops.DerivedCacheOwner, nn.Module):
         produces the outputs of all its tokens with ONE ea_ceva_decode_attn (each token against its block window [left
         extension, block] and the landmarks of the chunks before its own, masked after itself).  Both kernels compute in
         fp32 on rows of the cache's dtype, so fp32 decoding equals the fp32 full path; which chunks close is decided on the
-        host from the token count, with no read-back.  No limit on the context length or the number of landmarks."""
-        if not self.self_attention:
-            raise NotImplementedError("incremental decoding of encoder-decoder attention")
-        if not self.causal:
-            raise NotImplementedError("incremental decoding needs --causal: without the causal masks every query of the "
-                                      "training path sees the landmarks of future chunks (causal_eva.py:716-738)")
-        if self.training:
-            raise NotImplementedError("incremental decoding in training mode")
-        if self.adaptive_proj not in ("qk", "no-ln"):
-            raise NotImplementedError("Other adaptive projection methods are not implemented yet.")
+        host from the token count, with no read-back.  No limit on the context length or the number of landmarks.
+        A state made by `init_static_decoding` takes `_decode_static` instead."""
+        self._refuse_decoding()
         _ops.nv.require_cuda(query, "query")                       # (before any state is built: no CPU fallback)
         T_new, B, C = query.shape
         if key_padding_mask is not None:
@@ -364,8 +476,10 @@ class CausalEVAttention(_ops.DerivedCacheOwner, nn.Module):
         w, e, h, d = self.window_size, self.ext_size, self.num_heads, self.head_dim
         r = self.chunk_size
         if r is None:
-            raise NotImplementedError("incremental decoding needs --chunk-size (with --num-chunks the chunk length "
-                                      "depends on the final sequence length)")
+            raise NotImplementedError(_NEEDS_CHUNK_SIZE)
+        static = self.get_incremental_state(incremental_state, "attn_static")
+        if static is not None:
+            return self._decode_static(query, key_padding_mask, incremental_state, static)
         dev = query.device
         state = self._get_input_buffer(incremental_state)
         qkv_new = self._project(query, None, None, keep_f32=True)  # [T_new, B, 3, h, d]
@@ -504,6 +618,12 @@ class CausalEVAttention(_ops.DerivedCacheOwner, nn.Module):
 
     def reorder_incremental_state(self, incremental_state, new_order):
         buf = self._get_input_buffer(incremental_state)
+        if buf and self.get_incremental_state(incremental_state, "attn_static") is not None:
+            # a static state reorders IN PLACE: the pointers a captured step holds stay valid, and the reorder can itself
+            # be captured (pos, status and the step-invariant tensors are not per element)
+            for k in _STATIC_BATCH_FIRST:
+                buf[k].copy_(buf[k].index_select(0, new_order))
+            return incremental_state
         if buf:
             for k, t in buf.items():
                 if t is not None:

@@ -939,6 +939,38 @@ int ea_ceva_decode_close(const ea_ceva_dec_geom* g, const ea_t4* q, const ea_t4*
 int ea_ceva_decode_attn(const ea_ceva_dec_geom* g, const ea_t4* q, const ea_t4* k, const ea_t4* v, const uint8_t* pad,
                         const float* bias, const ea_t4* rf_k_bar, const ea_t4* beta, const ea_t4* out, void* stream);
 
+/* ---- causal EVA, static incremental decoding (ABI 18; CausalEVAttention.init_static_decoding) ----------------------------
+ * The same step with the token count in DEVICE memory, so that a step can be captured into a graph and replayed: no
+ * argument of these calls changes from one step to the next.  pos: int32, tokens decoded so far; status: int32, set to 1
+ * by a step that would pass cap (sticky; never cleared by these calls).  cap is a multiple of window, window of chunk.
+ * pad is always given (zeros where nothing is padded).  One step = these four launches, in this order, on one stream:
+ *   ea_ceva_sdecode_append: rows *pos .. *pos + T_new - 1 of the cache qkv [B, cap, 3, H, D] (contiguous, `dtype`) = the
+ *     step's time-first rows qkv_new [T_new, B, 3, H, D] (contiguous, `dtype`); pad [B, cap] at the same columns = new_pad
+ *     [B, T_new] uint8, or 0 when new_pad is NULL.
+ *   ea_ceva_sdecode_close: ea_ceva_decode_close for the chunks those tokens complete.
+ *   ea_ceva_sdecode_attn: ea_ceva_decode_attn for those tokens, t0 = *pos.
+ *   ea_ceva_sdecode_advance: *pos += T_new.
+ * A step with *pos + T_new > cap writes no byte of the cache, the pad or the landmark rows: append sets *status = 1, attn
+ * writes NaN into out, advance leaves *pos. */
+typedef struct {
+  int32_t B, H, D;
+  int32_t dtype;             /* EA_BF16 | EA_F16 | EA_F32: the cache rows and out */
+  int32_t window, ext, chunk;  /* w, e (left extension, 0 or w), r */
+  int32_t T_new;             /* tokens per step: fixed for a captured step */
+  int32_t cap;               /* cache capacity in tokens */
+  int32_t adaptive;          /* 1: 'qk' (Linear + LayerNorm), 0: 'no-ln' (Linear) */
+  int32_t has_bias;
+  const int32_t* pos;        /* device */
+  int32_t* status;           /* device */
+} ea_ceva_sdec_geom;
+int ea_ceva_sdecode_append(const ea_ceva_sdec_geom* g, const void* qkv_new, const uint8_t* new_pad, void* qkv, uint8_t* pad,
+                           void* stream);
+int ea_ceva_sdecode_close(const ea_ceva_sdec_geom* g, const ea_t4* q, const ea_t4* k, const ea_t4* v, const uint8_t* pad,
+                          const float* const* mu_params, const ea_t4* rf_k_bar, const ea_t4* beta, void* stream);
+int ea_ceva_sdecode_attn(const ea_ceva_sdec_geom* g, const ea_t4* q, const ea_t4* k, const ea_t4* v, const uint8_t* pad,
+                         const float* bias, const ea_t4* rf_k_bar, const ea_t4* beta, const ea_t4* out, void* stream);
+int ea_ceva_sdecode_advance(const ea_ceva_sdec_geom* g, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
