@@ -79,7 +79,7 @@ static Geo mk_geo(const ea_geom* g) {
 extern "C" {
 
 const char* ea_version(void) { return "ea_hip 0.1.0 gfx950"; }
-int32_t ea_abi_version(void) { return 18; }
+int32_t ea_abi_version(void) { return 19; }
 
 int32_t ea_window_bias_ld(const ea_geom* g) {
   WinTiling t;
@@ -2156,14 +2156,20 @@ int ea_ceva_decode_attn(const ea_ceva_dec_geom* g, const ea_t4* q, const ea_t4* 
 }  // extern "C"
 
 // static decoding: the geometry of a step whose token count is *g->pos (checked as t0 = 0; the kernels check t0 + T <= cap)
+// ring: 0 (cap rows, linear), or the rows of a rolling state -- a multiple of window that holds one step's span
+static bool sdec_ring_ok(const ea_ceva_sdec_geom* g) {
+  return g->ring == 0 || (g->ring > 0 && g->window > 0 && g->ring % g->window == 0 && g->ext >= 0 && g->T_new > 0 &&
+                          (int64_t)g->ring >= (int64_t)g->window + g->ext + g->T_new);
+}
 static int sdec_fill(const ea_ceva_sdec_geom* g, const ea_t4* q, const ea_t4* k, const ea_t4* v, const uint8_t* pad,
                      const ea_t4* lk, const ea_t4* lv, ea::DecP& p) {
   if (!g || !g->pos || !g->status || (uintptr_t)g->pos % 4 || (uintptr_t)g->status % 4 || !pad || g->window <= 0 ||
-      g->chunk <= 0 || g->cap % g->window || g->window % g->chunk) return EA_E_BADARG;
+      g->chunk <= 0 || g->cap % g->window || g->window % g->chunk || !sdec_ring_ok(g)) return EA_E_BADARG;
   const ea_ceva_dec_geom d = {g->B, g->H, g->D, g->dtype, g->window, g->ext, g->chunk, 0, g->T_new, 0, -1, g->cap,
                               g->adaptive, g->has_bias, 1};
   const int rc = dec_fill(&d, q, k, v, pad, lk, lv, p);
   p.pos = g->pos;
+  p.ring = g->ring;
   return rc;
 }
 
@@ -2173,12 +2179,12 @@ int ea_ceva_sdecode_append(const ea_ceva_sdec_geom* g, const void* qkv_new, cons
                            void* stream) {
   if (!g || !g->pos || !g->status || (uintptr_t)g->pos % 4 || (uintptr_t)g->status % 4 || !pad || !qkv_new || !qkv ||
       (uintptr_t)qkv_new % 16 || (uintptr_t)qkv % 16 || g->B <= 0 || g->H <= 0 || g->T_new <= 0 || g->cap < g->T_new ||
-      (g->dtype != EA_BF16 && g->dtype != EA_F16 && g->dtype != EA_F32)) return EA_E_BADARG;
+      (g->dtype != EA_BF16 && g->dtype != EA_F16 && g->dtype != EA_F32) || !sdec_ring_ok(g)) return EA_E_BADARG;
   if (g->D != 32 && g->D != 64 && g->D != 128) return EA_E_UNSUPPORTED;
   ea::AppP p = {};
   p.src = (const char*)qkv_new; p.src_pad = new_pad; p.cache = (char*)qkv; p.pad = pad;
   p.pos = g->pos; p.status = g->status;
-  p.B = g->B; p.T = g->T_new; p.cap = g->cap;
+  p.B = g->B; p.T = g->T_new; p.cap = g->cap; p.ring = g->ring;
   p.row_bytes = 3 * g->H * g->D * (g->dtype == EA_F32 ? 4 : 2);
   return ea::ceva_sdecode_append(p, (hipStream_t)stream);
 }

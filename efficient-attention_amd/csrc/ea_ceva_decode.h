@@ -11,15 +11,16 @@ struct DecT {                 // [B,H,N,D] view of any I/O type, element strides
 };
 
 struct DecP {
-  DecT q, k, v;               // the cache rows [B,H,cap,D] (dtype)
+  DecT q, k, v;               // the cache rows [B,H,cap,D] (dtype); [B,H,ring,D] when ring != 0
   DecT lk, lv;                // rf_k_bar, beta [B,H,Lcap,D] fp32: read by attn, written by close
   DecT o;                     // attn: out [B,H,T_new,D] (dtype), row t - t0
-  const uint8_t* pad;         // [B,cap] 1 = padded position, or null
+  const uint8_t* pad;         // [B,cap] ([B,ring]) 1 = padded position, or null
   const float* bias;          // [w, w + e] dense single-head bias (natural-log domain), or null
   const float* mu[8];         // close: the mu networks' parameters in _mu_params() order
   int B, H, D, dtype, w, e, r, t0, T, c_first, c_last, cap, adaptive;
   float scale;
   const int32_t* pos;         // static decoding: the token count in device memory (t0, c_first, c_last unused), or null
+  int ring;                   // static decoding: q, k, v and pad hold `ring` rows, token n at row n % ring; 0 = cap rows, linear
 };
 
 struct AppP {                 // static decoding, append: the step's rows into the cache at rows *pos ..
@@ -30,6 +31,7 @@ struct AppP {                 // static decoding, append: the step's rows into t
   const int32_t* pos;
   int32_t* status;            // set to 1 when the step would pass cap (nothing is written)
   int B, T, cap, row_bytes;   // row_bytes = 3 H D element bytes, a multiple of 16
+  int ring;                   // cache and pad hold `ring` rows, token n at row n % ring (cap bounds the step); 0 = cap rows
 };
 
 int ceva_decode_dispatch(bool close, const DecP& p, hipStream_t st);

@@ -20,6 +20,13 @@
 // Static decoding (CausalEVAttention.init_static_decoding; ea_ceva_sdecode_*) runs the same two kernels with DEV = true: the
 // step's first token is read from device memory (*p.pos) instead of a kernel argument, so that a captured step replays at
 // the right position.  ceva_append_kernel writes the step's rows into the cache first, ceva_advance_kernel moves *pos last.
+//
+// Rolling decoding (CausalEVAttention.init_rolling_decoding) is the static step with RING = true: the token rows and pad flags
+// live in a ring of p.ring slots, token n in slot n % ring, while the landmark rows stay linear.  ring is a multiple of w (so
+// of r) and at least w + e + T, so a window block and a chunk never straddle the end of the ring, a local window wraps at
+// most once, and the rows a step appends overwrite only tokens older than the earliest one it reads.  Only addresses change:
+// every test on a token (present, causal, capacity) stays on token indices, and the arithmetic and its order are the static
+// step's.  RING is a template flag, so the dynamic and the linear static kernels compile to what they were.
 #include "ea_common.h"
 #include "ea_ceva_decode.h"
 
@@ -93,11 +100,15 @@ EA_DEV void dot_rows(const char* rp, const float (*qs)[D], float* s) {
 }
 
 // acc[i] += sum over the tile rows j = kg, kg + NKG, .. of p[j][i] v_j[dc .. dc + 3]
-template <typename E, int D>
-EA_DEV void pv_rows(const DecT& t, int b, int h, int n0, int nrows, int kg, int dc, const float (*ps)[QPW], f32x4* acc) {
+// (RING: n0 is a slot of a ring of `ring` rows, and the rows wrap past its end)
+template <typename E, int D, bool RING = false>
+EA_DEV void pv_rows(const DecT& t, int b, int h, int n0, int nrows, int kg, int dc, const float (*ps)[QPW], f32x4* acc,
+                    int ring = 0) {
   constexpr int NKG = 64 / (D / 4);
   for (int j = kg; j < nrows; j += NKG) {
-    const f32x4 v = Io<E>::ld4(row<E>(t, b, h, n0 + j) + (size_t)dc * Io<E>::SZ);
+    int n = n0 + j;
+    if constexpr (RING) n -= n >= ring ? ring : 0;
+    const f32x4 v = Io<E>::ld4(row<E>(t, b, h, n) + (size_t)dc * Io<E>::SZ);
     const f32x4 p0 = *reinterpret_cast<const f32x4*>(&ps[j][0]), p1 = *reinterpret_cast<const f32x4*>(&ps[j][4]);
 #pragma unroll
     for (int i = 0; i < 4; ++i) { acc[i] += p0[i] * v; acc[4 + i] += p1[i] * v; }
@@ -117,10 +128,11 @@ EA_DEV void refuse_out(const DecP& p, int b, int h) {
 
 // DEV = false: t0 is the kernel argument (ea_ceva_decode_attn).  DEV = true: t0 = *p.pos, read from device memory
 // (ea_ceva_sdecode_attn); the grid holds the most window blocks T tokens can touch, and a block this step does not touch
-// exits at once.  The arithmetic is the same in both.
-template <typename E, int D, bool DEV>
+// exits at once.  The arithmetic is the same in both.  RING (with DEV): token n's row and pad flag are at slot n % p.ring.
+template <typename E, int D, bool DEV, bool RING>
 __global__ __launch_bounds__(NT) void ceva_attn_kernel(const DecP p) {
   static_assert(QPW == 8, "pv_rows reads the probabilities of a row as two float4");
+  static_assert(DEV || !RING, "the ring belongs to the static step");
   constexpr int G = D / 4;                         // lanes per value row in P.V
   __shared__ __attribute__((aligned(16))) float qs[NW][QPW][D];
   __shared__ __attribute__((aligned(16))) float ps[NW][KT][QPW];
@@ -141,6 +153,11 @@ __global__ __launch_bounds__(NT) void ceva_attn_kernel(const DecP p) {
   const int Wk = p.w + p.e, nlt = (Wk + KT - 1) / KT;
   const int tend = t0 + p.T;                       // cache rows [0, tend) hold tokens
   const int kbase = bk * p.w - p.e;                // token of local slot 0
+  // RING: the block's first token is at slot qs0 (w divides ring: the block does not straddle), local slot 0 at ks0; the
+  // window spans w + e < ring tokens, so it wraps at most once.  Pad rows are p.ring long.
+  const int qs0 = RING ? (bk * p.w) % p.ring - bk * p.w : 0;       // slot - token for the block's own tokens
+  const int ks0 = RING ? (kbase + qs0 < 0 ? kbase + qs0 + p.ring : kbase + qs0) : 0;
+  const int pst = RING ? p.ring : p.cap;           // row length of pad
   const int kg = lane / G, dc = (lane % G) * 4;
   for (int g = wave / nsplit; g < nqg; g += NW) {
     const int s = wave % nsplit;
@@ -148,14 +165,14 @@ __global__ __launch_bounds__(NT) void ceva_attn_kernel(const DecP p) {
     for (int idx = lane; idx < QPW * (D / 8); idx += 64) {
       const int i = idx / (D / 8), c = (idx - i * (D / 8)) * 8;
       float x[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
-      if (i < nql) Io<E>::ld8(row<E>(p.q, b, h, qa + i) + (size_t)c * Io<E>::SZ, x);
+      if (i < nql) Io<E>::ld8(row<E>(p.q, b, h, qa + i + qs0) + (size_t)c * Io<E>::SZ, x);
       *reinterpret_cast<f32x4*>(&qs[wave][i][c]) = f32x4{x[0], x[1], x[2], x[3]};
       *reinterpret_cast<f32x4*>(&qs[wave][i][c + 4]) = f32x4{x[4], x[5], x[6], x[7]};
     }
     __builtin_amdgcn_wave_barrier();
     bool qpad[QPW];
 #pragma unroll
-    for (int i = 0; i < QPW; ++i) qpad[i] = i < nql && p.pad && p.pad[(size_t)b * p.cap + qa + i];
+    for (int i = 0; i < QPW; ++i) qpad[i] = i < nql && p.pad && p.pad[(size_t)b * pst + qa + i + qs0];
     const int lmax = (qa + nql - 1) / p.r;         // landmark columns of the group's last query
     const int ntile = nlt + (lmax + KT - 1) / KT;
     float m[QPW], l[QPW];
@@ -172,8 +189,10 @@ __global__ __launch_bounds__(NT) void ceva_attn_kernel(const DecP p) {
       if (!lmk) {
         const int tok = kbase + col;
         const bool present = col < Wk && tok >= 0 && tok < tend;
-        if (present) dot_rows<E, D>(row<E>(p.k, b, h, tok), qs[wave], sc);
-        const bool kmask = !present || (p.pad && p.pad[(size_t)b * p.cap + tok]);
+        int sl = tok;                              // the key's row: reduced once per lane and tile
+        if constexpr (RING) { sl = ks0 + col; sl -= sl >= p.ring ? p.ring : 0; }
+        if (present) dot_rows<E, D>(row<E>(p.k, b, h, sl), qs[wave], sc);
+        const bool kmask = !present || (p.pad && p.pad[(size_t)b * pst + sl]);
 #pragma unroll
         for (int i = 0; i < QPW; ++i) {
           const int tq = qa + i;
@@ -200,7 +219,13 @@ __global__ __launch_bounds__(NT) void ceva_attn_kernel(const DecP p) {
       if (!lmk) {
         // rows of absent / not yet decoded tokens: p is zero for every live query, their value rows are not read
         const int j0 = max(0, -(kbase + tile * KT)), j1 = min(KT, min(Wk - tile * KT, tend - (kbase + tile * KT)));
-        if (j1 > j0) pv_rows<E, D>(p.v, b, h, kbase + tile * KT + j0, j1 - j0, kg, dc, &ps[wave][j0], acc);
+        if constexpr (RING) {
+          int n0 = ks0 + tile * KT + j0;
+          n0 -= n0 >= p.ring ? p.ring : 0;
+          if (j1 > j0) pv_rows<E, D, true>(p.v, b, h, n0, j1 - j0, kg, dc, &ps[wave][j0], acc, p.ring);
+        } else {
+          if (j1 > j0) pv_rows<E, D>(p.v, b, h, kbase + tile * KT + j0, j1 - j0, kg, dc, &ps[wave][j0], acc);
+        }
       } else {
         pv_rows<float, D>(p.lv, b, h, (tile - nlt) * KT, min(KT, lmax - (tile - nlt) * KT), kg, dc, ps[wave], acc);
       }
@@ -265,9 +290,11 @@ EA_DEV float block_max(float v, float* red) {
 
 // DEV = false: chunks c_first .. c_last of the kernel arguments (ea_ceva_decode_close).  DEV = true: the chunks that the
 // step's tokens *p.pos .. *p.pos + T - 1 complete (ea_ceva_sdecode_close); the grid holds ceil(T / r), the most T tokens can
-// complete, and a workgroup whose chunk this step does not complete exits at once.
-template <typename E, int D, bool DEV>
+// complete, and a workgroup whose chunk this step does not complete exits at once.  RING (with DEV): the chunk's rows start at
+// slot (c r) % p.ring and do not straddle the end of the ring (r divides ring); its landmark row stays row c.
+template <typename E, int D, bool DEV, bool RING>
 __global__ __launch_bounds__(NT) void ceva_close_kernel(const DecP p) {
+  static_assert(DEV || !RING, "the ring belongs to the static step");
   __shared__ __attribute__((aligned(16))) float xm[2][D];      // chunk means of q, k
   __shared__ __attribute__((aligned(16))) float y[2][D];       // after the Linear layers
   __shared__ __attribute__((aligned(16))) float mu[D];
@@ -281,8 +308,8 @@ __global__ __launch_bounds__(NT) void ceva_close_kernel(const DecP p) {
     if (t0 + p.T > p.cap || c > (t0 + p.T) / p.r - 1) return;
   }
   const int b = (int)blockIdx.y / p.H, h = (int)blockIdx.y - b * p.H;
-  const int n0 = c * p.r;
-  const uint8_t* pad = p.pad ? p.pad + (size_t)b * p.cap + n0 : nullptr;
+  const int n0 = RING ? (c * p.r) % p.ring : c * p.r;          // first row of the chunk
+  const uint8_t* pad = p.pad ? p.pad + (size_t)b * (RING ? p.ring : p.cap) + n0 : nullptr;
   // masked means over the chunk's rows, divided by the chunk length
   if (tid < 2 * D) {
     const int side = tid / D, o = tid - side * D;
@@ -376,7 +403,10 @@ __global__ __launch_bounds__(NT) void ceva_close_kernel(const DecP p) {
 // same count, and each decides from it alone whether the step fits the cache.  A step that does not fit writes no cache
 // byte: append sets *status, close exits, attn writes NaN rows, advance leaves *pos.
 
-// one workgroup per (token t, element b) of the step: the token's [3, H, D] row, 16 bytes per lane and load, and its pad flag
+// one workgroup per (token t, element b) of the step: the token's [3, H, D] row, 16 bytes per lane and load, and its pad flag.
+// RING: the cache and pad hold p.ring rows per element, and each token's slot is reduced on its own (a step may straddle
+// the end of the ring); the capacity test stays on p.cap, the landmark capacity.
+template <bool RING>
 __global__ __launch_bounds__(NT) void ceva_append_kernel(const AppP p) {
   const int t0 = *p.pos;
   const int t = (int)blockIdx.x, b = (int)blockIdx.y;
@@ -385,9 +415,10 @@ __global__ __launch_bounds__(NT) void ceva_append_kernel(const AppP p) {
     return;
   }
   const u32x4* src = reinterpret_cast<const u32x4*>(p.src + ((size_t)t * p.B + b) * p.row_bytes);
-  u32x4* dst = reinterpret_cast<u32x4*>(p.cache + ((size_t)b * p.cap + t0 + t) * p.row_bytes);
+  const size_t at = RING ? (size_t)b * p.ring + (t0 + t) % p.ring : (size_t)b * p.cap + t0 + t;
+  u32x4* dst = reinterpret_cast<u32x4*>(p.cache + at * p.row_bytes);
   for (int i = threadIdx.x; i < p.row_bytes / 16; i += NT) dst[i] = src[i];
-  if (threadIdx.x == 0) p.pad[(size_t)b * p.cap + t0 + t] = p.src_pad ? p.src_pad[(size_t)b * p.T + t] : (uint8_t)0;
+  if (threadIdx.x == 0) p.pad[at] = p.src_pad ? p.src_pad[(size_t)b * p.T + t] : (uint8_t)0;
 }
 
 // *pos += T, in a launch of its own after attn on the same stream: stream order puts it behind every read of *pos in the
@@ -401,50 +432,55 @@ __global__ __launch_bounds__(64) void ceva_advance_kernel(int32_t* pos, int T, i
   }
 }
 
-template <typename E, int D, bool DEV>
+template <typename E, int D, bool DEV, bool RING>
 int launch(bool close, const DecP& p, hipStream_t st) {
   if (close) {
     const unsigned nc = DEV ? (unsigned)((p.T + p.r - 1) / p.r) : (unsigned)(p.c_last - p.c_first + 1);
-    hipLaunchKernelGGL((ceva_close_kernel<E, D, DEV>), dim3(nc, (unsigned)(p.B * p.H)), dim3(NT), 0, st, p);
+    hipLaunchKernelGGL((ceva_close_kernel<E, D, DEV, RING>), dim3(nc, (unsigned)(p.B * p.H)), dim3(NT), 0, st, p);
   } else {
     // DEV: the most window blocks T tokens can touch, wherever they start
     const unsigned nb = DEV ? (unsigned)((p.T + p.w - 2) / p.w + 1) : (unsigned)((p.t0 + p.T - 1) / p.w - p.t0 / p.w + 1);
-    hipLaunchKernelGGL((ceva_attn_kernel<E, D, DEV>), dim3(nb, (unsigned)(p.B * p.H)), dim3(NT), 0, st, p);
+    hipLaunchKernelGGL((ceva_attn_kernel<E, D, DEV, RING>), dim3(nb, (unsigned)(p.B * p.H)), dim3(NT), 0, st, p);
   }
   return (int)hipGetLastError();
 }
 
-template <typename E, bool DEV>
+template <typename E, bool DEV, bool RING>
 int launch_d(bool close, const DecP& p, hipStream_t st) {
   switch (p.D) {
-    case 32: return launch<E, 32, DEV>(close, p, st);
-    case 64: return launch<E, 64, DEV>(close, p, st);
-    default: return launch<E, 128, DEV>(close, p, st);
+    case 32: return launch<E, 32, DEV, RING>(close, p, st);
+    case 64: return launch<E, 64, DEV, RING>(close, p, st);
+    default: return launch<E, 128, DEV, RING>(close, p, st);
   }
 }
 
-template <bool DEV>
+template <bool DEV, bool RING>
 int dispatch(bool close, const DecP& p, hipStream_t st) {
   if (p.D != 32 && p.D != 64 && p.D != 128) return EA_E_UNSUPPORTED;
   switch (p.dtype) {
-    case EA_BF16: return launch_d<BF16, DEV>(close, p, st);
-    case EA_F16: return launch_d<F16, DEV>(close, p, st);
-    case EA_F32: return launch_d<float, DEV>(close, p, st);
+    case EA_BF16: return launch_d<BF16, DEV, RING>(close, p, st);
+    case EA_F16: return launch_d<F16, DEV, RING>(close, p, st);
+    case EA_F32: return launch_d<float, DEV, RING>(close, p, st);
     default: return EA_E_BADARG;
   }
 }
 
 }  // namespace
 
-int ceva_decode_dispatch(bool close, const DecP& p, hipStream_t st) { return dispatch<false>(close, p, st); }
+int ceva_decode_dispatch(bool close, const DecP& p, hipStream_t st) {
+  if (p.ring) return EA_E_BADARG;
+  return dispatch<false, false>(close, p, st);
+}
 
+// (the C entry points have checked the ring: a multiple of w that holds the span of one step, ea_capi.hip sdec_ring_ok)
 int ceva_sdecode_dispatch(bool close, const DecP& p, hipStream_t st) {
   if (!p.pos || !p.pad) return EA_E_BADARG;
-  return dispatch<true>(close, p, st);
+  return p.ring ? dispatch<true, true>(close, p, st) : dispatch<true, false>(close, p, st);
 }
 
 int ceva_sdecode_append(const AppP& p, hipStream_t st) {
-  hipLaunchKernelGGL(ceva_append_kernel, dim3((unsigned)p.T, (unsigned)p.B), dim3(NT), 0, st, p);
+  if (p.ring) hipLaunchKernelGGL(ceva_append_kernel<true>, dim3((unsigned)p.T, (unsigned)p.B), dim3(NT), 0, st, p);
+  else hipLaunchKernelGGL(ceva_append_kernel<false>, dim3((unsigned)p.T, (unsigned)p.B), dim3(NT), 0, st, p);
   return (int)hipGetLastError();
 }
 

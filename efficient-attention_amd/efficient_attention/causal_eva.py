@@ -35,7 +35,9 @@ def _mu_net(d, with_ln):
 
 _NEEDS_CHUNK_SIZE = ("incremental decoding needs --chunk-size (with --num-chunks the chunk length depends on the final "
                      "sequence length)")
-_STATIC_BATCH_FIRST = ("qkv", "rf_k_bar", "beta", "pad")      # the buffers of a static state that a beam reorder permutes
+# the buffers of a static state that a beam reorder permutes; a rolling state has the same (its ring slots are per batch
+# element, the token count `pos` is shared)
+_STATIC_BATCH_FIRST = ("qkv", "rf_k_bar", "beta", "pad")
 
 
 class CausalEVAttention(_ops.DerivedCacheOwner, nn.Module):
@@ -352,6 +354,44 @@ class CausalEVAttention(_ops.DerivedCacheOwner, nn.Module):
                                           capture fixes the weights)
         A step's token count and the batch are fixed for a given capture; the prompt can go through the same state eagerly.
         Refuses what dynamic decoding refuses, with the same messages, and CPU devices (there is no CPU fallback)."""
+        B, T, device = self._check_static_decoding(batch_size, max_tokens, dtype, device)
+        w = self.window_size
+        cap = -(-T // w) * w
+        return self._alloc_static_decoding(incremental_state, B, cap, cap, dtype, device, {"count": 0})
+
+    def init_rolling_decoding(self, incremental_state, batch_size, max_tokens, dtype, device, max_step_tokens=None):
+        """`init_static_decoding` with the token rows in a fixed RING: the state is static in every respect (the same step,
+        capturable and replayable; `static_decoding_overflowed` and the in-place `reorder_incremental_state` work on it), but
+        `qkv` and `pad` hold R token slots instead of one row per token ever decoded, token n in slot n % R:
+            qkv       [B, R, 3, h, d]     `dtype`
+            pad       [B, R]              uint8
+            rf_k_bar  [B, h, cap / r, d]  fp32   } linear, as in the static state: cap = ceil(max_tokens / w) w bounds
+            beta      [B, h, cap / r, d]  fp32   } only the landmark rows (and `pos`)
+            pos, status, bias, mu         as in the static state
+        S = `max_step_tokens` (default w) is the largest step one launch sequence may hold, and R is the smallest multiple
+        of w with R >= w + e + S.  Why that is enough: a step of T <= S tokens that starts at token t0 reads the local keys /
+        values of tokens >= floor(t0 / w) w - e (the window block of its first token with its left extension), the rows of
+        the chunks it closes (inside those blocks, r divides w) and its own rows, and writes rows t0 .. t0 + T - 1.  From
+        the earliest token read to the last one written that is at most (w - 1) + e + S tokens, fewer than R, so the rows it
+        appends overwrite only tokens older than the earliest one it reads.  R does not depend on `max_tokens`.  A ring is
+        never larger than the linear cache would be: with R >= cap the layout is the linear one (R = cap, no wrap).
+        A step with more than S tokens (a prompt) is fed through the ring by the module itself, eagerly, in consecutive
+        pieces of at most S tokens, each an ordinary static step; while a stream is capturing it raises instead.
+        Arithmetic and its order are the static step's: for one sequence of step sizes the outputs equal bit for bit.
+        Refuses what `init_static_decoding` refuses, with the same messages, and `max_step_tokens <= 0`."""
+        B, T, device = self._check_static_decoding(batch_size, max_tokens, dtype, device)
+        w, e = self.window_size, self.ext_size
+        S = w if max_step_tokens is None else int(max_step_tokens)
+        if S <= 0:
+            raise ValueError("rolling decoding needs max_step_tokens > 0, got %d" % S)
+        cap = -(-T // w) * w
+        ring = -(-(w + e + S) // w) * w
+        rows = min(ring, cap)
+        static = {"count": 0, "cap": cap, "ring": ring if ring < cap else 0, "max_step": S}
+        return self._alloc_static_decoding(incremental_state, B, cap, rows, dtype, device, static)
+
+    def _check_static_decoding(self, batch_size, max_tokens, dtype, device):
+        """What a static (or rolling) state refuses, before anything is allocated -> (B, max_tokens, device)."""
         self._refuse_decoding()
         if self.chunk_size is None:
             raise NotImplementedError(_NEEDS_CHUNK_SIZE)
@@ -364,13 +404,16 @@ class CausalEVAttention(_ops.DerivedCacheOwner, nn.Module):
         B, T = int(batch_size), int(max_tokens)
         if B <= 0 or T <= 0:
             raise ValueError("static decoding needs batch_size > 0 and max_tokens > 0, got %d, %d" % (B, T))
+        return B, T, device
+
+    def _alloc_static_decoding(self, incremental_state, B, cap, rows, dtype, device, static):
+        """The buffers of a static state: `rows` token rows (cap, or a ring), cap / r landmark rows."""
         w, e, h, d, r = self.window_size, self.ext_size, self.num_heads, self.head_dim, self.chunk_size
-        cap = -(-T // w) * w
         state = {
-            "qkv": torch.zeros((B, cap, 3, h, d), dtype=dtype, device=device),
+            "qkv": torch.zeros((B, rows, 3, h, d), dtype=dtype, device=device),
             "rf_k_bar": torch.zeros((B, h, cap // r, d), dtype=torch.float32, device=device),
             "beta": torch.zeros((B, h, cap // r, d), dtype=torch.float32, device=device),
-            "pad": torch.zeros((B, cap), dtype=torch.uint8, device=device),
+            "pad": torch.zeros((B, rows), dtype=torch.uint8, device=device),
             "pos": torch.zeros((1,), dtype=torch.int32, device=device),
             "status": torch.zeros((1,), dtype=torch.int32, device=device),
         }
@@ -379,9 +422,21 @@ class CausalEVAttention(_ops.DerivedCacheOwner, nn.Module):
             state["bias"] = self.rel_pos_bias.dense(w, w + e, device)[0].contiguous() if self.use_t5_rpe else None
             state["mu"] = [_ops._f32c(p) for p in self._mu_params()]
         self._set_input_buffer(incremental_state, state)
-        # host side: the shadow count of EAGER steps (a replay advances only the device count), for the eager overflow check
-        self.set_incremental_state(incremental_state, "attn_static", {"count": 0})
+        # host side: the shadow count of EAGER steps (a replay advances only the device count), for the eager overflow check;
+        # a rolling state adds its landmark capacity, its ring length (0: linear rows) and its largest step
+        self.set_incremental_state(incremental_state, "attn_static", static)
         return incremental_state
+
+    def decoding_state_nbytes(self, incremental_state):
+        """Bytes of every tensor in this module's decoding buffer (dynamic, static or rolling): token rows, pad flags,
+        landmark rows, counters and, for a static state, the bias table and the fp32 mu parameters it holds.  Host only."""
+        def nbytes(v):
+            if torch.is_tensor(v):
+                return v.numel() * v.element_size()
+            if isinstance(v, (list, tuple)):
+                return sum(nbytes(x) for x in v)
+            return 0
+        return sum(nbytes(v) for v in self._get_input_buffer(incremental_state).values())
 
     def static_decoding_overflowed(self, incremental_state):
         """True once a step on this static state would have passed its capacity (the step wrote nothing; its outputs are
@@ -392,19 +447,31 @@ class CausalEVAttention(_ops.DerivedCacheOwner, nn.Module):
         """One decoding step on a state of `init_static_decoding`, safe to capture: four launches of the attention core
         (ea_ceva_sdecode_append, _close, _attn, _advance) that read the token count from `pos`, no allocation but the step's
         own outputs, no read-back, no host counter a replay would need.  The arithmetic is `_decode`'s, so the outputs equal
-        its outputs bit for bit."""
+        its outputs bit for bit.  On a state of `init_rolling_decoding` the same four launches address the token rows through
+        the ring, and a step above its `max_step_tokens` is fed in pieces (eager only)."""
         nv = _ops.nv
         T_new, B, C = query.shape
         w, e, h, d, r = self.window_size, self.ext_size, self.num_heads, self.head_dim, self.chunk_size
         state = self._get_input_buffer(incremental_state)
         cache, pad = state["qkv"], state["pad"]
-        cap = cache.shape[1]
+        cap, ring, max_step = static.get("cap", cache.shape[1]), static.get("ring", 0), static.get("max_step")
         if cache.shape[0] != B:
             raise RuntimeError("static decoding state holds batch %d, the step has %d" % (cache.shape[0], B))
         capturing = torch.cuda.is_current_stream_capturing()
         if not capturing and static["count"] + T_new > cap:
             raise RuntimeError("static decoding state is full: %d of its %d tokens decoded, the step adds %d "
-                               "(init_static_decoding(max_tokens=...))" % (static["count"], cap, T_new))
+                               "(%s(max_tokens=...))" % (static["count"], cap, T_new, "init_static_decoding"
+                                                         if max_step is None else "init_rolling_decoding"))
+        if max_step is not None and T_new > max_step:
+            if capturing:
+                raise RuntimeError("a captured step of %d tokens does not fit the rolling decoding state: max_step_tokens "
+                                   "is %d (init_rolling_decoding(max_step_tokens=...))" % (T_new, max_step))
+            # a prompt: consecutive pieces of at most max_step tokens, each an ordinary step; the pad flags of the step
+            # are the last T_new columns in both of fairseq's mask shapes, sliced with the pieces
+            step_pad = None if key_padding_mask is None else key_padding_mask[:, -T_new:]
+            ys = [self._decode_static(query[a:a + max_step], None if step_pad is None else step_pad[:, a:a + max_step],
+                                      incremental_state, static)[0] for a in range(0, T_new, max_step)]
+            return torch.cat(ys, 0), None
         qkv_new = self._project(query, None, None, keep_f32=True)   # [T_new, B, 3, h, d]
         if qkv_new.dtype != cache.dtype:
             # (the dynamic path's rule: an fp32 step on a 16-bit cache rounds with the warning, a 16-bit one on fp32 widens)
@@ -417,9 +484,9 @@ class CausalEVAttention(_ops.DerivedCacheOwner, nn.Module):
         bias = state["bias"]
         io = nv.EA_F32 if cache.dtype == torch.float32 else nv.io_dtype(cache)
         geom = nv.ea_ceva_sdec_geom(B, h, d, io, w, e, r, T_new, cap, 1 if self.adaptive_proj == "qk" else 0,
-                                    0 if bias is None else 1, state["pos"].data_ptr(), state["status"].data_ptr())
+                                    0 if bias is None else 1, ring, state["pos"].data_ptr(), state["status"].data_ptr())
         g = ctypes.byref(geom)
-        tq, tk, tv = [nv.t4(cache[:, :, i].transpose(1, 2)) for i in range(3)]      # [B, h, cap, d] views
+        tq, tk, tv = [nv.t4(cache[:, :, i].transpose(1, 2)) for i in range(3)]      # [B, h, cap (or ring), d] views
         tl, tb = nv.t4(state["rf_k_bar"]), nv.t4(state["beta"])
         mlp = state["mu"]
         mp = (ctypes.c_void_p * len(mlp))(*[p.data_ptr() for p in mlp])

@@ -939,7 +939,7 @@ int ea_ceva_decode_close(const ea_ceva_dec_geom* g, const ea_t4* q, const ea_t4*
 int ea_ceva_decode_attn(const ea_ceva_dec_geom* g, const ea_t4* q, const ea_t4* k, const ea_t4* v, const uint8_t* pad,
                         const float* bias, const ea_t4* rf_k_bar, const ea_t4* beta, const ea_t4* out, void* stream);
 
-/* ---- causal EVA, static incremental decoding (ABI 18; CausalEVAttention.init_static_decoding) ----------------------------
+/* ---- causal EVA, static incremental decoding (ABI 18; CausalEVAttention.init_static_decoding; ABI 19: ring) --------------
  * The same step with the token count in DEVICE memory, so that a step can be captured into a graph and replayed: no
  * argument of these calls changes from one step to the next.  pos: int32, tokens decoded so far; status: int32, set to 1
  * by a step that would pass cap (sticky; never cleared by these calls).  cap is a multiple of window, window of chunk.
@@ -951,15 +951,22 @@ int ea_ceva_decode_attn(const ea_ceva_dec_geom* g, const ea_t4* q, const ea_t4* 
  *   ea_ceva_sdecode_attn: ea_ceva_decode_attn for those tokens, t0 = *pos.
  *   ea_ceva_sdecode_advance: *pos += T_new.
  * A step with *pos + T_new > cap writes no byte of the cache, the pad or the landmark rows: append sets *status = 1, attn
- * writes NaN into out, advance leaves *pos. */
+ * writes NaN into out, advance leaves *pos.
+ * ABI 19, ring != 0 (CausalEVAttention.init_rolling_decoding): the token rows live in a ring.  qkv is [B, ring, 3, H, D], q, k, v
+ * address it as [B, H, ring, D], pad is [B, ring], and token n is at row n % ring; rf_k_bar and beta stay linear
+ * [B, H, cap / chunk, D], and cap bounds only them and *pos.  ring is a multiple of window with ring >= window + ext + T_new
+ * (else EA_E_BADARG): a step at *pos reads back to token floor(*pos / window) window - ext and appends up to *pos + T_new - 1,
+ * at most window - 1 + ext + T_new < ring tokens, so the rows it appends replace only tokens older than any it reads.  The
+ * arithmetic is that of ring = 0: for one sequence of step sizes the outputs and landmark rows are equal bit for bit. */
 typedef struct {
   int32_t B, H, D;
   int32_t dtype;             /* EA_BF16 | EA_F16 | EA_F32: the cache rows and out */
   int32_t window, ext, chunk;  /* w, e (left extension, 0 or w), r */
   int32_t T_new;             /* tokens per step: fixed for a captured step */
-  int32_t cap;               /* cache capacity in tokens */
+  int32_t cap;               /* cache capacity in tokens (ring != 0: of the landmark rows, cap / chunk of them) */
   int32_t adaptive;          /* 1: 'qk' (Linear + LayerNorm), 0: 'no-ln' (Linear) */
   int32_t has_bias;
+  int32_t ring;              /* 0: qkv and pad hold cap rows; else they hold ring rows, token n at row n % ring */
   const int32_t* pos;        /* device */
   int32_t* status;           /* device */
 } ea_ceva_sdec_geom;

@@ -1,11 +1,16 @@
 """Per-token latency of CausalEVAttention decoding at the wikitext-103 LM geometry (embed 1024, h 8, d 128, w 128, chunks of 8,
-T5 bias, adaptive 'qk'), 16 stacked residual attention layers (x + attn(x), no FFN), bf16 autocast, in three modes:
- - dynamic: the incremental state of `_decode` (host token count, two decode launches per layer step);
- - static:  `init_static_decoding`, the same step run eagerly (four decode launches per layer step);
- - graph:   that static step over all 16 layers captured once with torch.cuda.graph and replayed.
-   python tools/ceva_decode_latency.py [--context 512] [--steps 64]   (GPU)
-A 1-token step after a prefill of `context` tokens; a warm-up, then the median over 5 blocks of `steps` tokens, each block
-timed by the host clock around its steps and a device synchronise.  The rows of the three modes are compared (bitwise)."""
+T5 bias, adaptive 'qk'), 16 stacked residual attention layers (x + attn(x), no FFN), bf16 autocast, in five modes:
+ - dynamic:       the incremental state of `_decode` (host token count, two decode launches per layer step);
+ - static:        `init_static_decoding`, the same step run eagerly (four decode launches per layer step);
+ - graph:         that static step over all 16 layers captured once with torch.cuda.graph and replayed;
+ - rolling:       `init_rolling_decoding`, the static step on a state whose token rows live in a ring, eager;
+ - rolling-graph: that step captured and replayed.
+   python tools/ceva_decode_latency.py [--context 512] [--steps 64] [--modes dynamic,static,graph,rolling,rolling-graph]   (GPU)
+A 1-token step after a prefill of `context` tokens, fed in pieces of one window (the largest step of a rolling state) in
+every mode, so that all modes run one sequence of step sizes; a warm-up, then the median over 5 blocks of `steps` tokens,
+each block timed by the host clock around its steps and a device synchronise.  The rows of the modes are compared (bitwise)
+with those of the first mode, and the bytes of one layer's decoding state at `context` tokens are printed for the static and
+the rolling state (`decoding_state_nbytes`: allocation sizes); `--state-bytes 512,4096,32768` prints only those."""
 import argparse
 import os
 import sys
@@ -45,15 +50,18 @@ def run(mods, mode, B, context, steps, blocks=5, warmup=4):
     for m in mods:
         st = {}
         m.init_incremental_state()
-        if mode != "dynamic":
+        if mode in ("static", "graph"):
             m.init_static_decoding(st, B, n_tok, torch.bfloat16, "cuda")
+        elif mode in ("rolling", "rolling-graph"):
+            m.init_rolling_decoding(st, B, n_tok, torch.bfloat16, "cuda")
         states.append(st)
     rows, times = [], []
     with torch.no_grad(), torch.autocast("cuda", dtype=torch.bfloat16, cache_enabled=False):
-        step(mods, states, x[:context])
+        for a in range(0, context, RECIPE["window_size"]):
+            step(mods, states, x[a:min(a + RECIPE["window_size"], context)])
         t = context
         xin = x[t:t + 1].clone()
-        if mode == "graph":
+        if mode.endswith("graph"):
             s = torch.cuda.Stream()
             s.wait_stream(torch.cuda.current_stream())
             with torch.cuda.stream(s):
@@ -87,19 +95,47 @@ def run(mods, mode, B, context, steps, blocks=5, warmup=4):
     return sorted(times)[len(times) // 2], torch.cat(rows, 0)
 
 
+MODES = ("dynamic", "static", "graph", "rolling", "rolling-graph")
+
+
+def state_bytes(m, B, context):
+    """decoding_state_nbytes of one layer with room for `context` tokens -> (static, rolling)."""
+    out = []
+    for init in (m.init_static_decoding, m.init_rolling_decoding):
+        st = {}
+        init(st, B, context, torch.bfloat16, "cuda")
+        out.append(m.decoding_state_nbytes(st))
+    return tuple(out)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--context", type=int, default=512)
     ap.add_argument("--steps", type=int, default=64)
+    ap.add_argument("--modes", default=",".join(MODES))
+    ap.add_argument("--state-bytes", default=None, metavar="CONTEXTS",
+                    help="only print the state sizes at these comma-separated contexts (batch 1), no timing")
     a = ap.parse_args()
+    if a.state_bytes:
+        m = build()[0]
+        for ctx in [int(c) for c in a.state_bytes.split(",")]:
+            sb, rb = state_bytes(m, 1, ctx)
+            print("decoding_state_nbytes per layer, %d tokens, batch 1: static %d, rolling %d" % (ctx, sb, rb), flush=True)
+        return
+    modes = [m for m in a.modes.split(",") if m]
+    if [m for m in modes if m not in MODES]:
+        ap.error("--modes: a comma-separated subset of %s" % (MODES,))
     mods = build()
     print("ms per token, %d layers, bf16, context %d" % (LAYERS, a.context))
-    print("%3s %10s %10s %10s  %s" % ("B", "dynamic", "static", "graph", "rows equal (static, graph vs dynamic)"))
+    print("%3s " % "B" + " ".join("%13s" % m for m in modes) + "  rows equal (%s vs %s)" % (", ".join(modes[1:]), modes[0]))
     for B in (1, 8):
-        res = {mode: run(mods, mode, B, a.context, a.steps) for mode in ("dynamic", "static", "graph")}
-        ref = res["dynamic"][1]
-        same = [torch.equal(res[mode][1], ref) for mode in ("static", "graph")]
-        print("%3d %10.3f %10.3f %10.3f  %s" % (B, res["dynamic"][0], res["static"][0], res["graph"][0], same), flush=True)
+        res = {mode: run(mods, mode, B, a.context, a.steps) for mode in modes}
+        ref = res[modes[0]][1]
+        same = [torch.equal(res[mode][1], ref) for mode in modes[1:]]
+        print("%3d " % B + " ".join("%13.3f" % res[m][0] for m in modes) + "  %s" % same, flush=True)
+        sb, rb = state_bytes(mods[0], B, a.context)
+        print("    decoding_state_nbytes per layer, %d tokens, batch %d: static %d, rolling %d" % (a.context, B, sb, rb),
+              flush=True)
 
 
 if __name__ == "__main__":
