@@ -2108,79 +2108,95 @@ static ea::DecT dec_mk(const ea_t4* t) {
   r.p = (const char*)t->ptr; r.sb = t->sb; r.sh = t->sh; r.sn = t->sn;
   return r;
 }
-static int dec_fill(const ea_ceva_dec_geom* g, const ea_t4* q, const ea_t4* k, const ea_t4* v, const uint8_t* pad,
-                    const ea_t4* lk, const ea_t4* lv, ea::DecP& p) {
-  if (!g || g->B <= 0 || g->H <= 0 || g->window <= 0 || g->chunk <= 0 || g->ext < 0 || g->t0 < 0 || g->T_new <= 0 ||
-      g->cap < g->t0 + g->T_new || (g->dtype != EA_BF16 && g->dtype != EA_F16 && g->dtype != EA_F32)) return EA_E_BADARG;
-  if (g->D != 32 && g->D != 64 && g->D != 128) return EA_E_UNSUPPORTED;
-  const int esz = g->dtype == EA_F32 ? 4 : 2;
-  if (!dec_t4_ok(q, g->D, esz) || !dec_t4_ok(k, g->D, esz) || !dec_t4_ok(v, g->D, esz)) return EA_E_BADARG;
-  if (!dec_t4_ok(lk, g->D, 4) || !dec_t4_ok(lv, g->D, 4) || (g->has_mask && !pad)) return EA_E_BADARG;
-  p.q = dec_mk(q); p.k = dec_mk(k); p.v = dec_mk(v); p.lk = dec_mk(lk); p.lv = dec_mk(lv);
-  p.pad = g->has_mask ? pad : nullptr;
-  p.B = g->B; p.H = g->H; p.D = g->D; p.dtype = g->dtype; p.w = g->window; p.e = g->ext; p.r = g->chunk;
-  p.t0 = g->t0; p.T = g->T_new; p.c_first = g->c_first; p.c_last = g->c_last; p.cap = g->cap; p.adaptive = g->adaptive ? 1 : 0;
-  p.scale = (float)(1.0 / sqrt((double)g->D));
+// A step's geometry as both families hand it over.  Dynamic (ea_ceva_dec_geom): the host knows t0 and which chunks close.
+// Static (ea_ceva_sdec_geom, dev): the count is *pos, so the host can check only that a step fits an empty cache (t0 = 0; the
+// kernels check t0 + T <= cap), no chunk range is given, the pad flags are always read, and ring is 0 (cap rows, linear) or
+// the rows of a rolling state -- a multiple of window that holds one step's span.
+struct DecG {
+  int B, H, D, dtype, window, ext, chunk, t0, T_new, c_first, c_last, cap, adaptive, has_bias, has_mask, ring;
+  const int32_t* pos;
+  int32_t* status;
+  bool dev;
+};
+static DecG dec_read(const ea_ceva_dec_geom* g) {
+  return {g->B, g->H, g->D, g->dtype, g->window, g->ext, g->chunk, g->t0, g->T_new, g->c_first, g->c_last, g->cap,
+          g->adaptive, g->has_bias, g->has_mask, 0, nullptr, nullptr, false};
+}
+static DecG dec_read(const ea_ceva_sdec_geom* g) {
+  return {g->B, g->H, g->D, g->dtype, g->window, g->ext, g->chunk, 0, g->T_new, 0, -1, g->cap,
+          g->adaptive, g->has_bias, 1, g->ring, g->pos, g->status, true};
+}
+// What every launch of a step needs; with `windows`, also what close and attn need of the window geometry (append moves
+// rows and reads none of it).  Every EA_E_BADARG is decided before the head dim, the static state's own before the rest.
+static int dec_check(const DecG& g, const uint8_t* pad, bool windows) {
+  if (g.dev && (!g.pos || !g.status || (uintptr_t)g.pos % 4 || (uintptr_t)g.status % 4 || !pad)) return EA_E_BADARG;
+  if (windows && (g.window <= 0 || g.chunk <= 0 || g.ext < 0 || (g.dev && (g.cap % g.window || g.window % g.chunk))))
+    return EA_E_BADARG;
+  if (g.ring != 0 && !(g.ring > 0 && g.window > 0 && g.ring % g.window == 0 && g.ext >= 0 && g.T_new > 0 &&
+                       (int64_t)g.ring >= (int64_t)g.window + g.ext + g.T_new)) return EA_E_BADARG;
+  if (g.B <= 0 || g.H <= 0 || g.t0 < 0 || g.T_new <= 0 || g.cap < g.t0 + g.T_new ||
+      (g.dtype != EA_BF16 && g.dtype != EA_F16 && g.dtype != EA_F32)) return EA_E_BADARG;
+  if (g.D != 32 && g.D != 64 && g.D != 128) return EA_E_UNSUPPORTED;
   return EA_OK;
+}
+static int dec_fill(const DecG& g, const ea_t4* q, const ea_t4* k, const ea_t4* v, const uint8_t* pad, const ea_t4* lk,
+                    const ea_t4* lv, ea::DecP& p) {
+  const int rc = dec_check(g, pad, true);
+  if (rc != EA_OK) return rc;
+  const int esz = g.dtype == EA_F32 ? 4 : 2;
+  if (!dec_t4_ok(q, g.D, esz) || !dec_t4_ok(k, g.D, esz) || !dec_t4_ok(v, g.D, esz)) return EA_E_BADARG;
+  if (!dec_t4_ok(lk, g.D, 4) || !dec_t4_ok(lv, g.D, 4) || (g.has_mask && !pad)) return EA_E_BADARG;
+  p.q = dec_mk(q); p.k = dec_mk(k); p.v = dec_mk(v); p.lk = dec_mk(lk); p.lv = dec_mk(lv);
+  p.pad = g.has_mask ? pad : nullptr;
+  p.B = g.B; p.H = g.H; p.D = g.D; p.dtype = g.dtype; p.w = g.window; p.e = g.ext; p.r = g.chunk;
+  p.t0 = g.t0; p.T = g.T_new; p.c_first = g.c_first; p.c_last = g.c_last; p.cap = g.cap; p.adaptive = g.adaptive ? 1 : 0;
+  p.scale = (float)(1.0 / sqrt((double)g.D));
+  p.pos = g.pos; p.ring = g.ring;
+  return EA_OK;
+}
+static int dec_close(const DecG& g, const ea_t4* q, const ea_t4* k, const ea_t4* v, const uint8_t* pad,
+                     const float* const* mu_params, const ea_t4* lk, const ea_t4* lv, void* stream) {
+  ea::DecP p = {};
+  const int rc = dec_fill(g, q, k, v, pad, lk, lv, p);
+  if (rc != EA_OK) return rc;
+  // dynamic: the chunks must be decoded, rows [c_first r, (c_last + 1) r) lie in [0, t0 + T_new)
+  if (!mu_params || (!g.dev && (g.c_first < 0 || g.c_last < g.c_first || (int64_t)(g.c_last + 1) * g.chunk > g.t0 + g.T_new)))
+    return EA_E_BADARG;
+  const int np = g.adaptive ? 8 : 4;
+  for (int i = 0; i < np; ++i) {
+    if (!mu_params[i] || (uintptr_t)mu_params[i] % 16) return EA_E_BADARG;
+    p.mu[i] = mu_params[i];
+  }
+  return ea::ceva_decode_launch(ea::DEC_CLOSE, p, (hipStream_t)stream);
+}
+static int dec_attn(const DecG& g, const ea_t4* q, const ea_t4* k, const ea_t4* v, const uint8_t* pad, const float* bias,
+                    const ea_t4* lk, const ea_t4* lv, const ea_t4* out, void* stream) {
+  ea::DecP p = {};
+  const int rc = dec_fill(g, q, k, v, pad, lk, lv, p);
+  if (rc != EA_OK) return rc;
+  if (!dec_t4_ok(out, g.D, g.dtype == EA_F32 ? 4 : 2) || (g.has_bias && !bias)) return EA_E_BADARG;
+  p.o = dec_mk(out);
+  p.bias = g.has_bias ? bias : nullptr;
+  return ea::ceva_decode_launch(ea::DEC_ATTN, p, (hipStream_t)stream);
 }
 
 extern "C" {
 
 int ea_ceva_decode_close(const ea_ceva_dec_geom* g, const ea_t4* q, const ea_t4* k, const ea_t4* v, const uint8_t* pad,
                          const float* const* mu_params, const ea_t4* rf_k_bar, const ea_t4* beta, void* stream) {
-  ea::DecP p = {};
-  const int rc = dec_fill(g, q, k, v, pad, rf_k_bar, beta, p);
-  if (rc != EA_OK) return rc;
-  // the chunks must be decoded: rows [c_first r, (c_last + 1) r) lie in [0, t0 + T_new)
-  if (!mu_params || g->c_first < 0 || g->c_last < g->c_first || (int64_t)(g->c_last + 1) * g->chunk > g->t0 + g->T_new)
-    return EA_E_BADARG;
-  const int np = g->adaptive ? 8 : 4;
-  for (int i = 0; i < np; ++i) {
-    if (!mu_params[i] || (uintptr_t)mu_params[i] % 16) return EA_E_BADARG;
-    p.mu[i] = mu_params[i];
-  }
-  return ea::ceva_decode_dispatch(true, p, (hipStream_t)stream);
+  return g ? dec_close(dec_read(g), q, k, v, pad, mu_params, rf_k_bar, beta, stream) : EA_E_BADARG;
 }
 
 int ea_ceva_decode_attn(const ea_ceva_dec_geom* g, const ea_t4* q, const ea_t4* k, const ea_t4* v, const uint8_t* pad,
                         const float* bias, const ea_t4* rf_k_bar, const ea_t4* beta, const ea_t4* out, void* stream) {
-  ea::DecP p = {};
-  const int rc = dec_fill(g, q, k, v, pad, rf_k_bar, beta, p);
-  if (rc != EA_OK) return rc;
-  if (!dec_t4_ok(out, g->D, g->dtype == EA_F32 ? 4 : 2) || (g->has_bias && !bias)) return EA_E_BADARG;
-  p.o = dec_mk(out);
-  p.bias = g->has_bias ? bias : nullptr;
-  return ea::ceva_decode_dispatch(false, p, (hipStream_t)stream);
+  return g ? dec_attn(dec_read(g), q, k, v, pad, bias, rf_k_bar, beta, out, stream) : EA_E_BADARG;
 }
-
-}  // extern "C"
-
-// static decoding: the geometry of a step whose token count is *g->pos (checked as t0 = 0; the kernels check t0 + T <= cap)
-// ring: 0 (cap rows, linear), or the rows of a rolling state -- a multiple of window that holds one step's span
-static bool sdec_ring_ok(const ea_ceva_sdec_geom* g) {
-  return g->ring == 0 || (g->ring > 0 && g->window > 0 && g->ring % g->window == 0 && g->ext >= 0 && g->T_new > 0 &&
-                          (int64_t)g->ring >= (int64_t)g->window + g->ext + g->T_new);
-}
-static int sdec_fill(const ea_ceva_sdec_geom* g, const ea_t4* q, const ea_t4* k, const ea_t4* v, const uint8_t* pad,
-                     const ea_t4* lk, const ea_t4* lv, ea::DecP& p) {
-  if (!g || !g->pos || !g->status || (uintptr_t)g->pos % 4 || (uintptr_t)g->status % 4 || !pad || g->window <= 0 ||
-      g->chunk <= 0 || g->cap % g->window || g->window % g->chunk || !sdec_ring_ok(g)) return EA_E_BADARG;
-  const ea_ceva_dec_geom d = {g->B, g->H, g->D, g->dtype, g->window, g->ext, g->chunk, 0, g->T_new, 0, -1, g->cap,
-                              g->adaptive, g->has_bias, 1};
-  const int rc = dec_fill(&d, q, k, v, pad, lk, lv, p);
-  p.pos = g->pos;
-  p.ring = g->ring;
-  return rc;
-}
-
-extern "C" {
 
 int ea_ceva_sdecode_append(const ea_ceva_sdec_geom* g, const void* qkv_new, const uint8_t* new_pad, void* qkv, uint8_t* pad,
                            void* stream) {
-  if (!g || !g->pos || !g->status || (uintptr_t)g->pos % 4 || (uintptr_t)g->status % 4 || !pad || !qkv_new || !qkv ||
-      (uintptr_t)qkv_new % 16 || (uintptr_t)qkv % 16 || g->B <= 0 || g->H <= 0 || g->T_new <= 0 || g->cap < g->T_new ||
-      (g->dtype != EA_BF16 && g->dtype != EA_F16 && g->dtype != EA_F32) || !sdec_ring_ok(g)) return EA_E_BADARG;
-  if (g->D != 32 && g->D != 64 && g->D != 128) return EA_E_UNSUPPORTED;
+  if (!g || !qkv_new || !qkv || (uintptr_t)qkv_new % 16 || (uintptr_t)qkv % 16) return EA_E_BADARG;
+  const int rc = dec_check(dec_read(g), pad, false);
+  if (rc != EA_OK) return rc;
   ea::AppP p = {};
   p.src = (const char*)qkv_new; p.src_pad = new_pad; p.cache = (char*)qkv; p.pad = pad;
   p.pos = g->pos; p.status = g->status;
@@ -2191,27 +2207,12 @@ int ea_ceva_sdecode_append(const ea_ceva_sdec_geom* g, const void* qkv_new, cons
 
 int ea_ceva_sdecode_close(const ea_ceva_sdec_geom* g, const ea_t4* q, const ea_t4* k, const ea_t4* v, const uint8_t* pad,
                           const float* const* mu_params, const ea_t4* rf_k_bar, const ea_t4* beta, void* stream) {
-  ea::DecP p = {};
-  const int rc = sdec_fill(g, q, k, v, pad, rf_k_bar, beta, p);
-  if (rc != EA_OK) return rc;
-  if (!mu_params) return EA_E_BADARG;
-  const int np = g->adaptive ? 8 : 4;
-  for (int i = 0; i < np; ++i) {
-    if (!mu_params[i] || (uintptr_t)mu_params[i] % 16) return EA_E_BADARG;
-    p.mu[i] = mu_params[i];
-  }
-  return ea::ceva_sdecode_dispatch(true, p, (hipStream_t)stream);
+  return g ? dec_close(dec_read(g), q, k, v, pad, mu_params, rf_k_bar, beta, stream) : EA_E_BADARG;
 }
 
 int ea_ceva_sdecode_attn(const ea_ceva_sdec_geom* g, const ea_t4* q, const ea_t4* k, const ea_t4* v, const uint8_t* pad,
                          const float* bias, const ea_t4* rf_k_bar, const ea_t4* beta, const ea_t4* out, void* stream) {
-  ea::DecP p = {};
-  const int rc = sdec_fill(g, q, k, v, pad, rf_k_bar, beta, p);
-  if (rc != EA_OK) return rc;
-  if (!dec_t4_ok(out, g->D, g->dtype == EA_F32 ? 4 : 2) || (g->has_bias && !bias)) return EA_E_BADARG;
-  p.o = dec_mk(out);
-  p.bias = g->has_bias ? bias : nullptr;
-  return ea::ceva_sdecode_dispatch(false, p, (hipStream_t)stream);
+  return g ? dec_attn(dec_read(g), q, k, v, pad, bias, rf_k_bar, beta, out, stream) : EA_E_BADARG;
 }
 
 int ea_ceva_sdecode_advance(const ea_ceva_sdec_geom* g, void* stream) {

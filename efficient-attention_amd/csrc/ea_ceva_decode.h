@@ -34,8 +34,9 @@ struct AppP {                 // static decoding, append: the step's rows into t
   int ring;                   // cache and pad hold `ring` rows, token n at row n % ring (cap bounds the step); 0 = cap rows
 };
 
-int ceva_decode_dispatch(bool close, const DecP& p, hipStream_t st);
-int ceva_sdecode_dispatch(bool close, const DecP& p, hipStream_t st);
+enum DecKind { DEC_CLOSE, DEC_ATTN };
+// the step's close or attn launch; p.pos != null: t0 = *p.pos (needs p.pad); p.ring != 0: ring rows (needs p.pos)
+int ceva_decode_launch(DecKind kind, const DecP& p, hipStream_t st);
 int ceva_sdecode_append(const AppP& p, hipStream_t st);
 int ceva_sdecode_advance(int32_t* pos, int T, int cap, hipStream_t st);
 

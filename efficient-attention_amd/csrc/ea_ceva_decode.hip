@@ -17,16 +17,19 @@
 // G = D / 4 lanes per value row for P.V.  A wave owns up to QPW queries; when the step holds fewer query groups than
 // waves, the waves split the tiles of each group and merge their (max, sum, acc) partials in LDS.
 //
-// Static decoding (CausalEVAttention.init_static_decoding; ea_ceva_sdecode_*) runs the same two kernels with DEV = true: the
-// step's first token is read from device memory (*p.pos) instead of a kernel argument, so that a captured step replays at
-// the right position.  ceva_append_kernel writes the step's rows into the cache first, ceva_advance_kernel moves *pos last.
-//
-// Rolling decoding (CausalEVAttention.init_rolling_decoding) is the static step with RING = true: the token rows and pad flags
-// live in a ring of p.ring slots, token n in slot n % ring, while the landmark rows stay linear.  ring is a multiple of w (so
-// of r) and at least w + e + T, so a window block and a chunk never straddle the end of the ring, a local window wraps at
-// most once, and the rows a step appends overwrite only tokens older than the earliest one it reads.  Only addresses change:
-// every test on a token (present, causal, capacity) stays on token indices, and the arithmetic and its order are the static
-// step's.  RING is a template flag, so the dynamic and the linear static kernels compile to what they were.
+// A decoding step is append -> close -> attn -> advance over a state (efficient_attention/_ceva_decode.py), and the state
+// sets two switches, both template flags of the kernels, so that every combination compiles to its own straight-line code:
+//   DEV  (p.pos != null): where the step starts.  false: t0 is a kernel argument, the host has grown the cache, written the
+//        step's rows and decided which chunks close (ea_ceva_decode_*: close and attn only).  true: t0 = *p.pos in device
+//        memory, so that a captured step replays at the right position (ea_ceva_sdecode_*): ceva_append_kernel writes the
+//        step's rows first, ceva_advance_kernel moves *pos last, the grids hold the most a step of T tokens can need and a
+//        workgroup the step does not need exits at once.  `Step` reads the start; nothing else reads *pos.
+//   RING (p.ring != 0, with DEV): how a token index becomes a row of q / k / v / pad.  false: token n is row n of cap rows.
+//        true: slot n % ring of a ring of p.ring rows, the landmark rows staying linear.  ring is a multiple of w (so of r)
+//        and at least w + e + T, so a window block and a chunk never straddle the end of the ring, a local window wraps at
+//        most once, and the rows a step appends overwrite only tokens older than the earliest one it reads.  Only addresses
+//        change: every test on a token (present, causal, capacity) stays on token indices, and the arithmetic and its order
+//        are the linear step's.  `Rows` owns the mapping; no kernel spells it.
 #include "ea_common.h"
 #include "ea_ceva_decode.h"
 
@@ -75,6 +78,28 @@ template <typename E> EA_DEV const char* row(const DecT& t, int b, int h, int n)
   return t.p + ((size_t)b * t.sb + (size_t)h * t.sh + (size_t)n * t.sn) * Io<E>::SZ;
 }
 
+// Token index -> row of q / k / v / pad.  RING = false: the identity, every member folds away.  RING = true: slot
+// n % ring.  A kernel reduces once (`slot` of its first token) and then walks: a run of fewer than `ring` rows that starts
+// at a slot passes the end of the ring at most once (`wrap`), and one that starts up to `ring` rows before a slot falls
+// before slot 0 at most once (`unwrap`).
+template <bool RING> struct Rows {
+  int ring;
+  EA_DEV int slot(int n) const { return RING ? n % ring : n; }                     // n >= 0
+  EA_DEV size_t slot(int n, int j) const { return RING ? (size_t)((n + j) % ring) : (size_t)n + j; }
+  EA_DEV int wrap(int s) const { return RING ? s - (s >= ring ? ring : 0) : s; }   // 0 <= s < 2 ring
+  EA_DEV int unwrap(int s) const { return RING && s < 0 ? s + ring : s; }          // -ring <= s < ring
+  EA_DEV int len(int cap) const { return RING ? ring : cap; }                      // rows per batch element (of pad)
+};
+
+// Where the step starts, and whether it fits the cache.  DEV = false: the kernel argument (the host has checked the
+// capacity: `fits` is true and folds away).  DEV = true: the token count in device memory -- one value for every thread of
+// the step's launches up to advance, so every exit decided from it is uniform.
+template <bool DEV> struct Step {
+  int t0;
+  EA_DEV Step(const int32_t* pos, int arg_t0) : t0(DEV ? *pos : arg_t0) {}
+  EA_DEV bool fits(int T, int cap) const { return !DEV || t0 + T <= cap; }
+};
+
 EA_DEV float wave_max(float v) {
 #pragma unroll
   for (int o = 32; o > 0; o >>= 1) v = fmaxf(v, __shfl_xor(v, o));
@@ -99,16 +124,13 @@ EA_DEV void dot_rows(const char* rp, const float (*qs)[D], float* s) {
   }
 }
 
-// acc[i] += sum over the tile rows j = kg, kg + NKG, .. of p[j][i] v_j[dc .. dc + 3]
-// (RING: n0 is a slot of a ring of `ring` rows, and the rows wrap past its end)
-template <typename E, int D, bool RING = false>
-EA_DEV void pv_rows(const DecT& t, int b, int h, int n0, int nrows, int kg, int dc, const float (*ps)[QPW], f32x4* acc,
-                    int ring = 0) {
+// acc[i] += sum over the tile rows j = kg, kg + NKG, .. of p[j][i] v_j[dc .. dc + 3], v_j at row rows.wrap(n0 + j)
+template <typename E, int D, bool RING>
+EA_DEV void pv_rows(Rows<RING> rows, const DecT& t, int b, int h, int n0, int nrows, int kg, int dc, const float (*ps)[QPW],
+                    f32x4* acc) {
   constexpr int NKG = 64 / (D / 4);
   for (int j = kg; j < nrows; j += NKG) {
-    int n = n0 + j;
-    if constexpr (RING) n -= n >= ring ? ring : 0;
-    const f32x4 v = Io<E>::ld4(row<E>(t, b, h, n) + (size_t)dc * Io<E>::SZ);
+    const f32x4 v = Io<E>::ld4(row<E>(t, b, h, rows.wrap(n0 + j)) + (size_t)dc * Io<E>::SZ);
     const f32x4 p0 = *reinterpret_cast<const f32x4*>(&ps[j][0]), p1 = *reinterpret_cast<const f32x4*>(&ps[j][4]);
 #pragma unroll
     for (int i = 0; i < 4; ++i) { acc[i] += p0[i] * v; acc[4 + i] += p1[i] * v; }
@@ -126,9 +148,8 @@ EA_DEV void refuse_out(const DecP& p, int b, int h) {
   }
 }
 
-// DEV = false: t0 is the kernel argument (ea_ceva_decode_attn).  DEV = true: t0 = *p.pos, read from device memory
-// (ea_ceva_sdecode_attn); the grid holds the most window blocks T tokens can touch, and a block this step does not touch
-// exits at once.  The arithmetic is the same in both.  RING (with DEV): token n's row and pad flag are at slot n % p.ring.
+// One workgroup per window block of the step.  DEV: the grid holds the most window blocks T tokens can touch, and a block
+// this step does not touch exits at once; a step that does not fit writes NaN rows.
 template <typename E, int D, bool DEV, bool RING>
 __global__ __launch_bounds__(NT) void ceva_attn_kernel(const DecP p) {
   static_assert(QPW == 8, "pv_rows reads the probabilities of a row as two float4");
@@ -140,24 +161,23 @@ __global__ __launch_bounds__(NT) void ceva_attn_kernel(const DecP p) {
   __shared__ float ml[NW][QPW][2];
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int b = (int)blockIdx.y / p.H, h = (int)blockIdx.y - b * p.H;
-  int t0 = p.t0;
-  if constexpr (DEV) {
-    t0 = *p.pos;                                   // (one value for every thread: the exits below are uniform)
-    if (t0 + p.T > p.cap) { refuse_out<E, D>(p, b, h); return; }
-    if ((t0 / p.w + (int)blockIdx.x) * p.w >= t0 + p.T) return;
-  }
+  const Step<DEV> step(p.pos, p.t0);
+  const int t0 = step.t0;
+  if (!step.fits(p.T, p.cap)) { refuse_out<E, D>(p, b, h); return; }
   const int bk = t0 / p.w + (int)blockIdx.x;
+  if (DEV && bk * p.w >= t0 + p.T) return;
   const int tq0 = max(t0, bk * p.w), tq1 = min(t0 + p.T, (bk + 1) * p.w);
   const int nqg = (tq1 - tq0 + QPW - 1) / QPW;
   const int nsplit = nqg >= NW ? 1 : NW / nqg;     // waves per query group
   const int Wk = p.w + p.e, nlt = (Wk + KT - 1) / KT;
   const int tend = t0 + p.T;                       // cache rows [0, tend) hold tokens
   const int kbase = bk * p.w - p.e;                // token of local slot 0
-  // RING: the block's first token is at slot qs0 (w divides ring: the block does not straddle), local slot 0 at ks0; the
-  // window spans w + e < ring tokens, so it wraps at most once.  Pad rows are p.ring long.
-  const int qs0 = RING ? (bk * p.w) % p.ring - bk * p.w : 0;       // slot - token for the block's own tokens
-  const int ks0 = RING ? (kbase + qs0 < 0 ? kbase + qs0 + p.ring : kbase + qs0) : 0;
-  const int pst = RING ? p.ring : p.cap;           // row length of pad
+  // the block's own tokens do not straddle the end of a ring (w divides it): row = token + qs0.  Local slot 0 is row ks0,
+  // up to e < ring rows before them, and the window spans w + e < ring rows from there: it wraps at most once.
+  const Rows<RING> rows{p.ring};
+  const int qs0 = rows.slot(bk * p.w) - bk * p.w;
+  const int ks0 = rows.unwrap(kbase + qs0);
+  const int pst = rows.len(p.cap);                 // row length of pad
   const int kg = lane / G, dc = (lane % G) * 4;
   for (int g = wave / nsplit; g < nqg; g += NW) {
     const int s = wave % nsplit;
@@ -189,8 +209,7 @@ __global__ __launch_bounds__(NT) void ceva_attn_kernel(const DecP p) {
       if (!lmk) {
         const int tok = kbase + col;
         const bool present = col < Wk && tok >= 0 && tok < tend;
-        int sl = tok;                              // the key's row: reduced once per lane and tile
-        if constexpr (RING) { sl = ks0 + col; sl -= sl >= p.ring ? p.ring : 0; }
+        const int sl = rows.wrap(ks0 + col);       // the key's row: reduced once per lane and tile
         if (present) dot_rows<E, D>(row<E>(p.k, b, h, sl), qs[wave], sc);
         const bool kmask = !present || (p.pad && p.pad[(size_t)b * pst + sl]);
 #pragma unroll
@@ -219,15 +238,9 @@ __global__ __launch_bounds__(NT) void ceva_attn_kernel(const DecP p) {
       if (!lmk) {
         // rows of absent / not yet decoded tokens: p is zero for every live query, their value rows are not read
         const int j0 = max(0, -(kbase + tile * KT)), j1 = min(KT, min(Wk - tile * KT, tend - (kbase + tile * KT)));
-        if constexpr (RING) {
-          int n0 = ks0 + tile * KT + j0;
-          n0 -= n0 >= p.ring ? p.ring : 0;
-          if (j1 > j0) pv_rows<E, D, true>(p.v, b, h, n0, j1 - j0, kg, dc, &ps[wave][j0], acc, p.ring);
-        } else {
-          if (j1 > j0) pv_rows<E, D>(p.v, b, h, kbase + tile * KT + j0, j1 - j0, kg, dc, &ps[wave][j0], acc);
-        }
+        if (j1 > j0) pv_rows<E, D>(rows, p.v, b, h, rows.wrap(ks0 + tile * KT + j0), j1 - j0, kg, dc, &ps[wave][j0], acc);
       } else {
-        pv_rows<float, D>(p.lv, b, h, (tile - nlt) * KT, min(KT, lmax - (tile - nlt) * KT), kg, dc, ps[wave], acc);
+        pv_rows<float, D>(Rows<false>{}, p.lv, b, h, (tile - nlt) * KT, min(KT, lmax - (tile - nlt) * KT), kg, dc, ps[wave], acc);
       }
       __builtin_amdgcn_wave_barrier();
     }
@@ -288,10 +301,10 @@ EA_DEV float block_max(float v, float* red) {
   return r;
 }
 
-// DEV = false: chunks c_first .. c_last of the kernel arguments (ea_ceva_decode_close).  DEV = true: the chunks that the
-// step's tokens *p.pos .. *p.pos + T - 1 complete (ea_ceva_sdecode_close); the grid holds ceil(T / r), the most T tokens can
-// complete, and a workgroup whose chunk this step does not complete exits at once.  RING (with DEV): the chunk's rows start at
-// slot (c r) % p.ring and do not straddle the end of the ring (r divides ring); its landmark row stays row c.
+// One workgroup per chunk the step completes: c_first .. c_last of the kernel arguments, or (DEV) the chunks that tokens
+// t0 .. t0 + T - 1 complete; then the grid holds ceil(T / r), the most T tokens can complete, and a workgroup whose chunk
+// this step does not complete exits at once.  The chunk's rows do not straddle the end of a ring (r divides it); its
+// landmark row is row c.
 template <typename E, int D, bool DEV, bool RING>
 __global__ __launch_bounds__(NT) void ceva_close_kernel(const DecP p) {
   static_assert(DEV || !RING, "the ring belongs to the static step");
@@ -301,15 +314,13 @@ __global__ __launch_bounds__(NT) void ceva_close_kernel(const DecP p) {
   __shared__ float pt[NT];                                      // probabilities of the current row tile
   __shared__ float red[NW];
   const int tid = threadIdx.x;
-  int c = p.c_first + (int)blockIdx.x;
-  if constexpr (DEV) {
-    const int t0 = *p.pos;
-    c = t0 / p.r + (int)blockIdx.x;
-    if (t0 + p.T > p.cap || c > (t0 + p.T) / p.r - 1) return;
-  }
+  const Step<DEV> step(p.pos, p.t0);
+  const int c = (DEV ? step.t0 / p.r : p.c_first) + (int)blockIdx.x;
+  if (DEV && (!step.fits(p.T, p.cap) || c > (step.t0 + p.T) / p.r - 1)) return;
   const int b = (int)blockIdx.y / p.H, h = (int)blockIdx.y - b * p.H;
-  const int n0 = RING ? (c * p.r) % p.ring : c * p.r;          // first row of the chunk
-  const uint8_t* pad = p.pad ? p.pad + (size_t)b * (RING ? p.ring : p.cap) + n0 : nullptr;
+  const Rows<RING> rows{p.ring};
+  const int n0 = rows.slot(c * p.r);                           // first row of the chunk
+  const uint8_t* pad = p.pad ? p.pad + (size_t)b * rows.len(p.cap) + n0 : nullptr;
   // masked means over the chunk's rows, divided by the chunk length
   if (tid < 2 * D) {
     const int side = tid / D, o = tid - side * D;
@@ -398,24 +409,25 @@ __global__ __launch_bounds__(NT) void ceva_close_kernel(const DecP p) {
   if (tid < D) const_cast<float*>(reinterpret_cast<const float*>(row<float>(p.lv, b, h, c)))[tid] = acc / lrun;
 }
 
-// ---- static decoding (ea_ceva_sdecode_*): the token count lives in device memory --------------------------------------
+// ---- DEV steps: the token count lives in device memory -----------------------------------------------------------------
 // A step is append -> close -> attn -> advance on one stream.  Only advance writes *pos, so the three before it read the
 // same count, and each decides from it alone whether the step fits the cache.  A step that does not fit writes no cache
 // byte: append sets *status, close exits, attn writes NaN rows, advance leaves *pos.
 
 // one workgroup per (token t, element b) of the step: the token's [3, H, D] row, 16 bytes per lane and load, and its pad flag.
-// RING: the cache and pad hold p.ring rows per element, and each token's slot is reduced on its own (a step may straddle
-// the end of the ring); the capacity test stays on p.cap, the landmark capacity.
+// Each token's row is reduced on its own (a step may straddle the end of a ring); the capacity test stays on p.cap, the
+// landmark capacity.
 template <bool RING>
 __global__ __launch_bounds__(NT) void ceva_append_kernel(const AppP p) {
-  const int t0 = *p.pos;
+  const Step<true> step(p.pos, 0);
   const int t = (int)blockIdx.x, b = (int)blockIdx.y;
-  if (t0 + p.T > p.cap) {
+  if (!step.fits(p.T, p.cap)) {
     if (t == 0 && b == 0 && threadIdx.x == 0) *p.status = 1;
     return;
   }
   const u32x4* src = reinterpret_cast<const u32x4*>(p.src + ((size_t)t * p.B + b) * p.row_bytes);
-  const size_t at = RING ? (size_t)b * p.ring + (t0 + t) % p.ring : (size_t)b * p.cap + t0 + t;
+  const Rows<RING> rows{p.ring};
+  const size_t at = (size_t)b * rows.len(p.cap) + rows.slot(step.t0, t);
   u32x4* dst = reinterpret_cast<u32x4*>(p.cache + at * p.row_bytes);
   for (int i = threadIdx.x; i < p.row_bytes / 16; i += NT) dst[i] = src[i];
   if (threadIdx.x == 0) p.pad[at] = p.src_pad ? p.src_pad[(size_t)b * p.T + t] : (uint8_t)0;
@@ -427,60 +439,54 @@ __global__ __launch_bounds__(NT) void ceva_append_kernel(const AppP p) {
 // 1.5 us, eager or in a graph, and leaves no ordering to get wrong.)
 __global__ __launch_bounds__(64) void ceva_advance_kernel(int32_t* pos, int T, int cap) {
   if (threadIdx.x == 0) {
-    const int t0 = *pos;
-    if (t0 + T <= cap) *pos = t0 + T;
+    const Step<true> step(pos, 0);
+    if (step.fits(T, cap)) *pos = step.t0 + T;
   }
 }
 
-template <typename E, int D, bool DEV, bool RING>
-int launch(bool close, const DecP& p, hipStream_t st) {
-  if (close) {
-    const unsigned nc = DEV ? (unsigned)((p.T + p.r - 1) / p.r) : (unsigned)(p.c_last - p.c_first + 1);
-    hipLaunchKernelGGL((ceva_close_kernel<E, D, DEV, RING>), dim3(nc, (unsigned)(p.B * p.H)), dim3(NT), 0, st, p);
-  } else {
-    // DEV: the most window blocks T tokens can touch, wherever they start
-    const unsigned nb = DEV ? (unsigned)((p.T + p.w - 2) / p.w + 1) : (unsigned)((p.t0 + p.T - 1) / p.w - p.t0 / p.w + 1);
-    hipLaunchKernelGGL((ceva_attn_kernel<E, D, DEV, RING>), dim3(nb, (unsigned)(p.B * p.H)), dim3(NT), 0, st, p);
-  }
-  return (int)hipGetLastError();
+using DecKernel = void (*)(const DecP);
+
+template <typename E, int D>
+DecKernel kernel_of(DecKind kind, bool dev, bool ring) {
+  if (kind == DEC_CLOSE)
+    return !dev ? ceva_close_kernel<E, D, false, false> : ring ? ceva_close_kernel<E, D, true, true> : ceva_close_kernel<E, D, true, false>;
+  return !dev ? ceva_attn_kernel<E, D, false, false> : ring ? ceva_attn_kernel<E, D, true, true> : ceva_attn_kernel<E, D, true, false>;
 }
 
-template <typename E, bool DEV, bool RING>
-int launch_d(bool close, const DecP& p, hipStream_t st) {
-  switch (p.D) {
-    case 32: return launch<E, 32, DEV, RING>(close, p, st);
-    case 64: return launch<E, 64, DEV, RING>(close, p, st);
-    default: return launch<E, 128, DEV, RING>(close, p, st);
-  }
-}
-
-template <bool DEV, bool RING>
-int dispatch(bool close, const DecP& p, hipStream_t st) {
-  if (p.D != 32 && p.D != 64 && p.D != 128) return EA_E_UNSUPPORTED;
-  switch (p.dtype) {
-    case EA_BF16: return launch_d<BF16, DEV, RING>(close, p, st);
-    case EA_F16: return launch_d<F16, DEV, RING>(close, p, st);
-    case EA_F32: return launch_d<float, DEV, RING>(close, p, st);
-    default: return EA_E_BADARG;
+template <typename E>
+DecKernel kernel_of(int D, DecKind kind, bool dev, bool ring) {
+  switch (D) {
+    case 32: return kernel_of<E, 32>(kind, dev, ring);
+    case 64: return kernel_of<E, 64>(kind, dev, ring);
+    default: return kernel_of<E, 128>(kind, dev, ring);
   }
 }
 
 }  // namespace
 
-int ceva_decode_dispatch(bool close, const DecP& p, hipStream_t st) {
-  if (p.ring) return EA_E_BADARG;
-  return dispatch<false, false>(close, p, st);
-}
-
-// (the C entry points have checked the ring: a multiple of w that holds the span of one step, ea_capi.hip sdec_ring_ok)
-int ceva_sdecode_dispatch(bool close, const DecP& p, hipStream_t st) {
-  if (!p.pos || !p.pad) return EA_E_BADARG;
-  return p.ring ? dispatch<true, true>(close, p, st) : dispatch<true, false>(close, p, st);
+// DEV / RING follow the state: p.pos != null / p.ring != 0.  (The C entry points have checked the ring: a multiple of w
+// that holds the span of one step, ea_capi.hip.)
+int ceva_decode_launch(DecKind kind, const DecP& p, hipStream_t st) {
+  const bool dev = p.pos != nullptr, ring = p.ring != 0;
+  if (dev ? !p.pad : ring) return EA_E_BADARG;     // a DEV step always reads the pad flags; a ring belongs to a DEV step
+  if (p.D != 32 && p.D != 64 && p.D != 128) return EA_E_UNSUPPORTED;
+  DecKernel kernel;
+  switch (p.dtype) {
+    case EA_BF16: kernel = kernel_of<BF16>(p.D, kind, dev, ring); break;
+    case EA_F16: kernel = kernel_of<F16>(p.D, kind, dev, ring); break;
+    case EA_F32: kernel = kernel_of<float>(p.D, kind, dev, ring); break;
+    default: return EA_E_BADARG;
+  }
+  // x: the chunks the step closes / the window blocks it touches; DEV: the most T tokens can, wherever they start
+  const int nx = kind == DEC_CLOSE ? (dev ? (p.T + p.r - 1) / p.r : p.c_last - p.c_first + 1)
+                                   : (dev ? (p.T + p.w - 2) / p.w + 1 : (p.t0 + p.T - 1) / p.w - p.t0 / p.w + 1);
+  hipLaunchKernelGGL(kernel, dim3((unsigned)nx, (unsigned)(p.B * p.H)), dim3(NT), 0, st, p);
+  return (int)hipGetLastError();
 }
 
 int ceva_sdecode_append(const AppP& p, hipStream_t st) {
-  if (p.ring) hipLaunchKernelGGL(ceva_append_kernel<true>, dim3((unsigned)p.T, (unsigned)p.B), dim3(NT), 0, st, p);
-  else hipLaunchKernelGGL(ceva_append_kernel<false>, dim3((unsigned)p.T, (unsigned)p.B), dim3(NT), 0, st, p);
+  hipLaunchKernelGGL(p.ring ? ceva_append_kernel<true> : ceva_append_kernel<false>, dim3((unsigned)p.T, (unsigned)p.B), dim3(NT),
+                     0, st, p);
   return (int)hipGetLastError();
 }
 

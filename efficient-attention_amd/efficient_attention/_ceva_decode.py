@@ -1,0 +1,353 @@
+"""Incremental decoding of `CausalEVAttention` (reference causal_eva.py:537-665), as a mixin of the module.
+
+A decoding step is append, close, attn, advance over a STATE, and the state says where the step starts and how a token
+index becomes a cache row (csrc/ea_ceva_decode.hip).  There is one step body, `_decode`; the three kinds of state differ in
+
+                      dynamic (fairseq's, grown on demand)     static / rolling (`init_*_decoding`, capturable)
+    makes room        grow + slice-assign, on the host          ea_ceva_sdecode_append
+    bias, fp32 mu     the module's DerivedCaches                the copies taken at init (a capture fixes the weights)
+    entry points      ea_ceva_decode_* (t0, chunks from host)   ea_ceva_sdecode_* (t0 = *pos on the device)
+    close             skipped when no chunk completes           always launched (its workgroups decide)
+    count             host `attn_pos`, tensor `pos`             ea_ceva_sdecode_advance (+ host shadow, eager only)
+
+and in nothing else.
+"""
+import ctypes
+
+import torch
+
+from . import _ops
+from . import _f32
+
+_NEEDS_CHUNK_SIZE = ("incremental decoding needs --chunk-size (with --num-chunks the chunk length depends on the final "
+                     "sequence length)")
+# the buffers of a static state that a beam reorder permutes; a rolling state has the same (its ring slots are per batch
+# element, the token count `pos` is shared)
+_STATIC_BATCH_FIRST = ("qkv", "rf_k_bar", "beta", "pad")
+
+
+class CevaDecoding:
+    def _refuse_decoding(self):
+        """The cases incremental decoding does not define, dynamic and static state alike."""
+        if not self.self_attention:
+            raise NotImplementedError("incremental decoding of encoder-decoder attention")
+        if not self.causal:
+            raise NotImplementedError("incremental decoding needs --causal: without the causal masks every query of the "
+                                      "training path sees the landmarks of future chunks (causal_eva.py:716-738)")
+        if self.training:
+            raise NotImplementedError("incremental decoding in training mode")
+        if self.adaptive_proj not in ("qk", "no-ln"):
+            raise NotImplementedError("Other adaptive projection methods are not implemented yet.")
+
+    # ---- what a step reads besides the cache: built here for both kinds of state ---------------------------------------
+    def _decode_bias_table(self, device):
+        """The dense single-head [w, w + e] T5 table (already scaled), or None."""
+        if not self.use_t5_rpe:
+            return None
+        return self.rel_pos_bias.dense(self.window_size, self.window_size + self.ext_size, device)[0].contiguous()
+
+    def _decode_mu_f32(self):
+        """The close kernel reads fp32 parameters: fp32 masters pass through, a module converted with .half() / .bfloat16()
+        (fairseq's 16-bit generation) hands over fp32 copies, as the full path's _f32c does."""
+        return [_ops._f32c(p) for p in self._mu_params()]
+
+    # ---- static and rolling states ----------------------------------------------------------------------------------------
+    def init_static_decoding(self, incremental_state, batch_size, max_tokens, dtype, device):
+        """Allocate, once, every buffer a decoding step touches and mark this module's incremental state as STATIC: every
+        later `forward(..., incremental_state=incremental_state)` then runs a step that can be captured into a graph
+        (`torch.cuda.graph`) and replayed -- the token count lives in device memory and the kernels advance it: four
+        launches of the attention core (ea_ceva_sdecode_append, _close, _attn, _advance) that read the token count from
+        `pos`, no allocation but the step's own outputs, no read-back, no host counter a replay would need.  The arithmetic
+        is the dynamic step's, so the outputs equal its outputs bit for bit.
+        State, allocated here (cap = ceil(max_tokens / w) w):
+            qkv       [B, cap, 3, h, d]   `dtype` (bf16, fp16, or fp32 when the fp32 cores are enabled)
+            rf_k_bar  [B, h, cap / r, d]  fp32
+            beta      [B, h, cap / r, d]  fp32
+            pad       [B, cap]            uint8, zeros
+            pos       [1]                 int32 on the device: tokens decoded so far
+            status    [1]                 int32 on the device: 1 once a step would have passed cap
+            bias, mu                      the dense T5 table and fp32 copies of the mu parameters, built here once (a
+                                          capture fixes the weights)
+        A step's token count and the batch are fixed for a given capture; the prompt can go through the same state eagerly.
+        Refuses what dynamic decoding refuses, with the same messages, and CPU devices (there is no CPU fallback)."""
+        B, T, device = self._check_static_decoding(batch_size, max_tokens, dtype, device)
+        w = self.window_size
+        cap = -(-T // w) * w
+        return self._alloc_static_decoding(incremental_state, B, cap, cap, dtype, device, {"count": 0})
+
+    def init_rolling_decoding(self, incremental_state, batch_size, max_tokens, dtype, device, max_step_tokens=None):
+        """`init_static_decoding` with the token rows in a fixed RING: the state is static in every respect (the same step,
+        capturable and replayable; `static_decoding_overflowed` and the in-place `reorder_incremental_state` work on it), but
+        `qkv` and `pad` hold R token slots instead of one row per token ever decoded, token n in slot n % R:
+            qkv       [B, R, 3, h, d]     `dtype`
+            pad       [B, R]              uint8
+            rf_k_bar  [B, h, cap / r, d]  fp32   } linear, as in the static state: cap = ceil(max_tokens / w) w bounds
+            beta      [B, h, cap / r, d]  fp32   } only the landmark rows (and `pos`)
+            pos, status, bias, mu         as in the static state
+        S = `max_step_tokens` (default w) is the largest step one launch sequence may hold, and R is the smallest multiple
+        of w with R >= w + e + S.  Why that is enough: a step of T <= S tokens that starts at token t0 reads the local keys /
+        values of tokens >= floor(t0 / w) w - e (the window block of its first token with its left extension), the rows of
+        the chunks it closes (inside those blocks, r divides w) and its own rows, and writes rows t0 .. t0 + T - 1.  From
+        the earliest token read to the last one written that is at most (w - 1) + e + S tokens, fewer than R, so the rows it
+        appends overwrite only tokens older than the earliest one it reads.  R does not depend on `max_tokens`.  A ring is
+        never larger than the linear cache would be: with R >= cap the layout is the linear one (R = cap, no wrap).
+        A step with more than S tokens (a prompt) is fed through the ring by the module itself, eagerly, in consecutive
+        pieces of at most S tokens, each an ordinary static step; while a stream is capturing it raises instead.
+        Arithmetic and its order are the static step's: for one sequence of step sizes the outputs equal bit for bit.
+        Refuses what `init_static_decoding` refuses, with the same messages, and `max_step_tokens <= 0`."""
+        B, T, device = self._check_static_decoding(batch_size, max_tokens, dtype, device)
+        w, e = self.window_size, self.ext_size
+        S = w if max_step_tokens is None else int(max_step_tokens)
+        if S <= 0:
+            raise ValueError("rolling decoding needs max_step_tokens > 0, got %d" % S)
+        cap = -(-T // w) * w
+        ring = -(-(w + e + S) // w) * w
+        rows = min(ring, cap)
+        static = {"count": 0, "cap": cap, "ring": ring if ring < cap else 0, "max_step": S}
+        return self._alloc_static_decoding(incremental_state, B, cap, rows, dtype, device, static)
+
+    def _check_static_decoding(self, batch_size, max_tokens, dtype, device):
+        """What a static (or rolling) state refuses, before anything is allocated -> (B, max_tokens, device)."""
+        self._refuse_decoding()
+        if self.chunk_size is None:
+            raise NotImplementedError(_NEEDS_CHUNK_SIZE)
+        if dtype not in (torch.bfloat16, torch.float16, torch.float32):
+            raise ValueError("static decoding caches bf16, fp16 or fp32 rows, not %s" % (dtype,))
+        if dtype == torch.float32 and not _f32.ENABLED:
+            raise ValueError("an fp32 static decoding cache needs the fp32 cores (EA_F32_CORES=1)")
+        device = torch.device(device)
+        _ops.nv.require_cuda(torch.empty(0, device=device), "the static decoding state")
+        B, T = int(batch_size), int(max_tokens)
+        if B <= 0 or T <= 0:
+            raise ValueError("static decoding needs batch_size > 0 and max_tokens > 0, got %d, %d" % (B, T))
+        return B, T, device
+
+    def _alloc_static_decoding(self, incremental_state, B, cap, rows, dtype, device, static):
+        """The buffers of a static state: `rows` token rows (cap, or a ring), cap / r landmark rows."""
+        h, d, r = self.num_heads, self.head_dim, self.chunk_size
+        state = {
+            "qkv": torch.zeros((B, rows, 3, h, d), dtype=dtype, device=device),
+            "rf_k_bar": torch.zeros((B, h, cap // r, d), dtype=torch.float32, device=device),
+            "beta": torch.zeros((B, h, cap // r, d), dtype=torch.float32, device=device),
+            "pad": torch.zeros((B, rows), dtype=torch.uint8, device=device),
+            "pos": torch.zeros((1,), dtype=torch.int32, device=device),
+            "status": torch.zeros((1,), dtype=torch.int32, device=device),
+        }
+        with torch.no_grad():
+            state["bias"] = self._decode_bias_table(device)
+            state["mu"] = self._decode_mu_f32()
+        self._set_input_buffer(incremental_state, state)
+        # host side: the shadow count of EAGER steps (a replay advances only the device count), for the eager overflow check;
+        # a rolling state adds its landmark capacity, its ring length (0: linear rows) and its largest step
+        self.set_incremental_state(incremental_state, "attn_static", static)
+        return incremental_state
+
+    def decoding_state_nbytes(self, incremental_state):
+        """Bytes of every tensor in this module's decoding buffer (dynamic, static or rolling): token rows, pad flags,
+        landmark rows, counters and, for a static state, the bias table and the fp32 mu parameters it holds.  Host only."""
+        def nbytes(v):
+            if torch.is_tensor(v):
+                return v.numel() * v.element_size()
+            if isinstance(v, (list, tuple)):
+                return sum(nbytes(x) for x in v)
+            return 0
+        return sum(nbytes(v) for v in self._get_input_buffer(incremental_state).values())
+
+    def static_decoding_overflowed(self, incremental_state):
+        """True once a step on this static state would have passed its capacity (the step wrote nothing; its outputs are
+        NaN).  Reads the device flag back: call it after a replay, not inside a captured step."""
+        return bool(self._get_input_buffer(incremental_state)["status"].item())
+
+    def reorder_incremental_state(self, incremental_state, new_order):
+        buf = self._get_input_buffer(incremental_state)
+        if buf and self.get_incremental_state(incremental_state, "attn_static") is not None:
+            # a static state reorders IN PLACE: the pointers a captured step holds stay valid, and the reorder can itself
+            # be captured (pos, status and the step-invariant tensors are not per element)
+            for k in _STATIC_BATCH_FIRST:
+                buf[k].copy_(buf[k].index_select(0, new_order))
+            return incremental_state
+        if buf:
+            for k, t in buf.items():
+                if t is not None:
+                    buf[k] = t.index_select(0, new_order)
+            incremental_state = self._set_input_buffer(incremental_state, buf)
+        return incremental_state
+
+    # ---- how each kind of state makes room for a step -------------------------------------------------------------------------
+    def _static_room(self, state, static, T_new, B):
+        """A static step's host checks -> (capturing, pieces): `pieces` is the piece length when a rolling state must be fed
+        the step in consecutive pieces (a prompt above its `max_step_tokens`; eager only), else None."""
+        cache = state["qkv"]
+        cap, max_step = static.get("cap", cache.shape[1]), static.get("max_step")
+        if cache.shape[0] != B:
+            raise RuntimeError("static decoding state holds batch %d, the step has %d" % (cache.shape[0], B))
+        capturing = torch.cuda.is_current_stream_capturing()
+        if not capturing and static["count"] + T_new > cap:
+            raise RuntimeError("static decoding state is full: %d of its %d tokens decoded, the step adds %d "
+                               "(%s(max_tokens=...))" % (static["count"], cap, T_new, "init_static_decoding"
+                                                         if max_step is None else "init_rolling_decoding"))
+        if max_step is None or T_new <= max_step:
+            return capturing, None
+        if capturing:
+            raise RuntimeError("a captured step of %d tokens does not fit the rolling decoding state: max_step_tokens "
+                               "is %d (init_rolling_decoding(max_step_tokens=...))" % (T_new, max_step))
+        return capturing, max_step
+
+    def _dynamic_room(self, incremental_state, state, dtype, B, T_new, dev):
+        """The dynamic state: created by the first step (which fixes the cache's dtype), doubled when the step passes it
+        -> t0.  The token count also lives on the host, under its own key of the incremental state -- reading `pos` back
+        would synchronise every step, and reorder_incremental_state only touches the tensors of the buffer."""
+        w, h, d, r = self.window_size, self.num_heads, self.head_dim, self.chunk_size
+        if "qkv" not in state:
+            cap = max(2 * w, 64)
+            state["qkv"] = torch.zeros((B, cap, 3, h, d), dtype=dtype, device=dev)
+            lcap = max(cap // r, 1)
+            state["rf_k_bar"] = torch.zeros((B, h, lcap, d), dtype=torch.float32, device=dev)
+            state["beta"] = torch.zeros((B, h, lcap, d), dtype=torch.float32, device=dev)
+            state["pos"] = torch.zeros((B,), dtype=torch.long, device=dev)
+            state["pad"] = torch.zeros((B, cap), dtype=torch.uint8, device=dev)
+            self.set_incremental_state(incremental_state, "attn_pos", 0)
+            self.set_incremental_state(incremental_state, "attn_has_pad", False)
+        t0 = int(self.get_incremental_state(incremental_state, "attn_pos") or 0)
+        if state["qkv"].shape[0] != B:
+            raise RuntimeError("incremental state holds batch %d, the step has %d" % (state["qkv"].shape[0], B))
+        need = ((t0 + T_new + w - 1) // w) * w
+        if need > state["qkv"].shape[1]:
+            cap = max(need, 2 * state["qkv"].shape[1])
+
+            def grown(t, dim, n):                                  # zeros, n long in `dim`, that start with t
+                g = torch.zeros(t.shape[:dim] + (n,) + t.shape[dim + 1:], dtype=t.dtype, device=dev)
+                g.narrow(dim, 0, t.shape[dim]).copy_(t)
+                return g
+            state["qkv"], state["pad"] = grown(state["qkv"], 1, cap), grown(state["pad"], 1, cap)
+            state["rf_k_bar"], state["beta"] = grown(state["rf_k_bar"], 2, cap // r), grown(state["beta"], 2, cap // r)
+        return t0
+
+    # ---- the step -------------------------------------------------------------------------------------------------------------
+    def _decode(self, query, key_padding_mask, incremental_state):
+        """Token-by-token decoding with fairseq's incremental state.
+
+        The reference's branch for this (causal_eva.py:537-665) cannot run as shipped -- `N` and `B` are bound only when
+        `incremental_state is None` (:503-509), so any call with a state raises -- and what it sketches (a sliding window of
+        the last `window_size` keys) would not agree with the module's own training path (block windows with a left
+        extension).  This build therefore defines decoding by PREFIX CONSISTENCY with the pinned full-sequence path: the
+        output for token t equals row t of `forward()` on the tokens 0..t (tests/test_gpu_causal_eva.py).  The dynamic
+        state, all batch-first so that `reorder_incremental_state` can index it:
+            qkv       [B, cap, 3, h, d]   projected rows of every token so far (16-bit, or fp32 outside autocast; the
+                                          window needs the last w + e, a chunk its own rows)
+            rf_k_bar  [B, h, Lcap, d]     fp32, the landmark keys of the COMPLETED chunks (:588-634)
+            beta      [B, h, Lcap, d]     fp32, their control variates
+            pos       [B]                 tokens decoded so far
+            pad       [B, cap]            uint8, 1 = padded position (`key_padding_mask`, e.g. left-padded prompts of a batch):
+                                          handed to the kernels exactly as the full path hands them its mask -- a padded key
+                                          is invisible, a padded query sees no local key, a chunk's means skip its padded rows
+        A step projects its tokens (fp32 stays fp32 outside autocast when the fp32 cores are usable: the cache dtype is fixed by
+        the first step, a later step of another dtype is cast to it), writes them into the cache, closes every chunk its tokens
+        complete with ONE close launch (chunk means -> mu networks -> beta, on the module's fp32 mu parameters) and produces
+        the outputs of all its tokens with ONE attn launch (each token against its block window [left extension, block] and
+        the landmarks of the chunks before its own, masked after itself).  Both kernels compute in fp32 on rows of the
+        cache's dtype, so fp32 decoding equals the fp32 full path; on a dynamic state which chunks close is decided on the
+        host from the token count, with no read-back.  No limit on the context length or the number of landmarks.
+        A state made by `init_static_decoding` / `init_rolling_decoding` (docstrings there) takes the same step with the
+        right-hand column of this module's table; on a rolling state the launches address the token rows through the ring."""
+        nv = _ops.nv
+        self._refuse_decoding()
+        nv.require_cuda(query, "query")                            # (before any state is built: no CPU fallback)
+        T_new, B, C = query.shape
+        if key_padding_mask is not None:
+            # fairseq hands the decoder either the flags of the new positions [B, T_new] or of every position so far
+            # [B, t0 + T_new] (`self_attn_padding_mask`): the last T_new columns are this step's in both cases
+            if key_padding_mask.dim() != 2 or key_padding_mask.shape[0] != B or key_padding_mask.shape[1] < T_new:
+                raise ValueError("key_padding_mask %s does not cover the %d new positions of a batch of %d"
+                                 % (tuple(key_padding_mask.shape), T_new, B))
+        w, e, h, d, r = self.window_size, self.ext_size, self.num_heads, self.head_dim, self.chunk_size
+        if r is None:
+            raise NotImplementedError(_NEEDS_CHUNK_SIZE)
+        static = self.get_incremental_state(incremental_state, "attn_static")
+        dev = query.device
+        state = self._get_input_buffer(incremental_state)
+        if static is not None:
+            capturing, pieces = self._static_room(state, static, T_new, B)
+            if pieces:
+                # a prompt: consecutive pieces, each an ordinary step; the pad flags of the step are the last T_new columns
+                # in both of fairseq's mask shapes, sliced with the pieces
+                step_pad = None if key_padding_mask is None else key_padding_mask[:, -T_new:]
+                ys = [self._decode(query[a:a + pieces], None if step_pad is None else step_pad[:, a:a + pieces],
+                                   incremental_state)[0] for a in range(0, T_new, pieces)]
+                return torch.cat(ys, 0), None
+        qkv_new = self._project(query, None, None, keep_f32=True)  # [T_new, B, 3, h, d]
+        if static is None:
+            t0 = self._dynamic_room(incremental_state, state, qkv_new.dtype, B, T_new, dev)
+        cache = state["qkv"]
+        if qkv_new.dtype != cache.dtype:
+            # the cache's dtype is fixed: an fp32 step on a 16-bit cache rounds (with the one-time warning of
+            # _ops.to_io_dtype), a 16-bit step on an fp32 cache widens exactly
+            qkv_new = _ops.to_io_dtype(qkv_new) if cache.dtype != torch.float32 else qkv_new.float()
+            if static is not None:                                 # (append copies the rows as they are; the slice
+                qkv_new = qkv_new.to(cache.dtype)                  #  assignment of the dynamic state converts)
+        step_pad = None
+        if static is not None:
+            qkv_new = qkv_new.contiguous()
+            if key_padding_mask is not None:
+                step_pad = key_padding_mask[:, -T_new:].to(device=dev, dtype=torch.uint8).contiguous()
+            has_pad, bias = True, state["bias"]
+        else:
+            cache[:, t0:t0 + T_new] = qkv_new.transpose(0, 1)
+            # (whether a mask was ever given lives on the host: the unpadded case passes no mask without reading a flag back
+            #  from the device)
+            has_pad = bool(self.get_incremental_state(incremental_state, "attn_has_pad"))
+            if key_padding_mask is not None:
+                state["pad"][:, t0:t0 + T_new] = key_padding_mask[:, -T_new:].to(device=dev, dtype=torch.uint8)
+                if not has_pad:
+                    has_pad = True
+                    self.set_incremental_state(incremental_state, "attn_has_pad", True)
+            bias = None
+            if self.use_t5_rpe:
+                # the module is in eval mode, so the table is built once per weight and reused by every step
+                if not hasattr(self, "_decode_bias_cache"):
+                    self._decode_bias_cache = _ops.DerivedCache()
+                bias = self._decode_bias_cache.get(self, [self.rel_pos_bias.relative_attention_bias.weight],
+                                                   lambda: self._decode_bias_table(dev))
+        pad = state["pad"]
+        io = nv.EA_F32 if cache.dtype == torch.float32 else nv.io_dtype(cache)
+        adaptive, has_bias = 1 if self.adaptive_proj == "qk" else 0, 0 if bias is None else 1
+        if static is not None:
+            family, closes = "ea_ceva_sdecode_", True
+            geom = nv.ea_ceva_sdec_geom(B, h, d, io, w, e, r, T_new, static.get("cap", cache.shape[1]), adaptive, has_bias,
+                                        static.get("ring", 0), state["pos"].data_ptr(), state["status"].data_ptr())
+        else:
+            family = "ea_ceva_decode_"
+            c_first, c_last = t0 // r, (t0 + T_new) // r - 1        # the chunks this step's tokens complete
+            closes = c_last >= c_first
+            geom = nv.ea_ceva_dec_geom(B, h, d, io, w, e, r, t0, T_new, c_first, c_last, cache.shape[1], adaptive, has_bias,
+                                       1 if has_pad else 0)
+        g = ctypes.byref(geom)
+        tq, tk, tv = [nv.t4(cache[:, :, i].transpose(1, 2)) for i in range(3)]      # [B, h, cap (or ring), d] views
+        tl, tb = nv.t4(state["rf_k_bar"]), nv.t4(state["beta"])
+        mask_p = nv.ptr(pad) if has_pad else None
+        st = nv.stream()
+        if static is not None:
+            nv.call("ea_ceva_sdecode_append", g, nv.ptr(qkv_new), nv.ptr(step_pad), nv.ptr(cache), nv.ptr(pad), st)
+        if closes:
+            if static is not None:
+                mlp = state["mu"]
+            else:                                                  # (built once per weight)
+                if not hasattr(self, "_decode_mu_cache"):
+                    self._decode_mu_cache = _ops.DerivedCache()
+                mlp = self._decode_mu_cache.get(self, self._mu_params(), self._decode_mu_f32)
+            mp = (ctypes.c_void_p * len(mlp))(*[p.data_ptr() for p in mlp])
+            nv.call(family + "close", g, ctypes.byref(tq), ctypes.byref(tk), ctypes.byref(tv), mask_p, mp,
+                    ctypes.byref(tl), ctypes.byref(tb), st)
+        out = torch.empty((T_new, B, h, d), dtype=cache.dtype, device=dev)
+        to = nv.t4(out.permute(1, 2, 0, 3))                        # [B, h, T_new, d] view of the time-first rows
+        nv.call(family + "attn", g, ctypes.byref(tq), ctypes.byref(tk), ctypes.byref(tv), mask_p, nv.ptr(bias),
+                ctypes.byref(tl), ctypes.byref(tb), ctypes.byref(to), st)
+        if static is not None:
+            nv.call("ea_ceva_sdecode_advance", g, st)
+            if not capturing:                                      # (a replay advances only the device count)
+                static["count"] += T_new
+        else:
+            self.set_incremental_state(incremental_state, "attn_pos", t0 + T_new)
+            state["pos"] = state["pos"] + T_new
+            self._set_input_buffer(incremental_state, state)
+        return self._project_out(out.reshape(T_new, B, C), query.dtype).contiguous(), None

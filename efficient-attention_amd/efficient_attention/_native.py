@@ -357,10 +357,8 @@ KERNEL_TIMER = KernelTimer()
 _FN = {}
 
 
-def call_as(label, name, *args):
-    """call(name, ...) timed under `label` (one C-ABI entry, several shapes: the label tells them apart)."""
-    if not KERNEL_TIMER.enabled:
-        return call(name, *args)
+def _timed(label, name, args):
+    """One launch between two HIP events, recorded under `label`."""
     a = torch.cuda.Event(enable_timing=True)
     b = torch.cuda.Event(enable_timing=True)
     a.record()
@@ -368,6 +366,13 @@ def call_as(label, name, *args):
     b.record()
     KERNEL_TIMER.records.append((label, a, b))
     _check(rc, name)
+
+
+def call_as(label, name, *args):
+    """call(name, ...) timed under `label` (one C-ABI entry, several shapes: the label tells them apart)."""
+    if not KERNEL_TIMER.enabled:
+        return call(name, *args)
+    _timed(label, name, args)
 
 
 def call(name, *args):
@@ -379,16 +384,7 @@ def call(name, *args):
         if rc != 0:
             _check(rc, name)
         return
-    if KERNEL_TIMER.enabled:
-        a = torch.cuda.Event(enable_timing=True)
-        b = torch.cuda.Event(enable_timing=True)
-        a.record()
-        rc = getattr(lib(), name)(*args)
-        b.record()
-        KERNEL_TIMER.records.append((name, a, b))
-        _check(rc, name)
-        return
-    _check(getattr(lib(), name)(*args), name)
+    _timed(name, name, args)
 
 
 _QUERY_CACHE = {}

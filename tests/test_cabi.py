@@ -116,3 +116,99 @@ def test_eva_composite_entry_points_report_their_workspaces(lib):
     assert L.ea_eva_layer_fwd(ctypes.byref(cfg), None, None, None, None, None, None, None, None, 1, None) == -1
     assert L.ea_eva_layer_bwd(ctypes.byref(cfg), None, None, None, None, None, None, None, None, None, None, None, None, None,
                               None, None, None) == -1
+
+
+# ---- causal EVA decoding: what the six ea_ceva_* entry points refuse, before any HIP call --------------------------------
+# (entry point, what is wrong, expected return).  Geometry fields are overridden by name; a pointer is None (null) or an
+# offset from a 16-byte aligned host address; "q.sn" is a field of the ea_t4 `q`, "mu.3" the fourth mu parameter.  The valid
+# base: B 2, H 2, D 64, bf16, window 8, ext 8, chunk 4, T_new 2; dynamic t0 6, chunk 1 closing, cap 16; static cap 64, ring 0.
+# The expected codes are those of the library as it was BEFORE the entry points were folded onto one validation (this table
+# run against a build of that commit); where two faults meet, the rows pin which one decides.  (A ring behind
+# ea_ceva_decode_* cannot be written down here: ea_ceva_dec_geom has no such field, the refusal lives behind the C ABI.)
+_BADARG, _UNSUPPORTED = -1, -2
+_CEVA_DYNAMIC = ("decode_close", "decode_attn")
+_CEVA_STATIC = ("sdecode_close", "sdecode_attn")
+_CEVA_REFUSED = (
+    [(e, {"g": None}, _BADARG) for e in _CEVA_DYNAMIC + _CEVA_STATIC + ("sdecode_append", "sdecode_advance")]
+    # both families: the geometry dec_fill checks, the rows, the landmark rows, the pad flags
+    + [(e, bad, _BADARG) for e in _CEVA_DYNAMIC + _CEVA_STATIC for bad in (
+        {"B": 0}, {"H": 0}, {"window": 0}, {"chunk": 0}, {"ext": -1}, {"T_new": 0}, {"dtype": 3}, {"dtype": -1},
+        {"q": None}, {"k.ptr": None}, {"v.ptr": 2}, {"q.sn": 32}, {"k.sb": 4}, {"v.sh": 12}, {"lk": None}, {"lv.ptr": 8},
+        {"lv.sn": 2}, {"pad": None}, {"D": 48, "dtype": 3}, {"D": 48, "T_new": 0})]
+    + [(e, {"D": 48}, _UNSUPPORTED) for e in _CEVA_DYNAMIC + _CEVA_STATIC]
+    + [(e, {"D": 96}, _UNSUPPORTED) for e in _CEVA_DYNAMIC + _CEVA_STATIC]
+    + [(e, {"D": 48, "q.ptr": 2}, _UNSUPPORTED) for e in _CEVA_DYNAMIC + _CEVA_STATIC]       # D is decided before the rows
+    # dynamic: the step inside the cache, the chunks inside the step
+    + [(e, bad, _BADARG) for e in _CEVA_DYNAMIC for bad in ({"t0": -1}, {"cap": 7}, {"t0": 15})]
+    + [("decode_close", bad, _BADARG) for bad in (
+        {"mu": None}, {"mu.0": None}, {"mu.7": None}, {"mu.3": 4}, {"c_first": -1}, {"c_first": 2}, {"c_last": 2},
+        {"adaptive": 0, "mu.3": None})]
+    + [("decode_close", {"D": 48, "mu": None}, _UNSUPPORTED), ("decode_close", {"D": 48, "c_last": 0}, _UNSUPPORTED)]
+    # static: the counters, the capacity in whole windows, the ring -- all decided before D
+    + [(e, bad, _BADARG) for e in _CEVA_STATIC for bad in (
+        {"pos": None}, {"status": None}, {"pos": 2}, {"status": 18}, {"cap": 60}, {"chunk": 3}, {"ring": 20}, {"ring": 16},
+        {"ring": -8}, {"cap": 0}, {"D": 48, "pos": None}, {"D": 48, "cap": 60}, {"D": 48, "ring": 16}, {"D": 48, "pad": None})]
+    + [("sdecode_close", bad, _BADARG) for bad in ({"mu": None}, {"mu.4": None}, {"mu.1": 8})]
+    + [("sdecode_close", {"D": 48, "mu": None}, _UNSUPPORTED)]
+    # attn, both families: the output rows and the bias
+    + [(e, bad, _BADARG) for e in ("decode_attn", "sdecode_attn") for bad in (
+        {"out": None}, {"out.ptr": 4}, {"out.sn": 8}, {"bias": None})]
+    + [(e, {"D": 48, "bias": None}, _UNSUPPORTED) for e in ("decode_attn", "sdecode_attn")]
+    # append: its own subset, D last
+    + [("sdecode_append", bad, _BADARG) for bad in (
+        {"pos": None}, {"status": None}, {"pos": 2}, {"status": 18}, {"pad": None}, {"qkv_new": None}, {"qkv": None},
+        {"qkv_new": 8}, {"qkv": 4}, {"B": 0}, {"H": 0}, {"T_new": 0}, {"cap": 1}, {"dtype": 3}, {"ring": 20}, {"ring": 16},
+        {"D": 48, "pos": None}, {"D": 48, "dtype": 3}, {"D": 48, "qkv": 4}, {"D": 48, "ring": 16})]
+    + [("sdecode_append", {"D": 48}, _UNSUPPORTED)]
+    + [("sdecode_advance", bad, _BADARG) for bad in ({"pos": None}, {"pos": 2}, {"T_new": 0}, {"cap": 1})]
+)
+
+
+def _ceva_refused_call(nv, entry, bad):
+    buf = ctypes.create_string_buffer(64)
+    base = (ctypes.addressof(buf) + 15) & ~15          # never dereferenced: a refused call returns before any HIP call
+    static = entry.startswith("sdecode")
+    geo = dict(B=2, H=2, D=64, dtype=nv.EA_BF16, window=8, ext=8, chunk=4, T_new=2, adaptive=1, has_bias=1)
+    geo.update(dict(cap=64, ring=0, pos=0, status=16) if static else dict(cap=16, t0=6, c_first=1, c_last=1, has_mask=1))
+    arg = {n: {"ptr": 0, "sb": 2048, "sh": 64, "sn": 128} for n in ("q", "k", "v", "lk", "lv", "out")}
+    arg.update(g=1, pad=0, bias=0, qkv_new=0, qkv=0, mu=[0] * 8)
+    for key, val in bad.items():
+        name, _, field = key.partition(".")
+        if key in geo:
+            geo[key] = val
+        elif name == "mu" and field:
+            arg["mu"][int(field)] = val
+        elif field:
+            arg[name][field] = val
+        else:
+            arg[key] = val
+
+    def p(off):
+        return None if off is None else ctypes.c_void_p(base + off)
+
+    def t(name):
+        v = arg[name]
+        return None if v is None else ctypes.byref(nv.ea_t4(None if v["ptr"] is None else base + v["ptr"], v["sb"], v["sh"], v["sn"]))
+    for key in ("pos", "status"):
+        if key in geo:
+            geo[key] = None if geo[key] is None else base + geo[key]
+    geom = (nv.ea_ceva_sdec_geom if static else nv.ea_ceva_dec_geom)(**geo)
+    g = None if arg["g"] is None else ctypes.byref(geom)
+    mu = None if arg["mu"] is None else (ctypes.c_void_p * 8)(*[None if m is None else base + m for m in arg["mu"]])
+    fn = getattr(nv.lib(), "ea_ceva_" + entry)
+    if entry.endswith("close"):
+        return fn(g, t("q"), t("k"), t("v"), p(arg["pad"]), mu, t("lk"), t("lv"), None)
+    if entry.endswith("attn"):
+        return fn(g, t("q"), t("k"), t("v"), p(arg["pad"]), p(arg["bias"]), t("lk"), t("lv"), t("out"), None)
+    if entry.endswith("append"):
+        return fn(g, p(arg["qkv_new"]), None, p(arg["qkv"]), p(arg["pad"]), None)
+    return fn(g, None)
+
+
+def test_ceva_decoding_entry_points_refuse_before_any_launch(lib):
+    """Every refused argument combination of ea_ceva_decode_* / ea_ceva_sdecode_* keeps its return code, and where two faults
+    meet, the one that decided before still decides (_CEVA_REFUSED).  Only refused calls: an accepted one would launch."""
+    from efficient_attention import _native
+    got = [(entry, bad, want, _ceva_refused_call(_native, entry, bad)) for entry, bad, want in _CEVA_REFUSED]
+    wrong = [row for row in got if row[2] != row[3]]
+    assert len(got) >= 150 and not wrong, wrong

@@ -15,73 +15,16 @@ import torch
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path[:0] = [ROOT, os.path.join(ROOT, "efficient-attention_amd"), os.path.join(ROOT, "tests")]
 
+import ceva_decoding                                     # noqa: E402
+from ceva_decoding import F32_TOL, OLD, _Calls, _err, _geometry      # noqa: E402
 from test_gpu_causal_eva import RECIPE, _build          # noqa: E402
-
-F32_TOL = (2e-4, 1e-4)                                   # max |d| / max |ref|, rms(d) / rms(ref)
-DECODE = ("ea_ceva_decode_close", "ea_ceva_decode_attn")
-OLD = ("ea_window_attn_fwd", "ea_f32_attn_fwd")
-
-
-def _err(got, ref, live=None):
-    d = (got.double() - ref.double())
-    r = ref.double()
-    if live is not None:
-        d, r = d * live, r * live
-    return (d.abs().max() / r.abs().max().clamp_min(1e-30)).item(), (d.pow(2).mean().sqrt() / r.pow(2).mean().sqrt().clamp_min(1e-30)).item()
-
-
-class _Calls:
-    """Every C-ABI entry point called inside the block, one list per decoding step (nv.call patched as in test_gpu_f32_cores.py)."""
-
-    def __enter__(self):
-        from efficient_attention import _native as nv
-        self.nv, self.real, self.steps = nv, nv.call, []
-        nv.call = lambda nm, *a: (self.steps[-1].append(nm) if self.steps else None, self.real(nm, *a))[1]
-        return self
-
-    def step(self):
-        self.steps.append([])
-
-    def __exit__(self, *exc):
-        self.nv.call = self.real
-
-    def all(self):
-        return [c for s in self.steps for c in s]
-
-
-def _geometry(variant):
-    aa = dict(RECIPE)
-    embed, heads, T, B = 512, 8, 300, 2
-    if variant == "recipe_d128":
-        embed, heads, T = 1024, 8, 200
-    elif variant == "overlap_d64":
-        aa.update(overlap_window=True, window_size=32)
-        T = 150
-    elif variant == "no_rpe_noln":
-        aa.update(use_t5_rpe=False, adaptive_proj="no-ln", window_size=64, chunk_size=16)
-        T = 200
-    elif variant == "many_chunks":
-        aa.update(overlap_window=True, window_size=32, chunk_size=4)
-        embed, heads, T = 256, 4, 300
-    return aa, embed, heads, T, B
 
 
 def _decode(m, x, steps, calls, pad=None):
-    """Decode x [T, B, C] in steps of the given sizes (then single tokens); -> [T, B, C]."""
-    T = x.shape[0]
-    state, rows, t = {}, [], 0
+    """Decode x [T, B, C] on a fresh dynamic state in steps of the given sizes (then single tokens); -> [T, B, C]."""
     m.init_incremental_state()
-    for i, step in enumerate(list(steps) + [1] * T):
-        if t >= T:
-            break
-        n = min(step, T - t)
-        kpm = None if pad is None else (pad[:, t:t + n] if i % 2 == 0 else pad[:, :t + n])
-        calls.step()
-        y, _ = m(x[t:t + n], x[t:t + n], x[t:t + n], key_padding_mask=kpm, incremental_state=state)
-        rows.append(y)
-        t += n
+    rows, state = ceva_decoding._decode(m, x, steps, "dynamic", None, pad, calls=calls)
     return torch.cat(rows, 0), state
-
 
 def _fp32_checks(calls, rec):
     from efficient_attention import _ops

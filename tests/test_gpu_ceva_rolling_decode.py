@@ -17,25 +17,10 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path[:0] = [ROOT, os.path.join(ROOT, "efficient-attention_amd"), os.path.join(ROOT, "tests")]
 
 from test_gpu_causal_eva import RECIPE, _build                               # noqa: E402
-from test_gpu_ceva_decode import F32_TOL, OLD, _Calls, _err, _geometry       # noqa: E402
+from ceva_decoding import (DTYPES, IDS, OLD, STATIC, _Calls, _captured_run, _check_full, _ctx, _decode,   # noqa: E402
+                           _geometry, _init, _skip_f32, _stack_step)
 
-STATIC = ("ea_ceva_sdecode_append", "ea_ceva_sdecode_close", "ea_ceva_sdecode_attn", "ea_ceva_sdecode_advance")
-DTYPES = [torch.bfloat16, torch.float16, torch.float32]
-IDS = ["bf16", "fp16", "fp32"]
 VARIANTS = ["recipe_d64", "recipe_d128", "overlap_d64", "no_rpe_noln", "many_chunks"]
-
-
-def _skip_f32(dtype):
-    from efficient_attention import _f32
-    if dtype == torch.float32 and not _f32.ENABLED:
-        pytest.skip("the fp32 cores are switched off (EA_F32_CORES=0)")
-
-
-def _ctx(dtype):
-    """16-bit: autocast (without its weight-cast cache, which a capture may not use); fp32: the fp32 path outside autocast."""
-    if dtype == torch.float32:
-        return torch.autocast("cuda", enabled=False)
-    return torch.autocast("cuda", dtype=dtype, cache_enabled=False)
 
 
 def _ring(m, S=None):
@@ -43,50 +28,6 @@ def _ring(m, S=None):
     w, e = m.window_size, m.ext_size
     S = w if S is None else S
     return -(-(w + e + S) // w) * w
-
-
-def _init(m, kind, B, T, dtype, S=None):
-    """A fresh incremental state of `kind`.  (The module keeps the key it was built with: states made here stay readable
-    side by side.)"""
-    st = {}
-    if kind == "static":
-        m.init_static_decoding(st, B, T, dtype, "cuda")
-    elif kind == "rolling":
-        m.init_rolling_decoding(st, B, T, dtype, "cuda", max_step_tokens=S)
-    return st
-
-
-def _decode(m, x, steps, kind, dtype, pad=None, S=None, calls=None, before=None):
-    """Decode x [T, B, C] in steps of the given sizes, then single tokens, on a state of `kind` ("static" | "rolling" |
-    "dynamic"); before(state, t): called ahead of every step with the tokens decoded so far.  -> per-step outputs, state."""
-    T, B = x.shape[:2]
-    state, rows, t = _init(m, kind, B, T, dtype, S), [], 0
-    for i, step in enumerate(list(steps) + [1] * T):
-        if t >= T:
-            break
-        n = min(step, T - t)
-        kpm = None if pad is None else (pad[:, t:t + n] if i % 2 == 0 else pad[:, :t + n])
-        if before is not None:
-            before(state, t)
-        if calls is not None:
-            calls.step()
-        rows.append(m(x[t:t + n], x[t:t + n], x[t:t + n], key_padding_mask=kpm, incremental_state=state)[0])
-        t += n
-    return rows, state
-
-
-def _check_full(got, full, dtype, live=None):
-    """The project's bounds against the full forward: F32_TOL for fp32, 2e-2 of max |ref| for 16-bit rows."""
-    if dtype == torch.float32:
-        e = _err(got, full, live)
-        print("fp32 (max, rms) error vs full forward:", e)
-        assert e[0] <= F32_TOL[0] and e[1] <= F32_TOL[1], e
-    else:
-        d = (got.float() - full.float()).abs()
-        if live is not None:
-            d = d * live
-        print("16-bit max |d|, bound:", d.max().item(), 2e-2 * full.float().abs().max().item())
-        assert d.max().item() <= 2e-2 * full.float().abs().max().item()
 
 
 def _case(variant, padded, smode):
@@ -311,55 +252,6 @@ def test_oversized_step_under_capture_raises_before_any_launch(dtype):
 
 
 # ---- 7. capture --------------------------------------------------------------------------------------------------------------
-def _stack_step(mods, states, x):
-    """Residual layers y = h + attn(h), one incremental state per layer."""
-    h = x
-    for m, st in zip(mods, states):
-        h = h + m(h, h, h, incremental_state=st)[0]
-    return h
-
-
-def _captured_run(mods, x, P, dtype, kind="rolling", S=None, reorder=None, order=None, graph_reorder=False):
-    """Decoding of x [T, B, C] through the residual stack on states of `kind`: P tokens eagerly (in pieces of at most the
-    step bound), a warm-up step on a side stream, the capture of one 1-token step whose input is a static tensor, and replays
-    for the remaining tokens.  reorder: before the replay of token `reorder` the states are permuted by `order` (in a captured
-    graph when graph_reorder) and the inputs from there on are x[:, order].  -> [T - P, B, C] rows, states."""
-    T, B = x.shape[:2]
-    states = [_init(m, kind, B, T, dtype, S) for m in mods]
-    xr = x if order is None else x[:, order]
-    rows = []
-    _stack_step(mods, states, x[:P])
-    xin = x[P:P + 1].clone()
-    s = torch.cuda.Stream()
-    s.wait_stream(torch.cuda.current_stream())
-    with torch.cuda.stream(s):
-        rows.append(_stack_step(mods, states, xin).clone())             # warm-up: token P, eager
-    torch.cuda.current_stream().wait_stream(s)
-    g = torch.cuda.CUDAGraph()
-    with torch.cuda.graph(g):
-        yout = _stack_step(mods, states, xin)
-    greo = None
-    if reorder is not None and graph_reorder:
-        static_order = order.clone()
-        greo = torch.cuda.CUDAGraph()
-        with torch.cuda.graph(greo):
-            for m, st in zip(mods, states):
-                m.reorder_incremental_state(st, static_order)
-    for t in range(P + 1, T):
-        if reorder is not None and t == reorder:
-            if greo is not None:
-                greo.replay()
-            else:
-                for m, st in zip(mods, states):
-                    m.reorder_incremental_state(st, order)
-        src = xr if (reorder is not None and t >= reorder) else x
-        xin.copy_(src[t:t + 1])
-        g.replay()
-        rows.append(yout.clone())
-    torch.cuda.synchronize()
-    return torch.cat(rows, 0), states
-
-
 @pytest.mark.gpu
 @pytest.mark.parametrize("dtype", DTYPES, ids=IDS)
 def test_captured_rolling_step_replays_equal_rolling_eager(dtype):

@@ -15,55 +15,8 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path[:0] = [ROOT, os.path.join(ROOT, "efficient-attention_amd"), os.path.join(ROOT, "tests")]
 
 from test_gpu_causal_eva import RECIPE, _build                               # noqa: E402
-from test_gpu_ceva_decode import F32_TOL, OLD, _Calls, _err, _geometry       # noqa: E402
-
-STATIC = ("ea_ceva_sdecode_append", "ea_ceva_sdecode_close", "ea_ceva_sdecode_attn", "ea_ceva_sdecode_advance")
-DTYPES = [torch.bfloat16, torch.float16, torch.float32]
-IDS = ["bf16", "fp16", "fp32"]
-
-
-def _skip_f32(dtype):
-    from efficient_attention import _f32
-    if dtype == torch.float32 and not _f32.ENABLED:
-        pytest.skip("the fp32 cores are switched off (EA_F32_CORES=0)")
-
-
-def _ctx(dtype):
-    """16-bit: autocast (without its weight-cast cache, which a capture may not use); fp32: the fp32 path outside autocast."""
-    if dtype == torch.float32:
-        return torch.autocast("cuda", enabled=False)
-    return torch.autocast("cuda", dtype=dtype, cache_enabled=False)
-
-
-def _decode(m, x, steps, static, dtype, pad=None, calls=None):
-    """Decode x [T, B, C] in steps of the given sizes, then single tokens; -> list of per-step outputs, state."""
-    T, B = x.shape[:2]
-    state, rows, t = {}, [], 0
-    m.init_incremental_state()
-    if static:
-        m.init_static_decoding(state, B, T, dtype, "cuda")
-    for i, step in enumerate(list(steps) + [1] * T):
-        if t >= T:
-            break
-        n = min(step, T - t)
-        kpm = None if pad is None else (pad[:, t:t + n] if i % 2 == 0 else pad[:, :t + n])
-        if calls is not None:
-            calls.step()
-        rows.append(m(x[t:t + n], x[t:t + n], x[t:t + n], key_padding_mask=kpm, incremental_state=state)[0])
-        t += n
-    return rows, state
-
-
-def _check_full(got, full, dtype, live=None):
-    if dtype == torch.float32:
-        e = _err(got, full, live)
-        assert e[0] <= F32_TOL[0] and e[1] <= F32_TOL[1], e
-    else:
-        d = (got.float() - full.float()).abs()
-        if live is not None:
-            d = d * live
-        assert d.max().item() <= 2e-2 * full.float().abs().max().item()
-
+from ceva_decoding import (DTYPES, IDS, OLD, STATIC, _Calls, _captured_run, _check_full, _ctx, _decode,   # noqa: E402
+                           _geometry, _skip_f32, _stack_step)
 
 # ---- 1. static eager == dynamic, bit for bit --------------------------------------------------------------------------------
 @pytest.mark.gpu
@@ -85,9 +38,9 @@ def test_static_eager_equals_dynamic(dtype, variant, padded):
     steps = (37, 1, 1, 5)
     with torch.no_grad(), _ctx(dtype), warnings.catch_warnings():
         warnings.simplefilter("ignore")
-        dyn, _ = _decode(m, x, steps, False, dtype, pad)
+        dyn, _ = _decode(m, x, steps, "dynamic", dtype, pad)
         with _Calls() as calls:
-            sta, state = _decode(m, x, steps, True, dtype, pad, calls)
+            sta, state = _decode(m, x, steps, "static", dtype, pad, calls=calls)
     assert len(dyn) == len(sta)
     for i, (a, b) in enumerate(zip(dyn, sta)):
         assert a.dtype == b.dtype and torch.equal(a, b), (variant, i)
@@ -99,60 +52,6 @@ def test_static_eager_equals_dynamic(dtype, variant, padded):
 
 
 # ---- 2. a captured 1-token step, replayed ------------------------------------------------------------------------------------
-def _stack_step(mods, states, x):
-    """Residual layers y = h + attn(h), one incremental state per layer."""
-    h = x
-    for m, st in zip(mods, states):
-        h = h + m(h, h, h, incremental_state=st)[0]
-    return h
-
-
-def _captured_run(mods, x, P, dtype, reorder=None, order=None, graph_reorder=False):
-    """Static decoding of x [T, B, C] through the residual stack: P tokens eagerly, then a warm-up step on a side stream, the
-    capture of one 1-token step whose input is a static tensor, and replays for the remaining tokens (each copies the next
-    token into the static input).  reorder: before the replay of token `reorder`, the states are permuted by `order` (in a
-    captured graph when graph_reorder) and the inputs from there on are x[:, order].  -> [T - P, B, C] rows."""
-    T, B = x.shape[:2]
-    states = []
-    for m in mods:
-        st = {}
-        m.init_incremental_state()
-        m.init_static_decoding(st, B, T, dtype, "cuda")
-        states.append(st)
-    xr = x if order is None else x[:, order]
-    rows = []
-    _stack_step(mods, states, x[:P])
-    xin = x[P:P + 1].clone()
-    s = torch.cuda.Stream()
-    s.wait_stream(torch.cuda.current_stream())
-    with torch.cuda.stream(s):
-        rows.append(_stack_step(mods, states, xin).clone())             # warm-up: token P, eager
-    torch.cuda.current_stream().wait_stream(s)
-    g = torch.cuda.CUDAGraph()
-    with torch.cuda.graph(g):
-        yout = _stack_step(mods, states, xin)
-    greo, static_order = None, None
-    if reorder is not None and graph_reorder:
-        static_order = order.clone()
-        greo = torch.cuda.CUDAGraph()
-        with torch.cuda.graph(greo):
-            for m, st in zip(mods, states):
-                m.reorder_incremental_state(st, static_order)
-    for t in range(P + 1, T):
-        if reorder is not None and t == reorder:
-            if greo is not None:
-                greo.replay()
-            else:
-                for m, st in zip(mods, states):
-                    m.reorder_incremental_state(st, order)
-        src = xr if (reorder is not None and t >= reorder) else x
-        xin.copy_(src[t:t + 1])
-        g.replay()
-        rows.append(yout.clone())
-    torch.cuda.synchronize()
-    return torch.cat(rows, 0), states
-
-
 @pytest.mark.gpu
 @pytest.mark.parametrize("dtype", DTYPES, ids=IDS)
 def test_captured_step_replays_equal_static_eager(dtype):
@@ -167,9 +66,9 @@ def test_captured_step_replays_equal_static_eager(dtype):
     with torch.no_grad(), _ctx(dtype), warnings.catch_warnings():
         warnings.simplefilter("ignore")
         full, _ = m(x, x, x)
-        eager, _ = _decode(m, x, (P,), True, dtype)
+        eager, _ = _decode(m, x, (P,), "static", dtype)
         eager = torch.cat(eager, 0)
-        got, states = _captured_run([m], x, P, dtype)           # (one residual layer: the rows are x + attn(x))
+        got, states = _captured_run([m], x, P, dtype, "static")           # (one residual layer: the rows are x + attn(x))
     assert torch.equal(got, eager[P:] + x[P:]), (got.float() - (eager[P:] + x[P:]).float()).abs().max().item()
     _check_full(eager[P:], full[P:], dtype)
     assert not m.static_decoding_overflowed(states[0])
@@ -194,7 +93,7 @@ def test_two_stacked_layers_in_one_graph(dtype):
             m.init_static_decoding(st, B, T, dtype, "cuda")
         eager = [_stack_step(mods, states, x[:P])] + [_stack_step(mods, states, x[t:t + 1]) for t in range(P, T)]
         eager = torch.cat(eager, 0)
-        got, _ = _captured_run(mods, x, P, dtype)
+        got, _ = _captured_run(mods, x, P, dtype, "static")
         h = x
         for m in mods:                                         # the stack on the full forward
             h = h + m(h, h, h)[0]
@@ -228,7 +127,7 @@ def test_beam_reorder_between_replays(dtype, graph_reorder):
             ref.append(m(src[t:t + 1], src[t:t + 1], src[t:t + 1], incremental_state=st)[0])
         ref = torch.cat(ref, 0)
         xr = torch.cat([x[:R], x[R:, order]], 0)
-        got, states = _captured_run([m], x, P, dtype, reorder=R, order=order, graph_reorder=graph_reorder)
+        got, states = _captured_run([m], x, P, dtype, "static", reorder=R, order=order, graph_reorder=graph_reorder)
     assert torch.equal(got, ref[P:] + xr[P:]), (got.float() - (ref[P:] + xr[P:]).float()).abs().max().item()
     buf = m._get_input_buffer(states[0])
     assert int(buf["pos"].item()) == T
