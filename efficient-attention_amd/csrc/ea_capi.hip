@@ -1626,6 +1626,68 @@ int ea_scatter_fwd(const ea_sb_geom* g, const ea_t4* q, const ea_t4* k, const ea
   return sb_fwd_dispatch(p, g->dtype, (hipStream_t)stream);
 }
 
+// overlapping windows: the geometry of ea_sb_geom plus the extension of the key patch on every side
+static int fill_sb_ov(const ea_sb_geom* g, int32_t ext, SbP& p) {
+  int rc = fill_sb(g, p);
+  if (rc != EA_OK) return rc;
+  if (ext < 0) return EA_E_BADARG;
+  if (ext > g->window) return EA_E_UNSUPPORTED;      // the key pass looks at the adjacent windows only
+  const int t = g->window + 2 * ext;
+  p.ext = ext; p.Wk = g->attn_2d ? t * t : t;
+  p.wpb = 1;
+  return EA_OK;
+}
+
+int32_t ea_scatter_ov_windows(const ea_sb_geom* g, int32_t ext) {
+  SbP p = {};
+  int rc = fill_sb_ov(g, ext, p);
+  return rc != EA_OK ? rc : p.nwin;
+}
+
+int ea_scatter_ov_fwd(const ea_sb_geom* g, int32_t ext, const ea_t4* q, const ea_t4* k, const ea_t4* v,
+                      const uint8_t* mask, const float* W, const float* mx, const float* zall, const float* sall,
+                      const ea_t4* oloc, const float* lse_loc, const ea_t4* out, float* r, void* stream) {
+  SbP p = {};
+  int rc = fill_sb_ov(g, ext, p);
+  if (rc != EA_OK) return rc;
+  if (!t4_ok(q, 64) || !t4_ok(k, 64) || !t4_ok(v, 64) || !t4_ok(oloc, 64) || !t4_ok(out, 64) || !W || !mx || !zall ||
+      !sall || !lse_loc || !r) return EA_E_BADARG;
+  p.q = mks(q); p.k = mks(k); p.v = mks(v); p.oloc = mks(oloc); p.out = mks(out); p.mask = mask; p.Wf = W;
+  p.mx = mx; p.zall = zall; p.sall = sall; p.lse_loc = lse_loc; p.r = r;
+  return sb_ov_dispatch(0, p, g->dtype, (hipStream_t)stream);
+}
+
+int ea_scatter_ov_bwd_window(const ea_sb_geom* g, int32_t ext, const ea_t4* q, const ea_t4* k, const ea_t4* v,
+                             const uint8_t* mask, const float* W, const float* mx, const float* zall,
+                             const float* sall, const ea_t4* oloc, const float* lse_loc, const float* r,
+                             const ea_t4* dout, const ea_t4* dq, const ea_t4* doloc, float* dlse, float* w_ds,
+                             float* w_dzall, float* w_dzwin, void* stream) {
+  SbP p = {};
+  int rc = fill_sb_ov(g, ext, p);
+  if (rc != EA_OK) return rc;
+  if (!t4_ok(q, 64) || !t4_ok(k, 64) || !t4_ok(v, 64) || !t4_ok(oloc, 64) || !t4_ok(dout, 64) || !t4_ok(dq, 64) ||
+      !t4_ok(doloc, 64) || !W || !mx || !zall || !sall || !lse_loc || !r || !dlse || !w_ds || !w_dzall || !w_dzwin)
+    return EA_E_BADARG;
+  p.q = mks(q); p.k = mks(k); p.v = mks(v); p.oloc = mks(oloc); p.dout = mks(dout); p.dq = mks(dq);
+  p.doloc = mks(doloc); p.mask = mask; p.Wf = W; p.mx = mx; p.zall = zall; p.sall = sall;
+  p.lse_loc = lse_loc; p.r = const_cast<float*>(r); p.dlse = dlse; p.p_dsall = w_ds; p.p_dzall = w_dzall;
+  p.ws_dz = w_dzwin;
+  return sb_ov_dispatch(1, p, g->dtype, (hipStream_t)stream);
+}
+
+int ea_scatter_ov_bwd_keys(const ea_sb_geom* g, int32_t ext, const ea_t4* k, const ea_t4* v, const uint8_t* mask,
+                           const float* W, const float* mx, const float* dsall, const float* dzall, const float* w_ds,
+                           const float* w_dzwin, const ea_t4* dk, const ea_t4* dv, void* stream) {
+  SbP p = {};
+  int rc = fill_sb_ov(g, ext, p);
+  if (rc != EA_OK) return rc;
+  if (!t4_ok(k, 64) || !t4_ok(v, 64) || !t4_ok(dk, 64) || !t4_ok(dv, 64) || !W || !mx || !dsall || !dzall || !w_ds ||
+      !w_dzwin) return EA_E_BADARG;
+  p.k = mks(k); p.v = mks(v); p.dk = mks(dk); p.dv = mks(dv); p.mask = mask; p.Wf = W; p.mx = mx;
+  p.dsall = dsall; p.dzall = dzall; p.p_dsall = const_cast<float*>(w_ds); p.ws_dz = const_cast<float*>(w_dzwin);
+  return sb_ov_dispatch(2, p, g->dtype, (hipStream_t)stream);
+}
+
 }  // extern "C"
 
 // ---- composite per-module entry points (round 3): one call = the whole LARA core forward, one = the whole backward ----

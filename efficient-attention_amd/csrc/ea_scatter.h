@@ -23,9 +23,13 @@ struct SbP {
   int B, H, N, M, w, Wq, nwin, wpb;
   float a, b, lconst;           // d^-1/4, d^-1/2 / 2, log(M) / 2
   long long* prof;              // dev builds (-DEA_PROFILE): phase time stamps
+  // overlapping windows (sb_ov_*): key patch of Wk slots around every window, d z_win workspace [BH,G,M]
+  int ext, Wk;
+  float* ws_dz;
 };
 
 int sb_fwd_dispatch(const SbP& p, int dtype, hipStream_t st);
 int sb_bwd_dispatch(int which, const SbP& p, int dtype, hipStream_t st);
+int sb_ov_dispatch(int which, const SbP& p, int dtype, hipStream_t st);   // 0 forward, 1 backward window pass, 2 key pass
 
 }  // namespace ea

@@ -203,6 +203,10 @@ SIGNATURES = {
     "ea_scatter_bwd_parts": [_SG],
     "ea_scatter_bwd_window": [_SG, _T, _T, _T, _P, _P, _P, _P, _P, _T, _P, _P, _T, _T, _T, _T, _T, _P, _P, _P, _P],
     "ea_scatter_bwd_global": [_SG, _T, _T, _P, _P, _P, _P, _P, _T, _T, _P],
+    "ea_scatter_ov_windows": [_SG, _I],
+    "ea_scatter_ov_fwd": [_SG, _I, _T, _T, _T, _P, _P, _P, _P, _P, _T, _P, _T, _P, _P],
+    "ea_scatter_ov_bwd_window": [_SG, _I, _T, _T, _T, _P, _P, _P, _P, _P, _T, _P, _P, _T, _T, _T, _P, _P, _P, _P, _P],
+    "ea_scatter_ov_bwd_keys": [_SG, _I, _T, _T, _P, _P, _P, _P, _P, _P, _P, _T, _T, _P],
     "ea_performer_parts": [_PG],
     "ea_performer_kmax": [_PG, _T, _P, _P, _P],
     "ea_performer_kv": [_PG, _T, _T, _P, _P, _P, _P, _P, _P],

@@ -8,6 +8,7 @@ in place through strides, and the backward kernels write dq/dk/dv straight into 
 copies exist here.
 """
 import ctypes
+import math
 import os
 import threading
 import warnings
@@ -2603,10 +2604,12 @@ class PerformerAttnFn(torch.autograd.Function):
 SCATTER_TORCH = os.environ.get("EA_SCATTER_TORCH", "0") == "1"     # dev switch: feature half on torch ops
 
 
-def scatter_supported(qkv5, W, attn_2d, seq_shape, window):
+def scatter_supported(qkv5, W, attn_2d, seq_shape, window, ext_size=0):
+    """The feature half has HIP kernels for d = 64, m <= 64 and query windows of <= 64 tokens; with window overlap
+    (ext_size > 0) the key patch may be any size that follows from that, as long as it reaches the adjacent windows only."""
     B, N, _, h, d = qkv5.shape
     wq = window * window if attn_2d else window
-    return d == 64 and W.shape[1] <= 64 and wq <= 64
+    return d == 64 and W.shape[1] <= 64 and wq <= 64 and 0 <= ext_size <= window
 
 
 def _sb_geom(qkv5, W, attn_2d, seq_shape, window):
@@ -2615,8 +2618,10 @@ def _sb_geom(qkv5, W, attn_2d, seq_shape, window):
     return nv.ea_sb_geom(B, h, N, d, nv.io_dtype(qkv5), W.shape[1], 1 if attn_2d else 0, int(gh), int(gw), int(window))
 
 
-def scatter_stats(geom, qkv5, mask_u8, W):
-    """Sequence-wide feature statistics of the keys: mx [BH,M], z_all [BH,M], S_all [BH,M,d] (fp32)."""
+def scatter_stats(geom, qkv5, mask_u8, W, ext_size=0):
+    """Sequence-wide feature statistics of the keys: mx [BH,M], z_all [BH,M], S_all [BH,M,d] (fp32).  With window
+    overlap the patches of the border windows hold padding slots with log phi = 0, which enter the stabiliser (the
+    reference takes the maximum over the padded partition as well): mx >= log(M) / 2 in the kernels' scaling."""
     B, N, _, h, d = qkv5.shape
     BH, M, dev = B * h, W.shape[1], qkv5.device
     _, k, v = _qkv_views(qkv5)
@@ -2625,25 +2630,28 @@ def scatter_stats(geom, qkv5, mask_u8, W):
     p_ml = torch.empty((BH, S, M, 4), dtype=torch.float32, device=dev)
     nv.call("ea_scatter_kmax", ctypes.byref(geom), ctypes.byref(tk), nv.ptr(mask_u8), nv.ptr(W), nv.ptr(p_ml), nv.stream())
     mx = p_ml[..., 0].amax(1).contiguous()                                 # [BH, M]
+    if ext_size > 0:
+        mx = mx.clamp_(min=0.5 * math.log(M))
     p_kv = torch.empty((BH, S, M, d), dtype=torch.float32, device=dev)
     nv.call("ea_scatter_kv", ctypes.byref(geom), ctypes.byref(tk), ctypes.byref(tv), nv.ptr(mask_u8), nv.ptr(W),
             nv.ptr(mx), nv.ptr(p_ml), nv.ptr(p_kv), nv.stream())
     return mx, p_ml[..., 0].sum(1).contiguous(), p_kv.sum(1).contiguous()
 
 
-def scatter_feature_fwd(qkv5, mask_u8, W, o_loc, lse_loc, attn_2d, seq_shape, window):
+def scatter_feature_fwd(qkv5, mask_u8, W, o_loc, lse_loc, attn_2d, seq_shape, window, ext_size=0):
     """out [B,N,h,d] = merge of the window half (o_loc [B,N,h,d], lse_loc [B,h,N]) with the m feature columns;
-    also returns r [B,h,N] and the statistics (for the backward)."""
+    also returns r [B,h,N] and the statistics (for the backward).  ext_size > 0: overlapping windows (ea_scatter_ov_*)."""
     B, N, _, h, d = qkv5.shape
     W = W.float().contiguous()
     geom = _sb_geom(qkv5, W, attn_2d, seq_shape, window)
-    mx, zall, sall = scatter_stats(geom, qkv5, mask_u8, W)
+    mx, zall, sall = scatter_stats(geom, qkv5, mask_u8, W, ext_size)
     q, k, v = _qkv_views(qkv5)
     out = torch.empty((B, N, h, d), dtype=qkv5.dtype, device=qkv5.device)
     r = torch.empty((B, h, N), dtype=torch.float32, device=qkv5.device)
     lse_loc = lse_loc.float().contiguous()
     ts = [nv.t4(t) for t in (q, k, v, o_loc.permute(0, 2, 1, 3), out.permute(0, 2, 1, 3))]
-    nv.call("ea_scatter_fwd", ctypes.byref(geom), ctypes.byref(ts[0]), ctypes.byref(ts[1]), ctypes.byref(ts[2]),
+    name, head = ("ea_scatter_ov_fwd", (ctypes.byref(geom), int(ext_size))) if ext_size > 0 else ("ea_scatter_fwd", (ctypes.byref(geom),))
+    nv.call(name, *head, ctypes.byref(ts[0]), ctypes.byref(ts[1]), ctypes.byref(ts[2]),
             nv.ptr(mask_u8), nv.ptr(W), nv.ptr(mx), nv.ptr(zall), nv.ptr(sall), ctypes.byref(ts[3]), nv.ptr(lse_loc),
             ctypes.byref(ts[4]), nv.ptr(r), nv.stream())
     return out, r, (mx, zall, sall)
@@ -2656,18 +2664,18 @@ class ScatterFeatureFn(torch.autograd.Function):
     LocalAttnLseFn; no gradient reaches W (redrawn / fixed, like PerformerAttnFn)."""
 
     @staticmethod
-    def forward(ctx, qkv5, o_loc, lse_loc, mask_u8, W, attn_2d, seq_shape, window):
+    def forward(ctx, qkv5, o_loc, lse_loc, mask_u8, W, attn_2d, seq_shape, window, ext_size=0):
         nv.require_cuda(qkv5, "qkv")
-        out, r, (mx, zall, sall) = scatter_feature_fwd(qkv5, mask_u8, W, o_loc, lse_loc, attn_2d, seq_shape, window)
+        out, r, (mx, zall, sall) = scatter_feature_fwd(qkv5, mask_u8, W, o_loc, lse_loc, attn_2d, seq_shape, window, ext_size)
         Wc = W.float().contiguous()
         ctx.save_for_backward(qkv5, o_loc, lse_loc.float().contiguous(), mask_u8, Wc, r, mx, zall, sall)
-        ctx.geo = (attn_2d, tuple(seq_shape), window)
+        ctx.geo = (attn_2d, tuple(seq_shape), window, int(ext_size))
         return out
 
     @staticmethod
     def backward(ctx, dout):
         qkv5, o_loc, lse_loc, mask_u8, W, r, mx, zall, sall = ctx.saved_tensors
-        attn_2d, seq_shape, window = ctx.geo
+        attn_2d, seq_shape, window, ext = ctx.geo
         B, N, _, h, d = qkv5.shape
         BH, M, dev = B * h, W.shape[1], qkv5.device
         geom = _sb_geom(qkv5, W, attn_2d, seq_shape, window)
@@ -2675,6 +2683,28 @@ class ScatterFeatureFn(torch.autograd.Function):
         dqkv5 = torch.empty_like(qkv5)
         d_oloc = torch.empty_like(o_loc)
         dlse = torch.empty_like(lse_loc)
+        if ext > 0:
+            # overlapping patches: the window pass leaves every window's statistics gradients in a workspace, the key pass
+            # sums them per key over the windows whose patch holds it (stores only: the same bits on every run)
+            G = nv.lib().ea_scatter_ov_windows(ctypes.byref(geom), ext)
+            if G <= 0:
+                raise RuntimeError("ea_scatter_ov_windows refused the geometry (%d)" % G)
+            w_ds = torch.empty((BH, G, M, d), dtype=torch.float32, device=dev)
+            w_dz = torch.empty((2, BH, G, M), dtype=torch.float32, device=dev)          # shares of d z_all | d z_win
+            q, k, v = _qkv_views(qkv5)
+            dq, dk, dv = _qkv_views(dqkv5)
+            ts = [nv.t4(t) for t in (q, k, v, o_loc.permute(0, 2, 1, 3), dout.permute(0, 2, 1, 3), dq, dk, dv,
+                                     d_oloc.permute(0, 2, 1, 3))]
+            nv.call("ea_scatter_ov_bwd_window", ctypes.byref(geom), ext, ctypes.byref(ts[0]), ctypes.byref(ts[1]),
+                    ctypes.byref(ts[2]), nv.ptr(mask_u8), nv.ptr(W), nv.ptr(mx), nv.ptr(zall), nv.ptr(sall), ctypes.byref(ts[3]),
+                    nv.ptr(lse_loc), nv.ptr(r), ctypes.byref(ts[4]), ctypes.byref(ts[5]), ctypes.byref(ts[8]), nv.ptr(dlse),
+                    nv.ptr(w_ds), nv.ptr(w_dz[0]), nv.ptr(w_dz[1]), nv.stream())
+            dsall = w_ds.sum(1).contiguous()
+            dzall = w_dz[0].sum(1).contiguous()
+            nv.call("ea_scatter_ov_bwd_keys", ctypes.byref(geom), ext, ctypes.byref(ts[1]), ctypes.byref(ts[2]), nv.ptr(mask_u8),
+                    nv.ptr(W), nv.ptr(mx), nv.ptr(dsall), nv.ptr(dzall), nv.ptr(w_ds), nv.ptr(w_dz[1]), ctypes.byref(ts[6]),
+                    ctypes.byref(ts[7]), nv.stream())
+            return dqkv5, d_oloc, dlse, None, None, None, None, None, None
         P = nv.lib().ea_scatter_bwd_parts(ctypes.byref(geom))
         p_ds = torch.empty((BH, P, M, d), dtype=torch.float32, device=dev)
         p_dz = torch.empty((BH, P, M), dtype=torch.float32, device=dev)
@@ -2690,7 +2720,7 @@ class ScatterFeatureFn(torch.autograd.Function):
         dzall = p_dz.sum(1).contiguous()
         nv.call("ea_scatter_bwd_global", ctypes.byref(geom), ctypes.byref(ts[1]), ctypes.byref(ts[2]), nv.ptr(mask_u8),
                 nv.ptr(W), nv.ptr(mx), nv.ptr(dsall), nv.ptr(dzall), ctypes.byref(ts[6]), ctypes.byref(ts[7]), nv.stream())
-        return dqkv5, d_oloc, dlse, None, None, None, None, None
+        return dqkv5, d_oloc, dlse, None, None, None, None, None, None
 
 
 # ---- Performer in exact fp32 arithmetic (ea_performer_f32_*; round 4) --------------------------------------

@@ -12,13 +12,15 @@ Split of the work in this build: the window part -- logits, mask, relative-posit
 statistics, P.V and its backward -- is the HIP window kernel (`_ops.LocalAttnLseFn`, which hands back
 the per-query log-sum-exp); the feature columns are merged with it exactly through that log-sum-exp
 (out = e^{lse_loc - Z} o_loc + e^{R - Z} o_rfa, Z = logaddexp(lse_loc, R)).  The feature statistics
-themselves (global-minus-window sums) are batched GEMMs and reductions on torch device ops in fp32 --
-on HIP as well when the windows do not overlap (ea_scatter.hip).  With window overlap the
-key side of a window is the extended patch and the reference's zero padding of the partitioned
-log-features makes every out-of-range slot count as a key with phi = 1 and v = 0 (reference :99-100); that
-variant keeps the window half on the HIP kernel and evaluates the feature half with torch device ops.
+themselves (global-minus-window sums) and the merge are HIP kernels as well (ea_scatter.hip)
+for head_dim 64, at most 64 features and query windows of at most 64 tokens, with and without window
+overlap; beyond those limits, and behind the dev switch `_ops.SCATTER_TORCH`, the same algebra runs as
+batched GEMMs and reductions on torch device ops in fp32.  With window overlap the key side of a window
+is the extended patch and the reference's zero padding of the partitioned log-features makes every
+out-of-range slot count as a key with phi = 1 and v = 0 (reference :99-100); the kernels walk the patch
+in 64-row tiles and the backward sums every key's gradient over the windows whose patch holds it.
 (The reference returns NaN there as soon as a border window's padding outweighs the features of the keys
-outside it -- tests/golden/cases.py -- so it is a path for small-key regimes.)
+outside it -- tests/golden/cases.py -- so it is a path for small-key regimes; the kernels keep that.)
 """
 import math
 
@@ -109,9 +111,11 @@ class ScatterBrain(KernelizedAttention, LocalAttention):
         mask_u8 = _ops._mask_u8(mask, B, N, qkv5.device)
         o_loc, lse_loc = _ops.LocalAttnLseFn.apply(
             qkv5, self._table_bias(), mask_u8, self.attn_2d, tuple(seq_shape), w, self.ext_size)
-        if self.ext_size == 0 and _ops.scatter_supported(qkv5, proj, self.attn_2d, seq_shape, w) and not _ops.SCATTER_TORCH:
-            # feature half + merge on HIP (ea_scatter.hip); wider windows / more features fall through to torch ops
-            return _ops.ScatterFeatureFn.apply(qkv5, o_loc, lse_loc, mask_u8, proj, self.attn_2d, tuple(seq_shape), w)
+        if _ops.scatter_supported(qkv5, proj, self.attn_2d, seq_shape, w, self.ext_size) and not _ops.SCATTER_TORCH:
+            # feature half + merge on HIP (ea_scatter.hip), with and without window overlap; wider windows / more features
+            # fall through to torch ops
+            return _ops.ScatterFeatureFn.apply(qkv5, o_loc, lse_loc, mask_u8, proj, self.attn_2d, tuple(seq_shape), w,
+                                               self.ext_size)
 
         if self.attn_2d:
             H, W = seq_shape

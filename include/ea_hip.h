@@ -905,6 +905,36 @@ int ea_scatter_bwd_global(const ea_sb_geom* g, const ea_t4* k, const ea_t4* v, c
                           const float* mx, const float* dsall, const float* dzall, const ea_t4* dk, const ea_t4* dv,
                           void* stream);
 
+/* Overlapping windows (the module's overlap_window=True: ext = window / 2).  The key side of window g is the patch of
+ * (window + 2 ext) tokens per axis around it; a slot of the patch outside the sequence is the reference's zero padding:
+ * a key with log phi = 0 (phi = 1) for every feature and v = 0, which enters z_win and the stabiliser only.  So
+ *   - mx handed to ea_scatter_kv and to everything below is max(max_j log phi-arguments, log(M) / 2), i.e. the output of
+ *     ea_scatter_kmax raised to at least log(M) / 2 by the caller (log phi = 0 in the kernels' scaling, which keeps
+ *     the -log(M)/2 of log phi apart); z_all, S_all stay sums over the real keys;
+ *   - the non-local log-mass is the reference's max-shifted log_add_exp(lse_all, lse_win, mask (1,-1)): it is NaN, and
+ *     with it every output row of the window, where a border window's padding outweighs the keys outside its patch
+ *     (reference behaviour, not sanitised);
+ *   - a key lies in the patches of up to 2 (1-D) / 4 (2-D) windows: ea_scatter_ov_bwd_window writes dq, d o_loc,
+ *     d lse_loc and leaves, per window, w_ds [BH, G, M, 64] (the window's share of d S_all; d S_win[g] is its
+ *     negative), w_dzall [BH, G, M] (its share of d z_all) and w_dzwin [BH, G, M] (d z_win[g]), G =
+ *     ea_scatter_ov_windows(g, ext); the caller sums w_ds, w_dzall over G into dsall, dzall; ea_scatter_ov_bwd_keys
+ *     then WRITES every dk, dv row once from dsall, dzall and the windows whose patch holds the key (no atomics:
+ *     bit-reproducible).  Padding slots receive no gradient; mx is detached.
+ * 0 <= ext <= window (-1 below, -2 above), otherwise the limits of ea_sb_geom; ext = 0 computes the non-overlapping
+ * form through these kernels (the module uses ea_scatter_fwd / _bwd_* there). */
+int32_t ea_scatter_ov_windows(const ea_sb_geom* g, int32_t ext);
+int ea_scatter_ov_fwd(const ea_sb_geom* g, int32_t ext, const ea_t4* q, const ea_t4* k, const ea_t4* v,
+                      const uint8_t* mask, const float* W, const float* mx, const float* zall, const float* sall,
+                      const ea_t4* oloc, const float* lse_loc, const ea_t4* out, float* r, void* stream);
+int ea_scatter_ov_bwd_window(const ea_sb_geom* g, int32_t ext, const ea_t4* q, const ea_t4* k, const ea_t4* v,
+                             const uint8_t* mask, const float* W, const float* mx, const float* zall,
+                             const float* sall, const ea_t4* oloc, const float* lse_loc, const float* r,
+                             const ea_t4* dout, const ea_t4* dq, const ea_t4* doloc, float* dlse, float* w_ds,
+                             float* w_dzall, float* w_dzwin, void* stream);
+int ea_scatter_ov_bwd_keys(const ea_sb_geom* g, int32_t ext, const ea_t4* k, const ea_t4* v, const uint8_t* mask,
+                           const float* W, const float* mx, const float* dsall, const float* dzall, const float* w_ds,
+                           const float* w_dzwin, const ea_t4* dk, const ea_t4* dv, void* stream);
+
 /* ---- causal EVA, incremental decoding (ABI 17; causal_eva.py:537-665; ea_ceva_decode.hip) --------------------------
  * One decoding step of CausalEVAttention with fairseq's incremental state, defined by prefix consistency with the
  * full-sequence causal path (the output for token t equals row t of the forward on tokens 0..t).  q, k, v address the
