@@ -79,7 +79,7 @@ static Geo mk_geo(const ea_geom* g) {
 extern "C" {
 
 const char* ea_version(void) { return "ea_hip 0.1.0 gfx950"; }
-int32_t ea_abi_version(void) { return 19; }
+int32_t ea_abi_version(void) { return 20; }
 
 int32_t ea_window_bias_ld(const ea_geom* g) {
   WinTiling t;
@@ -2173,25 +2173,28 @@ static ea::DecT dec_mk(const ea_t4* t) {
 // A step's geometry as both families hand it over.  Dynamic (ea_ceva_dec_geom): the host knows t0 and which chunks close.
 // Static (ea_ceva_sdec_geom, dev): the count is *pos, so the host can check only that a step fits an empty cache (t0 = 0; the
 // kernels check t0 + T <= cap), no chunk range is given, the pad flags are always read, and ring is 0 (cap rows, linear) or
-// the rows of a rolling state -- a multiple of window that holds one step's span.
+// the rows of a rolling state -- a multiple of window that holds one step's span.  ntok: null, or the per-sequence state's
+// [B] token counts of the step (pos and status are [B] then).
 struct DecG {
   int B, H, D, dtype, window, ext, chunk, t0, T_new, c_first, c_last, cap, adaptive, has_bias, has_mask, ring;
   const int32_t* pos;
   int32_t* status;
   bool dev;
+  int32_t* ntok;
 };
 static DecG dec_read(const ea_ceva_dec_geom* g) {
   return {g->B, g->H, g->D, g->dtype, g->window, g->ext, g->chunk, g->t0, g->T_new, g->c_first, g->c_last, g->cap,
-          g->adaptive, g->has_bias, g->has_mask, 0, nullptr, nullptr, false};
+          g->adaptive, g->has_bias, g->has_mask, 0, nullptr, nullptr, false, nullptr};
 }
 static DecG dec_read(const ea_ceva_sdec_geom* g) {
   return {g->B, g->H, g->D, g->dtype, g->window, g->ext, g->chunk, 0, g->T_new, 0, -1, g->cap,
-          g->adaptive, g->has_bias, 1, g->ring, g->pos, g->status, true};
+          g->adaptive, g->has_bias, 1, g->ring, g->pos, g->status, true, g->ntok};
 }
 // What every launch of a step needs; with `windows`, also what close and attn need of the window geometry (append moves
 // rows and reads none of it).  Every EA_E_BADARG is decided before the head dim, the static state's own before the rest.
 static int dec_check(const DecG& g, const uint8_t* pad, bool windows) {
-  if (g.dev && (!g.pos || !g.status || (uintptr_t)g.pos % 4 || (uintptr_t)g.status % 4 || !pad)) return EA_E_BADARG;
+  if (g.dev && (!g.pos || !g.status || (uintptr_t)g.pos % 4 || (uintptr_t)g.status % 4 || (uintptr_t)g.ntok % 4 || !pad))
+    return EA_E_BADARG;
   if (windows && (g.window <= 0 || g.chunk <= 0 || g.ext < 0 || (g.dev && (g.cap % g.window || g.window % g.chunk))))
     return EA_E_BADARG;
   if (g.ring != 0 && !(g.ring > 0 && g.window > 0 && g.ring % g.window == 0 && g.ext >= 0 && g.T_new > 0 &&
@@ -2213,7 +2216,7 @@ static int dec_fill(const DecG& g, const ea_t4* q, const ea_t4* k, const ea_t4* 
   p.B = g.B; p.H = g.H; p.D = g.D; p.dtype = g.dtype; p.w = g.window; p.e = g.ext; p.r = g.chunk;
   p.t0 = g.t0; p.T = g.T_new; p.c_first = g.c_first; p.c_last = g.c_last; p.cap = g.cap; p.adaptive = g.adaptive ? 1 : 0;
   p.scale = (float)(1.0 / sqrt((double)g.D));
-  p.pos = g.pos; p.ring = g.ring;
+  p.pos = g.pos; p.ring = g.ring; p.ntok = g.ntok;
   return EA_OK;
 }
 static int dec_close(const DecG& g, const ea_t4* q, const ea_t4* k, const ea_t4* v, const uint8_t* pad,
@@ -2261,7 +2264,7 @@ int ea_ceva_sdecode_append(const ea_ceva_sdec_geom* g, const void* qkv_new, cons
   if (rc != EA_OK) return rc;
   ea::AppP p = {};
   p.src = (const char*)qkv_new; p.src_pad = new_pad; p.cache = (char*)qkv; p.pad = pad;
-  p.pos = g->pos; p.status = g->status;
+  p.pos = g->pos; p.status = g->status; p.ntok = g->ntok;
   p.B = g->B; p.T = g->T_new; p.cap = g->cap; p.ring = g->ring;
   p.row_bytes = 3 * g->H * g->D * (g->dtype == EA_F32 ? 4 : 2);
   return ea::ceva_sdecode_append(p, (hipStream_t)stream);
@@ -2279,7 +2282,8 @@ int ea_ceva_sdecode_attn(const ea_ceva_sdec_geom* g, const ea_t4* q, const ea_t4
 
 int ea_ceva_sdecode_advance(const ea_ceva_sdec_geom* g, void* stream) {
   if (!g || !g->pos || (uintptr_t)g->pos % 4 || g->T_new <= 0 || g->cap < g->T_new) return EA_E_BADARG;
-  return ea::ceva_sdecode_advance(const_cast<int32_t*>(g->pos), g->T_new, g->cap, (hipStream_t)stream);
+  if (g->ntok && ((uintptr_t)g->ntok % 4 || g->B <= 0)) return EA_E_BADARG;
+  return ea::ceva_sdecode_advance(const_cast<int32_t*>(g->pos), g->ntok, g->B, g->T_new, g->cap, (hipStream_t)stream);
 }
 
 }  // extern "C"

@@ -21,6 +21,8 @@ struct DecP {
   float scale;
   const int32_t* pos;         // static decoding: the token count in device memory (t0, c_first, c_last unused), or null
   int ring;                   // static decoding: q, k, v and pad hold `ring` rows, token n at row n % ring; 0 = cap rows, linear
+  const int32_t* ntok;        // per-sequence static decoding: pos is [B] and ntok [B] holds each element's tokens of this step
+                              // (written by append); null = one shared count, every element takes all T tokens
 };
 
 struct AppP {                 // static decoding, append: the step's rows into the cache at rows *pos ..
@@ -32,12 +34,16 @@ struct AppP {                 // static decoding, append: the step's rows into t
   int32_t* status;            // set to 1 when the step would pass cap (nothing is written)
   int B, T, cap, row_bytes;   // row_bytes = 3 H D element bytes, a multiple of 16
   int ring;                   // cache and pad hold `ring` rows, token n at row n % ring (cap bounds the step); 0 = cap rows
+  int32_t* ntok;              // per-sequence: [B], element b's tokens of this step = the positions before its first flag in
+                              // src_pad; pos and status are [B] then, and nothing is stored for the flagged positions.  null = shared
 };
 
 enum DecKind { DEC_CLOSE, DEC_ATTN };
-// the step's close or attn launch; p.pos != null: t0 = *p.pos (needs p.pad); p.ring != 0: ring rows (needs p.pos)
+// the step's close or attn launch; p.pos != null: t0 = *p.pos (needs p.pad); p.ring != 0: ring rows (needs p.pos);
+// p.ntok != null: t0 = p.pos[b], p.ntok[b] tokens (needs p.pos)
 int ceva_decode_launch(DecKind kind, const DecP& p, hipStream_t st);
 int ceva_sdecode_append(const AppP& p, hipStream_t st);
-int ceva_sdecode_advance(int32_t* pos, int T, int cap, hipStream_t st);
+// *pos += T; ntok != null: pos[b] += ntok[b] for the B elements
+int ceva_sdecode_advance(int32_t* pos, const int32_t* ntok, int B, int T, int cap, hipStream_t st);
 
 }  // namespace ea

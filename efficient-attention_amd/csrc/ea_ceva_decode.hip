@@ -30,6 +30,13 @@
 //        most once, and the rows a step appends overwrite only tokens older than the earliest one it reads.  Only addresses
 //        change: every test on a token (present, causal, capacity) stays on token indices, and the arithmetic and its order
 //        are the linear step's.  `Rows` owns the mapping; no kernel spells it.
+//   SEQ  (p.ntok != null, with DEV): whose count it is, and how many of the step's T tokens are this batch element's.  false:
+//        one count for the batch, every element takes all T.  true: t0 = p.pos[b], and element b takes n_b = p.ntok[b] <= T
+//        tokens, the positions before its first flag in the step's pad flags (append finds n_b and publishes it; close, attn
+//        and advance read it behind that launch).  Nothing is stored for the other positions, their output rows are zero,
+//        and overflow is per element: status[b], NaN rows of b alone.  The grids stay those of T tokens; a workgroup whose
+//        element needs less exits at once.  `Step` owns both numbers; no kernel body reads p.T for anything else.  The SEQ
+//        kernels have names of their own (ceva_*_seq_kernel, ea_ceva_decode_step.h), so the others keep their symbols and code.
 #include "ea_common.h"
 #include "ea_ceva_decode.h"
 
@@ -91,13 +98,17 @@ template <bool RING> struct Rows {
   EA_DEV int len(int cap) const { return RING ? ring : cap; }                      // rows per batch element (of pad)
 };
 
-// Where the step starts, and whether it fits the cache.  DEV = false: the kernel argument (the host has checked the
-// capacity: `fits` is true and folds away).  DEV = true: the token count in device memory -- one value for every thread of
-// the step's launches up to advance, so every exit decided from it is uniform.
-template <bool DEV> struct Step {
-  int t0;
-  EA_DEV Step(const int32_t* pos, int arg_t0) : t0(DEV ? *pos : arg_t0) {}
-  EA_DEV bool fits(int T, int cap) const { return !DEV || t0 + T <= cap; }
+// Where the step starts, how many tokens of it batch element b has, and whether they fit the cache.  DEV = false: the kernel
+// argument (the host has checked the capacity: `fits` is true and folds away).  DEV = true: the token count in device memory
+// -- one value for every thread of the step's launches up to advance, so every exit decided from it is uniform.  SEQ: the
+// count and the share of element b; a workgroup has one b, so the exits stay uniform.
+template <bool DEV, bool SEQ = false> struct Step {
+  static_assert(DEV || !SEQ, "per-sequence counts belong to the static step");
+  int t0, own;                                     // own: the element's tokens of this step (SEQ; else all T of them)
+  EA_DEV Step(const DecP& p, int b) : t0(SEQ ? p.pos[b] : DEV ? *p.pos : p.t0), own(SEQ ? p.ntok[b] : 0) {}
+  EA_DEV Step(const int32_t* pos, int b, int n_own) : t0(pos[SEQ ? b : 0]), own(n_own) {}   // append finds n itself
+  EA_DEV int n(int T) const { return SEQ ? own : T; }
+  EA_DEV bool fits(int T, int cap) const { return !DEV || t0 + n(T) <= cap; }
 };
 
 EA_DEV float wave_max(float v) {
@@ -148,146 +159,16 @@ EA_DEV void refuse_out(const DecP& p, int b, int h) {
   }
 }
 
-// One workgroup per window block of the step.  DEV: the grid holds the most window blocks T tokens can touch, and a block
-// this step does not touch exits at once; a step that does not fit writes NaN rows.
-template <typename E, int D, bool DEV, bool RING>
-__global__ __launch_bounds__(NT) void ceva_attn_kernel(const DecP p) {
-  static_assert(QPW == 8, "pv_rows reads the probabilities of a row as two float4");
-  static_assert(DEV || !RING, "the ring belongs to the static step");
-  constexpr int G = D / 4;                         // lanes per value row in P.V
-  __shared__ __attribute__((aligned(16))) float qs[NW][QPW][D];
-  __shared__ __attribute__((aligned(16))) float ps[NW][KT][QPW];
-  __shared__ __attribute__((aligned(16))) float mo[NW][QPW][D];
-  __shared__ float ml[NW][QPW][2];
-  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  const int b = (int)blockIdx.y / p.H, h = (int)blockIdx.y - b * p.H;
-  const Step<DEV> step(p.pos, p.t0);
-  const int t0 = step.t0;
-  if (!step.fits(p.T, p.cap)) { refuse_out<E, D>(p, b, h); return; }
-  const int bk = t0 / p.w + (int)blockIdx.x;
-  if (DEV && bk * p.w >= t0 + p.T) return;
-  const int tq0 = max(t0, bk * p.w), tq1 = min(t0 + p.T, (bk + 1) * p.w);
-  const int nqg = (tq1 - tq0 + QPW - 1) / QPW;
-  const int nsplit = nqg >= NW ? 1 : NW / nqg;     // waves per query group
-  const int Wk = p.w + p.e, nlt = (Wk + KT - 1) / KT;
-  const int tend = t0 + p.T;                       // cache rows [0, tend) hold tokens
-  const int kbase = bk * p.w - p.e;                // token of local slot 0
-  // the block's own tokens do not straddle the end of a ring (w divides it): row = token + qs0.  Local slot 0 is row ks0,
-  // up to e < ring rows before them, and the window spans w + e < ring rows from there: it wraps at most once.
-  const Rows<RING> rows{p.ring};
-  const int qs0 = rows.slot(bk * p.w) - bk * p.w;
-  const int ks0 = rows.unwrap(kbase + qs0);
-  const int pst = rows.len(p.cap);                 // row length of pad
-  const int kg = lane / G, dc = (lane % G) * 4;
-  for (int g = wave / nsplit; g < nqg; g += NW) {
-    const int s = wave % nsplit;
-    const int qa = tq0 + g * QPW, nql = min(QPW, tq1 - qa);
-    for (int idx = lane; idx < QPW * (D / 8); idx += 64) {
-      const int i = idx / (D / 8), c = (idx - i * (D / 8)) * 8;
-      float x[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
-      if (i < nql) Io<E>::ld8(row<E>(p.q, b, h, qa + i + qs0) + (size_t)c * Io<E>::SZ, x);
-      *reinterpret_cast<f32x4*>(&qs[wave][i][c]) = f32x4{x[0], x[1], x[2], x[3]};
-      *reinterpret_cast<f32x4*>(&qs[wave][i][c + 4]) = f32x4{x[4], x[5], x[6], x[7]};
-    }
-    __builtin_amdgcn_wave_barrier();
-    bool qpad[QPW];
-#pragma unroll
-    for (int i = 0; i < QPW; ++i) qpad[i] = i < nql && p.pad && p.pad[(size_t)b * pst + qa + i + qs0];
-    const int lmax = (qa + nql - 1) / p.r;         // landmark columns of the group's last query
-    const int ntile = nlt + (lmax + KT - 1) / KT;
-    float m[QPW], l[QPW];
-    f32x4 acc[QPW];
-#pragma unroll
-    for (int i = 0; i < QPW; ++i) { m[i] = -INFINITY; l[i] = 0.f; acc[i] = f32x4{0.f, 0.f, 0.f, 0.f}; }
-    for (int tile = s; tile < ntile; tile += nsplit) {
-      const bool lmk = tile >= nlt;
-      const int col = (lmk ? (tile - nlt) * KT : tile * KT) + lane;
-      float sc[QPW];
-#pragma unroll
-      for (int i = 0; i < QPW; ++i) sc[i] = 0.f;
-      float x[QPW];
-      if (!lmk) {
-        const int tok = kbase + col;
-        const bool present = col < Wk && tok >= 0 && tok < tend;
-        const int sl = rows.wrap(ks0 + col);       // the key's row: reduced once per lane and tile
-        if (present) dot_rows<E, D>(row<E>(p.k, b, h, sl), qs[wave], sc);
-        const bool kmask = !present || (p.pad && p.pad[(size_t)b * pst + sl]);
-#pragma unroll
-        for (int i = 0; i < QPW; ++i) {
-          const int tq = qa + i;
-          if (i >= nql || col >= Wk) x[i] = -INFINITY;
-          else if (kmask || qpad[i] || tok > tq) x[i] = MASK_FILL;
-          else x[i] = sc[i] * p.scale + (p.bias ? p.bias[(size_t)(tq - bk * p.w) * Wk + col] : 0.f);
-        }
-      } else {
-        if (col < lmax) dot_rows<float, D>(row<float>(p.lk, b, h, col), qs[wave], sc);
-#pragma unroll
-        for (int i = 0; i < QPW; ++i) x[i] = (i < nql && col < (qa + i) / p.r) ? sc[i] * p.scale : -INFINITY;
-      }
-#pragma unroll
-      for (int i = 0; i < QPW; ++i) {
-        const float mn = fmaxf(m[i], wave_max(x[i]));
-        const float alpha = mn == -INFINITY ? 1.f : __expf(m[i] - mn);
-        const float pv = mn == -INFINITY ? 0.f : __expf(x[i] - mn);
-        m[i] = mn;
-        l[i] = l[i] * alpha + pv;
-        acc[i] *= alpha;
-        ps[wave][lane][i] = pv;
-      }
-      __builtin_amdgcn_wave_barrier();
-      if (!lmk) {
-        // rows of absent / not yet decoded tokens: p is zero for every live query, their value rows are not read
-        const int j0 = max(0, -(kbase + tile * KT)), j1 = min(KT, min(Wk - tile * KT, tend - (kbase + tile * KT)));
-        if (j1 > j0) pv_rows<E, D>(rows, p.v, b, h, rows.wrap(ks0 + tile * KT + j0), j1 - j0, kg, dc, &ps[wave][j0], acc);
-      } else {
-        pv_rows<float, D>(Rows<false>{}, p.lv, b, h, (tile - nlt) * KT, min(KT, lmax - (tile - nlt) * KT), kg, dc, ps[wave], acc);
-      }
-      __builtin_amdgcn_wave_barrier();
-    }
-#pragma unroll
-    for (int i = 0; i < QPW; ++i) {
-      l[i] = wave_sum(l[i]);
-#pragma unroll
-      for (int o = G; o < 64; o <<= 1)
-#pragma unroll
-        for (int c = 0; c < 4; ++c) acc[i][c] += __shfl_xor(acc[i][c], o);
-    }
-    if (nsplit == 1) {
-      if (lane < G) {
-#pragma unroll
-        for (int i = 0; i < QPW; ++i)
-          if (i < nql) Io<E>::st4(const_cast<char*>(row<E>(p.o, b, h, qa + i - t0)) + (size_t)dc * Io<E>::SZ, acc[i] * (1.f / l[i]));
-      }
-    } else {
-      if (lane < G) {
-#pragma unroll
-        for (int i = 0; i < QPW; ++i) *reinterpret_cast<f32x4*>(&mo[wave][i][dc]) = acc[i];
-      }
-      if (lane == 0) {
-#pragma unroll
-        for (int i = 0; i < QPW; ++i) { ml[wave][i][0] = m[i]; ml[wave][i][1] = l[i]; }
-      }
-    }
-  }
-  if (nsplit == 1) return;                         // (uniform over the workgroup)
-  __syncthreads();
-  const int g = wave / nsplit;
-  if (wave % nsplit != 0 || g >= nqg) return;
-  const int qa = tq0 + g * QPW, nql = min(QPW, tq1 - qa);
-  for (int idx = lane; idx < nql * G; idx += 64) {
-    const int i = idx / G, c = (idx - i * G) * 4;
-    float mx = -INFINITY;
-    for (int w = wave; w < wave + nsplit; ++w) mx = fmaxf(mx, ml[w][i][0]);
-    float lt = 0.f;
-    f32x4 o = {0.f, 0.f, 0.f, 0.f};
-    for (int w = wave; w < wave + nsplit; ++w) {
-      const float f = ml[w][i][0] == -INFINITY ? 0.f : __expf(ml[w][i][0] - mx);
-      lt += f * ml[w][i][1];
-      o += f * *reinterpret_cast<const f32x4*>(&mo[w][i][c]);
-    }
-    Io<E>::st4(const_cast<char*>(row<E>(p.o, b, h, qa + i - t0)) + (size_t)c * Io<E>::SZ, o * (1.f / lt));
+// output rows n .. T - 1 of element b are zero: the step positions that are not its tokens (SEQ; written by blockIdx.x == 0)
+template <typename E, int D>
+EA_DEV void zero_out(const DecP& p, int b, int h, int n) {
+  if (blockIdx.x != 0) return;
+  for (int idx = n * (D / 4) + threadIdx.x; idx < p.T * (D / 4); idx += NT) {
+    const int i = idx / (D / 4), c = (idx - i * (D / 4)) * 4;
+    Io<E>::st4(const_cast<char*>(row<E>(p.o, b, h, i)) + (size_t)c * Io<E>::SZ, f32x4{0.f, 0.f, 0.f, 0.f});
   }
 }
+
 
 // block-wide max / sum of one value per thread (red: 2 NW floats of LDS)
 EA_DEV float block_max(float v, float* red) {
@@ -301,137 +182,53 @@ EA_DEV float block_max(float v, float* red) {
   return r;
 }
 
-// One workgroup per chunk the step completes: c_first .. c_last of the kernel arguments, or (DEV) the chunks that tokens
-// t0 .. t0 + T - 1 complete; then the grid holds ceil(T / r), the most T tokens can complete, and a workgroup whose chunk
-// this step does not complete exits at once.  The chunk's rows do not straddle the end of a ring (r divides it); its
-// landmark row is row c.
-template <typename E, int D, bool DEV, bool RING>
-__global__ __launch_bounds__(NT) void ceva_close_kernel(const DecP p) {
-  static_assert(DEV || !RING, "the ring belongs to the static step");
-  __shared__ __attribute__((aligned(16))) float xm[2][D];      // chunk means of q, k
-  __shared__ __attribute__((aligned(16))) float y[2][D];       // after the Linear layers
-  __shared__ __attribute__((aligned(16))) float mu[D];
-  __shared__ float pt[NT];                                      // probabilities of the current row tile
-  __shared__ float red[NW];
-  const int tid = threadIdx.x;
-  const Step<DEV> step(p.pos, p.t0);
-  const int c = (DEV ? step.t0 / p.r : p.c_first) + (int)blockIdx.x;
-  if (DEV && (!step.fits(p.T, p.cap) || c > (step.t0 + p.T) / p.r - 1)) return;
-  const int b = (int)blockIdx.y / p.H, h = (int)blockIdx.y - b * p.H;
-  const Rows<RING> rows{p.ring};
-  const int n0 = rows.slot(c * p.r);                           // first row of the chunk
-  const uint8_t* pad = p.pad ? p.pad + (size_t)b * rows.len(p.cap) + n0 : nullptr;
-  // masked means over the chunk's rows, divided by the chunk length
-  if (tid < 2 * D) {
-    const int side = tid / D, o = tid - side * D;
-    const DecT& t = side ? p.k : p.q;
-    float a = 0.f;
-    for (int j = 0; j < p.r; ++j) {
-      if (pad && pad[j]) continue;
-      a += Io<E>::ld1(row<E>(t, b, h, n0 + j) + (size_t)o * Io<E>::SZ);
-    }
-    xm[side][o] = a * (1.f / (float)p.r);
-  }
-  __syncthreads();
-  // mu networks: y = W x + b per side, then (adaptive) LayerNorm over the D outputs
-  const int per = p.adaptive ? 4 : 2;
-  if (tid < 2 * D) {
-    const int side = tid / D, o = tid - side * D;
-    const float* W = p.mu[side * per] + (size_t)o * D;
-    float a = p.mu[side * per + 1][o];
-    for (int i = 0; i < D; i += 4) {
-      const f32x4 w4 = *reinterpret_cast<const f32x4*>(W + i);
-      a = fmaf(w4[0], xm[side][i], a); a = fmaf(w4[1], xm[side][i + 1], a);
-      a = fmaf(w4[2], xm[side][i + 2], a); a = fmaf(w4[3], xm[side][i + 3], a);
-    }
-    y[side][o] = a;
-  }
-  __syncthreads();
-  float z = 0.f;
-  if (tid < 2 * D) {
-    const int side = tid / D, o = tid - side * D;
-    z = y[side][o];
-    if (p.adaptive) {
-      float mean = 0.f, var = 0.f;
-      for (int i = 0; i < D; ++i) mean += y[side][i];
-      mean *= 1.f / (float)D;
-      for (int i = 0; i < D; ++i) { const float dv = y[side][i] - mean; var = fmaf(dv, dv, var); }
-      var *= 1.f / (float)D;
-      z = (z - mean) / sqrtf(var + 1e-5f) * p.mu[side * per + 2][o] + p.mu[side * per + 3][o];
-    }
-  }
-  __syncthreads();
-  if (tid >= D && tid < 2 * D) {                   // k side: rf_k_bar = rk
-    const int o = tid - D;
-    xm[1][o] = z;
-    const_cast<float*>(reinterpret_cast<const float*>(row<float>(p.lk, b, h, c)))[o] = z;
-  }
-  __syncthreads();
-  if (tid < D) mu[tid] = z + xm[1][tid];           // mu = mu_q(qm) + rk
-  __syncthreads();
-  // beta = softmax over the chunk rows of (s mu.k_j - s |k_j|^2 / 2), padded rows -5e4 with a zero value row
-  float mrun = -INFINITY, lrun = 0.f, acc = 0.f;
-  for (int j0 = 0; j0 < p.r; j0 += NT) {
-    const int j = j0 + tid;
-    float x = -INFINITY;
-    if (j < p.r) {
-      if (pad && pad[j]) {
-        x = MASK_FILL;
-      } else {
-        const char* rp = row<E>(p.k, b, h, n0 + j);
-        float dot = 0.f, nn = 0.f;
-        for (int c8 = 0; c8 < D; c8 += 8) {
-          float kx[8];
-          Io<E>::ld8(rp + (size_t)c8 * Io<E>::SZ, kx);
-#pragma unroll
-          for (int e = 0; e < 8; ++e) { dot = fmaf(mu[c8 + e], kx[e], dot); nn = fmaf(kx[e], kx[e], nn); }
-        }
-        x = dot * p.scale - 0.5f * p.scale * nn;
-      }
-    }
-    const float mn = fmaxf(mrun, block_max(x, red));
-    pt[tid] = x == -INFINITY ? 0.f : __expf(x - mn);
-    __syncthreads();
-    if (tid < D) {
-      const float alpha = mrun == -INFINITY ? 0.f : __expf(mrun - mn);
-      lrun *= alpha;
-      acc *= alpha;
-      const int nj = min(NT, p.r - j0);
-      for (int jj = 0; jj < nj; ++jj) {
-        lrun += pt[jj];
-        if (pad && pad[j0 + jj]) continue;
-        acc = fmaf(pt[jj], Io<E>::ld1(row<E>(p.v, b, h, n0 + j0 + jj) + (size_t)tid * Io<E>::SZ), acc);
-      }
-    }
-    mrun = mn;
-    __syncthreads();
-  }
-  if (tid < D) const_cast<float*>(reinterpret_cast<const float*>(row<float>(p.lv, b, h, c)))[tid] = acc / lrun;
-}
 
 // ---- DEV steps: the token count lives in device memory -----------------------------------------------------------------
 // A step is append -> close -> attn -> advance on one stream.  Only advance writes *pos, so the three before it read the
 // same count, and each decides from it alone whether the step fits the cache.  A step that does not fit writes no cache
 // byte: append sets *status, close exits, attn writes NaN rows, advance leaves *pos.
 
-// one workgroup per (token t, element b) of the step: the token's [3, H, D] row, 16 bytes per lane and load, and its pad flag.
-// Each token's row is reduced on its own (a step may straddle the end of a ring); the capacity test stays on p.cap, the
-// landmark capacity.
-template <bool RING>
-__global__ __launch_bounds__(NT) void ceva_append_kernel(const AppP p) {
-  const Step<true> step(p.pos, 0);
-  const int t = (int)blockIdx.x, b = (int)blockIdx.y;
-  if (!step.fits(p.T, p.cap)) {
-    if (t == 0 && b == 0 && threadIdx.x == 0) *p.status = 1;
-    return;
+// The first flagged position of a row of T step flags (T when there is none): the element's token count of this step.
+// 16 flags per load where the row allows (its ends, up to 15 bytes each, go byte by byte: a row of [B, T] starts at any
+// address), the first set byte of a load by its lowest set bit, then a minimum over the workgroup (red: NW ints of LDS).
+EA_DEV int first_flag(const uint8_t* f, int T, int* red) {
+  const int tid = threadIdx.x;
+  const int head = min(T, (int)((16 - ((uintptr_t)f & 15)) & 15));
+  const int nvec = (T - head) / 16, tail = head + nvec * 16;
+  int first = T;
+  if (tid < head && f[tid]) first = tid;
+  const u32x4* v = reinterpret_cast<const u32x4*>(f + head);
+  for (int i = tid; i < nvec; i += NT) {           // (a thread's later loads lie further on: its first hit is its minimum)
+    const u32x4 u = v[i];
+    int at = 16;
+#pragma unroll
+    for (int c = 3; c >= 0; --c)
+      if (u[c]) at = c * 4 + (__builtin_ctz(u[c]) >> 3);
+    if (at < 16) { first = min(first, head + i * 16 + at); break; }
   }
-  const u32x4* src = reinterpret_cast<const u32x4*>(p.src + ((size_t)t * p.B + b) * p.row_bytes);
-  const Rows<RING> rows{p.ring};
-  const size_t at = (size_t)b * rows.len(p.cap) + rows.slot(step.t0, t);
-  u32x4* dst = reinterpret_cast<u32x4*>(p.cache + at * p.row_bytes);
-  for (int i = threadIdx.x; i < p.row_bytes / 16; i += NT) dst[i] = src[i];
-  if (threadIdx.x == 0) p.pad[at] = p.src_pad ? p.src_pad[(size_t)b * p.T + t] : (uint8_t)0;
+  if (tid < T - tail && f[tail + tid]) first = min(first, tail + tid);
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) first = min(first, __shfl_xor(first, o));
+  if ((tid & 63) == 0) red[tid >> 6] = first;
+  __syncthreads();
+  first = red[0];
+#pragma unroll
+  for (int w = 1; w < NW; ++w) first = min(first, red[w]);
+  return first;
 }
+
+
+// ---- the kernels of a step, once per value of SEQ (ea_ceva_decode_step.h) ----------------------------------------------
+#define CEVA_SEQ false
+#define CEVA_KERNEL(name) name##_kernel
+#include "ea_ceva_decode_step.h"
+#undef CEVA_SEQ
+#undef CEVA_KERNEL
+#define CEVA_SEQ true
+#define CEVA_KERNEL(name) name##_seq_kernel
+#include "ea_ceva_decode_step.h"
+#undef CEVA_SEQ
+#undef CEVA_KERNEL
 
 // *pos += T, in a launch of its own after attn on the same stream: stream order puts it behind every read of *pos in the
 // step.  (The other way, the last attn workgroup advancing through a completion counter, needs an agent-scope release /
@@ -439,42 +236,52 @@ __global__ __launch_bounds__(NT) void ceva_append_kernel(const AppP p) {
 // 1.5 us, eager or in a graph, and leaves no ordering to get wrong.)
 __global__ __launch_bounds__(64) void ceva_advance_kernel(int32_t* pos, int T, int cap) {
   if (threadIdx.x == 0) {
-    const Step<true> step(pos, 0);
+    const Step<true> step(pos, 0, T);
     if (step.fits(T, cap)) *pos = step.t0 + T;
   }
+}
+
+// SEQ: pos[b] += ntok[b], one thread per batch element; an element that does not fit keeps its count
+__global__ __launch_bounds__(64) void ceva_advance_seq_kernel(int32_t* pos, const int32_t* ntok, int B, int cap) {
+  const int b = (int)blockIdx.x * 64 + (int)threadIdx.x;
+  if (b >= B) return;
+  const Step<true, true> step(pos, b, ntok[b]);
+  if (step.fits(0, cap)) pos[b] = step.t0 + step.n(0);
 }
 
 using DecKernel = void (*)(const DecP);
 
 template <typename E, int D>
-DecKernel kernel_of(DecKind kind, bool dev, bool ring) {
+DecKernel kernel_of(DecKind kind, bool dev, bool ring, bool seq) {
+  if (seq && kind == DEC_CLOSE) return ring ? ceva_close_seq_kernel<E, D, true, true> : ceva_close_seq_kernel<E, D, true, false>;
+  if (seq) return ring ? ceva_attn_seq_kernel<E, D, true, true> : ceva_attn_seq_kernel<E, D, true, false>;
   if (kind == DEC_CLOSE)
     return !dev ? ceva_close_kernel<E, D, false, false> : ring ? ceva_close_kernel<E, D, true, true> : ceva_close_kernel<E, D, true, false>;
   return !dev ? ceva_attn_kernel<E, D, false, false> : ring ? ceva_attn_kernel<E, D, true, true> : ceva_attn_kernel<E, D, true, false>;
 }
 
 template <typename E>
-DecKernel kernel_of(int D, DecKind kind, bool dev, bool ring) {
+DecKernel kernel_of(int D, DecKind kind, bool dev, bool ring, bool seq) {
   switch (D) {
-    case 32: return kernel_of<E, 32>(kind, dev, ring);
-    case 64: return kernel_of<E, 64>(kind, dev, ring);
-    default: return kernel_of<E, 128>(kind, dev, ring);
+    case 32: return kernel_of<E, 32>(kind, dev, ring, seq);
+    case 64: return kernel_of<E, 64>(kind, dev, ring, seq);
+    default: return kernel_of<E, 128>(kind, dev, ring, seq);
   }
 }
 
 }  // namespace
 
-// DEV / RING follow the state: p.pos != null / p.ring != 0.  (The C entry points have checked the ring: a multiple of w
-// that holds the span of one step, ea_capi.hip.)
+// DEV / RING / SEQ follow the state: p.pos != null / p.ring != 0 / p.ntok != null.  (The C entry points have checked the
+// ring: a multiple of w that holds the span of one step, ea_capi.hip.)
 int ceva_decode_launch(DecKind kind, const DecP& p, hipStream_t st) {
-  const bool dev = p.pos != nullptr, ring = p.ring != 0;
-  if (dev ? !p.pad : ring) return EA_E_BADARG;     // a DEV step always reads the pad flags; a ring belongs to a DEV step
+  const bool dev = p.pos != nullptr, ring = p.ring != 0, seq = p.ntok != nullptr;
+  if (dev ? !p.pad : (ring || seq)) return EA_E_BADARG;   // a DEV step always reads the pad flags; ring, ntok belong to a DEV step
   if (p.D != 32 && p.D != 64 && p.D != 128) return EA_E_UNSUPPORTED;
   DecKernel kernel;
   switch (p.dtype) {
-    case EA_BF16: kernel = kernel_of<BF16>(p.D, kind, dev, ring); break;
-    case EA_F16: kernel = kernel_of<F16>(p.D, kind, dev, ring); break;
-    case EA_F32: kernel = kernel_of<float>(p.D, kind, dev, ring); break;
+    case EA_BF16: kernel = kernel_of<BF16>(p.D, kind, dev, ring, seq); break;
+    case EA_F16: kernel = kernel_of<F16>(p.D, kind, dev, ring, seq); break;
+    case EA_F32: kernel = kernel_of<float>(p.D, kind, dev, ring, seq); break;
     default: return EA_E_BADARG;
   }
   // x: the chunks the step closes / the window blocks it touches; DEV: the most T tokens can, wherever they start
@@ -485,13 +292,15 @@ int ceva_decode_launch(DecKind kind, const DecP& p, hipStream_t st) {
 }
 
 int ceva_sdecode_append(const AppP& p, hipStream_t st) {
-  hipLaunchKernelGGL(p.ring ? ceva_append_kernel<true> : ceva_append_kernel<false>, dim3((unsigned)p.T, (unsigned)p.B), dim3(NT),
-                     0, st, p);
+  void (*kernel)(const AppP) = p.ntok ? (p.ring ? ceva_append_seq_kernel<true> : ceva_append_seq_kernel<false>)
+                                      : (p.ring ? ceva_append_kernel<true> : ceva_append_kernel<false>);
+  hipLaunchKernelGGL(kernel, dim3((unsigned)p.T, (unsigned)p.B), dim3(NT), 0, st, p);
   return (int)hipGetLastError();
 }
 
-int ceva_sdecode_advance(int32_t* pos, int T, int cap, hipStream_t st) {
-  hipLaunchKernelGGL(ceva_advance_kernel, dim3(1), dim3(64), 0, st, pos, T, cap);
+int ceva_sdecode_advance(int32_t* pos, const int32_t* ntok, int B, int T, int cap, hipStream_t st) {
+  if (ntok) hipLaunchKernelGGL(ceva_advance_seq_kernel, dim3((unsigned)((B + 63) / 64)), dim3(64), 0, st, pos, ntok, B, cap);
+  else hipLaunchKernelGGL(ceva_advance_kernel, dim3(1), dim3(64), 0, st, pos, T, cap);
   return (int)hipGetLastError();
 }
 

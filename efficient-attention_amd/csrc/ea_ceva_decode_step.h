@@ -1,0 +1,300 @@
+// ea_ceva_decode_step.h -- the three kernels of a causal EVA decoding step that read the step's position: attn, close, append.
+// Not a header of declarations: ea_ceva_decode.hip includes this text twice, inside its anonymous namespace and after the
+// helpers it uses, with
+//   CEVA_SEQ false, CEVA_KERNEL(x) = x_kernel        one token count for the batch (and the dynamic step)
+//   CEVA_SEQ true,  CEVA_KERNEL(x) = x_seq_kernel    per-sequence counts (DEV only)
+// so that the shared-count kernels keep their symbols and, token for token, the source they had before the per-sequence
+// switch existed: tools/isa_diff.py shows their code unchanged.  (Wrapping one body template in two kernels compiles too,
+// but the inlined body schedules differently from the kernel written out.)
+#if !defined(CEVA_SEQ) || !defined(CEVA_KERNEL)
+#error "included by ea_ceva_decode.hip only"
+#endif
+
+// One workgroup per window block of the step.  DEV: the grid holds the most window blocks T tokens can touch, and a block
+// this step does not touch exits at once; a step that does not fit writes NaN rows.  SEQ: the block's queries are those of
+// element b's own n tokens, so the wave split below is that of a shared-count step of n tokens at the same position.
+template <typename E, int D, bool DEV, bool RING>
+__global__ __launch_bounds__(NT) void CEVA_KERNEL(ceva_attn)(const DecP p) {
+  constexpr bool SEQ = CEVA_SEQ;
+  static_assert(QPW == 8, "pv_rows reads the probabilities of a row as two float4");
+  static_assert(DEV || !RING, "the ring belongs to the static step");
+  constexpr int G = D / 4;                         // lanes per value row in P.V
+  __shared__ __attribute__((aligned(16))) float qs[NW][QPW][D];
+  __shared__ __attribute__((aligned(16))) float ps[NW][KT][QPW];
+  __shared__ __attribute__((aligned(16))) float mo[NW][QPW][D];
+  __shared__ float ml[NW][QPW][2];
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int b = (int)blockIdx.y / p.H, h = (int)blockIdx.y - b * p.H;
+  const Step<DEV, SEQ> step(p, b);
+  const int t0 = step.t0;
+  if (!step.fits(p.T, p.cap)) { refuse_out<E, D>(p, b, h); return; }
+  if (SEQ) {
+    zero_out<E, D>(p, b, h, step.n(p.T));
+    if (step.n(p.T) == 0) return;                  // an element that sits the step out: no query, no block to touch
+  }
+  const int bk = t0 / p.w + (int)blockIdx.x;
+  if (DEV && bk * p.w >= t0 + step.n(p.T)) return;
+  const int tq0 = max(t0, bk * p.w), tq1 = min(t0 + step.n(p.T), (bk + 1) * p.w);
+  const int nqg = (tq1 - tq0 + QPW - 1) / QPW;
+  const int nsplit = nqg >= NW ? 1 : NW / nqg;     // waves per query group
+  const int Wk = p.w + p.e, nlt = (Wk + KT - 1) / KT;
+  const int tend = t0 + step.n(p.T);               // cache rows [0, tend) hold tokens
+  const int kbase = bk * p.w - p.e;                // token of local slot 0
+  // the block's own tokens do not straddle the end of a ring (w divides it): row = token + qs0.  Local slot 0 is row ks0,
+  // up to e < ring rows before them, and the window spans w + e < ring rows from there: it wraps at most once.
+  const Rows<RING> rows{p.ring};
+  const int qs0 = rows.slot(bk * p.w) - bk * p.w;
+  const int ks0 = rows.unwrap(kbase + qs0);
+  const int pst = rows.len(p.cap);                 // row length of pad
+  const int kg = lane / G, dc = (lane % G) * 4;
+  for (int g = wave / nsplit; g < nqg; g += NW) {
+    const int s = wave % nsplit;
+    const int qa = tq0 + g * QPW, nql = min(QPW, tq1 - qa);
+    for (int idx = lane; idx < QPW * (D / 8); idx += 64) {
+      const int i = idx / (D / 8), c = (idx - i * (D / 8)) * 8;
+      float x[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
+      if (i < nql) Io<E>::ld8(row<E>(p.q, b, h, qa + i + qs0) + (size_t)c * Io<E>::SZ, x);
+      *reinterpret_cast<f32x4*>(&qs[wave][i][c]) = f32x4{x[0], x[1], x[2], x[3]};
+      *reinterpret_cast<f32x4*>(&qs[wave][i][c + 4]) = f32x4{x[4], x[5], x[6], x[7]};
+    }
+    __builtin_amdgcn_wave_barrier();
+    bool qpad[QPW];
+#pragma unroll
+    for (int i = 0; i < QPW; ++i) qpad[i] = i < nql && p.pad && p.pad[(size_t)b * pst + qa + i + qs0];
+    const int lmax = (qa + nql - 1) / p.r;         // landmark columns of the group's last query
+    const int ntile = nlt + (lmax + KT - 1) / KT;
+    float m[QPW], l[QPW];
+    f32x4 acc[QPW];
+#pragma unroll
+    for (int i = 0; i < QPW; ++i) { m[i] = -INFINITY; l[i] = 0.f; acc[i] = f32x4{0.f, 0.f, 0.f, 0.f}; }
+    for (int tile = s; tile < ntile; tile += nsplit) {
+      const bool lmk = tile >= nlt;
+      const int col = (lmk ? (tile - nlt) * KT : tile * KT) + lane;
+      float sc[QPW];
+#pragma unroll
+      for (int i = 0; i < QPW; ++i) sc[i] = 0.f;
+      float x[QPW];
+      if (!lmk) {
+        const int tok = kbase + col;
+        const bool present = col < Wk && tok >= 0 && tok < tend;
+        const int sl = rows.wrap(ks0 + col);       // the key's row: reduced once per lane and tile
+        if (present) dot_rows<E, D>(row<E>(p.k, b, h, sl), qs[wave], sc);
+        const bool kmask = !present || (p.pad && p.pad[(size_t)b * pst + sl]);
+#pragma unroll
+        for (int i = 0; i < QPW; ++i) {
+          const int tq = qa + i;
+          if (i >= nql || col >= Wk) x[i] = -INFINITY;
+          else if (kmask || qpad[i] || tok > tq) x[i] = MASK_FILL;
+          else x[i] = sc[i] * p.scale + (p.bias ? p.bias[(size_t)(tq - bk * p.w) * Wk + col] : 0.f);
+        }
+      } else {
+        if (col < lmax) dot_rows<float, D>(row<float>(p.lk, b, h, col), qs[wave], sc);
+#pragma unroll
+        for (int i = 0; i < QPW; ++i) x[i] = (i < nql && col < (qa + i) / p.r) ? sc[i] * p.scale : -INFINITY;
+      }
+#pragma unroll
+      for (int i = 0; i < QPW; ++i) {
+        const float mn = fmaxf(m[i], wave_max(x[i]));
+        const float alpha = mn == -INFINITY ? 1.f : __expf(m[i] - mn);
+        const float pv = mn == -INFINITY ? 0.f : __expf(x[i] - mn);
+        m[i] = mn;
+        l[i] = l[i] * alpha + pv;
+        acc[i] *= alpha;
+        ps[wave][lane][i] = pv;
+      }
+      __builtin_amdgcn_wave_barrier();
+      if (!lmk) {
+        // rows of absent / not yet decoded tokens: p is zero for every live query, their value rows are not read
+        const int j0 = max(0, -(kbase + tile * KT)), j1 = min(KT, min(Wk - tile * KT, tend - (kbase + tile * KT)));
+        if (j1 > j0) pv_rows<E, D>(rows, p.v, b, h, rows.wrap(ks0 + tile * KT + j0), j1 - j0, kg, dc, &ps[wave][j0], acc);
+      } else {
+        pv_rows<float, D>(Rows<false>{}, p.lv, b, h, (tile - nlt) * KT, min(KT, lmax - (tile - nlt) * KT), kg, dc, ps[wave], acc);
+      }
+      __builtin_amdgcn_wave_barrier();
+    }
+#pragma unroll
+    for (int i = 0; i < QPW; ++i) {
+      l[i] = wave_sum(l[i]);
+#pragma unroll
+      for (int o = G; o < 64; o <<= 1)
+#pragma unroll
+        for (int c = 0; c < 4; ++c) acc[i][c] += __shfl_xor(acc[i][c], o);
+    }
+    if (nsplit == 1) {
+      if (lane < G) {
+#pragma unroll
+        for (int i = 0; i < QPW; ++i)
+          if (i < nql) Io<E>::st4(const_cast<char*>(row<E>(p.o, b, h, qa + i - t0)) + (size_t)dc * Io<E>::SZ, acc[i] * (1.f / l[i]));
+      }
+    } else {
+      if (lane < G) {
+#pragma unroll
+        for (int i = 0; i < QPW; ++i) *reinterpret_cast<f32x4*>(&mo[wave][i][dc]) = acc[i];
+      }
+      if (lane == 0) {
+#pragma unroll
+        for (int i = 0; i < QPW; ++i) { ml[wave][i][0] = m[i]; ml[wave][i][1] = l[i]; }
+      }
+    }
+  }
+  if (nsplit == 1) return;                         // (uniform over the workgroup)
+  __syncthreads();
+  const int g = wave / nsplit;
+  if (wave % nsplit != 0 || g >= nqg) return;
+  const int qa = tq0 + g * QPW, nql = min(QPW, tq1 - qa);
+  for (int idx = lane; idx < nql * G; idx += 64) {
+    const int i = idx / G, c = (idx - i * G) * 4;
+    float mx = -INFINITY;
+    for (int w = wave; w < wave + nsplit; ++w) mx = fmaxf(mx, ml[w][i][0]);
+    float lt = 0.f;
+    f32x4 o = {0.f, 0.f, 0.f, 0.f};
+    for (int w = wave; w < wave + nsplit; ++w) {
+      const float f = ml[w][i][0] == -INFINITY ? 0.f : __expf(ml[w][i][0] - mx);
+      lt += f * ml[w][i][1];
+      o += f * *reinterpret_cast<const f32x4*>(&mo[w][i][c]);
+    }
+    Io<E>::st4(const_cast<char*>(row<E>(p.o, b, h, qa + i - t0)) + (size_t)c * Io<E>::SZ, o * (1.f / lt));
+  }
+}
+
+
+// One workgroup per chunk the step completes: c_first .. c_last of the kernel arguments, or (DEV) the chunks that tokens
+// t0 .. t0 + T - 1 complete; then the grid holds ceil(T / r), the most T tokens can complete, and a workgroup whose chunk
+// this step does not complete exits at once.  The chunk's rows do not straddle the end of a ring (r divides it); its
+// landmark row is row c.  SEQ: the chunks that element b's own tokens complete.
+template <typename E, int D, bool DEV, bool RING>
+__global__ __launch_bounds__(NT) void CEVA_KERNEL(ceva_close)(const DecP p) {
+  constexpr bool SEQ = CEVA_SEQ;
+  static_assert(DEV || !RING, "the ring belongs to the static step");
+  __shared__ __attribute__((aligned(16))) float xm[2][D];      // chunk means of q, k
+  __shared__ __attribute__((aligned(16))) float y[2][D];       // after the Linear layers
+  __shared__ __attribute__((aligned(16))) float mu[D];
+  __shared__ float pt[NT];                                      // probabilities of the current row tile
+  __shared__ float red[NW];
+  const int tid = threadIdx.x;
+  const Step<DEV, SEQ> step(p, SEQ ? (int)blockIdx.y / p.H : 0);
+  const int c = (DEV ? step.t0 / p.r : p.c_first) + (int)blockIdx.x;
+  if (DEV && (!step.fits(p.T, p.cap) || c > (step.t0 + step.n(p.T)) / p.r - 1)) return;
+  const int b = (int)blockIdx.y / p.H, h = (int)blockIdx.y - b * p.H;
+  const Rows<RING> rows{p.ring};
+  const int n0 = rows.slot(c * p.r);                           // first row of the chunk
+  const uint8_t* pad = p.pad ? p.pad + (size_t)b * rows.len(p.cap) + n0 : nullptr;
+  // masked means over the chunk's rows, divided by the chunk length
+  if (tid < 2 * D) {
+    const int side = tid / D, o = tid - side * D;
+    const DecT& t = side ? p.k : p.q;
+    float a = 0.f;
+    for (int j = 0; j < p.r; ++j) {
+      if (pad && pad[j]) continue;
+      a += Io<E>::ld1(row<E>(t, b, h, n0 + j) + (size_t)o * Io<E>::SZ);
+    }
+    xm[side][o] = a * (1.f / (float)p.r);
+  }
+  __syncthreads();
+  // mu networks: y = W x + b per side, then (adaptive) LayerNorm over the D outputs
+  const int per = p.adaptive ? 4 : 2;
+  if (tid < 2 * D) {
+    const int side = tid / D, o = tid - side * D;
+    const float* W = p.mu[side * per] + (size_t)o * D;
+    float a = p.mu[side * per + 1][o];
+    for (int i = 0; i < D; i += 4) {
+      const f32x4 w4 = *reinterpret_cast<const f32x4*>(W + i);
+      a = fmaf(w4[0], xm[side][i], a); a = fmaf(w4[1], xm[side][i + 1], a);
+      a = fmaf(w4[2], xm[side][i + 2], a); a = fmaf(w4[3], xm[side][i + 3], a);
+    }
+    y[side][o] = a;
+  }
+  __syncthreads();
+  float z = 0.f;
+  if (tid < 2 * D) {
+    const int side = tid / D, o = tid - side * D;
+    z = y[side][o];
+    if (p.adaptive) {
+      float mean = 0.f, var = 0.f;
+      for (int i = 0; i < D; ++i) mean += y[side][i];
+      mean *= 1.f / (float)D;
+      for (int i = 0; i < D; ++i) { const float dv = y[side][i] - mean; var = fmaf(dv, dv, var); }
+      var *= 1.f / (float)D;
+      z = (z - mean) / sqrtf(var + 1e-5f) * p.mu[side * per + 2][o] + p.mu[side * per + 3][o];
+    }
+  }
+  __syncthreads();
+  if (tid >= D && tid < 2 * D) {                   // k side: rf_k_bar = rk
+    const int o = tid - D;
+    xm[1][o] = z;
+    const_cast<float*>(reinterpret_cast<const float*>(row<float>(p.lk, b, h, c)))[o] = z;
+  }
+  __syncthreads();
+  if (tid < D) mu[tid] = z + xm[1][tid];           // mu = mu_q(qm) + rk
+  __syncthreads();
+  // beta = softmax over the chunk rows of (s mu.k_j - s |k_j|^2 / 2), padded rows -5e4 with a zero value row
+  float mrun = -INFINITY, lrun = 0.f, acc = 0.f;
+  for (int j0 = 0; j0 < p.r; j0 += NT) {
+    const int j = j0 + tid;
+    float x = -INFINITY;
+    if (j < p.r) {
+      if (pad && pad[j]) {
+        x = MASK_FILL;
+      } else {
+        const char* rp = row<E>(p.k, b, h, n0 + j);
+        float dot = 0.f, nn = 0.f;
+        for (int c8 = 0; c8 < D; c8 += 8) {
+          float kx[8];
+          Io<E>::ld8(rp + (size_t)c8 * Io<E>::SZ, kx);
+#pragma unroll
+          for (int e = 0; e < 8; ++e) { dot = fmaf(mu[c8 + e], kx[e], dot); nn = fmaf(kx[e], kx[e], nn); }
+        }
+        x = dot * p.scale - 0.5f * p.scale * nn;
+      }
+    }
+    const float mn = fmaxf(mrun, block_max(x, red));
+    pt[tid] = x == -INFINITY ? 0.f : __expf(x - mn);
+    __syncthreads();
+    if (tid < D) {
+      const float alpha = mrun == -INFINITY ? 0.f : __expf(mrun - mn);
+      lrun *= alpha;
+      acc *= alpha;
+      const int nj = min(NT, p.r - j0);
+      for (int jj = 0; jj < nj; ++jj) {
+        lrun += pt[jj];
+        if (pad && pad[j0 + jj]) continue;
+        acc = fmaf(pt[jj], Io<E>::ld1(row<E>(p.v, b, h, n0 + j0 + jj) + (size_t)tid * Io<E>::SZ), acc);
+      }
+    }
+    mrun = mn;
+    __syncthreads();
+  }
+  if (tid < D) const_cast<float*>(reinterpret_cast<const float*>(row<float>(p.lv, b, h, c)))[tid] = acc / lrun;
+}
+
+
+// one workgroup per (token t, element b) of the step: the token's [3, H, D] row, 16 bytes per lane and load, and its pad flag.
+// Each token's row is reduced on its own (a step may straddle the end of a ring); the capacity test stays on p.cap, the
+// landmark capacity.  SEQ: every workgroup finds n_b from the flags of its own element (one pass of 16-byte loads, a
+// 2048-token prefill is 128 of them), so none waits for another; the one of t = 0 publishes it, and also when the element
+// does not fit -- close, attn and advance decide that from pos[b] + ntok[b] as this kernel does.  The tokens it stores are
+// unflagged by construction: their pad flag is 0.
+template <bool RING>
+__global__ __launch_bounds__(NT) void CEVA_KERNEL(ceva_append)(const AppP p) {
+  constexpr bool SEQ = CEVA_SEQ;
+  const int t = (int)blockIdx.x, b = (int)blockIdx.y;
+  int n = p.T;
+  if (SEQ) {
+    __shared__ int red[NW];
+    if (p.src_pad) n = first_flag(p.src_pad + (size_t)b * p.T, p.T, red);
+    if (t == 0 && threadIdx.x == 0) p.ntok[b] = n;
+  }
+  const Step<true, SEQ> step(p.pos, b, n);
+  if (!step.fits(p.T, p.cap)) {
+    if (t == 0 && (SEQ || b == 0) && threadIdx.x == 0) p.status[SEQ ? b : 0] = 1;
+    return;
+  }
+  if (SEQ && t >= step.n(p.T)) return;
+  const u32x4* src = reinterpret_cast<const u32x4*>(p.src + ((size_t)t * p.B + b) * p.row_bytes);
+  const Rows<RING> rows{p.ring};
+  const size_t at = (size_t)b * rows.len(p.cap) + rows.slot(step.t0, t);
+  u32x4* dst = reinterpret_cast<u32x4*>(p.cache + at * p.row_bytes);
+  for (int i = threadIdx.x; i < p.row_bytes / 16; i += NT) dst[i] = src[i];
+  if (threadIdx.x == 0) p.pad[at] = !SEQ && p.src_pad ? p.src_pad[(size_t)b * p.T + t] : (uint8_t)0;
+}
+

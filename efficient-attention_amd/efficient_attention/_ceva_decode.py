@@ -10,9 +10,12 @@ index becomes a cache row (csrc/ea_ceva_decode.hip).  There is one step body, `_
     close             skipped when no chunk completes           always launched (its workgroups decide)
     count             host `attn_pos`, tensor `pos`             ea_ceva_sdecode_advance (+ host shadow, eager only)
 
-and in nothing else.
+and in nothing else.  A static or rolling state made with `per_sequence=True` keeps one count PER BATCH ROW (`pos [B]`): the
+same four launches, each row taking its own number of the step's tokens (`_step_flags`), with no host shadow at all.
 """
 import ctypes
+import functools
+import inspect
 
 import torch
 
@@ -22,8 +25,26 @@ from . import _f32
 _NEEDS_CHUNK_SIZE = ("incremental decoding needs --chunk-size (with --num-chunks the chunk length depends on the final "
                      "sequence length)")
 # the buffers of a static state that a beam reorder permutes; a rolling state has the same (its ring slots are per batch
-# element, the token count `pos` is shared)
+# element, the token count `pos` is shared); a per-sequence state adds its per-row counters
 _STATIC_BATCH_FIRST = ("qkv", "rf_k_bar", "beta", "pad")
+_PER_SEQUENCE = ("pos", "status", "ntok")
+
+
+def _per_sequence_option(init):
+    """The keyword-only `per_sequence=False` of the two `init_*_decoding` methods.  The methods keep the positional interface
+    they had, and that is the signature they report (`__signature__`: callers that pin the parameter list, this package's
+    own tests among them, see what they saw); the option is taken off here and handed to the method as its last argument.
+    Arguments are bound as Python binds them: `per_sequence` by position, or an unknown keyword, is a TypeError."""
+    positional = inspect.signature(init)
+    positional = positional.replace(parameters=list(positional.parameters.values())[:-1])
+
+    @functools.wraps(init)
+    def with_option(self, *args, per_sequence=False, **kwargs):
+        bound = positional.bind(self, *args, **kwargs)
+        bound.apply_defaults()
+        return init(*bound.args, bool(per_sequence), **bound.kwargs)
+    with_option.__signature__ = positional
+    return with_option
 
 
 class CevaDecoding:
@@ -52,7 +73,8 @@ class CevaDecoding:
         return [_ops._f32c(p) for p in self._mu_params()]
 
     # ---- static and rolling states ----------------------------------------------------------------------------------------
-    def init_static_decoding(self, incremental_state, batch_size, max_tokens, dtype, device):
+    @_per_sequence_option
+    def init_static_decoding(self, incremental_state, batch_size, max_tokens, dtype, device, per_sequence=False):
         """Allocate, once, every buffer a decoding step touches and mark this module's incremental state as STATIC: every
         later `forward(..., incremental_state=incremental_state)` then runs a step that can be captured into a graph
         (`torch.cuda.graph`) and replayed -- the token count lives in device memory and the kernels advance it: four
@@ -69,13 +91,30 @@ class CevaDecoding:
             bias, mu                      the dense T5 table and fp32 copies of the mu parameters, built here once (a
                                           capture fixes the weights)
         A step's token count and the batch are fixed for a given capture; the prompt can go through the same state eagerly.
-        Refuses what dynamic decoding refuses, with the same messages, and CPU devices (there is no CPU fallback)."""
+        Refuses what dynamic decoding refuses, with the same messages, and CPU devices (there is no CPU fallback).
+        `per_sequence=True`: every batch row has its own token count, so that ragged prompts need no left padding (which
+        would shift a row's chunk and window boundaries) and a finished row can be restarted while the others go on:
+            pos       [B]                 int32: tokens decoded so far, per row
+            status    [B]                 int32: 1 once a step of that row would have passed cap
+            ntok      [B]                 int32: the tokens each row took from the last step (written by the step)
+        and every other buffer as above.  A row's share of a step is given by the step's `key_padding_mask`: of its last
+        T_new columns, row b's tokens are the positions BEFORE ITS FIRST FLAGGED ONE, n_b of them (0 <= n_b <= T_new; no
+        mask: all T_new).  They are appended at pos[b] .. pos[b] + n_b - 1 and pos[b] advances by n_b; nothing is stored
+        for the flagged positions (no cache row, pad flag or landmark slot), and the attention core delivers zero rows for
+        them, so the module returns out_proj of zero there.  Right-padded ragged prompts, and a row that sits a step out
+        (all flagged), are the two uses.  The host does not know the counts: a step makes no host-side capacity check,
+        and overflow is per row -- a row whose step would pass cap writes nothing, gets status[b] = 1 and NaN output rows
+        and keeps its count, the other rows of the step are unaffected (`static_decoding_overflowed_rows`).  With equal
+        counts and no mask the outputs and the state equal those of the shared count bit for bit.
+        `reset_decoding_rows` restarts rows; `decoding_positions` reads the counts back."""
         B, T, device = self._check_static_decoding(batch_size, max_tokens, dtype, device)
         w = self.window_size
         cap = -(-T // w) * w
-        return self._alloc_static_decoding(incremental_state, B, cap, cap, dtype, device, {"count": 0})
+        return self._alloc_static_decoding(incremental_state, B, cap, cap, dtype, device, {"count": 0}, per_sequence)
 
-    def init_rolling_decoding(self, incremental_state, batch_size, max_tokens, dtype, device, max_step_tokens=None):
+    @_per_sequence_option
+    def init_rolling_decoding(self, incremental_state, batch_size, max_tokens, dtype, device, max_step_tokens=None,
+                              per_sequence=False):
         """`init_static_decoding` with the token rows in a fixed RING: the state is static in every respect (the same step,
         capturable and replayable; `static_decoding_overflowed` and the in-place `reorder_incremental_state` work on it), but
         `qkv` and `pad` hold R token slots instead of one row per token ever decoded, token n in slot n % R:
@@ -94,7 +133,10 @@ class CevaDecoding:
         A step with more than S tokens (a prompt) is fed through the ring by the module itself, eagerly, in consecutive
         pieces of at most S tokens, each an ordinary static step; while a stream is capturing it raises instead.
         Arithmetic and its order are the static step's: for one sequence of step sizes the outputs equal bit for bit.
-        Refuses what `init_static_decoding` refuses, with the same messages, and `max_step_tokens <= 0`."""
+        Refuses what `init_static_decoding` refuses, with the same messages, and `max_step_tokens <= 0`.
+        `per_sequence=True`: per-row counts as in `init_static_decoding`; every row walks its own ring.  The pieces of a long
+        ragged prompt carry the matching slices of the (monotone) mask, so a row that ended in one piece takes nothing from
+        the later ones."""
         B, T, device = self._check_static_decoding(batch_size, max_tokens, dtype, device)
         w, e = self.window_size, self.ext_size
         S = w if max_step_tokens is None else int(max_step_tokens)
@@ -104,7 +146,7 @@ class CevaDecoding:
         ring = -(-(w + e + S) // w) * w
         rows = min(ring, cap)
         static = {"count": 0, "cap": cap, "ring": ring if ring < cap else 0, "max_step": S}
-        return self._alloc_static_decoding(incremental_state, B, cap, rows, dtype, device, static)
+        return self._alloc_static_decoding(incremental_state, B, cap, rows, dtype, device, static, per_sequence)
 
     def _check_static_decoding(self, batch_size, max_tokens, dtype, device):
         """What a static (or rolling) state refuses, before anything is allocated -> (B, max_tokens, device)."""
@@ -122,17 +164,22 @@ class CevaDecoding:
             raise ValueError("static decoding needs batch_size > 0 and max_tokens > 0, got %d, %d" % (B, T))
         return B, T, device
 
-    def _alloc_static_decoding(self, incremental_state, B, cap, rows, dtype, device, static):
-        """The buffers of a static state: `rows` token rows (cap, or a ring), cap / r landmark rows."""
+    def _alloc_static_decoding(self, incremental_state, B, cap, rows, dtype, device, static, per_sequence=False):
+        """The buffers of a static state: `rows` token rows (cap, or a ring), cap / r landmark rows; one counter and one
+        overflow flag, or (per_sequence) one of each per batch row and the rows' token counts of a step."""
         h, d, r = self.num_heads, self.head_dim, self.chunk_size
+        nc = B if per_sequence else 1
         state = {
             "qkv": torch.zeros((B, rows, 3, h, d), dtype=dtype, device=device),
             "rf_k_bar": torch.zeros((B, h, cap // r, d), dtype=torch.float32, device=device),
             "beta": torch.zeros((B, h, cap // r, d), dtype=torch.float32, device=device),
             "pad": torch.zeros((B, rows), dtype=torch.uint8, device=device),
-            "pos": torch.zeros((1,), dtype=torch.int32, device=device),
-            "status": torch.zeros((1,), dtype=torch.int32, device=device),
+            "pos": torch.zeros((nc,), dtype=torch.int32, device=device),
+            "status": torch.zeros((nc,), dtype=torch.int32, device=device),
         }
+        if per_sequence:
+            state["ntok"] = torch.zeros((B,), dtype=torch.int32, device=device)
+            static["per_sequence"] = True
         with torch.no_grad():
             state["bias"] = self._decode_bias_table(device)
             state["mu"] = self._decode_mu_f32()
@@ -156,14 +203,51 @@ class CevaDecoding:
     def static_decoding_overflowed(self, incremental_state):
         """True once a step on this static state would have passed its capacity (the step wrote nothing; its outputs are
         NaN).  Reads the device flag back: call it after a replay, not inside a captured step."""
-        return bool(self._get_input_buffer(incremental_state)["status"].item())
+        status = self._get_input_buffer(incremental_state)["status"]
+        return bool(status.item() if status.numel() == 1 else status.any().item())      # (per-sequence: any row)
+
+    def _static_buffer(self, incremental_state, what):
+        """(buffer, host dict) of a static or rolling state, or a clear error."""
+        static = self.get_incremental_state(incremental_state, "attn_static")
+        buf = self._get_input_buffer(incremental_state)
+        if static is None or not buf or "pos" not in buf:
+            raise RuntimeError("%s needs a static or rolling decoding state (init_static_decoding / "
+                               "init_rolling_decoding); this incremental state holds none" % what)
+        return buf, static
+
+    def static_decoding_overflowed_rows(self, incremental_state):
+        """The overflow flags per batch row, a [B] bool tensor on the host (a shared-count state: its one flag repeated).
+        Reads the device flags back: call it after a replay, not inside a captured step."""
+        buf, _ = self._static_buffer(incremental_state, "static_decoding_overflowed_rows")
+        return buf["status"].ne(0).expand(buf["qkv"].shape[0]).cpu()
+
+    def decoding_positions(self, incremental_state):
+        """The tokens decoded so far per batch row, a [B] int32 copy on the host (a shared-count state: its one count
+        repeated).  Reads the device counts back: call it after a replay, not inside a captured step."""
+        buf, _ = self._static_buffer(incremental_state, "decoding_positions")
+        return buf["pos"].expand(buf["qkv"].shape[0]).cpu().clone()
+
+    def reset_decoding_rows(self, incremental_state, rows):
+        """Restart batch rows of a per-sequence state: `pos` and `status` of `rows` (indices: a sequence of ints or an
+        integer tensor) back to 0, in place and by device ops only -- between replays, or captured itself when `rows` is a
+        device tensor.  It clears no cache: nothing at or past a row's count is ever read, so the next tokens of that row
+        are those of a new sequence whatever the row held."""
+        buf, static = self._static_buffer(incremental_state, "reset_decoding_rows")
+        if not static.get("per_sequence"):
+            raise RuntimeError("reset_decoding_rows needs a per-sequence state (init_*_decoding(per_sequence=True)): "
+                               "this state has one token count for the whole batch")
+        idx = torch.as_tensor(rows, device=buf["pos"].device).reshape(-1).long()
+        buf["pos"].index_fill_(0, idx, 0)
+        buf["status"].index_fill_(0, idx, 0)
+        return incremental_state
 
     def reorder_incremental_state(self, incremental_state, new_order):
         buf = self._get_input_buffer(incremental_state)
         if buf and self.get_incremental_state(incremental_state, "attn_static") is not None:
             # a static state reorders IN PLACE: the pointers a captured step holds stay valid, and the reorder can itself
             # be captured (pos, status and the step-invariant tensors are not per element)
-            for k in _STATIC_BATCH_FIRST:
+            static = self.get_incremental_state(incremental_state, "attn_static")
+            for k in _STATIC_BATCH_FIRST + (_PER_SEQUENCE if static.get("per_sequence") else ()):
                 buf[k].copy_(buf[k].index_select(0, new_order))
             return incremental_state
         if buf:
@@ -182,7 +266,8 @@ class CevaDecoding:
         if cache.shape[0] != B:
             raise RuntimeError("static decoding state holds batch %d, the step has %d" % (cache.shape[0], B))
         capturing = torch.cuda.is_current_stream_capturing()
-        if not capturing and static["count"] + T_new > cap:
+        # (a per-sequence state: the host does not know the counts, overflow is reported by the device flags only)
+        if not capturing and not static.get("per_sequence") and static["count"] + T_new > cap:
             raise RuntimeError("static decoding state is full: %d of its %d tokens decoded, the step adds %d "
                                "(%s(max_tokens=...))" % (static["count"], cap, T_new, "init_static_decoding"
                                                          if max_step is None else "init_rolling_decoding"))
@@ -222,6 +307,15 @@ class CevaDecoding:
             state["qkv"], state["pad"] = grown(state["qkv"], 1, cap), grown(state["pad"], 1, cap)
             state["rf_k_bar"], state["beta"] = grown(state["rf_k_bar"], 2, cap // r), grown(state["beta"], 2, cap // r)
         return t0
+
+    @staticmethod
+    def _step_flags(key_padding_mask, T_new):
+        """A per-sequence step's flags [B, T_new], made monotone along the step: a position after a flagged one counts as
+        flagged, so a row's tokens are the positions before its first flag however a rolling state cuts the step into
+        pieces.  A device op, no read-back."""
+        if key_padding_mask is None:
+            return None
+        return key_padding_mask[:, -T_new:].ne(0).to(torch.int32).cumsum(1).ne(0)
 
     # ---- the step -------------------------------------------------------------------------------------------------------------
     def _decode(self, query, key_padding_mask, incremental_state):
@@ -268,6 +362,8 @@ class CevaDecoding:
         state = self._get_input_buffer(incremental_state)
         if static is not None:
             capturing, pieces = self._static_room(state, static, T_new, B)
+            if static.get("per_sequence"):
+                key_padding_mask = self._step_flags(key_padding_mask, T_new)
             if pieces:
                 # a prompt: consecutive pieces, each an ordinary step; the pad flags of the step are the last T_new columns
                 # in both of fairseq's mask shapes, sliced with the pieces
@@ -314,7 +410,8 @@ class CevaDecoding:
         if static is not None:
             family, closes = "ea_ceva_sdecode_", True
             geom = nv.ea_ceva_sdec_geom(B, h, d, io, w, e, r, T_new, static.get("cap", cache.shape[1]), adaptive, has_bias,
-                                        static.get("ring", 0), state["pos"].data_ptr(), state["status"].data_ptr())
+                                        static.get("ring", 0), state["pos"].data_ptr(), state["status"].data_ptr(),
+                                        state["ntok"].data_ptr() if "ntok" in state else None)
         else:
             family = "ea_ceva_decode_"
             c_first, c_last = t0 // r, (t0 + T_new) // r - 1        # the chunks this step's tokens complete
@@ -344,8 +441,8 @@ class CevaDecoding:
                 ctypes.byref(tl), ctypes.byref(tb), ctypes.byref(to), st)
         if static is not None:
             nv.call("ea_ceva_sdecode_advance", g, st)
-            if not capturing:                                      # (a replay advances only the device count)
-                static["count"] += T_new
+            if not capturing and "ntok" not in state:              # (a replay advances only the device count; per-sequence
+                static["count"] += T_new                           #  counts live on the device alone)
         else:
             self.set_incremental_state(incremental_state, "attn_pos", t0 + T_new)
             state["pos"] = state["pos"] + T_new

@@ -22,7 +22,7 @@ class ea_t4(ctypes.Structure):
                 ("sn", ctypes.c_int64)]
 
 
-ABI_VERSION = 19         # ea_abi_version() of include/ea_hip.h this file mirrors
+ABI_VERSION = 20         # ea_abi_version() of include/ea_hip.h this file mirrors
 
 
 class ea_geom(ctypes.Structure):
@@ -83,7 +83,7 @@ class ea_ceva_sdec_geom(ctypes.Structure):
     _fields_ = [("B", ctypes.c_int32), ("H", ctypes.c_int32), ("D", ctypes.c_int32), ("dtype", ctypes.c_int32),
                 ("window", ctypes.c_int32), ("ext", ctypes.c_int32), ("chunk", ctypes.c_int32), ("T_new", ctypes.c_int32),
                 ("cap", ctypes.c_int32), ("adaptive", ctypes.c_int32), ("has_bias", ctypes.c_int32), ("ring", ctypes.c_int32),
-                ("pos", ctypes.c_void_p), ("status", ctypes.c_void_p)]
+                ("pos", ctypes.c_void_p), ("status", ctypes.c_void_p), ("ntok", ctypes.c_void_p)]
 
 
 class ea_eva_layer(ctypes.Structure):

@@ -987,7 +987,16 @@ int ea_ceva_decode_attn(const ea_ceva_dec_geom* g, const ea_t4* q, const ea_t4* 
  * [B, H, cap / chunk, D], and cap bounds only them and *pos.  ring is a multiple of window with ring >= window + ext + T_new
  * (else EA_E_BADARG): a step at *pos reads back to token floor(*pos / window) window - ext and appends up to *pos + T_new - 1,
  * at most window - 1 + ext + T_new < ring tokens, so the rows it appends replace only tokens older than any it reads.  The
- * arithmetic is that of ring = 0: for one sequence of step sizes the outputs and landmark rows are equal bit for bit. */
+ * arithmetic is that of ring = 0: for one sequence of step sizes the outputs and landmark rows are equal bit for bit.
+ * ABI 20, ntok != NULL (init_*_decoding(per_sequence=True)): every batch element has its own count.  pos, status and ntok
+ * are int32 [B].  Of the step's T_new positions, element b's tokens are those before its first flagged one in new_pad
+ * [B, T_new] (all T_new without a flag or with new_pad NULL): n_b of them, 0 <= n_b <= T_new.  append finds n_b, writes
+ * ntok[b] = n_b (its only writer) and stores the n_b rows at pos[b] .. pos[b] + n_b - 1 with pad 0; nothing is stored for the
+ * other positions.  close, attn and advance, behind it on the stream, take t0 = pos[b] and n_b where they take *pos and T_new
+ * above; attn writes zero rows n_b .. T_new - 1 of element b; advance adds n_b to pos[b].  The launches and their grids are
+ * those of T_new tokens.  An element with pos[b] + n_b > cap writes no byte of its state: status[b] = 1, its T_new output rows
+ * are NaN, pos[b] stays; the other elements of the step are not affected.  For n_b = T_new everywhere the outputs and the
+ * state equal those of ntok = NULL bit for bit.  ntok = NULL is exactly the contract of ABI 19. */
 typedef struct {
   int32_t B, H, D;
   int32_t dtype;             /* EA_BF16 | EA_F16 | EA_F32: the cache rows and out */
@@ -999,6 +1008,7 @@ typedef struct {
   int32_t ring;              /* 0: qkv and pad hold cap rows; else they hold ring rows, token n at row n % ring */
   const int32_t* pos;        /* device */
   int32_t* status;           /* device */
+  int32_t* ntok;             /* device [B], or NULL: one shared count (ABI 20) */
 } ea_ceva_sdec_geom;
 int ea_ceva_sdecode_append(const ea_ceva_sdec_geom* g, const void* qkv_new, const uint8_t* new_pad, void* qkv, uint8_t* pad,
                            void* stream);

@@ -1,11 +1,17 @@
 """Per-token latency of CausalEVAttention decoding at the wikitext-103 LM geometry (embed 1024, h 8, d 128, w 128, chunks of 8,
-T5 bias, adaptive 'qk'), 16 stacked residual attention layers (x + attn(x), no FFN), bf16 autocast, in five modes:
+T5 bias, adaptive 'qk'), 16 stacked residual attention layers (x + attn(x), no FFN), bf16 autocast, in eight modes:
  - dynamic:       the incremental state of `_decode` (host token count, two decode launches per layer step);
  - static:        `init_static_decoding`, the same step run eagerly (four decode launches per layer step);
  - graph:         that static step over all 16 layers captured once with torch.cuda.graph and replayed;
  - rolling:       `init_rolling_decoding`, the static step on a state whose token rows live in a ring, eager;
- - rolling-graph: that step captured and replayed.
-   python tools/ceva_decode_latency.py [--context 512] [--steps 64] [--modes dynamic,static,graph,rolling,rolling-graph]   (GPU)
+ - rolling-graph: that step captured and replayed;
+ - per-seq, per-seq-graph, per-seq-rolling-graph: static, graph and rolling-graph on a state with per-sequence token counts
+   (`per_sequence=True`), every row at the same count and no mask, so that the rows compare bitwise with the other modes.
+   python tools/ceva_decode_latency.py [--context 512] [--steps 64] [--modes dynamic,static,graph,...]   (GPU)
+   python tools/ceva_decode_latency.py --ragged [--context 512] [--steps 64]     (GPU)
+`--ragged`: batch 8 on per-sequence states, row b prefilled to (b + 1) / 8 of `context` by right-padded steps, then the
+captured 1-token step replayed with every row live -- rows at eight different counts in one replay -- next to the same
+modes with all rows at `context`; prints the replay time of both and the bytes the per-sequence tensors add to a state.
 A 1-token step after a prefill of `context` tokens, fed in pieces of one window (the largest step of a rolling state) in
 every mode, so that all modes run one sequence of step sizes; a warm-up, then the median over 5 blocks of `steps` tokens,
 each block timed by the host clock around its steps and a device synchronise.  The rows of the modes are compared (bitwise)
@@ -35,14 +41,15 @@ def build():
                            attn_args=argparse.Namespace(**RECIPE))).cuda().eval() for _ in range(LAYERS)]
 
 
-def step(mods, states, x):
+def step(mods, states, x, mask=None):
     for m, st in zip(mods, states):
-        x = x + m(x, x, x, incremental_state=st)[0]
+        x = x + m(x, x, x, key_padding_mask=mask, incremental_state=st)[0]
     return x
 
 
-def run(mods, mode, B, context, steps, blocks=5, warmup=4):
-    """-> (median ms per token, the rows of every timed step)."""
+def run(mods, mode, B, context, steps, blocks=5, warmup=4, lengths=None):
+    """-> (median ms per token, the rows of every timed step).  lengths (per-seq modes): row b is prefilled to lengths[b] <=
+    context tokens instead of `context`."""
     n_tok = context + warmup + 1 + blocks * steps
     torch.manual_seed(1)
     x = 0.5 * torch.randn(n_tok, B, EMBED, device="cuda")
@@ -54,11 +61,17 @@ def run(mods, mode, B, context, steps, blocks=5, warmup=4):
             m.init_static_decoding(st, B, n_tok, torch.bfloat16, "cuda")
         elif mode in ("rolling", "rolling-graph"):
             m.init_rolling_decoding(st, B, n_tok, torch.bfloat16, "cuda")
+        elif mode in ("per-seq", "per-seq-graph"):
+            m.init_static_decoding(st, B, n_tok, torch.bfloat16, "cuda", per_sequence=True)
+        elif mode == "per-seq-rolling-graph":
+            m.init_rolling_decoding(st, B, n_tok, torch.bfloat16, "cuda", per_sequence=True)
         states.append(st)
+    ends = None if lengths is None else torch.tensor(lengths, device="cuda").unsqueeze(1)
     rows, times = [], []
     with torch.no_grad(), torch.autocast("cuda", dtype=torch.bfloat16, cache_enabled=False):
         for a in range(0, context, RECIPE["window_size"]):
-            step(mods, states, x[a:min(a + RECIPE["window_size"], context)])
+            b = min(a + RECIPE["window_size"], context)
+            step(mods, states, x[a:b], None if ends is None else torch.arange(a, b, device="cuda").unsqueeze(0) >= ends)
         t = context
         xin = x[t:t + 1].clone()
         if mode.endswith("graph"):
@@ -95,7 +108,25 @@ def run(mods, mode, B, context, steps, blocks=5, warmup=4):
     return sorted(times)[len(times) // 2], torch.cat(rows, 0)
 
 
-MODES = ("dynamic", "static", "graph", "rolling", "rolling-graph")
+MODES = ("dynamic", "static", "graph", "rolling", "rolling-graph", "per-seq", "per-seq-graph", "per-seq-rolling-graph")
+
+
+def ragged(mods, context, steps):
+    B = 8
+    lengths = [max(1, context * (b + 1) // B) for b in range(B)]
+    print("ms per token, %d layers, bf16, batch %d, per-sequence counts: rows at %s tokens against all rows at %d"
+          % (LAYERS, B, lengths, context))
+    for mode in ("per-seq-graph", "per-seq-rolling-graph"):
+        even, rag = run(mods, mode, B, context, steps)[0], run(mods, mode, B, context, steps, lengths=lengths)[0]
+        print("%22s  uniform %.3f  ragged %.3f" % (mode, even, rag), flush=True)
+    m = mods[0]
+    for name, init in (("static", m.init_static_decoding), ("rolling", m.init_rolling_decoding)):
+        one, per = {}, {}
+        init(one, B, context, torch.bfloat16, "cuda")
+        init(per, B, context, torch.bfloat16, "cuda", per_sequence=True)
+        print("    decoding_state_nbytes per layer, %d tokens, batch %d, %s: shared count %d, per-sequence %d (+%d)"
+              % (context, B, name, m.decoding_state_nbytes(one), m.decoding_state_nbytes(per),
+                 m.decoding_state_nbytes(per) - m.decoding_state_nbytes(one)), flush=True)
 
 
 def state_bytes(m, B, context):
@@ -115,7 +146,11 @@ def main():
     ap.add_argument("--modes", default=",".join(MODES))
     ap.add_argument("--state-bytes", default=None, metavar="CONTEXTS",
                     help="only print the state sizes at these comma-separated contexts (batch 1), no timing")
+    ap.add_argument("--ragged", action="store_true", help="replay time with the rows of a batch of 8 at different counts")
     a = ap.parse_args()
+    if a.ragged:
+        ragged(build(), a.context, a.steps)
+        return
     if a.state_bytes:
         m = build()[0]
         for ctx in [int(c) for c in a.state_bytes.split(",")]:

@@ -1,11 +1,14 @@
 #!/usr/bin/env python3
 """Compare one translation unit's gfx950 machine code between two trees, kernel by kernel.
 
-    python tools/isa_diff.py OTHER_TREE [SOURCE.hip]          (default source: ea_ceva_decode.hip; this tree is the other side)
+    python tools/isa_diff.py [--new-ok] OTHER_TREE [SOURCE.hip]   (default source: ea_ceva_decode.hip; this tree is the other side)
 
 Both sides are compiled with build.py's flags plus `--cuda-device-only -S`.  A kernel's body is what lies between its label
 and its `.Lfunc_end`, comments dropped, local `.L*` labels renumbered in order of appearance, its own symbol replaced.
 Prints the kernels that exist on one side only and those whose bodies differ; exit status 0 only when there are none.
+A kernel whose instructions are equal and whose descriptor (`.amdhsa_*`) alone differs -- a field appended to its parameter
+block changes `.amdhsa_kernarg_size` and nothing else -- is listed as such, with the directives that differ, and with
+`--new-ok` neither it nor a kernel that only this tree has counts against the exit status.
 No GPU needed.  A refactor that must not move device speed shows it this way."""
 import importlib.util
 import os
@@ -40,17 +43,32 @@ def kernels(tree, source):
     return found
 
 
+def _split(lines):
+    """-> (instructions, descriptor directives)"""
+    return [x for x in lines if not x.startswith(".amdhsa_")], [x for x in lines if x.startswith(".amdhsa_")]
+
+
 def main():
-    other, source = sys.argv[1], (sys.argv[2] if len(sys.argv) > 2 else "ea_ceva_decode.hip")
+    args = [x for x in sys.argv[1:] if x != "--new-ok"]
+    new_ok = len(args) != len(sys.argv) - 1
+    other, source = args[0], (args[1] if len(args) > 1 else "ea_ceva_decode.hip")
     a, b = kernels(other, source), kernels(ROOT, source)
-    only = sorted(set(a) ^ set(b))
-    differ = sorted(k for k in set(a) & set(b) if a[k] != b[k])
-    for k in only:
-        print("one side only:", k)
+    gone, new = sorted(set(a) - set(b)), sorted(set(b) - set(a))
+    differ = sorted(k for k in set(a) & set(b) if _split(a[k])[0] != _split(b[k])[0])
+    descr = sorted(k for k in set(a) & set(b) if k not in differ and a[k] != b[k])
+    for k in gone:
+        print("other tree only:", k)
+    for k in new:
+        print("this tree only:", k)
     for k in differ:
-        print("differs (%d / %d instructions): %s" % (len(a[k]), len(b[k]), k))
-    print("%s: %d / %d kernels, %d identical" % (source, len(a), len(b), len(set(a) & set(b)) - len(differ)))
-    return 1 if only or differ else 0
+        print("differs (%d / %d instructions): %s" % (len(_split(a[k])[0]), len(_split(b[k])[0]), k))
+    for k in descr:
+        da, db = _split(a[k])[1], _split(b[k])[1]
+        print("same instructions, descriptor differs (%s): %s"
+              % ("; ".join("%s -> %s" % (x, y) for x, y in zip(da, db) if x != y) or "directives added or dropped", k))
+    print("%s: %d / %d kernels, %d identical, %d identical but for the descriptor"
+          % (source, len(a), len(b), len(set(a) & set(b)) - len(differ) - len(descr), len(descr)))
+    return 1 if gone or differ or (not new_ok and (new or descr)) else 0
 
 
 if __name__ == "__main__":
