@@ -79,7 +79,7 @@ static Geo mk_geo(const ea_geom* g) {
 extern "C" {
 
 const char* ea_version(void) { return "ea_hip 0.1.0 gfx950"; }
-int32_t ea_abi_version(void) { return 20; }
+int32_t ea_abi_version(void) { return 21; }
 
 int32_t ea_window_bias_ld(const ea_geom* g) {
   WinTiling t;
@@ -2192,8 +2192,10 @@ static DecG dec_read(const ea_ceva_sdec_geom* g) {
 }
 // What every launch of a step needs; with `windows`, also what close and attn need of the window geometry (append moves
 // rows and reads none of it).  Every EA_E_BADARG is decided before the head dim, the static state's own before the rest.
-static int dec_check(const DecG& g, const uint8_t* pad, bool windows) {
-  if (g.dev && (!g.pos || !g.status || (uintptr_t)g.pos % 4 || (uintptr_t)g.status % 4 || (uintptr_t)g.ntok % 4 || !pad))
+// (reads_pad = false: merge, the one launch of a static step that takes no pad flags.)
+static int dec_check(const DecG& g, const uint8_t* pad, bool windows, bool reads_pad = true) {
+  if (g.dev && (!g.pos || !g.status || (uintptr_t)g.pos % 4 || (uintptr_t)g.status % 4 || (uintptr_t)g.ntok % 4 ||
+                (reads_pad && !pad)))
     return EA_E_BADARG;
   if (windows && (g.window <= 0 || g.chunk <= 0 || g.ext < 0 || (g.dev && (g.cap % g.window || g.window % g.chunk))))
     return EA_E_BADARG;
@@ -2244,6 +2246,12 @@ static int dec_attn(const DecG& g, const ea_t4* q, const ea_t4* k, const ea_t4* 
   p.bias = g.has_bias ? bias : nullptr;
   return ea::ceva_decode_launch(ea::DEC_ATTN, p, (hipStream_t)stream);
 }
+// What the two launches of a split step add to a static step: 2 .. 64 parts, a 16-byte aligned workspace of fp32 partials
+// [B, H, 8, parts, D + 4], and a step of at most 8 tokens (one query group per window block).  Decided first, like every
+// EA_E_BADARG of the static state.
+static int split_check(const ea_ceva_sdec_geom* g, int parts, const void* ws) {
+  return g && g->pos && parts >= 2 && parts <= 64 && ws && (uintptr_t)ws % 16 == 0 && g->T_new <= 8 ? EA_OK : EA_E_BADARG;
+}
 
 extern "C" {
 
@@ -2278,6 +2286,32 @@ int ea_ceva_sdecode_close(const ea_ceva_sdec_geom* g, const ea_t4* q, const ea_t
 int ea_ceva_sdecode_attn(const ea_ceva_sdec_geom* g, const ea_t4* q, const ea_t4* k, const ea_t4* v, const uint8_t* pad,
                          const float* bias, const ea_t4* rf_k_bar, const ea_t4* beta, const ea_t4* out, void* stream) {
   return g ? dec_attn(dec_read(g), q, k, v, pad, bias, rf_k_bar, beta, out, stream) : EA_E_BADARG;
+}
+
+int ea_ceva_sdecode_attn_split(const ea_ceva_sdec_geom* g, const ea_t4* q, const ea_t4* k, const ea_t4* v, const uint8_t* pad,
+                               const float* bias, const ea_t4* rf_k_bar, const ea_t4* beta, const ea_t4* out, int32_t parts,
+                               float* ws, void* stream) {
+  if (split_check(g, parts, ws) != EA_OK) return EA_E_BADARG;
+  const DecG dg = dec_read(g);
+  ea::DecP p = {};
+  const int rc = dec_fill(dg, q, k, v, pad, rf_k_bar, beta, p);
+  if (rc != EA_OK) return rc;
+  if (!dec_t4_ok(out, dg.D, dg.dtype == EA_F32 ? 4 : 2) || (dg.has_bias && !bias)) return EA_E_BADARG;
+  p.o = dec_mk(out);
+  p.bias = dg.has_bias ? bias : nullptr;
+  return ea::ceva_sdecode_attn_split(p, parts, ws, (hipStream_t)stream);
+}
+
+int ea_ceva_sdecode_merge(const ea_ceva_sdec_geom* g, const ea_t4* out, int32_t parts, const float* ws, void* stream) {
+  if (split_check(g, parts, ws) != EA_OK) return EA_E_BADARG;
+  const DecG dg = dec_read(g);
+  const int rc = dec_check(dg, nullptr, true, false);
+  if (rc != EA_OK) return rc;
+  if (!dec_t4_ok(out, dg.D, dg.dtype == EA_F32 ? 4 : 2)) return EA_E_BADARG;
+  ea::DecMergeP p = {};
+  p.o = dec_mk(out); p.ws = ws; p.pos = dg.pos; p.ntok = dg.ntok;
+  p.H = dg.H; p.T = dg.T_new; p.cap = dg.cap; p.parts = parts;
+  return ea::ceva_sdecode_merge(p, dg.D, dg.dtype, dg.B * dg.H, (hipStream_t)stream);
 }
 
 int ea_ceva_sdecode_advance(const ea_ceva_sdec_geom* g, void* stream) {

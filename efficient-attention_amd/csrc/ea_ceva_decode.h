@@ -38,10 +38,28 @@ struct AppP {                 // static decoding, append: the step's rows into t
                               // src_pad; pos and status are [B] then, and nothing is stored for the flagged positions.  null = shared
 };
 
+struct DecSplitP {               // attn_split: a DEV step of at most 8 tokens, its tile range shared by `parts` workgroups
+  DecP d;                     // the step, as attn takes it (d.pos != null)
+  float* ws;                  // [B, H, 8, parts, D + 4] fp32 partials (acc[D], m, l, 2 unused) of the step's tokens
+  int parts;
+};
+
+struct DecMergeP {               // merge: out row t = the parts of step token t combined and normalised
+  DecT o;                     // out [B,H,T_new,D] (dtype)
+  const float* ws;
+  const int32_t* pos;
+  const int32_t* ntok;        // null = shared count
+  int H, T, cap, parts;
+};
+
 enum DecKind { DEC_CLOSE, DEC_ATTN };
 // the step's close or attn launch; p.pos != null: t0 = *p.pos (needs p.pad); p.ring != 0: ring rows (needs p.pos);
 // p.ntok != null: t0 = p.pos[b], p.ntok[b] tokens (needs p.pos)
 int ceva_decode_launch(DecKind kind, const DecP& p, hipStream_t st);
+// attn as two launches for a DEV step of T <= 8 tokens (ea_ceva_decode_split.h): `parts` workgroups per window block write
+// partials to ws, then one workgroup per token combines them; p as for DEC_ATTN, 2 <= parts <= 64
+int ceva_sdecode_attn_split(const DecP& p, int parts, float* ws, hipStream_t st);
+int ceva_sdecode_merge(const DecMergeP& p, int D, int dtype, int BH, hipStream_t st);
 int ceva_sdecode_append(const AppP& p, hipStream_t st);
 // *pos += T; ntok != null: pos[b] += ntok[b] for the B elements
 int ceva_sdecode_advance(int32_t* pos, const int32_t* ntok, int B, int T, int cap, hipStream_t st);

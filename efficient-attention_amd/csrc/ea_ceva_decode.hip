@@ -37,6 +37,8 @@
 //        and overflow is per element: status[b], NaN rows of b alone.  The grids stay those of T tokens; a workgroup whose
 //        element needs less exits at once.  `Step` owns both numbers; no kernel body reads p.T for anything else.  The SEQ
 //        kernels have names of their own (ceva_*_seq_kernel, ea_ceva_decode_step.h), so the others keep their symbols and code.
+// A DEV step of at most QPW tokens can run attn as two launches, attn_split -> merge, with the tiles of a window block shared
+// by several workgroups (ea_ceva_decode_split.h): kernels of their own again, the ones above are not touched.
 #include "ea_common.h"
 #include "ea_ceva_decode.h"
 
@@ -230,6 +232,11 @@ EA_DEV int first_flag(const uint8_t* f, int T, int* red) {
 #undef CEVA_SEQ
 #undef CEVA_KERNEL
 
+// ---- a short step with its landmark range split over workgroups (ea_ceva_decode_split.h) -------------------------------
+#define CEVA_SPLIT_TEXT
+#include "ea_ceva_decode_split.h"
+#undef CEVA_SPLIT_TEXT
+
 // *pos += T, in a launch of its own after attn on the same stream: stream order puts it behind every read of *pos in the
 // step.  (The other way, the last attn workgroup advancing through a completion counter, needs an agent-scope release /
 // acquire pair across XCDs and a counter that every replay must find reset; a dependent launch boundary costs about
@@ -269,6 +276,33 @@ DecKernel kernel_of(int D, DecKind kind, bool dev, bool ring, bool seq) {
   }
 }
 
+using SplitKernel = void (*)(const DecSplitP);
+using MergeKernel = void (*)(const DecMergeP);
+
+template <typename E, int D>
+SplitKernel split_of(bool ring, bool seq) {
+  if (seq) return ring ? ceva_attn_split_kernel<E, D, true, true> : ceva_attn_split_kernel<E, D, false, true>;
+  return ring ? ceva_attn_split_kernel<E, D, true, false> : ceva_attn_split_kernel<E, D, false, false>;
+}
+
+template <typename E>
+SplitKernel split_of(int D, bool ring, bool seq) {
+  switch (D) {
+    case 32: return split_of<E, 32>(ring, seq);
+    case 64: return split_of<E, 64>(ring, seq);
+    default: return split_of<E, 128>(ring, seq);
+  }
+}
+
+template <typename E>
+MergeKernel merge_of(int D, bool seq) {
+  switch (D) {
+    case 32: return seq ? ceva_merge_kernel<E, 32, true> : ceva_merge_kernel<E, 32, false>;
+    case 64: return seq ? ceva_merge_kernel<E, 64, true> : ceva_merge_kernel<E, 64, false>;
+    default: return seq ? ceva_merge_kernel<E, 128, true> : ceva_merge_kernel<E, 128, false>;
+  }
+}
+
 }  // namespace
 
 // DEV / RING / SEQ follow the state: p.pos != null / p.ring != 0 / p.ntok != null.  (The C entry points have checked the
@@ -288,6 +322,39 @@ int ceva_decode_launch(DecKind kind, const DecP& p, hipStream_t st) {
   const int nx = kind == DEC_CLOSE ? (dev ? (p.T + p.r - 1) / p.r : p.c_last - p.c_first + 1)
                                    : (dev ? (p.T + p.w - 2) / p.w + 1 : (p.t0 + p.T - 1) / p.w - p.t0 / p.w + 1);
   hipLaunchKernelGGL(kernel, dim3((unsigned)nx, (unsigned)(p.B * p.H)), dim3(NT), 0, st, p);
+  return (int)hipGetLastError();
+}
+
+// (The C entry points have checked parts, the workspace and T <= QPW.)
+int ceva_sdecode_attn_split(const DecP& p, int parts, float* ws, hipStream_t st) {
+  const bool ring = p.ring != 0, seq = p.ntok != nullptr;
+  if (!p.pos || !p.pad || !ws || parts < 2 || parts > 64 || p.T > QPW) return EA_E_BADARG;
+  if (p.D != 32 && p.D != 64 && p.D != 128) return EA_E_UNSUPPORTED;
+  SplitKernel kernel;
+  switch (p.dtype) {
+    case EA_BF16: kernel = split_of<BF16>(p.D, ring, seq); break;
+    case EA_F16: kernel = split_of<F16>(p.D, ring, seq); break;
+    case EA_F32: kernel = split_of<float>(p.D, ring, seq); break;
+    default: return EA_E_BADARG;
+  }
+  const int nx = (p.T + p.w - 2) / p.w + 1;        // the most window blocks T tokens can touch
+  const DecSplitP sp = {p, ws, parts};
+  hipLaunchKernelGGL(kernel, dim3((unsigned)(nx * parts), (unsigned)(p.B * p.H)), dim3(NT), 0, st, sp);
+  return (int)hipGetLastError();
+}
+
+int ceva_sdecode_merge(const DecMergeP& p, int D, int dtype, int BH, hipStream_t st) {
+  const bool seq = p.ntok != nullptr;
+  if (!p.pos || !p.ws || p.parts < 2 || p.parts > 64 || p.T > QPW) return EA_E_BADARG;
+  if (D != 32 && D != 64 && D != 128) return EA_E_UNSUPPORTED;
+  MergeKernel kernel;
+  switch (dtype) {
+    case EA_BF16: kernel = merge_of<BF16>(D, seq); break;
+    case EA_F16: kernel = merge_of<F16>(D, seq); break;
+    case EA_F32: kernel = merge_of<float>(D, seq); break;
+    default: return EA_E_BADARG;
+  }
+  hipLaunchKernelGGL(kernel, dim3((unsigned)p.T, (unsigned)BH), dim3(64), 0, st, p);
   return (int)hipGetLastError();
 }
 

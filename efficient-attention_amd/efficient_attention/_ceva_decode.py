@@ -12,10 +12,13 @@ index becomes a cache row (csrc/ea_ceva_decode.hip).  There is one step body, `_
 
 and in nothing else.  A static or rolling state made with `per_sequence=True` keeps one count PER BATCH ROW (`pos [B]`): the
 same four launches, each row taking its own number of the step's tokens (`_step_flags`), with no host shadow at all.
+A static or rolling state made with `landmark_splits=P > 1` runs attn of a step of at most 8 tokens as two launches,
+ea_ceva_sdecode_attn_split (P workgroups per window block share the landmark rows) and ea_ceva_sdecode_merge.
 """
 import ctypes
 import functools
 import inspect
+import numbers
 
 import torch
 
@@ -28,23 +31,32 @@ _NEEDS_CHUNK_SIZE = ("incremental decoding needs --chunk-size (with --num-chunks
 # element, the token count `pos` is shared); a per-sequence state adds its per-row counters
 _STATIC_BATCH_FIRST = ("qkv", "rf_k_bar", "beta", "pad")
 _PER_SEQUENCE = ("pos", "status", "ntok")
+_SPLIT_MAX_STEP = 8          # QPW of ea_ceva_decode.hip: a step of at most this many tokens has one query group per window block
+_SPLIT_MAX_PARTS = 64
 
 
-def _per_sequence_option(init):
-    """The keyword-only `per_sequence=False` of the two `init_*_decoding` methods.  The methods keep the positional interface
-    they had, and that is the signature they report (`__signature__`: callers that pin the parameter list, this package's
-    own tests among them, see what they saw); the option is taken off here and handed to the method as its last argument.
-    Arguments are bound as Python binds them: `per_sequence` by position, or an unknown keyword, is a TypeError."""
+def _state_options(init):
+    """The keyword-only `per_sequence=False` and `landmark_splits=1` of the two `init_*_decoding` methods.  The methods keep
+    the positional interface they had, and that is the signature they report (`__signature__`: callers that pin the parameter
+    list, this package's own tests among them, see what they saw); the options are taken off here and handed to the method
+    as its last arguments.  Arguments are bound as Python binds them: an option by position, or an unknown keyword, is a
+    TypeError.  (`landmark_splits` is handed on as given: the method checks it behind its other refusals.)"""
     positional = inspect.signature(init)
-    positional = positional.replace(parameters=list(positional.parameters.values())[:-1])
+    positional = positional.replace(parameters=list(positional.parameters.values())[:-2])
 
     @functools.wraps(init)
-    def with_option(self, *args, per_sequence=False, **kwargs):
+    def with_options(self, *args, per_sequence=False, landmark_splits=1, **kwargs):
         bound = positional.bind(self, *args, **kwargs)
         bound.apply_defaults()
-        return init(*bound.args, bool(per_sequence), **bound.kwargs)
-    with_option.__signature__ = positional
-    return with_option
+        return init(*bound.args, bool(per_sequence), landmark_splits, **bound.kwargs)
+    with_options.__signature__ = positional
+    return with_options
+
+
+def _check_landmark_splits(P):
+    if isinstance(P, bool) or not isinstance(P, numbers.Integral) or not 1 <= P <= _SPLIT_MAX_PARTS:
+        raise ValueError("landmark_splits must be an int in [1, %d], got %r" % (_SPLIT_MAX_PARTS, P))
+    return int(P)
 
 
 class CevaDecoding:
@@ -73,8 +85,9 @@ class CevaDecoding:
         return [_ops._f32c(p) for p in self._mu_params()]
 
     # ---- static and rolling states ----------------------------------------------------------------------------------------
-    @_per_sequence_option
-    def init_static_decoding(self, incremental_state, batch_size, max_tokens, dtype, device, per_sequence=False):
+    @_state_options
+    def init_static_decoding(self, incremental_state, batch_size, max_tokens, dtype, device, per_sequence=False,
+                             landmark_splits=1):
         """Allocate, once, every buffer a decoding step touches and mark this module's incremental state as STATIC: every
         later `forward(..., incremental_state=incremental_state)` then runs a step that can be captured into a graph
         (`torch.cuda.graph`) and replayed -- the token count lives in device memory and the kernels advance it: four
@@ -106,15 +119,31 @@ class CevaDecoding:
         and overflow is per row -- a row whose step would pass cap writes nothing, gets status[b] = 1 and NaN output rows
         and keeps its count, the other rows of the step are unaffected (`static_decoding_overflowed_rows`).  With equal
         counts and no mask the outputs and the state equal those of the shared count bit for bit.
-        `reset_decoding_rows` restarts rows; `decoding_positions` reads the counts back."""
+        `reset_decoding_rows` restarts rows; `decoding_positions` reads the counts back.
+        `landmark_splits=P` (an int in [1, 64], default 1; combines with `per_sequence`): a step's attn launch runs one
+        workgroup per (window block, b, h) and streams every landmark row of the context through it, so a 1-token step at a
+        long context and a small batch keeps B h of the device's 256 compute units busy and is bound by the latency of one.
+        With P > 1 a step of AT MOST 8 TOKENS (the single-token step, a short verify step) takes five launches instead:
+        append, close, ea_ceva_sdecode_attn_split -- P workgroups per (window block, b, h) share the 64-column tiles of
+        [local keys, landmarks] and write unnormalised (max, sum, acc) partials -- ea_ceva_sdecode_merge, advance.  A larger
+        step (a prompt, and every piece a rolling state cuts it into) keeps the four launches: its many queries already give
+        it workgroups.  The choice depends on the step's token count alone, which a capture fixes.  The state holds one more tensor,
+            split_ws  [B, h, 8, P, d + 4] fp32: the partials of one step, allocated here so that a captured step allocates
+                                          nothing; scratch, fully rewritten by every step that reads it (a beam reorder and
+                                          `reset_decoding_rows` leave it alone; `decoding_state_nbytes` counts it).
+        Choosing P: about 256 / (B h) workgroups per (b, h) fill the device (B = 1, h = 8: 32; B = 8, h = 8: 4); more parts
+        than the context has 64-landmark tiles, ceil(tokens / (64 r)) of them, buy nothing, and at a short context the
+        extra launch costs more than the split saves.  The split changes the order in which a row's partial sums are merged,
+        so its outputs equal the unsplit step's to rounding, not bit for bit; P = 1 is the unsplit state in every respect."""
         B, T, device = self._check_static_decoding(batch_size, max_tokens, dtype, device)
+        P = _check_landmark_splits(landmark_splits)
         w = self.window_size
         cap = -(-T // w) * w
-        return self._alloc_static_decoding(incremental_state, B, cap, cap, dtype, device, {"count": 0}, per_sequence)
+        return self._alloc_static_decoding(incremental_state, B, cap, cap, dtype, device, {"count": 0}, per_sequence, P)
 
-    @_per_sequence_option
+    @_state_options
     def init_rolling_decoding(self, incremental_state, batch_size, max_tokens, dtype, device, max_step_tokens=None,
-                              per_sequence=False):
+                              per_sequence=False, landmark_splits=1):
         """`init_static_decoding` with the token rows in a fixed RING: the state is static in every respect (the same step,
         capturable and replayable; `static_decoding_overflowed` and the in-place `reorder_incremental_state` work on it), but
         `qkv` and `pad` hold R token slots instead of one row per token ever decoded, token n in slot n % R:
@@ -136,17 +165,21 @@ class CevaDecoding:
         Refuses what `init_static_decoding` refuses, with the same messages, and `max_step_tokens <= 0`.
         `per_sequence=True`: per-row counts as in `init_static_decoding`; every row walks its own ring.  The pieces of a long
         ragged prompt carry the matching slices of the (monotone) mask, so a row that ended in one piece takes nothing from
-        the later ones."""
+        the later ones.
+        `landmark_splits=P`: as in `init_static_decoding` -- the landmark rows, which a rolling state keeps for the whole
+        context, are what a step of at most 8 tokens shares between P workgroups per (window block, b, h).  About
+        256 / (B h) parts fill the device; more than ceil(tokens / (64 r)) buy nothing."""
         B, T, device = self._check_static_decoding(batch_size, max_tokens, dtype, device)
         w, e = self.window_size, self.ext_size
         S = w if max_step_tokens is None else int(max_step_tokens)
         if S <= 0:
             raise ValueError("rolling decoding needs max_step_tokens > 0, got %d" % S)
+        P = _check_landmark_splits(landmark_splits)
         cap = -(-T // w) * w
         ring = -(-(w + e + S) // w) * w
         rows = min(ring, cap)
         static = {"count": 0, "cap": cap, "ring": ring if ring < cap else 0, "max_step": S}
-        return self._alloc_static_decoding(incremental_state, B, cap, rows, dtype, device, static, per_sequence)
+        return self._alloc_static_decoding(incremental_state, B, cap, rows, dtype, device, static, per_sequence, P)
 
     def _check_static_decoding(self, batch_size, max_tokens, dtype, device):
         """What a static (or rolling) state refuses, before anything is allocated -> (B, max_tokens, device)."""
@@ -164,9 +197,10 @@ class CevaDecoding:
             raise ValueError("static decoding needs batch_size > 0 and max_tokens > 0, got %d, %d" % (B, T))
         return B, T, device
 
-    def _alloc_static_decoding(self, incremental_state, B, cap, rows, dtype, device, static, per_sequence=False):
+    def _alloc_static_decoding(self, incremental_state, B, cap, rows, dtype, device, static, per_sequence=False, splits=1):
         """The buffers of a static state: `rows` token rows (cap, or a ring), cap / r landmark rows; one counter and one
-        overflow flag, or (per_sequence) one of each per batch row and the rows' token counts of a step."""
+        overflow flag, or (per_sequence) one of each per batch row and the rows' token counts of a step; splits > 1: the
+        workspace of a short step's partials."""
         h, d, r = self.num_heads, self.head_dim, self.chunk_size
         nc = B if per_sequence else 1
         state = {
@@ -180,6 +214,9 @@ class CevaDecoding:
         if per_sequence:
             state["ntok"] = torch.zeros((B,), dtype=torch.int32, device=device)
             static["per_sequence"] = True
+        static["landmark_splits"] = splits
+        if splits > 1:
+            state["split_ws"] = torch.zeros((B, h, _SPLIT_MAX_STEP, splits, d + 4), dtype=torch.float32, device=device)
         with torch.no_grad():
             state["bias"] = self._decode_bias_table(device)
             state["mu"] = self._decode_mu_f32()
@@ -191,7 +228,8 @@ class CevaDecoding:
 
     def decoding_state_nbytes(self, incremental_state):
         """Bytes of every tensor in this module's decoding buffer (dynamic, static or rolling): token rows, pad flags,
-        landmark rows, counters and, for a static state, the bias table and the fp32 mu parameters it holds.  Host only."""
+        landmark rows, counters and, for a static state, the bias table, the fp32 mu parameters it holds and the workspace
+        of `landmark_splits`.  Host only."""
         def nbytes(v):
             if torch.is_tensor(v):
                 return v.numel() * v.element_size()
@@ -318,7 +356,7 @@ class CevaDecoding:
         return key_padding_mask[:, -T_new:].ne(0).to(torch.int32).cumsum(1).ne(0)
 
     # ---- the step -------------------------------------------------------------------------------------------------------------
-    def _decode(self, query, key_padding_mask, incremental_state):
+    def _decode(self, query, key_padding_mask, incremental_state, piece=False):
         """Token-by-token decoding with fairseq's incremental state.
 
         The reference's branch for this (causal_eva.py:537-665) cannot run as shipped -- `N` and `B` are bound only when
@@ -343,7 +381,8 @@ class CevaDecoding:
         cache's dtype, so fp32 decoding equals the fp32 full path; on a dynamic state which chunks close is decided on the
         host from the token count, with no read-back.  No limit on the context length or the number of landmarks.
         A state made by `init_static_decoding` / `init_rolling_decoding` (docstrings there) takes the same step with the
-        right-hand column of this module's table; on a rolling state the launches address the token rows through the ring."""
+        right-hand column of this module's table; on a rolling state the launches address the token rows through the ring, and on
+        a state with `landmark_splits > 1` a step of at most 8 tokens runs attn as attn_split + merge."""
         nv = _ops.nv
         self._refuse_decoding()
         nv.require_cuda(query, "query")                            # (before any state is built: no CPU fallback)
@@ -369,7 +408,7 @@ class CevaDecoding:
                 # in both of fairseq's mask shapes, sliced with the pieces
                 step_pad = None if key_padding_mask is None else key_padding_mask[:, -T_new:]
                 ys = [self._decode(query[a:a + pieces], None if step_pad is None else step_pad[:, a:a + pieces],
-                                   incremental_state)[0] for a in range(0, T_new, pieces)]
+                                   incremental_state, piece=True)[0] for a in range(0, T_new, pieces)]
                 return torch.cat(ys, 0), None
         qkv_new = self._project(query, None, None, keep_f32=True)  # [T_new, B, 3, h, d]
         if static is None:
@@ -437,8 +476,16 @@ class CevaDecoding:
                     ctypes.byref(tl), ctypes.byref(tb), st)
         out = torch.empty((T_new, B, h, d), dtype=cache.dtype, device=dev)
         to = nv.t4(out.permute(1, 2, 0, 3))                        # [B, h, T_new, d] view of the time-first rows
-        nv.call(family + "attn", g, ctypes.byref(tq), ctypes.byref(tk), ctypes.byref(tv), mask_p, nv.ptr(bias),
-                ctypes.byref(tl), ctypes.byref(tb), ctypes.byref(to), st)
+        if static is not None and "split_ws" in state and T_new <= _SPLIT_MAX_STEP and not piece:
+            # (the token count of the step the caller handed over decides, and a capture fixes it; the pieces of a prompt,
+            #  its short tail included, are the prompt's)
+            ws, parts = state["split_ws"], state["split_ws"].shape[3]
+            nv.call("ea_ceva_sdecode_attn_split", g, ctypes.byref(tq), ctypes.byref(tk), ctypes.byref(tv), mask_p, nv.ptr(bias),
+                    ctypes.byref(tl), ctypes.byref(tb), ctypes.byref(to), parts, nv.ptr(ws), st)
+            nv.call("ea_ceva_sdecode_merge", g, ctypes.byref(to), parts, nv.ptr(ws), st)
+        else:
+            nv.call(family + "attn", g, ctypes.byref(tq), ctypes.byref(tk), ctypes.byref(tv), mask_p, nv.ptr(bias),
+                    ctypes.byref(tl), ctypes.byref(tb), ctypes.byref(to), st)
         if static is not None:
             nv.call("ea_ceva_sdecode_advance", g, st)
             if not capturing and "ntok" not in state:              # (a replay advances only the device count; per-sequence

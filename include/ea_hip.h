@@ -996,7 +996,19 @@ int ea_ceva_decode_attn(const ea_ceva_dec_geom* g, const ea_t4* q, const ea_t4* 
  * above; attn writes zero rows n_b .. T_new - 1 of element b; advance adds n_b to pos[b].  The launches and their grids are
  * those of T_new tokens.  An element with pos[b] + n_b > cap writes no byte of its state: status[b] = 1, its T_new output rows
  * are NaN, pos[b] stays; the other elements of the step are not affected.  For n_b = T_new everywhere the outputs and the
- * state equal those of ntok = NULL bit for bit.  ntok = NULL is exactly the contract of ABI 19. */
+ * state equal those of ntok = NULL bit for bit.  ntok = NULL is exactly the contract of ABI 19.
+ * ABI 21, a step of T_new <= 8 tokens with its landmark range split over workgroups (init_*_decoding(landmark_splits=P)):
+ * ea_ceva_sdecode_attn streams every landmark row of a (b, h) through one workgroup; the two calls below replace it, in its
+ * place between close and advance, and take the geometry unchanged.
+ *   ea_ceva_sdecode_attn_split: `parts` workgroups per (window block, b, h) share the 64-column tiles of [local keys, then
+ *     landmarks] -- wave s of part p takes tiles 4 p + s, + 4 parts, .. -- with the arithmetic of ea_ceva_sdecode_attn, and
+ *     write, for every live query, the unnormalised partial (acc[D], max, sum) to ws: fp32 [B, H, 8, parts, D + 4], 16-byte
+ *     aligned, row (b, h, t - *pos, part); a part without a tile writes max = -inf, sum = 0.  Writes `out` only where the step
+ *     refuses: NaN rows (no partial) when it does not fit, zero rows n_b .. T_new - 1 of a per-sequence element.
+ *   ea_ceva_sdecode_merge: out row t = sum_p f_p acc_p / sum_p f_p l_p, f_p = exp(m_p - max_p m_p) (0 for m_p = -inf), for the
+ *     live queries; it leaves the NaN and zero rows alone.  Stream order puts it behind attn_split and before advance.
+ * ws is scratch: every row that merge reads has been written by the attn_split before it.  EA_E_BADARG: parts outside
+ * [2, 64], ws NULL or not 16-byte aligned, T_new > 8, pos NULL; every other refusal is that of ea_ceva_sdecode_attn. */
 typedef struct {
   int32_t B, H, D;
   int32_t dtype;             /* EA_BF16 | EA_F16 | EA_F32: the cache rows and out */
@@ -1016,6 +1028,10 @@ int ea_ceva_sdecode_close(const ea_ceva_sdec_geom* g, const ea_t4* q, const ea_t
                           const float* const* mu_params, const ea_t4* rf_k_bar, const ea_t4* beta, void* stream);
 int ea_ceva_sdecode_attn(const ea_ceva_sdec_geom* g, const ea_t4* q, const ea_t4* k, const ea_t4* v, const uint8_t* pad,
                          const float* bias, const ea_t4* rf_k_bar, const ea_t4* beta, const ea_t4* out, void* stream);
+int ea_ceva_sdecode_attn_split(const ea_ceva_sdec_geom* g, const ea_t4* q, const ea_t4* k, const ea_t4* v, const uint8_t* pad,
+                               const float* bias, const ea_t4* rf_k_bar, const ea_t4* beta, const ea_t4* out, int32_t parts,
+                               float* ws, void* stream);
+int ea_ceva_sdecode_merge(const ea_ceva_sdec_geom* g, const ea_t4* out, int32_t parts, const float* ws, void* stream);
 int ea_ceva_sdecode_advance(const ea_ceva_sdec_geom* g, void* stream);
 
 #ifdef __cplusplus

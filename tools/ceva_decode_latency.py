@@ -1,5 +1,5 @@
 """Per-token latency of CausalEVAttention decoding at the wikitext-103 LM geometry (embed 1024, h 8, d 128, w 128, chunks of 8,
-T5 bias, adaptive 'qk'), 16 stacked residual attention layers (x + attn(x), no FFN), bf16 autocast, in eight modes:
+T5 bias, adaptive 'qk'), 16 stacked residual attention layers (x + attn(x), no FFN), bf16 autocast, in twelve modes:
  - dynamic:       the incremental state of `_decode` (host token count, two decode launches per layer step);
  - static:        `init_static_decoding`, the same step run eagerly (four decode launches per layer step);
  - graph:         that static step over all 16 layers captured once with torch.cuda.graph and replayed;
@@ -7,7 +7,11 @@ T5 bias, adaptive 'qk'), 16 stacked residual attention layers (x + attn(x), no F
  - rolling-graph: that step captured and replayed;
  - per-seq, per-seq-graph, per-seq-rolling-graph: static, graph and rolling-graph on a state with per-sequence token counts
    (`per_sequence=True`), every row at the same count and no mask, so that the rows compare bitwise with the other modes.
-   python tools/ceva_decode_latency.py [--context 512] [--steps 64] [--modes dynamic,static,graph,...]   (GPU)
+ - split-graph, split-rolling-graph, per-seq-split-graph, per-seq-split-rolling-graph: graph, rolling-graph and their
+   per-sequence twins on a state made with `landmark_splits=P` (`--splits P`, default 256 / (B h)): the 1-token step runs attn
+   as attn_split + merge, P workgroups per (b, h).  Their rows differ from the unsplit modes' in rounding (another order of
+   the partial sums) and equal each other bitwise; the printed comparison reports the largest difference where rows differ.
+   python tools/ceva_decode_latency.py [--context 512|4096|32768] [--steps 64] [--splits P] [--modes dynamic,static,graph,...]   (GPU)
    python tools/ceva_decode_latency.py --ragged [--context 512] [--steps 64]     (GPU)
 `--ragged`: batch 8 on per-sequence states, row b prefilled to (b + 1) / 8 of `context` by right-padded steps, then the
 captured 1-token step replayed with every row live -- rows at eight different counts in one replay -- next to the same
@@ -47,17 +51,28 @@ def step(mods, states, x, mask=None):
     return x
 
 
-def run(mods, mode, B, context, steps, blocks=5, warmup=4, lengths=None):
+def default_splits(B):
+    """About 256 / (B h) workgroups per (b, h) fill the device."""
+    return max(2, min(64, 256 // (B * HEADS)))
+
+
+def run(mods, mode, B, context, steps, blocks=5, warmup=4, lengths=None, splits=None):
     """-> (median ms per token, the rows of every timed step).  lengths (per-seq modes): row b is prefilled to lengths[b] <=
-    context tokens instead of `context`."""
+    context tokens instead of `context`.  splits (split modes): landmark_splits of the states, default_splits(B) when None."""
     n_tok = context + warmup + 1 + blocks * steps
     torch.manual_seed(1)
     x = 0.5 * torch.randn(n_tok, B, EMBED, device="cuda")
     states = []
+    opt = dict(per_sequence=True) if mode.startswith("per-seq") else {}
+    if "split" in mode:
+        opt["landmark_splits"] = splits or default_splits(B)
     for m in mods:
         st = {}
         m.init_incremental_state()
-        if mode in ("static", "graph"):
+        if "split" in mode:
+            init = m.init_rolling_decoding if "rolling" in mode else m.init_static_decoding
+            init(st, B, n_tok, torch.bfloat16, "cuda", **opt)
+        elif mode in ("static", "graph"):
             m.init_static_decoding(st, B, n_tok, torch.bfloat16, "cuda")
         elif mode in ("rolling", "rolling-graph"):
             m.init_rolling_decoding(st, B, n_tok, torch.bfloat16, "cuda")
@@ -108,7 +123,9 @@ def run(mods, mode, B, context, steps, blocks=5, warmup=4, lengths=None):
     return sorted(times)[len(times) // 2], torch.cat(rows, 0)
 
 
-MODES = ("dynamic", "static", "graph", "rolling", "rolling-graph", "per-seq", "per-seq-graph", "per-seq-rolling-graph")
+MODES = ("dynamic", "static", "graph", "rolling", "rolling-graph", "per-seq", "per-seq-graph", "per-seq-rolling-graph",
+         "split-graph", "split-rolling-graph", "per-seq-split-graph", "per-seq-split-rolling-graph")
+CONTEXTS = (512, 4096, 32768)
 
 
 def ragged(mods, context, steps):
@@ -141,7 +158,10 @@ def state_bytes(m, B, context):
 
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument("--context", type=int, default=512)
+    ap.add_argument("--context", type=int, default=512, help="tokens before the timed steps; DESIGN.md 4a uses %s" % (CONTEXTS,))
+    ap.add_argument("--splits", type=int, default=None, metavar="P",
+                    help="landmark_splits of the split modes (default: 256 / (B h), i.e. 32 at batch 1 and 4 at batch 8)")
+    ap.add_argument("--batches", default="1,8", help="comma-separated batch sizes")
     ap.add_argument("--steps", type=int, default=64)
     ap.add_argument("--modes", default=",".join(MODES))
     ap.add_argument("--state-bytes", default=None, metavar="CONTEXTS",
@@ -163,14 +183,19 @@ def main():
     mods = build()
     print("ms per token, %d layers, bf16, context %d" % (LAYERS, a.context))
     print("%3s " % "B" + " ".join("%13s" % m for m in modes) + "  rows equal (%s vs %s)" % (", ".join(modes[1:]), modes[0]))
-    for B in (1, 8):
-        res = {mode: run(mods, mode, B, a.context, a.steps) for mode in modes}
+    for B in [int(b) for b in a.batches.split(",")]:
+        res = {mode: run(mods, mode, B, a.context, a.steps, splits=a.splits) for mode in modes}
         ref = res[modes[0]][1]
-        same = [torch.equal(res[mode][1], ref) for mode in modes[1:]]
+        same = [torch.equal(res[mode][1], ref) or "max |d| %.2e" % (res[mode][1].float() - ref.float()).abs().max().item()
+                for mode in modes[1:]]
         print("%3d " % B + " ".join("%13.3f" % res[m][0] for m in modes) + "  %s" % same, flush=True)
         sb, rb = state_bytes(mods[0], B, a.context)
         print("    decoding_state_nbytes per layer, %d tokens, batch %d: static %d, rolling %d" % (a.context, B, sb, rb),
               flush=True)
+        if [m for m in modes if "split" in m]:
+            P = a.splits or default_splits(B)
+            print("    landmark_splits %d: + %d bytes of workspace per layer" % (P, B * HEADS * 8 * P * (EMBED // HEADS + 4) * 4),
+                  flush=True)
 
 
 if __name__ == "__main__":
