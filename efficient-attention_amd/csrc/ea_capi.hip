@@ -79,7 +79,7 @@ static Geo mk_geo(const ea_geom* g) {
 extern "C" {
 
 const char* ea_version(void) { return "ea_hip 0.1.0 gfx950"; }
-int32_t ea_abi_version(void) { return 21; }
+int32_t ea_abi_version(void) { return 22; }
 
 int32_t ea_window_bias_ld(const ea_geom* g) {
   WinTiling t;
@@ -2161,6 +2161,7 @@ int ea_layernorm_bwd(int32_t xtype, int32_t rows, int32_t C, const void* x, cons
 
 // ---- causal EVA, incremental decoding (ea_ceva_decode.hip) ----
 #include "ea_ceva_decode.h"
+#include "ea_ceva_decode_linear.h"
 static bool dec_t4_ok(const ea_t4* t, int D, int esz) {
   const int a = 16 / esz;                                 // 16-byte aligned rows
   return t && t->ptr && ((uintptr_t)t->ptr % 16 == 0) && t->sb % a == 0 && t->sh % a == 0 && t->sn % a == 0 && t->sn >= D;
@@ -2318,6 +2319,22 @@ int ea_ceva_sdecode_advance(const ea_ceva_sdec_geom* g, void* stream) {
   if (!g || !g->pos || (uintptr_t)g->pos % 4 || g->T_new <= 0 || g->cap < g->T_new) return EA_E_BADARG;
   if (g->ntok && ((uintptr_t)g->ntok % 4 || g->B <= 0)) return EA_E_BADARG;
   return ea::ceva_sdecode_advance(const_cast<int32_t*>(g->pos), g->ntok, g->B, g->T_new, g->cap, (hipStream_t)stream);
+}
+
+int ea_ceva_sdecode_linear(int32_t M, int32_t K, int32_t N, const void* x, int32_t x_dtype, int64_t ldx,
+                           const void* w, int32_t w_dtype, const void* bias, void* y, int32_t y_dtype, int64_t ldy,
+                           void* stream) {
+  if (!x || !w || !y || (uintptr_t)x % 16 || (uintptr_t)w % 16 || (uintptr_t)y % 16 || (uintptr_t)bias % 16) return EA_E_BADARG;
+  if (w_dtype != EA_BF16 && w_dtype != EA_F16) return EA_E_BADARG;
+  if ((x_dtype != EA_F32 && x_dtype != w_dtype) || (y_dtype != EA_F32 && y_dtype != w_dtype)) return EA_E_BADARG;
+  if (M < 1 || K < 1 || N < 1 || ldx < K || ldy < N) return EA_E_BADARG;
+  if (ldx * (x_dtype == EA_F32 ? 4 : 2) % 16 || ldy * (y_dtype == EA_F32 ? 4 : 2) % 16) return EA_E_BADARG;
+  if (M > EA_CEVA_LINEAR_MAX_ROWS || K % 32 || N % 16) return EA_E_UNSUPPORTED;
+  ea::DecLinP p = {};
+  p.x = (const char*)x; p.w = (const char*)w; p.bias = (const char*)bias; p.y = (char*)y;
+  p.ldx = ldx; p.ldy = ldy; p.M = M; p.K = K; p.N = N; p.dtype = w_dtype;
+  p.x_f32 = x_dtype == EA_F32; p.y_f32 = y_dtype == EA_F32;
+  return ea::ceva_sdecode_linear(p, (hipStream_t)stream);
 }
 
 }  // extern "C"

@@ -14,6 +14,10 @@ and in nothing else.  A static or rolling state made with `per_sequence=True` ke
 same four launches, each row taking its own number of the step's tokens (`_step_flags`), with no host shadow at all.
 A static or rolling state made with `landmark_splits=P > 1` runs attn of a step of at most 8 tokens as two launches,
 ea_ceva_sdecode_attn_split (P workgroups per window block share the landmark rows) and ea_ceva_sdecode_merge.
+A static or rolling state made with `hold_projections=True` also HOLDS THE TWO PROJECTIONS, as 16-bit copies taken at init like
+the bias table and the mu parameters: a step of at most 64 rows (T_new B) runs them as two more launches,
+ea_ceva_sdecode_linear in front of append and behind advance, that stream the held weights once; no framework kernel of
+such a step touches a weight.
 """
 import ctypes
 import functools
@@ -33,22 +37,27 @@ _STATIC_BATCH_FIRST = ("qkv", "rf_k_bar", "beta", "pad")
 _PER_SEQUENCE = ("pos", "status", "ntok")
 _SPLIT_MAX_STEP = 8          # QPW of ea_ceva_decode.hip: a step of at most this many tokens has one query group per window block
 _SPLIT_MAX_PARTS = 64
+_LINEAR_MAX_ROWS = 64        # EA_CEVA_LINEAR_MAX_ROWS of include/ea_hip.h: the rows (T_new B) ea_ceva_sdecode_linear takes
+# what a state made with hold_projections=True adds to the buffer (step-invariant like `bias` and `mu`: a beam reorder and
+# reset_decoding_rows leave them alone)
+_HELD = ("w_qkv", "b_qkv", "w_out", "b_out", "proj_rows")
 
 
 def _state_options(init):
-    """The keyword-only `per_sequence=False` and `landmark_splits=1` of the two `init_*_decoding` methods.  The methods keep
+    """The keyword-only `per_sequence=False`, `landmark_splits=1` and `hold_projections=False` of the two `init_*_decoding`
+    methods.  The methods keep
     the positional interface they had, and that is the signature they report (`__signature__`: callers that pin the parameter
     list, this package's own tests among them, see what they saw); the options are taken off here and handed to the method
     as its last arguments.  Arguments are bound as Python binds them: an option by position, or an unknown keyword, is a
     TypeError.  (`landmark_splits` is handed on as given: the method checks it behind its other refusals.)"""
     positional = inspect.signature(init)
-    positional = positional.replace(parameters=list(positional.parameters.values())[:-2])
+    positional = positional.replace(parameters=list(positional.parameters.values())[:-3])
 
     @functools.wraps(init)
-    def with_options(self, *args, per_sequence=False, landmark_splits=1, **kwargs):
+    def with_options(self, *args, per_sequence=False, landmark_splits=1, hold_projections=False, **kwargs):
         bound = positional.bind(self, *args, **kwargs)
         bound.apply_defaults()
-        return init(*bound.args, bool(per_sequence), landmark_splits, **bound.kwargs)
+        return init(*bound.args, bool(per_sequence), landmark_splits, bool(hold_projections), **bound.kwargs)
     with_options.__signature__ = positional
     return with_options
 
@@ -87,7 +96,7 @@ class CevaDecoding:
     # ---- static and rolling states ----------------------------------------------------------------------------------------
     @_state_options
     def init_static_decoding(self, incremental_state, batch_size, max_tokens, dtype, device, per_sequence=False,
-                             landmark_splits=1):
+                             landmark_splits=1, hold_projections=False):
         """Allocate, once, every buffer a decoding step touches and mark this module's incremental state as STATIC: every
         later `forward(..., incremental_state=incremental_state)` then runs a step that can be captured into a graph
         (`torch.cuda.graph`) and replayed -- the token count lives in device memory and the kernels advance it: four
@@ -134,16 +143,40 @@ class CevaDecoding:
         Choosing P: about 256 / (B h) workgroups per (b, h) fill the device (B = 1, h = 8: 32; B = 8, h = 8: 4); more parts
         than the context has 64-landmark tiles, ceil(tokens / (64 r)) of them, buy nothing, and at a short context the
         extra launch costs more than the split saves.  The split changes the order in which a row's partial sums are merged,
-        so its outputs equal the unsplit step's to rounding, not bit for bit; P = 1 is the unsplit state in every respect."""
+        so its outputs equal the unsplit step's to rounding, not bit for bit; P = 1 is the unsplit state in every respect.
+        `hold_projections=True` (default False; combines with the other two; a 16-bit `dtype` only -- fp32 decoding is the
+        fidelity path and keeps the library's fp32 GEMMs -- and projections that all have a bias or all have none): the state
+        also holds the module's two projections, taken here once like the bias table and the mu parameters (a capture fixes
+        the weights):
+            w_qkv     [3 C, C]            `dtype`: q_proj, k_proj, v_proj weights stacked in that order
+            b_qkv     [3 C]               `dtype`, or None without biases
+            w_out     [C, C]              `dtype`: out_proj
+            b_out     [C]                 `dtype`, or None
+            proj_rows [64, 3 C]           `dtype`: the projected rows of a step, so that a captured step allocates only its
+                                          outputs; scratch like split_ws
+        A plain step rebuilds the stacked weight and casts both weights from the fp32 masters every time it is replayed (a
+        capture must record the producing kernels): about 56 MB of weight traffic and a dozen launches per layer at C = 1024
+        for a step whose inputs are 1 .. 8 rows.  On a held state a step of AT MOST 64 ROWS (T_new B) is
+            ea_ceva_sdecode_linear (query rows -> proj_rows), append, close, attn (or attn_split + merge), advance,
+            ea_ceva_sdecode_linear (attention rows -> the output)
+        -- the 8 MB of 16-bit weights read once, by a kernel that multiplies a handful of rows at the speed the weight can be
+        read, and no framework kernel that touches a weight.  The query is rounded to `dtype` as it is loaded (an fp32 query
+        outside autocast: with the one-time rounding warning), products are summed in fp32 and rounded once; the output has
+        the dtype the plain step returns.  A larger step (a prompt; every piece a rolling state cuts it into) runs the library
+        GEMM on the held operands: no concatenation and no cast of a weight either.  Outputs equal the plain state's to
+        rounding (16-bit weights, another summation order), not bit for bit.  After the parameters have changed,
+        `refresh_decoding_weights` re-reads them in place."""
         B, T, device = self._check_static_decoding(batch_size, max_tokens, dtype, device)
         P = _check_landmark_splits(landmark_splits)
+        self._check_hold_projections(hold_projections, dtype)
         w = self.window_size
         cap = -(-T // w) * w
-        return self._alloc_static_decoding(incremental_state, B, cap, cap, dtype, device, {"count": 0}, per_sequence, P)
+        return self._alloc_static_decoding(incremental_state, B, cap, cap, dtype, device, {"count": 0}, per_sequence, P,
+                                           hold_projections)
 
     @_state_options
     def init_rolling_decoding(self, incremental_state, batch_size, max_tokens, dtype, device, max_step_tokens=None,
-                              per_sequence=False, landmark_splits=1):
+                              per_sequence=False, landmark_splits=1, hold_projections=False):
         """`init_static_decoding` with the token rows in a fixed RING: the state is static in every respect (the same step,
         capturable and replayable; `static_decoding_overflowed` and the in-place `reorder_incremental_state` work on it), but
         `qkv` and `pad` hold R token slots instead of one row per token ever decoded, token n in slot n % R:
@@ -168,18 +201,34 @@ class CevaDecoding:
         the later ones.
         `landmark_splits=P`: as in `init_static_decoding` -- the landmark rows, which a rolling state keeps for the whole
         context, are what a step of at most 8 tokens shares between P workgroups per (window block, b, h).  About
-        256 / (B h) parts fill the device; more than ceil(tokens / (64 r)) buy nothing."""
+        256 / (B h) parts fill the device; more than ceil(tokens / (64 r)) buy nothing.
+        `hold_projections=True`: as in `init_static_decoding` -- the state holds 16-bit copies of the two projections (a capture
+        fixes the weights; `refresh_decoding_weights` re-reads them), a step of at most 64 rows runs them on
+        ea_ceva_sdecode_linear, and the pieces of a prompt run the library GEMM on the held operands."""
         B, T, device = self._check_static_decoding(batch_size, max_tokens, dtype, device)
         w, e = self.window_size, self.ext_size
         S = w if max_step_tokens is None else int(max_step_tokens)
         if S <= 0:
             raise ValueError("rolling decoding needs max_step_tokens > 0, got %d" % S)
         P = _check_landmark_splits(landmark_splits)
+        self._check_hold_projections(hold_projections, dtype)
         cap = -(-T // w) * w
         ring = -(-(w + e + S) // w) * w
         rows = min(ring, cap)
         static = {"count": 0, "cap": cap, "ring": ring if ring < cap else 0, "max_step": S}
-        return self._alloc_static_decoding(incremental_state, B, cap, rows, dtype, device, static, per_sequence, P)
+        return self._alloc_static_decoding(incremental_state, B, cap, rows, dtype, device, static, per_sequence, P,
+                                           hold_projections)
+
+    def _check_hold_projections(self, hold, dtype):
+        """What `hold_projections=True` refuses, behind every other refusal and before anything is allocated."""
+        if not hold:
+            return
+        if dtype == torch.float32:
+            raise ValueError("hold_projections=True holds 16-bit projection weights: an fp32 decoding state (the fidelity "
+                             "path) keeps the library's fp32 GEMMs")
+        has_b = [lin.bias is not None for lin in (self.q_proj, self.k_proj, self.v_proj)]
+        if any(has_b) != all(has_b):
+            raise ValueError("hold_projections=True needs q_proj, k_proj and v_proj to all have a bias or all have none")
 
     def _check_static_decoding(self, batch_size, max_tokens, dtype, device):
         """What a static (or rolling) state refuses, before anything is allocated -> (B, max_tokens, device)."""
@@ -197,10 +246,11 @@ class CevaDecoding:
             raise ValueError("static decoding needs batch_size > 0 and max_tokens > 0, got %d, %d" % (B, T))
         return B, T, device
 
-    def _alloc_static_decoding(self, incremental_state, B, cap, rows, dtype, device, static, per_sequence=False, splits=1):
+    def _alloc_static_decoding(self, incremental_state, B, cap, rows, dtype, device, static, per_sequence=False, splits=1,
+                               hold=False):
         """The buffers of a static state: `rows` token rows (cap, or a ring), cap / r landmark rows; one counter and one
         overflow flag, or (per_sequence) one of each per batch row and the rows' token counts of a step; splits > 1: the
-        workspace of a short step's partials."""
+        workspace of a short step's partials; hold: the 16-bit projections and the staging rows of a step."""
         h, d, r = self.num_heads, self.head_dim, self.chunk_size
         nc = B if per_sequence else 1
         state = {
@@ -217,19 +267,61 @@ class CevaDecoding:
         static["landmark_splits"] = splits
         if splits > 1:
             state["split_ws"] = torch.zeros((B, h, _SPLIT_MAX_STEP, splits, d + 4), dtype=torch.float32, device=device)
+        if hold:
+            C = self.embed_dim
+            qkv_b, out_b = self.q_proj.bias is not None, self.out_proj.bias is not None
+            state["proj_rows"] = torch.zeros((_LINEAR_MAX_ROWS, 3 * C), dtype=dtype, device=device)
+            state["w_qkv"] = torch.empty((3 * C, C), dtype=dtype, device=device)
+            state["b_qkv"] = torch.empty((3 * C,), dtype=dtype, device=device) if qkv_b else None
+            state["w_out"] = torch.empty((C, C), dtype=dtype, device=device)
+            state["b_out"] = torch.empty((C,), dtype=dtype, device=device) if out_b else None
+            static["hold_projections"] = True
         with torch.no_grad():
             state["bias"] = self._decode_bias_table(device)
             state["mu"] = self._decode_mu_f32()
+        if hold:
+            self._load_held_projections(state)
         self._set_input_buffer(incremental_state, state)
         # host side: the shadow count of EAGER steps (a replay advances only the device count), for the eager overflow check;
         # a rolling state adds its landmark capacity, its ring length (0: linear rows) and its largest step
         self.set_incremental_state(incremental_state, "attn_static", static)
         return incremental_state
 
+    def _load_held_projections(self, state):
+        """The module's projection parameters -> the held 16-bit tensors, in place (rounded to nearest even, the values
+        `multi_cast` produces); rows of w_qkv: q_proj, k_proj, v_proj, as `_project` stacks them.  Device copies only."""
+        C = self.embed_dim
+        with torch.no_grad():
+            for i, lin in enumerate((self.q_proj, self.k_proj, self.v_proj)):
+                state["w_qkv"][i * C:(i + 1) * C].copy_(lin.weight)
+                if state["b_qkv"] is not None:
+                    state["b_qkv"][i * C:(i + 1) * C].copy_(lin.bias)
+            state["w_out"].copy_(self.out_proj.weight)
+            if state["b_out"] is not None:
+                state["b_out"].copy_(self.out_proj.bias)
+
+    def refresh_decoding_weights(self, incremental_state):
+        """Re-read the module's parameters into what a static or rolling state holds of them, IN PLACE: the dense bias table,
+        the fp32 copies of the mu parameters (fp32 masters are read where they are and need none) and, on a state made with
+        `hold_projections=True`, the 16-bit projection weights and biases.  A capture fixes the weights -- a replayed step
+        reads these tensors, not the parameters -- so call this after the parameters have changed (an optimizer step, a loaded
+        checkpoint) and between replays: device ops only, every `data_ptr()` stays what it was, and a step captured before
+        sees the new weights without being captured again.  A state without held projections refreshes what it holds."""
+        buf, _ = self._static_buffer(incremental_state, "refresh_decoding_weights")
+        with torch.no_grad():
+            if buf.get("bias") is not None:
+                buf["bias"].copy_(self._decode_bias_table(buf["bias"].device))
+            for held, param in zip(buf["mu"], self._mu_params()):
+                if held.data_ptr() != param.data_ptr():
+                    held.copy_(param)
+        if "w_qkv" in buf:
+            self._load_held_projections(buf)
+        return incremental_state
+
     def decoding_state_nbytes(self, incremental_state):
         """Bytes of every tensor in this module's decoding buffer (dynamic, static or rolling): token rows, pad flags,
-        landmark rows, counters and, for a static state, the bias table, the fp32 mu parameters it holds and the workspace
-        of `landmark_splits`.  Host only."""
+        landmark rows, counters and, for a static state, the bias table, the fp32 mu parameters it holds, the workspace
+        of `landmark_splits` and what `hold_projections` holds.  Host only."""
         def nbytes(v):
             if torch.is_tensor(v):
                 return v.numel() * v.element_size()
@@ -410,11 +502,19 @@ class CevaDecoding:
                 ys = [self._decode(query[a:a + pieces], None if step_pad is None else step_pad[:, a:a + pieces],
                                    incremental_state, piece=True)[0] for a in range(0, T_new, pieces)]
                 return torch.cat(ys, 0), None
-        qkv_new = self._project(query, None, None, keep_f32=True)  # [T_new, B, 3, h, d]
+        held = static is not None and "w_qkv" in state
+        # (like the split: the rows of the step the caller handed over decide, and a capture fixes them)
+        held_rows = held and T_new * B <= _LINEAR_MAX_ROWS and not piece
+        if held_rows:
+            qkv_new = self._held_linear(query.reshape(T_new * B, C), state["w_qkv"], state["b_qkv"], state["proj_rows"])
+        elif held:
+            qkv_new = self._held_gemm(query, state["w_qkv"], state["b_qkv"]).reshape(T_new, B, 3, h, d)
+        else:
+            qkv_new = self._project(query, None, None, keep_f32=True)  # [T_new, B, 3, h, d]
         if static is None:
             t0 = self._dynamic_room(incremental_state, state, qkv_new.dtype, B, T_new, dev)
         cache = state["qkv"]
-        if qkv_new.dtype != cache.dtype:
+        if not held and qkv_new.dtype != cache.dtype:
             # the cache's dtype is fixed: an fp32 step on a 16-bit cache rounds (with the one-time warning of
             # _ops.to_io_dtype), a 16-bit step on an fp32 cache widens exactly
             qkv_new = _ops.to_io_dtype(qkv_new) if cache.dtype != torch.float32 else qkv_new.float()
@@ -422,7 +522,7 @@ class CevaDecoding:
                 qkv_new = qkv_new.to(cache.dtype)                  #  assignment of the dynamic state converts)
         step_pad = None
         if static is not None:
-            qkv_new = qkv_new.contiguous()
+            qkv_new = qkv_new if held_rows else qkv_new.contiguous()     # (proj_rows: the step's rows lead the buffer)
             if key_padding_mask is not None:
                 step_pad = key_padding_mask[:, -T_new:].to(device=dev, dtype=torch.uint8).contiguous()
             has_pad, bias = True, state["bias"]
@@ -494,4 +594,42 @@ class CevaDecoding:
             self.set_incremental_state(incremental_state, "attn_pos", t0 + T_new)
             state["pos"] = state["pos"] + T_new
             self._set_input_buffer(incremental_state, state)
+        if held:
+            ydtype = torch.get_autocast_dtype("cuda") if torch.is_autocast_enabled() else query.dtype
+            if held_rows:
+                ytype = ydtype if ydtype in (cache.dtype, torch.float32) else torch.float32
+                y = torch.empty((T_new, B, C), dtype=ytype, device=dev)
+                self._held_linear(out.view(T_new * B, C), state["w_out"], state["b_out"], y.view(T_new * B, C))
+            else:
+                y = self._held_gemm(out.view(T_new, B, C), state["w_out"], state["b_out"])
+            return (y if y.dtype == ydtype else y.to(ydtype)), None
         return self._project_out(out.reshape(T_new, B, C), query.dtype).contiguous(), None
+
+    # ---- the projections of a state that holds them ---------------------------------------------------------------------------
+    @staticmethod
+    def _held_x(x, wdtype):
+        """Rows as the held projections take them: fp32 or the weights' type (an fp32 row is rounded as it is loaded;
+        outside autocast that departs from the reference's fp32 arithmetic, and the caller is told once, as everywhere)."""
+        if x.dtype == torch.float32:
+            if not torch.is_autocast_enabled():
+                _ops.warn_fp32_rounded(x.dtype)
+        elif x.dtype != wdtype:
+            x = x.to(wdtype)
+        return x if x.is_contiguous() else x.contiguous()
+
+    def _held_linear(self, x2, weight, bias, y2):
+        """y2[:M] = x2 weight^T + bias on ea_ceva_sdecode_linear: x2 [M <= 64, K] (fp32 or the weight's type), y2 [>= M, N] rows
+        of the weight's type or fp32 -> y2."""
+        nv = _ops.nv
+        x2 = self._held_x(x2, weight.dtype)
+        code = lambda t: nv.EA_F32 if t.dtype == torch.float32 else nv.io_dtype(t)      # noqa: E731
+        nv.call("ea_ceva_sdecode_linear", x2.shape[0], weight.shape[1], weight.shape[0], nv.ptr(x2), code(x2), x2.stride(0),
+                nv.ptr(weight), nv.io_dtype(weight), nv.ptr(bias), nv.ptr(y2), code(y2), y2.stride(0), nv.stream())
+        return y2
+
+    def _held_gemm(self, x, weight, bias):
+        """A step above 64 rows: the library GEMM the plain step ends in, on the held 16-bit operands (no concatenation and
+        no cast of a weight) -> [..., N] in the weights' type."""
+        x = self._held_x(x, weight.dtype)
+        with torch.autocast(device_type="cuda", enabled=False):
+            return torch.nn.functional.linear(x if x.dtype == weight.dtype else x.to(weight.dtype), weight, bias)

@@ -186,16 +186,22 @@ def to_io_dtype(t):
     (EA_STRICT_FP32=1 turns the warning into an error)."""
     if t.dtype in (torch.bfloat16, torch.float16):
         return t
+    warn_fp32_rounded(t.dtype, stacklevel=4)
+    return t.to(torch.bfloat16)
+
+
+def warn_fp32_rounded(dtype, stacklevel=3):
+    """The one-time notice of to_io_dtype (EA_STRICT_FP32=1: the error), for a caller that rounds fp32 activations inside its
+    own kernel (the held projections of a decoding state)."""
     if os.environ.get("EA_STRICT_FP32", "0") == "1":
         raise RuntimeError("efficient_attention (MI355X build): %s activations reached an attention core outside "
-                           "torch.autocast; the HIP cores take bf16/fp16 operands (EA_STRICT_FP32=1)" % t.dtype)
+                           "torch.autocast; the HIP cores take bf16/fp16 operands (EA_STRICT_FP32=1)" % dtype)
     if not _FP32_WARNED[0]:
         _FP32_WARNED[0] = True
         warnings.warn("efficient_attention (MI355X build): %s activations outside torch.autocast are rounded to "
                       "bf16 for the attention cores (bf16 operands, fp32 accumulation / softmax); the reference "
                       "computes fp32 here. Wrap the call in torch.autocast('cuda', dtype=torch.bfloat16 | "
-                      "torch.float16) to choose the operand type explicitly." % t.dtype, stacklevel=3)
-    return t.to(torch.bfloat16)
+                      "torch.float16) to choose the operand type explicitly." % dtype, stacklevel=stacklevel)
 
 
 USE_TABLE_BIAS = os.environ.get("EA_TABLE_BIAS", "1") == "1"

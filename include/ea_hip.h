@@ -1034,6 +1034,22 @@ int ea_ceva_sdecode_attn_split(const ea_ceva_sdec_geom* g, const ea_t4* q, const
 int ea_ceva_sdecode_merge(const ea_ceva_sdec_geom* g, const ea_t4* out, int32_t parts, const float* ws, void* stream);
 int ea_ceva_sdecode_advance(const ea_ceva_sdec_geom* g, void* stream);
 
+/* ABI 22, the projections of a step on weights the static state holds (init_*_decoding(hold_projections=True);
+ * ea_ceva_decode_linear.hip):
+ *   y[m, n] = round_y( sum_k round_w(x[m, k]) w[n, k] + bias[n] ),  1 <= M <= EA_CEVA_LINEAR_MAX_ROWS
+ * x [M, ldx] rows of x_dtype = EA_F32 or w_dtype (fp32 rows are rounded to w_dtype, to nearest even, as they are loaded);
+ * w [N, K] row-major and bias [N] (or NULL) of w_dtype = EA_BF16 | EA_F16; products, sums and the bias add in fp32; y [M, ldy]
+ * rows of y_dtype = w_dtype or EA_F32.  ldx, ldy in elements.  One workgroup per 16 columns reads its rows of w once, its
+ * waves split K and add their partial tiles in a fixed order: no atomics, bitwise reproducible.  Rows >= M and columns >= N
+ * of y are not touched.
+ * EA_E_BADARG: x, w, y NULL or not 16-byte aligned (bias: not 16-byte aligned); ldx < K; ldy < N; a row stride of x or y
+ * that is no multiple of 16 bytes; M < 1, K < 1, N < 1; w_dtype not a 16-bit type; x_dtype neither EA_F32 nor w_dtype;
+ * y_dtype neither EA_F32 nor w_dtype.  EA_E_UNSUPPORTED: M > 64, K % 32 != 0, N % 16 != 0.  Decided before any launch. */
+#define EA_CEVA_LINEAR_MAX_ROWS 64
+int ea_ceva_sdecode_linear(int32_t M, int32_t K, int32_t N, const void* x, int32_t x_dtype, int64_t ldx,
+                           const void* w, int32_t w_dtype, const void* bias, void* y, int32_t y_dtype, int64_t ldy,
+                           void* stream);
+
 #ifdef __cplusplus
 }
 #endif

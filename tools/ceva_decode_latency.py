@@ -1,5 +1,5 @@
 """Per-token latency of CausalEVAttention decoding at the wikitext-103 LM geometry (embed 1024, h 8, d 128, w 128, chunks of 8,
-T5 bias, adaptive 'qk'), 16 stacked residual attention layers (x + attn(x), no FFN), bf16 autocast, in twelve modes:
+T5 bias, adaptive 'qk'), 16 stacked residual attention layers (x + attn(x), no FFN), bf16 autocast, in fifteen modes:
  - dynamic:       the incremental state of `_decode` (host token count, two decode launches per layer step);
  - static:        `init_static_decoding`, the same step run eagerly (four decode launches per layer step);
  - graph:         that static step over all 16 layers captured once with torch.cuda.graph and replayed;
@@ -11,6 +11,10 @@ T5 bias, adaptive 'qk'), 16 stacked residual attention layers (x + attn(x), no F
    per-sequence twins on a state made with `landmark_splits=P` (`--splits P`, default 256 / (B h)): the 1-token step runs attn
    as attn_split + merge, P workgroups per (b, h).  Their rows differ from the unsplit modes' in rounding (another order of
    the partial sums) and equal each other bitwise; the printed comparison reports the largest difference where rows differ.
+ - held-graph, held-rolling-graph, held-split-rolling-graph: graph, rolling-graph and split-rolling-graph on a state made with
+   `hold_projections=True`: the 1-token step runs its two projections on ea_ceva_sdecode_linear over the 16-bit weights the
+   state holds, and no framework kernel touches a weight.  Their rows differ from the other modes' in rounding (the query is
+   rounded before the products, another order of the sums).
    python tools/ceva_decode_latency.py [--context 512|4096|32768] [--steps 64] [--splits P] [--modes dynamic,static,graph,...]   (GPU)
    python tools/ceva_decode_latency.py --ragged [--context 512] [--steps 64]     (GPU)
 `--ragged`: batch 8 on per-sequence states, row b prefilled to (b + 1) / 8 of `context` by right-padded steps, then the
@@ -66,20 +70,14 @@ def run(mods, mode, B, context, steps, blocks=5, warmup=4, lengths=None, splits=
     opt = dict(per_sequence=True) if mode.startswith("per-seq") else {}
     if "split" in mode:
         opt["landmark_splits"] = splits or default_splits(B)
+    if mode.startswith("held-"):
+        opt["hold_projections"] = True
     for m in mods:
         st = {}
         m.init_incremental_state()
-        if "split" in mode:
+        if mode != "dynamic":
             init = m.init_rolling_decoding if "rolling" in mode else m.init_static_decoding
             init(st, B, n_tok, torch.bfloat16, "cuda", **opt)
-        elif mode in ("static", "graph"):
-            m.init_static_decoding(st, B, n_tok, torch.bfloat16, "cuda")
-        elif mode in ("rolling", "rolling-graph"):
-            m.init_rolling_decoding(st, B, n_tok, torch.bfloat16, "cuda")
-        elif mode in ("per-seq", "per-seq-graph"):
-            m.init_static_decoding(st, B, n_tok, torch.bfloat16, "cuda", per_sequence=True)
-        elif mode == "per-seq-rolling-graph":
-            m.init_rolling_decoding(st, B, n_tok, torch.bfloat16, "cuda", per_sequence=True)
         states.append(st)
     ends = None if lengths is None else torch.tensor(lengths, device="cuda").unsqueeze(1)
     rows, times = [], []
@@ -124,7 +122,8 @@ def run(mods, mode, B, context, steps, blocks=5, warmup=4, lengths=None, splits=
 
 
 MODES = ("dynamic", "static", "graph", "rolling", "rolling-graph", "per-seq", "per-seq-graph", "per-seq-rolling-graph",
-         "split-graph", "split-rolling-graph", "per-seq-split-graph", "per-seq-split-rolling-graph")
+         "split-graph", "split-rolling-graph", "per-seq-split-graph", "per-seq-split-rolling-graph",
+         "held-graph", "held-rolling-graph", "held-split-rolling-graph")
 CONTEXTS = (512, 4096, 32768)
 
 
@@ -146,12 +145,12 @@ def ragged(mods, context, steps):
                  m.decoding_state_nbytes(per) - m.decoding_state_nbytes(one)), flush=True)
 
 
-def state_bytes(m, B, context):
+def state_bytes(m, B, context, **opt):
     """decoding_state_nbytes of one layer with room for `context` tokens -> (static, rolling)."""
     out = []
     for init in (m.init_static_decoding, m.init_rolling_decoding):
         st = {}
-        init(st, B, context, torch.bfloat16, "cuda")
+        init(st, B, context, torch.bfloat16, "cuda", **opt)
         out.append(m.decoding_state_nbytes(st))
     return tuple(out)
 
@@ -192,6 +191,10 @@ def main():
         sb, rb = state_bytes(mods[0], B, a.context)
         print("    decoding_state_nbytes per layer, %d tokens, batch %d: static %d, rolling %d" % (a.context, B, sb, rb),
               flush=True)
+        if [m for m in modes if m.startswith("held-")]:
+            hs, hr = state_bytes(mods[0], B, a.context, hold_projections=True)
+            print("    hold_projections: static %d, rolling %d (+ %d bytes per layer: the 16-bit projections and the staging rows)"
+                  % (hs, hr, hs - sb), flush=True)
         if [m for m in modes if "split" in m]:
             P = a.splits or default_splits(B)
             print("    landmark_splits %d: + %d bytes of workspace per layer" % (P, B * HEADS * 8 * P * (EMBED // HEADS + 4) * 4),
