@@ -2237,15 +2237,21 @@ static int dec_close(const DecG& g, const ea_t4* q, const ea_t4* k, const ea_t4*
   }
   return ea::ceva_decode_launch(ea::DEC_CLOSE, p, (hipStream_t)stream);
 }
-static int dec_attn(const DecG& g, const ea_t4* q, const ea_t4* k, const ea_t4* v, const uint8_t* pad, const float* bias,
-                    const ea_t4* lk, const ea_t4* lv, const ea_t4* out, void* stream) {
-  ea::DecP p = {};
+// dec_fill, and what attn and attn_split add to it: the output rows and the bias
+static int dec_fill_attn(const DecG& g, const ea_t4* q, const ea_t4* k, const ea_t4* v, const uint8_t* pad, const float* bias,
+                         const ea_t4* lk, const ea_t4* lv, const ea_t4* out, ea::DecP& p) {
   const int rc = dec_fill(g, q, k, v, pad, lk, lv, p);
   if (rc != EA_OK) return rc;
   if (!dec_t4_ok(out, g.D, g.dtype == EA_F32 ? 4 : 2) || (g.has_bias && !bias)) return EA_E_BADARG;
   p.o = dec_mk(out);
   p.bias = g.has_bias ? bias : nullptr;
-  return ea::ceva_decode_launch(ea::DEC_ATTN, p, (hipStream_t)stream);
+  return EA_OK;
+}
+static int dec_attn(const DecG& g, const ea_t4* q, const ea_t4* k, const ea_t4* v, const uint8_t* pad, const float* bias,
+                    const ea_t4* lk, const ea_t4* lv, const ea_t4* out, void* stream) {
+  ea::DecP p = {};
+  const int rc = dec_fill_attn(g, q, k, v, pad, bias, lk, lv, out, p);
+  return rc != EA_OK ? rc : ea::ceva_decode_launch(ea::DEC_ATTN, p, (hipStream_t)stream);
 }
 // What the two launches of a split step add to a static step: 2 .. 64 parts, a 16-byte aligned workspace of fp32 partials
 // [B, H, 8, parts, D + 4], and a step of at most 8 tokens (one query group per window block).  Decided first, like every
@@ -2293,14 +2299,9 @@ int ea_ceva_sdecode_attn_split(const ea_ceva_sdec_geom* g, const ea_t4* q, const
                                const float* bias, const ea_t4* rf_k_bar, const ea_t4* beta, const ea_t4* out, int32_t parts,
                                float* ws, void* stream) {
   if (split_check(g, parts, ws) != EA_OK) return EA_E_BADARG;
-  const DecG dg = dec_read(g);
   ea::DecP p = {};
-  const int rc = dec_fill(dg, q, k, v, pad, rf_k_bar, beta, p);
-  if (rc != EA_OK) return rc;
-  if (!dec_t4_ok(out, dg.D, dg.dtype == EA_F32 ? 4 : 2) || (dg.has_bias && !bias)) return EA_E_BADARG;
-  p.o = dec_mk(out);
-  p.bias = dg.has_bias ? bias : nullptr;
-  return ea::ceva_sdecode_attn_split(p, parts, ws, (hipStream_t)stream);
+  const int rc = dec_fill_attn(dec_read(g), q, k, v, pad, bias, rf_k_bar, beta, out, p);
+  return rc != EA_OK ? rc : ea::ceva_sdecode_attn_split(p, parts, ws, (hipStream_t)stream);
 }
 
 int ea_ceva_sdecode_merge(const ea_ceva_sdec_geom* g, const ea_t4* out, int32_t parts, const float* ws, void* stream) {

@@ -38,7 +38,10 @@
 //        element needs less exits at once.  `Step` owns both numbers; no kernel body reads p.T for anything else.  The SEQ
 //        kernels have names of their own (ceva_*_seq_kernel, ea_ceva_decode_step.h), so the others keep their symbols and code.
 // A DEV step of at most QPW tokens can run attn as two launches, attn_split -> merge, with the tiles of a window block shared
-// by several workgroups (ea_ceva_decode_split.h): kernels of their own again, the ones above are not touched.
+// by several workgroups (ea_ceva_decode_split.h): kernels of their own again.  attn and attn_split are one body: the staging
+// of a query group, the tile loop with its online softmax, the stash of a wave's partial and the merge over waves exist
+// once, as the helpers below (Group, stage_queries, stream_tiles, stash_partial, merge_waves).  A kernel keeps its Step, its
+// refusals and exits, its map from blockIdx to (block, part), which tiles a wave takes and what becomes of the result.
 #include "ea_common.h"
 #include "ea_ceva_decode.h"
 
@@ -185,6 +188,143 @@ EA_DEV float block_max(float v, float* red) {
 }
 
 
+// ---- what ceva_attn and ceva_attn_split share: one query group of a window block against a strided list of its tiles -----
+// The pad flags of a launch.  OPT: they may be absent (the dynamic step's; null = no position is padded), and every read
+// tests the pointer; a launch that always has them (attn_split) reads them outright.
+template <bool OPT> struct Pad {
+  const uint8_t* f;
+  EA_DEV bool at(size_t i) const { return (!OPT || f) && f[i]; }
+};
+
+// Where the queries and the local keys of window block bk lie; the kernel sets [qa, qa + nql), the query group, itself.
+// The block's own tokens do not straddle the end of a ring (w divides it): row = token + qs0.  Local slot 0 is row ks0, up
+// to e < ring rows before them, and the window spans w + e < ring rows from there: it wraps at most once.
+struct Group {
+  int bk, qa, nql, tend, kbase, qs0, ks0, pst, Wk, nlt;
+  template <bool RING>
+  EA_DEV Group(const DecP& p, Rows<RING> rows, int bk, int tend)     // tend: cache rows [0, tend) hold tokens
+      : bk(bk), qa(0), nql(0), tend(tend),
+        kbase(bk * p.w - p.e),                     // token of local slot 0
+        qs0(rows.slot(bk * p.w) - bk * p.w), ks0(rows.unwrap(kbase + qs0)),
+        pst(rows.len(p.cap)),                      // row length of pad
+        Wk(p.w + p.e), nlt((Wk + KT - 1) / KT) {}
+};
+
+// the group's query rows -> qs as floats, rows nql .. QPW - 1 zero
+template <typename E, int D>
+EA_DEV void stage_queries(const DecP& p, int b, int h, const Group& g, float (*qs)[D], int lane) {
+  for (int idx = lane; idx < QPW * (D / 8); idx += 64) {
+    const int i = idx / (D / 8), c = (idx - i * (D / 8)) * 8;
+    float x[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
+    if (i < g.nql) Io<E>::ld8(row<E>(p.q, b, h, g.qa + i + g.qs0) + (size_t)c * Io<E>::SZ, x);
+    *reinterpret_cast<f32x4*>(&qs[i][c]) = f32x4{x[0], x[1], x[2], x[3]};
+    *reinterpret_cast<f32x4*>(&qs[i][c + 4]) = f32x4{x[4], x[5], x[6], x[7]};
+  }
+  __builtin_amdgcn_wave_barrier();
+}
+
+// tiles first, first + stride, .. of [local tiles, landmark tiles]: online softmax into (m, l, acc), then l and acc summed
+// over the lanes that hold a share of them
+template <typename E, int D, bool RING, bool OPT>
+EA_DEV void stream_tiles(const DecP& p, int b, int h, const Group& g, int first, int stride, const float (*qs)[D],
+                         float (*ps)[QPW], int lane, float* m, float* l, f32x4* acc) {
+  static_assert(QPW == 8, "pv_rows reads the probabilities of a row as two float4");
+  constexpr int G = D / 4;                         // lanes per value row in P.V
+  const Rows<RING> rows{p.ring};
+  const Pad<OPT> pad{p.pad};
+  const int kg = lane / G, dc = (lane % G) * 4;
+  const int bk = g.bk, qa = g.qa, nql = g.nql, tend = g.tend, kbase = g.kbase, ks0 = g.ks0, pst = g.pst, Wk = g.Wk, nlt = g.nlt;
+  bool qpad[QPW];
+#pragma unroll
+  for (int i = 0; i < QPW; ++i) qpad[i] = i < nql && pad.at((size_t)b * pst + qa + i + g.qs0);
+  const int lmax = (qa + nql - 1) / p.r;           // landmark columns of the group's last query
+  const int ntile = nlt + (lmax + KT - 1) / KT;
+#pragma unroll
+  for (int i = 0; i < QPW; ++i) { m[i] = -INFINITY; l[i] = 0.f; acc[i] = f32x4{0.f, 0.f, 0.f, 0.f}; }
+  for (int tile = first; tile < ntile; tile += stride) {
+    const bool lmk = tile >= nlt;
+    const int col = (lmk ? (tile - nlt) * KT : tile * KT) + lane;
+    float sc[QPW];
+#pragma unroll
+    for (int i = 0; i < QPW; ++i) sc[i] = 0.f;
+    float x[QPW];
+    if (!lmk) {
+      const int tok = kbase + col;
+      const bool present = col < Wk && tok >= 0 && tok < tend;
+      const int sl = rows.wrap(ks0 + col);         // the key's row: reduced once per lane and tile
+      if (present) dot_rows<E, D>(row<E>(p.k, b, h, sl), qs, sc);
+      const bool kmask = !present || pad.at((size_t)b * pst + sl);
+#pragma unroll
+      for (int i = 0; i < QPW; ++i) {
+        const int tq = qa + i;
+        if (i >= nql || col >= Wk) x[i] = -INFINITY;
+        else if (kmask || qpad[i] || tok > tq) x[i] = MASK_FILL;
+        else x[i] = sc[i] * p.scale + (p.bias ? p.bias[(size_t)(tq - bk * p.w) * Wk + col] : 0.f);
+      }
+    } else {
+      if (col < lmax) dot_rows<float, D>(row<float>(p.lk, b, h, col), qs, sc);
+#pragma unroll
+      for (int i = 0; i < QPW; ++i) x[i] = (i < nql && col < (qa + i) / p.r) ? sc[i] * p.scale : -INFINITY;
+    }
+#pragma unroll
+    for (int i = 0; i < QPW; ++i) {
+      const float mn = fmaxf(m[i], wave_max(x[i]));
+      const float alpha = mn == -INFINITY ? 1.f : __expf(m[i] - mn);
+      const float pv = mn == -INFINITY ? 0.f : __expf(x[i] - mn);
+      m[i] = mn;
+      l[i] = l[i] * alpha + pv;
+      acc[i] *= alpha;
+      ps[lane][i] = pv;
+    }
+    __builtin_amdgcn_wave_barrier();
+    if (!lmk) {
+      // rows of absent / not yet decoded tokens: p is zero for every live query, their value rows are not read
+      const int j0 = max(0, -(kbase + tile * KT)), j1 = min(KT, min(Wk - tile * KT, tend - (kbase + tile * KT)));
+      if (j1 > j0) pv_rows<E, D>(rows, p.v, b, h, rows.wrap(ks0 + tile * KT + j0), j1 - j0, kg, dc, &ps[j0], acc);
+    } else {
+      pv_rows<float, D>(Rows<false>{}, p.lv, b, h, (tile - nlt) * KT, min(KT, lmax - (tile - nlt) * KT), kg, dc, ps, acc);
+    }
+    __builtin_amdgcn_wave_barrier();
+  }
+#pragma unroll
+  for (int i = 0; i < QPW; ++i) {
+    l[i] = wave_sum(l[i]);
+#pragma unroll
+    for (int o = G; o < 64; o <<= 1)
+#pragma unroll
+      for (int c = 0; c < 4; ++c) acc[i][c] += __shfl_xor(acc[i][c], o);
+  }
+}
+
+// a wave's partial of its group -> LDS, for the merge over the waves that shared the group
+template <int D>
+EA_DEV void stash_partial(const float* m, const float* l, const f32x4* acc, float (*mo)[D], float (*ml)[2], int lane) {
+  constexpr int G = D / 4;
+  if (lane < G) {
+#pragma unroll
+    for (int i = 0; i < QPW; ++i) *reinterpret_cast<f32x4*>(&mo[i][lane * 4]) = acc[i];
+  }
+  if (lane == 0) {
+#pragma unroll
+    for (int i = 0; i < QPW; ++i) { ml[i][0] = m[i]; ml[i][1] = l[i]; }
+  }
+}
+
+// columns c .. c + 3 of query i, merged over waves w0 .. w0 + n - 1 in that order: not normalised
+template <int D>
+EA_DEV f32x4 merge_waves(const float (*mo)[QPW][D], const float (*ml)[QPW][2], int w0, int n, int i, int c, float& mx, float& lt) {
+  mx = -INFINITY;
+  for (int w = w0; w < w0 + n; ++w) mx = fmaxf(mx, ml[w][i][0]);
+  lt = 0.f;
+  f32x4 o = {0.f, 0.f, 0.f, 0.f};
+  for (int w = w0; w < w0 + n; ++w) {
+    const float f = ml[w][i][0] == -INFINITY ? 0.f : __expf(ml[w][i][0] - mx);
+    lt += f * ml[w][i][1];
+    o += f * *reinterpret_cast<const f32x4*>(&mo[w][i][c]);
+  }
+  return o;
+}
+
 // ---- DEV steps: the token count lives in device memory -----------------------------------------------------------------
 // A step is append -> close -> attn -> advance on one stream.  Only advance writes *pos, so the three before it read the
 // same count, and each decides from it alone whether the step fits the cache.  A step that does not fit writes no cache
@@ -257,6 +397,8 @@ __global__ __launch_bounds__(64) void ceva_advance_seq_kernel(int32_t* pos, cons
 }
 
 using DecKernel = void (*)(const DecP);
+using SplitKernel = void (*)(const DecSplitP);
+using MergeKernel = void (*)(const DecMergeP);
 
 template <typename E, int D>
 DecKernel kernel_of(DecKind kind, bool dev, bool ring, bool seq) {
@@ -267,39 +409,32 @@ DecKernel kernel_of(DecKind kind, bool dev, bool ring, bool seq) {
   return !dev ? ceva_attn_kernel<E, D, false, false> : ring ? ceva_attn_kernel<E, D, true, true> : ceva_attn_kernel<E, D, true, false>;
 }
 
-template <typename E>
-DecKernel kernel_of(int D, DecKind kind, bool dev, bool ring, bool seq) {
-  switch (D) {
-    case 32: return kernel_of<E, 32>(kind, dev, ring, seq);
-    case 64: return kernel_of<E, 64>(kind, dev, ring, seq);
-    default: return kernel_of<E, 128>(kind, dev, ring, seq);
-  }
-}
-
-using SplitKernel = void (*)(const DecSplitP);
-using MergeKernel = void (*)(const DecMergeP);
-
 template <typename E, int D>
 SplitKernel split_of(bool ring, bool seq) {
   if (seq) return ring ? ceva_attn_split_kernel<E, D, true, true> : ceva_attn_split_kernel<E, D, false, true>;
   return ring ? ceva_attn_split_kernel<E, D, true, false> : ceva_attn_split_kernel<E, D, false, false>;
 }
 
-template <typename E>
-SplitKernel split_of(int D, bool ring, bool seq) {
-  switch (D) {
-    case 32: return split_of<E, 32>(ring, seq);
-    case 64: return split_of<E, 64>(ring, seq);
-    default: return split_of<E, 128>(ring, seq);
-  }
-}
+template <typename E, int D>
+MergeKernel merge_of(bool seq) { return seq ? ceva_merge_kernel<E, D, true> : ceva_merge_kernel<E, D, false>; }
 
-template <typename E>
-MergeKernel merge_of(int D, bool seq) {
-  switch (D) {
-    case 32: return seq ? ceva_merge_kernel<E, 32, true> : ceva_merge_kernel<E, 32, false>;
-    case 64: return seq ? ceva_merge_kernel<E, 64, true> : ceva_merge_kernel<E, 64, false>;
-    default: return seq ? ceva_merge_kernel<E, 128, true> : ceva_merge_kernel<E, 128, false>;
+// (dtype, D) -> <E, D>: calls pick(E{}, Dim<D>{}), which chooses its kernel instance.  False for a dtype that is none of the
+// three; the callers have refused every D but 32, 64 and 128 before.
+template <int D> struct Dim { static constexpr int value = D; };
+template <typename F>
+bool with_types(int dtype, int D, F&& pick) {
+  const auto dims = [&](auto e) {
+    switch (D) {
+      case 32: pick(e, Dim<32>{}); break;
+      case 64: pick(e, Dim<64>{}); break;
+      default: pick(e, Dim<128>{}); break;
+    }
+  };
+  switch (dtype) {
+    case EA_BF16: dims(BF16{}); return true;
+    case EA_F16: dims(F16{}); return true;
+    case EA_F32: dims(0.f); return true;
+    default: return false;
   }
 }
 
@@ -312,12 +447,8 @@ int ceva_decode_launch(DecKind kind, const DecP& p, hipStream_t st) {
   if (dev ? !p.pad : (ring || seq)) return EA_E_BADARG;   // a DEV step always reads the pad flags; ring, ntok belong to a DEV step
   if (p.D != 32 && p.D != 64 && p.D != 128) return EA_E_UNSUPPORTED;
   DecKernel kernel;
-  switch (p.dtype) {
-    case EA_BF16: kernel = kernel_of<BF16>(p.D, kind, dev, ring, seq); break;
-    case EA_F16: kernel = kernel_of<F16>(p.D, kind, dev, ring, seq); break;
-    case EA_F32: kernel = kernel_of<float>(p.D, kind, dev, ring, seq); break;
-    default: return EA_E_BADARG;
-  }
+  if (!with_types(p.dtype, p.D, [&](auto e, auto d) { kernel = kernel_of<decltype(e), decltype(d)::value>(kind, dev, ring, seq); }))
+    return EA_E_BADARG;
   // x: the chunks the step closes / the window blocks it touches; DEV: the most T tokens can, wherever they start
   const int nx = kind == DEC_CLOSE ? (dev ? (p.T + p.r - 1) / p.r : p.c_last - p.c_first + 1)
                                    : (dev ? (p.T + p.w - 2) / p.w + 1 : (p.t0 + p.T - 1) / p.w - p.t0 / p.w + 1);
@@ -331,12 +462,8 @@ int ceva_sdecode_attn_split(const DecP& p, int parts, float* ws, hipStream_t st)
   if (!p.pos || !p.pad || !ws || parts < 2 || parts > 64 || p.T > QPW) return EA_E_BADARG;
   if (p.D != 32 && p.D != 64 && p.D != 128) return EA_E_UNSUPPORTED;
   SplitKernel kernel;
-  switch (p.dtype) {
-    case EA_BF16: kernel = split_of<BF16>(p.D, ring, seq); break;
-    case EA_F16: kernel = split_of<F16>(p.D, ring, seq); break;
-    case EA_F32: kernel = split_of<float>(p.D, ring, seq); break;
-    default: return EA_E_BADARG;
-  }
+  if (!with_types(p.dtype, p.D, [&](auto e, auto d) { kernel = split_of<decltype(e), decltype(d)::value>(ring, seq); }))
+    return EA_E_BADARG;
   const int nx = (p.T + p.w - 2) / p.w + 1;        // the most window blocks T tokens can touch
   const DecSplitP sp = {p, ws, parts};
   hipLaunchKernelGGL(kernel, dim3((unsigned)(nx * parts), (unsigned)(p.B * p.H)), dim3(NT), 0, st, sp);
@@ -348,12 +475,7 @@ int ceva_sdecode_merge(const DecMergeP& p, int D, int dtype, int BH, hipStream_t
   if (!p.pos || !p.ws || p.parts < 2 || p.parts > 64 || p.T > QPW) return EA_E_BADARG;
   if (D != 32 && D != 64 && D != 128) return EA_E_UNSUPPORTED;
   MergeKernel kernel;
-  switch (dtype) {
-    case EA_BF16: kernel = merge_of<BF16>(D, seq); break;
-    case EA_F16: kernel = merge_of<F16>(D, seq); break;
-    case EA_F32: kernel = merge_of<float>(D, seq); break;
-    default: return EA_E_BADARG;
-  }
+  if (!with_types(dtype, D, [&](auto e, auto d) { kernel = merge_of<decltype(e), decltype(d)::value>(seq); })) return EA_E_BADARG;
   hipLaunchKernelGGL(kernel, dim3((unsigned)p.T, (unsigned)BH), dim3(64), 0, st, p);
   return (int)hipGetLastError();
 }

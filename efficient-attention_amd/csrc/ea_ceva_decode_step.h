@@ -3,9 +3,10 @@
 // helpers it uses, with
 //   CEVA_SEQ false, CEVA_KERNEL(x) = x_kernel        one token count for the batch (and the dynamic step)
 //   CEVA_SEQ true,  CEVA_KERNEL(x) = x_seq_kernel    per-sequence counts (DEV only)
-// so that the shared-count kernels keep their symbols and, token for token, the source they had before the per-sequence
-// switch existed: tools/isa_diff.py shows their code unchanged.  (Wrapping one body template in two kernels compiles too,
-// but the inlined body schedules differently from the kernel written out.)
+// so that the shared-count kernels keep their symbols, and close and append, token for token, the source they had before the
+// per-sequence switch existed: tools/isa_diff.py shows their code unchanged.  (Wrapping one body template in two kernels
+// compiles too, but the inlined body schedules differently from the kernel written out.)  What attn does to a query group
+// it shares with attn_split (ea_ceva_decode_split.h) and takes from the helpers of ea_ceva_decode.hip.
 #if !defined(CEVA_SEQ) || !defined(CEVA_KERNEL)
 #error "included by ea_ceva_decode.hip only"
 #endif
@@ -13,10 +14,12 @@
 // One workgroup per window block of the step.  DEV: the grid holds the most window blocks T tokens can touch, and a block
 // this step does not touch exits at once; a step that does not fit writes NaN rows.  SEQ: the block's queries are those of
 // element b's own n tokens, so the wave split below is that of a shared-count step of n tokens at the same position.
+// Wave s of the nsplit that share a query group takes tiles s, s + nsplit, ..; a group with a wave to itself is normalised
+// and stored by that wave, the others by the group's first wave after the in-LDS merge.  The dynamic step may come without
+// pad flags, so every read of them tests the pointer (Pad<true>).
 template <typename E, int D, bool DEV, bool RING>
 __global__ __launch_bounds__(NT) void CEVA_KERNEL(ceva_attn)(const DecP p) {
   constexpr bool SEQ = CEVA_SEQ;
-  static_assert(QPW == 8, "pv_rows reads the probabilities of a row as two float4");
   static_assert(DEV || !RING, "the ring belongs to the static step");
   constexpr int G = D / 4;                         // lanes per value row in P.V
   __shared__ __attribute__((aligned(16))) float qs[NW][QPW][D];
@@ -37,104 +40,22 @@ __global__ __launch_bounds__(NT) void CEVA_KERNEL(ceva_attn)(const DecP p) {
   const int tq0 = max(t0, bk * p.w), tq1 = min(t0 + step.n(p.T), (bk + 1) * p.w);
   const int nqg = (tq1 - tq0 + QPW - 1) / QPW;
   const int nsplit = nqg >= NW ? 1 : NW / nqg;     // waves per query group
-  const int Wk = p.w + p.e, nlt = (Wk + KT - 1) / KT;
-  const int tend = t0 + step.n(p.T);               // cache rows [0, tend) hold tokens
-  const int kbase = bk * p.w - p.e;                // token of local slot 0
-  // the block's own tokens do not straddle the end of a ring (w divides it): row = token + qs0.  Local slot 0 is row ks0,
-  // up to e < ring rows before them, and the window spans w + e < ring rows from there: it wraps at most once.
-  const Rows<RING> rows{p.ring};
-  const int qs0 = rows.slot(bk * p.w) - bk * p.w;
-  const int ks0 = rows.unwrap(kbase + qs0);
-  const int pst = rows.len(p.cap);                 // row length of pad
-  const int kg = lane / G, dc = (lane % G) * 4;
+  Group gr(p, Rows<RING>{p.ring}, bk, t0 + step.n(p.T));
+  const int dc = (lane % G) * 4;
   for (int g = wave / nsplit; g < nqg; g += NW) {
-    const int s = wave % nsplit;
-    const int qa = tq0 + g * QPW, nql = min(QPW, tq1 - qa);
-    for (int idx = lane; idx < QPW * (D / 8); idx += 64) {
-      const int i = idx / (D / 8), c = (idx - i * (D / 8)) * 8;
-      float x[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
-      if (i < nql) Io<E>::ld8(row<E>(p.q, b, h, qa + i + qs0) + (size_t)c * Io<E>::SZ, x);
-      *reinterpret_cast<f32x4*>(&qs[wave][i][c]) = f32x4{x[0], x[1], x[2], x[3]};
-      *reinterpret_cast<f32x4*>(&qs[wave][i][c + 4]) = f32x4{x[4], x[5], x[6], x[7]};
-    }
-    __builtin_amdgcn_wave_barrier();
-    bool qpad[QPW];
-#pragma unroll
-    for (int i = 0; i < QPW; ++i) qpad[i] = i < nql && p.pad && p.pad[(size_t)b * pst + qa + i + qs0];
-    const int lmax = (qa + nql - 1) / p.r;         // landmark columns of the group's last query
-    const int ntile = nlt + (lmax + KT - 1) / KT;
+    gr.qa = tq0 + g * QPW; gr.nql = min(QPW, tq1 - gr.qa);
+    stage_queries<E, D>(p, b, h, gr, qs[wave], lane);
     float m[QPW], l[QPW];
     f32x4 acc[QPW];
-#pragma unroll
-    for (int i = 0; i < QPW; ++i) { m[i] = -INFINITY; l[i] = 0.f; acc[i] = f32x4{0.f, 0.f, 0.f, 0.f}; }
-    for (int tile = s; tile < ntile; tile += nsplit) {
-      const bool lmk = tile >= nlt;
-      const int col = (lmk ? (tile - nlt) * KT : tile * KT) + lane;
-      float sc[QPW];
-#pragma unroll
-      for (int i = 0; i < QPW; ++i) sc[i] = 0.f;
-      float x[QPW];
-      if (!lmk) {
-        const int tok = kbase + col;
-        const bool present = col < Wk && tok >= 0 && tok < tend;
-        const int sl = rows.wrap(ks0 + col);       // the key's row: reduced once per lane and tile
-        if (present) dot_rows<E, D>(row<E>(p.k, b, h, sl), qs[wave], sc);
-        const bool kmask = !present || (p.pad && p.pad[(size_t)b * pst + sl]);
-#pragma unroll
-        for (int i = 0; i < QPW; ++i) {
-          const int tq = qa + i;
-          if (i >= nql || col >= Wk) x[i] = -INFINITY;
-          else if (kmask || qpad[i] || tok > tq) x[i] = MASK_FILL;
-          else x[i] = sc[i] * p.scale + (p.bias ? p.bias[(size_t)(tq - bk * p.w) * Wk + col] : 0.f);
-        }
-      } else {
-        if (col < lmax) dot_rows<float, D>(row<float>(p.lk, b, h, col), qs[wave], sc);
-#pragma unroll
-        for (int i = 0; i < QPW; ++i) x[i] = (i < nql && col < (qa + i) / p.r) ? sc[i] * p.scale : -INFINITY;
-      }
-#pragma unroll
-      for (int i = 0; i < QPW; ++i) {
-        const float mn = fmaxf(m[i], wave_max(x[i]));
-        const float alpha = mn == -INFINITY ? 1.f : __expf(m[i] - mn);
-        const float pv = mn == -INFINITY ? 0.f : __expf(x[i] - mn);
-        m[i] = mn;
-        l[i] = l[i] * alpha + pv;
-        acc[i] *= alpha;
-        ps[wave][lane][i] = pv;
-      }
-      __builtin_amdgcn_wave_barrier();
-      if (!lmk) {
-        // rows of absent / not yet decoded tokens: p is zero for every live query, their value rows are not read
-        const int j0 = max(0, -(kbase + tile * KT)), j1 = min(KT, min(Wk - tile * KT, tend - (kbase + tile * KT)));
-        if (j1 > j0) pv_rows<E, D>(rows, p.v, b, h, rows.wrap(ks0 + tile * KT + j0), j1 - j0, kg, dc, &ps[wave][j0], acc);
-      } else {
-        pv_rows<float, D>(Rows<false>{}, p.lv, b, h, (tile - nlt) * KT, min(KT, lmax - (tile - nlt) * KT), kg, dc, ps[wave], acc);
-      }
-      __builtin_amdgcn_wave_barrier();
-    }
-#pragma unroll
-    for (int i = 0; i < QPW; ++i) {
-      l[i] = wave_sum(l[i]);
-#pragma unroll
-      for (int o = G; o < 64; o <<= 1)
-#pragma unroll
-        for (int c = 0; c < 4; ++c) acc[i][c] += __shfl_xor(acc[i][c], o);
-    }
+    stream_tiles<E, D, RING, true>(p, b, h, gr, wave % nsplit, nsplit, qs[wave], ps[wave], lane, m, l, acc);
     if (nsplit == 1) {
       if (lane < G) {
 #pragma unroll
         for (int i = 0; i < QPW; ++i)
-          if (i < nql) Io<E>::st4(const_cast<char*>(row<E>(p.o, b, h, qa + i - t0)) + (size_t)dc * Io<E>::SZ, acc[i] * (1.f / l[i]));
+          if (i < gr.nql) Io<E>::st4(const_cast<char*>(row<E>(p.o, b, h, gr.qa + i - t0)) + (size_t)dc * Io<E>::SZ, acc[i] * (1.f / l[i]));
       }
     } else {
-      if (lane < G) {
-#pragma unroll
-        for (int i = 0; i < QPW; ++i) *reinterpret_cast<f32x4*>(&mo[wave][i][dc]) = acc[i];
-      }
-      if (lane == 0) {
-#pragma unroll
-        for (int i = 0; i < QPW; ++i) { ml[wave][i][0] = m[i]; ml[wave][i][1] = l[i]; }
-      }
+      stash_partial<D>(m, l, acc, mo[wave], ml[wave], lane);
     }
   }
   if (nsplit == 1) return;                         // (uniform over the workgroup)
@@ -144,15 +65,8 @@ __global__ __launch_bounds__(NT) void CEVA_KERNEL(ceva_attn)(const DecP p) {
   const int qa = tq0 + g * QPW, nql = min(QPW, tq1 - qa);
   for (int idx = lane; idx < nql * G; idx += 64) {
     const int i = idx / G, c = (idx - i * G) * 4;
-    float mx = -INFINITY;
-    for (int w = wave; w < wave + nsplit; ++w) mx = fmaxf(mx, ml[w][i][0]);
-    float lt = 0.f;
-    f32x4 o = {0.f, 0.f, 0.f, 0.f};
-    for (int w = wave; w < wave + nsplit; ++w) {
-      const float f = ml[w][i][0] == -INFINITY ? 0.f : __expf(ml[w][i][0] - mx);
-      lt += f * ml[w][i][1];
-      o += f * *reinterpret_cast<const f32x4*>(&mo[w][i][c]);
-    }
+    float mx, lt;
+    const f32x4 o = merge_waves<D>(mo, ml, wave, nsplit, i, c, mx, lt);
     Io<E>::st4(const_cast<char*>(row<E>(p.o, b, h, qa + i - t0)) + (size_t)c * Io<E>::SZ, o * (1.f / lt));
   }
 }

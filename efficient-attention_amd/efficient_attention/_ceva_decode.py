@@ -561,6 +561,8 @@ class CevaDecoding:
         tq, tk, tv = [nv.t4(cache[:, :, i].transpose(1, 2)) for i in range(3)]      # [B, h, cap (or ring), d] views
         tl, tb = nv.t4(state["rf_k_bar"]), nv.t4(state["beta"])
         mask_p = nv.ptr(pad) if has_pad else None
+        rows = (ctypes.byref(tq), ctypes.byref(tk), ctypes.byref(tv), mask_p)      # the token rows and their pad flags
+        lmk = (ctypes.byref(tl), ctypes.byref(tb))                                 # the landmark rows
         st = nv.stream()
         if static is not None:
             nv.call("ea_ceva_sdecode_append", g, nv.ptr(qkv_new), nv.ptr(step_pad), nv.ptr(cache), nv.ptr(pad), st)
@@ -572,20 +574,17 @@ class CevaDecoding:
                     self._decode_mu_cache = _ops.DerivedCache()
                 mlp = self._decode_mu_cache.get(self, self._mu_params(), self._decode_mu_f32)
             mp = (ctypes.c_void_p * len(mlp))(*[p.data_ptr() for p in mlp])
-            nv.call(family + "close", g, ctypes.byref(tq), ctypes.byref(tk), ctypes.byref(tv), mask_p, mp,
-                    ctypes.byref(tl), ctypes.byref(tb), st)
+            nv.call(family + "close", g, *rows, mp, *lmk, st)
         out = torch.empty((T_new, B, h, d), dtype=cache.dtype, device=dev)
         to = nv.t4(out.permute(1, 2, 0, 3))                        # [B, h, T_new, d] view of the time-first rows
         if static is not None and "split_ws" in state and T_new <= _SPLIT_MAX_STEP and not piece:
             # (the token count of the step the caller handed over decides, and a capture fixes it; the pieces of a prompt,
             #  its short tail included, are the prompt's)
             ws, parts = state["split_ws"], state["split_ws"].shape[3]
-            nv.call("ea_ceva_sdecode_attn_split", g, ctypes.byref(tq), ctypes.byref(tk), ctypes.byref(tv), mask_p, nv.ptr(bias),
-                    ctypes.byref(tl), ctypes.byref(tb), ctypes.byref(to), parts, nv.ptr(ws), st)
+            nv.call("ea_ceva_sdecode_attn_split", g, *rows, nv.ptr(bias), *lmk, ctypes.byref(to), parts, nv.ptr(ws), st)
             nv.call("ea_ceva_sdecode_merge", g, ctypes.byref(to), parts, nv.ptr(ws), st)
         else:
-            nv.call(family + "attn", g, ctypes.byref(tq), ctypes.byref(tk), ctypes.byref(tv), mask_p, nv.ptr(bias),
-                    ctypes.byref(tl), ctypes.byref(tb), ctypes.byref(to), st)
+            nv.call(family + "attn", g, *rows, nv.ptr(bias), *lmk, ctypes.byref(to), st)
         if static is not None:
             nv.call("ea_ceva_sdecode_advance", g, st)
             if not capturing and "ntok" not in state:              # (a replay advances only the device count; per-sequence

@@ -261,6 +261,7 @@ ATTN_CASES = [
     ("ext_block0", 32, 16, 16, 8, 3, 4, 2),        # left extension in block 0 (absent slots)
     ("ext_boundary", 64, 32, 32, 8, 60, 9, 2),     # extension, across a boundary
     ("prefill", 128, 64, 0, 8, 0, 150, 1),         # many queries per block, three blocks
+    ("two_groups", 64, 32, 0, 4, 32, 12, 2),       # two query groups of two waves each: the in-LDS merge at waves 0 and 2
 ]
 
 
