@@ -223,8 +223,8 @@ class TableBias:
     ONE launch (ea_table_bias_fwd) and grad() takes the kernels' bias gradient back to the table in one (ea_table_bias_bwd):
     the framework spent an index_select, a permute copy, a scalar multiply, a pad (fill + copy) and, in the backward, a slice
     copy and the transposed chain on it -- six to eight launches of ~4 us in every EVA / local-window step.
-    The single-node module paths (EvaModuleFn, CoreModuleFn + LocalCore) take the TABLE as their differentiable input together
-    with this spec; every other path keeps the dense [h, Wq, Wk] bias."""
+    The single-node module paths (CoreModuleFn around an EvaCore or a LocalCore) take the TABLE as their differentiable input
+    together with this spec; every other path keeps the dense [h, Wq, Wk] bias."""
 
     def __init__(self, idx, rows, Wq, Wk, scale, inv=None):
         flat = idx.detach().reshape(-1).cpu().long()
@@ -485,6 +485,14 @@ class LocalAttnLseFn(torch.autograd.Function):
         return dqkv5, _opt(dbias), None, None, None, None, None
 
 
+def _mlp_grads(dW, dvec, d):
+    """The two d x d matrices and the 2 x 3 vectors of the landmark / mu networks' gradient, [2 d d] and [6 d] floats as the
+    kernels (or the sums over their per-(b,h) partials) leave them -> the eight gradients in parameter order: W, b, gamma,
+    beta of the q side, then of the k side."""
+    dWs, dvs = dW.view(2, d, d), dvec.view(2, 3, d)
+    return [dWs[0], dvs[0, 0], dvs[0, 1], dvs[0, 2], dWs[1], dvs[1, 0], dvs[1, 1], dvs[1, 2]]
+
+
 # ------------------------------------------------------------------------------------------
 # EVA  (reference eva.py:145-227)
 # ------------------------------------------------------------------------------------------
@@ -669,8 +677,7 @@ def eva_bwd_impl(dout, qkv5, mask_u8, keep, noise, out, saved_list, icfg, fcfg, 
                 extra = (tmp[o_db:o_db + rows_db * n_db].view(rows_db, n_db), tuple(bias_p.shape))
             return [dqkv5, _e(dbias, ws), ("partials", tmp[o_dW:o_dW + BH * 2 * d * d].view(BH, 2 * d * d),
                                           tmp[o_dvec:o_dvec + BH * 6 * d].view(BH, 6 * d)) + extra] + fin_
-        dWs, dvs = dpar[:2 * d * d].view(2, d, d), dpar[2 * d * d:].view(2, 3, d)
-        return [dqkv5, _e(dbias, ws), dWs[0], dvs[0, 0], dvs[0, 1], dvs[0, 2], dWs[1], dvs[1, 0], dvs[1, 1], dvs[1, 2]] + fin_
+        return [dqkv5, _e(dbias, ws)] + _mlp_grads(dpar[:2 * d * d], dpar[2 * d * d:], d) + fin_
     if defer_chunk_mean:
         raise RuntimeError("eva_bwd: defer_chunk_mean needs the composite entry points")
     geom, L, mu_scale, keep_scale, fused_mu = _eva_cfg(qkv5, icfg, fcfg, adaptive_proj)
@@ -704,10 +711,7 @@ def eva_bwd_impl(dout, qkv5, mask_u8, keep, noise, out, saved_list, icfg, fcfg, 
                 nv.ptr(mask_u8), ctypes.byref(tdq), ctypes.byref(tdk), nv.stream())
         if defer_param_sums:                       # (direct calls only) the per-(b,h) partials, still to be added up
             return [dqkv5, _e(dbias, lse), ("partials", dW.view(lg.BH, -1), dvec.view(lg.BH, -1))]
-        dWs, dvs = colsum2_f32(dW.view(lg.BH, -1), dvec.view(lg.BH, -1))
-        dWs, dvs = dWs.view(2, d, d), dvs.view(2, 3, d)
-        raw = [dWs[0], dvs[0, 0], dvs[0, 1], dvs[0, 2], dWs[1], dvs[1, 0], dvs[1, 1], dvs[1, 2]]
-        return [dqkv5, _e(dbias, lse)] + raw
+        return [dqkv5, _e(dbias, lse)] + _mlp_grads(*colsum2_f32(dW.view(lg.BH, -1), dvec.view(lg.BH, -1)), d)
     # mu networks backward (ea_rows_mlp_bwd): dz, dx = d(chunk means), per-workgroup dW partials
     # and the feed buffer whose column sums are the bias / gamma / beta gradients
     sides = 1 if adaptive_proj == "none" else 2
@@ -816,186 +820,11 @@ USE_EVA_MODULE_FN = os.environ.get("EA_EVA_MODULE_FN", "1") == "1"
 
 
 def eva_module_fn_supported(x, qkv, proj, cdtype, adaptive_proj, L, d):
-    """The single-node path of EVA (EvaModuleFn): what LaraModuleFn needs of the projections, plus the fused landmark
-    kernel for the mu networks (adaptive_proj 'default', L <= 64, d in {32, 64})."""
+    """The single-node path of EVA (EvaModuleFn = CoreModuleFn around an EvaCore): what the module node needs of the projections
+    (lara_module_fn_supported), plus the fused landmark kernel for the mu networks (adaptive_proj 'default', L <= 64, d in {32, 64})."""
     return (USE_EVA_MODULE_FN and adaptive_proj == "default" and L <= 64 and d in (32, 64)
             and lara_module_fn_supported(x, qkv, proj, cdtype, allow_lib=True)
             and not torch.compiler.is_compiling() and torch._C._len_torch_dispatch_stack() == 0 and _DIRECT)
-
-
-class EvaModuleFn(torch.autograd.Function):
-    """qkv projection -> EVA core -> output projection as ONE autograd node (round 4, the EVA counterpart of LaraModuleFn): the
-    same launches as LinearFn / LinearPoolFn + EvaAttnFn + LinearFn without two of the three nodes' host cost, the chunk means
-    out of the projection kernel where it can emit them, and the terminal sums of the backward (both weight gradients' slice
-    partials, the mu networks' per-(b,h) partials) in ONE launch (ea_multi_sum).
-    args: x [B, *seq, C], qkv weight / bias, proj weight / bias, dense bias [h, Wq, Wk] | None, mask_u8, noise, cfg (EvaAttnFn's
-    first seven entries), compute dtype, heads, then the mu-network parameters."""
-
-    @staticmethod
-    def forward(ctx, x, wq, bq, wp, bp, bias, mask_u8, noise, cfg, cdtype, heads, *params):
-        attn_2d, seq_shape, window, ext, chunk, L, adaptive_proj = cfg[:7]
-        tb = cfg[7] if len(cfg) > 7 else None         # TableBias: `bias` is then the TABLE [rows, h]
-        C = x.shape[-1]
-        B = x.shape[0]
-        N = x.numel() // (B * C)
-        d = C // heads
-        x2 = x.reshape(-1, C)
-        elem = _ELEM[cdtype]
-        bias_dt_in = None if bias is None else bias.dtype
-        if tb is not None:
-            bias = tb.dense(bias, tb.ld(B, heads, N, d, elem, attn_2d, seq_shape, window, ext, int(chunk), int(L), 0))
-        bq32 = None if bq is None else (bq if bq.dtype == torch.float32 else bq.float())
-        bp32 = None if bp is None else (bp if bp.dtype == torch.float32 else bp.float())
-        want = x2.dtype == torch.float32 and ctx.needs_input_grad[1]
-        icfg = _geo(attn_2d, seq_shape, window, ext) + [int(chunk), int(L), 0, int(any(ctx.needs_input_grad))]
-        fcfg = [0.5, 1.0]
-        pooled = None
-        comp = _eva_use_composite()
-        lcfg, sizes = (_eva_layer_cfg_dims(B, heads, d, elem, icfg, fcfg, adaptive_proj, bias is not None, mask_u8 is not None)
-                       if comp else (None, None))
-        lib = module_proj_lib(C)
-        w16p = b16p = None
-        w192 = prepare_w192(wq, wp, cdtype) if (not lib and w192_usable(wq, wp, cdtype)) else None
-        w16pT = None if w192 is None else w192[3]
-        if lib:
-            # 320 / 512 / 1024-wide layers (round 6): library GEMMs on 16-bit operands inside the node -- the four parameter
-            # casts in one launch, the rounded weights kept for the backward's two input-gradient GEMMs
-            w16, b16q, w16p, b16p = lib_casts(wq, bq, wp, bp, cdtype)
-            y, xc = lib_project(x2, wq, bq32, w16, b16q, cdtype)
-            want = True
-        elif (attn_2d and ext == 0 and mask_u8 is None
-                and proj_pool_supported(x2, wq, cdtype, B, seq_shape[0], seq_shape[1], chunk, heads)):
-            if lcfg is not None:
-                # the projection kernel writes the chunk means straight into the composite entry's workspace
-                ws = torch.empty(sizes[0], dtype=torch.float32, device=x.device)
-                n_p = B * heads * L * d
-                pq, pk = ws[sizes[2]:sizes[2] + n_p], ws[sizes[3]:sizes[3] + n_p]
-                pooled = (ws,)
-            else:
-                pq = torch.empty((B * heads, L, d), dtype=torch.float32, device=x.device)
-                pk = torch.empty_like(pq)
-                pooled = (pq, pk)
-            if w192 is not None:
-                w16 = w192[0]
-                y, xc = project_qkv_wsw(x2, w192[1], w16, bq32, cdtype, want, (B, seq_shape[0], seq_shape[1], chunk), pq, pk)
-            else:
-                w16 = torch.empty((3 * C, C), dtype=cdtype, device=x.device) if ctx.needs_input_grad[0] else None
-                y, xc = project_qkv_pooled(x2, wq, bq32, cdtype, want, B, seq_shape[0], seq_shape[1], chunk, pq, pk, w_cast=w16)
-        elif w192 is not None:
-            w16 = w192[0]
-            y, xc = project_qkv_wsw(x2, w192[1], w16, bq32, cdtype, want)
-            xc = xc if want else None
-        else:
-            w16 = None
-            y, xc = linear_w32_impl(x2, wq, bq32, elem, False, False, want)
-            xc = xc if want else None
-        xl = x2 if x2.dtype == cdtype else (xc if want else None)
-        qkv5 = y.view(B, N, 3, heads, d)
-        outs = eva_fwd_impl(qkv5, bias, noise, mask_u8, None, icfg, fcfg, adaptive_proj, list(params), pooled=pooled,
-                            composite=lcfg is not None)
-        o2 = outs[0].reshape(-1, C)
-        if lib:
-            with torch.autocast(device_type="cuda", enabled=False):
-                y2 = F.linear(o2, w16p, b16p)
-        elif w192 is not None:
-            y2 = ea_linear(o2, w192[2], bp32, cdtype)[0]
-        else:
-            y2 = linear_w32_impl(o2, wp, bp32, elem, False, False, False)[0]
-        ctx.save_for_backward(xl, qkv5, mask_u8, noise, o2, wq, wp, w16, w16p, w16pT, *outs[1:], *params)
-        ctx.icfg, ctx.fcfg, ctx.nsaved, ctx.adaptive = icfg, fcfg, len(outs) - 1, adaptive_proj
-        ctx.meta = (x.shape, x.dtype, cdtype, None if bq is None else bq.dtype, None if bp is None else bp.dtype, wq.dtype, wp.dtype,
-                    [t.dtype for t in params], heads, 0 if bias is None else bias.shape[-1], bias_dt_in)
-        ctx.tb = tb
-        return y2.view(x.shape)
-
-    @staticmethod
-    def backward(ctx, dy):
-        xl, qkv5, mask_u8, noise, o2, wq, wp, w16, w16p, w16pT, *rest = ctx.saved_tensors
-        saved, params = rest[:ctx.nsaved], rest[ctx.nsaved:]
-        xshape, xdtype, cdtype, bqd, bpd, wqd, wpd, pdtypes, heads, bias_cols, bias_dt = ctx.meta
-        C = xshape[-1]
-        d = C // heads
-        elem = _ELEM[cdtype]
-        need = ctx.needs_input_grad
-        dy2 = dy.reshape(-1, C)
-        if dy2.dtype != cdtype:
-            dy2 = dy2.to(cdtype)
-        if w16p is not None:                          # library flavour (module_proj_lib): d out = dy W_proj on the rounded weight
-            dy2 = dy2 if dy2.is_contiguous() else dy2.contiguous()
-            d_o2 = dy2 @ w16p
-        elif w16pT is not None and _lin_rows_ok(dy2, cdtype):   # prepared transposed copy (round 6)
-            d_o2 = ea_linear(dy2, w16pT, None, cdtype)[0]
-        else:
-            d_o2 = linear_w32_impl(dy2, wp, None, elem, True, False, False)[0]
-        defer = USE_MULTI_SUM
-        pend = []
-        dwp = dbp = dwq = dbq = dx = None
-        need_bp = bpd is not None and need[4]
-        pair = bool(defer and need[3] and need[1] and xl is not None
-                    and wgrad_pair_usable(qkv5.view(-1, 3 * C), xl, dy2, o2))
-        if need[3] and not pair:
-            r_ = wgrad(dy2, o2, need_bp, defer=defer)
-            if defer:
-                pend.append(("proj", r_[0], r_[1]))
-            else:
-                dwp, dbp = r_[0].to(wpd), (r_[1].to(bpd) if need_bp else None)
-        elif need_bp and not pair:
-            dbp = bias_grad(dy2 if dy2.is_contiguous() else dy2.contiguous()).to(bpd)
-        B, N = qkv5.shape[:2]
-        # round 5: with the composite workspace saved and the input gradient wanted, the chunk-mean backward is left to the
-        # input-gradient kernel (ea_linear_dgrad_finish adds the d(chunk mean) / r^2 terms on its way: one pass instead of two)
-        use_fin = bool(need[0] and len(saved) == 2 and dgrad_finish_usable(qkv5.view(-1, 3 * C), wq, xdtype, heads, d))
-        g = eva_bwd_impl(d_o2.view(B, N, heads, d), qkv5, mask_u8, None, noise, o2.view(B, N, heads, d), list(saved), ctx.icfg,
-                         ctx.fcfg, ctx.adaptive, bias_cols, list(params), defer_param_sums=defer, defer_chunk_mean=use_fin)
-        fin = g.pop()[1] if use_fin else None
-        dqkv2 = g[0].view(-1, 3 * C)
-        if fin is not None:
-            dx = qkv_dgrad_finish(dqkv2, None, wq, w16, xdtype, fin).view(xshape)    # (corrects dq / dk in place: before the weight gradient)
-        dbias = _opt(g[1])
-        pgrads = list(g[2:])
-        if pgrads and isinstance(pgrads[0], tuple):
-            pend.append(("mu_W", pgrads[0][1], None))
-            pend.append(("mu_v", pgrads[0][2], None))
-            if len(pgrads[0]) > 3:                                  # bias-gradient partials of the composite backward
-                pend.append(("dbias", pgrads[0][3], pgrads[0][4]))
-            pgrads = []
-        need_bq = bqd is not None and need[2]
-        if pair:
-            rq, rp = wgrad_pair(dqkv2, xl, need_bq, dy2, o2, need_bp)
-            pend.append(("qkv", rq[0], rq[1]))
-            pend.append(("proj", rp[0], rp[1]))
-        elif need[1]:
-            if xl is None:
-                raise RuntimeError("EvaModuleFn: the weight gradient was requested but the forward did not keep its input")
-            r_ = wgrad(dqkv2, xl, need_bq, defer=defer)
-            if defer:
-                pend.append(("qkv", r_[0], r_[1]))
-            else:
-                dwq, dbq = r_[0].to(wqd), (r_[1].to(bqd) if need_bq else None)
-        elif need_bq:
-            dbq = bias_grad(dqkv2).to(bqd)
-        if need[0] and dx is None:
-            dx = qkv_dgrad(dqkv2, wq, w16, xdtype).view(xshape)
-        if pend:
-            sums = multi_sum([t for _, t, _ in pend])
-            res = {what: (o, meta) for (what, _, meta), o in zip(pend, sums)}
-            if "proj" in res:
-                dwp, dbp32 = _wgrad_split(*res["proj"])
-                dwp, dbp = dwp.to(wpd), (dbp32.to(bpd) if need_bp else None)
-            if "qkv" in res:
-                dwq, dbq32 = _wgrad_split(*res["qkv"])
-                dwq, dbq = dwq.to(wqd), (dbq32.to(bqd) if need_bq else None)
-            if "mu_W" in res:
-                dWs, dvs = res["mu_W"][0].view(2, d, d), res["mu_v"][0].view(2, 3, d)
-                pgrads = [dWs[0], dvs[0, 0], dvs[0, 1], dvs[0, 2], dWs[1], dvs[1, 0], dvs[1, 1], dvs[1, 2]]
-            if "dbias" in res:
-                dbias = res["dbias"][0].view(res["dbias"][1])[..., :bias_cols].contiguous()
-        pgrads = [t.to(dt) for t, dt in zip(pgrads, pdtypes)]
-        if dbias is not None and ctx.tb is not None:
-            dbias = ctx.tb.grad(dbias)                 # [h, Wq, ld] -> d table [rows, h], one launch
-        if dbias is not None and bias_dt is not None:
-            dbias = dbias.to(bias_dt)
-        return (dx, dwq, dbq, dwp, dbp, dbias, None, None, None, None, None) + tuple(pgrads)
 
 
 # ------------------------------------------------------------------------------------------
@@ -1642,9 +1471,7 @@ def lara_bwd_impl(dout, qkv5, mask_u8, noise, saved_list, icfg, fcfg, params, de
             return grads[:1] + [("partials", tmp[o_dW:o_dW + BH * 2 * d * d].view(BH, 2 * d * d),
                                  tmp[o_dvec:o_dvec + BH * 6 * d].view(BH, 6 * d))] + grads[1:]
         if ps:
-            dWs, dvs = dpar[:2 * d * d].view(2, d, d), dpar[2 * d * d:].view(2, 3, d)
-            fin_ = grads[1:]
-            grads = grads[:1] + [dWs[0], dvs[0, 0], dvs[0, 1], dvs[0, 2], dWs[1], dvs[1, 0], dvs[1, 1], dvs[1, 2]] + fin_
+            grads = grads[:1] + _mlp_grads(dpar[:2 * d * d], dpar[2 * d * d:], d) + grads[1:]
         return grads
     (H, W, r, has_mlp, mixed, mis, dup, L, C), pgeom, lg, geom = _lara_cfg(qkv5, icfg, fcfg)
     if defer_finish and C > 64:
@@ -1684,9 +1511,7 @@ def lara_bwd_impl(dout, qkv5, mask_u8, noise, saved_list, icfg, fcfg, params, de
     if has_mlp and defer_param_sums:
         return grads + [("partials", dW.view(BH, -1), dvec.view(BH, -1))] + fin_
     if has_mlp:
-        dWs, dvs = colsum2_f32(dW.view(BH, -1), dvec.view(BH, -1))
-        dWs, dvs = dWs.view(2, d, d), dvs.view(2, 3, d)
-        grads += [dWs[0], dvs[0, 0], dvs[0, 1], dvs[0, 2], dWs[1], dvs[1, 0], dvs[1, 1], dvs[1, 2]]
+        grads += _mlp_grads(*colsum2_f32(dW.view(BH, -1), dvec.view(BH, -1)), d)
     return grads + fin_
 
 
@@ -1798,181 +1623,11 @@ def project_qkv_wsw(x2, wsw, w16q, bq32, cdtype, want_cast, grid=None, pq=None, 
     return y, a_cast
 
 
-class LaraModuleFn(torch.autograd.Function):
-    """qkv projection -> 2-D pooled LARA core -> output projection as ONE autograd node (round 3): the same launches as
-    LinearFn + LaraPooledFn + LinearFn, without two of the three nodes' host cost (ctx objects, saved-tensor packing, engine
-    hand-overs: ~0.1 ms of the eager step, which is host-bound).  Only for the common training case -- autocast in a 16-bit
-    dtype, fp32 master weights the projection kernels cover -- every other case keeps the three nodes (lara.py).
-    args: x [B, H, W, C], qkv weight / bias, proj weight / bias, mask_u8, noise, cfg (LaraPooledFn's), compute dtype, heads,
-    then the generator parameters."""
-
-    @staticmethod
-    def forward(ctx, x, wq, bq, wp, bp, mask_u8, noise, cfg, cdtype, heads, *params):
-        H, W, r, has_mlp, mixed, mis, dup, kappa, scale = cfg
-        C = x.shape[-1]
-        B = x.shape[0]
-        N = x.numel() // (B * C)
-        x2 = x.reshape(-1, C)
-        elem = _ELEM[cdtype]
-        bq32 = None if bq is None else (bq if bq.dtype == torch.float32 else bq.float())
-        bp32 = None if bp is None else (bp if bp.dtype == torch.float32 else bp.float())
-        want = x2.dtype == torch.float32 and ctx.needs_input_grad[1]
-        icfg = [int(H), int(W), int(r), int(bool(has_mlp)), int(bool(mixed)), int(mis), int(dup),
-                int(any(ctx.needs_input_grad))]
-        fcfg = [float(kappa), float(scale)]
-        direct = _DIRECT and not torch.compiler.is_compiling() and torch._C._len_torch_dispatch_stack() == 0
-        w192 = prepare_w192(wq, wp, cdtype) if (direct and w192_usable(wq, wp, cdtype)) else None
-        if direct and proj_pool_supported(x2, wq, cdtype, B, H, W, r, heads):
-            # round 4: the projection kernel walks the tokens cell by cell and emits the pooled q / k rows itself -- the
-            # pooling pass (ea_eva_chunk_mean_fwd: q, k read once more, 87 MB / 17 us at cfg3) is gone
-            d, L = C // heads, (H // r) * (W // r)
-            lcfg, sizes = _lara_layer_cfg_dims(B, heads, d, elem, icfg, fcfg) if _lara_use_composite() else (None, None)
-            if lcfg is not None:
-                ws = torch.empty(sizes[0], dtype=torch.float32, device=x.device)
-                o_pq, o_pk = sizes[3], sizes[4]
-                n_p = B * heads * L * d
-                pooled = (ws, None, None)
-                pq, pk = ws[o_pq:o_pq + n_p], ws[o_pk:o_pk + n_p]
-            else:
-                pq = torch.empty((B * heads, L, d), dtype=torch.float32, device=x.device)
-                pk = torch.empty_like(pq)
-                pooled = (None, pq, pk)
-            if w192 is not None:
-                # round 6: both weights rounded (and the qkv weight arranged for this kernel) by one launch up front
-                w16 = w192[0]
-                y, xc = project_qkv_wsw(x2, w192[1], w16, bq32, cdtype, want, (B, H, W, r), pq, pk)
-            else:
-                # the rounded weight for the backward's input-gradient GEMM leaves with the same launch (no cast kernel there)
-                w16 = torch.empty((3 * C, C), dtype=cdtype, device=x.device) if ctx.needs_input_grad[0] else None
-                y, xc = project_qkv_pooled(x2, wq, bq32, cdtype, want, B, H, W, r, pq, pk, w_cast=w16)
-            xl = x2 if x2.dtype == cdtype else (xc if want else None)
-            qkv5 = y.view(B, N, 3, heads, d)
-            outs = lara_fwd_impl(qkv5, mask_u8, noise, icfg, fcfg, list(params), pooled=pooled)
-        else:
-            w16 = None
-            if w192 is not None:
-                w16 = w192[0]
-                y, xc = project_qkv_wsw(x2, w192[1], w16, bq32, cdtype, want)
-            else:
-                y, xc = _ea_op("linear_w32", linear_w32_impl, x2, wq, bq32, elem, False, False, want)
-            xl = x2 if x2.dtype == cdtype else (xc if want else None)
-            qkv5 = y.view(B, N, 3, heads, C // heads)
-            outs = _ea_op("lara_fwd", lara_fwd_impl, qkv5, mask_u8, noise, icfg, fcfg, list(params))
-        o2 = outs[0].reshape(-1, C)
-        if w192 is not None:
-            y2 = ea_linear(o2, w192[2], bp32, cdtype)[0]
-        else:
-            y2 = _ea_op("linear_w32", linear_w32_impl, o2, wp, bp32, elem, False, False, False)[0]
-        w16pT = None if w192 is None else w192[3]
-        ctx.save_for_backward(xl, qkv5, mask_u8, noise, o2, wq, wp, w16, w16pT, *outs[1:], *params)
-        ctx.icfg, ctx.fcfg, ctx.nsaved = icfg, fcfg, len(outs) - 1
-        ctx.meta = (x.shape, x.dtype, cdtype, None if bq is None else bq.dtype, None if bp is None else bp.dtype, wq.dtype, wp.dtype,
-                    [t.dtype for t in params], heads)
-        return y2.view(x.shape)
-
-    @staticmethod
-    def backward(ctx, dy):
-        xl, qkv5, mask_u8, noise, o2, wq, wp, w16, w16pT, *rest = ctx.saved_tensors
-        saved, params = rest[:ctx.nsaved], rest[ctx.nsaved:]
-        xshape, xdtype, cdtype, bqd, bpd, wqd, wpd, pdtypes, heads = ctx.meta
-        C = xshape[-1]
-        elem = _ELEM[cdtype]
-        need = ctx.needs_input_grad
-        dy2 = dy.reshape(-1, C)
-        if dy2.dtype != cdtype:
-            dy2 = dy2.to(cdtype)
-        # output projection: input gradient from the master weight read transposed (or from the prepared transposed copy of
-        # round 6), weight + bias gradient in one pass
-        if w16pT is not None and _lin_rows_ok(dy2, cdtype):
-            d_o2 = ea_linear(dy2, w16pT, None, cdtype)[0]
-        else:
-            d_o2 = _ea_op("linear_w32", linear_w32_impl, dy2, wp, None, elem, True, False, False)[0]
-        direct = _DIRECT and not torch.compiler.is_compiling() and torch._C._len_torch_dispatch_stack() == 0
-        # round 4: the terminal sums of this backward -- slice partials of both weight gradients, per-(b,h) partials of the
-        # landmark parameters -- are added up by ONE launch at the end (ea_multi_sum) instead of three
-        defer = direct and USE_MULTI_SUM
-        pend = []                                                  # (what, partial tensor, meta)
-        dwp = dbp = None
-        need_bp = bpd is not None and need[4]
-        # both weight gradients in ONE launch at the end of this backward when both are wanted (ea_wgrad_pair)
-        pair = bool(defer and need[3] and need[1] and wgrad_pair_usable(dy2, o2, qkv5.view(-1, 3 * C), xl))
-        if need[3] and not pair:
-            r_ = wgrad(dy2, o2, need_bp, defer=defer)
-            if defer:
-                pend.append(("proj", r_[0], r_[1]))
-            else:
-                dwp, dbp32 = r_
-                dwp = dwp.to(wpd)
-                dbp = dbp32.to(bpd) if need_bp else None
-        elif need_bp and not pair:
-            dbp = bias_grad(dy2 if dy2.is_contiguous() else dy2.contiguous()).to(bpd)
-        B, N = qkv5.shape[:2]
-        fin = None
-        if defer:
-            # round 5: with a single composite workspace saved and the input gradient wanted, the finish pass of the core is
-            # left to the input-gradient kernel (ea_linear_dgrad_finish: one pass over the gradient rows instead of two)
-            use_fin = bool(need[0] and ctx.icfg[6] == 0 and dgrad_finish_usable(qkv5.view(-1, 3 * C), wq, xdtype, heads, C // heads)
-                           and (ctx.icfg[0] // ctx.icfg[2]) * (ctx.icfg[1] // ctx.icfg[2]) <= 64)
-            grads = lara_bwd_impl(d_o2.view(B, N, heads, C // heads), qkv5, mask_u8, noise, list(saved), ctx.icfg, ctx.fcfg,
-                                  list(params), defer_param_sums=True, defer_finish=use_fin)
-            if use_fin:
-                fin = grads.pop()[1]
-            if grads[1:] and isinstance(grads[1], tuple):
-                pend.append(("lmk_W", grads[1][1], None))
-                pend.append(("lmk_v", grads[1][2], None))
-                grads = grads[:1]
-        else:
-            grads = _ea_op("lara_bwd", lara_bwd_impl, d_o2.view(B, N, heads, C // heads), qkv5, mask_u8, noise, list(saved),
-                           ctx.icfg, ctx.fcfg, list(params))
-        dqkv2 = grads[0].view(-1, 3 * C)
-        dwq = dbq = dx = None
-        need_bq = bqd is not None and need[2]
-        if fin is not None:
-            # corrects the dq / dk columns of dqkv2 in place: BEFORE the weight gradient reads them
-            dx = qkv_dgrad_finish(dqkv2, qkv5.view(-1, 3 * C), wq, w16, xdtype, fin).view(xshape)
-        if pair:
-            rq, rp = wgrad_pair(dqkv2, xl, need_bq, dy2, o2, need_bp)
-            pend.append(("qkv", rq[0], rq[1]))
-            pend.append(("proj", rp[0], rp[1]))
-        elif need[1]:
-            if xl is None:
-                raise RuntimeError("LaraModuleFn: the weight gradient was requested but the forward did not keep its input")
-            r_ = wgrad(dqkv2, xl, need_bq, defer=defer)
-            if defer:
-                pend.append(("qkv", r_[0], r_[1]))
-            else:
-                dwq, dbq32 = r_
-                dwq = dwq.to(wqd)
-                dbq = dbq32.to(bqd) if need_bq else None
-        elif need_bq:
-            # frozen qkv weight, trainable bias (bias-only fine-tuning): a column sum of d qkv, no input rows needed
-            dbq = bias_grad(dqkv2).to(bqd)
-        if need[0] and dx is None:
-            dx = qkv_dgrad(dqkv2, wq, w16, xdtype).view(xshape)
-        if pend:
-            sums = multi_sum([t for _, t, _ in pend])
-            res = {what: (o, meta) for (what, _, meta), o in zip(pend, sums)}
-            if "proj" in res:
-                dwp, dbp32 = _wgrad_split(*res["proj"])
-                dwp = dwp.to(wpd)
-                dbp = dbp32.to(bpd) if need_bp else None
-            if "qkv" in res:
-                dwq, dbq32 = _wgrad_split(*res["qkv"])
-                dwq = dwq.to(wqd)
-                dbq = dbq32.to(bqd) if need_bq else None
-            if "lmk_W" in res:
-                d = C // heads
-                dWs, dvs = res["lmk_W"][0].view(2, d, d), res["lmk_v"][0].view(2, 3, d)
-                grads = grads + [dWs[0], dvs[0, 0], dvs[0, 1], dvs[0, 2], dWs[1], dvs[1, 0], dvs[1, 1], dvs[1, 2]]
-        pgrads = [g.to(dt) for g, dt in zip(grads[1:], pdtypes)]
-        return (dx, dwq, dbq, dwp, dbp, None, None, None, None, None) + tuple(pgrads)
-
-
 USE_CORE_MODULE_FN = os.environ.get("EA_CORE_MODULE_FN", "1") == "1"
 
 
 class SoftmaxCore:
-    """Core spec of CoreModuleFn: dropout(softmax(s QK^T)) V (softmax_fwd_impl / softmax_bwd_impl)."""
+    """Core spec of CoreModuleFn (protocol: its docstring): dropout(softmax(s QK^T)) V (softmax_fwd_impl / softmax_bwd_impl)."""
     n_inputs = 0
 
     def __init__(self, mask_u8, keep=None, keep_scale=1.0):
@@ -2074,38 +1729,205 @@ class GraphCore:
         return (dqkv5 if dqkv5.is_contiguous() else dqkv5.contiguous()), tuple(extra)
 
 
+def _pooled_rows(sizes, i, BH, L, d, device):
+    """Where a projection kernel leaves the pooled q / k rows [BH, L, d] (fp32) -> (ws | None, pq, pk): inside a fresh workspace
+    of a composite entry (`sizes`, its size list: workspace floats, the rows' offsets at i and i + 1), or (None) on their own."""
+    if sizes is None:
+        pq = torch.empty((BH, L, d), dtype=torch.float32, device=device)
+        return None, pq, torch.empty_like(pq)
+    ws = torch.empty(sizes[0], dtype=torch.float32, device=device)
+    n = BH * L * d
+    return ws, ws[sizes[i]:sizes[i] + n], ws[sizes[i + 1]:sizes[i + 1] + n]
+
+
+def _project_qkv_grid(x2, wq, bq32, cdtype, want, need_dx, w192, grid, pq, pk):
+    """The `project` hook's launch: the qkv projection that writes the cell means of q / k over grid = (B, H, W, r) to pq / pk
+    (round 4: no pooling pass, 87 MB / 17 us at cfg3), from the prepared weights (round 6) or from the fp32 master weight, whose
+    rounded copy for the backward's input-gradient GEMM leaves with the same launch -> (y, rounded x | None, rounded weight | None)."""
+    if w192 is not None:
+        y, xc = project_qkv_wsw(x2, w192[1], w192[0], bq32, cdtype, want, grid, pq, pk)
+        return y, xc, w192[0]
+    w16 = torch.empty(tuple(wq.shape), dtype=cdtype, device=x2.device) if need_dx else None
+    y, xc = project_qkv_pooled(x2, wq, bq32, cdtype, want, *grid, pq, pk, w_cast=w16)
+    return y, xc, w16
+
+
+def _mlp_partials(t):
+    """('partials', W [BH, 2 d d], v [BH, 6 d], ...) of eva_bwd_impl / lara_bwd_impl -> entries for the node's terminal sum."""
+    return [("mlp_W", t[1], None), ("mlp_v", t[2], None)]
+
+
+class EvaCore:
+    """Core spec of the module node (EvaModuleFn): the EVA core (eva_fwd_impl / eva_bwd_impl, the composite entry points where
+    the geometry allows).  cfg = EvaAttnFn's first seven entries (+ a TableBias); the differentiable inputs are the dense
+    window bias [h, Wq, Wk] | None -- with a TableBias its TABLE [rows, h] -- and then the mu-network parameters."""
+    defers = True
+
+    def __init__(self, mask_u8, noise, cfg):
+        self.mask_u8, self.noise, self.cfg = mask_u8, noise, cfg
+        self.tb = cfg[7] if len(cfg) > 7 else None
+
+    def setup(self, B, N, heads, d, elem, inputs, need_grad):
+        attn_2d, seq_shape, window, ext, chunk, L, self.adaptive = self.cfg[:7]
+        bias = inputs[0]
+        if self.tb is not None:
+            bias = self.tb.dense(bias, self.tb.ld(B, heads, N, d, elem, attn_2d, seq_shape, window, ext, int(chunk), int(L), 0))
+        self.bias, self.bias_cols = bias, 0 if bias is None else bias.shape[-1]       # (the dense bias lives until fwd())
+        self.icfg = _geo(attn_2d, seq_shape, window, ext) + [int(chunk), int(L), 0, int(need_grad)]
+        self.fcfg = [0.5, 1.0]
+        self.sizes = (_eva_layer_cfg_dims(B, heads, d, elem, self.icfg, self.fcfg, self.adaptive, bias is not None,
+                                          self.mask_u8 is not None)[1] if _eva_use_composite() else None)    # None: step by step
+        self.dims, self.pooled = (B, heads, d), None
+
+    def project(self, x2, wq, bq32, cdtype, want, need_dx, w192):
+        attn_2d, seq_shape, _, ext, chunk, L = self.cfg[:6]
+        B, heads, d = self.dims
+        if not (attn_2d and ext == 0 and self.mask_u8 is None
+                and proj_pool_supported(x2, wq, cdtype, B, seq_shape[0], seq_shape[1], chunk, heads)):
+            return None
+        ws, pq, pk = _pooled_rows(self.sizes, 2, B * heads, L, d, x2.device)     # (composite: straight into the entry's workspace)
+        self.pooled = (pq, pk) if ws is None else (ws,)
+        return _project_qkv_grid(x2, wq, bq32, cdtype, want, need_dx, w192, (B, seq_shape[0], seq_shape[1], chunk), pq, pk)
+
+    def fwd(self, qkv5, inputs):
+        bias, pooled, self.bias, self.pooled = self.bias, self.pooled, None, None
+        outs = eva_fwd_impl(qkv5, bias, self.noise, self.mask_u8, None, self.icfg, self.fcfg, self.adaptive, list(inputs[1:]),
+                            pooled=pooled, composite=self.sizes is not None)
+        self.nsaved = len(outs) - 1
+        return outs[0], tuple(outs[1:]) + tuple(inputs[1:])
+
+    def bwd(self, dout, qkv5, out, saved, defer, fin_ok):
+        saved, params = saved[:self.nsaved], saved[self.nsaved:]
+        use_fin = fin_ok and len(saved) == 2    # round 5, composite only: ea_linear_dgrad_finish adds the d(chunk mean) / r^2 terms
+        g = eva_bwd_impl(dout, qkv5, self.mask_u8, None, self.noise, out, list(saved), self.icfg, self.fcfg, self.adaptive,
+                         self.bias_cols, list(params), defer_param_sums=defer, defer_chunk_mean=use_fin)
+        fin = (g.pop()[1], None) if use_fin else None
+        extra, parts = [_opt(g[1])] + g[2:], ()
+        if g[2:] and isinstance(g[2], tuple):     # the mu networks' per-(b,h) partials (+ the composite backward's of the bias)
+            parts = _mlp_partials(g[2]) + ([("dbias", g[2][3], g[2][4])] if len(g[2]) > 3 else [])
+            extra = extra[:1]
+        return g[0], extra, parts, fin
+
+    def scatter(self, res, extra):
+        dbias, pgrads = extra[0], extra[1:]
+        if "mlp_W" in res:
+            pgrads = _mlp_grads(res["mlp_W"][0], res["mlp_v"][0], self.dims[2])
+        if "dbias" in res:
+            dbias = res["dbias"][0].view(res["dbias"][1])[..., :self.bias_cols].contiguous()
+        if dbias is not None and self.tb is not None:
+            dbias = self.tb.grad(dbias)                # [h, Wq, ld] -> d table [rows, h], one launch
+        return [dbias] + pgrads
+
+
+class LaraCore:
+    """Core spec of the module node (LaraModuleFn): the 2-D pooled LARA core (lara_fwd_impl / lara_bwd_impl; through the
+    dispatcher ops while somebody is tracing).  cfg = LaraPooledFn's; the differentiable inputs are the generator parameters."""
+    defers = True
+
+    def __init__(self, mask_u8, noise, cfg):
+        self.mask_u8, self.noise, self.cfg = mask_u8, noise, cfg
+
+    def setup(self, B, N, heads, d, elem, inputs, need_grad):
+        H, W, r, has_mlp, mixed, mis, dup, kappa, scale = self.cfg
+        self.icfg = [int(H), int(W), int(r), int(bool(has_mlp)), int(bool(mixed)), int(mis), int(dup), int(need_grad)]
+        self.fcfg = [float(kappa), float(scale)]
+        self.dims, self.pooled = (B, heads, d, elem), None
+
+    def project(self, x2, wq, bq32, cdtype, want, need_dx, w192):
+        H, W, r = self.icfg[:3]
+        B, heads, d, elem = self.dims
+        if not proj_pool_supported(x2, wq, cdtype, B, H, W, r, heads):
+            return None
+        sizes = _lara_layer_cfg_dims(B, heads, d, elem, self.icfg, self.fcfg)[1] if _lara_use_composite() else None
+        ws, pq, pk = _pooled_rows(sizes, 3, B * heads, (H // r) * (W // r), d, x2.device)
+        self.pooled = (ws, None, None) if ws is not None else (None, pq, pk)
+        return _project_qkv_grid(x2, wq, bq32, cdtype, want, need_dx, w192, (B, H, W, r), pq, pk)
+
+    def fwd(self, qkv5, inputs):
+        pooled, self.pooled = self.pooled, None
+        if pooled is not None:
+            outs = lara_fwd_impl(qkv5, self.mask_u8, self.noise, self.icfg, self.fcfg, list(inputs), pooled=pooled)
+        else:
+            outs = _ea_op("lara_fwd", lara_fwd_impl, qkv5, self.mask_u8, self.noise, self.icfg, self.fcfg, list(inputs))
+        self.nsaved = len(outs) - 1
+        return outs[0], tuple(outs[1:]) + tuple(inputs)
+
+    def bwd(self, dout, qkv5, out, saved, defer, fin_ok):
+        saved, params = saved[:self.nsaved], saved[self.nsaved:]
+        args = (dout, qkv5, self.mask_u8, self.noise, list(saved), self.icfg, self.fcfg, list(params))
+        if not defer:
+            g = _ea_op("lara_bwd", lara_bwd_impl, *args)
+            return g[0], g[1:], (), None
+        H, W, r = self.icfg[:3]
+        # round 5: the finish pass of the core is left to the input-gradient kernel (ea_linear_dgrad_finish: one pass, not two)
+        use_fin = bool(fin_ok and self.icfg[6] == 0 and (H // r) * (W // r) <= 64)
+        g = lara_bwd_impl(*args, defer_param_sums=True, defer_finish=use_fin)
+        fin = (g.pop()[1], qkv5.view(qkv5.shape[0] * qkv5.shape[1], -1)) if use_fin else None
+        if g[1:] and isinstance(g[1], tuple):
+            return g[0], [], _mlp_partials(g[1]), fin
+        return g[0], g[1:], (), fin
+
+    def scatter(self, res, extra):
+        return _mlp_grads(res["mlp_W"][0], res["mlp_v"][0], self.dims[2]) if "mlp_W" in res else extra
+
+
 class CoreModuleFn(torch.autograd.Function):
-    """qkv projection -> attention core -> output projection as ONE autograd node for the softmax and local-window baselines
-    (round 4; LaraModuleFn's scheme for cores without landmark parameters): the projections read the fp32 master weights, both
-    weight gradients leave in one launch (ea_wgrad_pair) and their slice partials are added up by one ea_multi_sum.
-    args: x [B, *seq, C], qkv weight / bias, proj weight / bias, core spec (SoftmaxCore / LocalCore: non-differentiable state
-    and the two core calls), compute dtype, heads, then the core's differentiable inputs."""
+    """qkv projection -> attention core -> output projection as ONE autograd node: the launches of LinearFn + the core's Function
+    + LinearFn without two of the three nodes' host cost (ctx objects, saved-tensor packing, engine hand-overs: ~0.1 ms of the
+    host-bound eager step).  Only for the common training case -- 16-bit autocast, fp32 master weights (the
+    *_module_fn_supported predicates); every other case keeps the three nodes.  This is the ONE body of that scheme: EvaModuleFn
+    and LaraModuleFn are its names around the two landmark cores.
+    args: x [B, *seq, C], qkv weight / bias, proj weight / bias, core spec, compute dtype, heads, the core's differentiable inputs.
+    Projections: library GEMMs on 16-bit operands at widths the streaming kernels do not cover (module_proj_lib, round 6: the
+    four parameter casts in one launch, the rounded weights kept for the backward's input-gradient GEMMs), else the prepared
+    16-bit weights of a 192-wide layer (prepare_w192), else the fp32 master weights (linear_w32).  Backward: both weight
+    gradients in one launch where possible (ea_wgrad_pair), else the output projection's before the core's backward and the qkv
+    projection's after it; all terminal sums -- the weight gradients' slice partials, the core's partials -- in ONE ea_multi_sum.
+    A core spec holds the core's non-differentiable state, with
+        fwd(qkv5, inputs) -> out [B,N,h,d], tensors to save;    bwd(dout, qkv5, out, saved) -> d qkv5, gradients of `inputs`
+    (SoftmaxCore, LocalCore, PerformerCore, GraphCore, _kernelized.KernelizedCore) and optionally (EvaCore, LaraCore)
+        setup(B, N, heads, d, elem, inputs, need_grad): before anything is launched -- geometry, derived inputs
+        project(x2, wq, bq32, cdtype, want, need_dx, w192) -> (y, rounded x | None, rounded qkv weight | None), None to decline:
+            the qkv projection by a kernel that also emits the core's pooled q / k rows (direct calls only)
+        defers = True: bwd(dout, qkv5, out, saved, defer, fin_ok) -> d qkv5, gradients, partials, fin.  partials: (key, [S, n]
+            fp32, meta) entries for the terminal sum (when `defer`); fin = (operands, qkv rows | None) leaves the core's last
+            correction of dq / dk to the input-gradient kernel (qkv_dgrad_finish; only when fin_ok)
+        scatter(sums, gradients) -> gradients of `inputs`, after the terminal sum; sums: key -> (summed partial, meta)."""
 
     @staticmethod
     def forward(ctx, x, wq, bq, wp, bp, core, cdtype, heads, *inputs):
-        C = x.shape[-1]
-        B = x.shape[0]
+        B, C = x.shape[0], x.shape[-1]
         N = x.numel() // (B * C)
         d = C // heads
         x2 = x.reshape(-1, C)
         elem = _ELEM[cdtype]
+        need = ctx.needs_input_grad
+        # (only LaraModuleFn is reached while somebody is tracing: its projections and core are dispatcher ops then)
+        direct = _DIRECT and not torch.compiler.is_compiling() and torch._C._len_torch_dispatch_stack() == 0
+        lin = linear_w32_impl if direct else torch.ops.ea.linear_w32
+        if hasattr(core, "setup"):
+            core.setup(B, N, heads, d, elem, inputs, any(need))
         bq32 = None if bq is None else (bq if bq.dtype == torch.float32 else bq.float())
         bp32 = None if bp is None else (bp if bp.dtype == torch.float32 else bp.float())
-        want = x2.dtype == torch.float32 and ctx.needs_input_grad[1]
+        want = x2.dtype == torch.float32 and need[1]
         lib = module_proj_lib(C)
         w16q = w16p = b16p = None
         w192 = prepare_w192(wq, wp, cdtype) if (not lib and w192_usable(wq, wp, cdtype)) else None
         w16pT = None if w192 is None else w192[3]
         if lib:
-            # 320 / 512 / 1024-wide layers (round 6): library GEMMs on 16-bit operands inside the node (see EvaModuleFn)
             w16q, b16q, w16p, b16p = lib_casts(wq, bq, wp, bp, cdtype)
             y, xc = lib_project(x2, wq, bq32, w16q, b16q, cdtype)
             want = True
-        elif w192 is not None:
-            w16q = w192[0]
-            y, xc = project_qkv_wsw(x2, w192[1], w16q, bq32, cdtype, want)
         else:
-            y, xc = linear_w32_impl(x2, wq, bq32, elem, False, False, want)
+            project = getattr(core, "project", None) if direct else None
+            done = None if project is None else project(x2, wq, bq32, cdtype, want, need[0], w192)
+            if done is not None:
+                y, xc, w16q = done
+            elif w192 is not None:
+                w16q = w192[0]
+                y, xc = project_qkv_wsw(x2, w192[1], w16q, bq32, cdtype, want)
+            else:
+                y, xc = lin(x2, wq, bq32, elem, False, False, want)
         xl = x2 if x2.dtype == cdtype else (xc if want else None)
         qkv5 = y.view(B, N, 3, heads, d)
         out, saved = core.fwd(qkv5, inputs)
@@ -2116,7 +1938,7 @@ class CoreModuleFn(torch.autograd.Function):
         elif w192 is not None:
             y2 = ea_linear(o2, w192[2], bp32, cdtype)[0]
         else:
-            y2 = linear_w32_impl(o2, wp, bp32, elem, False, False, False)[0]
+            y2 = lin(o2, wp, bp32, elem, False, False, False)[0]
         ctx.save_for_backward(xl, qkv5, o2, wq, wp, w16q, w16p, w16pT, *saved)
         ctx.core = core
         ctx.meta = (x.shape, x.dtype, cdtype, None if bq is None else bq.dtype, None if bp is None else bp.dtype, wq.dtype, wp.dtype,
@@ -2127,60 +1949,89 @@ class CoreModuleFn(torch.autograd.Function):
     def backward(ctx, dy):
         xl, qkv5, o2, wq, wp, w16q, w16p, w16pT, *saved = ctx.saved_tensors
         xshape, xdtype, cdtype, bqd, bpd, wqd, wpd, heads, in_dtypes = ctx.meta
+        core = ctx.core
         C = xshape[-1]
         d = C // heads
-        elem = _ELEM[cdtype]
         need = ctx.needs_input_grad
+        if need[1] and xl is None:
+            raise RuntimeError("%s: the weight gradient was requested but the forward did not keep its input"
+                               % ctx._forward_cls.__name__)
+        direct = _DIRECT and not torch.compiler.is_compiling() and torch._C._len_torch_dispatch_stack() == 0
         dy2 = dy.reshape(-1, C)
         if dy2.dtype != cdtype:
             dy2 = dy2.to(cdtype)
+        # output projection, input gradient: on the rounded weight (library flavour), the prepared W^T, or the master weight transposed
         if w16p is not None:
             dy2 = dy2 if dy2.is_contiguous() else dy2.contiguous()
             d_o2 = dy2 @ w16p
         elif w16pT is not None and _lin_rows_ok(dy2, cdtype):
             d_o2 = ea_linear(dy2, w16pT, None, cdtype)[0]
         else:
-            d_o2 = linear_w32_impl(dy2, wp, None, elem, True, False, False)[0]
-        B, N = qkv5.shape[:2]
-        dqkv5, extra = ctx.core.bwd(d_o2.view(B, N, heads, d), qkv5, o2.view(B, N, heads, d), saved)
-        dqkv2 = dqkv5.view(-1, 3 * C)
+            lin = linear_w32_impl if direct else torch.ops.ea.linear_w32
+            d_o2 = lin(dy2, wp, None, _ELEM[cdtype], True, False, False)[0]
+        defer = direct and USE_MULTI_SUM                    # the terminal sums wait for ONE ea_multi_sum at the end
         need_bq, need_bp = bqd is not None and need[2], bpd is not None and need[4]
+        qkv2 = qkv5.view(-1, 3 * C)
+        # both weight gradients in ONE launch after the core's backward (ea_wgrad_pair; d qkv has the shape and type of qkv)
+        pair = bool(defer and need[1] and need[3] and wgrad_pair_usable(qkv2, xl, dy2, o2))
         dwq = dbq = dwp = dbp = dx = None
-        pend = []
-        if need[1] and xl is None:
-            raise RuntimeError("CoreModuleFn: the weight gradient was requested but the forward did not keep its input")
-        if need[1] and need[3] and USE_MULTI_SUM and wgrad_pair_usable(dqkv2, xl, dy2, o2):
-            rq, rp = wgrad_pair(dqkv2, xl, need_bq, dy2, o2, need_bp)
-            pend = [("qkv", rq[0], rq[1]), ("proj", rp[0], rp[1])]
+        pend = []                                           # (what, partial tensor, meta)
+        if need[3] and not pair:
+            r_ = wgrad(dy2, o2, need_bp, defer=defer)
+            if defer:
+                pend.append(("proj", r_[0], r_[1]))
+            else:
+                dwp, dbp = r_[0].to(wpd), (r_[1].to(bpd) if need_bp else None)
+        elif need_bp and not pair:
+            dbp = bias_grad(dy2 if dy2.is_contiguous() else dy2.contiguous()).to(bpd)
+        B, N = qkv5.shape[:2]
+        dout, out = d_o2.view(B, N, heads, d), o2.view(B, N, heads, d)
+        if getattr(core, "defers", False):
+            dqkv5, extra, parts, fin = core.bwd(dout, qkv5, out, saved, defer,
+                                                bool(need[0] and dgrad_finish_usable(qkv2, wq, xdtype, heads, d)))
+            pend += parts
         else:
-            if need[3]:
-                r_ = wgrad(dy2, o2, need_bp, defer=USE_MULTI_SUM)
-                if USE_MULTI_SUM:
-                    pend.append(("proj", r_[0], r_[1]))
-                else:
-                    dwp, dbp = r_[0].to(wpd), (r_[1].to(bpd) if need_bp else None)
-            elif need_bp:
-                dbp = bias_grad(dy2 if dy2.is_contiguous() else dy2.contiguous()).to(bpd)
-            if need[1]:
-                r_ = wgrad(dqkv2, xl, need_bq, defer=USE_MULTI_SUM)
-                if USE_MULTI_SUM:
-                    pend.append(("qkv", r_[0], r_[1]))
-                else:
-                    dwq, dbq = r_[0].to(wqd), (r_[1].to(bqd) if need_bq else None)
-            elif need_bq:
-                dbq = bias_grad(dqkv2).to(bqd)
-        if need[0]:
+            (dqkv5, extra), fin = core.bwd(dout, qkv5, out, saved), None
+        dqkv2 = dqkv5.view(-1, 3 * C)
+        if fin is not None:
+            # corrects the dq / dk columns of dqkv2 in place: BEFORE the weight gradient reads them
+            dx = qkv_dgrad_finish(dqkv2, fin[1], wq, w16q, xdtype, fin[0]).view(xshape)
+        if pair:
+            rq, rp = wgrad_pair(dqkv2, xl, need_bq, dy2, o2, need_bp)
+            pend += [("qkv", rq[0], rq[1]), ("proj", rp[0], rp[1])]
+        elif need[1]:
+            r_ = wgrad(dqkv2, xl, need_bq, defer=defer)
+            if defer:
+                pend.append(("qkv", r_[0], r_[1]))
+            else:
+                dwq, dbq = r_[0].to(wqd), (r_[1].to(bqd) if need_bq else None)
+        elif need_bq:
+            # frozen qkv weight, trainable bias (bias-only fine-tuning): a column sum of d qkv, no input rows needed
+            dbq = bias_grad(dqkv2).to(bqd)
+        if need[0] and dx is None:
             dx = qkv_dgrad(dqkv2, wq, w16q, xdtype).view(xshape)
+        res = {}
         if pend:
             sums = multi_sum([t for _, t, _ in pend])
-            for (what, _, meta), o in zip(pend, sums):
-                dw_, db_ = _wgrad_split(o, meta)
-                if what == "proj":
-                    dwp, dbp = dw_.to(wpd), (db_.to(bpd) if need_bp else None)
-                else:
-                    dwq, dbq = dw_.to(wqd), (db_.to(bqd) if need_bq else None)
+            res = {what: (o, meta) for (what, _, meta), o in zip(pend, sums)}
+            if "proj" in res:
+                dwp, dbp = _wgrad_split(*res["proj"])
+                dwp, dbp = dwp.to(wpd), (dbp.to(bpd) if need_bp else None)
+            if "qkv" in res:
+                dwq, dbq = _wgrad_split(*res["qkv"])
+                dwq, dbq = dwq.to(wqd), (dbq.to(bqd) if need_bq else None)
+        if hasattr(core, "scatter"):
+            extra = core.scatter(res, extra)
         egrads = tuple(None if (g is None or dt is None) else g.to(dt) for g, dt in zip(extra, in_dtypes))
         return (dx, dwq, dbq, dwp, dbp, None, None, None) + egrads
+
+
+class EvaModuleFn(CoreModuleFn):
+    """CoreModuleFn around an EvaCore, under the name EVA's single node has in graphs, tests and messages."""
+
+
+class LaraModuleFn(CoreModuleFn):
+    """CoreModuleFn around a LaraCore, under the name LinearRA's single node has in graphs, tests and messages."""
 
 
 USE_WIDE_MODULE_FN = os.environ.get("EA_WIDE_MODULE_FN", "1") == "1"
@@ -2226,16 +2077,16 @@ def lib_casts(wq, bq, wp, bp, cdtype):
 
 
 def core_module_fn_supported(x, qkv, proj, cdtype):
-    """The single-node path of the softmax / local-window baselines (CoreModuleFn): what LaraModuleFn asks of the projections,
-    direct calls only."""
+    """The single-node path of the softmax / local-window baselines (CoreModuleFn): what the module node asks of the projections
+    (lara_module_fn_supported), direct calls only."""
     return (USE_CORE_MODULE_FN and _DIRECT and not torch.compiler.is_compiling() and torch._C._len_torch_dispatch_stack() == 0
             and lara_module_fn_supported(x, qkv, proj, cdtype, allow_lib=True))
 
 
 def lara_module_fn_supported(x, qkv, proj, cdtype, allow_lib=False):
-    """The single-node path of LinearRA (LaraModuleFn): 16-bit autocast dtype, fp32 master weights both projection kernels
-    cover (forward of both layers, the output projection's transposed input gradient), the one-pass weight gradient.
-    allow_lib (EvaModuleFn, CoreModuleFn; round 6): widths outside the streaming kernels' 64 .. 256 channels qualify too --
+    """What the module node (CoreModuleFn; here for LinearRA's LaraModuleFn) needs: 16-bit autocast dtype, fp32 master weights
+    both projection kernels cover (forward of both layers, the output projection's transposed input gradient), the one-pass
+    weight gradient.  allow_lib (every core but LARA; round 6): widths outside the streaming kernels' 64 .. 256 channels qualify too --
     their projections run as library GEMMs inside the node (module_proj_lib)."""
     if not (USE_LARA_MODULE_FN and x.is_cuda and cdtype in _ELEM and x.dtype in (torch.float32, cdtype)):
         return False
@@ -2329,9 +2180,7 @@ class LaraLandmarkFn(torch.autograd.Function):
                     nv.ptr(dW), nv.ptr(dvec), nv.ptr(d_cb), nv.ptr(ctx.lmk_saved), nv.stream())
         pgrads = []
         if geom.has_mlp:
-            dWs, dvs = colsum2_f32(dW.view(BH, -1), dvec.view(BH, -1))
-            dWs, dvs = dWs.view(2, d, d), dvs.view(2, 3, d)
-            raw = [dWs[0], dvs[0, 0], dvs[0, 1], dvs[0, 2], dWs[1], dvs[1, 0], dvs[1, 1], dvs[1, 2]]
+            raw = _mlp_grads(*colsum2_f32(dW.view(BH, -1), dvec.view(BH, -1)), d)
             pgrads = [g.to(dt) for g, dt in zip(raw, ctx.pdtypes)]
         return (dpq, dpk, None, d_cb, None) + tuple(pgrads)
 
@@ -3082,7 +2931,7 @@ def wgrad_supported(dy2, x2):
 # 51 us / 31 us for the two cfg3 projections against 94 / 48 us for the library split-K GEMM + its reduction + the
 # bias-gradient pass.  EA_WGRAD=0 switches back to the library path.
 USE_WGRAD = os.environ.get("EA_WGRAD", "1") == "1"
-# LinearRA as one autograd node (LaraModuleFn); EA_LARA_MODULE_FN=0 keeps the three nodes
+# LinearRA as one autograd node (LaraModuleFn: CoreModuleFn around a LaraCore); EA_LARA_MODULE_FN=0 keeps the three nodes
 USE_LARA_MODULE_FN = os.environ.get("EA_LARA_MODULE_FN", "1") == "1"
 
 

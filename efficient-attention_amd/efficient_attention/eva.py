@@ -197,8 +197,8 @@ class EVA(LocalAttention):
                     noise = torch.randn_like(torch.empty(B, h, L0, d, device=x.device, dtype=torch.float32))
                 mask = _ops._mask_u8(key_padding_mask, B, N, x.device)
                 cfg = (self.attn_2d, tuple(seq_shape), w, e, r0, L0, self.adaptive_proj) + ((tb,) if tb is not None else ())
-                y = _ops.EvaModuleFn.apply(x, self.qkv.weight, self.qkv.bias, self.proj.weight, self.proj.bias, bias, mask, noise,
-                                           cfg, cdt, h, *self._mu_params())
+                y = _ops.EvaModuleFn.apply(x, self.qkv.weight, self.qkv.bias, self.proj.weight, self.proj.bias,
+                                           _ops.EvaCore(mask, noise, cfg), cdt, h, bias, *self._mu_params())
                 y = self.proj_drop(y)
                 if not self.attn_2d:
                     y = y[..., :orig_n, :]

@@ -229,6 +229,16 @@ class LinearRA(_ops.DerivedCacheOwner, MultiheadAttention):
         q, k = self.q_bar_gen, self.k_bar_gen
         return [q[2].weight, q[2].bias, q[3].weight, q[3].bias, k[2].weight, k[2].bias, k[3].weight, k[3].bias]
 
+    def _draw_noise(self, B, nl, device):
+        """The landmark noise of a training step, [B, h, nl, d] fp32 (2 nl rows with multisample): the one sampling call of
+        the step; None in evaluation."""
+        if not self.training:
+            return None
+        h, d = self.num_heads, self.head_dim
+        if self.use_multisample:
+            return torch.randn(B, h, nl * 2, d, dtype=torch.float32, device=device)
+        return torch.randn_like(torch.empty(B, h, nl, d, dtype=torch.float32, device=device))
+
     def forward(self, x, key_padding_mask=None):
         B, *seq_shape, C = x.shape
         N = int(math.prod(seq_shape))
@@ -295,22 +305,15 @@ class LinearRA(_ops.DerivedCacheOwner, MultiheadAttention):
                    and seq_shape[0] % side == 0 and seq_shape[1] % side == 0
                    and seq_shape[0] // side == seq_shape[1] // side)
 
-        def draw_noise(nl):
-            if not self.training:
-                return None
-            if self.use_multisample:
-                return torch.randn(B, h, nl * 2, d, dtype=torch.float32, device=x.device)
-            return torch.randn_like(torch.empty(B, h, nl, d, dtype=torch.float32, device=x.device))
-
         if fused_a:
             # pooling + landmark pipeline + estimator as one autograd node (_ops.LaraPooledFn)
             params = self._mlp_params() if gen.startswith('pool') else ()
-            noise = draw_noise(n_lm)
+            noise = self._draw_noise(B, n_lm, x.device)
             cfg = (seq_shape[0], seq_shape[1], seq_shape[0] // side, bool(params), gen.endswith('mixed'),
                    _ops.MIS[self.mis_type], mode if noise is not None else 0, float(self.alpha_coeff), float(self.scale))
             if module_fn:
-                y = _ops.LaraModuleFn.apply(x, self.qkv.weight, self.qkv.bias, self.proj.weight, self.proj.bias, mask, noise, cfg,
-                                            torch.get_autocast_dtype("cuda"), h, *params)
+                y = _ops.LaraModuleFn.apply(x, self.qkv.weight, self.qkv.bias, self.proj.weight, self.proj.bias,
+                                            _ops.LaraCore(mask, noise, cfg), torch.get_autocast_dtype("cuda"), h, *params)
                 return self.proj_drop(y)
             out = _ops.LaraPooledFn.apply(qkv5, mask, noise, cfg, *params)
             return self.merge_and_project(out, B, seq_shape, C, x.dtype)
@@ -338,7 +341,7 @@ class LinearRA(_ops.DerivedCacheOwner, MultiheadAttention):
             pq, pk, qkv5 = self._proposal_gen_1d(qkv5, key_padding_mask)
         else:
             raise ValueError("LinearRA expects x of rank 3 or 4")
-        noise = draw_noise(pq.shape[-2])
+        noise = self._draw_noise(B, pq.shape[-2], x.device)
         if fused_b:
             omega, qrows, bhv, lp = _ops.lara_landmarks(pq, pk, noise, self.mis_type, mode, self.scale, None,
                                                         bool(mixed_k), colbias if mixed_k else None)
@@ -354,12 +357,7 @@ class LinearRA(_ops.DerivedCacheOwner, MultiheadAttention):
         _ops.GraphCore): the same kernels in the same order as the three-node path below it in forward()."""
         h, d, L = self.num_heads, self.head_dim, self.num_landmarks
         mask = _ops._mask_u8(key_padding_mask, B, N, x.device)
-        noise = None
-        if self.training:                                # (the one sampling call of the step, shapes as in forward())
-            if self.use_multisample:
-                noise = torch.randn(B, h, L * 2, d, dtype=torch.float32, device=x.device)
-            else:
-                noise = torch.randn_like(torch.empty(B, h, L, d, dtype=torch.float32, device=x.device))
+        noise = self._draw_noise(B, L, x.device)
         mis, kappa, scale, mis_type = _ops.MIS[self.mis_type], float(self.alpha_coeff), self.scale, self.mis_type
 
         def core(qkv5, lqw, lqb, lkw, lkb, nqw, nqb, nkw, nkb):
