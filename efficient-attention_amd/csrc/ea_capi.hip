@@ -79,7 +79,7 @@ static Geo mk_geo(const ea_geom* g) {
 extern "C" {
 
 const char* ea_version(void) { return "ea_hip 0.1.0 gfx950"; }
-int32_t ea_abi_version(void) { return 22; }
+int32_t ea_abi_version(void) { return 23; }
 
 int32_t ea_window_bias_ld(const ea_geom* g) {
   WinTiling t;
@@ -2175,21 +2175,23 @@ static ea::DecT dec_mk(const ea_t4* t) {
 // Static (ea_ceva_sdec_geom, dev): the count is *pos, so the host can check only that a step fits an empty cache (t0 = 0; the
 // kernels check t0 + T <= cap), no chunk range is given, the pad flags are always read, and ring is 0 (cap rows, linear) or
 // the rows of a rolling state -- a multiple of window that holds one step's span.  ntok: null, or the per-sequence state's
-// [B] token counts of the step (pos and status are [B] then).
+// [B] token counts of the step (pos and status are [B] then).  l16 (ea_ceva_sdecode_*_l16, a compact state): the landmark
+// rows have the geometry's dtype, which is then a 16-bit one.
 struct DecG {
   int B, H, D, dtype, window, ext, chunk, t0, T_new, c_first, c_last, cap, adaptive, has_bias, has_mask, ring;
   const int32_t* pos;
   int32_t* status;
   bool dev;
   int32_t* ntok;
+  bool l16;
 };
 static DecG dec_read(const ea_ceva_dec_geom* g) {
   return {g->B, g->H, g->D, g->dtype, g->window, g->ext, g->chunk, g->t0, g->T_new, g->c_first, g->c_last, g->cap,
-          g->adaptive, g->has_bias, g->has_mask, 0, nullptr, nullptr, false, nullptr};
+          g->adaptive, g->has_bias, g->has_mask, 0, nullptr, nullptr, false, nullptr, false};
 }
-static DecG dec_read(const ea_ceva_sdec_geom* g) {
+static DecG dec_read(const ea_ceva_sdec_geom* g, bool l16 = false) {
   return {g->B, g->H, g->D, g->dtype, g->window, g->ext, g->chunk, 0, g->T_new, 0, -1, g->cap,
-          g->adaptive, g->has_bias, 1, g->ring, g->pos, g->status, true, g->ntok};
+          g->adaptive, g->has_bias, 1, g->ring, g->pos, g->status, true, g->ntok, l16};
 }
 // What every launch of a step needs; with `windows`, also what close and attn need of the window geometry (append moves
 // rows and reads none of it).  Every EA_E_BADARG is decided before the head dim, the static state's own before the rest.
@@ -2203,7 +2205,7 @@ static int dec_check(const DecG& g, const uint8_t* pad, bool windows, bool reads
   if (g.ring != 0 && !(g.ring > 0 && g.window > 0 && g.ring % g.window == 0 && g.ext >= 0 && g.T_new > 0 &&
                        (int64_t)g.ring >= (int64_t)g.window + g.ext + g.T_new)) return EA_E_BADARG;
   if (g.B <= 0 || g.H <= 0 || g.t0 < 0 || g.T_new <= 0 || g.cap < g.t0 + g.T_new ||
-      (g.dtype != EA_BF16 && g.dtype != EA_F16 && g.dtype != EA_F32)) return EA_E_BADARG;
+      (g.dtype != EA_BF16 && g.dtype != EA_F16 && (g.l16 || g.dtype != EA_F32))) return EA_E_BADARG;
   if (g.D != 32 && g.D != 64 && g.D != 128) return EA_E_UNSUPPORTED;
   return EA_OK;
 }
@@ -2213,7 +2215,8 @@ static int dec_fill(const DecG& g, const ea_t4* q, const ea_t4* k, const ea_t4* 
   if (rc != EA_OK) return rc;
   const int esz = g.dtype == EA_F32 ? 4 : 2;
   if (!dec_t4_ok(q, g.D, esz) || !dec_t4_ok(k, g.D, esz) || !dec_t4_ok(v, g.D, esz)) return EA_E_BADARG;
-  if (!dec_t4_ok(lk, g.D, 4) || !dec_t4_ok(lv, g.D, 4) || (g.has_mask && !pad)) return EA_E_BADARG;
+  const int lsz = g.l16 ? esz : 4;                        // (l16: 16-byte aligned rows of 8-element multiples)
+  if (!dec_t4_ok(lk, g.D, lsz) || !dec_t4_ok(lv, g.D, lsz) || (g.has_mask && !pad)) return EA_E_BADARG;
   p.q = dec_mk(q); p.k = dec_mk(k); p.v = dec_mk(v); p.lk = dec_mk(lk); p.lv = dec_mk(lv);
   p.pad = g.has_mask ? pad : nullptr;
   p.B = g.B; p.H = g.H; p.D = g.D; p.dtype = g.dtype; p.w = g.window; p.e = g.ext; p.r = g.chunk;
@@ -2235,7 +2238,7 @@ static int dec_close(const DecG& g, const ea_t4* q, const ea_t4* k, const ea_t4*
     if (!mu_params[i] || (uintptr_t)mu_params[i] % 16) return EA_E_BADARG;
     p.mu[i] = mu_params[i];
   }
-  return ea::ceva_decode_launch(ea::DEC_CLOSE, p, (hipStream_t)stream);
+  return ea::ceva_decode_launch(ea::DEC_CLOSE, p, (hipStream_t)stream, g.l16);
 }
 // dec_fill, and what attn and attn_split add to it: the output rows and the bias
 static int dec_fill_attn(const DecG& g, const ea_t4* q, const ea_t4* k, const ea_t4* v, const uint8_t* pad, const float* bias,
@@ -2251,13 +2254,21 @@ static int dec_attn(const DecG& g, const ea_t4* q, const ea_t4* k, const ea_t4* 
                     const ea_t4* lk, const ea_t4* lv, const ea_t4* out, void* stream) {
   ea::DecP p = {};
   const int rc = dec_fill_attn(g, q, k, v, pad, bias, lk, lv, out, p);
-  return rc != EA_OK ? rc : ea::ceva_decode_launch(ea::DEC_ATTN, p, (hipStream_t)stream);
+  return rc != EA_OK ? rc : ea::ceva_decode_launch(ea::DEC_ATTN, p, (hipStream_t)stream, g.l16);
 }
 // What the two launches of a split step add to a static step: 2 .. 64 parts, a 16-byte aligned workspace of fp32 partials
 // [B, H, 8, parts, D + 4], and a step of at most 8 tokens (one query group per window block).  Decided first, like every
 // EA_E_BADARG of the static state.
 static int split_check(const ea_ceva_sdec_geom* g, int parts, const void* ws) {
   return g && g->pos && parts >= 2 && parts <= 64 && ws && (uintptr_t)ws % 16 == 0 && g->T_new <= 8 ? EA_OK : EA_E_BADARG;
+}
+static int dec_attn_split(const ea_ceva_sdec_geom* g, bool l16, const ea_t4* q, const ea_t4* k, const ea_t4* v,
+                          const uint8_t* pad, const float* bias, const ea_t4* lk, const ea_t4* lv, const ea_t4* out, int parts,
+                          float* ws, void* stream) {
+  if (split_check(g, parts, ws) != EA_OK) return EA_E_BADARG;
+  ea::DecP p = {};
+  const int rc = dec_fill_attn(dec_read(g, l16), q, k, v, pad, bias, lk, lv, out, p);
+  return rc != EA_OK ? rc : ea::ceva_sdecode_attn_split(p, parts, ws, (hipStream_t)stream, l16);
 }
 
 extern "C" {
@@ -2298,10 +2309,24 @@ int ea_ceva_sdecode_attn(const ea_ceva_sdec_geom* g, const ea_t4* q, const ea_t4
 int ea_ceva_sdecode_attn_split(const ea_ceva_sdec_geom* g, const ea_t4* q, const ea_t4* k, const ea_t4* v, const uint8_t* pad,
                                const float* bias, const ea_t4* rf_k_bar, const ea_t4* beta, const ea_t4* out, int32_t parts,
                                float* ws, void* stream) {
-  if (split_check(g, parts, ws) != EA_OK) return EA_E_BADARG;
-  ea::DecP p = {};
-  const int rc = dec_fill_attn(dec_read(g), q, k, v, pad, bias, rf_k_bar, beta, out, p);
-  return rc != EA_OK ? rc : ea::ceva_sdecode_attn_split(p, parts, ws, (hipStream_t)stream);
+  return dec_attn_split(g, false, q, k, v, pad, bias, rf_k_bar, beta, out, parts, ws, stream);
+}
+
+// a compact state's close, attn and attn_split: rf_k_bar and beta are rows of g->dtype (bf16 or fp16)
+int ea_ceva_sdecode_close_l16(const ea_ceva_sdec_geom* g, const ea_t4* q, const ea_t4* k, const ea_t4* v, const uint8_t* pad,
+                              const float* const* mu_params, const ea_t4* rf_k_bar, const ea_t4* beta, void* stream) {
+  return g ? dec_close(dec_read(g, true), q, k, v, pad, mu_params, rf_k_bar, beta, stream) : EA_E_BADARG;
+}
+
+int ea_ceva_sdecode_attn_l16(const ea_ceva_sdec_geom* g, const ea_t4* q, const ea_t4* k, const ea_t4* v, const uint8_t* pad,
+                             const float* bias, const ea_t4* rf_k_bar, const ea_t4* beta, const ea_t4* out, void* stream) {
+  return g ? dec_attn(dec_read(g, true), q, k, v, pad, bias, rf_k_bar, beta, out, stream) : EA_E_BADARG;
+}
+
+int ea_ceva_sdecode_attn_split_l16(const ea_ceva_sdec_geom* g, const ea_t4* q, const ea_t4* k, const ea_t4* v,
+                                   const uint8_t* pad, const float* bias, const ea_t4* rf_k_bar, const ea_t4* beta,
+                                   const ea_t4* out, int32_t parts, float* ws, void* stream) {
+  return dec_attn_split(g, true, q, k, v, pad, bias, rf_k_bar, beta, out, parts, ws, stream);
 }
 
 int ea_ceva_sdecode_merge(const ea_ceva_sdec_geom* g, const ea_t4* out, int32_t parts, const float* ws, void* stream) {

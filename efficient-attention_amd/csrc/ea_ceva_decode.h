@@ -12,7 +12,7 @@ struct DecT {                 // [B,H,N,D] view of any I/O type, element strides
 
 struct DecP {
   DecT q, k, v;               // the cache rows [B,H,cap,D] (dtype); [B,H,ring,D] when ring != 0
-  DecT lk, lv;                // rf_k_bar, beta [B,H,Lcap,D] fp32: read by attn, written by close
+  DecT lk, lv;                // rf_k_bar, beta [B,H,Lcap,D] fp32 (the l16 launches: dtype): read by attn, written by close
   DecT o;                     // attn: out [B,H,T_new,D] (dtype), row t - t0
   const uint8_t* pad;         // [B,cap] ([B,ring]) 1 = padded position, or null
   const float* bias;          // [w, w + e] dense single-head bias (natural-log domain), or null
@@ -54,11 +54,12 @@ struct DecMergeP {               // merge: out row t = the parts of step token t
 
 enum DecKind { DEC_CLOSE, DEC_ATTN };
 // the step's close or attn launch; p.pos != null: t0 = *p.pos (needs p.pad); p.ring != 0: ring rows (needs p.pos);
-// p.ntok != null: t0 = p.pos[b], p.ntok[b] tokens (needs p.pos)
-int ceva_decode_launch(DecKind kind, const DecP& p, hipStream_t st);
+// p.ntok != null: t0 = p.pos[b], p.ntok[b] tokens (needs p.pos).  l16 (a compact state; needs p.pos and a 16-bit p.dtype):
+// p.lk, p.lv are rows of p.dtype, strides in those elements -- close rounds its two stores, attn reads 16-bit landmark rows
+int ceva_decode_launch(DecKind kind, const DecP& p, hipStream_t st, bool l16 = false);
 // attn as two launches for a DEV step of T <= 8 tokens (ea_ceva_decode_split.h): `parts` workgroups per window block write
 // partials to ws, then one workgroup per token combines them; p as for DEC_ATTN, 2 <= parts <= 64
-int ceva_sdecode_attn_split(const DecP& p, int parts, float* ws, hipStream_t st);
+int ceva_sdecode_attn_split(const DecP& p, int parts, float* ws, hipStream_t st, bool l16 = false);
 int ceva_sdecode_merge(const DecMergeP& p, int D, int dtype, int BH, hipStream_t st);
 int ceva_sdecode_append(const AppP& p, hipStream_t st);
 // *pos += T; ntok != null: pos[b] += ntok[b] for the B elements

@@ -63,6 +63,7 @@ template <> struct Io<float> {
   static EA_DEV f32x4 ld4(const char* p) { return *reinterpret_cast<const f32x4*>(p); }
   static EA_DEV float ld1(const char* p) { return *reinterpret_cast<const float*>(p); }
   static EA_DEV void st4(char* p, f32x4 v) { *reinterpret_cast<f32x4*>(p) = v; }
+  static EA_DEV void st1(char* p, float v) { *reinterpret_cast<float*>(p) = v; }
   static constexpr int SZ = 4;
 };
 template <typename H> struct Io16 {
@@ -81,6 +82,7 @@ template <typename H> struct Io16 {
   }
   static EA_DEV float ld1(const char* p) { return H::to_f(*reinterpret_cast<const uint16_t*>(p)); }
   static EA_DEV void st4(char* p, f32x4 v) { *reinterpret_cast<u32x2*>(p) = u32x2{pack2<H>(v[0], v[1]), pack2<H>(v[2], v[3])}; }
+  static EA_DEV void st1(char* p, float v) { *reinterpret_cast<uint16_t*>(p) = H::from_f(v); }   // to nearest even
   static constexpr int SZ = 2;
 };
 template <> struct Io<BF16> : Io16<BF16> {};
@@ -88,6 +90,12 @@ template <> struct Io<F16> : Io16<F16> {};
 
 template <typename E> EA_DEV const char* row(const DecT& t, int b, int h, int n) {
   return t.p + ((size_t)b * t.sb + (size_t)h * t.sh + (size_t)n * t.sn) * Io<E>::SZ;
+}
+
+// element o of landmark row c (rf_k_bar, beta) = v: close's two stores.  L = float: the value as it is; a 16-bit L (a compact
+// state): rounded once, to nearest even
+template <typename L> EA_DEV void store_lmk(const DecT& t, int b, int h, int c, int o, float v) {
+  Io<L>::st1(const_cast<char*>(row<L>(t, b, h, c)) + (size_t)o * Io<L>::SZ, v);
 }
 
 // Token index -> row of q / k / v / pad.  RING = false: the identity, every member folds away.  RING = true: slot
@@ -224,8 +232,8 @@ EA_DEV void stage_queries(const DecP& p, int b, int h, const Group& g, float (*q
 }
 
 // tiles first, first + stride, .. of [local tiles, landmark tiles]: online softmax into (m, l, acc), then l and acc summed
-// over the lanes that hold a share of them
-template <typename E, int D, bool RING, bool OPT>
+// over the lanes that hold a share of them.  L: the element type of the landmark rows -- float, or E on a compact state
+template <typename E, int D, bool RING, bool OPT, typename L>
 EA_DEV void stream_tiles(const DecP& p, int b, int h, const Group& g, int first, int stride, const float (*qs)[D],
                          float (*ps)[QPW], int lane, float* m, float* l, f32x4* acc) {
   static_assert(QPW == 8, "pv_rows reads the probabilities of a row as two float4");
@@ -262,7 +270,7 @@ EA_DEV void stream_tiles(const DecP& p, int b, int h, const Group& g, int first,
         else x[i] = sc[i] * p.scale + (p.bias ? p.bias[(size_t)(tq - bk * p.w) * Wk + col] : 0.f);
       }
     } else {
-      if (col < lmax) dot_rows<float, D>(row<float>(p.lk, b, h, col), qs, sc);
+      if (col < lmax) dot_rows<L, D>(row<L>(p.lk, b, h, col), qs, sc);
 #pragma unroll
       for (int i = 0; i < QPW; ++i) x[i] = (i < nql && col < (qa + i) / p.r) ? sc[i] * p.scale : -INFINITY;
     }
@@ -282,7 +290,7 @@ EA_DEV void stream_tiles(const DecP& p, int b, int h, const Group& g, int first,
       const int j0 = max(0, -(kbase + tile * KT)), j1 = min(KT, min(Wk - tile * KT, tend - (kbase + tile * KT)));
       if (j1 > j0) pv_rows<E, D>(rows, p.v, b, h, rows.wrap(ks0 + tile * KT + j0), j1 - j0, kg, dc, &ps[j0], acc);
     } else {
-      pv_rows<float, D>(Rows<false>{}, p.lv, b, h, (tile - nlt) * KT, min(KT, lmax - (tile - nlt) * KT), kg, dc, ps, acc);
+      pv_rows<L, D>(Rows<false>{}, p.lv, b, h, (tile - nlt) * KT, min(KT, lmax - (tile - nlt) * KT), kg, dc, ps, acc);
     }
     __builtin_amdgcn_wave_barrier();
   }
@@ -374,7 +382,27 @@ EA_DEV int first_flag(const uint8_t* f, int T, int* red) {
 
 // ---- a short step with its landmark range split over workgroups (ea_ceva_decode_split.h) -------------------------------
 #define CEVA_SPLIT_TEXT
+#define CEVA_KERNEL(name) name##_kernel
 #include "ea_ceva_decode_split.h"
+#undef CEVA_KERNEL
+
+// ---- the same kernels over 16-bit landmark rows (a compact state: rf_k_bar and beta have the cache's dtype) -------------
+// CEVA_L16 makes the landmark element type E instead of float, and nothing else: close rounds its two stores, attn and
+// attn_split read landmark rows as they read key and value rows.  Kernels of their own (ceva_*_l16_kernel), DEV steps of a
+// 16-bit E only; the texts leave out what has no landmark row in it (append, merge).
+#define CEVA_L16
+#define CEVA_SEQ false
+#define CEVA_KERNEL(name) name##_l16_kernel
+#include "ea_ceva_decode_step.h"
+#include "ea_ceva_decode_split.h"
+#undef CEVA_SEQ
+#undef CEVA_KERNEL
+#define CEVA_SEQ true
+#define CEVA_KERNEL(name) name##_seq_l16_kernel
+#include "ea_ceva_decode_step.h"
+#undef CEVA_SEQ
+#undef CEVA_KERNEL
+#undef CEVA_L16
 #undef CEVA_SPLIT_TEXT
 
 // *pos += T, in a launch of its own after attn on the same stream: stream order puts it behind every read of *pos in the
@@ -415,6 +443,27 @@ SplitKernel split_of(bool ring, bool seq) {
   return ring ? ceva_attn_split_kernel<E, D, true, false> : ceva_attn_split_kernel<E, D, false, false>;
 }
 
+// the kernels of a compact state: 16-bit E, DEV steps (null for fp32 rows: the caller has refused them)
+template <typename E, int D>
+DecKernel l16_kernel_of(DecKind kind, bool ring, bool seq) {
+  if constexpr (Io<E>::SZ == 2) {
+    if (seq && kind == DEC_CLOSE) return ring ? ceva_close_seq_l16_kernel<E, D, true, true> : ceva_close_seq_l16_kernel<E, D, true, false>;
+    if (seq) return ring ? ceva_attn_seq_l16_kernel<E, D, true, true> : ceva_attn_seq_l16_kernel<E, D, true, false>;
+    if (kind == DEC_CLOSE) return ring ? ceva_close_l16_kernel<E, D, true, true> : ceva_close_l16_kernel<E, D, true, false>;
+    return ring ? ceva_attn_l16_kernel<E, D, true, true> : ceva_attn_l16_kernel<E, D, true, false>;
+  }
+  return nullptr;
+}
+
+template <typename E, int D>
+SplitKernel l16_split_of(bool ring, bool seq) {
+  if constexpr (Io<E>::SZ == 2) {
+    if (seq) return ring ? ceva_attn_split_l16_kernel<E, D, true, true> : ceva_attn_split_l16_kernel<E, D, false, true>;
+    return ring ? ceva_attn_split_l16_kernel<E, D, true, false> : ceva_attn_split_l16_kernel<E, D, false, false>;
+  }
+  return nullptr;
+}
+
 template <typename E, int D>
 MergeKernel merge_of(bool seq) { return seq ? ceva_merge_kernel<E, D, true> : ceva_merge_kernel<E, D, false>; }
 
@@ -441,13 +490,17 @@ bool with_types(int dtype, int D, F&& pick) {
 }  // namespace
 
 // DEV / RING / SEQ follow the state: p.pos != null / p.ring != 0 / p.ntok != null.  (The C entry points have checked the
-// ring: a multiple of w that holds the span of one step, ea_capi.hip.)
-int ceva_decode_launch(DecKind kind, const DecP& p, hipStream_t st) {
+// ring: a multiple of w that holds the span of one step, ea_capi.hip.)  l16: p.lk, p.lv are rows of p.dtype, a 16-bit type.
+int ceva_decode_launch(DecKind kind, const DecP& p, hipStream_t st, bool l16) {
   const bool dev = p.pos != nullptr, ring = p.ring != 0, seq = p.ntok != nullptr;
   if (dev ? !p.pad : (ring || seq)) return EA_E_BADARG;   // a DEV step always reads the pad flags; ring, ntok belong to a DEV step
+  if (l16 && (!dev || p.dtype == EA_F32)) return EA_E_BADARG;   // compact landmark rows belong to a 16-bit DEV step
   if (p.D != 32 && p.D != 64 && p.D != 128) return EA_E_UNSUPPORTED;
   DecKernel kernel;
-  if (!with_types(p.dtype, p.D, [&](auto e, auto d) { kernel = kernel_of<decltype(e), decltype(d)::value>(kind, dev, ring, seq); }))
+  if (!with_types(p.dtype, p.D, [&](auto e, auto d) {
+        kernel = l16 ? l16_kernel_of<decltype(e), decltype(d)::value>(kind, ring, seq)
+                     : kernel_of<decltype(e), decltype(d)::value>(kind, dev, ring, seq);
+      }))
     return EA_E_BADARG;
   // x: the chunks the step closes / the window blocks it touches; DEV: the most T tokens can, wherever they start
   const int nx = kind == DEC_CLOSE ? (dev ? (p.T + p.r - 1) / p.r : p.c_last - p.c_first + 1)
@@ -457,12 +510,14 @@ int ceva_decode_launch(DecKind kind, const DecP& p, hipStream_t st) {
 }
 
 // (The C entry points have checked parts, the workspace and T <= QPW.)
-int ceva_sdecode_attn_split(const DecP& p, int parts, float* ws, hipStream_t st) {
+int ceva_sdecode_attn_split(const DecP& p, int parts, float* ws, hipStream_t st, bool l16) {
   const bool ring = p.ring != 0, seq = p.ntok != nullptr;
-  if (!p.pos || !p.pad || !ws || parts < 2 || parts > 64 || p.T > QPW) return EA_E_BADARG;
+  if (!p.pos || !p.pad || !ws || parts < 2 || parts > 64 || p.T > QPW || (l16 && p.dtype == EA_F32)) return EA_E_BADARG;
   if (p.D != 32 && p.D != 64 && p.D != 128) return EA_E_UNSUPPORTED;
   SplitKernel kernel;
-  if (!with_types(p.dtype, p.D, [&](auto e, auto d) { kernel = split_of<decltype(e), decltype(d)::value>(ring, seq); }))
+  if (!with_types(p.dtype, p.D, [&](auto e, auto d) {
+        kernel = l16 ? l16_split_of<decltype(e), decltype(d)::value>(ring, seq) : split_of<decltype(e), decltype(d)::value>(ring, seq);
+      }))
     return EA_E_BADARG;
   const int nx = (p.T + p.w - 2) / p.w + 1;        // the most window blocks T tokens can touch
   const DecSplitP sp = {p, ws, parts};

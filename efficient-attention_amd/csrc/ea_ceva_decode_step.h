@@ -7,8 +7,15 @@
 // per-sequence switch existed: tools/isa_diff.py shows their code unchanged.  (Wrapping one body template in two kernels
 // compiles too, but the inlined body schedules differently from the kernel written out.)  What attn does to a query group
 // it shares with attn_split (ea_ceva_decode_split.h) and takes from the helpers of ea_ceva_decode.hip.
+// With CEVA_L16 (and CEVA_KERNEL(x) = x_l16_kernel / x_seq_l16_kernel) the text gives the attn and close of a compact state:
+// the landmark rows are of type E, not float (`Lmk` below), and that is the only difference.  append has no landmark row.
 #if !defined(CEVA_SEQ) || !defined(CEVA_KERNEL)
 #error "included by ea_ceva_decode.hip only"
+#endif
+#ifdef CEVA_L16
+#define CEVA_LMK(E) E
+#else
+#define CEVA_LMK(E) float
 #endif
 
 // One workgroup per window block of the step.  DEV: the grid holds the most window blocks T tokens can touch, and a block
@@ -47,7 +54,7 @@ __global__ __launch_bounds__(NT) void CEVA_KERNEL(ceva_attn)(const DecP p) {
     stage_queries<E, D>(p, b, h, gr, qs[wave], lane);
     float m[QPW], l[QPW];
     f32x4 acc[QPW];
-    stream_tiles<E, D, RING, true>(p, b, h, gr, wave % nsplit, nsplit, qs[wave], ps[wave], lane, m, l, acc);
+    stream_tiles<E, D, RING, true, CEVA_LMK(E)>(p, b, h, gr, wave % nsplit, nsplit, qs[wave], ps[wave], lane, m, l, acc);
     if (nsplit == 1) {
       if (lane < G) {
 #pragma unroll
@@ -136,7 +143,7 @@ __global__ __launch_bounds__(NT) void CEVA_KERNEL(ceva_close)(const DecP p) {
   if (tid >= D && tid < 2 * D) {                   // k side: rf_k_bar = rk
     const int o = tid - D;
     xm[1][o] = z;
-    const_cast<float*>(reinterpret_cast<const float*>(row<float>(p.lk, b, h, c)))[o] = z;
+    store_lmk<CEVA_LMK(E)>(p.lk, b, h, c, o, z);
   }
   __syncthreads();
   if (tid < D) mu[tid] = z + xm[1][tid];           // mu = mu_q(qm) + rk
@@ -178,10 +185,10 @@ __global__ __launch_bounds__(NT) void CEVA_KERNEL(ceva_close)(const DecP p) {
     mrun = mn;
     __syncthreads();
   }
-  if (tid < D) const_cast<float*>(reinterpret_cast<const float*>(row<float>(p.lv, b, h, c)))[tid] = acc / lrun;
+  if (tid < D) store_lmk<CEVA_LMK(E)>(p.lv, b, h, c, tid, acc / lrun);
 }
 
-
+#ifndef CEVA_L16
 // one workgroup per (token t, element b) of the step: the token's [3, H, D] row, 16 bytes per lane and load, and its pad flag.
 // Each token's row is reduced on its own (a step may straddle the end of a ring); the capacity test stays on p.cap, the
 // landmark capacity.  SEQ: every workgroup finds n_b from the flags of its own element (one pass of 16-byte loads, a
@@ -211,4 +218,5 @@ __global__ __launch_bounds__(NT) void CEVA_KERNEL(ceva_append)(const AppP p) {
   for (int i = threadIdx.x; i < p.row_bytes / 16; i += NT) dst[i] = src[i];
   if (threadIdx.x == 0) p.pad[at] = !SEQ && p.src_pad ? p.src_pad[(size_t)b * p.T + t] : (uint8_t)0;
 }
-
+#endif  // !CEVA_L16
+#undef CEVA_LMK

@@ -18,6 +18,9 @@ A static or rolling state made with `hold_projections=True` also HOLDS THE TWO P
 the bias table and the mu parameters: a step of at most 64 rows (T_new B) runs them as two more launches,
 ea_ceva_sdecode_linear in front of append and behind advance, that stream the held weights once; no framework kernel of
 such a step touches a weight.
+A bf16 or fp16 static or rolling state made with `compact_landmarks=True` keeps its landmark rows (`rf_k_bar`, `beta`) in its
+own dtype instead of fp32: close, attn and attn_split run as ea_ceva_sdecode_close_l16, _attn_l16 and _attn_split_l16, which
+round the two rows of a closed chunk once and read them as they read key and value rows; the arithmetic stays fp32.
 """
 import ctypes
 import functools
@@ -44,20 +47,22 @@ _HELD = ("w_qkv", "b_qkv", "w_out", "b_out", "proj_rows")
 
 
 def _state_options(init):
-    """The keyword-only `per_sequence=False`, `landmark_splits=1` and `hold_projections=False` of the two `init_*_decoding`
-    methods.  The methods keep
+    """The keyword-only `per_sequence=False`, `landmark_splits=1`, `hold_projections=False` and `compact_landmarks=False` of
+    the two `init_*_decoding` methods.  The methods keep
     the positional interface they had, and that is the signature they report (`__signature__`: callers that pin the parameter
     list, this package's own tests among them, see what they saw); the options are taken off here and handed to the method
     as its last arguments.  Arguments are bound as Python binds them: an option by position, or an unknown keyword, is a
     TypeError.  (`landmark_splits` is handed on as given: the method checks it behind its other refusals.)"""
     positional = inspect.signature(init)
-    positional = positional.replace(parameters=list(positional.parameters.values())[:-3])
+    positional = positional.replace(parameters=list(positional.parameters.values())[:-4])
 
     @functools.wraps(init)
-    def with_options(self, *args, per_sequence=False, landmark_splits=1, hold_projections=False, **kwargs):
+    def with_options(self, *args, per_sequence=False, landmark_splits=1, hold_projections=False, compact_landmarks=False,
+                     **kwargs):
         bound = positional.bind(self, *args, **kwargs)
         bound.apply_defaults()
-        return init(*bound.args, bool(per_sequence), landmark_splits, bool(hold_projections), **bound.kwargs)
+        return init(*bound.args, bool(per_sequence), landmark_splits, bool(hold_projections), bool(compact_landmarks),
+                    **bound.kwargs)
     with_options.__signature__ = positional
     return with_options
 
@@ -96,7 +101,7 @@ class CevaDecoding:
     # ---- static and rolling states ----------------------------------------------------------------------------------------
     @_state_options
     def init_static_decoding(self, incremental_state, batch_size, max_tokens, dtype, device, per_sequence=False,
-                             landmark_splits=1, hold_projections=False):
+                             landmark_splits=1, hold_projections=False, compact_landmarks=False):
         """Allocate, once, every buffer a decoding step touches and mark this module's incremental state as STATIC: every
         later `forward(..., incremental_state=incremental_state)` then runs a step that can be captured into a graph
         (`torch.cuda.graph`) and replayed -- the token count lives in device memory and the kernels advance it: four
@@ -165,25 +170,42 @@ class CevaDecoding:
         the dtype the plain step returns.  A larger step (a prompt; every piece a rolling state cuts it into) runs the library
         GEMM on the held operands: no concatenation and no cast of a weight either.  Outputs equal the plain state's to
         rounding (16-bit weights, another summation order), not bit for bit.  After the parameters have changed,
-        `refresh_decoding_weights` re-reads them in place."""
+        `refresh_decoding_weights` re-reads them in place.
+        `compact_landmarks=True` (default False; combines with the other three; a 16-bit `dtype` only -- the fp32 state is
+        the fidelity path and has nothing to compact): the landmark rows are kept in the state's dtype,
+            rf_k_bar  [B, h, cap / r, d]  `dtype`
+            beta      [B, h, cap / r, d]  `dtype`
+        which halves them -- at h = 8, d = 128, r = 8 and 32k tokens they are 33.5 MB of a 35 MB state in fp32 -- and halves
+        what a single-token step at a long context reads.  A step runs ea_ceva_sdecode_close_l16 and ea_ceva_sdecode_attn_l16
+        (or ea_ceva_sdecode_attn_split_l16 + merge) in place of their twins, for steps, prompt pieces and captured steps alike;
+        append, merge and advance are the same launches.  close computes what it computes on a plain state, in fp32 and in the
+        same order -- mu and beta from the unrounded rf_k_bar -- and rounds only the two rows it stores, once, to nearest even:
+        the landmark rows of a compact state are the plain state's rows rounded, bit for bit.  attn widens them as it widens key
+        and value rows, so the outputs differ from the plain state's by that one rounding of the landmark operands (about 5e-3
+        of the largest output for bf16, 1e-3 for fp16, on N(0, 1) operands) and are equal bit for bit while no landmark is
+        visible.  The token rows, pad flags and counters are those of the plain state.  The other methods need nothing
+        beyond what the dtype carries: `reorder_incremental_state` copies rows of whatever type, `reset_decoding_rows`,
+        `decoding_positions` and the overflow queries read no landmark row, `refresh_decoding_weights` touches none, and
+        `decoding_state_nbytes` counts the bytes the tensors have."""
         B, T, device = self._check_static_decoding(batch_size, max_tokens, dtype, device)
         P = _check_landmark_splits(landmark_splits)
         self._check_hold_projections(hold_projections, dtype)
+        self._check_compact_landmarks(compact_landmarks, dtype)
         w = self.window_size
         cap = -(-T // w) * w
         return self._alloc_static_decoding(incremental_state, B, cap, cap, dtype, device, {"count": 0}, per_sequence, P,
-                                           hold_projections)
+                                           hold_projections, compact_landmarks)
 
     @_state_options
     def init_rolling_decoding(self, incremental_state, batch_size, max_tokens, dtype, device, max_step_tokens=None,
-                              per_sequence=False, landmark_splits=1, hold_projections=False):
+                              per_sequence=False, landmark_splits=1, hold_projections=False, compact_landmarks=False):
         """`init_static_decoding` with the token rows in a fixed RING: the state is static in every respect (the same step,
         capturable and replayable; `static_decoding_overflowed` and the in-place `reorder_incremental_state` work on it), but
         `qkv` and `pad` hold R token slots instead of one row per token ever decoded, token n in slot n % R:
             qkv       [B, R, 3, h, d]     `dtype`
             pad       [B, R]              uint8
             rf_k_bar  [B, h, cap / r, d]  fp32   } linear, as in the static state: cap = ceil(max_tokens / w) w bounds
-            beta      [B, h, cap / r, d]  fp32   } only the landmark rows (and `pos`)
+            beta      [B, h, cap / r, d]  fp32   } only the landmark rows (and `pos`); `dtype` with compact_landmarks
             pos, status, bias, mu         as in the static state
         S = `max_step_tokens` (default w) is the largest step one launch sequence may hold, and R is the smallest multiple
         of w with R >= w + e + S.  Why that is enough: a step of T <= S tokens that starts at token t0 reads the local keys /
@@ -204,7 +226,11 @@ class CevaDecoding:
         256 / (B h) parts fill the device; more than ceil(tokens / (64 r)) buy nothing.
         `hold_projections=True`: as in `init_static_decoding` -- the state holds 16-bit copies of the two projections (a capture
         fixes the weights; `refresh_decoding_weights` re-reads them), a step of at most 64 rows runs them on
-        ea_ceva_sdecode_linear, and the pieces of a prompt run the library GEMM on the held operands."""
+        ea_ceva_sdecode_linear, and the pieces of a prompt run the library GEMM on the held operands.
+        `compact_landmarks=True`: as in `init_static_decoding` -- a bf16 or fp16 state keeps `rf_k_bar` and `beta` in its own
+        dtype, the plain state's rows rounded once, and its steps run the `_l16` entry points.  The landmark rows are nearly
+        all of a rolling state at a long context (33.5 of 35 MB per layer and sequence at 32k tokens, h = 8, d = 128, r = 8),
+        so the option about halves it."""
         B, T, device = self._check_static_decoding(batch_size, max_tokens, dtype, device)
         w, e = self.window_size, self.ext_size
         S = w if max_step_tokens is None else int(max_step_tokens)
@@ -212,12 +238,20 @@ class CevaDecoding:
             raise ValueError("rolling decoding needs max_step_tokens > 0, got %d" % S)
         P = _check_landmark_splits(landmark_splits)
         self._check_hold_projections(hold_projections, dtype)
+        self._check_compact_landmarks(compact_landmarks, dtype)
         cap = -(-T // w) * w
         ring = -(-(w + e + S) // w) * w
         rows = min(ring, cap)
         static = {"count": 0, "cap": cap, "ring": ring if ring < cap else 0, "max_step": S}
         return self._alloc_static_decoding(incremental_state, B, cap, rows, dtype, device, static, per_sequence, P,
-                                           hold_projections)
+                                           hold_projections, compact_landmarks)
+
+    @staticmethod
+    def _check_compact_landmarks(compact, dtype):
+        """What `compact_landmarks=True` refuses, behind every other refusal and before anything is allocated."""
+        if compact and dtype == torch.float32:
+            raise ValueError("compact_landmarks=True keeps the landmark rows in the state's 16-bit dtype: an fp32 decoding "
+                             "state is the fidelity path and has nothing to compact")
 
     def _check_hold_projections(self, hold, dtype):
         """What `hold_projections=True` refuses, behind every other refusal and before anything is allocated."""
@@ -247,16 +281,17 @@ class CevaDecoding:
         return B, T, device
 
     def _alloc_static_decoding(self, incremental_state, B, cap, rows, dtype, device, static, per_sequence=False, splits=1,
-                               hold=False):
-        """The buffers of a static state: `rows` token rows (cap, or a ring), cap / r landmark rows; one counter and one
-        overflow flag, or (per_sequence) one of each per batch row and the rows' token counts of a step; splits > 1: the
-        workspace of a short step's partials; hold: the 16-bit projections and the staging rows of a step."""
+                               hold=False, compact=False):
+        """The buffers of a static state: `rows` token rows (cap, or a ring), cap / r landmark rows (fp32; compact: `dtype`);
+        one counter and one overflow flag, or (per_sequence) one of each per batch row and the rows' token counts of a step;
+        splits > 1: the workspace of a short step's partials; hold: the 16-bit projections and the staging rows of a step."""
         h, d, r = self.num_heads, self.head_dim, self.chunk_size
         nc = B if per_sequence else 1
+        ldtype = dtype if compact else torch.float32
         state = {
             "qkv": torch.zeros((B, rows, 3, h, d), dtype=dtype, device=device),
-            "rf_k_bar": torch.zeros((B, h, cap // r, d), dtype=torch.float32, device=device),
-            "beta": torch.zeros((B, h, cap // r, d), dtype=torch.float32, device=device),
+            "rf_k_bar": torch.zeros((B, h, cap // r, d), dtype=ldtype, device=device),
+            "beta": torch.zeros((B, h, cap // r, d), dtype=ldtype, device=device),
             "pad": torch.zeros((B, rows), dtype=torch.uint8, device=device),
             "pos": torch.zeros((nc,), dtype=torch.int32, device=device),
             "status": torch.zeros((nc,), dtype=torch.int32, device=device),
@@ -276,6 +311,8 @@ class CevaDecoding:
             state["w_out"] = torch.empty((C, C), dtype=dtype, device=device)
             state["b_out"] = torch.empty((C,), dtype=dtype, device=device) if out_b else None
             static["hold_projections"] = True
+        if compact:
+            static["compact_landmarks"] = True
         with torch.no_grad():
             state["bias"] = self._decode_bias_table(device)
             state["mu"] = self._decode_mu_f32()
@@ -320,7 +357,7 @@ class CevaDecoding:
 
     def decoding_state_nbytes(self, incremental_state):
         """Bytes of every tensor in this module's decoding buffer (dynamic, static or rolling): token rows, pad flags,
-        landmark rows, counters and, for a static state, the bias table, the fp32 mu parameters it holds, the workspace
+        landmark rows (fp32, or 16-bit on a state made with `compact_landmarks=True`), counters and, for a static state, the bias table, the fp32 mu parameters it holds, the workspace
         of `landmark_splits` and what `hold_projections` holds.  Host only."""
         def nbytes(v):
             if torch.is_tensor(v):
@@ -372,6 +409,9 @@ class CevaDecoding:
         return incremental_state
 
     def reorder_incremental_state(self, incremental_state, new_order):
+        """Permute the batch rows of this module's decoding buffer.  A static or rolling state: `qkv`, `rf_k_bar`, `beta`, `pad`
+        (and the per-row counters of a per-sequence state), in place; the landmark rows are copied in the type they have, fp32
+        or the 16 bits of a compact state."""
         buf = self._get_input_buffer(incremental_state)
         if buf and self.get_incremental_state(incremental_state, "attn_static") is not None:
             # a static state reorders IN PLACE: the pointers a captured step holds stay valid, and the reorder can itself
@@ -473,8 +513,9 @@ class CevaDecoding:
         cache's dtype, so fp32 decoding equals the fp32 full path; on a dynamic state which chunks close is decided on the
         host from the token count, with no read-back.  No limit on the context length or the number of landmarks.
         A state made by `init_static_decoding` / `init_rolling_decoding` (docstrings there) takes the same step with the
-        right-hand column of this module's table; on a rolling state the launches address the token rows through the ring, and on
-        a state with `landmark_splits > 1` a step of at most 8 tokens runs attn as attn_split + merge."""
+        right-hand column of this module's table; on a rolling state the launches address the token rows through the ring, on
+        a state with `landmark_splits > 1` a step of at most 8 tokens runs attn as attn_split + merge, and on a state with
+        `compact_landmarks` close, attn and attn_split are the `_l16` entry points over 16-bit landmark rows."""
         nv = _ops.nv
         self._refuse_decoding()
         nv.require_cuda(query, "query")                            # (before any state is built: no CPU fallback)
@@ -548,11 +589,12 @@ class CevaDecoding:
         adaptive, has_bias = 1 if self.adaptive_proj == "qk" else 0, 0 if bias is None else 1
         if static is not None:
             family, closes = "ea_ceva_sdecode_", True
+            l16 = "_l16" if static.get("compact_landmarks") else ""     # (16-bit landmark rows: close, attn, attn_split)
             geom = nv.ea_ceva_sdec_geom(B, h, d, io, w, e, r, T_new, static.get("cap", cache.shape[1]), adaptive, has_bias,
                                         static.get("ring", 0), state["pos"].data_ptr(), state["status"].data_ptr(),
                                         state["ntok"].data_ptr() if "ntok" in state else None)
         else:
-            family = "ea_ceva_decode_"
+            family, l16 = "ea_ceva_decode_", ""
             c_first, c_last = t0 // r, (t0 + T_new) // r - 1        # the chunks this step's tokens complete
             closes = c_last >= c_first
             geom = nv.ea_ceva_dec_geom(B, h, d, io, w, e, r, t0, T_new, c_first, c_last, cache.shape[1], adaptive, has_bias,
@@ -574,17 +616,17 @@ class CevaDecoding:
                     self._decode_mu_cache = _ops.DerivedCache()
                 mlp = self._decode_mu_cache.get(self, self._mu_params(), self._decode_mu_f32)
             mp = (ctypes.c_void_p * len(mlp))(*[p.data_ptr() for p in mlp])
-            nv.call(family + "close", g, *rows, mp, *lmk, st)
+            nv.call(family + "close" + l16, g, *rows, mp, *lmk, st)
         out = torch.empty((T_new, B, h, d), dtype=cache.dtype, device=dev)
         to = nv.t4(out.permute(1, 2, 0, 3))                        # [B, h, T_new, d] view of the time-first rows
         if static is not None and "split_ws" in state and T_new <= _SPLIT_MAX_STEP and not piece:
             # (the token count of the step the caller handed over decides, and a capture fixes it; the pieces of a prompt,
             #  its short tail included, are the prompt's)
             ws, parts = state["split_ws"], state["split_ws"].shape[3]
-            nv.call("ea_ceva_sdecode_attn_split", g, *rows, nv.ptr(bias), *lmk, ctypes.byref(to), parts, nv.ptr(ws), st)
+            nv.call("ea_ceva_sdecode_attn_split" + l16, g, *rows, nv.ptr(bias), *lmk, ctypes.byref(to), parts, nv.ptr(ws), st)
             nv.call("ea_ceva_sdecode_merge", g, ctypes.byref(to), parts, nv.ptr(ws), st)
         else:
-            nv.call(family + "attn", g, *rows, nv.ptr(bias), *lmk, ctypes.byref(to), st)
+            nv.call(family + "attn" + l16, g, *rows, nv.ptr(bias), *lmk, ctypes.byref(to), st)
         if static is not None:
             nv.call("ea_ceva_sdecode_advance", g, st)
             if not capturing and "ntok" not in state:              # (a replay advances only the device count; per-sequence

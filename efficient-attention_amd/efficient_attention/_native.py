@@ -22,7 +22,7 @@ class ea_t4(ctypes.Structure):
                 ("sn", ctypes.c_int64)]
 
 
-ABI_VERSION = 22         # ea_abi_version() of include/ea_hip.h this file mirrors
+ABI_VERSION = 23         # ea_abi_version() of include/ea_hip.h this file mirrors
 
 
 class ea_geom(ctypes.Structure):
@@ -239,6 +239,9 @@ SIGNATURES = {
     "ea_ceva_sdecode_close": [_SDG, _T, _T, _T, _P, _P, _T, _T, _P],
     "ea_ceva_sdecode_attn": [_SDG, _T, _T, _T, _P, _P, _T, _T, _T, _P],
     "ea_ceva_sdecode_attn_split": [_SDG, _T, _T, _T, _P, _P, _T, _T, _T, _I, _P, _P],
+    "ea_ceva_sdecode_close_l16": [_SDG, _T, _T, _T, _P, _P, _T, _T, _P],
+    "ea_ceva_sdecode_attn_l16": [_SDG, _T, _T, _T, _P, _P, _T, _T, _T, _P],
+    "ea_ceva_sdecode_attn_split_l16": [_SDG, _T, _T, _T, _P, _P, _T, _T, _T, _I, _P, _P],
     "ea_ceva_sdecode_merge": [_SDG, _T, _I, _P, _P],
     "ea_ceva_sdecode_advance": [_SDG, _P],
     "ea_ceva_sdecode_linear": [_I, _I, _I, _P, _I, _L, _P, _I, _P, _P, _I, _L, _P],

@@ -1034,6 +1034,24 @@ int ea_ceva_sdecode_attn_split(const ea_ceva_sdec_geom* g, const ea_t4* q, const
 int ea_ceva_sdecode_merge(const ea_ceva_sdec_geom* g, const ea_t4* out, int32_t parts, const float* ws, void* stream);
 int ea_ceva_sdecode_advance(const ea_ceva_sdec_geom* g, void* stream);
 
+/* ABI 23, a static state with 16-bit landmark rows (init_*_decoding(compact_landmarks=True)): rf_k_bar and beta are rows of
+ * the geometry's dtype, EA_BF16 or EA_F16, their ea_t4 strides in those elements.  The three calls below take the place of
+ * their twins in a step (append, merge and advance touch no landmark row) and take the geometry unchanged.
+ *   ea_ceva_sdecode_close_l16: the arithmetic of ea_ceva_sdecode_close in its order, in fp32; mu and beta are formed from the
+ *     unrounded rf_k_bar, and only the stores of the two rows round, once, to nearest even: the rows written equal the
+ *     twin's rows rounded, bit for bit.
+ *   ea_ceva_sdecode_attn_l16, ea_ceva_sdecode_attn_split_l16: the twins' arithmetic on the rows widened to fp32 (exact).
+ * Every refusal is the twin's, decided in the same order, and besides EA_E_BADARG for: dtype EA_F32 (decided with the other
+ * faults of the dtype, before the head dim); a landmark pointer not 16-byte aligned; a landmark stride that is no multiple
+ * of 8 elements (rows of D 16-bit elements, D >= 32, stay 16-byte aligned). */
+int ea_ceva_sdecode_close_l16(const ea_ceva_sdec_geom* g, const ea_t4* q, const ea_t4* k, const ea_t4* v, const uint8_t* pad,
+                              const float* const* mu_params, const ea_t4* rf_k_bar, const ea_t4* beta, void* stream);
+int ea_ceva_sdecode_attn_l16(const ea_ceva_sdec_geom* g, const ea_t4* q, const ea_t4* k, const ea_t4* v, const uint8_t* pad,
+                             const float* bias, const ea_t4* rf_k_bar, const ea_t4* beta, const ea_t4* out, void* stream);
+int ea_ceva_sdecode_attn_split_l16(const ea_ceva_sdec_geom* g, const ea_t4* q, const ea_t4* k, const ea_t4* v,
+                                   const uint8_t* pad, const float* bias, const ea_t4* rf_k_bar, const ea_t4* beta,
+                                   const ea_t4* out, int32_t parts, float* ws, void* stream);
+
 /* ABI 22, the projections of a step on weights the static state holds (init_*_decoding(hold_projections=True);
  * ea_ceva_decode_linear.hip):
  *   y[m, n] = round_y( sum_k round_w(x[m, k]) w[n, k] + bias[n] ),  1 <= M <= EA_CEVA_LINEAR_MAX_ROWS

@@ -1,5 +1,5 @@
 """Per-token latency of CausalEVAttention decoding at the wikitext-103 LM geometry (embed 1024, h 8, d 128, w 128, chunks of 8,
-T5 bias, adaptive 'qk'), 16 stacked residual attention layers (x + attn(x), no FFN), bf16 autocast, in fifteen modes:
+T5 bias, adaptive 'qk'), 16 stacked residual attention layers (x + attn(x), no FFN), bf16 autocast, in eighteen modes:
  - dynamic:       the incremental state of `_decode` (host token count, two decode launches per layer step);
  - static:        `init_static_decoding`, the same step run eagerly (four decode launches per layer step);
  - graph:         that static step over all 16 layers captured once with torch.cuda.graph and replayed;
@@ -15,6 +15,10 @@ T5 bias, adaptive 'qk'), 16 stacked residual attention layers (x + attn(x), no F
    `hold_projections=True`: the 1-token step runs its two projections on ea_ceva_sdecode_linear over the 16-bit weights the
    state holds, and no framework kernel touches a weight.  Their rows differ from the other modes' in rounding (the query is
    rounded before the products, another order of the sums).
+ - compact-graph, compact-rolling-graph, compact-split-rolling-graph: graph, rolling-graph and split-rolling-graph on a state
+   made with `compact_landmarks=True`: rf_k_bar and beta are bf16, and the step runs close, attn and attn_split on the `_l16`
+   entry points.  Their rows differ from the plain modes' by the one rounding of the landmark rows: for these modes the
+   "rows equal" column always reports the distance to the first mode's rows, never bitwise equality.
    python tools/ceva_decode_latency.py [--context 512|4096|32768] [--steps 64] [--splits P] [--modes dynamic,static,graph,...]   (GPU)
    python tools/ceva_decode_latency.py --ragged [--context 512] [--steps 64]     (GPU)
 `--ragged`: batch 8 on per-sequence states, row b prefilled to (b + 1) / 8 of `context` by right-padded steps, then the
@@ -72,6 +76,8 @@ def run(mods, mode, B, context, steps, blocks=5, warmup=4, lengths=None, splits=
         opt["landmark_splits"] = splits or default_splits(B)
     if mode.startswith("held-"):
         opt["hold_projections"] = True
+    if mode.startswith("compact-"):
+        opt["compact_landmarks"] = True
     for m in mods:
         st = {}
         m.init_incremental_state()
@@ -123,7 +129,8 @@ def run(mods, mode, B, context, steps, blocks=5, warmup=4, lengths=None, splits=
 
 MODES = ("dynamic", "static", "graph", "rolling", "rolling-graph", "per-seq", "per-seq-graph", "per-seq-rolling-graph",
          "split-graph", "split-rolling-graph", "per-seq-split-graph", "per-seq-split-rolling-graph",
-         "held-graph", "held-rolling-graph", "held-split-rolling-graph")
+         "held-graph", "held-rolling-graph", "held-split-rolling-graph",
+         "compact-graph", "compact-rolling-graph", "compact-split-rolling-graph")
 CONTEXTS = (512, 4096, 32768)
 
 
@@ -175,6 +182,8 @@ def main():
         for ctx in [int(c) for c in a.state_bytes.split(",")]:
             sb, rb = state_bytes(m, 1, ctx)
             print("decoding_state_nbytes per layer, %d tokens, batch 1: static %d, rolling %d" % (ctx, sb, rb), flush=True)
+            cs, cr = state_bytes(m, 1, ctx, compact_landmarks=True)
+            print("    compact_landmarks: static %d, rolling %d" % (cs, cr), flush=True)
         return
     modes = [m for m in a.modes.split(",") if m]
     if [m for m in modes if m not in MODES]:
@@ -185,8 +194,9 @@ def main():
     for B in [int(b) for b in a.batches.split(",")]:
         res = {mode: run(mods, mode, B, a.context, a.steps, splits=a.splits) for mode in modes}
         ref = res[modes[0]][1]
-        same = [torch.equal(res[mode][1], ref) or "max |d| %.2e" % (res[mode][1].float() - ref.float()).abs().max().item()
-                for mode in modes[1:]]
+        def dist(mode):                                       # (compact modes: the distance, also where it is 0)
+            return "max |d| %.2e" % (res[mode][1].float() - ref.float()).abs().max().item()
+        same = [dist(mode) if mode.startswith("compact-") else torch.equal(res[mode][1], ref) or dist(mode) for mode in modes[1:]]
         print("%3d " % B + " ".join("%13.3f" % res[m][0] for m in modes) + "  %s" % same, flush=True)
         sb, rb = state_bytes(mods[0], B, a.context)
         print("    decoding_state_nbytes per layer, %d tokens, batch %d: static %d, rolling %d" % (a.context, B, sb, rb),
@@ -195,6 +205,10 @@ def main():
             hs, hr = state_bytes(mods[0], B, a.context, hold_projections=True)
             print("    hold_projections: static %d, rolling %d (+ %d bytes per layer: the 16-bit projections and the staging rows)"
                   % (hs, hr, hs - sb), flush=True)
+        if [m for m in modes if m.startswith("compact-")]:
+            cs, cr = state_bytes(mods[0], B, a.context, compact_landmarks=True)
+            print("    compact_landmarks: static %d, rolling %d (- %d bytes per layer: rf_k_bar and beta in bf16)"
+                  % (cs, cr, sb - cs), flush=True)
         if [m for m in modes if "split" in m]:
             P = a.splits or default_splits(B)
             print("    landmark_splits %d: + %d bytes of workspace per layer" % (P, B * HEADS * 8 * P * (EMBED // HEADS + 4) * 4),
