@@ -35,15 +35,17 @@
 //        tokens, the positions before its first flag in the step's pad flags (append finds n_b and publishes it; close, attn
 //        and advance read it behind that launch).  Nothing is stored for the other positions, their output rows are zero,
 //        and overflow is per element: status[b], NaN rows of b alone.  The grids stay those of T tokens; a workgroup whose
-//        element needs less exits at once.  `Step` owns both numbers; no kernel body reads p.T for anything else.  The SEQ
-//        kernels have names of their own (ceva_*_seq_kernel, ea_ceva_decode_step.h), so the others keep their symbols and code.
+//        element needs less exits at once.  `Step` owns both numbers; no kernel body reads p.T for anything else.
+// A fourth template parameter of close, attn and attn_split is no switch of the step but the element type L of the landmark
+// rows (rf_k_bar, beta): float, or E on a compact state (16-bit DEV steps only).
 // A DEV step of at most QPW tokens can run attn as two launches, attn_split -> merge, with the tiles of a window block shared
-// by several workgroups (ea_ceva_decode_split.h): kernels of their own again.  attn and attn_split are one body: the staging
+// by several workgroups (ea_ceva_decode_split.h).  attn and attn_split are one body: the staging
 // of a query group, the tile loop with its online softmax, the stash of a wave's partial and the merge over waves exist
 // once, as the helpers below (Group, stage_queries, stream_tiles, stash_partial, merge_waves).  A kernel keeps its Step, its
 // refusals and exits, its map from blockIdx to (block, part), which tiles a wave takes and what becomes of the result.
 #include "ea_common.h"
 #include "ea_ceva_decode.h"
+#include <type_traits>
 
 namespace ea {
 
@@ -368,42 +370,10 @@ EA_DEV int first_flag(const uint8_t* f, int T, int* red) {
 }
 
 
-// ---- the kernels of a step, once per value of SEQ (ea_ceva_decode_step.h) ----------------------------------------------
-#define CEVA_SEQ false
-#define CEVA_KERNEL(name) name##_kernel
-#include "ea_ceva_decode_step.h"
-#undef CEVA_SEQ
-#undef CEVA_KERNEL
-#define CEVA_SEQ true
-#define CEVA_KERNEL(name) name##_seq_kernel
-#include "ea_ceva_decode_step.h"
-#undef CEVA_SEQ
-#undef CEVA_KERNEL
-
-// ---- a short step with its landmark range split over workgroups (ea_ceva_decode_split.h) -------------------------------
-#define CEVA_SPLIT_TEXT
-#define CEVA_KERNEL(name) name##_kernel
-#include "ea_ceva_decode_split.h"
-#undef CEVA_KERNEL
-
-// ---- the same kernels over 16-bit landmark rows (a compact state: rf_k_bar and beta have the cache's dtype) -------------
-// CEVA_L16 makes the landmark element type E instead of float, and nothing else: close rounds its two stores, attn and
-// attn_split read landmark rows as they read key and value rows.  Kernels of their own (ceva_*_l16_kernel), DEV steps of a
-// 16-bit E only; the texts leave out what has no landmark row in it (append, merge).
-#define CEVA_L16
-#define CEVA_SEQ false
-#define CEVA_KERNEL(name) name##_l16_kernel
+// ---- the kernels of a step (ea_ceva_decode_step.h), and of a short step with its landmark range split over workgroups
+// (ea_ceva_decode_split.h)
 #include "ea_ceva_decode_step.h"
 #include "ea_ceva_decode_split.h"
-#undef CEVA_SEQ
-#undef CEVA_KERNEL
-#define CEVA_SEQ true
-#define CEVA_KERNEL(name) name##_seq_l16_kernel
-#include "ea_ceva_decode_step.h"
-#undef CEVA_SEQ
-#undef CEVA_KERNEL
-#undef CEVA_L16
-#undef CEVA_SPLIT_TEXT
 
 // *pos += T, in a launch of its own after attn on the same stream: stream order puts it behind every read of *pos in the
 // step.  (The other way, the last attn workgroup advancing through a completion counter, needs an agent-scope release /
@@ -428,40 +398,31 @@ using DecKernel = void (*)(const DecP);
 using SplitKernel = void (*)(const DecSplitP);
 using MergeKernel = void (*)(const DecMergeP);
 
-template <typename E, int D>
+// a run-time flag -> its template argument: f(std::bool_constant<flag>{}), the one place a flag of a step is mapped
+template <typename F>
+auto with_flag(bool flag, F&& f) { return flag ? f(std::true_type{}) : f(std::false_type{}); }
+
+// L: the landmark element type, float or (a compact state) E; for fp32 rows the two are one instance.  RING, SEQ and a
+// 16-bit L belong to a DEV step: null without it (the launchers have refused that)
+template <typename E, int D, typename L>
 DecKernel kernel_of(DecKind kind, bool dev, bool ring, bool seq) {
-  if (seq && kind == DEC_CLOSE) return ring ? ceva_close_seq_kernel<E, D, true, true> : ceva_close_seq_kernel<E, D, true, false>;
-  if (seq) return ring ? ceva_attn_seq_kernel<E, D, true, true> : ceva_attn_seq_kernel<E, D, true, false>;
-  if (kind == DEC_CLOSE)
-    return !dev ? ceva_close_kernel<E, D, false, false> : ring ? ceva_close_kernel<E, D, true, true> : ceva_close_kernel<E, D, true, false>;
-  return !dev ? ceva_attn_kernel<E, D, false, false> : ring ? ceva_attn_kernel<E, D, true, true> : ceva_attn_kernel<E, D, true, false>;
+  return with_flag(dev, [&](auto dv) {
+    return with_flag(ring, [&](auto rg) {
+      return with_flag(seq, [&](auto sq) -> DecKernel {
+        constexpr bool DEV = decltype(dv)::value, RING = decltype(rg)::value, SEQ = decltype(sq)::value;
+        if constexpr (DEV || !(RING || SEQ || Io<L>::SZ == 2))
+          return kind == DEC_CLOSE ? ceva_close_kernel<E, D, DEV, RING, SEQ, L> : ceva_attn_kernel<E, D, DEV, RING, SEQ, L>;
+        return nullptr;
+      });
+    });
+  });
 }
 
-template <typename E, int D>
+template <typename E, int D, typename L>
 SplitKernel split_of(bool ring, bool seq) {
-  if (seq) return ring ? ceva_attn_split_kernel<E, D, true, true> : ceva_attn_split_kernel<E, D, false, true>;
-  return ring ? ceva_attn_split_kernel<E, D, true, false> : ceva_attn_split_kernel<E, D, false, false>;
-}
-
-// the kernels of a compact state: 16-bit E, DEV steps (null for fp32 rows: the caller has refused them)
-template <typename E, int D>
-DecKernel l16_kernel_of(DecKind kind, bool ring, bool seq) {
-  if constexpr (Io<E>::SZ == 2) {
-    if (seq && kind == DEC_CLOSE) return ring ? ceva_close_seq_l16_kernel<E, D, true, true> : ceva_close_seq_l16_kernel<E, D, true, false>;
-    if (seq) return ring ? ceva_attn_seq_l16_kernel<E, D, true, true> : ceva_attn_seq_l16_kernel<E, D, true, false>;
-    if (kind == DEC_CLOSE) return ring ? ceva_close_l16_kernel<E, D, true, true> : ceva_close_l16_kernel<E, D, true, false>;
-    return ring ? ceva_attn_l16_kernel<E, D, true, true> : ceva_attn_l16_kernel<E, D, true, false>;
-  }
-  return nullptr;
-}
-
-template <typename E, int D>
-SplitKernel l16_split_of(bool ring, bool seq) {
-  if constexpr (Io<E>::SZ == 2) {
-    if (seq) return ring ? ceva_attn_split_l16_kernel<E, D, true, true> : ceva_attn_split_l16_kernel<E, D, false, true>;
-    return ring ? ceva_attn_split_l16_kernel<E, D, true, false> : ceva_attn_split_l16_kernel<E, D, false, false>;
-  }
-  return nullptr;
+  return with_flag(ring, [&](auto rg) {
+    return with_flag(seq, [&](auto sq) -> SplitKernel { return ceva_attn_split_kernel<E, D, decltype(rg)::value, decltype(sq)::value, L>; });
+  });
 }
 
 template <typename E, int D>
@@ -498,8 +459,9 @@ int ceva_decode_launch(DecKind kind, const DecP& p, hipStream_t st, bool l16) {
   if (p.D != 32 && p.D != 64 && p.D != 128) return EA_E_UNSUPPORTED;
   DecKernel kernel;
   if (!with_types(p.dtype, p.D, [&](auto e, auto d) {
-        kernel = l16 ? l16_kernel_of<decltype(e), decltype(d)::value>(kind, ring, seq)
-                     : kernel_of<decltype(e), decltype(d)::value>(kind, dev, ring, seq);
+        using E = decltype(e);
+        constexpr int D = decltype(d)::value;
+        kernel = l16 ? kernel_of<E, D, E>(kind, dev, ring, seq) : kernel_of<E, D, float>(kind, dev, ring, seq);
       }))
     return EA_E_BADARG;
   // x: the chunks the step closes / the window blocks it touches; DEV: the most T tokens can, wherever they start
@@ -516,7 +478,9 @@ int ceva_sdecode_attn_split(const DecP& p, int parts, float* ws, hipStream_t st,
   if (p.D != 32 && p.D != 64 && p.D != 128) return EA_E_UNSUPPORTED;
   SplitKernel kernel;
   if (!with_types(p.dtype, p.D, [&](auto e, auto d) {
-        kernel = l16 ? l16_split_of<decltype(e), decltype(d)::value>(ring, seq) : split_of<decltype(e), decltype(d)::value>(ring, seq);
+        using E = decltype(e);
+        constexpr int D = decltype(d)::value;
+        kernel = l16 ? split_of<E, D, E>(ring, seq) : split_of<E, D, float>(ring, seq);
       }))
     return EA_E_BADARG;
   const int nx = (p.T + p.w - 2) / p.w + 1;        // the most window blocks T tokens can touch
@@ -536,8 +500,9 @@ int ceva_sdecode_merge(const DecMergeP& p, int D, int dtype, int BH, hipStream_t
 }
 
 int ceva_sdecode_append(const AppP& p, hipStream_t st) {
-  void (*kernel)(const AppP) = p.ntok ? (p.ring ? ceva_append_seq_kernel<true> : ceva_append_seq_kernel<false>)
-                                      : (p.ring ? ceva_append_kernel<true> : ceva_append_kernel<false>);
+  void (*kernel)(const AppP) = with_flag(p.ring != 0, [&](auto rg) {
+    return with_flag(p.ntok != nullptr, [&](auto sq) { return &ceva_append_kernel<decltype(rg)::value, decltype(sq)::value>; });
+  });
   hipLaunchKernelGGL(kernel, dim3((unsigned)p.T, (unsigned)p.B), dim3(NT), 0, st, p);
   return (int)hipGetLastError();
 }

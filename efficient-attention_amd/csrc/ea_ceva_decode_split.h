@@ -1,6 +1,5 @@
 // ea_ceva_decode_split.h -- a short decoding step with its landmark range split over workgroups: attn_split, merge.
-// Not a header of declarations: ea_ceva_decode.hip includes this text once, inside its anonymous namespace and after the
-// kernels of ea_ceva_decode_step.h.
+// Included once by ea_ceva_decode.hip, inside its anonymous namespace and after the kernels of ea_ceva_decode_step.h.
 //
 // ceva_attn streams every landmark row of a (b, h) through ONE workgroup: at a long context a 1-token step is bound by the
 // latency of that one CU, not by bandwidth.  A step of at most QPW tokens has one query group per window block, and there the
@@ -22,21 +21,13 @@
 // What a step refuses stays with blockIdx.x == 0 of attn_split (block 0, part 0): NaN rows of a step that does not fit, zero
 // rows n_b .. T - 1 of a per-sequence element; merge re-evaluates both tests from pos / ntok (advance runs behind it) and leaves
 // those rows alone.
-// ea_ceva_decode.hip includes the text once more with CEVA_L16 and CEVA_KERNEL(x) = x_l16_kernel: attn_split over landmark
-// rows of type E (a compact state).  The partials are fp32 either way, so merge and the workspace layout exist once.
-#if !defined(CEVA_SPLIT_TEXT) || !defined(CEVA_KERNEL)
-#error "included by ea_ceva_decode.hip only"
-#endif
+// L is the element type of the landmark rows attn_split reads: float, or E on a compact state.  The partials are fp32
+// either way, so merge and the workspace layout do not depend on it.
 
-#ifndef CEVA_L16
 constexpr int WSX = 4;                             // floats behind acc[D] in a workspace row: m, l, 2 unused
-#define CEVA_LMK(E) float
-#else
-#define CEVA_LMK(E) E
-#endif
 
-template <typename E, int D, bool RING, bool SEQ>
-__global__ __launch_bounds__(NT) void CEVA_KERNEL(ceva_attn_split)(const DecSplitP sp) {
+template <typename E, int D, bool RING, bool SEQ, typename L>
+__global__ __launch_bounds__(NT) void ceva_attn_split_kernel(const DecSplitP sp) {
   const DecP& p = sp.d;
   constexpr int G = D / 4;                         // lanes that share a row of the merged partial
   __shared__ __attribute__((aligned(16))) float qs[NW][QPW][D];
@@ -61,7 +52,7 @@ __global__ __launch_bounds__(NT) void CEVA_KERNEL(ceva_attn_split)(const DecSpli
   stage_queries<E, D>(p, b, h, gr, qs[wave], lane);
   float m[QPW], l[QPW];
   f32x4 acc[QPW];
-  stream_tiles<E, D, RING, false, CEVA_LMK(E)>(p, b, h, gr, part * NW + wave, sp.parts * NW, qs[wave], ps[wave], lane, m, l, acc);
+  stream_tiles<E, D, RING, false, L>(p, b, h, gr, part * NW + wave, sp.parts * NW, qs[wave], ps[wave], lane, m, l, acc);
   stash_partial<D>(m, l, acc, mo[wave], ml[wave], lane);
   __syncthreads();
   if (wave != 0) return;
@@ -77,9 +68,6 @@ __global__ __launch_bounds__(NT) void CEVA_KERNEL(ceva_attn_split)(const DecSpli
   }
 }
 
-#undef CEVA_LMK
-
-#ifndef CEVA_L16
 // One wave per (step token t, b, h).  Lane p reads (m, l) of part p and the wave finds the common maximum; then G lanes
 // add the parts' rows in part order, as the in-LDS merge adds its waves.
 template <typename E, int D, bool SEQ>
@@ -111,4 +99,3 @@ __global__ __launch_bounds__(64) void ceva_merge_kernel(const DecMergeP p) {
   }
   Io<E>::st4(const_cast<char*>(row<E>(p.o, b, h, t)) + (size_t)lane * 4 * Io<E>::SZ, o * (1.f / lt));
 }
-#endif  // !CEVA_L16

@@ -1,22 +1,10 @@
 // ea_ceva_decode_step.h -- the three kernels of a causal EVA decoding step that read the step's position: attn, close, append.
-// Not a header of declarations: ea_ceva_decode.hip includes this text twice, inside its anonymous namespace and after the
-// helpers it uses, with
-//   CEVA_SEQ false, CEVA_KERNEL(x) = x_kernel        one token count for the batch (and the dynamic step)
-//   CEVA_SEQ true,  CEVA_KERNEL(x) = x_seq_kernel    per-sequence counts (DEV only)
-// so that the shared-count kernels keep their symbols, and close and append, token for token, the source they had before the
-// per-sequence switch existed: tools/isa_diff.py shows their code unchanged.  (Wrapping one body template in two kernels
-// compiles too, but the inlined body schedules differently from the kernel written out.)  What attn does to a query group
-// it shares with attn_split (ea_ceva_decode_split.h) and takes from the helpers of ea_ceva_decode.hip.
-// With CEVA_L16 (and CEVA_KERNEL(x) = x_l16_kernel / x_seq_l16_kernel) the text gives the attn and close of a compact state:
-// the landmark rows are of type E, not float (`Lmk` below), and that is the only difference.  append has no landmark row.
-#if !defined(CEVA_SEQ) || !defined(CEVA_KERNEL)
-#error "included by ea_ceva_decode.hip only"
-#endif
-#ifdef CEVA_L16
-#define CEVA_LMK(E) E
-#else
-#define CEVA_LMK(E) float
-#endif
+// Included once by ea_ceva_decode.hip, inside its anonymous namespace and after the helpers it uses.  The state's switches
+// (DEV, RING, SEQ) and the landmark element type L -- float, or E on a compact state, where close rounds its two stores and
+// attn reads landmark rows as it reads key and value rows -- are template parameters of the kernels themselves: every
+// combination is the kernel written out, nothing wrapped and nothing inlined.  append has no landmark row.
+// What attn does to a query group it shares with attn_split (ea_ceva_decode_split.h) and takes from the helpers of
+// ea_ceva_decode.hip.
 
 // One workgroup per window block of the step.  DEV: the grid holds the most window blocks T tokens can touch, and a block
 // this step does not touch exits at once; a step that does not fit writes NaN rows.  SEQ: the block's queries are those of
@@ -24,9 +12,8 @@
 // Wave s of the nsplit that share a query group takes tiles s, s + nsplit, ..; a group with a wave to itself is normalised
 // and stored by that wave, the others by the group's first wave after the in-LDS merge.  The dynamic step may come without
 // pad flags, so every read of them tests the pointer (Pad<true>).
-template <typename E, int D, bool DEV, bool RING>
-__global__ __launch_bounds__(NT) void CEVA_KERNEL(ceva_attn)(const DecP p) {
-  constexpr bool SEQ = CEVA_SEQ;
+template <typename E, int D, bool DEV, bool RING, bool SEQ, typename L>
+__global__ __launch_bounds__(NT) void ceva_attn_kernel(const DecP p) {
   static_assert(DEV || !RING, "the ring belongs to the static step");
   constexpr int G = D / 4;                         // lanes per value row in P.V
   __shared__ __attribute__((aligned(16))) float qs[NW][QPW][D];
@@ -54,7 +41,7 @@ __global__ __launch_bounds__(NT) void CEVA_KERNEL(ceva_attn)(const DecP p) {
     stage_queries<E, D>(p, b, h, gr, qs[wave], lane);
     float m[QPW], l[QPW];
     f32x4 acc[QPW];
-    stream_tiles<E, D, RING, true, CEVA_LMK(E)>(p, b, h, gr, wave % nsplit, nsplit, qs[wave], ps[wave], lane, m, l, acc);
+    stream_tiles<E, D, RING, true, L>(p, b, h, gr, wave % nsplit, nsplit, qs[wave], ps[wave], lane, m, l, acc);
     if (nsplit == 1) {
       if (lane < G) {
 #pragma unroll
@@ -83,9 +70,8 @@ __global__ __launch_bounds__(NT) void CEVA_KERNEL(ceva_attn)(const DecP p) {
 // t0 .. t0 + T - 1 complete; then the grid holds ceil(T / r), the most T tokens can complete, and a workgroup whose chunk
 // this step does not complete exits at once.  The chunk's rows do not straddle the end of a ring (r divides it); its
 // landmark row is row c.  SEQ: the chunks that element b's own tokens complete.
-template <typename E, int D, bool DEV, bool RING>
-__global__ __launch_bounds__(NT) void CEVA_KERNEL(ceva_close)(const DecP p) {
-  constexpr bool SEQ = CEVA_SEQ;
+template <typename E, int D, bool DEV, bool RING, bool SEQ, typename L>
+__global__ __launch_bounds__(NT) void ceva_close_kernel(const DecP p) {
   static_assert(DEV || !RING, "the ring belongs to the static step");
   __shared__ __attribute__((aligned(16))) float xm[2][D];      // chunk means of q, k
   __shared__ __attribute__((aligned(16))) float y[2][D];       // after the Linear layers
@@ -143,7 +129,7 @@ __global__ __launch_bounds__(NT) void CEVA_KERNEL(ceva_close)(const DecP p) {
   if (tid >= D && tid < 2 * D) {                   // k side: rf_k_bar = rk
     const int o = tid - D;
     xm[1][o] = z;
-    store_lmk<CEVA_LMK(E)>(p.lk, b, h, c, o, z);
+    store_lmk<L>(p.lk, b, h, c, o, z);
   }
   __syncthreads();
   if (tid < D) mu[tid] = z + xm[1][tid];           // mu = mu_q(qm) + rk
@@ -185,19 +171,17 @@ __global__ __launch_bounds__(NT) void CEVA_KERNEL(ceva_close)(const DecP p) {
     mrun = mn;
     __syncthreads();
   }
-  if (tid < D) store_lmk<CEVA_LMK(E)>(p.lv, b, h, c, tid, acc / lrun);
+  if (tid < D) store_lmk<L>(p.lv, b, h, c, tid, acc / lrun);
 }
 
-#ifndef CEVA_L16
 // one workgroup per (token t, element b) of the step: the token's [3, H, D] row, 16 bytes per lane and load, and its pad flag.
 // Each token's row is reduced on its own (a step may straddle the end of a ring); the capacity test stays on p.cap, the
 // landmark capacity.  SEQ: every workgroup finds n_b from the flags of its own element (one pass of 16-byte loads, a
 // 2048-token prefill is 128 of them), so none waits for another; the one of t = 0 publishes it, and also when the element
 // does not fit -- close, attn and advance decide that from pos[b] + ntok[b] as this kernel does.  The tokens it stores are
 // unflagged by construction: their pad flag is 0.
-template <bool RING>
-__global__ __launch_bounds__(NT) void CEVA_KERNEL(ceva_append)(const AppP p) {
-  constexpr bool SEQ = CEVA_SEQ;
+template <bool RING, bool SEQ>
+__global__ __launch_bounds__(NT) void ceva_append_kernel(const AppP p) {
   const int t = (int)blockIdx.x, b = (int)blockIdx.y;
   int n = p.T;
   if (SEQ) {
@@ -218,5 +202,3 @@ __global__ __launch_bounds__(NT) void CEVA_KERNEL(ceva_append)(const AppP p) {
   for (int i = threadIdx.x; i < p.row_bytes / 16; i += NT) dst[i] = src[i];
   if (threadIdx.x == 0) p.pad[at] = !SEQ && p.src_pad ? p.src_pad[(size_t)b * p.T + t] : (uint8_t)0;
 }
-#endif  // !CEVA_L16
-#undef CEVA_LMK

@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Compare one translation unit's gfx950 machine code between two trees, kernel by kernel.
 
-    python tools/isa_diff.py [--new-ok] OTHER_TREE [SOURCE.hip]   (default source: ea_ceva_decode.hip; this tree is the other side)
+    python tools/isa_diff.py [--new-ok | --by-code] OTHER_TREE [SOURCE.hip]   (default source: ea_ceva_decode.hip; this tree is the other side)
 
 Both sides are compiled with build.py's flags plus `--cuda-device-only -S`.  A kernel's body is what lies between its label
 and its `.Lfunc_end`, comments dropped, local `.L*` labels renumbered in order of appearance, its own symbol replaced.
@@ -9,6 +9,8 @@ Prints the kernels that exist on one side only and those whose bodies differ; ex
 A kernel whose instructions are equal and whose descriptor (`.amdhsa_*`) alone differs -- a field appended to its parameter
 block changes `.amdhsa_kernarg_size` and nothing else -- is listed as such, with the directives that differ, and with
 `--new-ok` neither it nor a kernel that only this tree has counts against the exit status.
+`--by-code` is for a change that renames kernels: it pairs them by body (instructions and descriptor) whatever their symbols,
+prints the symbols left without a partner on either side, and exits 0 only when there are none.
 No GPU needed.  A refactor that must not move device speed shows it this way."""
 import importlib.util
 import os
@@ -48,11 +50,33 @@ def _split(lines):
     return [x for x in lines if not x.startswith(".amdhsa_")], [x for x in lines if x.startswith(".amdhsa_")]
 
 
+def by_code(a, b, source):
+    pool = {}
+    for k in sorted(b):
+        pool.setdefault(tuple(b[k]), []).append(k)
+    gone = []
+    for k in sorted(a):
+        twins = pool.get(tuple(a[k]))
+        if twins:
+            twins.pop()
+        else:
+            gone.append(k)
+    new = sorted(k for twins in pool.values() for k in twins)
+    for k in gone:
+        print("other tree only:", k)
+    for k in new:
+        print("this tree only:", k)
+    print("%s: %d / %d kernels, %d paired by code, %d / %d unmatched" % (source, len(a), len(b), len(a) - len(gone), len(gone), len(new)))
+    return 1 if gone or new else 0
+
+
 def main():
-    args = [x for x in sys.argv[1:] if x != "--new-ok"]
-    new_ok = len(args) != len(sys.argv) - 1
+    args = [x for x in sys.argv[1:] if x not in ("--new-ok", "--by-code")]
+    new_ok = "--new-ok" in sys.argv
     other, source = args[0], (args[1] if len(args) > 1 else "ea_ceva_decode.hip")
     a, b = kernels(other, source), kernels(ROOT, source)
+    if "--by-code" in sys.argv:
+        return by_code(a, b, source)
     gone, new = sorted(set(a) - set(b)), sorted(set(b) - set(a))
     differ = sorted(k for k in set(a) & set(b) if _split(a[k])[0] != _split(b[k])[0])
     descr = sorted(k for k in set(a) & set(b) if k not in differ and a[k] != b[k])
