@@ -2,6 +2,7 @@
 // Argument validation and launch-parameter construction only; every kernel lives in its own
 // translation unit and is reached through a *_dispatch function.
 #include <stdlib.h>
+#include <cmath>
 #include "ea_window.h"
 
 namespace ea {
@@ -79,7 +80,7 @@ static Geo mk_geo(const ea_geom* g) {
 extern "C" {
 
 const char* ea_version(void) { return "ea_hip 0.1.0 gfx950"; }
-int32_t ea_abi_version(void) { return 23; }
+int32_t ea_abi_version(void) { return 24; }
 
 int32_t ea_window_bias_ld(const ea_geom* g) {
   WinTiling t;
@@ -2361,6 +2362,36 @@ int ea_ceva_sdecode_linear(int32_t M, int32_t K, int32_t N, const void* x, int32
   p.ldx = ldx; p.ldy = ldy; p.M = M; p.K = K; p.N = N; p.dtype = w_dtype;
   p.x_f32 = x_dtype == EA_F32; p.y_f32 = y_dtype == EA_F32;
   return ea::ceva_sdecode_linear(p, (hipStream_t)stream);
+}
+
+int ea_ceva_sdecode_linear_fused(int32_t M, int32_t K, int32_t N, const void* x, int32_t x_dtype, int64_t ldx,
+                                 const float* ln_gamma, const float* ln_beta, float ln_eps, const void* w, int32_t w_dtype,
+                                 const void* bias, int32_t act, const void* res, int32_t res_dtype, int64_t ldr, void* y,
+                                 int32_t y_dtype, int64_t ldy, void* stream) {
+  // what ea_ceva_sdecode_linear refuses, in its order ...
+  if (!x || !w || !y || (uintptr_t)x % 16 || (uintptr_t)w % 16 || (uintptr_t)y % 16 || (uintptr_t)bias % 16) return EA_E_BADARG;
+  if (w_dtype != EA_BF16 && w_dtype != EA_F16) return EA_E_BADARG;
+  if ((x_dtype != EA_F32 && x_dtype != w_dtype) || (y_dtype != EA_F32 && y_dtype != w_dtype)) return EA_E_BADARG;
+  if (M < 1 || K < 1 || N < 1 || ldx < K || ldy < N) return EA_E_BADARG;
+  if (ldx * (x_dtype == EA_F32 ? 4 : 2) % 16 || ldy * (y_dtype == EA_F32 ? 4 : 2) % 16) return EA_E_BADARG;
+  // ... then the prologue's and the epilogue's operands, and the geometry last
+  if ((ln_gamma == nullptr) != (ln_beta == nullptr)) return EA_E_BADARG;
+  if ((uintptr_t)ln_gamma % 16 || (uintptr_t)ln_beta % 16 || (uintptr_t)res % 16) return EA_E_BADARG;
+  if (ln_gamma && !(std::isfinite(ln_eps) && ln_eps > 0.f)) return EA_E_BADARG;
+  if (res) {
+    if (res_dtype != EA_F32 && res_dtype != w_dtype) return EA_E_BADARG;
+    if (ldr < N || ldr * (res_dtype == EA_F32 ? 4 : 2) % 16) return EA_E_BADARG;
+  }
+  if (x == y) return EA_E_BADARG;
+  if (M > EA_CEVA_LINEAR_MAX_ROWS || K % 32 || N % 16) return EA_E_UNSUPPORTED;
+  if (act != 0 && act != 1) return EA_E_UNSUPPORTED;
+  ea::DecLinFusedP p = {};
+  p.x = (const char*)x; p.w = (const char*)w; p.bias = (const char*)bias; p.y = (char*)y;
+  p.gamma = ln_gamma; p.beta = ln_beta; p.ln_eps = ln_gamma ? ln_eps : 0.f;
+  p.res = (const char*)res; p.res_f32 = res && res_dtype == EA_F32; p.ldr = res ? ldr : 0;
+  p.ldx = ldx; p.ldy = ldy; p.M = M; p.K = K; p.N = N; p.dtype = w_dtype; p.act = act;
+  p.x_f32 = x_dtype == EA_F32; p.y_f32 = y_dtype == EA_F32;
+  return ea::ceva_sdecode_linear_fused(p, (hipStream_t)stream);
 }
 
 }  // extern "C"

@@ -10,6 +10,10 @@ as WHOLE models (eager, autocast, DistributedDataParallel over RCCL) on syntheti
                            (vit/models/pvt_legacy.py:66-93,187-268; state_dict keys match)
   sequence.EncoderStack -- a fairseq-free Time x Batch x Channel encoder whose self-attention is the
                            adapter of fairseq/fairseq/modules/efficient_attention.py:107-132
+  sequence.DecoderStack -- the decoder-only LM of the wikitext-103 recipe around CausalEVAttention
+                           (fairseq/modules/transformer_layer.py:236-308 without encoder attention), with
+                           incremental decoding on the attention's static / rolling states: init_decoding,
+                           decode, generate
   trainer               -- one synthetic training step (forward, loss, backward, optimizer) eagerly or
                            captured in a hipGraph, single process or one process per GPU
 
@@ -18,3 +22,4 @@ Only the attention layers are this repo's product; everything else here is plain
 """
 from .vision import DeiTStack, PvTStack, deit_tiny, pvt_b2           # noqa: F401
 from .sequence import EncoderStack, wmt_en_de_encoder                # noqa: F401
+from .sequence import DecoderLayer, DecoderStack, wikitext103_decoder   # noqa: F401

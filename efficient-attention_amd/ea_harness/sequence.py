@@ -5,12 +5,19 @@ builds the attention from (attn_name, attn_args) with dim / num_heads / qkv_bias
 filled in, takes `query [T, B, C]` and `key_padding_mask [B, T]` (1 = pad), calls the module batch-first
 and hands back `[T, B, C]`.  EncoderLayer is the post-norm residual layer of transformer_wmt_en_de
 (self-attention, LayerNorm, ReLU feed-forward, LayerNorm).  Parameter names under `self_attn.attn.*`
-are the attention module's own, as in the reference adapter."""
+are the attention module's own, as in the reference adapter.
+
+DecoderLayer / DecoderStack are the decoder-only language model of the wikitext-103 recipe around `CausalEVAttention`
+(fairseq/modules/transformer_layer.py:236-308 without the encoder attention), with incremental decoding on the attention's
+static and rolling states: `init_decoding`, `decode`, `generate`."""
+import argparse
+import contextlib
+
 import torch
 import torch.nn as nn
 import torch.nn.functional as F
 
-from efficient_attention import AttentionFactory
+from efficient_attention import AttentionFactory, CausalEVAttention
 
 
 class TimeFirstSelfAttention(nn.Module):
@@ -97,3 +104,318 @@ class EncoderStack(nn.Module):
 def wmt_en_de_encoder(attn_name, attn_args=None, vocab=32768, **kw):
     """Encoder half of transformer_wmt_en_de (512 / 2048 / 8 heads / 6 layers, post-norm)."""
     return EncoderStack(vocab, 512, 2048, 8, 6, attn_name, attn_args, **kw)
+
+
+# ---- the decoder ----------------------------------------------------------------------------------------------------------------
+_FUSED = "ea_ceva_sdecode_linear_fused"
+_FUSED_MAX_ROWS = 64         # EA_CEVA_LINEAR_MAX_ROWS of include/ea_hip.h
+
+
+def _fused_linear(x2, ln, weight, bias, act, res2, y2):
+    """y2 = act(LN(x2) weight^T + bias) + res2 on ea_ceva_sdecode_linear_fused.  x2 [M <= 64, K] fp32 or the weight's type;
+    ln: an nn.LayerNorm over K or None; weight [N, K], bias [N] 16-bit; act 0 | 1 (ReLU); res2 [M, N] fp32 or the weight's
+    type, or None, and may be y2 itself; y2 [M, N] fp32 or the weight's type -> y2."""
+    from efficient_attention import _native as nv
+
+    def code(t):
+        return nv.EA_F32 if t.dtype == torch.float32 else nv.io_dtype(t)
+    gamma = beta = None
+    eps = 0.0
+    if ln is not None:                                  # (fp32 masters are read where they are)
+        gamma, beta, eps = ln.weight.detach(), ln.bias.detach(), ln.eps
+        if gamma.dtype != torch.float32:
+            gamma, beta = gamma.float(), beta.float()
+    nv.call(_FUSED, x2.shape[0], weight.shape[1], weight.shape[0], nv.ptr(x2), code(x2), x2.stride(0),
+            nv.ptr(gamma), nv.ptr(beta), eps, nv.ptr(weight), nv.io_dtype(weight), nv.ptr(bias), act,
+            nv.ptr(res2), 0 if res2 is None else code(res2), 0 if res2 is None else res2.stride(0),
+            nv.ptr(y2), code(y2), y2.stride(0), nv.stream())
+    return y2
+
+
+class DecoderLayer(nn.Module):
+    """fairseq's TransformerDecoderLayerBase without encoder attention, under its member names: `self_attn` (a
+    CausalEVAttention built as transformer_layer.py:298-308 builds it, no adapter in between), `self_attn_layer_norm`, `fc1`,
+    ReLU, `fc2`, `final_layer_norm`; pre-norm (the wikitext-103 recipe) or post-norm."""
+
+    def __init__(self, embed_dim, ffn_dim, num_heads, attn_args=None, dropout=0.1, attention_dropout=0.0,
+                 activation_dropout=0.0, normalize_before=True):
+        super().__init__()
+        self.embed_dim, self.ffn_dim = embed_dim, ffn_dim
+        if not isinstance(attn_args, argparse.Namespace):
+            attn_args = argparse.Namespace(**dict(attn_args or {}))
+        self.self_attn = CausalEVAttention(embed_dim, num_heads, dropout=attention_dropout, self_attention=True,
+                                           q_noise=0.0, qn_block_size=8, attn_args=attn_args)
+        self.dropout_module = nn.Dropout(dropout)
+        self.activation_dropout_module = nn.Dropout(activation_dropout)
+        self.normalize_before = normalize_before
+        self.self_attn_layer_norm = nn.LayerNorm(embed_dim)
+        self.fc1 = nn.Linear(embed_dim, ffn_dim)
+        self.fc2 = nn.Linear(ffn_dim, embed_dim)
+        self.final_layer_norm = nn.LayerNorm(embed_dim)
+
+    def forward(self, x, key_padding_mask=None):
+        """The full causal path: x [T, B, C], key_padding_mask [B, T] (1 = pad) -> [T, B, C]."""
+        return self._feed_forward(self._attend(x, key_padding_mask, None), None)
+
+    def _attend(self, x, key_padding_mask, incremental_state):
+        res = x
+        if self.normalize_before:
+            x = self.self_attn_layer_norm(x)
+        x, _ = self.self_attn(x, x, x, key_padding_mask=key_padding_mask, incremental_state=incremental_state,
+                              need_weights=False)
+        x = res + self.dropout_module(x)
+        return x if self.normalize_before else self.self_attn_layer_norm(x)
+
+    def _feed_forward(self, x, held):
+        """x [T, B, C] behind the attention block -> the layer's output.  held: None -- the layer's own modules; else the
+        16-bit (w1, b1, w2, b2) of a decoding state: at most 64 rows run as two ea_ceva_sdecode_linear_fused launches (the
+        LayerNorm of a pre-norm layer in the first one's prologue, ReLU in its epilogue, the residual in the second one's:
+        fc2's fp32 sums meet the residual unrounded, one rounding fewer than the full path), more rows as the library GEMM
+        on the held operands."""
+        if held is None:
+            res = x
+            if self.normalize_before:
+                x = self.final_layer_norm(x)
+            x = self.fc2(self.activation_dropout_module(F.relu(self.fc1(x))))
+            x = res + self.dropout_module(x)
+            return x if self.normalize_before else self.final_layer_norm(x)
+        w1, b1, w2, b2 = held
+        T, B, C = x.shape
+        if x.dtype not in (torch.float32, w1.dtype):
+            x = x.float()
+        if T * B <= _FUSED_MAX_ROWS:
+            # (x is this step's own tensor -- the sum behind the attention, or its LayerNorm: the residual stream in place)
+            x2 = x.contiguous().view(T * B, C)
+            h = torch.empty((T * B, self.ffn_dim), dtype=w1.dtype, device=x.device)
+            _fused_linear(x2, self.final_layer_norm if self.normalize_before else None, w1, b1, 1, None, h)
+            _fused_linear(h, None, w2, b2, 0, x2, x2)
+            x = x2.view(T, B, C)
+        else:
+            res = x
+            if self.normalize_before:
+                x = self.final_layer_norm(x)
+            with torch.autocast(device_type="cuda", enabled=False):
+                h = F.relu(F.linear(x.to(w1.dtype), w1, b1))
+                x = res + F.linear(h, w2, b2)
+        return x if self.normalize_before else self.final_layer_norm(x)
+
+
+class DecodingState:
+    """What `DecoderStack.init_decoding` returns: `incremental` (the incremental state every layer's attention keeps its
+    static or rolling state in, under its own key), `ffn` (per layer the held 16-bit (fc1.weight, fc1.bias, fc2.weight,
+    fc2.bias), or None without hold_weights) and the arguments it was made with (`options`)."""
+
+    def __init__(self, incremental, ffn, options):
+        self.incremental, self.ffn, self.options = incremental, ffn, options
+
+    @property
+    def hold_weights(self):
+        return self.ffn is not None
+
+
+class DecoderStack(nn.Module):
+    """Decoder-only language model shaped like EncoderStack: token embedding (scaled) + sinusoidal positions -> `layers`
+    DecoderLayers (-> a final LayerNorm with final_norm=True) -> [T, B, C]; `logits` is the tied output projection.
+    fairseq's adaptive input and adaptive softmax (the wikitext-103 recipe's embedding and output layers) are out of scope:
+    a plain tied embedding stands in for both.
+
+    Incremental decoding runs on the attention's static / rolling states (CausalEVAttention.init_*_decoding):
+        state = stack.init_decoding(B, max_tokens, torch.bfloat16, "cuda")
+        rows = stack.decode(tokens [T, B], state)              # [T, B, C], prompts and single tokens alike
+        new = stack.generate(prompt [B, P], n_new, state)      # greedy, one captured step replayed"""
+
+    def __init__(self, vocab, embed_dim, ffn_dim, num_heads, layers, attn_args=None, dropout=0.1, attention_dropout=0.0,
+                 activation_dropout=0.0, normalize_before=True, final_norm=False, max_positions=4096, pad_idx=1):
+        super().__init__()
+        self.embed_dim, self.pad_idx = embed_dim, pad_idx
+        self.embed_tokens = nn.Embedding(vocab, embed_dim, padding_idx=pad_idx)
+        nn.init.normal_(self.embed_tokens.weight, mean=0, std=embed_dim ** -0.5)
+        nn.init.constant_(self.embed_tokens.weight[pad_idx], 0)
+        self.register_buffer("positions", EncoderStack._sinusoid(max_positions, embed_dim), persistent=False)
+        self.dropout = nn.Dropout(dropout)
+        self.layers = nn.ModuleList([DecoderLayer(embed_dim, ffn_dim, num_heads, attn_args, dropout, attention_dropout,
+                                                  activation_dropout, normalize_before) for _ in range(layers)])
+        self.layer_norm = nn.LayerNorm(embed_dim) if final_norm else None
+
+    def forward(self, tokens, key_padding_mask=None):                      # tokens [B, T] int64, mask [B, T] (1 = pad)
+        B, T = tokens.shape
+        x = self.embed_tokens(tokens) * (self.embed_dim ** 0.5) + self.positions[:T].to(self.embed_tokens.weight.dtype)
+        x = self.dropout(x).transpose(0, 1)                                 # [T, B, C]
+        for layer in self.layers:
+            x = layer(x, key_padding_mask)
+        return x if self.layer_norm is None else self.layer_norm(x)
+
+    def logits(self, x):                                                    # [T, B, C] -> [T, B, vocab]
+        return F.linear(x, self.embed_tokens.weight)
+
+    # ---- incremental decoding -----------------------------------------------------------------------------------------------
+    def init_decoding(self, batch_size, max_tokens, dtype, device, rolling=True, hold_weights=True, per_sequence=False,
+                      landmark_splits=1, compact_landmarks=False, max_step_tokens=None):
+        """One static (rolling=False) or rolling decoding state per layer's attention, made by `init_static_decoding` /
+        `init_rolling_decoding` with `per_sequence`, `landmark_splits`, `compact_landmarks` (and, rolling, `max_step_tokens`)
+        handed on and `hold_projections=hold_weights` -> a DecodingState.  With hold_weights (a 16-bit `dtype` only: fp32 is
+        refused with the attention's ValueError) the state also holds 16-bit copies of every layer's fc1 / fc2 weights and
+        biases, 2 (C F + F + F C + C) bytes per layer, taken here once: a capture fixes the weights, and
+        `refresh_decoding_weights` re-reads them.  `max_tokens` may not pass the position table."""
+        if hold_weights:
+            self.layers[0].self_attn._check_hold_projections(True, dtype)
+        if int(max_tokens) > self.positions.shape[0]:
+            raise ValueError("max_tokens %d passes the %d positions of the table (max_positions)"
+                             % (int(max_tokens), self.positions.shape[0]))
+        options = dict(batch_size=int(batch_size), max_tokens=int(max_tokens), dtype=dtype, device=device, rolling=bool(rolling),
+                       hold_weights=bool(hold_weights), per_sequence=bool(per_sequence), landmark_splits=landmark_splits,
+                       compact_landmarks=bool(compact_landmarks), max_step_tokens=max_step_tokens)
+        opt = dict(per_sequence=per_sequence, landmark_splits=landmark_splits, hold_projections=hold_weights,
+                   compact_landmarks=compact_landmarks)
+        incremental = {}
+        for layer in self.layers:
+            if rolling:
+                layer.self_attn.init_rolling_decoding(incremental, batch_size, max_tokens, dtype, device,
+                                                      max_step_tokens=max_step_tokens, **opt)
+            else:
+                layer.self_attn.init_static_decoding(incremental, batch_size, max_tokens, dtype, device, **opt)
+        ffn = None
+        if hold_weights:
+            ffn = [tuple(torch.empty(p.shape, dtype=dtype, device=device)
+                         for p in (layer.fc1.weight, layer.fc1.bias, layer.fc2.weight, layer.fc2.bias)) for layer in self.layers]
+        state = DecodingState(incremental, ffn, options)
+        self._load_held_ffn(state)
+        return state
+
+    def _load_held_ffn(self, state):
+        if state.ffn is None:
+            return
+        with torch.no_grad():
+            for layer, held in zip(self.layers, state.ffn):
+                for dst, src in zip(held, (layer.fc1.weight, layer.fc1.bias, layer.fc2.weight, layer.fc2.bias)):
+                    dst.copy_(src)                      # (rounded to nearest even, in place: every data_ptr() stays)
+
+    def refresh_decoding_weights(self, state):
+        """Re-read the parameters into what the state holds of them, in place and by device ops only: every layer's attention
+        (`CausalEVAttention.refresh_decoding_weights`) and the held fc1 / fc2.  A step captured before sees the new weights."""
+        for layer in self.layers:
+            layer.self_attn.refresh_decoding_weights(state.incremental)
+        self._load_held_ffn(state)
+        return state
+
+    def reorder_decoding_state(self, state, new_order):
+        for layer in self.layers:
+            layer.self_attn.reorder_incremental_state(state.incremental, new_order)
+        return state
+
+    def reset_decoding_rows(self, state, rows):
+        for layer in self.layers:
+            layer.self_attn.reset_decoding_rows(state.incremental, rows)
+        return state
+
+    def decoding_state_nbytes(self, state):
+        """Bytes of every layer's attention state and of the held feed-forward weights."""
+        n = sum(layer.self_attn.decoding_state_nbytes(state.incremental) for layer in self.layers)
+        return n + sum(t.numel() * t.element_size() for held in (state.ffn or ()) for t in held)
+
+    def decoding_overflowed(self, state):
+        """True once a step of any layer would have passed the state's capacity.  Reads device flags back."""
+        return any(layer.self_attn.static_decoding_overflowed(state.incremental) for layer in self.layers)
+
+    def decode(self, tokens, state, key_padding_mask=None):
+        """One decoding step: tokens [T, B] int64 (a prompt, a single token, a short verify step) -> [T, B, C], the rows
+        `forward` gives for these positions.  Positions are gathered from the sinusoid table by the DEVICE counts of the first
+        layer's state (`decoding_positions_tensor`): no read-back, so the step can be captured, and a row of a per-sequence
+        state gets its own positions.  key_padding_mask: handed to every attention (a per-sequence state: a row's tokens are
+        those before its first flag).  Every launch is a device op; under autocast the residual stream stays fp32 as in
+        `forward`.  On a state made with hold_weights a step of T B <= 64 rows runs each layer as
+            LayerNorm, ea_ceva_sdecode_linear, the attention's launches, ea_ceva_sdecode_linear, add,
+            ea_ceva_sdecode_linear_fused (LayerNorm, fc1, ReLU), ea_ceva_sdecode_linear_fused (fc2, residual, in place)
+        (post-norm: the two LayerNorms behind the sums, by the framework); a larger step runs the library GEMM on the held
+        operands; without hold_weights the feed-forward is the layer's own modules."""
+        if self.training:
+            raise NotImplementedError("incremental decoding in training mode")
+        T, B = tokens.shape
+        attn0 = self.layers[0].self_attn
+        pos = attn0.decoding_positions_tensor(state.incremental)             # [1] or [B] int32, on the device
+        idx = pos.to(torch.long).view(1, -1) + torch.arange(T, device=pos.device).view(T, 1)
+        idx = idx.clamp_(max=self.positions.shape[0] - 1).expand(T, B)       # (a step past the table overflows the state too)
+        w = self.embed_tokens.weight
+        x = self.embed_tokens(tokens) * (self.embed_dim ** 0.5) + self.positions[idx].to(w.dtype)
+        for i, layer in enumerate(self.layers):
+            x = layer._attend(x, key_padding_mask, state.incremental)
+            x = layer._feed_forward(x, None if state.ffn is None else state.ffn[i])
+        return x if self.layer_norm is None else self.layer_norm(x)
+
+    def generate(self, prompt, n_new, state=None, graph=True, return_rows=False):
+        """Greedy decoding: prompt [B, P] int64 -> the n_new tokens that follow, [B, n_new] (return_rows: and the final-layer
+        rows they were read from, [n_new, B, C]).  state: a fresh DecodingState of this stack (default: rolling, held weights,
+        the autocast dtype).  The prompt is fed eagerly in one `decode`; on a per-sequence state it may be ragged and
+        right-padded with `pad_idx`, and each row continues behind its own last token.
+        graph=True: a warm-up step runs on a side stream, on a scratch state made with the same options, so that the state
+        itself is untouched; then ONE single-token step -- embedding, layers, logits, argmax and the copy of the new token into
+        the step's static input, device ops only -- is captured and replayed n_new - 1 times.  graph=False runs the same steps
+        eagerly: the same tokens and rows bit for bit.  An overflow flagged by any layer raises after the loop."""
+        if self.training:
+            raise NotImplementedError("incremental decoding in training mode")
+        B, P = prompt.shape
+        n_new = int(n_new)
+        if n_new < 1:
+            raise ValueError("generate needs n_new >= 1, got %d" % n_new)
+        amp = torch.is_autocast_enabled()
+        ctx = torch.autocast("cuda", dtype=torch.get_autocast_dtype("cuda"), cache_enabled=False) if amp \
+            else contextlib.nullcontext()                        # (a capture may not use autocast's weight-cast cache)
+        with torch.no_grad(), ctx:
+            if state is None:
+                dtype = torch.get_autocast_dtype("cuda") if amp else self.embed_tokens.weight.dtype
+                state = self.init_decoding(B, P + n_new, dtype, prompt.device, hold_weights=dtype != torch.float32)
+            per_seq = state.options["per_sequence"]
+            mask = prompt.eq(self.pad_idx) if per_seq else None
+            x = self.decode(prompt.t(), state, mask)                         # [P, B, C]
+            if per_seq:                                                      # the row of each sequence's last token
+                n_b = P - mask.ne(0).to(torch.int32).cumsum(1).ne(0).sum(1)
+                last = x[(n_b - 1).clamp_(min=0), torch.arange(B, device=x.device)].unsqueeze(0)
+            else:
+                last = x[P - 1:P]
+            tok_in = self.logits(last).argmax(-1)                            # [1, B]: the step's static input
+            out = torch.empty((B, n_new), dtype=torch.long, device=prompt.device)
+            rows = torch.empty((n_new,) + tuple(last.shape[1:]), dtype=last.dtype, device=prompt.device) if return_rows else None
+            out[:, 0] = tok_in[0]
+            if rows is not None:
+                rows[0] = last[0]
+
+            def step(st):
+                y = self.decode(tok_in, st)
+                tok_in.copy_(self.logits(y).argmax(-1))
+                return y
+            g = None
+            if graph and n_new > 1:
+                scratch = self.init_decoding(**dict(state.options, max_tokens=1))
+                first = tok_in.clone()
+                side = torch.cuda.Stream()
+                side.wait_stream(torch.cuda.current_stream())
+                with torch.cuda.stream(side):
+                    step(scratch)
+                torch.cuda.current_stream().wait_stream(side)
+                tok_in.copy_(first)
+                del scratch
+                g = torch.cuda.CUDAGraph()
+                with torch.cuda.graph(g):
+                    y = step(state)
+            for i in range(1, n_new):
+                if g is None:
+                    y = step(state)
+                else:
+                    g.replay()
+                out[:, i] = tok_in[0]
+                if rows is not None:
+                    rows[i] = y[0]
+            if self.decoding_overflowed(state):
+                raise RuntimeError("the decoding state overflowed: a step passed its %d tokens (init_decoding(max_tokens=...))"
+                                   % state.options["max_tokens"])
+        return (out, rows) if return_rows else out
+
+
+def wikitext103_decoder(attn_args=None, vocab=32768, **kw):
+    """The decoder of the wikitext-103 recipe (transformer_lm_wiki103: 1024 / 4096 / 8 heads / 16 layers, pre-norm, no final
+    decoder norm) around CausalEVAttention; attn_args default to the recipe's (window 128, chunks of 8, causal, adaptive 'qk',
+    T5 bias).  Adaptive input and adaptive softmax are out of scope (see DecoderStack)."""
+    if attn_args is None:
+        attn_args = dict(window_size=128, chunk_size=8, causal=True, adaptive_proj="qk", use_t5_rpe=True, num_chunks=None,
+                         overlap_window=False)
+    return DecoderStack(vocab, 1024, 4096, 8, 16, attn_args, normalize_before=True, final_norm=False, **kw)

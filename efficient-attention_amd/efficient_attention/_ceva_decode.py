@@ -394,6 +394,13 @@ class CevaDecoding:
         buf, _ = self._static_buffer(incremental_state, "decoding_positions")
         return buf["pos"].expand(buf["qkv"].shape[0]).cpu().clone()
 
+    def decoding_positions_tensor(self, incremental_state):
+        """The DEVICE tensor a static or rolling state counts in -- `pos [1]` int32, or `[B]` on a per-sequence state -- itself,
+        not a copy: no read-back, so a captured step may index with it (the positions of a decoder's new tokens); the steps
+        advance it.  Raises on a dynamic state, as `decoding_positions` does."""
+        buf, _ = self._static_buffer(incremental_state, "decoding_positions_tensor")
+        return buf["pos"]
+
     def reset_decoding_rows(self, incremental_state, rows):
         """Restart batch rows of a per-sequence state: `pos` and `status` of `rows` (indices: a sequence of ints or an
         integer tensor) back to 0, in place and by device ops only -- between replays, or captured itself when `rows` is a

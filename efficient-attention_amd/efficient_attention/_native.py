@@ -22,7 +22,7 @@ class ea_t4(ctypes.Structure):
                 ("sn", ctypes.c_int64)]
 
 
-ABI_VERSION = 23         # ea_abi_version() of include/ea_hip.h this file mirrors
+ABI_VERSION = 24         # ea_abi_version() of include/ea_hip.h this file mirrors
 
 
 class ea_geom(ctypes.Structure):
@@ -245,6 +245,7 @@ SIGNATURES = {
     "ea_ceva_sdecode_merge": [_SDG, _T, _I, _P, _P],
     "ea_ceva_sdecode_advance": [_SDG, _P],
     "ea_ceva_sdecode_linear": [_I, _I, _I, _P, _I, _L, _P, _I, _P, _P, _I, _L, _P],
+    "ea_ceva_sdecode_linear_fused": [_I, _I, _I, _P, _I, _L, _P, _P, _F, _P, _I, _P, _I, _P, _I, _L, _P, _I, _L, _P],
     "ea_softmax_attn_fwd": [_I, _I, _I, _I, _I, _F, _T, _T, _T, _P, _T, _P, _P, _F, _I, _P],
     "ea_softmax_sample": [_I, _I, _I, _I, _I, _F, _T, _T, _P, _P, _P],
     "ea_softmax_attn_bwd": [_I, _I, _I, _I, _I, _F, _T, _T, _T, _P, _T, _T, _P, _P, _T, _T, _T, _P, _F, _I, _P],

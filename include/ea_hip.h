@@ -1068,6 +1068,25 @@ int ea_ceva_sdecode_linear(int32_t M, int32_t K, int32_t N, const void* x, int32
                            const void* w, int32_t w_dtype, const void* bias, void* y, int32_t y_dtype, int64_t ldy,
                            void* stream);
 
+/* ABI 24, the feed-forward of a decoder layer's short step on held weights (ea_harness DecoderStack.decode;
+ * ea_ceva_decode_linear.hip): ea_ceva_sdecode_linear with a LayerNorm in front and an activation and a residual behind,
+ *   y[m, n] = round_y( act( sum_k round_w(LN(x)[m, k]) w[n, k] + bias[n] ) + res[m, n] )
+ * in its envelope (1 <= M <= 64, K % 32 == 0, N % 16 == 0).  ln_gamma, ln_beta: fp32 [K], both NULL = no LayerNorm; else every
+ * workgroup computes (mean, rstd) of the M rows over K in fp32 -- two passes, biased variance, rsqrt(var + ln_eps), as
+ * ea_layernorm_fwd -- and an operand is (x - mean) rstd gamma + beta in fp32, rounded once to w_dtype as it is loaded.
+ * act: 0 none, 1 relu.  res: NULL, or [M, ldr] rows of res_dtype = EA_F32 | w_dtype (res_dtype and ldr are not read without
+ * res).  Sums, bias, activation and the residual add are fp32, applied by the thread that stores the element after the
+ * fixed-order sum over the waves: no atomics, bitwise reproducible.  res may be exactly y (same pointer, dtype, stride: an
+ * in-place residual stream); any other overlap of res and y, and x == y, are not supported.
+ * Refuses what ea_ceva_sdecode_linear refuses, with its codes, and besides EA_E_BADARG: exactly one of ln_gamma / ln_beta;
+ * ln_gamma, ln_beta or res not 16-byte aligned; ln_eps not finite or <= 0 with LayerNorm on; res_dtype neither EA_F32 nor
+ * w_dtype; ldr < N or a residual row stride that is no multiple of 16 bytes; x == y.  EA_E_UNSUPPORTED: act outside {0, 1}.
+ * Bad arguments are decided before the geometry, everything before any launch. */
+int ea_ceva_sdecode_linear_fused(int32_t M, int32_t K, int32_t N, const void* x, int32_t x_dtype, int64_t ldx,
+                                 const float* ln_gamma, const float* ln_beta, float ln_eps, const void* w, int32_t w_dtype,
+                                 const void* bias, int32_t act, const void* res, int32_t res_dtype, int64_t ldr, void* y,
+                                 int32_t y_dtype, int64_t ldy, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
