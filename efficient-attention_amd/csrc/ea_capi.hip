@@ -36,7 +36,8 @@ int proj_rs_pool_supported(int K, int NO, int B, int gh, int gw, int r);
 int proj_rs_dispatch(int dtype, const void* a, int a_f32, const float* w, const float* bias, void* y, void* a_cast, int rows,
                      long lda, long ldy, hipStream_t st, int B, int gh, int gw, int r, float* pq, float* pk, void* w_cast,
                      const void* wsw);
-int w192_prepare_dispatch(int dtype, const float* wq, const float* wp, void* w16q, void* wsw, void* w16p, void* w16pT, hipStream_t st);
+int w192_prepare_dispatch(int dtype, const float* wq, const float* wp, void* w16q, void* wsw, void* w16p, void* w16pT, void* wtsw,
+                          hipStream_t st);
 int dgrad_rs_supported(int K, int NO);
 int dgrad_fin_launch(int dtype, const void* dqkv, long ldy, const void* qkv, long ldq, const void* w, int w_f32, void* dx, int dx_f32,
                      long ldx, int B, int gh, int gw, int pool_r, int C, float scale, const float* qbar, const float* uq,
@@ -80,7 +81,7 @@ static Geo mk_geo(const ea_geom* g) {
 extern "C" {
 
 const char* ea_version(void) { return "ea_hip 0.1.0 gfx950"; }
-int32_t ea_abi_version(void) { return 24; }
+int32_t ea_abi_version(void) { return 25; }
 
 int32_t ea_window_bias_ld(const ea_geom* g) {
   WinTiling t;
@@ -1487,7 +1488,16 @@ int ea_linear_w192_prepare(int32_t dtype, const float* wq, const float* wp, void
       ((uintptr_t)w16p & 15) || ((uintptr_t)w16pT & 15))
     return EA_E_BADARG;
   if (wp && (!w16p || !w16pT)) return EA_E_BADARG;
-  return w192_prepare_dispatch(dtype, wq, wp, w16q, wq_sw, w16p, w16pT, (hipStream_t)stream);
+  return w192_prepare_dispatch(dtype, wq, wp, w16q, wq_sw, w16p, w16pT, nullptr, (hipStream_t)stream);
+}
+
+int ea_linear_w192_prepare_t(int32_t dtype, const float* wq, const float* wp, void* w16q, void* wq_sw, void* w16p, void* w16pT,
+                             void* wqT_sw, void* stream) {
+  if (!wq || !w16q || !wq_sw || !wqT_sw || ((uintptr_t)wq & 15) || ((uintptr_t)wp & 15) || ((uintptr_t)w16q & 15) ||
+      ((uintptr_t)wq_sw & 15) || ((uintptr_t)w16p & 15) || ((uintptr_t)w16pT & 15) || ((uintptr_t)wqT_sw & 15))
+    return EA_E_BADARG;
+  if (wp && (!w16p || !w16pT)) return EA_E_BADARG;
+  return w192_prepare_dispatch(dtype, wq, wp, w16q, wq_sw, w16p, w16pT, wqT_sw, (hipStream_t)stream);
 }
 
 int ea_linear_wsw(int32_t dtype, int32_t rows, int32_t B, int32_t gh, int32_t gw, int32_t r, const void* a, int32_t a_f32, int64_t lda,

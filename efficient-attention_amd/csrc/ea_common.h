@@ -15,6 +15,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include "../../include/ea_hip.h"
+#include "ea_lds_swizzle.h"
 
 // ---- dev-only phase profiling (-DEA_PROFILE, tools/build_prof_lib.sh): thread 0 of workgroup 0
 // stamps s_memtime into p.prof[i]; the dispatcher prints the deltas.  Compiled out of the product.
@@ -341,10 +342,20 @@ template <int D> struct LaneOff {
 // D rows <-> channels 16 dt + 4 g + r: a lane owns four 4-channel pieces 16 channels apart instead of 16 contiguous
 // channels; quad_transpose() below moves the pieces between the four lanes of a token (8 v_permlane swaps on packed
 // data) so that stores stay 32 contiguous bytes per lane.
-EA_DEV int phi2(int row) { return (((row >> 1) & 3) << 1) | ((row ^ (row >> 3)) & 1); }
+EA_DEV int phi2(int row) { return swz_phi2(row); }
 template <int D> EA_DEV int lds_off2(int row, int chunk16) {
   static_assert(D == 64, "lds_off2: 128-byte rows only");
   return row * (D * 2) + ((chunk16 ^ phi2(row)) << 4);
+}
+// The 32-token activation tiles of the register-resident projection kernels (ea_proj_rs.hip, ea_dgrad_rs.hip) are read with
+// chunk 4 (ks & 1) + g of row li -- a k-step is 32 contiguous channels, as in lin_kernel -- which phi2 serves in 8 LDS cycles,
+// not 4 (two rows of a lane group on every 16-byte slot: SQ_LDS_BANK_CONFLICT / SQ_LDS_IDX_ACTIVE 0.38 and 0.32 in those
+// kernels, 0.00 - 0.05 elsewhere).  psi (ea_lds_swizzle.h) is conflict-free for that mapping AND for everything phi2 serves;
+// tools/lds_bank_model.cpp evaluates both, tests/test_lds_swizzle_model.py holds the counts.
+EA_DEV int psi(int row) { return swz_psi(row); }
+template <int D> EA_DEV int lds_off3(int row, int chunk16) {
+  static_assert(D == 64, "lds_off3: 128-byte rows only");
+  return row * (D * 2) + ((chunk16 ^ psi(row)) << 4);
 }
 template <int D> struct LaneOff2 {
   static constexpr int ROWB = D * 2, KS = D / 32, DT = D / 16;

@@ -6,11 +6,14 @@
 // holds W^T in its registers -- wave w owns the output columns 16 w .. 16 w + 15 as MFMA A operands over all 576 contraction
 // slots, 72 VGPRs per lane -- and the dqkv rows stream through LDS exactly once: a 32-token tile (36 KB) is fetched by all 768
 // threads (three 16-byte chunks each), double-buffered, one barrier per tile; every wave reads the whole tile as B operands
-// (ds_read_b128, phi2 layout per 64-channel slab) and forms its [16 x 32] piece transposed, D[column][token] -> 16-byte fp32
+// (ds_read_b128, psi layout per 64-channel slab) and forms its [16 x 32] piece transposed, D[column][token] -> 16-byte fp32
 // stores (4 consecutive columns of one token per lane).
 // The weight reaches the registers TRANSPOSED without a transposed copy in memory: the [576][192] matrix (fp32 master, rounded
 // on the way, or the 16-bit copy the forward projection left) passes LDS in 18 pieces of 32 rows, stored row-permuted so that
 // two ds_read_b64_tr_b16 per piece hand lane (g, li) the values W[32 p + 8 g .. + 7][16 w + li] -- its eight k-slots.
+// WT: the weight comes PREPARED in that lane order (w192_prepare_kernel's fifth image: piece (wave, p, lane) = those eight
+// values, 16 bytes): 18 independent 16-byte loads per lane, in flight with the first tile's rows -- no LDS, no barrier.  (The
+// staging through LDS is 18 store / barrier / transposed-read rounds before the first tile: ~5 us of every launch.)
 #include <stdlib.h>
 #include "ea_common.h"
 
@@ -18,7 +21,7 @@ namespace ea {
 
 struct DgP {
   const char* dy;       // [rows, 576] element type, row stride ldy elements
-  const char* w;        // [576, 192] fp32 master weight (WF32) or element type
+  const char* w;        // [576, 192] fp32 master weight (WF32) or element type; WT: the prepared image, 12 x 18 x 64 x 16 bytes
   char* dx;             // [rows, 192] fp32 (OF32) or element type, row stride ldx elements
   int rows, ntiles;
   long ldy, ldx;
@@ -30,10 +33,13 @@ constexpr int DG_TILE = DG_SLABS * DG_TOK * 128;          // 36 KB
 constexpr int DG_PIECE = 32 * DG_NO * 2;                  // one 32-row weight piece, 16-bit: 12 KB
 constexpr int DG_LDS = 2 * DG_TILE;
 
-EA_DEV int dg_off(int slab, int tok, int chunk16) { return slab * (DG_TOK * 128) + lds_off2<64>(tok, chunk16); }
+EA_DEV int dg_off(int slab, int tok, int chunk16) { return slab * (DG_TOK * 128) + lds_off3<64>(tok, chunk16); }
 
-template <typename E, bool WF32, bool OF32>
-__global__ __launch_bounds__(DG_WAVES * 64, 3) void dgrad_rs_kernel(const DgP p) {
+EA_DEV size_t dg_wt_off(int wave, int ks, int lane) { return ((size_t)(wave * DG_KT + ks) * 64 + lane) * 16; }
+
+template <typename E, bool WF32, bool OF32, bool WT>
+EA_DEV void dgrad_rs_body(const DgP& p) {
+  static_assert(!(WT && WF32), "the prepared image is in the element type");
   extern __shared__ __attribute__((aligned(16))) char smem[];
   char* const tile0 = smem;
   char* const tile1 = smem + DG_TILE;
@@ -61,7 +67,10 @@ __global__ __launch_bounds__(DG_WAVES * 64, 3) void dgrad_rs_kernel(const DgP p)
   // writes after its first barrier).  Row o of a piece is parked at row rho(o) = ((o >> 2) & 1) 16 + (o >> 3) 4 + (o & 3):
   // the two transposed reads of lane-row g then cover o = 8 g .. 8 g + 3 and 8 g + 4 .. 8 g + 7, in k-slot order. ----
   typename E::x8 wr[DG_KT];
-  {
+  if constexpr (WT) {
+#pragma unroll
+    for (int ks = 0; ks < DG_KT; ++ks) wr[ks] = as_x8<E>(ldg16(p.w + dg_wt_off(wave, ks, lane)));
+  } else {
     const int o_l = tid / 24, c = tid - o_l * 24;                     // 32 rows x 24 chunks of 8 columns = 768 slots
     const int rho = ((o_l >> 2) & 1) * 16 + (o_l >> 3) * 4 + (o_l & 3);
     const int wofs = rho * (DG_NO * 2) + c * 16;
@@ -131,6 +140,11 @@ __global__ __launch_bounds__(DG_WAVES * 64, 3) void dgrad_rs_kernel(const DgP p)
   }
 }
 
+template <typename E, bool WF32, bool OF32>
+__global__ __launch_bounds__(DG_WAVES * 64, 3) void dgrad_rs_kernel(const DgP p) { dgrad_rs_body<E, WF32, OF32, false>(p); }
+template <typename E, bool OF32>
+__global__ __launch_bounds__(DG_WAVES * 64, 3) void dgrad_rs_wt_kernel(const DgP p) { dgrad_rs_body<E, false, OF32, true>(p); }
+
 // ------------------------------------------------------------------------------------------------------------------
 // dgrad_fin_kernel (round 5): the LAST corrections of dq / dk and the input gradient in ONE pass over the gradient rows.
 //   LARA (lara.py:201-246, 43,48,145-151 differentiated; until now ea_lara_bwd_finish, 242 MB / 53 us at cfg3, followed by
@@ -168,8 +182,9 @@ constexpr int DG_FIN_LDS = 2 * DG_TILE + 2 * DG_QT + 6 * DG_LMR + 3 * 64 * 4;
 // -- ea_proj_rs.hip walks the forward the same way).  In row-major order a 32-token tile of a 28-wide grid touches 8-9 cells
 // per head and side: 12 KB of pooled-gradient rows per tile next to the tile's own 48 KB, a quarter more through the CU's
 // L2 port (measured with the reads compiled out: 86 -> 76 us at cfg3); cell-major it is 2 cells = 3 KB.
-template <typename E, bool WF32, bool OF32, bool HAS_T, bool POOL, int PR>
-__global__ __launch_bounds__(DG_WAVES * 64, 3) void dgrad_fin_kernel(const DgFinP p) {
+template <typename E, bool WF32, bool OF32, bool HAS_T, bool POOL, int PR, bool WT>
+EA_DEV void dgrad_fin_body(const DgFinP& p) {
+  static_assert(!(WT && WF32), "the prepared image is in the element type");
   static_assert(PR == 0 || (POOL && (PR == 2 || PR == 4)), "cell-major order needs 2 x 2 or 4 x 4 pooling cells");
   constexpr int TPC = PR * PR, CPT = PR ? DG_TOK / (PR * PR) : 1;      // tokens per cell, cells per tile
   extern __shared__ __attribute__((aligned(16))) char smem[];
@@ -190,7 +205,10 @@ __global__ __launch_bounds__(DG_WAVES * 64, 3) void dgrad_fin_kernel(const DgFin
   //  global offsets derived from them sat in ~16 registers that the tile loop does not have -- they were spilled and re-read)
   // ---- W^T -> registers (as dgrad_rs_kernel) ----
   typename E::x8 wr[DG_KT];
-  {
+  if constexpr (WT) {
+#pragma unroll
+    for (int ks = 0; ks < DG_KT; ++ks) wr[ks] = as_x8<E>(ldg16(p.d.w + dg_wt_off(wave, ks, lane)));
+  } else {
     const int o_l = tid / 24, c = tid - o_l * 24;
     const int rho = ((o_l >> 2) & 1) * 16 + (o_l >> 3) * 4 + (o_l & 3);
     const int wofs = rho * (DG_NO * 2) + c * 16;
@@ -466,10 +484,21 @@ __global__ __launch_bounds__(DG_WAVES * 64, 3) void dgrad_fin_kernel(const DgFin
   EA_BLK(p.d, 1);
 }
 
+template <typename E, bool WF32, bool OF32, bool HAS_T, bool POOL, int PR>
+__global__ __launch_bounds__(DG_WAVES * 64, 3) void dgrad_fin_kernel(const DgFinP p) {
+  dgrad_fin_body<E, WF32, OF32, HAS_T, POOL, PR, false>(p);
+}
+template <typename E, bool OF32, bool HAS_T, bool POOL, int PR>
+__global__ __launch_bounds__(DG_WAVES * 64, 3) void dgrad_fin_wt_kernel(const DgFinP p) {
+  dgrad_fin_body<E, false, OF32, HAS_T, POOL, PR, true>(p);
+}
+
 int dgrad_rs_supported(int K, int NO) { return K == DG_K && NO == DG_NO; }
 
-int dgrad_rs_dispatch(int dtype, const void* dy, const void* w, int w_f32, void* dx, int dx_f32, int rows, long ldy, long ldx,
+// w_kind: 0 = [576, 192] in the element type, 1 = the fp32 master, 2 = the prepared image (WT)
+int dgrad_rs_dispatch(int dtype, const void* dy, const void* w, int w_kind, void* dx, int dx_f32, int rows, long ldy, long ldx,
                       hipStream_t st) {
+  if (w_kind < 0 || w_kind > 2) return EA_E_BADARG;
   if (rows <= 0) return EA_OK;
   DgP p = {};
   p.dy = (const char*)dy; p.w = (const char*)w; p.dx = (char*)dx;
@@ -482,21 +511,29 @@ int dgrad_rs_dispatch(int dtype, const void* dy, const void* w, int w_f32, void*
     EA_SET_LDS_ONCE((&dgrad_rs_kernel<E_, WF_, OF_>), DG_LDS);                            \
     hipLaunchKernelGGL((dgrad_rs_kernel<E_, WF_, OF_>), g, b, DG_LDS, st, p);             \
   } while (0)
+#define EA_DG_LAUNCH_WT(E_, OF_)                                                          \
+  do {                                                                                    \
+    EA_SET_LDS_ONCE((&dgrad_rs_wt_kernel<E_, OF_>), DG_LDS);                              \
+    hipLaunchKernelGGL((dgrad_rs_wt_kernel<E_, OF_>), g, b, DG_LDS, st, p);               \
+  } while (0)
 #define EA_DG_SEL(E_)                                                                     \
   do {                                                                                    \
-    if (w_f32) { if (dx_f32) EA_DG_LAUNCH(E_, true, true); else EA_DG_LAUNCH(E_, true, false); }   \
+    if (w_kind == 2) { if (dx_f32) EA_DG_LAUNCH_WT(E_, true); else EA_DG_LAUNCH_WT(E_, false); }   \
+    else if (w_kind) { if (dx_f32) EA_DG_LAUNCH(E_, true, true); else EA_DG_LAUNCH(E_, true, false); }   \
     else { if (dx_f32) EA_DG_LAUNCH(E_, false, true); else EA_DG_LAUNCH(E_, false, false); }       \
   } while (0)
   if (dtype == EA_BF16) EA_DG_SEL(BF16);
   else if (dtype == EA_F16) EA_DG_SEL(F16);
   else return EA_E_BADARG;
 #undef EA_DG_SEL
+#undef EA_DG_LAUNCH_WT
 #undef EA_DG_LAUNCH
   return (int)hipGetLastError();
 }
 
-int dgrad_fin_dispatch(int dtype, const DgFinP& p0, int w_f32, int dx_f32, bool has_t, int pr, hipStream_t st) {
+int dgrad_fin_dispatch(int dtype, const DgFinP& p0, int w_kind, int dx_f32, bool has_t, int pr, hipStream_t st) {
   DgFinP p = p0;
+  if (w_kind < 0 || w_kind > 2) return EA_E_BADARG;
   if (p.d.rows <= 0) return EA_OK;
   int grid = ea_device_cus();
   if (grid > p.nunits) grid = p.nunits;
@@ -505,10 +542,21 @@ int dgrad_fin_dispatch(int dtype, const DgFinP& p0, int w_f32, int dx_f32, bool 
   ProfReport rep;
   p.d.prof = rep.arm(st, "dgrad_fin", pr);
 #endif
-#define EA_DF_LAUNCH(E_, WF_, OF_, T_, P_, R_)                                                    \
+#define EA_DF_LAUNCH_W(E_, WF_, OF_, T_, P_, R_)                                                  \
   do {                                                                                            \
     EA_SET_LDS_ONCE((&dgrad_fin_kernel<E_, WF_, OF_, T_, P_, R_>), DG_FIN_LDS);                   \
     hipLaunchKernelGGL((dgrad_fin_kernel<E_, WF_, OF_, T_, P_, R_>), g, b, DG_FIN_LDS, st, p);    \
+  } while (0)
+#define EA_DF_LAUNCH_WT(E_, OF_, T_, P_, R_)                                                      \
+  do {                                                                                            \
+    EA_SET_LDS_ONCE((&dgrad_fin_wt_kernel<E_, OF_, T_, P_, R_>), DG_FIN_LDS);                     \
+    hipLaunchKernelGGL((dgrad_fin_wt_kernel<E_, OF_, T_, P_, R_>), g, b, DG_FIN_LDS, st, p);      \
+  } while (0)
+// (WF_ = 2: the prepared image)
+#define EA_DF_LAUNCH(E_, WF_, OF_, T_, P_, R_)                                                    \
+  do {                                                                                            \
+    if constexpr (WF_ == 2) EA_DF_LAUNCH_WT(E_, OF_, T_, P_, R_);                                 \
+    else EA_DF_LAUNCH_W(E_, (WF_ == 1), OF_, T_, P_, R_);                                         \
   } while (0)
 #define EA_DF_SEL3(E_, WF_, OF_, T_)                                                          \
   do {                                                                                        \
@@ -524,8 +572,9 @@ int dgrad_fin_dispatch(int dtype, const DgFinP& p0, int w_f32, int dx_f32, bool 
   } while (0)
 #define EA_DF_SEL(E_)                                                                     \
   do {                                                                                    \
-    if (w_f32) { if (dx_f32) EA_DF_SEL2(E_, true, true); else EA_DF_SEL2(E_, true, false); }   \
-    else { if (dx_f32) EA_DF_SEL2(E_, false, true); else EA_DF_SEL2(E_, false, false); }       \
+    if (w_kind == 2) { if (dx_f32) EA_DF_SEL2(E_, 2, true); else EA_DF_SEL2(E_, 2, false); }   \
+    else if (w_kind) { if (dx_f32) EA_DF_SEL2(E_, 1, true); else EA_DF_SEL2(E_, 1, false); }   \
+    else { if (dx_f32) EA_DF_SEL2(E_, 0, true); else EA_DF_SEL2(E_, 0, false); }               \
   } while (0)
   if (dtype == EA_BF16) EA_DF_SEL(BF16);
   else if (dtype == EA_F16) EA_DF_SEL(F16);
@@ -534,11 +583,13 @@ int dgrad_fin_dispatch(int dtype, const DgFinP& p0, int w_f32, int dx_f32, bool 
 #undef EA_DF_SEL2
 #undef EA_DF_SEL3
 #undef EA_DF_LAUNCH
+#undef EA_DF_LAUNCH_W
+#undef EA_DF_LAUNCH_WT
   return (int)hipGetLastError();
 }
 
 // host side of ea_linear_dgrad_finish: three heads of 64 channels, images of gh x gw tokens
-int dgrad_fin_launch(int dtype, const void* dqkv, long ldy, const void* qkv, long ldq, const void* w, int w_f32, void* dx, int dx_f32,
+int dgrad_fin_launch(int dtype, const void* dqkv, long ldy, const void* qkv, long ldq, const void* w, int w_kind, void* dx, int dx_f32,
                      long ldx, int B, int gh, int gw, int pool_r, int C, float scale, const float* qbar, const float* uq,
                      const float* lse_t, const float* dpq, const float* dpk, hipStream_t st) {
   DgFinP p = {};
@@ -571,7 +622,7 @@ int dgrad_fin_launch(int dtype, const void* dqkv, long ldy, const void* qkv, lon
     p.m_cw = (unsigned)((1ull << 32) / (unsigned)p.cw) + 1u;
   }
   p.nunits = B * p.splits;
-  return dgrad_fin_dispatch(dtype, p, w_f32, dx_f32, uq != nullptr, pr, st);
+  return dgrad_fin_dispatch(dtype, p, w_kind, dx_f32, uq != nullptr, pr, st);
 }
 
 }  // namespace ea

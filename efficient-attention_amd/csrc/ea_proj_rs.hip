@@ -7,7 +7,7 @@
 // -- and the activations stream through LDS exactly once: a 32-token tile is fetched by all 768 threads (one 16-byte
 // bf16 chunk each: two 16-byte fp32 loads, the autocast cast folded in; the rounded copy is written out for the
 // weight-gradient pass), double-buffered, one barrier per tile; every wave then reads the tile's rows as B operands
-// (ds_read_b128, conflict-free phi2 layout per 64-channel slab) and forms its [48 x 32] piece transposed, D[out][token].
+// (ds_read_b128, conflict-free psi layout per 64-channel slab) and forms its [48 x 32] piece transposed, D[out][token].
 // The weight rows of a tile PAIR are interleaved in fours, so a lane ends up with eight consecutive columns of one token
 // (16-byte stores); the third tile of a wave gives 8-byte stores.
 #include "ea_common.h"
@@ -37,8 +37,9 @@ struct RsP {
 
 constexpr int RS_K = 192, RS_NO = 576, RS_WAVES = 12, RS_TOK = 32, RS_KT = RS_K / 32, RS_SLABS = RS_K / 64;
 
-// LDS tile: [slab][token][64 channels] element type, phi2-swizzled 128-byte rows
-EA_DEV int rs_off(int slab, int tok, int chunk16) { return slab * (RS_TOK * 128) + lds_off2<64>(tok, chunk16); }
+// LDS tile: [slab][token][64 channels] element type, psi-swizzled 128-byte rows (conflict-free for the 4 (ks & 1) + g reads
+// below, which phi2 is not: ea_common.h)
+EA_DEV int rs_off(int slab, int tok, int chunk16) { return slab * (RS_TOK * 128) + lds_off3<64>(tok, chunk16); }
 
 // POOL: tokens per pooling cell (0: none; 16: 4 x 4 cells, two per tile; 4: 2 x 2 cells, eight per tile)
 // lane (g, li) of wave `wave`, column group j: the output column whose weight row it holds as MFMA A operand
@@ -115,7 +116,6 @@ __global__ __launch_bounds__(RS_WAVES * 64, 3) void proj_rs_kernel(const RsP p) 
           stg16(p.w_cast + ((size_t)col[j] * RS_K + ks * 32 + 8 * g) * 2, __builtin_bit_cast(u32x4, wr[j][ks]));
       }
   }
-  const int slab_s = st_c >> 3, ch_s = st_c & 7;
   // ---- pooling epilogue (POOL > 0), all of it on the matrix pipe -- a first version that summed the rounded outputs
   // across the lanes of a cell (12 values x 4 DPP adds x 2 tiles per wave and tile) cost 9 us of VALU time at cfg3:
   //   (1) xbar[cell][ch] = mean over the cell's tokens of the staged (rounded) x rows: ONE MFMA per wave and tile --
@@ -131,8 +131,11 @@ __global__ __launch_bounds__(RS_WAVES * 64, 3) void proj_rs_kernel(const RsP p) 
   auto pool_x = [&](int b_) {
     const int slab = wave >> 2, dt = wave & 3;
     const char* tb = tile[b_] + slab * (RS_TOK * 128);
-    const int r_ = 4 * g + (li >> 2);
-    const int off = lds_off2<64>(r_, 2 * dt + ((li & 3) >> 1)) + 8 * (li & 1);
+    // (from an opaque copy of the lane index: as a loop invariant this offset is one register more than the kernel has)
+    int lane_x = lane;
+    asm volatile("" : "+v"(lane_x));
+    const int r_ = lane_x >> 2;                                          // 4 g + (li >> 2)
+    const int off = lds_off3<64>(r_, 2 * dt + ((lane_x & 3) >> 1)) + 8 * (lane_x & 1);
     const typename E::x8 a = as_x8<E>(E::tr4(tb + off), E::tr4(tb + 16 * 128 + off));
     // (the pattern is rebuilt per tile -- two compares -- instead of living in four registers: the kernel sits at its
     //  register limit, 168 of 170 at three waves per SIMD)
@@ -196,7 +199,13 @@ __global__ __launch_bounds__(RS_WAVES * 64, 3) void proj_rs_kernel(const RsP p) 
       } else {
         w8 = nb[0];
       }
-      sts16(tile[buf] + rs_off(slab_s, st_tok, ch_s), w8);
+      {
+        // (slot offset from an opaque copy of the thread index, as in dgrad_fin_kernel: not a register held across the tile loop)
+        int tid_s = tid;
+        asm volatile("" : "+v"(tid_s));
+        const int tk = tid_s / 24, c = tid_s - tk * 24;
+        sts16(tile[buf] + rs_off(c >> 3, tk, c & 7), w8);
+      }
       if (AF32 && p.a_cast) {
         const int tok = tok_of(t, st_tok);                          // (clamped rows rewrite the last row with its own values)
         stg16(p.a_cast + ((size_t)tok * RS_K + st_c * 8) * 2, w8);
@@ -281,13 +290,16 @@ int proj_rs_pool_supported(int K, int NO, int B, int gh, int gw, int r) {
 
 // The 16-bit copies of a 192-wide layer's two weights in ONE launch (round 6): wq [576, 192], wp [192, 192] fp32 ->
 //   w16q [576, 192] (input gradient), wsw = the same values in proj_rs_kernel<.., WSW>'s staging order, w16p [192, 192] (output
-//   projection), w16pT = its transpose (the output projection's input gradient as the same streaming kernel).
+//   projection), w16pT = its transpose (the output projection's input gradient as the same streaming kernel);
+//   wtsw (or null) = wq's values once more, in the order the input-gradient kernels (ea_dgrad_rs.hip, WT) hold W^T: piece
+//   (wave, ks, lane = (g, li)) = W[32 ks + 8 g .. + 7][16 wave + li], 12 x 18 x 64 pieces of 16 bytes.
 // One thread per 8-element piece; round to nearest even like every cast of the library.
 template <typename E>
 __global__ __launch_bounds__(256) void w192_prepare_kernel(const float* __restrict__ wq, const float* __restrict__ wp,
                                                             char* __restrict__ w16q, char* __restrict__ wsw,
-                                                            char* __restrict__ w16p, char* __restrict__ w16pT) {
-  constexpr int NQ = RS_WAVES * 3 * RS_KT * 64, NP = RS_K * RS_K / 8;
+                                                            char* __restrict__ w16p, char* __restrict__ w16pT,
+                                                            char* __restrict__ wtsw) {
+  constexpr int NQ = RS_WAVES * 3 * RS_KT * 64, NP = RS_K * RS_K / 8, NT = 12 * (RS_NO / 32) * 64;
   const int i = blockIdx.x * 256 + threadIdx.x;
   if (i < NQ) {
     const int lane = i & 63, pc = i >> 6, ks = pc % RS_KT, wj = pc / RS_KT, j = wj % 3, wave = wj / 3;
@@ -311,15 +323,23 @@ __global__ __launch_bounds__(256) void w192_prepare_kernel(const float* __restri
       t[(size_t)(c * 8 + 2 * q) * RS_K + row] = (uint16_t)(w8[q] & 0xffffu);
       t[(size_t)(c * 8 + 2 * q + 1) * RS_K + row] = (uint16_t)(w8[q] >> 16);
     }
+  } else if (i >= NQ + NP && i < NQ + NP + NT && wtsw) {
+    const int k = i - NQ - NP, lane = k & 63, pc = k >> 6, ks = pc % (RS_NO / 32), wave = pc / (RS_NO / 32);
+    const int g = lane >> 4, li = lane & 15;
+    const float* src = wq + (size_t)(32 * ks + 8 * g) * RS_K + 16 * wave + li;     // a column piece: 16 lanes = 64 contiguous bytes per row
+    float f[8];
+#pragma unroll
+    for (int q = 0; q < 8; ++q) f[q] = src[(size_t)q * RS_K];
+    stg16(wtsw + (size_t)k * 16, pack8<E>(f));
   }
 }
 
 int w192_prepare_dispatch(int dtype, const float* wq, const float* wp, void* w16q, void* wsw, void* w16p, void* w16pT,
-                          hipStream_t st) {
-  constexpr int N = RS_WAVES * 3 * RS_KT * 64 + RS_K * RS_K / 8;
+                          void* wtsw, hipStream_t st) {
+  const int N = RS_WAVES * 3 * RS_KT * 64 + RS_K * RS_K / 8 + (wtsw ? 12 * (RS_NO / 32) * 64 : 0);
   const dim3 g((N + 255) / 256), b(256);
-  if (dtype == EA_BF16) hipLaunchKernelGGL(w192_prepare_kernel<BF16>, g, b, 0, st, wq, wp, (char*)w16q, (char*)wsw, (char*)w16p, (char*)w16pT);
-  else if (dtype == EA_F16) hipLaunchKernelGGL(w192_prepare_kernel<F16>, g, b, 0, st, wq, wp, (char*)w16q, (char*)wsw, (char*)w16p, (char*)w16pT);
+  if (dtype == EA_BF16) hipLaunchKernelGGL(w192_prepare_kernel<BF16>, g, b, 0, st, wq, wp, (char*)w16q, (char*)wsw, (char*)w16p, (char*)w16pT, (char*)wtsw);
+  else if (dtype == EA_F16) hipLaunchKernelGGL(w192_prepare_kernel<F16>, g, b, 0, st, wq, wp, (char*)w16q, (char*)wsw, (char*)w16p, (char*)w16pT, (char*)wtsw);
   else return EA_E_BADARG;
   return (int)hipGetLastError();
 }

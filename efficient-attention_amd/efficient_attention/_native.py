@@ -22,7 +22,7 @@ class ea_t4(ctypes.Structure):
                 ("sn", ctypes.c_int64)]
 
 
-ABI_VERSION = 24         # ea_abi_version() of include/ea_hip.h this file mirrors
+ABI_VERSION = 25         # ea_abi_version() of include/ea_hip.h this file mirrors
 
 
 class ea_geom(ctypes.Structure):
@@ -165,6 +165,7 @@ SIGNATURES = {
     "ea_table_bias_fwd": [_I, _I, _I, _I, _I, _F, _P, _P, _P, _P],
     "ea_multi_cast": [_I, _I, _P, _P, _P, _P],
     "ea_linear_w192_prepare": [_I, _P, _P, _P, _P, _P, _P, _P],
+    "ea_linear_w192_prepare_t": [_I, _P, _P, _P, _P, _P, _P, _P, _P],
     "ea_linear_wsw": [_I, _I, _I, _I, _I, _I, _P, _I, _L, _P, _P, _P, _L, _P, _P, _P, _P],
     "ea_table_bias_bwd": [_I, _I, _I, _I, _I, _I, _F, _P, _P, _P, _P],
     "ea_linear_supported": [_I, _I],

@@ -1592,14 +1592,30 @@ def prepare_w192(wq, wp, cdtype):
     rounded output-projection weight and its transpose (its input gradient through the same streaming kernel).  The kernels
     fed by the fp32 master weights pull twice the bytes through every CU's L2 port before their first tile: 13 us of the
     pooled projection at any row count (workgroup timelines of round 6)."""
+    return _prepare_w192(wq, wp, cdtype, False)
+
+
+def prepare_w192_t(wq, wp, cdtype):
+    """prepare_w192 with a fifth image from the same launch (ea_linear_w192_prepare_t): wqT_sw, the bits of w16q in the order the
+    input-gradient kernels hold W^T in registers -- 16-byte piece (wave, ks, lane = 16 g + li) = wq[32 ks + 8 g .. + 7, 16 wave + li]
+    -- which qkv_dgrad / qkv_dgrad_finish load directly instead of transposing w16q through LDS at the start of every launch."""
+    return _prepare_w192(wq, wp, cdtype, True)
+
+
+def _prepare_w192(wq, wp, cdtype, with_t):
     dev = wq.device
     w16q = torch.empty((576, 192), dtype=cdtype, device=dev)
     wsw = torch.empty((576 * 192,), dtype=cdtype, device=dev)
     w16p = torch.empty((192, 192), dtype=cdtype, device=dev)
     w16pT = torch.empty((192, 192), dtype=cdtype, device=dev)
-    nv.call("ea_linear_w192_prepare", _ELEM[cdtype], nv.ptr(wq.detach()), nv.ptr(wp.detach()), nv.ptr(w16q), nv.ptr(wsw),
-            nv.ptr(w16p), nv.ptr(w16pT), nv.stream())
-    return w16q, wsw, w16p, w16pT
+    if not with_t:
+        nv.call("ea_linear_w192_prepare", _ELEM[cdtype], nv.ptr(wq.detach()), nv.ptr(wp.detach()), nv.ptr(w16q), nv.ptr(wsw),
+                nv.ptr(w16p), nv.ptr(w16pT), nv.stream())
+        return w16q, wsw, w16p, w16pT
+    wtsw = torch.empty((576 * 192,), dtype=cdtype, device=dev)
+    nv.call("ea_linear_w192_prepare_t", _ELEM[cdtype], nv.ptr(wq.detach()), nv.ptr(wp.detach()), nv.ptr(w16q), nv.ptr(wsw),
+            nv.ptr(w16p), nv.ptr(w16pT), nv.ptr(wtsw), nv.stream())
+    return w16q, wsw, w16p, w16pT, wtsw
 
 
 def project_qkv_wsw(x2, wsw, w16q, bq32, cdtype, want_cast, grid=None, pq=None, pk=None):
@@ -1912,7 +1928,7 @@ class CoreModuleFn(torch.autograd.Function):
         want = x2.dtype == torch.float32 and need[1]
         lib = module_proj_lib(C)
         w16q = w16p = b16p = None
-        w192 = prepare_w192(wq, wp, cdtype) if (not lib and w192_usable(wq, wp, cdtype)) else None
+        w192 = prepare_w192_t(wq, wp, cdtype) if (not lib and w192_usable(wq, wp, cdtype)) else None
         w16pT = None if w192 is None else w192[3]
         if lib:
             w16q, b16q, w16p, b16p = lib_casts(wq, bq, wp, bp, cdtype)
@@ -1939,7 +1955,9 @@ class CoreModuleFn(torch.autograd.Function):
             y2 = ea_linear(o2, w192[2], bp32, cdtype)[0]
         else:
             y2 = lin(o2, wp, bp32, elem, False, False, False)[0]
-        ctx.save_for_backward(xl, qkv5, o2, wq, wp, w16q, w16p, w16pT, *saved)
+        # the prepared W^T goes with the rounded weight it was made from
+        wqT = w192[4] if (w192 is not None and w16q is w192[0]) else None
+        ctx.save_for_backward(xl, qkv5, o2, wq, wp, w16q, w16p, w16pT, wqT, *saved)
         ctx.core = core
         ctx.meta = (x.shape, x.dtype, cdtype, None if bq is None else bq.dtype, None if bp is None else bp.dtype, wq.dtype, wp.dtype,
                     heads, [None if t is None else t.dtype for t in inputs])
@@ -1947,7 +1965,7 @@ class CoreModuleFn(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, dy):
-        xl, qkv5, o2, wq, wp, w16q, w16p, w16pT, *saved = ctx.saved_tensors
+        xl, qkv5, o2, wq, wp, w16q, w16p, w16pT, wqT, *saved = ctx.saved_tensors
         xshape, xdtype, cdtype, bqd, bpd, wqd, wpd, heads, in_dtypes = ctx.meta
         core = ctx.core
         C = xshape[-1]
@@ -1995,7 +2013,7 @@ class CoreModuleFn(torch.autograd.Function):
         dqkv2 = dqkv5.view(-1, 3 * C)
         if fin is not None:
             # corrects the dq / dk columns of dqkv2 in place: BEFORE the weight gradient reads them
-            dx = qkv_dgrad_finish(dqkv2, fin[1], wq, w16q, xdtype, fin[0]).view(xshape)
+            dx = qkv_dgrad_finish(dqkv2, fin[1], wq, w16q, xdtype, fin[0], wqT).view(xshape)
         if pair:
             rq, rp = wgrad_pair(dqkv2, xl, need_bq, dy2, o2, need_bp)
             pend += [("qkv", rq[0], rq[1]), ("proj", rp[0], rp[1])]
@@ -2009,7 +2027,7 @@ class CoreModuleFn(torch.autograd.Function):
             # frozen qkv weight, trainable bias (bias-only fine-tuning): a column sum of d qkv, no input rows needed
             dbq = bias_grad(dqkv2).to(bqd)
         if need[0] and dx is None:
-            dx = qkv_dgrad(dqkv2, wq, w16q, xdtype).view(xshape)
+            dx = qkv_dgrad(dqkv2, wq, w16q, xdtype, wqT).view(xshape)
         res = {}
         if pend:
             sums = multi_sum([t for _, t, _ in pend])
@@ -2763,10 +2781,18 @@ USE_DGRAD_RS = os.environ.get("EA_DGRAD_RS", "1") == "1"
 DGRAD_RS_MIN_ROWS = int(os.environ.get("EA_DGRAD_RS_MIN_ROWS", "16384"))
 
 
-def qkv_dgrad(dqkv2, wq, w16, xdtype):
+def _dgrad_weight(wq, w16, wt, cdtype):
+    """(weight operand of ea_linear_dgrad*, its kind: 0 = [576, 192] in cdtype, 1 = fp32 master, 2 = prepare_w192_t's image)."""
+    if wt is not None and wt.dtype == cdtype and wt.is_contiguous() and wt.numel() == 576 * 192:
+        return wt, 2
+    w = w16 if (w16 is not None and w16.dtype == cdtype and w16.is_contiguous()) else wq
+    return w, int(w.dtype == torch.float32)
+
+
+def qkv_dgrad(dqkv2, wq, w16, xdtype, wt=None):
     """dx = dqkv2 @ W for the qkv projection (abstract_attention.py:72-78 differentiated) in `xdtype`.
     192-wide layers: ea_linear_dgrad (round 5) -- the weight resident in registers (the 16-bit copy the forward projection
-    left, `w16`, or the fp32 master `wq` rounded on the way), the gradient rows through LDS once; no library GEMM and no cast
+    left, `w16`, its prepared transpose `wt`, or the fp32 master `wq` rounded on the way), the gradient rows through LDS once; no library GEMM and no cast
     kernel.  Other widths, tracing and small row counts: the library GEMM with an fp32 result."""
     rows, NO = dqkv2.shape
     cdtype = dqkv2.dtype
@@ -2776,7 +2802,7 @@ def qkv_dgrad(dqkv2, wq, w16, xdtype):
             and tuple(wq.shape) == (NO, K) and dqkv2.stride(1) == 1 and dqkv2.stride(0) % 8 == 0
             and (w16 is not None or wq.dtype == torch.float32)
             and bool(nv.lib().ea_linear_dgrad_supported(K, NO))):
-        w = w16 if (w16 is not None and w16.dtype == cdtype and w16.is_contiguous()) else wq
+        w, w_kind = _dgrad_weight(wq, w16, wt, cdtype)
         if w.dtype in (torch.float32, cdtype) and w.is_contiguous():
             dx = torch.empty((rows, K), dtype=xdtype, device=dqkv2.device)
             label = "ea_linear_dgrad"
@@ -2784,7 +2810,7 @@ def qkv_dgrad(dqkv2, wq, w16, xdtype):
                 label = "ea_linear_dgrad[%d->%d,16->%s]" % (NO, K, "f32" if xdtype == torch.float32 else "16")
                 _note_bytes(label, rows * (NO * 2 + K * dx.element_size()))
             nv.call_as(label, "ea_linear_dgrad", _ELEM[cdtype], rows, K, NO, nv.ptr(dqkv2), dqkv2.stride(0), nv.ptr(w),
-                       int(w.dtype == torch.float32), nv.ptr(dx), int(xdtype == torch.float32), K, nv.stream())
+                       w_kind, nv.ptr(dx), int(xdtype == torch.float32), K, nv.stream())
             return dx
     return _mm_out(dqkv2, w16 if w16 is not None else wq.to(cdtype), xdtype)
 
@@ -2800,15 +2826,15 @@ def dgrad_finish_usable(dqkv2, wq, xdtype, heads, d):
             and dqkv2.shape[0] >= DGRAD_RS_MIN_ROWS)
 
 
-def qkv_dgrad_finish(dqkv2, qkv2, wq, w16, xdtype, fin):
+def qkv_dgrad_finish(dqkv2, qkv2, wq, w16, xdtype, fin, wt=None):
     """dx = dqkv2 @ W after the LAST corrections of the dq / dk columns of dqkv2 (in place) -- ea_linear_dgrad_finish, one pass:
     LARA: fin = dict(B, gh, gw, r, C, scale, qbar, uq, lse_t, dpq, dpk) from lara_bwd_impl(defer_finish=True) (lara.py:223,
     43,48,145-151 differentiated); EVA: uq = qbar = lse_t = None, dpq / dpk = the chunk-mean gradients (eva.py:178-181)."""
     rows = dqkv2.shape[0]
     cdtype = dqkv2.dtype
-    w = w16 if (w16 is not None and w16.dtype == cdtype and w16.is_contiguous()) else wq
+    w, w_kind = _dgrad_weight(wq, w16, wt, cdtype)
     if not (w.dtype in (torch.float32, cdtype) and w.is_contiguous()):
-        w = wq.to(cdtype).contiguous()
+        w, w_kind = wq.to(cdtype).contiguous(), 0
     dx = torch.empty((rows, 192), dtype=xdtype, device=dqkv2.device)
     label = "ea_linear_dgrad_finish"
     if nv.KERNEL_TIMER.enabled:
@@ -2817,7 +2843,7 @@ def qkv_dgrad_finish(dqkv2, qkv2, wq, w16, xdtype, fin):
         _note_bytes(label, rows * (576 * 2 + 384 * 2 + 192 * dx.element_size() + (192 * 2 if fin.get("uq") is not None else 0)))
     nv.call_as(label, "ea_linear_dgrad_finish", _ELEM[cdtype], fin["B"], fin["gh"], fin["gw"], fin["r"], fin["C"], fin["scale"],
                nv.ptr(dqkv2), dqkv2.stride(0), nv.ptr(qkv2), 0 if qkv2 is None else qkv2.stride(0), nv.ptr(w),
-               int(w.dtype == torch.float32), nv.ptr(dx), int(xdtype == torch.float32), 192, nv.ptr(fin.get("qbar")),
+               w_kind, nv.ptr(dx), int(xdtype == torch.float32), 192, nv.ptr(fin.get("qbar")),
                nv.ptr(fin.get("uq")), nv.ptr(fin.get("lse_t")), nv.ptr(fin.get("dpq")), nv.ptr(fin.get("dpk")), nv.stream())
     return dx
 

@@ -678,11 +678,18 @@ int ea_linear_w192_prepare(int32_t dtype, const float* wq, const float* wp, void
 int ea_linear_wsw(int32_t dtype, int32_t rows, int32_t B, int32_t gh, int32_t gw, int32_t r, const void* a, int32_t a_f32, int64_t lda,
                   const void* wq_sw, const float* bias, void* y, int64_t ldy, void* a_cast, float* pooled_q, float* pooled_k,
                   void* stream);
+/* ABI 25: ea_linear_w192_prepare with a fifth image, wqT_sw (576 * 192 elements): wq's rounded values -- the bits of w16q --
+ * in the order the input-gradient kernels hold W^T in their registers: 16-byte piece (wave, ks, lane = 16 g + li), wave < 12,
+ * ks < 18, = wq[32 ks + 8 g .. + 7][16 wave + li].  ea_linear_dgrad / ea_linear_dgrad_finish take it with w_f32 == 2 and load it
+ * straight into registers instead of transposing the weight through LDS at the start of every launch. */
+int ea_linear_w192_prepare_t(int32_t dtype, const float* wq, const float* wp, void* w16q, void* wq_sw, void* w16p, void* w16pT,
+                             void* wqT_sw, void* stream);
 
 /* The INPUT gradient of that qkv projection (abstract_attention.py:72-78 differentiated; ABI 10, ea_dgrad_rs.hip):
  *   dx[rows, in] = dy[rows, out] w[out, in]          in = 192, out = 576 (ea_linear_dgrad_supported != 0)
- * dy: EA dtype, row stride ldy elements; w: the layer's weight [out, in] contiguous -- the fp32 master (w_f32 != 0, rounded
- * to the EA dtype on its way into the registers) or a copy in the EA dtype (e.g. ea_linear_w32_pool's w_cast); dx: fp32
+ * dy: EA dtype, row stride ldy elements; w: the layer's weight [out, in] contiguous -- the fp32 master (w_f32 == 1, rounded
+ * to the EA dtype on its way into the registers) or a copy in the EA dtype (w_f32 == 0, e.g. ea_linear_w32_pool's w_cast) --
+ * or, ABI 25, ea_linear_w192_prepare_t's wqT_sw image (w_f32 == 2); any other w_f32 is EA_E_BADARG; dx: fp32
  * (dx_f32 != 0: the gradient of an fp32 module input under autocast) or the EA dtype, row stride ldx elements.  The weight
  * stays resident in the registers of a 12-wave workgroup per CU, dy passes LDS once: no library GEMM, no cast kernel. */
 int32_t ea_linear_dgrad_supported(int32_t in_features, int32_t out_features);
