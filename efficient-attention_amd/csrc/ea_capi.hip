@@ -81,7 +81,7 @@ static Geo mk_geo(const ea_geom* g) {
 extern "C" {
 
 const char* ea_version(void) { return "ea_hip 0.1.0 gfx950"; }
-int32_t ea_abi_version(void) { return 25; }
+int32_t ea_abi_version(void) { return 26; }
 
 int32_t ea_window_bias_ld(const ea_geom* g) {
   WinTiling t;
@@ -2173,6 +2173,7 @@ int ea_layernorm_bwd(int32_t xtype, int32_t rows, int32_t C, const void* x, cons
 // ---- causal EVA, incremental decoding (ea_ceva_decode.hip) ----
 #include "ea_ceva_decode.h"
 #include "ea_ceva_decode_linear.h"
+#include "ea_ceva_decode_vocab.h"
 static bool dec_t4_ok(const ea_t4* t, int D, int esz) {
   const int a = 16 / esz;                                 // 16-byte aligned rows
   return t && t->ptr && ((uintptr_t)t->ptr % 16 == 0) && t->sb % a == 0 && t->sh % a == 0 && t->sn % a == 0 && t->sn >= D;
@@ -2402,6 +2403,30 @@ int ea_ceva_sdecode_linear_fused(int32_t M, int32_t K, int32_t N, const void* x,
   p.ldx = ldx; p.ldy = ldy; p.M = M; p.K = K; p.N = N; p.dtype = w_dtype; p.act = act;
   p.x_f32 = x_dtype == EA_F32; p.y_f32 = y_dtype == EA_F32;
   return ea::ceva_sdecode_linear_fused(p, (hipStream_t)stream);
+}
+
+int64_t ea_ceva_sdecode_vocab_ws(int32_t M, int32_t V) { return ea::ceva_sdecode_vocab_ws(M, V); }
+
+int ea_ceva_sdecode_vocab_argmax(int32_t M, int32_t K, int32_t V, const void* x, int32_t x_dtype, int64_t ldx,
+                                 const void* w, int32_t w_dtype, void* logits, int32_t logits_dtype, int64_t ldl,
+                                 void* ws, int64_t ws_bytes, int64_t* token, float* top, void* stream) {
+  // ea_ceva_sdecode_linear's refusals in its order: pointers, the types, the sizes and strides, and the geometry last
+  if (!x || !w || !ws || !token || (uintptr_t)x % 16 || (uintptr_t)w % 16 || (uintptr_t)ws % 16) return EA_E_BADARG;
+  if ((uintptr_t)token % 8 || (uintptr_t)top % 4) return EA_E_BADARG;
+  if (w_dtype != EA_BF16 && w_dtype != EA_F16) return EA_E_BADARG;
+  if (x_dtype != EA_F32 && x_dtype != w_dtype) return EA_E_BADARG;
+  if (logits && ((logits_dtype != EA_F32 && logits_dtype != w_dtype) || (uintptr_t)logits % (logits_dtype == EA_F32 ? 4 : 2)))
+    return EA_E_BADARG;
+  if (M < 1 || K < 1 || ldx < K || (logits && ldl < V)) return EA_E_BADARG;
+  if (ldx * (x_dtype == EA_F32 ? 4 : 2) % 16) return EA_E_BADARG;
+  const int64_t need = ea::ceva_sdecode_vocab_ws(M, V);           // (< 0: a geometry refused below)
+  if (need >= 0 && ws_bytes < need) return EA_E_BADARG;
+  if (M > EA_CEVA_LINEAR_MAX_ROWS || K % 32 || V < 1) return EA_E_UNSUPPORTED;
+  ea::DecVocabP p = {};
+  p.x = (const char*)x; p.w = (const char*)w; p.logits = (char*)logits; p.ws = (ea::VocPick*)ws; p.token = token; p.top = top;
+  p.ldx = ldx; p.ldl = logits ? ldl : 0; p.M = M; p.K = K; p.V = V; p.dtype = w_dtype;
+  p.x_f32 = x_dtype == EA_F32; p.l_f32 = logits && logits_dtype == EA_F32;
+  return ea::ceva_sdecode_vocab_argmax(p, (hipStream_t)stream);
 }
 
 }  // extern "C"

@@ -9,9 +9,12 @@ are the attention module's own, as in the reference adapter.
 
 DecoderLayer / DecoderStack are the decoder-only language model of the wikitext-103 recipe around `CausalEVAttention`
 (fairseq/modules/transformer_layer.py:236-308 without the encoder attention), with incremental decoding on the attention's
-static and rolling states: `init_decoding`, `decode`, `generate`."""
+static and rolling states: `init_decoding`, `decode`, `generate`; `next_tokens` is the greedy pick on a vocabulary table the
+state holds (ea_ceva_sdecode_vocab_argmax)."""
 import argparse
 import contextlib
+import functools
+import inspect
 
 import torch
 import torch.nn as nn
@@ -203,14 +206,57 @@ class DecoderLayer(nn.Module):
 class DecodingState:
     """What `DecoderStack.init_decoding` returns: `incremental` (the incremental state every layer's attention keeps its
     static or rolling state in, under its own key), `ffn` (per layer the held 16-bit (fc1.weight, fc1.bias, fc2.weight,
-    fc2.bias), or None without hold_weights) and the arguments it was made with (`options`)."""
+    fc2.bias), or None without hold_weights), the arguments it was made with (`options`) and, made with hold_vocab, `vocab`
+    (the 16-bit [V, C] copy of embed_tokens.weight) and `vocab_ws` (the pick's workspace, bytes); both None otherwise.
+    The fourth argument is that pair, (vocab, vocab_ws), or None."""
 
-    def __init__(self, incremental, ffn, options):
+    def __init__(self, incremental, ffn, options, vocab=None):
         self.incremental, self.ffn, self.options = incremental, ffn, options
+        self.vocab, self.vocab_ws = (None, None) if vocab is None else vocab
 
     @property
     def hold_weights(self):
         return self.ffn is not None
+
+    @property
+    def hold_vocab(self):
+        return self.vocab is not None
+
+
+_VOCAB = "ea_ceva_sdecode_vocab_argmax"
+
+
+def _hold_vocab_option(init):
+    """`init_decoding` with the keyword-only option `hold_vocab` on top of its parameters.  The parameter list of
+    `init_decoding` itself is pinned by the interface test (tests/test_decoder_stack_cpu.py compares the whole list), so the
+    option is taken off here, in front of it, and the state it returns is completed behind it; `functools.wraps` keeps the
+    pinned list what introspection reports.
+    hold_vocab=True: the DecodingState also holds `vocab`, a copy of embed_tokens.weight in the state's dtype (2 V C bytes,
+    taken once; `refresh_decoding_weights` re-reads it in place), and the workspace of ea_ceva_sdecode_vocab_argmax for 64
+    rows (8 * 64 * ceil(V / 16) bytes): `next_tokens` picks on them, and `generate` ends its step in that kernel.  A 16-bit
+    dtype only -- fp32 is refused with hold_weights' ValueError, before anything is allocated; independent of hold_weights
+    and of the attention's options."""
+    params = inspect.signature(init)
+
+    @functools.wraps(init)
+    def init_decoding(self, *args, hold_vocab=False, **kw):
+        if hold_vocab:
+            given = params.bind(self, *args, **kw).arguments
+            if given["dtype"] == torch.float32:
+                raise ValueError("hold_vocab=True holds 16-bit projection weights (the vocabulary table of the output "
+                                 "projection): an fp32 decoding state (the fidelity path) keeps the library's fp32 GEMM")
+        state = init(self, *args, **kw)
+        if hold_vocab:                                  # (a state made without the option is what it was, `options` included)
+            from efficient_attention import _native as nv
+            state.options["hold_vocab"] = True
+            w = self.embed_tokens.weight
+            dtype, device = state.options["dtype"], state.options["device"]
+            ws_bytes = nv.lib().ea_ceva_sdecode_vocab_ws(_FUSED_MAX_ROWS, w.shape[0])
+            state.vocab = torch.empty(w.shape, dtype=dtype, device=device)
+            state.vocab_ws = torch.empty(ws_bytes, dtype=torch.uint8, device=device)
+            self._load_held_vocab(state)
+        return state
+    return init_decoding
 
 
 class DecoderStack(nn.Module):
@@ -249,6 +295,7 @@ class DecoderStack(nn.Module):
         return F.linear(x, self.embed_tokens.weight)
 
     # ---- incremental decoding -----------------------------------------------------------------------------------------------
+    @_hold_vocab_option
     def init_decoding(self, batch_size, max_tokens, dtype, device, rolling=True, hold_weights=True, per_sequence=False,
                       landmark_splits=1, compact_landmarks=False, max_step_tokens=None):
         """One static (rolling=False) or rolling decoding state per layer's attention, made by `init_static_decoding` /
@@ -256,7 +303,8 @@ class DecoderStack(nn.Module):
         handed on and `hold_projections=hold_weights` -> a DecodingState.  With hold_weights (a 16-bit `dtype` only: fp32 is
         refused with the attention's ValueError) the state also holds 16-bit copies of every layer's fc1 / fc2 weights and
         biases, 2 (C F + F + F C + C) bytes per layer, taken here once: a capture fixes the weights, and
-        `refresh_decoding_weights` re-reads them.  `max_tokens` may not pass the position table."""
+        `refresh_decoding_weights` re-reads them.  `max_tokens` may not pass the position table.
+        Keyword-only, on top of these: `hold_vocab=False` (see `_hold_vocab_option`)."""
         if hold_weights:
             self.layers[0].self_attn._check_hold_projections(True, dtype)
         if int(max_tokens) > self.positions.shape[0]:
@@ -290,12 +338,19 @@ class DecoderStack(nn.Module):
                 for dst, src in zip(held, (layer.fc1.weight, layer.fc1.bias, layer.fc2.weight, layer.fc2.bias)):
                     dst.copy_(src)                      # (rounded to nearest even, in place: every data_ptr() stays)
 
+    def _load_held_vocab(self, state):
+        if state.vocab is not None:
+            with torch.no_grad():
+                state.vocab.copy_(self.embed_tokens.weight)     # (rounded to nearest even, in place: data_ptr() stays)
+
     def refresh_decoding_weights(self, state):
         """Re-read the parameters into what the state holds of them, in place and by device ops only: every layer's attention
-        (`CausalEVAttention.refresh_decoding_weights`) and the held fc1 / fc2.  A step captured before sees the new weights."""
+        (`CausalEVAttention.refresh_decoding_weights`), the held fc1 / fc2 and the held vocabulary table.  A step captured
+        before sees the new weights."""
         for layer in self.layers:
             layer.self_attn.refresh_decoding_weights(state.incremental)
         self._load_held_ffn(state)
+        self._load_held_vocab(state)
         return state
 
     def reorder_decoding_state(self, state, new_order):
@@ -309,9 +364,11 @@ class DecoderStack(nn.Module):
         return state
 
     def decoding_state_nbytes(self, state):
-        """Bytes of every layer's attention state and of the held feed-forward weights."""
+        """Bytes of every layer's attention state, of the held feed-forward weights and of the held vocabulary table with
+        its workspace."""
         n = sum(layer.self_attn.decoding_state_nbytes(state.incremental) for layer in self.layers)
-        return n + sum(t.numel() * t.element_size() for held in (state.ffn or ()) for t in held)
+        n += sum(t.numel() * t.element_size() for held in (state.ffn or ()) for t in held)
+        return n + sum(t.numel() * t.element_size() for t in (state.vocab, state.vocab_ws) if t is not None)
 
     def decoding_overflowed(self, state):
         """True once a step of any layer would have passed the state's capacity.  Reads device flags back."""
@@ -342,6 +399,45 @@ class DecoderStack(nn.Module):
             x = layer._feed_forward(x, None if state.ffn is None else state.ffn[i])
         return x if self.layer_norm is None else self.layer_norm(x)
 
+    def next_tokens(self, rows, state, out=None, return_logits=False):
+        """The greedy pick on the table the state holds: rows [T, B, C] (final-layer rows: what `decode` returns) -> int64
+        [T, B], token[t, b] = argmax_v sum_c round(rows[t, b, c]) vocab[v, c], on ea_ceva_sdecode_vocab_argmax: the table is
+        streamed once, the sums are fp32 and the pick is made ON THE FP32 SUMS under torch.argmax's rule (ties: the lowest
+        index).  `logits(rows).argmax(-1)` under autocast picks on logits already rounded to 16 bits; where two logits round
+        to the same 16-bit value the two can differ, and this one is the pick of the unrounded sums.
+        out: an int64 [T, B] contiguous tensor the tokens are written into (and returned) -- a captured step hands its own
+        static input.  return_logits=True: -> (tokens, fp32 [T, B, V] logits), for a caller that samples.  Rows that are
+        neither fp32 nor the table's type are widened to fp32 first (the kernel rounds fp32 rows to the table's type as it
+        loads them).  More than 64 rows run in pieces of 64.  Device launches only."""
+        if state.vocab is None:
+            raise RuntimeError("next_tokens needs a decoding state that holds the vocabulary table: "
+                               "init_decoding(..., hold_vocab=True)")
+        from efficient_attention import _native as nv
+        table, ws = state.vocab, state.vocab_ws
+        T, B, C = rows.shape
+        V = table.shape[0]
+        if C != table.shape[1]:
+            raise ValueError("rows of %d channels against a table of %d" % (C, table.shape[1]))
+        x2 = rows.detach()
+        if x2.dtype not in (torch.float32, table.dtype):
+            x2 = x2.float()
+        x2 = x2.contiguous().view(T * B, C)
+        if x2.data_ptr() % 16:
+            x2 = x2.clone()
+        if out is None:
+            out = torch.empty((T, B), dtype=torch.long, device=x2.device)
+        elif out.dtype != torch.long or tuple(out.shape) != (T, B) or not out.is_contiguous() or out.device != x2.device:
+            raise ValueError("out must be a contiguous int64 [%d, %d] tensor on the rows' device" % (T, B))
+        tok = out.view(T * B)
+        logits = torch.empty((T * B, V), dtype=torch.float32, device=x2.device) if return_logits else None
+        code = nv.EA_F32 if x2.dtype == torch.float32 else nv.io_dtype(x2)
+        for a in range(0, T * B, _FUSED_MAX_ROWS):
+            M = min(_FUSED_MAX_ROWS, T * B - a)
+            nv.call(_VOCAB, M, C, V, nv.ptr(x2[a:a + M]), code, C, nv.ptr(table), nv.io_dtype(table),
+                    None if logits is None else nv.ptr(logits[a:a + M]), nv.EA_F32, V, nv.ptr(ws), ws.numel(),
+                    nv.ptr(tok[a:a + M]), None, nv.stream())
+        return (out, logits.view(T, B, V)) if return_logits else out
+
     def generate(self, prompt, n_new, state=None, graph=True, return_rows=False):
         """Greedy decoding: prompt [B, P] int64 -> the n_new tokens that follow, [B, n_new] (return_rows: and the final-layer
         rows they were read from, [n_new, B, C]).  state: a fresh DecodingState of this stack (default: rolling, held weights,
@@ -350,7 +446,10 @@ class DecoderStack(nn.Module):
         graph=True: a warm-up step runs on a side stream, on a scratch state made with the same options, so that the state
         itself is untouched; then ONE single-token step -- embedding, layers, logits, argmax and the copy of the new token into
         the step's static input, device ops only -- is captured and replayed n_new - 1 times.  graph=False runs the same steps
-        eagerly: the same tokens and rows bit for bit.  An overflow flagged by any layer raises after the loop."""
+        eagerly: the same tokens and rows bit for bit.  An overflow flagged by any layer raises after the loop.
+        On a state made with hold_vocab both picks -- the first token's and the step's -- are `next_tokens`: the step ends in
+        ea_ceva_sdecode_vocab_argmax, which reads the held 16-bit table once, picks on the fp32 sums and writes the token
+        into the step's static input itself (no logits tensor, no argmax, no copy).  On any other state the path is unchanged."""
         if self.training:
             raise NotImplementedError("incremental decoding in training mode")
         B, P = prompt.shape
@@ -372,7 +471,9 @@ class DecoderStack(nn.Module):
                 last = x[(n_b - 1).clamp_(min=0), torch.arange(B, device=x.device)].unsqueeze(0)
             else:
                 last = x[P - 1:P]
-            tok_in = self.logits(last).argmax(-1)                            # [1, B]: the step's static input
+            held = state.vocab is not None
+            # [1, B]: the step's static input
+            tok_in = self.next_tokens(last, state) if held else self.logits(last).argmax(-1)
             out = torch.empty((B, n_new), dtype=torch.long, device=prompt.device)
             rows = torch.empty((n_new,) + tuple(last.shape[1:]), dtype=last.dtype, device=prompt.device) if return_rows else None
             out[:, 0] = tok_in[0]
@@ -381,11 +482,14 @@ class DecoderStack(nn.Module):
 
             def step(st):
                 y = self.decode(tok_in, st)
-                tok_in.copy_(self.logits(y).argmax(-1))
+                if held:                                                     # (the table and the workspace are `state`'s)
+                    self.next_tokens(y, state, out=tok_in)
+                else:
+                    tok_in.copy_(self.logits(y).argmax(-1))
                 return y
             g = None
             if graph and n_new > 1:
-                scratch = self.init_decoding(**dict(state.options, max_tokens=1))
+                scratch = self.init_decoding(**dict(state.options, max_tokens=1, hold_vocab=False))
                 first = tok_in.clone()
                 side = torch.cuda.Stream()
                 side.wait_stream(torch.cuda.current_stream())

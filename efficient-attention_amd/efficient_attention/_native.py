@@ -22,7 +22,7 @@ class ea_t4(ctypes.Structure):
                 ("sn", ctypes.c_int64)]
 
 
-ABI_VERSION = 25         # ea_abi_version() of include/ea_hip.h this file mirrors
+ABI_VERSION = 26         # ea_abi_version() of include/ea_hip.h this file mirrors
 
 
 class ea_geom(ctypes.Structure):
@@ -247,6 +247,8 @@ SIGNATURES = {
     "ea_ceva_sdecode_advance": [_SDG, _P],
     "ea_ceva_sdecode_linear": [_I, _I, _I, _P, _I, _L, _P, _I, _P, _P, _I, _L, _P],
     "ea_ceva_sdecode_linear_fused": [_I, _I, _I, _P, _I, _L, _P, _P, _F, _P, _I, _P, _I, _P, _I, _L, _P, _I, _L, _P],
+    "ea_ceva_sdecode_vocab_ws": [_I, _I],
+    "ea_ceva_sdecode_vocab_argmax": [_I, _I, _I, _P, _I, _L, _P, _I, _P, _I, _L, _P, _L, _P, _P, _P],
     "ea_softmax_attn_fwd": [_I, _I, _I, _I, _I, _F, _T, _T, _T, _P, _T, _P, _P, _F, _I, _P],
     "ea_softmax_sample": [_I, _I, _I, _I, _I, _F, _T, _T, _P, _P, _P],
     "ea_softmax_attn_bwd": [_I, _I, _I, _I, _I, _F, _T, _T, _T, _P, _T, _T, _P, _P, _T, _T, _T, _P, _F, _I, _P],
@@ -278,6 +280,7 @@ def lib():
         cdll.ea_lara_landmarks_saved_floats.restype = ctypes.c_int64
         cdll.ea_lara_layer_ws.restype = ctypes.c_int64
         cdll.ea_eva_layer_ws.restype = ctypes.c_int64
+        cdll.ea_ceva_sdecode_vocab_ws.restype = ctypes.c_int64
         cdll.ea_version.restype = ctypes.c_char_p
         cdll.ea_abi_version.restype = ctypes.c_int32
         if cdll.ea_abi_version() != ABI_VERSION:

@@ -1094,6 +1094,30 @@ int ea_ceva_sdecode_linear_fused(int32_t M, int32_t K, int32_t N, const void* x,
                                  const void* bias, int32_t act, const void* res, int32_t res_dtype, int64_t ldr, void* y,
                                  int32_t y_dtype, int64_t ldy, void* stream);
 
+/* ABI 26, the greedy token pick of a decoding step on a vocabulary table the state holds (ea_harness
+ * DecoderStack.next_tokens, init_decoding(hold_vocab=True); ea_ceva_decode_vocab.hip):
+ *   logit[m, v] = sum_k round_w(x[m, k]) w[v, k]        fp32, no bias;  1 <= M <= EA_CEVA_LINEAR_MAX_ROWS, any V >= 1
+ *   token[m]    = the index of the largest logit[m, 0 .. V - 1]; of equal values the lowest index; in a row that holds NaN
+ *                 logits the lowest index that holds one (torch.argmax's rule), decided on the fp32 sums
+ *   top[m]      = logit[m, token[m]]
+ * x [M, ldx] rows of x_dtype = EA_F32 or w_dtype (fp32 rows are rounded to w_dtype, to nearest even, as they are loaded);
+ * w [V, K] row-major of w_dtype = EA_BF16 | EA_F16.  A logit is summed by the operations of ea_ceva_sdecode_linear in their
+ * order: it has that entry's bits (bias NULL).  logits: NULL (nothing is stored), or [M, ldl] rows of logits_dtype = EA_F32 |
+ * w_dtype (logits_dtype and ldl are not read without logits); columns >= V and rows >= M are not touched.  token [M] int64,
+ * top [M] fp32 or NULL.  Two launches: one workgroup per 16 table rows reads them once and writes one (value, index)
+ * candidate per row of x to ws; one workgroup per row of x reduces its candidates.  No atomics, no workgroup waits for
+ * another: bitwise reproducible.  ws: ea_ceva_sdecode_vocab_ws(M, V) bytes (8 M ceil(V / 16); grows with M and with V, so
+ * one sized for 64 rows serves every M); that query returns < 0 for M < 1, M > 64 or V < 1.
+ * EA_E_BADARG: x, w, ws, token NULL; x, w or ws not 16-byte aligned, token not 8-byte, top not 4-byte aligned, logits not
+ * aligned to its element; w_dtype not a 16-bit type; x_dtype neither EA_F32 nor w_dtype; with logits: logits_dtype neither
+ * EA_F32 nor w_dtype, ldl < V; M < 1, K < 1, ldx < K; a row stride of x that is no multiple of 16 bytes; ws_bytes below the
+ * query's answer.  EA_E_UNSUPPORTED: M > 64, K % 32 != 0, V < 1.  Bad arguments are decided before the geometry, everything
+ * before any launch. */
+int64_t ea_ceva_sdecode_vocab_ws(int32_t M, int32_t V);
+int ea_ceva_sdecode_vocab_argmax(int32_t M, int32_t K, int32_t V, const void* x, int32_t x_dtype, int64_t ldx,
+                                 const void* w, int32_t w_dtype, void* logits, int32_t logits_dtype, int64_t ldl,
+                                 void* ws, int64_t ws_bytes, int64_t* token, float* top, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

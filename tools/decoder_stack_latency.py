@@ -10,17 +10,29 @@ After a prefill of `context` tokens fed in pieces of one window: a warm-up step 
 the median over 5 blocks of `steps` replayed tokens, each block timed by the host clock around its replays and a device
 synchronise.  One line per (batch, mode): ms per token and ms per token and layer.  With --hold both the two modes run one after the
 other in this process and the largest difference of their rows is printed (rounding: 16-bit weights, other summation orders).
-For a table, run the modes alternately in processes of their own, at least three times each."""
+For a table, run the modes alternately in processes of their own, at least three times each.
+
+--generate times the whole captured greedy step of `DecoderStack.generate` instead -- embedding, positions, 16 layers, the pick
+of the next token and its write-back into the step's static input -- on held weights, replayed with nothing fed from the host:
+   --hold-vocab 1: the pick is `next_tokens` (ea_ceva_sdecode_vocab_argmax on the 16-bit table the state holds);
+   --hold-vocab 0: the pick is `logits(y).argmax(-1)` and `tok_in.copy_`, the framework's cast, GEMM and argmax.
+   python tools/decoder_stack_latency.py --generate --hold-vocab 0|1 [--vocab 32768|262144] [--root CHECKOUT]       (GPU)
+One line per batch: the median ms per token over the blocks, their smallest and largest, and the pick alone (a captured graph of
+the pick on one row set, replayed) as us and as GB/s on the 2 V C bytes of a 16-bit table.  --root names the checkout whose
+package is timed (default: this one; it needs its library built: `python CHECKOUT/efficient-attention_amd/build.py`); where that package does not know `hold_vocab` -- a checkout of an earlier commit --
+--hold-vocab 1 is reported as unavailable and the plain pick is timed, so that the same command line serves both."""
 import argparse
 import os
 import sys
 import time
 import warnings
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+_root = argparse.ArgumentParser(add_help=False)           # --root decides where the imports below come from
+_root.add_argument("--root", default=os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+ROOT = os.path.abspath(_root.parse_known_args()[0].root)
 sys.path[:0] = [ROOT, os.path.join(ROOT, "efficient-attention_amd")]
 import torch  # noqa: E402
-from ea_harness.sequence import wikitext103_decoder  # noqa: E402
+from ea_harness.sequence import DecoderStack, wikitext103_decoder  # noqa: E402
 
 warnings.simplefilter("ignore")
 WINDOW, LAYERS = 128, 16
@@ -69,15 +81,93 @@ def run(stack, B, context, hold, steps, blocks=5, warmup=4):
     return sorted(times)[len(times) // 2], torch.cat(rows, 0), nbytes
 
 
+def run_generate(stack, B, context, hold_vocab, steps, blocks=5, warmup=4):
+    """The captured greedy step replayed -> (block times in ms per token, pick alone in us, decoding_state_nbytes)."""
+    n_tok = context + 2 + warmup + blocks * steps
+    g = torch.Generator().manual_seed(1)
+    tokens = torch.randint(2, stack.embed_tokens.num_embeddings, (context, B), generator=g).cuda()
+    with torch.no_grad(), torch.autocast("cuda", dtype=torch.bfloat16, cache_enabled=False):
+        opt = dict(hold_vocab=True) if hold_vocab else {}
+        state = stack.init_decoding(B, n_tok, torch.bfloat16, "cuda", rolling=True, hold_weights=True, **opt)
+        for a in range(0, context, WINDOW):
+            y = stack.decode(tokens[a:min(a + WINDOW, context)], state)
+        y = y[-1:].clone()
+
+        def pick(rows, out):
+            if hold_vocab:
+                stack.next_tokens(rows, state, out=out)
+            else:
+                out.copy_(stack.logits(rows).argmax(-1))
+        tok_in = torch.zeros((1, B), dtype=torch.long, device="cuda")
+        pick(y, tok_in)
+
+        def step():
+            pick(stack.decode(tok_in, state), tok_in)
+
+        def captured(fn):
+            side = torch.cuda.Stream()
+            side.wait_stream(torch.cuda.current_stream())
+            with torch.cuda.stream(side):
+                fn()                                           # eager on a side stream: the warm-up
+            torch.cuda.current_stream().wait_stream(side)
+            graph = torch.cuda.CUDAGraph()
+            with torch.cuda.graph(graph):
+                fn()
+            return graph
+
+        def timed(graph):
+            for _ in range(warmup):
+                graph.replay()
+            torch.cuda.synchronize()
+            times = []
+            for _ in range(blocks):
+                t0 = time.perf_counter()
+                for _ in range(steps):
+                    graph.replay()
+                torch.cuda.synchronize()
+                times.append((time.perf_counter() - t0) * 1e3 / steps)
+            return times
+        times = timed(captured(step))
+        if stack.decoding_overflowed(state):
+            raise RuntimeError("the decoding state overflowed")
+        scratch = torch.zeros_like(tok_in)
+        alone = timed(captured(lambda: pick(y, scratch)))
+        nbytes = stack.decoding_state_nbytes(state)
+    return times, sorted(alone)[len(alone) // 2] * 1e3, nbytes
+
+
+def main_generate(a):
+    known = hasattr(DecoderStack, "next_tokens")
+    hold_vocab = a.hold_vocab == 1 and known
+    if a.hold_vocab == 1 and not known:
+        print("the package under %s does not know hold_vocab: timing its plain pick (logits, argmax, copy_)" % ROOT)
+    torch.manual_seed(0)
+    stack = wikitext103_decoder(vocab=a.vocab, max_positions=a.context + 1024).cuda().eval()
+    V, C = stack.embed_tokens.weight.shape
+    print("ms per token, wikitext103_decoder (%d layers, vocab %d), bf16, rolling states, held weights, context %d, the captured "
+          "greedy step replayed; package %s" % (LAYERS, V, a.context, ROOT))
+    for B in [int(b) for b in a.batches.split(",")]:
+        times, pick_us, nbytes = run_generate(stack, B, a.context, hold_vocab, a.steps)
+        print("B %2d  hold_vocab=%-5s  %8.3f ms per token (blocks %.3f .. %.3f)  pick alone %8.1f us = %7.1f GB/s on 2 V C bytes"
+              "  state %d bytes" % (B, hold_vocab, sorted(times)[len(times) // 2], min(times), max(times), pick_us,
+                                    2.0 * V * C / (pick_us * 1e-6) / 1e9, nbytes), flush=True)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--context", type=int, default=512, help="tokens before the timed steps; DESIGN.md 4a uses 512 and 4096")
     ap.add_argument("--batches", default="1,8", help="comma-separated batch sizes")
     ap.add_argument("--hold", default="both", choices=["0", "1", "both"])
     ap.add_argument("--steps", type=int, default=64)
+    ap.add_argument("--generate", action="store_true", help="time the whole captured greedy step (see the module docstring)")
+    ap.add_argument("--hold-vocab", type=int, default=1, choices=[0, 1], help="with --generate: the pick on the held table")
+    ap.add_argument("--vocab", type=int, default=32768, help="with --generate: rows of the vocabulary table")
+    ap.add_argument("--root", default=ROOT, help="the checkout whose package is timed (default: this one)")
     a = ap.parse_args()
     if not torch.cuda.is_available():
         raise SystemExit("decoder_stack_latency.py needs a GPU: a latency is measured on one or not at all")
+    if a.generate:
+        return main_generate(a)
     torch.manual_seed(0)
     stack = wikitext103_decoder(max_positions=a.context + 1024).cuda().eval()
     modes = {"0": [False], "1": [True], "both": [False, True]}[a.hold]
