@@ -1,4 +1,5 @@
-// ea_ceva_decode_vocab.h -- parameter block of the greedy token pick on a held vocabulary table (ea_ceva_decode_vocab.hip)
+// ea_ceva_decode_vocab.h -- parameter blocks of the greedy and the sampled token pick on a held vocabulary table
+// (ea_ceva_decode_vocab.hip)
 #pragma once
 #include <stdint.h>
 #include <hip/hip_runtime.h>
@@ -26,8 +27,29 @@ struct DecVocabP {
   int x_f32, l_f32;           // 1: fp32 rows (x is rounded to `dtype` on load)
 };
 
+constexpr int VOC_SAMPLE_MAX_K = 64;  // top_k of the sampled pick: the selection is sorted by one wave
+
+// the sampled pick's second launch (ceva_vocab_sample_kernel); a block of its own: DecVocabP is ceva_vocab_kernel's
+// parameter and stays what it is
+struct DecSampleP {
+  const VocPick* ws;          // [M, ceil(V / 16)] candidates of the first launch
+  const float* logits;        // [M, ldl] fp32 logits of the first launch
+  int64_t* token;             // [M]
+  int64_t* ctr;               // [M] draw counters, read and advanced by one
+  const int32_t* sid;         // [M] stream ids
+  int32_t* sel_idx;           // [M, top_k] the selection in order, or null
+  float* sel_val;             // [M, top_k], or null
+  int32_t* kept;              // [M], or null
+  int64_t ldl;
+  int V, top_k;
+  float top_p, temperature;
+  uint32_t seed_lo, seed_hi;
+};
+
 // bytes of ws for (M, V); < 0: outside the envelope
 int64_t ceva_sdecode_vocab_ws(int M, int V);
 int ceva_sdecode_vocab_argmax(const DecVocabP& p, hipStream_t st);
+// the first launch on p (token and top are not read), the second on s
+int ceva_sdecode_vocab_sample(const DecVocabP& p, const DecSampleP& s, hipStream_t st);
 
 }  // namespace ea

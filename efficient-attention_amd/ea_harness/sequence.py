@@ -10,11 +10,12 @@ are the attention module's own, as in the reference adapter.
 DecoderLayer / DecoderStack are the decoder-only language model of the wikitext-103 recipe around `CausalEVAttention`
 (fairseq/modules/transformer_layer.py:236-308 without the encoder attention), with incremental decoding on the attention's
 static and rolling states: `init_decoding`, `decode`, `generate`; `next_tokens` is the greedy pick on a vocabulary table the
-state holds (ea_ceva_sdecode_vocab_argmax)."""
+state holds (ea_ceva_sdecode_vocab_argmax), `init_sampling` / `sample_tokens` the sampled one (ea_ceva_sdecode_vocab_sample)."""
 import argparse
 import contextlib
 import functools
 import inspect
+import math
 
 import torch
 import torch.nn as nn
@@ -208,7 +209,10 @@ class DecodingState:
     static or rolling state in, under its own key), `ffn` (per layer the held 16-bit (fc1.weight, fc1.bias, fc2.weight,
     fc2.bias), or None without hold_weights), the arguments it was made with (`options`) and, made with hold_vocab, `vocab`
     (the 16-bit [V, C] copy of embed_tokens.weight) and `vocab_ws` (the pick's workspace, bytes); both None otherwise.
-    The fourth argument is that pair, (vocab, vocab_ws), or None."""
+    The fourth argument is that pair, (vocab, vocab_ws), or None.
+    `sampler` is None until `DecoderStack.init_sampling` attaches a Sampler."""
+
+    sampler = None
 
     def __init__(self, incremental, ffn, options, vocab=None):
         self.incremental, self.ffn, self.options = incremental, ffn, options
@@ -224,6 +228,20 @@ class DecodingState:
 
 
 _VOCAB = "ea_ceva_sdecode_vocab_argmax"
+_SAMPLE = "ea_ceva_sdecode_vocab_sample"
+_SAMPLE_MAX_K = 64
+
+
+class Sampler:
+    """What `DecoderStack.init_sampling` attaches to a DecodingState: the fp32 `logits` buffer [batch_size, V] of the sampled
+    pick, the draw counters `ctr` (int64 [B]: draw n of a row is made at ctr = n) and the stream ids `sid` (int32 [B]), both
+    on the device, the host scalars `seed`, `top_k`, `top_p`, `temperature`, and `next_sid`, the first stream id no row of
+    this state has had."""
+
+    def __init__(self, logits, ctr, sid, seed, top_k, top_p, temperature):
+        self.logits, self.ctr, self.sid = logits, ctr, sid
+        self.seed, self.top_k, self.top_p, self.temperature = seed, top_k, top_p, temperature
+        self.next_sid = sid.numel()
 
 
 def _hold_vocab_option(init):
@@ -356,19 +374,34 @@ class DecoderStack(nn.Module):
     def reorder_decoding_state(self, state, new_order):
         for layer in self.layers:
             layer.self_attn.reorder_incremental_state(state.incremental, new_order)
+        sm = state.sampler
+        if sm is not None:                              # a row takes its stream along: counters and ids, in place
+            order = new_order.to(device=sm.ctr.device, dtype=torch.long)
+            sm.ctr.copy_(sm.ctr.index_select(0, order))
+            sm.sid.copy_(sm.sid.index_select(0, order))
         return state
 
     def reset_decoding_rows(self, state, rows):
         for layer in self.layers:
             layer.self_attn.reset_decoding_rows(state.incremental, rows)
+        sm = state.sampler
+        if sm is not None:                              # a new sequence: draw 0 of a stream no row has had
+            at = torch.as_tensor(rows, device=sm.ctr.device).reshape(-1).long()
+            if at.numel():                              # (how many is known on the host: no read-back)
+                fresh = torch.arange(sm.next_sid, sm.next_sid + at.numel(), dtype=torch.int32, device=sm.sid.device)
+                sm.next_sid += at.numel()
+                sm.ctr.index_fill_(0, at, 0)
+                sm.sid.index_copy_(0, at, fresh)
         return state
 
     def decoding_state_nbytes(self, state):
-        """Bytes of every layer's attention state, of the held feed-forward weights and of the held vocabulary table with
-        its workspace."""
+        """Bytes of every layer's attention state, of the held feed-forward weights, of the held vocabulary table with
+        its workspace and of a sampler's logits, counters and stream ids (4 B V + 8 B + 4 B)."""
         n = sum(layer.self_attn.decoding_state_nbytes(state.incremental) for layer in self.layers)
         n += sum(t.numel() * t.element_size() for held in (state.ffn or ()) for t in held)
-        return n + sum(t.numel() * t.element_size() for t in (state.vocab, state.vocab_ws) if t is not None)
+        sm = state.sampler
+        extra = () if sm is None else (sm.logits, sm.ctr, sm.sid)
+        return n + sum(t.numel() * t.element_size() for t in (state.vocab, state.vocab_ws) + extra if t is not None)
 
     def decoding_overflowed(self, state):
         """True once a step of any layer would have passed the state's capacity.  Reads device flags back."""
@@ -438,6 +471,76 @@ class DecoderStack(nn.Module):
                     nv.ptr(tok[a:a + M]), None, nv.stream())
         return (out, logits.view(T, B, V)) if return_logits else out
 
+    def init_sampling(self, state, seed, top_k, top_p=1.0, temperature=1.0):
+        """Make `state` (made with hold_vocab=True) sample its tokens: `sample_tokens` draws on it, and `generate` takes both
+        of its picks from there.  A token is drawn from the `top_k` (1 .. 64) largest logits of its row, softmax weights at
+        `temperature` (> 0), cut to the smallest head of that list whose weight reaches `top_p` (0 < top_p <= 1) of the
+        list's -- ea_ceva_sdecode_vocab_sample, include/ea_hip.h.  The draws are Philox4x32-10 words keyed by `seed`
+        (0 .. 2^64 - 1) at the counter (ctr[b], sid[b]): row b starts as stream b at draw 0, every draw advances ctr[b] on the
+        device, so a captured step draws afresh at every replay; `reorder_decoding_state` moves (ctr, sid) with the rows and
+        `reset_decoding_rows` starts a reset row on a stream id no row of this state has had.  A row's tokens are therefore
+        what it would draw decoded alone with its (seed, sid), whatever batch it sits in.
+        Attaches `state.sampler` (a Sampler: fp32 logits [batch_size, V], ctr, sid, the scalars; 4 B V + 12 B bytes; the
+        pick's workspace is `vocab_ws`) and returns the state.  Values outside the envelope raise ValueError before anything
+        is allocated; full-vocabulary sampling stays with `next_tokens(return_logits=True)`."""
+        if state.vocab is None:
+            raise RuntimeError("init_sampling needs a decoding state that holds the vocabulary table: "
+                               "init_decoding(..., hold_vocab=True)")
+        seed, top_k, top_p, temperature = int(seed), int(top_k), float(top_p), float(temperature)
+        if not 1 <= top_k <= _SAMPLE_MAX_K:
+            raise ValueError("top_k must be in 1 .. %d, got %d" % (_SAMPLE_MAX_K, top_k))
+        if not 0.0 < top_p <= 1.0:
+            raise ValueError("top_p must be in (0, 1], got %r" % top_p)
+        if not (math.isfinite(temperature) and temperature > 0.0):
+            raise ValueError("temperature must be finite and > 0, got %r" % temperature)
+        if not 0 <= seed < 1 << 64:
+            raise ValueError("seed must be in 0 .. 2^64 - 1, got %d" % seed)
+        B, device = state.options["batch_size"], state.vocab.device
+        state.sampler = Sampler(torch.empty((B, state.vocab.shape[0]), dtype=torch.float32, device=device),
+                                torch.zeros(B, dtype=torch.long, device=device),
+                                torch.arange(B, dtype=torch.int32, device=device), seed, top_k, top_p, temperature)
+        return state
+
+    def sample_tokens(self, rows, state, out=None, return_details=False):
+        """The sampled pick on a state with a sampler (`init_sampling`): rows [1, B, C] (final-layer rows of a single-token
+        step, B <= 64 and at most the state's batch size) -> int64 [1, B], one draw per row from ea_ceva_sdecode_vocab_sample on
+        the held table; row b draws at (ctr[b], sid[b]) and its counter advances.  out: as in `next_tokens`.
+        return_details=True: -> (tokens, sel_idx int32 [B, top_k], sel_val fp32 [B, top_k], kept int32 [B]): the selection in
+        order (entries from min(top_k, V) on are not written; log-probabilities follow from sel_val), and how many of it the
+        nucleus kept (0: a row whose best logit is NaN or infinite, which gets the greedy pick).  Device launches only."""
+        sm = state.sampler
+        if sm is None:
+            raise RuntimeError("sample_tokens needs a decoding state with a sampler: init_sampling(state, seed, top_k, ...)")
+        from efficient_attention import _native as nv
+        table, ws = state.vocab, state.vocab_ws
+        T, B, C = rows.shape
+        V = table.shape[0]
+        if T != 1 or B > min(_FUSED_MAX_ROWS, sm.ctr.numel()):
+            raise ValueError("sample_tokens takes the rows of one single-token step, [1, B <= %d, C]; got %s"
+                             % (min(_FUSED_MAX_ROWS, sm.ctr.numel()), tuple(rows.shape)))
+        if C != table.shape[1]:
+            raise ValueError("rows of %d channels against a table of %d" % (C, table.shape[1]))
+        x2 = rows.detach()
+        if x2.dtype not in (torch.float32, table.dtype):
+            x2 = x2.float()
+        x2 = x2.contiguous().view(B, C)
+        if x2.data_ptr() % 16:
+            x2 = x2.clone()
+        if out is None:
+            out = torch.empty((1, B), dtype=torch.long, device=x2.device)
+        elif out.dtype != torch.long or tuple(out.shape) != (1, B) or not out.is_contiguous() or out.device != x2.device:
+            raise ValueError("out must be a contiguous int64 [1, %d] tensor on the rows' device" % B)
+        details = None
+        if return_details:
+            details = (torch.empty((B, sm.top_k), dtype=torch.int32, device=x2.device),
+                       torch.empty((B, sm.top_k), dtype=torch.float32, device=x2.device),
+                       torch.empty((B,), dtype=torch.int32, device=x2.device))
+        code = nv.EA_F32 if x2.dtype == torch.float32 else nv.io_dtype(x2)
+        nv.call(_SAMPLE, B, C, V, nv.ptr(x2), code, C, nv.ptr(table), nv.io_dtype(table), nv.ptr(sm.logits), V, nv.ptr(ws),
+                ws.numel(), sm.top_k, sm.top_p, sm.temperature, sm.seed, nv.ptr(sm.ctr), nv.ptr(sm.sid), nv.ptr(out),
+                *((None, None, None) if details is None else [nv.ptr(t) for t in details]), nv.stream())
+        return (out,) + details if return_details else out
+
     def generate(self, prompt, n_new, state=None, graph=True, return_rows=False):
         """Greedy decoding: prompt [B, P] int64 -> the n_new tokens that follow, [B, n_new] (return_rows: and the final-layer
         rows they were read from, [n_new, B, C]).  state: a fresh DecodingState of this stack (default: rolling, held weights,
@@ -449,7 +552,10 @@ class DecoderStack(nn.Module):
         eagerly: the same tokens and rows bit for bit.  An overflow flagged by any layer raises after the loop.
         On a state made with hold_vocab both picks -- the first token's and the step's -- are `next_tokens`: the step ends in
         ea_ceva_sdecode_vocab_argmax, which reads the held 16-bit table once, picks on the fp32 sums and writes the token
-        into the step's static input itself (no logits tensor, no argmax, no copy).  On any other state the path is unchanged."""
+        into the step's static input itself (no logits tensor, no argmax, no copy).  On any other state the path is unchanged.
+        On a state with a sampler (`init_sampling`) both picks are `sample_tokens` instead: sampled, not greedy, decoding.  The
+        warm-up's draw is undone -- the counters are saved before it and restored behind it -- so replayed and eager runs
+        draw the same tokens."""
         if self.training:
             raise NotImplementedError("incremental decoding in training mode")
         B, P = prompt.shape
@@ -472,8 +578,9 @@ class DecoderStack(nn.Module):
             else:
                 last = x[P - 1:P]
             held = state.vocab is not None
+            pick = self.next_tokens if state.sampler is None else self.sample_tokens
             # [1, B]: the step's static input
-            tok_in = self.next_tokens(last, state) if held else self.logits(last).argmax(-1)
+            tok_in = pick(last, state) if held else self.logits(last).argmax(-1)
             out = torch.empty((B, n_new), dtype=torch.long, device=prompt.device)
             rows = torch.empty((n_new,) + tuple(last.shape[1:]), dtype=last.dtype, device=prompt.device) if return_rows else None
             out[:, 0] = tok_in[0]
@@ -483,7 +590,7 @@ class DecoderStack(nn.Module):
             def step(st):
                 y = self.decode(tok_in, st)
                 if held:                                                     # (the table and the workspace are `state`'s)
-                    self.next_tokens(y, state, out=tok_in)
+                    pick(y, state, out=tok_in)
                 else:
                     tok_in.copy_(self.logits(y).argmax(-1))
                 return y
@@ -491,12 +598,15 @@ class DecoderStack(nn.Module):
             if graph and n_new > 1:
                 scratch = self.init_decoding(**dict(state.options, max_tokens=1, hold_vocab=False))
                 first = tok_in.clone()
+                drawn = None if state.sampler is None else state.sampler.ctr.clone()
                 side = torch.cuda.Stream()
                 side.wait_stream(torch.cuda.current_stream())
                 with torch.cuda.stream(side):
                     step(scratch)
                 torch.cuda.current_stream().wait_stream(side)
                 tok_in.copy_(first)
+                if drawn is not None:                                        # (the warm-up drew once)
+                    state.sampler.ctr.copy_(drawn)
                 del scratch
                 g = torch.cuda.CUDAGraph()
                 with torch.cuda.graph(g):

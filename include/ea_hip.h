@@ -1118,6 +1118,39 @@ int ea_ceva_sdecode_vocab_argmax(int32_t M, int32_t K, int32_t V, const void* x,
                                  const void* w, int32_t w_dtype, void* logits, int32_t logits_dtype, int64_t ldl,
                                  void* ws, int64_t ws_bytes, int64_t* token, float* top, void* stream);
 
+/* ABI 27, the SAMPLED token pick on that table (ea_harness DecoderStack.init_sampling, sample_tokens): temperature, top-k and
+ * top-p inside the top-k, drawn from a counter-based generator whose per-row counters live on the device.  Two launches.
+ * The first is ea_ceva_sdecode_vocab_argmax's first: fp32 logits into logits [M, ldl] (required here; they have
+ * ea_ceva_sdecode_linear's bits) and one (value, index) candidate per 16-column tile into ws.  The second, one workgroup per
+ * row of x; (value, index) pairs are ordered as the greedy pick orders them -- the larger value first, equal values (+0 and
+ * -0 too) by the lower index, NaN (every NaN alike) above every number -- a total order:
+ *   1. of the row's NB = ceil(V / 16) candidates the min(top_k, NB) best: the top_k best logits lie in those tiles;
+ *   2. of those tiles' logits (columns < V) the k' = min(top_k, V) best, in order: val_0 .. val_{k'-1}, their columns sel_idx;
+ *   3. w_j = exp((val_j - val_0) / temperature) in fp32 (expf of library accuracy), c_j = ((w_0 + w_1) + ..) + w_j;
+ *   4. kept = the smallest n >= 1 with c_{n-1} >= top_p c_{k'-1}; top_p = 1: k';
+ *   5. n = ctr[m]; Philox4x32-10 with the key (seed's low word, seed's high word) and the counter (n's low word, n's high
+ *      word, sid[m], 0); u = ((word 0 >> 8) + 0.5) 2^-24 in fp32 (rounded to nearest even where the sum has 25 bits: never 0;
+ *      1 for the one largest word); r = u c_{kept-1}; token[m] = sel_idx[j] for the first j < kept with c_j > r, j = kept - 1
+ *      when none is; ctr[m] = n + 1.
+ *   6. val_0 NaN or infinite: token[m] = sel_idx[0] (the greedy pick's answer), kept = 0, ctr[m] = n + 1.  (A -inf entry
+ *      further down has weight 0.)
+ * Only row m's workgroup touches ctr[m]; no atomics on memory, no workgroup waits for another: token is a function of the
+ * row's logits, (seed, ctr[m], sid[m]) and the three scalars -- not of the batch the row sits in, nor of its position in it.
+ * token [M] int64; ctr [M] int64 in / out; sid [M] int32; optional sel_idx [M, top_k] int32, sel_val [M, top_k] fp32 (the
+ * stored logits' bits) and kept [M] int32 report the selection: entries j >= k' are not written.  top_k, top_p, temperature
+ * and seed are host scalars: a capture fixes them.  ws: ea_ceva_sdecode_vocab_sample_ws(M, V) bytes, which is
+ * ea_ceva_sdecode_vocab_ws(M, V): the two entries can share one workspace.
+ * EA_E_BADARG: what ea_ceva_sdecode_vocab_argmax answers with it (pointers, alignment, types, strides, ws_bytes); logits,
+ * ctr or sid NULL; logits, sid, sel_idx, sel_val or kept not 4-byte, ctr not 8-byte aligned; top_p outside (0, 1];
+ * temperature not finite or <= 0; top_k < 1.  EA_E_UNSUPPORTED: top_k > 64, M > 64, K % 32 != 0, V < 1.  Bad arguments are
+ * decided before the geometry, everything before any launch. */
+int64_t ea_ceva_sdecode_vocab_sample_ws(int32_t M, int32_t V);
+int ea_ceva_sdecode_vocab_sample(int32_t M, int32_t K, int32_t V, const void* x, int32_t x_dtype, int64_t ldx,
+                                 const void* w, int32_t w_dtype, float* logits, int64_t ldl, void* ws, int64_t ws_bytes,
+                                 int32_t top_k, float top_p, float temperature, uint64_t seed, int64_t* ctr,
+                                 const int32_t* sid, int64_t* token, int32_t* sel_idx, float* sel_val, int32_t* kept,
+                                 void* stream);
+
 #ifdef __cplusplus
 }
 #endif

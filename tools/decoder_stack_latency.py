@@ -20,7 +20,14 @@ of the next token and its write-back into the step's static input -- on held wei
 One line per batch: the median ms per token over the blocks, their smallest and largest, and the pick alone (a captured graph of
 the pick on one row set, replayed) as us and as GB/s on the 2 V C bytes of a 16-bit table.  --root names the checkout whose
 package is timed (default: this one; it needs its library built: `python CHECKOUT/efficient-attention_amd/build.py`); where that package does not know `hold_vocab` -- a checkout of an earlier commit --
---hold-vocab 1 is reported as unavailable and the plain pick is timed, so that the same command line serves both."""
+--hold-vocab 1 is reported as unavailable and the plain pick is timed, so that the same command line serves both.
+
+--generate --sample K,P,T times the captured SAMPLED step (top_k, top_p, temperature) on a held table:
+   a package with `DecoderStack.init_sampling`: the pick is `sample_tokens` (ea_ceva_sdecode_vocab_sample; device counters);
+   a package without it (--root an earlier checkout): the framework sampler, written with that checkout's interface --
+       `next_tokens(rows, state, return_logits=True)`, then torch.topk, torch.softmax at the temperature, torch.multinomial
+       and `tok_in.copy_`, all inside the capture (no nucleus cut: fewer launches than a full equivalent, in its favour).
+   python tools/decoder_stack_latency.py --generate --sample 40,0.9,1.0 [--vocab 32768|262144] [--root CHECKOUT]   (GPU)"""
 import argparse
 import os
 import sys
@@ -81,8 +88,9 @@ def run(stack, B, context, hold, steps, blocks=5, warmup=4):
     return sorted(times)[len(times) // 2], torch.cat(rows, 0), nbytes
 
 
-def run_generate(stack, B, context, hold_vocab, steps, blocks=5, warmup=4):
-    """The captured greedy step replayed -> (block times in ms per token, pick alone in us, decoding_state_nbytes)."""
+def run_generate(stack, B, context, hold_vocab, steps, blocks=5, warmup=4, sample=None):
+    """The captured greedy step (sample = (top_k, top_p, temperature): the sampled step) replayed -> (block times in ms per
+    token, pick alone in us, decoding_state_nbytes)."""
     n_tok = context + 2 + warmup + blocks * steps
     g = torch.Generator().manual_seed(1)
     tokens = torch.randint(2, stack.embed_tokens.num_embeddings, (context, B), generator=g).cuda()
@@ -92,9 +100,19 @@ def run_generate(stack, B, context, hold_vocab, steps, blocks=5, warmup=4):
         for a in range(0, context, WINDOW):
             y = stack.decode(tokens[a:min(a + WINDOW, context)], state)
         y = y[-1:].clone()
+        native = sample is not None and hasattr(stack, "init_sampling")
+        if native:
+            stack.init_sampling(state, 1234, sample[0], sample[1], sample[2])
 
         def pick(rows, out):
-            if hold_vocab:
+            if native:
+                stack.sample_tokens(rows, state, out=out)
+            elif sample is not None:                           # the framework sampler on the fp32 logits handed back
+                _, logits = stack.next_tokens(rows, state, return_logits=True)
+                val, idx = torch.topk(logits[0], sample[0], dim=-1)
+                j = torch.multinomial(torch.softmax(val / sample[2], -1), 1)
+                out.copy_(idx.gather(1, j).t())
+            elif hold_vocab:
                 stack.next_tokens(rows, state, out=out)
             else:
                 out.copy_(stack.logits(rows).argmax(-1))
@@ -138,6 +156,16 @@ def run_generate(stack, B, context, hold_vocab, steps, blocks=5, warmup=4):
 
 def main_generate(a):
     known = hasattr(DecoderStack, "next_tokens")
+    sample = None
+    if a.sample:
+        k, p, t = a.sample.split(",")
+        sample = (int(k), float(p), float(t))
+        if not known:
+            raise SystemExit("--sample needs a package with hold_vocab (next_tokens(return_logits=True) is its yardstick)")
+        a.hold_vocab = 1
+        print("sampled step, top_k %d, top_p %g, temperature %g: %s" % (sample + (
+            "sample_tokens (ea_ceva_sdecode_vocab_sample)" if hasattr(DecoderStack, "init_sampling") else
+            "the framework sampler (next_tokens(return_logits=True), topk, softmax, multinomial, copy_)",)))
     hold_vocab = a.hold_vocab == 1 and known
     if a.hold_vocab == 1 and not known:
         print("the package under %s does not know hold_vocab: timing its plain pick (logits, argmax, copy_)" % ROOT)
@@ -147,7 +175,7 @@ def main_generate(a):
     print("ms per token, wikitext103_decoder (%d layers, vocab %d), bf16, rolling states, held weights, context %d, the captured "
           "greedy step replayed; package %s" % (LAYERS, V, a.context, ROOT))
     for B in [int(b) for b in a.batches.split(",")]:
-        times, pick_us, nbytes = run_generate(stack, B, a.context, hold_vocab, a.steps)
+        times, pick_us, nbytes = run_generate(stack, B, a.context, hold_vocab, a.steps, sample=sample)
         print("B %2d  hold_vocab=%-5s  %8.3f ms per token (blocks %.3f .. %.3f)  pick alone %8.1f us = %7.1f GB/s on 2 V C bytes"
               "  state %d bytes" % (B, hold_vocab, sorted(times)[len(times) // 2], min(times), max(times), pick_us,
                                     2.0 * V * C / (pick_us * 1e-6) / 1e9, nbytes), flush=True)
@@ -162,6 +190,7 @@ def main():
     ap.add_argument("--generate", action="store_true", help="time the whole captured greedy step (see the module docstring)")
     ap.add_argument("--hold-vocab", type=int, default=1, choices=[0, 1], help="with --generate: the pick on the held table")
     ap.add_argument("--vocab", type=int, default=32768, help="with --generate: rows of the vocabulary table")
+    ap.add_argument("--sample", default="", help="with --generate: K,P,T -- time the sampled step (see the module docstring)")
     ap.add_argument("--root", default=ROOT, help="the checkout whose package is timed (default: this one)")
     a = ap.parse_args()
     if not torch.cuda.is_available():
