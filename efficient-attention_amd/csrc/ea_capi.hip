@@ -81,7 +81,7 @@ static Geo mk_geo(const ea_geom* g) {
 extern "C" {
 
 const char* ea_version(void) { return "ea_hip 0.1.0 gfx950"; }
-int32_t ea_abi_version(void) { return 27; }
+int32_t ea_abi_version(void) { return 28; }
 
 int32_t ea_window_bias_ld(const ea_geom* g) {
   WinTiling t;
@@ -2460,6 +2460,72 @@ int ea_ceva_sdecode_vocab_sample(int32_t M, int32_t K, int32_t V, const void* x,
   s.sel_idx = sel_idx; s.sel_val = sel_val; s.kept = kept; s.ldl = ldl; s.V = V; s.top_k = top_k;
   s.top_p = top_p; s.temperature = temperature; s.seed_lo = (uint32_t)seed; s.seed_hi = (uint32_t)(seed >> 32);
   return ea::ceva_sdecode_vocab_sample(p, s, (hipStream_t)stream);
+}
+
+int64_t ea_ceva_sdecode_vocab_lse_ws(int32_t M, int32_t V) { return ea::ceva_sdecode_vocab_lse_ws(M, V); }
+
+int ea_ceva_sdecode_vocab_logprob(int32_t M, int32_t K, int32_t V, const void* x, int32_t x_dtype, int64_t ldx,
+                                  const void* w, int32_t w_dtype, void* logits, int32_t logits_dtype, int64_t ldl,
+                                  void* ws, int64_t ws_bytes, int64_t* token, float* top, void* lws, int64_t lws_bytes,
+                                  const int64_t* targets, float* lse, float* logp, void* stream) {
+  // ea_ceva_sdecode_vocab_argmax's refusals in its order, then this entry's own, and the geometry last
+  if (!x || !w || !ws || !token || (uintptr_t)x % 16 || (uintptr_t)w % 16 || (uintptr_t)ws % 16) return EA_E_BADARG;
+  if ((uintptr_t)token % 8 || (uintptr_t)top % 4) return EA_E_BADARG;
+  if (w_dtype != EA_BF16 && w_dtype != EA_F16) return EA_E_BADARG;
+  if (x_dtype != EA_F32 && x_dtype != w_dtype) return EA_E_BADARG;
+  if (logits && ((logits_dtype != EA_F32 && logits_dtype != w_dtype) || (uintptr_t)logits % (logits_dtype == EA_F32 ? 4 : 2)))
+    return EA_E_BADARG;
+  if (M < 1 || K < 1 || ldx < K || (logits && ldl < V)) return EA_E_BADARG;
+  if (ldx * (x_dtype == EA_F32 ? 4 : 2) % 16) return EA_E_BADARG;
+  const int64_t need = ea::ceva_sdecode_vocab_ws(M, V);           // (< 0: a geometry refused below)
+  if (need >= 0 && ws_bytes < need) return EA_E_BADARG;
+  if (!lws || !lse || !logp || (uintptr_t)lws % 16 || (uintptr_t)lse % 4 || (uintptr_t)logp % 4 || (uintptr_t)targets % 8)
+    return EA_E_BADARG;
+  const int64_t lneed = ea::ceva_sdecode_vocab_lse_ws(M, V);
+  if (lneed >= 0 && lws_bytes < lneed) return EA_E_BADARG;
+  if (M > EA_CEVA_LINEAR_MAX_ROWS || K % 32 || V < 1) return EA_E_UNSUPPORTED;
+  ea::DecLseP p = {};
+  p.x = (const char*)x; p.w = (const char*)w; p.logits = (char*)logits; p.ws = (ea::VocPick*)ws; p.token = token; p.top = top;
+  p.lws = (float*)lws; p.tlogit = p.lws + (int64_t)M * ((V - 1) / ea::VOC_TILE + 1); p.targets = targets;
+  p.lse = lse; p.logp = logp;
+  p.ldx = ldx; p.ldl = logits ? ldl : 0; p.M = M; p.K = K; p.V = V; p.dtype = w_dtype;
+  p.x_f32 = x_dtype == EA_F32; p.l_f32 = logits && logits_dtype == EA_F32;
+  return ea::ceva_sdecode_vocab_logprob(p, (hipStream_t)stream);
+}
+
+int ea_ceva_sdecode_vocab_sample_logprob(int32_t M, int32_t K, int32_t V, const void* x, int32_t x_dtype, int64_t ldx,
+                                         const void* w, int32_t w_dtype, float* logits, int64_t ldl, void* ws,
+                                         int64_t ws_bytes, int32_t top_k, float top_p, float temperature, uint64_t seed,
+                                         int64_t* ctr, const int32_t* sid, int64_t* token, int32_t* sel_idx, float* sel_val,
+                                         int32_t* kept, void* lws, int64_t lws_bytes, float* lse, float* logp, void* stream) {
+  // ea_ceva_sdecode_vocab_sample's refusals in its order, then this entry's own, and the geometry last
+  if (!x || !w || !ws || !token || (uintptr_t)x % 16 || (uintptr_t)w % 16 || (uintptr_t)ws % 16) return EA_E_BADARG;
+  if ((uintptr_t)token % 8) return EA_E_BADARG;
+  if (w_dtype != EA_BF16 && w_dtype != EA_F16) return EA_E_BADARG;
+  if (x_dtype != EA_F32 && x_dtype != w_dtype) return EA_E_BADARG;
+  if (!logits || (uintptr_t)logits % 4) return EA_E_BADARG;
+  if (M < 1 || K < 1 || ldx < K || ldl < V) return EA_E_BADARG;
+  if (ldx * (x_dtype == EA_F32 ? 4 : 2) % 16) return EA_E_BADARG;
+  const int64_t need = ea::ceva_sdecode_vocab_ws(M, V);           // (< 0: a geometry refused below)
+  if (need >= 0 && ws_bytes < need) return EA_E_BADARG;
+  if (!ctr || !sid || (uintptr_t)ctr % 8 || (uintptr_t)sid % 4) return EA_E_BADARG;
+  if ((uintptr_t)sel_idx % 4 || (uintptr_t)sel_val % 4 || (uintptr_t)kept % 4) return EA_E_BADARG;
+  if (!(top_p > 0.f && top_p <= 1.f) || !(std::isfinite(temperature) && temperature > 0.f) || top_k < 1) return EA_E_BADARG;
+  if (!lws || !lse || !logp || (uintptr_t)lws % 16 || (uintptr_t)lse % 4 || (uintptr_t)logp % 4) return EA_E_BADARG;
+  const int64_t lneed = ea::ceva_sdecode_vocab_lse_ws(M, V);
+  if (lneed >= 0 && lws_bytes < lneed) return EA_E_BADARG;
+  if (top_k > 64 || M > EA_CEVA_LINEAR_MAX_ROWS || K % 32 || V < 1) return EA_E_UNSUPPORTED;
+  ea::DecLseP p = {};
+  p.x = (const char*)x; p.w = (const char*)w; p.logits = (char*)logits; p.ws = (ea::VocPick*)ws;
+  p.lws = (float*)lws; p.tlogit = p.lws + (int64_t)M * ((V - 1) / ea::VOC_TILE + 1); p.token_in = token;
+  p.lse = lse; p.logp = logp;
+  p.ldx = ldx; p.ldl = ldl; p.M = M; p.K = K; p.V = V; p.dtype = w_dtype;
+  p.x_f32 = x_dtype == EA_F32; p.l_f32 = 1;
+  ea::DecSampleP s = {};
+  s.ws = p.ws; s.logits = logits; s.token = token; s.ctr = ctr; s.sid = sid;
+  s.sel_idx = sel_idx; s.sel_val = sel_val; s.kept = kept; s.ldl = ldl; s.V = V; s.top_k = top_k;
+  s.top_p = top_p; s.temperature = temperature; s.seed_lo = (uint32_t)seed; s.seed_hi = (uint32_t)(seed >> 32);
+  return ea::ceva_sdecode_vocab_sample_logprob(p, s, (hipStream_t)stream);
 }
 
 }  // extern "C"

@@ -1,4 +1,5 @@
-// ea_ceva_decode_vocab.h -- parameter blocks of the greedy and the sampled token pick on a held vocabulary table
+// ea_ceva_decode_vocab.h -- parameter blocks of the greedy and the sampled token pick and of the token log-probabilities on a
+// held vocabulary table
 // (ea_ceva_decode_vocab.hip)
 #pragma once
 #include <stdint.h>
@@ -46,10 +47,43 @@ struct DecSampleP {
   uint32_t seed_lo, seed_hi;
 };
 
+// token log-probabilities (ABI 28): the parameter block of ceva_vocab_lse_kernel (the table pass that also writes one
+// sum exp(logit - tile maximum) per tile) and of ceva_vocab_lse_pick_kernel (the pick, the log-sum-exp and the
+// log-probability); a block of its own: DecVocabP and DecSampleP stay what they are.
+//   lse[m]  = log sum_v exp(logit[m, v]) over the whole row: the RAW distribution, temperature 1, nothing truncated -- in the
+//             sampled mode too, whatever temperature, top_k and top_p the draw was made with
+//   logp[m] = tl - lse[m]; tl: logits[m, token_in[m]] in the sampled mode (token_in set), else logit[m, targets[m]] when
+//             targets are given (a target outside [0, V): NaN), else top[m]
+struct DecLseP {
+  const char* x;              // [M, ldx] rows, fp32 or the table's type
+  const char* w;              // [V, K] row-major 16-bit table
+  char* logits;               // [M, ldl] rows, fp32 or the table's type, or null (the sampled mode: fp32, required)
+  VocPick* ws;                // [M, ceil(V / 16)] partial picks (m_t, i_t)
+  float* lws;                 // [M, ceil(V / 16)] s_t = sum over the tile's columns of exp(logit - m_t)
+  float* tlogit;              // [M] the targets' logits
+  const int64_t* targets;     // [M], or null
+  const int64_t* token_in;    // [M] the tokens drawn before the second launch: the sampled mode; or null
+  int64_t* token;             // [M]; not written in the sampled mode
+  float* top;                 // [M], or null; not written in the sampled mode
+  float* lse;                 // [M]
+  float* logp;                // [M]
+  int64_t ldx, ldl;           // row strides in elements
+  int M, K, V;                // 1 <= M <= 64, K % 32 == 0, V >= 1
+  int dtype;                  // EA_BF16 | EA_F16: w
+  int x_f32, l_f32;           // 1: fp32 rows (x is rounded to `dtype` on load)
+};
+
 // bytes of ws for (M, V); < 0: outside the envelope
 int64_t ceva_sdecode_vocab_ws(int M, int V);
 int ceva_sdecode_vocab_argmax(const DecVocabP& p, hipStream_t st);
 // the first launch on p (token and top are not read), the second on s
 int ceva_sdecode_vocab_sample(const DecVocabP& p, const DecSampleP& s, hipStream_t st);
+
+// bytes of lws and tlogit together for (M, V); < 0: outside the envelope
+int64_t ceva_sdecode_vocab_lse_ws(int M, int V);
+// the table pass with tile sums, then the pick with lse and logp
+int ceva_sdecode_vocab_logprob(const DecLseP& p, hipStream_t st);
+// the table pass with tile sums on p, ceva_vocab_sample_kernel on s, then lse and logp of the drawn tokens (p.token_in = s.token)
+int ceva_sdecode_vocab_sample_logprob(const DecLseP& p, const DecSampleP& s, hipStream_t st);
 
 }  // namespace ea

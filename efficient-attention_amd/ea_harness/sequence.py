@@ -10,7 +10,9 @@ are the attention module's own, as in the reference adapter.
 DecoderLayer / DecoderStack are the decoder-only language model of the wikitext-103 recipe around `CausalEVAttention`
 (fairseq/modules/transformer_layer.py:236-308 without the encoder attention), with incremental decoding on the attention's
 static and rolling states: `init_decoding`, `decode`, `generate`; `next_tokens` is the greedy pick on a vocabulary table the
-state holds (ea_ceva_sdecode_vocab_argmax), `init_sampling` / `sample_tokens` the sampled one (ea_ceva_sdecode_vocab_sample)."""
+state holds (ea_ceva_sdecode_vocab_argmax), `init_sampling` / `sample_tokens` the sampled one (ea_ceva_sdecode_vocab_sample);
+`init_logprobs` / `token_logprobs` / `sample_tokens_logprobs` / `score` report a token's log-probability under the model's own
+distribution from the same pass over the table (ea_ceva_sdecode_vocab_logprob, ea_ceva_sdecode_vocab_sample_logprob)."""
 import argparse
 import contextlib
 import functools
@@ -210,9 +212,11 @@ class DecodingState:
     fc2.bias), or None without hold_weights), the arguments it was made with (`options`) and, made with hold_vocab, `vocab`
     (the 16-bit [V, C] copy of embed_tokens.weight) and `vocab_ws` (the pick's workspace, bytes); both None otherwise.
     The fourth argument is that pair, (vocab, vocab_ws), or None.
-    `sampler` is None until `DecoderStack.init_sampling` attaches a Sampler."""
+    `sampler` is None until `DecoderStack.init_sampling` attaches a Sampler, `scorer` until `DecoderStack.init_logprobs`
+    attaches a Scorer."""
 
     sampler = None
+    scorer = None
 
     def __init__(self, incremental, ffn, options, vocab=None):
         self.incremental, self.ffn, self.options = incremental, ffn, options
@@ -230,6 +234,8 @@ class DecodingState:
 _VOCAB = "ea_ceva_sdecode_vocab_argmax"
 _SAMPLE = "ea_ceva_sdecode_vocab_sample"
 _SAMPLE_MAX_K = 64
+_LOGPROB = "ea_ceva_sdecode_vocab_logprob"
+_SAMPLE_LOGPROB = "ea_ceva_sdecode_vocab_sample_logprob"
 
 
 class Sampler:
@@ -242,6 +248,15 @@ class Sampler:
         self.logits, self.ctr, self.sid = logits, ctr, sid
         self.seed, self.top_k, self.top_p, self.temperature = seed, top_k, top_p, temperature
         self.next_sid = sid.numel()
+
+
+class Scorer:
+    """What `DecoderStack.init_logprobs` attaches to a DecodingState: `ws`, the tile sums and target logits of
+    ea_ceva_sdecode_vocab_logprob for 64 rows (bytes), and the static fp32 buffers `lse` and `logp` [batch_size] a captured
+    step writes its log-sum-exp and its token's log-probability into."""
+
+    def __init__(self, ws, lse, logp):
+        self.ws, self.lse, self.logp = ws, lse, logp
 
 
 def _hold_vocab_option(init):
@@ -396,11 +411,15 @@ class DecoderStack(nn.Module):
 
     def decoding_state_nbytes(self, state):
         """Bytes of every layer's attention state, of the held feed-forward weights, of the held vocabulary table with
-        its workspace and of a sampler's logits, counters and stream ids (4 B V + 8 B + 4 B)."""
+        its workspace, of a sampler's logits, counters and stream ids (4 B V + 8 B + 4 B) and of a scorer's workspace and
+        buffers (4 * 64 * (ceil(V / 16) + 1) + 8 B)."""
         n = sum(layer.self_attn.decoding_state_nbytes(state.incremental) for layer in self.layers)
         n += sum(t.numel() * t.element_size() for held in (state.ffn or ()) for t in held)
         sm = state.sampler
         extra = () if sm is None else (sm.logits, sm.ctr, sm.sid)
+        sc = state.scorer
+        if sc is not None:
+            extra += (sc.ws, sc.lse, sc.logp)
         return n + sum(t.numel() * t.element_size() for t in (state.vocab, state.vocab_ws) + extra if t is not None)
 
     def decoding_overflowed(self, state):
@@ -541,7 +560,145 @@ class DecoderStack(nn.Module):
                 *((None, None, None) if details is None else [nv.ptr(t) for t in details]), nv.stream())
         return (out,) + details if return_details else out
 
-    def generate(self, prompt, n_new, state=None, graph=True, return_rows=False):
+    def init_logprobs(self, state):
+        """Make `state` (made with hold_vocab=True) report log-probabilities: `token_logprobs`, `sample_tokens_logprobs`,
+        `score` and `generate(return_logprobs=True)` run on it.  A log-probability is log softmax(logits)[token] of the row's
+        WHOLE, raw distribution at temperature 1 -- of a sampled token too, whatever the sampler's temperature, top_k and
+        top_p -- formed in the pass that picks the token: ea_ceva_sdecode_vocab_logprob, include/ea_hip.h.
+        Attaches `state.scorer` (a Scorer: the workspace for 64 rows, 4 * 64 * (ceil(V / 16) + 1) bytes, and fp32 `lse`,
+        `logp` [batch_size]) and returns the state.  A beam reorder, a row reset and a weight refresh have nothing of it to
+        move."""
+        if state.vocab is None:
+            raise RuntimeError("init_logprobs needs a decoding state that holds the vocabulary table: "
+                               "init_decoding(..., hold_vocab=True)")
+        from efficient_attention import _native as nv
+        B, device = state.options["batch_size"], state.vocab.device
+        nbytes = nv.lib().ea_ceva_sdecode_vocab_lse_ws(_FUSED_MAX_ROWS, state.vocab.shape[0])
+        state.scorer = Scorer(torch.empty(nbytes, dtype=torch.uint8, device=device),
+                              torch.empty(B, dtype=torch.float32, device=device),
+                              torch.empty(B, dtype=torch.float32, device=device))
+        return state
+
+    def _vocab_rows(self, rows, state, single_step):
+        """rows [T, B, C] -> the [T B, C] operand of the vocabulary kernels (fp32 or the table's type, 16-byte aligned)."""
+        table = state.vocab
+        T, B, C = rows.shape
+        if single_step and (T != 1 or B > min(_FUSED_MAX_ROWS, state.sampler.ctr.numel())):
+            raise ValueError("a sampled pick takes the rows of one single-token step, [1, B <= %d, C]; got %s"
+                             % (min(_FUSED_MAX_ROWS, state.sampler.ctr.numel()), tuple(rows.shape)))
+        if C != table.shape[1]:
+            raise ValueError("rows of %d channels against a table of %d" % (C, table.shape[1]))
+        x2 = rows.detach()
+        if x2.dtype not in (torch.float32, table.dtype):
+            x2 = x2.float()
+        x2 = x2.contiguous().view(T * B, C)
+        if x2.data_ptr() % 16:
+            x2 = x2.clone()
+        return x2
+
+    @staticmethod
+    def _vocab_out(out, shape, dtype, device, what):
+        if out is None:
+            return torch.empty(shape, dtype=dtype, device=device)
+        if out.dtype != dtype or tuple(out.shape) != tuple(shape) or not out.is_contiguous() or out.device != device:
+            raise ValueError("%s must be a contiguous %s %s tensor on the rows' device"
+                             % (what, str(dtype).replace("torch.", ""), list(shape)))
+        return out
+
+    def _logprob_pick(self, rows, state, targets, out, logp, lse):
+        """`token_logprobs` with the places of logp and lse [T, B] given (None: allocated)."""
+        if state.vocab is None or state.scorer is None:
+            raise RuntimeError("token_logprobs needs a decoding state with a scorer: init_logprobs(state), on a state made "
+                               "with init_decoding(..., hold_vocab=True)")
+        from efficient_attention import _native as nv
+        table, ws, lws = state.vocab, state.vocab_ws, state.scorer.ws
+        T, B, C = rows.shape
+        V = table.shape[0]
+        x2 = self._vocab_rows(rows, state, False)
+        dev = x2.device
+        out = self._vocab_out(out, (T, B), torch.long, dev, "out")
+        logp = self._vocab_out(logp, (T, B), torch.float32, dev, "logp")
+        lse = self._vocab_out(lse, (T, B), torch.float32, dev, "lse")
+        if targets is not None:
+            if targets.dtype != torch.long or tuple(targets.shape) != (T, B) or targets.device != dev:
+                raise ValueError("targets must be an int64 [%d, %d] tensor on the rows' device" % (T, B))
+            targets = targets.contiguous().view(T * B)
+        tok, lp, ls = out.view(T * B), logp.view(T * B), lse.view(T * B)
+        code = nv.EA_F32 if x2.dtype == torch.float32 else nv.io_dtype(x2)
+        for a in range(0, T * B, _FUSED_MAX_ROWS):
+            M = min(_FUSED_MAX_ROWS, T * B - a)
+            nv.call(_LOGPROB, M, C, V, nv.ptr(x2[a:a + M]), code, C, nv.ptr(table), nv.io_dtype(table), None, nv.EA_F32, V,
+                    nv.ptr(ws), ws.numel(), nv.ptr(tok[a:a + M]), None, nv.ptr(lws), lws.numel(),
+                    None if targets is None else nv.ptr(targets[a:a + M]), nv.ptr(ls[a:a + M]), nv.ptr(lp[a:a + M]),
+                    nv.stream())
+        return out, logp, lse
+
+    def token_logprobs(self, rows, state, targets=None, out=None, return_lse=False):
+        """The greedy pick of `next_tokens` and a log-probability per row, on a state with a scorer (`init_logprobs`): rows
+        [T, B, C] -> (tokens int64 [T, B], logp fp32 [T, B]); return_lse=True: and lse fp32 [T, B], the log-sum-exp of the row's
+        fp32 logits.  logp[t, b] = logit[targets[t, b]] - lse with `targets` (int64 [T, B] on the device; one outside [0, V)
+        gives NaN), else the picked token's, top - lse.  `tokens` is the greedy pick either way, bit for bit `next_tokens`'.
+        The distribution is the model's own at temperature 1; the table is streamed once per 64 rows, no [T B, V] tensor
+        exists.  A row's results do not depend on the rows beside it.  out: as in `next_tokens`.  Device launches only."""
+        tokens, logp, lse = self._logprob_pick(rows, state, targets, out, None, None)
+        return (tokens, logp, lse) if return_lse else (tokens, logp)
+
+    def _sample_logprob_pick(self, rows, state, out, logp, lse):
+        sm, sc = state.sampler, state.scorer
+        if sm is None or sc is None:
+            raise RuntimeError("sample_tokens_logprobs needs a decoding state with a sampler and a scorer: "
+                               "init_sampling(state, seed, top_k, ...) and init_logprobs(state)")
+        from efficient_attention import _native as nv
+        table, ws = state.vocab, state.vocab_ws
+        T, B, C = rows.shape
+        V = table.shape[0]
+        x2 = self._vocab_rows(rows, state, True)
+        dev = x2.device
+        out = self._vocab_out(out, (1, B), torch.long, dev, "out")
+        logp = self._vocab_out(logp, (1, B), torch.float32, dev, "logp")
+        lse = self._vocab_out(lse, (1, B), torch.float32, dev, "lse")
+        code = nv.EA_F32 if x2.dtype == torch.float32 else nv.io_dtype(x2)
+        nv.call(_SAMPLE_LOGPROB, B, C, V, nv.ptr(x2), code, C, nv.ptr(table), nv.io_dtype(table), nv.ptr(sm.logits), V,
+                nv.ptr(ws), ws.numel(), sm.top_k, sm.top_p, sm.temperature, sm.seed, nv.ptr(sm.ctr), nv.ptr(sm.sid),
+                nv.ptr(out), None, None, None, nv.ptr(sc.ws), sc.ws.numel(), nv.ptr(lse), nv.ptr(logp), nv.stream())
+        return out, logp, lse
+
+    def sample_tokens_logprobs(self, rows, state, out=None):
+        """`sample_tokens` and the drawn tokens' log-probabilities, on a state with a sampler and a scorer: rows [1, B, C] ->
+        (tokens int64 [1, B], logp fp32 [1, B]).  The tokens, and the counters behind them, are `sample_tokens`' at the same
+        (seed, ctr, sid).  logp is the token's log-probability under the RAW distribution at temperature 1 -- not inside the
+        top-k list or the nucleus, not at the sampler's temperature.  Device launches only."""
+        tokens, logp, _ = self._sample_logprob_pick(rows, state, out, None, None)
+        return tokens, logp
+
+    def score(self, tokens, state=None):
+        """Teacher-forced log-probabilities: tokens [B, T] int64 -> fp32 [B, T - 1], entry [b, t] = log p(tokens[b, t + 1] |
+        tokens[b, :t + 1]) under the model's own distribution; entries whose target is `pad_idx` are 0.  One `decode` of
+        tokens[:, :-1] on `state` (a fresh state with a scorer; default: one made here with hold_vocab and the autocast or
+        the weights' 16-bit dtype), then `token_logprobs` with the targets.  The vocabulary table is re-streamed once per 64
+        rows of T - 1 times B: this serves prompt scoring, not corpus-scale evaluation."""
+        if self.training:
+            raise NotImplementedError("incremental decoding in training mode")
+        B, T = tokens.shape
+        if T < 2:
+            raise ValueError("score needs at least two tokens per row, got %d" % T)
+        amp = torch.is_autocast_enabled()
+        ctx = torch.autocast("cuda", dtype=torch.get_autocast_dtype("cuda"), cache_enabled=False) if amp \
+            else contextlib.nullcontext()
+        with torch.no_grad(), ctx:
+            if state is None:
+                dtype = torch.get_autocast_dtype("cuda") if amp else self.embed_tokens.weight.dtype
+                state = self.init_logprobs(self.init_decoding(B, T - 1, dtype, tokens.device, hold_vocab=True))
+            elif state.scorer is None:
+                raise RuntimeError("score needs a decoding state with a scorer: init_logprobs(state)")
+            fed = tokens[:, :-1]
+            mask = fed.eq(self.pad_idx) if state.options["per_sequence"] else None
+            rows = self.decode(fed.t(), state, mask)                         # [T - 1, B, C]
+            targets = tokens[:, 1:].t().contiguous()
+            _, logp = self.token_logprobs(rows, state, targets=targets)
+            return logp.masked_fill_(targets.eq(self.pad_idx), 0.0).t().contiguous()
+
+    def generate(self, prompt, n_new, state=None, graph=True, return_rows=False, return_logprobs=False):
         """Greedy decoding: prompt [B, P] int64 -> the n_new tokens that follow, [B, n_new] (return_rows: and the final-layer
         rows they were read from, [n_new, B, C]).  state: a fresh DecodingState of this stack (default: rolling, held weights,
         the autocast dtype).  The prompt is fed eagerly in one `decode`; on a per-sequence state it may be ragged and
@@ -555,13 +712,22 @@ class DecoderStack(nn.Module):
         into the step's static input itself (no logits tensor, no argmax, no copy).  On any other state the path is unchanged.
         On a state with a sampler (`init_sampling`) both picks are `sample_tokens` instead: sampled, not greedy, decoding.  The
         warm-up's draw is undone -- the counters are saved before it and restored behind it -- so replayed and eager runs
-        draw the same tokens."""
+        draw the same tokens.
+        return_logprobs=True (a state with a scorer, `init_logprobs`; its absence is reported before the prefill): both picks
+        run on ea_ceva_sdecode_vocab_logprob / ea_ceva_sdecode_vocab_sample_logprob instead and write each token's
+        log-probability under the model's own distribution (temperature 1, nothing truncated) into the scorer's static
+        buffer; -> (tokens[, rows], logp fp32 [B, n_new]).  The tokens are those of the same call without the keyword."""
         if self.training:
             raise NotImplementedError("incremental decoding in training mode")
         B, P = prompt.shape
         n_new = int(n_new)
         if n_new < 1:
             raise ValueError("generate needs n_new >= 1, got %d" % n_new)
+        if return_logprobs:
+            if state is None or state.scorer is None:
+                raise RuntimeError("generate(return_logprobs=True) needs a decoding state with a scorer: init_logprobs(state)")
+            if B > state.scorer.logp.numel():
+                raise ValueError("a prompt of %d rows on a scorer made for %d" % (B, state.scorer.logp.numel()))
         amp = torch.is_autocast_enabled()
         ctx = torch.autocast("cuda", dtype=torch.get_autocast_dtype("cuda"), cache_enabled=False) if amp \
             else contextlib.nullcontext()                        # (a capture may not use autocast's weight-cast cache)
@@ -579,6 +745,16 @@ class DecoderStack(nn.Module):
                 last = x[P - 1:P]
             held = state.vocab is not None
             pick = self.next_tokens if state.sampler is None else self.sample_tokens
+            lp_in = logps = None
+            if return_logprobs:                                              # [1, B] views of the scorer's static buffers
+                lp_in, lse_in = state.scorer.logp[:B].view(1, B), state.scorer.lse[:B].view(1, B)
+                logps = torch.empty((B, n_new), dtype=torch.float32, device=prompt.device)
+                if state.sampler is None:
+                    def pick(y, st, out=None):
+                        return self._logprob_pick(y, st, None, out, lp_in, lse_in)[0]
+                else:
+                    def pick(y, st, out=None):
+                        return self._sample_logprob_pick(y, st, out, lp_in, lse_in)[0]
             # [1, B]: the step's static input
             tok_in = pick(last, state) if held else self.logits(last).argmax(-1)
             out = torch.empty((B, n_new), dtype=torch.long, device=prompt.device)
@@ -586,6 +762,8 @@ class DecoderStack(nn.Module):
             out[:, 0] = tok_in[0]
             if rows is not None:
                 rows[0] = last[0]
+            if logps is not None:
+                logps[:, 0] = lp_in[0]
 
             def step(st):
                 y = self.decode(tok_in, st)
@@ -619,9 +797,13 @@ class DecoderStack(nn.Module):
                 out[:, i] = tok_in[0]
                 if rows is not None:
                     rows[i] = y[0]
+                if logps is not None:
+                    logps[:, i] = lp_in[0]
             if self.decoding_overflowed(state):
                 raise RuntimeError("the decoding state overflowed: a step passed its %d tokens (init_decoding(max_tokens=...))"
                                    % state.options["max_tokens"])
+        if logps is not None:
+            return (out, rows, logps) if return_rows else (out, logps)
         return (out, rows) if return_rows else out
 
 

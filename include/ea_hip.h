@@ -1151,6 +1151,41 @@ int ea_ceva_sdecode_vocab_sample(int32_t M, int32_t K, int32_t V, const void* x,
                                  const int32_t* sid, int64_t* token, int32_t* sel_idx, float* sel_val, int32_t* kept,
                                  void* stream);
 
+/* ABI 28, TOKEN LOG-PROBABILITIES on that table (ea_harness DecoderStack.init_logprobs, token_logprobs,
+ * sample_tokens_logprobs, score): what the greedy and the sampled pick give, and with it
+ *   lse[m]  = log sum_{v < V} exp(logit[m, v])          the normaliser of the row's whole, RAW distribution
+ *   logp[m] = tl - lse[m]                               one fp32 subtraction
+ * The log-probability is that of the model's own, untruncated distribution at temperature 1 -- in the sampled entry too,
+ * whatever temperature, top_k and top_p the token was drawn with (what serving stacks report by default).
+ * ea_ceva_sdecode_vocab_logprob, two launches.  The first is ea_ceva_sdecode_vocab_argmax's first (logits, candidates and
+ * therefore token and top have that entry's bits) and besides writes, per row and 16-column tile t with the maximum m_t,
+ * s_t = sum over the tile's columns < V of expf(logit - m_t), summed by an xor butterfly (offsets 8, 4, 2, 1), to lws; with
+ * targets it also keeps logit[m, targets[m]].  The second, one workgroup of 512 threads per row, reduces the candidates to
+ * token[m], top[m] as the greedy pick does, then by cases on top[m]: NaN -> lse NaN; +inf -> +inf; -inf (every logit is
+ * -inf) -> -inf; else lse = top + logf(S), S = sum_t s_t expf(m_t - top) over the tiles with m_t != -inf (such a tile is
+ * skipped, never multiplied), each thread its tiles t = thread, thread + 512, .. in order, six xor exchanges per wave, the 8
+ * waves added in wave order.  tl is logit[m, targets[m]] with targets (int64 [M], on the device; a target outside [0, V):
+ * logp NaN), top[m] without.  Ordinary stores only, no atomics, no workgroup waits for another: bitwise reproducible, and a
+ * row's results do not depend on its batch, nor on whether logits are stored.  lse, logp [M] fp32.
+ * lws: ea_ceva_sdecode_vocab_lse_ws(M, V) bytes (4 M ceil(V / 16) + 4 M: the tile sums and the targets' logits; grows with M
+ * and V); < 0 for M < 1, M > 64 or V < 1.  ws is ea_ceva_sdecode_vocab_ws(M, V) bytes as before.
+ * ea_ceva_sdecode_vocab_sample_logprob, three launches: that first launch, ea_ceva_sdecode_vocab_sample's second unchanged
+ * (token, ctr, sel_idx, sel_val, kept are that entry's), then the second launch above with tl = logits[m, token[m]], the
+ * stored fp32 logit of the token just drawn; token and top are not written by it.
+ * EA_E_BADARG: what ea_ceva_sdecode_vocab_argmax / ea_ceva_sdecode_vocab_sample answer with it; lws, lse or logp NULL; lws
+ * not 16-byte, lse or logp not 4-byte, targets not 8-byte aligned; lws_bytes below the query's answer.  EA_E_UNSUPPORTED:
+ * what those entries answer with it.  Bad arguments are decided before the geometry, everything before any launch. */
+int64_t ea_ceva_sdecode_vocab_lse_ws(int32_t M, int32_t V);
+int ea_ceva_sdecode_vocab_logprob(int32_t M, int32_t K, int32_t V, const void* x, int32_t x_dtype, int64_t ldx,
+                                  const void* w, int32_t w_dtype, void* logits, int32_t logits_dtype, int64_t ldl,
+                                  void* ws, int64_t ws_bytes, int64_t* token, float* top, void* lws, int64_t lws_bytes,
+                                  const int64_t* targets, float* lse, float* logp, void* stream);
+int ea_ceva_sdecode_vocab_sample_logprob(int32_t M, int32_t K, int32_t V, const void* x, int32_t x_dtype, int64_t ldx,
+                                         const void* w, int32_t w_dtype, float* logits, int64_t ldl, void* ws,
+                                         int64_t ws_bytes, int32_t top_k, float top_p, float temperature, uint64_t seed,
+                                         int64_t* ctr, const int32_t* sid, int64_t* token, int32_t* sel_idx, float* sel_val,
+                                         int32_t* kept, void* lws, int64_t lws_bytes, float* lse, float* logp, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

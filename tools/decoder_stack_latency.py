@@ -27,7 +27,14 @@ package is timed (default: this one; it needs its library built: `python CHECKOU
    a package without it (--root an earlier checkout): the framework sampler, written with that checkout's interface --
        `next_tokens(rows, state, return_logits=True)`, then torch.topk, torch.softmax at the temperature, torch.multinomial
        and `tok_in.copy_`, all inside the capture (no nucleus cut: fewer launches than a full equivalent, in its favour).
-   python tools/decoder_stack_latency.py --generate --sample 40,0.9,1.0 [--vocab 32768|262144] [--root CHECKOUT]   (GPU)"""
+   python tools/decoder_stack_latency.py --generate --sample 40,0.9,1.0 [--vocab 32768|262144] [--root CHECKOUT]   (GPU)
+
+--generate --hold-vocab 1 --logprobs times the captured greedy step that also writes the token's log-probability (ABI 28):
+   --logprobs (= --logprobs native): the pick is `token_logprobs` into static buffers (ea_ceva_sdecode_vocab_logprob);
+   --logprobs framework: the yardstick on this same tree, inside the capture -- `next_tokens(rows, state, return_logits=True)`,
+       torch.logsumexp over the fp32 [B, V] logits, a gather of the token's logit and the subtraction.
+   Without --logprobs the same command line times the greedy held step alone: what the feature costs.
+   python tools/decoder_stack_latency.py --generate --hold-vocab 1 --logprobs [native|framework] [--vocab 32768|262144]   (GPU)"""
 import argparse
 import os
 import sys
@@ -88,7 +95,7 @@ def run(stack, B, context, hold, steps, blocks=5, warmup=4):
     return sorted(times)[len(times) // 2], torch.cat(rows, 0), nbytes
 
 
-def run_generate(stack, B, context, hold_vocab, steps, blocks=5, warmup=4, sample=None):
+def run_generate(stack, B, context, hold_vocab, steps, blocks=5, warmup=4, sample=None, logprobs=None):
     """The captured greedy step (sample = (top_k, top_p, temperature): the sampled step) replayed -> (block times in ms per
     token, pick alone in us, decoding_state_nbytes)."""
     n_tok = context + 2 + warmup + blocks * steps
@@ -103,9 +110,17 @@ def run_generate(stack, B, context, hold_vocab, steps, blocks=5, warmup=4, sampl
         native = sample is not None and hasattr(stack, "init_sampling")
         if native:
             stack.init_sampling(state, 1234, sample[0], sample[1], sample[2])
+        lp = torch.zeros((1, B), dtype=torch.float32, device="cuda")
+        if logprobs == "native":
+            stack.init_logprobs(state)
 
         def pick(rows, out):
-            if native:
+            if logprobs == "native":                            # (the scorer's static buffers, as generate hands them)
+                stack._logprob_pick(rows, state, None, out, state.scorer.logp[:B].view(1, B), state.scorer.lse[:B].view(1, B))
+            elif logprobs == "framework":
+                _, logits = stack.next_tokens(rows, state, out=out, return_logits=True)
+                lp.copy_(logits.gather(2, out.unsqueeze(2)).squeeze(2) - torch.logsumexp(logits, -1))
+            elif native:
                 stack.sample_tokens(rows, state, out=out)
             elif sample is not None:                           # the framework sampler on the fp32 logits handed back
                 _, logits = stack.next_tokens(rows, state, return_logits=True)
@@ -167,6 +182,13 @@ def main_generate(a):
             "sample_tokens (ea_ceva_sdecode_vocab_sample)" if hasattr(DecoderStack, "init_sampling") else
             "the framework sampler (next_tokens(return_logits=True), topk, softmax, multinomial, copy_)",)))
     hold_vocab = a.hold_vocab == 1 and known
+    if a.logprobs:
+        if sample is not None or not hold_vocab or not hasattr(DecoderStack, "init_logprobs"):
+            raise SystemExit("--logprobs times the greedy step on a held table (--hold-vocab 1, no --sample) of a package "
+                             "with init_logprobs")
+        print("greedy step with the token's log-probability: %s" % (
+            "token_logprobs (ea_ceva_sdecode_vocab_logprob)" if a.logprobs == "native" else
+            "the framework route (next_tokens(return_logits=True), logsumexp, gather, sub, copy_)"))
     if a.hold_vocab == 1 and not known:
         print("the package under %s does not know hold_vocab: timing its plain pick (logits, argmax, copy_)" % ROOT)
     torch.manual_seed(0)
@@ -175,7 +197,7 @@ def main_generate(a):
     print("ms per token, wikitext103_decoder (%d layers, vocab %d), bf16, rolling states, held weights, context %d, the captured "
           "greedy step replayed; package %s" % (LAYERS, V, a.context, ROOT))
     for B in [int(b) for b in a.batches.split(",")]:
-        times, pick_us, nbytes = run_generate(stack, B, a.context, hold_vocab, a.steps, sample=sample)
+        times, pick_us, nbytes = run_generate(stack, B, a.context, hold_vocab, a.steps, sample=sample, logprobs=a.logprobs or None)
         print("B %2d  hold_vocab=%-5s  %8.3f ms per token (blocks %.3f .. %.3f)  pick alone %8.1f us = %7.1f GB/s on 2 V C bytes"
               "  state %d bytes" % (B, hold_vocab, sorted(times)[len(times) // 2], min(times), max(times), pick_us,
                                     2.0 * V * C / (pick_us * 1e-6) / 1e9, nbytes), flush=True)
@@ -191,6 +213,8 @@ def main():
     ap.add_argument("--hold-vocab", type=int, default=1, choices=[0, 1], help="with --generate: the pick on the held table")
     ap.add_argument("--vocab", type=int, default=32768, help="with --generate: rows of the vocabulary table")
     ap.add_argument("--sample", default="", help="with --generate: K,P,T -- time the sampled step (see the module docstring)")
+    ap.add_argument("--logprobs", nargs="?", const="native", default="", choices=["native", "framework"],
+                    help="with --generate --hold-vocab 1: the step also writes the token's log-probability")
     ap.add_argument("--root", default=ROOT, help="the checkout whose package is timed (default: this one)")
     a = ap.parse_args()
     if not torch.cuda.is_available():
