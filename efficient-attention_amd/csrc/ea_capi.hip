@@ -28,6 +28,8 @@ int rows_mlp_blocks(int R, int D);
 int lara_x_dispatch(int mode, const LaraP& p, int dtype, hipStream_t st);
 int lara_y_dispatch(int mode, const LaraP& p, int dtype, hipStream_t st);
 int lara_f_dispatch(int which, const LaraP& p, int dtype, hipStream_t st);
+bool lara_xp_supported(int H, int D, int C, int S);
+int lara_xp_dispatch(const LaraP& p, const LaraXpP& xp, int dtype, hipStream_t st);
 int pool2d_dispatch(bool bwd, int dtype, const void* x, long sb, long sh, long sn, float* mean, int B, int H, int gh, int gw,
                     int side, int D, hipStream_t st);
 int linear_supported(int K, int NO);
@@ -81,7 +83,7 @@ static Geo mk_geo(const ea_geom* g) {
 extern "C" {
 
 const char* ea_version(void) { return "ea_hip 0.1.0 gfx950"; }
-int32_t ea_abi_version(void) { return 28; }
+int32_t ea_abi_version(void) { return 29; }
 
 int32_t ea_window_bias_ld(const ea_geom* g) {
   WinTiling t;
@@ -471,6 +473,30 @@ int ea_lara_out_fwd_merge(const ea_lara_geom* g, const ea_t4* q, const float* om
   p.m_S = S; p.m_ml = p_ml; p.m_acc0 = p_kv; p.m_lp = lp;
   p.m_kv = kv; p.m_lsek = lse_k; p.m_lset = lse_t; p.m_cst = cst;
   return lara_x_dispatch(LX_FWDM, p, g->dtype, (hipStream_t)stream);
+}
+
+// ABI 29: the same pass with the output projection inside (ea_lara_xp.hip).  Out-of-scope geometry is refused first, so a
+// caller that probes with it falls back to ea_lara_out_fwd_merge + ea_linear without having launched anything.
+int ea_lara_out_proj_fwd_merge(const ea_lara_geom* g, const ea_t4* q, const float* omega, const float* qbar, const float* bhv,
+                               int32_t S, const float* p_ml, const float* p_kv, const float* lp, float* kv, float* lse_k,
+                               float* lse_t, float* cst, const ea_t4* out, float* lseZ, float* tmean, const void* w_proj16,
+                               const float* bias, void* y, int64_t ldy, void* stream) {
+  LaraP p = {};
+  int rc = fill_lara(g, p, false);
+  if (rc != EA_OK) return rc;
+  if (!lara_xp_supported(g->H, g->D, g->C, S)) return EA_E_UNSUPPORTED;
+  if (!t4_ok(q, g->D) || !t4_ok(out, g->D) || !omega || !p_ml || !p_kv || !lp || !kv || !lse_k || !cst) return EA_E_BADARG;
+  if (g->mis == EA_MIS_OPT && (!qbar || !lse_t || !bhv)) return EA_E_BADARG;
+  if (g->mis == EA_MIS_BIASED && !qbar) return EA_E_BADARG;
+  if ((lseZ == nullptr) != (tmean == nullptr)) return EA_E_BADARG;
+  if (!w_proj16 || ((uintptr_t)w_proj16 & 15) || !y || ((uintptr_t)y & 7) || ldy < 192 || (ldy & 3) ||
+      (bias && ((uintptr_t)bias & 3))) return EA_E_BADARG;
+  p.q = mkl(q); p.o = mkl(out); p.omega = omega; p.qbar = qbar; p.bhv = bhv; p.lseZ = lseZ; p.tmean = tmean;
+  p.m_S = S; p.m_ml = p_ml; p.m_acc0 = p_kv; p.m_lp = lp;
+  p.m_kv = kv; p.m_lsek = lse_k; p.m_lset = lse_t; p.m_cst = cst;
+  LaraXpP xp;
+  xp.w = (const char*)w_proj16; xp.bias = bias; xp.y = (char*)y; xp.ldy = (long)ldy;
+  return lara_xp_dispatch(p, xp, g->dtype, (hipStream_t)stream);
 }
 
 int ea_lara_bwd_k_fused_merge(const ea_lara_geom* g, const ea_t4* k, const ea_t4* v, const uint8_t* mask, const float* omega,
@@ -1795,12 +1821,19 @@ int64_t ea_lara_layer_ws(const ea_lara_layer* c, int32_t which) {
   }
 }
 
-int ea_lara_layer_fwd(const ea_lara_layer* c, const ea_t4* q, const ea_t4* k, const ea_t4* v, const uint8_t* mask,
-                      const float* noise, const float* const* params, const ea_t4* out, float* saved, float* tmp,
-                      int32_t keep_for_backward, void* stream) {
+// proj: the output projection's operands (ea_lara_layer_fwd_proj) or null
+static int lara_layer_fwd_impl(const ea_lara_layer* c, const ea_t4* q, const ea_t4* k, const ea_t4* v, const uint8_t* mask,
+                               const float* noise, const float* const* params, const ea_t4* out, float* saved, float* tmp,
+                               int32_t keep_for_backward, const LaraXpP* proj, void* stream) {
   LaraLayerPlan P;
   int rc = lara_layer_plan(c, P);
   if (rc != EA_OK) return rc;
+  if (proj) {
+    // everything the last launch would refuse is refused here, before the first one
+    if (!P.fold_f || !lara_xp_supported(c->H, c->D, P.C, P.S_fwd)) return EA_E_UNSUPPORTED;
+    if (!proj->w || ((uintptr_t)proj->w & 15) || !proj->y || ((uintptr_t)proj->y & 7) || proj->ldy < 192 || (proj->ldy & 3) ||
+        (proj->bias && ((uintptr_t)proj->bias & 3)) || !t4_ok(q, c->D) || !t4_ok(out, c->D)) return EA_E_BADARG;
+  }
   if (!saved || !tmp || (c->has_mlp && !params)) return EA_E_BADARG;
   const float* pr[8] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
   if (c->has_mlp) for (int i = 0; i < 8; ++i) pr[i] = params[i];
@@ -1821,6 +1854,10 @@ int ea_lara_layer_fwd(const ea_lara_layer* c, const ea_t4* q, const ea_t4* k, co
   rc = ea_lara_stats_fwd(&P.g, q, k, v, mask, omega, qrows, tmp + P.f_ml, tmp + P.f_kv, stream);
   if (rc != EA_OK) return rc;
   float* tok = keep_for_backward ? saved + P.o_tok : nullptr;
+  if (proj)
+    return ea_lara_out_proj_fwd_merge(&P.g, q, omega, qrows, bhv, P.S_fwd, tmp + P.f_ml, tmp + P.f_kv, tmp + P.f_lp,
+                                      saved + P.o_kv, saved + P.o_lsek, lse_t, saved + P.o_cst, out, tok,
+                                      tok ? tok + (size_t)P.BH * P.g.N : nullptr, proj->w, proj->bias, proj->y, proj->ldy, stream);
   if (P.fold_f)
     return ea_lara_out_fwd_merge(&P.g, q, omega, qrows, bhv, P.S_fwd, tmp + P.f_ml, tmp + P.f_kv, tmp + P.f_lp, saved + P.o_kv,
                                  saved + P.o_lsek, lse_t, saved + P.o_cst, out, tok, tok ? tok + (size_t)P.BH * P.g.N : nullptr,
@@ -1830,6 +1867,21 @@ int ea_lara_layer_fwd(const ea_lara_layer* c, const ea_t4* q, const ea_t4* k, co
   if (rc != EA_OK) return rc;
   return ea_lara_out_fwd(&P.g, q, omega, qrows, saved + P.o_kv, lse_t, bhv, saved + P.o_cst, out, tok,
                          tok ? tok + (size_t)P.BH * P.g.N : nullptr, stream);
+}
+
+int ea_lara_layer_fwd(const ea_lara_layer* c, const ea_t4* q, const ea_t4* k, const ea_t4* v, const uint8_t* mask,
+                      const float* noise, const float* const* params, const ea_t4* out, float* saved, float* tmp,
+                      int32_t keep_for_backward, void* stream) {
+  return lara_layer_fwd_impl(c, q, k, v, mask, noise, params, out, saved, tmp, keep_for_backward, nullptr, stream);
+}
+
+int ea_lara_layer_fwd_proj(const ea_lara_layer* c, const ea_t4* q, const ea_t4* k, const ea_t4* v, const uint8_t* mask,
+                           const float* noise, const float* const* params, const ea_t4* out, float* saved, float* tmp,
+                           int32_t keep_for_backward, const void* w_proj16, const float* bias, void* y, int64_t ldy,
+                           void* stream) {
+  LaraXpP xp;
+  xp.w = (const char*)w_proj16; xp.bias = bias; xp.y = (char*)y; xp.ldy = (long)ldy;
+  return lara_layer_fwd_impl(c, q, k, v, mask, noise, params, out, saved, tmp, keep_for_backward, &xp, stream);
 }
 
 int ea_lara_layer_bwd(const ea_lara_layer* c, const ea_t4* q, const ea_t4* k, const ea_t4* v, const uint8_t* mask,

@@ -263,6 +263,7 @@ EA_DEV float wave_sum(float v) {
 // stores of the previous tile).  64 bytes per thread; nobody reads it.
 static __device__ __attribute__((aligned(64))) char ea_trash[512 * 64];
 EA_DEV char* ea_trash_line() { return ea_trash + threadIdx.x * 64; }
+EA_DEV char* ea_trash_line256() { return ea_trash + (threadIdx.x & 255) * 64; }     // for workgroups of more than 512 threads
 
 #ifdef EA_NT_LOADS
 EA_DEV u32x4 ldg16(const void* p) { return __builtin_nontemporal_load(reinterpret_cast<const u32x4*>(p)); }

@@ -74,6 +74,14 @@ struct LaraP {
   long long* prof;              // dev builds (-DEA_PROFILE): phase time stamps
 };
 
+// operands of the output projection inside the forward combine (ea_lara_xp.hip): y[t][o] = sum_k out[t][k] w[o][k] + bias[o]
+struct LaraXpP {
+  const char* w;        // [192, 192] element type, contiguous (the image ea_linear takes)
+  const float* bias;    // [192] fp32 or null
+  char* y;              // [B*N, 192] element type, row stride ldy elements
+  long ldy;
+};
+
 // ---- the elementwise core of the estimator (lara.py:221-243), one (c, n) entry -------------
 // inputs in the log2 domain: A2 = s*log2e*omega_c.q_n, T2 = s*log2e*qbar_c.q_n
 struct LaraElem {

@@ -22,7 +22,7 @@ class ea_t4(ctypes.Structure):
                 ("sn", ctypes.c_int64)]
 
 
-ABI_VERSION = 28         # ea_abi_version() of include/ea_hip.h this file mirrors
+ABI_VERSION = 29         # ea_abi_version() of include/ea_hip.h this file mirrors
 
 
 class ea_geom(ctypes.Structure):
@@ -132,6 +132,7 @@ SIGNATURES = {
     "ea_lara_landmarks_bwd": [_MG] + [_P] * 21,
     "ea_lara_landmarks_bwd_parts": [_MG] + [_P] * 12 + [_I, _P, _F] + [_P] * 9,
     "ea_lara_out_fwd_merge": [_LG, _T, _P, _P, _P, _I, _P, _P, _P, _P, _P, _P, _P, _T, _P, _P, _P],
+    "ea_lara_out_proj_fwd_merge": [_LG, _T, _P, _P, _P, _I, _P, _P, _P, _P, _P, _P, _P, _T, _P, _P, _P, _P, _P, _L, _P],
     "ea_lara_bwd_k_fused_merge": [_LG, _T, _T, _P, _P, _P, _P, _P, _I, _P, _P, _P, _P, _P, _T, _T, _P, _P, _P, _P, _P, _P, _P],
     "ea_lara_landmarks_fwd_cb": [_MG] + [_P] * 18,
     "ea_lara_landmarks_bwd_cb": [_MG] + [_P] * 23,
@@ -192,6 +193,7 @@ SIGNATURES = {
     "ea_multi_sum": [_I, _P, _P, _P, _P, _P, _P],
     "ea_lara_layer_ws": [_LL, _I],
     "ea_lara_layer_fwd": [_LL, _T, _T, _T, _P, _P, _P, _T, _P, _P, _I, _P],
+    "ea_lara_layer_fwd_proj": [_LL, _T, _T, _T, _P, _P, _P, _T, _P, _P, _I, _P, _P, _P, _L, _P],
     "ea_lara_layer_bwd": [_LL, _T, _T, _T, _P, _P, _P, _T, _T, _T, _T, _P, _P, _P, _P],
     "ea_lara_layer_bwd2": [_LL, _T, _T, _T, _P, _P, _P, _T, _T, _T, _T, _P, _P, _P, _I, _P],
     "ea_eva_layer_ws": [_EL, _I],
@@ -398,6 +400,29 @@ def call_as(label, name, *args):
     if not KERNEL_TIMER.enabled:
         return call(name, *args)
     _timed(label, name, args)
+
+
+def call_probe(label, name, *args):
+    """call_as for an entry point that may decline: True when it ran, False when it answered EA_E_UNSUPPORTED (such an entry
+    refuses before it launches anything, so the caller's fallback starts from a clean stream); every other code raises."""
+    fn = _FN.get(name)
+    if fn is None:
+        fn = _FN[name] = getattr(lib(), name)
+    if KERNEL_TIMER.enabled:
+        a = torch.cuda.Event(enable_timing=True)
+        b = torch.cuda.Event(enable_timing=True)
+        a.record()
+        rc = fn(*args)
+        b.record()
+        if rc == 0:
+            KERNEL_TIMER.records.append((label, a, b))
+    else:
+        rc = fn(*args)
+    if rc == -2:
+        return False
+    if rc != 0:
+        _check(rc, name)
+    return True
 
 
 def call(name, *args):

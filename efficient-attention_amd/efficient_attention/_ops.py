@@ -100,6 +100,7 @@ KERNEL_ALGO_UNITS = {
     "ea_kernelized_bwd_k": 4,     # read k,v; write dk,dv
     "ea_lara_stats_fwd": 3,       # read q,k,v
     "ea_lara_out_fwd": 2,         # read q; write out
+    "ea_lara_out_proj_fwd": 2,    # read q; write out (+ y = out W_proj^T + bias, priced under LABEL_ALGO_BYTES)
     "ea_lara_bwd_q": 3,           # read q,dout; write dq
     "ea_lara_bwd_qstats": 2,      # read q,dout
     "ea_lara_bwd_k": 4,           # read k,v; write dk,dv
@@ -1122,9 +1123,21 @@ def lara_fold(C, S):
     return C <= 64 and 1 <= S <= 4 and os.environ.get("EA_LARA_FOLD", "1") != "0"
 
 
-def _lara_fwd_core(geom, qkv5, mask_u8, omega, qbar_c, bhv_c, lp_c, want_tokst=True):
+def lara_out_proj_on():
+    """ABI 29: the output projection of a three-head, 64-channel layer inside the forward combine (ea_lara_xp.hip).
+    EA_LARA_OUT_PROJ=0 keeps the two launches (read per call: the tests and the A/B runs switch it inside one process)."""
+    return os.environ.get("EA_LARA_OUT_PROJ", "1") != "0"
+
+
+def _lara_proj_fallback(out, proj):
+    """The library declined the fused launch (it does so before launching anything): the projection as its own launch."""
+    proj[2] = ea_linear(out.view(out.shape[0] * out.shape[1], -1), proj[0], proj[1], out.dtype)[0]
+
+
+def _lara_fwd_core(geom, qkv5, mask_u8, omega, qbar_c, bhv_c, lp_c, want_tokst=True, proj=None):
     """Estimator forward (ea_lara_stats_fwd -> ea_lara_merge_fwd -> ea_lara_out_fwd) on contiguous fp32
-    landmark tensors [BH,C,d] / [BH,C].  Returns out [B,N,h,d] and (cst, kv, lse_k, lse_t)."""
+    landmark tensors [BH,C,d] / [BH,C].  Returns out [B,N,h,d] and (cst, kv, lse_k, lse_t).
+    proj = [w16p, bias32, y2]: the output projection y2 = out W^T + bias leaves with the combine pass (or, declined, after it)."""
     B, N, _, h, d = qkv5.shape
     C, BH, dev, mis = geom.C, B * h, qkv5.device, geom.mis
     q, k, v = _qkv_views(qkv5)
@@ -1143,11 +1156,22 @@ def _lara_fwd_core(geom, qkv5, mask_u8, omega, qbar_c, bhv_c, lp_c, want_tokst=T
     to = nv.t4(out.permute(0, 2, 1, 3))
     # per-token softmax statistics (lse_Z in log2 units, mean_c t) for the fused backward: 8 bytes per token-head
     tokst = torch.empty((2, BH, N), dtype=torch.float32, device=dev) if (want_tokst and C <= 64) else None
+    if proj is not None and lara_fold(C, S):
+        label = "ea_lara_out_proj_fwd"
+        if nv.KERNEL_TIMER.enabled:
+            _note_bytes(label, B * N * 3 * h * d * 2)                 # q in, out and y out
+        if nv.call_probe(label, "ea_lara_out_proj_fwd_merge", ctypes.byref(geom), ctypes.byref(tq), nv.ptr(omega), nv.ptr(qbar_c),
+                         nv.ptr(bhv_c), S, nv.ptr(p_ml), nv.ptr(p_kv), nv.ptr(lp_c), nv.ptr(kv), nv.ptr(lse_k), nv.ptr(lse_t),
+                         nv.ptr(cst), ctypes.byref(to), nv.ptr(tokst), None if tokst is None else nv.ptr(tokst[1]),
+                         nv.ptr(proj[0]), nv.ptr(proj[1]), nv.ptr(proj[2]), proj[2].stride(0), nv.stream()):
+            return out, (cst, kv, lse_k, lse_t, tokst)
     if lara_fold(C, S):
         # round 5: the combine pass merges the slice partials in its prologue (block 0 of a (b,h) writes kv / lse / cst)
         nv.call_as("ea_lara_out_fwd", "ea_lara_out_fwd_merge", ctypes.byref(geom), ctypes.byref(tq), nv.ptr(omega), nv.ptr(qbar_c), nv.ptr(bhv_c),
                 S, nv.ptr(p_ml), nv.ptr(p_kv), nv.ptr(lp_c), nv.ptr(kv), nv.ptr(lse_k), nv.ptr(lse_t), nv.ptr(cst),
                 ctypes.byref(to), nv.ptr(tokst), None if tokst is None else nv.ptr(tokst[1]), nv.stream())
+        if proj is not None:
+            _lara_proj_fallback(out, proj)
         return out, (cst, kv, lse_k, lse_t, tokst)
     # merge the sequence slices: log-sum-exp merge of the online-softmax partials (one tiny kernel)
     nv.call("ea_lara_merge_fwd", BH, S, C, d, 1 if mis == 0 else 0, nv.ptr(p_ml), nv.ptr(p_kv),
@@ -1155,6 +1179,8 @@ def _lara_fwd_core(geom, qkv5, mask_u8, omega, qbar_c, bhv_c, lp_c, want_tokst=T
     nv.call("ea_lara_out_fwd", ctypes.byref(geom), ctypes.byref(tq), nv.ptr(omega), nv.ptr(qbar_c),
             nv.ptr(kv), nv.ptr(lse_t), nv.ptr(bhv_c), nv.ptr(cst), ctypes.byref(to),
             nv.ptr(tokst), None if tokst is None else nv.ptr(tokst[1]), nv.stream())
+    if proj is not None:
+        _lara_proj_fallback(out, proj)
     return out, (cst, kv, lse_k, lse_t, tokst)
 
 
@@ -1365,7 +1391,7 @@ def _param_ptrs(ps):
     return arr
 
 
-def lara_fwd_impl(qkv5, mask_u8, noise, icfg, fcfg, params, pooled=None):
+def lara_fwd_impl(qkv5, mask_u8, noise, icfg, fcfg, params, pooled=None, proj=None):
     """torch.ops.ea.lara_fwd: uniform r x r pooling of q, k -> fused landmark pipeline -> estimator.
     icfg = [H, W, r, has_mlp, mixed, mis, dup(, keep_for_backward = 1)], fcfg = [kappa, scale], params = (Wq,
     bq, gq, cq, Wk, bk, gk, ck) when has_mlp.
@@ -1374,7 +1400,9 @@ def lara_fwd_impl(qkv5, mask_u8, noise, icfg, fcfg, params, pooled=None):
     (absent tensors are empty).
     pooled (direct calls only, never through the dispatcher): what project_qkv_pooled returned -- the pooled q / k rows
     already computed by the projection kernel, either inside the composite workspace (ws, None, None) or as two tensors
-    (None, pq, pk): the pooling pass is skipped."""
+    (None, pq, pk): the pooling pass is skipped.
+    proj (direct calls only) = [w16p, bias32, y2]: the output projection y2 [B*N, h*d] = out w16p^T + bias is written by the
+    combine pass (ea_lara_layer_fwd_proj / ea_lara_out_proj_fwd_merge); where the library declines, by ea_linear after it."""
     global LAST_LMK_GEOM
     nv.require_cuda(qkv5, "qkv")
     lcfg, sizes = _lara_layer_cfg(qkv5, icfg, fcfg) if _lara_use_composite() else (None, None)
@@ -1395,9 +1423,16 @@ def lara_fwd_impl(qkv5, mask_u8, noise, icfg, fcfg, params, pooled=None):
         pp = _param_ptrs(ps) if ps else None
         LAST_LMK_GEOM = (B * h, (lcfg.gh // lcfg.pool_r) * (lcfg.gw // lcfg.pool_r),
                          (lcfg.gh // lcfg.pool_r) * (lcfg.gw // lcfg.pool_r) * (2 if lcfg.dup else 1), d, lcfg.has_mlp, lcfg.mixed, 0)
+        keep = int(need_grad) | (2 if pooled is not None else 0)
+        if proj is not None and nv.call_probe("ea_lara_layer_fwd_proj", "ea_lara_layer_fwd_proj", ctypes.byref(lcfg), ctypes.byref(tq),
+                                              ctypes.byref(tk), ctypes.byref(tv), nv.ptr(mask_u8), nv.ptr(noise_c), pp, ctypes.byref(to),
+                                              nv.ptr(ws), nv.ptr(tmp), keep, nv.ptr(proj[0]), nv.ptr(proj[1]), nv.ptr(proj[2]),
+                                              proj[2].stride(0), nv.stream()):
+            return [out, ws]
         nv.call("ea_lara_layer_fwd", ctypes.byref(lcfg), ctypes.byref(tq), ctypes.byref(tk), ctypes.byref(tv),
-                nv.ptr(mask_u8), nv.ptr(noise_c), pp, ctypes.byref(to), nv.ptr(ws), nv.ptr(tmp),
-                int(need_grad) | (2 if pooled is not None else 0), nv.stream())
+                nv.ptr(mask_u8), nv.ptr(noise_c), pp, ctypes.byref(to), nv.ptr(ws), nv.ptr(tmp), keep, nv.stream())
+        if proj is not None:
+            _lara_proj_fallback(out, proj)
         return [out, ws]
     (H, W, r, has_mlp, mixed, mis, dup, L, C), pgeom, lg, geom = _lara_cfg(qkv5, icfg, fcfg)
     B, N, _, h, d = qkv5.shape
@@ -1422,7 +1457,7 @@ def lara_fwd_impl(qkv5, mask_u8, noise, icfg, fcfg, params, pooled=None):
     saved = _lmk_saved(lg, dev) if need_grad else None
     nv.call("ea_lara_landmarks_fwd", ctypes.byref(lg), nv.ptr(pq), nv.ptr(pk), *pp, nv.ptr(noise_c),
             nv.ptr(omega), nv.ptr(qrows), nv.ptr(bhv), nv.ptr(lp), nv.ptr(saved), nv.stream())
-    out, (cst, kv, lse_k, lse_t, tokst) = _lara_fwd_core(geom, qkv5, mask_u8, omega, qrows, bhv, lp, need_grad)
+    out, (cst, kv, lse_k, lse_t, tokst) = _lara_fwd_core(geom, qkv5, mask_u8, omega, qrows, bhv, lp, need_grad, proj=proj)
     e = lp
     return [out, omega, _e(qrows, e), _e(bhv, e), cst, kv, lse_k, _e(lse_t, e), pq, pk, _e(saved, e), _e(tokst, e)]
 
@@ -1868,6 +1903,24 @@ class LaraCore:
         self.nsaved = len(outs) - 1
         return outs[0], tuple(outs[1:]) + tuple(inputs)
 
+    def fwd_project(self, qkv5, inputs, w16p, bp32, cdtype):
+        """fwd with the module's output projection inside the combine pass (ABI 29) -> (out, y2 [B*N, h*d], saved), or None
+        -- before anything is launched or consumed -- where that pass does not apply: not three heads of 64 channels, more
+        than 64 samples, the projection switched off (EA_LARA_OUT_PROJ=0)."""
+        B, heads, d, elem = self.dims
+        H, W, r = self.icfg[:3]
+        C = (H // r) * (W // r) * (2 if self.icfg[6] else 1)
+        if not (lara_out_proj_on() and heads == 3 and d == 64 and C <= 64 and qkv5.dtype == cdtype and w16p.dtype == cdtype
+                and w16p.is_contiguous() and tuple(w16p.shape) == (192, 192)
+                and (bp32 is None or (bp32.dtype == torch.float32 and bp32.is_contiguous()))):
+            return None
+        y2 = torch.empty((qkv5.shape[0] * qkv5.shape[1], heads * d), dtype=cdtype, device=qkv5.device)
+        proj = [w16p, bp32, y2]
+        pooled, self.pooled = self.pooled, None
+        outs = lara_fwd_impl(qkv5, self.mask_u8, self.noise, self.icfg, self.fcfg, list(inputs), pooled=pooled, proj=proj)
+        self.nsaved = len(outs) - 1
+        return outs[0], proj[2], tuple(outs[1:]) + tuple(inputs)
+
     def bwd(self, dout, qkv5, out, saved, defer, fin_ok):
         saved, params = saved[:self.nsaved], saved[self.nsaved:]
         args = (dout, qkv5, self.mask_u8, self.noise, list(saved), self.icfg, self.fcfg, list(params))
@@ -1905,6 +1958,8 @@ class CoreModuleFn(torch.autograd.Function):
         setup(B, N, heads, d, elem, inputs, need_grad): before anything is launched -- geometry, derived inputs
         project(x2, wq, bq32, cdtype, want, need_dx, w192) -> (y, rounded x | None, rounded qkv weight | None), None to decline:
             the qkv projection by a kernel that also emits the core's pooled q / k rows (direct calls only)
+        fwd_project(qkv5, inputs, w16p, bp32, cdtype) -> (out, y2, saved), None to decline: fwd with the output projection
+            y2 = out w16p^T + bias formed by the core's last pass (direct calls with the prepared 192-wide weights only)
         defers = True: bwd(dout, qkv5, out, saved, defer, fin_ok) -> d qkv5, gradients, partials, fin.  partials: (key, [S, n]
             fp32, meta) entries for the terminal sum (when `defer`); fin = (operands, qkv rows | None) leaves the core's last
             correction of dq / dk to the input-gradient kernel (qkv_dgrad_finish; only when fin_ok)
@@ -1946,9 +2001,17 @@ class CoreModuleFn(torch.autograd.Function):
                 y, xc = lin(x2, wq, bq32, elem, False, False, want)
         xl = x2 if x2.dtype == cdtype else (xc if want else None)
         qkv5 = y.view(B, N, 3, heads, d)
-        out, saved = core.fwd(qkv5, inputs)
+        # the output projection inside the core's last pass, where the core offers it (LaraCore.fwd_project, ABI 29)
+        fwd_project = getattr(core, "fwd_project", None) if (direct and w192 is not None) else None
+        done = None if fwd_project is None else fwd_project(qkv5, inputs, w192[2], bp32, cdtype)
+        if done is not None:
+            out, y2, saved = done
+        else:
+            out, saved = core.fwd(qkv5, inputs)
         o2 = out.reshape(-1, C)
-        if lib:
+        if done is not None:
+            pass
+        elif lib:
             with torch.autocast(device_type="cuda", enabled=False):
                 y2 = F.linear(o2, w16p, b16p)
         elif w192 is not None:

@@ -1186,6 +1186,26 @@ int ea_ceva_sdecode_vocab_sample_logprob(int32_t M, int32_t K, int32_t V, const 
                                          int64_t* ctr, const int32_t* sid, int64_t* token, int32_t* sel_idx, float* sel_val,
                                          int32_t* kept, void* lws, int64_t lws_bytes, float* lse, float* logp, void* stream);
 
+/* ABI 29, the LARA forward combine with the OUTPUT PROJECTION inside (ea_lara_xp.hip): for a model of three heads of 64
+ * channels, y = out W_proj^T + bias is formed by the pass that forms `out`, from registers and LDS -- one launch instead of
+ * ea_lara_out_fwd_merge + ea_linear[192->192], `out` written once (the weight gradient reads it) and not read back.
+ *   ea_lara_out_proj_fwd_merge: ea_lara_out_fwd_merge plus w_proj16 [192,192] in the EA dtype (contiguous, 16-byte aligned:
+ *       ea_linear's weight operand, w16p of ea_linear_w192_prepare), bias [192] fp32 or NULL (rounded to the EA dtype before
+ *       it is added, the sum rounded once, as ea_linear does), y [B*N, 192] in the EA dtype with row stride ldy elements
+ *       (ldy >= 192, a multiple of 4; y 8-byte aligned).  out, lseZ, tmean, kv, lse_k, lse_t, cst have ea_lara_out_fwd_merge's
+ *       bits and y those of ea_linear on that `out` (its k-slots, its order of accumulation).
+ *   ea_lara_layer_fwd_proj: ea_lara_layer_fwd with that pass as its last launch.
+ * EA_E_UNSUPPORTED -- before anything is launched, so the caller can fall back to the two calls -- unless H = 3, D = 64,
+ * C <= 64 samples and the folded merge applies (S = ea_lara_parts <= 4; EA_LARA_FOLD not 0). */
+int ea_lara_out_proj_fwd_merge(const ea_lara_geom* g, const ea_t4* q, const float* omega, const float* qbar, const float* bhv,
+                               int32_t S, const float* p_ml, const float* p_kv, const float* lp, float* kv, float* lse_k,
+                               float* lse_t, float* cst, const ea_t4* out, float* lseZ, float* tmean, const void* w_proj16,
+                               const float* bias, void* y, int64_t ldy, void* stream);
+int ea_lara_layer_fwd_proj(const ea_lara_layer* cfg, const ea_t4* q, const ea_t4* k, const ea_t4* v, const uint8_t* mask,
+                           const float* noise, const float* const* params, const ea_t4* out, float* saved, float* tmp,
+                           int32_t keep_for_backward, const void* w_proj16, const float* bias, void* y, int64_t ldy,
+                           void* stream);
+
 #ifdef __cplusplus
 }
 #endif
