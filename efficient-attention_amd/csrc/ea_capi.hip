@@ -2411,14 +2411,91 @@ int ea_ceva_sdecode_advance(const ea_ceva_sdec_geom* g, void* stream) {
   return ea::ceva_sdecode_advance(const_cast<int32_t*>(g->pos), g->ntok, g->B, g->T_new, g->cap, (hipStream_t)stream);
 }
 
+}  // extern "C"
+
+// ---- the few-row passes on a held table: what each entry refuses as a bad argument, group by group.  Every entry asks its
+// groups first and the geometry (EA_E_UNSUPPORTED) last, so no bad argument is ever reported as an unsupported shape. -------
+static int64_t dec_row_bytes(int64_t ld, int dtype) { return ld * (dtype == EA_F32 ? 4 : 2); }
+
+// x [M, ldx] in fp32 or the table's type against the 16-bit table w [., K]
+static bool dec_table_ok(int M, int K, const void* x, int x_dtype, int64_t ldx, const void* w, int w_dtype) {
+  if (!x || !w || (uintptr_t)x % 16 || (uintptr_t)w % 16) return false;
+  if (w_dtype != EA_BF16 && w_dtype != EA_F16) return false;
+  if (x_dtype != EA_F32 && x_dtype != w_dtype) return false;
+  return M >= 1 && K >= 1 && ldx >= K && dec_row_bytes(ldx, x_dtype) % 16 == 0;
+}
+
+// a linear's y [M, ldy] in fp32 or the weight's type, and its optional bias
+static bool dec_lin_out_ok(int N, const void* bias, const void* y, int y_dtype, int64_t ldy, int w_dtype) {
+  if (!y || (uintptr_t)y % 16 || (uintptr_t)bias % 16) return false;
+  if (y_dtype != EA_F32 && y_dtype != w_dtype) return false;
+  return N >= 1 && ldy >= N && dec_row_bytes(ldy, y_dtype) % 16 == 0;
+}
+
+// a vocab pass's optional logits [M, ldl] in fp32 or the table's type
+static bool dec_logits_ok(int V, const void* logits, int logits_dtype, int64_t ldl, int w_dtype) {
+  if (!logits) return true;
+  if (logits_dtype != EA_F32 && logits_dtype != w_dtype) return false;
+  return (uintptr_t)logits % (logits_dtype == EA_F32 ? 4 : 2) == 0 && ldl >= V;
+}
+
+// a vocab pass's candidates workspace and what the pick writes (top: optional).  (need < 0: a geometry the entry refuses)
+static bool dec_pick_ok(int M, int V, const void* ws, int64_t ws_bytes, const int64_t* token, const float* top) {
+  if (!ws || !token || (uintptr_t)ws % 16 || (uintptr_t)token % 8 || (uintptr_t)top % 4) return false;
+  const int64_t need = ea::ceva_sdecode_vocab_ws(M, V);
+  return need < 0 || ws_bytes >= need;
+}
+
+// the sampler's state, optional outputs and arguments but for top_k's upper bound: that one is geometry
+static bool dec_sampler_ok(int top_k, float top_p, float temperature, const int64_t* ctr, const int32_t* sid,
+                           const int32_t* sel_idx, const float* sel_val, const int32_t* kept) {
+  if (!ctr || !sid || (uintptr_t)ctr % 8 || (uintptr_t)sid % 4) return false;
+  if ((uintptr_t)sel_idx % 4 || (uintptr_t)sel_val % 4 || (uintptr_t)kept % 4) return false;
+  return top_p > 0.f && top_p <= 1.f && std::isfinite(temperature) && temperature > 0.f && top_k >= 1;
+}
+
+// the scorer's workspace and outputs (targets: optional)
+static bool dec_scorer_ok(int M, int V, const void* lws, int64_t lws_bytes, const int64_t* targets, const float* lse,
+                          const float* logp) {
+  if (!lws || !lse || !logp || (uintptr_t)lws % 16 || (uintptr_t)lse % 4 || (uintptr_t)logp % 4 || (uintptr_t)targets % 8)
+    return false;
+  const int64_t need = ea::ceva_sdecode_vocab_lse_ws(M, V);
+  return need < 0 || lws_bytes >= need;
+}
+
+static bool dec_vocab_geometry_ok(int M, int K, int V) { return M <= EA_CEVA_LINEAR_MAX_ROWS && K % 32 == 0 && V >= 1; }
+
+// the fields DecVocabP and DecLseP share
+template <typename P>
+static void dec_vocab_fill(P* p, int M, int K, int V, const void* x, int x_dtype, int64_t ldx, const void* w, int w_dtype,
+                           void* logits, int logits_dtype, int64_t ldl, void* ws) {
+  p->x = (const char*)x; p->w = (const char*)w; p->logits = (char*)logits; p->ws = (ea::VocPick*)ws;
+  p->ldx = ldx; p->ldl = logits ? ldl : 0; p->M = M; p->K = K; p->V = V; p->dtype = w_dtype;
+  p->x_f32 = x_dtype == EA_F32; p->l_f32 = logits && logits_dtype == EA_F32;
+}
+
+// DecLseP's own workspace, behind dec_vocab_fill (M and V are read): lws [M, ceil(V / 16)], then tlogit [M]
+static void dec_scorer_fill(ea::DecLseP* p, void* lws, float* lse, float* logp) {
+  p->lws = (float*)lws; p->tlogit = p->lws + (int64_t)p->M * ((p->V - 1) / ea::VOC_TILE + 1);
+  p->lse = lse; p->logp = logp;
+}
+
+static ea::DecSampleP dec_sample_fill(int V, const void* ws, float* logits, int64_t ldl, int top_k, float top_p,
+                                      float temperature, uint64_t seed, int64_t* ctr, const int32_t* sid, int64_t* token,
+                                      int32_t* sel_idx, float* sel_val, int32_t* kept) {
+  ea::DecSampleP s = {};
+  s.ws = (const ea::VocPick*)ws; s.logits = logits; s.token = token; s.ctr = ctr; s.sid = sid;
+  s.sel_idx = sel_idx; s.sel_val = sel_val; s.kept = kept; s.ldl = ldl; s.V = V; s.top_k = top_k;
+  s.top_p = top_p; s.temperature = temperature; s.seed_lo = (uint32_t)seed; s.seed_hi = (uint32_t)(seed >> 32);
+  return s;
+}
+
+extern "C" {
+
 int ea_ceva_sdecode_linear(int32_t M, int32_t K, int32_t N, const void* x, int32_t x_dtype, int64_t ldx,
                            const void* w, int32_t w_dtype, const void* bias, void* y, int32_t y_dtype, int64_t ldy,
                            void* stream) {
-  if (!x || !w || !y || (uintptr_t)x % 16 || (uintptr_t)w % 16 || (uintptr_t)y % 16 || (uintptr_t)bias % 16) return EA_E_BADARG;
-  if (w_dtype != EA_BF16 && w_dtype != EA_F16) return EA_E_BADARG;
-  if ((x_dtype != EA_F32 && x_dtype != w_dtype) || (y_dtype != EA_F32 && y_dtype != w_dtype)) return EA_E_BADARG;
-  if (M < 1 || K < 1 || N < 1 || ldx < K || ldy < N) return EA_E_BADARG;
-  if (ldx * (x_dtype == EA_F32 ? 4 : 2) % 16 || ldy * (y_dtype == EA_F32 ? 4 : 2) % 16) return EA_E_BADARG;
+  if (!dec_table_ok(M, K, x, x_dtype, ldx, w, w_dtype) || !dec_lin_out_ok(N, bias, y, y_dtype, ldy, w_dtype)) return EA_E_BADARG;
   if (M > EA_CEVA_LINEAR_MAX_ROWS || K % 32 || N % 16) return EA_E_UNSUPPORTED;
   ea::DecLinP p = {};
   p.x = (const char*)x; p.w = (const char*)w; p.bias = (const char*)bias; p.y = (char*)y;
@@ -2431,19 +2508,14 @@ int ea_ceva_sdecode_linear_fused(int32_t M, int32_t K, int32_t N, const void* x,
                                  const float* ln_gamma, const float* ln_beta, float ln_eps, const void* w, int32_t w_dtype,
                                  const void* bias, int32_t act, const void* res, int32_t res_dtype, int64_t ldr, void* y,
                                  int32_t y_dtype, int64_t ldy, void* stream) {
-  // what ea_ceva_sdecode_linear refuses, in its order ...
-  if (!x || !w || !y || (uintptr_t)x % 16 || (uintptr_t)w % 16 || (uintptr_t)y % 16 || (uintptr_t)bias % 16) return EA_E_BADARG;
-  if (w_dtype != EA_BF16 && w_dtype != EA_F16) return EA_E_BADARG;
-  if ((x_dtype != EA_F32 && x_dtype != w_dtype) || (y_dtype != EA_F32 && y_dtype != w_dtype)) return EA_E_BADARG;
-  if (M < 1 || K < 1 || N < 1 || ldx < K || ldy < N) return EA_E_BADARG;
-  if (ldx * (x_dtype == EA_F32 ? 4 : 2) % 16 || ldy * (y_dtype == EA_F32 ? 4 : 2) % 16) return EA_E_BADARG;
-  // ... then the prologue's and the epilogue's operands, and the geometry last
+  if (!dec_table_ok(M, K, x, x_dtype, ldx, w, w_dtype) || !dec_lin_out_ok(N, bias, y, y_dtype, ldy, w_dtype)) return EA_E_BADARG;
+  // the prologue's and the epilogue's operands
   if ((ln_gamma == nullptr) != (ln_beta == nullptr)) return EA_E_BADARG;
   if ((uintptr_t)ln_gamma % 16 || (uintptr_t)ln_beta % 16 || (uintptr_t)res % 16) return EA_E_BADARG;
   if (ln_gamma && !(std::isfinite(ln_eps) && ln_eps > 0.f)) return EA_E_BADARG;
   if (res) {
     if (res_dtype != EA_F32 && res_dtype != w_dtype) return EA_E_BADARG;
-    if (ldr < N || ldr * (res_dtype == EA_F32 ? 4 : 2) % 16) return EA_E_BADARG;
+    if (ldr < N || dec_row_bytes(ldr, res_dtype) % 16) return EA_E_BADARG;
   }
   if (x == y) return EA_E_BADARG;
   if (M > EA_CEVA_LINEAR_MAX_ROWS || K % 32 || N % 16) return EA_E_UNSUPPORTED;
@@ -2462,55 +2534,31 @@ int64_t ea_ceva_sdecode_vocab_ws(int32_t M, int32_t V) { return ea::ceva_sdecode
 int ea_ceva_sdecode_vocab_argmax(int32_t M, int32_t K, int32_t V, const void* x, int32_t x_dtype, int64_t ldx,
                                  const void* w, int32_t w_dtype, void* logits, int32_t logits_dtype, int64_t ldl,
                                  void* ws, int64_t ws_bytes, int64_t* token, float* top, void* stream) {
-  // ea_ceva_sdecode_linear's refusals in its order: pointers, the types, the sizes and strides, and the geometry last
-  if (!x || !w || !ws || !token || (uintptr_t)x % 16 || (uintptr_t)w % 16 || (uintptr_t)ws % 16) return EA_E_BADARG;
-  if ((uintptr_t)token % 8 || (uintptr_t)top % 4) return EA_E_BADARG;
-  if (w_dtype != EA_BF16 && w_dtype != EA_F16) return EA_E_BADARG;
-  if (x_dtype != EA_F32 && x_dtype != w_dtype) return EA_E_BADARG;
-  if (logits && ((logits_dtype != EA_F32 && logits_dtype != w_dtype) || (uintptr_t)logits % (logits_dtype == EA_F32 ? 4 : 2)))
-    return EA_E_BADARG;
-  if (M < 1 || K < 1 || ldx < K || (logits && ldl < V)) return EA_E_BADARG;
-  if (ldx * (x_dtype == EA_F32 ? 4 : 2) % 16) return EA_E_BADARG;
-  const int64_t need = ea::ceva_sdecode_vocab_ws(M, V);           // (< 0: a geometry refused below)
-  if (need >= 0 && ws_bytes < need) return EA_E_BADARG;
-  if (M > EA_CEVA_LINEAR_MAX_ROWS || K % 32 || V < 1) return EA_E_UNSUPPORTED;
+  if (!dec_table_ok(M, K, x, x_dtype, ldx, w, w_dtype) || !dec_logits_ok(V, logits, logits_dtype, ldl, w_dtype) ||
+      !dec_pick_ok(M, V, ws, ws_bytes, token, top)) return EA_E_BADARG;
+  if (!dec_vocab_geometry_ok(M, K, V)) return EA_E_UNSUPPORTED;
   ea::DecVocabP p = {};
-  p.x = (const char*)x; p.w = (const char*)w; p.logits = (char*)logits; p.ws = (ea::VocPick*)ws; p.token = token; p.top = top;
-  p.ldx = ldx; p.ldl = logits ? ldl : 0; p.M = M; p.K = K; p.V = V; p.dtype = w_dtype;
-  p.x_f32 = x_dtype == EA_F32; p.l_f32 = logits && logits_dtype == EA_F32;
+  dec_vocab_fill(&p, M, K, V, x, x_dtype, ldx, w, w_dtype, logits, logits_dtype, ldl, ws);
+  p.token = token; p.top = top;
   return ea::ceva_sdecode_vocab_argmax(p, (hipStream_t)stream);
 }
 
 int64_t ea_ceva_sdecode_vocab_sample_ws(int32_t M, int32_t V) { return ea::ceva_sdecode_vocab_ws(M, V); }
 
+// (the logits are required and fp32)
 int ea_ceva_sdecode_vocab_sample(int32_t M, int32_t K, int32_t V, const void* x, int32_t x_dtype, int64_t ldx,
                                  const void* w, int32_t w_dtype, float* logits, int64_t ldl, void* ws, int64_t ws_bytes,
                                  int32_t top_k, float top_p, float temperature, uint64_t seed, int64_t* ctr,
                                  const int32_t* sid, int64_t* token, int32_t* sel_idx, float* sel_val, int32_t* kept,
                                  void* stream) {
-  // ea_ceva_sdecode_vocab_argmax's refusals in its order (the logits are required and fp32), then the sampler's own, and the
-  // geometry last
-  if (!x || !w || !ws || !token || (uintptr_t)x % 16 || (uintptr_t)w % 16 || (uintptr_t)ws % 16) return EA_E_BADARG;
-  if ((uintptr_t)token % 8) return EA_E_BADARG;
-  if (w_dtype != EA_BF16 && w_dtype != EA_F16) return EA_E_BADARG;
-  if (x_dtype != EA_F32 && x_dtype != w_dtype) return EA_E_BADARG;
-  if (!logits || (uintptr_t)logits % 4) return EA_E_BADARG;
-  if (M < 1 || K < 1 || ldx < K || ldl < V) return EA_E_BADARG;
-  if (ldx * (x_dtype == EA_F32 ? 4 : 2) % 16) return EA_E_BADARG;
-  const int64_t need = ea::ceva_sdecode_vocab_ws(M, V);           // (< 0: a geometry refused below)
-  if (need >= 0 && ws_bytes < need) return EA_E_BADARG;
-  if (!ctr || !sid || (uintptr_t)ctr % 8 || (uintptr_t)sid % 4) return EA_E_BADARG;
-  if ((uintptr_t)sel_idx % 4 || (uintptr_t)sel_val % 4 || (uintptr_t)kept % 4) return EA_E_BADARG;
-  if (!(top_p > 0.f && top_p <= 1.f) || !(std::isfinite(temperature) && temperature > 0.f) || top_k < 1) return EA_E_BADARG;
-  if (top_k > 64 || M > EA_CEVA_LINEAR_MAX_ROWS || K % 32 || V < 1) return EA_E_UNSUPPORTED;
+  if (!dec_table_ok(M, K, x, x_dtype, ldx, w, w_dtype) || !logits || !dec_logits_ok(V, logits, EA_F32, ldl, w_dtype) ||
+      !dec_pick_ok(M, V, ws, ws_bytes, token, nullptr) ||
+      !dec_sampler_ok(top_k, top_p, temperature, ctr, sid, sel_idx, sel_val, kept)) return EA_E_BADARG;
+  if (top_k > 64 || !dec_vocab_geometry_ok(M, K, V)) return EA_E_UNSUPPORTED;
   ea::DecVocabP p = {};
-  p.x = (const char*)x; p.w = (const char*)w; p.logits = (char*)logits; p.ws = (ea::VocPick*)ws;
-  p.ldx = ldx; p.ldl = ldl; p.M = M; p.K = K; p.V = V; p.dtype = w_dtype;
-  p.x_f32 = x_dtype == EA_F32; p.l_f32 = 1;
-  ea::DecSampleP s = {};
-  s.ws = p.ws; s.logits = logits; s.token = token; s.ctr = ctr; s.sid = sid;
-  s.sel_idx = sel_idx; s.sel_val = sel_val; s.kept = kept; s.ldl = ldl; s.V = V; s.top_k = top_k;
-  s.top_p = top_p; s.temperature = temperature; s.seed_lo = (uint32_t)seed; s.seed_hi = (uint32_t)(seed >> 32);
+  dec_vocab_fill(&p, M, K, V, x, x_dtype, ldx, w, w_dtype, logits, EA_F32, ldl, ws);
+  const ea::DecSampleP s = dec_sample_fill(V, ws, logits, ldl, top_k, top_p, temperature, seed, ctr, sid, token, sel_idx,
+                                           sel_val, kept);
   return ea::ceva_sdecode_vocab_sample(p, s, (hipStream_t)stream);
 }
 
@@ -2520,63 +2568,34 @@ int ea_ceva_sdecode_vocab_logprob(int32_t M, int32_t K, int32_t V, const void* x
                                   const void* w, int32_t w_dtype, void* logits, int32_t logits_dtype, int64_t ldl,
                                   void* ws, int64_t ws_bytes, int64_t* token, float* top, void* lws, int64_t lws_bytes,
                                   const int64_t* targets, float* lse, float* logp, void* stream) {
-  // ea_ceva_sdecode_vocab_argmax's refusals in its order, then this entry's own, and the geometry last
-  if (!x || !w || !ws || !token || (uintptr_t)x % 16 || (uintptr_t)w % 16 || (uintptr_t)ws % 16) return EA_E_BADARG;
-  if ((uintptr_t)token % 8 || (uintptr_t)top % 4) return EA_E_BADARG;
-  if (w_dtype != EA_BF16 && w_dtype != EA_F16) return EA_E_BADARG;
-  if (x_dtype != EA_F32 && x_dtype != w_dtype) return EA_E_BADARG;
-  if (logits && ((logits_dtype != EA_F32 && logits_dtype != w_dtype) || (uintptr_t)logits % (logits_dtype == EA_F32 ? 4 : 2)))
+  if (!dec_table_ok(M, K, x, x_dtype, ldx, w, w_dtype) || !dec_logits_ok(V, logits, logits_dtype, ldl, w_dtype) ||
+      !dec_pick_ok(M, V, ws, ws_bytes, token, top) || !dec_scorer_ok(M, V, lws, lws_bytes, targets, lse, logp))
     return EA_E_BADARG;
-  if (M < 1 || K < 1 || ldx < K || (logits && ldl < V)) return EA_E_BADARG;
-  if (ldx * (x_dtype == EA_F32 ? 4 : 2) % 16) return EA_E_BADARG;
-  const int64_t need = ea::ceva_sdecode_vocab_ws(M, V);           // (< 0: a geometry refused below)
-  if (need >= 0 && ws_bytes < need) return EA_E_BADARG;
-  if (!lws || !lse || !logp || (uintptr_t)lws % 16 || (uintptr_t)lse % 4 || (uintptr_t)logp % 4 || (uintptr_t)targets % 8)
-    return EA_E_BADARG;
-  const int64_t lneed = ea::ceva_sdecode_vocab_lse_ws(M, V);
-  if (lneed >= 0 && lws_bytes < lneed) return EA_E_BADARG;
-  if (M > EA_CEVA_LINEAR_MAX_ROWS || K % 32 || V < 1) return EA_E_UNSUPPORTED;
+  if (!dec_vocab_geometry_ok(M, K, V)) return EA_E_UNSUPPORTED;
   ea::DecLseP p = {};
-  p.x = (const char*)x; p.w = (const char*)w; p.logits = (char*)logits; p.ws = (ea::VocPick*)ws; p.token = token; p.top = top;
-  p.lws = (float*)lws; p.tlogit = p.lws + (int64_t)M * ((V - 1) / ea::VOC_TILE + 1); p.targets = targets;
-  p.lse = lse; p.logp = logp;
-  p.ldx = ldx; p.ldl = logits ? ldl : 0; p.M = M; p.K = K; p.V = V; p.dtype = w_dtype;
-  p.x_f32 = x_dtype == EA_F32; p.l_f32 = logits && logits_dtype == EA_F32;
+  dec_vocab_fill(&p, M, K, V, x, x_dtype, ldx, w, w_dtype, logits, logits_dtype, ldl, ws);
+  dec_scorer_fill(&p, lws, lse, logp);
+  p.token = token; p.top = top; p.targets = targets;
   return ea::ceva_sdecode_vocab_logprob(p, (hipStream_t)stream);
 }
 
+// (the logits are required and fp32; the scorer reads the drawn tokens, not targets)
 int ea_ceva_sdecode_vocab_sample_logprob(int32_t M, int32_t K, int32_t V, const void* x, int32_t x_dtype, int64_t ldx,
                                          const void* w, int32_t w_dtype, float* logits, int64_t ldl, void* ws,
                                          int64_t ws_bytes, int32_t top_k, float top_p, float temperature, uint64_t seed,
                                          int64_t* ctr, const int32_t* sid, int64_t* token, int32_t* sel_idx, float* sel_val,
                                          int32_t* kept, void* lws, int64_t lws_bytes, float* lse, float* logp, void* stream) {
-  // ea_ceva_sdecode_vocab_sample's refusals in its order, then this entry's own, and the geometry last
-  if (!x || !w || !ws || !token || (uintptr_t)x % 16 || (uintptr_t)w % 16 || (uintptr_t)ws % 16) return EA_E_BADARG;
-  if ((uintptr_t)token % 8) return EA_E_BADARG;
-  if (w_dtype != EA_BF16 && w_dtype != EA_F16) return EA_E_BADARG;
-  if (x_dtype != EA_F32 && x_dtype != w_dtype) return EA_E_BADARG;
-  if (!logits || (uintptr_t)logits % 4) return EA_E_BADARG;
-  if (M < 1 || K < 1 || ldx < K || ldl < V) return EA_E_BADARG;
-  if (ldx * (x_dtype == EA_F32 ? 4 : 2) % 16) return EA_E_BADARG;
-  const int64_t need = ea::ceva_sdecode_vocab_ws(M, V);           // (< 0: a geometry refused below)
-  if (need >= 0 && ws_bytes < need) return EA_E_BADARG;
-  if (!ctr || !sid || (uintptr_t)ctr % 8 || (uintptr_t)sid % 4) return EA_E_BADARG;
-  if ((uintptr_t)sel_idx % 4 || (uintptr_t)sel_val % 4 || (uintptr_t)kept % 4) return EA_E_BADARG;
-  if (!(top_p > 0.f && top_p <= 1.f) || !(std::isfinite(temperature) && temperature > 0.f) || top_k < 1) return EA_E_BADARG;
-  if (!lws || !lse || !logp || (uintptr_t)lws % 16 || (uintptr_t)lse % 4 || (uintptr_t)logp % 4) return EA_E_BADARG;
-  const int64_t lneed = ea::ceva_sdecode_vocab_lse_ws(M, V);
-  if (lneed >= 0 && lws_bytes < lneed) return EA_E_BADARG;
-  if (top_k > 64 || M > EA_CEVA_LINEAR_MAX_ROWS || K % 32 || V < 1) return EA_E_UNSUPPORTED;
+  if (!dec_table_ok(M, K, x, x_dtype, ldx, w, w_dtype) || !logits || !dec_logits_ok(V, logits, EA_F32, ldl, w_dtype) ||
+      !dec_pick_ok(M, V, ws, ws_bytes, token, nullptr) ||
+      !dec_sampler_ok(top_k, top_p, temperature, ctr, sid, sel_idx, sel_val, kept) ||
+      !dec_scorer_ok(M, V, lws, lws_bytes, nullptr, lse, logp)) return EA_E_BADARG;
+  if (top_k > 64 || !dec_vocab_geometry_ok(M, K, V)) return EA_E_UNSUPPORTED;
   ea::DecLseP p = {};
-  p.x = (const char*)x; p.w = (const char*)w; p.logits = (char*)logits; p.ws = (ea::VocPick*)ws;
-  p.lws = (float*)lws; p.tlogit = p.lws + (int64_t)M * ((V - 1) / ea::VOC_TILE + 1); p.token_in = token;
-  p.lse = lse; p.logp = logp;
-  p.ldx = ldx; p.ldl = ldl; p.M = M; p.K = K; p.V = V; p.dtype = w_dtype;
-  p.x_f32 = x_dtype == EA_F32; p.l_f32 = 1;
-  ea::DecSampleP s = {};
-  s.ws = p.ws; s.logits = logits; s.token = token; s.ctr = ctr; s.sid = sid;
-  s.sel_idx = sel_idx; s.sel_val = sel_val; s.kept = kept; s.ldl = ldl; s.V = V; s.top_k = top_k;
-  s.top_p = top_p; s.temperature = temperature; s.seed_lo = (uint32_t)seed; s.seed_hi = (uint32_t)(seed >> 32);
+  dec_vocab_fill(&p, M, K, V, x, x_dtype, ldx, w, w_dtype, logits, EA_F32, ldl, ws);
+  dec_scorer_fill(&p, lws, lse, logp);
+  p.token_in = token;
+  const ea::DecSampleP s = dec_sample_fill(V, ws, logits, ldl, top_k, top_p, temperature, seed, ctr, sid, token, sel_idx,
+                                           sel_val, kept);
   return ea::ceva_sdecode_vocab_sample_logprob(p, s, (hipStream_t)stream);
 }
 

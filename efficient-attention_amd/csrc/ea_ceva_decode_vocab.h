@@ -30,7 +30,7 @@ struct DecVocabP {
 
 constexpr int VOC_SAMPLE_MAX_K = 64;  // top_k of the sampled pick: the selection is sorted by one wave
 
-// the sampled pick's second launch (ceva_vocab_sample_kernel); a block of its own: DecVocabP is ceva_vocab_kernel's
+// the sampled pick's second launch (ceva_vocab_sample_kernel); a block of its own: DecVocabP is the table pass's
 // parameter and stays what it is
 struct DecSampleP {
   const VocPick* ws;          // [M, ceil(V / 16)] candidates of the first launch
@@ -47,9 +47,9 @@ struct DecSampleP {
   uint32_t seed_lo, seed_hi;
 };
 
-// token log-probabilities (ABI 28): the parameter block of ceva_vocab_lse_kernel (the table pass that also writes one
-// sum exp(logit - tile maximum) per tile) and of ceva_vocab_lse_pick_kernel (the pick, the log-sum-exp and the
-// log-probability); a block of its own: DecVocabP and DecSampleP stay what they are.
+// token log-probabilities (ABI 28): the parameter block of ceva_rows_kernel as the table pass that also writes one
+// sum exp(logit - tile maximum) per tile, and of ceva_vocab_pick_kernel as the pick with the log-sum-exp and the
+// log-probability; a block of its own: DecVocabP and DecSampleP stay what they are.
 //   lse[m]  = log sum_v exp(logit[m, v]) over the whole row: the RAW distribution, temperature 1, nothing truncated -- in the
 //             sampled mode too, whatever temperature, top_k and top_p the draw was made with
 //   logp[m] = tl - lse[m]; tl: logits[m, token_in[m]] in the sampled mode (token_in set), else logit[m, targets[m]] when
