@@ -83,7 +83,7 @@ static Geo mk_geo(const ea_geom* g) {
 extern "C" {
 
 const char* ea_version(void) { return "ea_hip 0.1.0 gfx950"; }
-int32_t ea_abi_version(void) { return 29; }
+int32_t ea_abi_version(void) { return 30; }
 
 int32_t ea_window_bias_ld(const ea_geom* g) {
   WinTiling t;
@@ -2226,6 +2226,7 @@ int ea_layernorm_bwd(int32_t xtype, int32_t rows, int32_t C, const void* x, cons
 #include "ea_ceva_decode.h"
 #include "ea_ceva_decode_linear.h"
 #include "ea_ceva_decode_vocab.h"
+#include "ea_vocab_score.h"
 static bool dec_t4_ok(const ea_t4* t, int D, int esz) {
   const int a = 16 / esz;                                 // 16-byte aligned rows
   return t && t->ptr && ((uintptr_t)t->ptr % 16 == 0) && t->sb % a == 0 && t->sh % a == 0 && t->sn % a == 0 && t->sn >= D;
@@ -2597,6 +2598,37 @@ int ea_ceva_sdecode_vocab_sample_logprob(int32_t M, int32_t K, int32_t V, const 
   const ea::DecSampleP s = dec_sample_fill(V, ws, logits, ldl, top_k, top_p, temperature, seed, ctr, sid, token, sel_idx,
                                            sel_val, kept);
   return ea::ceva_sdecode_vocab_sample_logprob(p, s, (hipStream_t)stream);
+}
+
+// ---- the many-row vocabulary pass (ABI 30, ea_vocab_score.hip): the few-row entries' groups in their order -- the table
+// operands, the optional logits, then the workspace and the outputs -- and the geometry last ---------------------------------
+int64_t ea_vocab_score_ws(int32_t M, int32_t V) { return ea::vocab_score_ws(M, V); }
+
+int32_t ea_vocab_score_tile(int32_t which) {
+  switch (which) {
+    case 0: return ea::VS_BM;
+    case 1: return ea::VS_BN;
+    case 2: return ea::VS_SL;
+    default: return EA_E_BADARG;
+  }
+}
+
+int ea_vocab_score(int32_t M, int32_t K, int32_t V, const void* x, int32_t x_dtype, int64_t ldx, const void* w,
+                   int32_t w_dtype, const int64_t* targets, void* logits, int32_t logits_dtype, int64_t ldl, void* ws,
+                   int64_t ws_bytes, int64_t* token, float* top, float* lse, float* logp, void* stream) {
+  if (!dec_table_ok(M, K, x, x_dtype, ldx, w, w_dtype) || !dec_logits_ok(V, logits, logits_dtype, ldl, w_dtype)) return EA_E_BADARG;
+  if (!ws || !token || !lse || !logp) return EA_E_BADARG;
+  if ((uintptr_t)ws % 16 || (uintptr_t)token % 8 || (uintptr_t)targets % 8) return EA_E_BADARG;
+  if ((uintptr_t)top % 4 || (uintptr_t)lse % 4 || (uintptr_t)logp % 4) return EA_E_BADARG;
+  const int64_t need = ea::vocab_score_ws(M, V);       // (< 0: a geometry refused below)
+  if (need >= 0 && ws_bytes < need) return EA_E_BADARG;
+  if (K % 32 || V < 1 || need < 0) return EA_E_UNSUPPORTED;
+  ea::VocabScoreP p = {};
+  p.x = (const char*)x; p.w = (const char*)w; p.targets = targets; p.logits = (char*)logits; p.pick = (ea::VsPick*)ws;
+  p.token = token; p.top = top; p.lse = lse; p.logp = logp;
+  p.ldx = ldx; p.ldl = logits ? ldl : 0; p.M = M; p.K = K; p.V = V; p.dtype = w_dtype;
+  p.x_f32 = x_dtype == EA_F32; p.l_f32 = logits && logits_dtype == EA_F32;
+  return ea::vocab_score(p, (hipStream_t)stream);
 }
 
 }  // extern "C"

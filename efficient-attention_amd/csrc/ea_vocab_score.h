@@ -1,0 +1,50 @@
+// ea_vocab_score.h -- the many-row vocabulary pass (ABI 30): tile constants, workspace layout and parameter block
+// (ea_vocab_score.hip)
+#pragma once
+#include <stdint.h>
+#include <hip/hip_runtime.h>
+#include "../../include/ea_hip.h"
+
+namespace ea {
+
+constexpr int VS_BM = EA_VOCAB_SCORE_BM;   // rows of x of one workgroup
+constexpr int VS_BN = EA_VOCAB_SCORE_BN;   // columns of one column block: the accumulator tile is VS_BM x VS_BN
+constexpr int VS_BK = 64;                  // k of one LDS stage: 128-byte tile rows, two MFMA k-steps
+constexpr int VS_SL = EA_VOCAB_SCORE_SL;   // columns of one slice: VS_SL / VS_BN column blocks fold into one partial per row
+constexpr int64_t VS_MAX_WORKGROUPS = (int64_t)1 << 23;   // row tiles x slices of the first launch: 2^31 threads
+
+// one candidate of a row and slice: the largest fp32 sum and its column (the layout of ea_ceva_decode_vocab.h's VocPick)
+struct alignas(8) VsPick {
+  float v;
+  int32_t i;
+};
+
+// ws, for NS = ceil(V / VS_SL) slices:  VsPick pick[NS][M] | float sum[NS][M] | float tlogit[M]
+//   pick[t][m]  the best (value, index) of row m in slice t
+//   sum[t][m]   sum over the slice's columns of exp(logit - pick[t][m].v)
+//   tlogit[m]   logit[m, targets[m]], written by the one thread that holds it (a target outside [0, V): by nobody)
+struct VocabScoreP {
+  const char* x;              // [M, ldx] rows, fp32 or the table's type
+  const char* w;              // [V, K] row-major 16-bit table
+  const int64_t* targets;     // [M], or null
+  char* logits;               // [M, ldl] rows, fp32 or the table's type, or null: nothing is stored
+  VsPick* pick;               // ws
+  float* sum;
+  float* tlogit;
+  int64_t* token;             // [M]
+  float* top;                 // [M], or null
+  float* lse;                 // [M]
+  float* logp;                // [M]
+  int64_t ldx, ldl;           // row strides in elements
+  int M, K, V;                // M >= 1, K % 32 == 0, V >= 1
+  int MT, NS;                 // row tiles, slices
+  int dtype;                  // EA_BF16 | EA_F16: w
+  int x_f32, l_f32;           // 1: fp32 rows (x is rounded to `dtype` on load)
+};
+
+// bytes of ws for (M, V); < 0: outside the envelope (M < 1, V < 1, more than VS_MAX_WORKGROUPS workgroups)
+int64_t vocab_score_ws(int M, int V);
+// the two launches; the C entry point has checked pointers, alignment, strides, types and the size of ws
+int vocab_score(VocabScoreP p, hipStream_t st);
+
+}  // namespace ea

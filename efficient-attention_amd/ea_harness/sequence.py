@@ -236,6 +236,7 @@ _SAMPLE = "ea_ceva_sdecode_vocab_sample"
 _SAMPLE_MAX_K = 64
 _LOGPROB = "ea_ceva_sdecode_vocab_logprob"
 _SAMPLE_LOGPROB = "ea_ceva_sdecode_vocab_sample_logprob"
+_SCORE = "ea_vocab_score"
 
 
 class Sampler:
@@ -697,6 +698,87 @@ class DecoderStack(nn.Module):
             targets = tokens[:, 1:].t().contiguous()
             _, logp = self.token_logprobs(rows, state, targets=targets)
             return logp.masked_fill_(targets.eq(self.pad_idx), 0.0).t().contiguous()
+
+    # ---- corpus-scale scoring (ea_vocab_score, C ABI 30) --------------------------------------------------------------------
+    @staticmethod
+    def _score_rows(rows, table):
+        """rows [T, B, C] against table [V, C] -> the [T B, C] operand of ea_vocab_score (fp32 or the table's type, 16-byte
+        aligned); the argument errors of `rows_logprobs`."""
+        if not isinstance(table, torch.Tensor) or table.dim() != 2 or table.dtype not in (torch.bfloat16, torch.float16) \
+                or not table.is_contiguous() or table.data_ptr() % 16:
+            raise ValueError("table must be a contiguous, 16-byte aligned 16-bit [V, C] tensor (bfloat16 or float16); got %s"
+                             % (("%s %s" % (str(table.dtype).replace("torch.", ""), list(table.shape)))
+                                if isinstance(table, torch.Tensor) else type(table).__name__))
+        if rows.dim() != 3 or rows.shape[0] * rows.shape[1] < 1:
+            raise ValueError("rows must be a [T, B, C] tensor of at least one row; got %s" % (tuple(rows.shape),))
+        T, B, C = rows.shape
+        if C != table.shape[1]:
+            raise ValueError("rows of %d channels against a table of %d" % (C, table.shape[1]))
+        if rows.device != table.device:
+            raise ValueError("table must be on the rows' device (%s); it is on %s" % (rows.device, table.device))
+        x2 = rows.detach()
+        if x2.dtype not in (torch.float32, table.dtype):
+            x2 = x2.float()
+        x2 = x2.contiguous().view(T * B, C)
+        if x2.data_ptr() % 16:
+            x2 = x2.clone()
+        return x2
+
+    def rows_logprobs(self, rows, table, targets=None, return_lse=False):
+        """`token_logprobs` for ANY number of rows, on a table the caller holds: rows [T, B, C], table a contiguous 16-bit
+        [V, C] tensor on the rows' device (`state.vocab` of a hold_vocab state serves) -> (tokens int64 [T, B], logp fp32
+        [T, B]); return_lse=True: and lse fp32 [T, B].  tokens is the greedy pick, logp[t, b] = logit[targets[t, b]] - lse
+        with `targets` (int64 [T, B] on the device; one outside [0, V) gives NaN), else top - lse.  ONE call of
+        ea_vocab_score (include/ea_hip.h, ABI 30) on a workspace sized by its query: a tiled GEMM on the matrix cores with
+        the pick and an online log-sum-exp as its epilogue -- no framework GEMM, no [T B, V] tensor; the table is read once
+        per 128 rows.  A logit's order of summation is that kernel's own: results agree with `token_logprobs` to rounding,
+        not bit for bit.  A row's results do not depend on the rows beside it."""
+        from efficient_attention import _native as nv
+        x2 = self._score_rows(rows, table)
+        T, B, C = rows.shape
+        V, dev = table.shape[0], x2.device
+        if targets is not None:
+            if targets.dtype != torch.long or tuple(targets.shape) != (T, B) or targets.device != dev:
+                raise ValueError("targets must be an int64 [%d, %d] tensor on the rows' device" % (T, B))
+            targets = targets.contiguous().view(T * B)
+        nv.require_cuda(x2, "rows")
+        # (the entry's sizes are int32: a count of 2^31 or more would wrap on its way into the query)
+        nbytes = nv.lib().ea_vocab_score_ws(T * B, V) if max(T * B, V, C) < 2 ** 31 else -1
+        if nbytes < 0:
+            raise ValueError("%d rows against %d table rows are outside ea_vocab_score's envelope" % (T * B, V))
+        ws = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+        out = torch.empty((T, B), dtype=torch.long, device=dev)
+        logp = torch.empty((T, B), dtype=torch.float32, device=dev)
+        lse = torch.empty((T, B), dtype=torch.float32, device=dev)
+        code = nv.EA_F32 if x2.dtype == torch.float32 else nv.io_dtype(x2)
+        nv.call(_SCORE, T * B, C, V, nv.ptr(x2), code, C, nv.ptr(table), nv.io_dtype(table), nv.ptr(targets), None, nv.EA_F32,
+                V, nv.ptr(ws), ws.numel(), nv.ptr(out), None, nv.ptr(lse), nv.ptr(logp), nv.stream())
+        return (out, logp, lse) if return_lse else (out, logp)
+
+    def evaluate(self, tokens, table=None, key_padding_mask=None, return_tokens=False):
+        """Teacher-forced log-probabilities for corpus-scale evaluation (perplexity): tokens [B, T] int64 -> fp32 [B, T - 1],
+        entry [b, t] = log p(tokens[b, t + 1] | tokens[b, :t + 1]); entries whose target is `pad_idx` are 0, as in `score`;
+        return_tokens=True: and the greedy tokens, int64 [B, T - 1].  Runs the FULL path, `self(tokens[:, :-1],
+        key_padding_mask)`, under no_grad, then `rows_logprobs` on `table` (default: a 16-bit copy of embed_tokens.weight made
+        for the call, in the autocast dtype under autocast, else bfloat16).
+        How it differs from `score`: that one feeds the tokens through `decode` -- the incremental DECODING path and its
+        state -- and streams the table once per 64 rows, ceil(rows / 64) passes; this one runs the full (training-shaped)
+        forward and passes over the table in proportion to ceil(rows / 128), the row tile of ea_vocab_score, each pass on
+        the matrix cores at full tiles.  The two agree to rounding, not bit for bit."""
+        if self.training:
+            raise NotImplementedError("evaluate in training mode")
+        B, T = tokens.shape
+        if T < 2:
+            raise ValueError("evaluate needs at least two tokens per row, got %d" % T)
+        with torch.no_grad():
+            if table is None:
+                dtype = torch.get_autocast_dtype("cuda") if torch.is_autocast_enabled() else torch.bfloat16
+                table = self.embed_tokens.weight.detach().to(dtype).contiguous()
+            rows = self(tokens[:, :-1], key_padding_mask)                    # [T - 1, B, C]
+            targets = tokens[:, 1:].t().contiguous()
+            greedy, logp = self.rows_logprobs(rows, table, targets)
+            logp = logp.masked_fill_(targets.eq(self.pad_idx), 0.0).t().contiguous()
+            return (logp, greedy.t().contiguous()) if return_tokens else logp
 
     def generate(self, prompt, n_new, state=None, graph=True, return_rows=False, return_logprobs=False):
         """Greedy decoding: prompt [B, P] int64 -> the n_new tokens that follow, [B, n_new] (return_rows: and the final-layer

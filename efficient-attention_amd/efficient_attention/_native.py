@@ -22,7 +22,7 @@ class ea_t4(ctypes.Structure):
                 ("sn", ctypes.c_int64)]
 
 
-ABI_VERSION = 29         # ea_abi_version() of include/ea_hip.h this file mirrors
+ABI_VERSION = 30         # ea_abi_version() of include/ea_hip.h this file mirrors
 
 
 class ea_geom(ctypes.Structure):
@@ -259,6 +259,9 @@ SIGNATURES = {
     "ea_ceva_sdecode_vocab_logprob": [_I, _I, _I, _P, _I, _L, _P, _I, _P, _I, _L, _P, _L, _P, _P, _P, _L, _P, _P, _P, _P],
     "ea_ceva_sdecode_vocab_sample_logprob": [_I, _I, _I, _P, _I, _L, _P, _I, _P, _L, _P, _L, _I, _F, _F, _U64, _P, _P, _P, _P,
                                              _P, _P, _P, _L, _P, _P, _P],
+    "ea_vocab_score_ws": [_I, _I],
+    "ea_vocab_score_tile": [_I],
+    "ea_vocab_score": [_I, _I, _I, _P, _I, _L, _P, _I, _P, _P, _I, _L, _P, _L, _P, _P, _P, _P, _P],
     "ea_softmax_attn_fwd": [_I, _I, _I, _I, _I, _F, _T, _T, _T, _P, _T, _P, _P, _F, _I, _P],
     "ea_softmax_sample": [_I, _I, _I, _I, _I, _F, _T, _T, _P, _P, _P],
     "ea_softmax_attn_bwd": [_I, _I, _I, _I, _I, _F, _T, _T, _T, _P, _T, _T, _P, _P, _T, _T, _T, _P, _F, _I, _P],
@@ -293,6 +296,7 @@ def lib():
         cdll.ea_ceva_sdecode_vocab_ws.restype = ctypes.c_int64
         cdll.ea_ceva_sdecode_vocab_sample_ws.restype = ctypes.c_int64
         cdll.ea_ceva_sdecode_vocab_lse_ws.restype = ctypes.c_int64
+        cdll.ea_vocab_score_ws.restype = ctypes.c_int64
         cdll.ea_version.restype = ctypes.c_char_p
         cdll.ea_abi_version.restype = ctypes.c_int32
         if cdll.ea_abi_version() != ABI_VERSION:
@@ -304,6 +308,12 @@ def lib():
 
 def version():
     return lib().ea_version().decode()
+
+
+def vocab_score_tiles():
+    """(BM, BN, SL) of ea_vocab_score: the row tile, the column block and the slice width the library was compiled with."""
+    fn = lib().ea_vocab_score_tile
+    return tuple(int(fn(i)) for i in range(3))
 
 
 def _check(rc, what):

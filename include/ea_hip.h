@@ -1206,6 +1206,45 @@ int ea_lara_layer_fwd_proj(const ea_lara_layer* cfg, const ea_t4* q, const ea_t4
                            int32_t keep_for_backward, const void* w_proj16, const float* bias, void* y, int64_t ldy,
                            void* stream);
 
+/* ABI 30, the MANY-ROW vocabulary pass (ea_harness DecoderStack.rows_logprobs, evaluate; ea_vocab_score.hip): what
+ * ea_ceva_sdecode_vocab_logprob gives, for any number of rows in one call -- a GEMM on the matrix cores whose epilogue is the
+ * pick and an online log-sum-exp, so that no logit leaves the chip and the table is read once per 128 rows, not per 64:
+ *   logit[m, v] = sum_k round_w(x[m, k]) w[v, k]        fp32, no bias;  any M >= 1, K % 32 == 0, any V >= 1
+ *   token[m]    = the index of the largest logit[m, 0 .. V - 1]; of equal values the lowest index; in a row that holds NaN
+ *                 logits the lowest index that holds one (torch.argmax's rule), decided on the fp32 sums
+ *   top[m]      = logit[m, token[m]]
+ *   lse[m]      = by cases on top[m]: NaN -> NaN; +inf -> +inf; -inf (every logit is -inf) -> -inf; else top + logf(S),
+ *                 S = sum_v expf-weights of the row against top; partials whose maximum is -inf are skipped, never multiplied
+ *   logp[m]     = logit[m, targets[m]] - lse[m] with targets (int64 [M] on the device; one outside [0, V): NaN), else
+ *                 top[m] - lse[m]; one fp32 subtraction
+ * x [M, ldx] rows of x_dtype = EA_F32 or w_dtype (fp32 rows are rounded to w_dtype, to nearest even, as they are loaded);
+ * w [V, K] row-major of w_dtype = EA_BF16 | EA_F16.  The order of a logit's summation is this kernel's own (k in steps of 32
+ * on one accumulator): a logit need NOT have the bits ea_ceva_sdecode_vocab_argmax gives it.  logits: NULL (nothing is
+ * stored: the normal case), or [M, ldl] rows of logits_dtype = EA_F32 | w_dtype (not read without logits); columns >= V and
+ * rows >= M are not touched; token, top, lse and logp have the same bits with and without it.  top [M] fp32 or NULL.
+ * Two launches.  The first: workgroup (slice, row tile) owns EA_VOCAB_SCORE_BM rows of x and one slice of EA_VOCAB_SCORE_SL
+ * columns, walks it in blocks of EA_VOCAB_SCORE_BN columns (v_mfma_f32_16x16x32 on LDS-staged tiles) and keeps per row a
+ * running (maximum, index, sum of exponentials, the target's logit) across the blocks; the sum is rescaled only when the
+ * maximum rises; one partial per (row, slice) goes to ws.  The second: one thread per row folds the row's slices in slice
+ * order.  The three widths are compile-time constants (ea_vocab_score_tile(0 | 1 | 2) = BM | BN | SL; another argument:
+ * EA_E_BADARG), so the partition of the columns depends on V alone: a row's four results do not depend on M, on the rows
+ * beside it or on its place in the batch.  Ordinary stores only, no atomics, no workgroup waits for another: bitwise
+ * reproducible.  ws: ea_vocab_score_ws(M, V) bytes (12 M ceil(V / SL) + 4 M, rounded up to 16; grows with M and with V);
+ * < 0 for M < 1, V < 1 or more than 2^23 workgroups (ceil(M / BM) ceil(V / SL)).
+ * EA_E_BADARG: x, w, ws, token, lse, logp NULL; x, w or ws not 16-byte aligned, token or targets not 8-byte, top, lse or logp
+ * not 4-byte aligned, logits not aligned to its element; w_dtype not a 16-bit type; x_dtype neither EA_F32 nor w_dtype; with
+ * logits: logits_dtype neither EA_F32 nor w_dtype, ldl < V; M < 1, K < 1, ldx < K; a row stride of x that is no multiple of
+ * 16 bytes; ws_bytes below the query's answer.  EA_E_UNSUPPORTED: K % 32 != 0, V < 1, more than 2^23 workgroups.  Bad
+ * arguments are decided before the geometry, everything before any launch. */
+#define EA_VOCAB_SCORE_BM 128
+#define EA_VOCAB_SCORE_BN 128
+#define EA_VOCAB_SCORE_SL 2048
+int64_t ea_vocab_score_ws(int32_t M, int32_t V);
+int32_t ea_vocab_score_tile(int32_t which);
+int ea_vocab_score(int32_t M, int32_t K, int32_t V, const void* x, int32_t x_dtype, int64_t ldx, const void* w,
+                   int32_t w_dtype, const int64_t* targets, void* logits, int32_t logits_dtype, int64_t ldl, void* ws,
+                   int64_t ws_bytes, int64_t* token, float* top, float* lse, float* logp, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
