@@ -21,6 +21,7 @@ int window_bwd_dispatch(const WinP& p, const ea_geom& geom, const T4& outp, cons
 #include "ea_rows_mlp.h"
 #include "ea_performer_f32.h"
 #include "ea_kernelized.h"
+#include "ea_f32_tile.h"
 #include "ea_f32_attn.h"
 namespace ea {
 int rows_mlp_dispatch(const RowsP& p, int D, int sides, int layer_norm, bool bwd, hipStream_t st);
@@ -61,14 +62,9 @@ int multi_sum_dispatch(int K, const float* const* part, const int* S, const int*
 
 using namespace ea;
 
-static bool t4_ok(const ea_t4* t, int D) {
-  // 16-byte vector access: base and every stride must be a multiple of 8 elements
-  return t && t->ptr && ((uintptr_t)t->ptr % 16 == 0) && t->sb % 8 == 0 && t->sh % 8 == 0 &&
-         t->sn % 8 == 0 && t->sn >= D;
-}
 // kernels that form token * stride in 32-bit arithmetic additionally need N * sn < 2^31 elements
 static bool t4_ok32(const ea_t4* t, int D, int N) {
-  return t4_ok(t, D) && (int64_t)N * t->sn < ((int64_t)1 << 31);
+  return view_ok(t, D, 2) && (int64_t)N * t->sn < ((int64_t)1 << 31);
 }
 static bool geom_ok(const ea_geom* g) {
   return g && g->B > 0 && g->H > 0 && g->N > 0 && (g->D == 32 || g->D == 64 || g->D == 128) &&
@@ -144,7 +140,7 @@ int ea_window_attn_fwd(const ea_geom* g, const ea_t4* q, const ea_t4* k, const e
   if (rc != EA_OK) return rc;
   if (keep && !g->causal) return EA_E_UNSUPPORTED;
   p.keep = keep; p.keep_scale = keep_scale; p.keep_ld = p.t.biasLd + p.t.nCT * 16;
-  if (!t4_ok(q, g->D) || !t4_ok(k, g->D) || !t4_ok(v, g->D) || !t4_ok(out, g->D) || !lse) return EA_E_BADARG;
+  if (!view_ok(q, g->D, 2) || !view_ok(k, g->D, 2) || !view_ok(v, g->D, 2) || !view_ok(out, g->D, 2) || !lse) return EA_E_BADARG;
   if (g->L > 0 && (!lk || !lv)) return EA_E_BADARG;
   p.q = mk(q); p.k = mk(k); p.v = mk(v); p.o = mk(out);
   p.lk = lk; p.lv = lv; p.bias = bias; p.mask = mask; p.lse = lse;
@@ -200,7 +196,7 @@ int ea_eva_chunk_mean_fwd(const ea_geom* g, const ea_t4* q, const ea_t4* k, cons
   LmP p = {};
   int rc = fill_lm(g, p);
   if (rc != EA_OK) return rc;
-  if (!t4_ok(q, g->D) || !t4_ok(k, g->D) || !qmean || !kmean) return EA_E_BADARG;
+  if (!view_ok(q, g->D, 2) || !view_ok(k, g->D, 2) || !qmean || !kmean) return EA_E_BADARG;
   SET3(q, q); SET3(k, k);
   p.mask = mask; p.qmean = qmean; p.kmean = kmean;
   return landmark_dispatch(0, p, g->dtype, g->D, (hipStream_t)stream);
@@ -211,7 +207,7 @@ int ea_eva_chunk_mean_bwd(const ea_geom* g, const float* dqmean, const float* dk
   LmP p = {};
   int rc = fill_lm(g, p);
   if (rc != EA_OK) return rc;
-  if (!t4_ok(dq, g->D) || !t4_ok(dk, g->D) || !dqmean || !dkmean) return EA_E_BADARG;
+  if (!view_ok(dq, g->D, 2) || !view_ok(dk, g->D, 2) || !dqmean || !dkmean) return EA_E_BADARG;
   SET3(dq, dq); SET3(dk, dk);
   p.mask = mask; p.dqmean = dqmean; p.dkmean = dkmean;
   return landmark_dispatch(1, p, g->dtype, g->D, (hipStream_t)stream);
@@ -222,7 +218,7 @@ int ea_eva_beta_fwd(const ea_geom* g, const ea_t4* k, const ea_t4* v, const uint
   LmP p = {};
   int rc = fill_lm(g, p);
   if (rc != EA_OK) return rc;
-  if (!t4_ok(k, g->D) || !t4_ok(v, g->D) || !omega || !beta) return EA_E_BADARG;
+  if (!view_ok(k, g->D, 2) || !view_ok(v, g->D, 2) || !omega || !beta) return EA_E_BADARG;
   SET3(k, k); SET3(v, v);
   p.mask = mask; p.omega = omega; p.beta_out = beta;
   return landmark_dispatch(2, p, g->dtype, g->D, (hipStream_t)stream);
@@ -235,7 +231,7 @@ static int eva_beta_bwd_parts(const ea_geom* g, const ea_t4* k, const ea_t4* v, 
   LmP p = {};
   int rc = fill_lm(g, p);
   if (rc != EA_OK) return rc;
-  if (!t4_ok(k, g->D) || !t4_ok(v, g->D) || !t4_ok(dk, g->D) || !t4_ok(dv, g->D) || !omega ||
+  if (!view_ok(k, g->D, 2) || !view_ok(v, g->D, 2) || !view_ok(dk, g->D, 2) || !view_ok(dv, g->D, 2) || !omega ||
       !beta || !dbeta || !domega || dbeta_S < 1 || dbeta_S > 4) return EA_E_BADARG;
   SET3(k, k); SET3(v, v); SET3(dk, dk); SET3(dv, dv);
   p.mask = mask; p.omega = omega; p.beta = beta; p.dbeta = dbeta; p.domega = domega;
@@ -252,12 +248,6 @@ int ea_eva_beta_bwd(const ea_geom* g, const ea_t4* k, const ea_t4* v, const uint
 }  // extern "C"
 
 // ---- LARA ----
-static T4l mkl(const ea_t4* t) {
-  T4l r;
-  r.p = t ? (char*)t->ptr : nullptr;
-  r.sb = t ? t->sb : 0; r.sh = t ? t->sh : 0; r.sn = t ? t->sn : 0;
-  return r;
-}
 static int lara_nsub(int NCT) { return NCT == 1 ? 4 : (NCT == 2 ? 2 : 1); }
 // X passes: blocks per (b,h) and tokens per block; Y passes: sequence splits
 static int fill_lara(const ea_lara_geom* g, LaraP& p, bool ypass) {
@@ -306,9 +296,9 @@ int ea_lara_stats_fwd(const ea_lara_geom* g, const ea_t4* q, const ea_t4* k, con
   LaraP p = {};
   int rc = fill_lara(g, p, true);
   if (rc != EA_OK) return rc;
-  if (!t4_ok(q, g->D) || !t4_ok(k, g->D) || !t4_ok(v, g->D) || !omega || !p_ml || !p_kv ||
+  if (!view_ok(q, g->D, 2) || !view_ok(k, g->D, 2) || !view_ok(v, g->D, 2) || !omega || !p_ml || !p_kv ||
       (g->mis == EA_MIS_OPT && !qbar)) return EA_E_BADARG;
-  p.q = mkl(q); p.k = mkl(k); p.v = mkl(v); p.mask = mask; p.omega = omega; p.qbar = qbar;
+  p.q = mk(q); p.k = mk(k); p.v = mk(v); p.mask = mask; p.omega = omega; p.qbar = qbar;
   p.p_ml = p_ml; p.p_acc0 = p_kv;
   return lara_y_dispatch(LY_FWD, p, g->dtype, (hipStream_t)stream);
 }
@@ -319,11 +309,11 @@ int ea_lara_out_fwd(const ea_lara_geom* g, const ea_t4* q, const float* omega, c
   LaraP p = {};
   int rc = fill_lara(g, p, false);
   if (rc != EA_OK) return rc;
-  if (!t4_ok(q, g->D) || !t4_ok(out, g->D) || !omega || !kv || !cst) return EA_E_BADARG;
+  if (!view_ok(q, g->D, 2) || !view_ok(out, g->D, 2) || !omega || !kv || !cst) return EA_E_BADARG;
   if (g->mis == EA_MIS_OPT && (!qbar || !lse_t || !bhv)) return EA_E_BADARG;
   if (g->mis == EA_MIS_BIASED && !qbar) return EA_E_BADARG;
   if ((lseZ == nullptr) != (tmean == nullptr)) return EA_E_BADARG;
-  p.q = mkl(q); p.o = mkl(out); p.omega = omega; p.qbar = qbar; p.kv = kv; p.lse_t = lse_t;
+  p.q = mk(q); p.o = mk(out); p.omega = omega; p.qbar = qbar; p.kv = kv; p.lse_t = lse_t;
   p.bhv = bhv; p.cst = cst; p.lseZ = lseZ; p.tmean = tmean;
   return lara_x_dispatch(LX_FWD, p, g->dtype, (hipStream_t)stream);
 }
@@ -335,11 +325,11 @@ int ea_lara_bwd_q(const ea_lara_geom* g, const ea_t4* q, const ea_t4* dout, cons
   LaraP p = {};
   int rc = fill_lara(g, p, false);
   if (rc != EA_OK) return rc;
-  if (!t4_ok(q, g->D) || !t4_ok(dout, g->D) || !t4_ok(dq, g->D) || !omega || !kv || !cst ||
+  if (!view_ok(q, g->D, 2) || !view_ok(dout, g->D, 2) || !view_ok(dq, g->D, 2) || !omega || !kv || !cst ||
       !lseZ || !tmean || !rowdot || !sda) return EA_E_BADARG;
   if (g->mis == EA_MIS_OPT && (!qbar || !lse_t || !bhv)) return EA_E_BADARG;
   if (g->mis == EA_MIS_BIASED && !qbar) return EA_E_BADARG;
-  p.q = mkl(q); p.dout = mkl(dout); p.dq = mkl(dq); p.omega = omega; p.qbar = qbar; p.kv = kv;
+  p.q = mk(q); p.dout = mk(dout); p.dq = mk(dq); p.omega = omega; p.qbar = qbar; p.kv = kv;
   p.lse_t = lse_t; p.bhv = bhv; p.cst = cst;
   p.lseZ = lseZ; p.tmean = tmean; p.rowdot = rowdot; p.sda = sda;
   return lara_x_dispatch(LX_BWDQ, p, g->dtype, (hipStream_t)stream);
@@ -353,11 +343,11 @@ int ea_lara_bwd_qstats(const ea_lara_geom* g, const ea_t4* q, const ea_t4* dout,
   LaraP p = {};
   int rc = fill_lara(g, p, true);
   if (rc != EA_OK) return rc;
-  if (!t4_ok(q, g->D) || !t4_ok(dout, g->D) || !omega || !kv || !cst || !lseZ || !tmean ||
+  if (!view_ok(q, g->D, 2) || !view_ok(dout, g->D, 2) || !omega || !kv || !cst || !lseZ || !tmean ||
       !rowdot || !sda || !p_ml || !p_dkv || !p_dom) return EA_E_BADARG;
   if (g->mis == EA_MIS_OPT && (!qbar || !lse_t || !bhv || !p_m1 || !p_m2)) return EA_E_BADARG;
   if (g->mis == EA_MIS_BIASED && !qbar) return EA_E_BADARG;
-  p.q = mkl(q); p.dout = mkl(dout); p.omega = omega; p.qbar = qbar; p.kv = kv; p.lse_t = lse_t;
+  p.q = mk(q); p.dout = mk(dout); p.omega = omega; p.qbar = qbar; p.kv = kv; p.lse_t = lse_t;
   p.bhv = bhv; p.cst = cst;
   p.lseZ = const_cast<float*>(lseZ); p.tmean = const_cast<float*>(tmean);
   p.rowdot = const_cast<float*>(rowdot); p.sda = const_cast<float*>(sda);
@@ -371,9 +361,9 @@ int ea_lara_bwd_k(const ea_lara_geom* g, const ea_t4* k, const ea_t4* v, const u
   LaraP p = {};
   int rc = fill_lara(g, p, false);
   if (rc != EA_OK) return rc;
-  if (!t4_ok(k, g->D) || !t4_ok(v, g->D) || !t4_ok(dk, g->D) || !t4_ok(dv, g->D) || !omega ||
+  if (!view_ok(k, g->D, 2) || !view_ok(v, g->D, 2) || !view_ok(dk, g->D, 2) || !view_ok(dv, g->D, 2) || !omega ||
       !dkv || !lse_k || !dkk || !rsum) return EA_E_BADARG;
-  p.k = mkl(k); p.v = mkl(v); p.dk = mkl(dk); p.dv = mkl(dv); p.mask = mask; p.omega = omega;
+  p.k = mk(k); p.v = mk(v); p.dk = mk(dk); p.dv = mk(dv); p.mask = mask; p.omega = omega;
   p.dkv = dkv; p.lse_k = lse_k; p.dkk = dkk; p.rsum = rsum;
   return lara_x_dispatch(LX_BWDK, p, g->dtype, (hipStream_t)stream);
 }
@@ -384,9 +374,9 @@ int ea_lara_bwd_kstats(const ea_lara_geom* g, const ea_t4* k, const ea_t4* v, co
   LaraP p = {};
   int rc = fill_lara(g, p, true);
   if (rc != EA_OK) return rc;
-  if (!t4_ok(k, g->D) || !t4_ok(v, g->D) || !omega || !dkv || !lse_k || !dkk || !rsum || !p_dom)
+  if (!view_ok(k, g->D, 2) || !view_ok(v, g->D, 2) || !omega || !dkv || !lse_k || !dkk || !rsum || !p_dom)
     return EA_E_BADARG;
-  p.k = mkl(k); p.v = mkl(v); p.mask = mask; p.omega = omega; p.dkv = dkv; p.lse_k = lse_k;
+  p.k = mk(k); p.v = mk(v); p.mask = mask; p.omega = omega; p.dkv = dkv; p.lse_k = lse_k;
   p.dkk = dkk; p.rsum = rsum; p.p_acc0 = p_dom;
   return lara_y_dispatch(LY_BWDK, p, g->dtype, (hipStream_t)stream);
 }
@@ -407,11 +397,11 @@ int ea_lara_bwd_q_fused(const ea_lara_geom* g, const ea_t4* q, const ea_t4* dout
   int rc = fill_lara(g, p, false);
   if (rc != EA_OK) return rc;
   if (p.NCT > 4) return EA_E_UNSUPPORTED;
-  if (!t4_ok(q, g->D) || !t4_ok(dout, g->D) || !t4_ok(dq, g->D) || !omega || !kv || !cst || !p_ml ||
+  if (!view_ok(q, g->D, 2) || !view_ok(dout, g->D, 2) || !view_ok(dq, g->D, 2) || !omega || !kv || !cst || !p_ml ||
       !p_dkv || !p_dom || !lseZ || !tmean) return EA_E_BADARG;
   if (g->mis == EA_MIS_OPT && (!qbar || !lse_t || !bhv || !p_m1 || !p_m2)) return EA_E_BADARG;
   if (g->mis == EA_MIS_BIASED && !qbar) return EA_E_BADARG;
-  p.q = mkl(q); p.dout = mkl(dout); p.dq = mkl(dq); p.omega = omega; p.qbar = qbar; p.kv = kv;
+  p.q = mk(q); p.dout = mk(dout); p.dq = mk(dq); p.omega = omega; p.qbar = qbar; p.kv = kv;
   p.lse_t = lse_t; p.bhv = bhv; p.cst = cst;
   p.lseZ = const_cast<float*>(lseZ); p.tmean = const_cast<float*>(tmean);
   p.p_ml = p_ml; p.p_acc0 = p_dkv; p.p_acc1 = p_dom; p.p_acc2 = p_m1; p.p_acc3 = p_m2;
@@ -425,9 +415,9 @@ int ea_lara_bwd_k_fused(const ea_lara_geom* g, const ea_t4* k, const ea_t4* v, c
   int rc = fill_lara(g, p, false);
   if (rc != EA_OK) return rc;
   if (p.NCT > 4) return EA_E_UNSUPPORTED;
-  if (!t4_ok(k, g->D) || !t4_ok(v, g->D) || !t4_ok(dk, g->D) || !t4_ok(dv, g->D) || !omega ||
+  if (!view_ok(k, g->D, 2) || !view_ok(v, g->D, 2) || !view_ok(dk, g->D, 2) || !view_ok(dv, g->D, 2) || !omega ||
       !dkv || !lse_k || !dkk || !rsum || !p_dom) return EA_E_BADARG;
-  p.k = mkl(k); p.v = mkl(v); p.dk = mkl(dk); p.dv = mkl(dv); p.mask = mask; p.omega = omega;
+  p.k = mk(k); p.v = mk(v); p.dk = mk(dk); p.dv = mk(dv); p.mask = mask; p.omega = omega;
   p.dkv = dkv; p.lse_k = lse_k; p.dkk = dkk; p.rsum = rsum; p.p_acc0 = p_dom;
   return lara_f_dispatch(1, p, g->dtype, (hipStream_t)stream);
 }
@@ -439,21 +429,21 @@ int ea_lara_bwd_finish(const ea_lara_geom* g, const ea_t4* q, const float* qbar,
   int rc = fill_lara(g, p, false);
   if (rc != EA_OK) return rc;
   if (p.NCT > 4) return EA_E_UNSUPPORTED;
-  if (!t4_ok(dq, g->D)) return EA_E_BADARG;
+  if (!view_ok(dq, g->D, 2)) return EA_E_BADARG;
   const bool has_t = uq != nullptr;
-  if (has_t && (g->mis != EA_MIS_OPT || !t4_ok(q, g->D) || !qbar || !lse_t)) return EA_E_BADARG;
+  if (has_t && (g->mis != EA_MIS_OPT || !view_ok(q, g->D, 2) || !qbar || !lse_t)) return EA_E_BADARG;
   if (pool_r > 0) {
-    if (!dpq || !dpk || !t4_ok(dk, g->D) || gh <= 0 || gw <= 0 || gh * gw != g->N || gh % pool_r || gw % pool_r)
+    if (!dpq || !dpk || !view_ok(dk, g->D, 2) || gh <= 0 || gw <= 0 || gh * gw != g->N || gh % pool_r || gw % pool_r)
       return EA_E_BADARG;
     p.dpq = dpq; p.dpk = dpk; p.pool_r = pool_r; p.pool_gw = gw;
     p.pool_L = (gh / pool_r) * (gw / pool_r);
     p.pool_inv = 1.f / (float)(pool_r * pool_r);
-    p.dk = mkl(dk);
+    p.dk = mk(dk);
   } else if (!has_t) {
     return EA_OK;                                   // nothing to do
   }
-  if (has_t) { p.q = mkl(q); p.qbar = qbar; p.uq = uq; p.lse_t = lse_t; }
-  p.dq = mkl(dq);
+  if (has_t) { p.q = mk(q); p.qbar = qbar; p.uq = uq; p.lse_t = lse_t; }
+  p.dq = mk(dq);
   return lara_f_dispatch(2, p, g->dtype, (hipStream_t)stream);
 }
 
@@ -465,11 +455,11 @@ int ea_lara_out_fwd_merge(const ea_lara_geom* g, const ea_t4* q, const float* om
   int rc = fill_lara(g, p, false);
   if (rc != EA_OK) return rc;
   if (p.NCT > 4 || S < 1 || S > 4) return EA_E_UNSUPPORTED;
-  if (!t4_ok(q, g->D) || !t4_ok(out, g->D) || !omega || !p_ml || !p_kv || !lp || !kv || !lse_k || !cst) return EA_E_BADARG;
+  if (!view_ok(q, g->D, 2) || !view_ok(out, g->D, 2) || !omega || !p_ml || !p_kv || !lp || !kv || !lse_k || !cst) return EA_E_BADARG;
   if (g->mis == EA_MIS_OPT && (!qbar || !lse_t || !bhv)) return EA_E_BADARG;
   if (g->mis == EA_MIS_BIASED && !qbar) return EA_E_BADARG;
   if ((lseZ == nullptr) != (tmean == nullptr)) return EA_E_BADARG;
-  p.q = mkl(q); p.o = mkl(out); p.omega = omega; p.qbar = qbar; p.bhv = bhv; p.lseZ = lseZ; p.tmean = tmean;
+  p.q = mk(q); p.o = mk(out); p.omega = omega; p.qbar = qbar; p.bhv = bhv; p.lseZ = lseZ; p.tmean = tmean;
   p.m_S = S; p.m_ml = p_ml; p.m_acc0 = p_kv; p.m_lp = lp;
   p.m_kv = kv; p.m_lsek = lse_k; p.m_lset = lse_t; p.m_cst = cst;
   return lara_x_dispatch(LX_FWDM, p, g->dtype, (hipStream_t)stream);
@@ -485,13 +475,13 @@ int ea_lara_out_proj_fwd_merge(const ea_lara_geom* g, const ea_t4* q, const floa
   int rc = fill_lara(g, p, false);
   if (rc != EA_OK) return rc;
   if (!lara_xp_supported(g->H, g->D, g->C, S)) return EA_E_UNSUPPORTED;
-  if (!t4_ok(q, g->D) || !t4_ok(out, g->D) || !omega || !p_ml || !p_kv || !lp || !kv || !lse_k || !cst) return EA_E_BADARG;
+  if (!view_ok(q, g->D, 2) || !view_ok(out, g->D, 2) || !omega || !p_ml || !p_kv || !lp || !kv || !lse_k || !cst) return EA_E_BADARG;
   if (g->mis == EA_MIS_OPT && (!qbar || !lse_t || !bhv)) return EA_E_BADARG;
   if (g->mis == EA_MIS_BIASED && !qbar) return EA_E_BADARG;
   if ((lseZ == nullptr) != (tmean == nullptr)) return EA_E_BADARG;
   if (!w_proj16 || ((uintptr_t)w_proj16 & 15) || !y || ((uintptr_t)y & 7) || ldy < 192 || (ldy & 3) ||
       (bias && ((uintptr_t)bias & 3))) return EA_E_BADARG;
-  p.q = mkl(q); p.o = mkl(out); p.omega = omega; p.qbar = qbar; p.bhv = bhv; p.lseZ = lseZ; p.tmean = tmean;
+  p.q = mk(q); p.o = mk(out); p.omega = omega; p.qbar = qbar; p.bhv = bhv; p.lseZ = lseZ; p.tmean = tmean;
   p.m_S = S; p.m_ml = p_ml; p.m_acc0 = p_kv; p.m_lp = lp;
   p.m_kv = kv; p.m_lsek = lse_k; p.m_lset = lse_t; p.m_cst = cst;
   LaraXpP xp;
@@ -508,11 +498,11 @@ int ea_lara_bwd_k_fused_merge(const ea_lara_geom* g, const ea_t4* k, const ea_t4
   int rc = fill_lara(g, p, false);
   if (rc != EA_OK) return rc;
   if (p.NCT > 4 || S < 1 || S > 4) return EA_E_UNSUPPORTED;
-  if (!t4_ok(k, g->D) || !t4_ok(v, g->D) || !t4_ok(dk, g->D) || !t4_ok(dv, g->D) || !omega || !kv || !lse_k || !p_ml ||
+  if (!view_ok(k, g->D, 2) || !view_ok(v, g->D, 2) || !view_ok(dk, g->D, 2) || !view_ok(dv, g->D, 2) || !omega || !kv || !lse_k || !p_ml ||
       !p_dkv || !p_dom || !p_domk || !dlp || !domq) return EA_E_BADARG;
   if (g->mis == EA_MIS_OPT && (!qbar || !p_m1 || !p_m2 || !dqbar || !uq || !dbh)) return EA_E_BADARG;
   if (g->mis == EA_MIS_BIASED && !dqbar) return EA_E_BADARG;
-  p.k = mkl(k); p.v = mkl(v); p.dk = mkl(dk); p.dv = mkl(dv); p.mask = mask; p.omega = omega; p.qbar = qbar;
+  p.k = mk(k); p.v = mk(v); p.dk = mk(dk); p.dv = mk(dv); p.mask = mask; p.omega = omega; p.qbar = qbar;
   p.kv = kv; p.lse_k = lse_k; p.p_acc0 = p_domk;
   p.m_S = S; p.m_ml = p_ml; p.m_acc0 = p_dkv; p.m_acc1 = p_dom; p.m_acc2 = p_m1; p.m_acc3 = p_m2;
   p.m_dbh = dbh; p.m_dlp = dlp; p.m_domq = domq; p.m_dqbar = dqbar; p.m_uq = uq;
@@ -525,8 +515,8 @@ int ea_lara_bwd_qcorr(const ea_lara_geom* g, const ea_t4* q, const float* qbar, 
   int rc = fill_lara(g, p, false);
   if (rc != EA_OK) return rc;
   if (g->mis != EA_MIS_OPT) return EA_E_BADARG;
-  if (!t4_ok(q, g->D) || !t4_ok(dq, g->D) || !qbar || !uq || !lse_t) return EA_E_BADARG;
-  p.q = mkl(q); p.dq = mkl(dq); p.qbar = qbar; p.uq = uq; p.lse_t = lse_t;
+  if (!view_ok(q, g->D, 2) || !view_ok(dq, g->D, 2) || !qbar || !uq || !lse_t) return EA_E_BADARG;
+  p.q = mk(q); p.dq = mk(dq); p.qbar = qbar; p.uq = uq; p.lse_t = lse_t;
   return lara_x_dispatch(LX_QCORR, p, g->dtype, (hipStream_t)stream);
 }
 
@@ -550,7 +540,7 @@ int ea_softmax_attn_fwd(int32_t B, int32_t H, int32_t N, int32_t D, int32_t dtyp
   SmP p = {};
   int rc = fill_sm(B, H, N, D, dtype, scale, p);
   if (rc != EA_OK) return rc;
-  if (!t4_ok(q, D) || !t4_ok(k, D) || !t4_ok(v, D) || !t4_ok(out, D) || !lse) return EA_E_BADARG;
+  if (!view_ok(q, D, 2) || !view_ok(k, D, 2) || !view_ok(v, D, 2) || !view_ok(out, D, 2) || !lse) return EA_E_BADARG;
   if (key_norm_bias && keep) return EA_E_UNSUPPORTED;
   p.key_norm_bias = key_norm_bias;
   p.keep = keep; p.keep_scale = keep_scale; p.keep_ld = (N + 63) / 64 * 64;
@@ -570,8 +560,8 @@ int ea_softmax_attn_bwd(int32_t B, int32_t H, int32_t N, int32_t D, int32_t dtyp
   if (key_norm_bias && keep) return EA_E_UNSUPPORTED;
   p.key_norm_bias = key_norm_bias;
   p.keep = keep; p.keep_scale = keep_scale; p.keep_ld = (N + 63) / 64 * 64;
-  if (!t4_ok(q, D) || !t4_ok(k, D) || !t4_ok(v, D) || !t4_ok(out, D) || !t4_ok(dout, D) ||
-      !t4_ok(dq, D) || !t4_ok(dk, D) || !t4_ok(dv, D) || !lse || !delta) return EA_E_BADARG;
+  if (!view_ok(q, D, 2) || !view_ok(k, D, 2) || !view_ok(v, D, 2) || !view_ok(out, D, 2) || !view_ok(dout, D, 2) ||
+      !view_ok(dq, D, 2) || !view_ok(dk, D, 2) || !view_ok(dv, D, 2) || !lse || !delta) return EA_E_BADARG;
   SM_SET(q, q); SM_SET(k, k); SM_SET(v, v); SM_SET(o, out); SM_SET(dout, dout);
   SM_SET(dq, dq); SM_SET(dk, dk); SM_SET(dv, dv);
   p.mask = mask; p.lse = const_cast<float*>(lse); p.delta = delta;
@@ -583,7 +573,7 @@ int ea_softmax_sample(int32_t B, int32_t H, int32_t N, int32_t D, int32_t dtype,
   SmP p = {};
   int rc = fill_sm(B, H, N, D, dtype, scale, p);
   if (rc != EA_OK) return rc;
-  if (!t4_ok(q, D) || !t4_ok(k, D) || !seed || !index) return EA_E_BADARG;
+  if (!view_ok(q, D, 2) || !view_ok(k, D, 2) || !seed || !index) return EA_E_BADARG;
   SM_SET(q, q); SM_SET(k, k);
   p.seed = reinterpret_cast<const unsigned long long*>(seed);
   p.sample_out = reinterpret_cast<long long*>(index);
@@ -621,8 +611,8 @@ int ea_performer_kmax(const ea_perf_geom* g, const ea_t4* k, const float* W, flo
   LaraP p = {};
   int rc = fill_perf(g, p, true);
   if (rc != EA_OK) return rc;
-  if (!t4_ok(k, g->D) || !W || !p_ml) return EA_E_BADARG;
-  p.k = mkl(k); p.omega = W; p.p_ml = p_ml;
+  if (!view_ok(k, g->D, 2) || !W || !p_ml) return EA_E_BADARG;
+  p.k = mk(k); p.omega = W; p.p_ml = p_ml;
   return lara_y_dispatch(LY_PMAX, p, g->dtype, (hipStream_t)stream);
 }
 
@@ -631,8 +621,8 @@ int ea_performer_kv(const ea_perf_geom* g, const ea_t4* k, const ea_t4* v, const
   LaraP p = {};
   int rc = fill_perf(g, p, true);
   if (rc != EA_OK) return rc;
-  if (!t4_ok(k, g->D) || !t4_ok(v, g->D) || !W || !stab || !p_ml || !p_kv) return EA_E_BADARG;
-  p.k = mkl(k); p.v = mkl(v); p.mask = mask; p.omega = W; p.stab = stab; p.p_ml = p_ml; p.p_acc0 = p_kv;
+  if (!view_ok(k, g->D, 2) || !view_ok(v, g->D, 2) || !W || !stab || !p_ml || !p_kv) return EA_E_BADARG;
+  p.k = mk(k); p.v = mk(v); p.mask = mask; p.omega = W; p.stab = stab; p.p_ml = p_ml; p.p_acc0 = p_kv;
   return lara_y_dispatch(LY_PKV, p, g->dtype, (hipStream_t)stream);
 }
 
@@ -641,8 +631,8 @@ int ea_performer_out(const ea_perf_geom* g, const ea_t4* q, const float* W, cons
   LaraP p = {};
   int rc = fill_perf(g, p, false);
   if (rc != EA_OK) return rc;
-  if (!t4_ok(q, g->D) || !t4_ok(out, g->D) || !W || !kv || !ksum) return EA_E_BADARG;
-  p.q = mkl(q); p.o = mkl(out); p.omega = W; p.kv = kv; p.cst = ksum;
+  if (!view_ok(q, g->D, 2) || !view_ok(out, g->D, 2) || !W || !kv || !ksum) return EA_E_BADARG;
+  p.q = mk(q); p.o = mk(out); p.omega = W; p.kv = kv; p.cst = ksum;
   return lara_x_dispatch(LX_POUT, p, g->dtype, (hipStream_t)stream);
 }
 
@@ -652,9 +642,9 @@ int ea_performer_bwd_q(const ea_perf_geom* g, const ea_t4* q, const ea_t4* out, 
   LaraP p = {};
   int rc = fill_perf(g, p, false);
   if (rc != EA_OK) return rc;
-  if (!t4_ok(q, g->D) || !t4_ok(out, g->D) || !t4_ok(dout, g->D) || !t4_ok(dq, g->D) || !W || !kv ||
+  if (!view_ok(q, g->D, 2) || !view_ok(out, g->D, 2) || !view_ok(dout, g->D, 2) || !view_ok(dq, g->D, 2) || !W || !kv ||
       !ksum || !stabq || !invden || !dden) return EA_E_BADARG;
-  p.q = mkl(q); p.o = mkl(out); p.dout = mkl(dout); p.dq = mkl(dq); p.omega = W; p.kv = kv; p.cst = ksum;
+  p.q = mk(q); p.o = mk(out); p.dout = mk(dout); p.dq = mk(dq); p.omega = W; p.kv = kv; p.cst = ksum;
   p.lseZ = stabq; p.tmean = invden; p.rowdot = dden;
   return lara_x_dispatch(LX_PBWDQ, p, g->dtype, (hipStream_t)stream);
 }
@@ -665,9 +655,9 @@ int ea_performer_bwd_qstats(const ea_perf_geom* g, const ea_t4* q, const ea_t4* 
   LaraP p = {};
   int rc = fill_perf(g, p, true);
   if (rc != EA_OK) return rc;
-  if (!t4_ok(q, g->D) || !t4_ok(dout, g->D) || !W || !stabq || !invden || !dden || !p_ml || !p_dkv)
+  if (!view_ok(q, g->D, 2) || !view_ok(dout, g->D, 2) || !W || !stabq || !invden || !dden || !p_ml || !p_dkv)
     return EA_E_BADARG;
-  p.q = mkl(q); p.dout = mkl(dout); p.omega = W;
+  p.q = mk(q); p.dout = mk(dout); p.omega = W;
   p.lseZ = const_cast<float*>(stabq); p.tmean = const_cast<float*>(invden); p.rowdot = const_cast<float*>(dden);
   p.p_ml = p_ml; p.p_acc0 = p_dkv;
   return lara_y_dispatch(LY_PBWDQ, p, g->dtype, (hipStream_t)stream);
@@ -679,9 +669,9 @@ int ea_performer_bwd_k(const ea_perf_geom* g, const ea_t4* k, const ea_t4* v, co
   LaraP p = {};
   int rc = fill_perf(g, p, false);
   if (rc != EA_OK) return rc;
-  if (!t4_ok(k, g->D) || !t4_ok(v, g->D) || !t4_ok(dk, g->D) || !t4_ok(dv, g->D) || !W || !stab ||
+  if (!view_ok(k, g->D, 2) || !view_ok(v, g->D, 2) || !view_ok(dk, g->D, 2) || !view_ok(dv, g->D, 2) || !W || !stab ||
       !dkv || !dksum) return EA_E_BADARG;
-  p.k = mkl(k); p.v = mkl(v); p.dk = mkl(dk); p.dv = mkl(dv); p.mask = mask; p.omega = W; p.stab = stab;
+  p.k = mk(k); p.v = mk(v); p.dk = mk(dk); p.dv = mk(dv); p.mask = mask; p.omega = W; p.stab = stab;
   p.dkv = dkv; p.rsum = dksum;
   return lara_x_dispatch(LX_PBWDK, p, g->dtype, (hipStream_t)stream);
 }
@@ -1257,19 +1247,9 @@ int ea_lara_fold_bwd(int32_t C, int32_t heads, const float* W, const float* b, c
 }  // extern "C"
 
 // ---- Performer in exact fp32 arithmetic (ea_performer_f32.hip) ----
-static bool pf_t4_ok(const ea_t4* t, int dtype) {
-  const int a = dtype == EA_F32 ? 4 : 8;                  // 16-byte vector access
-  return t && t->ptr && ((uintptr_t)t->ptr % 16 == 0) && t->sb % a == 0 && t->sh % a == 0 && t->sn % a == 0 && t->sn >= 64;
-}
-static Pf32T pf_mk(const ea_t4* t) {
-  Pf32T r;
-  r.p = t ? (char*)t->ptr : nullptr;
-  r.sb = t ? t->sb : 0; r.sh = t ? t->sh : 0; r.sn = t ? t->sn : 0;
-  return r;
-}
 static int pf_fill(const ea_perf_geom* g, Pf32P& p) {
   if (!g || g->B <= 0 || g->H <= 0 || g->N <= 0 || g->dtype < 0 || g->dtype > EA_F32) return EA_E_BADARG;
-  if (g->D != 64 || g->M <= 0 || g->M > 96 || (g->M & 15)) return EA_E_UNSUPPORTED;
+  if (g->D != 64 || g->M <= 0 || g->M > PF32_MAX_M || (g->M & 15)) return EA_E_UNSUPPORTED;
   p.B = g->B; p.H = g->H; p.N = g->N; p.M = g->M; p.dtype = g->dtype;
   return EA_OK;
 }
@@ -1279,15 +1259,16 @@ extern "C" {
 int32_t ea_performer_f32_parts(const ea_perf_geom* g) {
   Pf32P p = {};
   const int rc = pf_fill(g, p);
-  return rc != EA_OK ? rc : pf32_slices(g->B * g->H, g->N);
+  return rc != EA_OK ? rc : f32tile::plan_slices(g->B * g->H, g->N).S;
 }
 
 int ea_performer_f32_kmax(const ea_perf_geom* g, const ea_t4* k, const float* W, float* p_max, void* stream) {
   Pf32P p = {};
   const int rc = pf_fill(g, p);
   if (rc != EA_OK) return rc;
-  if (!pf_t4_ok(k, g->dtype) || !W || !p_max) return EA_E_BADARG;
-  p.k = pf_mk(k); p.W = W; p.p_max = p_max;
+  const int esz = g->dtype == EA_F32 ? 4 : 2;
+  if (!view_ok(k, 64, esz) || !W || !p_max) return EA_E_BADARG;
+  p.k = mk(k); p.W = W; p.p_max = p_max;
   return pf32_dispatch(0, p, (hipStream_t)stream);
 }
 
@@ -1296,8 +1277,9 @@ int ea_performer_f32_kv(const ea_perf_geom* g, const ea_t4* k, const ea_t4* v, c
   Pf32P p = {};
   const int rc = pf_fill(g, p);
   if (rc != EA_OK) return rc;
-  if (!pf_t4_ok(k, g->dtype) || !pf_t4_ok(v, g->dtype) || !W || !p_max || !p_kv || !p_ksum) return EA_E_BADARG;
-  p.k = pf_mk(k); p.v = pf_mk(v); p.mask = mask; p.W = W; p.p_max = const_cast<float*>(p_max); p.p_kv = p_kv; p.p_ks = p_ksum;
+  const int esz = g->dtype == EA_F32 ? 4 : 2;
+  if (!view_ok(k, 64, esz) || !view_ok(v, 64, esz) || !W || !p_max || !p_kv || !p_ksum) return EA_E_BADARG;
+  p.k = mk(k); p.v = mk(v); p.mask = mask; p.W = W; p.p_max = const_cast<float*>(p_max); p.p_kv = p_kv; p.p_ks = p_ksum;
   return pf32_dispatch(1, p, (hipStream_t)stream);
 }
 
@@ -1306,8 +1288,9 @@ int ea_performer_f32_out(const ea_perf_geom* g, const ea_t4* q, const float* W, 
   Pf32P p = {};
   const int rc = pf_fill(g, p);
   if (rc != EA_OK) return rc;
-  if (!pf_t4_ok(q, g->dtype) || !pf_t4_ok(out, g->dtype) || !W || !kv || !ksum) return EA_E_BADARG;
-  p.q = pf_mk(q); p.o = pf_mk(out); p.W = W; p.kv = kv; p.ksum = ksum;
+  const int esz = g->dtype == EA_F32 ? 4 : 2;
+  if (!view_ok(q, 64, esz) || !view_ok(out, 64, esz) || !W || !kv || !ksum) return EA_E_BADARG;
+  p.q = mk(q); p.o = mk(out); p.W = W; p.kv = kv; p.ksum = ksum;
   return pf32_dispatch(2, p, (hipStream_t)stream);
 }
 
@@ -1316,9 +1299,10 @@ int ea_performer_f32_bwd_q(const ea_perf_geom* g, const ea_t4* q, const ea_t4* d
   Pf32P p = {};
   const int rc = pf_fill(g, p);
   if (rc != EA_OK) return rc;
-  if (!pf_t4_ok(q, g->dtype) || !pf_t4_ok(dout, g->dtype) || !pf_t4_ok(dq, g->dtype) || !W || !kv || !ksum || !p_dkv || !p_dksum)
+  const int esz = g->dtype == EA_F32 ? 4 : 2;
+  if (!view_ok(q, 64, esz) || !view_ok(dout, 64, esz) || !view_ok(dq, 64, esz) || !W || !kv || !ksum || !p_dkv || !p_dksum)
     return EA_E_BADARG;
-  p.q = pf_mk(q); p.dout = pf_mk(dout); p.dq = pf_mk(dq); p.W = W; p.kv = kv; p.ksum = ksum; p.p_kv = p_dkv; p.p_ks = p_dksum;
+  p.q = mk(q); p.dout = mk(dout); p.dq = mk(dq); p.W = W; p.kv = kv; p.ksum = ksum; p.p_kv = p_dkv; p.p_ks = p_dksum;
   return pf32_dispatch(3, p, (hipStream_t)stream);
 }
 
@@ -1328,10 +1312,11 @@ int ea_performer_f32_bwd_k(const ea_perf_geom* g, const ea_t4* k, const ea_t4* v
   Pf32P p = {};
   const int rc = pf_fill(g, p);
   if (rc != EA_OK) return rc;
-  if (!pf_t4_ok(k, g->dtype) || !pf_t4_ok(v, g->dtype) || !pf_t4_ok(dk, g->dtype) || !pf_t4_ok(dv, g->dtype) || !W || !p_max ||
+  const int esz = g->dtype == EA_F32 ? 4 : 2;
+  if (!view_ok(k, 64, esz) || !view_ok(v, 64, esz) || !view_ok(dk, 64, esz) || !view_ok(dv, 64, esz) || !W || !p_max ||
       !dkv || !dksum) return EA_E_BADARG;
-  p.k = pf_mk(k); p.v = pf_mk(v); p.mask = mask; p.W = W; p.p_max = const_cast<float*>(p_max); p.dkv = dkv; p.dksum = dksum;
-  p.dk = pf_mk(dk); p.dv = pf_mk(dv);
+  p.k = mk(k); p.v = mk(v); p.mask = mask; p.W = W; p.p_max = const_cast<float*>(p_max); p.dkv = dkv; p.dksum = dksum;
+  p.dk = mk(dk); p.dv = mk(dv);
   return pf32_dispatch(4, p, (hipStream_t)stream);
 }
 
@@ -1341,11 +1326,11 @@ int ea_performer_f32_bwd_k(const ea_perf_geom* g, const ea_t4* k, const ea_t4* v
 static int kz_fill(const ea_kz_geom* g, KzP& p) {
   if (!g || g->B <= 0 || g->H <= 0 || g->N <= 0 || g->dtype < 0 || g->dtype > EA_F32 || g->map < EA_KZ_FAVORP ||
       g->map > EA_KZ_DPFP || (g->cos != 0 && g->cos != 1)) return EA_E_BADARG;
-  const bool w = g->map <= EA_KZ_FOURIER;
-  if (g->D != 64 || (w && (g->M <= 0 || g->M > 128 || (g->M & 15))) || (g->map == EA_KZ_DPFP && g->nu < 1))
+  const bool w = kz_has_w(g->map);
+  if (g->D != 64 || (w && (g->M <= 0 || g->M > KZ_MAX_M || (g->M & 15))) || (g->map == EA_KZ_DPFP && g->nu < 1))
     return EA_E_UNSUPPORTED;
-  const int Fb = g->map == EA_KZ_FOURIER ? 2 * g->M : w ? g->M : g->map == EA_KZ_DPFP ? 128 * g->nu : 64;
-  if (g->F != Fb * (g->cos ? 2 : 1) || g->F > 256) return EA_E_UNSUPPORTED;
+  const int Fb = kz_base_features(g->map, g->M, g->nu);
+  if (g->F != Fb * (g->cos ? 2 : 1) || g->F > KZ_MAX_F) return EA_E_UNSUPPORTED;
   p.B = g->B; p.H = g->H; p.N = g->N; p.M = w ? g->M : 16; p.F = g->F; p.Fb = Fb; p.nu = g->nu; p.cos = g->cos;
   p.map = g->map; p.dtype = g->dtype;
   return EA_OK;
@@ -1360,17 +1345,18 @@ extern "C" {
 int32_t ea_kernelized_parts(const ea_kz_geom* g) {
   KzP p = {};
   const int rc = kz_fill(g, p);
-  return rc != EA_OK ? rc : kz_slices(g->B * g->H, g->N);
+  return rc != EA_OK ? rc : f32tile::plan_slices(g->B * g->H, g->N).S;
 }
 
 int ea_kernelized_stats(const ea_kz_geom* g, const ea_t4* q, const ea_t4* k, const float* W, float* p_st, void* stream) {
   KzP p = {};
   const int rc = kz_fill(g, p);
   if (rc != EA_OK) return rc;
+  const int esz = g->dtype == EA_F32 ? 4 : 2;
   if (g->map != EA_KZ_FAVORP && g->map != EA_KZ_FOURIER) return EA_E_BADARG;
-  if (!pf_t4_ok(k, g->dtype) || (g->map == EA_KZ_FOURIER && !pf_t4_ok(q, g->dtype)) || !kz_w_ok(g, W) || !p_st)
+  if (!view_ok(k, 64, esz) || (g->map == EA_KZ_FOURIER && !view_ok(q, 64, esz)) || !kz_w_ok(g, W) || !p_st)
     return EA_E_BADARG;
-  p.q = pf_mk(q); p.k = pf_mk(k); p.W = W; p.p_st = p_st;
+  p.q = mk(q); p.k = mk(k); p.W = W; p.p_st = p_st;
   return kz_dispatch(0, p, (hipStream_t)stream);
 }
 
@@ -1379,9 +1365,10 @@ int ea_kernelized_kv(const ea_kz_geom* g, const ea_t4* k, const ea_t4* v, const 
   KzP p = {};
   const int rc = kz_fill(g, p);
   if (rc != EA_OK) return rc;
-  if (!pf_t4_ok(k, g->dtype) || !pf_t4_ok(v, g->dtype) || !kz_w_ok(g, W) || !kz_st_ok(g, p_st) || !p_kv || !p_ksum)
+  const int esz = g->dtype == EA_F32 ? 4 : 2;
+  if (!view_ok(k, 64, esz) || !view_ok(v, 64, esz) || !kz_w_ok(g, W) || !kz_st_ok(g, p_st) || !p_kv || !p_ksum)
     return EA_E_BADARG;
-  p.k = pf_mk(k); p.v = pf_mk(v); p.mask = mask; p.W = W; p.p_st = const_cast<float*>(p_st); p.p_kv = p_kv; p.p_ks = p_ksum;
+  p.k = mk(k); p.v = mk(v); p.mask = mask; p.W = W; p.p_st = const_cast<float*>(p_st); p.p_kv = p_kv; p.p_ks = p_ksum;
   return kz_dispatch(1, p, (hipStream_t)stream);
 }
 
@@ -1390,9 +1377,10 @@ int ea_kernelized_out(const ea_kz_geom* g, const ea_t4* q, const float* W, const
   KzP p = {};
   const int rc = kz_fill(g, p);
   if (rc != EA_OK) return rc;
-  if (!pf_t4_ok(q, g->dtype) || !pf_t4_ok(out, g->dtype) || !kz_w_ok(g, W) || !kz_st_ok(g, p_st) || !kv || !ksum)
+  const int esz = g->dtype == EA_F32 ? 4 : 2;
+  if (!view_ok(q, 64, esz) || !view_ok(out, 64, esz) || !kz_w_ok(g, W) || !kz_st_ok(g, p_st) || !kv || !ksum)
     return EA_E_BADARG;
-  p.q = pf_mk(q); p.o = pf_mk(out); p.W = W; p.p_st = const_cast<float*>(p_st); p.kv = kv; p.ksum = ksum;
+  p.q = mk(q); p.o = mk(out); p.W = W; p.p_st = const_cast<float*>(p_st); p.kv = kv; p.ksum = ksum;
   return kz_dispatch(2, p, (hipStream_t)stream);
 }
 
@@ -1402,9 +1390,10 @@ int ea_kernelized_bwd_q(const ea_kz_geom* g, const ea_t4* q, const ea_t4* dout, 
   KzP p = {};
   const int rc = kz_fill(g, p);
   if (rc != EA_OK) return rc;
-  if (!pf_t4_ok(q, g->dtype) || !pf_t4_ok(dout, g->dtype) || !pf_t4_ok(dq, g->dtype) || !kz_w_ok(g, W) || !kz_st_ok(g, p_st) ||
+  const int esz = g->dtype == EA_F32 ? 4 : 2;
+  if (!view_ok(q, 64, esz) || !view_ok(dout, 64, esz) || !view_ok(dq, 64, esz) || !kz_w_ok(g, W) || !kz_st_ok(g, p_st) ||
       !kv || !ksum || !p_dkv || !p_dksum || (p_dw && g->map > EA_KZ_FOURIER)) return EA_E_BADARG;
-  p.q = pf_mk(q); p.dout = pf_mk(dout); p.dq = pf_mk(dq); p.W = W; p.p_st = const_cast<float*>(p_st); p.kv = kv; p.ksum = ksum;
+  p.q = mk(q); p.dout = mk(dout); p.dq = mk(dq); p.W = W; p.p_st = const_cast<float*>(p_st); p.kv = kv; p.ksum = ksum;
   p.p_kv = p_dkv; p.p_ks = p_dksum; p.p_dw = p_dw;
   return kz_dispatch(3, p, (hipStream_t)stream);
 }
@@ -1415,10 +1404,11 @@ int ea_kernelized_bwd_k(const ea_kz_geom* g, const ea_t4* k, const ea_t4* v, con
   KzP p = {};
   const int rc = kz_fill(g, p);
   if (rc != EA_OK) return rc;
-  if (!pf_t4_ok(k, g->dtype) || !pf_t4_ok(v, g->dtype) || !pf_t4_ok(dk, g->dtype) || !pf_t4_ok(dv, g->dtype) ||
+  const int esz = g->dtype == EA_F32 ? 4 : 2;
+  if (!view_ok(k, 64, esz) || !view_ok(v, 64, esz) || !view_ok(dk, 64, esz) || !view_ok(dv, 64, esz) ||
       !kz_w_ok(g, W) || !kz_st_ok(g, p_st) || !dkv || !dksum || (p_dw && g->map > EA_KZ_FOURIER)) return EA_E_BADARG;
-  p.k = pf_mk(k); p.v = pf_mk(v); p.mask = mask; p.W = W; p.p_st = const_cast<float*>(p_st); p.dkv = dkv; p.dksum = dksum;
-  p.dk = pf_mk(dk); p.dv = pf_mk(dv); p.p_dw = p_dw;
+  p.k = mk(k); p.v = mk(v); p.mask = mask; p.W = W; p.p_st = const_cast<float*>(p_st); p.dkv = dkv; p.dksum = dksum;
+  p.dk = mk(dk); p.dv = mk(dv); p.p_dw = p_dw;
   return kz_dispatch(4, p, (hipStream_t)stream);
 }
 
@@ -1544,12 +1534,6 @@ int ea_linear_wsw(int32_t dtype, int32_t rows, int32_t B, int32_t gh, int32_t gw
 }  // extern "C"
 
 // ---- ScatterBrain feature half (ea_scatter.hip) ----
-static T4s mks(const ea_t4* t) {
-  T4s r;
-  r.p = t ? (char*)t->ptr : nullptr;
-  r.sb = t ? t->sb : 0; r.sh = t ? t->sh : 0; r.sn = t ? t->sn : 0;
-  return r;
-}
 static int fill_sb(const ea_sb_geom* g, SbP& p) {
   if (!g || g->B <= 0 || g->H <= 0 || g->N <= 0 || g->window <= 0 || (g->dtype != EA_BF16 && g->dtype != EA_F16))
     return EA_E_BADARG;
@@ -1596,8 +1580,8 @@ int ea_scatter_kmax(const ea_sb_geom* g, const ea_t4* k, const uint8_t* mask, co
   if (!g) return EA_E_BADARG;
   int rc = fill_sb_stats(g, p);
   if (rc != EA_OK) return rc;
-  if (!t4_ok(k, g->D) || !W || !p_ml) return EA_E_BADARG;
-  p.k = mkl(k); p.mask = mask; p.omega = W; p.p_ml = p_ml;
+  if (!view_ok(k, g->D, 2) || !W || !p_ml) return EA_E_BADARG;
+  p.k = mk(k); p.mask = mask; p.omega = W; p.p_ml = p_ml;
   return lara_y_dispatch(LY_PMAX, p, g->dtype, (hipStream_t)stream);
 }
 
@@ -1607,8 +1591,8 @@ int ea_scatter_kv(const ea_sb_geom* g, const ea_t4* k, const ea_t4* v, const uin
   if (!g) return EA_E_BADARG;
   int rc = fill_sb_stats(g, p);
   if (rc != EA_OK) return rc;
-  if (!t4_ok(k, g->D) || !t4_ok(v, g->D) || !W || !mx || !p_ml || !p_kv) return EA_E_BADARG;
-  p.k = mkl(k); p.v = mkl(v); p.mask = mask; p.omega = W; p.stab = mx; p.p_ml = p_ml; p.p_acc0 = p_kv;
+  if (!view_ok(k, g->D, 2) || !view_ok(v, g->D, 2) || !W || !mx || !p_ml || !p_kv) return EA_E_BADARG;
+  p.k = mk(k); p.v = mk(v); p.mask = mask; p.omega = W; p.stab = mx; p.p_ml = p_ml; p.p_acc0 = p_kv;
   return lara_y_dispatch(LY_PKV, p, g->dtype, (hipStream_t)stream);
 }
 
@@ -1626,11 +1610,11 @@ int ea_scatter_bwd_window(const ea_sb_geom* g, const ea_t4* q, const ea_t4* k, c
   SbP p = {};
   int rc = fill_sb(g, p);
   if (rc != EA_OK) return rc;
-  if (!t4_ok(q, 64) || !t4_ok(k, 64) || !t4_ok(v, 64) || !t4_ok(oloc, 64) || !t4_ok(dout, 64) || !t4_ok(dq, 64) ||
-      !t4_ok(dk, 64) || !t4_ok(dv, 64) || !t4_ok(doloc, 64) || !W || !mx || !zall || !sall || !lse_loc || !r || !dlse ||
+  if (!view_ok(q, 64, 2) || !view_ok(k, 64, 2) || !view_ok(v, 64, 2) || !view_ok(oloc, 64, 2) || !view_ok(dout, 64, 2) || !view_ok(dq, 64, 2) ||
+      !view_ok(dk, 64, 2) || !view_ok(dv, 64, 2) || !view_ok(doloc, 64, 2) || !W || !mx || !zall || !sall || !lse_loc || !r || !dlse ||
       !p_dsall || !p_dzall) return EA_E_BADARG;
-  p.q = mks(q); p.k = mks(k); p.v = mks(v); p.oloc = mks(oloc); p.dout = mks(dout); p.dq = mks(dq); p.dk = mks(dk);
-  p.dv = mks(dv); p.doloc = mks(doloc); p.mask = mask; p.Wf = W; p.mx = mx; p.zall = zall; p.sall = sall;
+  p.q = mk(q); p.k = mk(k); p.v = mk(v); p.oloc = mk(oloc); p.dout = mk(dout); p.dq = mk(dq); p.dk = mk(dk);
+  p.dv = mk(dv); p.doloc = mk(doloc); p.mask = mask; p.Wf = W; p.mx = mx; p.zall = zall; p.sall = sall;
   p.lse_loc = lse_loc; p.r = const_cast<float*>(r); p.dlse = dlse; p.p_dsall = p_dsall; p.p_dzall = p_dzall;
   return sb_bwd_dispatch(0, p, g->dtype, (hipStream_t)stream);
 }
@@ -1641,9 +1625,9 @@ int ea_scatter_bwd_global(const ea_sb_geom* g, const ea_t4* k, const ea_t4* v, c
   SbP p = {};
   int rc = fill_sb(g, p);
   if (rc != EA_OK) return rc;
-  if (!t4_ok(k, 64) || !t4_ok(v, 64) || !t4_ok(dk, 64) || !t4_ok(dv, 64) || !W || !mx || !dsall || !dzall)
+  if (!view_ok(k, 64, 2) || !view_ok(v, 64, 2) || !view_ok(dk, 64, 2) || !view_ok(dv, 64, 2) || !W || !mx || !dsall || !dzall)
     return EA_E_BADARG;
-  p.k = mks(k); p.v = mks(v); p.dk = mks(dk); p.dv = mks(dv); p.mask = mask; p.Wf = W; p.mx = mx;
+  p.k = mk(k); p.v = mk(v); p.dk = mk(dk); p.dv = mk(dv); p.mask = mask; p.Wf = W; p.mx = mx;
   p.zall = mx; p.sall = dsall;                       // (unused in the global pass; kept valid)
   p.dsall = dsall; p.dzall = dzall;
   p.wpb = 1;
@@ -1656,9 +1640,9 @@ int ea_scatter_fwd(const ea_sb_geom* g, const ea_t4* q, const ea_t4* k, const ea
   SbP p = {};
   int rc = fill_sb(g, p);
   if (rc != EA_OK) return rc;
-  if (!t4_ok(q, 64) || !t4_ok(k, 64) || !t4_ok(v, 64) || !t4_ok(oloc, 64) || !t4_ok(out, 64) || !W || !mx || !zall ||
+  if (!view_ok(q, 64, 2) || !view_ok(k, 64, 2) || !view_ok(v, 64, 2) || !view_ok(oloc, 64, 2) || !view_ok(out, 64, 2) || !W || !mx || !zall ||
       !sall || !lse_loc || !r) return EA_E_BADARG;
-  p.q = mks(q); p.k = mks(k); p.v = mks(v); p.oloc = mks(oloc); p.out = mks(out); p.mask = mask; p.Wf = W;
+  p.q = mk(q); p.k = mk(k); p.v = mk(v); p.oloc = mk(oloc); p.out = mk(out); p.mask = mask; p.Wf = W;
   p.mx = mx; p.zall = zall; p.sall = sall; p.lse_loc = lse_loc; p.r = r;
   return sb_fwd_dispatch(p, g->dtype, (hipStream_t)stream);
 }
@@ -1687,9 +1671,9 @@ int ea_scatter_ov_fwd(const ea_sb_geom* g, int32_t ext, const ea_t4* q, const ea
   SbP p = {};
   int rc = fill_sb_ov(g, ext, p);
   if (rc != EA_OK) return rc;
-  if (!t4_ok(q, 64) || !t4_ok(k, 64) || !t4_ok(v, 64) || !t4_ok(oloc, 64) || !t4_ok(out, 64) || !W || !mx || !zall ||
+  if (!view_ok(q, 64, 2) || !view_ok(k, 64, 2) || !view_ok(v, 64, 2) || !view_ok(oloc, 64, 2) || !view_ok(out, 64, 2) || !W || !mx || !zall ||
       !sall || !lse_loc || !r) return EA_E_BADARG;
-  p.q = mks(q); p.k = mks(k); p.v = mks(v); p.oloc = mks(oloc); p.out = mks(out); p.mask = mask; p.Wf = W;
+  p.q = mk(q); p.k = mk(k); p.v = mk(v); p.oloc = mk(oloc); p.out = mk(out); p.mask = mask; p.Wf = W;
   p.mx = mx; p.zall = zall; p.sall = sall; p.lse_loc = lse_loc; p.r = r;
   return sb_ov_dispatch(0, p, g->dtype, (hipStream_t)stream);
 }
@@ -1702,11 +1686,11 @@ int ea_scatter_ov_bwd_window(const ea_sb_geom* g, int32_t ext, const ea_t4* q, c
   SbP p = {};
   int rc = fill_sb_ov(g, ext, p);
   if (rc != EA_OK) return rc;
-  if (!t4_ok(q, 64) || !t4_ok(k, 64) || !t4_ok(v, 64) || !t4_ok(oloc, 64) || !t4_ok(dout, 64) || !t4_ok(dq, 64) ||
-      !t4_ok(doloc, 64) || !W || !mx || !zall || !sall || !lse_loc || !r || !dlse || !w_ds || !w_dzall || !w_dzwin)
+  if (!view_ok(q, 64, 2) || !view_ok(k, 64, 2) || !view_ok(v, 64, 2) || !view_ok(oloc, 64, 2) || !view_ok(dout, 64, 2) || !view_ok(dq, 64, 2) ||
+      !view_ok(doloc, 64, 2) || !W || !mx || !zall || !sall || !lse_loc || !r || !dlse || !w_ds || !w_dzall || !w_dzwin)
     return EA_E_BADARG;
-  p.q = mks(q); p.k = mks(k); p.v = mks(v); p.oloc = mks(oloc); p.dout = mks(dout); p.dq = mks(dq);
-  p.doloc = mks(doloc); p.mask = mask; p.Wf = W; p.mx = mx; p.zall = zall; p.sall = sall;
+  p.q = mk(q); p.k = mk(k); p.v = mk(v); p.oloc = mk(oloc); p.dout = mk(dout); p.dq = mk(dq);
+  p.doloc = mk(doloc); p.mask = mask; p.Wf = W; p.mx = mx; p.zall = zall; p.sall = sall;
   p.lse_loc = lse_loc; p.r = const_cast<float*>(r); p.dlse = dlse; p.p_dsall = w_ds; p.p_dzall = w_dzall;
   p.ws_dz = w_dzwin;
   return sb_ov_dispatch(1, p, g->dtype, (hipStream_t)stream);
@@ -1718,9 +1702,9 @@ int ea_scatter_ov_bwd_keys(const ea_sb_geom* g, int32_t ext, const ea_t4* k, con
   SbP p = {};
   int rc = fill_sb_ov(g, ext, p);
   if (rc != EA_OK) return rc;
-  if (!t4_ok(k, 64) || !t4_ok(v, 64) || !t4_ok(dk, 64) || !t4_ok(dv, 64) || !W || !mx || !dsall || !dzall || !w_ds ||
+  if (!view_ok(k, 64, 2) || !view_ok(v, 64, 2) || !view_ok(dk, 64, 2) || !view_ok(dv, 64, 2) || !W || !mx || !dsall || !dzall || !w_ds ||
       !w_dzwin) return EA_E_BADARG;
-  p.k = mks(k); p.v = mks(v); p.dk = mks(dk); p.dv = mks(dv); p.mask = mask; p.Wf = W; p.mx = mx;
+  p.k = mk(k); p.v = mk(v); p.dk = mk(dk); p.dv = mk(dv); p.mask = mask; p.Wf = W; p.mx = mx;
   p.dsall = dsall; p.dzall = dzall; p.p_dsall = const_cast<float*>(w_ds); p.ws_dz = const_cast<float*>(w_dzwin);
   return sb_ov_dispatch(2, p, g->dtype, (hipStream_t)stream);
 }
@@ -1832,7 +1816,7 @@ static int lara_layer_fwd_impl(const ea_lara_layer* c, const ea_t4* q, const ea_
     // everything the last launch would refuse is refused here, before the first one
     if (!P.fold_f || !lara_xp_supported(c->H, c->D, P.C, P.S_fwd)) return EA_E_UNSUPPORTED;
     if (!proj->w || ((uintptr_t)proj->w & 15) || !proj->y || ((uintptr_t)proj->y & 7) || proj->ldy < 192 || (proj->ldy & 3) ||
-        (proj->bias && ((uintptr_t)proj->bias & 3)) || !t4_ok(q, c->D) || !t4_ok(out, c->D)) return EA_E_BADARG;
+        (proj->bias && ((uintptr_t)proj->bias & 3)) || !view_ok(q, c->D, 2) || !view_ok(out, c->D, 2)) return EA_E_BADARG;
   }
   if (!saved || !tmp || (c->has_mlp && !params)) return EA_E_BADARG;
   const float* pr[8] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
@@ -2126,9 +2110,6 @@ int ea_eva_layer_bwd2(const ea_eva_layer* c, const ea_t4* q, const ea_t4* k, con
 }  // extern "C"
 
 // ---- fp32-faithful gathered attention (ea_f32_attn.hip) ----
-static bool f32_t4_ok(const ea_t4* t, int D) {
-  return t && t->ptr && ((uintptr_t)t->ptr % 16 == 0) && t->sb % 4 == 0 && t->sh % 4 == 0 && t->sn % 4 == 0 && t->sn >= D;
-}
 static F32T f32_mk(const ea_t4* t) {
   F32T r;
   r.p = t ? (const float*)t->ptr : nullptr;
@@ -2141,8 +2122,8 @@ static int fill_ga(const ea_f32_attn* g, const ea_t4* q, const ea_t4* k, const e
   if (!g || g->B <= 0 || g->H <= 0 || g->Nq <= 0 || g->Nk <= 0 || g->G <= 0 || g->Wq <= 0 || g->Wk < 0 || g->L < 0 ||
       g->Wk + g->L <= 0 || !idx_q || (g->Wk > 0 && !idx_k)) return EA_E_BADARG;
   if (g->D != 32 && g->D != 64 && g->D != 128) return EA_E_UNSUPPORTED;
-  if (!f32_t4_ok(q, g->D) || !f32_t4_ok(k, g->D) || !f32_t4_ok(v, g->D)) return EA_E_BADARG;
-  if (g->L > 0 && (!f32_t4_ok(ek, g->D) || !f32_t4_ok(ev, g->D))) return EA_E_BADARG;
+  if (!view_ok(q, g->D, 4) || !view_ok(k, g->D, 4) || !view_ok(v, g->D, 4)) return EA_E_BADARG;
+  if (g->L > 0 && (!view_ok(ek, g->D, 4) || !view_ok(ev, g->D, 4))) return EA_E_BADARG;
   if (bias && g->bias_ld < g->Wk) return EA_E_BADARG;
   if (keep && g->keep_ld < g->Wk + g->L) return EA_E_BADARG;
   p.q = f32_mk(q); p.k = f32_mk(k); p.v = f32_mk(v); p.ek = f32_mk(g->L > 0 ? ek : nullptr); p.ev = f32_mk(g->L > 0 ? ev : nullptr);
@@ -2162,7 +2143,7 @@ int ea_f32_attn_fwd(const ea_f32_attn* g, const ea_t4* q, const ea_t4* k, const 
   GaP p = {};
   int rc = fill_ga(g, q, k, v, ek, ev, idx_q, idx_k, bias, kmask, qmask, keep, p);
   if (rc != EA_OK) return rc;
-  if (!f32_t4_ok(out, g->D)) return EA_E_BADARG;
+  if (!view_ok(out, g->D, 4)) return EA_E_BADARG;
   p.o = f32_mk(out); p.lse = lse; p.stat = stat;
   return ga_dispatch(false, p, (hipStream_t)stream);
 }
@@ -2174,7 +2155,7 @@ int ea_f32_attn_bwd(const ea_f32_attn* g, const ea_t4* q, const ea_t4* k, const 
   GaP p = {};
   int rc = fill_ga(g, q, k, v, ek, ev, idx_q, idx_k, bias, kmask, qmask, keep, p);
   if (rc != EA_OK) return rc;
-  if (!f32_t4_ok(out, g->D) || !f32_t4_ok(dout, g->D) || !f32_t4_ok(dq, g->D) || !stat) return EA_E_BADARG;
+  if (!view_ok(out, g->D, 4) || !view_ok(dout, g->D, 4) || !view_ok(dq, g->D, 4) || !stat) return EA_E_BADARG;
   if (dbias && !bias) return EA_E_BADARG;
   p.o = f32_mk(out); p.dout = f32_mk(dout); p.dq = f32_mk(dq); p.stat = const_cast<float*>(stat); p.dlse = dlse;
   p.dk = dk; p.dv = dv; p.dek = g->L > 0 ? dek : nullptr; p.dev = g->L > 0 ? dev : nullptr; p.dbias = dbias;
@@ -2183,7 +2164,7 @@ int ea_f32_attn_bwd(const ea_f32_attn* g, const ea_t4* q, const ea_t4* k, const 
 
 int ea_f32_gather_mean_fwd(int32_t B, int32_t H, int32_t N, int32_t D, int32_t Cn, int32_t J, const ea_t4* x, const int32_t* idx,
                            const uint8_t* mask, float* mean, void* stream) {
-  if (B <= 0 || H <= 0 || N <= 0 || D <= 0 || (D & 3) || Cn <= 0 || J <= 0 || !f32_t4_ok(x, D) || !idx || !mean) return EA_E_BADARG;
+  if (B <= 0 || H <= 0 || N <= 0 || D <= 0 || (D & 3) || Cn <= 0 || J <= 0 || !view_ok(x, D, 4) || !idx || !mean) return EA_E_BADARG;
   GmP p = {};
   p.x = f32_mk(x); p.idx = idx; p.mask = mask; p.mean = mean; p.B = B; p.H = H; p.N = N; p.D = D; p.Cn = Cn; p.J = J;
   return gm_dispatch(false, p, (hipStream_t)stream);
@@ -2227,10 +2208,6 @@ int ea_layernorm_bwd(int32_t xtype, int32_t rows, int32_t C, const void* x, cons
 #include "ea_ceva_decode_linear.h"
 #include "ea_ceva_decode_vocab.h"
 #include "ea_vocab_score.h"
-static bool dec_t4_ok(const ea_t4* t, int D, int esz) {
-  const int a = 16 / esz;                                 // 16-byte aligned rows
-  return t && t->ptr && ((uintptr_t)t->ptr % 16 == 0) && t->sb % a == 0 && t->sh % a == 0 && t->sn % a == 0 && t->sn >= D;
-}
 static ea::DecT dec_mk(const ea_t4* t) {
   ea::DecT r;
   r.p = (const char*)t->ptr; r.sb = t->sb; r.sh = t->sh; r.sn = t->sn;
@@ -2279,9 +2256,9 @@ static int dec_fill(const DecG& g, const ea_t4* q, const ea_t4* k, const ea_t4* 
   const int rc = dec_check(g, pad, true);
   if (rc != EA_OK) return rc;
   const int esz = g.dtype == EA_F32 ? 4 : 2;
-  if (!dec_t4_ok(q, g.D, esz) || !dec_t4_ok(k, g.D, esz) || !dec_t4_ok(v, g.D, esz)) return EA_E_BADARG;
+  if (!view_ok(q, g.D, esz) || !view_ok(k, g.D, esz) || !view_ok(v, g.D, esz)) return EA_E_BADARG;
   const int lsz = g.l16 ? esz : 4;                        // (l16: 16-byte aligned rows of 8-element multiples)
-  if (!dec_t4_ok(lk, g.D, lsz) || !dec_t4_ok(lv, g.D, lsz) || (g.has_mask && !pad)) return EA_E_BADARG;
+  if (!view_ok(lk, g.D, lsz) || !view_ok(lv, g.D, lsz) || (g.has_mask && !pad)) return EA_E_BADARG;
   p.q = dec_mk(q); p.k = dec_mk(k); p.v = dec_mk(v); p.lk = dec_mk(lk); p.lv = dec_mk(lv);
   p.pad = g.has_mask ? pad : nullptr;
   p.B = g.B; p.H = g.H; p.D = g.D; p.dtype = g.dtype; p.w = g.window; p.e = g.ext; p.r = g.chunk;
@@ -2310,7 +2287,7 @@ static int dec_fill_attn(const DecG& g, const ea_t4* q, const ea_t4* k, const ea
                          const ea_t4* lk, const ea_t4* lv, const ea_t4* out, ea::DecP& p) {
   const int rc = dec_fill(g, q, k, v, pad, lk, lv, p);
   if (rc != EA_OK) return rc;
-  if (!dec_t4_ok(out, g.D, g.dtype == EA_F32 ? 4 : 2) || (g.has_bias && !bias)) return EA_E_BADARG;
+  if (!view_ok(out, g.D, g.dtype == EA_F32 ? 4 : 2) || (g.has_bias && !bias)) return EA_E_BADARG;
   p.o = dec_mk(out);
   p.bias = g.has_bias ? bias : nullptr;
   return EA_OK;
@@ -2399,7 +2376,7 @@ int ea_ceva_sdecode_merge(const ea_ceva_sdec_geom* g, const ea_t4* out, int32_t 
   const DecG dg = dec_read(g);
   const int rc = dec_check(dg, nullptr, true, false);
   if (rc != EA_OK) return rc;
-  if (!dec_t4_ok(out, dg.D, dg.dtype == EA_F32 ? 4 : 2)) return EA_E_BADARG;
+  if (!view_ok(out, dg.D, dg.dtype == EA_F32 ? 4 : 2)) return EA_E_BADARG;
   ea::DecMergeP p = {};
   p.o = dec_mk(out); p.ws = ws; p.pos = dg.pos; p.ntok = dg.ntok;
   p.H = dg.H; p.T = dg.T_new; p.cap = dg.cap; p.parts = parts;

@@ -11,37 +11,33 @@
 // cos weighting (cosFormer) doubles the features to [phi cos t_n, phi sin t_n], t_n = (pi/2) n / N.
 //
 // The skeleton is ea_performer_f32.hip's: one 8-wave workgroup per (b,h, sequence slice), 64-token tiles in fp32 LDS, every
-// product on v_mfma_f32_16x16x4_f32 (tile_mm), sequence-wide sums as per-slice partials added by ea_slice_sum.  What is new
+// product on v_mfma_f32_16x16x4_f32 (tile_mm), sequence-wide sums as per-slice partials added by ea_slice_sum; what the two
+// units share word for word (tile moves, row reductions, constants, slice plan) is ea_f32_tile.h.  What is new
 // is that the feature map is a compile-time policy (forward: tile -> phi; backward: d phi -> d logits / dx) and that the
 // feature dimension (up to 256) is processed in blocks of fb = 32 or 16 columns: the features of a tile are never whole in
 // LDS, only the block being worked on, so every kernel stays within the 160 KB of a CU next to the tiles, W and the logits.
 #include "ea_common.h"
 #include "ea_kernelized.h"
 #include "ea_f32_mm.h"
+#include "ea_f32_tile.h"
 
 namespace ea {
 
+using namespace f32tile;
+
 namespace {
 
-constexpr int TB = 64;            // tokens per tile
-constexpr int PD = 64;            // head dim
-constexpr int LDD = PD + 1;       // row stride of the [*][64] images
-constexpr int NTH = 512;          // 8 waves
-constexpr int NWV = NTH / 64;
-constexpr int LPR = NTH / TB;     // lanes per token row in the elementwise stages (8)
 constexpr int FBM = 32;           // largest feature block
 constexpr int LDF = FBM + 1;      // row stride of the feature-block images
-constexpr int FMAX = 256;         // features
+constexpr int FMAX = KZ_MAX_F;    // features
 constexpr int NACC = FMAX / 16 * (PD / 16) / NWV;   // [F][64] accumulator tiles per wave (8)
 constexpr int DP2 = 2 * PD;       // dpfp's x' width
 
-constexpr bool has_w(int map) { return map <= KZ_FOURIER; }
-
 // LDS image (floats) -- the same function sizes the launch on the host
-__host__ __device__ inline int kz_ld_l(int map, int M) { return has_w(map) ? M + 1 : 0; }
-__host__ __device__ inline int kz_ld_g(int map, int M) { return has_w(map) ? M + 1 : map == KZ_DPFP ? DP2 + 1 : LDD; }
+__host__ __device__ inline int kz_ld_l(int map, int M) { return kz_has_w(map) ? M + 1 : 0; }
+__host__ __device__ inline int kz_ld_g(int map, int M) { return kz_has_w(map) ? M + 1 : map == KZ_DPFP ? DP2 + 1 : LDD; }
 __host__ __device__ inline size_t kz_lds_floats(int map, int M) {
-  const size_t w = has_w(map) ? (size_t)M * LDD : 0, l = (size_t)TB * kz_ld_l(map, M);
+  const size_t w = kz_has_w(map) ? (size_t)M * LDD : 0, l = (size_t)TB * kz_ld_l(map, M);
   size_t g = (size_t)TB * kz_ld_g(map, M);
   if (g < (size_t)TB * LDD) g = (size_t)TB * LDD;                  // (the bwd_q out tile lives there too)
   return w + 2 * TB * LDD + l + 2 * TB * LDF + FBM * LDD + g + 8 * TB + FMAX;
@@ -60,7 +56,7 @@ EA_DEV Sm carve(float* sm, int map, int M) {
   size_t g = (size_t)TB * s.ldg;
   if (g < (size_t)TB * LDD) g = (size_t)TB * LDD;
   float* c = sm;
-  s.W = c; c += has_w(map) ? M * LDD : 0;
+  s.W = c; c += kz_has_w(map) ? M * LDD : 0;
   s.X = c; c += TB * LDD;
   s.Y = c; c += TB * LDD;
   s.L = c; c += TB * s.ldl;
@@ -73,63 +69,6 @@ EA_DEV Sm carve(float* sm, int map, int M) {
   s.vec = c + 8 * TB;
   return s;
 }
-
-// rows n0 .. n0 + 63 of a [B,H,N,64] view -> dst[row][65] fp32 (rows >= N: zeros); thread = (row, 8 channels)
-EA_DEV void load_tile(float* dst, const Pf32T& t, int b, int h, int n0, int N, int dtype, int tid) {
-  const int row = tid / LPR, c0 = (tid % LPR) * 8;
-  float f[8];
-#pragma unroll
-  for (int i = 0; i < 8; ++i) f[i] = 0.f;
-  if (n0 + row < N) {
-    const size_t eo = (size_t)b * t.sb + (size_t)h * t.sh + (size_t)(n0 + row) * t.sn + c0;
-    if (dtype == 2) {
-      const float* s = reinterpret_cast<const float*>(t.p) + eo;
-      const f32x4 v0 = *reinterpret_cast<const f32x4*>(s), v1 = *reinterpret_cast<const f32x4*>(s + 4);
-      f[0] = v0[0]; f[1] = v0[1]; f[2] = v0[2]; f[3] = v0[3]; f[4] = v1[0]; f[5] = v1[1]; f[6] = v1[2]; f[7] = v1[3];
-    } else {
-      const u32x4 w0 = ldg16(t.p + eo * 2);
-      if (dtype == 0) unpack8<BF16>(w0, f);
-      else unpack8<F16>(w0, f);
-    }
-  }
-#pragma unroll
-  for (int i = 0; i < 8; ++i) dst[row * LDD + c0 + i] = f[i];
-}
-
-// src[row][65] fp32 -> rows n0 .. of a [B,H,N,64] view in its I/O type (rows >= N dropped)
-EA_DEV void store_tile(const float* src, const Pf32T& t, int b, int h, int n0, int N, int dtype, int tid) {
-  const int row = tid / LPR, c0 = (tid % LPR) * 8;
-  if (n0 + row >= N) return;
-  float f[8];
-#pragma unroll
-  for (int i = 0; i < 8; ++i) f[i] = src[row * LDD + c0 + i];
-  const size_t eo = (size_t)b * t.sb + (size_t)h * t.sh + (size_t)(n0 + row) * t.sn + c0;
-  if (dtype == 2) {
-    float* d = reinterpret_cast<float*>(t.p) + eo;
-    *reinterpret_cast<f32x4*>(d) = f32x4{f[0], f[1], f[2], f[3]};
-    *reinterpret_cast<f32x4*>(d + 4) = f32x4{f[4], f[5], f[6], f[7]};
-  } else {
-    char* d = t.p + eo * 2;
-    if (dtype == 0) stg16(d, pack8<BF16>(f));
-    else stg16(d, pack8<F16>(f));
-  }
-}
-
-// [rows][64] fp32 global matrix -> dst[rows][65]
-EA_DEV void load_mat(float* dst, const float* src, int rows, int tid) {
-  for (int idx = tid; idx < rows * (PD / 4); idx += NTH) {
-    const int r = idx / (PD / 4), c = (idx - r * (PD / 4)) * 4;
-    const f32x4 v = *reinterpret_cast<const f32x4*>(src + (size_t)r * PD + c);
-    float* d = dst + r * LDD + c;
-    d[0] = v[0]; d[1] = v[1]; d[2] = v[2]; d[3] = v[3];
-  }
-}
-
-EA_DEV float row8_sum(float v) { v += __shfl_xor(v, 1); v += __shfl_xor(v, 2); v += __shfl_xor(v, 4); return v; }
-EA_DEV float row8_max(float v) { v = fmaxf(v, __shfl_xor(v, 1)); v = fmaxf(v, __shfl_xor(v, 2)); v = fmaxf(v, __shfl_xor(v, 4)); return v; }
-
-constexpr float KC = 0.35355339059327373f;   // 64^-1/4
-constexpr float KC2 = 0.0625f;               // 64^-1/2 / 2
 
 // c2 |x_n|^2 of the tile in X -> diag (row owners)
 EA_DEV void sq_norms(const float* X, float* diag, int tid) {
@@ -151,11 +90,6 @@ EA_DEV void logits(const Sm& s, int M, int tid) {
 #pragma unroll
     for (int r = 0; r < 4; ++r) s.L[(m0 + 4 * g + r) * s.ldl + n0 + li] = acc[r] * KC;
   }
-}
-
-EA_DEV void slice_range(const KzP& p, int s, int& n0, int& n1) {
-  n0 = s * p.tps;
-  n1 = min(p.N, n0 + p.tps);
 }
 
 // the (b,h)'s statistic `side` (0 key side, 1 query side): maximum of the slice maxima
@@ -278,7 +212,7 @@ EA_DEV void feat_bwd_block(const Sm& s, int f0, int fb, int Fb, int M, float r, 
 // the input gradient of the tile -> dst[64][65]: W maps c G W -/+ 2 c2 sdl x; dpfp dx' -> dx; relu / sigmoid-only G itself
 template <int MAP>
 EA_DEV void input_grad(float* dst, const Sm& s, int M, int tid) {
-  if (has_w(MAP)) {
+  if (kz_has_w(MAP)) {
     const int lane = tid & 63, wave = tid >> 6, g = lane >> 4, li = lane & 15;
     const float sg = MAP == KZ_FAVORP ? -2.f * KC2 : MAP == KZ_FOURIER ? 2.f * KC2 : 0.f;
     for (int t = wave; t < 16; t += NWV) {
@@ -308,13 +242,13 @@ EA_DEV void zero_g(const Sm& s, int M, int map, int tid) {
 
 // per-tile start shared by every kernel: load the x tile (and the second tile), logits, |x|^2, row prologue
 template <int MAP, bool COS>
-EA_DEV void tile_start(const Sm& s, const KzP& p, const Pf32T& xt, const Pf32T* yt, int ylim, int b, int h, int t0, int n1,
+EA_DEV void tile_start(const Sm& s, const KzP& p, const T4& xt, const T4* yt, int ylim, int b, int h, int t0, int n1,
                        bool key, float stat, float r, int tid) {
   __syncthreads();
   load_tile(s.X, xt, b, h, t0, p.N, p.dtype, tid);
   if (yt) load_tile(s.Y, *yt, b, h, t0, ylim, p.dtype, tid);
   __syncthreads();
-  if (has_w(MAP)) logits(s, p.M, tid);
+  if (kz_has_w(MAP)) logits(s, p.M, tid);
   if (MAP == KZ_FAVORP || MAP == KZ_FOURIER) sq_norms(s.X, s.diag, tid);
   __syncthreads();
   rows_prologue<MAP, COS>(s, p, b, t0, n1, key, stat, p.M, r, tid);
@@ -322,7 +256,7 @@ EA_DEV void tile_start(const Sm& s, const KzP& p, const Pf32T& xt, const Pf32T* 
 }
 
 EA_DEV void load_w(const Sm& s, const KzP& p, int map, int h, int tid) {
-  if (has_w(map)) load_mat(s.W, p.W + (size_t)h * p.M * PD, p.M, tid);
+  if (kz_has_w(map)) load_mat(s.W, p.W + (size_t)h * p.M * PD, p.M, tid);
 }
 
 // does accumulator tile i of this wave ([F][64] tiles t = wave + 8 i: feature tile t / 4, channel tile t % 4) lie in the
@@ -532,7 +466,7 @@ __global__ __launch_bounds__(NTH) void kz_bwd_q_kernel(const KzP p) {
   const float stat = MAP == KZ_FOURIER ? stat_of(p, bh, 1) : 0.f;
   int n0, n1;
   slice_range(p, sl, n0, n1);
-  if (has_w(MAP) && p.p_dw) dw_zero_if_empty(dw_part(p, b, h, 0, sl), p.M, n0, n1, tid);
+  if (kz_has_w(MAP) && p.p_dw) dw_zero_if_empty(dw_part(p, b, h, 0, sl), p.M, n0, n1, tid);
   f32x4 acc[NACC];
 #pragma unroll
   for (int i = 0; i < NACC; ++i) acc[i] = f32x4{0.f, 0.f, 0.f, 0.f};
@@ -593,7 +527,7 @@ __global__ __launch_bounds__(NTH) void kz_bwd_q_kernel(const KzP p) {
       feat_bwd_block<MAP, COS>(s, f0, p.fb, p.Fb, p.M, r, tid);
       __syncthreads();
     }
-    if (has_w(MAP) && p.p_dw) dw_accumulate(s, dw_part(p, b, h, 0, sl), p.M, t0 == n0, wave, lane);
+    if (kz_has_w(MAP) && p.p_dw) dw_accumulate(s, dw_part(p, b, h, 0, sl), p.M, t0 == n0, wave, lane);
     input_grad<MAP>(s.Y, s, p.M, tid);                       // dq tile (d num is dead)
     __syncthreads();
     store_tile(s.Y, p.dq, b, h, t0, n1, p.dtype, tid);
@@ -624,7 +558,7 @@ __global__ __launch_bounds__(NTH) void kz_bwd_k_kernel(const KzP p) {
   const float stat = MAP == KZ_FAVORP || MAP == KZ_FOURIER ? stat_of(p, bh, 0) : 0.f;
   int n0, n1;
   slice_range(p, sl, n0, n1);
-  if (has_w(MAP) && p.p_dw) dw_zero_if_empty(dw_part(p, b, h, 1, sl), p.M, n0, n1, tid);
+  if (kz_has_w(MAP) && p.p_dw) dw_zero_if_empty(dw_part(p, b, h, 1, sl), p.M, n0, n1, tid);
   for (int t0 = n0; t0 < n1; t0 += TB) {
     tile_start<MAP, COS>(s, p, p.k, &p.v, p.N, b, h, t0, n1, true, stat, r, tid);
     zero_g(s, p.M, MAP, tid);
@@ -649,7 +583,7 @@ __global__ __launch_bounds__(NTH) void kz_bwd_k_kernel(const KzP p) {
       feat_bwd_block<MAP, COS>(s, f0, p.fb, p.Fb, p.M, r, tid);
       __syncthreads();
     }
-    if (has_w(MAP) && p.p_dw) dw_accumulate(s, dw_part(p, b, h, 1, sl), p.M, t0 == n0, wave, lane);
+    if (kz_has_w(MAP) && p.p_dw) dw_accumulate(s, dw_part(p, b, h, 1, sl), p.M, t0 == n0, wave, lane);
     acc_to_tile(s.Y, acc2, wave, lane, [](int) { return 1.f; });     // v is dead: its tile takes dv
     __syncthreads();
     store_tile(s.Y, p.dv, b, h, t0, n1, p.dtype, tid);
@@ -661,15 +595,6 @@ __global__ __launch_bounds__(NTH) void kz_bwd_k_kernel(const KzP p) {
 }
 
 // ------------------------------------------------------------------------------------------------------------------------
-int kz_slices(int BH, int N) {
-  const int tiles = (N + TB - 1) / TB;
-  int S = (1024 + BH - 1) / BH;
-  if (S > tiles) S = tiles;
-  if (S < 1) S = 1;
-  if (S > 64) S = 64;
-  return S;
-}
-
 namespace {
 
 template <int MAP, bool COS>
@@ -713,29 +638,18 @@ int kz_launch_map(int which, const KzP& p, dim3 grid, size_t lds, hipStream_t st
 
 }  // namespace
 
-// feature count of a map before cos weighting (0: not a map / geometry this file is built for)
-static int kz_base_features(int map, int M, int nu) {
-  switch (map) {
-    case KZ_FAVORP: case KZ_RELU: return M;
-    case KZ_FOURIER: return 2 * M;
-    case KZ_RELU_ONLY: case KZ_SIGMOID_ONLY: return PD;
-    case KZ_DPFP: return nu >= 1 ? DP2 * nu : 0;
-    default: return 0;
-  }
-}
-
 int kz_dispatch(int which, const KzP& p0, hipStream_t st) {
   KzP p = p0;
   if (p.map < KZ_FAVORP || p.map > KZ_DPFP || p.dtype < 0 || p.dtype > 2 || p.B <= 0 || p.H <= 0 || p.N <= 0)
     return EA_E_BADARG;
-  if (has_w(p.map) && (p.M <= 0 || p.M > 128 || (p.M & 15))) return EA_E_UNSUPPORTED;
-  if (!has_w(p.map)) p.M = 16;                       // (unused: only sizes r = M^-1/2, which these maps do not read)
+  if (kz_has_w(p.map) && (p.M <= 0 || p.M > KZ_MAX_M || (p.M & 15))) return EA_E_UNSUPPORTED;
+  if (!kz_has_w(p.map)) p.M = 16;                       // (unused: only sizes r = M^-1/2, which these maps do not read)
   const int Fb = kz_base_features(p.map, p.M, p.nu);
   if (Fb <= 0 || Fb != p.Fb || p.F != Fb * (p.cos ? 2 : 1) || p.F > FMAX) return EA_E_UNSUPPORTED;
   p.fb = (Fb % FBM == 0 && (p.map != KZ_FOURIER || p.M % FBM == 0)) ? FBM : 16;
-  p.S = kz_slices(p.B * p.H, p.N);
-  const int tiles = (p.N + TB - 1) / TB;
-  p.tps = ((tiles + p.S - 1) / p.S) * TB;
+  const Slices sl = plan_slices(p.B * p.H, p.N);
+  p.S = sl.S;
+  p.tps = sl.tps;
   const dim3 grid((unsigned)(p.B * p.H), (unsigned)p.S);
   const size_t lds = kz_lds_floats(p.map, p.M) * sizeof(float);
   switch (p.map) {

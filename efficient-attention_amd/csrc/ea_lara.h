@@ -12,13 +12,9 @@
 // Natural-log quantities are carried in the log2 domain inside the kernels (suffix 2).
 #pragma once
 #include "ea_common.h"
+#include "ea_t4.h"
 
 namespace ea {
-
-struct T4l {
-  char* p;
-  int64_t sb, sh, sn;
-};
 
 enum { MIS_OPT = 0, MIS_BIASED = 1, MIS_BH = 2 };
 enum { LX_FWD = 0, LX_BWDQ = 1, LX_BWDK = 2, LX_QCORR = 3, LX_POUT = 4, LX_PBWDQ = 5, LX_PBWDK = 6, LX_FWDM = 7 };
@@ -28,7 +24,7 @@ enum { LY_FWD = 0, LY_BWDQ = 1, LY_BWDK = 2, LY_PMAX = 3, LY_PKV = 4, LY_PBWDQ =
 //   phi(x)[j] = m^-1/2 exp(d^-1/4 W_j.x - d^-1/2 |x|^2/2 - stab) + 1e-4
 
 struct LaraP {
-  T4l q, k, v, o, dout, dq, dk, dv;
+  T4 q, k, v, o, dout, dq, dk, dv;
   const uint8_t* mask;          // [B,N] key padding mask or null
   // landmark-side matrices, fp32 [BH, C, D]
   const float *omega, *qbar, *kv, *dkv, *uq;

@@ -51,9 +51,9 @@ EA_DEV void lara_x_body(const LaraP p, const LaraXpP xp) {
   EA_BLK(p, 0);
   constexpr bool KEYS = MODE == LX_BWDK || MODE == LX_PBWDK;
   constexpr bool TWO_TOK = MODE == LX_BWDQ || MODE == LX_BWDK || MODE == LX_PBWDQ || MODE == LX_PBWDK;
-  const T4l& tk1 = KEYS ? p.k : p.q;
+  const T4& tk1 = KEYS ? p.k : p.q;
   const char* t1b = tk1.p + (b * tk1.sb + h * tk1.sh) * 2;
-  const T4l& tk2 = KEYS ? p.v : p.dout;
+  const T4& tk2 = KEYS ? p.v : p.dout;
   const char* t2b = tk2.p ? tk2.p + (b * tk2.sb + h * tk2.sh) * 2 : nullptr;
   const float invC = 1.f / (float)p.C;
   const int n0 = blk * p.tok_per_block;

@@ -119,8 +119,8 @@ __global__ __launch_bounds__(256, 2) void lara_y_kernel(const LaraP p) {
 
   auto run_phase = [&](auto keys_tag, int phase) {
     constexpr bool keys = decltype(keys_tag)::value;
-    const T4l& a1 = keys ? p.k : p.q;
-    const T4l& a2 = keys ? p.v : p.dout;
+    const T4& a1 = keys ? p.k : p.q;
+    const T4& a2 = keys ? p.v : p.dout;
     constexpr bool need2 = MODE == LY_FWD ? keys : MODE != LY_PMAX;
     const char* a1b = a1.p + (b * a1.sb + h * a1.sh) * 2;
     const char* a2b = need2 ? a2.p + (b * a2.sb + h * a2.sh) * 2 : nullptr;

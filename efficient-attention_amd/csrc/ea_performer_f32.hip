@@ -17,90 +17,20 @@
 // odd row stride (conflict-free for both operand orientations).  Sequence-wide sums (KV, ksum, their gradients) leave as
 // per-slice partials, added by ea_slice_sum.  Simple on purpose: this is the faithful path, the 16-bit kernels stay the
 // fast one (EA_PERFORMER_16BIT=1).
+// The tile layer (constants, tile / matrix moves, row reductions, slice plan) is ea_f32_tile.h, shared with ea_kernelized.hip.
 #include "ea_common.h"
 #include "ea_performer_f32.h"
 #include "ea_f32_mm.h"
+#include "ea_f32_tile.h"
 
 namespace ea {
 
+using namespace f32tile;
+
 namespace {
 
-constexpr int TB = 64;            // tokens per tile
-constexpr int PD = 64;            // head dim
-constexpr int LDD = PD + 1;       // row stride of the [*][64] images
-constexpr int NTH = 512;          // threads per workgroup: 8 waves, two per SIMD (the LDS images allow one workgroup per CU)
-constexpr int NWV = NTH / 64;     // waves
-constexpr int LPR = NTH / TB;     // lanes per token row in the elementwise stages (8)
-
-// rows n0 .. n0 + 63 of a [B,H,N,64] view -> dst[row][65] fp32 (rows >= N: zeros); thread = (row, 8 channels)
-EA_DEV void load_tile(float* dst, const Pf32T& t, int b, int h, int n0, int N, int dtype, int tid) {
-  const int row = tid / LPR, c0 = (tid % LPR) * 8;
-  float f[8];
-#pragma unroll
-  for (int i = 0; i < 8; ++i) f[i] = 0.f;
-  if (n0 + row < N) {
-    const size_t eo = (size_t)b * t.sb + (size_t)h * t.sh + (size_t)(n0 + row) * t.sn + c0;
-    if (dtype == 2) {
-      const float* s = reinterpret_cast<const float*>(t.p) + eo;
-      const f32x4 v0 = *reinterpret_cast<const f32x4*>(s), v1 = *reinterpret_cast<const f32x4*>(s + 4);
-      f[0] = v0[0]; f[1] = v0[1]; f[2] = v0[2]; f[3] = v0[3]; f[4] = v1[0]; f[5] = v1[1]; f[6] = v1[2]; f[7] = v1[3];
-    } else {
-      const u32x4 w0 = ldg16(t.p + eo * 2);
-      if (dtype == 0) unpack8<BF16>(w0, f);
-      else unpack8<F16>(w0, f);
-    }
-  }
-#pragma unroll
-  for (int i = 0; i < 8; ++i) dst[row * LDD + c0 + i] = f[i];
-}
-
-// src[row][65] fp32 -> rows n0 .. of a [B,H,N,64] view in its I/O type (rows >= N dropped)
-EA_DEV void store_tile(const float* src, const Pf32T& t, int b, int h, int n0, int N, int dtype, int tid) {
-  const int row = tid / LPR, c0 = (tid % LPR) * 8;
-  if (n0 + row >= N) return;
-  float f[8];
-#pragma unroll
-  for (int i = 0; i < 8; ++i) f[i] = src[row * LDD + c0 + i];
-  const size_t eo = (size_t)b * t.sb + (size_t)h * t.sh + (size_t)(n0 + row) * t.sn + c0;
-  if (dtype == 2) {
-    float* d = reinterpret_cast<float*>(t.p) + eo;
-    *reinterpret_cast<f32x4*>(d) = f32x4{f[0], f[1], f[2], f[3]};
-    *reinterpret_cast<f32x4*>(d + 4) = f32x4{f[4], f[5], f[6], f[7]};
-  } else {
-    char* d = t.p + eo * 2;
-    if (dtype == 0) stg16(d, pack8<BF16>(f));
-    else stg16(d, pack8<F16>(f));
-  }
-}
-
-// [rows][64] fp32 global matrix -> dst[rows][65]
-EA_DEV void load_mat(float* dst, const float* src, int rows, int tid) {
-  for (int idx = tid; idx < rows * (PD / 4); idx += NTH) {
-    const int r = idx / (PD / 4), c = (idx - r * (PD / 4)) * 4;
-    const f32x4 v = *reinterpret_cast<const f32x4*>(src + (size_t)r * PD + c);
-    float* d = dst + r * LDD + c;
-    d[0] = v[0]; d[1] = v[1]; d[2] = v[2]; d[3] = v[3];
-  }
-}
-
-// sum over the LPR lanes that share a row (row = tid / LPR); lane q4 of a row walks the CONTIGUOUS part q4 of it, which with
-// the odd row stride keeps the 64 lanes of a wave on distinct LDS banks
-EA_DEV float row4_sum(float v) { v += __shfl_xor(v, 1); v += __shfl_xor(v, 2); v += __shfl_xor(v, 4); return v; }
-EA_DEV float row4_max(float v) { v = fmaxf(v, __shfl_xor(v, 1)); v = fmaxf(v, __shfl_xor(v, 2)); v = fmaxf(v, __shfl_xor(v, 4)); return v; }
-
-struct Consts {
-  float c, c2, ratio;
-};
-EA_DEV Consts consts(int M) {
-  Consts k;
-  k.c = 0.35355339059327373f;            // 64^-1/4
-  k.c2 = 0.0625f;                        // 64^-1/2 / 2
-  k.ratio = rsqrtf((float)M);
-  return k;
-}
-
 // Ps[n][j] = c W_j . x_n (the reference's data_dash) for the tile in Xs; diag[n] = c2 |x_n|^2
-EA_DEV void logits(float* Ps, int ldp, const float* Xs, const float* Ws, float* diag, int M, float c, float c2, int tid) {
+EA_DEV void logits(float* Ps, int ldp, const float* Xs, const float* Ws, float* diag, int M, int tid) {
   const int lane = tid & 63, wave = tid >> 6, g = lane >> 4, li = lane & 15;
   const int ntn = M / 16;
   for (int t = wave; t < (TB / 16) * ntn; t += NWV) {
@@ -108,19 +38,13 @@ EA_DEV void logits(float* Ps, int ldp, const float* Xs, const float* Ws, float* 
     f32x4 acc = {0.f, 0.f, 0.f, 0.f};
     tile_mm<false, true, PD>(acc, Xs, LDD, Ws, LDD, m0, n0, PD, lane);
 #pragma unroll
-    for (int r = 0; r < 4; ++r) Ps[(m0 + 4 * g + r) * ldp + n0 + li] = acc[r] * c;
+    for (int r = 0; r < 4; ++r) Ps[(m0 + 4 * g + r) * ldp + n0 + li] = acc[r] * KC;
   }
   const int row = tid / LPR, q4 = tid % LPR;
   float s = 0.f;
   for (int e = q4 * (PD / LPR); e < (q4 + 1) * (PD / LPR); ++e) { const float x = Xs[row * LDD + e]; s += x * x; }
-  s = row4_sum(s);
-  if (q4 == 0) diag[row] = s * c2;
-}
-
-// the token range of this workgroup
-EA_DEV void slice_range(const Pf32P& p, int s, int& n0, int& n1) {
-  n0 = s * p.tps;
-  n1 = min(p.N, n0 + p.tps);
+  s = row8_sum(s);
+  if (q4 == 0) diag[row] = s * KC2;
 }
 
 }  // namespace
@@ -138,7 +62,6 @@ __global__ __launch_bounds__(NTH) void pf32_kmax_kernel(const Pf32P p) {
   float* red = diag + TB;
   const int tid = threadIdx.x;
   const int bh = blockIdx.x, s = blockIdx.y, b = bh / p.H, h = bh - b * p.H;
-  const Consts k = consts(M);
   load_mat(Ws, p.W + (size_t)h * M * PD, M, tid);
   int n0, n1;
   slice_range(p, s, n0, n1);
@@ -147,7 +70,7 @@ __global__ __launch_bounds__(NTH) void pf32_kmax_kernel(const Pf32P p) {
     __syncthreads();
     load_tile(Xs, p.k, b, h, t0, p.N, p.dtype, tid);
     __syncthreads();
-    logits(Ps, ldp, Xs, Ws, diag, M, k.c, k.c2, tid);
+    logits(Ps, ldp, Xs, Ws, diag, M, tid);
     __syncthreads();
     {
       const int row = tid / LPR, q4 = tid % LPR;                         // (no index divisions: four lanes per token row)
@@ -194,7 +117,7 @@ __global__ __launch_bounds__(NTH) void pf32_kv_kernel(const Pf32P p) {
   float* diag = Ps + TB * ldp;
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, g = lane >> 4, li = lane & 15;
   const int bh = blockIdx.x, s = blockIdx.y, b = bh / p.H, h = bh - b * p.H;
-  const Consts k = consts(M);
+  const float ratio = rsqrtf((float)M);
   load_mat(Ws, p.W + (size_t)h * M * PD, M, tid);
   const float stab = key_stab(p, bh);
   int n0, n1;
@@ -209,9 +132,9 @@ __global__ __launch_bounds__(NTH) void pf32_kv_kernel(const Pf32P p) {
     load_tile(Xs, p.k, b, h, t0, p.N, p.dtype, tid);
     load_tile(Ys, p.v, b, h, t0, p.N, p.dtype, tid);
     __syncthreads();
-    logits(Ps, ldp, Xs, Ws, diag, M, k.c, k.c2, tid);
+    logits(Ps, ldp, Xs, Ws, diag, M, tid);
     __syncthreads();
-    key_features(Ps, ldp, diag, p, b, t0, n1, stab, k.ratio, tid);
+    key_features(Ps, ldp, diag, p, b, t0, n1, stab, ratio, tid);
     __syncthreads();
 #pragma unroll
     for (int i = 0; i < 3; ++i) {
@@ -242,7 +165,7 @@ EA_DEV void query_features(float* Ps, int ldp, const float* diag, float* den, co
   const int row = tid / LPR, q4 = tid % LPR;
   float mx = -INFINITY;
   for (int j = q4 * (M / LPR), je = j + (M / LPR); j < je; ++j) mx = fmaxf(mx, Ps[row * ldp + j]);
-  mx = row4_max(mx);
+  mx = row8_max(mx);
   const float sh = diag[row] + mx;
   float dn = 0.f;
   for (int j = q4 * (M / LPR), je = j + (M / LPR); j < je; ++j) {
@@ -250,7 +173,7 @@ EA_DEV void query_features(float* Ps, int ldp, const float* diag, float* den, co
     Ps[row * ldp + j] = f;
     dn += f * ksum_s[j];
   }
-  dn = row4_sum(dn);
+  dn = row8_sum(dn);
   if (q4 == 0) den[row] = dn;
 }
 
@@ -282,7 +205,7 @@ __global__ __launch_bounds__(NTH) void pf32_out_kernel(const Pf32P p) {
   float* ksum_s = den + TB;
   const int tid = threadIdx.x;
   const int bh = blockIdx.x, s = blockIdx.y, b = bh / p.H, h = bh - b * p.H;
-  const Consts k = consts(M);
+  const float ratio = rsqrtf((float)M);
   load_mat(Ws, p.W + (size_t)h * M * PD, M, tid);
   load_mat(KVs, p.kv + (size_t)bh * M * PD, M, tid);
   if (tid < M) ksum_s[tid] = p.ksum[(size_t)bh * M + tid];
@@ -292,9 +215,9 @@ __global__ __launch_bounds__(NTH) void pf32_out_kernel(const Pf32P p) {
     __syncthreads();
     load_tile(Xs, p.q, b, h, t0, p.N, p.dtype, tid);
     __syncthreads();
-    logits(Ps, ldp, Xs, Ws, diag, M, k.c, k.c2, tid);
+    logits(Ps, ldp, Xs, Ws, diag, M, tid);
     __syncthreads();
-    query_features(Ps, ldp, diag, den, ksum_s, M, k.ratio, tid);
+    query_features(Ps, ldp, diag, den, ksum_s, M, ratio, tid);
     __syncthreads();
     feat_times(Os, Ps, ldp, KVs, M, tid, [&](int n) { return 1.f / fmaxf(den[n], 1e-2f); });
     __syncthreads();
@@ -303,8 +226,7 @@ __global__ __launch_bounds__(NTH) void pf32_out_kernel(const Pf32P p) {
 }
 
 // dX[n][e] = c sum_j Gs[n][j] Ws[j][e] - 2 c2 sdl[n] Xs[n][e]  -> Os   (gradient through the logits and the -|x|^2 term)
-EA_DEV void logit_grad(float* Os, const float* Gs, int ldp, const float* Ws, const float* Xs, const float* sdl, int M, float c,
-                       float c2, int tid) {
+EA_DEV void logit_grad(float* Os, const float* Gs, int ldp, const float* Ws, const float* Xs, const float* sdl, int M, int tid) {
   const int lane = tid & 63, wave = tid >> 6, g = lane >> 4, li = lane & 15;
   for (int t = wave; t < 16; t += NWV) {
     const int m0 = (t >> 2) * 16, n0 = (t & 3) * 16;
@@ -314,7 +236,7 @@ EA_DEV void logit_grad(float* Os, const float* Gs, int ldp, const float* Ws, con
 #pragma unroll
     for (int r = 0; r < 4; ++r) {
       const int n = m0 + 4 * g + r, e = n0 + li;
-      Os[n * LDD + e] = c * acc[r] - 2.f * c2 * sdl[n] * Xs[n * LDD + e];
+      Os[n * LDD + e] = KC * acc[r] - 2.f * KC2 * sdl[n] * Xs[n * LDD + e];
     }
   }
 }
@@ -336,7 +258,7 @@ __global__ __launch_bounds__(NTH) void pf32_bwd_q_kernel(const Pf32P p) {
   float* ksum_s = sdl + TB;
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, g = lane >> 4, li = lane & 15;
   const int bh = blockIdx.x, s = blockIdx.y, b = bh / p.H, h = bh - b * p.H;
-  const Consts k = consts(M);
+  const float ratio = rsqrtf((float)M);
   load_mat(Ws, p.W + (size_t)h * M * PD, M, tid);
   load_mat(KVs, p.kv + (size_t)bh * M * PD, M, tid);
   if (tid < M) ksum_s[tid] = p.ksum[(size_t)bh * M + tid];
@@ -353,9 +275,9 @@ __global__ __launch_bounds__(NTH) void pf32_bwd_q_kernel(const Pf32P p) {
     load_tile(Xs, p.q, b, h, t0, p.N, p.dtype, tid);
     load_tile(Ys, p.dout, b, h, t0, n1, p.dtype, tid);          // rows beyond the slice: zero cotangent
     __syncthreads();
-    logits(Ps, ldp, Xs, Ws, diag, M, k.c, k.c2, tid);
+    logits(Ps, ldp, Xs, Ws, diag, M, tid);
     __syncthreads();
-    query_features(Ps, ldp, diag, den, ksum_s, M, k.ratio, tid);
+    query_features(Ps, ldp, diag, den, ksum_s, M, ratio, tid);
     __syncthreads();
     float* Os = Gs;
     feat_times(Os, Ps, ldp, KVs, M, tid, [&](int n) { return 1.f / fmaxf(den[n], 1e-2f); });     // out
@@ -365,7 +287,7 @@ __global__ __launch_bounds__(NTH) void pf32_bwd_q_kernel(const Pf32P p) {
       const float inv = 1.f / fmaxf(den[row], 1e-2f);
       float rd = 0.f;
       for (int e = q4 * (PD / LPR); e < (q4 + 1) * (PD / LPR); ++e) rd += Ys[row * LDD + e] * Os[row * LDD + e];
-      rd = row4_sum(rd);
+      rd = row8_sum(rd);
       for (int e = q4 * (PD / LPR); e < (q4 + 1) * (PD / LPR); ++e) Ys[row * LDD + e] *= inv;
       if (q4 == 0) dden[row] = den[row] > 1e-2f ? -rd * inv : 0.f;
     }
@@ -385,7 +307,7 @@ __global__ __launch_bounds__(NTH) void pf32_bwd_q_kernel(const Pf32P p) {
     {
       float sacc = 0.f;
       for (int j = q4 * (M / LPR), je = j + (M / LPR); j < je; ++j) sacc += Gs[row * ldp + j];
-      sacc = row4_sum(sacc);
+      sacc = row8_sum(sacc);
       if (q4 == 0) sdl[row] = sacc;
     }
     // partial d KV[j][e] += sum_n phi[n][j] d num[n][e];  d ksum[j] += sum_n phi[n][j] d den[n]
@@ -400,7 +322,7 @@ __global__ __launch_bounds__(NTH) void pf32_bwd_q_kernel(const Pf32P p) {
       dks += a;
     }
     __syncthreads();
-    logit_grad(Ys, Gs, ldp, Ws, Xs, sdl, M, k.c, k.c2, tid);      // dq tile (d num is dead)
+    logit_grad(Ys, Gs, ldp, Ws, Xs, sdl, M, tid);      // dq tile (d num is dead)
     __syncthreads();
     store_tile(Ys, p.dq, b, h, t0, n1, p.dtype, tid);
   }
@@ -432,7 +354,7 @@ __global__ __launch_bounds__(NTH) void pf32_bwd_k_kernel(const Pf32P p) {
   float* dks_s = sdl + TB;
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, g = lane >> 4, li = lane & 15;
   const int bh = blockIdx.x, s = blockIdx.y, b = bh / p.H, h = bh - b * p.H;
-  const Consts k = consts(M);
+  const float ratio = rsqrtf((float)M);
   load_mat(Ws, p.W + (size_t)h * M * PD, M, tid);
   load_mat(KVs, p.dkv + (size_t)bh * M * PD, M, tid);
   if (tid < M) dks_s[tid] = p.dksum[(size_t)bh * M + tid];
@@ -446,9 +368,9 @@ __global__ __launch_bounds__(NTH) void pf32_bwd_k_kernel(const Pf32P p) {
     load_tile(Xs, p.k, b, h, t0, p.N, p.dtype, tid);
     load_tile(Ys, p.v, b, h, t0, p.N, p.dtype, tid);
     __syncthreads();
-    logits(Ps, ldp, Xs, Ws, diag, M, k.c, k.c2, tid);
+    logits(Ps, ldp, Xs, Ws, diag, M, tid);
     __syncthreads();
-    key_features(Ps, ldp, diag, p, b, t0, n1, stab, k.ratio, tid);
+    key_features(Ps, ldp, diag, p, b, t0, n1, stab, ratio, tid);
     __syncthreads();
     // d phi[n][j] = v[n] . dKV[j] + d ksum[j];  d logit = d phi (phi - eps), 0 where phi was masked to 0
     for (int t = wave; t < (TB / 16) * nt; t += NWV) {
@@ -466,7 +388,7 @@ __global__ __launch_bounds__(NTH) void pf32_bwd_k_kernel(const Pf32P p) {
     {
       float sacc = 0.f;
       for (int j = q4 * (M / LPR), je = j + (M / LPR); j < je; ++j) sacc += Gs[row * ldp + j];
-      sacc = row4_sum(sacc);
+      sacc = row8_sum(sacc);
       if (q4 == 0) sdl[row] = sacc;
     }
     // dv[n] = sum_j phi[n][j] dKV[j]   (v is dead: its tile takes dv)
@@ -474,22 +396,13 @@ __global__ __launch_bounds__(NTH) void pf32_bwd_k_kernel(const Pf32P p) {
     __syncthreads();
     store_tile(Ys, p.dv, b, h, t0, n1, p.dtype, tid);
     __syncthreads();
-    logit_grad(Ys, Gs, ldp, Ws, Xs, sdl, M, k.c, k.c2, tid);
+    logit_grad(Ys, Gs, ldp, Ws, Xs, sdl, M, tid);
     __syncthreads();
     store_tile(Ys, p.dk, b, h, t0, n1, p.dtype, tid);
   }
 }
 
 // ------------------------------------------------------------------------------------------------------------
-int pf32_slices(int BH, int N) {
-  const int tiles = (N + TB - 1) / TB;
-  int S = (1024 + BH - 1) / BH;
-  if (S > tiles) S = tiles;
-  if (S < 1) S = 1;
-  if (S > 64) S = 64;
-  return S;
-}
-
 static size_t pf32_lds(int which, int M) {
   const size_t ldp = M + 1, big = ldp > LDD ? ldp : LDD;
   switch (which) {
@@ -503,10 +416,10 @@ static size_t pf32_lds(int which, int M) {
 
 int pf32_dispatch(int which, const Pf32P& p0, hipStream_t st) {
   Pf32P p = p0;
-  if (p.M <= 0 || p.M > 96 || (p.M & 15) || p.dtype < 0 || p.dtype > 2) return EA_E_UNSUPPORTED;
-  p.S = pf32_slices(p.B * p.H, p.N);
-  const int tiles = (p.N + TB - 1) / TB;
-  p.tps = ((tiles + p.S - 1) / p.S) * TB;
+  if (p.M <= 0 || p.M > PF32_MAX_M || (p.M & 15) || p.dtype < 0 || p.dtype > 2) return EA_E_UNSUPPORTED;
+  const Slices sl = plan_slices(p.B * p.H, p.N);
+  p.S = sl.S;
+  p.tps = sl.tps;
   const dim3 grid((unsigned)(p.B * p.H), (unsigned)p.S), block(NTH);
   const size_t lds = pf32_lds(which, p.M);
   switch (which) {

@@ -1,16 +1,12 @@
 // ea_scatter.h -- parameter block of the ScatterBrain feature-half kernels (ea_scatter.hip).
 #pragma once
 #include "ea_common.h"
+#include "ea_t4.h"
 
 namespace ea {
 
-struct T4s {
-  char* p;
-  int64_t sb, sh, sn;
-};
-
 struct SbP {
-  T4s q, k, v, oloc, out, dout, doloc, dq, dk, dv;
+  T4 q, k, v, oloc, out, dout, doloc, dq, dk, dv;
   const uint8_t* mask;          // [B,N] key padding mask or null
   const float* Wf;              // [H, M, 64] random features
   const float *mx, *zall, *sall;   // sequence-wide statistics: [BH,M], [BH,M], [BH,M,64]

@@ -28,7 +28,7 @@ constexpr int TB = 64 * 128;      // bytes of a [64][64] 16-bit tile
 // every global load of a phase is in flight before the first use: the loads are unconditional (slots beyond
 // the window are clamped and zeroed at commit -- a predicated load is a branch plus a full round trip each).
 struct RowRegs { u32x4 v[2]; };
-EA_DEV void issue_window(RowRegs& rr, const T4s& t, int b, int h, const Geo& G, int win, int w, int Wq, int tid) {
+EA_DEV void issue_window(RowRegs& rr, const T4& t, int b, int h, const Geo& G, int win, int w, int Wq, int tid) {
   const char* base = t.p + (b * t.sb + h * t.sh) * 2;
 #pragma unroll
   for (int k = 0; k < 2; ++k) {

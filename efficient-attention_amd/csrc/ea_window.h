@@ -3,6 +3,7 @@
 #pragma once
 #include <stdlib.h>
 #include "ea_common.h"
+#include "ea_t4.h"
 
 namespace ea {
 
@@ -266,17 +267,6 @@ template <int a, int b, int c, int d, bool ho = false, bool pw = false> struct S
   static constexpr int NQT = a, NLT = b, NCT = c, WPI = d;
   static constexpr bool HO = ho, PW = pw;
 };
-
-struct T4 {
-  char* p;
-  int64_t sb, sh, sn;
-};
-inline T4 mk(const ea_t4* t) {
-  T4 r;
-  r.p = t ? (char*)t->ptr : nullptr;
-  r.sb = t ? t->sb : 0; r.sh = t ? t->sh : 0; r.sn = t ? t->sn : 0;
-  return r;
-}
 
 struct WinP {
   T4 q, k, v, o;            // o = out (fwd) / dout (bwd)

@@ -8,12 +8,11 @@ precision, kernelized_attention.py:345): bf16 / fp16 qkv under autocast, fp32 ou
 
 A configuration is `cfg = (map id, m, nu, cos)`; W is the [h, m, 64] fp32 feature matrix of the maps that have one, else
 None.  With `learn`, W receives its gradient (sample_scheme='learnable')."""
-import ctypes
-
 import torch
 
+from . import _feature_cores as _fc
 from . import _native as nv
-from ._ops import _ea_op, _qkv_views, _IO32
+from ._ops import _ea_op, _IO32
 
 MAPS = {"favorp": 0, "relu": 1, "fourier": 2, "relu-only": 3, "sigmoid-only": 4, "dpfp": 5}
 W_MAPS = ("favorp", "relu", "fourier")
@@ -58,78 +57,26 @@ def _parts(geom):
     return nv.query("ea_kernelized_parts", geom)
 
 
+_FAMILY = _fc.Family("ea_kernelized_", "stats", stats_take_q=True, q_side_stat=True, has_dw=True)
+
+
 def kernelized_fwd_impl(qkv5, mask_u8, W, cfg):
     """torch.ops.ea.kernelized_fwd -> [out [B,N,h,d], p_st [BH,S,2] (empty for the maps without statistics), kv [BH,F,d],
     ksum [BH,F]]."""
     nv.require_cuda(qkv5, "qkv")
     cfg = tuple(int(c) for c in cfg)
-    B, N, _, h, d = qkv5.shape
-    BH, dev = B * h, qkv5.device
-    F = _features(cfg)
-    if W is not None:
-        W = W.float().contiguous()
     geom = _geom(qkv5, cfg)
-    S = _parts(geom)
-    q, k, v = _qkv_views(qkv5)
-    tq, tk, tv = nv.t4(q), nv.t4(k), nv.t4(v)
-    gp = ctypes.byref(geom)
-    if cfg[0] in STAT_MAPS:
-        p_st = torch.empty((BH, S, 2), dtype=torch.float32, device=dev)
-        nv.call("ea_kernelized_stats", gp, ctypes.byref(tq), ctypes.byref(tk), nv.ptr(W), nv.ptr(p_st), nv.stream())
-    else:
-        p_st = torch.empty((0,), dtype=torch.float32, device=dev)
-    st = nv.ptr(p_st) if p_st.numel() else None
-    p_kv = torch.empty((BH, S, F, d), dtype=torch.float32, device=dev)
-    p_ks = torch.empty((BH, S, F), dtype=torch.float32, device=dev)
-    nv.call("ea_kernelized_kv", gp, ctypes.byref(tk), ctypes.byref(tv), nv.ptr(mask_u8), nv.ptr(W), st, nv.ptr(p_kv),
-            nv.ptr(p_ks), nv.stream())
-    kv = torch.empty((BH, F, d), dtype=torch.float32, device=dev)
-    ksum = torch.empty((BH, F), dtype=torch.float32, device=dev)
-    nv.call("ea_slice_sum", BH, S, F * d, 1.0, None, nv.ptr(p_kv), nv.ptr(kv), nv.stream())
-    nv.call("ea_slice_sum", BH, S, F, 1.0, None, nv.ptr(p_ks), nv.ptr(ksum), nv.stream())
-    out = torch.empty((B, N, h, d), dtype=qkv5.dtype, device=dev)
-    to = nv.t4(out.permute(0, 2, 1, 3))
-    nv.call("ea_kernelized_out", gp, ctypes.byref(tq), nv.ptr(W), st, nv.ptr(kv), nv.ptr(ksum), ctypes.byref(to),
-            nv.stream())
-    return [out, p_st, kv, ksum]
+    return list(_fc.forward(_FAMILY, geom, _parts(geom), _features(cfg), qkv5, mask_u8, W,
+                            (2,) if cfg[0] in STAT_MAPS else None))
 
 
 def kernelized_bwd_impl(dout, qkv5, mask_u8, W, p_st, kv, ksum, cfg, need_dw):
     """torch.ops.ea.kernelized_bwd -> [dqkv [B,N,3,h,d], dW [h,m,d] fp32 (need_dw) or empty]."""
     cfg = tuple(int(c) for c in cfg)
-    B, N, _, h, d = qkv5.shape
-    BH, dev = B * h, qkv5.device
-    F = _features(cfg)
-    m = cfg[1]
-    if W is not None:
-        W = W.float().contiguous()
     geom = _geom(qkv5, cfg)
-    gp = ctypes.byref(geom)
-    S = _parts(geom)
-    dout = dout.to(qkv5.dtype).contiguous()
-    dqkv5 = torch.empty_like(qkv5)
-    q, k, v = _qkv_views(qkv5)
-    dq, dk, dv = _qkv_views(dqkv5)
-    tq, tk, tv, tdo = nv.t4(q), nv.t4(k), nv.t4(v), nv.t4(dout.permute(0, 2, 1, 3))
-    tdq, tdk, tdv = nv.t4(dq), nv.t4(dk), nv.t4(dv)
-    st = nv.ptr(p_st) if p_st.numel() else None
-    p_dw = torch.empty((h, B, 2, S, m, d), dtype=torch.float32, device=dev) if need_dw else None
-    p_dkv = torch.empty((BH, S, F, d), dtype=torch.float32, device=dev)
-    p_dks = torch.empty((BH, S, F), dtype=torch.float32, device=dev)
-    nv.call("ea_kernelized_bwd_q", gp, ctypes.byref(tq), ctypes.byref(tdo), nv.ptr(W), st, nv.ptr(kv), nv.ptr(ksum),
-            ctypes.byref(tdq), nv.ptr(p_dkv), nv.ptr(p_dks), nv.ptr(p_dw), nv.stream())
-    dkv = torch.empty((BH, F, d), dtype=torch.float32, device=dev)
-    dksum = torch.empty((BH, F), dtype=torch.float32, device=dev)
-    nv.call("ea_slice_sum", BH, S, F * d, 1.0, None, nv.ptr(p_dkv), nv.ptr(dkv), nv.stream())
-    nv.call("ea_slice_sum", BH, S, F, 1.0, None, nv.ptr(p_dks), nv.ptr(dksum), nv.stream())
-    nv.call("ea_kernelized_bwd_k", gp, ctypes.byref(tk), ctypes.byref(tv), nv.ptr(mask_u8), nv.ptr(W), st, nv.ptr(dkv),
-            nv.ptr(dksum), ctypes.byref(tdk), ctypes.byref(tdv), nv.ptr(p_dw), nv.stream())
-    if need_dw:
-        dW = torch.empty((h, m, d), dtype=torch.float32, device=dev)
-        nv.call("ea_slice_sum", h, B * 2 * S, m * d, 1.0, None, nv.ptr(p_dw), nv.ptr(dW), nv.stream())
-    else:
-        dW = torch.empty((0,), dtype=torch.float32, device=dev)
-    return [dqkv5, dW]
+    dqkv5, dW = _fc.backward(_FAMILY, geom, _parts(geom), _features(cfg), dout, qkv5, mask_u8, W,
+                             p_st, kv, ksum, need_dw)
+    return [dqkv5, dW if need_dw else torch.empty((0,), dtype=torch.float32, device=qkv5.device)]
 
 
 def supported(qkv5):

@@ -16,6 +16,7 @@ import warnings
 import torch
 import torch.nn.functional as F
 
+from . import _feature_cores as _fc
 from . import _native as nv
 
 KERNEL_TIMER = nv.KERNEL_TIMER
@@ -2671,60 +2672,27 @@ def performer_f32_supported(qkv5, W):
     return qkv5.is_cuda and qkv5.dtype in _IO32 and qkv5.shape[-1] == 64 and W.shape[1] <= 96 and W.shape[1] % 16 == 0
 
 
+_PERFORMER_F32 = _fc.Family("ea_performer_f32_", "kmax", stats_take_q=False, q_side_stat=False, has_dw=False)
+
+
+def _performer_f32_geom(qkv5, W):
+    B, N, _, h, d = qkv5.shape
+    return nv.ea_perf_geom(B, h, N, d, _IO32[qkv5.dtype], W.shape[1])
+
+
 def performer_f32_fwd(qkv5, mask_u8, W):
     """-> out [B,N,h,d] (dtype of qkv5), p_max [BH,S], kv [BH,m,d], ksum [BH,m]."""
     nv.require_cuda(qkv5, "qkv")
-    B, N, _, h, d = qkv5.shape
-    m = W.shape[1]
-    BH, dev = B * h, qkv5.device
-    W = W.float().contiguous()
-    geom = nv.ea_perf_geom(B, h, N, d, _IO32[qkv5.dtype], m)
-    q, k, v = _qkv_views(qkv5)
-    tq, tk, tv = nv.t4(q), nv.t4(k), nv.t4(v)
+    geom = _performer_f32_geom(qkv5, W)
     S = nv.lib().ea_performer_f32_parts(ctypes.byref(geom))
     if S <= 0:
         raise RuntimeError("ea_performer_f32_parts: %d" % S)
-    p_max = torch.empty((BH, S), dtype=torch.float32, device=dev)
-    nv.call("ea_performer_f32_kmax", ctypes.byref(geom), ctypes.byref(tk), nv.ptr(W), nv.ptr(p_max), nv.stream())
-    p_kv = torch.empty((BH, S, m, d), dtype=torch.float32, device=dev)
-    p_ks = torch.empty((BH, S, m), dtype=torch.float32, device=dev)
-    nv.call("ea_performer_f32_kv", ctypes.byref(geom), ctypes.byref(tk), ctypes.byref(tv), nv.ptr(mask_u8), nv.ptr(W),
-            nv.ptr(p_max), nv.ptr(p_kv), nv.ptr(p_ks), nv.stream())
-    kv = torch.empty((BH, m, d), dtype=torch.float32, device=dev)
-    ksum = torch.empty((BH, m), dtype=torch.float32, device=dev)
-    nv.call("ea_slice_sum", BH, S, m * d, 1.0, None, nv.ptr(p_kv), nv.ptr(kv), nv.stream())
-    nv.call("ea_slice_sum", BH, S, m, 1.0, None, nv.ptr(p_ks), nv.ptr(ksum), nv.stream())
-    out = torch.empty((B, N, h, d), dtype=qkv5.dtype, device=dev)
-    to = nv.t4(out.permute(0, 2, 1, 3))
-    nv.call("ea_performer_f32_out", ctypes.byref(geom), ctypes.byref(tq), nv.ptr(W), nv.ptr(kv), nv.ptr(ksum),
-            ctypes.byref(to), nv.stream())
-    return out, p_max, kv, ksum
+    return _fc.forward(_PERFORMER_F32, geom, S, W.shape[1], qkv5, mask_u8, W, ())
 
 
 def performer_f32_bwd(dout, qkv5, mask_u8, W, p_max, kv, ksum):
-    B, N, _, h, d = qkv5.shape
-    m = W.shape[1]
-    BH, dev = B * h, qkv5.device
-    W = W.float().contiguous()
-    geom = nv.ea_perf_geom(B, h, N, d, _IO32[qkv5.dtype], m)
-    S = p_max.shape[1]
-    dout = dout.to(qkv5.dtype).contiguous()
-    dqkv5 = torch.empty_like(qkv5)
-    q, k, v = _qkv_views(qkv5)
-    dq, dk, dv = _qkv_views(dqkv5)
-    tq, tk, tv, tdo = nv.t4(q), nv.t4(k), nv.t4(v), nv.t4(dout.permute(0, 2, 1, 3))
-    tdq, tdk, tdv = nv.t4(dq), nv.t4(dk), nv.t4(dv)
-    p_dkv = torch.empty((BH, S, m, d), dtype=torch.float32, device=dev)
-    p_dks = torch.empty((BH, S, m), dtype=torch.float32, device=dev)
-    nv.call("ea_performer_f32_bwd_q", ctypes.byref(geom), ctypes.byref(tq), ctypes.byref(tdo), nv.ptr(W), nv.ptr(kv),
-            nv.ptr(ksum), ctypes.byref(tdq), nv.ptr(p_dkv), nv.ptr(p_dks), nv.stream())
-    dkv = torch.empty((BH, m, d), dtype=torch.float32, device=dev)
-    dksum = torch.empty((BH, m), dtype=torch.float32, device=dev)
-    nv.call("ea_slice_sum", BH, S, m * d, 1.0, None, nv.ptr(p_dkv), nv.ptr(dkv), nv.stream())
-    nv.call("ea_slice_sum", BH, S, m, 1.0, None, nv.ptr(p_dks), nv.ptr(dksum), nv.stream())
-    nv.call("ea_performer_f32_bwd_k", ctypes.byref(geom), ctypes.byref(tk), ctypes.byref(tv), nv.ptr(mask_u8), nv.ptr(W),
-            nv.ptr(p_max), nv.ptr(dkv), nv.ptr(dksum), ctypes.byref(tdk), ctypes.byref(tdv), nv.stream())
-    return dqkv5
+    return _fc.backward(_PERFORMER_F32, _performer_f32_geom(qkv5, W), p_max.shape[1], W.shape[1], dout, qkv5, mask_u8, W,
+                        p_max, kv, ksum)[0]
 
 
 class PerformerF32Fn(torch.autograd.Function):

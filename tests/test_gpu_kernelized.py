@@ -110,6 +110,32 @@ def test_favorp_entry_points_match_the_performer_kernels(m, mask, dtype):
         assert err <= rtol, (what, err)
 
 
+@pytest.mark.gpu
+@pytest.mark.parametrize("cfg", [(0, 16, 0, 0), (2, 16, 0, 0)], ids=["favorp", "fourier"])
+def test_fp32_views_with_4_element_strides_equal_contiguous_bitwise(cfg):
+    """The fp32 granule on the accepting side: an fp32 view needs strides that are multiples of 4 elements (16 bytes), not of
+    8.  qkv as the [..., :64] slice of a [1, 70, 3, 1, 68] buffer has a token stride of 204 floats and a head stride of 68 --
+    multiples of 4, not of 8 -- and 16-byte aligned bases.  Two 64-token tiles, the second ragged, its last 3 keys padded;
+    favorp and fourier between them run both statistics kernels.  The kernels are deterministic, use no atomics and plan
+    their grid from B, H, N alone, so out, kv, ksum and dqkv equal those of the same call on the contiguous copy bit for bit."""
+    from efficient_attention import _kernelized
+    g = torch.Generator(device="cuda").manual_seed(70 + cfg[0])
+    B, h, N, d, m = 1, 1, 70, 64, cfg[1]
+    qkv5 = (torch.randn(B, N, 3, h, d + 4, device="cuda", generator=g) * 0.7)[..., :d]
+    assert qkv5.stride(1) == 204 and qkv5.stride(3) == 68 and not qkv5.is_contiguous()
+    W = torch.randn(h, m, d, device="cuda", generator=g)
+    mask = torch.zeros(B, N, dtype=torch.uint8, device="cuda")
+    mask[0, N - 3:] = 1
+    dout = torch.randn(B, N, h, d, device="cuda", generator=g)
+    got = {}
+    for what, x in (("strided", qkv5), ("contiguous", qkv5.contiguous())):
+        out, p_st, kv, ksum = _kernelized.kernelized_fwd_impl(x, mask, W, cfg)
+        dqkv, _ = _kernelized.kernelized_bwd_impl(dout, x, mask, W, p_st, kv, ksum, cfg, False)
+        got[what] = dict(out=out, kv=kv, ksum=ksum, dqkv=dqkv)
+    for name, a in got["strided"].items():
+        assert torch.isfinite(a).all() and torch.equal(a, got["contiguous"][name]), name
+
+
 def _fullsize(proj_method, x_shape, heads, m, cos, scheme, mode):
     import efficient_attention as ea
     import kz_contract

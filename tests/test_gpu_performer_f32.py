@@ -65,6 +65,32 @@ def test_performer_f32_core_matches_fp64_oracle(B, h, N, m, io, masked):
         assert float((a - b).abs().max() / b.abs().max()) <= tol, (nm, float((a - b).abs().max() / b.abs().max()))
 
 
+@pytest.mark.gpu
+def test_performer_f32_fp32_views_with_4_element_strides_equal_contiguous_bitwise():
+    """The fp32 granule on the accepting side: an fp32 view needs strides that are multiples of 4 elements (16 bytes), not of
+    8.  qkv as the [..., :64] slice of a [1, 70, 3, 1, 68] buffer has a token stride of 204 floats and a head stride of 68 --
+    multiples of 4, not of 8 -- and 16-byte aligned bases.  Two 64-token tiles, the second ragged, its last 3 keys padded.
+    The kernels are deterministic, use no atomics and plan their grid from B, H, N alone, so out, kv, ksum and dqkv equal
+    those of the same call on the contiguous copy bit for bit."""
+    import torch
+    from efficient_attention import _ops
+    g = torch.Generator(device="cuda").manual_seed(70)
+    B, h, N, d, m = 1, 1, 70, 64, 16
+    qkv5 = (torch.randn(B, N, 3, h, d + 4, device="cuda", generator=g) * 0.7)[..., :d]
+    assert qkv5.stride(1) == 204 and qkv5.stride(3) == 68 and not qkv5.is_contiguous()
+    W = torch.randn(h, m, d, device="cuda", generator=g)
+    mask = torch.zeros(B, N, dtype=torch.uint8, device="cuda")
+    mask[0, N - 3:] = 1
+    dout = torch.randn(B, N, h, d, device="cuda", generator=g)
+    got = {}
+    for what, x in (("strided", qkv5), ("contiguous", qkv5.contiguous())):
+        out, p_max, kv, ksum = _ops.performer_f32_fwd(x, mask, W)
+        dqkv = _ops.performer_f32_bwd(dout, x, mask, W, p_max, kv, ksum)
+        got[what] = dict(out=out, kv=kv, ksum=ksum, dqkv=dqkv)
+    for name, a in got["strided"].items():
+        assert torch.isfinite(a).all() and torch.equal(a, got["contiguous"][name]), name
+
+
 @NEEDS_F32_DEFAULT
 @pytest.mark.gpu
 @pytest.mark.parametrize("name", PERFORMER_FIXTURES)
