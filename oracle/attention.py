@@ -259,7 +259,7 @@ def eva_core(q, k, v, mask, attn_2d, seq_shape, window_size, ext_size, num_landm
 # causal EVA (training / evaluation path, no incremental state)
 # --------------------------------------------------------------------------------------
 def causal_eva_core(q, k, v, mask, window_size, ext_size, chunk_size, mu_fn, noise=None,
-                    bias=None, causal=True, scale=None, drop_keep=None, p_drop=0.0):
+                    bias=None, causal=True, scale=None, drop_keep=None, p_drop=0.0, return_aux=False):
     """CausalEVAttention's q,k,v -> out core (causal_eva.py:666-783).
 
     q,k,v: [B,h,N,d] with N a multiple of the window (after _process_input); mask [B,N] bool or
@@ -315,7 +315,10 @@ def causal_eva_core(q, k, v, mask, window_size, ext_size, chunk_size, mu_fn, noi
         p = p * drop_keep.reshape(p.shape).to(p.dtype) / (1.0 - p_drop)
     out_w = torch.einsum("bhwij,bhwjd->bhwid", p[..., :Wk], wv) \
         + torch.einsum("bhwic,bhcd->bhwid", p[..., Wk:], beta)
-    return _scatter_windows(out_w, idx_q, n)
+    out = _scatter_windows(out_w, idx_q, n)
+    if return_aux:
+        return out, dict(beta=beta, rf_k_bar=rf_k_bar, omega=omega, mu=mu)
+    return out
 
 
 # --------------------------------------------------------------------------------------
