@@ -4,12 +4,6 @@
 #include <stdlib.h>
 #include <cmath>
 #include "ea_window.h"
-
-namespace ea {
-int window_fwd_dispatch(const WinP& p, int dtype, int D, hipStream_t st);
-int window_bwd_dispatch(const WinP& p, const ea_geom& geom, const T4& outp, const float* biasT, int dtype, int D,
-                        hipStream_t st);
-}  // namespace ea
 #include "ea_landmark_params.h"
 #include "ea_lara.h"
 #include "ea_softmax.h"
@@ -23,42 +17,10 @@ int window_bwd_dispatch(const WinP& p, const ea_geom& geom, const T4& outp, cons
 #include "ea_kernelized.h"
 #include "ea_f32_tile.h"
 #include "ea_f32_attn.h"
-namespace ea {
-int rows_mlp_dispatch(const RowsP& p, int D, int sides, int layer_norm, bool bwd, hipStream_t st);
-int rows_mlp_blocks(int R, int D);
-int lara_x_dispatch(int mode, const LaraP& p, int dtype, hipStream_t st);
-int lara_y_dispatch(int mode, const LaraP& p, int dtype, hipStream_t st);
-int lara_f_dispatch(int which, const LaraP& p, int dtype, hipStream_t st);
-bool lara_xp_supported(int H, int D, int C, int S);
-int lara_xp_dispatch(const LaraP& p, const LaraXpP& xp, int dtype, hipStream_t st);
-int pool2d_dispatch(bool bwd, int dtype, const void* x, long sb, long sh, long sn, float* mean, int B, int H, int gh, int gw,
-                    int side, int D, hipStream_t st);
-int linear_supported(int K, int NO);
-int proj_rs_supported(int K, int NO);
-int proj_rs_pool_supported(int K, int NO, int B, int gh, int gw, int r);
-int proj_rs_dispatch(int dtype, const void* a, int a_f32, const float* w, const float* bias, void* y, void* a_cast, int rows,
-                     long lda, long ldy, hipStream_t st, int B, int gh, int gw, int r, float* pq, float* pk, void* w_cast,
-                     const void* wsw);
-int w192_prepare_dispatch(int dtype, const float* wq, const float* wp, void* w16q, void* wsw, void* w16p, void* w16pT, void* wtsw,
-                          hipStream_t st);
-int dgrad_rs_supported(int K, int NO);
-int dgrad_fin_launch(int dtype, const void* dqkv, long ldy, const void* qkv, long ldq, const void* w, int w_f32, void* dx, int dx_f32,
-                     long ldx, int B, int gh, int gw, int pool_r, int C, float scale, const float* qbar, const float* uq,
-                     const float* lse_t, const float* dpq, const float* dpk, hipStream_t st);
-int dgrad_rs_dispatch(int dtype, const void* dy, const void* w, int w_f32, void* dx, int dx_f32, int rows, long ldy, long ldx,
-                      hipStream_t st);
-int linear_dispatch(int dtype, const void* a, int a_f32, const void* w, int w_mode, const float* bias, void* y, int y_f32,
-                    void* a_cast, int rows, int K, int NO, long lda, long ldy, hipStream_t st);
-int wgrad_slices(int rows, int M, int K);
-int wgrad_pair_slices(int rows, int M1, int K1, int M2, int K2);
-int wgrad_pair_dispatch(int dtype, int rows, const void* dy1, const void* x1, float* part1, float* db1, long ld1, int M1, int K1,
-                        const void* dy2, const void* x2, float* part2, float* db2, long ld2, int M2, int K2, hipStream_t st);
-int wgrad_dispatch(int dtype, const void* dy, const void* x, float* part, float* db_part, long part_ld, int rows, int M,
-                   int K, hipStream_t st);
-int part_sum_dispatch(const float* part, float* out, int S, int n, long ld, hipStream_t st);
-int multi_sum_dispatch(int K, const float* const* part, const int* S, const int* n, const long long* ld, float* const* out,
-                       hipStream_t st);
-}
+#include "ea_linear.h"
+#include "ea_proj.h"
+#include "ea_fold.h"
+#include "ea_lara_seglin.h"
 
 using namespace ea;
 
@@ -849,20 +811,6 @@ int ea_lara_merge_bwd(int32_t BH, int32_t S, int32_t C, int32_t D, int32_t has_t
 }  // extern "C"
 
 // ---- projection bias gradient ----
-namespace ea {
-int colsum_parts(int rows, int cols);
-int colsum_dispatch(int dtype, const void* x, float* part, float* out, int rows, int cols, hipStream_t st);
-int colsum_f32_dispatch(const float* x, float* out, int rows, int cols, const float* x2, float* out2, int cols2, hipStream_t st);
-int gather_sum_dispatch(const float* g, const int* inv, float* out, int rows, int K, int cols, hipStream_t st);
-int slice_sum_dispatch(const float* a, const float* p, float* out, int BH, int S, int n, float scale, hipStream_t st);
-int multi_cast_dispatch(int dtype, int K, const float* const* src, const long long* n, void* const* dst, hipStream_t st);
-int table_bias_fwd_dispatch(const float* table, const int* idx, float* out, int h, int th, int Wq, int Wk, int ld, float scale,
-                            hipStream_t st);
-int table_bias_bwd_dispatch(const float* g, const int* inv, float* dtable, int rows, int K, int h, int Wq, int Wk, int ld,
-                            float scale, hipStream_t st);
-int stream_copy_dispatch(const void* src, void* dst, size_t bytes, hipStream_t st);
-}  // namespace ea
-
 extern "C" {
 
 int ea_bias_grad_parts(int32_t rows, int32_t cols) { return ea::colsum_parts(rows, cols); }
@@ -963,28 +911,6 @@ int ea_lara_segment_bwd(const ea_geom* g, const ea_t4* q2, const ea_t4* k2, cons
 }  // extern "C"
 
 // ---- LARA 'adaptive-1d' with the generator Linear inside the segment kernels (ea_lara_seglin.hip) ----
-namespace ea {
-struct SegLinP {
-  char *q, *k;
-  int64_t q_sb, q_sh, q_sn, k_sb, k_sh, k_sn;
-  char *dq, *dk;
-  int64_t dq_sb, dq_sh, dq_sn, dk_sb, dk_sh, dk_sn;
-  const float *Gq, *Gk, *gqb, *gkb;
-  const float *lnq_w, *lnq_b, *lnk_w, *lnk_b;
-  float *qbar, *kbar;
-  const float *d_qbar, *d_kbar;
-  float* part;
-  void* stats;
-  float* dG_part;
-  int B, H, N, L, segs, nshort, groups, seg_per_group, cgroups, cseg_per_group;
-  const float *fin_qbar, *fin_uq, *fin_lse;
-  int C;
-  float fin_scale, fin_scale_log2;
-};
-int seglin_groups(int BH, int L);
-int seglin_dispatch(int which, const SegLinP& p, int dtype, hipStream_t st);
-}  // namespace ea
-
 static int fill_seglin(const ea_geom* g, ea::SegLinP& p) {
   SegP sp = {};
   const int rc = fill_seg(g, sp);
@@ -1035,7 +961,7 @@ static int seglin_bwd_impl(const ea_geom* g, const ea_t4* q, const ea_t4* k, con
   }
   SET3(q, q); SET3(k, k); SET3(dq, dq); SET3(dk, dk);
   p.Gq = Gq; p.gqb = gq_b; p.Gk = Gk; p.gkb = gk_b; p.lnq_w = lnq_w; p.lnq_b = lnq_b; p.lnk_w = lnk_w; p.lnk_b = lnk_b;
-  p.d_qbar = d_qbar; p.d_kbar = d_kbar; p.part = part; p.dG_part = dG_part; p.stats = stats;
+  p.d_qbar = d_qbar; p.d_kbar = d_kbar; p.part = part; p.dG_part = dG_part; p.stats = reinterpret_cast<f32x4*>(stats);
   rc = ea::seglin_dispatch(fin ? 3 : 1, p, g->dtype, (hipStream_t)stream);
   if (rc != EA_OK) return rc;
   return ea::seglin_dispatch(2, p, g->dtype, (hipStream_t)stream);
@@ -1197,22 +1123,6 @@ int ea_adaptive_pool2d_bwd(int32_t dtype, int32_t B, int32_t H, int32_t gh, int3
 }  // extern "C"
 
 // ---- LARA 'adaptive-1d': the generators' Linear folded into the qkv projection (ea_fold.hip) ----
-namespace ea {
-struct FoldP {
-  const float *W, *b, *Gq, *Gk, *gqb, *gkb;
-  char* w_ext;
-  char* b_ext;
-  float *bias_q, *bias_k;
-  const float *dW_ext, *db_ext, *dbias_q, *dbias_k;
-  float *dW, *db, *dGq, *dGk, *dgqb, *dgkb;
-  float *dG_part, *dG_base;
-  long ldw;
-  int C, h, d;
-};
-int fold_dispatch(bool bwd, int dtype, const FoldP& p, hipStream_t st);
-int fold_bwd_parts(int heads);
-}  // namespace ea
-
 extern "C" {
 
 int ea_lara_fold_fwd(int32_t dtype, int32_t C, int32_t heads, const float* W, const float* b, const float* Gq, const float* gq_b,

@@ -16,6 +16,7 @@
 #include <stdint.h>
 #include "../../include/ea_hip.h"
 #include "ea_lds_swizzle.h"
+#include "ea_launch.h"      // per-device launch state: ea_device_cus(), ea_lds_limit(), ea_occupancy()
 
 // ---- dev-only phase profiling (-DEA_PROFILE, tools/build_prof_lib.sh): thread 0 of workgroup 0
 // stamps s_memtime into p.prof[i]; the dispatcher prints the deltas.  Compiled out of the product.
@@ -89,38 +90,6 @@ struct ProfReport {
 
 
 namespace ea {
-
-// ---- per-device launch state.  hipFuncSetAttribute acts on the CURRENT device's copy of a kernel and the CU
-// count is a device property: a process that drives several GPUs must keep both per device.
-constexpr int EA_MAX_DEV = 64;
-inline int ea_cur_device() {
-  int dev = 0;
-  if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= EA_MAX_DEV) dev = 0;
-  return dev;
-}
-inline int ea_device_cus() {
-  static int n[EA_MAX_DEV] = {};
-  const int dev = ea_cur_device();
-  if (!n[dev]) {
-    hipDeviceProp_t prop;
-    int v = 0;
-    if (hipGetDeviceProperties(&prop, dev) == hipSuccess) v = prop.multiProcessorCount;
-    n[dev] = v > 0 ? v : 256;
-  }
-  return n[dev];
-}
-// once per (call site, device): raise the dynamic-LDS limit of kernel `fn`
-#define EA_SET_LDS_ONCE(fn, bytes)                                                                              \
-  do {                                                                                                         \
-    static bool ea_done_[ea::EA_MAX_DEV] = {};                                                                 \
-    const int ea_dev_ = ea::ea_cur_device();                                                                   \
-    if (!ea_done_[ea_dev_]) {                                                                                  \
-      hipError_t ea_e_ = hipFuncSetAttribute(reinterpret_cast<const void*>(fn),                                \
-                                             hipFuncAttributeMaxDynamicSharedMemorySize, (int)(bytes));       \
-      if (ea_e_ != hipSuccess) return (int)ea_e_;                                                              \
-      ea_done_[ea_dev_] = true;                                                                                \
-    }                                                                                                          \
-  } while (0)
 
 typedef __attribute__((ext_vector_type(4))) float f32x4;
 typedef __attribute__((ext_vector_type(2))) float f32x2;   // arithmetic on it maps to v_pk_*_f32

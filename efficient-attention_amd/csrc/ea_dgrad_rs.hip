@@ -16,6 +16,7 @@
 // staging through LDS is 18 store / barrier / transposed-read rounds before the first tile: ~5 us of every launch.)
 #include <stdlib.h>
 #include "ea_common.h"
+#include "ea_linear.h"
 
 namespace ea {
 
@@ -508,12 +509,12 @@ int dgrad_rs_dispatch(int dtype, const void* dy, const void* w, int w_kind, void
   const dim3 g((unsigned)grid), b(DG_WAVES * 64);
 #define EA_DG_LAUNCH(E_, WF_, OF_)                                                        \
   do {                                                                                    \
-    EA_SET_LDS_ONCE((&dgrad_rs_kernel<E_, WF_, OF_>), DG_LDS);                            \
+    if (const int e = ea_lds_limit(&dgrad_rs_kernel<E_, WF_, OF_>, DG_LDS)) return e;     \
     hipLaunchKernelGGL((dgrad_rs_kernel<E_, WF_, OF_>), g, b, DG_LDS, st, p);             \
   } while (0)
 #define EA_DG_LAUNCH_WT(E_, OF_)                                                          \
   do {                                                                                    \
-    EA_SET_LDS_ONCE((&dgrad_rs_wt_kernel<E_, OF_>), DG_LDS);                              \
+    if (const int e = ea_lds_limit(&dgrad_rs_wt_kernel<E_, OF_>, DG_LDS)) return e;       \
     hipLaunchKernelGGL((dgrad_rs_wt_kernel<E_, OF_>), g, b, DG_LDS, st, p);               \
   } while (0)
 #define EA_DG_SEL(E_)                                                                     \
@@ -544,12 +545,14 @@ int dgrad_fin_dispatch(int dtype, const DgFinP& p0, int w_kind, int dx_f32, bool
 #endif
 #define EA_DF_LAUNCH_W(E_, WF_, OF_, T_, P_, R_)                                                  \
   do {                                                                                            \
-    EA_SET_LDS_ONCE((&dgrad_fin_kernel<E_, WF_, OF_, T_, P_, R_>), DG_FIN_LDS);                   \
+    if (const int e = ea_lds_limit(&dgrad_fin_kernel<E_, WF_, OF_, T_, P_, R_>, DG_FIN_LDS))      \
+      return e;                                                                                   \
     hipLaunchKernelGGL((dgrad_fin_kernel<E_, WF_, OF_, T_, P_, R_>), g, b, DG_FIN_LDS, st, p);    \
   } while (0)
 #define EA_DF_LAUNCH_WT(E_, OF_, T_, P_, R_)                                                      \
   do {                                                                                            \
-    EA_SET_LDS_ONCE((&dgrad_fin_wt_kernel<E_, OF_, T_, P_, R_>), DG_FIN_LDS);                     \
+    if (const int e = ea_lds_limit(&dgrad_fin_wt_kernel<E_, OF_, T_, P_, R_>, DG_FIN_LDS))        \
+      return e;                                                                                   \
     hipLaunchKernelGGL((dgrad_fin_wt_kernel<E_, OF_, T_, P_, R_>), g, b, DG_FIN_LDS, st, p);      \
   } while (0)
 // (WF_ = 2: the prepared image)

@@ -401,10 +401,10 @@ int ga_launch(bool bwd, const GaP& p, hipStream_t st) {
   const int nqb = (p.Wq + QB - 1) / QB;
   const dim3 grid((unsigned)(p.G * nqb), (unsigned)(p.B * p.H)), block(NT);
   if (bwd) {
-    EA_SET_LDS_ONCE((&ga_bwd_kernel<D, KC>), lds);
+    if (const int e = ea_lds_limit(&ga_bwd_kernel<D, KC>, lds)) return e;
     hipLaunchKernelGGL((ga_bwd_kernel<D, KC>), grid, block, lds, st, p);
   } else {
-    EA_SET_LDS_ONCE((&ga_fwd_kernel<D, KC>), lds);
+    if (const int e = ea_lds_limit(&ga_fwd_kernel<D, KC>, lds)) return e;
     hipLaunchKernelGGL((ga_fwd_kernel<D, KC>), grid, block, lds, st, p);
   }
   return (int)hipGetLastError();

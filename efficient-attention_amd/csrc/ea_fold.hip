@@ -10,21 +10,9 @@
 //             db [3C] = db_ext[:3C] + Gq^T dbias_q (q part) + Gk^T dbias_k (k part)
 #include "ea_common.h"
 #include "ea_f32_mm.h"
+#include "ea_fold.h"
 
 namespace ea {
-
-struct FoldP {
-  const float *W, *b, *Gq, *Gk, *gqb, *gkb;     // [3C, C], [3C] | null, [d, d] x 2, [d] x 2
-  char* w_ext;                                   // [5C, C] element type
-  char* b_ext;                                   // [5C] element type | null
-  float *bias_q, *bias_k;                        // [h, d]
-  // backward
-  const float *dW_ext, *db_ext, *dbias_q, *dbias_k;   // [5C, ldw], [5C] | null, [h, d] x 2
-  float *dW, *db, *dGq, *dGk, *dgqb, *dgkb;            // [3C, C], [3C] | null, [d, d] x 2, [d] x 2
-  float *dG_part, *dG_base;                            // [2][h FB_SPLIT][64 x 64] partials, [2][64 x 64] bias part
-  long ldw;
-  int C, h, d;
-};
 
 // 64 x 64 fp32 tile of a row-major matrix (row stride ld) -> LDS image [64][65]
 EA_DEV void fold_load(float* dst, const float* src, long ld, int tid) {

@@ -603,26 +603,26 @@ int kz_launch(int which, const KzP& p, dim3 grid, size_t lds, hipStream_t st) {
   switch (which) {
     case 0:
       if constexpr (MAP == KZ_FAVORP || MAP == KZ_FOURIER) {
-        EA_SET_LDS_ONCE((&kz_stats_kernel<MAP>), lds);
+        if (const int e = ea_lds_limit(&kz_stats_kernel<MAP>, lds)) return e;
         hipLaunchKernelGGL(kz_stats_kernel<MAP>, grid, block, lds, st, p);
       } else {
         return EA_E_BADARG;
       }
       break;
     case 1:
-      EA_SET_LDS_ONCE((&kz_kv_kernel<MAP, COS>), lds);
+      if (const int e = ea_lds_limit(&kz_kv_kernel<MAP, COS>, lds)) return e;
       hipLaunchKernelGGL((kz_kv_kernel<MAP, COS>), grid, block, lds, st, p);
       break;
     case 2:
-      EA_SET_LDS_ONCE((&kz_out_kernel<MAP, COS>), lds);
+      if (const int e = ea_lds_limit(&kz_out_kernel<MAP, COS>, lds)) return e;
       hipLaunchKernelGGL((kz_out_kernel<MAP, COS>), grid, block, lds, st, p);
       break;
     case 3:
-      EA_SET_LDS_ONCE((&kz_bwd_q_kernel<MAP, COS>), lds);
+      if (const int e = ea_lds_limit(&kz_bwd_q_kernel<MAP, COS>, lds)) return e;
       hipLaunchKernelGGL((kz_bwd_q_kernel<MAP, COS>), grid, block, lds, st, p);
       break;
     case 4:
-      EA_SET_LDS_ONCE((&kz_bwd_k_kernel<MAP, COS>), lds);
+      if (const int e = ea_lds_limit(&kz_bwd_k_kernel<MAP, COS>, lds)) return e;
       hipLaunchKernelGGL((kz_bwd_k_kernel<MAP, COS>), grid, block, lds, st, p);
       break;
     default:

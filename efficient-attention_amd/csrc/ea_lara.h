@@ -96,4 +96,11 @@ EA_DEV LaraElem lara_alpha(int mis, float T2, float lse_t2, float bh, float kapp
   return e;
 }
 
+// the passes: ea_lara_x.hip, ea_lara_y.hip, ea_lara_f.hip, ea_lara_xp.hip
+int lara_x_dispatch(int mode, const LaraP& p, int dtype, hipStream_t st);
+int lara_y_dispatch(int mode, const LaraP& p, int dtype, hipStream_t st);
+int lara_f_dispatch(int which, const LaraP& p, int dtype, hipStream_t st);
+bool lara_xp_supported(int H, int D, int C, int S);
+int lara_xp_dispatch(const LaraP& p, const LaraXpP& xp, int dtype, hipStream_t st);
+
 }  // namespace ea

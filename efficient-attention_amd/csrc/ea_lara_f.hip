@@ -930,10 +930,6 @@ size_t lara_f_lds(int which, int D, int Cp) {
 // dispatch the BH first slices start next to slots - BH second slices and the remaining second slices
 // follow in rb = ceil(BH / (slots - BH)) rounds, so first : second = rb : 1 keeps every slot busy to
 // the end (B*h = 384 on 256 CUs x 2 workgroups: 592 + 192 tokens instead of 448 + 336).
-static int f_env_int(const char* name, int dflt) {
-  const char* s = getenv(name);
-  return s ? atoi(s) : dflt;
-}
 static void lara_f_plan(LaraP& p, int slots, int F, int last_extra = 0) {
   if (p.nsplit != 2) return;
   const int BH = p.B * p.H, gran = 64;
@@ -952,7 +948,7 @@ static void lara_f_plan(LaraP& p, int slots, int F, int last_extra = 0) {
     const int rb = (BH + (slots - BH) - 1) / (slots - BH);
     // F: fixed prologue / epilogue of a workgroup, in token-times (query side, round 3: ~8 us against 0.05 us per token)
     int b = ((p.N - (rb - 1) * F) / (1 + rb) + gran / 2) / gran * gran;
-    static const int b_env = f_env_int("EA_LARA_FQ_B", 0);      // dev knob: tokens of the second slice (query side)
+    static const int b_env = ea_env_int("EA_LARA_FQ_B", 0);      // dev knob: tokens of the second slice (query side)
     if (b_env > 0 && F != 96) b = b_env;
     if (b >= 16 && b < p.N) p.tok_begin[1] = p.N - b;
     // Short sequences (round 6, N = 196 at B*h = 384): a second slice cannot even carry its own fixed cost -- equal halves run
@@ -963,51 +959,28 @@ static void lara_f_plan(LaraP& p, int slots, int F, int last_extra = 0) {
   }
 }
 
-static int f_device_cus() {
-  static int n = 0;
-  if (!n) {
-    int dev = 0;
-    hipDeviceProp_t prop;
-    if (hipGetDevice(&dev) == hipSuccess && hipGetDeviceProperties(&prop, dev) == hipSuccess) n = prop.multiProcessorCount;
-    if (n <= 0) n = 256;
-  }
-  return n;
-}
-
-template <typename K>
-static int f_occupancy(K kern, size_t lds) {
-  int n = 0;
-  if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, reinterpret_cast<const void*>(kern), 256, lds) != hipSuccess || n <= 0) n = 2;
-  return n;
-}
-
 template <typename E, int D, int NCT>
 static int launch_f(int which, LaraP& p, hipStream_t st) {
   const size_t lds = lara_f_lds(which == 3 ? 1 : which, D, NCT * 16);
   const dim3 grid((unsigned)(p.B * p.H * p.nsplit)), block(256);
-  static int occ[9] = {0, 0, 0, 0, 0, 0, 0, 0, 0};   // resident workgroups per CU of the instantiations
-  static const int fq_fixed = f_env_int("EA_LARA_FQ_F", 160);
-  static const int fk_extra = f_env_int("EA_LARA_FK_X", 128);      // dev knob: the merging slice's extra work in token-times
-#define EA_LF(K, slot, ...)                                                                           \
+  static const int fq_fixed = ea_env_int("EA_LARA_FQ_F", 160);
+  static const int fk_extra = ea_env_int("EA_LARA_FK_X", 128);      // dev knob: the merging slice's extra work in token-times
+#define EA_LF(K, ...)                                                                                 \
   do {                                                                                                \
-    if (lds > 64 * 1024) {                                                                            \
-      hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&K<__VA_ARGS__>),              \
-                                         hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);      \
-      if (e != hipSuccess) return (int)e;                                                             \
-    }                                                                                                 \
-    if (!occ[slot]) occ[slot] = f_occupancy(&K<__VA_ARGS__>, lds);                                    \
-    lara_f_plan(p, occ[slot] * f_device_cus(), which == 0 ? fq_fixed : 96, which == 3 ? fk_extra : 0); \
+    if (const int e = ea_lds_limit(&K<__VA_ARGS__>, lds)) return e;                                   \
+    const int slots = ea_occupancy(&K<__VA_ARGS__>, 256, lds) * ea_device_cus();                      \
+    lara_f_plan(p, slots, which == 0 ? fq_fixed : 96, which == 3 ? fk_extra : 0);                     \
     hipLaunchKernelGGL((K<__VA_ARGS__>), grid, block, lds, st, p);                                    \
   } while (0)
   if (which == 0) {
     // r-pairs of the last landmark tile that can be populated (see lara_fq_kernel); the estimator variant
     const bool lh1 = NCT == 4 && p.C - 16 * (NCT - 1) <= 2;
-    if (p.mis == MIS_OPT) { if (lh1) EA_LF(lara_fq_kernel, 0, E, D, NCT, (NCT == 4 ? 1 : 2), MIS_OPT); else EA_LF(lara_fq_kernel, 3, E, D, NCT, 2, MIS_OPT); }
-    else if (p.mis == MIS_BIASED) { if (lh1) EA_LF(lara_fq_kernel, 4, E, D, NCT, (NCT == 4 ? 1 : 2), MIS_BIASED); else EA_LF(lara_fq_kernel, 5, E, D, NCT, 2, MIS_BIASED); }
-    else { if (lh1) EA_LF(lara_fq_kernel, 6, E, D, NCT, (NCT == 4 ? 1 : 2), MIS_BH); else EA_LF(lara_fq_kernel, 7, E, D, NCT, 2, MIS_BH); }
-  } else if (which == 1) EA_LF(lara_fk_kernel, 1, E, D, NCT, false);
-  else if (which == 3) EA_LF(lara_fk_kernel, 8, E, D, NCT, true);
-  else EA_LF(lara_fin_kernel, 2, E, D, NCT);
+    if (p.mis == MIS_OPT) { if (lh1) EA_LF(lara_fq_kernel, E, D, NCT, (NCT == 4 ? 1 : 2), MIS_OPT); else EA_LF(lara_fq_kernel, E, D, NCT, 2, MIS_OPT); }
+    else if (p.mis == MIS_BIASED) { if (lh1) EA_LF(lara_fq_kernel, E, D, NCT, (NCT == 4 ? 1 : 2), MIS_BIASED); else EA_LF(lara_fq_kernel, E, D, NCT, 2, MIS_BIASED); }
+    else { if (lh1) EA_LF(lara_fq_kernel, E, D, NCT, (NCT == 4 ? 1 : 2), MIS_BH); else EA_LF(lara_fq_kernel, E, D, NCT, 2, MIS_BH); }
+  } else if (which == 1) EA_LF(lara_fk_kernel, E, D, NCT, false);
+  else if (which == 3) EA_LF(lara_fk_kernel, E, D, NCT, true);
+  else EA_LF(lara_fin_kernel, E, D, NCT);
 #undef EA_LF
   return (int)hipGetLastError();
 }

@@ -19,27 +19,9 @@
 // One wave per (b, h, side, segment) -- the dG pass: per group of segments, its [64 x 64] partial in registers.
 #include <stdlib.h>
 #include "ea_lara_segment.h"
+#include "ea_lara_seglin.h"
 
 namespace ea {
-
-struct SegLinP {
-  char *q, *k;                       // stored q / k rows (element type), [B,H,N,64] views
-  int64_t q_sb, q_sh, q_sn, k_sb, k_sh, k_sn;
-  char *dq, *dk;                     // backward: accumulated into
-  int64_t dq_sb, dq_sh, dq_sn, dk_sb, dk_sh, dk_sn;
-  const float *Gq, *Gk, *gqb, *gkb;  // generator Linear [64, 64] (out, in), bias [64]
-  const float *lnq_w, *lnq_b, *lnk_w, *lnk_b;   // LayerNorm weight / bias [64]
-  float *qbar, *kbar;                // forward outputs [B*H, L, 64]
-  const float *d_qbar, *d_kbar;      // backward inputs
-  float* part;                       // backward: [B*H*groups, 2, 4, 64] partial sums (d ln_w, d ln_b, d g_b, unused)
-  f32x4* stats;                      // backward scratch [B*H, 2, N]: (mean, rstd, mean(a xhat), -) of every token's LayerNorm
-  float* dG_part;                    // backward: [nG, 2, 64, 64] partial sums of dG (nG = B*H*groups)
-  int B, H, N, L, segs, nshort, groups, seg_per_group, cgroups, cseg_per_group;
-  // the estimator's last dq correction riding on the dq / dk pass (ea_lara_seglin_bwd_fin, round 6): dq_n -= s sum_c t[c,n] (u qbar)_c
-  const float *fin_qbar, *fin_uq, *fin_lse;   // [B*H, C, 64], [B*H, C, 64], [B*H, C]; null: none
-  int C;
-  float fin_scale, fin_scale_log2;
-};
 
 namespace {
 
@@ -581,11 +563,7 @@ int seglin_dispatch(int which, const SegLinP& p0, int dtype, hipStream_t st) {
 #define EA_SLF(E_, NCT_)                                                                                           \
   do {                                                                                                             \
     constexpr int lds_ = 4 * (2 * NCT_ * 16 * 128 + NCT_ * 16 * 4);                                                \
-    if (lds_ > 48 * 1024) {                                                                                        \
-      hipError_t e_ = hipFuncSetAttribute(reinterpret_cast<const void*>(&seglin_col_kernel<E_, true, NCT_>),       \
-                                          hipFuncAttributeMaxDynamicSharedMemorySize, lds_);                      \
-      if (e_ != hipSuccess) return (int)e_;                                                                        \
-    }                                                                                                              \
+    if (const int e_ = ea_lds_limit(&seglin_col_kernel<E_, true, NCT_>, lds_)) return e_;                          \
     hipLaunchKernelGGL((seglin_col_kernel<E_, true, NCT_>), grid, block, lds_, st, p);                             \
   } while (0)
   if (which == 3 && (p.C < 1 || p.C > 64 || !p.fin_qbar || !p.fin_uq || !p.fin_lse)) return EA_E_BADARG;

@@ -32,4 +32,8 @@ struct SampP {
 };
 int lara_sample_dispatch(bool bwd, const SampP& p, hipStream_t st);
 
+// [side x side] block means of a 2-D token grid and their backward
+int pool2d_dispatch(bool bwd, int dtype, const void* x, long sb, long sh, long sn, float* mean, int B, int H, int gh, int gw,
+                    int side, int D, hipStream_t st);
+
 }  // namespace ea

@@ -356,18 +356,10 @@ int lara_sample_dispatch(bool bwd, const SampP& p, hipStream_t st) {
   const size_t lds = lara_sample_lds(p.L, p.C, p.D, bwd);
   if (lds > 150 * 1024) return EA_E_UNSUPPORTED;
   if (bwd) {
-    if (lds > 64 * 1024) {
-      hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&lara_sample_kernel<true>),
-                                         hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-      if (e != hipSuccess) return (int)e;
-    }
+    if (const int e = ea_lds_limit(&lara_sample_kernel<true>, lds)) return e;
     hipLaunchKernelGGL(lara_sample_kernel<true>, dim3((unsigned)p.BH), dim3(256), lds, st, p);
   } else {
-    if (lds > 64 * 1024) {
-      hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&lara_sample_kernel<false>),
-                                         hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-      if (e != hipSuccess) return (int)e;
-    }
+    if (const int e = ea_lds_limit(&lara_sample_kernel<false>, lds)) return e;
     hipLaunchKernelGGL(lara_sample_kernel<false>, dim3((unsigned)p.BH), dim3(256), lds, st, p);
   }
   return (int)hipGetLastError();

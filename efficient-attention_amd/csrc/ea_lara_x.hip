@@ -26,11 +26,7 @@ static int launch_x(int mode, const LaraP& p, hipStream_t st) {
   const dim3 grid((unsigned)(p.B * p.H * p.nsplit)), block(256);
 #define EA_LXM(M, S)                                                                              \
   do {                                                                                            \
-    if (lds > 64 * 1024) {                                                                        \
-      hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&lara_x_kernel<E, D, NCT, M, S>), \
-                                         hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);  \
-      if (e != hipSuccess) return (int)e;                                                         \
-    }                                                                                             \
+    if (const int e = ea_lds_limit(&lara_x_kernel<E, D, NCT, M, S>, lds)) return e;               \
     hipLaunchKernelGGL((lara_x_kernel<E, D, NCT, M, S>), grid, block, lds, st, p);                \
   } while (0)
 #define EA_LX(M) EA_LXM(M, -1)

@@ -27,7 +27,7 @@ size_t lara_xp_lds(int NCT) { return (size_t)3 * lara_xp_head_lds(NCT) + 2 * LAR
 template <typename E, int NCT, int MIS>
 static int launch_xp1(const LaraP& p, const LaraXpP& xp, hipStream_t st) {
   const size_t lds = lara_xp_lds(NCT);
-  EA_SET_LDS_ONCE((&lara_xp_kernel<E, NCT, MIS>), lds);
+  if (const int e = ea_lds_limit(&lara_xp_kernel<E, NCT, MIS>, lds)) return e;
   const dim3 grid((unsigned)(p.B * p.nsplit)), block(768);
   hipLaunchKernelGGL((lara_xp_kernel<E, NCT, MIS>), grid, block, lds, st, p, xp);
   return (int)hipGetLastError();

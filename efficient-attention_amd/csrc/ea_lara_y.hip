@@ -435,27 +435,10 @@ static void lara_y_plan(LaraP& p, int slots) {
   }
 }
 
-static int device_cus() {
-  static int n = 0;
-  if (!n) {
-    int dev = 0;
-    hipDeviceProp_t prop;
-    if (hipGetDevice(&dev) == hipSuccess && hipGetDeviceProperties(&prop, dev) == hipSuccess) n = prop.multiProcessorCount;
-    if (n <= 0) n = 256;
-  }
-  return n;
-}
-
 template <typename E, int D, int MODE, int MIS = -1>
 static int launch_y_mode(LaraP& p, hipStream_t st) {
   const size_t lds = (size_t)2 * 128 * D * 2 + (size_t)4 * 128 * sizeof(float);
-  static int occ = 0;                       // resident workgroups per CU of this instantiation
-  if (!occ) {
-    int n = 0;
-    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, reinterpret_cast<const void*>(&lara_y_kernel<E, D, MODE, MIS>), 256, lds) != hipSuccess || n <= 0) n = 2;
-    occ = n;
-  }
-  lara_y_plan(p, occ * device_cus());
+  lara_y_plan(p, ea_occupancy(&lara_y_kernel<E, D, MODE, MIS>, 256, lds) * ea_device_cus());
   const dim3 grid((unsigned)(p.B * p.H * p.nsplit), (unsigned)((p.NCT + 3) / 4)), block(256);
   hipLaunchKernelGGL((lara_y_kernel<E, D, MODE, MIS>), grid, block, lds, st, p);
   return (int)hipGetLastError();

@@ -19,6 +19,7 @@
 // activations leave HBM once.
 #include <stdlib.h>
 #include "ea_common.h"
+#include "ea_linear.h"
 
 namespace ea {
 
@@ -201,20 +202,13 @@ __global__ __launch_bounds__((NPR > 8 ? 512 : 256), (NPR > 8 ? 1 : 2)) void lin_
   }
 }
 
-static int lin_cus() { return ea_device_cus(); }
-
-static int env_int(const char* name, int dflt) {
-  const char* s = getenv(name);
-  return s ? atoi(s) : dflt;
-}
-
 // weight rows of a part (its bias, <= 1.5 KB, rides on top): two workgroups per CU / one 8-wave workgroup
 constexpr int LIN_LDS_MAX = 72 * 1024, LIN_LDS_MAX1 = 112 * 1024;
 
 template <typename E, int KT, int RT, bool AF32, int NPR, bool YF32>
 static int launch_lin1(const LinP& p, hipStream_t st) {
   const size_t lds = (size_t)(NPR * 32) * (KT * 64 + 4);
-  EA_SET_LDS_ONCE((&lin_kernel<E, KT, RT, AF32, NPR, YF32>), (NPR > 8 ? LIN_LDS_MAX1 : LIN_LDS_MAX) + 2048);
+  if (const int e = ea_lds_limit(&lin_kernel<E, KT, RT, AF32, NPR, YF32>, (NPR > 8 ? LIN_LDS_MAX1 : LIN_LDS_MAX) + 2048)) return e;
   const dim3 grid((unsigned)(p.wg_per_part * p.nsplit)), block(NPR > 8 ? 512 : 256);
   hipLaunchKernelGGL((lin_kernel<E, KT, RT, AF32, NPR, YF32>), grid, block, lds, st, p);
   return (int)hipGetLastError();
@@ -225,7 +219,7 @@ static int launch_lin1(const LinP& p, hipStream_t st) {
 // 576 columns of 192 channels (the qkv projection of a 192-wide model) go as two parts of 288 on one 8-wave workgroup
 // per CU instead: the activations pass the load pipes twice, not three times
 static int lin_nsplit(int K, int NO) {
-  static const int wide = env_int("EA_LIN_WIDE", 1);
+  static const int wide = ea_env_int("EA_LIN_WIDE", 1);
   if (wide && NO == 576 && K == 192) return 2;
   for (int ns = 1; ns <= 4; ++ns) {
     if (NO % ns) continue;
@@ -280,11 +274,11 @@ int linear_dispatch(int dtype, const void* a, int a_f32, const void* w, int w_mo
   p.rows = rows; p.NO = NO; p.y_f32 = y_f32; p.w_mode = w_mode; p.lda = lda; p.ldy = ldy;
   p.nsplit = lin_nsplit(K, NO);
   // two resident workgroups per CU in total, a multiple of 8 per part (one XCD each), no more than there are tiles
-  static const int per_cu_env = env_int("EA_LIN_PER_CU", 0);
+  static const int per_cu_env = ea_env_int("EA_LIN_PER_CU", 0);
   const int per_cu = per_cu_env > 0 ? per_cu_env : (NO / p.nsplit > 256 ? 1 : 2);
   const int rt = K <= 192 ? 2 : 1;
   const int nsteps = (rows + 16 * rt - 1) / (16 * rt);
-  int wgp = per_cu * lin_cus() / p.nsplit / 8 * 8;
+  int wgp = per_cu * ea_device_cus() / p.nsplit / 8 * 8;
   const int nw = NO / p.nsplit > 256 ? 8 : 4;
   const int need = ((nsteps + nw - 1) / nw + 7) / 8 * 8;
   if (wgp > need) wgp = need;

@@ -705,10 +705,7 @@ static int launch_lmk2(bool bwd, const LmkP& p, hipStream_t st) {
   const size_t lds = lmk2_lds(D, bwd);
   const void* fn = bwd ? reinterpret_cast<const void*>(&lmk2::lmk2_kernel<D, true>)
                        : reinterpret_cast<const void*>(&lmk2::lmk2_kernel<D, false>);
-  if (lds > 64 * 1024) {
-    hipError_t e = hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    if (e != hipSuccess) return (int)e;
-  }
+  if (const int e = ea_lds_limit(fn, lds)) return e;
   if (bwd) hipLaunchKernelGGL((lmk2::lmk2_kernel<D, true>), dim3(p.BH), dim3(256), lds, st, p);
   else hipLaunchKernelGGL((lmk2::lmk2_kernel<D, false>), dim3(p.BH), dim3(256), lds, st, p);
   return (int)hipGetLastError();

@@ -424,23 +424,23 @@ int pf32_dispatch(int which, const Pf32P& p0, hipStream_t st) {
   const size_t lds = pf32_lds(which, p.M);
   switch (which) {
     case 0:
-      EA_SET_LDS_ONCE((&pf32_kmax_kernel), lds);
+      if (const int e = ea_lds_limit(&pf32_kmax_kernel, lds)) return e;
       hipLaunchKernelGGL(pf32_kmax_kernel, grid, block, lds, st, p);
       break;
     case 1:
-      EA_SET_LDS_ONCE((&pf32_kv_kernel), lds);
+      if (const int e = ea_lds_limit(&pf32_kv_kernel, lds)) return e;
       hipLaunchKernelGGL(pf32_kv_kernel, grid, block, lds, st, p);
       break;
     case 2:
-      EA_SET_LDS_ONCE((&pf32_out_kernel), lds);
+      if (const int e = ea_lds_limit(&pf32_out_kernel, lds)) return e;
       hipLaunchKernelGGL(pf32_out_kernel, grid, block, lds, st, p);
       break;
     case 3:
-      EA_SET_LDS_ONCE((&pf32_bwd_q_kernel), lds);
+      if (const int e = ea_lds_limit(&pf32_bwd_q_kernel, lds)) return e;
       hipLaunchKernelGGL(pf32_bwd_q_kernel, grid, block, lds, st, p);
       break;
     case 4:
-      EA_SET_LDS_ONCE((&pf32_bwd_k_kernel), lds);
+      if (const int e = ea_lds_limit(&pf32_bwd_k_kernel, lds)) return e;
       hipLaunchKernelGGL(pf32_bwd_k_kernel, grid, block, lds, st, p);
       break;
     default:

@@ -5,6 +5,7 @@
 //   * fp32 column sums of per-(b,h) parameter-gradient partials;
 //   * scale * (a + sum over sequence slices) of a per-landmark tensor.
 #include "ea_common.h"
+#include "ea_proj.h"
 
 namespace ea {
 

@@ -11,6 +11,7 @@
 // The weight rows of a tile PAIR are interleaved in fours, so a lane ends up with eight consecutive columns of one token
 // (16-byte stores); the third tile of a wave gives 8-byte stores.
 #include "ea_common.h"
+#include "ea_linear.h"
 
 namespace ea {
 

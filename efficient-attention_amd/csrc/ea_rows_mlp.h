@@ -20,4 +20,7 @@ struct RowsP {
   float* dW_part;                      // bwd: [blocks, sides, D, D]
 };
 
+int rows_mlp_dispatch(const RowsP& p, int D, int sides, int layer_norm, bool bwd, hipStream_t st);
+int rows_mlp_blocks(int R, int D);
+
 }  // namespace ea

@@ -271,10 +271,7 @@ static int launch_rows(const RowsP& p, int sides, bool bwd, hipStream_t st) {
   const size_t lds = rows_lds<D>(bwd);
   const void* fn = bwd ? reinterpret_cast<const void*>(&rows_mlp_bwd_kernel<D, LN>)
                        : reinterpret_cast<const void*>(&rows_mlp_fwd_kernel<D, LN>);
-  if (lds > 64 * 1024) {
-    hipError_t e = hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    if (e != hipSuccess) return (int)e;
-  }
+  if (const int e = ea_lds_limit(fn, lds)) return e;
   const dim3 grid((unsigned)rows_mlp_blocks(p.R, D), (unsigned)sides);
   if (bwd) hipLaunchKernelGGL((rows_mlp_bwd_kernel<D, LN>), grid, dim3(RowsCfg<D>::NT), lds, st, p);
   else hipLaunchKernelGGL((rows_mlp_fwd_kernel<D, LN>), grid, dim3(RowsCfg<D>::NT), lds, st, p);

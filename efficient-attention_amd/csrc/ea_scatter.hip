@@ -1286,9 +1286,7 @@ int sb_ov_dispatch(int which, const SbP& p0, int dtype, hipStream_t st) {
   const dim3 grid((unsigned)(p.B * p.H * p.nwin)), block(256);
 #define EA_SBO(K)                                                                                           \
   do {                                                                                                      \
-    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&K),                                   \
-                                       hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);              \
-    if (e != hipSuccess) return (int)e;                                                                     \
+    if (const int e = ea_lds_limit(&K, lds)) return e;                                                      \
     hipLaunchKernelGGL(K, grid, block, lds, st, p);                                                         \
   } while (0)
   if (dtype == EA_BF16) {
@@ -1331,9 +1329,7 @@ int sb_bwd_dispatch(int which, const SbP& p0, int dtype, hipStream_t st) {
   const dim3 grid((unsigned)(p.B * p.H * (p.nwin / p.wpb))), block(256);
 #define EA_SB(E, G)                                                                                         \
   do {                                                                                                      \
-    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&sb_bwd_kernel<E, G>),                 \
-                                       hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);              \
-    if (e != hipSuccess) return (int)e;                                                                     \
+    if (const int e = ea_lds_limit(&sb_bwd_kernel<E, G>, lds)) return e;                                    \
     hipLaunchKernelGGL((sb_bwd_kernel<E, G>), grid, block, lds, st, p);                                     \
   } while (0)
   if (dtype == EA_BF16) { if (which) EA_SB(BF16, true); else EA_SB(BF16, false); }

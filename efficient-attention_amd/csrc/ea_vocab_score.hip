@@ -329,7 +329,7 @@ __global__ __launch_bounds__(VS_FOLD_THREADS) void vocab_score_fold_kernel(const
 
 template <typename E, bool XF32>
 int vs_launch(const VocabScoreP& p, hipStream_t st) {
-  EA_SET_LDS_ONCE((vocab_score_kernel<E, XF32>), VS_LDS_BYTES);
+  if (const int e = ea_lds_limit(vocab_score_kernel<E, XF32>, VS_LDS_BYTES)) return e;
   hipLaunchKernelGGL((vocab_score_kernel<E, XF32>), dim3((unsigned)(p.MT * p.NS)), dim3(VS_THREADS), VS_LDS_BYTES, st, p);
   return (int)hipGetLastError();
 }

@@ -17,6 +17,7 @@
 #include <stdlib.h>
 #include <algorithm>
 #include "ea_common.h"
+#include "ea_linear.h"
 
 namespace ea {
 
@@ -350,7 +351,6 @@ int part_sum_dispatch(const float* part, float* out, int S, int n, long ld, hipS
   return (int)hipGetLastError();
 }
 
-static int wg_cus() { return ea_device_cus(); }
 
 // tile edge along one axis.  The kernel is fed from L2 at ~10 B/clk/CU, so its MFMA rate is set by the FLOPs per staged
 // byte = (BM * BN) / (BM + BN): a [256 x 256] tile (wide models: 512 / 1024 / 1536 / 3072 channels) does twice the work
@@ -368,15 +368,15 @@ static int wg_bt(int M) {
 int wgrad_slices(int rows, int M, int K) {
   if (rows <= 0 || M <= 0 || K <= 0 || (M & 63) || (K & 63)) return EA_E_UNSUPPORTED;
   const int T = (M / wg_bt(M)) * (K / wg_bt(K));
-  const int per_xcd = wg_cus() / 8;
+  const int per_xcd = ea_device_cus() / 8;
   int S = per_xcd / T * 8;
   if (S < 8) S = 8;
   while (S > 8 && rows / S < 256) S -= 8;
   // many tiles (wide models): a multiple of 8 slices can leave a third of the CUs idle (20 tiles x 8 slices = 160
   // workgroups).  The kernel is bound by what ONE CU can pull out of L2 (~12.5 B/clk measured), so filling the CUs beats
   // keeping a slice's tiles on one XCD -- the re-reads of a dY / X row by the other XCDs hit the Infinity Cache.
-  if (S * T < wg_cus() * 85 / 100 && T <= wg_cus()) {
-    int Sf = wg_cus() / T;
+  if (S * T < ea_device_cus() * 85 / 100 && T <= ea_device_cus()) {
+    int Sf = ea_device_cus() / T;
     while (Sf > 1 && rows / Sf < 256) --Sf;
     if (Sf * T > S * T && (Sf & 7) != 0) S = Sf;
   }
@@ -388,7 +388,7 @@ int wgrad_slices(int rows, int M, int K) {
 template <typename E, int BM, int BN>
 static int launch_wg(const WgP& p, hipStream_t st) {
   const size_t lds = (size_t)2 * (BM / 64 + BN / 64) * 64 * 128;
-  if (lds > 64 * 1024) EA_SET_LDS_ONCE((&wgrad_kernel<E, BM, BN>), lds);
+  if (const int e = ea_lds_limit(&wgrad_kernel<E, BM, BN>, lds)) return e;
   const int T = p.tiles_m * p.tiles_n + p.T2;
   // (the staging addresses are 32-bit byte offsets from a slice's first row)
   const long widest = std::max(std::max(p.M, p.K), std::max(p.M2, p.K2));
@@ -414,7 +414,7 @@ int wgrad_pair_slices(int rows, int M1, int K1, int M2, int K2) {
   if (rows <= 0 || M1 <= 0 || K1 <= 0 || M2 <= 0 || K2 <= 0 || ((M1 | K1 | M2 | K2) & 63)) return EA_E_UNSUPPORTED;
   if (wg_bt(M1) != wg_bt(M2) || wg_bt(K1) != wg_bt(K2)) return EA_E_UNSUPPORTED;
   const int T = (M1 / wg_bt(M1)) * (K1 / wg_bt(K1)) + (M2 / wg_bt(M2)) * (K2 / wg_bt(K2));
-  const int per_xcd = wg_cus() / 8;
+  const int per_xcd = ea_device_cus() / 8;
   int S = per_xcd / T * 8;
   if (S < 8) S = 8;
   while (S > 8 && rows / S < 256) S -= 8;

@@ -47,20 +47,6 @@ struct WinTiling {
 
 __host__ __device__ inline int ceil_div(int a, int b) { return (a + b - 1) / b; }
 
-// CUs of the current device (cached; 256 = MI355X when no device is visible, e.g. build checks)
-inline int device_cu_count() {
-  static int n = 0;
-  if (!n) {
-    int dev = 0;
-    hipDeviceProp_t prop;
-    if (hipGetDevice(&dev) == hipSuccess && hipGetDeviceProperties(&prop, dev) == hipSuccess && prop.multiProcessorCount > 0)
-      n = prop.multiProcessorCount;
-    else
-      n = 256;
-  }
-  return n;
-}
-
 // LDS image of the backward kernel (ea_window_bwd.hip) for a tiling
 inline size_t window_bwd_lds(const WinTiling& t, int D, bool bias, bool bias_lds) {
   const int nQTe = (t.nQT + 1) & ~1;
@@ -101,7 +87,7 @@ inline void win_blocks(const ea_geom& g, WinTiling& t, bool backward) {
   int per_cu = backward ? (g.D == 128 ? 1 : 2) : (g.D == 128 ? 2 : 4);
   const size_t lds = backward ? window_bwd_lds(t, g.D, false, false) : (size_t)t.rowsTotal * g.D * 4;
   if (lds > WIN_LDS_MAX / 2) per_cu = 1;
-  const long slots = (long)device_cu_count() * per_cu;
+  const long slots = (long)ea_device_cus() * per_cu;
   int best = 1;
   double best_cost = 1e30;
   for (int nb = 1; nb <= t.niter; ++nb) {
@@ -357,5 +343,10 @@ EA_DEV int slot_token(const Geo& G, int packed, int oy, int ox) {
   const int tok = oy + packed;
   return (tok >= 0 && tok < G.N) ? tok : -1;
 }
+
+// ea_window_fwd.hip / ea_window_bwd.hip
+int window_fwd_dispatch(const WinP& p, int dtype, int D, hipStream_t st);
+int window_bwd_dispatch(const WinP& p, const ea_geom& geom, const T4& outp, const float* biasT, int dtype, int D,
+                        hipStream_t st);
 
 }  // namespace ea

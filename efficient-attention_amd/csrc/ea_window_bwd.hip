@@ -1006,11 +1006,7 @@ static int launch_bwd(const WinP& p0, const ea_geom& geom, const T4& outp, const
       // hand-over variant: no bias table / bias-gradient image in LDS, P / dS tiles of the landmark keys instead
       lds = window_bwd_lds(p.t, D, false, false) + (size_t)p.t.wpi * p.t.nQT * p.t.nCT * 1024;
     if (lds > WIN_LDS_MAX) return EA_E_UNSUPPORTED;
-    if (lds > 64 * 1024) {
-      hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern),
-                                         hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-      if (e != hipSuccess) return (int)e;
-    }
+    if (const int e = ea_lds_limit(kern, lds)) return e;
     hipLaunchKernelGGL(kern, dim3(blocks), dim3(256), lds, st, p, outp, biasT);
     return EA_OK;
   };

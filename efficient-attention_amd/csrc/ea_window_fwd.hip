@@ -323,11 +323,7 @@ template <typename E, int D, bool CA, bool DR, typename SG = SGdyn>
 static int launch_fwd_ca(const WinP& p, hipStream_t st) {
   const size_t lds = window_fwd_lds(p.t, D);
   if (lds > 160 * 1024) return EA_E_UNSUPPORTED;
-  if (lds > 64 * 1024) {
-    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&win_fwd_kernel<E, D, CA, DR, SG>),
-                                       hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    if (e != hipSuccess) return (int)e;
-  }
+  if (const int e = ea_lds_limit(&win_fwd_kernel<E, D, CA, DR, SG>, lds)) return e;
   const dim3 grid((unsigned)(p.B * p.H * p.t.nblk));
   hipLaunchKernelGGL((win_fwd_kernel<E, D, CA, DR, SG>), grid, dim3(256), lds, st, p);
   return (int)hipGetLastError();
