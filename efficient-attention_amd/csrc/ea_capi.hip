@@ -41,7 +41,7 @@ static Geo mk_geo(const ea_geom* g) {
 extern "C" {
 
 const char* ea_version(void) { return "ea_hip 0.1.0 gfx950"; }
-int32_t ea_abi_version(void) { return 30; }
+int32_t ea_abi_version(void) { return 31; }
 
 int32_t ea_window_bias_ld(const ea_geom* g) {
   WinTiling t;
@@ -1624,7 +1624,7 @@ int ea_scatter_ov_bwd_keys(const ea_sb_geom* g, int32_t ext, const ea_t4* k, con
 // ---- composite per-module entry points (round 3): one call = the whole LARA core forward, one = the whole backward ----
 // The reference's call sites run eagerly (vit/engine.py:47-64); issued from Python the core was ~15 C-ABI calls and ~30
 // tensor allocations per step.  Here the launch sequence lives in C++ and every intermediate sits in two caller-owned
-// workspaces (`saved`: what the backward needs again; `tmp`: scratch of one direction) whose sizes ea_lara_layer_ws reports.
+// workspaces (`saved`: what the backward needs again; `tmp`: scratch of one direction) whose sizes ea_lara_layer_plan reports.
 namespace {
 struct LaraLayerPlan {
   ea_geom pg;            // pooling geometry (uniform r x r average pooling of q, k: lara.py:43,48,145-151)
@@ -1692,27 +1692,19 @@ int lara_layer_plan(const ea_lara_layer* c, LaraLayerPlan& P) {
 
 extern "C" {
 
-int64_t ea_lara_layer_ws(const ea_lara_layer* c, int32_t which) {
+int ea_lara_layer_plan(const ea_lara_layer* c, ea_lara_layer_sizes* out) {
   LaraLayerPlan P;
   const int rc = lara_layer_plan(c, P);
   if (rc != EA_OK) return rc;
-  switch (which) {
-    case 0: return (int64_t)P.n_saved;
-    case 1: return (int64_t)P.n_ftmp;
-    case 2: return (int64_t)P.n_btmp;
-    case 3: return (int64_t)P.o_pq;
-    case 4: return (int64_t)P.o_pk;
-    case 5: return (int64_t)P.b_dW;
-    case 6: return (int64_t)P.b_dvec;
-    // round 5 (ea_lara_layer_bwd2 with EA_LARA_DEFER_FINISH): what ea_linear_dgrad_finish needs -- in the backward scratch
-    // u qbar rows (7), d(pooled q) (8), d(pooled k) (9); in `saved` the qbar rows (10) and lse_t (11)
-    case 7: return (int64_t)(P.b_big + 3 * (size_t)P.BH * P.C * c->D);
-    case 8: return (int64_t)P.b_dpq;
-    case 9: return (int64_t)P.b_dpk;
-    case 10: return (int64_t)P.o_qrows;
-    case 11: return (int64_t)P.o_lset;
-    default: return EA_E_BADARG;
-  }
+  if (!out) return EA_E_BADARG;
+  // bwd_uq .. saved_lse_t: what ea_linear_dgrad_finish needs after ea_lara_layer_bwd with EA_LARA_DEFER_FINISH -- in the backward
+  // scratch u qbar rows (the fourth [B*H, C, D] block of `big`), d(pooled q), d(pooled k); in `saved` the qbar rows and lse_t
+  ea_lara_layer_sizes& o = *out;
+  o.n_saved = (int64_t)P.n_saved; o.n_fwd_tmp = (int64_t)P.n_ftmp; o.n_bwd_tmp = (int64_t)P.n_btmp;
+  o.saved_pq = (int64_t)P.o_pq; o.saved_pk = (int64_t)P.o_pk; o.saved_qrows = (int64_t)P.o_qrows; o.saved_lse_t = (int64_t)P.o_lset;
+  o.bwd_dW = (int64_t)P.b_dW; o.bwd_dvec = (int64_t)P.b_dvec; o.bwd_uq = (int64_t)(P.b_big + 3 * (size_t)P.BH * P.C * c->D);
+  o.bwd_dpq = (int64_t)P.b_dpq; o.bwd_dpk = (int64_t)P.b_dpk;
+  return EA_OK;
 }
 
 // proj: the output projection's operands (ea_lara_layer_fwd_proj) or null
@@ -1780,13 +1772,7 @@ int ea_lara_layer_fwd_proj(const ea_lara_layer* c, const ea_t4* q, const ea_t4* 
 
 int ea_lara_layer_bwd(const ea_lara_layer* c, const ea_t4* q, const ea_t4* k, const ea_t4* v, const uint8_t* mask,
                       const float* noise, const float* const* params, const ea_t4* dout, const ea_t4* dq, const ea_t4* dk,
-                      const ea_t4* dv, const float* saved, float* tmp, float* dparams, void* stream) {
-  return ea_lara_layer_bwd2(c, q, k, v, mask, noise, params, dout, dq, dk, dv, saved, tmp, dparams, 0, stream);
-}
-
-int ea_lara_layer_bwd2(const ea_lara_layer* c, const ea_t4* q, const ea_t4* k, const ea_t4* v, const uint8_t* mask,
-                       const float* noise, const float* const* params, const ea_t4* dout, const ea_t4* dq, const ea_t4* dk,
-                       const ea_t4* dv, const float* saved, float* tmp, float* dparams, int32_t flags, void* stream) {
+                      const ea_t4* dv, const float* saved, float* tmp, float* dparams, int32_t flags, void* stream) {
   const bool defer_finish = (flags & EA_LARA_DEFER_FINISH) != 0;
   LaraLayerPlan P;
   int rc = lara_layer_plan(c, P);
@@ -1853,7 +1839,7 @@ int ea_lara_layer_bwd2(const ea_lara_layer* c, const ea_t4* q, const ea_t4* k, c
     rc = ea_lara_bwd_finish(&P.g, q, qrows, opt ? uq : nullptr, lse_t, dpq, dpk, c->pool_r, c->gh, c->gw, dq, dk, stream);
     if (rc != EA_OK) return rc;
   }
-  // dparams == NULL: the caller adds the per-(b,h) partials up itself (tmp + ea_lara_layer_ws(cfg, 5 / 6): [B*H, 2 D D] and
+  // dparams == NULL: the caller adds the per-(b,h) partials up itself (tmp + bwd_dW / bwd_dvec of the plan: [B*H, 2 D D] and
   // [B*H, 6 D]), e.g. together with other terminal sums of its backward in one ea_multi_sum launch
   if (c->has_mlp && dparams) rc = ea_colsum2_f32(P.BH, 2 * D * D, dW, dparams, 6 * D, dvec, dparams + (size_t)2 * D * D, stream);
   return rc;
@@ -1865,7 +1851,7 @@ int ea_lara_layer_bwd2(const ea_lara_layer* c, const ea_t4* q, const ea_t4* k, c
 // chunk means (or the projection kernel's) -> mu networks + omega (fused landmark kernel, eva mode) -> beta -> window
 // attention with the control-variate columns; backward: window backward -> landmark-gradient slice sum (+ bias-gradient
 // column sum) -> beta backward -> mu-network backward -> chunk-mean backward (-> parameter sums).  Same contract as the
-// LARA pair: caller-owned workspaces, sizes from ea_eva_layer_ws.
+// LARA pair: caller-owned workspaces, sizes from ea_eva_layer_plan.
 namespace {
 struct EvaLayerPlan {
   ea_geom g;
@@ -1919,27 +1905,18 @@ int eva_layer_plan(const ea_eva_layer* c, EvaLayerPlan& P) {
 
 extern "C" {
 
-int64_t ea_eva_layer_ws(const ea_eva_layer* c, int32_t which) {
+int ea_eva_layer_plan(const ea_eva_layer* c, ea_eva_layer_sizes* out) {
   EvaLayerPlan P;
   const int rc = eva_layer_plan(c, P);
   if (rc != EA_OK) return rc;
-  switch (which) {
-    case 0: return (int64_t)P.n_saved;
-    case 1: return 0;
-    case 2: return (int64_t)P.n_btmp;
-    case 3: return (int64_t)P.o_qm;
-    case 4: return (int64_t)P.o_km;
-    case 5: return (int64_t)P.b_dW;
-    case 6: return (int64_t)P.b_dvec;
-    case 7: return (int64_t)P.ld;
-    case 8: return (int64_t)P.o_lse;
-    case 9: return (int64_t)P.b_dbp;
-    case 10: return (int64_t)P.bparts * c->B;
-    // round 5 (ea_eva_layer_bwd2 with EA_EVA_DEFER_CHUNK_MEAN): the chunk-mean gradients ea_linear_dgrad_finish adds to dq / dk
-    case 11: return (int64_t)P.b_dqm;
-    case 12: return (int64_t)P.b_dkm;
-    default: return EA_E_BADARG;
-  }
+  if (!out) return EA_E_BADARG;
+  // bwd_dqmean / bwd_dkmean: the chunk-mean gradients ea_linear_dgrad_finish adds to dq / dk after EA_EVA_DEFER_CHUNK_MEAN
+  ea_eva_layer_sizes& o = *out;
+  o.n_saved = (int64_t)P.n_saved; o.n_bwd_tmp = (int64_t)P.n_btmp;
+  o.saved_qmean = (int64_t)P.o_qm; o.saved_kmean = (int64_t)P.o_km; o.saved_lse = (int64_t)P.o_lse; o.bias_ld = (int64_t)P.ld;
+  o.bwd_dW = (int64_t)P.b_dW; o.bwd_dvec = (int64_t)P.b_dvec; o.bwd_dbias_part = (int64_t)P.b_dbp;
+  o.dbias_part_rows = (int64_t)P.bparts * c->B; o.bwd_dqmean = (int64_t)P.b_dqm; o.bwd_dkmean = (int64_t)P.b_dkm;
+  return EA_OK;
 }
 
 int ea_eva_layer_fwd(const ea_eva_layer* c, const ea_t4* q, const ea_t4* k, const ea_t4* v, const float* bias,
@@ -1966,14 +1943,7 @@ int ea_eva_layer_fwd(const ea_eva_layer* c, const ea_t4* q, const ea_t4* k, cons
 int ea_eva_layer_bwd(const ea_eva_layer* c, const ea_t4* q, const ea_t4* k, const ea_t4* v, const float* bias,
                      const float* noise, const float* const* params, const ea_t4* out, const ea_t4* dout, const ea_t4* dq,
                      const ea_t4* dk, const ea_t4* dv, const float* saved, float* tmp, float* dbias, float* dparams,
-                     void* stream) {
-  return ea_eva_layer_bwd2(c, q, k, v, bias, noise, params, out, dout, dq, dk, dv, saved, tmp, dbias, dparams, 0, stream);
-}
-
-int ea_eva_layer_bwd2(const ea_eva_layer* c, const ea_t4* q, const ea_t4* k, const ea_t4* v, const float* bias,
-                      const float* noise, const float* const* params, const ea_t4* out, const ea_t4* dout, const ea_t4* dq,
-                      const ea_t4* dk, const ea_t4* dv, const float* saved, float* tmp, float* dbias, float* dparams,
-                      int32_t flags, void* stream) {
+                     int32_t flags, void* stream) {
   EvaLayerPlan P;
   int rc = eva_layer_plan(c, P);
   if (rc != EA_OK) return rc;
@@ -1995,7 +1965,7 @@ int ea_eva_layer_bwd2(const ea_eva_layer* c, const ea_t4* q, const ea_t4* k, con
     rc = ea_slice_sum(2, P.parts, (int32_t)LD, 1.f, nullptr, dl_p, dl, stream);
     if (rc != EA_OK) return rc;
   }
-  if (c->has_bias && dbias) {        // dbias == NULL: the partials stay in tmp for the caller's reduction (selectors 9 / 10)
+  if (c->has_bias && dbias) {        // dbias == NULL: the partials stay in tmp for the caller's reduction (bwd_dbias_part, dbias_part_rows)
     rc = ea_colsum_f32(P.bparts * c->B, c->H * P.Wq * P.ld, dbp, dbias, stream);
     if (rc != EA_OK) return rc;
   }
@@ -2012,7 +1982,7 @@ int ea_eva_layer_bwd2(const ea_eva_layer* c, const ea_t4* q, const ea_t4* k, con
     rc = ea_eva_chunk_mean_bwd(&P.g, dqm, dkm, nullptr, dq, dk, stream);
     if (rc != EA_OK) return rc;
   }
-  // dparams == NULL: the per-(b,h) partials stay in tmp (offsets ea_eva_layer_ws(cfg, 5 / 6)) for the caller's own reduction
+  // dparams == NULL: the per-(b,h) partials stay in tmp (offsets bwd_dW / bwd_dvec of the plan) for the caller's own reduction
   if (dparams) rc = ea_colsum2_f32(P.BH, 2 * D * D, dW, dparams, 6 * D, dvec, dparams + (size_t)2 * D * D, stream);
   return rc;
 }

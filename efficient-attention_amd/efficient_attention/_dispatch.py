@@ -151,7 +151,7 @@ def _(qkv, mask, noise, icfg, fcfg, params):
     # traced output count must be what the implementation will return when the graph runs)
     lcfg, sizes = _ops._lara_layer_cfg(qkv, icfg, fcfg) if _ops._lara_use_composite() else (None, None)
     if lcfg is not None:
-        return [qkv.new_empty((B, N, h, d)), _f32(qkv, sizes[0])]
+        return [qkv.new_empty((B, N, h, d)), _f32(qkv, sizes.n_saved)]
     return [qkv.new_empty((B, N, h, d)), _f32(qkv, BH, C, d), _f32(qkv, BH, C, d) if mis != 2 else _none(qkv),
             _f32(qkv, BH, C) if mis == 0 else _none(qkv), _f32(qkv, BH, C), _f32(qkv, BH, C, d), _f32(qkv, BH, C),
             _f32(qkv, BH, C) if mis == 0 else _none(qkv), _f32(qkv, BH, L, d), _f32(qkv, BH, L, d),

@@ -22,7 +22,7 @@ class ea_t4(ctypes.Structure):
                 ("sn", ctypes.c_int64)]
 
 
-ABI_VERSION = 30         # ea_abi_version() of include/ea_hip.h this file mirrors
+ABI_VERSION = 31         # ea_abi_version() of include/ea_hip.h this file mirrors
 
 
 class ea_geom(ctypes.Structure):
@@ -63,6 +63,11 @@ class ea_lara_layer(ctypes.Structure):
                 ("kappa", ctypes.c_float), ("scale", ctypes.c_float)]
 
 
+class ea_lara_layer_sizes(ctypes.Structure):
+    _fields_ = [(f, ctypes.c_int64) for f in ("n_saved", "n_fwd_tmp", "n_bwd_tmp", "saved_pq", "saved_pk", "saved_qrows",
+                                              "saved_lse_t", "bwd_dW", "bwd_dvec", "bwd_uq", "bwd_dpq", "bwd_dpk")]
+
+
 class ea_f32_attn(ctypes.Structure):
     _fields_ = [("B", ctypes.c_int32), ("H", ctypes.c_int32), ("Nq", ctypes.c_int32), ("Nk", ctypes.c_int32), ("D", ctypes.c_int32),
                 ("G", ctypes.c_int32), ("Wq", ctypes.c_int32), ("Wk", ctypes.c_int32), ("L", ctypes.c_int32),
@@ -90,6 +95,11 @@ class ea_eva_layer(ctypes.Structure):
     _fields_ = [("B", ctypes.c_int32), ("H", ctypes.c_int32), ("D", ctypes.c_int32), ("dtype", ctypes.c_int32),
                 ("gh", ctypes.c_int32), ("gw", ctypes.c_int32), ("window", ctypes.c_int32), ("chunk", ctypes.c_int32),
                 ("has_bias", ctypes.c_int32), ("scale", ctypes.c_float)]
+
+
+class ea_eva_layer_sizes(ctypes.Structure):
+    _fields_ = [(f, ctypes.c_int64) for f in ("n_saved", "n_bwd_tmp", "saved_qmean", "saved_kmean", "saved_lse", "bias_ld", "bwd_dW",
+                                              "bwd_dvec", "bwd_dbias_part", "dbias_part_rows", "bwd_dqmean", "bwd_dkmean")]
 
 
 class ea_lara_geom(ctypes.Structure):
@@ -191,15 +201,13 @@ SIGNATURES = {
     "ea_wgrad_pair": [_I, _I, _I, _I, _P, _P, _P, _P, _L, _I, _I, _P, _P, _P, _P, _L, _P],
     "ea_part_sum": [_I, _I, _L, _P, _P, _P],
     "ea_multi_sum": [_I, _P, _P, _P, _P, _P, _P],
-    "ea_lara_layer_ws": [_LL, _I],
+    "ea_lara_layer_plan": [_LL, ctypes.POINTER(ea_lara_layer_sizes)],
     "ea_lara_layer_fwd": [_LL, _T, _T, _T, _P, _P, _P, _T, _P, _P, _I, _P],
     "ea_lara_layer_fwd_proj": [_LL, _T, _T, _T, _P, _P, _P, _T, _P, _P, _I, _P, _P, _P, _L, _P],
-    "ea_lara_layer_bwd": [_LL, _T, _T, _T, _P, _P, _P, _T, _T, _T, _T, _P, _P, _P, _P],
-    "ea_lara_layer_bwd2": [_LL, _T, _T, _T, _P, _P, _P, _T, _T, _T, _T, _P, _P, _P, _I, _P],
-    "ea_eva_layer_ws": [_EL, _I],
+    "ea_lara_layer_bwd": [_LL, _T, _T, _T, _P, _P, _P, _T, _T, _T, _T, _P, _P, _P, _I, _P],
+    "ea_eva_layer_plan": [_EL, ctypes.POINTER(ea_eva_layer_sizes)],
     "ea_eva_layer_fwd": [_EL, _T, _T, _T, _P, _P, _P, _T, _P, _I, _P],
-    "ea_eva_layer_bwd": [_EL, _T, _T, _T, _P, _P, _P, _T, _T, _T, _T, _T, _P, _P, _P, _P, _P],
-    "ea_eva_layer_bwd2": [_EL, _T, _T, _T, _P, _P, _P, _T, _T, _T, _T, _T, _P, _P, _P, _P, _I, _P],
+    "ea_eva_layer_bwd": [_EL, _T, _T, _T, _P, _P, _P, _T, _T, _T, _T, _T, _P, _P, _P, _P, _I, _P],
     "ea_scatter_parts": [_SG],
     "ea_scatter_kmax": [_SG, _T, _P, _P, _P, _P],
     "ea_scatter_kv": [_SG, _T, _T, _P, _P, _P, _P, _P, _P],
@@ -291,8 +299,6 @@ def lib():
             fn.argtypes = argtypes
             fn.restype = ctypes.c_int
         cdll.ea_lara_landmarks_saved_floats.restype = ctypes.c_int64
-        cdll.ea_lara_layer_ws.restype = ctypes.c_int64
-        cdll.ea_eva_layer_ws.restype = ctypes.c_int64
         cdll.ea_ceva_sdecode_vocab_ws.restype = ctypes.c_int64
         cdll.ea_ceva_sdecode_vocab_sample_ws.restype = ctypes.c_int64
         cdll.ea_ceva_sdecode_vocab_lse_ws.restype = ctypes.c_int64

@@ -7,6 +7,7 @@ in place through strides, and the backward kernels write dq/dk/dv straight into 
 [B, N, 3, h, d] gradient buffer, so none of the reference's permute/contiguous/select-backward
 copies exist here.
 """
+import collections
 import ctypes
 import math
 import os
@@ -518,8 +519,8 @@ _EVA_LAYER_CFG = {}
 
 
 def _eva_layer_cfg_dims(B, h, d, io, icfg, fcfg, adaptive_proj, has_bias, masked):
-    """(ea_eva_layer, [saved floats, backward scratch floats, offsets of qmean, kmean, dW partials, dvec partials]) of the
-    composite entry points, or (None, None): 2-D non-overlapping windows, no pad mask / dropout, the fused mu networks."""
+    """(ea_eva_layer, ea_eva_layer_sizes: the workspace plan, read by field name) of the composite entry points, or
+    (None, None): 2-D non-overlapping windows, no pad mask / dropout, the fused mu networks.  Memoised per geometry."""
     attn_2d, s0, s1, window, ext, chunk, L, causal = [int(v) for v in icfg[:8]]
     if (not attn_2d or ext != 0 or causal != 0 or masked or adaptive_proj != "default" or float(fcfg[0]) != 0.5
             or float(fcfg[1]) != 1.0 or chunk <= 0 or s0 % chunk or s1 % chunk or (s0 // chunk) * (s1 // chunk) != L):
@@ -528,11 +529,34 @@ def _eva_layer_cfg_dims(B, h, d, io, icfg, fcfg, adaptive_proj, has_bias, masked
     hit = _EVA_LAYER_CFG.get(key)
     if hit is None:
         cfg = nv.ea_eva_layer(B, h, d, io, s0, s1, window, chunk, int(has_bias), float(d) ** -0.5)
-        sizes = [int(nv.lib().ea_eva_layer_ws(ctypes.byref(cfg), w)) for w in (0, 2, 3, 4, 5, 6, 9, 10, 11, 12)]   # 8, 9: d(chunk means)
-        hit = (cfg, sizes) if min(sizes) >= 0 else (None, None)
+        sizes = nv.ea_eva_layer_sizes()
+        hit = (cfg, sizes) if nv.lib().ea_eva_layer_plan(ctypes.byref(cfg), ctypes.byref(sizes)) == 0 else (None, None)
         if len(_EVA_LAYER_CFG) < 256:
             _EVA_LAYER_CFG[key] = hit
     return hit
+
+
+# pooled q / k rows [BH, L, d] (fp32) a projection kernel wrote (_pooled_rows): inside the fresh `saved` workspace `ws` of a
+# composite entry, or as two tensors for the step-by-step launches -- exactly one of ws and the pq / pk pair is set
+Pooled = collections.namedtuple("Pooled", "ws pq pk")
+# of _lara_backward / _eva_backward.  params: the summed parameter gradients (fp32, parameter order), None when deferred; partials:
+# (key, tensor [S, n], meta) entries for the caller's terminal sum; finish: the operands of qkv_dgrad_finish (a dict) or None
+CoreGrads = collections.namedtuple("CoreGrads", "dqkv dbias params partials finish")
+
+
+def _ws_rows(ws, at, rows, cols=None):
+    """rows [x cols] floats of a composite workspace from offset `at` (a field of its plan)."""
+    return ws[at:at + rows] if cols is None else ws[at:at + rows * cols].view(rows, cols)
+
+
+def _param_partials(dW, dvec):
+    """The landmark / mu networks' per-(b,h) gradient partials W [BH, 2 d d], v [BH, 6 d] -> entries for the terminal sum."""
+    return [("mlp_W", dW, None), ("mlp_v", dvec, None)]
+
+
+def _eva_saved_is_composite(saved_list):
+    """TWO tensors after `out` = eva_fwd_impl (just below) ran ea_eva_layer_fwd: the count crosses save_for_backward and the dispatcher."""
+    return len(saved_list) == 2
 
 
 def eva_fwd_impl(qkv5, bias, noise, mask_u8, keep, icfg, fcfg, adaptive_proj, mlp_params, pooled=None, composite=False):
@@ -541,40 +565,36 @@ def eva_fwd_impl(qkv5, bias, noise, mask_u8, keep, icfg, fcfg, adaptive_proj, ml
     fcfg = [mu_scale, keep_scale].  -> [out, bias_padded, lse, qmean, kmean, omega, beta, rf_k_bar, noise, lmk_saved, zhat, rstd]
     (absent tensors are empty).
     composite (direct calls only, never through the dispatcher): ONE C-ABI call (ea_eva_layer_fwd) on a caller-owned
-    workspace where the geometry allows it -> [out, bias_padded, saved workspace]; pooled is then (ws,) -- the chunk means
-    already written into that workspace by the projection kernel -- or None."""
+    workspace where the geometry allows it -> [out, bias_padded, saved workspace]; pooled (direct calls only): a Pooled --
+    the chunk means the projection kernel already wrote, into that workspace or as two tensors -- or None."""
     global LAST_LMK_GEOM
     nv.require_cuda(qkv5, "qkv")
     B, N, _, h, d = qkv5.shape
     dev = qkv5.device
-    if composite:
-        lcfg, sizes = _eva_layer_cfg_dims(B, h, d, nv.io_dtype(qkv5), icfg, fcfg, adaptive_proj, bias is not None,
-                                          mask_u8 is not None or keep is not None)
-        if pooled is not None and (len(pooled) == 1) != (lcfg is not None):
-            raise RuntimeError("eva_fwd: chunk means prepared for the other launch path")
-        if lcfg is not None:
-            need_grad = len(icfg) < 9 or bool(icfg[8])
-            q, k, v = _qkv_views(qkv5)
-            tq, tk, tv = nv.t4(q), nv.t4(k), nv.t4(v)
-            ws = pooled[0] if pooled is not None else torch.empty(sizes[0], dtype=torch.float32, device=dev)
-            out = torch.empty((B, N, h, d), dtype=qkv5.dtype, device=dev)
-            to = nv.t4(out.permute(0, 2, 1, 3))
-            geom = _eva_cfg(qkv5, icfg, fcfg, adaptive_proj)[0]
-            bias_p = _bias_padded(bias, geom)
-            noise_c = None if noise is None else noise.float().contiguous()
-            ps = [_f32c(p) for p in mlp_params]
-            LAST_LMK_GEOM = (B * h, int(icfg[6]), int(icfg[6]), d, 1, 0, 1)
-            nv.call("ea_eva_layer_fwd", ctypes.byref(lcfg), ctypes.byref(tq), ctypes.byref(tk), ctypes.byref(tv),
-                    nv.ptr(bias_p), nv.ptr(noise_c), _param_ptrs(ps), ctypes.byref(to), nv.ptr(ws),
-                    int(need_grad) | (2 if pooled is not None else 0), nv.stream())
-            return [out, _e(bias_p, ws), ws]
-    geom, L, mu_scale, keep_scale, fused_mu = _eva_cfg(qkv5, icfg, fcfg, adaptive_proj)
+    lcfg, sizes = _eva_layer_cfg_dims(B, h, d, nv.io_dtype(qkv5), icfg, fcfg, adaptive_proj, bias is not None,
+                                      mask_u8 is not None or keep is not None) if composite else (None, None)
+    if pooled is not None and (pooled.ws is not None) != (lcfg is not None):
+        raise RuntimeError("eva_fwd: chunk means prepared for the other launch path")
     need_grad = len(icfg) < 9 or bool(icfg[8])
     q, k, v = _qkv_views(qkv5)
     tq, tk, tv = nv.t4(q), nv.t4(k), nv.t4(v)
+    if lcfg is not None:
+        ws = pooled.ws if pooled is not None else torch.empty(sizes.n_saved, dtype=torch.float32, device=dev)
+        out = torch.empty((B, N, h, d), dtype=qkv5.dtype, device=dev)
+        to = nv.t4(out.permute(0, 2, 1, 3))
+        geom = _eva_cfg(qkv5, icfg, fcfg, adaptive_proj)[0]
+        bias_p = _bias_padded(bias, geom)
+        noise_c = None if noise is None else noise.float().contiguous()
+        ps = [_f32c(p) for p in mlp_params]
+        LAST_LMK_GEOM = (B * h, int(icfg[6]), int(icfg[6]), d, 1, 0, 1)
+        nv.call("ea_eva_layer_fwd", ctypes.byref(lcfg), ctypes.byref(tq), ctypes.byref(tk), ctypes.byref(tv),
+                nv.ptr(bias_p), nv.ptr(noise_c), _param_ptrs(ps), ctypes.byref(to), nv.ptr(ws),
+                int(need_grad) | (2 if pooled is not None else 0), nv.stream())
+        return [out, _e(bias_p, ws), ws]                  # composite: _eva_saved_is_composite
+    geom, L, mu_scale, keep_scale, fused_mu = _eva_cfg(qkv5, icfg, fcfg, adaptive_proj)
     if pooled is not None:
         # (direct calls only) the chunk means came out of the projection kernel (ea_linear_w32_pool, LinearPoolFn)
-        qmean, kmean = pooled[0].view(B, h, L, d), pooled[1].view(B, h, L, d)
+        qmean, kmean = pooled.pq.view(B, h, L, d), pooled.pk.view(B, h, L, d)
     else:
         qmean = torch.empty((B, h, L, d), dtype=torch.float32, device=dev)
         kmean = torch.empty_like(qmean)
@@ -634,59 +654,56 @@ def eva_fwd_impl(qkv5, bias, noise, mask_u8, keep, icfg, fcfg, adaptive_proj, ml
     return [out, _e(bias_p, e), lse, qmean, kmean, omega, beta, rf_k_bar, _e(saved, e), _e(zhat, e), _e(rstd, e)]
 
 
-def eva_bwd_impl(dout, qkv5, mask_u8, keep, noise, out, saved_list, icfg, fcfg, adaptive_proj, bias_cols, mlp_params,
-                 defer_param_sums=False, defer_chunk_mean=False):
+def eva_bwd_impl(dout, qkv5, mask_u8, keep, noise, out, saved_list, icfg, fcfg, adaptive_proj, bias_cols, mlp_params):
     """torch.ops.ea.eva_bwd -> [dqkv, dbias | empty, *parameter gradients (fp32, in the order of mlp_params)]."""
-    if len(saved_list) == 2:
-        # the forward went through ea_eva_layer_fwd: (bias_padded | empty, saved workspace)
+    g = _eva_backward(dout, qkv5, mask_u8, keep, noise, out, saved_list, icfg, fcfg, adaptive_proj, bias_cols, mlp_params)
+    return [g.dqkv, _e(g.dbias, saved_list[1])] + g.params
+
+
+def _eva_backward(dout, qkv5, mask_u8, keep, noise, out, saved_list, icfg, fcfg, adaptive_proj, bias_cols, mlp_params,
+                  defer_param_sums=False, defer_chunk_mean=False):
+    """The EVA core's backward -> CoreGrads.  defer_param_sums: the per-(b,h) partials of the mu networks' (composite: and the bias)
+    gradients wait for the caller's terminal sum; defer_chunk_mean (composite only, round 5): ea_linear_dgrad_finish adds
+    d(chunk mean) / r^2 to dq, dk on its way through the gradient rows."""
+    B, N, _, h, d = qkv5.shape
+    noise_c = None if noise is None else noise.float().contiguous()
+    dqkv5 = torch.empty_like(qkv5)
+    if _eva_saved_is_composite(saved_list):
         bias_p, ws = _opt(saved_list[0]), saved_list[1]
-        B, N, _, h, d = qkv5.shape
         lcfg, sizes = _eva_layer_cfg_dims(B, h, d, nv.io_dtype(qkv5), icfg, fcfg, adaptive_proj, bias_p is not None, False)
         if lcfg is None:
-            raise RuntimeError("eva_bwd: a composite workspace was saved for a geometry ea_eva_layer_ws rejects")
-        dev = qkv5.device
+            raise RuntimeError("eva_bwd: a composite workspace was saved for a geometry ea_eva_layer_plan rejects")
         dout = _rows_contiguous(dout)
-        dqkv5 = torch.empty_like(qkv5)
         q, k, v = _qkv_views(qkv5)
         dq, dk, dv = _qkv_views(dqkv5)
         ts = [nv.t4(t) for t in (q, k, v, out.permute(0, 2, 1, 3), dout.permute(0, 2, 1, 3), dq, dk, dv)]
-        tmp = torch.empty(sizes[1], dtype=torch.float32, device=dev)
-        noise_c = None if noise is None else noise.float().contiguous()
+        tmp = torch.empty(sizes.n_bwd_tmp, dtype=torch.float32, device=qkv5.device)
         ps = [_f32c(p) for p in mlp_params]
         # deferred sums: the bias-gradient partials join the caller's terminal reductions too (one launch for all of them)
         defer_bias = bool(defer_param_sums and bias_p is not None)
         dbias = None if (bias_p is None or defer_bias) else torch.empty_like(bias_p)
-        dpar = None if defer_param_sums else torch.empty(2 * d * d + 6 * d, dtype=torch.float32, device=dev)
-        # defer_chunk_mean (direct calls only, round 5): the chunk-mean backward is left to ea_linear_dgrad_finish, which adds
-        # d(chunk mean) / r^2 to dq, dk on its way through the gradient rows (the last element of the result says where they are)
-        nv.call("ea_eva_layer_bwd2", ctypes.byref(lcfg), ctypes.byref(ts[0]), ctypes.byref(ts[1]), ctypes.byref(ts[2]),
+        dpar = None if defer_param_sums else torch.empty(2 * d * d + 6 * d, dtype=torch.float32, device=qkv5.device)
+        nv.call("ea_eva_layer_bwd", ctypes.byref(lcfg), ctypes.byref(ts[0]), ctypes.byref(ts[1]), ctypes.byref(ts[2]),
                 nv.ptr(bias_p), nv.ptr(noise_c), _param_ptrs(ps), ctypes.byref(ts[3]), ctypes.byref(ts[4]), ctypes.byref(ts[5]),
                 ctypes.byref(ts[6]), ctypes.byref(ts[7]), nv.ptr(ws), nv.ptr(tmp), nv.ptr(dbias), nv.ptr(dpar),
                 1 if defer_chunk_mean else 0, nv.stream())
         if dbias is not None:
             dbias = dbias[..., :bias_cols].contiguous()
-        BH = B * h
-        fin_ = []
+        BH, fin = B * h, None
         if defer_chunk_mean:
             Lc = (lcfg.gh // lcfg.chunk) * (lcfg.gw // lcfg.chunk)
-            fin_ = [("finish", dict(B=B, gh=lcfg.gh, gw=lcfg.gw, r=lcfg.chunk, C=Lc, scale=float(lcfg.scale), uq=None, qbar=None,
-                                    lse_t=None, dpq=tmp[sizes[8]:sizes[8] + BH * Lc * d], dpk=tmp[sizes[9]:sizes[9] + BH * Lc * d]))]
-        if defer_param_sums:
-            o_dW, o_dvec = sizes[4], sizes[5]
-            extra = ()
-            if defer_bias:
-                o_db, rows_db, n_db = sizes[6], sizes[7], bias_p.numel()
-                extra = (tmp[o_db:o_db + rows_db * n_db].view(rows_db, n_db), tuple(bias_p.shape))
-            return [dqkv5, _e(dbias, ws), ("partials", tmp[o_dW:o_dW + BH * 2 * d * d].view(BH, 2 * d * d),
-                                          tmp[o_dvec:o_dvec + BH * 6 * d].view(BH, 6 * d)) + extra] + fin_
-        return [dqkv5, _e(dbias, ws)] + _mlp_grads(dpar[:2 * d * d], dpar[2 * d * d:], d) + fin_
+            fin = dict(B=B, gh=lcfg.gh, gw=lcfg.gw, r=lcfg.chunk, C=Lc, scale=float(lcfg.scale), uq=None, qbar=None, lse_t=None,
+                       dpq=_ws_rows(tmp, sizes.bwd_dqmean, BH * Lc * d), dpk=_ws_rows(tmp, sizes.bwd_dkmean, BH * Lc * d))
+        if not defer_param_sums:
+            return CoreGrads(dqkv5, dbias, _mlp_grads(dpar[:2 * d * d], dpar[2 * d * d:], d), (), fin)
+        parts = _param_partials(_ws_rows(tmp, sizes.bwd_dW, BH, 2 * d * d), _ws_rows(tmp, sizes.bwd_dvec, BH, 6 * d))
+        if defer_bias:
+            parts.append(("dbias", _ws_rows(tmp, sizes.bwd_dbias_part, sizes.dbias_part_rows, bias_p.numel()), tuple(bias_p.shape)))
+        return CoreGrads(dqkv5, dbias, None, parts, fin)
     if defer_chunk_mean:
         raise RuntimeError("eva_bwd: defer_chunk_mean needs the composite entry points")
     geom, L, mu_scale, keep_scale, fused_mu = _eva_cfg(qkv5, icfg, fcfg, adaptive_proj)
     bias_p, lse, qmean, kmean, omega, beta, rf_k_bar, saved, zhat, rstd = [_opt(t) for t in saved_list]
-    noise_c = None if noise is None else noise.float().contiguous()
-    B, N, _, h, d = qkv5.shape
-    dqkv5 = torch.empty_like(qkv5)
     d_rfk, d_beta, dbias = _window_bwd(geom, qkv5, rf_k_bar, beta, bias_p, mask_u8, out,
                                        _rows_contiguous(dout), lse, dqkv5, keep, keep_scale)
     q, k, v = _qkv_views(qkv5)
@@ -711,9 +728,9 @@ def eva_bwd_impl(dout, qkv5, mask_u8, keep, noise, out, saved_list, icfg, fcfg, 
                 None, None, nv.ptr(dqm), nv.ptr(dkm), nv.ptr(dW), nv.ptr(dvec), nv.ptr(saved), nv.stream())
         nv.call("ea_eva_chunk_mean_bwd", ctypes.byref(geom), nv.ptr(dqm), nv.ptr(dkm),
                 nv.ptr(mask_u8), ctypes.byref(tdq), ctypes.byref(tdk), nv.stream())
-        if defer_param_sums:                       # (direct calls only) the per-(b,h) partials, still to be added up
-            return [dqkv5, _e(dbias, lse), ("partials", dW.view(lg.BH, -1), dvec.view(lg.BH, -1))]
-        return [dqkv5, _e(dbias, lse)] + _mlp_grads(*colsum2_f32(dW.view(lg.BH, -1), dvec.view(lg.BH, -1)), d)
+        if defer_param_sums:                       # the per-(b,h) partials, still to be added up
+            return CoreGrads(dqkv5, dbias, None, _param_partials(dW.view(lg.BH, -1), dvec.view(lg.BH, -1)), None)
+        return CoreGrads(dqkv5, dbias, _mlp_grads(*colsum2_f32(dW.view(lg.BH, -1), dvec.view(lg.BH, -1)), d), (), None)
     # mu networks backward (ea_rows_mlp_bwd): dz, dx = d(chunk means), per-workgroup dW partials
     # and the feed buffer whose column sums are the bias / gamma / beta gradients
     sides = 1 if adaptive_proj == "none" else 2
@@ -749,7 +766,7 @@ def eva_bwd_impl(dout, qkv5, mask_u8, keep, noise, out, saved_list, icfg, fcfg, 
     raw = []
     for i in range(sides):
         raw += [dW[i], vec[0, i]] + ([vec[1, i], vec[2, i]] if ln else [])
-    return [dqkv5, _e(dbias, lse)] + raw
+    return CoreGrads(dqkv5, dbias, raw, (), None)
 
 
 class EvaAttnFn(torch.autograd.Function):
@@ -766,7 +783,7 @@ class EvaAttnFn(torch.autograd.Function):
         keep, keep_scale = cfg[9:11] if len(cfg) > 9 else (None, 1.0)
         icfg = _geo(attn_2d, seq_shape, window, ext) + [int(chunk), int(L), int(causal), int(any(ctx.needs_input_grad))]
         fcfg = [float(mu_scale), float(keep_scale)]
-        pooled = cfg[-1][1:] if (isinstance(cfg[-1], tuple) and cfg[-1][:1] == ("pooled",)) else None
+        pooled = Pooled(None, *cfg[-1][1:]) if (isinstance(cfg[-1], tuple) and cfg[-1][:1] == ("pooled",)) else None
         direct = _DIRECT and not torch.compiler.is_compiling() and torch._C._len_torch_dispatch_stack() == 0
         # a TableBias anywhere in cfg (round 6; direct calls only): `bias` is the TABLE ([rows, h] or [rows, 1]) and the dense
         # bias is built from it / its gradient taken back to it in one launch each way
@@ -798,24 +815,24 @@ class EvaAttnFn(torch.autograd.Function):
         qkv5, mask_u8, keep, noise, out, *rest = ctx.saved_tensors
         saved, params = rest[:ctx.nsaved], rest[ctx.nsaved:]
         icfg, fcfg, adaptive_proj, bias_cols = ctx.cfg
-        if len(saved) == 2:             # composite workspace: only a direct forward saves one
-            g = eva_bwd_impl(dout, qkv5, mask_u8, keep, noise, out, list(saved), icfg, fcfg, adaptive_proj, bias_cols, list(params))
+        args = (dout, qkv5, mask_u8, keep, noise, out, list(saved), icfg, fcfg, adaptive_proj, bias_cols, list(params))
+        if _eva_saved_is_composite(saved):             # only a direct forward saves a composite workspace
+            g = _eva_backward(*args)
         elif ctx.tb is not None and ctx.tb_heads == 1 and BIAS_HEAD_SUM:
             # (a TableBias means a direct call: the implementation runs right here, in this thread)
             _BIAS_HEAD_SUM.on = True
             try:
-                g = eva_bwd_impl(dout, qkv5, mask_u8, keep, noise, out, list(saved), icfg, fcfg, adaptive_proj, bias_cols,
-                                 list(params))
+                g = _eva_backward(*args)
             finally:
                 _BIAS_HEAD_SUM.on = False
         else:
-            g = _ea_op("eva_bwd", eva_bwd_impl, dout, qkv5, mask_u8, keep, noise, out, list(saved), icfg, fcfg, adaptive_proj,
-                       bias_cols, list(params))
-        pgrads = [t.to(dt) for t, dt in zip(g[2:], ctx.pdtypes)]
-        dbias = _opt(g[1])
+            g = _ea_op("eva_bwd", eva_bwd_impl, *args)
+            g = CoreGrads(g[0], _opt(g[1]), g[2:], (), None)
+        pgrads = [t.to(dt) for t, dt in zip(g.params, ctx.pdtypes)]
+        dbias = g.dbias
         if ctx.tb is not None and dbias is not None:
             dbias = ctx.tb.grad(dbias, ctx.tb_heads)
-        return (g[0], dbias, None, None, None) + tuple(pgrads)
+        return (g.dqkv, dbias, None, None, None) + tuple(pgrads)
 
 
 USE_EVA_MODULE_FN = os.environ.get("EA_EVA_MODULE_FN", "1") == "1"
@@ -1364,16 +1381,16 @@ _LARA_LAYER_CFG = {}
 
 
 def _lara_layer_cfg_dims(B, h, d, io, icfg, fcfg):
-    """(ea_lara_layer, [saved, forward scratch, backward scratch floats; offsets of pq, pk, dW partials, dvec partials]) or
-    (None, None) -- a pure function of the geometry, memoised (seven host calls per query otherwise, twice per eager step)."""
+    """(ea_lara_layer, ea_lara_layer_sizes: the workspace plan, read by field name) or (None, None) -- a pure function of the
+    geometry, memoised (a host call per query otherwise, twice per eager step)."""
     key = (B, h, d, io) + tuple(int(v) for v in icfg[:7]) + tuple(float(v) for v in fcfg)
     hit = _LARA_LAYER_CFG.get(key)
     if hit is None:
         H, W, r, has_mlp, mixed, mis, dup = key[4:11]
         kappa, scale = key[11:13]
         cfg = nv.ea_lara_layer(B, h, d, io, H, W, r, has_mlp, mixed, mis, dup, kappa, scale)
-        sizes = [int(nv.lib().ea_lara_layer_ws(ctypes.byref(cfg), w)) for w in range(12)]   # 7-11: operands of the deferred finish
-        hit = (cfg, sizes) if min(sizes) >= 0 else (None, None)
+        sizes = nv.ea_lara_layer_sizes()
+        hit = (cfg, sizes) if nv.lib().ea_lara_layer_plan(ctypes.byref(cfg), ctypes.byref(sizes)) == 0 else (None, None)
         if len(_LARA_LAYER_CFG) < 256:
             _LARA_LAYER_CFG[key] = hit
     return hit
@@ -1392,6 +1409,11 @@ def _param_ptrs(ps):
     return arr
 
 
+def _lara_saved_is_composite(saved_list):
+    """ONE tensor after `out` = lara_fwd_impl (just below) ran a composite entry: the count crosses save_for_backward and the dispatcher."""
+    return len(saved_list) == 1
+
+
 def lara_fwd_impl(qkv5, mask_u8, noise, icfg, fcfg, params, pooled=None, proj=None):
     """torch.ops.ea.lara_fwd: uniform r x r pooling of q, k -> fused landmark pipeline -> estimator.
     icfg = [H, W, r, has_mlp, mixed, mis, dup(, keep_for_backward = 1)], fcfg = [kappa, scale], params = (Wq,
@@ -1399,24 +1421,23 @@ def lara_fwd_impl(qkv5, mask_u8, noise, icfg, fcfg, params, pooled=None, proj=No
     C <= 64: ONE composite C-ABI call (ea_lara_layer_fwd) on two workspaces -> [out, saved workspace].
     Otherwise the step-by-step launch sequence -> [out, omega, qrows, bhv, cst, kv, lse_k, lse_t, pq, pk, noise, lmk_saved, tokst]
     (absent tensors are empty).
-    pooled (direct calls only, never through the dispatcher): what project_qkv_pooled returned -- the pooled q / k rows
-    already computed by the projection kernel, either inside the composite workspace (ws, None, None) or as two tensors
-    (None, pq, pk): the pooling pass is skipped.
+    pooled (direct calls only, never through the dispatcher): a Pooled -- the pooled q / k rows already computed by the
+    projection kernel, inside the composite workspace or as two tensors: the pooling pass is skipped.
     proj (direct calls only) = [w16p, bias32, y2]: the output projection y2 [B*N, h*d] = out w16p^T + bias is written by the
     combine pass (ea_lara_layer_fwd_proj / ea_lara_out_proj_fwd_merge); where the library declines, by ea_linear after it."""
     global LAST_LMK_GEOM
     nv.require_cuda(qkv5, "qkv")
     lcfg, sizes = _lara_layer_cfg(qkv5, icfg, fcfg) if _lara_use_composite() else (None, None)
     need_grad = len(icfg) < 8 or bool(icfg[7])
-    if pooled is not None and (pooled[0] is not None) != (lcfg is not None):
+    if pooled is not None and (pooled.ws is not None) != (lcfg is not None):
         raise RuntimeError("lara_fwd: pooled rows prepared for the other launch path")
+    B, N, _, h, d = qkv5.shape
+    BH, dev = B * h, qkv5.device
     if lcfg is not None:
-        B, N, _, h, d = qkv5.shape
-        dev = qkv5.device
         q, k, v = _qkv_views(qkv5)
         tq, tk, tv = nv.t4(q), nv.t4(k), nv.t4(v)
-        ws = pooled[0] if pooled is not None else torch.empty(sizes[0], dtype=torch.float32, device=dev)
-        tmp = torch.empty(sizes[1], dtype=torch.float32, device=dev)
+        ws = pooled.ws if pooled is not None else torch.empty(sizes.n_saved, dtype=torch.float32, device=dev)
+        tmp = torch.empty(sizes.n_fwd_tmp, dtype=torch.float32, device=dev)
         out = torch.empty((B, N, h, d), dtype=qkv5.dtype, device=dev)
         to = nv.t4(out.permute(0, 2, 1, 3))
         noise_c = None if noise is None else noise.float().contiguous()
@@ -1429,19 +1450,17 @@ def lara_fwd_impl(qkv5, mask_u8, noise, icfg, fcfg, params, pooled=None, proj=No
                                               ctypes.byref(tk), ctypes.byref(tv), nv.ptr(mask_u8), nv.ptr(noise_c), pp, ctypes.byref(to),
                                               nv.ptr(ws), nv.ptr(tmp), keep, nv.ptr(proj[0]), nv.ptr(proj[1]), nv.ptr(proj[2]),
                                               proj[2].stride(0), nv.stream()):
-            return [out, ws]
+            return [out, ws]                              # composite: _lara_saved_is_composite
         nv.call("ea_lara_layer_fwd", ctypes.byref(lcfg), ctypes.byref(tq), ctypes.byref(tk), ctypes.byref(tv),
                 nv.ptr(mask_u8), nv.ptr(noise_c), pp, ctypes.byref(to), nv.ptr(ws), nv.ptr(tmp), keep, nv.stream())
         if proj is not None:
             _lara_proj_fallback(out, proj)
         return [out, ws]
     (H, W, r, has_mlp, mixed, mis, dup, L, C), pgeom, lg, geom = _lara_cfg(qkv5, icfg, fcfg)
-    B, N, _, h, d = qkv5.shape
-    BH, dev = B * h, qkv5.device
     q, k, _ = _qkv_views(qkv5)
     tq, tk = nv.t4(q), nv.t4(k)
     if pooled is not None:
-        pq, pk = pooled[1].view(BH, L, d), pooled[2].view(BH, L, d)
+        pq, pk = pooled.pq.view(BH, L, d), pooled.pk.view(BH, L, d)
     else:
         pq = torch.empty((BH, L, d), dtype=torch.float32, device=dev)
         pk = torch.empty_like(pq)
@@ -1463,62 +1482,57 @@ def lara_fwd_impl(qkv5, mask_u8, noise, icfg, fcfg, params, pooled=None, proj=No
     return [out, omega, _e(qrows, e), _e(bhv, e), cst, kv, lse_k, _e(lse_t, e), pq, pk, _e(saved, e), _e(tokst, e)]
 
 
-def lara_bwd_impl(dout, qkv5, mask_u8, noise, saved_list, icfg, fcfg, params, defer_param_sums=False, defer_finish=False):
+def lara_bwd_impl(dout, qkv5, mask_u8, noise, saved_list, icfg, fcfg, params):
     """torch.ops.ea.lara_bwd -> [dqkv, *parameter gradients (fp32, in the order of params)].  saved_list is what lara_fwd
     returned after `out`: the composite workspace (one tensor -> ea_lara_layer_bwd) or the step-by-step tensors."""
-    if len(saved_list) == 1:
+    g = _lara_backward(dout, qkv5, mask_u8, noise, saved_list, icfg, fcfg, params)
+    return [g.dqkv] + g.params
+
+
+def _lara_backward(dout, qkv5, mask_u8, noise, saved_list, icfg, fcfg, params, defer_param_sums=False, defer_finish=False):
+    """The 2-D pooled LARA core's backward -> CoreGrads (dbias: None).  defer_param_sums: the per-(b,h) partials of the generator
+    parameters' gradients wait for the caller's terminal sum; defer_finish (C <= 64, round 5): ea_linear_dgrad_finish applies the
+    softmax-over-sequence correction of dq and the pooling terms of dq / dk on its way through the gradient rows."""
+    B, N, _, h, d = qkv5.shape
+    BH, dev = B * h, qkv5.device
+    noise_c = None if noise is None else noise.float().contiguous()
+    ps = [_f32c(t) for t in params]
+    dqkv5 = torch.empty_like(qkv5)
+    if _lara_saved_is_composite(saved_list):
         lcfg, sizes = _lara_layer_cfg(qkv5, icfg, fcfg)          # pure geometry / size query: valid whenever the forward's was
         if lcfg is None:
-            raise RuntimeError("lara_bwd: a composite workspace was saved for a geometry ea_lara_layer_ws rejects")
-        B, N, _, h, d = qkv5.shape
-        dev = qkv5.device
+            raise RuntimeError("lara_bwd: a composite workspace was saved for a geometry ea_lara_layer_plan rejects")
         ws = saved_list[0]
         dout = _rows_contiguous(dout)
-        dqkv5 = torch.empty_like(qkv5)
         q, k, v = _qkv_views(qkv5)
         dq, dk, dv = _qkv_views(dqkv5)
         ts = [nv.t4(t) for t in (q, k, v, dout.permute(0, 2, 1, 3), dq, dk, dv)]
-        tmp = torch.empty(sizes[2], dtype=torch.float32, device=dev)
-        noise_c = None if noise is None else noise.float().contiguous()
-        ps = [_f32c(t) for t in params]
+        tmp = torch.empty(sizes.n_bwd_tmp, dtype=torch.float32, device=dev)
         pp = _param_ptrs(ps) if ps else None
         defer = bool(defer_param_sums and ps)
         dpar = torch.empty(2 * d * d + 6 * d, dtype=torch.float32, device=dev) if (ps and not defer) else None
-        # defer_finish (direct calls only, round 5): the finish pass is left to ea_linear_dgrad_finish, which applies the
-        # softmax-over-sequence correction of dq and the pooling terms of dq / dk on its way through the gradient rows
-        nv.call("ea_lara_layer_bwd2", ctypes.byref(lcfg), ctypes.byref(ts[0]), ctypes.byref(ts[1]), ctypes.byref(ts[2]),
+        nv.call("ea_lara_layer_bwd", ctypes.byref(lcfg), ctypes.byref(ts[0]), ctypes.byref(ts[1]), ctypes.byref(ts[2]),
                 nv.ptr(mask_u8), nv.ptr(noise_c), pp, ctypes.byref(ts[3]), ctypes.byref(ts[4]), ctypes.byref(ts[5]),
                 ctypes.byref(ts[6]), nv.ptr(ws), nv.ptr(tmp), nv.ptr(dpar), 1 if defer_finish else 0, nv.stream())
-        grads = [dqkv5]
+        fin = None
         if defer_finish:
-            BH, L = B * h, (lcfg.gh // lcfg.pool_r) * (lcfg.gw // lcfg.pool_r)
+            L = (lcfg.gh // lcfg.pool_r) * (lcfg.gw // lcfg.pool_r)
             C = L * (2 if lcfg.dup else 1)
             opt = lcfg.mis == 0
             fin = dict(B=B, gh=lcfg.gh, gw=lcfg.gw, r=lcfg.pool_r, C=C, scale=float(lcfg.scale),
-                       uq=tmp[sizes[7]:sizes[7] + BH * C * d] if opt else None,
-                       dpq=tmp[sizes[8]:sizes[8] + BH * L * d], dpk=tmp[sizes[9]:sizes[9] + BH * L * d],
-                       qbar=ws[sizes[10]:sizes[10] + BH * C * d] if opt else None,
-                       lse_t=ws[sizes[11]:sizes[11] + BH * C] if opt else None)
-            grads.append(("finish", fin))
-        if defer:
-            # (direct calls only) the per-(b,h) partials, still to be added up: [B*h, 2 d d], [B*h, 6 d]
-            o_dW, o_dvec = sizes[5], sizes[6]
-            BH = B * h
-            return grads[:1] + [("partials", tmp[o_dW:o_dW + BH * 2 * d * d].view(BH, 2 * d * d),
-                                 tmp[o_dvec:o_dvec + BH * 6 * d].view(BH, 6 * d))] + grads[1:]
-        if ps:
-            grads = grads[:1] + _mlp_grads(dpar[:2 * d * d], dpar[2 * d * d:], d) + grads[1:]
-        return grads
+                       uq=_ws_rows(tmp, sizes.bwd_uq, BH * C * d) if opt else None,
+                       dpq=_ws_rows(tmp, sizes.bwd_dpq, BH * L * d), dpk=_ws_rows(tmp, sizes.bwd_dpk, BH * L * d),
+                       qbar=_ws_rows(ws, sizes.saved_qrows, BH * C * d) if opt else None,
+                       lse_t=_ws_rows(ws, sizes.saved_lse_t, BH * C) if opt else None)
+        if defer:                      # the per-(b,h) partials, still to be added up: [B*h, 2 d d], [B*h, 6 d]
+            parts = _param_partials(_ws_rows(tmp, sizes.bwd_dW, BH, 2 * d * d), _ws_rows(tmp, sizes.bwd_dvec, BH, 6 * d))
+            return CoreGrads(dqkv5, None, None, parts, fin)
+        return CoreGrads(dqkv5, None, _mlp_grads(dpar[:2 * d * d], dpar[2 * d * d:], d) if ps else [], (), fin)
     (H, W, r, has_mlp, mixed, mis, dup, L, C), pgeom, lg, geom = _lara_cfg(qkv5, icfg, fcfg)
     if defer_finish and C > 64:
         raise RuntimeError("lara_bwd: defer_finish needs C <= 64 samples")
     omega, qrows, bhv, cst, kv, lse_k, lse_t, pq, pk, saved, tokst = [_opt(t) for t in saved_list]
-    noise_c = None if noise is None else noise.float().contiguous()
-    B, N, _, h, d = qkv5.shape
-    BH, dev = B * h, qkv5.device
-    ps = [_f32c(t) for t in params]
     dout = dout.contiguous()
-    dqkv5 = torch.empty_like(qkv5)
     d_omega, d_qrows, d_bhv, d_lp, uq = _lara_bwd_core(geom, qkv5, mask_u8, dout, dqkv5, omega, qrows, bhv,
                                                        cst, kv, lse_k, lse_t, tokst, want_parts=True)
     dpq = torch.empty_like(pq)
@@ -1537,18 +1551,15 @@ def lara_bwd_impl(dout, qkv5, mask_u8, noise, saved_list, icfg, fcfg, params, de
         nv.call("ea_lara_landmarks_bwd", ctypes.byref(lg), nv.ptr(pq), nv.ptr(pk), *pp, nv.ptr(noise_c),
                 nv.ptr(d_omega), nv.ptr(d_qrows), nv.ptr(d_bhv), nv.ptr(d_lp), nv.ptr(dpq), nv.ptr(dpk),
                 nv.ptr(dW), nv.ptr(dvec), nv.ptr(saved), nv.stream())
-    fin_ = []
+    fin = None
     if defer_finish:
-        fin_ = [("finish", dict(B=B, gh=H, gw=W, r=r, C=C, scale=float(fcfg[1]), uq=uq, dpq=dpq, dpk=dpk,
-                                qbar=qrows if uq is not None else None, lse_t=lse_t if uq is not None else None))]
+        fin = dict(B=B, gh=H, gw=W, r=r, C=C, scale=float(fcfg[1]), uq=uq, dpq=dpq, dpk=dpk,
+                   qbar=qrows if uq is not None else None, lse_t=lse_t if uq is not None else None)
     else:
         _lara_finish(geom, qkv5, dqkv5, qrows, uq, lse_t, dpq, dpk, (r, H, W))
-    grads = [dqkv5]
     if has_mlp and defer_param_sums:
-        return grads + [("partials", dW.view(BH, -1), dvec.view(BH, -1))] + fin_
-    if has_mlp:
-        grads += _mlp_grads(*colsum2_f32(dW.view(BH, -1), dvec.view(BH, -1)), d)
-    return grads + fin_
+        return CoreGrads(dqkv5, None, None, _param_partials(dW.view(BH, -1), dvec.view(BH, -1)), fin)
+    return CoreGrads(dqkv5, None, _mlp_grads(*colsum2_f32(dW.view(BH, -1), dvec.view(BH, -1)), d) if has_mlp else [], (), fin)
 
 
 class LaraPooledFn(torch.autograd.Function):
@@ -1781,15 +1792,15 @@ class GraphCore:
         return (dqkv5 if dqkv5.is_contiguous() else dqkv5.contiguous()), tuple(extra)
 
 
-def _pooled_rows(sizes, i, BH, L, d, device):
-    """Where a projection kernel leaves the pooled q / k rows [BH, L, d] (fp32) -> (ws | None, pq, pk): inside a fresh workspace
-    of a composite entry (`sizes`, its size list: workspace floats, the rows' offsets at i and i + 1), or (None) on their own."""
-    if sizes is None:
+def _pooled_rows(where, BH, L, d, device):
+    """Where a projection kernel leaves the pooled q / k rows [BH, L, d] (fp32) -> (Pooled for the core's forward, pq, pk): inside
+    a fresh `saved` workspace of a composite entry, where = (n_saved, the rows' two offsets) of its plan, or (None) on their own."""
+    if where is None:
         pq = torch.empty((BH, L, d), dtype=torch.float32, device=device)
-        return None, pq, torch.empty_like(pq)
-    ws = torch.empty(sizes[0], dtype=torch.float32, device=device)
-    n = BH * L * d
-    return ws, ws[sizes[i]:sizes[i] + n], ws[sizes[i + 1]:sizes[i + 1] + n]
+        pk = torch.empty_like(pq)
+        return Pooled(None, pq, pk), pq, pk
+    ws = torch.empty(where[0], dtype=torch.float32, device=device)
+    return Pooled(ws, None, None), _ws_rows(ws, where[1], BH * L * d), _ws_rows(ws, where[2], BH * L * d)
 
 
 def _project_qkv_grid(x2, wq, bq32, cdtype, want, need_dx, w192, grid, pq, pk):
@@ -1802,11 +1813,6 @@ def _project_qkv_grid(x2, wq, bq32, cdtype, want, need_dx, w192, grid, pq, pk):
     w16 = torch.empty(tuple(wq.shape), dtype=cdtype, device=x2.device) if need_dx else None
     y, xc = project_qkv_pooled(x2, wq, bq32, cdtype, want, *grid, pq, pk, w_cast=w16)
     return y, xc, w16
-
-
-def _mlp_partials(t):
-    """('partials', W [BH, 2 d d], v [BH, 6 d], ...) of eva_bwd_impl / lara_bwd_impl -> entries for the node's terminal sum."""
-    return [("mlp_W", t[1], None), ("mlp_v", t[2], None)]
 
 
 class EvaCore:
@@ -1837,8 +1843,9 @@ class EvaCore:
         if not (attn_2d and ext == 0 and self.mask_u8 is None
                 and proj_pool_supported(x2, wq, cdtype, B, seq_shape[0], seq_shape[1], chunk, heads)):
             return None
-        ws, pq, pk = _pooled_rows(self.sizes, 2, B * heads, L, d, x2.device)     # (composite: straight into the entry's workspace)
-        self.pooled = (pq, pk) if ws is None else (ws,)
+        pl = self.sizes                                              # (composite: straight into the entry's workspace)
+        where = None if pl is None else (pl.n_saved, pl.saved_qmean, pl.saved_kmean)
+        self.pooled, pq, pk = _pooled_rows(where, B * heads, L, d, x2.device)
         return _project_qkv_grid(x2, wq, bq32, cdtype, want, need_dx, w192, (B, seq_shape[0], seq_shape[1], chunk), pq, pk)
 
     def fwd(self, qkv5, inputs):
@@ -1850,15 +1857,10 @@ class EvaCore:
 
     def bwd(self, dout, qkv5, out, saved, defer, fin_ok):
         saved, params = saved[:self.nsaved], saved[self.nsaved:]
-        use_fin = fin_ok and len(saved) == 2    # round 5, composite only: ea_linear_dgrad_finish adds the d(chunk mean) / r^2 terms
-        g = eva_bwd_impl(dout, qkv5, self.mask_u8, None, self.noise, out, list(saved), self.icfg, self.fcfg, self.adaptive,
-                         self.bias_cols, list(params), defer_param_sums=defer, defer_chunk_mean=use_fin)
-        fin = (g.pop()[1], None) if use_fin else None
-        extra, parts = [_opt(g[1])] + g[2:], ()
-        if g[2:] and isinstance(g[2], tuple):     # the mu networks' per-(b,h) partials (+ the composite backward's of the bias)
-            parts = _mlp_partials(g[2]) + ([("dbias", g[2][3], g[2][4])] if len(g[2]) > 3 else [])
-            extra = extra[:1]
-        return g[0], extra, parts, fin
+        use_fin = fin_ok and _eva_saved_is_composite(saved)   # round 5: ea_linear_dgrad_finish adds the d(chunk mean) / r^2 terms
+        g = _eva_backward(dout, qkv5, self.mask_u8, None, self.noise, out, list(saved), self.icfg, self.fcfg, self.adaptive,
+                          self.bias_cols, list(params), defer_param_sums=defer, defer_chunk_mean=use_fin)
+        return g.dqkv, [g.dbias] + (g.params or []), g.partials, (g.finish, None) if use_fin else None
 
     def scatter(self, res, extra):
         dbias, pgrads = extra[0], extra[1:]
@@ -1890,9 +1892,9 @@ class LaraCore:
         B, heads, d, elem = self.dims
         if not proj_pool_supported(x2, wq, cdtype, B, H, W, r, heads):
             return None
-        sizes = _lara_layer_cfg_dims(B, heads, d, elem, self.icfg, self.fcfg)[1] if _lara_use_composite() else None
-        ws, pq, pk = _pooled_rows(sizes, 3, B * heads, (H // r) * (W // r), d, x2.device)
-        self.pooled = (ws, None, None) if ws is not None else (None, pq, pk)
+        pl = _lara_layer_cfg_dims(B, heads, d, elem, self.icfg, self.fcfg)[1] if _lara_use_composite() else None
+        where = None if pl is None else (pl.n_saved, pl.saved_pq, pl.saved_pk)
+        self.pooled, pq, pk = _pooled_rows(where, B * heads, (H // r) * (W // r), d, x2.device)
         return _project_qkv_grid(x2, wq, bq32, cdtype, want, need_dx, w192, (B, H, W, r), pq, pk)
 
     def fwd(self, qkv5, inputs):
@@ -1931,11 +1933,9 @@ class LaraCore:
         H, W, r = self.icfg[:3]
         # round 5: the finish pass of the core is left to the input-gradient kernel (ea_linear_dgrad_finish: one pass, not two)
         use_fin = bool(fin_ok and self.icfg[6] == 0 and (H // r) * (W // r) <= 64)
-        g = lara_bwd_impl(*args, defer_param_sums=True, defer_finish=use_fin)
-        fin = (g.pop()[1], qkv5.view(qkv5.shape[0] * qkv5.shape[1], -1)) if use_fin else None
-        if g[1:] and isinstance(g[1], tuple):
-            return g[0], [], _mlp_partials(g[1]), fin
-        return g[0], g[1:], (), fin
+        g = _lara_backward(*args, defer_param_sums=True, defer_finish=use_fin)
+        fin = (g.finish, qkv5.view(qkv5.shape[0] * qkv5.shape[1], -1)) if use_fin else None
+        return g.dqkv, g.params or [], g.partials, fin
 
     def scatter(self, res, extra):
         return _mlp_grads(res["mlp_W"][0], res["mlp_v"][0], self.dims[2]) if "mlp_W" in res else extra
@@ -2859,7 +2859,7 @@ def dgrad_finish_usable(dqkv2, wq, xdtype, heads, d):
 
 def qkv_dgrad_finish(dqkv2, qkv2, wq, w16, xdtype, fin, wt=None):
     """dx = dqkv2 @ W after the LAST corrections of the dq / dk columns of dqkv2 (in place) -- ea_linear_dgrad_finish, one pass:
-    LARA: fin = dict(B, gh, gw, r, C, scale, qbar, uq, lse_t, dpq, dpk) from lara_bwd_impl(defer_finish=True) (lara.py:223,
+    LARA: fin = dict(B, gh, gw, r, C, scale, qbar, uq, lse_t, dpq, dpk) from _lara_backward(defer_finish=True) (lara.py:223,
     43,48,145-151 differentiated); EVA: uq = qbar = lse_t = None, dpq / dpk = the chunk-mean gradients (eva.py:178-181)."""
     rows = dqkv2.shape[0]
     cdtype = dqkv2.dtype

@@ -780,15 +780,15 @@ int ea_f32_gather_mean_bwd(int32_t B, int32_t H, int32_t N, int32_t D, int32_t C
  * ea_lara_merge_* / ea_lara_out_fwd / ea_lara_bwd_*_fused / ea_slice_sum / ea_lara_bwd_finish / ea_colsum2_f32 issued from
  * C++ on caller-owned workspaces, so that an eagerly stepping caller (vit/engine.py:47-64) pays two FFI calls per layer
  * step instead of ~15 (and two allocations instead of ~30).  C = L (x 2 with antithetic / multi-sample noise) <= 64.
- *   ea_lara_layer_ws(cfg, which): floats of workspace 0 = `saved` (forward -> backward), 1 = forward scratch, 2 = backward
- *       scratch; 3 / 4 = offsets (floats) of the pooled q / k rows [B*H, L, D] inside `saved`; 5 / 6 = offsets inside the
- *       backward scratch of the per-(b,h) parameter-gradient partials [B*H, 2 D D] (dW_q, dW_k) and [B*H, 6 D]
- *       (negative: EA_E_*).  ea_lara_layer_bwd with dparams == NULL leaves those partials to the caller (ea_multi_sum).
+ *   ea_lara_layer_plan(cfg, out) (ABI 31): the workspace layout, a pure host function of cfg -> EA_OK with *out filled, or
+ *       EA_E_* (a NULL `out`: EA_E_BADARG).
  *   keep_for_backward: bit 0 = keep the intermediates the backward needs; bit 1 (EA_LARA_POOLED_READY) = the pooled q / k
- *       rows are already in `saved` at those offsets (written by ea_linear_w32_pool): the pooling pass is skipped.
+ *       rows are already in `saved` at saved_pq / saved_pk (written by ea_linear_w32_pool): the pooling pass is skipped.
  *   params: NULL or 8 pointers (Wq, bq, gamma_q, beta_q, Wk, bk, gamma_k, beta_k: q_bar_gen / k_bar_gen, lara.py:45-54);
  *   noise: [B*H, C, D] standard normal or NULL (eval); dparams: [2*D*D + 6*D] fp32 = dW_q, dW_k, then (db, dgamma, dbeta)
- *   of q and of k, summed over the batch and heads. */
+ *   of q and of k, summed over the batch and heads, or NULL: the partials at bwd_dW / bwd_dvec are the caller's (ea_multi_sum).
+ *   flags: EA_LARA_DEFER_FINISH leaves out the finish pass -- dq lacks the softmax-over-sequence correction and dq, dk the
+ *       pooling terms; ea_linear_dgrad_finish applies them (saved_qrows, saved_lse_t, bwd_uq, bwd_dpq, bwd_dpk) on its way. */
 typedef struct {
   int32_t B, H, D;
   int32_t dtype;             /* EA_BF16 | EA_F16 */
@@ -797,41 +797,36 @@ typedef struct {
   int32_t has_mlp, mixed, mis, dup;   /* as in ea_lmk_geom */
   float   kappa, scale;      /* alpha_coeff (lara.py:231), D^-0.5 */
 } ea_lara_layer;
+typedef struct {             /* sizes in floats; saved_* / bwd_*: offsets in floats into `saved` / the backward scratch */
+  int64_t n_saved, n_fwd_tmp, n_bwd_tmp;                 /* `saved` (forward -> backward), forward scratch, backward scratch */
+  int64_t saved_pq, saved_pk, saved_qrows, saved_lse_t;  /* pooled q / k rows [B*H, L, D]; qbar rows [B*H, C, D]; lse_t [B*H, C] */
+  int64_t bwd_dW, bwd_dvec, bwd_uq, bwd_dpq, bwd_dpk;    /* per-(b,h) partials [B*H, 2 D D] (dW_q, dW_k), [B*H, 6 D]; u qbar rows; d(pooled q / k) */
+} ea_lara_layer_sizes;
 #define EA_LARA_POOLED_READY 2
-int64_t ea_lara_layer_ws(const ea_lara_layer* cfg, int32_t which);
+#define EA_LARA_DEFER_FINISH 1
+int ea_lara_layer_plan(const ea_lara_layer* cfg, ea_lara_layer_sizes* out);
 int ea_lara_layer_fwd(const ea_lara_layer* cfg, const ea_t4* q, const ea_t4* k, const ea_t4* v, const uint8_t* mask,
                       const float* noise, const float* const* params, const ea_t4* out, float* saved, float* tmp,
                       int32_t keep_for_backward, void* stream);
 int ea_lara_layer_bwd(const ea_lara_layer* cfg, const ea_t4* q, const ea_t4* k, const ea_t4* v, const uint8_t* mask,
                       const float* noise, const float* const* params, const ea_t4* dout, const ea_t4* dq, const ea_t4* dk,
-                      const ea_t4* dv, const float* saved, float* tmp, float* dparams, void* stream);
-/* ABI 10: flags = EA_LARA_DEFER_FINISH leaves out the finish pass -- dq lacks the softmax-over-sequence correction and dq, dk the
- * pooling terms; ea_linear_dgrad_finish applies them on its way (operands at ea_lara_layer_ws(cfg, 7..9) inside the backward
- * scratch and (10, 11) inside `saved`). */
-#define EA_LARA_DEFER_FINISH 1
-int ea_lara_layer_bwd2(const ea_lara_layer* cfg, const ea_t4* q, const ea_t4* k, const ea_t4* v, const uint8_t* mask,
-                       const float* noise, const float* const* params, const ea_t4* dout, const ea_t4* dq, const ea_t4* dk,
-                       const ea_t4* dv, const float* saved, float* tmp, float* dparams, int32_t flags, void* stream);
+                      const ea_t4* dv, const float* saved, float* tmp, float* dparams, int32_t flags, void* stream);
 
 /* ---- composite per-module entry points, EVA (round 4) -----------------------------------------------------------
  * The 2-D EVA core (eva.py:145-227: non-overlapping w x w windows, r x r landmark chunks, adaptive_proj 'default', no pad
  * mask) in one call each way -- the launch sequences of ea_eva_chunk_mean_fwd / ea_lara_landmarks_* (eva mode) /
  * ea_eva_beta_* / ea_window_attn_* / ea_slice_sum / ea_colsum_f32 / ea_eva_chunk_mean_bwd / ea_colsum2_f32 on caller-owned
  * workspaces, for the same reason as the LARA pair above (eagerly stepping call sites, vit/engine.py:47-64).
- *   ea_eva_layer_ws(cfg, which): 0 = floats of `saved` (forward -> backward), 1 = 0 (no forward scratch), 2 = floats of the
- *       backward scratch; 3 / 4 = offsets (floats) inside `saved` of the chunk means of q / k [B*H, L, D]; 5 / 6 = offsets
- *       inside the backward scratch of the per-(b,h) parameter-gradient partials [B*H, 2 D D] and [B*H, 6 D]; 7 = padded
- *       row length of `bias` (= ea_window_bias_ld); 8 = offset inside `saved` of the joint log-sum-exp [B,H,N]
- *       (negative: EA_E_*; EA_E_UNSUPPORTED: L > 64 or a window geometry whose backward needs scratch slices -- use the
- *       step-by-step entry points).
+ *   ea_eva_layer_plan(cfg, out) (ABI 31): as ea_lara_layer_plan; EA_E_UNSUPPORTED: L > 64 or a window geometry whose backward
+ *       needs scratch slices -- use the step-by-step entry points.
  *   bias: fp32 [H, w*w, ld] dense per-head bias multiplied by log2(e), rows padded to ld (as for ea_window_attn_fwd), or
  *       NULL (then cfg->has_bias == 0); dbias: fp32 [H, w*w, ld], gradient with respect to the NATURAL-unit bias, or NULL:
- *       its partial sums then stay in the backward scratch -- ea_eva_layer_ws(cfg, 9) = their offset, (cfg, 10) = their row
- *       count, rows of H * w*w * ld floats -- for the caller's own reduction (ea_multi_sum, with the other terminal sums).
+ *       its partial sums then stay at bwd_dbias_part for the caller's own reduction (ea_multi_sum, with the other sums).
  *   params: 8 pointers (W, b, gamma, beta of the q and of the k mu network: eva.py:93-103); noise: [B*H, L, D] or NULL.
- *   keep_for_backward: bit 0 = keep the intermediates; bit 1 (EA_LARA_POOLED_READY) = the chunk means are already in
- *       `saved` (ea_linear_w32_pool wrote them).  dparams: [2 D D + 6 D] fp32 as for ea_lara_layer_bwd, or NULL (partials
- *       left in the scratch for the caller's reduction).  dq, dk, dv are WRITTEN. */
+ *   keep_for_backward: as for ea_lara_layer_fwd (bit 1: ea_linear_w32_pool wrote the chunk means to saved_qmean / saved_kmean).
+ *   dparams: [2 D D + 6 D] fp32 as for ea_lara_layer_bwd, or NULL (partials left at bwd_dW / bwd_dvec).  dq, dk, dv are WRITTEN.
+ *   flags: EA_EVA_DEFER_CHUNK_MEAN leaves out the chunk-mean backward (eva.py:178-181 differentiated): dq / dk lack the
+ *       d(chunk mean) / r^2 terms, which ea_linear_dgrad_finish adds (from bwd_dqmean / bwd_dkmean) on its way. */
 typedef struct {
   int32_t B, H, D;
   int32_t dtype;             /* EA_BF16 | EA_F16 */
@@ -841,22 +836,21 @@ typedef struct {
   int32_t has_bias;
   float   scale;             /* D^-0.5 */
 } ea_eva_layer;
-int64_t ea_eva_layer_ws(const ea_eva_layer* cfg, int32_t which);
+typedef struct {             /* as ea_lara_layer_sizes (there is no forward scratch); bias_ld and dbias_part_rows are counts */
+  int64_t n_saved, n_bwd_tmp;
+  int64_t saved_qmean, saved_kmean, saved_lse, bias_ld;  /* chunk means of q / k [B*H, L, D]; joint log-sum-exp [B,H,N]; = ea_window_bias_ld */
+  int64_t bwd_dW, bwd_dvec, bwd_dbias_part, dbias_part_rows;   /* partials: [B*H, 2 D D], [B*H, 6 D]; of dbias, so many rows of H * w*w * ld */
+  int64_t bwd_dqmean, bwd_dkmean;                        /* chunk-mean gradients [B*H, L, D] */
+} ea_eva_layer_sizes;
+#define EA_EVA_DEFER_CHUNK_MEAN 1
+int ea_eva_layer_plan(const ea_eva_layer* cfg, ea_eva_layer_sizes* out);
 int ea_eva_layer_fwd(const ea_eva_layer* cfg, const ea_t4* q, const ea_t4* k, const ea_t4* v, const float* bias,
                      const float* noise, const float* const* params, const ea_t4* out, float* saved,
                      int32_t keep_for_backward, void* stream);
 int ea_eva_layer_bwd(const ea_eva_layer* cfg, const ea_t4* q, const ea_t4* k, const ea_t4* v, const float* bias,
                      const float* noise, const float* const* params, const ea_t4* out, const ea_t4* dout, const ea_t4* dq,
                      const ea_t4* dk, const ea_t4* dv, const float* saved, float* tmp, float* dbias, float* dparams,
-                     void* stream);
-/* ABI 10: flags = EA_EVA_DEFER_CHUNK_MEAN leaves out the chunk-mean backward (eva.py:178-181 differentiated): dq / dk lack the
- * d(chunk mean) / r^2 terms, which ea_linear_dgrad_finish adds on its way (their gradients [B*H, L, D] fp32 sit at
- * ea_eva_layer_ws(cfg, 11 / 12) inside the backward scratch). */
-#define EA_EVA_DEFER_CHUNK_MEAN 1
-int ea_eva_layer_bwd2(const ea_eva_layer* cfg, const ea_t4* q, const ea_t4* k, const ea_t4* v, const float* bias,
-                      const float* noise, const float* const* params, const ea_t4* out, const ea_t4* dout, const ea_t4* dq,
-                      const ea_t4* dk, const ea_t4* dv, const float* saved, float* tmp, float* dbias, float* dparams,
-                      int32_t flags, void* stream);
+                     int32_t flags, void* stream);
 
 /* ---- row LayerNorm (ea_layernorm.hip) -------------------------------------------------------------------------
  * The LayerNorm of LinearRA's model-wide ('dense') landmark generators (lara.py:34-44,64-71: Linear(dim, dim) + LayerNorm(dim)

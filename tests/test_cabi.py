@@ -74,48 +74,55 @@ def test_version_and_argument_validation(lib):
 
 
 def test_composite_layer_entry_points_report_their_workspaces(lib):
-    """ea_lara_layer_ws / _fwd / _bwd (one call per direction for the whole LARA core): sizes on the host, argument
+    """ea_lara_layer_plan / _fwd / _bwd (one call per direction for the whole LARA core): sizes on the host, argument
     validation before any launch.  The numerical check of the composite path is every LARA test of the GPU suite (the
-    module goes through it) plus tests/test_gpu_primitives.py::test_lara_composite_equals_step_by_step."""
+    module goes through it) plus tests/test_gpu_primitives.py::test_lara_composite_equals_step_by_step; the layout itself is
+    pinned by tests/test_layer_plan_cpu.py."""
     from efficient_attention import _native
+    L = _native.lib()
     cfg = _native.ea_lara_layer(128, 3, 64, 0, 28, 28, 4, 1, 1, 0, 0, 2.0, 0.125)      # cfg3: 49 landmarks, mis-opt, pool-mixed
-    n = [lib.ea_lara_layer_ws(ctypes.byref(cfg), w) for w in (0, 1, 2)]
-    lib.ea_lara_layer_ws.restype = ctypes.c_int64
-    n = [_native.lib().ea_lara_layer_ws(ctypes.byref(cfg), w) for w in (0, 1, 2)]
-    BH, C, L, D, N = 384, 49, 49, 64, 784
-    assert n[0] >= 3 * BH * C * D + 2 * BH * L * D + 2 * BH * N and n[1] >= BH * C * D and n[2] >= 9 * BH * C * D
+    n = _native.ea_lara_layer_sizes()
+    assert L.ea_lara_layer_plan(ctypes.byref(cfg), ctypes.byref(n)) == 0
+    BH, C, Lm, D, N = 384, 49, 49, 64, 784
+    assert n.n_saved >= 3 * BH * C * D + 2 * BH * Lm * D + 2 * BH * N and n.n_fwd_tmp >= BH * C * D and n.n_bwd_tmp >= 9 * BH * C * D
+    assert L.ea_lara_layer_plan(ctypes.byref(cfg), None) == -1
     bad = _native.ea_lara_layer(128, 3, 64, 0, 28, 27, 4, 1, 1, 0, 0, 2.0, 0.125)      # grid not divisible by the pooling side
-    assert _native.lib().ea_lara_layer_ws(ctypes.byref(bad), 0) == -1
+    assert L.ea_lara_layer_plan(ctypes.byref(bad), ctypes.byref(n)) == -1
     big = _native.ea_lara_layer(2, 3, 64, 0, 28, 28, 2, 0, 0, 0, 0, 2.0, 0.125)        # 196 landmarks: step-by-step path
-    assert _native.lib().ea_lara_layer_ws(ctypes.byref(big), 0) == -2
-    rc = _native.lib().ea_lara_layer_fwd(ctypes.byref(cfg), None, None, None, None, None, None, None, None, None, 1, None)
+    assert L.ea_lara_layer_plan(ctypes.byref(big), ctypes.byref(n)) == -2
+    rc = L.ea_lara_layer_fwd(ctypes.byref(cfg), None, None, None, None, None, None, None, None, None, 1, None)
     assert rc == -1
+    assert L.ea_lara_layer_bwd(ctypes.byref(cfg), None, None, None, None, None, None, None, None, None, None, None, None, None,
+                               0, None) == -1
 
 
 def test_eva_composite_entry_points_report_their_workspaces(lib):
-    """ea_eva_layer_ws / _fwd / _bwd (one call per direction for the 2-D EVA core): host-side sizes and argument validation.
+    """ea_eva_layer_plan / _fwd / _bwd (one call per direction for the 2-D EVA core): host-side sizes and argument validation.
     Numerics: tests/test_gpu_primitives.py::test_eva_composite_equals_step_by_step and every EVA test of the GPU suite."""
     from efficient_attention import _native
     L = _native.lib()
     cfg = _native.ea_eva_layer(128, 3, 64, 0, 28, 28, 7, 4, 1, 0.125)              # cfg3: 7 x 7 windows, 49 chunks of 4 x 4
-    n = [L.ea_eva_layer_ws(ctypes.byref(cfg), w) for w in range(11)]
+    n = _native.ea_eva_layer_sizes()
+    assert L.ea_eva_layer_plan(ctypes.byref(cfg), ctypes.byref(n)) == 0
     BH, Lm, D, N = 384, 49, 64, 784
-    assert n[0] >= BH * N + 5 * BH * Lm * D and n[1] == 0 and n[2] >= 5 * BH * Lm * D + BH * (2 * D * D + 6 * D)
-    assert 0 <= n[8] < n[3] < n[4] < n[0] and 0 <= n[5] < n[6] < n[2] and n[7] >= 49
+    assert n.n_saved >= BH * N + 5 * BH * Lm * D and n.n_bwd_tmp >= 5 * BH * Lm * D + BH * (2 * D * D + 6 * D)
+    assert 0 <= n.saved_lse < n.saved_qmean < n.saved_kmean < n.n_saved and 0 <= n.bwd_dW < n.bwd_dvec < n.n_bwd_tmp and n.bias_ld >= 49
     geom = _native.make_geom(128, 3, N, 64, 0, True, (28, 28), 7, 0, 4, 49)
-    assert n[7] == L.ea_window_bias_ld(ctypes.byref(geom))
-    assert 0 <= n[9] < n[2] and n[10] >= 128 and n[9] + n[10] * 3 * 49 * n[7] <= n[2]      # bias-gradient partials in the scratch
-    assert 0 <= n[2] and 0 <= L.ea_eva_layer_ws(ctypes.byref(cfg), 11) < L.ea_eva_layer_ws(ctypes.byref(cfg), 12) < n[2]   # d(chunk means) (ABI 10)
-    assert L.ea_eva_layer_ws(ctypes.byref(cfg), 13) == -1
+    assert n.bias_ld == L.ea_window_bias_ld(ctypes.byref(geom))
+    # bias-gradient partials in the scratch
+    assert 0 <= n.bwd_dbias_part < n.n_bwd_tmp and n.dbias_part_rows >= 128
+    assert n.bwd_dbias_part + n.dbias_part_rows * 3 * 49 * n.bias_ld <= n.n_bwd_tmp
+    assert 0 <= n.n_bwd_tmp and 0 <= n.bwd_dqmean < n.bwd_dkmean < n.n_bwd_tmp                        # d(chunk means) (ABI 10)
+    assert L.ea_eva_layer_plan(ctypes.byref(cfg), None) == -1
     bad = _native.ea_eva_layer(128, 3, 64, 0, 28, 28, 8, 4, 1, 0.125)              # grid not divisible by the window side
-    assert L.ea_eva_layer_ws(ctypes.byref(bad), 0) == -1
+    assert L.ea_eva_layer_plan(ctypes.byref(bad), ctypes.byref(n)) == -1
     big = _native.ea_eva_layer(2, 3, 64, 0, 28, 28, 7, 2, 0, 0.125)                # 196 landmarks: step-by-step path
-    assert L.ea_eva_layer_ws(ctypes.byref(big), 0) == -2
+    assert L.ea_eva_layer_plan(ctypes.byref(big), ctypes.byref(n)) == -2
     odd = _native.ea_eva_layer(2, 3, 48, 0, 28, 28, 7, 4, 0, 0.125)                # head dim not built
-    assert L.ea_eva_layer_ws(ctypes.byref(odd), 0) == -2
+    assert L.ea_eva_layer_plan(ctypes.byref(odd), ctypes.byref(n)) == -2
     assert L.ea_eva_layer_fwd(ctypes.byref(cfg), None, None, None, None, None, None, None, None, 1, None) == -1
     assert L.ea_eva_layer_bwd(ctypes.byref(cfg), None, None, None, None, None, None, None, None, None, None, None, None, None,
-                              None, None, None) == -1
+                              None, None, 0, None) == -1
 
 
 # ---- causal EVA decoding: what the six ea_ceva_* entry points refuse, before any HIP call --------------------------------

@@ -65,8 +65,8 @@ def _layer_fwd(qkv, noise, params, icfg, fcfg, keep, proj=None):
     B, N, _, h, d = qkv.shape
     q, k, v = _ops._qkv_views(qkv)
     tq, tk, tv = nv.t4(q), nv.t4(k), nv.t4(v)
-    ws = torch.zeros(sizes[0], dtype=torch.float32, device="cuda")
-    tmp = torch.zeros(sizes[1], dtype=torch.float32, device="cuda")
+    ws = torch.zeros(sizes.n_saved, dtype=torch.float32, device="cuda")
+    tmp = torch.zeros(sizes.n_fwd_tmp, dtype=torch.float32, device="cuda")
     out = torch.zeros((B, N, h, d), dtype=qkv.dtype, device="cuda")
     to = nv.t4(out.permute(0, 2, 1, 3))
     ps = [t.float().contiguous() for t in params]

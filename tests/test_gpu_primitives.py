@@ -1121,7 +1121,7 @@ def test_eva_composite_equals_step_by_step(dtype, dim, heads, grid, window, land
             y.backward(g)
             monkeypatch.setattr(_ops.nv, "call", orig)
             res[comp] = (y.detach().clone(), x.grad.clone(), {n: p.grad.clone() for n, p in m.named_parameters() if p.grad is not None})
-            used[comp] = ("ea_eva_layer_fwd" in calls, "ea_eva_layer_bwd" in calls or "ea_eva_layer_bwd2" in calls)
+            used[comp] = ("ea_eva_layer_fwd" in calls, "ea_eva_layer_bwd" in calls)
         pooled_three_nodes = (not module_fn) and dim == 192 and _ops.USE_PROJ_POOL
         assert used[True] == ((False, False) if pooled_three_nodes else (True, True)), used
         assert used[False] == (False, False)
