@@ -130,7 +130,7 @@ def _(qkv, mask, W, cfg):
     cfg = tuple(int(c) for c in cfg)
     F = _kernelized._features(cfg)
     S = _kernelized._parts(_kernelized._geom(qkv, cfg))           # (host-side size query: works on fake tensors)
-    p_st = _f32(qkv, B * h, S, 2) if cfg[0] in _kernelized.STAT_MAPS else _none(qkv)
+    p_st = _f32(qkv, B * h, S, 2) if _kernelized._has_stat(cfg) else _none(qkv)
     return [qkv.new_empty((B, N, h, d)), p_st, _f32(qkv, B * h, F, d), _f32(qkv, B * h, F)]
 
 
@@ -143,20 +143,18 @@ def _(dout, qkv, mask, W, p_st, kv, ksum, cfg, need_dw):
 @torch.library.register_fake("ea::lara_fwd")
 def _(qkv, mask, noise, icfg, fcfg, params):
     B, N, _, h, d = qkv.shape
-    H, W, r, has_mlp, mixed, mis, dup = [int(v) for v in icfg[:7]]
-    L = (H // r) * (W // r)
-    C = L * (2 if dup else 1)
-    BH = B * h
+    cfg, need = _ops.LaraCfg.from_lists(icfg, fcfg)
+    L, C, mis, BH = cfg.L, cfg.C, cfg.mis, B * h
     # (host-side size query: works on fake tensors; the composite decision is taken like the real forward takes it -- the
     # traced output count must be what the implementation will return when the graph runs)
-    lcfg, sizes = _ops._lara_layer_cfg(qkv, icfg, fcfg) if _ops._lara_use_composite() else (None, None)
+    lcfg, sizes = _ops._lara_layer_plan(qkv, cfg) if _ops._lara_use_composite() else (None, None)
     if lcfg is not None:
         return [qkv.new_empty((B, N, h, d)), _f32(qkv, sizes.n_saved)]
     return [qkv.new_empty((B, N, h, d)), _f32(qkv, BH, C, d), _f32(qkv, BH, C, d) if mis != 2 else _none(qkv),
             _f32(qkv, BH, C) if mis == 0 else _none(qkv), _f32(qkv, BH, C), _f32(qkv, BH, C, d), _f32(qkv, BH, C),
             _f32(qkv, BH, C) if mis == 0 else _none(qkv), _f32(qkv, BH, L, d), _f32(qkv, BH, L, d),
-            _f32(qkv, BH * (3 * L * d + L * 64 + 128)) if (len(icfg) < 8 or icfg[7]) else _none(qkv),
-            _f32(qkv, 2, BH, N) if ((len(icfg) < 8 or icfg[7]) and C <= 64) else _none(qkv)]
+            _f32(qkv, BH * (3 * L * d + L * 64 + 128)) if need else _none(qkv),
+            _f32(qkv, 2, BH, N) if (need and C <= 64) else _none(qkv)]
 
 
 @torch.library.register_fake("ea::lara_bwd")
@@ -167,11 +165,11 @@ def _(dout, qkv, mask, noise, saved, icfg, fcfg, params):
 @torch.library.register_fake("ea::eva_fwd")
 def _(qkv, bias, noise, mask, keep, icfg, fcfg, adaptive_proj, params):
     B, N, _, h, d = qkv.shape
-    L = int(icfg[6])
+    cfg, need = _ops.EvaCfg.from_lists(icfg, fcfg, adaptive_proj)
+    L = cfg.L
     lm = _f32(qkv, B, h, L, d)
     bias_p = _none(qkv) if bias is None else _f32(qkv, bias.shape[0], bias.shape[1], -(-bias.shape[2] // 16) * 16)
-    fused = adaptive_proj == "default" and L <= 64 and d in (32, 64) and float(fcfg[0]) == 0.5
-    need = len(icfg) < 9 or bool(icfg[8])
+    fused = _ops._eva_fused_mu(cfg, d)
     saved = _f32(qkv, B * h * (3 * L * d + L * 64 + 128)) if (fused and need) else _none(qkv)
     sides = 1 if adaptive_proj == "none" else 2
     ln = (not fused) and need and adaptive_proj != "no-ln"

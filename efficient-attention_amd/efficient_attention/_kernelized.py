@@ -12,7 +12,7 @@ import torch
 
 from . import _feature_cores as _fc
 from . import _native as nv
-from ._ops import _ea_op, _IO32
+from ._ops import Core, _ea_op, _IO32
 
 MAPS = {"favorp": 0, "relu": 1, "fourier": 2, "relu-only": 3, "sigmoid-only": 4, "dpfp": 5}
 W_MAPS = ("favorp", "relu", "fourier")
@@ -47,6 +47,10 @@ def _features(cfg):
     return f * (2 if cos else 1)
 
 
+def _has_stat(cfg):
+    return cfg[0] in STAT_MAPS
+
+
 def _geom(qkv5, cfg):
     B, N, _, h, d = qkv5.shape
     map_id, m, nu, cos = cfg
@@ -67,7 +71,7 @@ def kernelized_fwd_impl(qkv5, mask_u8, W, cfg):
     cfg = tuple(int(c) for c in cfg)
     geom = _geom(qkv5, cfg)
     return list(_fc.forward(_FAMILY, geom, _parts(geom), _features(cfg), qkv5, mask_u8, W,
-                            (2,) if cfg[0] in STAT_MAPS else None))
+                            (2,) if _has_stat(cfg) else None))
 
 
 def kernelized_bwd_impl(dout, qkv5, mask_u8, W, p_st, kv, ksum, cfg, need_dw):
@@ -110,13 +114,12 @@ def kernelized_attention(qkv5, mask_u8, W, cfg, learn):
     return KernelizedFn.apply(qkv5, mask_u8, W, tuple(cfg), bool(learn))
 
 
-class KernelizedCore:
+class KernelizedCore(Core):
     """Core spec of _ops.CoreModuleFn: this core on the 16-bit qkv of an autocast step.  With `learn` the feature matrix is
     the node's one differentiable input (W is then passed through `inputs`), else it is fixed state (or None)."""
 
     def __init__(self, mask_u8, W, cfg, learn):
         self.mask_u8, self.W, self.cfg, self.learn = mask_u8, W, tuple(cfg), bool(learn)
-        self.n_inputs = 1 if learn else 0
 
     def _w(self, inputs):
         return inputs[0] if self.learn else self.W
@@ -126,7 +129,7 @@ class KernelizedCore:
         out, p_st, kv, ksum = kernelized_fwd_impl(qkv5, self.mask_u8, W, self.cfg)
         return out, (p_st, kv, ksum) + ((W,) if self.learn else ())
 
-    def bwd(self, dout, qkv5, out, saved):
+    def bwd(self, dout, qkv5, out, saved, defer, fin_ok):
         W = saved[3] if self.learn else self.W
         dqkv5, dW = kernelized_bwd_impl(dout, qkv5, self.mask_u8, W, saved[0], saved[1], saved[2], self.cfg, self.learn)
-        return dqkv5, ((dW,) if self.learn else ())
+        return dqkv5, ((dW,) if self.learn else ()), (), None

@@ -12,6 +12,7 @@ import ctypes
 import math
 import os
 import threading
+import typing
 import warnings
 
 import torch
@@ -419,12 +420,17 @@ def _e(t, like):
     return like.new_empty(0) if t is None else t
 
 
+def _local_geom(qkv5, geo):
+    """geo = [attn_2d, s0, s1, window, ext] of the local ops (_geo) -> ea_geom."""
+    B, N, _, h, d = qkv5.shape
+    attn_2d, s0, s1, window, ext = [int(v) for v in geo]
+    return nv.make_geom(B, h, N, d, nv.io_dtype(qkv5), bool(attn_2d), (s0, s1) if attn_2d else (s0,), window, ext, 0, 0)
+
+
 def local_fwd_impl(qkv5, bias, mask_u8, geo):
     """torch.ops.ea.local_fwd: geo = [attn_2d, s0, s1, window, ext] -> [out, lse, bias_padded | empty]."""
     nv.require_cuda(qkv5, "qkv")
-    B, N, _, h, d = qkv5.shape
-    attn_2d, s0, s1, window, ext = [int(v) for v in geo]
-    geom = nv.make_geom(B, h, N, d, nv.io_dtype(qkv5), bool(attn_2d), (s0, s1) if attn_2d else (s0,), window, ext, 0, 0)
+    geom = _local_geom(qkv5, geo)
     bias_p = _bias_padded(bias, geom)
     out, lse = _window_fwd(geom, qkv5, None, None, bias_p, mask_u8)
     return [out, lse, _e(bias_p, lse)]
@@ -432,9 +438,7 @@ def local_fwd_impl(qkv5, bias, mask_u8, geo):
 
 def local_bwd_impl(dout, dlse, qkv5, bias_p, mask_u8, out, lse, geo, bias_cols):
     """torch.ops.ea.local_bwd -> [dqkv, dbias | empty]."""
-    B, N, _, h, d = qkv5.shape
-    attn_2d, s0, s1, window, ext = [int(v) for v in geo]
-    geom = nv.make_geom(B, h, N, d, nv.io_dtype(qkv5), bool(attn_2d), (s0, s1) if attn_2d else (s0,), window, ext, 0, 0)
+    geom = _local_geom(qkv5, geo)
     dqkv5 = torch.empty_like(qkv5)
     _, _, dbias = _window_bwd(geom, qkv5, None, None, bias_p, mask_u8, out, dout.contiguous(), lse, dqkv5,
                               dlse=None if dlse is None else dlse.float().contiguous())
@@ -499,14 +503,50 @@ def _mlp_grads(dW, dvec, d):
 # ------------------------------------------------------------------------------------------
 # EVA  (reference eva.py:145-227)
 # ------------------------------------------------------------------------------------------
-def _eva_cfg(qkv5, icfg, fcfg, adaptive_proj):
-    attn_2d, s0, s1, window, ext, chunk, L, causal = [int(v) for v in icfg[:8]]
-    mu_scale, keep_scale = [float(v) for v in fcfg]
+class EvaCfg(typing.NamedTuple):
+    """The EVA core's configuration (plain values, hashable).  causal / mu_scale select causal_eva.py's geometry, masks
+    (ea_geom.causal) and its mu = rq + rk; keep_scale = 1 / (1 - p) scales the attention dropout's keep mask (EvaExtras.keep).
+    lists() / from_lists() are the ONE encoder and decoder of the int[] / float[] arguments of torch.ops.ea.eva_fwd / eva_bwd:
+    icfg = [attn_2d, s0, s1 | 0, window, ext, chunk, L, causal(, keep_for_backward = 1)], fcfg = [mu_scale, keep_scale]."""
+    attn_2d: bool
+    seq_shape: tuple
+    window: int
+    ext: int
+    chunk: int
+    L: int
+    adaptive_proj: str
+    causal: int = 0
+    mu_scale: float = 0.5
+    keep_scale: float = 1.0
+
+    def lists(self, need_grad):
+        return (_geo(self.attn_2d, self.seq_shape, self.window, self.ext)
+                + [int(self.chunk), int(self.L), int(self.causal), int(bool(need_grad))],
+                [float(self.mu_scale), float(self.keep_scale)])
+
+    @classmethod
+    def from_lists(cls, icfg, fcfg, adaptive_proj):
+        """-> (cfg, need_grad); an absent trailing entry means keep for backward."""
+        attn_2d, s0, s1, window, ext, chunk, L, causal, *keep = [int(v) for v in icfg]
+        mu_scale, keep_scale = [float(v) for v in fcfg]
+        cfg = cls(bool(attn_2d), (s0, s1) if attn_2d else (s0,), window, ext, chunk, L, adaptive_proj, causal, mu_scale, keep_scale)
+        return cfg, not keep or bool(keep[0])
+
+
+# what an EVA call may carry besides its EvaCfg: the uint8 keep mask of the attention dropout (causal_eva only), a TableBias
+# -- `bias` is then the TABLE ([rows, h] or [rows, 1]); direct calls only --, the Pooled chunk means a projection kernel wrote
+EvaExtras = collections.namedtuple("EvaExtras", "keep table_bias pooled", defaults=(None, None, None))
+
+
+def _eva_cfg(qkv5, cfg):
+    """-> (ea_geom, whether the fused mu networks -- Linear + LayerNorm + mu + omega in one kernel -- apply)."""
     B, N, _, h, d = qkv5.shape
-    geom = nv.make_geom(B, h, N, d, nv.io_dtype(qkv5), bool(attn_2d), (s0, s1) if attn_2d else (s0,), window, ext,
-                        chunk, L, causal)
-    fused_mu = adaptive_proj == "default" and L <= 64 and d in (32, 64) and mu_scale == 0.5
-    return geom, L, mu_scale, keep_scale, fused_mu
+    geom = nv.make_geom(B, h, N, d, nv.io_dtype(qkv5), cfg.attn_2d, cfg.seq_shape, cfg.window, cfg.ext, cfg.chunk, cfg.L, cfg.causal)
+    return geom, _eva_fused_mu(cfg, d)
+
+
+def _eva_fused_mu(cfg, d):
+    return cfg.adaptive_proj == "default" and cfg.L <= 64 and d in (32, 64) and cfg.mu_scale == 0.5
 
 
 def _eva_use_composite():
@@ -518,19 +558,22 @@ def _eva_use_composite():
 _EVA_LAYER_CFG = {}
 
 
-def _eva_layer_cfg_dims(B, h, d, io, icfg, fcfg, adaptive_proj, has_bias, masked):
+def _eva_layer_cfg_dims(B, h, d, io, cfg, has_bias, masked):
     """(ea_eva_layer, ea_eva_layer_sizes: the workspace plan, read by field name) of the composite entry points, or
     (None, None): 2-D non-overlapping windows, no pad mask / dropout, the fused mu networks.  Memoised per geometry."""
-    attn_2d, s0, s1, window, ext, chunk, L, causal = [int(v) for v in icfg[:8]]
-    if (not attn_2d or ext != 0 or causal != 0 or masked or adaptive_proj != "default" or float(fcfg[0]) != 0.5
-            or float(fcfg[1]) != 1.0 or chunk <= 0 or s0 % chunk or s1 % chunk or (s0 // chunk) * (s1 // chunk) != L):
+    chunk = cfg.chunk
+    if (not cfg.attn_2d or cfg.ext != 0 or cfg.causal != 0 or masked or cfg.adaptive_proj != "default" or cfg.mu_scale != 0.5
+            or cfg.keep_scale != 1.0 or chunk <= 0):
         return None, None
-    key = (B, h, d, io, s0, s1, window, chunk, int(has_bias))
+    s0, s1 = cfg.seq_shape
+    if s0 % chunk or s1 % chunk or (s0 // chunk) * (s1 // chunk) != cfg.L:
+        return None, None
+    key = (B, h, d, io, s0, s1, cfg.window, chunk, int(has_bias))
     hit = _EVA_LAYER_CFG.get(key)
     if hit is None:
-        cfg = nv.ea_eva_layer(B, h, d, io, s0, s1, window, chunk, int(has_bias), float(d) ** -0.5)
+        lcfg = nv.ea_eva_layer(B, h, d, io, s0, s1, cfg.window, chunk, int(has_bias), float(d) ** -0.5)
         sizes = nv.ea_eva_layer_sizes()
-        hit = (cfg, sizes) if nv.lib().ea_eva_layer_plan(ctypes.byref(cfg), ctypes.byref(sizes)) == 0 else (None, None)
+        hit = (lcfg, sizes) if nv.lib().ea_eva_layer_plan(ctypes.byref(lcfg), ctypes.byref(sizes)) == 0 else (None, None)
         if len(_EVA_LAYER_CFG) < 256:
             _EVA_LAYER_CFG[key] = hit
     return hit
@@ -540,8 +583,11 @@ def _eva_layer_cfg_dims(B, h, d, io, icfg, fcfg, adaptive_proj, has_bias, masked
 # composite entry, or as two tensors for the step-by-step launches -- exactly one of ws and the pq / pk pair is set
 Pooled = collections.namedtuple("Pooled", "ws pq pk")
 # of _lara_backward / _eva_backward.  params: the summed parameter gradients (fp32, parameter order), None when deferred; partials:
-# (key, tensor [S, n], meta) entries for the caller's terminal sum; finish: the operands of qkv_dgrad_finish (a dict) or None
+# (key, tensor [S, n], meta) entries for the caller's terminal sum; finish: the operands of qkv_dgrad_finish (a Finish) or None
 CoreGrads = collections.namedtuple("CoreGrads", "dqkv dbias params partials finish")
+# the operands of qkv_dgrad_finish: the r x r cells of a gh x gw grid, C samples; dpq / dpk [BH, L, d] the gradients of the pooled
+# rows (EVA: of the chunk means); uq, qbar [BH, C, d] and lse_t [BH, C] only for LARA's softmax-over-sequence correction
+Finish = collections.namedtuple("Finish", "B gh gw r C scale dpq dpk uq qbar lse_t", defaults=(None, None, None))
 
 
 def _ws_rows(ws, at, rows, cols=None):
@@ -561,37 +607,36 @@ def _eva_saved_is_composite(saved_list):
 
 def eva_fwd_impl(qkv5, bias, noise, mask_u8, keep, icfg, fcfg, adaptive_proj, mlp_params, pooled=None, composite=False):
     """torch.ops.ea.eva_fwd: chunk means -> mu MLP -> omega -> beta -> window attention with control-variate
-    columns (eva.py:145-227).  icfg = [attn_2d, s0, s1, window, ext, chunk, L, causal(, keep_for_backward = 1)],
-    fcfg = [mu_scale, keep_scale].  -> [out, bias_padded, lse, qmean, kmean, omega, beta, rf_k_bar, noise, lmk_saved, zhat, rstd]
-    (absent tensors are empty).
+    columns (eva.py:145-227).  icfg, fcfg, adaptive_proj: an EvaCfg and the keep-for-backward flag as EvaCfg.lists() encodes
+    them.  -> [out, bias_padded, lse, qmean, kmean, omega, beta, rf_k_bar, lmk_saved, zhat, rstd] (absent tensors are empty).
     composite (direct calls only, never through the dispatcher): ONE C-ABI call (ea_eva_layer_fwd) on a caller-owned
     workspace where the geometry allows it -> [out, bias_padded, saved workspace]; pooled (direct calls only): a Pooled --
     the chunk means the projection kernel already wrote, into that workspace or as two tensors -- or None."""
     global LAST_LMK_GEOM
     nv.require_cuda(qkv5, "qkv")
+    cfg, need_grad = EvaCfg.from_lists(icfg, fcfg, adaptive_proj)
     B, N, _, h, d = qkv5.shape
     dev = qkv5.device
-    lcfg, sizes = _eva_layer_cfg_dims(B, h, d, nv.io_dtype(qkv5), icfg, fcfg, adaptive_proj, bias is not None,
+    lcfg, sizes = _eva_layer_cfg_dims(B, h, d, nv.io_dtype(qkv5), cfg, bias is not None,
                                       mask_u8 is not None or keep is not None) if composite else (None, None)
     if pooled is not None and (pooled.ws is not None) != (lcfg is not None):
         raise RuntimeError("eva_fwd: chunk means prepared for the other launch path")
-    need_grad = len(icfg) < 9 or bool(icfg[8])
+    geom, fused_mu = _eva_cfg(qkv5, cfg)
+    L, mu_scale = cfg.L, cfg.mu_scale
     q, k, v = _qkv_views(qkv5)
     tq, tk, tv = nv.t4(q), nv.t4(k), nv.t4(v)
     if lcfg is not None:
         ws = pooled.ws if pooled is not None else torch.empty(sizes.n_saved, dtype=torch.float32, device=dev)
         out = torch.empty((B, N, h, d), dtype=qkv5.dtype, device=dev)
         to = nv.t4(out.permute(0, 2, 1, 3))
-        geom = _eva_cfg(qkv5, icfg, fcfg, adaptive_proj)[0]
         bias_p = _bias_padded(bias, geom)
         noise_c = None if noise is None else noise.float().contiguous()
         ps = [_f32c(p) for p in mlp_params]
-        LAST_LMK_GEOM = (B * h, int(icfg[6]), int(icfg[6]), d, 1, 0, 1)
+        LAST_LMK_GEOM = (B * h, L, L, d, 1, 0, 1)
         nv.call("ea_eva_layer_fwd", ctypes.byref(lcfg), ctypes.byref(tq), ctypes.byref(tk), ctypes.byref(tv),
                 nv.ptr(bias_p), nv.ptr(noise_c), _param_ptrs(ps), ctypes.byref(to), nv.ptr(ws),
                 int(need_grad) | (2 if pooled is not None else 0), nv.stream())
         return [out, _e(bias_p, ws), ws]                  # composite: _eva_saved_is_composite
-    geom, L, mu_scale, keep_scale, fused_mu = _eva_cfg(qkv5, icfg, fcfg, adaptive_proj)
     if pooled is not None:
         # (direct calls only) the chunk means came out of the projection kernel (ea_linear_w32_pool, LinearPoolFn)
         qmean, kmean = pooled.pq.view(B, h, L, d), pooled.pk.view(B, h, L, d)
@@ -615,8 +660,8 @@ def eva_fwd_impl(qkv5, bias, noise, mask_u8, keep, icfg, fcfg, adaptive_proj, ml
                 nv.ptr(saved), nv.stream())
     else:
         # Linear (+ LayerNorm) of both sides in one exact-fp32 HIP pass (ea_rows_mlp_fwd)
-        sides = 1 if adaptive_proj == "none" else 2
-        ln = adaptive_proj != "no-ln"
+        sides = 1 if cfg.adaptive_proj == "none" else 2
+        ln = cfg.adaptive_proj != "no-ln"
         per = 4 if ln else 2
         side_p = [ps[i * per:(i + 1) * per] for i in range(sides)]          # (W, b[, gamma, beta]) per side
         xs = [qmean, kmean] if sides == 2 else [kmean]
@@ -649,18 +694,19 @@ def eva_fwd_impl(qkv5, bias, noise, mask_u8, keep, icfg, fcfg, adaptive_proj, ml
     nv.call("ea_eva_beta_fwd", ctypes.byref(geom), ctypes.byref(tk), ctypes.byref(tv),
             nv.ptr(mask_u8), nv.ptr(omega), nv.ptr(beta), nv.stream())
     bias_p = _bias_padded(bias, geom)
-    out, lse = _window_fwd(geom, qkv5, rf_k_bar, beta, bias_p, mask_u8, keep, keep_scale)
+    out, lse = _window_fwd(geom, qkv5, rf_k_bar, beta, bias_p, mask_u8, keep, cfg.keep_scale)
     e = lse
     return [out, _e(bias_p, e), lse, qmean, kmean, omega, beta, rf_k_bar, _e(saved, e), _e(zhat, e), _e(rstd, e)]
 
 
 def eva_bwd_impl(dout, qkv5, mask_u8, keep, noise, out, saved_list, icfg, fcfg, adaptive_proj, bias_cols, mlp_params):
     """torch.ops.ea.eva_bwd -> [dqkv, dbias | empty, *parameter gradients (fp32, in the order of mlp_params)]."""
-    g = _eva_backward(dout, qkv5, mask_u8, keep, noise, out, saved_list, icfg, fcfg, adaptive_proj, bias_cols, mlp_params)
+    cfg, _ = EvaCfg.from_lists(icfg, fcfg, adaptive_proj)
+    g = _eva_backward(dout, qkv5, mask_u8, keep, noise, out, saved_list, cfg, bias_cols, mlp_params)
     return [g.dqkv, _e(g.dbias, saved_list[1])] + g.params
 
 
-def _eva_backward(dout, qkv5, mask_u8, keep, noise, out, saved_list, icfg, fcfg, adaptive_proj, bias_cols, mlp_params,
+def _eva_backward(dout, qkv5, mask_u8, keep, noise, out, saved_list, cfg, bias_cols, mlp_params,
                   defer_param_sums=False, defer_chunk_mean=False):
     """The EVA core's backward -> CoreGrads.  defer_param_sums: the per-(b,h) partials of the mu networks' (composite: and the bias)
     gradients wait for the caller's terminal sum; defer_chunk_mean (composite only, round 5): ea_linear_dgrad_finish adds
@@ -670,7 +716,7 @@ def _eva_backward(dout, qkv5, mask_u8, keep, noise, out, saved_list, icfg, fcfg,
     dqkv5 = torch.empty_like(qkv5)
     if _eva_saved_is_composite(saved_list):
         bias_p, ws = _opt(saved_list[0]), saved_list[1]
-        lcfg, sizes = _eva_layer_cfg_dims(B, h, d, nv.io_dtype(qkv5), icfg, fcfg, adaptive_proj, bias_p is not None, False)
+        lcfg, sizes = _eva_layer_cfg_dims(B, h, d, nv.io_dtype(qkv5), cfg, bias_p is not None, False)
         if lcfg is None:
             raise RuntimeError("eva_bwd: a composite workspace was saved for a geometry ea_eva_layer_plan rejects")
         dout = _rows_contiguous(dout)
@@ -692,8 +738,8 @@ def _eva_backward(dout, qkv5, mask_u8, keep, noise, out, saved_list, icfg, fcfg,
         BH, fin = B * h, None
         if defer_chunk_mean:
             Lc = (lcfg.gh // lcfg.chunk) * (lcfg.gw // lcfg.chunk)
-            fin = dict(B=B, gh=lcfg.gh, gw=lcfg.gw, r=lcfg.chunk, C=Lc, scale=float(lcfg.scale), uq=None, qbar=None, lse_t=None,
-                       dpq=_ws_rows(tmp, sizes.bwd_dqmean, BH * Lc * d), dpk=_ws_rows(tmp, sizes.bwd_dkmean, BH * Lc * d))
+            fin = Finish(B=B, gh=lcfg.gh, gw=lcfg.gw, r=lcfg.chunk, C=Lc, scale=float(lcfg.scale),
+                         dpq=_ws_rows(tmp, sizes.bwd_dqmean, BH * Lc * d), dpk=_ws_rows(tmp, sizes.bwd_dkmean, BH * Lc * d))
         if not defer_param_sums:
             return CoreGrads(dqkv5, dbias, _mlp_grads(dpar[:2 * d * d], dpar[2 * d * d:], d), (), fin)
         parts = _param_partials(_ws_rows(tmp, sizes.bwd_dW, BH, 2 * d * d), _ws_rows(tmp, sizes.bwd_dvec, BH, 6 * d))
@@ -702,10 +748,11 @@ def _eva_backward(dout, qkv5, mask_u8, keep, noise, out, saved_list, icfg, fcfg,
         return CoreGrads(dqkv5, dbias, None, parts, fin)
     if defer_chunk_mean:
         raise RuntimeError("eva_bwd: defer_chunk_mean needs the composite entry points")
-    geom, L, mu_scale, keep_scale, fused_mu = _eva_cfg(qkv5, icfg, fcfg, adaptive_proj)
+    geom, fused_mu = _eva_cfg(qkv5, cfg)
+    L, mu_scale = cfg.L, cfg.mu_scale
     bias_p, lse, qmean, kmean, omega, beta, rf_k_bar, saved, zhat, rstd = [_opt(t) for t in saved_list]
     d_rfk, d_beta, dbias = _window_bwd(geom, qkv5, rf_k_bar, beta, bias_p, mask_u8, out,
-                                       _rows_contiguous(dout), lse, dqkv5, keep, keep_scale)
+                                       _rows_contiguous(dout), lse, dqkv5, keep, cfg.keep_scale)
     q, k, v = _qkv_views(qkv5)
     dq, dk, dv = _qkv_views(dqkv5)
     tk, tv, tdq, tdk, tdv = nv.t4(k), nv.t4(v), nv.t4(dq), nv.t4(dk), nv.t4(dv)
@@ -733,8 +780,8 @@ def _eva_backward(dout, qkv5, mask_u8, keep, noise, out, saved_list, icfg, fcfg,
         return CoreGrads(dqkv5, dbias, _mlp_grads(*colsum2_f32(dW.view(lg.BH, -1), dvec.view(lg.BH, -1)), d), (), None)
     # mu networks backward (ea_rows_mlp_bwd): dz, dx = d(chunk means), per-workgroup dW partials
     # and the feed buffer whose column sums are the bias / gamma / beta gradients
-    sides = 1 if adaptive_proj == "none" else 2
-    ln = adaptive_proj != "no-ln"
+    sides = 1 if cfg.adaptive_proj == "none" else 2
+    ln = cfg.adaptive_proj != "no-ln"
     per = 4 if ln else 2
     side_p = [ps[i * per:(i + 1) * per] for i in range(sides)]
     R = B * h * L
@@ -772,41 +819,34 @@ def _eva_backward(dout, qkv5, mask_u8, keep, noise, out, saved_list, icfg, fcfg,
 class EvaAttnFn(torch.autograd.Function):
     """EVA core on a fused qkv tensor (torch.ops.ea.eva_fwd / eva_bwd): chunk means -> mu MLP -> omega ->
     beta -> window attention with control-variate columns.  Returns out [B,N,h,d].
-    cfg = (attn_2d, seq_shape, window, ext, chunk, L, adaptive_proj[, causal, mu_scale[, keep, keep_scale]]);
-    causal / mu_scale select causal_eva.py's geometry, masks (ea_geom.causal) and its mu = rq + rk; keep is
-    the uint8 keep mask of the attention dropout (causal_eva only), scaled by keep_scale = 1 / (1 - p)."""
+    cfg: an EvaCfg; extras: an EvaExtras (keep mask, TableBias, pooled chunk means) or None."""
 
     @staticmethod
-    def forward(ctx, qkv5, bias, noise, mask_u8, cfg, *mlp_params):
-        attn_2d, seq_shape, window, ext, chunk, L, adaptive_proj = cfg[:7]
-        causal, mu_scale = cfg[7:9] if len(cfg) > 7 else (0, 0.5)
-        keep, keep_scale = cfg[9:11] if len(cfg) > 9 else (None, 1.0)
-        icfg = _geo(attn_2d, seq_shape, window, ext) + [int(chunk), int(L), int(causal), int(any(ctx.needs_input_grad))]
-        fcfg = [float(mu_scale), float(keep_scale)]
-        pooled = Pooled(None, *cfg[-1][1:]) if (isinstance(cfg[-1], tuple) and cfg[-1][:1] == ("pooled",)) else None
+    def forward(ctx, qkv5, bias, noise, mask_u8, cfg, extras, *mlp_params):
+        keep, tb, pooled = extras or EvaExtras()
+        icfg, fcfg = cfg.lists(any(ctx.needs_input_grad))
         direct = _DIRECT and not torch.compiler.is_compiling() and torch._C._len_torch_dispatch_stack() == 0
-        # a TableBias anywhere in cfg (round 6; direct calls only): `bias` is the TABLE ([rows, h] or [rows, 1]) and the dense
-        # bias is built from it / its gradient taken back to it in one launch each way
-        tb = next((c for c in cfg if isinstance(c, TableBias)), None)
+        # a TableBias (round 6; direct calls only): `bias` is the TABLE ([rows, h] or [rows, 1]) and the dense bias is built
+        # from it / its gradient taken back to it in one launch each way
         ctx.tb, ctx.tb_heads = tb, None
         if tb is not None:
             if not direct:
                 raise RuntimeError("EvaAttnFn: a TableBias spec needs the direct (untraced) call path")
             B_, N_, _, h_, d_ = qkv5.shape
             ctx.tb_heads = bias.shape[1]
-            bias = tb.dense(bias, tb.ld(B_, h_, N_, d_, nv.io_dtype(qkv5), attn_2d, seq_shape, window, ext, int(chunk), int(L),
-                                        int(causal)), heads=h_)
+            bias = tb.dense(bias, tb.ld(B_, h_, N_, d_, nv.io_dtype(qkv5), cfg.attn_2d, cfg.seq_shape, cfg.window, cfg.ext,
+                                        int(cfg.chunk), int(cfg.L), int(cfg.causal)), heads=h_)
         if pooled is not None:
-            outs = eva_fwd_impl(qkv5, bias, noise, mask_u8, keep, icfg, fcfg, adaptive_proj, list(mlp_params), pooled=pooled)
+            outs = eva_fwd_impl(qkv5, bias, noise, mask_u8, keep, icfg, fcfg, cfg.adaptive_proj, list(mlp_params), pooled=pooled)
         elif direct:
             # round 4: one C-ABI call for the whole core where the geometry allows it (ea_eva_layer_fwd)
-            outs = eva_fwd_impl(qkv5, bias, noise, mask_u8, keep, icfg, fcfg, adaptive_proj, list(mlp_params),
+            outs = eva_fwd_impl(qkv5, bias, noise, mask_u8, keep, icfg, fcfg, cfg.adaptive_proj, list(mlp_params),
                                 composite=_eva_use_composite())
         else:
-            outs = _ea_op("eva_fwd", eva_fwd_impl, qkv5, bias, noise, mask_u8, keep, icfg, fcfg, adaptive_proj, list(mlp_params))
+            outs = _ea_op("eva_fwd", eva_fwd_impl, qkv5, bias, noise, mask_u8, keep, icfg, fcfg, cfg.adaptive_proj, list(mlp_params))
         ctx.save_for_backward(qkv5, mask_u8, keep, noise, *outs, *mlp_params)
         ctx.nsaved = len(outs) - 1
-        ctx.cfg = (icfg, fcfg, adaptive_proj, 0 if bias is None else bias.shape[-1])
+        ctx.cfg, ctx.bias_cols = cfg, 0 if bias is None else bias.shape[-1]
         ctx.pdtypes = [p.dtype for p in mlp_params]
         return outs[0]
 
@@ -814,25 +854,25 @@ class EvaAttnFn(torch.autograd.Function):
     def backward(ctx, dout):
         qkv5, mask_u8, keep, noise, out, *rest = ctx.saved_tensors
         saved, params = rest[:ctx.nsaved], rest[ctx.nsaved:]
-        icfg, fcfg, adaptive_proj, bias_cols = ctx.cfg
-        args = (dout, qkv5, mask_u8, keep, noise, out, list(saved), icfg, fcfg, adaptive_proj, bias_cols, list(params))
+        cfg = ctx.cfg
+        head, tail = (dout, qkv5, mask_u8, keep, noise, out, list(saved)), (ctx.bias_cols, list(params))
         if _eva_saved_is_composite(saved):             # only a direct forward saves a composite workspace
-            g = _eva_backward(*args)
+            g = _eva_backward(*head, cfg, *tail)
         elif ctx.tb is not None and ctx.tb_heads == 1 and BIAS_HEAD_SUM:
             # (a TableBias means a direct call: the implementation runs right here, in this thread)
             _BIAS_HEAD_SUM.on = True
             try:
-                g = _eva_backward(*args)
+                g = _eva_backward(*head, cfg, *tail)
             finally:
                 _BIAS_HEAD_SUM.on = False
         else:
-            g = _ea_op("eva_bwd", eva_bwd_impl, *args)
+            g = _ea_op("eva_bwd", eva_bwd_impl, *head, *cfg.lists(True), cfg.adaptive_proj, *tail)
             g = CoreGrads(g[0], _opt(g[1]), g[2:], (), None)
         pgrads = [t.to(dt) for t, dt in zip(g.params, ctx.pdtypes)]
         dbias = g.dbias
         if ctx.tb is not None and dbias is not None:
             dbias = ctx.tb.grad(dbias, ctx.tb_heads)
-        return (g.dqkv, dbias, None, None, None) + tuple(pgrads)
+        return (g.dqkv, dbias, None, None, None, None) + tuple(pgrads)
 
 
 USE_EVA_MODULE_FN = os.environ.get("EA_EVA_MODULE_FN", "1") == "1"
@@ -1358,39 +1398,74 @@ class LaraAttnFn(torch.autograd.Function):
                 d_lp.view(B, h, C), None, None, None)
 
 
-def _lara_cfg(qkv5, icfg, fcfg):
-    H, W, r, has_mlp, mixed, mis, dup = [int(v) for v in icfg[:7]]
-    kappa, scale = [float(v) for v in fcfg]
+class LaraCfg(typing.NamedTuple):
+    """The 2-D pooled LARA core's configuration (plain values, hashable): r x r pooling of an H x W grid, the generator
+    networks, the MIS flavour (MIS), duplicated samples, kappa = alpha_coeff.  lists() / from_lists() are the ONE encoder and decoder
+    of the int[] / float[] arguments of torch.ops.ea.lara_fwd / lara_bwd:
+    icfg = [H, W, r, has_mlp, mixed, mis, dup(, keep_for_backward = 1)], fcfg = [kappa, scale]."""
+    H: int
+    W: int
+    r: int
+    has_mlp: bool
+    mixed: bool
+    mis: int
+    dup: int
+    kappa: float
+    scale: float
+
+    @property
+    def L(self):
+        return (self.H // self.r) * (self.W // self.r)
+
+    @property
+    def C(self):
+        return self.L * (2 if self.dup else 1)
+
+    def lists(self, need_grad):
+        return ([int(self.H), int(self.W), int(self.r), int(bool(self.has_mlp)), int(bool(self.mixed)), int(self.mis), int(self.dup),
+                 int(bool(need_grad))], [float(self.kappa), float(self.scale)])
+
+    @classmethod
+    def from_lists(cls, icfg, fcfg):
+        """-> (cfg, need_grad); an absent trailing entry means keep for backward."""
+        H, W, r, has_mlp, mixed, mis, dup, *keep = [int(v) for v in icfg]
+        kappa, scale = [float(v) for v in fcfg]
+        return cls(H, W, r, has_mlp, mixed, mis, dup, kappa, scale), not keep or bool(keep[0])
+
+
+def _lara_cfg(qkv5, cfg):
+    """-> the pooling's ea_geom, the landmark pipeline's ea_lmk_geom, the estimator's ea_lara_geom."""
     B, N, _, h, d = qkv5.shape
-    L = (H // r) * (W // r)
-    C = L * (2 if dup else 1)
     io = nv.io_dtype(qkv5)
-    pgeom = nv.make_geom(B, h, N, d, io, True, (H, W), r, 0, r, L)
-    lg = nv.ea_lmk_geom(B * h, L, C, d, has_mlp, mixed, mis, dup, scale, 0)
-    geom = nv.ea_lara_geom(B, h, N, d, io, C, mis, kappa, scale)
-    return (H, W, r, has_mlp, mixed, mis, dup, L, C), pgeom, lg, geom
+    pgeom = nv.make_geom(B, h, N, d, io, True, (cfg.H, cfg.W), cfg.r, 0, cfg.r, cfg.L)
+    lg = nv.ea_lmk_geom(B * h, cfg.L, cfg.C, d, cfg.has_mlp, cfg.mixed, cfg.mis, cfg.dup, cfg.scale, 0)
+    geom = nv.ea_lara_geom(B, h, N, d, io, cfg.C, cfg.mis, cfg.kappa, cfg.scale)
+    return pgeom, lg, geom
+
+
+def _lara_layer_plan(qkv5, cfg):
+    """ea_lara_layer of the composite entry points, or None when the geometry needs the step-by-step path (C > 64)."""
+    B, N, _, h, d = qkv5.shape
+    return _lara_layer_cfg_dims(B, h, d, nv.io_dtype(qkv5), cfg)
 
 
 def _lara_layer_cfg(qkv5, icfg, fcfg):
-    """ea_lara_layer of the composite entry points, or None when the geometry needs the step-by-step path (C > 64)."""
-    B, N, _, h, d = qkv5.shape
-    return _lara_layer_cfg_dims(B, h, d, nv.io_dtype(qkv5), icfg, fcfg)
+    """_lara_layer_plan of an op call's lists (the suite drives the C entries with them)."""
+    return _lara_layer_plan(qkv5, LaraCfg.from_lists(icfg, fcfg)[0])
 
 
 _LARA_LAYER_CFG = {}
 
 
-def _lara_layer_cfg_dims(B, h, d, io, icfg, fcfg):
+def _lara_layer_cfg_dims(B, h, d, io, cfg):
     """(ea_lara_layer, ea_lara_layer_sizes: the workspace plan, read by field name) or (None, None) -- a pure function of the
     geometry, memoised (a host call per query otherwise, twice per eager step)."""
-    key = (B, h, d, io) + tuple(int(v) for v in icfg[:7]) + tuple(float(v) for v in fcfg)
+    key = (B, h, d, io, cfg)
     hit = _LARA_LAYER_CFG.get(key)
     if hit is None:
-        H, W, r, has_mlp, mixed, mis, dup = key[4:11]
-        kappa, scale = key[11:13]
-        cfg = nv.ea_lara_layer(B, h, d, io, H, W, r, has_mlp, mixed, mis, dup, kappa, scale)
+        lcfg = nv.ea_lara_layer(B, h, d, io, cfg.H, cfg.W, cfg.r, cfg.has_mlp, cfg.mixed, cfg.mis, cfg.dup, cfg.kappa, cfg.scale)
         sizes = nv.ea_lara_layer_sizes()
-        hit = (cfg, sizes) if nv.lib().ea_lara_layer_plan(ctypes.byref(cfg), ctypes.byref(sizes)) == 0 else (None, None)
+        hit = (lcfg, sizes) if nv.lib().ea_lara_layer_plan(ctypes.byref(lcfg), ctypes.byref(sizes)) == 0 else (None, None)
         if len(_LARA_LAYER_CFG) < 256:
             _LARA_LAYER_CFG[key] = hit
     return hit
@@ -1416,8 +1491,8 @@ def _lara_saved_is_composite(saved_list):
 
 def lara_fwd_impl(qkv5, mask_u8, noise, icfg, fcfg, params, pooled=None, proj=None):
     """torch.ops.ea.lara_fwd: uniform r x r pooling of q, k -> fused landmark pipeline -> estimator.
-    icfg = [H, W, r, has_mlp, mixed, mis, dup(, keep_for_backward = 1)], fcfg = [kappa, scale], params = (Wq,
-    bq, gq, cq, Wk, bk, gk, ck) when has_mlp.
+    icfg, fcfg: a LaraCfg and the keep-for-backward flag as LaraCfg.lists() encodes them; params = (Wq, bq, gq, cq, Wk, bk,
+    gk, ck) when has_mlp.
     C <= 64: ONE composite C-ABI call (ea_lara_layer_fwd) on two workspaces -> [out, saved workspace].
     Otherwise the step-by-step launch sequence -> [out, omega, qrows, bhv, cst, kv, lse_k, lse_t, pq, pk, noise, lmk_saved, tokst]
     (absent tensors are empty).
@@ -1427,8 +1502,8 @@ def lara_fwd_impl(qkv5, mask_u8, noise, icfg, fcfg, params, pooled=None, proj=No
     combine pass (ea_lara_layer_fwd_proj / ea_lara_out_proj_fwd_merge); where the library declines, by ea_linear after it."""
     global LAST_LMK_GEOM
     nv.require_cuda(qkv5, "qkv")
-    lcfg, sizes = _lara_layer_cfg(qkv5, icfg, fcfg) if _lara_use_composite() else (None, None)
-    need_grad = len(icfg) < 8 or bool(icfg[7])
+    cfg, need_grad = LaraCfg.from_lists(icfg, fcfg)
+    lcfg, sizes = _lara_layer_plan(qkv5, cfg) if _lara_use_composite() else (None, None)
     if pooled is not None and (pooled.ws is not None) != (lcfg is not None):
         raise RuntimeError("lara_fwd: pooled rows prepared for the other launch path")
     B, N, _, h, d = qkv5.shape
@@ -1443,8 +1518,7 @@ def lara_fwd_impl(qkv5, mask_u8, noise, icfg, fcfg, params, pooled=None, proj=No
         noise_c = None if noise is None else noise.float().contiguous()
         ps = [_f32c(t) for t in params]
         pp = _param_ptrs(ps) if ps else None
-        LAST_LMK_GEOM = (B * h, (lcfg.gh // lcfg.pool_r) * (lcfg.gw // lcfg.pool_r),
-                         (lcfg.gh // lcfg.pool_r) * (lcfg.gw // lcfg.pool_r) * (2 if lcfg.dup else 1), d, lcfg.has_mlp, lcfg.mixed, 0)
+        LAST_LMK_GEOM = (B * h, cfg.L, cfg.C, d, cfg.has_mlp, cfg.mixed, 0)
         keep = int(need_grad) | (2 if pooled is not None else 0)
         if proj is not None and nv.call_probe("ea_lara_layer_fwd_proj", "ea_lara_layer_fwd_proj", ctypes.byref(lcfg), ctypes.byref(tq),
                                               ctypes.byref(tk), ctypes.byref(tv), nv.ptr(mask_u8), nv.ptr(noise_c), pp, ctypes.byref(to),
@@ -1456,7 +1530,8 @@ def lara_fwd_impl(qkv5, mask_u8, noise, icfg, fcfg, params, pooled=None, proj=No
         if proj is not None:
             _lara_proj_fallback(out, proj)
         return [out, ws]
-    (H, W, r, has_mlp, mixed, mis, dup, L, C), pgeom, lg, geom = _lara_cfg(qkv5, icfg, fcfg)
+    pgeom, lg, geom = _lara_cfg(qkv5, cfg)
+    L, C, has_mlp, mis = cfg.L, cfg.C, cfg.has_mlp, cfg.mis
     q, k, _ = _qkv_views(qkv5)
     tq, tk = nv.t4(q), nv.t4(k)
     if pooled is not None:
@@ -1468,7 +1543,7 @@ def lara_fwd_impl(qkv5, mask_u8, noise, icfg, fcfg, params, pooled=None, proj=No
                 nv.ptr(pq), nv.ptr(pk), nv.stream())
     noise_c = None if noise is None else noise.float().contiguous()
     ps = [_f32c(t) for t in params]
-    LAST_LMK_GEOM = (BH, L, C, d, has_mlp, mixed, 0)
+    LAST_LMK_GEOM = (BH, L, C, d, has_mlp, cfg.mixed, 0)
     omega = torch.empty((BH, C, d), dtype=torch.float32, device=dev)
     qrows = torch.empty_like(omega) if mis != 2 else None
     bhv = torch.empty((BH, C), dtype=torch.float32, device=dev) if mis == 0 else None
@@ -1485,11 +1560,11 @@ def lara_fwd_impl(qkv5, mask_u8, noise, icfg, fcfg, params, pooled=None, proj=No
 def lara_bwd_impl(dout, qkv5, mask_u8, noise, saved_list, icfg, fcfg, params):
     """torch.ops.ea.lara_bwd -> [dqkv, *parameter gradients (fp32, in the order of params)].  saved_list is what lara_fwd
     returned after `out`: the composite workspace (one tensor -> ea_lara_layer_bwd) or the step-by-step tensors."""
-    g = _lara_backward(dout, qkv5, mask_u8, noise, saved_list, icfg, fcfg, params)
+    g = _lara_backward(dout, qkv5, mask_u8, noise, saved_list, LaraCfg.from_lists(icfg, fcfg)[0], params)
     return [g.dqkv] + g.params
 
 
-def _lara_backward(dout, qkv5, mask_u8, noise, saved_list, icfg, fcfg, params, defer_param_sums=False, defer_finish=False):
+def _lara_backward(dout, qkv5, mask_u8, noise, saved_list, cfg, params, defer_param_sums=False, defer_finish=False):
     """The 2-D pooled LARA core's backward -> CoreGrads (dbias: None).  defer_param_sums: the per-(b,h) partials of the generator
     parameters' gradients wait for the caller's terminal sum; defer_finish (C <= 64, round 5): ea_linear_dgrad_finish applies the
     softmax-over-sequence correction of dq and the pooling terms of dq / dk on its way through the gradient rows."""
@@ -1499,7 +1574,7 @@ def _lara_backward(dout, qkv5, mask_u8, noise, saved_list, icfg, fcfg, params, d
     ps = [_f32c(t) for t in params]
     dqkv5 = torch.empty_like(qkv5)
     if _lara_saved_is_composite(saved_list):
-        lcfg, sizes = _lara_layer_cfg(qkv5, icfg, fcfg)          # pure geometry / size query: valid whenever the forward's was
+        lcfg, sizes = _lara_layer_plan(qkv5, cfg)                # pure geometry / size query: valid whenever the forward's was
         if lcfg is None:
             raise RuntimeError("lara_bwd: a composite workspace was saved for a geometry ea_lara_layer_plan rejects")
         ws = saved_list[0]
@@ -1516,20 +1591,19 @@ def _lara_backward(dout, qkv5, mask_u8, noise, saved_list, icfg, fcfg, params, d
                 ctypes.byref(ts[6]), nv.ptr(ws), nv.ptr(tmp), nv.ptr(dpar), 1 if defer_finish else 0, nv.stream())
         fin = None
         if defer_finish:
-            L = (lcfg.gh // lcfg.pool_r) * (lcfg.gw // lcfg.pool_r)
-            C = L * (2 if lcfg.dup else 1)
-            opt = lcfg.mis == 0
-            fin = dict(B=B, gh=lcfg.gh, gw=lcfg.gw, r=lcfg.pool_r, C=C, scale=float(lcfg.scale),
-                       uq=_ws_rows(tmp, sizes.bwd_uq, BH * C * d) if opt else None,
-                       dpq=_ws_rows(tmp, sizes.bwd_dpq, BH * L * d), dpk=_ws_rows(tmp, sizes.bwd_dpk, BH * L * d),
-                       qbar=_ws_rows(ws, sizes.saved_qrows, BH * C * d) if opt else None,
-                       lse_t=_ws_rows(ws, sizes.saved_lse_t, BH * C) if opt else None)
+            L, C = cfg.L, cfg.C
+            fin = Finish(B=B, gh=cfg.H, gw=cfg.W, r=cfg.r, C=C, scale=float(lcfg.scale),
+                         dpq=_ws_rows(tmp, sizes.bwd_dpq, BH * L * d), dpk=_ws_rows(tmp, sizes.bwd_dpk, BH * L * d))
+            if cfg.mis == 0:
+                fin = fin._replace(uq=_ws_rows(tmp, sizes.bwd_uq, BH * C * d), qbar=_ws_rows(ws, sizes.saved_qrows, BH * C * d),
+                                   lse_t=_ws_rows(ws, sizes.saved_lse_t, BH * C))
         if defer:                      # the per-(b,h) partials, still to be added up: [B*h, 2 d d], [B*h, 6 d]
             parts = _param_partials(_ws_rows(tmp, sizes.bwd_dW, BH, 2 * d * d), _ws_rows(tmp, sizes.bwd_dvec, BH, 6 * d))
             return CoreGrads(dqkv5, None, None, parts, fin)
         return CoreGrads(dqkv5, None, _mlp_grads(dpar[:2 * d * d], dpar[2 * d * d:], d) if ps else [], (), fin)
-    (H, W, r, has_mlp, mixed, mis, dup, L, C), pgeom, lg, geom = _lara_cfg(qkv5, icfg, fcfg)
-    if defer_finish and C > 64:
+    pgeom, lg, geom = _lara_cfg(qkv5, cfg)
+    has_mlp = cfg.has_mlp
+    if defer_finish and cfg.C > 64:
         raise RuntimeError("lara_bwd: defer_finish needs C <= 64 samples")
     omega, qrows, bhv, cst, kv, lse_k, lse_t, pq, pk, saved, tokst = [_opt(t) for t in saved_list]
     dout = dout.contiguous()
@@ -1553,10 +1627,11 @@ def _lara_backward(dout, qkv5, mask_u8, noise, saved_list, icfg, fcfg, params, d
                 nv.ptr(dW), nv.ptr(dvec), nv.ptr(saved), nv.stream())
     fin = None
     if defer_finish:
-        fin = dict(B=B, gh=H, gw=W, r=r, C=C, scale=float(fcfg[1]), uq=uq, dpq=dpq, dpk=dpk,
-                   qbar=qrows if uq is not None else None, lse_t=lse_t if uq is not None else None)
+        fin = Finish(B=B, gh=cfg.H, gw=cfg.W, r=cfg.r, C=cfg.C, scale=cfg.scale, dpq=dpq, dpk=dpk)
+        if uq is not None:
+            fin = fin._replace(uq=uq, qbar=qrows, lse_t=lse_t)
     else:
-        _lara_finish(geom, qkv5, dqkv5, qrows, uq, lse_t, dpq, dpk, (r, H, W))
+        _lara_finish(geom, qkv5, dqkv5, qrows, uq, lse_t, dpq, dpk, (cfg.r, cfg.H, cfg.W))
     if has_mlp and defer_param_sums:
         return CoreGrads(dqkv5, None, None, _param_partials(dW.view(BH, -1), dvec.view(BH, -1)), fin)
     return CoreGrads(dqkv5, None, _mlp_grads(*colsum2_f32(dW.view(BH, -1), dvec.view(BH, -1)), d) if has_mlp else [], (), fin)
@@ -1566,20 +1641,16 @@ class LaraPooledFn(torch.autograd.Function):
     """The whole 2-D LARA core as ONE autograd node (no gradient side channels between nodes): uniform
     r x r average pooling of q, k (lara.py:43,48,145-151) -> fused landmark pipeline (:45-54,157-198,
     214-238) -> estimator (:201-246), through the dispatcher ops torch.ops.ea.lara_fwd / lara_bwd.
-    cfg = (H, W, r, has_mlp, mixed, mis, dup, kappa, scale); params = (Wq, bq, gq, cq, Wk, bk, gk, ck)
-    when has_mlp.  Returns out [B,N,h,d].
+    cfg: a LaraCfg; params = (Wq, bq, gq, cq, Wk, bk, gk, ck) when has_mlp.  Returns out [B,N,h,d].
     Backward: one fused pass per side, the landmark backward, and ONE finish pass that applies the
     softmax-over-sequence correction of dq together with the pooling backward of dq and dk."""
 
     @staticmethod
     def forward(ctx, qkv5, mask_u8, noise, cfg, *params):
-        H, W, r, has_mlp, mixed, mis, dup, kappa, scale = cfg
-        icfg = [int(H), int(W), int(r), int(bool(has_mlp)), int(bool(mixed)), int(mis), int(dup),
-                int(any(ctx.needs_input_grad))]
-        fcfg = [float(kappa), float(scale)]
-        outs = _ea_op("lara_fwd", lara_fwd_impl, qkv5, mask_u8, noise, icfg, fcfg, list(params))
+        ctx.lists = cfg.lists(any(ctx.needs_input_grad))
+        outs = _ea_op("lara_fwd", lara_fwd_impl, qkv5, mask_u8, noise, *ctx.lists, list(params))
         ctx.save_for_backward(qkv5, mask_u8, noise, *outs[1:], *params)
-        ctx.icfg, ctx.fcfg, ctx.nsaved = icfg, fcfg, len(outs) - 1
+        ctx.nsaved = len(outs) - 1
         ctx.pdtypes = [t.dtype for t in params]
         return outs[0]
 
@@ -1587,7 +1658,7 @@ class LaraPooledFn(torch.autograd.Function):
     def backward(ctx, dout):
         qkv5, mask_u8, noise, *rest = ctx.saved_tensors
         saved, params = rest[:ctx.nsaved], rest[ctx.nsaved:]
-        grads = _ea_op("lara_bwd", lara_bwd_impl, dout, qkv5, mask_u8, noise, list(saved), ctx.icfg, ctx.fcfg, list(params))
+        grads = _ea_op("lara_bwd", lara_bwd_impl, dout, qkv5, mask_u8, noise, list(saved), *ctx.lists, list(params))
         pgrads = [g.to(dt) for g, dt in zip(grads[1:], ctx.pdtypes)]
         return (grads[0], None, None, None) + tuple(pgrads)
 
@@ -1689,9 +1760,40 @@ def project_qkv_wsw(x2, wsw, w16q, bq32, cdtype, want_cast, grid=None, pq=None, 
 USE_CORE_MODULE_FN = os.environ.get("EA_CORE_MODULE_FN", "1") == "1"
 
 
-class SoftmaxCore:
-    """Core spec of CoreModuleFn (protocol: its docstring): dropout(softmax(s QK^T)) V (softmax_fwd_impl / softmax_bwd_impl)."""
-    n_inputs = 0
+class Core:
+    """What CoreModuleFn asks of a core spec, the holder of a core's non-differentiable state.  A spec defines fwd and bwd; the
+    other methods default to "nothing to do" / "declined".  `inputs` are the core's differentiable inputs."""
+
+    def setup(self, B, N, heads, d, elem, inputs, need_grad):
+        """Before anything is launched: geometry, derived inputs."""
+
+    def project(self, x2, wq, bq32, cdtype, want, need_dx, w192):
+        """The qkv projection by a kernel that also emits the core's pooled q / k rows (direct calls only)
+        -> (y, rounded x | None, rounded qkv weight | None), or None to decline."""
+        return None
+
+    def fwd(self, qkv5, inputs):
+        """-> out [B,N,h,d], tensors to save."""
+        raise NotImplementedError
+
+    def fwd_project(self, qkv5, inputs, w16p, bp32, cdtype):
+        """fwd with the output projection y2 = out w16p^T + bias formed by the core's last pass (direct calls with the prepared
+        192-wide weights only) -> (out, y2, saved), or None -- before anything is launched or consumed -- to decline."""
+        return None
+
+    def bwd(self, dout, qkv5, out, saved, defer, fin_ok):
+        """-> d qkv5, gradients of `inputs`, partials, fin.  partials: (key, [S, n] fp32, meta) entries for the terminal sum
+        (only when `defer`), else (); fin = (Finish, qkv rows | None) leaves the core's last correction of dq / dk to the
+        input-gradient kernel (qkv_dgrad_finish; only when fin_ok), else None."""
+        raise NotImplementedError
+
+    def scatter(self, sums, grads):
+        """After the terminal sum; sums: key -> (summed partial, meta) -> gradients of `inputs`."""
+        return grads
+
+
+class SoftmaxCore(Core):
+    """Core spec of CoreModuleFn (protocol: Core): dropout(softmax(s QK^T)) V (softmax_fwd_impl / softmax_bwd_impl)."""
 
     def __init__(self, mask_u8, keep=None, keep_scale=1.0):
         self.mask_u8, self.keep, self.keep_scale = mask_u8, keep, float(keep_scale)
@@ -1700,14 +1802,13 @@ class SoftmaxCore:
         out, lse = softmax_fwd_impl(qkv5, self.mask_u8, self.keep, self.keep_scale)
         return out, (lse,)
 
-    def bwd(self, dout, qkv5, out, saved):
-        return softmax_bwd_impl(dout, qkv5, self.mask_u8, out, saved[0], self.keep, self.keep_scale), ()
+    def bwd(self, dout, qkv5, out, saved, defer, fin_ok):
+        return softmax_bwd_impl(dout, qkv5, self.mask_u8, out, saved[0], self.keep, self.keep_scale), (), (), None
 
 
-class LocalCore:
+class LocalCore(Core):
     """Core spec of CoreModuleFn: per-window softmax attention with the dense per-head bias (local_fwd_impl / local_bwd_impl);
     its one differentiable input is the bias [h, Wq, Wk] (or None)."""
-    n_inputs = 1
 
     def __init__(self, mask_u8, attn_2d, seq_shape, window, ext, tb=None):
         self.mask_u8, self.geo = mask_u8, _geo(attn_2d, seq_shape, window, ext)
@@ -1724,18 +1825,17 @@ class LocalCore:
         out, lse, bias_p = local_fwd_impl(qkv5, bias, self.mask_u8, self.geo)
         return out, (lse, bias_p)
 
-    def bwd(self, dout, qkv5, out, saved):
+    def bwd(self, dout, qkv5, out, saved, defer, fin_ok):
         dqkv5, dbias = local_bwd_impl(dout, None, qkv5, _opt(saved[1]), self.mask_u8, out, saved[0], self.geo, self.bias_cols)
         dbias = _opt(dbias)
         if self.tb is not None and dbias is not None:
             dbias = self.tb.grad(dbias)
-        return dqkv5, (dbias,)
+        return dqkv5, (dbias,), (), None
 
 
-class PerformerCore:
+class PerformerCore(Core):
     """Core spec of CoreModuleFn: the Performer core in exact fp32 arithmetic on the 16-bit qkv of an autocast step
     (performer_f32_fwd / performer_f32_bwd); the random features W [h, m, d] carry no gradient."""
-    n_inputs = 0
 
     def __init__(self, mask_u8, W):
         self.mask_u8, self.W = mask_u8, W
@@ -1744,8 +1844,8 @@ class PerformerCore:
         out, p_max, kv, ksum = performer_f32_fwd(qkv5, self.mask_u8, self.W)
         return out, (p_max, kv, ksum)
 
-    def bwd(self, dout, qkv5, out, saved):
-        return performer_f32_bwd(dout, qkv5, self.mask_u8, self.W, saved[0], saved[1], saved[2]), ()
+    def bwd(self, dout, qkv5, out, saved, defer, fin_ok):
+        return performer_f32_bwd(dout, qkv5, self.mask_u8, self.W, saved[0], saved[1], saved[2]), (), (), None
 
 
 USE_LARA_1D_MODULE_FN = os.environ.get("EA_LARA_1D_MODULE_FN", "1") == "1"
@@ -1754,7 +1854,7 @@ EVA_1D_NO_MASK = os.environ.get("EA_EVA_1D_NO_MASK", "1") == "1"            # de
 USE_GRAPH_CORE = os.environ.get("EA_GRAPH_CORE", "1") == "1"                # opt-in subclasses of MultiheadAttention (RA, ScatterBrain)
 
 
-class GraphCore:
+class GraphCore(Core):
     """Core spec of CoreModuleFn for a core that is itself a small autograd graph -- LinearRA 'adaptive-1d': segment kernels ->
     landmark kernels -> estimator, three Functions with hand-overs between them (_GradSlot).  fwd() builds that graph on a
     detached qkv with autograd switched back on (a Function's forward runs without it), bwd() differentiates it with
@@ -1763,8 +1863,8 @@ class GraphCore:
     two ea_wgrad + two ea_part_sum (cfg5 LARA at the recipe's batch of one: 28 launches of ~10 us each, profiles/
     r06_step_trace_cfg5_lara_b1.txt).  fn(qkv5, *inputs) -> out [B,N,h,d]; the differentiable inputs are its parameters."""
 
-    def __init__(self, fn, n_inputs, need_grad):
-        self.fn, self.n_inputs, self.need_grad = fn, int(n_inputs), bool(need_grad)
+    def __init__(self, fn, need_grad):
+        self.fn, self.need_grad = fn, bool(need_grad)
         self.leaf = self.out = self.inputs = None
 
     def fwd(self, qkv5, inputs):
@@ -1776,7 +1876,7 @@ class GraphCore:
         self.leaf, self.out, self.inputs = leaf, out, list(inputs)
         return out.detach(), ()
 
-    def bwd(self, dout, qkv5, out, saved):
+    def bwd(self, dout, qkv5, out, saved, defer, fin_ok):
         if self.out is None:
             raise RuntimeError("GraphCore: backward without a recorded forward (or a second backward through it)")
         idx = [i for i, t in enumerate(self.inputs) if t is not None and t.requires_grad]
@@ -1789,7 +1889,7 @@ class GraphCore:
         self.leaf = self.out = self.inputs = None
         if dqkv5 is None:
             dqkv5 = torch.zeros_like(qkv5)
-        return (dqkv5 if dqkv5.is_contiguous() else dqkv5.contiguous()), tuple(extra)
+        return (dqkv5 if dqkv5.is_contiguous() else dqkv5.contiguous()), tuple(extra), (), None
 
 
 def _pooled_rows(where, BH, L, d, device):
@@ -1815,42 +1915,41 @@ def _project_qkv_grid(x2, wq, bq32, cdtype, want, need_dx, w192, grid, pq, pk):
     return y, xc, w16
 
 
-class EvaCore:
+class EvaCore(Core):
     """Core spec of the module node (EvaModuleFn): the EVA core (eva_fwd_impl / eva_bwd_impl, the composite entry points where
-    the geometry allows).  cfg = EvaAttnFn's first seven entries (+ a TableBias); the differentiable inputs are the dense
-    window bias [h, Wq, Wk] | None -- with a TableBias its TABLE [rows, h] -- and then the mu-network parameters."""
-    defers = True
+    the geometry allows).  cfg: an EvaCfg with its defaults (not causal, no dropout); the differentiable inputs are the dense
+    window bias [h, Wq, Wk] | None -- with table_bias, a TableBias, its TABLE [rows, h] -- and then the mu-network parameters."""
 
-    def __init__(self, mask_u8, noise, cfg):
-        self.mask_u8, self.noise, self.cfg = mask_u8, noise, cfg
-        self.tb = cfg[7] if len(cfg) > 7 else None
+    def __init__(self, mask_u8, noise, cfg, table_bias=None):
+        self.mask_u8, self.noise, self.cfg, self.tb = mask_u8, noise, cfg, table_bias
 
     def setup(self, B, N, heads, d, elem, inputs, need_grad):
-        attn_2d, seq_shape, window, ext, chunk, L, self.adaptive = self.cfg[:7]
+        cfg = self.cfg
         bias = inputs[0]
         if self.tb is not None:
-            bias = self.tb.dense(bias, self.tb.ld(B, heads, N, d, elem, attn_2d, seq_shape, window, ext, int(chunk), int(L), 0))
+            bias = self.tb.dense(bias, self.tb.ld(B, heads, N, d, elem, cfg.attn_2d, cfg.seq_shape, cfg.window, cfg.ext,
+                                                  int(cfg.chunk), int(cfg.L), 0))
         self.bias, self.bias_cols = bias, 0 if bias is None else bias.shape[-1]       # (the dense bias lives until fwd())
-        self.icfg = _geo(attn_2d, seq_shape, window, ext) + [int(chunk), int(L), 0, int(need_grad)]
-        self.fcfg = [0.5, 1.0]
-        self.sizes = (_eva_layer_cfg_dims(B, heads, d, elem, self.icfg, self.fcfg, self.adaptive, bias is not None,
-                                          self.mask_u8 is not None)[1] if _eva_use_composite() else None)    # None: step by step
+        self.lists = cfg.lists(need_grad)
+        self.sizes = (_eva_layer_cfg_dims(B, heads, d, elem, cfg, bias is not None, self.mask_u8 is not None)[1]
+                      if _eva_use_composite() else None)                              # None: step by step
         self.dims, self.pooled = (B, heads, d), None
 
     def project(self, x2, wq, bq32, cdtype, want, need_dx, w192):
-        attn_2d, seq_shape, _, ext, chunk, L = self.cfg[:6]
+        cfg = self.cfg
         B, heads, d = self.dims
-        if not (attn_2d and ext == 0 and self.mask_u8 is None
-                and proj_pool_supported(x2, wq, cdtype, B, seq_shape[0], seq_shape[1], chunk, heads)):
+        if not (cfg.attn_2d and cfg.ext == 0 and self.mask_u8 is None
+                and proj_pool_supported(x2, wq, cdtype, B, cfg.seq_shape[0], cfg.seq_shape[1], cfg.chunk, heads)):
             return None
         pl = self.sizes                                              # (composite: straight into the entry's workspace)
         where = None if pl is None else (pl.n_saved, pl.saved_qmean, pl.saved_kmean)
-        self.pooled, pq, pk = _pooled_rows(where, B * heads, L, d, x2.device)
-        return _project_qkv_grid(x2, wq, bq32, cdtype, want, need_dx, w192, (B, seq_shape[0], seq_shape[1], chunk), pq, pk)
+        self.pooled, pq, pk = _pooled_rows(where, B * heads, cfg.L, d, x2.device)
+        return _project_qkv_grid(x2, wq, bq32, cdtype, want, need_dx, w192, (B, cfg.seq_shape[0], cfg.seq_shape[1], cfg.chunk),
+                                 pq, pk)
 
     def fwd(self, qkv5, inputs):
         bias, pooled, self.bias, self.pooled = self.bias, self.pooled, None, None
-        outs = eva_fwd_impl(qkv5, bias, self.noise, self.mask_u8, None, self.icfg, self.fcfg, self.adaptive, list(inputs[1:]),
+        outs = eva_fwd_impl(qkv5, bias, self.noise, self.mask_u8, None, *self.lists, self.cfg.adaptive_proj, list(inputs[1:]),
                             pooled=pooled, composite=self.sizes is not None)
         self.nsaved = len(outs) - 1
         return outs[0], tuple(outs[1:]) + tuple(inputs[1:])
@@ -1858,8 +1957,8 @@ class EvaCore:
     def bwd(self, dout, qkv5, out, saved, defer, fin_ok):
         saved, params = saved[:self.nsaved], saved[self.nsaved:]
         use_fin = fin_ok and _eva_saved_is_composite(saved)   # round 5: ea_linear_dgrad_finish adds the d(chunk mean) / r^2 terms
-        g = _eva_backward(dout, qkv5, self.mask_u8, None, self.noise, out, list(saved), self.icfg, self.fcfg, self.adaptive,
-                          self.bias_cols, list(params), defer_param_sums=defer, defer_chunk_mean=use_fin)
+        g = _eva_backward(dout, qkv5, self.mask_u8, None, self.noise, out, list(saved), self.cfg, self.bias_cols, list(params),
+                          defer_param_sums=defer, defer_chunk_mean=use_fin)
         return g.dqkv, [g.dbias] + (g.params or []), g.partials, (g.finish, None) if use_fin else None
 
     def scatter(self, res, extra):
@@ -1873,36 +1972,33 @@ class EvaCore:
         return [dbias] + pgrads
 
 
-class LaraCore:
+class LaraCore(Core):
     """Core spec of the module node (LaraModuleFn): the 2-D pooled LARA core (lara_fwd_impl / lara_bwd_impl; through the
-    dispatcher ops while somebody is tracing).  cfg = LaraPooledFn's; the differentiable inputs are the generator parameters."""
-    defers = True
+    dispatcher ops while somebody is tracing).  cfg: a LaraCfg; the differentiable inputs are the generator parameters."""
 
     def __init__(self, mask_u8, noise, cfg):
         self.mask_u8, self.noise, self.cfg = mask_u8, noise, cfg
 
     def setup(self, B, N, heads, d, elem, inputs, need_grad):
-        H, W, r, has_mlp, mixed, mis, dup, kappa, scale = self.cfg
-        self.icfg = [int(H), int(W), int(r), int(bool(has_mlp)), int(bool(mixed)), int(mis), int(dup), int(need_grad)]
-        self.fcfg = [float(kappa), float(scale)]
+        self.lists = self.cfg.lists(need_grad)
         self.dims, self.pooled = (B, heads, d, elem), None
 
     def project(self, x2, wq, bq32, cdtype, want, need_dx, w192):
-        H, W, r = self.icfg[:3]
+        cfg = self.cfg
         B, heads, d, elem = self.dims
-        if not proj_pool_supported(x2, wq, cdtype, B, H, W, r, heads):
+        if not proj_pool_supported(x2, wq, cdtype, B, cfg.H, cfg.W, cfg.r, heads):
             return None
-        pl = _lara_layer_cfg_dims(B, heads, d, elem, self.icfg, self.fcfg)[1] if _lara_use_composite() else None
+        pl = _lara_layer_cfg_dims(B, heads, d, elem, cfg)[1] if _lara_use_composite() else None
         where = None if pl is None else (pl.n_saved, pl.saved_pq, pl.saved_pk)
-        self.pooled, pq, pk = _pooled_rows(where, B * heads, (H // r) * (W // r), d, x2.device)
-        return _project_qkv_grid(x2, wq, bq32, cdtype, want, need_dx, w192, (B, H, W, r), pq, pk)
+        self.pooled, pq, pk = _pooled_rows(where, B * heads, cfg.L, d, x2.device)
+        return _project_qkv_grid(x2, wq, bq32, cdtype, want, need_dx, w192, (B, cfg.H, cfg.W, cfg.r), pq, pk)
 
     def fwd(self, qkv5, inputs):
         pooled, self.pooled = self.pooled, None
         if pooled is not None:
-            outs = lara_fwd_impl(qkv5, self.mask_u8, self.noise, self.icfg, self.fcfg, list(inputs), pooled=pooled)
+            outs = lara_fwd_impl(qkv5, self.mask_u8, self.noise, *self.lists, list(inputs), pooled=pooled)
         else:
-            outs = _ea_op("lara_fwd", lara_fwd_impl, qkv5, self.mask_u8, self.noise, self.icfg, self.fcfg, list(inputs))
+            outs = _ea_op("lara_fwd", lara_fwd_impl, qkv5, self.mask_u8, self.noise, *self.lists, list(inputs))
         self.nsaved = len(outs) - 1
         return outs[0], tuple(outs[1:]) + tuple(inputs)
 
@@ -1911,29 +2007,26 @@ class LaraCore:
         -- before anything is launched or consumed -- where that pass does not apply: not three heads of 64 channels, more
         than 64 samples, the projection switched off (EA_LARA_OUT_PROJ=0)."""
         B, heads, d, elem = self.dims
-        H, W, r = self.icfg[:3]
-        C = (H // r) * (W // r) * (2 if self.icfg[6] else 1)
-        if not (lara_out_proj_on() and heads == 3 and d == 64 and C <= 64 and qkv5.dtype == cdtype and w16p.dtype == cdtype
+        if not (lara_out_proj_on() and heads == 3 and d == 64 and self.cfg.C <= 64 and qkv5.dtype == cdtype and w16p.dtype == cdtype
                 and w16p.is_contiguous() and tuple(w16p.shape) == (192, 192)
                 and (bp32 is None or (bp32.dtype == torch.float32 and bp32.is_contiguous()))):
             return None
         y2 = torch.empty((qkv5.shape[0] * qkv5.shape[1], heads * d), dtype=cdtype, device=qkv5.device)
         proj = [w16p, bp32, y2]
         pooled, self.pooled = self.pooled, None
-        outs = lara_fwd_impl(qkv5, self.mask_u8, self.noise, self.icfg, self.fcfg, list(inputs), pooled=pooled, proj=proj)
+        outs = lara_fwd_impl(qkv5, self.mask_u8, self.noise, *self.lists, list(inputs), pooled=pooled, proj=proj)
         self.nsaved = len(outs) - 1
         return outs[0], proj[2], tuple(outs[1:]) + tuple(inputs)
 
     def bwd(self, dout, qkv5, out, saved, defer, fin_ok):
         saved, params = saved[:self.nsaved], saved[self.nsaved:]
-        args = (dout, qkv5, self.mask_u8, self.noise, list(saved), self.icfg, self.fcfg, list(params))
+        head = (dout, qkv5, self.mask_u8, self.noise, list(saved))
         if not defer:
-            g = _ea_op("lara_bwd", lara_bwd_impl, *args)
+            g = _ea_op("lara_bwd", lara_bwd_impl, *head, *self.lists, list(params))
             return g[0], g[1:], (), None
-        H, W, r = self.icfg[:3]
         # round 5: the finish pass of the core is left to the input-gradient kernel (ea_linear_dgrad_finish: one pass, not two)
-        use_fin = bool(fin_ok and self.icfg[6] == 0 and (H // r) * (W // r) <= 64)
-        g = _lara_backward(*args, defer_param_sums=True, defer_finish=use_fin)
+        use_fin = bool(fin_ok and self.cfg.dup == 0 and self.cfg.L <= 64)
+        g = _lara_backward(*head, self.cfg, list(params), defer_param_sums=True, defer_finish=use_fin)
         fin = (g.finish, qkv5.view(qkv5.shape[0] * qkv5.shape[1], -1)) if use_fin else None
         return g.dqkv, g.params or [], g.partials, fin
 
@@ -1953,18 +2046,7 @@ class CoreModuleFn(torch.autograd.Function):
     16-bit weights of a 192-wide layer (prepare_w192), else the fp32 master weights (linear_w32).  Backward: both weight
     gradients in one launch where possible (ea_wgrad_pair), else the output projection's before the core's backward and the qkv
     projection's after it; all terminal sums -- the weight gradients' slice partials, the core's partials -- in ONE ea_multi_sum.
-    A core spec holds the core's non-differentiable state, with
-        fwd(qkv5, inputs) -> out [B,N,h,d], tensors to save;    bwd(dout, qkv5, out, saved) -> d qkv5, gradients of `inputs`
-    (SoftmaxCore, LocalCore, PerformerCore, GraphCore, _kernelized.KernelizedCore) and optionally (EvaCore, LaraCore)
-        setup(B, N, heads, d, elem, inputs, need_grad): before anything is launched -- geometry, derived inputs
-        project(x2, wq, bq32, cdtype, want, need_dx, w192) -> (y, rounded x | None, rounded qkv weight | None), None to decline:
-            the qkv projection by a kernel that also emits the core's pooled q / k rows (direct calls only)
-        fwd_project(qkv5, inputs, w16p, bp32, cdtype) -> (out, y2, saved), None to decline: fwd with the output projection
-            y2 = out w16p^T + bias formed by the core's last pass (direct calls with the prepared 192-wide weights only)
-        defers = True: bwd(dout, qkv5, out, saved, defer, fin_ok) -> d qkv5, gradients, partials, fin.  partials: (key, [S, n]
-            fp32, meta) entries for the terminal sum (when `defer`); fin = (operands, qkv rows | None) leaves the core's last
-            correction of dq / dk to the input-gradient kernel (qkv_dgrad_finish; only when fin_ok)
-        scatter(sums, gradients) -> gradients of `inputs`, after the terminal sum; sums: key -> (summed partial, meta)."""
+    The core spec's protocol: Core."""
 
     @staticmethod
     def forward(ctx, x, wq, bq, wp, bp, core, cdtype, heads, *inputs):
@@ -1977,8 +2059,7 @@ class CoreModuleFn(torch.autograd.Function):
         # (only LaraModuleFn is reached while somebody is tracing: its projections and core are dispatcher ops then)
         direct = _DIRECT and not torch.compiler.is_compiling() and torch._C._len_torch_dispatch_stack() == 0
         lin = linear_w32_impl if direct else torch.ops.ea.linear_w32
-        if hasattr(core, "setup"):
-            core.setup(B, N, heads, d, elem, inputs, any(need))
+        core.setup(B, N, heads, d, elem, inputs, any(need))
         bq32 = None if bq is None else (bq if bq.dtype == torch.float32 else bq.float())
         bp32 = None if bp is None else (bp if bp.dtype == torch.float32 else bp.float())
         want = x2.dtype == torch.float32 and need[1]
@@ -1991,8 +2072,7 @@ class CoreModuleFn(torch.autograd.Function):
             y, xc = lib_project(x2, wq, bq32, w16q, b16q, cdtype)
             want = True
         else:
-            project = getattr(core, "project", None) if direct else None
-            done = None if project is None else project(x2, wq, bq32, cdtype, want, need[0], w192)
+            done = core.project(x2, wq, bq32, cdtype, want, need[0], w192) if direct else None
             if done is not None:
                 y, xc, w16q = done
             elif w192 is not None:
@@ -2003,8 +2083,7 @@ class CoreModuleFn(torch.autograd.Function):
         xl = x2 if x2.dtype == cdtype else (xc if want else None)
         qkv5 = y.view(B, N, 3, heads, d)
         # the output projection inside the core's last pass, where the core offers it (LaraCore.fwd_project, ABI 29)
-        fwd_project = getattr(core, "fwd_project", None) if (direct and w192 is not None) else None
-        done = None if fwd_project is None else fwd_project(qkv5, inputs, w192[2], bp32, cdtype)
+        done = core.fwd_project(qkv5, inputs, w192[2], bp32, cdtype) if (direct and w192 is not None) else None
         if done is not None:
             out, y2, saved = done
         else:
@@ -2068,12 +2147,9 @@ class CoreModuleFn(torch.autograd.Function):
             dbp = bias_grad(dy2 if dy2.is_contiguous() else dy2.contiguous()).to(bpd)
         B, N = qkv5.shape[:2]
         dout, out = d_o2.view(B, N, heads, d), o2.view(B, N, heads, d)
-        if getattr(core, "defers", False):
-            dqkv5, extra, parts, fin = core.bwd(dout, qkv5, out, saved, defer,
-                                                bool(need[0] and dgrad_finish_usable(qkv2, wq, xdtype, heads, d)))
-            pend += parts
-        else:
-            (dqkv5, extra), fin = core.bwd(dout, qkv5, out, saved), None
+        dqkv5, extra, parts, fin = core.bwd(dout, qkv5, out, saved, defer,
+                                            bool(need[0] and dgrad_finish_usable(qkv2, wq, xdtype, heads, d)))
+        pend += parts
         dqkv2 = dqkv5.view(-1, 3 * C)
         if fin is not None:
             # corrects the dq / dk columns of dqkv2 in place: BEFORE the weight gradient reads them
@@ -2102,8 +2178,7 @@ class CoreModuleFn(torch.autograd.Function):
             if "qkv" in res:
                 dwq, dbq = _wgrad_split(*res["qkv"])
                 dwq, dbq = dwq.to(wqd), (dbq.to(bqd) if need_bq else None)
-        if hasattr(core, "scatter"):
-            extra = core.scatter(res, extra)
+        extra = core.scatter(res, extra)
         egrads = tuple(None if (g is None or dt is None) else g.to(dt) for g, dt in zip(extra, in_dtypes))
         return (dx, dwq, dbq, dwp, dbp, None, None, None) + egrads
 
@@ -2859,8 +2934,10 @@ def dgrad_finish_usable(dqkv2, wq, xdtype, heads, d):
 
 def qkv_dgrad_finish(dqkv2, qkv2, wq, w16, xdtype, fin, wt=None):
     """dx = dqkv2 @ W after the LAST corrections of the dq / dk columns of dqkv2 (in place) -- ea_linear_dgrad_finish, one pass:
-    LARA: fin = dict(B, gh, gw, r, C, scale, qbar, uq, lse_t, dpq, dpk) from _lara_backward(defer_finish=True) (lara.py:223,
-    43,48,145-151 differentiated); EVA: uq = qbar = lse_t = None, dpq / dpk = the chunk-mean gradients (eva.py:178-181)."""
+    fin: a Finish (or its fields as a dict) -- LARA: from _lara_backward(defer_finish=True) (lara.py:223, 43,48,145-151
+    differentiated); EVA: uq = qbar = lse_t = None, dpq / dpk = the chunk-mean gradients (eva.py:178-181)."""
+    if isinstance(fin, dict):
+        fin = Finish(**fin)
     rows = dqkv2.shape[0]
     cdtype = dqkv2.dtype
     w, w_kind = _dgrad_weight(wq, w16, wt, cdtype)
@@ -2869,13 +2946,13 @@ def qkv_dgrad_finish(dqkv2, qkv2, wq, w16, xdtype, fin, wt=None):
     dx = torch.empty((rows, 192), dtype=xdtype, device=dqkv2.device)
     label = "ea_linear_dgrad_finish"
     if nv.KERNEL_TIMER.enabled:
-        label = "ea_linear_dgrad_finish[576->192,16->%s%s]" % ("f32" if xdtype == torch.float32 else "16", ",+t" if fin.get("uq") is not None else "")
+        label = "ea_linear_dgrad_finish[576->192,16->%s%s]" % ("f32" if xdtype == torch.float32 else "16", ",+t" if fin.uq is not None else "")
         # dqkv read + dq, dk rewritten, dx written, q read for the t correction
-        _note_bytes(label, rows * (576 * 2 + 384 * 2 + 192 * dx.element_size() + (192 * 2 if fin.get("uq") is not None else 0)))
-    nv.call_as(label, "ea_linear_dgrad_finish", _ELEM[cdtype], fin["B"], fin["gh"], fin["gw"], fin["r"], fin["C"], fin["scale"],
+        _note_bytes(label, rows * (576 * 2 + 384 * 2 + 192 * dx.element_size() + (192 * 2 if fin.uq is not None else 0)))
+    nv.call_as(label, "ea_linear_dgrad_finish", _ELEM[cdtype], fin.B, fin.gh, fin.gw, fin.r, fin.C, fin.scale,
                nv.ptr(dqkv2), dqkv2.stride(0), nv.ptr(qkv2), 0 if qkv2 is None else qkv2.stride(0), nv.ptr(w),
-               w_kind, nv.ptr(dx), int(xdtype == torch.float32), 192, nv.ptr(fin.get("qbar")),
-               nv.ptr(fin.get("uq")), nv.ptr(fin.get("lse_t")), nv.ptr(fin.get("dpq")), nv.ptr(fin.get("dpk")), nv.stream())
+               w_kind, nv.ptr(dx), int(xdtype == torch.float32), 192, nv.ptr(fin.qbar),
+               nv.ptr(fin.uq), nv.ptr(fin.lse_t), nv.ptr(fin.dpq), nv.ptr(fin.dpk), nv.stream())
     return dx
 
 

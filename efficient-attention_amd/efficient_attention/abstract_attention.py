@@ -135,7 +135,7 @@ class MultiheadAttention(nn.Module):
             return None, ()
         params = tuple(getattr(self, n) for n in names)
         need = torch.is_grad_enabled()
-        return _ops.GraphCore(lambda qkv5, *ps: self._attend(qkv5, key_padding_mask, seq_shape), len(params), need), params
+        return _ops.GraphCore(lambda qkv5, *ps: self._attend(qkv5, key_padding_mask, seq_shape), need), params
 
     def _attend(self, qkv5, key_padding_mask, seq_shape):
         B, N = qkv5.shape[:2]

@@ -246,21 +246,29 @@ class CausalEVAttention(CevaDecoding, _ops.DerivedCacheOwner, nn.Module):
                                            _ops._mask_u8(mask, B, N, x.device), w, e, r, bool(self.causal), mu_fn,
                                            *self._dropout_keep(B, h, N, w + e, L, x.device, raw=True)).to(qkv5.dtype)
         else:
-            cfg = (False, (N,), w, e, r, L, "default" if self.adaptive_proj == "qk" else "no-ln",
-                   2 if self.causal else 1, 1.0) + (self._dropout_keep(B, h, N, w + e, L, x.device) or (None, 1.0))
+            cfg, keep = self._core_cfg(B, N, r, L, x.device)
+            tb = None
             if tb_ok:
                 # round 6: the single-head T5 table handed over as it is -- the [h, w, w + e] bias built from it, and its
                 # gradient taken back to it, by one launch each way inside the core's node (_ops.TableBias)
-                bias = self.rel_pos_bias.relative_attention_bias.weight
-                cfg = cfg + (self.rel_pos_bias.table_spec(w, w + e),)
+                bias, tb = self.rel_pos_bias.relative_attention_bias.weight, self.rel_pos_bias.table_spec(w, w + e)
             out = _ops.EvaAttnFn.apply(qkv5, bias, noise, _ops._mask_u8(mask, B, N, x.device), cfg,
-                                       *self._mu_params())
+                                       _ops.EvaExtras(keep=keep, table_bias=tb), *self._mu_params())
         # out [B, N, h, d] comes back as a view of a time-first buffer (it follows qkv's layout)
         self._quant_noise_(self.out_proj)
         y = self._project_out(out.transpose(0, 1).reshape(N, B, C), query.dtype)
         if N != tgt_len:
             y = y[:tgt_len]
         return y.contiguous(), None
+
+    def _core_cfg(self, B, N, r, L, device):
+        """-> (the _ops.EvaCfg of this module's core: 1-D windows, causal or not, mu = rq + rk; the attention dropout's keep mask
+        or None -- drawn here)."""
+        w, e = self.window_size, self.ext_size
+        keep, keep_scale = self._dropout_keep(B, self.num_heads, N, w + e, L, device) or (None, 1.0)
+        return _ops.EvaCfg(attn_2d=False, seq_shape=(N,), window=w, ext=e, chunk=r, L=L,
+                           adaptive_proj="default" if self.adaptive_proj == "qk" else "no-ln",
+                           causal=2 if self.causal else 1, mu_scale=1.0, keep_scale=keep_scale), keep
 
     def _project_out(self, x, dtype):
         """Attention rows [N, B, C] -> out_proj, in the caller's dtype outside autocast (the full path and decoding)."""
@@ -304,24 +312,21 @@ class CausalEVAttention(CevaDecoding, _ops.DerivedCacheOwner, nn.Module):
         mask_u8 = _ops._mask_u8(mask, B, N, x.device)
         mu = self._mu_params()
         table = self.rel_pos_bias.relative_attention_bias.weight if self.use_t5_rpe else None
-        adaptive = "default" if self.adaptive_proj == "qk" else "no-ln"
 
         def core(qkv_tf, *params):                       # [N, B, 3, h, d] time-first -> out [N, B, h, d]
             qkv5 = qkv_tf.transpose(0, 1)
-            cfg = (False, (N,), w, e, r, L, adaptive, 2 if self.causal else 1, 1.0) \
-                + (self._dropout_keep(B, h, N, w + e, L, x.device) or (None, 1.0))
-            bias = None
+            cfg, keep = self._core_cfg(B, N, r, L, x.device)
+            bias = tb = None
             if tb_ok:
-                bias = table
-                cfg = cfg + (self.rel_pos_bias.table_spec(w, w + e),)
+                bias, tb = table, self.rel_pos_bias.table_spec(w, w + e)
             elif self.use_t5_rpe:
                 bias = self.rel_pos_bias.dense(w, w + e, x.device).expand(h, w, w + e)
-            out = _ops.EvaAttnFn.apply(qkv5, bias, noise, mask_u8, cfg, *mu)
+            out = _ops.EvaAttnFn.apply(qkv5, bias, noise, mask_u8, cfg, _ops.EvaExtras(keep=keep, table_bias=tb), *mu)
             return out.transpose(0, 1)
 
         inputs = ([table] if table is not None else []) + list(mu)
         y = _ops.CoreModuleFn.apply(x, wq, bq, self.out_proj.weight, self.out_proj.bias,
-                                    _ops.GraphCore(core, len(inputs), True), cdtype, h, *inputs)
+                                    _ops.GraphCore(core, True), cdtype, h, *inputs)
         return y
 
     def _dropout_keep(self, B, h, N, Wk, L, device, raw=False):

@@ -196,9 +196,10 @@ class EVA(LocalAttention):
                 if self.training:
                     noise = torch.randn_like(torch.empty(B, h, L0, d, device=x.device, dtype=torch.float32))
                 mask = _ops._mask_u8(key_padding_mask, B, N, x.device)
-                cfg = (self.attn_2d, tuple(seq_shape), w, e, r0, L0, self.adaptive_proj) + ((tb,) if tb is not None else ())
+                cfg = _ops.EvaCfg(attn_2d=self.attn_2d, seq_shape=tuple(seq_shape), window=w, ext=e, chunk=r0, L=L0,
+                                  adaptive_proj=self.adaptive_proj)
                 y = _ops.EvaModuleFn.apply(x, self.qkv.weight, self.qkv.bias, self.proj.weight, self.proj.bias,
-                                           _ops.EvaCore(mask, noise, cfg), cdt, h, bias, *self._mu_params())
+                                           _ops.EvaCore(mask, noise, cfg, table_bias=tb), cdt, h, bias, *self._mu_params())
                 y = self.proj_drop(y)
                 if not self.attn_2d:
                     y = y[..., :orig_n, :]
@@ -216,7 +217,7 @@ class EVA(LocalAttention):
                 y, pq, pk = _ops.LinearPoolFn.apply(x.reshape(B, N, C), self.qkv.weight, self.qkv.bias,
                                                     torch.get_autocast_dtype("cuda"), grid)
                 qkv5 = y.reshape(B, N, 3, h, d)
-                pooled = ("pooled", pq, pk)
+                pooled = _ops.Pooled(None, pq, pk)
         else:
             r = int(N // self.num_landmarks)
             L = N // r
@@ -235,9 +236,8 @@ class EVA(LocalAttention):
         if self.training:
             noise = torch.randn_like(torch.empty(B, h, L, d, device=x.device, dtype=torch.float32))
         mask = _ops._mask_u8(key_padding_mask, B, N, x.device)
-        cfg = (self.attn_2d, tuple(seq_shape), w, e, r, L, self.adaptive_proj)
-        if pooled is not None:
-            cfg = cfg + (0, 0.5, None, 1.0, pooled)
+        cfg = _ops.EvaCfg(attn_2d=self.attn_2d, seq_shape=tuple(seq_shape), window=w, ext=e, chunk=r, L=L,
+                          adaptive_proj=self.adaptive_proj)
         if qkv5.dtype == torch.float32:
             # fp32 outside autocast (round 5): the core on the fp32-faithful kernels, the mu networks as the module's own layers
             out = _f32.eva_core(qkv5, bias, noise, mask, self.attn_2d, tuple(seq_shape), w, e, r, self._mu_f32)
@@ -248,7 +248,7 @@ class EVA(LocalAttention):
                 out = _f32.eva_core(qkv5.float(), None if bias is None else bias.float(), noise, mask, self.attn_2d,
                                     tuple(seq_shape), w, e, r, self._mu_f32).to(qkv5.dtype)
         else:
-            out = _ops.EvaAttnFn.apply(qkv5, bias, noise, mask, cfg, *self._mu_params())
+            out = _ops.EvaAttnFn.apply(qkv5, bias, noise, mask, cfg, _ops.EvaExtras(pooled=pooled), *self._mu_params())
         y = self.merge_and_project(out, B, seq_shape, C, x.dtype)
         if not self.attn_2d:
             y = y[..., :orig_n, :]

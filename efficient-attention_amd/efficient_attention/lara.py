@@ -309,8 +309,9 @@ class LinearRA(_ops.DerivedCacheOwner, MultiheadAttention):
             # pooling + landmark pipeline + estimator as one autograd node (_ops.LaraPooledFn)
             params = self._mlp_params() if gen.startswith('pool') else ()
             noise = self._draw_noise(B, n_lm, x.device)
-            cfg = (seq_shape[0], seq_shape[1], seq_shape[0] // side, bool(params), gen.endswith('mixed'),
-                   _ops.MIS[self.mis_type], mode if noise is not None else 0, float(self.alpha_coeff), float(self.scale))
+            cfg = _ops.LaraCfg(H=seq_shape[0], W=seq_shape[1], r=seq_shape[0] // side, has_mlp=bool(params),
+                               mixed=gen.endswith('mixed'), mis=_ops.MIS[self.mis_type], dup=mode if noise is not None else 0,
+                               kappa=float(self.alpha_coeff), scale=float(self.scale))
             if module_fn:
                 y = _ops.LaraModuleFn.apply(x, self.qkv.weight, self.qkv.bias, self.proj.weight, self.proj.bias,
                                             _ops.LaraCore(mask, noise, cfg), torch.get_autocast_dtype("cuda"), h, *params)
@@ -374,7 +375,7 @@ class LinearRA(_ops.DerivedCacheOwner, MultiheadAttention):
         params = (lq.weight, lq.bias, lk.weight, lk.bias, nq.weight, nq.bias, nk.weight, nk.bias)
         need_grad = torch.is_grad_enabled() and (x.requires_grad or any(p.requires_grad for p in self.parameters()))
         y = _ops.CoreModuleFn.apply(x, self.qkv.weight, self.qkv.bias, self.proj.weight, self.proj.bias,
-                                    _ops.GraphCore(core, len(params), need_grad), torch.get_autocast_dtype("cuda"), h, *params)
+                                    _ops.GraphCore(core, need_grad), torch.get_autocast_dtype("cuda"), h, *params)
         return self.proj_drop(y)
 
     @staticmethod

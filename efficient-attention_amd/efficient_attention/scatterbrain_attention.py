@@ -93,7 +93,7 @@ class ScatterBrain(KernelizedAttention, LocalAttention):
                 and _ops.core_module_fn_supported(xs, self.qkv, self.proj, torch.get_autocast_dtype("cuda"))):
             params = (self.local_relative_position_bias_table,) if self.use_rpe else ()
             shape = list(seq_shape)
-            core = _ops.GraphCore(lambda qkv5, *ps: self._scatter(qkv5, mask, shape), len(params), torch.is_grad_enabled())
+            core = _ops.GraphCore(lambda qkv5, *ps: self._scatter(qkv5, mask, shape), torch.is_grad_enabled())
             y = _ops.CoreModuleFn.apply(xs, self.qkv.weight, self.qkv.bias, self.proj.weight, self.proj.bias, core,
                                         torch.get_autocast_dtype("cuda"), self.num_heads, *params)
             y = self.proj_drop(y.view(B, *seq_shape, C))
