@@ -41,7 +41,7 @@ static Geo mk_geo(const ea_geom* g) {
 extern "C" {
 
 const char* ea_version(void) { return "ea_hip 0.1.0 gfx950"; }
-int32_t ea_abi_version(void) { return 31; }
+int32_t ea_abi_version(void) { return 32; }
 
 int32_t ea_window_bias_ld(const ea_geom* g) {
   WinTiling t;
@@ -2348,6 +2348,33 @@ static ea::DecSampleP dec_sample_fill(int V, const void* ws, float* logits, int6
   return s;
 }
 
+// the state and the outputs of a merge, the optional reports and the scalars but for the envelope: that one is geometry
+static bool dec_beam_ok(int W, int eos, int max_new, const float* score, const int32_t* t, const int32_t* nfin,
+                        const int32_t* done, const int64_t* token, const int64_t* parent, const int32_t* hist_tok,
+                        const int32_t* hist_par, const float* fin_score, const int32_t* fin_len, const int32_t* fin_beam,
+                        const int32_t* cand_idx, const float* cand_score, const float* lse, const float* sel_val) {
+  if (!score || !t || !nfin || !done || !token || !parent || !hist_tok || !hist_par || !fin_score || !fin_len || !fin_beam)
+    return false;
+  if ((uintptr_t)token % 8 || (uintptr_t)parent % 8) return false;
+  for (const void* q : {(const void*)score, (const void*)t, (const void*)nfin, (const void*)done, (const void*)hist_tok,
+                        (const void*)hist_par, (const void*)fin_score, (const void*)fin_len, (const void*)fin_beam,
+                        (const void*)cand_idx, (const void*)cand_score, (const void*)lse, (const void*)sel_val})
+    if ((uintptr_t)q % 4) return false;
+  return W >= 1 && eos >= 0 && max_new >= 1;
+}
+
+// the merge's block: what ea_beam_merge reads; ea_ceva_sdecode_vocab_beam adds the row kernel's fields
+static ea::DecBeamP dec_beam_fill(int S, int W, int kc, int eos, int max_new, float* score, int32_t* t, int32_t* nfin,
+                                  int32_t* done, int64_t* token, int64_t* parent, int32_t* hist_tok, int32_t* hist_par,
+                                  float* fin_score, int32_t* fin_len, int32_t* fin_beam, int32_t* cand_idx,
+                                  float* cand_score) {
+  ea::DecBeamP b = {};
+  b.S = S; b.W = W; b.kc = kc; b.eos = eos; b.max_new = max_new; b.score = score; b.t = t; b.nfin = nfin; b.done = done;
+  b.token = token; b.parent = parent; b.hist_tok = hist_tok; b.hist_par = hist_par; b.fin_score = fin_score;
+  b.fin_len = fin_len; b.fin_beam = fin_beam; b.cand_idx = cand_idx; b.cand_score = cand_score;
+  return b;
+}
+
 extern "C" {
 
 int ea_ceva_sdecode_linear(int32_t M, int32_t K, int32_t N, const void* x, int32_t x_dtype, int64_t ldx,
@@ -2455,6 +2482,46 @@ int ea_ceva_sdecode_vocab_sample_logprob(int32_t M, int32_t K, int32_t V, const 
   const ea::DecSampleP s = dec_sample_fill(V, ws, logits, ldl, top_k, top_p, temperature, seed, ctr, sid, token, sel_idx,
                                            sel_val, kept);
   return ea::ceva_sdecode_vocab_sample_logprob(p, s, (hipStream_t)stream);
+}
+
+// ---- the beam step (ABI 32): the table operands, the logits, the workspace, then the beam's state and outputs; the
+// geometry last -------------------------------------------------------------------------------------------------------------
+int64_t ea_ceva_sdecode_vocab_beam_ws(int32_t M, int32_t V, int32_t W) { return ea::ceva_sdecode_vocab_beam_ws(M, V, W); }
+
+// (the logits are required and fp32)
+int ea_ceva_sdecode_vocab_beam(int32_t M, int32_t K, int32_t V, const void* x, int32_t x_dtype, int64_t ldx,
+                               const void* w, int32_t w_dtype, float* logits, int64_t ldl, void* ws, int64_t ws_bytes,
+                               int32_t W, int32_t eos, int32_t max_new, float* score, int32_t* t, int32_t* nfin,
+                               int32_t* done, int64_t* token, int64_t* parent, int32_t* hist_tok, int32_t* hist_par,
+                               float* fin_score, int32_t* fin_len, int32_t* fin_beam, int32_t* cand_idx, float* cand_score,
+                               float* lse, float* sel_val, void* stream) {
+  if (!dec_table_ok(M, K, x, x_dtype, ldx, w, w_dtype) || !logits || !dec_logits_ok(V, logits, EA_F32, ldl, w_dtype) ||
+      !ws || (uintptr_t)ws % 16 ||
+      !dec_beam_ok(W, eos, max_new, score, t, nfin, done, token, parent, hist_tok, hist_par, fin_score, fin_len, fin_beam,
+                   cand_idx, cand_score, lse, sel_val) || (V >= 1 && eos >= V)) return EA_E_BADARG;
+  const int64_t need = ea::ceva_sdecode_vocab_beam_ws(M, V, W);
+  if (need >= 0 && ws_bytes < need) return EA_E_BADARG;
+  if (W > 32 || M % W || !dec_vocab_geometry_ok(M, K, V) || need < 0) return EA_E_UNSUPPORTED;
+  ea::DecLseP p = {};
+  dec_vocab_fill(&p, M, K, V, x, x_dtype, ldx, w, w_dtype, logits, EA_F32, ldl, ws);
+  ea::DecBeamP b = dec_beam_fill(M / W, W, 2 * W < V ? 2 * W : V, eos, max_new, score, t, nfin, done, token, parent, hist_tok,
+                                 hist_par, fin_score, fin_len, fin_beam, cand_idx, cand_score);
+  b.logits = logits; b.ldl = ldl; b.V = V; b.lse = lse; b.sel_val = sel_val;
+  ea::ceva_sdecode_vocab_beam_carve(ws, &p, &b);
+  p.token = token;                                        // (required by the block; the table pass does not write it)
+  return ea::ceva_sdecode_vocab_beam(p, b, (hipStream_t)stream);
+}
+
+int ea_beam_merge(int32_t S, int32_t W, int32_t kc, const int32_t* cand_idx, const float* cand_score, int32_t eos,
+                  int32_t max_new, float* score, int32_t* t, int32_t* nfin, int32_t* done, int64_t* token, int64_t* parent,
+                  int32_t* hist_tok, int32_t* hist_par, float* fin_score, int32_t* fin_len, int32_t* fin_beam, void* stream) {
+  if (S < 1 || !cand_idx || !cand_score ||
+      !dec_beam_ok(W, eos, max_new, score, t, nfin, done, token, parent, hist_tok, hist_par, fin_score, fin_len, fin_beam,
+                   cand_idx, cand_score, nullptr, nullptr) || kc < 1 || kc > 2 * (int64_t)W) return EA_E_BADARG;
+  if (W > 32 || (int64_t)S * W > EA_CEVA_LINEAR_MAX_ROWS) return EA_E_UNSUPPORTED;
+  const ea::DecBeamP b = dec_beam_fill(S, W, kc, eos, max_new, score, t, nfin, done, token, parent, hist_tok, hist_par,
+                                       fin_score, fin_len, fin_beam, (int32_t*)cand_idx, (float*)cand_score);
+  return ea::ceva_beam_merge(b, (hipStream_t)stream);
 }
 
 // ---- the many-row vocabulary pass (ABI 30, ea_vocab_score.hip): the few-row entries' groups in their order -- the table

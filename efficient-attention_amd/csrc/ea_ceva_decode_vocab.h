@@ -73,6 +73,43 @@ struct DecLseP {
   int x_f32, l_f32;           // 1: fp32 rows (x is rounded to `dtype` on load)
 };
 
+// the beam step (ABI 32): the parameter block of ceva_vocab_beam_rows_kernel (one workgroup per row, behind the table pass
+// on DecLseP) and of ceva_vocab_beam_merge_kernel (one workgroup per sentence); a block of its own: the others stay what
+// they are.  M = S W rows, row s W + b is beam b of sentence s.  The merge alone reads from cand_idx on.
+struct DecBeamP {
+  const VocPick* ws;          // [M, ceil(V / 16)] candidates of the table pass
+  const float* lws;           // [M, ceil(V / 16)] its tile sums
+  const float* logits;        // [M, ldl] its fp32 logits
+  float* lse;                 // [M]
+  float* sel_val;             // [M, 2 W] the selected logits, or null
+  int64_t ldl;
+  int V;
+  int32_t* cand_idx;          // [M, 2 W] a row's candidates in order, kc live (the forced step: 1)
+  float* cand_score;          // [M, 2 W] score[m] + (logit - lse[m])
+  float* score;               // [M] in / out: the beams' cumulative scores
+  int32_t* t;                 // [S] in / out: tokens generated
+  int32_t* nfin;              // [S] in / out: finished hypotheses
+  int32_t* done;              // [S] in / out
+  int64_t* token;             // [M]
+  int64_t* parent;            // [M] global rows: reorder_incremental_state's new_order
+  int32_t* hist_tok;          // [max_new, M]
+  int32_t* hist_par;          // [max_new, M] beams
+  float* fin_score;           // [S, W]
+  int32_t* fin_len;           // [S, W]
+  int32_t* fin_beam;          // [S, W]
+  int S, W, kc, eos, max_new;
+};
+
+// bytes of the beam step's workspace for (M, V, W); < 0: outside the envelope
+int64_t ceva_sdecode_vocab_beam_ws(int M, int V, int W);
+// p's and b's workspace pointers from one buffer of that size (p->M, p->V, b->W are read; b's candidate lists and lse stay
+// where the caller has put them)
+void ceva_sdecode_vocab_beam_carve(void* ws, DecLseP* p, DecBeamP* b);
+// the table pass with tile sums on p, then the rows and the merge kernel on b
+int ceva_sdecode_vocab_beam(const DecLseP& p, const DecBeamP& b, hipStream_t st);
+// the merge kernel alone, on the caller's candidate lists
+int ceva_beam_merge(const DecBeamP& b, hipStream_t st);
+
 // bytes of ws for (M, V); < 0: outside the envelope
 int64_t ceva_sdecode_vocab_ws(int M, int V);
 int ceva_sdecode_vocab_argmax(const DecVocabP& p, hipStream_t st);

@@ -29,21 +29,9 @@ constexpr int PICK_THREADS = 512;
 
 static_assert(sizeof(VocPick) == 8, "a candidate is one 8-byte store");
 
-// The launch behind the table pass that picks: one workgroup per row reduces the row's candidates.  On DecLseP
-// (ABI 28; the table pass has also written s_t = sum_columns exp(logit - m_t) of every tile to lws[m][tile]) it goes on: it
-// folds the tile sums into lse[m] = top + log(sum_t s_t exp(m_t - top)) and writes logp[m] = (the token's, the target's or
-// the top logit) - lse[m]: the log-probability under the model's own distribution at temperature 1, nothing truncated.
-template <typename P>
-__global__ __launch_bounds__(PICK_THREADS) void ceva_vocab_pick_kernel(const P p) {
-  constexpr bool LSE = std::is_same<P, DecLseP>::value;
-  static_assert(LSE || std::is_same<P, DecVocabP>::value, "one of the two blocks that pick");
-  __shared__ VocPick best[PICK_THREADS / 64];
-  __shared__ float part[PICK_THREADS / 64];
-  __shared__ float top_of_row;
-  const int m = blockIdx.x;
-  const int NB = (p.V - 1) / VOC_TILE + 1;
-  const VocPick* row = p.ws + (int64_t)m * NB;
-  // pass 1: the pick
+// The best of a row's NB candidates under voc_beats' rule -> thread 0's return value.  Every thread of the PICK_THREADS
+// calls it; best [PICK_THREADS / 64].
+EA_DEV VocPick voc_row_best(const VocPick* row, int NB, VocPick* best) {
   VocPick c = voc_none();
 #pragma unroll 4
   for (int j = threadIdx.x; j < NB; j += PICK_THREADS) {
@@ -61,6 +49,52 @@ __global__ __launch_bounds__(PICK_THREADS) void ceva_vocab_pick_kernel(const P p
 #pragma unroll
     for (int w = 1; w < PICK_THREADS / 64; ++w)
       if (voc_beats(best[w], c)) c = best[w];
+  }
+  return c;
+}
+
+// S = sum_t s_t exp(m_t - top) over the tiles that hold a number (a finite top: every m_t is finite or -inf, every
+// exponent <= 0; a tile of -inf alone is skipped, never multiplied) -> thread 0's return value; `top` is uniform.  Every
+// thread of the PICK_THREADS calls it; part [PICK_THREADS / 64].
+EA_DEV float voc_row_expsum(const VocPick* row, const float* srow, int NB, float top, float* part) {
+  float s = 0.f;
+  if (top - top == 0.f) {                                 // (uniform)
+    for (int j = threadIdx.x; j < NB; j += PICK_THREADS) {
+      const float mt = row[j].v;
+      if (mt != -INFINITY) s += srow[j] * expf(mt - top);
+    }
+  }
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) s += __shfl_xor(s, o);
+  if ((threadIdx.x & 63) == 0) part[threadIdx.x >> 6] = s;
+  __syncthreads();
+  if (threadIdx.x != 0) return 0.f;
+  float total = part[0];
+#pragma unroll
+  for (int w = 1; w < PICK_THREADS / 64; ++w) total += part[w];
+  return total;
+}
+
+// top NaN: NaN; +inf: +inf; -inf (every logit is -inf): -inf
+EA_DEV float voc_lse_of(float top, float total) { return top - top == 0.f ? top + logf(total) : top; }
+
+// The launch behind the table pass that picks: one workgroup per row reduces the row's candidates.  On DecLseP
+// (ABI 28; the table pass has also written s_t = sum_columns exp(logit - m_t) of every tile to lws[m][tile]) it goes on: it
+// folds the tile sums into lse[m] = top + log(sum_t s_t exp(m_t - top)) and writes logp[m] = (the token's, the target's or
+// the top logit) - lse[m]: the log-probability under the model's own distribution at temperature 1, nothing truncated.
+template <typename P>
+__global__ __launch_bounds__(PICK_THREADS) void ceva_vocab_pick_kernel(const P p) {
+  constexpr bool LSE = std::is_same<P, DecLseP>::value;
+  static_assert(LSE || std::is_same<P, DecVocabP>::value, "one of the two blocks that pick");
+  __shared__ VocPick best[PICK_THREADS / 64];
+  __shared__ float part[PICK_THREADS / 64];
+  __shared__ float top_of_row;
+  const int m = blockIdx.x;
+  const int NB = (p.V - 1) / VOC_TILE + 1;
+  const VocPick* row = p.ws + (int64_t)m * NB;
+  // pass 1: the pick
+  const VocPick c = voc_row_best(row, NB, best);
+  if (threadIdx.x == 0) {
     if constexpr (LSE) {
       if (!p.token_in) {                                  // (the sampled mode: the token was drawn before this launch)
         p.token[m] = (int64_t)c.i;
@@ -73,28 +107,12 @@ __global__ __launch_bounds__(PICK_THREADS) void ceva_vocab_pick_kernel(const P p
     }
   }
   if constexpr (LSE) {
-    const float* srow = p.lws + (int64_t)m * NB;
     __syncthreads();
     const float top = top_of_row;
-    // pass 2: S = sum_t s_t exp(m_t - top) over the tiles that hold a number (a finite top: every m_t is finite or -inf,
-    // every exponent <= 0).  A tile of -inf alone is skipped, never multiplied.
-    float s = 0.f;
-    if (top - top == 0.f) {                               // (uniform)
-      for (int j = threadIdx.x; j < NB; j += PICK_THREADS) {
-        const float mt = row[j].v;
-        if (mt != -INFINITY) s += srow[j] * expf(mt - top);
-      }
-    }
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) s += __shfl_xor(s, o);
-    if ((threadIdx.x & 63) == 0) part[threadIdx.x >> 6] = s;
-    __syncthreads();
+    // pass 2: the tile sums against the top
+    const float total = voc_row_expsum(row, p.lws + (int64_t)m * NB, NB, top, part);
     if (threadIdx.x != 0) return;
-    float total = part[0];
-#pragma unroll
-    for (int w = 1; w < PICK_THREADS / 64; ++w) total += part[w];
-    // top NaN: NaN; +inf: +inf; -inf (every logit is -inf): -inf
-    const float lse = top - top == 0.f ? top + logf(total) : top;
+    const float lse = voc_lse_of(top, total);
     float tl = top;
     if (p.token_in) {
       const int64_t t = p.token_in[m];
@@ -212,6 +230,17 @@ EA_DEV void voc_compact(Load key_of, int n, uint64_t t, uint64_t* out, int cap, 
   }
 }
 
+// n <= 64 distinct keys sel[0 .. n - 1] -> sorted[0 .. n - 1], the largest first; it ends behind a barrier
+EA_DEV void voc_rank_sort(const uint64_t* sel, uint64_t* sorted, int n) {
+  if ((int)threadIdx.x < n) {
+    const uint64_t key = sel[threadIdx.x];
+    int rank = 0;
+    for (int i = 0; i < n; ++i) rank += sel[i] > key;
+    sorted[rank] = key;
+  }
+  __syncthreads();
+}
+
 // word 0 of Philox4x32-10 (Salmon et al., SC 2011)
 EA_DEV uint32_t philox4x32_10_word0(uint32_t k0, uint32_t k1, uint32_t c0, uint32_t c1, uint32_t c2, uint32_t c3) {
 #pragma unroll
@@ -224,45 +253,52 @@ EA_DEV uint32_t philox4x32_10_word0(uint32_t k0, uint32_t k1, uint32_t c0, uint3
   return c0;
 }
 
-__global__ __launch_bounds__(SMP_THREADS) void ceva_vocab_sample_kernel(const DecSampleP p) {
-  __shared__ uint64_t pool[SMP_POOL];                     // the keys of the selected tiles' columns (0: a column >= V)
-  __shared__ uint64_t sel[VOC_SAMPLE_MAX_K];              // the selected tiles' candidates; then the top_k keys, unordered
-  __shared__ uint64_t sorted[VOC_SAMPLE_MAX_K];
-  __shared__ uint32_t hist[256];
-  __shared__ uint32_t pass[3];
-  __shared__ uint32_t count[2];
-  const int m = blockIdx.x, lane = threadIdx.x & 63;
-  const int NB = (p.V - 1) / VOC_TILE + 1;
-  const VocPick* cand = p.ws + (int64_t)m * NB;
-  const float* lrow = p.logits + (int64_t)m * p.ldl;
-  const int kt = min(p.top_k, NB);                        // tiles: a tile that holds one of the k best logits has a maximum
-  const int kk = min(p.top_k, p.V);                       // that is among the k best maxima
-  if (threadIdx.x < 2) count[threadIdx.x] = 0u;
+// what voc_select works in
+struct VocSelect {
+  uint64_t pool[SMP_POOL];                                // the keys of the selected tiles' columns (0: a column >= V)
+  uint64_t sel[VOC_SAMPLE_MAX_K];                         // the selected tiles' candidates; then the top_k keys, unordered
+  uint64_t sorted[VOC_SAMPLE_MAX_K];
+  uint32_t hist[256];
+  uint32_t pass[3];
+  uint32_t count[2];
+};
+
+// Steps 1 and 2 of the sampled pick on one row: cand [NB] the table pass's candidates, lrow [V] its fp32 logits ->
+// kk = min(top_k, V), and sh.sorted[0 .. kk - 1]: the keys of the row's kk best logits, in order.  Every thread of the
+// SMP_THREADS calls it; it ends behind a barrier.
+EA_DEV int voc_select(const VocPick* cand, const float* lrow, int V, int NB, int top_k, VocSelect& sh) {
+  const int kt = min(top_k, NB);                          // tiles: a tile that holds one of the k best logits has a maximum
+  const int kk = min(top_k, V);                           // that is among the k best maxima
+  if (threadIdx.x < 2) sh.count[threadIdx.x] = 0u;
   // 1. the kt best candidates
   auto cand_key = [&](int j) { const VocPick c = cand[j]; return voc_key(c.v, c.i); };
-  const uint64_t t1 = kt < NB ? voc_threshold(cand_key, NB, kt, hist, pass) : 0ull;
+  const uint64_t t1 = kt < NB ? voc_threshold(cand_key, NB, kt, sh.hist, sh.pass) : 0ull;
   __syncthreads();
-  voc_compact(cand_key, NB, t1, sel, kt, &count[0]);
+  voc_compact(cand_key, NB, t1, sh.sel, kt, &sh.count[0]);
   __syncthreads();
   // 2. their columns' logits, and the kk best of those, in order
   const int np = kt * VOC_TILE;
   for (int e = threadIdx.x; e < np; e += SMP_THREADS) {
-    const int col = (voc_key_index(sel[e >> 4]) & ~(VOC_TILE - 1)) + (e & (VOC_TILE - 1));
-    pool[e] = (uint32_t)col < (uint32_t)p.V ? voc_key(lrow[col], col) : 0ull;
+    const int col = (voc_key_index(sh.sel[e >> 4]) & ~(VOC_TILE - 1)) + (e & (VOC_TILE - 1));
+    sh.pool[e] = (uint32_t)col < (uint32_t)V ? voc_key(lrow[col], col) : 0ull;
   }
   __syncthreads();
-  auto pool_key = [&](int j) { return pool[j]; };
-  const uint64_t t2 = kk < np ? voc_threshold(pool_key, np, kk, hist, pass) : 1ull;
+  auto pool_key = [&](int j) { return sh.pool[j]; };
+  const uint64_t t2 = kk < np ? voc_threshold(pool_key, np, kk, sh.hist, sh.pass) : 1ull;
   __syncthreads();
-  voc_compact(pool_key, np, t2, sel, kk, &count[1]);
+  voc_compact(pool_key, np, t2, sh.sel, kk, &sh.count[1]);
   __syncthreads();
-  if ((int)threadIdx.x < kk) {
-    const uint64_t key = sel[threadIdx.x];
-    int rank = 0;
-    for (int i = 0; i < kk; ++i) rank += sel[i] > key;
-    sorted[rank] = key;
-  }
-  __syncthreads();
+  voc_rank_sort(sh.sel, sh.sorted, kk);
+  return kk;
+}
+
+__global__ __launch_bounds__(SMP_THREADS) void ceva_vocab_sample_kernel(const DecSampleP p) {
+  __shared__ VocSelect sh;
+  const int m = blockIdx.x, lane = threadIdx.x & 63;
+  const int NB = (p.V - 1) / VOC_TILE + 1;
+  const float* lrow = p.logits + (int64_t)m * p.ldl;
+  const int kk = voc_select(p.ws + (int64_t)m * NB, lrow, p.V, NB, p.top_k, sh);
+  const uint64_t* sorted = sh.sorted;
   if (threadIdx.x >= 64) return;
   // 3 .. 6: one wave, entry j of the selection in lane j
   const bool live = lane < kk;
@@ -294,6 +330,141 @@ __global__ __launch_bounds__(SMP_THREADS) void ceva_vocab_sample_kernel(const De
     p.token[m] = (int64_t)token;
     if (p.kept) p.kept[m] = kept;
     p.ctr[m] = n + 1;                                     // (this workgroup alone reads and writes ctr[m])
+  }
+}
+
+// ---- the beam step (ABI 32) --------------------------------------------------------------------------------------------------
+// Two launches behind the table pass on DecLseP (fp32 logits, one candidate and one sum of exponentials per tile); the rule
+// is spelled out in include/ea_hip.h.  Row m = s W + b is beam b of sentence s.
+static_assert(PICK_THREADS == SMP_THREADS, "the beam step's row kernel runs the pick's and the sampler's helpers in one workgroup");
+constexpr int BEAM_MAX_W = 32;                            // 2 W <= VOC_SAMPLE_MAX_K: a row's candidates are one selection
+constexpr int BEAM_POOL = BEAM_MAX_W * VOC_SAMPLE_MAX_K;  // candidates of one sentence
+static_assert(BEAM_POOL <= SMP_UNROLL * SMP_THREADS, "voc_threshold and voc_compact walk a sentence in one iteration");
+
+// One workgroup per row (rule A): lse[m] by ceva_vocab_pick_kernel<DecLseP>'s operations, the k' = min(2 W, V) best logits
+// by the sampler's steps 1-2 (the forced step: eos alone), and every candidate's score = score[m] + (value - lse[m]): two fp32
+// operations, no product anywhere near them.  The rows of a done sentence are skipped.
+__global__ __launch_bounds__(SMP_THREADS) void ceva_vocab_beam_rows_kernel(const DecBeamP p) {
+  __shared__ VocSelect sh;
+  __shared__ VocPick best[PICK_THREADS / 64];
+  __shared__ float part[PICK_THREADS / 64];
+  __shared__ float top_of_row, lse_of_row;
+  const int m = blockIdx.x, s = m / p.W, lane = threadIdx.x & 63;
+  if (p.done[s]) return;                                  // (uniform)
+  const bool forced = p.t[s] + 1 >= p.max_new;
+  const int NB = (p.V - 1) / VOC_TILE + 1;
+  const VocPick* cand = p.ws + (int64_t)m * NB;
+  const float* lrow = p.logits + (int64_t)m * p.ldl;
+  const VocPick c = voc_row_best(cand, NB, best);
+  if (threadIdx.x == 0) top_of_row = c.v;
+  __syncthreads();
+  const float total = voc_row_expsum(cand, p.lws + (int64_t)m * NB, NB, top_of_row, part);
+  if (threadIdx.x == 0) {
+    lse_of_row = voc_lse_of(top_of_row, total);
+    p.lse[m] = lse_of_row;
+  }
+  __syncthreads();
+  const float lse = lse_of_row, score = p.score[m];
+  const int64_t at = (int64_t)m * (2 * p.W);
+  if (forced) {
+    if (threadIdx.x == 0) {
+      const float val = lrow[p.eos];
+      p.cand_idx[at] = p.eos;
+      p.cand_score[at] = score + (val - lse);
+      if (p.sel_val) p.sel_val[at] = val;
+    }
+    return;
+  }
+  const int kk = voc_select(cand, lrow, p.V, NB, 2 * p.W, sh);
+  if (threadIdx.x >= 64 || lane >= kk) return;
+  const int32_t idx = min(max(voc_key_index(sh.sorted[lane]), 0), p.V - 1);   // (a column of the row, come what may)
+  const float val = lrow[idx];                            // (the stored logit's own bits: the key has folded -0 and NaNs)
+  p.cand_idx[at + lane] = idx;
+  p.cand_score[at + lane] = score + (val - lse);
+  if (p.sel_val) p.sel_val[at + lane] = val;
+}
+
+// One workgroup per sentence (rules B and C): the sentence's W k' candidates (k' = kc; the forced step: 1) as keys -- the
+// score's image in the high word, the complement of the flat index f = b k' + j in the low one -- the n2 = min(2 W, W k')
+// largest in order, then one wave walks them, candidate i in lane i.  Only this workgroup touches t[s], nfin[s], done[s],
+// the sentence's records and its W rows of token, parent, score and the history.
+__global__ __launch_bounds__(SMP_THREADS) void ceva_vocab_beam_merge_kernel(const DecBeamP p) {
+  __shared__ uint64_t keys[BEAM_POOL];
+  __shared__ uint64_t sel[VOC_SAMPLE_MAX_K];
+  __shared__ uint64_t sorted[VOC_SAMPLE_MAX_K];
+  __shared__ uint32_t hist[256];
+  __shared__ uint32_t pass[3];
+  __shared__ uint32_t count;
+  const int s = blockIdx.x, W = p.W, lane = threadIdx.x & 63;
+  const int M = p.S * W, row0 = s * W;
+  if (p.done[s]) {                                        // (uniform) rule C
+    if ((int)threadIdx.x < W) {
+      p.token[row0 + threadIdx.x] = (int64_t)p.eos;
+      p.parent[row0 + threadIdx.x] = (int64_t)(row0 + threadIdx.x);
+    }
+    return;
+  }
+  const int t = p.t[s], nfin = p.nfin[s];
+  const bool forced = t + 1 >= p.max_new;
+  const int kc = forced ? 1 : p.kc;
+  const int n = W * kc, n2 = min(2 * W, n);
+  const int32_t* cidx = p.cand_idx + (int64_t)row0 * (2 * W);
+  const float* cscore = p.cand_score + (int64_t)row0 * (2 * W);
+  if (threadIdx.x == 0) count = 0u;
+  for (int f = threadIdx.x; f < n; f += SMP_THREADS) keys[f] = voc_key(cscore[(f / kc) * (2 * W) + f % kc], f);
+  __syncthreads();
+  auto key_of = [&](int f) { return keys[f]; };
+  const uint64_t t1 = n2 < n ? voc_threshold(key_of, n, n2, hist, pass) : 0ull;
+  __syncthreads();
+  voc_compact(key_of, n, t1, sel, n2, &count);
+  __syncthreads();
+  voc_rank_sort(sel, sorted, n2);
+  if (threadIdx.x >= 64) return;
+  // candidate i of the walk in lane i
+  const bool live = lane < n2;
+  const int f = live ? min(max(voc_key_index(sorted[lane]), 0), n - 1) : 0;
+  const int b = f / kc;
+  const int32_t tok = live ? cidx[b * (2 * W) + f % kc] : 0;
+  const float sc = live ? cscore[b * (2 * W) + f % kc] : 0.f;   // (the stored score's own bits)
+  const uint64_t below = (1ull << lane) - 1ull;
+  const bool is_eos = live && tok == p.eos;
+  // finished hypotheses: an eos among the first W whose score is not -inf, while a slot is free
+  const bool ends = is_eos && lane < W && sc != -INFINITY;
+  const uint64_t ending = __ballot(ends);
+  const int slot = nfin + __popcll(ending & below);
+  if (ends && slot < W) {
+    p.fin_score[row0 + slot] = sc;
+    p.fin_len[row0 + slot] = t + 1;
+    p.fin_beam[row0 + slot] = b;
+  }
+  const int nfin_new = min(W, nfin + __popcll(ending));
+  // the next step's beams: the first W candidates that go on; the rest of the W are dead
+  const bool goes = live && !is_eos;
+  const uint64_t going = __ballot(goes);
+  const int r = __popcll(going & below), ngo = min(W, __popcll(going));
+  const bool hist_ok = t >= 0 && t < p.max_new;          // (otherwise only in a state no step of this kernel leaves)
+  if (goes && r < W) {
+    p.token[row0 + r] = (int64_t)tok;
+    p.parent[row0 + r] = (int64_t)(row0 + b);
+    p.score[row0 + r] = sc;
+    if (hist_ok) {
+      p.hist_tok[(int64_t)t * M + row0 + r] = tok;
+      p.hist_par[(int64_t)t * M + row0 + r] = b;
+    }
+  }
+  if (lane >= ngo && lane < W) {
+    p.token[row0 + lane] = (int64_t)p.eos;
+    p.parent[row0 + lane] = (int64_t)(row0 + lane);
+    p.score[row0 + lane] = -INFINITY;
+    if (hist_ok) {
+      p.hist_tok[(int64_t)t * M + row0 + lane] = p.eos;
+      p.hist_par[(int64_t)t * M + row0 + lane] = lane;
+    }
+  }
+  if (lane == 0) {
+    p.t[s] = t + 1;
+    p.nfin[s] = nfin_new;
+    p.done[s] = nfin_new == W || forced;
   }
 }
 
@@ -362,6 +533,52 @@ int ceva_sdecode_vocab_sample_logprob(const DecLseP& p, const DecSampleP& s, hip
   int rc = voc_table_pass(p, s.top_k, st);
   if (rc == 0) rc = voc_row_pass(ceva_vocab_sample_kernel, SMP_THREADS, s, p.M, st);
   return rc != 0 ? rc : voc_row_pass(ceva_vocab_pick_kernel<DecLseP>, PICK_THREADS, p, p.M, st);
+}
+
+// ---- the beam step (ABI 32) ----
+static int64_t beam_round16(int64_t n) { return (n + 15) & ~(int64_t)15; }
+
+static bool beam_envelope(int M, int W) { return W >= 1 && W <= BEAM_MAX_W && M >= 1 && M <= EA_CEVA_LINEAR_MAX_ROWS && M % W == 0; }
+
+int64_t ceva_sdecode_vocab_beam_ws(int M, int V, int W) {
+  if (V < 1 || !beam_envelope(M, W)) return -1;
+  return beam_round16(ceva_sdecode_vocab_ws(M, V)) + beam_round16(ceva_sdecode_vocab_lse_ws(M, V)) +
+         2 * beam_round16((int64_t)M * 2 * W * 4) + beam_round16((int64_t)M * 4);
+}
+
+void ceva_sdecode_vocab_beam_carve(void* ws, DecLseP* p, DecBeamP* b) {
+  const int M = p->M, V = p->V, NB = (V - 1) / VOC_TILE + 1;
+  char* at = (char*)ws;
+  p->ws = (VocPick*)at; at += beam_round16(ceva_sdecode_vocab_ws(M, V));
+  p->lws = (float*)at; p->tlogit = p->lws + (int64_t)M * NB; at += beam_round16(ceva_sdecode_vocab_lse_ws(M, V));
+  int32_t* idx = (int32_t*)at; at += beam_round16((int64_t)M * 2 * b->W * 4);
+  float* score = (float*)at; at += beam_round16((int64_t)M * 2 * b->W * 4);
+  float* lse = (float*)at;
+  if (!b->cand_idx) b->cand_idx = idx;
+  if (!b->cand_score) b->cand_score = score;
+  if (!b->lse) b->lse = lse;
+  p->lse = p->logp = lse;                                 // (required by the block; the table pass writes neither)
+  b->ws = p->ws; b->lws = p->lws;
+}
+
+static bool beam_state_ok(const DecBeamP& b) {
+  return b.cand_idx && b.cand_score && b.score && b.t && b.nfin && b.done && b.token && b.parent && b.hist_tok && b.hist_par &&
+         b.fin_score && b.fin_len && b.fin_beam && b.eos >= 0 && b.max_new >= 1 && b.kc >= 1 && b.kc <= 2 * b.W;
+}
+
+int ceva_beam_merge(const DecBeamP& b, hipStream_t st) {
+  if (b.S < 1 || b.W < 1 || !beam_state_ok(b)) return EA_E_BADARG;
+  if (!beam_envelope(b.S * b.W, b.W)) return EA_E_UNSUPPORTED;
+  return voc_row_pass(ceva_vocab_beam_merge_kernel, SMP_THREADS, b, b.S, st);
+}
+
+int ceva_sdecode_vocab_beam(const DecLseP& p, const DecBeamP& b, hipStream_t st) {
+  if (b.W < 1 || !beam_state_ok(b) || !p.logits || !p.l_f32 || (const char*)b.logits != p.logits || b.ldl != p.ldl ||
+      b.ws != p.ws || b.lws != p.lws || !b.lse || b.V != p.V || b.eos >= p.V || p.targets || p.token_in) return EA_E_BADARG;
+  if (!beam_envelope(p.M, b.W) || b.S * b.W != p.M || b.kc != (2 * b.W < p.V ? 2 * b.W : p.V)) return EA_E_UNSUPPORTED;
+  int rc = voc_table_pass(p, 0, st);
+  if (rc == 0) rc = voc_row_pass(ceva_vocab_beam_rows_kernel, SMP_THREADS, b, p.M, st);
+  return rc != 0 ? rc : voc_row_pass(ceva_vocab_beam_merge_kernel, SMP_THREADS, b, b.S, st);
 }
 
 }  // namespace ea

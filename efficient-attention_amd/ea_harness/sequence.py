@@ -12,7 +12,9 @@ DecoderLayer / DecoderStack are the decoder-only language model of the wikitext-
 static and rolling states: `init_decoding`, `decode`, `generate`; `next_tokens` is the greedy pick on a vocabulary table the
 state holds (ea_ceva_sdecode_vocab_argmax), `init_sampling` / `sample_tokens` the sampled one (ea_ceva_sdecode_vocab_sample);
 `init_logprobs` / `token_logprobs` / `sample_tokens_logprobs` / `score` report a token's log-probability under the model's own
-distribution from the same pass over the table (ea_ceva_sdecode_vocab_logprob, ea_ceva_sdecode_vocab_sample_logprob)."""
+distribution from the same pass over the table (ea_ceva_sdecode_vocab_logprob, ea_ceva_sdecode_vocab_sample_logprob);
+`init_beam_search` / `beam_step` / `beam_search` are a beam search whose step -- candidates, merge, finished hypotheses and the
+parent index of the state reorder -- runs on the device (ea_ceva_sdecode_vocab_beam)."""
 import argparse
 import contextlib
 import functools
@@ -213,10 +215,11 @@ class DecodingState:
     (the 16-bit [V, C] copy of embed_tokens.weight) and `vocab_ws` (the pick's workspace, bytes); both None otherwise.
     The fourth argument is that pair, (vocab, vocab_ws), or None.
     `sampler` is None until `DecoderStack.init_sampling` attaches a Sampler, `scorer` until `DecoderStack.init_logprobs`
-    attaches a Scorer."""
+    attaches a Scorer, `beam` until `DecoderStack.init_beam_search` attaches a Beam."""
 
     sampler = None
     scorer = None
+    beam = None
 
     def __init__(self, incremental, ffn, options, vocab=None):
         self.incremental, self.ffn, self.options = incremental, ffn, options
@@ -237,6 +240,8 @@ _SAMPLE_MAX_K = 64
 _LOGPROB = "ea_ceva_sdecode_vocab_logprob"
 _SAMPLE_LOGPROB = "ea_ceva_sdecode_vocab_sample_logprob"
 _SCORE = "ea_vocab_score"
+_BEAM = "ea_ceva_sdecode_vocab_beam"
+_BEAM_MAX_W = 32
 
 
 class Sampler:
@@ -258,6 +263,26 @@ class Scorer:
 
     def __init__(self, ws, lse, logp):
         self.ws, self.lse, self.logp = ws, lse, logp
+
+
+class Beam:
+    """What `DecoderStack.init_beam_search` attaches to a DecodingState: the host scalars `beam_size` (W), `eos_idx`,
+    `max_new`, `len_penalty` and the static buffers of ea_ceva_sdecode_vocab_beam (include/ea_hip.h, ABI 32) for M = the
+    state's batch size = S W rows: `logits` fp32 [M, V], `ws` (the entry's workspace, bytes), `score` fp32 [M], `t`, `nfin`,
+    `done` int32 [S], `parent` int64 [M], `hist_tok`, `hist_par` int32 [max_new, M], `fin_score` fp32 [S, W], `fin_len`,
+    `fin_beam` int32 [S, W].  `replays`: how many steps behind the first pick the last `beam_search` on it ran."""
+
+    def __init__(self, beam_size, eos_idx, max_new, len_penalty, logits, ws, score, t, nfin, done, parent, hist_tok, hist_par,
+                 fin_score, fin_len, fin_beam):
+        self.beam_size, self.eos_idx, self.max_new, self.len_penalty = beam_size, eos_idx, max_new, len_penalty
+        self.logits, self.ws, self.score, self.t, self.nfin, self.done, self.parent = logits, ws, score, t, nfin, done, parent
+        self.hist_tok, self.hist_par = hist_tok, hist_par
+        self.fin_score, self.fin_len, self.fin_beam = fin_score, fin_len, fin_beam
+        self.replays = 0
+
+    def buffers(self):
+        return (self.logits, self.ws, self.score, self.t, self.nfin, self.done, self.parent, self.hist_tok, self.hist_par,
+                self.fin_score, self.fin_len, self.fin_beam)
 
 
 def _hold_vocab_option(init):
@@ -413,7 +438,9 @@ class DecoderStack(nn.Module):
     def decoding_state_nbytes(self, state):
         """Bytes of every layer's attention state, of the held feed-forward weights, of the held vocabulary table with
         its workspace, of a sampler's logits, counters and stream ids (4 B V + 8 B + 4 B) and of a scorer's workspace and
-        buffers (4 * 64 * (ceil(V / 16) + 1) + 8 B)."""
+        buffers (4 * 64 * (ceil(V / 16) + 1) + 8 B), and of a beam search's buffers for M = S W rows (`init_beam_search`):
+        4 M V (logits) + ea_ceva_sdecode_vocab_beam_ws(M, V, W) (workspace) + 4 M (score) + 12 S (t, nfin, done) + 8 M
+        (parent) + 8 max_new M (the history) + 12 S W (the records)."""
         n = sum(layer.self_attn.decoding_state_nbytes(state.incremental) for layer in self.layers)
         n += sum(t.numel() * t.element_size() for held in (state.ffn or ()) for t in held)
         sm = state.sampler
@@ -421,6 +448,8 @@ class DecoderStack(nn.Module):
         sc = state.scorer
         if sc is not None:
             extra += (sc.ws, sc.lse, sc.logp)
+        if state.beam is not None:
+            extra += state.beam.buffers()
         return n + sum(t.numel() * t.element_size() for t in (state.vocab, state.vocab_ws) + extra if t is not None)
 
     def decoding_overflowed(self, state):
@@ -779,6 +808,198 @@ class DecoderStack(nn.Module):
             greedy, logp = self.rows_logprobs(rows, table, targets)
             logp = logp.masked_fill_(targets.eq(self.pad_idx), 0.0).t().contiguous()
             return (logp, greedy.t().contiguous()) if return_tokens else logp
+
+    # ---- beam search (ea_ceva_sdecode_vocab_beam, C ABI 32) ------------------------------------------------------------------
+    def init_beam_search(self, state, beam_size, eos_idx, max_new, len_penalty=1.0):
+        """Make `state` (made with hold_vocab=True, no sampler; its batch size M a multiple of `beam_size`) search with beams:
+        rows s W .. s W + W - 1 are the W = beam_size beams of sentence s, S = M / W sentences.  `eos_idx` (0 <= eos_idx < V)
+        ends a hypothesis; `max_new` >= 1 is the largest number of generated tokens of one, the closing eos included (the
+        step that would pass it ends every live beam with eos); `len_penalty`: a finished hypothesis ranks by its raw score
+        (the fp32 sum of its tokens' log-probabilities) over length ** len_penalty, on the host, behind the search.
+        Envelope: 1 <= W <= 32, M <= 64.  Values outside it raise ValueError before anything is allocated.  Attaches
+        `state.beam` (a Beam: the static buffers of the step, initialised; bytes: `decoding_state_nbytes`) and returns the
+        state."""
+        if state.vocab is None:
+            raise RuntimeError("init_beam_search needs a decoding state that holds the vocabulary table: "
+                               "init_decoding(..., hold_vocab=True)")
+        if state.sampler is not None:
+            raise RuntimeError("init_beam_search on a state with a sampler: a beam search draws nothing")
+        W, eos, max_new, len_penalty = int(beam_size), int(eos_idx), int(max_new), float(len_penalty)
+        M, V = int(state.options["batch_size"]), state.vocab.shape[0]
+        if not 1 <= W <= _BEAM_MAX_W:
+            raise ValueError("beam_size must be in 1 .. %d, got %d" % (_BEAM_MAX_W, W))
+        if M > _FUSED_MAX_ROWS or M % W:
+            raise ValueError("beam_size %d on a state of %d rows: the batch size must be a multiple of beam_size and at most %d"
+                             % (W, M, _FUSED_MAX_ROWS))
+        if not 0 <= eos < V:
+            raise ValueError("eos_idx must be in 0 .. %d, got %d" % (V - 1, eos))
+        if max_new < 1:
+            raise ValueError("max_new must be >= 1, got %d" % max_new)
+        if not math.isfinite(len_penalty):
+            raise ValueError("len_penalty must be finite, got %r" % len_penalty)
+        from efficient_attention import _native as nv
+        S, device = M // W, state.vocab.device
+        nbytes = nv.lib().ea_ceva_sdecode_vocab_beam_ws(M, V, W)
+
+        def buf(shape, dtype):
+            return torch.empty(shape, dtype=dtype, device=device)
+        i32, f32 = torch.int32, torch.float32
+        state.beam = Beam(W, eos, max_new, len_penalty, buf((M, V), f32), buf(nbytes, torch.uint8), buf(M, f32), buf(S, i32),
+                          buf(S, i32), buf(S, i32), buf(M, torch.long), buf((max_new, M), i32), buf((max_new, M), i32),
+                          buf((S, W), f32), buf((S, W), i32), buf((S, W), i32))
+        return self.reset_beam_search(state)
+
+    def reset_beam_search(self, state):
+        """Back to the start of a search, in place and by device ops only: score 0 for beam 0 of every sentence and -inf for
+        the others, t = nfin = done = 0, the records and the history cleared.  (The attention's own state is the caller's.)"""
+        bm = state.beam
+        if bm is None:
+            raise RuntimeError("reset_beam_search needs a decoding state with a beam search: init_beam_search(state, ...)")
+        bm.score.fill_(float("-inf")).view(-1, bm.beam_size)[:, 0].fill_(0.0)
+        for t in (bm.t, bm.nfin, bm.done, bm.parent, bm.hist_tok, bm.hist_par, bm.fin_score, bm.fin_len, bm.fin_beam):
+            t.zero_()
+        return state
+
+    def beam_step(self, rows, state, out=None, return_details=False):
+        """One step of the beam search on a state with a beam (`init_beam_search`): rows [1, M, C] (final-layer rows of a
+        single-token step, M the state's batch size) -> (tokens int64 [1, M], parent int64 [M]): the next input token of every
+        beam and the row it continues -- `reorder_decoding_state(state, parent)` makes the state follow.  ONE call of
+        ea_ceva_sdecode_vocab_beam (include/ea_hip.h has the rule): the table pass, a row's 2 W best candidates with their
+        cumulative scores, the merge per sentence with the finished hypotheses and the history; everything it decides stays
+        on the device, in the Beam's buffers (`parent` is one of them).  out: as in `next_tokens`.
+        return_details=True: -> (tokens, parent, cand_idx int32 [M, 2 W], cand_score fp32 [M, 2 W], lse fp32 [M]); entries
+        from min(2 W, V) on (the forced step: from 1 on) and the rows of a done sentence are not written.  Device launches
+        only."""
+        bm = state.beam
+        if bm is None:
+            raise RuntimeError("beam_step needs a decoding state with a beam search: init_beam_search(state, beam_size, ...)")
+        from efficient_attention import _native as nv
+        table = state.vocab
+        T, M, C = rows.shape
+        V, W = table.shape[0], bm.beam_size
+        if T != 1 or M != bm.score.numel():
+            raise ValueError("beam_step takes the rows of one single-token step of the whole state, [1, %d, C]; got %s"
+                             % (bm.score.numel(), tuple(rows.shape)))
+        x2 = self._vocab_rows(rows, state, False)
+        out = self._vocab_out(out, (1, M), torch.long, x2.device, "out")
+        details = None
+        if return_details:
+            details = (torch.empty((M, 2 * W), dtype=torch.int32, device=x2.device),
+                       torch.empty((M, 2 * W), dtype=torch.float32, device=x2.device),
+                       torch.empty((M,), dtype=torch.float32, device=x2.device))
+        code = nv.EA_F32 if x2.dtype == torch.float32 else nv.io_dtype(x2)
+        nv.call(_BEAM, M, C, V, nv.ptr(x2), code, C, nv.ptr(table), nv.io_dtype(table), nv.ptr(bm.logits), V, nv.ptr(bm.ws),
+                bm.ws.numel(), W, bm.eos_idx, bm.max_new, nv.ptr(bm.score), nv.ptr(bm.t), nv.ptr(bm.nfin), nv.ptr(bm.done),
+                nv.ptr(out), nv.ptr(bm.parent), nv.ptr(bm.hist_tok), nv.ptr(bm.hist_par), nv.ptr(bm.fin_score),
+                nv.ptr(bm.fin_len), nv.ptr(bm.fin_beam), *((None, None, None) if details is None else [nv.ptr(t) for t in details]),
+                None, nv.stream())
+        return (out, bm.parent) + details if return_details else (out, bm.parent)
+
+    @staticmethod
+    def _beam_hypotheses(bm):
+        """The host's part of a search, behind the loop: the records and the history read back -> per sentence the finished
+        hypotheses, the best normalised score first, ties by finishing order."""
+        nfin, fin_score = bm.nfin.tolist(), bm.fin_score.cpu()
+        fin_len, fin_beam = bm.fin_len.tolist(), bm.fin_beam.tolist()
+        hist_tok, hist_par = bm.hist_tok.cpu(), bm.hist_par.cpu()
+        W, result = bm.beam_size, []
+        for s, n in enumerate(nfin):
+            hyps = []
+            for i in range(n):
+                raw, length, b = fin_score[s, i], fin_len[s][i], fin_beam[s][i]
+                tokens = [bm.eos_idx]
+                for t in range(length - 2, -1, -1):
+                    tokens.append(int(hist_tok[t, s * W + b]))
+                    b = int(hist_par[t, s * W + b])
+                hyps.append(dict(tokens=torch.tensor(tokens[::-1], dtype=torch.long), raw_score=raw,
+                                 score=float(raw) / float(length) ** bm.len_penalty))
+            order = sorted(range(n), key=lambda i: (not math.isnan(hyps[i]["score"]), -hyps[i]["score"], i))
+            result.append([hyps[i] for i in order])
+        return result
+
+    def beam_search(self, prompt, state=None, *, beam_size, eos_idx, max_new, len_penalty=1.0, graph=True, poll=16):
+        """Beam search: prompt [S, P] int64 -> per sentence a list of its finished hypotheses, the best first: dicts with
+        `tokens` (int64 1-D, the closing eos included), `score` (raw_score / length ** len_penalty; ties by finishing order)
+        and `raw_score` (an fp32 scalar tensor: the sum of the tokens' log-probabilities under the model's own distribution).
+        At most beam_size per sentence; fewer where live beams ran out.  The rule -- fairseq's SequenceGenerator without
+        min_len, n-gram blocking, prefix tokens and match_source_len, with ties decided and a -inf-scored eos dropped -- is in
+        include/ea_hip.h (ABI 32).
+        state: a fresh DecodingState of S beam_size rows made with hold_vocab=True (default: rolling, held weights, the
+        autocast dtype, P + max_new tokens); one without a beam gets `init_beam_search(state, beam_size, eos_idx, max_new,
+        len_penalty)`, one with a beam must have been given the same four values and be at its start (`reset_beam_search`).
+        The prompt is repeated beam_size times and fed eagerly in one `decode` (a per-sequence state: ragged, right-padded
+        with `pad_idx`, as in `generate`); `beam_step` on the last rows and `reorder_decoding_state(state, parent)` follow.
+        graph=True: then ONE step -- `decode` of the beams' tokens, `beam_step` writing the next tokens into the step's
+        static input, the reorder by the parents it has just written; device ops only -- is warmed up on a scratch state and
+        scratch beam buffers, captured, and replayed at most max_new - 1 times; every `poll` replays `done` is read back and
+        the loop ends once every sentence is done.  graph=False runs the same steps eagerly: the same bits.  An overflow
+        flagged by any layer raises after the loop."""
+        if self.training:
+            raise NotImplementedError("incremental decoding in training mode")
+        S, P = prompt.shape
+        W, max_new, poll = int(beam_size), int(max_new), int(poll)
+        if poll < 1:
+            raise ValueError("poll must be >= 1, got %d" % poll)
+        M = S * W
+        amp = torch.is_autocast_enabled()
+        ctx = torch.autocast("cuda", dtype=torch.get_autocast_dtype("cuda"), cache_enabled=False) if amp \
+            else contextlib.nullcontext()
+        with torch.no_grad(), ctx:
+            if state is None:
+                dtype = torch.get_autocast_dtype("cuda") if amp else self.embed_tokens.weight.dtype
+                state = self.init_decoding(M, P + max(max_new, 1), dtype, prompt.device, hold_vocab=True)
+            if state.beam is None:
+                self.init_beam_search(state, W, eos_idx, max_new, len_penalty)
+            bm = state.beam
+            if (bm.beam_size, bm.eos_idx, bm.max_new, bm.len_penalty) != (W, int(eos_idx), max_new, float(len_penalty)):
+                raise ValueError("the state's beam search was made with (beam_size, eos_idx, max_new, len_penalty) = %r"
+                                 % ((bm.beam_size, bm.eos_idx, bm.max_new, bm.len_penalty),))
+            if M != bm.score.numel():
+                raise ValueError("a prompt of %d sentences at beam_size %d on a state of %d rows" % (S, W, bm.score.numel()))
+            prompt = prompt.repeat_interleave(W, 0)                          # [M, P]: row s W + b is beam b of sentence s
+            per_seq = state.options["per_sequence"]
+            mask = prompt.eq(self.pad_idx) if per_seq else None
+            x = self.decode(prompt.t(), state, mask)                         # [P, M, C]
+            if per_seq:
+                n_b = P - mask.ne(0).to(torch.int32).cumsum(1).ne(0).sum(1)
+                last = x[(n_b - 1).clamp_(min=0), torch.arange(M, device=x.device)].unsqueeze(0)
+            else:
+                last = x[P - 1:P]
+            tok_in, parent = self.beam_step(last, state)                     # [1, M]: the step's static input
+            self.reorder_decoding_state(state, parent)
+
+            def step(st, beams):
+                self.beam_step(self.decode(tok_in, st), beams, out=tok_in)
+                self.reorder_decoding_state(st, beams.beam.parent)
+            g = None
+            if graph and max_new > 1:
+                scratch = self.init_decoding(**dict(state.options, max_tokens=1, hold_vocab=False))
+                scratch.vocab, scratch.vocab_ws = state.vocab, state.vocab_ws
+                self.init_beam_search(scratch, W, eos_idx, max_new, len_penalty)
+                first = tok_in.clone()
+                side = torch.cuda.Stream()
+                side.wait_stream(torch.cuda.current_stream())
+                with torch.cuda.stream(side):
+                    step(scratch, scratch)
+                torch.cuda.current_stream().wait_stream(side)
+                tok_in.copy_(first)
+                del scratch
+                g = torch.cuda.CUDAGraph()
+                with torch.cuda.graph(g):
+                    step(state, state)
+            bm.replays = 0
+            for i in range(1, max_new):
+                if g is None:
+                    step(state, state)
+                else:
+                    g.replay()
+                bm.replays = i
+                if i % poll == 0 and i + 1 < max_new and bool(bm.done.ne(0).all()):
+                    break
+            if self.decoding_overflowed(state):
+                raise RuntimeError("the decoding state overflowed: a step passed its %d tokens (init_decoding(max_tokens=...))"
+                                   % state.options["max_tokens"])
+            return self._beam_hypotheses(bm)
 
     def generate(self, prompt, n_new, state=None, graph=True, return_rows=False, return_logprobs=False):
         """Greedy decoding: prompt [B, P] int64 -> the n_new tokens that follow, [B, n_new] (return_rows: and the final-layer

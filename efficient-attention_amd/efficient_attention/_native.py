@@ -22,7 +22,7 @@ class ea_t4(ctypes.Structure):
                 ("sn", ctypes.c_int64)]
 
 
-ABI_VERSION = 31         # ea_abi_version() of include/ea_hip.h this file mirrors
+ABI_VERSION = 32         # ea_abi_version() of include/ea_hip.h this file mirrors
 
 
 class ea_geom(ctypes.Structure):
@@ -267,6 +267,10 @@ SIGNATURES = {
     "ea_ceva_sdecode_vocab_logprob": [_I, _I, _I, _P, _I, _L, _P, _I, _P, _I, _L, _P, _L, _P, _P, _P, _L, _P, _P, _P, _P],
     "ea_ceva_sdecode_vocab_sample_logprob": [_I, _I, _I, _P, _I, _L, _P, _I, _P, _L, _P, _L, _I, _F, _F, _U64, _P, _P, _P, _P,
                                              _P, _P, _P, _L, _P, _P, _P],
+    "ea_ceva_sdecode_vocab_beam_ws": [_I, _I, _I],
+    "ea_ceva_sdecode_vocab_beam": [_I, _I, _I, _P, _I, _L, _P, _I, _P, _L, _P, _L, _I, _I, _I, _P, _P, _P, _P, _P, _P, _P, _P,
+                                   _P, _P, _P, _P, _P, _P, _P, _P],
+    "ea_beam_merge": [_I, _I, _I, _P, _P, _I, _I, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P],
     "ea_vocab_score_ws": [_I, _I],
     "ea_vocab_score_tile": [_I],
     "ea_vocab_score": [_I, _I, _I, _P, _I, _L, _P, _I, _P, _P, _I, _L, _P, _L, _P, _P, _P, _P, _P],
@@ -302,6 +306,7 @@ def lib():
         cdll.ea_ceva_sdecode_vocab_ws.restype = ctypes.c_int64
         cdll.ea_ceva_sdecode_vocab_sample_ws.restype = ctypes.c_int64
         cdll.ea_ceva_sdecode_vocab_lse_ws.restype = ctypes.c_int64
+        cdll.ea_ceva_sdecode_vocab_beam_ws.restype = ctypes.c_int64
         cdll.ea_vocab_score_ws.restype = ctypes.c_int64
         cdll.ea_version.restype = ctypes.c_char_p
         cdll.ea_abi_version.restype = ctypes.c_int32

@@ -1239,6 +1239,60 @@ int ea_vocab_score(int32_t M, int32_t K, int32_t V, const void* x, int32_t x_dty
                    int32_t w_dtype, const int64_t* targets, void* logits, int32_t logits_dtype, int64_t ldl, void* ws,
                    int64_t ws_bytes, int64_t* token, float* top, float* lse, float* logp, void* stream);
 
+/* ABI 32, the BEAM STEP on the held vocabulary table (ea_harness DecoderStack.init_beam_search, beam_step, beam_search;
+ * ea_ceva_decode_vocab.hip): one step of a beam search whose whole state lives on the device, so that a captured step can
+ * be replayed.  S sentences, beam width W, M = S W rows, row m = s W + b is beam b of sentence s; 1 <= W <= 32, M <= 64,
+ * 0 <= eos < V; max_new >= 1 is the largest number of generated tokens of a hypothesis, the closing eos included.
+ * State, in / out: score [M] fp32 (the sum of the log-probabilities of a beam's tokens; to start: 0 for beam 0, -inf for the
+ * others, so that of W copies of a prompt only the first counts), t [S] int32 (tokens generated), nfin [S] int32 (finished
+ * hypotheses, <= W), done [S] int32; t = nfin = done = 0 to start.
+ * ea_ceva_sdecode_vocab_beam, three launches.  The first is ea_ceva_sdecode_vocab_logprob's first: fp32 logits into logits
+ * [M, ldl] (required), one (value, index) candidate and one sum of exponentials per 16-column tile into the workspace.
+ *   A. the rows, one workgroup of 512 threads per row of a sentence that is not done; t = t[s]:
+ *      lse[m]: ea_ceva_sdecode_vocab_logprob's, by the same operations in the same order: the same bits;
+ *      forced step (t + 1 == max_new): one candidate (k' = 1), token eos, value logits[m, eos]; otherwise the row's
+ *      k' = min(2 W, V) best logits in order, steps 1-2 of ea_ceva_sdecode_vocab_sample at top_k = 2 W: sel_idx, sel_val;
+ *      cand_idx[m, j] = sel_idx[j], cand_score[m, j] = score[m] + (sel_val[j] - lse[m]): two fp32 operations, the subtraction
+ *      first, nothing fused or reassociated.  Entries j >= k' are not written.
+ *   B. the merge, one workgroup per sentence that is not done: its W k' candidates are ordered by score under the sampler's
+ *      total order -- NaN above every number, the larger first, +0 and -0 equal, equal scores by the lower flat index
+ *      f = b k' + j -- and the first n2 = min(2 W, W k') are walked in order, i = 0 .. n2 - 1.  A candidate whose token is eos
+ *      never continues; it is recorded as a finished hypothesis iff i < W, its score is not -inf and nfin[s] < W, in slot
+ *      nfin[s]++: fin_score (the raw score), fin_len = t + 1, fin_beam = b (the beam it extends).  The first W candidates
+ *      whose token is not eos become the beams r = 0 .. W - 1 of the next step: token[s W + r], parent[s W + r] = s W + b (a
+ *      global row: the new_order of a state reorder), score[s W + r], hist_tok[t, s W + r], hist_par[t, s W + r] = b.  Where
+ *      fewer than W go on, the remaining beams are dead: token eos, parent their own row, score -inf, hist_tok eos,
+ *      hist_par their own beam.  Then t[s] += 1, and done[s] = 1 if nfin[s] == W or the step was the forced one.
+ *   C. a done sentence: token eos and parent = own row for its W rows; score, t, nfin, the records and the history stay.
+ * The normalised score (fin_score / fin_len ** len_penalty) is the host's: it never feeds back into the search.  Tokens of a
+ * hypothesis: backtrack hist_par / hist_tok from (fin_len - 2, fin_beam), then eos.
+ * token, parent [M] int64; hist_tok, hist_par [max_new, M] int32; fin_score [S, W] fp32; fin_len, fin_beam [S, W] int32.
+ * Optional reports, each NULL or: cand_idx [M, 2 W] int32, cand_score [M, 2 W] fp32, lse [M] fp32 (the merge then reads the
+ * lists from there), sel_val [M, 2 W] fp32 (the selected logits' stored bits).  W, eos and max_new are host scalars: a capture
+ * fixes them.  Ordinary stores only, no atomics on memory, no workgroup waits for another; only sentence s's workgroup touches
+ * t[s], nfin[s], done[s] and its records: bitwise reproducible, and a sentence's results do not depend on its batch.
+ * ws: ea_ceva_sdecode_vocab_beam_ws(M, V, W) bytes = r16(8 M NB) + r16(4 M NB + 4 M) + 2 r16(8 M W) + r16(4 M), NB =
+ * ceil(V / 16), r16 rounding up to a multiple of 16: the candidates, the tile sums (with ea_ceva_sdecode_vocab_lse_ws' M
+ * spare floats), the two [M, 2 W] lists and lse; < 0 for M < 1, M > 64, V < 1, W < 1, W > 32 or M % W != 0.
+ * EA_E_BADARG: what ea_ceva_sdecode_vocab_sample answers with it for x, w, logits and their strides; ws NULL or not 16-byte
+ * aligned; a state or output pointer NULL; token or parent not 8-byte, any other one (the reports too) not 4-byte aligned;
+ * W < 1, eos outside [0, V), max_new < 1; ws_bytes below the query's answer.  EA_E_UNSUPPORTED: W > 32, M > 64, M % W != 0,
+ * K % 32 != 0, V < 1.  Bad arguments are decided before the geometry, everything before any launch.
+ * ea_beam_merge: launch B / C alone, on candidate lists the caller supplies: cand_idx, cand_score [S W, 2 W] (the row stride
+ * is 2 W whatever kc), kc <= 2 W live per row (k' = kc; the forced step reads entry 0 of each row alone: k' = 1), the same
+ * state and outputs; eos is any token id >= 0.  ea_ceva_sdecode_vocab_beam launches the same kernel.  EA_E_BADARG: S < 1,
+ * W < 1, kc outside 1 .. 2 W, eos < 0, max_new < 1, a NULL or misaligned pointer; EA_E_UNSUPPORTED: W > 32, S W > 64. */
+int64_t ea_ceva_sdecode_vocab_beam_ws(int32_t M, int32_t V, int32_t W);
+int ea_ceva_sdecode_vocab_beam(int32_t M, int32_t K, int32_t V, const void* x, int32_t x_dtype, int64_t ldx,
+                               const void* w, int32_t w_dtype, float* logits, int64_t ldl, void* ws, int64_t ws_bytes,
+                               int32_t W, int32_t eos, int32_t max_new, float* score, int32_t* t, int32_t* nfin,
+                               int32_t* done, int64_t* token, int64_t* parent, int32_t* hist_tok, int32_t* hist_par,
+                               float* fin_score, int32_t* fin_len, int32_t* fin_beam, int32_t* cand_idx, float* cand_score,
+                               float* lse, float* sel_val, void* stream);
+int ea_beam_merge(int32_t S, int32_t W, int32_t kc, const int32_t* cand_idx, const float* cand_score, int32_t eos,
+                  int32_t max_new, float* score, int32_t* t, int32_t* nfin, int32_t* done, int64_t* token, int64_t* parent,
+                  int32_t* hist_tok, int32_t* hist_par, float* fin_score, int32_t* fin_len, int32_t* fin_beam, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
