@@ -41,7 +41,7 @@ static Geo mk_geo(const ea_geom* g) {
 extern "C" {
 
 const char* ea_version(void) { return "ea_hip 0.1.0 gfx950"; }
-int32_t ea_abi_version(void) { return 32; }
+int32_t ea_abi_version(void) { return 33; }
 
 int32_t ea_window_bias_ld(const ea_geom* g) {
   WinTiling t;
@@ -2088,6 +2088,7 @@ int ea_layernorm_bwd(int32_t xtype, int32_t rows, int32_t C, const void* x, cons
 #include "ea_ceva_decode_linear.h"
 #include "ea_ceva_decode_vocab.h"
 #include "ea_vocab_score.h"
+#include "ea_adaptive_score.h"
 static ea::DecT dec_mk(const ea_t4* t) {
   ea::DecT r;
   r.p = (const char*)t->ptr; r.sb = t->sb; r.sh = t->sh; r.sn = t->sn;
@@ -2553,6 +2554,76 @@ int ea_vocab_score(int32_t M, int32_t K, int32_t V, const void* x, int32_t x_dty
   p.ldx = ldx; p.ldl = logits ? ldl : 0; p.M = M; p.K = K; p.V = V; p.dtype = w_dtype;
   p.x_f32 = x_dtype == EA_F32; p.l_f32 = logits && logits_dtype == EA_F32;
   return ea::vocab_score(p, (hipStream_t)stream);
+}
+
+// ---- adaptive-softmax scoring (ABI 33, ea_adaptive_score.hip): the routing, the vocabulary pass over a row set, the composite.
+// Host arrays (cutoffs, dims, the per-tail operand pointers) are read here, before the first launch --------------------------
+static bool adp_cutoffs_ok(int32_t n_tails, const int64_t* cutoffs) {
+  if (n_tails < 1 || !cutoffs) return false;
+  for (int i = 0; i < n_tails && i < EA_ADAPTIVE_MAX_TAILS; ++i)
+    if (cutoffs[i + 1] <= cutoffs[i]) return false;
+  return cutoffs[0] >= 1;
+}
+
+int ea_adaptive_route(int32_t M, int32_t n_tails, const int64_t* cutoffs, const int64_t* targets, int64_t* head_target,
+                      int32_t* rows, int32_t* count, void* stream) {
+  if (M < 1 || !adp_cutoffs_ok(n_tails, cutoffs) || !targets || !head_target || !rows || !count) return EA_E_BADARG;
+  if ((uintptr_t)targets % 8 || (uintptr_t)head_target % 8 || (uintptr_t)rows % 4 || (uintptr_t)count % 4) return EA_E_BADARG;
+  if (n_tails > EA_ADAPTIVE_MAX_TAILS || cutoffs[n_tails] > INT32_MAX) return EA_E_UNSUPPORTED;
+  ea::AdaptiveRouteP p = {};
+  p.targets = targets; p.head_target = head_target; p.rows = rows; p.count = count; p.M = M; p.n = n_tails;
+  for (int i = 0; i <= n_tails; ++i) p.cut[i] = cutoffs[i];
+  return ea::adaptive_route(p, (hipStream_t)stream);
+}
+
+int64_t ea_vocab_score_rows_ws(int32_t M, int32_t V) { return ea::vocab_score_ws(M, V); }
+
+int ea_vocab_score_rows(int32_t M, int32_t K, int32_t V, const void* x, int32_t x_dtype, int64_t ldx, const void* w,
+                        int32_t w_dtype, const int64_t* targets, void* logits, int32_t logits_dtype, int64_t ldl, void* ws,
+                        int64_t ws_bytes, int64_t* token, float* top, float* lse, float* logp, const int32_t* rows,
+                        const int32_t* count, int64_t target_base, int32_t logits_only, void* stream) {
+  if (!dec_table_ok(M, K, x, x_dtype, ldx, w, w_dtype) || !dec_logits_ok(V, logits, logits_dtype, ldl, w_dtype)) return EA_E_BADARG;
+  if (logits_only ? !logits : (!token || !lse || !logp)) return EA_E_BADARG;
+  if (!ws || (uintptr_t)ws % 16 || (uintptr_t)token % 8 || (uintptr_t)targets % 8) return EA_E_BADARG;
+  if ((uintptr_t)top % 4 || (uintptr_t)lse % 4 || (uintptr_t)logp % 4 || (uintptr_t)rows % 4 || (uintptr_t)count % 4) return EA_E_BADARG;
+  if (target_base < 0 || (logits_only != 0 && logits_only != 1)) return EA_E_BADARG;
+  const int64_t need = ea::vocab_score_ws(M, V);       // (< 0: a geometry refused below)
+  if (need >= 0 && ws_bytes < need) return EA_E_BADARG;
+  if (K % 32 || V < 1 || need < 0) return EA_E_UNSUPPORTED;
+  ea::VocabScoreRowsP p = {};
+  p.x = (const char*)x; p.w = (const char*)w; p.targets = logits_only ? nullptr : targets; p.logits = (char*)logits;
+  p.pick = (ea::VsPick*)ws; p.token = token; p.top = top; p.lse = lse; p.logp = logp;
+  p.ldx = ldx; p.ldl = logits ? ldl : 0; p.M = M; p.K = K; p.V = V; p.dtype = w_dtype;
+  p.x_f32 = x_dtype == EA_F32; p.l_f32 = logits && logits_dtype == EA_F32;
+  p.xrows = rows; p.trows = rows; p.count = count; p.target_base = target_base; p.logits_only = logits_only;
+  return ea::vocab_score_rows(p, (hipStream_t)stream);
+}
+
+int64_t ea_adaptive_score_ws(int32_t M, int32_t n_tails, const int64_t* cutoffs, const int32_t* dims) {
+  return ea::adaptive_plan(M, n_tails, cutoffs, dims, nullptr);
+}
+
+int ea_adaptive_score(int32_t M, int32_t C, int32_t n_tails, const int64_t* cutoffs, const int32_t* dims, const void* x,
+                      int32_t x_dtype, int64_t ldx, const int64_t* targets, const void* head, int32_t w_dtype,
+                      const void* const* proj, const void* const* tables, void* ws, int64_t ws_bytes, float* logp,
+                      int64_t* token_head, void* stream) {
+  if (!adp_cutoffs_ok(n_tails, cutoffs) || !dims || !proj || !tables) return EA_E_BADARG;
+  if (!dec_table_ok(M, C, x, x_dtype, ldx, head, w_dtype)) return EA_E_BADARG;
+  for (int i = 0; i < n_tails && i < EA_ADAPTIVE_MAX_TAILS; ++i)
+    if (dims[i] < 1 || !proj[i] || !tables[i] || (uintptr_t)proj[i] % 16 || (uintptr_t)tables[i] % 16) return EA_E_BADARG;
+  if (!targets || !ws || !logp || (uintptr_t)targets % 8 || (uintptr_t)ws % 16 || (uintptr_t)logp % 4 || (uintptr_t)token_head % 8)
+    return EA_E_BADARG;
+  const int64_t need = n_tails <= EA_ADAPTIVE_MAX_TAILS ? ea::adaptive_plan(M, n_tails, cutoffs, dims, nullptr) : -1;
+  if (need >= 0 && ws_bytes < need) return EA_E_BADARG;
+  if (n_tails > EA_ADAPTIVE_MAX_TAILS || C % 32 || need < 0) return EA_E_UNSUPPORTED;
+  for (int i = 0; i < n_tails; ++i)
+    if (dims[i] % 32) return EA_E_UNSUPPORTED;
+  ea::AdaptiveScoreP p = {};
+  p.x = (const char*)x; p.targets = targets; p.head = (const char*)head; p.ws = (char*)ws; p.logp = logp;
+  p.token_head = token_head; p.ldx = ldx; p.M = M; p.C = C; p.n = n_tails; p.dtype = w_dtype; p.x_f32 = x_dtype == EA_F32;
+  for (int i = 0; i <= n_tails; ++i) p.cut[i] = cutoffs[i];
+  for (int i = 0; i < n_tails; ++i) { p.dims[i] = dims[i]; p.proj[i] = (const char*)proj[i]; p.table[i] = (const char*)tables[i]; }
+  return ea::adaptive_score(p, (hipStream_t)stream);
 }
 
 }  // extern "C"

@@ -42,6 +42,16 @@ struct VocabScoreP {
   int x_f32, l_f32;           // 1: fp32 rows (x is rounded to `dtype` on load)
 };
 
+// the same pass over a gathered, device-counted set of rows (ABI 33, ea_adaptive_score.hip): M is the number of POSITIONS the
+// grid and ws are sized for; position j < live reads row xrows[j] of x and targets[trows[j]] and writes results j
+struct VocabScoreRowsP : VocabScoreP {
+  const int32_t* xrows;       // [M] rows of x, or null: the identity
+  const int32_t* trows;       // [M] entries of targets, or null: the identity
+  const int32_t* count;       // device scalar, the live positions (kept inside [0, M]), or null: M
+  int64_t target_base;        // >= 0, taken off a target before the range test against [0, V)
+  int logits_only;            // 1: the first launch alone, without pick, sums and target logits: a GEMM into `logits`
+};
+
 // bytes of ws for (M, V); < 0: outside the envelope (M < 1, V < 1, more than VS_MAX_WORKGROUPS workgroups)
 int64_t vocab_score_ws(int M, int V);
 // the two launches; the C entry point has checked pointers, alignment, strides, types and the size of ws

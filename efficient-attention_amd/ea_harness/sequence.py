@@ -240,6 +240,7 @@ _SAMPLE_MAX_K = 64
 _LOGPROB = "ea_ceva_sdecode_vocab_logprob"
 _SAMPLE_LOGPROB = "ea_ceva_sdecode_vocab_sample_logprob"
 _SCORE = "ea_vocab_score"
+_ADAPTIVE = "ea_adaptive_score"
 _BEAM = "ea_ceva_sdecode_vocab_beam"
 _BEAM_MAX_W = 32
 
@@ -263,6 +264,48 @@ class Scorer:
 
     def __init__(self, ws, lse, logp):
         self.ws, self.lse, self.logp = ws, lse, logp
+
+
+class AdaptiveTables:
+    """What `DecoderStack.adaptive_tables(dtype)` returns, the held 16-bit operands of ea_adaptive_score (include/ea_hip.h, ABI
+    33): `cutoff` (the list, ending with V), `dims` (d_i per tail), `head` [c0 + n, C] (band 0's table with the class rows
+    behind it), `proj[i]` [d_i, C] (K-contiguous: a tied [C, d_i] projection is transposed as the copy is taken) and
+    `tables[i]` [V_i, d_i].  `refresh()` re-reads the parameters in place (rounded to nearest even; every data_ptr() stays)."""
+
+    def __init__(self, softmax, dtype, device):
+        if dtype not in (torch.bfloat16, torch.float16):
+            raise ValueError("adaptive_tables holds 16-bit operands (bfloat16 or float16), got %s" % dtype)
+        self.softmax, self.cutoff, self.dims = softmax, list(softmax.cutoff), softmax.band_dims()
+        n, C = len(self.dims), softmax.input_dim
+
+        def buf(*shape):
+            return torch.empty(shape, dtype=dtype, device=device)
+        self.head = buf(self.cutoff[0] + n, C)
+        self.proj = [buf(d, C) for d in self.dims]
+        self.tables = [buf(self.cutoff[i + 1] - self.cutoff[i], d) for i, d in enumerate(self.dims)]
+        self.refresh()
+
+    @property
+    def dtype(self):
+        return self.head.dtype
+
+    @property
+    def device(self):
+        return self.head.device
+
+    def refresh(self):
+        sm, c0 = self.softmax, self.cutoff[0]
+        with torch.no_grad():
+            full = sm.head_table()
+            self.head[:c0].copy_(full[:c0])
+            self.head[c0:].copy_(full[c0:])
+            for i in range(len(self.dims)):
+                self.proj[i].copy_(sm.tail_projection(i))
+                self.tables[i].copy_(sm.tail_table(i))
+        return self
+
+    def nbytes(self):
+        return sum(t.numel() * t.element_size() for t in [self.head] + self.proj + self.tables)
 
 
 class Beam:
@@ -299,6 +342,10 @@ def _hold_vocab_option(init):
 
     @functools.wraps(init)
     def init_decoding(self, *args, hold_vocab=False, **kw):
+        if hold_vocab and self.is_adaptive:
+            raise NotImplementedError("hold_vocab=True on an adaptive stack: the held pick, sampler, scorer and beam entries "
+                                      "read one [V, C] table; decoding from the adaptive head on HIP is not built "
+                                      "(`logits` is the slow route, `rows_logprobs` / `evaluate` score)")
         if hold_vocab:
             given = params.bind(self, *args, **kw).arguments
             if given["dtype"] == torch.float32:
@@ -321,8 +368,12 @@ def _hold_vocab_option(init):
 class DecoderStack(nn.Module):
     """Decoder-only language model shaped like EncoderStack: token embedding (scaled) + sinusoidal positions -> `layers`
     DecoderLayers (-> a final LayerNorm with final_norm=True) -> [T, B, C]; `logits` is the tied output projection.
-    fairseq's adaptive input and adaptive softmax (the wikitext-103 recipe's embedding and output layers) are out of scope:
-    a plain tied embedding stands in for both.
+    Without `adaptive` a plain tied embedding is both the input and the output layer.  adaptive=dict(cutoff=[...], factor=4,
+    dropout=0.0, tie_weights=True, tie_proj=True) builds fairseq's adaptive input and adaptive softmax (the wikitext-103
+    recipe's embedding and output layers, ea_harness/adaptive.py) under fairseq's member names, `embed_tokens` and
+    `adaptive_softmax`: a reference checkpoint's decoder keys load.  On such a stack `forward`, `decode`, `evaluate` and
+    `rows_logprobs` (teacher-forced scoring on ea_adaptive_score, C ABI 33) work, `logits` is the slow torch route, and
+    `init_decoding(hold_vocab=True)` raises: greedy, sampled and beam decoding from the adaptive head on HIP are out of scope.
 
     Incremental decoding runs on the attention's static / rolling states (CausalEVAttention.init_*_decoding):
         state = stack.init_decoding(B, max_tokens, torch.bfloat16, "cuda")
@@ -330,12 +381,24 @@ class DecoderStack(nn.Module):
         new = stack.generate(prompt [B, P], n_new, state)      # greedy, one captured step replayed"""
 
     def __init__(self, vocab, embed_dim, ffn_dim, num_heads, layers, attn_args=None, dropout=0.1, attention_dropout=0.0,
-                 activation_dropout=0.0, normalize_before=True, final_norm=False, max_positions=4096, pad_idx=1):
+                 activation_dropout=0.0, normalize_before=True, final_norm=False, max_positions=4096, pad_idx=1,
+                 adaptive=None):
         super().__init__()
         self.embed_dim, self.pad_idx = embed_dim, pad_idx
-        self.embed_tokens = nn.Embedding(vocab, embed_dim, padding_idx=pad_idx)
-        nn.init.normal_(self.embed_tokens.weight, mean=0, std=embed_dim ** -0.5)
-        nn.init.constant_(self.embed_tokens.weight[pad_idx], 0)
+        if adaptive is None:
+            self.embed_tokens = nn.Embedding(vocab, embed_dim, padding_idx=pad_idx)
+            nn.init.normal_(self.embed_tokens.weight, mean=0, std=embed_dim ** -0.5)
+            nn.init.constant_(self.embed_tokens.weight[pad_idx], 0)
+        else:
+            from .adaptive import AdaptiveInput, AdaptiveSoftmax
+            opt = dict(dict(factor=4, dropout=0.0, tie_weights=True, tie_proj=True), **adaptive)
+            unknown = set(opt) - {"cutoff", "factor", "dropout", "tie_weights", "tie_proj"}
+            if unknown or "cutoff" not in opt:
+                raise ValueError("adaptive takes cutoff (required), factor, dropout, tie_weights, tie_proj; got %s"
+                                 % sorted(adaptive))
+            self.embed_tokens = AdaptiveInput(vocab, pad_idx, embed_dim, opt["factor"], embed_dim, list(opt["cutoff"]))
+            self.adaptive_softmax = AdaptiveSoftmax(vocab, embed_dim, list(opt["cutoff"]), opt["dropout"], opt["factor"],
+                                                    self.embed_tokens if opt["tie_weights"] else None, opt["tie_proj"])
         self.register_buffer("positions", EncoderStack._sinusoid(max_positions, embed_dim), persistent=False)
         self.dropout = nn.Dropout(dropout)
         self.layers = nn.ModuleList([DecoderLayer(embed_dim, ffn_dim, num_heads, attn_args, dropout, attention_dropout,
@@ -344,13 +407,25 @@ class DecoderStack(nn.Module):
 
     def forward(self, tokens, key_padding_mask=None):                      # tokens [B, T] int64, mask [B, T] (1 = pad)
         B, T = tokens.shape
-        x = self.embed_tokens(tokens) * (self.embed_dim ** 0.5) + self.positions[:T].to(self.embed_tokens.weight.dtype)
+        x = self.embed_tokens(tokens) * (self.embed_dim ** 0.5) + self.positions[:T].to(self._embed_dtype())
         x = self.dropout(x).transpose(0, 1)                                 # [T, B, C]
         for layer in self.layers:
             x = layer(x, key_padding_mask)
         return x if self.layer_norm is None else self.layer_norm(x)
 
+    @property
+    def is_adaptive(self):
+        return hasattr(self, "adaptive_softmax")
+
+    def _embed_dtype(self):
+        return self.embed_tokens.dtype if self.is_adaptive else self.embed_tokens.weight.dtype
+
     def logits(self, x):                                                    # [T, B, C] -> [T, B, vocab]
+        """The tied output projection.  On an adaptive stack: the log-probabilities of the WHOLE vocabulary by the torch
+        restatement (AdaptiveSoftmax.get_log_prob: every tail on every row, a [T, B, V] tensor) -- the slow route, for
+        `generate` on a state without hold_vocab; scoring runs on `rows_logprobs`."""
+        if self.is_adaptive:
+            return self.adaptive_softmax.get_log_prob(x)
         return F.linear(x, self.embed_tokens.weight)
 
     # ---- incremental decoding -----------------------------------------------------------------------------------------------
@@ -474,8 +549,7 @@ class DecoderStack(nn.Module):
         pos = attn0.decoding_positions_tensor(state.incremental)             # [1] or [B] int32, on the device
         idx = pos.to(torch.long).view(1, -1) + torch.arange(T, device=pos.device).view(T, 1)
         idx = idx.clamp_(max=self.positions.shape[0] - 1).expand(T, B)       # (a step past the table overflows the state too)
-        w = self.embed_tokens.weight
-        x = self.embed_tokens(tokens) * (self.embed_dim ** 0.5) + self.positions[idx].to(w.dtype)
+        x = self.embed_tokens(tokens) * (self.embed_dim ** 0.5) + self.positions[idx].to(self._embed_dtype())
         for i, layer in enumerate(self.layers):
             x = layer._attend(x, key_padding_mask, state.incremental)
             x = layer._feed_forward(x, None if state.ffn is None else state.ffn[i])
@@ -717,7 +791,7 @@ class DecoderStack(nn.Module):
             else contextlib.nullcontext()
         with torch.no_grad(), ctx:
             if state is None:
-                dtype = torch.get_autocast_dtype("cuda") if amp else self.embed_tokens.weight.dtype
+                dtype = torch.get_autocast_dtype("cuda") if amp else self._embed_dtype()
                 state = self.init_logprobs(self.init_decoding(B, T - 1, dtype, tokens.device, hold_vocab=True))
             elif state.scorer is None:
                 raise RuntimeError("score needs a decoding state with a scorer: init_logprobs(state)")
@@ -761,7 +835,12 @@ class DecoderStack(nn.Module):
         ea_vocab_score (include/ea_hip.h, ABI 30) on a workspace sized by its query: a tiled GEMM on the matrix cores with
         the pick and an online log-sum-exp as its epilogue -- no framework GEMM, no [T B, V] tensor; the table is read once
         per 128 rows.  A logit's order of summation is that kernel's own: results agree with `token_logprobs` to rounding,
-        not bit for bit.  A row's results do not depend on the rows beside it."""
+        not bit for bit.  A row's results do not depend on the rows beside it.
+        table an AdaptiveTables (`adaptive_tables`): ONE call of ea_adaptive_score (ABI 33) -> (head_tokens int64 [T, B], the
+        greedy pick among the head's c0 + n columns, logp fp32 [T, B]), the targets' log-probabilities under the adaptive
+        softmax; `targets` is required there (the whole distribution is `logits`, the slow route), return_lse is not offered."""
+        if isinstance(table, AdaptiveTables):
+            return self._adaptive_rows_logprobs(rows, table, targets, return_lse)
         from efficient_attention import _native as nv
         x2 = self._score_rows(rows, table)
         T, B, C = rows.shape
@@ -784,6 +863,45 @@ class DecoderStack(nn.Module):
                 V, nv.ptr(ws), ws.numel(), nv.ptr(out), None, nv.ptr(lse), nv.ptr(logp), nv.stream())
         return (out, logp, lse) if return_lse else (out, logp)
 
+    def adaptive_tables(self, dtype=torch.bfloat16, device=None):
+        """The 16-bit operands of `rows_logprobs` on an adaptive stack, copied once (an AdaptiveTables; `refresh()` re-reads
+        them in place): about 2 (c0 C + sum_i (d_i C + V_i d_i)) bytes."""
+        if not self.is_adaptive:
+            raise RuntimeError("adaptive_tables needs a stack built with adaptive=dict(cutoff=...)")
+        if device is None:
+            device = self.adaptive_softmax.tail_table(0).device
+        return AdaptiveTables(self.adaptive_softmax, dtype, device)
+
+    def _adaptive_rows_logprobs(self, rows, tables, targets, return_lse):
+        if targets is None:
+            raise ValueError("rows_logprobs on adaptive tables scores targets: pass targets (the whole distribution is "
+                             "`logits`, the slow route)")
+        if return_lse:
+            raise ValueError("rows_logprobs on adaptive tables has no single log-sum-exp to return")
+        from efficient_attention import _native as nv
+        import ctypes
+        x2 = self._score_rows(rows, tables.head)
+        T, B, C = rows.shape
+        dev, n = x2.device, len(tables.dims)
+        if targets.dtype != torch.long or tuple(targets.shape) != (T, B) or targets.device != dev:
+            raise ValueError("targets must be an int64 [%d, %d] tensor on the rows' device" % (T, B))
+        targets = targets.contiguous().view(T * B)
+        nv.require_cuda(x2, "rows")
+        cut = nv.host_array(ctypes.c_int64, tables.cutoff)
+        dims = nv.host_array(ctypes.c_int32, tables.dims)
+        nbytes = nv.lib().ea_adaptive_score_ws(T * B, n, cut, dims) if max(T * B, C) < 2 ** 31 else -1
+        if nbytes < 0:
+            raise ValueError("%d rows against cutoffs %s are outside ea_adaptive_score's envelope" % (T * B, tables.cutoff))
+        ws = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+        head = torch.empty((T, B), dtype=torch.long, device=dev)
+        logp = torch.empty((T, B), dtype=torch.float32, device=dev)
+        code = nv.EA_F32 if x2.dtype == torch.float32 else nv.io_dtype(x2)
+        nv.call(_ADAPTIVE, T * B, C, n, cut, dims, nv.ptr(x2), code, C, nv.ptr(targets), nv.ptr(tables.head),
+                nv.io_dtype(tables.head), nv.host_array(ctypes.c_void_p, [t.data_ptr() for t in tables.proj]),
+                nv.host_array(ctypes.c_void_p, [t.data_ptr() for t in tables.tables]), nv.ptr(ws), ws.numel(), nv.ptr(logp),
+                nv.ptr(head), nv.stream())
+        return head, logp
+
     def evaluate(self, tokens, table=None, key_padding_mask=None, return_tokens=False):
         """Teacher-forced log-probabilities for corpus-scale evaluation (perplexity): tokens [B, T] int64 -> fp32 [B, T - 1],
         entry [b, t] = log p(tokens[b, t + 1] | tokens[b, :t + 1]); entries whose target is `pad_idx` are 0, as in `score`;
@@ -793,7 +911,10 @@ class DecoderStack(nn.Module):
         How it differs from `score`: that one feeds the tokens through `decode` -- the incremental DECODING path and its
         state -- and streams the table once per 64 rows, ceil(rows / 64) passes; this one runs the full (training-shaped)
         forward and passes over the table in proportion to ceil(rows / 128), the row tile of ea_vocab_score, each pass on
-        the matrix cores at full tiles.  The two agree to rounding, not bit for bit."""
+        the matrix cores at full tiles.  The two agree to rounding, not bit for bit.
+        On an adaptive stack `table` is an AdaptiveTables (default: `adaptive_tables` in the autocast dtype, else bfloat16)
+        and the rows are scored by ONE ea_adaptive_score call: no [rows, V] and no [rows, c0 + n] tensor exists;
+        return_tokens gives the greedy pick among the head's columns (a class column c0 + i stands for tail i)."""
         if self.training:
             raise NotImplementedError("evaluate in training mode")
         B, T = tokens.shape
@@ -802,7 +923,8 @@ class DecoderStack(nn.Module):
         with torch.no_grad():
             if table is None:
                 dtype = torch.get_autocast_dtype("cuda") if torch.is_autocast_enabled() else torch.bfloat16
-                table = self.embed_tokens.weight.detach().to(dtype).contiguous()
+                table = self.adaptive_tables(dtype, tokens.device) if self.is_adaptive \
+                    else self.embed_tokens.weight.detach().to(dtype).contiguous()
             rows = self(tokens[:, :-1], key_padding_mask)                    # [T - 1, B, C]
             targets = tokens[:, 1:].t().contiguous()
             greedy, logp = self.rows_logprobs(rows, table, targets)
@@ -946,7 +1068,7 @@ class DecoderStack(nn.Module):
             else contextlib.nullcontext()
         with torch.no_grad(), ctx:
             if state is None:
-                dtype = torch.get_autocast_dtype("cuda") if amp else self.embed_tokens.weight.dtype
+                dtype = torch.get_autocast_dtype("cuda") if amp else self._embed_dtype()
                 state = self.init_decoding(M, P + max(max_new, 1), dtype, prompt.device, hold_vocab=True)
             if state.beam is None:
                 self.init_beam_search(state, W, eos_idx, max_new, len_penalty)
@@ -1036,7 +1158,7 @@ class DecoderStack(nn.Module):
             else contextlib.nullcontext()                        # (a capture may not use autocast's weight-cast cache)
         with torch.no_grad(), ctx:
             if state is None:
-                dtype = torch.get_autocast_dtype("cuda") if amp else self.embed_tokens.weight.dtype
+                dtype = torch.get_autocast_dtype("cuda") if amp else self._embed_dtype()
                 state = self.init_decoding(B, P + n_new, dtype, prompt.device, hold_weights=dtype != torch.float32)
             per_seq = state.options["per_sequence"]
             mask = prompt.eq(self.pad_idx) if per_seq else None
@@ -1110,10 +1232,16 @@ class DecoderStack(nn.Module):
         return (out, rows) if return_rows else out
 
 
-def wikitext103_decoder(attn_args=None, vocab=32768, **kw):
+def wikitext103_decoder(attn_args=None, vocab=32768, adaptive=None, **kw):
     """The decoder of the wikitext-103 recipe (transformer_lm_wiki103: 1024 / 4096 / 8 heads / 16 layers, pre-norm, no final
     decoder norm) around CausalEVAttention; attn_args default to the recipe's (window 128, chunks of 8, causal, adaptive 'qk',
-    T5 bias).  Adaptive input and adaptive softmax are out of scope (see DecoderStack)."""
+    T5 bias).  adaptive=None: a plain tied embedding stands in for the recipe's adaptive input and adaptive softmax.
+    adaptive=True (with vocab=267744, the recipe's dictionary): the recipe's own -- cutoffs 20000, 60000, factor 4, softmax
+    dropout 0.2, weights and projections tied; a dict is handed to DecoderStack as it is."""
+    if adaptive is True:
+        adaptive = dict(cutoff=[20000, 60000], factor=4, dropout=0.2, tie_weights=True, tie_proj=True)
+    if adaptive:
+        kw["adaptive"] = adaptive
     if attn_args is None:
         attn_args = dict(window_size=128, chunk_size=8, causal=True, adaptive_proj="qk", use_t5_rpe=True, num_chunks=None,
                          overlap_window=False)

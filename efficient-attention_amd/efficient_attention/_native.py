@@ -22,7 +22,7 @@ class ea_t4(ctypes.Structure):
                 ("sn", ctypes.c_int64)]
 
 
-ABI_VERSION = 32         # ea_abi_version() of include/ea_hip.h this file mirrors
+ABI_VERSION = 33         # ea_abi_version() of include/ea_hip.h this file mirrors
 
 
 class ea_geom(ctypes.Structure):
@@ -274,6 +274,11 @@ SIGNATURES = {
     "ea_vocab_score_ws": [_I, _I],
     "ea_vocab_score_tile": [_I],
     "ea_vocab_score": [_I, _I, _I, _P, _I, _L, _P, _I, _P, _P, _I, _L, _P, _L, _P, _P, _P, _P, _P],
+    "ea_adaptive_route": [_I, _I, _P, _P, _P, _P, _P, _P],
+    "ea_vocab_score_rows_ws": [_I, _I],
+    "ea_vocab_score_rows": [_I, _I, _I, _P, _I, _L, _P, _I, _P, _P, _I, _L, _P, _L, _P, _P, _P, _P, _P, _P, _L, _I, _P],
+    "ea_adaptive_score_ws": [_I, _I, _P, _P],
+    "ea_adaptive_score": [_I, _I, _I, _P, _P, _P, _I, _L, _P, _P, _I, _P, _P, _P, _L, _P, _P, _P],
     "ea_softmax_attn_fwd": [_I, _I, _I, _I, _I, _F, _T, _T, _T, _P, _T, _P, _P, _F, _I, _P],
     "ea_softmax_sample": [_I, _I, _I, _I, _I, _F, _T, _T, _P, _P, _P],
     "ea_softmax_attn_bwd": [_I, _I, _I, _I, _I, _F, _T, _T, _T, _P, _T, _T, _P, _P, _T, _T, _T, _P, _F, _I, _P],
@@ -308,6 +313,8 @@ def lib():
         cdll.ea_ceva_sdecode_vocab_lse_ws.restype = ctypes.c_int64
         cdll.ea_ceva_sdecode_vocab_beam_ws.restype = ctypes.c_int64
         cdll.ea_vocab_score_ws.restype = ctypes.c_int64
+        cdll.ea_vocab_score_rows_ws.restype = ctypes.c_int64
+        cdll.ea_adaptive_score_ws.restype = ctypes.c_int64
         cdll.ea_version.restype = ctypes.c_char_p
         cdll.ea_abi_version.restype = ctypes.c_int32
         if cdll.ea_abi_version() != ABI_VERSION:
@@ -325,6 +332,11 @@ def vocab_score_tiles():
     """(BM, BN, SL) of ea_vocab_score: the row tile, the column block and the slice width the library was compiled with."""
     fn = lib().ea_vocab_score_tile
     return tuple(int(fn(i)) for i in range(3))
+
+
+def host_array(ctype, values):
+    """A host array argument of the C ABI (cutoffs, dims, per-tail operand pointers): read by the entry before it returns."""
+    return (ctype * len(values))(*values)
 
 
 def _check(rc, what):

@@ -1293,6 +1293,73 @@ int ea_beam_merge(int32_t S, int32_t W, int32_t kc, const int32_t* cand_idx, con
                   int32_t max_new, float* score, int32_t* t, int32_t* nfin, int32_t* done, int64_t* token, int64_t* parent,
                   int32_t* hist_tok, int32_t* hist_par, float* fin_score, int32_t* fin_len, int32_t* fin_beam, void* stream);
 
+/* ABI 33, ADAPTIVE-SOFTMAX SCORING (ea_harness DecoderStack.adaptive_tables, rows_logprobs, evaluate on an adaptive stack;
+ * ea_adaptive_score.hip): teacher-forced log-probabilities under fairseq's adaptive softmax, on the tile loop of ABI 30.
+ * cutoffs [n_tails + 1] (a HOST array, read before the first launch): 1 <= c0 < c1 < .. < c_n = V < 2^31.  The head holds the
+ * tokens [0, c0) and one class column per tail, c0 + n_tails columns; tail i holds [c_i, c_{i+1}), V_i tokens at width d_i.
+ * 1 <= n_tails <= EA_ADAPTIVE_MAX_TAILS.  Every kernel: ordinary stores only, no atomics, no workgroup waits for another,
+ * bitwise reproducible, launches only (a call can be captured; sizes and cutoffs are host scalars a capture fixes).
+ *
+ * ea_adaptive_route, one launch of one workgroup: targets [M] int64 ->
+ *   head_target[m] (int64) = t for 0 <= t < c0; c0 + i for t in tail i; -1 for t outside [0, V)
+ *   rows[i][0 .. count[i]) (int32, rows is [n_tails][M], row stride M) = the rows whose target lies in tail i, ASCENDING (a
+ *   stable compaction); entries at or beyond count[i] are left as they were;  count [n_tails] int32, on the device.
+ * EA_E_BADARG: M < 1, n_tails < 1, cutoffs NULL, not increasing or c0 < 1, a NULL pointer, targets or head_target not 8-byte,
+ * rows or count not 4-byte aligned.  EA_E_UNSUPPORTED: n_tails > EA_ADAPTIVE_MAX_TAILS, V >= 2^31.
+ *
+ * ea_vocab_score_rows: ea_vocab_score over a gathered, device-counted set of rows.  Its arguments, then
+ *   rows         int32 [M] on the device, indices of rows of x and of entries of targets; NULL: the identity
+ *   count        int32 device scalar, 0 <= *count <= M (kept inside that range); NULL: M
+ *   target_base  >= 0, subtracted from a target before the test against [0, V): logp[j] = logit[j, targets[rows[j]] -
+ *                target_base] - lse[j]
+ *   logits_only  0 | 1.  1: the first launch alone, without the pick / log-sum-exp bookkeeping: a GEMM whose output is
+ *                `logits` (then required; token, top, lse, logp, targets are neither read nor written and may be NULL)
+ * M is the number of POSITIONS: the grid and ws (ea_vocab_score_rows_ws(M, V) = ea_vocab_score_ws(M, V)) are sized for it.
+ * Position j < *count reads row rows[j] of x and writes token[j], top[j], lse[j], logp[j] and row j of logits.  A workgroup
+ * whose row tile starts at or beyond *count returns before its first operand load; inside the last live tile a position
+ * >= *count is clamped to position *count - 1 BEFORE rows[] is read, so a list entry at or beyond *count is never
+ * dereferenced; results at positions >= *count are not written; *count == 0 writes nothing.  A position's results depend on
+ * the row it names, on V and on K alone; with rows = count = NULL, target_base = 0 they have ea_vocab_score's bits.
+ * Errors: ea_vocab_score's; also target_base < 0, logits_only outside {0, 1}, rows or count not 4-byte aligned: EA_E_BADARG.
+ *
+ * ea_adaptive_score: the whole score in one call, 4 + 3 n_tails launches.  x [M, ldx] of x_dtype = EA_F32 | w_dtype, targets
+ * [M] int64; the held operands, all of w_dtype = EA_BF16 | EA_F16, row-major, 16-byte aligned: head [c0 + n_tails, C] (the
+ * band-0 table with the class rows behind it); proj[i] [d_i, C] (K-contiguous: a tied [C, d_i] projection transposed once);
+ * tables[i] [V_i, d_i].  dims, proj, tables are HOST arrays of n_tails entries.
+ *   route;  head: ea_vocab_score_rows' two launches on every row with head_target;  per tail i: the projection (one launch,
+ *   logits_only, rows[i] / count[i]: h_i = round_w(x[rows[i][j]] proj_i^T), compact, row j of h_i for position j), then the
+ *   tail (two launches on h_i, identity rows, count[i], targets read through rows[i], target_base = c_i);  combine (one
+ *   launch): logp[m] = logp_head[m] for a head row, logp_head[m] + logp_tail_i[j] where rows[i][j] == m: one fp32 addition.
+ * A row whose target is outside [0, V) gets NaN.  token_head [M] int64 or NULL: the greedy pick among the head's columns.
+ * ws, r16 rounding up to a multiple of 16, the parts in this order from byte 0:
+ *   head_target int64 [M]  r16(8 M) | rows int32 [n_tails][M]  r16(4 n_tails M) | count int32 [EA_ADAPTIVE_MAX_TAILS]  16 |
+ *   token_head int64 [M]  r16(8 M) | lse_head fp32 [M]  r16(4 M) | logp_head fp32 [M]  r16(4 M) |
+ *   for i = 0 .. n_tails - 1:  h_i w_dtype [M][d_i]  r16(2 M d_i) | token_i int64 [M]  r16(8 M) | lse_i  r16(4 M) | logp_i
+ *   r16(4 M)  (position-indexed: entry j belongs to row rows[i][j]) |
+ *   inner: ONE ea_vocab_score_rows workspace the passes use in turn, the largest of ea_vocab_score_ws(M, c0 + n_tails),
+ *   ea_vocab_score_ws(M, d_i), ea_vocab_score_ws(M, V_i)
+ * ea_adaptive_score_ws(M, n_tails, cutoffs, dims) = 16 + r16(4 n_tails M) + 2 r16(8 M) + 2 r16(4 M) + sum_i (r16(2 M d_i) +
+ * r16(8 M) + 2 r16(4 M)) + inner; < 0 for M < 1, n_tails outside 1 .. EA_ADAPTIVE_MAX_TAILS, cutoffs not increasing, c0 < 1,
+ * V >= 2^31, d_i < 1, or an inner pass outside ea_vocab_score_ws' envelope.
+ * EA_E_BADARG: a NULL array or operand, misaligned operands (x, head, proj[i], tables[i], ws: 16 bytes; targets, token_head: 8;
+ * logp: 4), cutoffs as above, w_dtype not 16-bit, x_dtype neither EA_F32 nor w_dtype, M < 1, C < 1, ldx < C or a row stride of
+ * x that is no multiple of 16 bytes, d_i < 1, ws_bytes below the query's answer.  EA_E_UNSUPPORTED: n_tails >
+ * EA_ADAPTIVE_MAX_TAILS, C % 32 != 0, d_i % 32 != 0, a geometry the query refuses.  Bad arguments are decided before the
+ * geometry, everything before any launch. */
+#define EA_ADAPTIVE_MAX_TAILS 4
+int ea_adaptive_route(int32_t M, int32_t n_tails, const int64_t* cutoffs, const int64_t* targets, int64_t* head_target,
+                      int32_t* rows, int32_t* count, void* stream);
+int64_t ea_vocab_score_rows_ws(int32_t M, int32_t V);
+int ea_vocab_score_rows(int32_t M, int32_t K, int32_t V, const void* x, int32_t x_dtype, int64_t ldx, const void* w,
+                        int32_t w_dtype, const int64_t* targets, void* logits, int32_t logits_dtype, int64_t ldl, void* ws,
+                        int64_t ws_bytes, int64_t* token, float* top, float* lse, float* logp, const int32_t* rows,
+                        const int32_t* count, int64_t target_base, int32_t logits_only, void* stream);
+int64_t ea_adaptive_score_ws(int32_t M, int32_t n_tails, const int64_t* cutoffs, const int32_t* dims);
+int ea_adaptive_score(int32_t M, int32_t C, int32_t n_tails, const int64_t* cutoffs, const int32_t* dims, const void* x,
+                      int32_t x_dtype, int64_t ldx, const int64_t* targets, const void* head, int32_t w_dtype,
+                      const void* const* proj, const void* const* tables, void* ws, int64_t ws_bytes, float* logp,
+                      int64_t* token_head, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
