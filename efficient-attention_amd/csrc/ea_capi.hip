@@ -41,7 +41,7 @@ static Geo mk_geo(const ea_geom* g) {
 extern "C" {
 
 const char* ea_version(void) { return "ea_hip 0.1.0 gfx950"; }
-int32_t ea_abi_version(void) { return 33; }
+int32_t ea_abi_version(void) { return 34; }
 
 int32_t ea_window_bias_ld(const ea_geom* g) {
   WinTiling t;
@@ -2089,6 +2089,7 @@ int ea_layernorm_bwd(int32_t xtype, int32_t rows, int32_t C, const void* x, cons
 #include "ea_ceva_decode_vocab.h"
 #include "ea_vocab_score.h"
 #include "ea_adaptive_score.h"
+#include "ea_adaptive_pick.h"
 static ea::DecT dec_mk(const ea_t4* t) {
   ea::DecT r;
   r.p = (const char*)t->ptr; r.sb = t->sb; r.sh = t->sh; r.sn = t->sn;
@@ -2624,6 +2625,35 @@ int ea_adaptive_score(int32_t M, int32_t C, int32_t n_tails, const int64_t* cuto
   for (int i = 0; i <= n_tails; ++i) p.cut[i] = cutoffs[i];
   for (int i = 0; i < n_tails; ++i) { p.dims[i] = dims[i]; p.proj[i] = (const char*)proj[i]; p.table[i] = (const char*)tables[i]; }
   return ea::adaptive_score(p, (hipStream_t)stream);
+}
+
+// ---- the greedy pick from the adaptive head (ABI 34, ea_adaptive_pick.hip): ea_adaptive_score's groups in their order ----------
+int64_t ea_adaptive_pick_ws(int32_t M, int32_t n_tails, const int64_t* cutoffs, const int32_t* dims) {
+  return ea::adaptive_pick_plan(M, n_tails, cutoffs, dims, nullptr);
+}
+
+int ea_adaptive_pick(int32_t M, int32_t C, int32_t n_tails, const int64_t* cutoffs, const int32_t* dims, const void* x,
+                     int32_t x_dtype, int64_t ldx, const int64_t* targets, const void* head, int32_t w_dtype,
+                     const void* const* proj, const void* const* tables, void* ws, int64_t ws_bytes, int64_t* token,
+                     float* logp, void* stream) {
+  if (!adp_cutoffs_ok(n_tails, cutoffs) || !dims || !proj || !tables) return EA_E_BADARG;
+  if (!dec_table_ok(M, C, x, x_dtype, ldx, head, w_dtype)) return EA_E_BADARG;
+  for (int i = 0; i < n_tails && i < EA_ADAPTIVE_MAX_TAILS; ++i)
+    if (dims[i] < 1 || !proj[i] || !tables[i] || (uintptr_t)proj[i] % 16 || (uintptr_t)tables[i] % 16) return EA_E_BADARG;
+  if (!ws || !token || !logp || (uintptr_t)targets % 8 || (uintptr_t)ws % 16 || (uintptr_t)token % 8 || (uintptr_t)logp % 4)
+    return EA_E_BADARG;
+  const bool envelope = n_tails <= EA_ADAPTIVE_MAX_TAILS && M <= EA_CEVA_LINEAR_MAX_ROWS;
+  const int64_t need = envelope ? ea::adaptive_pick_plan(M, n_tails, cutoffs, dims, nullptr) : -1;
+  if (need >= 0 && ws_bytes < need) return EA_E_BADARG;
+  if (!envelope || C % 32 || need < 0) return EA_E_UNSUPPORTED;
+  for (int i = 0; i < n_tails; ++i)
+    if (dims[i] % 32) return EA_E_UNSUPPORTED;
+  ea::AdaptivePickP p = {};
+  p.x = (const char*)x; p.targets = targets; p.head = (const char*)head; p.ws = (char*)ws; p.token = token; p.logp = logp;
+  p.ldx = ldx; p.M = M; p.C = C; p.n = n_tails; p.dtype = w_dtype; p.x_f32 = x_dtype == EA_F32;
+  for (int i = 0; i <= n_tails; ++i) p.cut[i] = cutoffs[i];
+  for (int i = 0; i < n_tails; ++i) { p.dims[i] = dims[i]; p.proj[i] = (const char*)proj[i]; p.table[i] = (const char*)tables[i]; }
+  return ea::adaptive_pick(p, (hipStream_t)stream);
 }
 
 }  // extern "C"

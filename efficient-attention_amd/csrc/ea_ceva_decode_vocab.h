@@ -120,6 +120,9 @@ int ceva_sdecode_vocab_sample(const DecVocabP& p, const DecSampleP& s, hipStream
 int64_t ceva_sdecode_vocab_lse_ws(int M, int V);
 // the table pass with tile sums, then the pick with lse and logp
 int ceva_sdecode_vocab_logprob(const DecLseP& p, hipStream_t st);
+// that entry's first launch alone (candidates, tile sums, the targets' logits; token, top, lse, logp are not written): the
+// adaptive pick folds the partials of several tables itself (ea_adaptive_pick.hip)
+int ceva_sdecode_vocab_table_pass(const DecLseP& p, hipStream_t st);
 // the table pass with tile sums on p, ceva_vocab_sample_kernel on s, then lse and logp of the drawn tokens (p.token_in = s.token)
 int ceva_sdecode_vocab_sample_logprob(const DecLseP& p, const DecSampleP& s, hipStream_t st);
 

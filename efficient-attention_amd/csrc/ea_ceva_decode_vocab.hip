@@ -528,6 +528,11 @@ int ceva_sdecode_vocab_logprob(const DecLseP& p, hipStream_t st) {
   return rc != 0 ? rc : voc_row_pass(ceva_vocab_pick_kernel<DecLseP>, PICK_THREADS, p, p.M, st);
 }
 
+int ceva_sdecode_vocab_table_pass(const DecLseP& p, hipStream_t st) {
+  if (p.token_in) return EA_E_BADARG;
+  return voc_table_pass(p, 0, st);
+}
+
 int ceva_sdecode_vocab_sample_logprob(const DecLseP& p, const DecSampleP& s, hipStream_t st) {
   if (!voc_sampler_ok(p, s) || p.token_in != s.token || p.targets) return EA_E_BADARG;
   int rc = voc_table_pass(p, s.top_k, st);

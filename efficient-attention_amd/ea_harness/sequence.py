@@ -14,7 +14,9 @@ state holds (ea_ceva_sdecode_vocab_argmax), `init_sampling` / `sample_tokens` th
 `init_logprobs` / `token_logprobs` / `sample_tokens_logprobs` / `score` report a token's log-probability under the model's own
 distribution from the same pass over the table (ea_ceva_sdecode_vocab_logprob, ea_ceva_sdecode_vocab_sample_logprob);
 `init_beam_search` / `beam_step` / `beam_search` are a beam search whose step -- candidates, merge, finished hypotheses and the
-parent index of the state reorder -- runs on the device (ea_ceva_sdecode_vocab_beam)."""
+parent index of the state reorder -- runs on the device (ea_ceva_sdecode_vocab_beam).  On an adaptive stack
+`init_adaptive_decoding` makes a state pick greedily, with log-probabilities, from the held adaptive tables
+(ea_adaptive_pick)."""
 import argparse
 import contextlib
 import functools
@@ -215,11 +217,13 @@ class DecodingState:
     (the 16-bit [V, C] copy of embed_tokens.weight) and `vocab_ws` (the pick's workspace, bytes); both None otherwise.
     The fourth argument is that pair, (vocab, vocab_ws), or None.
     `sampler` is None until `DecoderStack.init_sampling` attaches a Sampler, `scorer` until `DecoderStack.init_logprobs`
-    attaches a Scorer, `beam` until `DecoderStack.init_beam_search` attaches a Beam."""
+    attaches a Scorer, `beam` until `DecoderStack.init_beam_search` attaches a Beam, `adaptive` until
+    `DecoderStack.init_adaptive_decoding` attaches an AdaptivePick."""
 
     sampler = None
     scorer = None
     beam = None
+    adaptive = None
 
     def __init__(self, incremental, ffn, options, vocab=None):
         self.incremental, self.ffn, self.options = incremental, ffn, options
@@ -241,6 +245,7 @@ _LOGPROB = "ea_ceva_sdecode_vocab_logprob"
 _SAMPLE_LOGPROB = "ea_ceva_sdecode_vocab_sample_logprob"
 _SCORE = "ea_vocab_score"
 _ADAPTIVE = "ea_adaptive_score"
+_ADAPTIVE_PICK = "ea_adaptive_pick"
 _BEAM = "ea_ceva_sdecode_vocab_beam"
 _BEAM_MAX_W = 32
 
@@ -270,7 +275,9 @@ class AdaptiveTables:
     """What `DecoderStack.adaptive_tables(dtype)` returns, the held 16-bit operands of ea_adaptive_score (include/ea_hip.h, ABI
     33): `cutoff` (the list, ending with V), `dims` (d_i per tail), `head` [c0 + n, C] (band 0's table with the class rows
     behind it), `proj[i]` [d_i, C] (K-contiguous: a tied [C, d_i] projection is transposed as the copy is taken) and
-    `tables[i]` [V_i, d_i].  `refresh()` re-reads the parameters in place (rounded to nearest even; every data_ptr() stays)."""
+    `tables[i]` [V_i, d_i].  The projections are the row blocks of ONE [sum d_i, C] buffer (`proj_all`), so that
+    ea_adaptive_pick forms every h_i in one launch.  `refresh()` re-reads the parameters in place (rounded to nearest even;
+    every data_ptr() stays)."""
 
     def __init__(self, softmax, dtype, device):
         if dtype not in (torch.bfloat16, torch.float16):
@@ -281,7 +288,8 @@ class AdaptiveTables:
         def buf(*shape):
             return torch.empty(shape, dtype=dtype, device=device)
         self.head = buf(self.cutoff[0] + n, C)
-        self.proj = [buf(d, C) for d in self.dims]
+        self.proj_all = buf(sum(self.dims), C)
+        self.proj = list(self.proj_all.split(self.dims, 0))
         self.tables = [buf(self.cutoff[i + 1] - self.cutoff[i], d) for i, d in enumerate(self.dims)]
         self.refresh()
 
@@ -306,6 +314,15 @@ class AdaptiveTables:
 
     def nbytes(self):
         return sum(t.numel() * t.element_size() for t in [self.head] + self.proj + self.tables)
+
+
+class AdaptivePick:
+    """What `DecoderStack.init_adaptive_decoding` attaches to a DecodingState: `tables` (an AdaptiveTables in the state's
+    dtype), `ws` (the workspace of ea_adaptive_pick for 64 rows, bytes) and the static fp32 buffer `logp` [batch_size] a
+    captured step writes its token's log-probability into."""
+
+    def __init__(self, tables, ws, logp):
+        self.tables, self.ws, self.logp = tables, ws, logp
 
 
 class Beam:
@@ -344,8 +361,8 @@ def _hold_vocab_option(init):
     def init_decoding(self, *args, hold_vocab=False, **kw):
         if hold_vocab and self.is_adaptive:
             raise NotImplementedError("hold_vocab=True on an adaptive stack: the held pick, sampler, scorer and beam entries "
-                                      "read one [V, C] table; decoding from the adaptive head on HIP is not built "
-                                      "(`logits` is the slow route, `rows_logprobs` / `evaluate` score)")
+                                      "read one [V, C] table; the greedy pick from the adaptive head is "
+                                      "init_adaptive_decoding(state) (sampling and beam search from it are not built)")
         if hold_vocab:
             given = params.bind(self, *args, **kw).arguments
             if given["dtype"] == torch.float32:
@@ -372,8 +389,10 @@ class DecoderStack(nn.Module):
     dropout=0.0, tie_weights=True, tie_proj=True) builds fairseq's adaptive input and adaptive softmax (the wikitext-103
     recipe's embedding and output layers, ea_harness/adaptive.py) under fairseq's member names, `embed_tokens` and
     `adaptive_softmax`: a reference checkpoint's decoder keys load.  On such a stack `forward`, `decode`, `evaluate` and
-    `rows_logprobs` (teacher-forced scoring on ea_adaptive_score, C ABI 33) work, `logits` is the slow torch route, and
-    `init_decoding(hold_vocab=True)` raises: greedy, sampled and beam decoding from the adaptive head on HIP are out of scope.
+    `rows_logprobs` (teacher-forced scoring on ea_adaptive_score, C ABI 33) work, and `init_adaptive_decoding(state)` makes a
+    decoding state pick greedily from the held adaptive tables (ea_adaptive_pick, C ABI 34): `next_tokens`, `token_logprobs`,
+    `score` and `generate` run on it.  `logits` is the slow torch route (a state without it), and
+    `init_decoding(hold_vocab=True)` raises: sampled and beam decoding from the adaptive head are out of scope.
 
     Incremental decoding runs on the attention's static / rolling states (CausalEVAttention.init_*_decoding):
         state = stack.init_decoding(B, max_tokens, torch.bfloat16, "cuda")
@@ -423,7 +442,7 @@ class DecoderStack(nn.Module):
     def logits(self, x):                                                    # [T, B, C] -> [T, B, vocab]
         """The tied output projection.  On an adaptive stack: the log-probabilities of the WHOLE vocabulary by the torch
         restatement (AdaptiveSoftmax.get_log_prob: every tail on every row, a [T, B, V] tensor) -- the slow route, for
-        `generate` on a state without hold_vocab; scoring runs on `rows_logprobs`."""
+        `generate` on a state without `init_adaptive_decoding`; scoring runs on `rows_logprobs`."""
         if self.is_adaptive:
             return self.adaptive_softmax.get_log_prob(x)
         return F.linear(x, self.embed_tokens.weight)
@@ -485,6 +504,8 @@ class DecoderStack(nn.Module):
             layer.self_attn.refresh_decoding_weights(state.incremental)
         self._load_held_ffn(state)
         self._load_held_vocab(state)
+        if state.adaptive is not None:
+            state.adaptive.tables.refresh()
         return state
 
     def reorder_decoding_state(self, state, new_order):
@@ -515,7 +536,8 @@ class DecoderStack(nn.Module):
         its workspace, of a sampler's logits, counters and stream ids (4 B V + 8 B + 4 B) and of a scorer's workspace and
         buffers (4 * 64 * (ceil(V / 16) + 1) + 8 B), and of a beam search's buffers for M = S W rows (`init_beam_search`):
         4 M V (logits) + ea_ceva_sdecode_vocab_beam_ws(M, V, W) (workspace) + 4 M (score) + 12 S (t, nfin, done) + 8 M
-        (parent) + 8 max_new M (the history) + 12 S W (the records)."""
+        (parent) + 8 max_new M (the history) + 12 S W (the records), and of an adaptive pick's tables, workspace
+        (ea_adaptive_pick_ws for 64 rows) and 4 B (logp)."""
         n = sum(layer.self_attn.decoding_state_nbytes(state.incremental) for layer in self.layers)
         n += sum(t.numel() * t.element_size() for held in (state.ffn or ()) for t in held)
         sm = state.sampler
@@ -525,6 +547,9 @@ class DecoderStack(nn.Module):
             extra += (sc.ws, sc.lse, sc.logp)
         if state.beam is not None:
             extra += state.beam.buffers()
+        if state.adaptive is not None:
+            n += state.adaptive.tables.nbytes()
+            extra += (state.adaptive.ws, state.adaptive.logp)
         return n + sum(t.numel() * t.element_size() for t in (state.vocab, state.vocab_ws) + extra if t is not None)
 
     def decoding_overflowed(self, state):
@@ -564,7 +589,14 @@ class DecoderStack(nn.Module):
         out: an int64 [T, B] contiguous tensor the tokens are written into (and returned) -- a captured step hands its own
         static input.  return_logits=True: -> (tokens, fp32 [T, B, V] logits), for a caller that samples.  Rows that are
         neither fp32 nor the table's type are widened to fp32 first (the kernel rounds fp32 rows to the table's type as it
-        loads them).  More than 64 rows run in pieces of 64.  Device launches only."""
+        loads them).  More than 64 rows run in pieces of 64.  Device launches only.
+        On a state with an adaptive pick (`init_adaptive_decoding`) the token is the argmax of the adaptive softmax's joint
+        log-probabilities, on ea_adaptive_pick; return_logits is not offered there."""
+        if state.adaptive is not None:
+            if return_logits:
+                raise ValueError("next_tokens(return_logits=True) on an adaptive pick: no [T, B, V] tensor exists there "
+                                 "(`logits` is the slow route)")
+            return self._adaptive_pick(rows, state, None, out, None)[0]
         if state.vocab is None:
             raise RuntimeError("next_tokens needs a decoding state that holds the vocabulary table: "
                                "init_decoding(..., hold_vocab=True)")
@@ -743,9 +775,76 @@ class DecoderStack(nn.Module):
         fp32 logits.  logp[t, b] = logit[targets[t, b]] - lse with `targets` (int64 [T, B] on the device; one outside [0, V)
         gives NaN), else the picked token's, top - lse.  `tokens` is the greedy pick either way, bit for bit `next_tokens`'.
         The distribution is the model's own at temperature 1; the table is streamed once per 64 rows, no [T B, V] tensor
-        exists.  A row's results do not depend on the rows beside it.  out: as in `next_tokens`.  Device launches only."""
+        exists.  A row's results do not depend on the rows beside it.  out: as in `next_tokens`.  Device launches only.
+        On a state with an adaptive pick (`init_adaptive_decoding`; no `init_logprobs` needed) logp is the joint
+        log-probability under the adaptive softmax, of targets[t, b] or of the picked token; there is no single log-sum-exp,
+        so return_lse raises."""
+        if state.adaptive is not None:
+            if return_lse:
+                raise ValueError("token_logprobs(return_lse=True) on an adaptive pick: an adaptive softmax has no single "
+                                 "log-sum-exp to return")
+            return self._adaptive_pick(rows, state, targets, out, None)
         tokens, logp, lse = self._logprob_pick(rows, state, targets, out, None, None)
         return (tokens, logp, lse) if return_lse else (tokens, logp)
+
+    # ---- the greedy pick from the adaptive head (ea_adaptive_pick, C ABI 34) ---------------------------------------------------
+    def init_adaptive_decoding(self, state, tables=None):
+        """Make `state` (a 16-bit decoding state of an adaptive stack) pick its tokens from the adaptive head on HIP:
+        `next_tokens`, `token_logprobs`, `score` and `generate` (with return_logprobs too) then end in ea_adaptive_pick
+        (include/ea_hip.h, ABI 34) -- the head, the projections and the tails are streamed once per 64 rows (89 MB on the
+        recipe's geometry against the 548 MB of a plain [V, C] table), no [rows, V] tensor exists, and the call can be
+        captured.  tables: an AdaptiveTables in the state's dtype on its device (default: `adaptive_tables` of them).
+        Attaches `state.adaptive` (an AdaptivePick: the tables, the workspace for 64 rows, fp32 logp [batch_size]) and
+        returns the state.  A beam reorder and a row reset have nothing of it to move; `refresh_decoding_weights` re-reads
+        the tables in place."""
+        if not self.is_adaptive:
+            raise RuntimeError("init_adaptive_decoding needs a stack built with adaptive=dict(cutoff=...)")
+        dtype, device = state.options["dtype"], state.options["device"]
+        if dtype == torch.float32:
+            raise ValueError("init_adaptive_decoding holds 16-bit tables: an fp32 decoding state (the fidelity path) keeps "
+                             "`logits`, the slow route")
+        if tables is None:
+            tables = self.adaptive_tables(dtype, device)
+        elif not isinstance(tables, AdaptiveTables) or tables.dtype != dtype:
+            raise ValueError("tables must be an AdaptiveTables in the state's dtype (%s)" % str(dtype).replace("torch.", ""))
+        from efficient_attention import _native as nv
+        import ctypes
+        nbytes = nv.lib().ea_adaptive_pick_ws(_FUSED_MAX_ROWS, len(tables.dims), nv.host_array(ctypes.c_int64, tables.cutoff),
+                                              nv.host_array(ctypes.c_int32, tables.dims))
+        if nbytes < 0:
+            raise ValueError("cutoffs %s at widths %s are outside ea_adaptive_pick's envelope" % (tables.cutoff, tables.dims))
+        state.adaptive = AdaptivePick(tables, torch.empty(nbytes, dtype=torch.uint8, device=tables.device),
+                                      torch.empty(state.options["batch_size"], dtype=torch.float32, device=tables.device))
+        return state
+
+    def _adaptive_pick(self, rows, state, targets, out, logp):
+        """rows [T, B, C] -> (tokens int64 [T, B], logp fp32 [T, B]) on ea_adaptive_pick, in pieces of 64 rows; out, logp:
+        the places of the two (None: allocated)."""
+        from efficient_attention import _native as nv
+        import ctypes
+        ad = state.adaptive
+        tb = ad.tables
+        x2 = self._score_rows(rows, tb.head)
+        T, B, C = rows.shape
+        dev, n = x2.device, len(tb.dims)
+        out = self._vocab_out(out, (T, B), torch.long, dev, "out")
+        logp = self._vocab_out(logp, (T, B), torch.float32, dev, "logp")
+        if targets is not None:
+            if targets.dtype != torch.long or tuple(targets.shape) != (T, B) or targets.device != dev:
+                raise ValueError("targets must be an int64 [%d, %d] tensor on the rows' device" % (T, B))
+            targets = targets.contiguous().view(T * B)
+        nv.require_cuda(x2, "rows")
+        cut, dims = nv.host_array(ctypes.c_int64, tb.cutoff), nv.host_array(ctypes.c_int32, tb.dims)
+        proj = nv.host_array(ctypes.c_void_p, [t.data_ptr() for t in tb.proj])
+        tabs = nv.host_array(ctypes.c_void_p, [t.data_ptr() for t in tb.tables])
+        tok, lp = out.view(T * B), logp.view(T * B)
+        code = nv.EA_F32 if x2.dtype == torch.float32 else nv.io_dtype(x2)
+        for a in range(0, T * B, _FUSED_MAX_ROWS):
+            M = min(_FUSED_MAX_ROWS, T * B - a)
+            nv.call(_ADAPTIVE_PICK, M, C, n, cut, dims, nv.ptr(x2[a:a + M]), code, C,
+                    None if targets is None else nv.ptr(targets[a:a + M]), nv.ptr(tb.head), nv.io_dtype(tb.head), proj, tabs,
+                    nv.ptr(ad.ws), ad.ws.numel(), nv.ptr(tok[a:a + M]), nv.ptr(lp[a:a + M]), nv.stream())
+        return out, logp
 
     def _sample_logprob_pick(self, rows, state, out, logp, lse):
         sm, sc = state.sampler, state.scorer
@@ -778,8 +877,9 @@ class DecoderStack(nn.Module):
     def score(self, tokens, state=None):
         """Teacher-forced log-probabilities: tokens [B, T] int64 -> fp32 [B, T - 1], entry [b, t] = log p(tokens[b, t + 1] |
         tokens[b, :t + 1]) under the model's own distribution; entries whose target is `pad_idx` are 0.  One `decode` of
-        tokens[:, :-1] on `state` (a fresh state with a scorer; default: one made here with hold_vocab and the autocast or
-        the weights' 16-bit dtype), then `token_logprobs` with the targets.  The vocabulary table is re-streamed once per 64
+        tokens[:, :-1] on `state` (a fresh state with a scorer, or with an adaptive pick; default: one made here with
+        hold_vocab -- on an adaptive stack with `init_adaptive_decoding` -- and the autocast or the weights' 16-bit dtype),
+        then `token_logprobs` with the targets.  The vocabulary table is re-streamed once per 64
         rows of T - 1 times B: this serves prompt scoring, not corpus-scale evaluation."""
         if self.training:
             raise NotImplementedError("incremental decoding in training mode")
@@ -792,8 +892,11 @@ class DecoderStack(nn.Module):
         with torch.no_grad(), ctx:
             if state is None:
                 dtype = torch.get_autocast_dtype("cuda") if amp else self._embed_dtype()
-                state = self.init_logprobs(self.init_decoding(B, T - 1, dtype, tokens.device, hold_vocab=True))
-            elif state.scorer is None:
+                if self.is_adaptive:
+                    state = self.init_adaptive_decoding(self.init_decoding(B, T - 1, dtype, tokens.device))
+                else:
+                    state = self.init_logprobs(self.init_decoding(B, T - 1, dtype, tokens.device, hold_vocab=True))
+            elif state.scorer is None and state.adaptive is None:
                 raise RuntimeError("score needs a decoding state with a scorer: init_logprobs(state)")
             fed = tokens[:, :-1]
             mask = fed.eq(self.pad_idx) if state.options["per_sequence"] else None
@@ -1141,14 +1244,20 @@ class DecoderStack(nn.Module):
         return_logprobs=True (a state with a scorer, `init_logprobs`; its absence is reported before the prefill): both picks
         run on ea_ceva_sdecode_vocab_logprob / ea_ceva_sdecode_vocab_sample_logprob instead and write each token's
         log-probability under the model's own distribution (temperature 1, nothing truncated) into the scorer's static
-        buffer; -> (tokens[, rows], logp fp32 [B, n_new]).  The tokens are those of the same call without the keyword."""
+        buffer; -> (tokens[, rows], logp fp32 [B, n_new]).  The tokens are those of the same call without the keyword.
+        On a state with an adaptive pick (`init_adaptive_decoding`) both picks are ea_adaptive_pick: the step ends in that
+        kernel, which writes the token into the step's static input and its joint log-probability into
+        `state.adaptive.logp`, where return_logprobs=True takes it from (no scorer needed)."""
         if self.training:
             raise NotImplementedError("incremental decoding in training mode")
         B, P = prompt.shape
         n_new = int(n_new)
         if n_new < 1:
             raise ValueError("generate needs n_new >= 1, got %d" % n_new)
-        if return_logprobs:
+        adaptive = state is not None and state.adaptive is not None
+        if adaptive and B > state.adaptive.logp.numel():
+            raise ValueError("a prompt of %d rows on an adaptive pick made for %d" % (B, state.adaptive.logp.numel()))
+        if return_logprobs and not adaptive:
             if state is None or state.scorer is None:
                 raise RuntimeError("generate(return_logprobs=True) needs a decoding state with a scorer: init_logprobs(state)")
             if B > state.scorer.logp.numel():
@@ -1168,10 +1277,17 @@ class DecoderStack(nn.Module):
                 last = x[(n_b - 1).clamp_(min=0), torch.arange(B, device=x.device)].unsqueeze(0)
             else:
                 last = x[P - 1:P]
-            held = state.vocab is not None
+            held = state.vocab is not None or adaptive
             pick = self.next_tokens if state.sampler is None else self.sample_tokens
             lp_in = logps = None
-            if return_logprobs:                                              # [1, B] views of the scorer's static buffers
+            if adaptive:                                                     # [1, B] view of the pick's static buffer
+                lp_in = state.adaptive.logp[:B].view(1, B)
+                if return_logprobs:
+                    logps = torch.empty((B, n_new), dtype=torch.float32, device=prompt.device)
+
+                def pick(y, st, out=None):
+                    return self._adaptive_pick(y, st, None, out, lp_in)[0]
+            elif return_logprobs:                                            # [1, B] views of the scorer's static buffers
                 lp_in, lse_in = state.scorer.logp[:B].view(1, B), state.scorer.lse[:B].view(1, B)
                 logps = torch.empty((B, n_new), dtype=torch.float32, device=prompt.device)
                 if state.sampler is None:

@@ -22,7 +22,7 @@ class ea_t4(ctypes.Structure):
                 ("sn", ctypes.c_int64)]
 
 
-ABI_VERSION = 33         # ea_abi_version() of include/ea_hip.h this file mirrors
+ABI_VERSION = 34         # ea_abi_version() of include/ea_hip.h this file mirrors
 
 
 class ea_geom(ctypes.Structure):
@@ -279,6 +279,8 @@ SIGNATURES = {
     "ea_vocab_score_rows": [_I, _I, _I, _P, _I, _L, _P, _I, _P, _P, _I, _L, _P, _L, _P, _P, _P, _P, _P, _P, _L, _I, _P],
     "ea_adaptive_score_ws": [_I, _I, _P, _P],
     "ea_adaptive_score": [_I, _I, _I, _P, _P, _P, _I, _L, _P, _P, _I, _P, _P, _P, _L, _P, _P, _P],
+    "ea_adaptive_pick_ws": [_I, _I, _P, _P],
+    "ea_adaptive_pick": [_I, _I, _I, _P, _P, _P, _I, _L, _P, _P, _I, _P, _P, _P, _L, _P, _P, _P],
     "ea_softmax_attn_fwd": [_I, _I, _I, _I, _I, _F, _T, _T, _T, _P, _T, _P, _P, _F, _I, _P],
     "ea_softmax_sample": [_I, _I, _I, _I, _I, _F, _T, _T, _P, _P, _P],
     "ea_softmax_attn_bwd": [_I, _I, _I, _I, _I, _F, _T, _T, _T, _P, _T, _T, _P, _P, _T, _T, _T, _P, _F, _I, _P],
@@ -315,6 +317,7 @@ def lib():
         cdll.ea_vocab_score_ws.restype = ctypes.c_int64
         cdll.ea_vocab_score_rows_ws.restype = ctypes.c_int64
         cdll.ea_adaptive_score_ws.restype = ctypes.c_int64
+        cdll.ea_adaptive_pick_ws.restype = ctypes.c_int64
         cdll.ea_version.restype = ctypes.c_char_p
         cdll.ea_abi_version.restype = ctypes.c_int32
         if cdll.ea_abi_version() != ABI_VERSION:

@@ -1360,6 +1360,69 @@ int ea_adaptive_score(int32_t M, int32_t C, int32_t n_tails, const int64_t* cuto
                       const void* const* proj, const void* const* tables, void* ws, int64_t ws_bytes, float* logp,
                       int64_t* token_head, void* stream);
 
+/* ABI 34, THE GREEDY PICK FROM THE ADAPTIVE HEAD (ea_harness DecoderStack.init_adaptive_decoding, next_tokens,
+ * token_logprobs, score, generate on such a state; ea_adaptive_pick.hip): fairseq's get_log_prob(x, None) followed by an
+ * argmax, for the 1 <= M <= 64 rows of a decoding step, from the held tables of ABI 33 and without a [M, V] tensor.
+ * cutoffs, dims, proj, tables: HOST arrays as in ea_adaptive_score; x [M, ldx] of x_dtype = EA_F32 | w_dtype; targets [M]
+ * int64 on the device, or NULL; token [M] int64, logp [M] fp32.  For row m, every operation in fp32:
+ *   a[v], v < c0 + n         the head's logits, x against head (ea_ceva_sdecode_vocab_logprob's bits)
+ *   h_i = round_w(x proj_i^T) ea_ceva_sdecode_linear's bits (bias NULL, y_dtype = w_dtype)
+ *   b_i[u], u < V_i          tail i's logits, h_i against tables[i]
+ *   lse_h over ALL c0 + n head columns, lse_i over tail i;  lse by ABI 28's cases on the maximum: NaN -> NaN; +inf -> +inf;
+ *                            -inf -> -inf; else max + logf(S), a partial whose maximum is -inf skipped, never multiplied
+ *   s(v) = a[v] - lse_h for a word v < c0;  s(c_i + u) = (a[c0 + i] - lse_h) + (b_i[u] - lse_i): those operations, that order
+ *   token[m] = the index of the largest s: per band the candidate is the largest RAW logit under the pick's total order
+ *              (the larger value, of equals the lower index, NaN above every number); the n + 1 candidates' scores are
+ *              compared under the same order on (s, vocabulary index): equal scores go to the lower token.  Always in [0, V).
+ *   logp[m]  = s(targets[m]) with targets (one outside [0, V): NaN), else s(token[m]).
+ * A row with non-finite logits follows the cases per band: its logp may be NaN; no other row's bits change.
+ * Launches: 4 + n_tails with joined projections (3.), n_tails - 1 more with separate ones, and one more per tail wider than
+ * EA_ADAPTIVE_PICK_MAX_K when targets are given:
+ *   1. the head's words: ea_ceva_sdecode_vocab_logprob's first launch on head[0 .. c0): per 16-column tile (maximum, index,
+ *      sum of exponentials), and the target's logit;
+ *   2. the head's classes: the same kernel on the n rows at head + c0 C, the fp32 logits stored;
+ *   3. the projections: ea_ceva_sdecode_linear's kernel into h [M][D], D = sum d_i, h_i in columns off_i = d_0 + .. + d_{i-1};
+ *      ONE launch where proj[i + 1] == proj[i] + d_i C elements for every i (one concatenated copy), else one per tail;
+ *   4. per tail: d_i <= EA_ADAPTIVE_PICK_MAX_K: the column-split kernel.  A workgroup of 8 waves owns EA_ADAPTIVE_PICK_SPAN
+ *      columns, a wave EA_ADAPTIVE_PICK_SPAN / 128 whole 16-column tiles; a logit is ONE v_mfma_f32_16x16x32 accumulator
+ *      chained over the d_i / 32 k-steps in ascending order -- this kernel's own summation order, NOT
+ *      ea_ceva_sdecode_linear's.  Per row and wave the vocab epilogue's partial over the wave's columns: a lane folds its
+ *      column of the wave's tiles in tile order, the 16 lanes of a row reduce once (the candidate; then the sum of
+ *      expf(logit - its value), a lane's terms in tile order, the xor butterfly 8, 4, 2, 1); the workgroup merges its waves
+ *      in wave order (the better candidate; sum = s_a expf(m_a - m) + s_b expf(m_b - m), a side whose maximum is -inf
+ *      skipped): one partial per row and span.  d_i > EA_ADAPTIVE_PICK_MAX_K: launch 1's kernel on h_i
+ *      (K split over the waves; one partial per 16 columns), behind a launch that writes targets - c_i where targets are given;
+ *   5. the pick, one workgroup of 256 threads per row: per band the best partial (thread j its partials j, j + 256, .. in
+ *      order, six xor exchanges per wave, the 4 waves in wave order), then S = sum_j s_j expf(m_j - top) the same way, added
+ *      in wave order; the head's top is the larger of the words' and the classes' maximum and its S takes the class tile's
+ *      partial last; then the scores, token and logp.  token may be a captured step's static input.
+ * Ordinary stores only, no atomics, no workgroup waits for another: bitwise reproducible; a row's results depend on that row
+ * alone (not on M, nor on the rows beside it).
+ * ws, r16 rounding up to a multiple of 16, the parts in this order from byte 0; after a call it holds
+ *   cls fp32 [M][n]  r16(4 M n): a[c0 + i] | h w_dtype [M][D]  r16(2 M D) |
+ *   for b = 0 .. n (band 0: the head's words; band i + 1: tail i):  best (fp32 value, int32 index IN the band) [M]  r16(8 M) |
+ *   lse fp32 [M]  r16(4 M) (band 0: lse_h) | tlogit fp32 [M]  r16(4 M) (written only where the row's target lies in the band) |
+ *   for each tail with d_i > EA_ADAPTIVE_PICK_MAX_K: int64 [M]  r16(8 M) |
+ *   the class tile's partial: r16(8 M), r16(4 M) |
+ *   for b = 0 .. n the passes' partials: (value, index) [M][P_b]  r16(8 M P_b), sums fp32 [M][P_b]  r16(4 M P_b);
+ *   P_0 = ceil(c0 / 16); P_{i+1} = ceil(V_i / EA_ADAPTIVE_PICK_SPAN) for d_i <= EA_ADAPTIVE_PICK_MAX_K, else ceil(V_i / 16)
+ * ea_adaptive_pick_ws(M, n_tails, cutoffs, dims) is their sum (it grows with M); < 0 for M < 1, M > 64, n_tails outside
+ * 1 .. EA_ADAPTIVE_MAX_TAILS, cutoffs not increasing, c0 < 1, d_i < 1, V > 2^31 - 1 - 2 EA_ADAPTIVE_PICK_SPAN.
+ * EA_E_BADARG: a NULL array or operand, misaligned operands (x, head, proj[i], tables[i], ws: 16 bytes; targets, token: 8;
+ * logp: 4), cutoffs as above, w_dtype not 16-bit, x_dtype neither EA_F32 nor w_dtype, M < 1, C < 1, ldx < C or a row stride of
+ * x that is no multiple of 16 bytes, d_i < 1, ws_bytes below the query's answer.  EA_E_UNSUPPORTED: M > 64, n_tails >
+ * EA_ADAPTIVE_MAX_TAILS, C % 32 != 0, d_i % 32 != 0, a geometry the query refuses.  Bad arguments are decided before the
+ * geometry, everything before any launch. */
+#ifndef EA_ADAPTIVE_PICK_SPAN                 /* (a build may try another multiple of 128) */
+#define EA_ADAPTIVE_PICK_SPAN 512
+#endif
+#define EA_ADAPTIVE_PICK_MAX_K 256
+int64_t ea_adaptive_pick_ws(int32_t M, int32_t n_tails, const int64_t* cutoffs, const int32_t* dims);
+int ea_adaptive_pick(int32_t M, int32_t C, int32_t n_tails, const int64_t* cutoffs, const int32_t* dims, const void* x,
+                     int32_t x_dtype, int64_t ldx, const int64_t* targets, const void* head, int32_t w_dtype,
+                     const void* const* proj, const void* const* tables, void* ws, int64_t ws_bytes, int64_t* token,
+                     float* logp, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
