@@ -13,7 +13,11 @@ as WHOLE models (eager, autocast, DistributedDataParallel over RCCL) on syntheti
   sequence.DecoderStack -- the decoder-only LM of the wikitext-103 recipe around CausalEVAttention
                            (fairseq/modules/transformer_layer.py:236-308 without encoder attention), with
                            incremental decoding on the attention's static / rolling states: init_decoding,
-                           decode, generate
+                           decode, generate, beam_search, score; every decoding mode is its argument checks
+                           around a pick of token_pick
+  token_pick            -- what the decoding modes share: DecodingState and what is attached to it (Sampler,
+                           Scorer, Beam, AdaptivePick, the held vocabulary pair) with one lifecycle, the operand
+                           helpers of the vocabulary entries, and one pick per launch behind one selector
   trainer               -- one synthetic training step (forward, loss, backward, optimizer) eagerly or
                            captured in a hipGraph, single process or one process per GPU
 

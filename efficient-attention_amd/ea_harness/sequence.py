@@ -16,7 +16,13 @@ distribution from the same pass over the table (ea_ceva_sdecode_vocab_logprob, e
 `init_beam_search` / `beam_step` / `beam_search` are a beam search whose step -- candidates, merge, finished hypotheses and the
 parent index of the state reorder -- runs on the device (ea_ceva_sdecode_vocab_beam).  On an adaptive stack
 `init_adaptive_decoding` makes a state pick greedily, with log-probabilities, from the held adaptive tables
-(ea_adaptive_pick)."""
+(ea_adaptive_pick).
+
+What the modes share lives in token_pick.py: the DecodingState and what the `init_*` methods attach to it, the operand
+helpers, and one pick per launch.  Every public method above is its argument checks and that pick's `run`; `generate` and
+`beam_search` are one prefill (`_prefill`) and one warm-up / capture / replay loop (`_run_steps`) around the pick
+`select_pick` returns for the state, and the four lifecycle methods (`refresh_decoding_weights`, `reorder_decoding_state`,
+`reset_decoding_rows`, `decoding_state_nbytes`) loop over `state.attachments()`."""
 import argparse
 import contextlib
 import functools
@@ -28,6 +34,10 @@ import torch.nn as nn
 import torch.nn.functional as F
 
 from efficient_attention import AttentionFactory, CausalEVAttention
+
+from . import token_pick as tp
+from .token_pick import (AdaptivePick, AdaptiveTables, Beam, DecodingState, Sampler, Scorer,    # noqa: F401  (they lived here)
+                         MAX_ROWS as _FUSED_MAX_ROWS)
 
 
 class TimeFirstSelfAttention(nn.Module):
@@ -117,8 +127,7 @@ def wmt_en_de_encoder(attn_name, attn_args=None, vocab=32768, **kw):
 
 
 # ---- the decoder ----------------------------------------------------------------------------------------------------------------
-_FUSED = "ea_ceva_sdecode_linear_fused"
-_FUSED_MAX_ROWS = 64         # EA_CEVA_LINEAR_MAX_ROWS of include/ea_hip.h
+_FUSED = "ea_ceva_sdecode_linear_fused"                   # (at most _FUSED_MAX_ROWS rows: EA_CEVA_LINEAR_MAX_ROWS of include/ea_hip.h)
 
 
 def _fused_linear(x2, ln, weight, bias, act, res2, y2):
@@ -126,9 +135,7 @@ def _fused_linear(x2, ln, weight, bias, act, res2, y2):
     ln: an nn.LayerNorm over K or None; weight [N, K], bias [N] 16-bit; act 0 | 1 (ReLU); res2 [M, N] fp32 or the weight's
     type, or None, and may be y2 itself; y2 [M, N] fp32 or the weight's type -> y2."""
     from efficient_attention import _native as nv
-
-    def code(t):
-        return nv.EA_F32 if t.dtype == torch.float32 else nv.io_dtype(t)
+    code = tp.type_code
     gamma = beta = None
     eps = 0.0
     if ln is not None:                                  # (fp32 masters are read where they are)
@@ -210,139 +217,10 @@ class DecoderLayer(nn.Module):
         return x if self.normalize_before else self.final_layer_norm(x)
 
 
-class DecodingState:
-    """What `DecoderStack.init_decoding` returns: `incremental` (the incremental state every layer's attention keeps its
-    static or rolling state in, under its own key), `ffn` (per layer the held 16-bit (fc1.weight, fc1.bias, fc2.weight,
-    fc2.bias), or None without hold_weights), the arguments it was made with (`options`) and, made with hold_vocab, `vocab`
-    (the 16-bit [V, C] copy of embed_tokens.weight) and `vocab_ws` (the pick's workspace, bytes); both None otherwise.
-    The fourth argument is that pair, (vocab, vocab_ws), or None.
-    `sampler` is None until `DecoderStack.init_sampling` attaches a Sampler, `scorer` until `DecoderStack.init_logprobs`
-    attaches a Scorer, `beam` until `DecoderStack.init_beam_search` attaches a Beam, `adaptive` until
-    `DecoderStack.init_adaptive_decoding` attaches an AdaptivePick."""
-
-    sampler = None
-    scorer = None
-    beam = None
-    adaptive = None
-
-    def __init__(self, incremental, ffn, options, vocab=None):
-        self.incremental, self.ffn, self.options = incremental, ffn, options
-        self.vocab, self.vocab_ws = (None, None) if vocab is None else vocab
-
-    @property
-    def hold_weights(self):
-        return self.ffn is not None
-
-    @property
-    def hold_vocab(self):
-        return self.vocab is not None
-
-
-_VOCAB = "ea_ceva_sdecode_vocab_argmax"
-_SAMPLE = "ea_ceva_sdecode_vocab_sample"
-_SAMPLE_MAX_K = 64
-_LOGPROB = "ea_ceva_sdecode_vocab_logprob"
-_SAMPLE_LOGPROB = "ea_ceva_sdecode_vocab_sample_logprob"
+# ---- decoding states, what they carry and the picks made on them: token_pick.py -----------------------------------------------
+_SAMPLE_MAX_K, _BEAM_MAX_W = tp.SAMPLE_MAX_K, tp.BEAM_MAX_W
 _SCORE = "ea_vocab_score"
 _ADAPTIVE = "ea_adaptive_score"
-_ADAPTIVE_PICK = "ea_adaptive_pick"
-_BEAM = "ea_ceva_sdecode_vocab_beam"
-_BEAM_MAX_W = 32
-
-
-class Sampler:
-    """What `DecoderStack.init_sampling` attaches to a DecodingState: the fp32 `logits` buffer [batch_size, V] of the sampled
-    pick, the draw counters `ctr` (int64 [B]: draw n of a row is made at ctr = n) and the stream ids `sid` (int32 [B]), both
-    on the device, the host scalars `seed`, `top_k`, `top_p`, `temperature`, and `next_sid`, the first stream id no row of
-    this state has had."""
-
-    def __init__(self, logits, ctr, sid, seed, top_k, top_p, temperature):
-        self.logits, self.ctr, self.sid = logits, ctr, sid
-        self.seed, self.top_k, self.top_p, self.temperature = seed, top_k, top_p, temperature
-        self.next_sid = sid.numel()
-
-
-class Scorer:
-    """What `DecoderStack.init_logprobs` attaches to a DecodingState: `ws`, the tile sums and target logits of
-    ea_ceva_sdecode_vocab_logprob for 64 rows (bytes), and the static fp32 buffers `lse` and `logp` [batch_size] a captured
-    step writes its log-sum-exp and its token's log-probability into."""
-
-    def __init__(self, ws, lse, logp):
-        self.ws, self.lse, self.logp = ws, lse, logp
-
-
-class AdaptiveTables:
-    """What `DecoderStack.adaptive_tables(dtype)` returns, the held 16-bit operands of ea_adaptive_score (include/ea_hip.h, ABI
-    33): `cutoff` (the list, ending with V), `dims` (d_i per tail), `head` [c0 + n, C] (band 0's table with the class rows
-    behind it), `proj[i]` [d_i, C] (K-contiguous: a tied [C, d_i] projection is transposed as the copy is taken) and
-    `tables[i]` [V_i, d_i].  The projections are the row blocks of ONE [sum d_i, C] buffer (`proj_all`), so that
-    ea_adaptive_pick forms every h_i in one launch.  `refresh()` re-reads the parameters in place (rounded to nearest even;
-    every data_ptr() stays)."""
-
-    def __init__(self, softmax, dtype, device):
-        if dtype not in (torch.bfloat16, torch.float16):
-            raise ValueError("adaptive_tables holds 16-bit operands (bfloat16 or float16), got %s" % dtype)
-        self.softmax, self.cutoff, self.dims = softmax, list(softmax.cutoff), softmax.band_dims()
-        n, C = len(self.dims), softmax.input_dim
-
-        def buf(*shape):
-            return torch.empty(shape, dtype=dtype, device=device)
-        self.head = buf(self.cutoff[0] + n, C)
-        self.proj_all = buf(sum(self.dims), C)
-        self.proj = list(self.proj_all.split(self.dims, 0))
-        self.tables = [buf(self.cutoff[i + 1] - self.cutoff[i], d) for i, d in enumerate(self.dims)]
-        self.refresh()
-
-    @property
-    def dtype(self):
-        return self.head.dtype
-
-    @property
-    def device(self):
-        return self.head.device
-
-    def refresh(self):
-        sm, c0 = self.softmax, self.cutoff[0]
-        with torch.no_grad():
-            full = sm.head_table()
-            self.head[:c0].copy_(full[:c0])
-            self.head[c0:].copy_(full[c0:])
-            for i in range(len(self.dims)):
-                self.proj[i].copy_(sm.tail_projection(i))
-                self.tables[i].copy_(sm.tail_table(i))
-        return self
-
-    def nbytes(self):
-        return sum(t.numel() * t.element_size() for t in [self.head] + self.proj + self.tables)
-
-
-class AdaptivePick:
-    """What `DecoderStack.init_adaptive_decoding` attaches to a DecodingState: `tables` (an AdaptiveTables in the state's
-    dtype), `ws` (the workspace of ea_adaptive_pick for 64 rows, bytes) and the static fp32 buffer `logp` [batch_size] a
-    captured step writes its token's log-probability into."""
-
-    def __init__(self, tables, ws, logp):
-        self.tables, self.ws, self.logp = tables, ws, logp
-
-
-class Beam:
-    """What `DecoderStack.init_beam_search` attaches to a DecodingState: the host scalars `beam_size` (W), `eos_idx`,
-    `max_new`, `len_penalty` and the static buffers of ea_ceva_sdecode_vocab_beam (include/ea_hip.h, ABI 32) for M = the
-    state's batch size = S W rows: `logits` fp32 [M, V], `ws` (the entry's workspace, bytes), `score` fp32 [M], `t`, `nfin`,
-    `done` int32 [S], `parent` int64 [M], `hist_tok`, `hist_par` int32 [max_new, M], `fin_score` fp32 [S, W], `fin_len`,
-    `fin_beam` int32 [S, W].  `replays`: how many steps behind the first pick the last `beam_search` on it ran."""
-
-    def __init__(self, beam_size, eos_idx, max_new, len_penalty, logits, ws, score, t, nfin, done, parent, hist_tok, hist_par,
-                 fin_score, fin_len, fin_beam):
-        self.beam_size, self.eos_idx, self.max_new, self.len_penalty = beam_size, eos_idx, max_new, len_penalty
-        self.logits, self.ws, self.score, self.t, self.nfin, self.done, self.parent = logits, ws, score, t, nfin, done, parent
-        self.hist_tok, self.hist_par = hist_tok, hist_par
-        self.fin_score, self.fin_len, self.fin_beam = fin_score, fin_len, fin_beam
-        self.replays = 0
-
-    def buffers(self):
-        return (self.logits, self.ws, self.score, self.t, self.nfin, self.done, self.parent, self.hist_tok, self.hist_par,
-                self.fin_score, self.fin_len, self.fin_beam)
 
 
 def _hold_vocab_option(init):
@@ -493,8 +371,7 @@ class DecoderStack(nn.Module):
 
     def _load_held_vocab(self, state):
         if state.vocab is not None:
-            with torch.no_grad():
-                state.vocab.copy_(self.embed_tokens.weight)     # (rounded to nearest even, in place: data_ptr() stays)
+            tp.HeldVocab(state).refresh(self)
 
     def refresh_decoding_weights(self, state):
         """Re-read the parameters into what the state holds of them, in place and by device ops only: every layer's attention
@@ -503,32 +380,22 @@ class DecoderStack(nn.Module):
         for layer in self.layers:
             layer.self_attn.refresh_decoding_weights(state.incremental)
         self._load_held_ffn(state)
-        self._load_held_vocab(state)
-        if state.adaptive is not None:
-            state.adaptive.tables.refresh()
+        for held in state.attachments():
+            held.refresh(self)
         return state
 
     def reorder_decoding_state(self, state, new_order):
         for layer in self.layers:
             layer.self_attn.reorder_incremental_state(state.incremental, new_order)
-        sm = state.sampler
-        if sm is not None:                              # a row takes its stream along: counters and ids, in place
-            order = new_order.to(device=sm.ctr.device, dtype=torch.long)
-            sm.ctr.copy_(sm.ctr.index_select(0, order))
-            sm.sid.copy_(sm.sid.index_select(0, order))
+        for held in state.attachments():
+            held.reorder(new_order)
         return state
 
     def reset_decoding_rows(self, state, rows):
         for layer in self.layers:
             layer.self_attn.reset_decoding_rows(state.incremental, rows)
-        sm = state.sampler
-        if sm is not None:                              # a new sequence: draw 0 of a stream no row has had
-            at = torch.as_tensor(rows, device=sm.ctr.device).reshape(-1).long()
-            if at.numel():                              # (how many is known on the host: no read-back)
-                fresh = torch.arange(sm.next_sid, sm.next_sid + at.numel(), dtype=torch.int32, device=sm.sid.device)
-                sm.next_sid += at.numel()
-                sm.ctr.index_fill_(0, at, 0)
-                sm.sid.index_copy_(0, at, fresh)
+        for held in state.attachments():
+            held.reset_rows(rows)
         return state
 
     def decoding_state_nbytes(self, state):
@@ -540,17 +407,7 @@ class DecoderStack(nn.Module):
         (ea_adaptive_pick_ws for 64 rows) and 4 B (logp)."""
         n = sum(layer.self_attn.decoding_state_nbytes(state.incremental) for layer in self.layers)
         n += sum(t.numel() * t.element_size() for held in (state.ffn or ()) for t in held)
-        sm = state.sampler
-        extra = () if sm is None else (sm.logits, sm.ctr, sm.sid)
-        sc = state.scorer
-        if sc is not None:
-            extra += (sc.ws, sc.lse, sc.logp)
-        if state.beam is not None:
-            extra += state.beam.buffers()
-        if state.adaptive is not None:
-            n += state.adaptive.tables.nbytes()
-            extra += (state.adaptive.ws, state.adaptive.logp)
-        return n + sum(t.numel() * t.element_size() for t in (state.vocab, state.vocab_ws) + extra if t is not None)
+        return n + sum(t.numel() * t.element_size() for held in state.attachments() for t in held.tensors())
 
     def decoding_overflowed(self, state):
         """True once a step of any layer would have passed the state's capacity.  Reads device flags back."""
@@ -580,6 +437,59 @@ class DecoderStack(nn.Module):
             x = layer._feed_forward(x, None if state.ffn is None else state.ffn[i])
         return x if self.layer_norm is None else self.layer_norm(x)
 
+    # ---- the decoding loop of `generate` and `beam_search` ------------------------------------------------------------------
+    def _decoding_context(self):
+        """-> (the context a decoding call runs its steps in, the dtype of a state it makes for itself): under autocast that
+        autocast again without its weight-cast cache (a capture may not use it) and its dtype, else the embedding's."""
+        if torch.is_autocast_enabled():
+            dtype = torch.get_autocast_dtype("cuda")
+            return torch.autocast("cuda", dtype=dtype, cache_enabled=False), dtype
+        return contextlib.nullcontext(), self._embed_dtype()
+
+    def _prefill(self, prompt, state):
+        """The prompt [B, P] fed in one `decode` -> [1, B, C], the row of each sequence's last token (a per-sequence state:
+        the prompt may be ragged and right-padded with `pad_idx`)."""
+        B, P = prompt.shape
+        if not state.options["per_sequence"]:
+            return self.decode(prompt.t(), state, None)[P - 1:P]
+        mask = prompt.eq(self.pad_idx)
+        x = self.decode(prompt.t(), state, mask)                             # [P, B, C]
+        n_b = P - mask.ne(0).to(torch.int32).cumsum(1).ne(0).sum(1)
+        return x[(n_b - 1).clamp_(min=0), torch.arange(B, device=x.device)].unsqueeze(0)
+
+    def _run_steps(self, step, state, n, graph, tok_in, scratch, pick=None, each=None):
+        """Steps 1 .. n - 1 behind a first pick: step(st) is one step on the state `st`, reading and writing the static input
+        `tok_in`, -> its rows.  graph=True: warmed up on a side stream on `scratch()`, a state of its own, with `tok_in` and
+        what `pick` saved restored behind it; then captured on `state` once and replayed.  each(i, rows), behind step i (the
+        rows are the capture's static ones), ends the loop by returning True.  An overflow flagged by any layer raises."""
+        g = y = None
+        if graph and n > 1:
+            st = scratch()
+            first = tok_in.clone()
+            saved = None if pick is None else pick.save()
+            side = torch.cuda.Stream()
+            side.wait_stream(torch.cuda.current_stream())
+            with torch.cuda.stream(side):
+                step(st)
+            torch.cuda.current_stream().wait_stream(side)
+            tok_in.copy_(first)
+            if saved is not None:                                            # (the warm-up drew once)
+                pick.restore(saved)
+            del st
+            g = torch.cuda.CUDAGraph()
+            with torch.cuda.graph(g):
+                y = step(state)
+        for i in range(1, n):
+            if g is None:
+                y = step(state)
+            else:
+                g.replay()
+            if each is not None and each(i, y):
+                break
+        if self.decoding_overflowed(state):
+            raise RuntimeError("the decoding state overflowed: a step passed its %d tokens (init_decoding(max_tokens=...))"
+                               % state.options["max_tokens"])
+
     def next_tokens(self, rows, state, out=None, return_logits=False):
         """The greedy pick on the table the state holds: rows [T, B, C] (final-layer rows: what `decode` returns) -> int64
         [T, B], token[t, b] = argmax_v sum_c round(rows[t, b, c]) vocab[v, c], on ea_ceva_sdecode_vocab_argmax: the table is
@@ -596,35 +506,11 @@ class DecoderStack(nn.Module):
             if return_logits:
                 raise ValueError("next_tokens(return_logits=True) on an adaptive pick: no [T, B, V] tensor exists there "
                                  "(`logits` is the slow route)")
-            return self._adaptive_pick(rows, state, None, out, None)[0]
+            return tp.AdaptiveGreedy(self, state).run(rows, None, out, None)[0]
         if state.vocab is None:
             raise RuntimeError("next_tokens needs a decoding state that holds the vocabulary table: "
                                "init_decoding(..., hold_vocab=True)")
-        from efficient_attention import _native as nv
-        table, ws = state.vocab, state.vocab_ws
-        T, B, C = rows.shape
-        V = table.shape[0]
-        if C != table.shape[1]:
-            raise ValueError("rows of %d channels against a table of %d" % (C, table.shape[1]))
-        x2 = rows.detach()
-        if x2.dtype not in (torch.float32, table.dtype):
-            x2 = x2.float()
-        x2 = x2.contiguous().view(T * B, C)
-        if x2.data_ptr() % 16:
-            x2 = x2.clone()
-        if out is None:
-            out = torch.empty((T, B), dtype=torch.long, device=x2.device)
-        elif out.dtype != torch.long or tuple(out.shape) != (T, B) or not out.is_contiguous() or out.device != x2.device:
-            raise ValueError("out must be a contiguous int64 [%d, %d] tensor on the rows' device" % (T, B))
-        tok = out.view(T * B)
-        logits = torch.empty((T * B, V), dtype=torch.float32, device=x2.device) if return_logits else None
-        code = nv.EA_F32 if x2.dtype == torch.float32 else nv.io_dtype(x2)
-        for a in range(0, T * B, _FUSED_MAX_ROWS):
-            M = min(_FUSED_MAX_ROWS, T * B - a)
-            nv.call(_VOCAB, M, C, V, nv.ptr(x2[a:a + M]), code, C, nv.ptr(table), nv.io_dtype(table),
-                    None if logits is None else nv.ptr(logits[a:a + M]), nv.EA_F32, V, nv.ptr(ws), ws.numel(),
-                    nv.ptr(tok[a:a + M]), None, nv.stream())
-        return (out, logits.view(T, B, V)) if return_logits else out
+        return tp.HeldGreedy(self, state).run(rows, out, return_logits)
 
     def init_sampling(self, state, seed, top_k, top_p=1.0, temperature=1.0):
         """Make `state` (made with hold_vocab=True) sample its tokens: `sample_tokens` draws on it, and `generate` takes both
@@ -663,38 +549,9 @@ class DecoderStack(nn.Module):
         return_details=True: -> (tokens, sel_idx int32 [B, top_k], sel_val fp32 [B, top_k], kept int32 [B]): the selection in
         order (entries from min(top_k, V) on are not written; log-probabilities follow from sel_val), and how many of it the
         nucleus kept (0: a row whose best logit is NaN or infinite, which gets the greedy pick).  Device launches only."""
-        sm = state.sampler
-        if sm is None:
+        if state.sampler is None:
             raise RuntimeError("sample_tokens needs a decoding state with a sampler: init_sampling(state, seed, top_k, ...)")
-        from efficient_attention import _native as nv
-        table, ws = state.vocab, state.vocab_ws
-        T, B, C = rows.shape
-        V = table.shape[0]
-        if T != 1 or B > min(_FUSED_MAX_ROWS, sm.ctr.numel()):
-            raise ValueError("sample_tokens takes the rows of one single-token step, [1, B <= %d, C]; got %s"
-                             % (min(_FUSED_MAX_ROWS, sm.ctr.numel()), tuple(rows.shape)))
-        if C != table.shape[1]:
-            raise ValueError("rows of %d channels against a table of %d" % (C, table.shape[1]))
-        x2 = rows.detach()
-        if x2.dtype not in (torch.float32, table.dtype):
-            x2 = x2.float()
-        x2 = x2.contiguous().view(B, C)
-        if x2.data_ptr() % 16:
-            x2 = x2.clone()
-        if out is None:
-            out = torch.empty((1, B), dtype=torch.long, device=x2.device)
-        elif out.dtype != torch.long or tuple(out.shape) != (1, B) or not out.is_contiguous() or out.device != x2.device:
-            raise ValueError("out must be a contiguous int64 [1, %d] tensor on the rows' device" % B)
-        details = None
-        if return_details:
-            details = (torch.empty((B, sm.top_k), dtype=torch.int32, device=x2.device),
-                       torch.empty((B, sm.top_k), dtype=torch.float32, device=x2.device),
-                       torch.empty((B,), dtype=torch.int32, device=x2.device))
-        code = nv.EA_F32 if x2.dtype == torch.float32 else nv.io_dtype(x2)
-        nv.call(_SAMPLE, B, C, V, nv.ptr(x2), code, C, nv.ptr(table), nv.io_dtype(table), nv.ptr(sm.logits), V, nv.ptr(ws),
-                ws.numel(), sm.top_k, sm.top_p, sm.temperature, sm.seed, nv.ptr(sm.ctr), nv.ptr(sm.sid), nv.ptr(out),
-                *((None, None, None) if details is None else [nv.ptr(t) for t in details]), nv.stream())
-        return (out,) + details if return_details else out
+        return tp.HeldSampled(self, state).run(rows, out, return_details)
 
     def init_logprobs(self, state):
         """Make `state` (made with hold_vocab=True) report log-probabilities: `token_logprobs`, `sample_tokens_logprobs`,
@@ -715,60 +572,6 @@ class DecoderStack(nn.Module):
                               torch.empty(B, dtype=torch.float32, device=device))
         return state
 
-    def _vocab_rows(self, rows, state, single_step):
-        """rows [T, B, C] -> the [T B, C] operand of the vocabulary kernels (fp32 or the table's type, 16-byte aligned)."""
-        table = state.vocab
-        T, B, C = rows.shape
-        if single_step and (T != 1 or B > min(_FUSED_MAX_ROWS, state.sampler.ctr.numel())):
-            raise ValueError("a sampled pick takes the rows of one single-token step, [1, B <= %d, C]; got %s"
-                             % (min(_FUSED_MAX_ROWS, state.sampler.ctr.numel()), tuple(rows.shape)))
-        if C != table.shape[1]:
-            raise ValueError("rows of %d channels against a table of %d" % (C, table.shape[1]))
-        x2 = rows.detach()
-        if x2.dtype not in (torch.float32, table.dtype):
-            x2 = x2.float()
-        x2 = x2.contiguous().view(T * B, C)
-        if x2.data_ptr() % 16:
-            x2 = x2.clone()
-        return x2
-
-    @staticmethod
-    def _vocab_out(out, shape, dtype, device, what):
-        if out is None:
-            return torch.empty(shape, dtype=dtype, device=device)
-        if out.dtype != dtype or tuple(out.shape) != tuple(shape) or not out.is_contiguous() or out.device != device:
-            raise ValueError("%s must be a contiguous %s %s tensor on the rows' device"
-                             % (what, str(dtype).replace("torch.", ""), list(shape)))
-        return out
-
-    def _logprob_pick(self, rows, state, targets, out, logp, lse):
-        """`token_logprobs` with the places of logp and lse [T, B] given (None: allocated)."""
-        if state.vocab is None or state.scorer is None:
-            raise RuntimeError("token_logprobs needs a decoding state with a scorer: init_logprobs(state), on a state made "
-                               "with init_decoding(..., hold_vocab=True)")
-        from efficient_attention import _native as nv
-        table, ws, lws = state.vocab, state.vocab_ws, state.scorer.ws
-        T, B, C = rows.shape
-        V = table.shape[0]
-        x2 = self._vocab_rows(rows, state, False)
-        dev = x2.device
-        out = self._vocab_out(out, (T, B), torch.long, dev, "out")
-        logp = self._vocab_out(logp, (T, B), torch.float32, dev, "logp")
-        lse = self._vocab_out(lse, (T, B), torch.float32, dev, "lse")
-        if targets is not None:
-            if targets.dtype != torch.long or tuple(targets.shape) != (T, B) or targets.device != dev:
-                raise ValueError("targets must be an int64 [%d, %d] tensor on the rows' device" % (T, B))
-            targets = targets.contiguous().view(T * B)
-        tok, lp, ls = out.view(T * B), logp.view(T * B), lse.view(T * B)
-        code = nv.EA_F32 if x2.dtype == torch.float32 else nv.io_dtype(x2)
-        for a in range(0, T * B, _FUSED_MAX_ROWS):
-            M = min(_FUSED_MAX_ROWS, T * B - a)
-            nv.call(_LOGPROB, M, C, V, nv.ptr(x2[a:a + M]), code, C, nv.ptr(table), nv.io_dtype(table), None, nv.EA_F32, V,
-                    nv.ptr(ws), ws.numel(), nv.ptr(tok[a:a + M]), None, nv.ptr(lws), lws.numel(),
-                    None if targets is None else nv.ptr(targets[a:a + M]), nv.ptr(ls[a:a + M]), nv.ptr(lp[a:a + M]),
-                    nv.stream())
-        return out, logp, lse
-
     def token_logprobs(self, rows, state, targets=None, out=None, return_lse=False):
         """The greedy pick of `next_tokens` and a log-probability per row, on a state with a scorer (`init_logprobs`): rows
         [T, B, C] -> (tokens int64 [T, B], logp fp32 [T, B]); return_lse=True: and lse fp32 [T, B], the log-sum-exp of the row's
@@ -783,8 +586,11 @@ class DecoderStack(nn.Module):
             if return_lse:
                 raise ValueError("token_logprobs(return_lse=True) on an adaptive pick: an adaptive softmax has no single "
                                  "log-sum-exp to return")
-            return self._adaptive_pick(rows, state, targets, out, None)
-        tokens, logp, lse = self._logprob_pick(rows, state, targets, out, None, None)
+            return tp.AdaptiveGreedy(self, state).run(rows, targets, out, None)
+        if state.vocab is None or state.scorer is None:
+            raise RuntimeError("token_logprobs needs a decoding state with a scorer: init_logprobs(state), on a state made "
+                               "with init_decoding(..., hold_vocab=True)")
+        tokens, logp, lse = tp.HeldGreedyLogprob(self, state).run(rows, targets, out, None, None)
         return (tokens, logp, lse) if return_lse else (tokens, logp)
 
     # ---- the greedy pick from the adaptive head (ea_adaptive_pick, C ABI 34) ---------------------------------------------------
@@ -808,70 +614,22 @@ class DecoderStack(nn.Module):
         elif not isinstance(tables, AdaptiveTables) or tables.dtype != dtype:
             raise ValueError("tables must be an AdaptiveTables in the state's dtype (%s)" % str(dtype).replace("torch.", ""))
         from efficient_attention import _native as nv
-        import ctypes
-        nbytes = nv.lib().ea_adaptive_pick_ws(_FUSED_MAX_ROWS, len(tables.dims), nv.host_array(ctypes.c_int64, tables.cutoff),
-                                              nv.host_array(ctypes.c_int32, tables.dims))
+        nbytes = nv.lib().ea_adaptive_pick_ws(_FUSED_MAX_ROWS, len(tables.dims), *tables.host_arrays()[:2])
         if nbytes < 0:
             raise ValueError("cutoffs %s at widths %s are outside ea_adaptive_pick's envelope" % (tables.cutoff, tables.dims))
         state.adaptive = AdaptivePick(tables, torch.empty(nbytes, dtype=torch.uint8, device=tables.device),
                                       torch.empty(state.options["batch_size"], dtype=torch.float32, device=tables.device))
         return state
 
-    def _adaptive_pick(self, rows, state, targets, out, logp):
-        """rows [T, B, C] -> (tokens int64 [T, B], logp fp32 [T, B]) on ea_adaptive_pick, in pieces of 64 rows; out, logp:
-        the places of the two (None: allocated)."""
-        from efficient_attention import _native as nv
-        import ctypes
-        ad = state.adaptive
-        tb = ad.tables
-        x2 = self._score_rows(rows, tb.head)
-        T, B, C = rows.shape
-        dev, n = x2.device, len(tb.dims)
-        out = self._vocab_out(out, (T, B), torch.long, dev, "out")
-        logp = self._vocab_out(logp, (T, B), torch.float32, dev, "logp")
-        if targets is not None:
-            if targets.dtype != torch.long or tuple(targets.shape) != (T, B) or targets.device != dev:
-                raise ValueError("targets must be an int64 [%d, %d] tensor on the rows' device" % (T, B))
-            targets = targets.contiguous().view(T * B)
-        nv.require_cuda(x2, "rows")
-        cut, dims = nv.host_array(ctypes.c_int64, tb.cutoff), nv.host_array(ctypes.c_int32, tb.dims)
-        proj = nv.host_array(ctypes.c_void_p, [t.data_ptr() for t in tb.proj])
-        tabs = nv.host_array(ctypes.c_void_p, [t.data_ptr() for t in tb.tables])
-        tok, lp = out.view(T * B), logp.view(T * B)
-        code = nv.EA_F32 if x2.dtype == torch.float32 else nv.io_dtype(x2)
-        for a in range(0, T * B, _FUSED_MAX_ROWS):
-            M = min(_FUSED_MAX_ROWS, T * B - a)
-            nv.call(_ADAPTIVE_PICK, M, C, n, cut, dims, nv.ptr(x2[a:a + M]), code, C,
-                    None if targets is None else nv.ptr(targets[a:a + M]), nv.ptr(tb.head), nv.io_dtype(tb.head), proj, tabs,
-                    nv.ptr(ad.ws), ad.ws.numel(), nv.ptr(tok[a:a + M]), nv.ptr(lp[a:a + M]), nv.stream())
-        return out, logp
-
-    def _sample_logprob_pick(self, rows, state, out, logp, lse):
-        sm, sc = state.sampler, state.scorer
-        if sm is None or sc is None:
-            raise RuntimeError("sample_tokens_logprobs needs a decoding state with a sampler and a scorer: "
-                               "init_sampling(state, seed, top_k, ...) and init_logprobs(state)")
-        from efficient_attention import _native as nv
-        table, ws = state.vocab, state.vocab_ws
-        T, B, C = rows.shape
-        V = table.shape[0]
-        x2 = self._vocab_rows(rows, state, True)
-        dev = x2.device
-        out = self._vocab_out(out, (1, B), torch.long, dev, "out")
-        logp = self._vocab_out(logp, (1, B), torch.float32, dev, "logp")
-        lse = self._vocab_out(lse, (1, B), torch.float32, dev, "lse")
-        code = nv.EA_F32 if x2.dtype == torch.float32 else nv.io_dtype(x2)
-        nv.call(_SAMPLE_LOGPROB, B, C, V, nv.ptr(x2), code, C, nv.ptr(table), nv.io_dtype(table), nv.ptr(sm.logits), V,
-                nv.ptr(ws), ws.numel(), sm.top_k, sm.top_p, sm.temperature, sm.seed, nv.ptr(sm.ctr), nv.ptr(sm.sid),
-                nv.ptr(out), None, None, None, nv.ptr(sc.ws), sc.ws.numel(), nv.ptr(lse), nv.ptr(logp), nv.stream())
-        return out, logp, lse
-
     def sample_tokens_logprobs(self, rows, state, out=None):
         """`sample_tokens` and the drawn tokens' log-probabilities, on a state with a sampler and a scorer: rows [1, B, C] ->
         (tokens int64 [1, B], logp fp32 [1, B]).  The tokens, and the counters behind them, are `sample_tokens`' at the same
         (seed, ctr, sid).  logp is the token's log-probability under the RAW distribution at temperature 1 -- not inside the
         top-k list or the nucleus, not at the sampler's temperature.  Device launches only."""
-        tokens, logp, _ = self._sample_logprob_pick(rows, state, out, None, None)
+        if state.sampler is None or state.scorer is None:
+            raise RuntimeError("sample_tokens_logprobs needs a decoding state with a sampler and a scorer: "
+                               "init_sampling(state, seed, top_k, ...) and init_logprobs(state)")
+        tokens, logp, _ = tp.HeldSampledLogprob(self, state).run(rows, out, None, None)
         return tokens, logp
 
     def score(self, tokens, state=None):
@@ -886,12 +644,9 @@ class DecoderStack(nn.Module):
         B, T = tokens.shape
         if T < 2:
             raise ValueError("score needs at least two tokens per row, got %d" % T)
-        amp = torch.is_autocast_enabled()
-        ctx = torch.autocast("cuda", dtype=torch.get_autocast_dtype("cuda"), cache_enabled=False) if amp \
-            else contextlib.nullcontext()
+        ctx, dtype = self._decoding_context()
         with torch.no_grad(), ctx:
             if state is None:
-                dtype = torch.get_autocast_dtype("cuda") if amp else self._embed_dtype()
                 if self.is_adaptive:
                     state = self.init_adaptive_decoding(self.init_decoding(B, T - 1, dtype, tokens.device))
                 else:
@@ -906,30 +661,6 @@ class DecoderStack(nn.Module):
             return logp.masked_fill_(targets.eq(self.pad_idx), 0.0).t().contiguous()
 
     # ---- corpus-scale scoring (ea_vocab_score, C ABI 30) --------------------------------------------------------------------
-    @staticmethod
-    def _score_rows(rows, table):
-        """rows [T, B, C] against table [V, C] -> the [T B, C] operand of ea_vocab_score (fp32 or the table's type, 16-byte
-        aligned); the argument errors of `rows_logprobs`."""
-        if not isinstance(table, torch.Tensor) or table.dim() != 2 or table.dtype not in (torch.bfloat16, torch.float16) \
-                or not table.is_contiguous() or table.data_ptr() % 16:
-            raise ValueError("table must be a contiguous, 16-byte aligned 16-bit [V, C] tensor (bfloat16 or float16); got %s"
-                             % (("%s %s" % (str(table.dtype).replace("torch.", ""), list(table.shape)))
-                                if isinstance(table, torch.Tensor) else type(table).__name__))
-        if rows.dim() != 3 or rows.shape[0] * rows.shape[1] < 1:
-            raise ValueError("rows must be a [T, B, C] tensor of at least one row; got %s" % (tuple(rows.shape),))
-        T, B, C = rows.shape
-        if C != table.shape[1]:
-            raise ValueError("rows of %d channels against a table of %d" % (C, table.shape[1]))
-        if rows.device != table.device:
-            raise ValueError("table must be on the rows' device (%s); it is on %s" % (rows.device, table.device))
-        x2 = rows.detach()
-        if x2.dtype not in (torch.float32, table.dtype):
-            x2 = x2.float()
-        x2 = x2.contiguous().view(T * B, C)
-        if x2.data_ptr() % 16:
-            x2 = x2.clone()
-        return x2
-
     def rows_logprobs(self, rows, table, targets=None, return_lse=False):
         """`token_logprobs` for ANY number of rows, on a table the caller holds: rows [T, B, C], table a contiguous 16-bit
         [V, C] tensor on the rows' device (`state.vocab` of a hold_vocab state serves) -> (tokens int64 [T, B], logp fp32
@@ -945,13 +676,10 @@ class DecoderStack(nn.Module):
         if isinstance(table, AdaptiveTables):
             return self._adaptive_rows_logprobs(rows, table, targets, return_lse)
         from efficient_attention import _native as nv
-        x2 = self._score_rows(rows, table)
+        x2 = tp.score_operand(table, rows)
         T, B, C = rows.shape
         V, dev = table.shape[0], x2.device
-        if targets is not None:
-            if targets.dtype != torch.long or tuple(targets.shape) != (T, B) or targets.device != dev:
-                raise ValueError("targets must be an int64 [%d, %d] tensor on the rows' device" % (T, B))
-            targets = targets.contiguous().view(T * B)
+        targets = tp.checked_targets(targets, T, B, dev)
         nv.require_cuda(x2, "rows")
         # (the entry's sizes are int32: a count of 2^31 or more would wrap on its way into the query)
         nbytes = nv.lib().ea_vocab_score_ws(T * B, V) if max(T * B, V, C) < 2 ** 31 else -1
@@ -961,8 +689,7 @@ class DecoderStack(nn.Module):
         out = torch.empty((T, B), dtype=torch.long, device=dev)
         logp = torch.empty((T, B), dtype=torch.float32, device=dev)
         lse = torch.empty((T, B), dtype=torch.float32, device=dev)
-        code = nv.EA_F32 if x2.dtype == torch.float32 else nv.io_dtype(x2)
-        nv.call(_SCORE, T * B, C, V, nv.ptr(x2), code, C, nv.ptr(table), nv.io_dtype(table), nv.ptr(targets), None, nv.EA_F32,
+        nv.call(_SCORE, T * B, C, V, nv.ptr(x2), tp.type_code(x2), C, nv.ptr(table), nv.io_dtype(table), nv.ptr(targets), None, nv.EA_F32,
                 V, nv.ptr(ws), ws.numel(), nv.ptr(out), None, nv.ptr(lse), nv.ptr(logp), nv.stream())
         return (out, logp, lse) if return_lse else (out, logp)
 
@@ -982,27 +709,20 @@ class DecoderStack(nn.Module):
         if return_lse:
             raise ValueError("rows_logprobs on adaptive tables has no single log-sum-exp to return")
         from efficient_attention import _native as nv
-        import ctypes
-        x2 = self._score_rows(rows, tables.head)
+        x2 = tp.score_operand(tables.head, rows)
         T, B, C = rows.shape
         dev, n = x2.device, len(tables.dims)
-        if targets.dtype != torch.long or tuple(targets.shape) != (T, B) or targets.device != dev:
-            raise ValueError("targets must be an int64 [%d, %d] tensor on the rows' device" % (T, B))
-        targets = targets.contiguous().view(T * B)
+        targets = tp.checked_targets(targets, T, B, dev)
         nv.require_cuda(x2, "rows")
-        cut = nv.host_array(ctypes.c_int64, tables.cutoff)
-        dims = nv.host_array(ctypes.c_int32, tables.dims)
+        cut, dims, proj, tabs = tables.host_arrays()
         nbytes = nv.lib().ea_adaptive_score_ws(T * B, n, cut, dims) if max(T * B, C) < 2 ** 31 else -1
         if nbytes < 0:
             raise ValueError("%d rows against cutoffs %s are outside ea_adaptive_score's envelope" % (T * B, tables.cutoff))
         ws = torch.empty(nbytes, dtype=torch.uint8, device=dev)
         head = torch.empty((T, B), dtype=torch.long, device=dev)
         logp = torch.empty((T, B), dtype=torch.float32, device=dev)
-        code = nv.EA_F32 if x2.dtype == torch.float32 else nv.io_dtype(x2)
-        nv.call(_ADAPTIVE, T * B, C, n, cut, dims, nv.ptr(x2), code, C, nv.ptr(targets), nv.ptr(tables.head),
-                nv.io_dtype(tables.head), nv.host_array(ctypes.c_void_p, [t.data_ptr() for t in tables.proj]),
-                nv.host_array(ctypes.c_void_p, [t.data_ptr() for t in tables.tables]), nv.ptr(ws), ws.numel(), nv.ptr(logp),
-                nv.ptr(head), nv.stream())
+        nv.call(_ADAPTIVE, T * B, C, n, cut, dims, nv.ptr(x2), tp.type_code(x2), C, nv.ptr(targets), nv.ptr(tables.head),
+                nv.io_dtype(tables.head), proj, tabs, nv.ptr(ws), ws.numel(), nv.ptr(logp), nv.ptr(head), nv.stream())
         return head, logp
 
     def evaluate(self, tokens, table=None, key_padding_mask=None, return_tokens=False):
@@ -1098,27 +818,11 @@ class DecoderStack(nn.Module):
         bm = state.beam
         if bm is None:
             raise RuntimeError("beam_step needs a decoding state with a beam search: init_beam_search(state, beam_size, ...)")
-        from efficient_attention import _native as nv
-        table = state.vocab
         T, M, C = rows.shape
-        V, W = table.shape[0], bm.beam_size
         if T != 1 or M != bm.score.numel():
             raise ValueError("beam_step takes the rows of one single-token step of the whole state, [1, %d, C]; got %s"
                              % (bm.score.numel(), tuple(rows.shape)))
-        x2 = self._vocab_rows(rows, state, False)
-        out = self._vocab_out(out, (1, M), torch.long, x2.device, "out")
-        details = None
-        if return_details:
-            details = (torch.empty((M, 2 * W), dtype=torch.int32, device=x2.device),
-                       torch.empty((M, 2 * W), dtype=torch.float32, device=x2.device),
-                       torch.empty((M,), dtype=torch.float32, device=x2.device))
-        code = nv.EA_F32 if x2.dtype == torch.float32 else nv.io_dtype(x2)
-        nv.call(_BEAM, M, C, V, nv.ptr(x2), code, C, nv.ptr(table), nv.io_dtype(table), nv.ptr(bm.logits), V, nv.ptr(bm.ws),
-                bm.ws.numel(), W, bm.eos_idx, bm.max_new, nv.ptr(bm.score), nv.ptr(bm.t), nv.ptr(bm.nfin), nv.ptr(bm.done),
-                nv.ptr(out), nv.ptr(bm.parent), nv.ptr(bm.hist_tok), nv.ptr(bm.hist_par), nv.ptr(bm.fin_score),
-                nv.ptr(bm.fin_len), nv.ptr(bm.fin_beam), *((None, None, None) if details is None else [nv.ptr(t) for t in details]),
-                None, nv.stream())
-        return (out, bm.parent) + details if return_details else (out, bm.parent)
+        return tp.BeamStep(self, state).run(rows, out, return_details)
 
     @staticmethod
     def _beam_hypotheses(bm):
@@ -1166,12 +870,9 @@ class DecoderStack(nn.Module):
         if poll < 1:
             raise ValueError("poll must be >= 1, got %d" % poll)
         M = S * W
-        amp = torch.is_autocast_enabled()
-        ctx = torch.autocast("cuda", dtype=torch.get_autocast_dtype("cuda"), cache_enabled=False) if amp \
-            else contextlib.nullcontext()
+        ctx, dtype = self._decoding_context()
         with torch.no_grad(), ctx:
             if state is None:
-                dtype = torch.get_autocast_dtype("cuda") if amp else self._embed_dtype()
                 state = self.init_decoding(M, P + max(max_new, 1), dtype, prompt.device, hold_vocab=True)
             if state.beam is None:
                 self.init_beam_search(state, W, eos_idx, max_new, len_penalty)
@@ -1182,48 +883,23 @@ class DecoderStack(nn.Module):
             if M != bm.score.numel():
                 raise ValueError("a prompt of %d sentences at beam_size %d on a state of %d rows" % (S, W, bm.score.numel()))
             prompt = prompt.repeat_interleave(W, 0)                          # [M, P]: row s W + b is beam b of sentence s
-            per_seq = state.options["per_sequence"]
-            mask = prompt.eq(self.pad_idx) if per_seq else None
-            x = self.decode(prompt.t(), state, mask)                         # [P, M, C]
-            if per_seq:
-                n_b = P - mask.ne(0).to(torch.int32).cumsum(1).ne(0).sum(1)
-                last = x[(n_b - 1).clamp_(min=0), torch.arange(M, device=x.device)].unsqueeze(0)
-            else:
-                last = x[P - 1:P]
-            tok_in, parent = self.beam_step(last, state)                     # [1, M]: the step's static input
+            tok_in, parent = self.beam_step(self._prefill(prompt, state), state)     # [1, M]: the step's static input
             self.reorder_decoding_state(state, parent)
 
-            def step(st, beams):
-                self.beam_step(self.decode(tok_in, st), beams, out=tok_in)
-                self.reorder_decoding_state(st, beams.beam.parent)
-            g = None
-            if graph and max_new > 1:
-                scratch = self.init_decoding(**dict(state.options, max_tokens=1, hold_vocab=False))
-                scratch.vocab, scratch.vocab_ws = state.vocab, state.vocab_ws
-                self.init_beam_search(scratch, W, eos_idx, max_new, len_penalty)
-                first = tok_in.clone()
-                side = torch.cuda.Stream()
-                side.wait_stream(torch.cuda.current_stream())
-                with torch.cuda.stream(side):
-                    step(scratch, scratch)
-                torch.cuda.current_stream().wait_stream(side)
-                tok_in.copy_(first)
-                del scratch
-                g = torch.cuda.CUDAGraph()
-                with torch.cuda.graph(g):
-                    step(state, state)
-            bm.replays = 0
-            for i in range(1, max_new):
-                if g is None:
-                    step(state, state)
-                else:
-                    g.replay()
+            def step(st):
+                self.beam_step(self.decode(tok_in, st), st, out=tok_in)
+                self.reorder_decoding_state(st, st.beam.parent)
+
+            def scratch():                                                   # (the table is shared, the beam buffers are not)
+                st = self.init_decoding(**dict(state.options, max_tokens=1, hold_vocab=False))
+                st.vocab, st.vocab_ws = state.vocab, state.vocab_ws
+                return self.init_beam_search(st, W, eos_idx, max_new, len_penalty)
+
+            def each(i, _):
                 bm.replays = i
-                if i % poll == 0 and i + 1 < max_new and bool(bm.done.ne(0).all()):
-                    break
-            if self.decoding_overflowed(state):
-                raise RuntimeError("the decoding state overflowed: a step passed its %d tokens (init_decoding(max_tokens=...))"
-                                   % state.options["max_tokens"])
+                return i % poll == 0 and i + 1 < max_new and bool(bm.done.ne(0).all())
+            bm.replays = 0
+            self._run_steps(step, state, max_new, graph, tok_in, scratch, each=each)
             return self._beam_hypotheses(bm)
 
     def generate(self, prompt, n_new, state=None, graph=True, return_rows=False, return_logprobs=False):
@@ -1254,95 +930,33 @@ class DecoderStack(nn.Module):
         n_new = int(n_new)
         if n_new < 1:
             raise ValueError("generate needs n_new >= 1, got %d" % n_new)
-        adaptive = state is not None and state.adaptive is not None
-        if adaptive and B > state.adaptive.logp.numel():
-            raise ValueError("a prompt of %d rows on an adaptive pick made for %d" % (B, state.adaptive.logp.numel()))
-        if return_logprobs and not adaptive:
-            if state is None or state.scorer is None:
-                raise RuntimeError("generate(return_logprobs=True) needs a decoding state with a scorer: init_logprobs(state)")
-            if B > state.scorer.logp.numel():
-                raise ValueError("a prompt of %d rows on a scorer made for %d" % (B, state.scorer.logp.numel()))
-        amp = torch.is_autocast_enabled()
-        ctx = torch.autocast("cuda", dtype=torch.get_autocast_dtype("cuda"), cache_enabled=False) if amp \
-            else contextlib.nullcontext()                        # (a capture may not use autocast's weight-cast cache)
+        pick = tp.select_pick(self, state, B, return_logprobs)               # (what is not attached is reported here)
+        ctx, dtype = self._decoding_context()
         with torch.no_grad(), ctx:
             if state is None:
-                dtype = torch.get_autocast_dtype("cuda") if amp else self._embed_dtype()
                 state = self.init_decoding(B, P + n_new, dtype, prompt.device, hold_weights=dtype != torch.float32)
-            per_seq = state.options["per_sequence"]
-            mask = prompt.eq(self.pad_idx) if per_seq else None
-            x = self.decode(prompt.t(), state, mask)                         # [P, B, C]
-            if per_seq:                                                      # the row of each sequence's last token
-                n_b = P - mask.ne(0).to(torch.int32).cumsum(1).ne(0).sum(1)
-                last = x[(n_b - 1).clamp_(min=0), torch.arange(B, device=x.device)].unsqueeze(0)
-            else:
-                last = x[P - 1:P]
-            held = state.vocab is not None or adaptive
-            pick = self.next_tokens if state.sampler is None else self.sample_tokens
-            lp_in = logps = None
-            if adaptive:                                                     # [1, B] view of the pick's static buffer
-                lp_in = state.adaptive.logp[:B].view(1, B)
-                if return_logprobs:
-                    logps = torch.empty((B, n_new), dtype=torch.float32, device=prompt.device)
-
-                def pick(y, st, out=None):
-                    return self._adaptive_pick(y, st, None, out, lp_in)[0]
-            elif return_logprobs:                                            # [1, B] views of the scorer's static buffers
-                lp_in, lse_in = state.scorer.logp[:B].view(1, B), state.scorer.lse[:B].view(1, B)
-                logps = torch.empty((B, n_new), dtype=torch.float32, device=prompt.device)
-                if state.sampler is None:
-                    def pick(y, st, out=None):
-                        return self._logprob_pick(y, st, None, out, lp_in, lse_in)[0]
-                else:
-                    def pick(y, st, out=None):
-                        return self._sample_logprob_pick(y, st, out, lp_in, lse_in)[0]
-            # [1, B]: the step's static input
-            tok_in = pick(last, state) if held else self.logits(last).argmax(-1)
+            last = self._prefill(prompt, state)
+            tok_in = pick(last)                                              # [1, B]: the step's static input
             out = torch.empty((B, n_new), dtype=torch.long, device=prompt.device)
             rows = torch.empty((n_new,) + tuple(last.shape[1:]), dtype=last.dtype, device=prompt.device) if return_rows else None
-            out[:, 0] = tok_in[0]
-            if rows is not None:
-                rows[0] = last[0]
-            if logps is not None:
-                logps[:, 0] = lp_in[0]
+            logps = torch.empty((B, n_new), dtype=torch.float32, device=prompt.device) if return_logprobs else None
 
-            def step(st):
-                y = self.decode(tok_in, st)
-                if held:                                                     # (the table and the workspace are `state`'s)
-                    pick(y, state, out=tok_in)
-                else:
-                    tok_in.copy_(self.logits(y).argmax(-1))
-                return y
-            g = None
-            if graph and n_new > 1:
-                scratch = self.init_decoding(**dict(state.options, max_tokens=1, hold_vocab=False))
-                first = tok_in.clone()
-                drawn = None if state.sampler is None else state.sampler.ctr.clone()
-                side = torch.cuda.Stream()
-                side.wait_stream(torch.cuda.current_stream())
-                with torch.cuda.stream(side):
-                    step(scratch)
-                torch.cuda.current_stream().wait_stream(side)
-                tok_in.copy_(first)
-                if drawn is not None:                                        # (the warm-up drew once)
-                    state.sampler.ctr.copy_(drawn)
-                del scratch
-                g = torch.cuda.CUDAGraph()
-                with torch.cuda.graph(g):
-                    y = step(state)
-            for i in range(1, n_new):
-                if g is None:
-                    y = step(state)
-                else:
-                    g.replay()
+            def record(i, y):
                 out[:, i] = tok_in[0]
                 if rows is not None:
                     rows[i] = y[0]
                 if logps is not None:
-                    logps[:, i] = lp_in[0]
-            if self.decoding_overflowed(state):
-                raise RuntimeError("the decoding state overflowed: a step passed its %d tokens (init_decoding(max_tokens=...))"
-                                   % state.options["max_tokens"])
+                    logps[:, i] = pick.logp[0]
+            record(0, last)
+
+            def step(st):                                                    # (the pick's table and workspaces are `state`'s)
+                y = self.decode(tok_in, st)
+                pick(y, out=tok_in)
+                return y
+
+            def scratch():
+                return self.init_decoding(**dict(state.options, max_tokens=1, hold_vocab=False))
+            self._run_steps(step, state, n_new, graph, tok_in, scratch, pick, record)
         if logps is not None:
             return (out, rows, logps) if return_rows else (out, logps)
         return (out, rows) if return_rows else out

@@ -113,10 +113,15 @@ def run_generate(stack, B, context, hold_vocab, steps, blocks=5, warmup=4, sampl
         lp = torch.zeros((1, B), dtype=torch.float32, device="cuda")
         if logprobs == "native":
             stack.init_logprobs(state)
+            if hasattr(state, "pick"):                          # generate's own pick: it writes the scorer's static buffers
+                lp_pick = state.pick(stack, B, return_logprobs=True)
+            else:                                               # (a --root from before ea_harness/token_pick.py)
+                def lp_pick(rows, out):
+                    stack._logprob_pick(rows, state, None, out, state.scorer.logp[:B].view(1, B), state.scorer.lse[:B].view(1, B))
 
         def pick(rows, out):
-            if logprobs == "native":                            # (the scorer's static buffers, as generate hands them)
-                stack._logprob_pick(rows, state, None, out, state.scorer.logp[:B].view(1, B), state.scorer.lse[:B].view(1, B))
+            if logprobs == "native":
+                lp_pick(rows, out)
             elif logprobs == "framework":
                 _, logits = stack.next_tokens(rows, state, out=out, return_logits=True)
                 lp.copy_(logits.gather(2, out.unsqueeze(2)).squeeze(2) - torch.logsumexp(logits, -1))

@@ -61,7 +61,7 @@ def route_few_rows(x, w, targets):
     logp = torch.empty(M, dtype=torch.float32, device="cuda")
 
     def call():
-        for a in range(0, M, FEW_ROWS):                   # DecoderStack._logprob_pick's loop
+        for a in range(0, M, FEW_ROWS):                   # token_pick.HeldGreedyLogprob.run's loop
             n = min(FEW_ROWS, M - a)
             nv.call("ea_ceva_sdecode_vocab_logprob", n, K, V, nv.ptr(x[a:a + n]), nv.io_dtype(x), K, nv.ptr(w), nv.io_dtype(w),
                     None, nv.EA_F32, V, nv.ptr(ws), nbytes, nv.ptr(tok[a:a + n]), None, nv.ptr(lws), lbytes,
