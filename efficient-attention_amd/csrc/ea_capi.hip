@@ -41,7 +41,7 @@ static Geo mk_geo(const ea_geom* g) {
 extern "C" {
 
 const char* ea_version(void) { return "ea_hip 0.1.0 gfx950"; }
-int32_t ea_abi_version(void) { return 34; }
+int32_t ea_abi_version(void) { return 35; }
 
 int32_t ea_window_bias_ld(const ea_geom* g) {
   WinTiling t;
@@ -2654,6 +2654,92 @@ int ea_adaptive_pick(int32_t M, int32_t C, int32_t n_tails, const int64_t* cutof
   for (int i = 0; i <= n_tails; ++i) p.cut[i] = cutoffs[i];
   for (int i = 0; i < n_tails; ++i) { p.dims[i] = dims[i]; p.proj[i] = (const char*)proj[i]; p.table[i] = (const char*)tables[i]; }
   return ea::adaptive_pick(p, (hipStream_t)stream);
+}
+
+}  // extern "C"
+
+// ---- the sampled pick and the beam step from the adaptive head (ABI 35, ea_adaptive_pick.hip): ea_adaptive_pick's operands,
+// then ea_ceva_sdecode_vocab_sample's / ea_beam_merge's groups in their order --------------------------------------------------
+// the operands the three adaptive pick entries share: EA_E_BADARG, or 0
+static int adp_operands_ok(int32_t M, int32_t C, int32_t n_tails, const int64_t* cutoffs, const int32_t* dims, const void* x,
+                           int32_t x_dtype, int64_t ldx, const void* head, int32_t w_dtype, const void* const* proj,
+                           const void* const* tables, const void* ws) {
+  if (!adp_cutoffs_ok(n_tails, cutoffs) || !dims || !proj || !tables) return EA_E_BADARG;
+  if (!dec_table_ok(M, C, x, x_dtype, ldx, head, w_dtype)) return EA_E_BADARG;
+  for (int i = 0; i < n_tails && i < EA_ADAPTIVE_MAX_TAILS; ++i)
+    if (dims[i] < 1 || !proj[i] || !tables[i] || (uintptr_t)proj[i] % 16 || (uintptr_t)tables[i] % 16) return EA_E_BADARG;
+  return !ws || (uintptr_t)ws % 16 ? EA_E_BADARG : 0;
+}
+
+// the workspace's size and the geometry, behind the argument checks: EA_E_BADARG, EA_E_UNSUPPORTED, or 0
+static int adp_select_geometry(int32_t M, int32_t C, int32_t n_tails, const int64_t* cutoffs, const int32_t* dims, int32_t W,
+                               int64_t ws_bytes) {
+  const bool envelope = n_tails <= EA_ADAPTIVE_MAX_TAILS && M <= EA_CEVA_LINEAR_MAX_ROWS && W <= 32 && (W == 0 || M % W == 0);
+  const int64_t need = envelope ? ea::adaptive_select_plan(M, n_tails, cutoffs, dims, W, nullptr) : -1;
+  if (need >= 0 && ws_bytes < need) return EA_E_BADARG;
+  if (!envelope || C % 32 || need < 0) return EA_E_UNSUPPORTED;
+  for (int i = 0; i < n_tails; ++i)
+    if (dims[i] % 32) return EA_E_UNSUPPORTED;
+  return 0;
+}
+
+static ea::AdaptivePickP adp_pick_fill(int32_t M, int32_t C, int32_t n_tails, const int64_t* cutoffs, const int32_t* dims,
+                                       const void* x, int32_t x_dtype, int64_t ldx, const void* head, int32_t w_dtype,
+                                       const void* const* proj, const void* const* tables, void* ws) {
+  ea::AdaptivePickP p = {};
+  p.x = (const char*)x; p.head = (const char*)head; p.ws = (char*)ws;
+  p.ldx = ldx; p.M = M; p.C = C; p.n = n_tails; p.dtype = w_dtype; p.x_f32 = x_dtype == EA_F32;
+  for (int i = 0; i <= n_tails; ++i) p.cut[i] = cutoffs[i];
+  for (int i = 0; i < n_tails; ++i) { p.dims[i] = dims[i]; p.proj[i] = (const char*)proj[i]; p.table[i] = (const char*)tables[i]; }
+  return p;
+}
+
+extern "C" {
+
+int64_t ea_adaptive_sample_ws(int32_t M, int32_t n_tails, const int64_t* cutoffs, const int32_t* dims) {
+  return ea::adaptive_select_plan(M, n_tails, cutoffs, dims, 0, nullptr);
+}
+
+int ea_adaptive_sample(int32_t M, int32_t C, int32_t n_tails, const int64_t* cutoffs, const int32_t* dims, const void* x,
+                       int32_t x_dtype, int64_t ldx, const void* head, int32_t w_dtype, const void* const* proj,
+                       const void* const* tables, void* ws, int64_t ws_bytes, int32_t top_k, float top_p, float temperature,
+                       uint64_t seed, int64_t* ctr, const int32_t* sid, int64_t* token, float* logp, int32_t* sel_idx,
+                       float* sel_val, int32_t* kept, void* stream) {
+  if (const int rc = adp_operands_ok(M, C, n_tails, cutoffs, dims, x, x_dtype, ldx, head, w_dtype, proj, tables, ws)) return rc;
+  if (!token || !logp || (uintptr_t)token % 8 || (uintptr_t)logp % 4 ||
+      !dec_sampler_ok(top_k, top_p, temperature, ctr, sid, sel_idx, sel_val, kept)) return EA_E_BADARG;
+  if (top_k > 64) return EA_E_UNSUPPORTED;
+  if (const int rc = adp_select_geometry(M, C, n_tails, cutoffs, dims, 0, ws_bytes)) return rc;
+  ea::AdaptivePickP p = adp_pick_fill(M, C, n_tails, cutoffs, dims, x, x_dtype, ldx, head, w_dtype, proj, tables, ws);
+  p.token = token; p.logp = logp;
+  ea::AdaptiveJointArgs j = {};
+  j.top_k = top_k; j.top_p = top_p; j.temperature = temperature; j.seed_lo = (uint32_t)seed; j.seed_hi = (uint32_t)(seed >> 32);
+  j.ctr = ctr; j.sid = sid; j.token = token; j.logp = logp; j.sel_idx = sel_idx; j.sel_val = sel_val; j.kept = kept;
+  return ea::adaptive_select(p, j, (hipStream_t)stream);
+}
+
+int64_t ea_adaptive_beam_ws(int32_t M, int32_t n_tails, const int64_t* cutoffs, const int32_t* dims, int32_t W) {
+  return W < 1 ? -1 : ea::adaptive_select_plan(M, n_tails, cutoffs, dims, W, nullptr);
+}
+
+int ea_adaptive_beam(int32_t M, int32_t C, int32_t n_tails, const int64_t* cutoffs, const int32_t* dims, const void* x,
+                     int32_t x_dtype, int64_t ldx, const void* head, int32_t w_dtype, const void* const* proj,
+                     const void* const* tables, void* ws, int64_t ws_bytes, int32_t W, int32_t eos, int32_t max_new,
+                     float* score, int32_t* t, int32_t* nfin, int32_t* done, int64_t* token, int64_t* parent,
+                     int32_t* hist_tok, int32_t* hist_par, float* fin_score, int32_t* fin_len, int32_t* fin_beam,
+                     int32_t* cand_idx, float* cand_score, void* stream) {
+  if (const int rc = adp_operands_ok(M, C, n_tails, cutoffs, dims, x, x_dtype, ldx, head, w_dtype, proj, tables, ws)) return rc;
+  if (!dec_beam_ok(W, eos, max_new, score, t, nfin, done, token, parent, hist_tok, hist_par, fin_score, fin_len, fin_beam,
+                   cand_idx, cand_score, nullptr, nullptr) ||
+      (n_tails <= EA_ADAPTIVE_MAX_TAILS && eos >= cutoffs[n_tails])) return EA_E_BADARG;
+  if (const int rc = adp_select_geometry(M, C, n_tails, cutoffs, dims, W, ws_bytes)) return rc;
+  ea::AdaptivePickP p = adp_pick_fill(M, C, n_tails, cutoffs, dims, x, x_dtype, ldx, head, w_dtype, proj, tables, ws);
+  const int64_t V = cutoffs[n_tails];
+  ea::AdaptiveJointArgs j = {};
+  j.W = W;
+  j.beam = dec_beam_fill(M / W, W, 2 * W < V ? 2 * W : (int)V, eos, max_new, score, t, nfin, done, token, parent, hist_tok,
+                         hist_par, fin_score, fin_len, fin_beam, cand_idx, cand_score);
+  return ea::adaptive_select(p, j, (hipStream_t)stream);
 }
 
 }  // extern "C"

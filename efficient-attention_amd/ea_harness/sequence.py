@@ -16,7 +16,8 @@ distribution from the same pass over the table (ea_ceva_sdecode_vocab_logprob, e
 `init_beam_search` / `beam_step` / `beam_search` are a beam search whose step -- candidates, merge, finished hypotheses and the
 parent index of the state reorder -- runs on the device (ea_ceva_sdecode_vocab_beam).  On an adaptive stack
 `init_adaptive_decoding` makes a state pick greedily, with log-probabilities, from the held adaptive tables
-(ea_adaptive_pick).
+(ea_adaptive_pick); on such a state `init_sampling` / `init_beam_search` sample and search from the adaptive head too
+(ea_adaptive_sample, ea_adaptive_beam).
 
 What the modes share lives in token_pick.py: the DecodingState and what the `init_*` methods attach to it, the operand
 helpers, and one pick per launch.  Every public method above is its argument checks and that pick's `run`; `generate` and
@@ -240,7 +241,7 @@ def _hold_vocab_option(init):
         if hold_vocab and self.is_adaptive:
             raise NotImplementedError("hold_vocab=True on an adaptive stack: the held pick, sampler, scorer and beam entries "
                                       "read one [V, C] table; the greedy pick from the adaptive head is "
-                                      "init_adaptive_decoding(state) (sampling and beam search from it are not built)")
+                                      "init_adaptive_decoding(state) (then init_sampling(state, ...) and init_beam_search(state, ...) run from it)")
         if hold_vocab:
             given = params.bind(self, *args, **kw).arguments
             if given["dtype"] == torch.float32:
@@ -404,7 +405,8 @@ class DecoderStack(nn.Module):
         buffers (4 * 64 * (ceil(V / 16) + 1) + 8 B), and of a beam search's buffers for M = S W rows (`init_beam_search`):
         4 M V (logits) + ea_ceva_sdecode_vocab_beam_ws(M, V, W) (workspace) + 4 M (score) + 12 S (t, nfin, done) + 8 M
         (parent) + 8 max_new M (the history) + 12 S W (the records), and of an adaptive pick's tables, workspace
-        (ea_adaptive_pick_ws for 64 rows) and 4 B (logp)."""
+        (ea_adaptive_pick_ws for 64 rows) and 4 B (logp).  On a state with an adaptive pick the sampler's logits give way to
+        ea_adaptive_sample_ws(B, ..) and the beam's logits and workspace to ea_adaptive_beam_ws(M, .., W)."""
         n = sum(layer.self_attn.decoding_state_nbytes(state.incremental) for layer in self.layers)
         n += sum(t.numel() * t.element_size() for held in (state.ffn or ()) for t in held)
         return n + sum(t.numel() * t.element_size() for held in state.attachments() for t in held.tensors())
@@ -523,8 +525,12 @@ class DecoderStack(nn.Module):
         what it would draw decoded alone with its (seed, sid), whatever batch it sits in.
         Attaches `state.sampler` (a Sampler: fp32 logits [batch_size, V], ctr, sid, the scalars; 4 B V + 12 B bytes; the
         pick's workspace is `vocab_ws`) and returns the state.  Values outside the envelope raise ValueError before anything
-        is allocated; full-vocabulary sampling stays with `next_tokens(return_logits=True)`."""
-        if state.vocab is None:
+        is allocated; full-vocabulary sampling stays with `next_tokens(return_logits=True)`.
+        On a state with an adaptive pick (`init_adaptive_decoding`) the list is the `top_k` largest JOINT log-probabilities of
+        the adaptive softmax and the temperature acts on them -- ea_adaptive_sample, include/ea_hip.h (ABI 35); fairseq
+        divides the features by it instead.  The Sampler then holds `ws`, that entry's workspace for batch_size rows (every
+        band's fp32 logits: about 4 B V bytes) in place of the logits buffer; everything else above holds."""
+        if state.vocab is None and state.adaptive is None:
             raise RuntimeError("init_sampling needs a decoding state that holds the vocabulary table: "
                                "init_decoding(..., hold_vocab=True)")
         seed, top_k, top_p, temperature = int(seed), int(top_k), float(top_p), float(temperature)
@@ -536,10 +542,20 @@ class DecoderStack(nn.Module):
             raise ValueError("temperature must be finite and > 0, got %r" % temperature)
         if not 0 <= seed < 1 << 64:
             raise ValueError("seed must be in 0 .. 2^64 - 1, got %d" % seed)
-        B, device = state.options["batch_size"], state.vocab.device
-        state.sampler = Sampler(torch.empty((B, state.vocab.shape[0]), dtype=torch.float32, device=device),
-                                torch.zeros(B, dtype=torch.long, device=device),
-                                torch.arange(B, dtype=torch.int32, device=device), seed, top_k, top_p, temperature)
+        B = state.options["batch_size"]
+        if state.adaptive is not None:
+            from efficient_attention import _native as nv
+            tables = state.adaptive.tables
+            device = tables.device
+            nbytes = nv.lib().ea_adaptive_sample_ws(B, len(tables.dims), *tables.host_arrays()[:2])
+            if nbytes < 0:
+                raise ValueError("a state of %d rows is outside ea_adaptive_sample's envelope (at most %d)" % (B, _FUSED_MAX_ROWS))
+            logits, ws = None, torch.empty(nbytes, dtype=torch.uint8, device=device)
+        else:
+            device = state.vocab.device
+            logits, ws = torch.empty((B, state.vocab.shape[0]), dtype=torch.float32, device=device), None
+        state.sampler = Sampler(logits, torch.zeros(B, dtype=torch.long, device=device),
+                                torch.arange(B, dtype=torch.int32, device=device), seed, top_k, top_p, temperature, ws=ws)
         return state
 
     def sample_tokens(self, rows, state, out=None, return_details=False):
@@ -548,9 +564,14 @@ class DecoderStack(nn.Module):
         the held table; row b draws at (ctr[b], sid[b]) and its counter advances.  out: as in `next_tokens`.
         return_details=True: -> (tokens, sel_idx int32 [B, top_k], sel_val fp32 [B, top_k], kept int32 [B]): the selection in
         order (entries from min(top_k, V) on are not written; log-probabilities follow from sel_val), and how many of it the
-        nucleus kept (0: a row whose best logit is NaN or infinite, which gets the greedy pick).  Device launches only."""
+        nucleus kept (0: a row whose best logit is NaN or infinite, which gets the greedy pick).  Device launches only.
+        On a state with an adaptive pick the draw is ea_adaptive_sample's: sel_idx are vocabulary indices, sel_val their
+        joint log-probabilities."""
         if state.sampler is None:
             raise RuntimeError("sample_tokens needs a decoding state with a sampler: init_sampling(state, seed, top_k, ...)")
+        if state.adaptive is not None:
+            got = tp.AdaptiveSampled(self, state).run(rows, out, None, return_details)
+            return (got[0],) + got[2:] if return_details else got[0]
         return tp.HeldSampled(self, state).run(rows, out, return_details)
 
     def init_logprobs(self, state):
@@ -625,7 +646,11 @@ class DecoderStack(nn.Module):
         """`sample_tokens` and the drawn tokens' log-probabilities, on a state with a sampler and a scorer: rows [1, B, C] ->
         (tokens int64 [1, B], logp fp32 [1, B]).  The tokens, and the counters behind them, are `sample_tokens`' at the same
         (seed, ctr, sid).  logp is the token's log-probability under the RAW distribution at temperature 1 -- not inside the
-        top-k list or the nucleus, not at the sampler's temperature.  Device launches only."""
+        top-k list or the nucleus, not at the sampler's temperature.  Device launches only.
+        On a state with an adaptive pick and a sampler (no scorer needed) logp is the drawn token's joint log-probability,
+        from the same ea_adaptive_sample call."""
+        if state.sampler is not None and state.adaptive is not None:
+            return tp.AdaptiveSampled(self, state).run(rows, out, None, False, who="a sampled pick")
         if state.sampler is None or state.scorer is None:
             raise RuntimeError("sample_tokens_logprobs needs a decoding state with a sampler and a scorer: "
                                "init_sampling(state, seed, top_k, ...) and init_logprobs(state)")
@@ -763,14 +788,17 @@ class DecoderStack(nn.Module):
         (the fp32 sum of its tokens' log-probabilities) over length ** len_penalty, on the host, behind the search.
         Envelope: 1 <= W <= 32, M <= 64.  Values outside it raise ValueError before anything is allocated.  Attaches
         `state.beam` (a Beam: the static buffers of the step, initialised; bytes: `decoding_state_nbytes`) and returns the
-        state."""
-        if state.vocab is None:
+        state.  On a state with an adaptive pick (`init_adaptive_decoding`) the step is ea_adaptive_beam (ABI 35): a row's 2 W
+        candidates are its best JOINT log-probabilities; the Beam's `ws` is that entry's workspace (it holds the bands'
+        fp32 logits, about 4 M V bytes) and `logits` is None."""
+        if state.vocab is None and state.adaptive is None:
             raise RuntimeError("init_beam_search needs a decoding state that holds the vocabulary table: "
                                "init_decoding(..., hold_vocab=True)")
         if state.sampler is not None:
             raise RuntimeError("init_beam_search on a state with a sampler: a beam search draws nothing")
         W, eos, max_new, len_penalty = int(beam_size), int(eos_idx), int(max_new), float(len_penalty)
-        M, V = int(state.options["batch_size"]), state.vocab.shape[0]
+        tables = None if state.adaptive is None else state.adaptive.tables
+        M, V = int(state.options["batch_size"]), state.vocab.shape[0] if tables is None else tables.cutoff[-1]
         if not 1 <= W <= _BEAM_MAX_W:
             raise ValueError("beam_size must be in 1 .. %d, got %d" % (_BEAM_MAX_W, W))
         if M > _FUSED_MAX_ROWS or M % W:
@@ -783,13 +811,18 @@ class DecoderStack(nn.Module):
         if not math.isfinite(len_penalty):
             raise ValueError("len_penalty must be finite, got %r" % len_penalty)
         from efficient_attention import _native as nv
-        S, device = M // W, state.vocab.device
-        nbytes = nv.lib().ea_ceva_sdecode_vocab_beam_ws(M, V, W)
+        if tables is None:
+            S, device = M // W, state.vocab.device
+            nbytes = nv.lib().ea_ceva_sdecode_vocab_beam_ws(M, V, W)
+        else:
+            S, device = M // W, tables.device
+            nbytes = nv.lib().ea_adaptive_beam_ws(M, len(tables.dims), *tables.host_arrays()[:2], W)
 
         def buf(shape, dtype):
             return torch.empty(shape, dtype=dtype, device=device)
         i32, f32 = torch.int32, torch.float32
-        state.beam = Beam(W, eos, max_new, len_penalty, buf((M, V), f32), buf(nbytes, torch.uint8), buf(M, f32), buf(S, i32),
+        state.beam = Beam(W, eos, max_new, len_penalty, buf((M, V), f32) if tables is None else None, buf(nbytes, torch.uint8),
+                          buf(M, f32), buf(S, i32),
                           buf(S, i32), buf(S, i32), buf(M, torch.long), buf((max_new, M), i32), buf((max_new, M), i32),
                           buf((S, W), f32), buf((S, W), i32), buf((S, W), i32))
         return self.reset_beam_search(state)
@@ -814,7 +847,8 @@ class DecoderStack(nn.Module):
         on the device, in the Beam's buffers (`parent` is one of them).  out: as in `next_tokens`.
         return_details=True: -> (tokens, parent, cand_idx int32 [M, 2 W], cand_score fp32 [M, 2 W], lse fp32 [M]); entries
         from min(2 W, V) on (the forced step: from 1 on) and the rows of a done sentence are not written.  Device launches
-        only."""
+        only.  On a state with an adaptive pick: ONE call of ea_adaptive_beam; cand_idx are vocabulary indices, cand_score the
+        cumulative joint log-probabilities, and the details end there (no single log-sum-exp exists)."""
         bm = state.beam
         if bm is None:
             raise RuntimeError("beam_step needs a decoding state with a beam search: init_beam_search(state, beam_size, ...)")
@@ -822,7 +856,7 @@ class DecoderStack(nn.Module):
         if T != 1 or M != bm.score.numel():
             raise ValueError("beam_step takes the rows of one single-token step of the whole state, [1, %d, C]; got %s"
                              % (bm.score.numel(), tuple(rows.shape)))
-        return tp.BeamStep(self, state).run(rows, out, return_details)
+        return (tp.BeamStep if state.adaptive is None else tp.AdaptiveBeamStep)(self, state).run(rows, out, return_details)
 
     @staticmethod
     def _beam_hypotheses(bm):
@@ -852,7 +886,8 @@ class DecoderStack(nn.Module):
         and `raw_score` (an fp32 scalar tensor: the sum of the tokens' log-probabilities under the model's own distribution).
         At most beam_size per sentence; fewer where live beams ran out.  The rule -- fairseq's SequenceGenerator without
         min_len, n-gram blocking, prefix tokens and match_source_len, with ties decided and a -inf-scored eos dropped -- is in
-        include/ea_hip.h (ABI 32).
+        include/ea_hip.h (ABI 32).  On an adaptive stack the state carries an adaptive pick instead of a held table
+        (`init_adaptive_decoding`; the default state is made so) and the step is ea_adaptive_beam (ABI 35).
         state: a fresh DecodingState of S beam_size rows made with hold_vocab=True (default: rolling, held weights, the
         autocast dtype, P + max_new tokens); one without a beam gets `init_beam_search(state, beam_size, eos_idx, max_new,
         len_penalty)`, one with a beam must have been given the same four values and be at its start (`reset_beam_search`).
@@ -873,7 +908,10 @@ class DecoderStack(nn.Module):
         ctx, dtype = self._decoding_context()
         with torch.no_grad(), ctx:
             if state is None:
-                state = self.init_decoding(M, P + max(max_new, 1), dtype, prompt.device, hold_vocab=True)
+                if self.is_adaptive:
+                    state = self.init_adaptive_decoding(self.init_decoding(M, P + max(max_new, 1), dtype, prompt.device))
+                else:
+                    state = self.init_decoding(M, P + max(max_new, 1), dtype, prompt.device, hold_vocab=True)
             if state.beam is None:
                 self.init_beam_search(state, W, eos_idx, max_new, len_penalty)
             bm = state.beam
@@ -892,7 +930,7 @@ class DecoderStack(nn.Module):
 
             def scratch():                                                   # (the table is shared, the beam buffers are not)
                 st = self.init_decoding(**dict(state.options, max_tokens=1, hold_vocab=False))
-                st.vocab, st.vocab_ws = state.vocab, state.vocab_ws
+                st.vocab, st.vocab_ws, st.adaptive = state.vocab, state.vocab_ws, state.adaptive
                 return self.init_beam_search(st, W, eos_idx, max_new, len_penalty)
 
             def each(i, _):
@@ -923,7 +961,9 @@ class DecoderStack(nn.Module):
         buffer; -> (tokens[, rows], logp fp32 [B, n_new]).  The tokens are those of the same call without the keyword.
         On a state with an adaptive pick (`init_adaptive_decoding`) both picks are ea_adaptive_pick: the step ends in that
         kernel, which writes the token into the step's static input and its joint log-probability into
-        `state.adaptive.logp`, where return_logprobs=True takes it from (no scorer needed)."""
+        `state.adaptive.logp`, where return_logprobs=True takes it from (no scorer needed).  With a sampler on such a state
+        (`init_sampling`) both picks are ea_adaptive_sample: sampled decoding from the adaptive head, the drawn tokens' joint
+        log-probabilities in the same buffer."""
         if self.training:
             raise NotImplementedError("incremental decoding in training mode")
         B, P = prompt.shape

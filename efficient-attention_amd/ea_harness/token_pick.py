@@ -9,7 +9,8 @@
                       state has, so that the stack's four lifecycle methods name none of them.
   picks            -- one class per launch: `HeldGreedy` (ea_ceva_sdecode_vocab_argmax), `HeldSampled` (.._sample),
                       `HeldGreedyLogprob` (.._logprob), `HeldSampledLogprob` (.._sample_logprob), `AdaptiveGreedy`
-                      (ea_adaptive_pick), `BeamStep` (.._beam), and `FrameworkGreedy`, `logits(rows).argmax(-1)`.  `run` is the
+                      (ea_adaptive_pick), `AdaptiveSampled` (ea_adaptive_sample), `BeamStep` (.._beam), `AdaptiveBeamStep`
+                      (ea_adaptive_beam), and `FrameworkGreedy`, `logits(rows).argmax(-1)`.  `run` is the
                       launch behind the stack's public method of that mode; calling the pick, `pick(rows, out=None) -> tokens`,
                       is what a decoding loop does with it: `logp` is the [1, B] view of the static log-probability buffer the
                       call writes (None: the mode has none), `save()` / `restore(saved)` bracket a warm-up call (the sampler's
@@ -27,6 +28,8 @@ LOGPROB = "ea_ceva_sdecode_vocab_logprob"
 SAMPLE_LOGPROB = "ea_ceva_sdecode_vocab_sample_logprob"
 ADAPTIVE_PICK = "ea_adaptive_pick"
 BEAM = "ea_ceva_sdecode_vocab_beam"
+ADAPTIVE_SAMPLE = "ea_adaptive_sample"
+ADAPTIVE_BEAM = "ea_adaptive_beam"
 
 
 def _native():
@@ -142,15 +145,16 @@ class Sampler(Attachment):
     """What `DecoderStack.init_sampling` attaches to a DecodingState: the fp32 `logits` buffer [batch_size, V] of the sampled
     pick, the draw counters `ctr` (int64 [B]: draw n of a row is made at ctr = n) and the stream ids `sid` (int32 [B]), both
     on the device, the host scalars `seed`, `top_k`, `top_p`, `temperature`, and `next_sid`, the first stream id no row of
-    this state has had."""
+    this state has had.  On a state with an adaptive pick there is no [batch_size, V] row: `logits` is None and `ws` is the
+    workspace of ea_adaptive_sample for batch_size rows (bytes; it holds every band's fp32 logits, about 4 B V)."""
 
-    def __init__(self, logits, ctr, sid, seed, top_k, top_p, temperature):
-        self.logits, self.ctr, self.sid = logits, ctr, sid
+    def __init__(self, logits, ctr, sid, seed, top_k, top_p, temperature, ws=None):
+        self.logits, self.ctr, self.sid, self.ws = logits, ctr, sid, ws
         self.seed, self.top_k, self.top_p, self.temperature = seed, top_k, top_p, temperature
         self.next_sid = sid.numel()
 
     def tensors(self):
-        return (self.logits, self.ctr, self.sid)
+        return tuple(t for t in (self.logits, self.ws, self.ctr, self.sid) if t is not None)
 
     def reorder(self, new_order):                       # a row takes its stream along: counters and ids, in place
         order = new_order.to(device=self.ctr.device, dtype=torch.long)
@@ -254,7 +258,8 @@ class Beam(Attachment):
     `max_new`, `len_penalty` and the static buffers of ea_ceva_sdecode_vocab_beam (include/ea_hip.h, ABI 32) for M = the
     state's batch size = S W rows: `logits` fp32 [M, V], `ws` (the entry's workspace, bytes), `score` fp32 [M], `t`, `nfin`,
     `done` int32 [S], `parent` int64 [M], `hist_tok`, `hist_par` int32 [max_new, M], `fin_score` fp32 [S, W], `fin_len`,
-    `fin_beam` int32 [S, W].  `replays`: how many steps behind the first pick the last `beam_search` on it ran."""
+    `fin_beam` int32 [S, W].  `replays`: how many steps behind the first pick the last `beam_search` on it ran.
+    On a state with an adaptive pick `logits` is None and `ws` is ea_adaptive_beam's workspace (it holds the bands' logits)."""
 
     def __init__(self, beam_size, eos_idx, max_new, len_penalty, logits, ws, score, t, nfin, done, parent, hist_tok, hist_par,
                  fin_score, fin_len, fin_beam):
@@ -265,8 +270,8 @@ class Beam(Attachment):
         self.replays = 0
 
     def buffers(self):
-        return (self.logits, self.ws, self.score, self.t, self.nfin, self.done, self.parent, self.hist_tok, self.hist_par,
-                self.fin_score, self.fin_len, self.fin_beam)
+        return tuple(t for t in (self.logits, self.ws, self.score, self.t, self.nfin, self.done, self.parent, self.hist_tok,
+                                 self.hist_par, self.fin_score, self.fin_len, self.fin_beam) if t is not None)
 
     tensors = buffers
 
@@ -319,7 +324,7 @@ def select_pick(stack, state, B, return_logprobs=False):
     if state is not None and state.adaptive is not None:
         if B > state.adaptive.logp.numel():
             raise ValueError("a prompt of %d rows on an adaptive pick made for %d" % (B, state.adaptive.logp.numel()))
-        return AdaptiveGreedy(stack, state, B)
+        return (AdaptiveGreedy if state.sampler is None else AdaptiveSampled)(stack, state, B)
     if return_logprobs:
         if state is None or state.scorer is None:
             raise RuntimeError("generate(return_logprobs=True) needs a decoding state with a scorer: init_logprobs(state)")
@@ -510,6 +515,42 @@ class AdaptiveGreedy(Pick):
         return out, logp
 
 
+class AdaptiveSampled(Pick):
+    """ea_adaptive_sample on the held adaptive tables and the sampler's workspace: `sample_tokens` and
+    `sample_tokens_logprobs` of a state with an adaptive pick and a sampler; called as a pick it writes the drawn tokens'
+    joint log-probabilities into the first B entries of the static `state.adaptive.logp`.  A warm-up draws once: `save` /
+    `restore` keep the counters."""
+    save, restore = HeldSampled.save, HeldSampled.restore
+
+    def _static(self, B):
+        self.logp = self.state.adaptive.logp[:B].view(1, B)
+
+    def __call__(self, rows, out=None):
+        return self.run(rows, out, self.logp, False)[0]
+
+    def run(self, rows, out, logp, return_details, who="sample_tokens"):
+        """-> (tokens int64 [1, B], logp fp32 [1, B]), with return_details and (sel_idx, sel_val, kept); out, logp: their
+        places (None: allocated)."""
+        nv, sm, tb = _native(), self.state.sampler, self.state.adaptive.tables
+        single_step(rows, min(MAX_ROWS, sm.ctr.numel()), who)
+        x2 = score_operand(tb.head, rows)
+        B, C = x2.shape
+        dev, n = x2.device, len(tb.dims)
+        out = checked_out(out, (1, B), torch.long, dev)
+        logp = checked_out(logp, (1, B), torch.float32, dev, "logp")
+        nv.require_cuda(x2, "rows")
+        details = None
+        if return_details:
+            details = (torch.empty((B, sm.top_k), dtype=torch.int32, device=dev),
+                       torch.empty((B, sm.top_k), dtype=torch.float32, device=dev),
+                       torch.empty((B,), dtype=torch.int32, device=dev))
+        cut, dims, proj, tabs = tb.host_arrays()
+        nv.call(ADAPTIVE_SAMPLE, B, C, n, cut, dims, nv.ptr(x2), type_code(x2), C, nv.ptr(tb.head), nv.io_dtype(tb.head), proj,
+                tabs, nv.ptr(sm.ws), sm.ws.numel(), sm.top_k, sm.top_p, sm.temperature, sm.seed, nv.ptr(sm.ctr), nv.ptr(sm.sid),
+                nv.ptr(out), nv.ptr(logp), *_ptr_or_none(nv, details), nv.stream())
+        return (out, logp) + details if return_details else (out, logp)
+
+
 class BeamStep(Pick):
     """ea_ceva_sdecode_vocab_beam on the held table and the state's Beam: `beam_step`.  The tokens it picks are the beams' next
     inputs; the parents they continue are written into `state.beam.parent`.  (No pick of `generate`: a search's step also
@@ -529,4 +570,27 @@ class BeamStep(Pick):
                 nv.ptr(bm.ws), bm.ws.numel(), W, bm.eos_idx, bm.max_new, nv.ptr(bm.score), nv.ptr(bm.t), nv.ptr(bm.nfin),
                 nv.ptr(bm.done), nv.ptr(out), nv.ptr(bm.parent), nv.ptr(bm.hist_tok), nv.ptr(bm.hist_par), nv.ptr(bm.fin_score),
                 nv.ptr(bm.fin_len), nv.ptr(bm.fin_beam), *_ptr_or_none(nv, details), None, nv.stream())
+        return (out, bm.parent) + details if return_details else (out, bm.parent)
+
+
+class AdaptiveBeamStep(Pick):
+    """ea_adaptive_beam on the held adaptive tables and the state's Beam: `beam_step` of a state with an adaptive pick.  What
+    `BeamStep` says of tokens and parents holds; the details have no single log-sum-exp."""
+
+    def run(self, rows, out, return_details):
+        nv, bm, tb = _native(), self.state.beam, self.state.adaptive.tables
+        x2 = score_operand(tb.head, rows)
+        M, C = x2.shape
+        W, dev, n = bm.beam_size, x2.device, len(tb.dims)
+        out = checked_out(out, (1, M), torch.long, dev)
+        nv.require_cuda(x2, "rows")
+        details = None
+        if return_details:
+            details = (torch.empty((M, 2 * W), dtype=torch.int32, device=dev),
+                       torch.empty((M, 2 * W), dtype=torch.float32, device=dev))
+        cut, dims, proj, tabs = tb.host_arrays()
+        nv.call(ADAPTIVE_BEAM, M, C, n, cut, dims, nv.ptr(x2), type_code(x2), C, nv.ptr(tb.head), nv.io_dtype(tb.head), proj, tabs,
+                nv.ptr(bm.ws), bm.ws.numel(), W, bm.eos_idx, bm.max_new, nv.ptr(bm.score), nv.ptr(bm.t), nv.ptr(bm.nfin),
+                nv.ptr(bm.done), nv.ptr(out), nv.ptr(bm.parent), nv.ptr(bm.hist_tok), nv.ptr(bm.hist_par), nv.ptr(bm.fin_score),
+                nv.ptr(bm.fin_len), nv.ptr(bm.fin_beam), *(_ptr_or_none(nv, details)[:2]), nv.stream())
         return (out, bm.parent) + details if return_details else (out, bm.parent)

@@ -1423,6 +1423,82 @@ int ea_adaptive_pick(int32_t M, int32_t C, int32_t n_tails, const int64_t* cutof
                      const void* const* proj, const void* const* tables, void* ws, int64_t ws_bytes, int64_t* token,
                      float* logp, void* stream);
 
+/* ABI 35, SAMPLING AND THE BEAM STEP FROM THE ADAPTIVE HEAD (ea_harness DecoderStack.init_sampling, sample_tokens,
+ * sample_tokens_logprobs, init_beam_search, beam_step, beam_search, generate on a state with an adaptive pick;
+ * ea_adaptive_pick.hip): the exact k best JOINT log-probabilities of a row across the head and the tails, 1 <= k <= 64, then
+ * ea_ceva_sdecode_vocab_sample's draw on them (k = top_k) or the beam step's candidates (k = 2 W) and ea_beam_merge.  Names
+ * and operands are ABI 34's (no targets); 1 <= M <= 64 rows, 16-bit tables.
+ * THE RULE.  The joint score of a token is formed in fp32 by these operations only, in this order (a host program that reads
+ * the stored logits, cls and lse out of the workspace reproduces the bits):
+ *   a word v < c0:     s = a[v] - lse_h
+ *   a token c_i + u:   s = (a[c0 + i] - lse_h) + (b_i[u] - lse_i)
+ * Bands: band 0 is the head's words (V_0 = c0 columns), band i + 1 is tail i.  Per band the min(k, V_b) best RAW logits under
+ * the pick's total order (the larger value, of equals -- +0 and -0 are equal -- the lower index, NaN above every number) are
+ * taken; their joint scores are formed; the min(k, V) best of those (at most (n + 1) k) under the same order on
+ * (s, vocabulary index) are the selection, sorted, the best first.  One consequence: where fp32 rounding makes two logits of
+ * one band equal as joint scores exactly at that band's k-th place, the band's RAW order has decided which of them is a
+ * candidate; and inside the selection equal joint scores stand in the order of their vocabulary indices.  With k = 1 the
+ * selection is ea_adaptive_pick's token and logp bit for bit (the same launches, the same lse device function); with k > 1
+ * entry 0 has ea_adaptive_pick's logp, and its token unless rounding has made a lower-indexed logit of the winner's band equal
+ * to it as a joint score.  A row with non-finite logits follows ABI 34's cases per band; a best joint score that is NaN or
+ * infinite gives the greedy token (entry 0) and kept = 0, as ea_ceva_sdecode_vocab_sample does.
+ * LAUNCHES, 6 + n_tails with joined projections (the beam step: one more):
+ *   1 .. 4. ea_adaptive_pick's launches 1 .. 4, with every band's fp32 logits stored: the table pass with `logits` set for the
+ *      head's words and for tails with d_i > EA_ADAPTIVE_PICK_MAX_K (its 16-column partials are the tile candidates); for
+ *      d_i <= EA_ADAPTIVE_PICK_MAX_K the column-split kernel's instance that also stores its logits and writes one (value,
+ *      index) candidate per 16-column tile -- a 16-lane reduction per tile, before the fold across tiles; the span partials
+ *      and sums are what launch 4 of ABI 34 writes.
+ *   5. the select, grid (row, band), 512 threads: the band's lse by the pick kernel's two passes (its first 256 threads, its
+ *      order; the head takes the class tile's partial last), then ea_ceva_sdecode_vocab_sample's steps 1-2 (the exact radix
+ *      selection) over the band's tile candidates and stored logits: lse[b][m] and the band's sorted (column, raw logit) list.
+ *   6. the joint, one workgroup of 512 threads per row: the lists' joint scores as 64-bit keys (score image, complement of the
+ *      vocabulary index), the radix threshold, compaction and rank sort in LDS, entry j in lane j of one wave, its score formed
+ *      again from the stored logit.  Then one of
+ *      sampled: ea_ceva_sdecode_vocab_sample's steps 3-6 on the joint scores: weights expf((s_j - s_0) / temperature) -- the
+ *        temperature acts on the joint log-probabilities --, c_j = ((w_0 + w_1) + ..) + w_j, the smallest head reaching top_p of
+ *        the list's weight (kept), one Philox4x32-10 word at counter (ctr[m], sid[m]) under `seed`, ctr[m] += 1; token [M]
+ *        int64, logp[m] = s(token[m]) (the RAW distribution's, temperature 1, nothing truncated), and, each NULL or: sel_idx
+ *        [M, top_k] int32 (vocabulary indices), sel_val [M, top_k] fp32 (joint scores), kept [M] int32; entries from
+ *        min(top_k, V) on are not written.
+ *      beam (k = 2 W): cand_idx[m, j] = the token, cand_score[m, j] = score[m] + s_j (one fp32 addition), j < min(2 W, V); the
+ *        rows of a done sentence are skipped (by launch 5 too); on the forced step (t[s] + 1 >= max_new) the single candidate is
+ *        eos with its joint score from the stored logits of the band eos lies in.
+ *   7. the beam step: ea_beam_merge's launch on those lists, unchanged (ABI 32, B / C); kc = min(2 W, V).
+ * Ordinary vector stores only; integer LDS atomics in the radix histograms (their counts do not depend on their order); no
+ * atomics on memory; no workgroup waits for another; launches only: capturable, bitwise reproducible, and a row's (the beam
+ * step: a sentence's) results do not depend on the rows beside it nor on M.
+ * ws, r16 rounding up to a multiple of 16, the parts in this order from byte 0:
+ *   ea_adaptive_pick's workspace for the same (M, n_tails, cutoffs, dims), ea_adaptive_pick_ws bytes: after a call cls, h, lse
+ *   (per band), the class tile's partial and the passes' partials are what ea_adaptive_pick leaves; best and tlogit are not
+ *   written |
+ *   for b = 0 .. n: the band's logits fp32 [M][V_b]  r16(4 M V_b) |
+ *   for each tail with d_i <= EA_ADAPTIVE_PICK_MAX_K: tile candidates (value, index) [M][ceil(V_i / 16)]  r16(8 M ceil(V_i / 16)) |
+ *   the bands' lists: columns IN the band int32 [M][n + 1][64]  r16(256 M (n + 1)), raw logits fp32 [M][n + 1][64]  the same
+ *   (entries from min(k, V_b) on are not written) |
+ *   ea_adaptive_beam alone: cand_idx int32 [M][2 W]  r16(8 M W), cand_score fp32 [M][2 W]  r16(8 M W) (used where the
+ *   caller passes NULL for them)
+ * ea_adaptive_sample_ws / ea_adaptive_beam_ws are their sums: about 4 M V bytes; < 0 where ea_adaptive_pick_ws is, and for
+ * W < 1, W > 32 or M % W != 0.
+ * EA_E_BADARG: ea_adaptive_pick's for the operands and ws; token NULL or not 8-byte aligned, logp NULL; ctr, sid NULL or
+ * misaligned (8, 4 bytes), a misaligned report, top_k < 1, top_p outside (0, 1], temperature not finite or <= 0; the beam's state
+ * as in ea_ceva_sdecode_vocab_beam (a state or output pointer NULL or misaligned, W < 1, eos outside [0, V), max_new < 1);
+ * ws_bytes below the query's answer.  EA_E_UNSUPPORTED: top_k > 64, W > 32, M > 64, M % W != 0, and ea_adaptive_pick's
+ * geometry refusals.  Bad arguments are decided before the geometry, everything before any launch.  ea_adaptive_pick and
+ * ea_adaptive_pick_ws are what they were. */
+int64_t ea_adaptive_sample_ws(int32_t M, int32_t n_tails, const int64_t* cutoffs, const int32_t* dims);
+int ea_adaptive_sample(int32_t M, int32_t C, int32_t n_tails, const int64_t* cutoffs, const int32_t* dims, const void* x,
+                       int32_t x_dtype, int64_t ldx, const void* head, int32_t w_dtype, const void* const* proj,
+                       const void* const* tables, void* ws, int64_t ws_bytes, int32_t top_k, float top_p, float temperature,
+                       uint64_t seed, int64_t* ctr, const int32_t* sid, int64_t* token, float* logp, int32_t* sel_idx,
+                       float* sel_val, int32_t* kept, void* stream);
+int64_t ea_adaptive_beam_ws(int32_t M, int32_t n_tails, const int64_t* cutoffs, const int32_t* dims, int32_t W);
+int ea_adaptive_beam(int32_t M, int32_t C, int32_t n_tails, const int64_t* cutoffs, const int32_t* dims, const void* x,
+                     int32_t x_dtype, int64_t ldx, const void* head, int32_t w_dtype, const void* const* proj,
+                     const void* const* tables, void* ws, int64_t ws_bytes, int32_t W, int32_t eos, int32_t max_new,
+                     float* score, int32_t* t, int32_t* nfin, int32_t* done, int64_t* token, int64_t* parent,
+                     int32_t* hist_tok, int32_t* hist_par, float* fin_score, int32_t* fin_len, int32_t* fin_beam,
+                     int32_t* cand_idx, float* cand_score, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
