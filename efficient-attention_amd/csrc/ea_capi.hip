@@ -248,7 +248,7 @@ extern "C" {
 
 int32_t ea_lara_parts(const ea_lara_geom* g) {
   LaraP p = {};
-  if (fill_lara(g, p, true) != EA_OK) return EA_E_BADARG;
+  if (const int rc = fill_lara(g, p, true)) return rc;      // (C > 128 is an unsupported geometry, not a bad argument)
   return p.nsplit * lara_nsub(p.NCT);
 }
 
@@ -346,7 +346,7 @@ int ea_lara_bwd_kstats(const ea_lara_geom* g, const ea_t4* k, const ea_t4* v, co
 // ---- fused backward (ea_lara_f.hip): one pass per side + one finish pass ----
 int32_t ea_lara_fused_parts(const ea_lara_geom* g) {
   LaraP p = {};
-  if (fill_lara(g, p, false) != EA_OK) return EA_E_BADARG;
+  if (const int rc = fill_lara(g, p, false)) return rc;
   if (p.NCT > 4) return EA_E_UNSUPPORTED;
   return p.nsplit * (p.NCT <= 2 ? 2 : 1);
 }
