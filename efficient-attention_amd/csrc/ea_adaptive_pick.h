@@ -83,6 +83,7 @@ struct AdaptiveJointArgs {
 int64_t adaptive_select_plan(int M, int n, const int64_t* cut, const int32_t* dims, int W, AdaptiveSelectPlan* plan);
 // the band passes with their logits kept, the select and the joint launch; beam: then the merge.  p.targets is not read.
 // The caller has checked the arguments.
-int adaptive_select(const AdaptivePickP& p, const AdaptiveJointArgs& j, hipStream_t st);
+// bans (ABI 36, the beam step alone; or null): ceva_beam_bans on it ahead of the select launch, which then applies the list.
+int adaptive_select(const AdaptivePickP& p, const AdaptiveJointArgs& j, hipStream_t st, const BeamBanP* bans = nullptr);
 
 }  // namespace ea

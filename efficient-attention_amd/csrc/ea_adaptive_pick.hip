@@ -42,6 +42,7 @@ namespace {
 
 #include "ea_ceva_decode_rows.h"
 #include "ea_voc_select.h"
+#include "ea_voc_ban.h"
 
 constexpr int AP_THREADS = AP_WAVES * 64;
 constexpr int AP_LDH = AP_MAX_K + 8;                   // elements of a row of h in LDS: 16 bytes of padding
@@ -355,9 +356,17 @@ struct AdaptiveSelectP {
   int n, k, W;
 };
 
-__global__ __launch_bounds__(SMP_THREADS) void adaptive_select_kernel(const AdaptiveSelectP p) {
-  __shared__ VocSelect sh;
-  __shared__ ApFold fold;
+// the constrained beam step's list (ABI 36) and where a band's columns lie among the tokens
+struct AdaptiveBanP {
+  BanListP list;
+  int64_t base[NB_MAX];          // the token of band b's column 0: 0, then cut[b - 1]
+};
+
+// BANS (ABI 36): the listed tokens that fall in band b are applied to the band's stored logits and tile candidates, behind the
+// fold (the band's lse is the unconstrained one) and ahead of the selection (ea_voc_ban.h); class columns are no band's.  The
+// body of both kernels, inlined: the unconstrained one -- the sampler's too -- keeps its instructions.
+template <bool BANS>
+EA_DEV void adaptive_select_body(const AdaptiveSelectP& p, const AdaptiveBanP& c, VocSelect& sh, ApFold& fold) {
   const int m = blockIdx.x, b = blockIdx.y, lane = threadIdx.x & 63;
   if (p.done && p.done[m / p.W]) return;                  // (uniform)
   const int NP = p.parts[b], Vb = p.vb[b], NT = (Vb - 1) / VOC_TILE + 1;
@@ -367,12 +376,29 @@ __global__ __launch_bounds__(SMP_THREADS) void adaptive_select_kernel(const Adap
                      p.cls_sum + m, fold, best, lse);
   if (threadIdx.x == 0) p.lse[b][m] = lse;
   const float* lrow = p.logits[b] + (int64_t)m * Vb;
+  if constexpr (BANS) {                                   // (this workgroup alone reads and writes the band's row from here on)
+    const int nb = min(max(c.list.nban[m], 0), c.list.cap);
+    voc_apply_bans(const_cast<float*>(lrow), const_cast<VocPick*>(p.tile[b]) + (int64_t)m * NT, Vb,
+                   c.list.ban + (int64_t)m * c.list.cap, nb, c.base[b]);
+  }
   const int kk = voc_select(p.tile[b] + (int64_t)m * NT, lrow, Vb, NT, p.k, sh);
   if (threadIdx.x >= 64 || lane >= kk) return;
   const int32_t idx = min(max(voc_key_index(sh.sorted[lane]), 0), Vb - 1);   // (a column of the band, come what may)
   const int64_t at = ((int64_t)m * (p.n + 1) + b) * ASEL_MAX_K + lane;
   p.list_idx[at] = idx;
   p.list_val[at] = lrow[idx];                              // (the stored logit's own bits: the key has folded -0 and NaNs)
+}
+
+__global__ __launch_bounds__(SMP_THREADS) void adaptive_select_kernel(const AdaptiveSelectP p) {
+  __shared__ VocSelect sh;
+  __shared__ ApFold fold;
+  adaptive_select_body<false>(p, AdaptiveBanP{}, sh, fold);
+}
+
+__global__ __launch_bounds__(SMP_THREADS) void adaptive_select_c_kernel(const AdaptiveSelectP p, const AdaptiveBanP c) {
+  __shared__ VocSelect sh;
+  __shared__ ApFold fold;
+  adaptive_select_body<true>(p, c, sh, fold);
 }
 
 struct AdaptiveJointP {
@@ -624,7 +650,8 @@ int64_t adaptive_select_plan(int M, int n, const int64_t* cut, const int32_t* di
   return sp.total;
 }
 
-int adaptive_select(const AdaptivePickP& a0, const AdaptiveJointArgs& j, hipStream_t st) {
+int adaptive_select(const AdaptivePickP& a0, const AdaptiveJointArgs& j, hipStream_t st, const BeamBanP* bans) {
+  if (bans && !j.W) return EA_E_BADARG;
   AdaptiveSelectPlan sp;
   if (adaptive_select_plan(a0.M, a0.n, a0.cut, a0.dims, j.W, &sp) < 0) return EA_E_UNSUPPORTED;
   if (a0.dtype != EA_BF16 && a0.dtype != EA_F16) return EA_E_BADARG;
@@ -651,7 +678,15 @@ int adaptive_select(const AdaptivePickP& a0, const AdaptiveJointArgs& j, hipStre
   s.cls_cand = vp(pl.cls_cand); s.cls_sum = fp(pl.cls_sum);
   s.list_idx = reinterpret_cast<int32_t*>(a.ws + sp.list_idx); s.list_val = fp(sp.list_val);
   s.done = j.W ? j.beam.done : nullptr; s.n = n; s.k = k; s.W = j.W;
-  hipLaunchKernelGGL(adaptive_select_kernel, dim3((unsigned)a.M, (unsigned)(n + 1)), dim3(SMP_THREADS), 0, st, s);
+  if (bans) {                                             // (ABI 36) the ban-list launch, then the selection with the list applied
+    if (const int rc = ceva_beam_bans(*bans, st)) return rc;
+    AdaptiveBanP c = {};
+    c.list = BanListP{bans->ban, bans->nban, bans->cap};
+    for (int b = 1; b <= n; ++b) c.base[b] = a.cut[b - 1];
+    hipLaunchKernelGGL(adaptive_select_c_kernel, dim3((unsigned)a.M, (unsigned)(n + 1)), dim3(SMP_THREADS), 0, st, s, c);
+  } else {
+    hipLaunchKernelGGL(adaptive_select_kernel, dim3((unsigned)a.M, (unsigned)(n + 1)), dim3(SMP_THREADS), 0, st, s);
+  }
   if (const int rc = (int)hipGetLastError()) return rc;
   // 6. per row: the joint scores, the k best, the draw or the beam's candidates
   q.cls = fp(pl.cls); q.list_idx = s.list_idx; q.list_val = s.list_val; q.n = n; q.k = k; q.a = j;

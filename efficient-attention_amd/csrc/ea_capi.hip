@@ -41,7 +41,7 @@ static Geo mk_geo(const ea_geom* g) {
 extern "C" {
 
 const char* ea_version(void) { return "ea_hip 0.1.0 gfx950"; }
-int32_t ea_abi_version(void) { return 35; }
+int32_t ea_abi_version(void) { return 36; }
 
 int32_t ea_window_bias_ld(const ea_geom* g) {
   WinTiling t;
@@ -2377,6 +2377,27 @@ static ea::DecBeamP dec_beam_fill(int S, int W, int kc, int eos, int max_new, fl
   return b;
 }
 
+// the constraints of a beam step (ABI 36) -> c but for ban, nban and cap; V < 0: no table to hold the static bans against.
+// EA_E_BADARG, or 0
+static int dec_bans_fill(ea::BeamBanP* c, int S, int W, int eos, int max_new, int64_t V, int min_len, int ngram,
+                         const int32_t* ban_tokens, int n_ban_tokens, const int32_t* prompt_tok, int prompt_cap,
+                         const int32_t* prompt_len, const int32_t* t, const int32_t* done, const int32_t* hist_tok,
+                         const int32_t* hist_par, int32_t* gen) {
+  if (max_new < 1 || min_len < 0 || min_len > max_new - 1 || ngram < 0 || ngram > ea::BAN_MAX_NGRAM || n_ban_tokens < 0 ||
+      n_ban_tokens > ea::BAN_MAX_STATIC || (n_ban_tokens > 0 && !ban_tokens) || prompt_cap < 0 ||
+      (prompt_cap > 0 && (!prompt_tok || !prompt_len)) || !gen) return EA_E_BADARG;
+  if ((uintptr_t)prompt_tok % 4 || (uintptr_t)prompt_len % 4 || (uintptr_t)gen % 4) return EA_E_BADARG;
+  *c = ea::BeamBanP{};
+  for (int j = 0; j < n_ban_tokens; ++j) {
+    if (ban_tokens[j] < 0 || ban_tokens[j] == eos || (V >= 0 && ban_tokens[j] >= V)) return EA_E_BADARG;
+    c->static_tok[j] = ban_tokens[j];
+  }
+  c->t = t; c->done = done; c->hist_tok = hist_tok; c->hist_par = hist_par; c->prompt_tok = prompt_tok;
+  c->prompt_len = prompt_len; c->gen = gen; c->S = S; c->W = W; c->eos = eos; c->max_new = max_new; c->min_len = min_len;
+  c->ngram = ngram; c->prompt_cap = prompt_cap; c->n_static = n_ban_tokens;
+  return 0;
+}
+
 extern "C" {
 
 int ea_ceva_sdecode_linear(int32_t M, int32_t K, int32_t N, const void* x, int32_t x_dtype, int64_t ldx,
@@ -2524,6 +2545,61 @@ int ea_beam_merge(int32_t S, int32_t W, int32_t kc, const int32_t* cand_idx, con
   const ea::DecBeamP b = dec_beam_fill(S, W, kc, eos, max_new, score, t, nfin, done, token, parent, hist_tok, hist_par,
                                        fin_score, fin_len, fin_beam, (int32_t*)cand_idx, (float*)cand_score);
   return ea::ceva_beam_merge(b, (hipStream_t)stream);
+}
+
+// ---- the constrained beam step (ABI 36): the unconstrained entry's groups in their order, then the constraints, the prompt
+// and the beams' generated tokens ---------------------------------------------------------------------------------------------
+int ea_beam_bans(int32_t S, int32_t W, int32_t eos, int32_t max_new, int32_t min_len, int32_t ngram, const int32_t* ban_tokens,
+                 int32_t n_ban_tokens, const int32_t* prompt_tok, int32_t prompt_cap, const int32_t* prompt_len,
+                 const int32_t* t, const int32_t* done, const int32_t* hist_tok, const int32_t* hist_par, int32_t* gen,
+                 int32_t* ban, int32_t cap, int32_t* nban, void* stream) {
+  if (S < 1 || W < 1 || eos < 0 || !t || !done || !hist_tok || !hist_par || !ban || !nban) return EA_E_BADARG;
+  for (const void* q : {(const void*)t, (const void*)done, (const void*)hist_tok, (const void*)hist_par, (const void*)ban,
+                        (const void*)nban})
+    if ((uintptr_t)q % 4) return EA_E_BADARG;
+  ea::BeamBanP c;
+  if (const int rc = dec_bans_fill(&c, S, W, eos, max_new, -1, min_len, ngram, ban_tokens, n_ban_tokens, prompt_tok, prompt_cap,
+                                   prompt_len, t, done, hist_tok, hist_par, gen)) return rc;
+  if ((int64_t)cap < ea::beam_ban_cap(prompt_cap, max_new)) return EA_E_BADARG;
+  if (W > 32 || (int64_t)S * W > EA_CEVA_LINEAR_MAX_ROWS) return EA_E_UNSUPPORTED;
+  c.ban = ban; c.nban = nban; c.cap = cap;
+  return ea::ceva_beam_bans(c, (hipStream_t)stream);
+}
+
+int64_t ea_ceva_sdecode_vocab_beam_c_ws(int32_t M, int32_t V, int32_t W, int32_t prompt_cap, int32_t max_new) {
+  const int64_t base = ea::ceva_sdecode_vocab_beam_ws(M, V, W), more = ea::ceva_beam_bans_ws(M, prompt_cap, max_new);
+  return base < 0 || more < 0 ? -1 : base + more;
+}
+
+// (the logits are required and fp32)
+int ea_ceva_sdecode_vocab_beam_c(int32_t M, int32_t K, int32_t V, const void* x, int32_t x_dtype, int64_t ldx,
+                                 const void* w, int32_t w_dtype, float* logits, int64_t ldl, void* ws, int64_t ws_bytes,
+                                 int32_t W, int32_t eos, int32_t max_new, float* score, int32_t* t, int32_t* nfin,
+                                 int32_t* done, int64_t* token, int64_t* parent, int32_t* hist_tok, int32_t* hist_par,
+                                 float* fin_score, int32_t* fin_len, int32_t* fin_beam, int32_t* cand_idx, float* cand_score,
+                                 float* lse, float* sel_val, int32_t min_len, int32_t ngram, const int32_t* ban_tokens,
+                                 int32_t n_ban_tokens, const int32_t* prompt_tok, int32_t prompt_cap,
+                                 const int32_t* prompt_len, int32_t* gen, void* stream) {
+  if (!dec_table_ok(M, K, x, x_dtype, ldx, w, w_dtype) || !logits || !dec_logits_ok(V, logits, EA_F32, ldl, w_dtype) ||
+      !ws || (uintptr_t)ws % 16 ||
+      !dec_beam_ok(W, eos, max_new, score, t, nfin, done, token, parent, hist_tok, hist_par, fin_score, fin_len, fin_beam,
+                   cand_idx, cand_score, lse, sel_val) || (V >= 1 && eos >= V)) return EA_E_BADARG;
+  ea::BeamBanP c;
+  if (const int rc = dec_bans_fill(&c, M / W, W, eos, max_new, V >= 1 ? V : -1, min_len, ngram, ban_tokens, n_ban_tokens,
+                                   prompt_tok, prompt_cap, prompt_len, t, done, hist_tok, hist_par, gen)) return rc;
+  const int64_t base = ea::ceva_sdecode_vocab_beam_ws(M, V, W);
+  const int64_t need = ea_ceva_sdecode_vocab_beam_c_ws(M, V, W, prompt_cap, max_new);
+  if (need >= 0 && ws_bytes < need) return EA_E_BADARG;
+  if (W > 32 || M % W || !dec_vocab_geometry_ok(M, K, V) || need < 0) return EA_E_UNSUPPORTED;
+  ea::DecLseP p = {};
+  dec_vocab_fill(&p, M, K, V, x, x_dtype, ldx, w, w_dtype, logits, EA_F32, ldl, ws);
+  ea::DecBeamP b = dec_beam_fill(M / W, W, 2 * W < V ? 2 * W : V, eos, max_new, score, t, nfin, done, token, parent, hist_tok,
+                                 hist_par, fin_score, fin_len, fin_beam, cand_idx, cand_score);
+  b.logits = logits; b.ldl = ldl; b.V = V; b.lse = lse; b.sel_val = sel_val;
+  ea::ceva_sdecode_vocab_beam_carve(ws, &p, &b);
+  ea::ceva_beam_bans_carve((char*)ws + base, M, &c);
+  p.token = token;                                        // (required by the block; the table pass does not write it)
+  return ea::ceva_sdecode_vocab_beam_c(p, b, c, (hipStream_t)stream);
 }
 
 // ---- the many-row vocabulary pass (ABI 30, ea_vocab_score.hip): the few-row entries' groups in their order -- the table
@@ -2740,6 +2816,44 @@ int ea_adaptive_beam(int32_t M, int32_t C, int32_t n_tails, const int64_t* cutof
   j.beam = dec_beam_fill(M / W, W, 2 * W < V ? 2 * W : (int)V, eos, max_new, score, t, nfin, done, token, parent, hist_tok,
                          hist_par, fin_score, fin_len, fin_beam, cand_idx, cand_score);
   return ea::adaptive_select(p, j, (hipStream_t)stream);
+}
+
+// ---- the constrained beam step from the adaptive head (ABI 36): ea_adaptive_beam's groups, then ea_ceva_sdecode_vocab_beam_c's
+// constraints ------------------------------------------------------------------------------------------------------------------
+int64_t ea_adaptive_beam_c_ws(int32_t M, int32_t n_tails, const int64_t* cutoffs, const int32_t* dims, int32_t W,
+                              int32_t prompt_cap, int32_t max_new) {
+  const int64_t base = ea_adaptive_beam_ws(M, n_tails, cutoffs, dims, W), more = ea::ceva_beam_bans_ws(M, prompt_cap, max_new);
+  return base < 0 || more < 0 ? -1 : base + more;
+}
+
+int ea_adaptive_beam_c(int32_t M, int32_t C, int32_t n_tails, const int64_t* cutoffs, const int32_t* dims, const void* x,
+                       int32_t x_dtype, int64_t ldx, const void* head, int32_t w_dtype, const void* const* proj,
+                       const void* const* tables, void* ws, int64_t ws_bytes, int32_t W, int32_t eos, int32_t max_new,
+                       float* score, int32_t* t, int32_t* nfin, int32_t* done, int64_t* token, int64_t* parent,
+                       int32_t* hist_tok, int32_t* hist_par, float* fin_score, int32_t* fin_len, int32_t* fin_beam,
+                       int32_t* cand_idx, float* cand_score, int32_t min_len, int32_t ngram, const int32_t* ban_tokens,
+                       int32_t n_ban_tokens, const int32_t* prompt_tok, int32_t prompt_cap, const int32_t* prompt_len,
+                       int32_t* gen, void* stream) {
+  if (const int rc = adp_operands_ok(M, C, n_tails, cutoffs, dims, x, x_dtype, ldx, head, w_dtype, proj, tables, ws)) return rc;
+  if (!dec_beam_ok(W, eos, max_new, score, t, nfin, done, token, parent, hist_tok, hist_par, fin_score, fin_len, fin_beam,
+                   cand_idx, cand_score, nullptr, nullptr) ||
+      (n_tails <= EA_ADAPTIVE_MAX_TAILS && eos >= cutoffs[n_tails])) return EA_E_BADARG;
+  ea::BeamBanP c;
+  if (const int rc = dec_bans_fill(&c, M / W, W, eos, max_new, n_tails <= EA_ADAPTIVE_MAX_TAILS ? cutoffs[n_tails] : -1, min_len,
+                                   ngram, ban_tokens, n_ban_tokens, prompt_tok, prompt_cap, prompt_len, t, done, hist_tok,
+                                   hist_par, gen)) return rc;
+  const int64_t more = ea::ceva_beam_bans_ws(M, prompt_cap, max_new);
+  if (more < 0) return EA_E_UNSUPPORTED;
+  if (const int rc = adp_select_geometry(M, C, n_tails, cutoffs, dims, W, ws_bytes - more)) return rc;
+  const int64_t base = ea::adaptive_select_plan(M, n_tails, cutoffs, dims, W, nullptr);
+  ea::AdaptivePickP p = adp_pick_fill(M, C, n_tails, cutoffs, dims, x, x_dtype, ldx, head, w_dtype, proj, tables, ws);
+  const int64_t V = cutoffs[n_tails];
+  ea::AdaptiveJointArgs j = {};
+  j.W = W;
+  j.beam = dec_beam_fill(M / W, W, 2 * W < V ? 2 * W : (int)V, eos, max_new, score, t, nfin, done, token, parent, hist_tok,
+                         hist_par, fin_score, fin_len, fin_beam, cand_idx, cand_score);
+  ea::ceva_beam_bans_carve((char*)ws + base, M, &c);
+  return ea::adaptive_select(p, j, (hipStream_t)stream, &c);
 }
 
 }  // extern "C"

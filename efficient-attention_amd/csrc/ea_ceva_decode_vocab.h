@@ -110,6 +110,44 @@ int ceva_sdecode_vocab_beam(const DecLseP& p, const DecBeamP& b, hipStream_t st)
 // the merge kernel alone, on the caller's candidate lists
 int ceva_beam_merge(const DecBeamP& b, hipStream_t st);
 
+// ---- the constrained beam step (ABI 36) ----
+constexpr int BAN_MAX_STATIC = 16;  // static bans of a capture
+constexpr int BAN_MAX_NGRAM = 16;   // no_repeat_ngram_size
+
+// the ban-list launch (beam_bans_kernel, one workgroup per row): it keeps the beams' generated tokens row-major in `gen` and
+// writes a row's banned tokens; a block of its own: DecBeamP stays what it is.  Row m = s W + b; t = t[s].
+struct BeamBanP {
+  const int32_t* t;           // [S] tokens generated (read, never written)
+  const int32_t* done;        // [S] the rows of a done sentence are skipped
+  const int32_t* hist_tok;    // [max_new, M] row t - 1 is read: what the previous merge wrote
+  const int32_t* hist_par;    // [max_new, M]
+  const int32_t* prompt_tok;  // [S, prompt_cap] (prompt_cap == 0: not read)
+  const int32_t* prompt_len;  // [S] clamped to 0 .. prompt_cap (prompt_cap == 0: not read)
+  int32_t* gen;               // [2, M, max_new] buffer t & 1 is written, buffer (t - 1) & 1 read
+  int32_t* ban;               // [M, cap] a row's banned tokens, duplicates allowed
+  int32_t* nban;              // [M] how many
+  int S, W, eos, max_new, min_len, ngram, prompt_cap, cap, n_static;
+  int32_t static_tok[BAN_MAX_STATIC];
+};
+
+// what the constrained row kernels read of it
+struct BanListP {
+  const int32_t* ban;         // [M, cap]
+  const int32_t* nban;        // [M]
+  int cap;
+};
+
+// entries of a row's list: prompt_cap + max_new windows at the most, the static bans and eos
+inline int64_t beam_ban_cap(int prompt_cap, int max_new) { return (int64_t)prompt_cap + max_new + BAN_MAX_STATIC + 1; }
+// bytes of ban and nban behind the unconstrained entry's workspace; < 0: outside the envelope
+int64_t ceva_beam_bans_ws(int M, int prompt_cap, int max_new);
+// b.ban, b.nban (and b.cap) from a buffer of that size
+void ceva_beam_bans_carve(void* ws, int M, BeamBanP* b);
+// the ban-list launch alone
+int ceva_beam_bans(const BeamBanP& b, hipStream_t st);
+// the table pass on p, the ban-list launch on c, the rows kernel with c's list applied behind lse, the merge on b
+int ceva_sdecode_vocab_beam_c(const DecLseP& p, const DecBeamP& b, const BeamBanP& c, hipStream_t st);
+
 // bytes of ws for (M, V); < 0: outside the envelope
 int64_t ceva_sdecode_vocab_ws(int M, int V);
 int ceva_sdecode_vocab_argmax(const DecVocabP& p, hipStream_t st);

@@ -158,6 +158,7 @@ __global__ __launch_bounds__(SMP_THREADS) void ceva_vocab_sample_kernel(const De
 // ---- the beam step (ABI 32) --------------------------------------------------------------------------------------------------
 // Two launches behind the table pass on DecLseP (fp32 logits, one candidate and one sum of exponentials per tile); the rule
 // is spelled out in include/ea_hip.h.  Row m = s W + b is beam b of sentence s.
+#include "ea_voc_ban.h"
 static_assert(PICK_THREADS == SMP_THREADS, "the beam step's row kernel runs the pick's and the sampler's helpers in one workgroup");
 constexpr int BEAM_MAX_W = 32;                            // 2 W <= VOC_SAMPLE_MAX_K: a row's candidates are one selection
 constexpr int BEAM_POOL = BEAM_MAX_W * VOC_SAMPLE_MAX_K;  // candidates of one sentence
@@ -166,11 +167,11 @@ static_assert(BEAM_POOL <= SMP_UNROLL * SMP_THREADS, "voc_threshold and voc_comp
 // One workgroup per row (rule A): lse[m] by ceva_vocab_pick_kernel<DecLseP>'s operations, the k' = min(2 W, V) best logits
 // by the sampler's steps 1-2 (the forced step: eos alone), and every candidate's score = score[m] + (value - lse[m]): two fp32
 // operations, no product anywhere near them.  The rows of a done sentence are skipped.
-__global__ __launch_bounds__(SMP_THREADS) void ceva_vocab_beam_rows_kernel(const DecBeamP p) {
-  __shared__ VocSelect sh;
-  __shared__ VocPick best[PICK_THREADS / 64];
-  __shared__ float part[PICK_THREADS / 64];
-  __shared__ float top_of_row, lse_of_row;
+// BANS (ABI 36): the row's ban list is applied behind lse and ahead of the selection (ea_voc_ban.h); the forced step's list
+// is empty.  The body of both kernels, inlined: the unconstrained one keeps its instructions.
+template <bool BANS>
+EA_DEV void beam_rows_body(const DecBeamP& p, const BanListP& c_list, VocSelect& sh, VocPick* best, float* part,
+                           float& top_of_row, float& lse_of_row) {
   const int m = blockIdx.x, s = m / p.W, lane = threadIdx.x & 63;
   if (p.done[s]) return;                                  // (uniform)
   const bool forced = p.t[s] + 1 >= p.max_new;
@@ -197,6 +198,10 @@ __global__ __launch_bounds__(SMP_THREADS) void ceva_vocab_beam_rows_kernel(const
     }
     return;
   }
+  if constexpr (BANS) {                                   // (this workgroup alone reads and writes the row from here on)
+    const int nb = min(max(c_list.nban[m], 0), c_list.cap);
+    voc_apply_bans(const_cast<float*>(lrow), const_cast<VocPick*>(cand), p.V, c_list.ban + (int64_t)m * c_list.cap, nb, 0);
+  }
   const int kk = voc_select(cand, lrow, p.V, NB, 2 * p.W, sh);
   if (threadIdx.x >= 64 || lane >= kk) return;
   const int32_t idx = min(max(voc_key_index(sh.sorted[lane]), 0), p.V - 1);   // (a column of the row, come what may)
@@ -204,6 +209,79 @@ __global__ __launch_bounds__(SMP_THREADS) void ceva_vocab_beam_rows_kernel(const
   p.cand_idx[at + lane] = idx;
   p.cand_score[at + lane] = score + (val - lse);
   if (p.sel_val) p.sel_val[at + lane] = val;
+}
+
+__global__ __launch_bounds__(SMP_THREADS) void ceva_vocab_beam_rows_kernel(const DecBeamP p) {
+  __shared__ VocSelect sh;
+  __shared__ VocPick best[PICK_THREADS / 64];
+  __shared__ float part[PICK_THREADS / 64];
+  __shared__ float top_of_row, lse_of_row;
+  beam_rows_body<false>(p, BanListP{}, sh, best, part, top_of_row, lse_of_row);
+}
+
+__global__ __launch_bounds__(SMP_THREADS) void ceva_vocab_beam_rows_c_kernel(const DecBeamP p, const BanListP c) {
+  __shared__ VocSelect sh;
+  __shared__ VocPick best[PICK_THREADS / 64];
+  __shared__ float part[PICK_THREADS / 64];
+  __shared__ float top_of_row, lse_of_row;
+  beam_rows_body<true>(p, c, sh, best, part, top_of_row, lse_of_row);
+}
+
+// ---- the ban-list launch (ABI 36) ------------------------------------------------------------------------------------------
+// One wave per row of a sentence that is not done; the rule is spelled out in include/ea_hip.h.  The row's tokens
+// x = prompt ++ generated are read where they lie: the prompt, the parent's row of buffer (t - 1) & 1 and the token the
+// previous merge wrote -- while the same lanes copy that row, with the token appended, into the row's own place in buffer
+// t & 1.  The list: the static bans, eos while t < min_len, then window i of x in lane i % 64, 64 at a time: a window that
+// equals the suffix lists the token behind it, at the slot a ballot counts out, so the list's order is fixed too.  The
+// forced step lists nothing.  A workgroup writes its own row alone; ordinary vector stores.
+constexpr int BAN_THREADS = 64;
+
+__global__ __launch_bounds__(BAN_THREADS) void beam_bans_kernel(const BeamBanP p) {
+  const int m = blockIdx.x, s = m / p.W, lane = threadIdx.x;
+  if (p.done[s]) return;                                  // (uniform)
+  const int M = p.S * p.W;
+  const int t = min(max(p.t[s], 0), p.max_new - 1);       // (otherwise only in a state no step of the merge leaves)
+  const int plen = p.prompt_cap > 0 ? min(max(p.prompt_len[s], 0), p.prompt_cap) : 0;
+  const int32_t* prompt = p.prompt_tok + (int64_t)s * p.prompt_cap;
+  int32_t* dst = p.gen + ((int64_t)(t & 1) * M + m) * p.max_new;
+  const int32_t* src = dst;
+  int32_t last = 0;
+  if (t >= 1) {
+    const int par = min(max(p.hist_par[(int64_t)(t - 1) * M + m], 0), p.W - 1);
+    src = p.gen + ((int64_t)((t - 1) & 1) * M + s * p.W + par) * p.max_new;
+    last = p.hist_tok[(int64_t)(t - 1) * M + m];
+    for (int j = lane; j < t - 1; j += BAN_THREADS) dst[j] = src[j];
+    if (lane == 0) dst[t - 1] = last;
+  }
+  const int L = plen + t;
+  auto x = [&](int i) { return i < plen ? prompt[i] : (i - plen < t - 1 ? src[i - plen] : last); };   // i < L
+  int32_t* ban = p.ban + (int64_t)m * p.cap;
+  int n = 0;                                              // (uniform)
+  if (t + 1 < p.max_new) {
+#pragma unroll
+    for (int j = 0; j < BAN_MAX_STATIC; ++j)
+      if (lane == j && j < p.n_static) ban[j] = p.static_tok[j];
+    n = min(p.n_static, BAN_MAX_STATIC);
+    if (t < p.min_len) {
+      if (lane == 0) ban[n] = p.eos;
+      ++n;
+    }
+    const int ng = p.ngram;
+    if (ng >= 1) {
+      const int suffix = L - ng + 1;                      // x[suffix .. L): the ng - 1 tokens a new one would follow
+      const uint64_t below = (1ull << lane) - 1ull;
+      for (int i0 = 0; i0 + ng <= L; i0 += BAN_THREADS) {  // windows i = 0 .. L - ng
+        const int i = i0 + lane;
+        bool hit = i + ng <= L;
+        for (int j = 0; j < ng - 1 && hit; ++j) hit = x(i + j) == x(suffix + j);
+        const uint64_t hits = __ballot(hit);
+        const int at = n + __popcll(hits & below);
+        if (hit && at < p.cap) ban[at] = x(i + ng - 1);
+        n += __popcll(hits);
+      }
+    }
+  }
+  if (lane == 0) p.nban[m] = min(n, p.cap);
 }
 
 // One workgroup per sentence (rules B and C): the sentence's W k' candidates (k' = kc; the forced step: 1) as keys -- the
@@ -405,6 +483,54 @@ int ceva_sdecode_vocab_beam(const DecLseP& p, const DecBeamP& b, hipStream_t st)
   if (!beam_envelope(p.M, b.W) || b.S * b.W != p.M || b.kc != (2 * b.W < p.V ? 2 * b.W : p.V)) return EA_E_UNSUPPORTED;
   int rc = voc_table_pass(p, 0, st);
   if (rc == 0) rc = voc_row_pass(ceva_vocab_beam_rows_kernel, SMP_THREADS, b, p.M, st);
+  return rc != 0 ? rc : voc_row_pass(ceva_vocab_beam_merge_kernel, SMP_THREADS, b, b.S, st);
+}
+
+// ---- the constrained beam step (ABI 36) ----
+int64_t ceva_beam_bans_ws(int M, int prompt_cap, int max_new) {
+  if (M < 1 || M > EA_CEVA_LINEAR_MAX_ROWS || prompt_cap < 0 || max_new < 1) return -1;
+  const int64_t cap = beam_ban_cap(prompt_cap, max_new);
+  if (cap > INT_MAX) return -1;
+  return beam_round16((int64_t)M * cap * 4) + beam_round16((int64_t)M * 4);
+}
+
+void ceva_beam_bans_carve(void* ws, int M, BeamBanP* b) {
+  b->cap = (int)beam_ban_cap(b->prompt_cap, b->max_new);
+  b->ban = (int32_t*)ws;
+  b->nban = (int32_t*)((char*)ws + beam_round16((int64_t)M * b->cap * 4));
+}
+
+static bool beam_bans_ok(const BeamBanP& c) {
+  if (!c.t || !c.done || !c.hist_tok || !c.hist_par || !c.gen || !c.ban || !c.nban || c.S < 1 || c.W < 1 || c.eos < 0 ||
+      c.max_new < 1 || c.prompt_cap < 0 || (c.prompt_cap > 0 && (!c.prompt_tok || !c.prompt_len))) return false;
+  if (c.min_len < 0 || c.min_len > c.max_new - 1 || c.ngram < 0 || c.ngram > BAN_MAX_NGRAM || c.n_static < 0 ||
+      c.n_static > BAN_MAX_STATIC || (int64_t)c.cap < beam_ban_cap(c.prompt_cap, c.max_new)) return false;
+  for (int j = 0; j < c.n_static; ++j)
+    if (c.static_tok[j] < 0 || c.static_tok[j] == c.eos) return false;
+  return true;
+}
+
+int ceva_beam_bans(const BeamBanP& c, hipStream_t st) {
+  if (!beam_bans_ok(c)) return EA_E_BADARG;
+  if (!beam_envelope(c.S * c.W, c.W)) return EA_E_UNSUPPORTED;
+  return voc_row_pass(beam_bans_kernel, BAN_THREADS, c, c.S * c.W, st);
+}
+
+int ceva_sdecode_vocab_beam_c(const DecLseP& p, const DecBeamP& b, const BeamBanP& c, hipStream_t st) {
+  if (b.W < 1 || !beam_state_ok(b) || !p.logits || !p.l_f32 || (const char*)b.logits != p.logits || b.ldl != p.ldl ||
+      b.ws != p.ws || b.lws != p.lws || !b.lse || b.V != p.V || b.eos >= p.V || p.targets || p.token_in) return EA_E_BADARG;
+  if (!beam_bans_ok(c) || c.S != b.S || c.W != b.W || c.eos != b.eos || c.max_new != b.max_new || c.t != b.t ||
+      c.done != b.done || c.hist_tok != b.hist_tok || c.hist_par != b.hist_par) return EA_E_BADARG;
+  for (int j = 0; j < c.n_static; ++j)
+    if (c.static_tok[j] >= p.V) return EA_E_BADARG;
+  if (!beam_envelope(p.M, b.W) || b.S * b.W != p.M || b.kc != (2 * b.W < p.V ? 2 * b.W : p.V)) return EA_E_UNSUPPORTED;
+  int rc = voc_table_pass(p, 0, st);
+  if (rc == 0) rc = voc_row_pass(beam_bans_kernel, BAN_THREADS, c, p.M, st);
+  if (rc == 0) {
+    const BanListP list = {c.ban, c.nban, c.cap};
+    hipLaunchKernelGGL(ceva_vocab_beam_rows_c_kernel, dim3((unsigned)p.M), dim3(SMP_THREADS), 0, st, b, list);
+    rc = (int)hipGetLastError();
+  }
   return rc != 0 ? rc : voc_row_pass(ceva_vocab_beam_merge_kernel, SMP_THREADS, b, b.S, st);
 }
 

@@ -13,8 +13,9 @@ static and rolling states: `init_decoding`, `decode`, `generate`; `next_tokens` 
 state holds (ea_ceva_sdecode_vocab_argmax), `init_sampling` / `sample_tokens` the sampled one (ea_ceva_sdecode_vocab_sample);
 `init_logprobs` / `token_logprobs` / `sample_tokens_logprobs` / `score` report a token's log-probability under the model's own
 distribution from the same pass over the table (ea_ceva_sdecode_vocab_logprob, ea_ceva_sdecode_vocab_sample_logprob);
-`init_beam_search` / `beam_step` / `beam_search` are a beam search whose step -- candidates, merge, finished hypotheses and the
-parent index of the state reorder -- runs on the device (ea_ceva_sdecode_vocab_beam).  On an adaptive stack
+`init_beam_search` / `set_beam_prompt` / `beam_step` / `beam_search` are a beam search whose step -- candidates, merge,
+finished hypotheses, the parent index of the state reorder, and min_len, n-gram blocking and static bans where asked for --
+runs on the device (ea_ceva_sdecode_vocab_beam, ea_ceva_sdecode_vocab_beam_c).  On an adaptive stack
 `init_adaptive_decoding` makes a state pick greedily, with log-probabilities, from the held adaptive tables
 (ea_adaptive_pick); on such a state `init_sampling` / `init_beam_search` sample and search from the adaptive head too
 (ea_adaptive_sample, ea_adaptive_beam).
@@ -790,7 +791,8 @@ class DecoderStack(nn.Module):
         `state.beam` (a Beam: the static buffers of the step, initialised; bytes: `decoding_state_nbytes`) and returns the
         state.  On a state with an adaptive pick (`init_adaptive_decoding`) the step is ea_adaptive_beam (ABI 35): a row's 2 W
         candidates are its best JOINT log-probabilities; the Beam's `ws` is that entry's workspace (it holds the bands'
-        fp32 logits, about 4 M V bytes) and `logits` is None."""
+        fp32 logits, about 4 M V bytes) and `logits` is None.  min_len, n-gram blocking and static bans:
+        `init_beam_constraints(state, ...)` behind this call."""
         if state.vocab is None and state.adaptive is None:
             raise RuntimeError("init_beam_search needs a decoding state that holds the vocabulary table: "
                                "init_decoding(..., hold_vocab=True)")
@@ -827,15 +829,99 @@ class DecoderStack(nn.Module):
                           buf((S, W), f32), buf((S, W), i32), buf((S, W), i32))
         return self.reset_beam_search(state)
 
+    def init_beam_constraints(self, state, *, min_len=0, no_repeat_ngram_size=0, ban_tokens=(), prompt_cap=0):
+        """Constrain the beam search of `state` (behind `init_beam_search`, at its start): fairseq's --min-len,
+        --no-repeat-ngram-size and its ban on pad, decided on the device inside the step (ABI 36, include/ea_hip.h has the
+        rule).  `min_len` (0 .. max_new - 1: no eos before that many tokens), `no_repeat_ngram_size` (0 .. 16: no n-gram of
+        prompt ++ generated tokens ends twice), `ban_tokens` (at most 16 ids in [0, V), eos not among them: never picked) and
+        `prompt_cap` (the longest prompt `set_beam_prompt` will be given: the prompt counts for the n-grams).  The forced step
+        (the max_new-th token) ignores them all.  Values outside the envelope raise ValueError before anything is allocated.
+        With all four at their defaults nothing is attached (a constraint the beam had is taken off) and the step is the
+        unconstrained entry: the state is what `init_beam_search` left.  Otherwise `state.beam.constraint` (a BeamConstraint)
+        holds the scalars with its buffers -- 4 S prompt_cap + 4 S bytes of prompt, 8 M max_new of generated tokens -- the
+        Beam's `ws` becomes the constrained entry's (the ban list behind the step's: 4 M (prompt_cap + max_new + 18) bytes
+        more, rounded), all counted by `decoding_state_nbytes`, and the step is ea_ceva_sdecode_vocab_beam_c /
+        ea_adaptive_beam_c.  Returns the state."""
+        bm = state.beam
+        if bm is None:
+            raise RuntimeError("init_beam_constraints needs a decoding state with a beam search: init_beam_search(state, ...)")
+        tables = None if state.adaptive is None else state.adaptive.tables
+        V = state.vocab.shape[0] if tables is None else tables.cutoff[-1]
+        W, eos, max_new, M = bm.beam_size, bm.eos_idx, bm.max_new, bm.score.numel()
+        min_len, ngram, prompt_cap = int(min_len), int(no_repeat_ngram_size), int(prompt_cap)
+        bans = tuple(int(v) for v in ban_tokens)
+        if not 0 <= min_len <= max_new - 1:
+            raise ValueError("min_len must be in 0 .. max_new - 1 = %d, got %d" % (max_new - 1, min_len))
+        if not 0 <= ngram <= tp.BAN_MAX_NGRAM:
+            raise ValueError("no_repeat_ngram_size must be in 0 .. %d, got %d" % (tp.BAN_MAX_NGRAM, ngram))
+        if len(bans) > tp.BAN_MAX_STATIC:
+            raise ValueError("at most %d ban_tokens, got %d" % (tp.BAN_MAX_STATIC, len(bans)))
+        for v in bans:
+            if not 0 <= v < V or v == eos:
+                raise ValueError("ban_tokens must lie in 0 .. %d and not hold eos_idx (%d), got %d" % (V - 1, eos, v))
+        if prompt_cap < 0:
+            raise ValueError("prompt_cap must be >= 0, got %d" % prompt_cap)
+        constrained = bool(min_len or ngram or bans or prompt_cap)
+        from efficient_attention import _native as nv
+        S, device = M // W, bm.score.device
+        if tables is None:
+            nbytes = nv.lib().ea_ceva_sdecode_vocab_beam_c_ws(M, V, W, prompt_cap, max_new) if constrained \
+                else nv.lib().ea_ceva_sdecode_vocab_beam_ws(M, V, W)
+        else:
+            geometry = (M, len(tables.dims), *tables.host_arrays()[:2], W)
+            nbytes = nv.lib().ea_adaptive_beam_c_ws(*geometry, prompt_cap, max_new) if constrained \
+                else nv.lib().ea_adaptive_beam_ws(*geometry)
+        if nbytes < 0:
+            raise ValueError("prompt_cap %d with max_new %d is outside the constrained step's envelope" % (prompt_cap, max_new))
+        i32 = torch.int32
+        bm.constraint = None
+        if constrained:
+            bm.constraint = tp.BeamConstraint(min_len, ngram, bans, prompt_cap,
+                                              torch.zeros((S, prompt_cap), dtype=i32, device=device) if prompt_cap else None,
+                                              torch.zeros(S, dtype=i32, device=device) if prompt_cap else None,
+                                              torch.zeros((2, M, max_new), dtype=i32, device=device))
+        if bm.ws.numel() != nbytes:
+            bm.ws = torch.empty(nbytes, dtype=torch.uint8, device=device)
+        return state
+
+    def set_beam_prompt(self, state, prompt, lengths=None):
+        """Tell a constrained beam search (`init_beam_constraints(state, ..., prompt_cap=P_max)`) the prompts its n-gram
+        blocking counts: prompt [S, P] int64 or int32 with P <= prompt_cap, one row per sentence; lengths: None (every prompt has P tokens) or
+        an integer [S] tensor of the prompts' lengths (right-padded rows; values are clamped to 0 .. P).  Device ops only; for
+        callers who run their own loop around `beam_step` -- `beam_search` does it itself.  Returns the state."""
+        bm = state.beam
+        if bm is None or bm.constraint is None:
+            raise RuntimeError("set_beam_prompt needs a beam search with constraints: init_beam_constraints(state, ..., prompt_cap=P)")
+        c, S = bm.constraint, bm.t.numel()
+        if prompt.dim() != 2 or prompt.shape[0] != S or prompt.dtype not in (torch.long, torch.int32):
+            raise ValueError("prompt must be an integer [%d, P] tensor, got %s %s" % (S, prompt.dtype, tuple(prompt.shape)))
+        P = prompt.shape[1]
+        if P > c.prompt_cap:
+            raise ValueError("a prompt of %d tokens on a beam search made with prompt_cap = %d" % (P, c.prompt_cap))
+        if lengths is not None and (tuple(lengths.shape) != (S,) or lengths.dtype.is_floating_point):
+            raise ValueError("lengths must be an integer [%d] tensor" % S)
+        if c.prompt_cap == 0:
+            return state
+        c.prompt_tok.zero_()
+        c.prompt_tok[:, :P].copy_(prompt)
+        if lengths is None:
+            c.prompt_len.fill_(P)
+        else:
+            c.prompt_len.copy_(lengths.clamp(0, P))
+        return state
+
     def reset_beam_search(self, state):
         """Back to the start of a search, in place and by device ops only: score 0 for beam 0 of every sentence and -inf for
-        the others, t = nfin = done = 0, the records and the history cleared.  (The attention's own state is the caller's.)"""
+        the others, t = nfin = done = 0, the records and the history cleared; a constraint's generated tokens are cleared and
+        its prompt is kept.  (The attention's own state is the caller's.)"""
         bm = state.beam
         if bm is None:
             raise RuntimeError("reset_beam_search needs a decoding state with a beam search: init_beam_search(state, ...)")
         bm.score.fill_(float("-inf")).view(-1, bm.beam_size)[:, 0].fill_(0.0)
         for t in (bm.t, bm.nfin, bm.done, bm.parent, bm.hist_tok, bm.hist_par, bm.fin_score, bm.fin_len, bm.fin_beam):
             t.zero_()
+        if bm.constraint is not None:                                        # (the prompt stays: `set_beam_prompt`)
+            bm.constraint.gen.zero_()
         return state
 
     def beam_step(self, rows, state, out=None, return_details=False):
@@ -885,8 +971,10 @@ class DecoderStack(nn.Module):
         `tokens` (int64 1-D, the closing eos included), `score` (raw_score / length ** len_penalty; ties by finishing order)
         and `raw_score` (an fp32 scalar tensor: the sum of the tokens' log-probabilities under the model's own distribution).
         At most beam_size per sentence; fewer where live beams ran out.  The rule -- fairseq's SequenceGenerator without
-        min_len, n-gram blocking, prefix tokens and match_source_len, with ties decided and a -inf-scored eos dropped -- is in
-        include/ea_hip.h (ABI 32).  On an adaptive stack the state carries an adaptive pick instead of a held table
+        prefix tokens and match_source_len, with ties decided and a -inf-scored eos dropped -- is in include/ea_hip.h (ABI 32).
+        min_len, n-gram blocking and static bans (fairseq's --min-len, --no-repeat-ngram-size and its ban on pad; ABI 36) are
+        `constrained_beam_search`'s keywords; this method runs them too on a state whose beam carries them
+        (`init_beam_constraints`, prompt_cap >= P): it sets the prompt itself.  On an adaptive stack the state carries an adaptive pick instead of a held table
         (`init_adaptive_decoding`; the default state is made so) and the step is ea_adaptive_beam (ABI 35).
         state: a fresh DecodingState of S beam_size rows made with hold_vocab=True (default: rolling, held weights, the
         autocast dtype, P + max_new tokens); one without a beam gets `init_beam_search(state, beam_size, eos_idx, max_new,
@@ -898,6 +986,26 @@ class DecoderStack(nn.Module):
         scratch beam buffers, captured, and replayed at most max_new - 1 times; every `poll` replays `done` is read back and
         the loop ends once every sentence is done.  graph=False runs the same steps eagerly: the same bits.  An overflow
         flagged by any layer raises after the loop."""
+        return self._beam_search(prompt, state, beam_size, eos_idx, max_new, len_penalty, graph, poll, None)
+
+    def constrained_beam_search(self, prompt, state=None, *, beam_size, eos_idx, max_new, len_penalty=1.0, graph=True, poll=16,
+                                min_len=0, no_repeat_ngram_size=0, ban_tokens=()):
+        """`beam_search` with fairseq's --min-len, --no-repeat-ngram-size and a list of tokens that are never picked (what
+        fairseq does to pad): see `init_beam_constraints` for the three and include/ea_hip.h (ABI 36) for the rule.  They are
+        decided on the device inside the step -- the captured step still replays without a host decision -- the prompt counts
+        for the n-grams, and the forced step (the max_new-th token) ignores them.  Not built: prefix tokens (the prompt is
+        prefilled) and match_source_len (no encoder).
+        A state without a beam gets `init_beam_search` and `init_beam_constraints(prompt_cap=P)`; one with a beam must have
+        been given the same values (and a prompt_cap >= P) and be at its start.  The prompt is set by this call: on a
+        per-sequence state a ragged, right-padded prompt counts up to its first pad, as the prefill reads it.  The warm-up's
+        scratch state gets the same constraints on buffers of its own.  With the three at their defaults this is `beam_search`.
+        Everything else -- arguments, result, graph and poll -- is `beam_search`'s."""
+        limits = (int(min_len), int(no_repeat_ngram_size), tuple(int(v) for v in ban_tokens))
+        return self._beam_search(prompt, state, beam_size, eos_idx, max_new, len_penalty, graph, poll, limits)
+
+    def _beam_search(self, prompt, state, beam_size, eos_idx, max_new, len_penalty, graph, poll, limits):
+        """The search behind `beam_search` (limits None: the constraints the state's beam carries, if any) and
+        `constrained_beam_search` (limits: (min_len, no_repeat_ngram_size, ban_tokens))."""
         if self.training:
             raise NotImplementedError("incremental decoding in training mode")
         S, P = prompt.shape
@@ -914,12 +1022,25 @@ class DecoderStack(nn.Module):
                     state = self.init_decoding(M, P + max(max_new, 1), dtype, prompt.device, hold_vocab=True)
             if state.beam is None:
                 self.init_beam_search(state, W, eos_idx, max_new, len_penalty)
+                if limits is not None and any(limits):
+                    self.init_beam_constraints(state, min_len=limits[0], no_repeat_ngram_size=limits[1], ban_tokens=limits[2],
+                                               prompt_cap=P)
             bm = state.beam
-            if (bm.beam_size, bm.eos_idx, bm.max_new, bm.len_penalty) != (W, int(eos_idx), max_new, float(len_penalty)):
-                raise ValueError("the state's beam search was made with (beam_size, eos_idx, max_new, len_penalty) = %r"
-                                 % ((bm.beam_size, bm.eos_idx, bm.max_new, bm.len_penalty),))
+            had = (0, 0, ()) if bm.constraint is None else bm.constraint.scalars()
+            made = (bm.beam_size, bm.eos_idx, bm.max_new, bm.len_penalty)
+            if made != (W, int(eos_idx), max_new, float(len_penalty)):
+                raise ValueError("the state's beam search was made with (beam_size, eos_idx, max_new, len_penalty) = %r" % (made,))
+            if limits is not None and had != limits:
+                raise ValueError("the state's beam search was made with (min_len, no_repeat_ngram_size, ban_tokens) = %r" % (had,))
             if M != bm.score.numel():
                 raise ValueError("a prompt of %d sentences at beam_size %d on a state of %d rows" % (S, W, bm.score.numel()))
+            if bm.constraint is not None:                                    # (ragged prompts: the lengths `_prefill` reads)
+                if P > bm.constraint.prompt_cap:
+                    raise ValueError("a prompt of %d tokens on a beam search made with prompt_cap = %d" % (P, bm.constraint.prompt_cap))
+                lengths = None
+                if state.options["per_sequence"]:
+                    lengths = P - prompt.eq(self.pad_idx).to(torch.int32).cumsum(1).ne(0).sum(1)
+                self.set_beam_prompt(state, prompt, lengths)
             prompt = prompt.repeat_interleave(W, 0)                          # [M, P]: row s W + b is beam b of sentence s
             tok_in, parent = self.beam_step(self._prefill(prompt, state), state)     # [1, M]: the step's static input
             self.reorder_decoding_state(state, parent)
@@ -931,7 +1052,15 @@ class DecoderStack(nn.Module):
             def scratch():                                                   # (the table is shared, the beam buffers are not)
                 st = self.init_decoding(**dict(state.options, max_tokens=1, hold_vocab=False))
                 st.vocab, st.vocab_ws, st.adaptive = state.vocab, state.vocab_ws, state.adaptive
-                return self.init_beam_search(st, W, eos_idx, max_new, len_penalty)
+                self.init_beam_search(st, W, eos_idx, max_new, len_penalty)
+                if bm.constraint is None:
+                    return st
+                self.init_beam_constraints(st, min_len=had[0], no_repeat_ngram_size=had[1], ban_tokens=had[2],
+                                           prompt_cap=bm.constraint.prompt_cap)
+                if bm.constraint.prompt_cap:                                 # (the same constraints, on its own buffers)
+                    st.beam.constraint.prompt_tok.copy_(bm.constraint.prompt_tok)
+                    st.beam.constraint.prompt_len.copy_(bm.constraint.prompt_len)
+                return st
 
             def each(i, _):
                 bm.replays = i

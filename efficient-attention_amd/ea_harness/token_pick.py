@@ -9,8 +9,8 @@
                       state has, so that the stack's four lifecycle methods name none of them.
   picks            -- one class per launch: `HeldGreedy` (ea_ceva_sdecode_vocab_argmax), `HeldSampled` (.._sample),
                       `HeldGreedyLogprob` (.._logprob), `HeldSampledLogprob` (.._sample_logprob), `AdaptiveGreedy`
-                      (ea_adaptive_pick), `AdaptiveSampled` (ea_adaptive_sample), `BeamStep` (.._beam), `AdaptiveBeamStep`
-                      (ea_adaptive_beam), and `FrameworkGreedy`, `logits(rows).argmax(-1)`.  `run` is the
+                      (ea_adaptive_pick), `AdaptiveSampled` (ea_adaptive_sample), `BeamStep` (.._beam; .._beam_c on a Beam with a constraint),
+                      `AdaptiveBeamStep` (ea_adaptive_beam, ea_adaptive_beam_c), and `FrameworkGreedy`, `logits(rows).argmax(-1)`.  `run` is the
                       launch behind the stack's public method of that mode; calling the pick, `pick(rows, out=None) -> tokens`,
                       is what a decoding loop does with it: `logp` is the [1, B] view of the static log-probability buffer the
                       call writes (None: the mode has none), `save()` / `restore(saved)` bracket a warm-up call (the sampler's
@@ -30,6 +30,10 @@ ADAPTIVE_PICK = "ea_adaptive_pick"
 BEAM = "ea_ceva_sdecode_vocab_beam"
 ADAPTIVE_SAMPLE = "ea_adaptive_sample"
 ADAPTIVE_BEAM = "ea_adaptive_beam"
+BEAM_C = "ea_ceva_sdecode_vocab_beam_c"
+ADAPTIVE_BEAM_C = "ea_adaptive_beam_c"
+BAN_MAX_STATIC = 16          # static bans and the largest no_repeat_ngram_size of the constrained beam step (ABI 36)
+BAN_MAX_NGRAM = 16
 
 
 def _native():
@@ -253,16 +257,43 @@ class AdaptivePick(Attachment):
         self.tables.refresh()
 
 
+class BeamConstraint:
+    """What `DecoderStack.init_beam_constraints` hangs on a Beam when it is given min_len, no_repeat_ngram_size, ban_tokens or
+    prompt_cap (include/ea_hip.h, ABI 36): those host scalars and the static buffers of the constrained entries --
+    `prompt_tok` int32 [S, prompt_cap] and `prompt_len` int32 [S] (`set_beam_prompt`; both None at prompt_cap = 0) and `gen`
+    int32 [2, M, max_new], the beams' generated tokens, row-major, a ping-pong pair the ban-list launch keeps.  The ban list
+    itself lies behind the step's workspace in the Beam's `ws`."""
+
+    def __init__(self, min_len, ngram, ban_tokens, prompt_cap, prompt_tok, prompt_len, gen):
+        self.min_len, self.ngram, self.ban_tokens, self.prompt_cap = min_len, ngram, ban_tokens, prompt_cap
+        self.prompt_tok, self.prompt_len, self.gen = prompt_tok, prompt_len, gen
+
+    def tensors(self):
+        return tuple(t for t in (self.prompt_tok, self.prompt_len, self.gen) if t is not None)
+
+    def scalars(self):
+        return (self.min_len, self.ngram, self.ban_tokens)
+
+    def arguments(self, nv):
+        """The constrained entries' arguments behind the unconstrained ones'."""
+        bans = nv.host_array(ctypes.c_int32, list(self.ban_tokens)) if self.ban_tokens else None
+        return [self.min_len, self.ngram, bans, len(self.ban_tokens), nv.ptr(self.prompt_tok), self.prompt_cap,
+                nv.ptr(self.prompt_len), nv.ptr(self.gen)]
+
+
 class Beam(Attachment):
     """What `DecoderStack.init_beam_search` attaches to a DecodingState: the host scalars `beam_size` (W), `eos_idx`,
     `max_new`, `len_penalty` and the static buffers of ea_ceva_sdecode_vocab_beam (include/ea_hip.h, ABI 32) for M = the
     state's batch size = S W rows: `logits` fp32 [M, V], `ws` (the entry's workspace, bytes), `score` fp32 [M], `t`, `nfin`,
     `done` int32 [S], `parent` int64 [M], `hist_tok`, `hist_par` int32 [max_new, M], `fin_score` fp32 [S, W], `fin_len`,
     `fin_beam` int32 [S, W].  `replays`: how many steps behind the first pick the last `beam_search` on it ran.
-    On a state with an adaptive pick `logits` is None and `ws` is ea_adaptive_beam's workspace (it holds the bands' logits)."""
+    On a state with an adaptive pick `logits` is None and `ws` is ea_adaptive_beam's workspace (it holds the bands' logits).
+    `constraint`: None, or the BeamConstraint of a search with min_len, n-gram blocking or static bans (ABI 36); `ws` is then
+    the constrained entry's workspace."""
 
     def __init__(self, beam_size, eos_idx, max_new, len_penalty, logits, ws, score, t, nfin, done, parent, hist_tok, hist_par,
-                 fin_score, fin_len, fin_beam):
+                 fin_score, fin_len, fin_beam, constraint=None):
+        self.constraint = constraint
         self.beam_size, self.eos_idx, self.max_new, self.len_penalty = beam_size, eos_idx, max_new, len_penalty
         self.logits, self.ws, self.score, self.t, self.nfin, self.done, self.parent = logits, ws, score, t, nfin, done, parent
         self.hist_tok, self.hist_par = hist_tok, hist_par
@@ -271,7 +302,8 @@ class Beam(Attachment):
 
     def buffers(self):
         return tuple(t for t in (self.logits, self.ws, self.score, self.t, self.nfin, self.done, self.parent, self.hist_tok,
-                                 self.hist_par, self.fin_score, self.fin_len, self.fin_beam) if t is not None)
+                                 self.hist_par, self.fin_score, self.fin_len, self.fin_beam) if t is not None) \
+            + (() if self.constraint is None else self.constraint.tensors())
 
     tensors = buffers
 
@@ -566,10 +598,13 @@ class BeamStep(Pick):
             details = (torch.empty((M, 2 * W), dtype=torch.int32, device=dev),
                        torch.empty((M, 2 * W), dtype=torch.float32, device=dev),
                        torch.empty((M,), dtype=torch.float32, device=dev))
-        nv.call(BEAM, M, C, V, nv.ptr(x2), type_code(x2), C, nv.ptr(table), nv.io_dtype(table), nv.ptr(bm.logits), V,
+        c = bm.constraint
+        nv.call(BEAM if c is None else BEAM_C, M, C, V, nv.ptr(x2), type_code(x2), C, nv.ptr(table), nv.io_dtype(table),
+                nv.ptr(bm.logits), V,
                 nv.ptr(bm.ws), bm.ws.numel(), W, bm.eos_idx, bm.max_new, nv.ptr(bm.score), nv.ptr(bm.t), nv.ptr(bm.nfin),
                 nv.ptr(bm.done), nv.ptr(out), nv.ptr(bm.parent), nv.ptr(bm.hist_tok), nv.ptr(bm.hist_par), nv.ptr(bm.fin_score),
-                nv.ptr(bm.fin_len), nv.ptr(bm.fin_beam), *_ptr_or_none(nv, details), None, nv.stream())
+                nv.ptr(bm.fin_len), nv.ptr(bm.fin_beam), *_ptr_or_none(nv, details), None,
+                *(() if c is None else c.arguments(nv)), nv.stream())
         return (out, bm.parent) + details if return_details else (out, bm.parent)
 
 
@@ -589,8 +624,11 @@ class AdaptiveBeamStep(Pick):
             details = (torch.empty((M, 2 * W), dtype=torch.int32, device=dev),
                        torch.empty((M, 2 * W), dtype=torch.float32, device=dev))
         cut, dims, proj, tabs = tb.host_arrays()
-        nv.call(ADAPTIVE_BEAM, M, C, n, cut, dims, nv.ptr(x2), type_code(x2), C, nv.ptr(tb.head), nv.io_dtype(tb.head), proj, tabs,
+        c = bm.constraint
+        nv.call(ADAPTIVE_BEAM if c is None else ADAPTIVE_BEAM_C, M, C, n, cut, dims, nv.ptr(x2), type_code(x2), C, nv.ptr(tb.head),
+                nv.io_dtype(tb.head), proj, tabs,
                 nv.ptr(bm.ws), bm.ws.numel(), W, bm.eos_idx, bm.max_new, nv.ptr(bm.score), nv.ptr(bm.t), nv.ptr(bm.nfin),
                 nv.ptr(bm.done), nv.ptr(out), nv.ptr(bm.parent), nv.ptr(bm.hist_tok), nv.ptr(bm.hist_par), nv.ptr(bm.fin_score),
-                nv.ptr(bm.fin_len), nv.ptr(bm.fin_beam), *(_ptr_or_none(nv, details)[:2]), nv.stream())
+                nv.ptr(bm.fin_len), nv.ptr(bm.fin_beam), *(_ptr_or_none(nv, details)[:2]),
+                *(() if c is None else c.arguments(nv)), nv.stream())
         return (out, bm.parent) + details if return_details else (out, bm.parent)

@@ -22,7 +22,7 @@ class ea_t4(ctypes.Structure):
                 ("sn", ctypes.c_int64)]
 
 
-ABI_VERSION = 35         # ea_abi_version() of include/ea_hip.h this file mirrors
+ABI_VERSION = 36         # ea_abi_version() of include/ea_hip.h this file mirrors
 
 
 class ea_geom(ctypes.Structure):
@@ -287,6 +287,13 @@ SIGNATURES = {
     "ea_adaptive_beam_ws": [_I, _I, _P, _P, _I],
     "ea_adaptive_beam": [_I, _I, _I, _P, _P, _P, _I, _L, _P, _I, _P, _P, _P, _L, _I, _I, _I, _P, _P, _P, _P, _P, _P, _P, _P, _P,
                          _P, _P, _P, _P, _P],
+    "ea_beam_bans": [_I, _I, _I, _I, _I, _I, _P, _I, _P, _I, _P, _P, _P, _P, _P, _P, _P, _I, _P, _P],
+    "ea_ceva_sdecode_vocab_beam_c_ws": [_I, _I, _I, _I, _I],
+    "ea_ceva_sdecode_vocab_beam_c": [_I, _I, _I, _P, _I, _L, _P, _I, _P, _L, _P, _L, _I, _I, _I, _P, _P, _P, _P, _P, _P, _P, _P,
+                                     _P, _P, _P, _P, _P, _P, _P, _I, _I, _P, _I, _P, _I, _P, _P, _P],
+    "ea_adaptive_beam_c_ws": [_I, _I, _P, _P, _I, _I, _I],
+    "ea_adaptive_beam_c": [_I, _I, _I, _P, _P, _P, _I, _L, _P, _I, _P, _P, _P, _L, _I, _I, _I, _P, _P, _P, _P, _P, _P, _P, _P, _P,
+                           _P, _P, _P, _P, _I, _I, _P, _I, _P, _I, _P, _P, _P],
     "ea_softmax_attn_fwd": [_I, _I, _I, _I, _I, _F, _T, _T, _T, _P, _T, _P, _P, _F, _I, _P],
     "ea_softmax_sample": [_I, _I, _I, _I, _I, _F, _T, _T, _P, _P, _P],
     "ea_softmax_attn_bwd": [_I, _I, _I, _I, _I, _F, _T, _T, _T, _P, _T, _T, _P, _P, _T, _T, _T, _P, _F, _I, _P],
@@ -326,6 +333,8 @@ def lib():
         cdll.ea_adaptive_pick_ws.restype = ctypes.c_int64
         cdll.ea_adaptive_sample_ws.restype = ctypes.c_int64
         cdll.ea_adaptive_beam_ws.restype = ctypes.c_int64
+        cdll.ea_ceva_sdecode_vocab_beam_c_ws.restype = ctypes.c_int64
+        cdll.ea_adaptive_beam_c_ws.restype = ctypes.c_int64
         cdll.ea_version.restype = ctypes.c_char_p
         cdll.ea_abi_version.restype = ctypes.c_int32
         if cdll.ea_abi_version() != ABI_VERSION:

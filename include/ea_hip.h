@@ -1499,6 +1499,77 @@ int ea_adaptive_beam(int32_t M, int32_t C, int32_t n_tails, const int64_t* cutof
                      int32_t* hist_tok, int32_t* hist_par, float* fin_score, int32_t* fin_len, int32_t* fin_beam,
                      int32_t* cand_idx, float* cand_score, void* stream);
 
+/* ABI 36, THE CONSTRAINED BEAM STEP: min_len, n-gram blocking and static bans in the beam step of both heads (ea_harness
+ * DecoderStack.init_beam_constraints, set_beam_prompt, constrained_beam_search; beam_search on a state that carries them;
+ * ea_ceva_decode_vocab.hip, ea_voc_ban.h, ea_adaptive_pick.hip).  fairseq's SequenceGenerator options --min-len and
+ * --no-repeat-ngram-size and its ban on pad, decided on the device from state the captured step already carries.
+ * THE RULE, for row m of sentence s at t = t[s], the sentence not done and the step not the forced one (t + 1 < max_new):
+ *   the row's sequence is x = prompt_s[0 .. plen_s) ++ g_m[0 .. t), L = plen_s + t tokens: the prompt counts (in fairseq's
+ *   language-model generation the prompt is part of `tokens`), g_m are the tokens this beam has generated;
+ *   its banned set is the union of
+ *     the static bans   ban_tokens[0 .. n_ban_tokens), at most 16 host scalars a capture fixes, none of them eos;
+ *     minimum length    eos, while t < min_len: a finished hypothesis has at least min_len tokens before its eos;
+ *     n-gram blocking   n = ngram >= 1: for every i in 0 .. L - n (none when L < n) with x[i .. i + n - 1) == x[L - n + 1 .. L),
+ *                       the token x[i + n - 1]; n = 1 bans every token of x.  NGramRepeatBlock._no_repeat_ngram of fairseq,
+ *                       position for position.
+ *   lse[m] (the adaptive head: every band's) comes from the UNCONSTRAINED logits, by the unconstrained entry's operations: the
+ *   same bits (fairseq bans after log_softmax).  The row's k' = min(2 W, V) candidates are its best logits (joint scores) with
+ *   every banned column at -inf; the total order is unchanged, ties to the lower index.  With fewer than k' columns unbanned
+ *   a banned one is selected, with score -inf; rule B drops an eos whose score is -inf.
+ *   THE FORCED STEP IGNORES EVERY CONSTRAINT: eos alone, as in ABI 32 -- a departure from fairseq, the only way the length
+ *   cap and a ban on eos both hold.  Rules B and C, the records, the history and the host's backtracking are ABI 32's.
+ * Not built: prefix_tokens (the prompt is prefilled), match_source_len (no encoder), unk_penalty.
+ * LAUNCHES: the unconstrained entry's, one more (the ban list), and the constrained instance of the row kernel:
+ *   ea_beam_bans, one wave per row of a sentence that is not done.  gen int32 [2, M, max_new] holds the beams' generated tokens
+ *   row-major, a ping-pong pair: at t >= 1 row m copies gen[(t - 1) & 1][s W + hist_par[t - 1, m]][0 .. t - 1) into
+ *   gen[t & 1][m] and appends hist_tok[t - 1, m] (what the previous merge wrote); nobody walks hist_par back t steps.  In the
+ *   same pass it writes the row's banned tokens into ban[m, 0 .. nban[m]) (int32 [M, cap], cap >= prompt_cap + max_new + 17;
+ *   duplicates allowed; the static bans, eos, then the n-gram bans by window position): every window yields at most one
+ *   entry, so the list cannot overflow.  The forced step writes nban[m] = 0.  prompt_tok int32 [S, prompt_cap], prompt_len
+ *   int32 [S] (clamped to 0 .. prompt_cap; both unread at prompt_cap = 0).  A workgroup writes its own row of buffer t & 1
+ *   and of ban / nban alone and reads buffer (t - 1) & 1: no atomics on memory, no workgroup waits for another, the list's
+ *   order is fixed: bitwise reproducible.  gen need not be cleared: entries from t on are never read.
+ *   Plain head (ea_ceva_sdecode_vocab_beam_c): launch A with the list applied behind lse[m] and ahead of the selection: -inf
+ *   is stored into logits[m, v] for every listed v < V, then every such v's tile candidate is formed again, the best of the
+ *   tile's stored logits below V under the pick's order.  AFTER THE CALL logits [M, ldl] HOLDS -inf AT THE BANNED COLUMNS of
+ *   the rows of live sentences (not on the forced step).
+ *   Adaptive head (ea_adaptive_beam_c): launch 5 of ABI 35 with the listed tokens that fall in band b applied to that band's
+ *   stored logits and tile candidates, behind the band's fold; class columns are never banned; launch 6 re-reads the stored
+ *   logits, so a banned pick scores -inf there.  ea_adaptive_sample and the unconstrained entries launch what they launched.
+ * ARGUMENTS: the unconstrained entry's, then min_len, ngram, ban_tokens (host, NULL at n_ban_tokens = 0), n_ban_tokens,
+ * prompt_tok, prompt_cap, prompt_len, gen.  ws: the unconstrained entry's workspace from byte 0, then ban r16(4 M cap) and nban
+ * r16(4 M), cap = prompt_cap + max_new + 17: the _c_ws queries; < 0 where the unconstrained query is, and for prompt_cap < 0 or
+ * max_new < 1.  The ban list can later serve the greedy and the sampled pick too: it is a launch of its own.
+ * EA_E_BADARG: what the unconstrained entry answers with it; min_len outside 0 .. max_new - 1; ngram outside 0 .. 16;
+ * n_ban_tokens outside 0 .. 16, a static ban outside [0, V) (ea_beam_bans: < 0) or equal to eos; prompt_cap < 0; prompt_tok or
+ * prompt_len NULL at prompt_cap > 0; gen NULL; one of them not 4-byte aligned; ea_beam_bans: cap below prompt_cap + max_new + 17,
+ * S < 1, W < 1, eos < 0, a NULL or misaligned pointer.  EA_E_UNSUPPORTED: the unconstrained entry's refusals.  Bad arguments
+ * are decided before the geometry, everything before any launch.  prompt_len[s] <= prompt_cap is the caller's promise; the
+ * kernel clamps it. */
+int ea_beam_bans(int32_t S, int32_t W, int32_t eos, int32_t max_new, int32_t min_len, int32_t ngram, const int32_t* ban_tokens,
+                 int32_t n_ban_tokens, const int32_t* prompt_tok, int32_t prompt_cap, const int32_t* prompt_len,
+                 const int32_t* t, const int32_t* done, const int32_t* hist_tok, const int32_t* hist_par, int32_t* gen,
+                 int32_t* ban, int32_t cap, int32_t* nban, void* stream);
+int64_t ea_ceva_sdecode_vocab_beam_c_ws(int32_t M, int32_t V, int32_t W, int32_t prompt_cap, int32_t max_new);
+int ea_ceva_sdecode_vocab_beam_c(int32_t M, int32_t K, int32_t V, const void* x, int32_t x_dtype, int64_t ldx,
+                                 const void* w, int32_t w_dtype, float* logits, int64_t ldl, void* ws, int64_t ws_bytes,
+                                 int32_t W, int32_t eos, int32_t max_new, float* score, int32_t* t, int32_t* nfin,
+                                 int32_t* done, int64_t* token, int64_t* parent, int32_t* hist_tok, int32_t* hist_par,
+                                 float* fin_score, int32_t* fin_len, int32_t* fin_beam, int32_t* cand_idx, float* cand_score,
+                                 float* lse, float* sel_val, int32_t min_len, int32_t ngram, const int32_t* ban_tokens,
+                                 int32_t n_ban_tokens, const int32_t* prompt_tok, int32_t prompt_cap,
+                                 const int32_t* prompt_len, int32_t* gen, void* stream);
+int64_t ea_adaptive_beam_c_ws(int32_t M, int32_t n_tails, const int64_t* cutoffs, const int32_t* dims, int32_t W,
+                              int32_t prompt_cap, int32_t max_new);
+int ea_adaptive_beam_c(int32_t M, int32_t C, int32_t n_tails, const int64_t* cutoffs, const int32_t* dims, const void* x,
+                       int32_t x_dtype, int64_t ldx, const void* head, int32_t w_dtype, const void* const* proj,
+                       const void* const* tables, void* ws, int64_t ws_bytes, int32_t W, int32_t eos, int32_t max_new,
+                       float* score, int32_t* t, int32_t* nfin, int32_t* done, int64_t* token, int64_t* parent,
+                       int32_t* hist_tok, int32_t* hist_par, float* fin_score, int32_t* fin_len, int32_t* fin_beam,
+                       int32_t* cand_idx, float* cand_score, int32_t min_len, int32_t ngram, const int32_t* ban_tokens,
+                       int32_t n_ban_tokens, const int32_t* prompt_tok, int32_t prompt_cap, const int32_t* prompt_len,
+                       int32_t* gen, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
