@@ -41,7 +41,7 @@ static Geo mk_geo(const ea_geom* g) {
 extern "C" {
 
 const char* ea_version(void) { return "ea_hip 0.1.0 gfx950"; }
-int32_t ea_abi_version(void) { return 36; }
+int32_t ea_abi_version(void) { return 37; }
 
 int32_t ea_window_bias_ld(const ea_geom* g) {
   WinTiling t;
@@ -540,6 +540,14 @@ int ea_softmax_sample(int32_t B, int32_t H, int32_t N, int32_t D, int32_t dtype,
   p.seed = reinterpret_cast<const unsigned long long*>(seed);
   p.sample_out = reinterpret_cast<long long*>(index);
   return softmax_dispatch(2, p, dtype, D, (hipStream_t)stream);
+}
+
+int32_t ea_softmax_tiles(int32_t which, int32_t B, int32_t H, int32_t N, int32_t D, int32_t has_keep, int32_t cus) {
+  SmP p = {};
+  int rc = fill_sm(B, H, N, D, EA_BF16, 1.f, p);          // (the rule does not depend on the I/O type)
+  if (rc != EA_OK) return rc;
+  if ((which != 0 && which != 1) || cus < 0) return EA_E_BADARG;
+  return softmax_tiles(which, (long)B * H, N, D, has_keep != 0, cus > 0 ? cus : ea_device_cus());
 }
 
 }  // extern "C"

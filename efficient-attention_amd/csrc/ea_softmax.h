@@ -27,4 +27,11 @@ struct SmP {
 
 int softmax_dispatch(int which, const SmP& p, int dtype, int D, hipStream_t st);
 
+// The 16-token tiles a wave of the softmax kernels works on (QT of sm_fwd_kernel / sm_bwd_dq_kernel, KT of sm_bwd_dkv_kernel)
+// for bh = B H sequences of N tokens at head size D on a device of `cus` compute units; which: 0 forward (1, 2 or 4),
+// 1 backward (1 or 2; both backward kernels); has_keep: a dropout keep mask is passed.  The one statement of the rule:
+// launch_sm_dr launches what it answers, ea_softmax_tiles (C ABI) reports it.  Pure but for the dev knobs EA_SM_QT (forward)
+// and EA_SM_BQT (backward), read once per process; a knob value that is no tile count of that direction is ignored.
+int softmax_tiles(int which, long bh, int N, int D, bool has_keep, int cus);
+
 }  // namespace ea

@@ -701,29 +701,35 @@ static int launch_sample(const SmP& p, hipStream_t st) {
   return (int)hipGetLastError();
 }
 
-template <typename E, int D, bool DR, bool KB>
-static int launch_sm_dr(int which, const SmP& p, hipStream_t st) {
-  const dim3 grid((unsigned)((long)p.B * p.H * ((p.N + 63) / 64))), block(256);
+int softmax_tiles(int which, long bh, int N, int D, bool has_keep, int cus) {
   if (which == 0) {
     // two (D <= 64: four) query tiles per wave whenever that still leaves every CU a few workgroups
-    const long bh = (long)p.B * p.H;
-    static const int qt_env = [] { const char* e = getenv("EA_SM_QT"); return e ? atoi(e) : 0; }();   // dev knob
+    static const int qt_env = [] { const int e = ea_env_int("EA_SM_QT", 0); return (e == 1 || e == 2 || e == 4) ? e : 0; }();   // dev knob
     int qt = 1;
-    if (bh * ((p.N + 127) / 128) >= 2 * ea_device_cus()) qt = 2;
-    if (D <= 64 && bh * ((p.N + 255) / 256) >= 2 * ea_device_cus()) qt = 4;
+    if (bh * ((N + 127) / 128) >= 2 * cus) qt = 2;
+    if (D <= 64 && bh * ((N + 255) / 256) >= 2 * cus) qt = 4;
     if (qt_env > 0) qt = qt_env;
-    if ((D > 64 || DR) && qt > 2) qt = 2;              // (with the keep-mask reads four query tiles do not fit 256 VGPRs)
-    const dim3 gq((unsigned)(bh * ((p.N + 64 * qt - 1) / (64 * qt))));
+    if ((D > 64 || has_keep) && qt > 2) qt = 2;        // (with the keep-mask reads four query tiles do not fit 256 VGPRs)
+    return qt;
+  }
+  static const int qt_env = [] { const int e = ea_env_int("EA_SM_BQT", 0); return (e == 1 || e == 2) ? e : 0; }();   // dev knob
+  int qt = (D <= 64 && bh * ((N + 127) / 128) >= 2 * cus) ? 2 : 1;
+  if (qt_env > 0) qt = qt_env;
+  if (D > 64) qt = 1;
+  return qt;
+}
+
+template <typename E, int D, bool DR, bool KB>
+static int launch_sm_dr(int which, const SmP& p, hipStream_t st) {
+  const dim3 block(256);
+  const long bh = (long)p.B * p.H;
+  const int qt = softmax_tiles(which, bh, p.N, D, DR, ea_device_cus());
+  const dim3 gq((unsigned)(bh * ((p.N + 64 * qt - 1) / (64 * qt))));
+  if (which == 0) {
     if (qt == 4) { if constexpr (D <= 64 && !DR) hipLaunchKernelGGL((sm_fwd_kernel<E, D, DR, KB, 4>), gq, block, 0, st, p); }
     else if (qt == 2) hipLaunchKernelGGL((sm_fwd_kernel<E, D, DR, KB, 2>), gq, block, 0, st, p);
     else hipLaunchKernelGGL((sm_fwd_kernel<E, D, DR, KB, 1>), gq, block, 0, st, p);
   } else {
-    const long bh = (long)p.B * p.H;
-    static const int qt_env = [] { const char* e = getenv("EA_SM_BQT"); return e ? atoi(e) : 0; }();   // dev knob
-    int qt = (D <= 64 && bh * ((p.N + 127) / 128) >= 2 * ea_device_cus()) ? 2 : 1;
-    if (qt_env > 0) qt = qt_env;
-    if (D > 64) qt = 1;
-    const dim3 gq((unsigned)(bh * ((p.N + 64 * qt - 1) / (64 * qt))));
     if (qt == 2) { if constexpr (D <= 64) hipLaunchKernelGGL((sm_bwd_dq_kernel<E, D, DR, KB, 2>), gq, block, 0, st, p); }
     else hipLaunchKernelGGL((sm_bwd_dq_kernel<E, D, DR, KB, 1>), gq, block, 0, st, p);
     if (qt == 2) { if constexpr (D <= 64) hipLaunchKernelGGL((sm_bwd_dkv_kernel<E, D, DR, KB, 2>), gq, block, 0, st, p); }

@@ -22,7 +22,7 @@ class ea_t4(ctypes.Structure):
                 ("sn", ctypes.c_int64)]
 
 
-ABI_VERSION = 36         # ea_abi_version() of include/ea_hip.h this file mirrors
+ABI_VERSION = 37         # ea_abi_version() of include/ea_hip.h this file mirrors
 
 
 class ea_geom(ctypes.Structure):
@@ -296,6 +296,7 @@ SIGNATURES = {
                            _P, _P, _P, _P, _I, _I, _P, _I, _P, _I, _P, _P, _P],
     "ea_softmax_attn_fwd": [_I, _I, _I, _I, _I, _F, _T, _T, _T, _P, _T, _P, _P, _F, _I, _P],
     "ea_softmax_sample": [_I, _I, _I, _I, _I, _F, _T, _T, _P, _P, _P],
+    "ea_softmax_tiles": [_I, _I, _I, _I, _I, _I, _I],
     "ea_softmax_attn_bwd": [_I, _I, _I, _I, _I, _F, _T, _T, _T, _P, _T, _T, _P, _P, _T, _T, _T, _P, _F, _I, _P],
     "ea_window_bias_ld": [_G],
     "ea_window_bwd_parts": [_G],

@@ -249,6 +249,18 @@ int ea_softmax_attn_bwd(int32_t B, int32_t H, int32_t N, int32_t D, int32_t dtyp
                         const ea_t4* out, const ea_t4* dout, const float* lse, float* delta,
                         const ea_t4* dq, const ea_t4* dk, const ea_t4* dv,
                         const uint8_t* keep, float keep_scale, int32_t key_norm_bias, void* stream);
+/* ABI 37.  The 16-token tiles per wave (QT) the softmax launcher uses: which 0 = forward (1, 2 or 4 query tiles), 1 = backward
+ * (1 or 2; the dQ pass and the dK/dV pass use the same count); has_keep: a keep mask is passed; cus > 0: for a device of that
+ * many compute units (pure, runs without a GPU); cus = 0: the current device's.  The launcher calls the same function, so
+ * what this answers is what runs:
+ *   forward   4 if D <= 64 and B H ceil(N / 256) >= 2 cus; else 2 if B H ceil(N / 128) >= 2 cus; else 1; at most 2 when
+ *             D > 64 or a keep mask is passed
+ *   backward  2 if D <= 64 and B H ceil(N / 128) >= 2 cus; else 1
+ * The dev knobs EA_SM_QT (forward: 1, 2 or 4) and EA_SM_BQT (backward: 1 or 2), read once per process, replace the count
+ * before the clamps for D > 64 and the keep mask; any other value of a knob is ignored.
+ * -> 1, 2 or 4, or a negative EA_E* code for a geometry ea_softmax_attn_fwd refuses (B, H, N <= 0, D not 32 / 64 / 128) and
+ * for which not 0 / 1 or cus < 0. */
+int32_t ea_softmax_tiles(int32_t which, int32_t B, int32_t H, int32_t N, int32_t D, int32_t has_keep, int32_t cus);
 /* Randomized attention (randomized_attention.py:21-52) is two passes of the kernels above:
  *   mu = q + softmax(s q k^T) k (num_samples = -1) or q + k[index] with one index per query drawn
  *   from softmax(s q k^T) (ea_softmax_sample: Gumbel-max with counter-based noise from the 64-bit
