@@ -7,7 +7,8 @@
 //
 // Decomposition: token slices x output tiles.  A workgroup owns a [BM out x 64 in] tile of dW for one
 // token slice and streams its slice of dY[:, BM] and X[:, 64] through LDS in 64-token stages (double
-// buffered: the next stage's global loads are in flight during the MFMAs, one barrier per stage).  Both
+// buffered: the next stage's global loads are in flight during the MFMAs -- the next two stages' in the
+// [192 x 192] tile, wgrad_stages_of -- one barrier per stage).  Both
 // MFMA operands are token-contracted, i.e. transposed reads of row-major tiles: ds_read_b64_tr_b16 on
 // the XOR-swizzled [64 tokens][64 channels] sub-tiles every kernel here uses.  All tiles of a slice
 // are placed on ONE XCD (block id -> XCD is round-robin), so a dY / X row is fetched from HBM once
@@ -16,6 +17,7 @@
 // are summed in a fixed order by ea_slice_sum (deterministic; no atomics).
 #include <stdlib.h>
 #include <algorithm>
+#include <type_traits>
 #include "ea_common.h"
 #include "ea_linear.h"
 
@@ -39,8 +41,25 @@ struct WgP {
   int M2, K2, tiles_n2, T2;
 };
 
-template <typename E, int BM, int BN>
+// Token stages of global loads in flight per workgroup: 1 requests stage s+1 while stage s is multiplied; 2 keeps a second set
+// of staging registers, so stage s+2 has been requested as well.  Which tiles take two: [192 x 192] only, the tile of the
+// 192-wide layers, whose ~2.5 us stage leaves its one stage of loads landed and the memory pipe idle for most of it.  The
+// second register set is SA + SB 16-byte registers per lane on top of the accumulators (BM * BN / 512 per lane) within
+// __launch_bounds__(512, 1)'s 256 VGPRs: [192 x 192] fits it without a spill; a tile with a 256 edge ([256 x 192] has 250
+// with ONE set) would not.  The small tiles have the registers but nothing to gain: their ~1 us stage is barrier, LDS
+// hand-over and MFMA chain, not the wait for rows ([64 x 64] 21.4 -> 27.4 us with two stages).
+template <int BM, int BN> constexpr int wgrad_stages_of() { return (BM == 192 && BN == 192) ? 2 : 1; }
+// EA_WGRAD_STAGES=1 (dev switch): wgrad_kernel<OneStage<E>, BM, BN> is the tile's kernel with the one-stage loop.  (A variant of
+// the element type and not a fourth template argument or a body shared by two kernels: tools and tests know the kernels as
+// wgrad_kernel<E, BM, BN>, and called through a device function the tiles that did not change compile to other code.)
+template <typename E> struct OneStage {};
+template <typename EV> struct WgElem { using type = EV; static constexpr bool one_stage = false; };
+template <typename E> struct WgElem<OneStage<E>> { using type = E; static constexpr bool one_stage = true; };
+
+template <typename EV, int BM, int BN>
 __global__ __launch_bounds__(512, 1) void wgrad_kernel(const WgP p) {
+  using E = typename WgElem<EV>::type;
+  constexpr int NS = WgElem<EV>::one_stage ? 1 : wgrad_stages_of<BM, BN>();
   constexpr int SA = BM / 64, SB = BN / 64;   // 64-channel sub-tiles of the dY / X stage
   constexpr int FA = BM / 64;                 // A fragments (16 out-channels) per wave: BM / 4 waves / 16
   constexpr int FB = BN / 32;                 // B fragments (16 in-channels) per wave:  BN / 2 waves / 16
@@ -77,7 +96,10 @@ __global__ __launch_bounds__(512, 1) void wgrad_kernel(const WgP p) {
   // 64-bit address pair per load and selected around it): the loads are unconditional, from a 32-bit byte offset per staged
   // chunk that advances by 64 rows per stage (base pointer in SGPRs); only the LAST stage of a slice can reach past it, and
   // only there the rows are clamped (issue) and zeroed (commit) -- a uniform branch.
+  // The staging registers are named statically (pa, pb | pa2, pb2) and handed to issue / commit by reference: a set picked by
+  // a run-time index would live in scratch (see aoff / boff below).
   u32x4 pa[SA], pb[SB];
+  u32x4 pa2[NS == 2 ? SA : 1], pb2[NS == 2 ? SB : 1];
   uint32_t offa[SA], offb[SB];
 #pragma unroll
   for (int k = 0; k < SA; ++k) {
@@ -94,8 +116,9 @@ __global__ __launch_bounds__(512, 1) void wgrad_kernel(const WgP p) {
   const uint32_t stepa = (uint32_t)(64 * pM * 2), stepb = (uint32_t)(64 * pK * 2);
   const char* const dys = dyp + (size_t)r0 * pM * 2;       // (a slice spans < 4 GB: checked at dispatch)
   const char* const xs = xp + (size_t)r0 * pK * 2;
-  auto issue = [&](int rb) {
-    if (rb + 64 <= r1) {
+  // (`full`: the caller knows that the stage has all its 64 rows -- no branch to the clamped / zeroed path is compiled)
+  auto issue = [&](auto full, int rb, u32x4 (&pa)[SA], u32x4 (&pb)[SB]) {
+    if (decltype(full)::value || rb + 64 <= r1) {
 #pragma unroll
       for (int k = 0; k < SA; ++k) pa[k] = ldg16(dys + offa[k]);
 #pragma unroll
@@ -129,8 +152,8 @@ __global__ __launch_bounds__(512, 1) void wgrad_kernel(const WgP p) {
   for (int k = 0; k < NB; ++k)
 #pragma unroll
     for (int e = 0; e < 8; ++e) accb[k][e] = 0.f;
-  auto commit = [&](char* st, int rb) {
-    if (rb + 64 > r1) {                                // (uniform) the slice's last stage: rows past it count as zeros
+  auto commit = [&](auto full, char* st, int rb, u32x4 (&pa)[SA], u32x4 (&pb)[SB]) {
+    if (!decltype(full)::value && rb + 64 > r1) {      // (uniform) the slice's last stage: rows past it count as zeros
       const u32x4 z = {0u, 0u, 0u, 0u};
 #pragma unroll
       for (int k = 0; k < SA; ++k) { if (rb + (tid + k * 512) / CPRA >= r1) pa[k] = z; }
@@ -156,6 +179,9 @@ __global__ __launch_bounds__(512, 1) void wgrad_kernel(const WgP p) {
       sts16(st + (SA + (ch >> 3)) * (64 * 128) + lds_off2<64>(row, ch & 7), pb[k]);
     }
   };
+  // (the one-stage loop's issue / commit, on the one register set)
+  auto issue1 = [&](int rb) { issue(std::false_type{}, rb, pa, pb); };
+  auto commit1 = [&](char* st, int rb) { commit(std::false_type{}, st, rb, pa, pb); };
 
   // 8 waves as 4 (out channels) x 2 (in channels): wave (wa, wb) owns [BM / 4] x [BN / 2] of the tile
   const int wa = wave & 3, wb = wave >> 2;
@@ -183,16 +209,13 @@ __global__ __launch_bounds__(512, 1) void wgrad_kernel(const WgP p) {
 #pragma unroll
     for (int c = 0; c < FB; ++c) acc[f][c] = f32x4{0.f, 0.f, 0.f, 0.f};
 
-  issue(r0);
-  commit(smem, r0);
-  __syncthreads();
-  int buf = 0;
-  for (int rb = r0; rb < r1; rb += 64) {
-    char* cur = smem + buf * STAGE;
-    const bool more = rb + 64 < r1;
-    if (more) issue(rb + 64);
+  // stage `cur` of LDS times itself: the order of the MFMAs over kb, f, c is the same in every loop below
+  auto mma = [&](const char* cur) {
 #pragma unroll
     for (int kb = 0; kb < 64; kb += 32) {
+      // (NS = 2: the second half's LDS reads stay behind the first half's MFMAs -- hoisted over them, as the scheduler does
+      // with registers to spare, they spill beside two live staging sets)
+      if constexpr (NS == 2) { if (kb) __builtin_amdgcn_sched_barrier(0); }
       typename E::x8 af[FA];
 #pragma unroll
       for (int f = 0; f < FA; ++f) {
@@ -207,9 +230,91 @@ __global__ __launch_bounds__(512, 1) void wgrad_kernel(const WgP p) {
         for (int f = 0; f < FA; ++f) acc[f][c] = E::mma(af[f], bf, acc[f][c]);
       }
     }
-    if (more) commit(smem + (buf ^ 1) * STAGE, rb + 64);
+  };
+  char* const buf0 = smem;
+  char* const buf1 = smem + STAGE;
+  constexpr std::true_type full{};
+  constexpr std::false_type any{};
+  if constexpr (NS == 1) {
+    // The one-stage loop as it was (its MFMA block written out, not through `mma`): every one-stage kernel compiles to the
+    // code it had before the second stage, instruction for instruction (tools/isa_diff.py --by-code against that commit).
+    issue1(r0);
+    commit1(smem, r0);
     __syncthreads();
-    buf ^= 1;
+    int buf = 0;
+    for (int rb = r0; rb < r1; rb += 64) {
+      char* cur = smem + buf * STAGE;
+      const bool more = rb + 64 < r1;
+      if (more) issue1(rb + 64);
+#pragma unroll
+      for (int kb = 0; kb < 64; kb += 32) {
+        typename E::x8 af[FA];
+#pragma unroll
+        for (int f = 0; f < FA; ++f) {
+          const char* ap = cur + kb * 128 + aoff[f];
+          af[f] = as_x8<E>(E::tr4(ap), E::tr4(ap + 16 * 128));
+        }
+#pragma unroll
+        for (int c = 0; c < FB; ++c) {
+          const char* bp = cur + kb * 128 + boff[c];
+          const typename E::x8 bf = as_x8<E>(E::tr4(bp), E::tr4(bp + 16 * 128));
+#pragma unroll
+          for (int f = 0; f < FA; ++f) acc[f][c] = E::mma(af[f], bf, acc[f][c]);
+        }
+      }
+      if (more) commit1(smem + (buf ^ 1) * STAGE, rb + 64);
+      __syncthreads();
+      buf ^= 1;
+    }
+  } else {
+    // Two stages of loads in flight.  LDS stays double-buffered with one barrier per stage; what moves is the distance of the
+    // global loads: while stage s is multiplied out of buffer b, stage s+1 waits in one register set (committed to buffer b^1
+    // at the end of the iteration) and stage s+2 has been requested into the other.  The loads of a wave return in order, so
+    // the wait in front of a commit is a COUNTED one that leaves the younger stage's SA + SB loads outstanding -- which the
+    // compiler can only emit where every path to the commit has requested that younger stage.  So the steady loop (two
+    // stages per trip, the sets alternating by name) runs while both stages it requests are whole ones, and requests without
+    // a condition; the last two to four stages of a slice drain after it, one stage in flight as in the NS = 1 loop.
+    // Invariant at the top of the steady loop and of the drain: stage rb is in buffer 0, stage rb + 64 (if any) has been
+    // requested into the second set, nothing later has.  The scheduling fence after a steady issue keeps the loads in front
+    // of the stage's MFMAs (left alone the scheduler sinks them past half of them to shorten the registers' live range).
+    issue(any, r0, pa, pb);
+    if (r0 + 64 < r1) issue(any, r0 + 64, pa2, pb2);
+    commit(any, buf0, r0, pa, pb);
+    __syncthreads();
+    int rb = r0;
+    for (; rb + 256 <= r1; rb += 128) {                  // stages rb + 128 and rb + 192 exist and have 64 rows each
+      issue(full, rb + 128, pa, pb);
+      __builtin_amdgcn_sched_barrier(0);
+      mma(buf0);
+      commit(full, buf1, rb + 64, pa2, pb2);
+      __syncthreads();
+      issue(full, rb + 192, pa2, pb2);
+      __builtin_amdgcn_sched_barrier(0);
+      mma(buf1);
+      commit(full, buf0, rb + 128, pa, pb);
+      __syncthreads();
+    }
+    // the drain: r1 - rb <= 255, i.e. one to four stages, written out so that the buffers keep their static addresses
+    if (rb + 128 < r1) issue(any, rb + 128, pa, pb);
+    mma(buf0);
+    if (rb + 64 < r1) {
+      commit(any, buf1, rb + 64, pa2, pb2);
+      __syncthreads();
+      mma(buf1);
+      if (rb + 128 < r1) {
+        commit(any, buf0, rb + 128, pa, pb);
+        __syncthreads();
+        const bool fourth = rb + 192 < r1;
+        if (fourth) issue(any, rb + 192, pa, pb);
+        mma(buf0);
+        if (fourth) {
+          commit(any, buf1, rb + 192, pa, pb);
+          __syncthreads();
+          mma(buf1);
+        }
+      }
+    }
+    __syncthreads();
   }
   // ---- partial tile -> part[slice][m][n], through LDS so that it leaves in 16-byte row segments (D row 4g+r of
   // fragment fa <-> out channel 64 sa + 16 dt + 4 g + r, D column li of fragment fb <-> in channel 16 fb + li): 72
@@ -385,16 +490,26 @@ int wgrad_slices(int rows, int M, int K) {
   return S;
 }
 
+// EA_WGRAD_STAGES = 1 | 2 (dev switch, default 2): 1 launches the one-stage kernel for every tile
+static int wgrad_stages() {
+  static const int v = ea_env_int("EA_WGRAD_STAGES", 2) == 1 ? 1 : 2;
+  return v;
+}
+
 template <typename E, int BM, int BN>
 static int launch_wg(const WgP& p, hipStream_t st) {
+  void (*kernel)(const WgP) = &wgrad_kernel<E, BM, BN>;
+  if constexpr (wgrad_stages_of<BM, BN>() == 2) {
+    if (wgrad_stages() == 1) kernel = &wgrad_kernel<OneStage<E>, BM, BN>;
+  }
   const size_t lds = (size_t)2 * (BM / 64 + BN / 64) * 64 * 128;
-  if (const int e = ea_lds_limit(&wgrad_kernel<E, BM, BN>, lds)) return e;
+  if (const int e = ea_lds_limit(kernel, lds)) return e;
   const int T = p.tiles_m * p.tiles_n + p.T2;
   // (the staging addresses are 32-bit byte offsets from a slice's first row)
   const long widest = std::max(std::max(p.M, p.K), std::max(p.M2, p.K2));
   if ((long)(p.rows_per_slice + 64) * widest * 2 >= (1L << 32)) return EA_E_UNSUPPORTED;
   const dim3 grid((unsigned)(((p.S & 7) == 0 ? ((p.S + 7) / 8) * 8 : p.S) * T)), block(512);
-  hipLaunchKernelGGL((wgrad_kernel<E, BM, BN>), grid, block, lds, st, p);
+  hipLaunchKernelGGL(kernel, grid, block, lds, st, p);
   return (int)hipGetLastError();
 }
 
