@@ -41,7 +41,7 @@ static Geo mk_geo(const ea_geom* g) {
 extern "C" {
 
 const char* ea_version(void) { return "ea_hip 0.1.0 gfx950"; }
-int32_t ea_abi_version(void) { return 37; }
+int32_t ea_abi_version(void) { return 38; }
 
 int32_t ea_window_bias_ld(const ea_geom* g) {
   WinTiling t;
@@ -2639,6 +2639,42 @@ int ea_vocab_score(int32_t M, int32_t K, int32_t V, const void* x, int32_t x_dty
   p.ldx = ldx; p.ldl = logits ? ldl : 0; p.M = M; p.K = K; p.V = V; p.dtype = w_dtype;
   p.x_f32 = x_dtype == EA_F32; p.l_f32 = logits && logits_dtype == EA_F32;
   return ea::vocab_score(p, (hipStream_t)stream);
+}
+
+// ---- the vocabulary cross-entropy's backward (ABI 38, ea_vocab_nll.hip): the chunk's logit gradient and the plain GEMM ----------
+int32_t ea_vocab_nll_chunk(int32_t M, int32_t V) { return ea::vocab_nll_chunk(M, V); }
+
+int64_t ea_vocab_nll_ws(int32_t M, int32_t K, int32_t V, int32_t chunk_cols) { return ea::vocab_nll_ws(M, K, V, chunk_cols); }
+
+int ea_vocab_nll_grad(int32_t M, int32_t K, int32_t V, const void* x, int32_t x_dtype, int64_t ldx, const void* w,
+                      int32_t w_dtype, const int64_t* targets, const float* lse, const float* d, int32_t v0, int32_t Vc,
+                      void* g, int64_t ldg, void* gt, int64_t ldm, void* stream) {
+  if (!dec_table_ok(M, K, x, x_dtype, ldx, w, w_dtype)) return EA_E_BADARG;
+  if (!targets || !lse || !d || !g || !gt) return EA_E_BADARG;
+  if ((uintptr_t)targets % 8 || (uintptr_t)lse % 4 || (uintptr_t)d % 4 || (uintptr_t)g % 16 || (uintptr_t)gt % 16) return EA_E_BADARG;
+  if (v0 < 0 || Vc < 1 || v0 % ea::VS_SL || (V >= 1 && (int64_t)v0 + Vc > V)) return EA_E_BADARG;
+  if (ldg < Vc || ldm < M || ldg % 64 || ldm % 64) return EA_E_BADARG;
+  const int64_t grid = (((int64_t)M - 1) / ea::VS_BM + 1) * (((int64_t)Vc - 1) / ea::VS_SL + 1);
+  if (K % 32 || V < 1 || grid > ea::VS_MAX_WORKGROUPS) return EA_E_UNSUPPORTED;
+  ea::VocabNllGradP p = {};
+  p.x = (const char*)x; p.w = (const char*)w; p.targets = targets; p.ldx = ldx; p.M = M; p.K = K; p.V = V; p.dtype = w_dtype;
+  p.x_f32 = x_dtype == EA_F32;
+  p.lse_in = lse; p.d = d; p.g = (uint16_t*)g; p.gt = (uint16_t*)gt; p.ldg = ldg; p.ldm = ldm; p.v0 = v0; p.Vc = Vc;
+  return ea::vocab_nll_grad(p, (hipStream_t)stream);
+}
+
+int ea_gemm_nt16(int32_t M, int32_t N, int32_t K, const void* a, int64_t lda, const void* b, int64_t ldb, int32_t dtype,
+                 float* out, int64_t ldo, int32_t accumulate, void* stream) {
+  if (!a || !b || !out || (uintptr_t)a % 16 || (uintptr_t)b % 16 || (uintptr_t)out % 4) return EA_E_BADARG;
+  if (dtype != EA_BF16 && dtype != EA_F16) return EA_E_BADARG;
+  if (M < 1 || N < 1 || K < 1 || lda < K || ldb < K || ldo < N || lda % 8 || ldb % 8) return EA_E_BADARG;
+  if (accumulate != 0 && accumulate != 1) return EA_E_BADARG;
+  const int64_t grid = (((int64_t)M - 1) / ea::VS_BM + 1) * (((int64_t)N - 1) / ea::VS_BN + 1);
+  if (K % 32 || grid > ea::VS_MAX_WORKGROUPS) return EA_E_UNSUPPORTED;
+  ea::GemmNt16P p = {};
+  p.x = (const char*)a; p.w = (const char*)b; p.logits = (char*)out; p.ldx = lda; p.ldw = ldb; p.ldl = ldo;
+  p.M = M; p.K = K; p.V = N; p.dtype = dtype; p.l_f32 = 1; p.accumulate = accumulate;
+  return ea::gemm_nt16(p, (hipStream_t)stream);
 }
 
 // ---- adaptive-softmax scoring (ABI 33, ea_adaptive_score.hip): the routing, the vocabulary pass over a row set, the composite.

@@ -52,9 +52,33 @@ struct VocabScoreRowsP : VocabScoreP {
   int logits_only;            // 1: the first launch alone, without pick, sums and target logits: a GEMM into `logits`
 };
 
+// the logit gradient of a column chunk (ABI 38, ea_vocab_nll.hip): of the base block x, w (the WHOLE table), targets, ldx, M, K,
+// V, dtype and x_f32 are read; MT row tiles, NS slices of the chunk
+struct VocabNllGradP : VocabScoreP {
+  const float* lse_in;        // [M] the rows' log-sum-exp, as ea_vocab_score wrote it
+  const float* d;             // [M] dL / dlogp
+  uint16_t* g;                // [M, ldg]: G of the chunk; columns Vc .. ldg - 1 are written as zeros
+  uint16_t* gt;               // [Vc, ldm]: its transpose; columns M .. ldm - 1 are written as zeros
+  int64_t ldg, ldm;           // multiples of 64, ldg >= Vc, ldm >= M
+  int v0, Vc;                 // the chunk: table rows [v0, v0 + Vc), v0 % VS_SL == 0
+};
+
+// out (+)= a b^T (ABI 38, ea_vocab_nll.hip): x = a [M, ldx], w = b [V, ldw], logits = out [M, ldl] fp32, K % 32 == 0
+struct GemmNt16P : VocabScoreP {
+  int64_t ldw;                // the row stride of b in elements
+  int accumulate;             // 1: out += , 0: out =
+};
+
 // bytes of ws for (M, V); < 0: outside the envelope (M < 1, V < 1, more than VS_MAX_WORKGROUPS workgroups)
 int64_t vocab_score_ws(int M, int V);
 // the two launches; the C entry point has checked pointers, alignment, strides, types and the size of ws
 int vocab_score(VocabScoreP p, hipStream_t st);
+
+// ABI 38 (ea_vocab_nll.hip).  The default chunk width for (M, V); the workspace of a backward; the two launches' entries,
+// on arguments their C entry points have checked
+int vocab_nll_chunk(int M, int V);
+int64_t vocab_nll_ws(int M, int K, int V, int chunk_cols);
+int vocab_nll_grad(VocabNllGradP p, hipStream_t st);
+int gemm_nt16(GemmNt16P p, hipStream_t st);
 
 }  // namespace ea

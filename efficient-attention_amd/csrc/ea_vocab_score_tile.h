@@ -10,6 +10,15 @@
 // position >= live is clamped to position live - 1 BEFORE a list is read (the clamp to row M - 1 of ROWS = false), so a list
 // entry at or beyond the count is never dereferenced; nothing is written at such a position.  With no lists, no count and
 // base 0 the arithmetic is that of ROWS = false, operation for operation: the same bits.
+//
+// EPI picks what stands behind a column block's last k stage (ABI 38, ea_vocab_nll.hip; ROWS = false only):
+//   VS_EPI_SCORE  the above: every `if constexpr` on EPI falls away and the kernels of ABI 30 / 33 are what they were.
+//   VS_EPI_GRAD   a VocabNllGradP: the logit tiles of the table's columns [v0, v0 + Vc) are formed again -- the same k order
+//                 per accumulator, so the same bits -- and G = d ((v == target) - expf(a - lse)) is stored in 16 bits, row-major
+//                 and transposed.  The table rows of a block are staged in LDS in a permuted order, so that a lane's four
+//                 accumulator tiles are four CONSECUTIVE columns: both images are written with 8-byte stores.
+//   VS_EPI_GEMM   a GemmNt16P: the loop as a plain GEMM, out (+)= a b^T in fp32; b has a row stride of its own, and a "slice"
+//                 is one column block (there is nothing to fold across blocks, and narrow outputs get a wider grid).
 #pragma once
 #include <limits.h>
 #include <math.h>
@@ -32,6 +41,11 @@ static_assert(VS_SL % VS_BN == 0, "a slice is whole column blocks");
 static_assert(sizeof(VsPick) == 8, "a candidate is one 8-byte store");
 
 template <bool ROWS> using VsParams = std::conditional_t<ROWS, VocabScoreRowsP, VocabScoreP>;
+
+constexpr int VS_EPI_SCORE = 0, VS_EPI_GRAD = 1, VS_EPI_GEMM = 2;
+template <bool ROWS, int EPI> struct VsEpiParams { using type = VsParams<ROWS>; };
+template <> struct VsEpiParams<false, VS_EPI_GRAD> { using type = VocabNllGradP; };
+template <> struct VsEpiParams<false, VS_EPI_GEMM> { using type = GemmNt16P; };
 
 // a takes b's place: a NaN beats every number, a larger number a smaller one, and of two equals (two NaNs, +0 and -0) the
 // lower index (the few-row entries' voc_beats).  Selects, no branches: the epilogue is straight-line code.
@@ -85,8 +99,10 @@ template <bool ROWS> EA_DEV int32_t vs_target(const VsParams<ROWS>& p, int m) {
   }
 }
 
-template <typename E, bool XF32, bool ROWS>
-__global__ __launch_bounds__(VS_THREADS) void vocab_score_kernel(const VsParams<ROWS> p) {
+template <typename E, bool XF32, bool ROWS, int EPI = VS_EPI_SCORE>
+__global__ __launch_bounds__(VS_THREADS) void vocab_score_kernel(const typename VsEpiParams<ROWS, EPI>::type p) {
+  static_assert(EPI == VS_EPI_SCORE || !ROWS, "the gradient and the plain GEMM take every row of the call");
+  constexpr int SL = EPI == VS_EPI_GEMM ? VS_BN : VS_SL;   // columns of one workgroup
   extern __shared__ __attribute__((aligned(16))) char vs_lds[];
   int32_t* tgts = reinterpret_cast<int32_t*>(vs_lds + VS_LDS_TGT);
   float* merge = reinterpret_cast<float*>(vs_lds + VS_LDS_MERGE);
@@ -99,8 +115,12 @@ __global__ __launch_bounds__(VS_THREADS) void vocab_score_kernel(const VsParams<
   if constexpr (ROWS) {
     if (m0 >= live) return;                            // (uniform: the whole workgroup, before its first operand load)
   }
-  const int s0 = slice * VS_SL;                        // (< V)
-  const int ncols = min(VS_SL, p.V - s0);              // columns of this slice: at least one
+  int s0 = slice * SL;                                 // (< V)
+  int ncols = min(SL, p.V - s0);                       // columns of this slice: at least one
+  if constexpr (EPI == VS_EPI_GRAD) {                  // (the chunk's slices: s0 < v0 + Vc <= V)
+    s0 += p.v0;
+    ncols = min(SL, p.v0 + p.Vc - s0);
+  }
   const int nblk = (ncols + VS_BN - 1) / VS_BN;
   const int KT = (p.K + VS_BK - 1) / VS_BK;
   const int IT = nblk * KT;
@@ -119,7 +139,13 @@ __global__ __launch_bounds__(VS_THREADS) void vocab_score_kernel(const VsParams<
     }
     xrow[q] = p.x + r * p.ldx * (XF32 ? 4 : 2);
   }
-  const char* wslice = p.w + (int64_t)s0 * p.K * 2;
+  int64_t ldw = p.K;                                   // the row stride of w
+  if constexpr (EPI == VS_EPI_GEMM) ldw = p.ldw;
+  const char* wslice = p.w + (int64_t)s0 * ldw * 2;
+  // the table row that tile row lr + 64 q holds: itself, or (VS_EPI_GRAD) tile row 16 j + li of a half holds row 4 li + j
+  int wrow[2];
+#pragma unroll
+  for (int q = 0; q < 2; ++q) wrow[q] = EPI == VS_EPI_GRAD ? 64 * q + 4 * (lr & 15) + (lr >> 4) : lr + 64 * q;
   VsX<XF32> rx[2];
   u32x4 rw[2];
   auto fetch = [&](int blk, int kt) {
@@ -128,8 +154,8 @@ __global__ __launch_bounds__(VS_THREADS) void vocab_score_kernel(const VsParams<
 #pragma unroll
       for (int q = 0; q < 2; ++q) {
         rx[q].load(xrow[q], k);
-        const int n = min(blk * VS_BN + lr + 64 * q, ncols - 1);   // (a column past V: the slice's last row again)
-        rw[q] = ldg16(wslice + ((int64_t)n * p.K + k) * 2);
+        const int n = min(blk * VS_BN + wrow[q], ncols - 1);       // (a column past V: the slice's last row again)
+        rw[q] = ldg16(wslice + ((int64_t)n * ldw + k) * 2);
       }
     } else {
 #pragma unroll
@@ -153,6 +179,17 @@ __global__ __launch_bounds__(VS_THREADS) void vocab_score_kernel(const VsParams<
   }
   bool bookkeeping = true;                             // (uniform)
   if constexpr (ROWS) bookkeeping = !p.logits_only;
+  if constexpr (EPI != VS_EPI_SCORE) bookkeeping = false;
+  // VS_EPI_GRAD: d and lse of row 16 i + 4 g + r (of the wave's 32), entry 4 i + r; a row >= M: d = 0
+  float gd[8], gl[8];
+  if constexpr (EPI == VS_EPI_GRAD) {
+#pragma unroll
+    for (int q = 0; q < 8; ++q) {
+      const int m = m0 + wm * 32 + 16 * (q >> 2) + 4 * g + (q & 3);
+      gd[q] = m < live ? p.d[m] : 0.f;
+      gl[q] = m < live ? p.lse_in[m] : 0.f;
+    }
+  }
 
   // the operand reads of a stage: row 16 i + li of the wave's 32 rows / 16 j + li of its 64 columns, chunk 4 ks + g
   int aoff[2], boff[2];
@@ -199,7 +236,72 @@ __global__ __launch_bounds__(VS_THREADS) void vocab_score_kernel(const VsParams<
     if (last_k) {
       // the block's logits: D[row 16 i + 4 g + r][column 16 j + li] of the wave's 32 x 64
       const int c0 = blk * VS_BN + wn * 64 + li;       // this lane's first column, within the slice
-      if (p.logits) {                                  // (uniform; the tests' and a curious caller's path)
+      if constexpr (EPI == VS_EPI_GRAD) {
+        // this lane's columns are 4 li + j of its wave's 64; cb: the first of them, within the chunk
+        const int cb = slice * SL + blk * VS_BN + wn * 64 + 4 * li;
+        uint16_t gv[2][4][4];                          // [i][r][j]
+#pragma unroll
+        for (int i = 0; i < 2; ++i)
+#pragma unroll
+          for (int r = 0; r < 4; ++r) {
+            const int q = 4 * i + r;
+            const int tgt = tgts[wm * 32 + 16 * i + 4 * g + r];
+#pragma unroll
+            for (int j = 0; j < 4; ++j) {
+              const float hit = p.v0 + cb + j == tgt ? 1.f : 0.f;
+              const float gf = gd[q] * (hit - expf(acc[i][j][r] - gl[q]));
+              gv[i][r][j] = gd[q] == 0.f ? (uint16_t)0 : E::from_f(gf);   // (a select: such a row's logits may be NaN)
+            }
+          }
+        const int mb = m0 + wm * 32 + 4 * g;           // this lane's first row
+#pragma unroll
+        for (int i = 0; i < 2; ++i)
+#pragma unroll
+          for (int r = 0; r < 4; ++r) {
+            const int m = mb + 16 * i + r;
+            if (m >= live) continue;
+            uint16_t* at = p.g + (int64_t)m * p.ldg + cb;
+            if (cb + 3 < p.Vc) {
+              *reinterpret_cast<u32x2*>(at) = u32x2{(uint32_t)gv[i][r][0] | (uint32_t)gv[i][r][1] << 16,
+                                                    (uint32_t)gv[i][r][2] | (uint32_t)gv[i][r][3] << 16};
+            } else {
+#pragma unroll
+              for (int j = 0; j < 4; ++j)
+                if (cb + j < p.Vc) at[j] = gv[i][r][j];
+            }
+          }
+#pragma unroll
+        for (int i = 0; i < 2; ++i)
+#pragma unroll
+          for (int j = 0; j < 4; ++j) {
+            if (cb + j >= p.Vc) continue;
+            const int m = mb + 16 * i;
+            uint16_t* at = p.gt + (int64_t)(cb + j) * p.ldm + m;
+            if (m + 3 < live) {
+              *reinterpret_cast<u32x2*>(at) = u32x2{(uint32_t)gv[i][0][j] | (uint32_t)gv[i][1][j] << 16,
+                                                    (uint32_t)gv[i][2][j] | (uint32_t)gv[i][3][j] << 16};
+            } else {
+#pragma unroll
+              for (int r = 0; r < 4; ++r)
+                if (m + r < live) at[r] = gv[i][r][j];
+            }
+          }
+      } else if constexpr (EPI == VS_EPI_GEMM) {
+#pragma unroll
+        for (int i = 0; i < 2; ++i)
+#pragma unroll
+          for (int r = 0; r < 4; ++r) {
+            const int m = m0 + wm * 32 + 16 * i + 4 * g + r;
+#pragma unroll
+            for (int j = 0; j < 4; ++j) {
+              const int cs = c0 + 16 * j;
+              if (cs < ncols && m < live) {
+                float* at = reinterpret_cast<float*>(p.logits) + (int64_t)m * p.ldl + s0 + cs;
+                *at = p.accumulate ? *at + acc[i][j][r] : acc[i][j][r];
+              }
+            }
+          }
+      } else if (p.logits) {                           // (uniform; the tests' and a curious caller's path)
 #pragma unroll
         for (int i = 0; i < 2; ++i)
 #pragma unroll
@@ -251,6 +353,24 @@ __global__ __launch_bounds__(VS_THREADS) void vocab_score_kernel(const VsParams<
     }
     blk = blk_next; kt = kt_next;
     __syncthreads();
+  }
+  if constexpr (EPI == VS_EPI_GRAD) {
+    // the pad positions the two GEMMs contract over, as zeros: columns Vc .. ldg - 1 of this tile's rows of G by the
+    // workgroups of the chunk's last slice, rows M .. ldm - 1 of this slice's rows of G^T by those of the last row tile
+    if (slice == p.NS - 1) {
+      const int64_t np = p.ldg - p.Vc, n = np * min(VS_BM, live - m0);
+      for (int64_t at = tid; at < n; at += VS_THREADS) {
+        const int64_t r = at / np;
+        p.g[(m0 + r) * p.ldg + p.Vc + (at - r * np)] = 0;
+      }
+    }
+    if (m0 + VS_BM >= live) {
+      const int64_t np = p.ldm - live, n = np * ncols;
+      for (int64_t at = tid; at < n; at += VS_THREADS) {
+        const int64_t c = at / np;
+        p.gt[((int64_t)slice * SL + c) * p.ldm + live + (at - c * np)] = 0;
+      }
+    }
   }
   if (!bookkeeping) return;                            // (uniform: a plain GEMM has no partials)
 
@@ -342,10 +462,11 @@ __global__ __launch_bounds__(VS_FOLD_THREADS) void vocab_score_fold_kernel(const
 }
 
 // the two launches on a filled parameter block (MT, NS, sum, tlogit set by the caller); ROWS with logits_only: the first alone
-template <typename E, bool XF32, bool ROWS>
-int vs_launch(const VsParams<ROWS>& p, hipStream_t st) {
-  if (const int e = ea_lds_limit(vocab_score_kernel<E, XF32, ROWS>, VS_LDS_BYTES)) return e;
-  hipLaunchKernelGGL((vocab_score_kernel<E, XF32, ROWS>), dim3((unsigned)(p.MT * p.NS)), dim3(VS_THREADS), VS_LDS_BYTES, st, p);
+template <typename E, bool XF32, bool ROWS, int EPI = VS_EPI_SCORE>
+int vs_launch(const typename VsEpiParams<ROWS, EPI>::type& p, hipStream_t st) {
+  if (const int e = ea_lds_limit(vocab_score_kernel<E, XF32, ROWS, EPI>, VS_LDS_BYTES)) return e;
+  hipLaunchKernelGGL((vocab_score_kernel<E, XF32, ROWS, EPI>), dim3((unsigned)(p.MT * p.NS)), dim3(VS_THREADS), VS_LDS_BYTES, st,
+                     p);
   return (int)hipGetLastError();
 }
 

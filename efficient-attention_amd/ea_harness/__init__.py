@@ -18,6 +18,9 @@ as WHOLE models (eager, autocast, DistributedDataParallel over RCCL) on syntheti
   token_pick            -- what the decoding modes share: DecodingState and what is attached to it (Sampler,
                            Scorer, Beam, AdaptivePick, the held vocabulary pair) with one lifecycle, the operand
                            helpers of the vocabulary entries, and one pick per launch behind one selector
+  vocab_loss            -- vocab_nll: the vocabulary cross-entropy of the plain tied table as one autograd Function,
+                           ea_vocab_score forward and a chunked HIP backward (ea_vocab_nll_grad, ea_gemm_nt16), without
+                           a [rows, V] tensor; DecoderStack.loss is the stack's forward in front of it
   trainer               -- one synthetic training step (forward, loss, backward, optimizer) eagerly or
                            captured in a hipGraph, single process or one process per GPU
 

@@ -780,6 +780,35 @@ class DecoderStack(nn.Module):
             logp = logp.masked_fill_(targets.eq(self.pad_idx), 0.0).t().contiguous()
             return (logp, greedy.t().contiguous()) if return_tokens else logp
 
+    # ---- the training loss (ea_vocab_score forward, ea_vocab_nll_grad / ea_gemm_nt16 backward, C ABI 38) -----------------------
+    def loss(self, tokens, key_padding_mask=None, reduction="mean"):
+        """The next-token cross-entropy with a gradient: tokens [B, T] int64 -> the negative log-likelihood of tokens[:, 1:]
+        given what precedes them.  Runs the full (training-shaped) forward on tokens[:, :-1], then
+        `ea_harness.vocab_loss.vocab_nll` on embed_tokens.weight: the scorer of `evaluate` forward, HIP kernels backward, no
+        [rows, V] tensor in either direction and a log-sum-exp over unrounded fp32 sums.  Targets equal to `pad_idx` have
+        loss 0 and add exact zeros to every gradient.  reduction: "mean" (over the non-pad targets, counted on the device;
+        nothing is read back), "sum", or "none" (fp32 [B, T - 1]; in eval mode -`evaluate(tokens)` bit for bit).  The table
+        is the tied embedding: autograd adds the lookup's gradient to the projection's by itself.
+        On an adaptive stack: NotImplementedError (the adaptive-softmax loss is a follow-up)."""
+        if self.is_adaptive:
+            raise NotImplementedError("loss on an adaptive stack: the adaptive-softmax training loss is a follow-up (it would "
+                                      "reuse ea_vocab_nll_grad and ea_gemm_nt16 per band); this loss takes the plain tied table")
+        if reduction not in ("mean", "sum", "none"):
+            raise ValueError("reduction must be 'mean', 'sum' or 'none', got %r" % (reduction,))
+        B, T = tokens.shape
+        if T < 2:
+            raise ValueError("loss needs at least two tokens per row, got %d" % T)
+        from .vocab_loss import vocab_nll
+        rows = self(tokens[:, :-1], key_padding_mask)                        # [T - 1, B, C]
+        targets = tokens[:, 1:].t().contiguous()
+        pad = targets.eq(self.pad_idx)
+        nll = -vocab_nll(rows, self.embed_tokens.weight, targets).masked_fill(pad, 0.0)
+        if reduction == "none":
+            return nll.t().contiguous()
+        if reduction == "sum":
+            return nll.sum()
+        return nll.sum() / pad.logical_not().sum().clamp(min=1)
+
     # ---- beam search (ea_ceva_sdecode_vocab_beam, C ABI 32) ------------------------------------------------------------------
     def init_beam_search(self, state, beam_size, eos_idx, max_new, len_penalty=1.0):
         """Make `state` (made with hold_vocab=True, no sampler; its batch size M a multiple of `beam_size`) search with beams:

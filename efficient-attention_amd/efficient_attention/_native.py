@@ -22,7 +22,7 @@ class ea_t4(ctypes.Structure):
                 ("sn", ctypes.c_int64)]
 
 
-ABI_VERSION = 37         # ea_abi_version() of include/ea_hip.h this file mirrors
+ABI_VERSION = 38         # ea_abi_version() of include/ea_hip.h this file mirrors
 
 
 class ea_geom(ctypes.Structure):
@@ -274,6 +274,10 @@ SIGNATURES = {
     "ea_vocab_score_ws": [_I, _I],
     "ea_vocab_score_tile": [_I],
     "ea_vocab_score": [_I, _I, _I, _P, _I, _L, _P, _I, _P, _P, _I, _L, _P, _L, _P, _P, _P, _P, _P],
+    "ea_vocab_nll_chunk": [_I, _I],
+    "ea_vocab_nll_ws": [_I, _I, _I, _I],
+    "ea_vocab_nll_grad": [_I, _I, _I, _P, _I, _L, _P, _I, _P, _P, _P, _I, _I, _P, _L, _P, _L, _P],
+    "ea_gemm_nt16": [_I, _I, _I, _P, _L, _P, _L, _I, _P, _L, _I, _P],
     "ea_adaptive_route": [_I, _I, _P, _P, _P, _P, _P, _P],
     "ea_vocab_score_rows_ws": [_I, _I],
     "ea_vocab_score_rows": [_I, _I, _I, _P, _I, _L, _P, _I, _P, _P, _I, _L, _P, _L, _P, _P, _P, _P, _P, _P, _L, _I, _P],
@@ -330,6 +334,7 @@ def lib():
         cdll.ea_ceva_sdecode_vocab_beam_ws.restype = ctypes.c_int64
         cdll.ea_vocab_score_ws.restype = ctypes.c_int64
         cdll.ea_vocab_score_rows_ws.restype = ctypes.c_int64
+        cdll.ea_vocab_nll_ws.restype = ctypes.c_int64
         cdll.ea_adaptive_score_ws.restype = ctypes.c_int64
         cdll.ea_adaptive_pick_ws.restype = ctypes.c_int64
         cdll.ea_adaptive_sample_ws.restype = ctypes.c_int64

@@ -1582,6 +1582,47 @@ int ea_adaptive_beam_c(int32_t M, int32_t C, int32_t n_tails, const int64_t* cut
                        int32_t n_ban_tokens, const int32_t* prompt_tok, int32_t prompt_cap, const int32_t* prompt_len,
                        int32_t* gen, void* stream);
 
+/* ABI 38, THE VOCABULARY CROSS-ENTROPY'S BACKWARD (ea_harness.vocab_loss.vocab_nll, DecoderStack.loss; ea_vocab_nll.hip): the
+ * gradient of logp[m] = logit[m, t_m] - lse[m], ea_vocab_score's result on a plain [V, K] table, without a [M, V] tensor.
+ * Nothing is fused (a dX or dW tile of 128 rows by K = 1024 would be 512 KB of fp32 accumulators): the logit gradient is
+ * materialised in 16 bits one column CHUNK at a time and two plain GEMMs per chunk contract over it.  E is w_dtype.
+ * ea_vocab_nll_grad, one launch: for the table rows [v0, v0 + Vc) and all M rows of x the tile loop of ea_vocab_score forms
+ * the logits a[m, v] again -- the same k order per accumulator: the bits ea_vocab_score stores with fp32 logits -- and writes
+ *   G[m, v] = E( d[m] * ((v == targets[m]) - expf(a[m, v] - lse[m])) )      every operation in fp32, one rounding to E
+ * as g [M, ldg] (G[m, v0 + c] at g[m * ldg + c]) and as its transpose gt [Vc, ldm] (at gt[c * ldm + m]).  A row with
+ * d[m] == 0 is exact zeros, by a select: its logits and lse may be anything, NaN included.  A target outside [0, V) has no
+ * (v == target) term.  Columns Vc .. ldg - 1 of g and columns M .. ldm - 1 of gt are WRITTEN as zeros: the GEMMs below
+ * contract over them.  x, w (the WHOLE table, [V, K] row-major), targets as in ea_vocab_score; lse, d: fp32 [M].  A row's values
+ * do not depend on the rows beside it, on M or on the chunking.  Ordinary vector stores, no atomics, no workgroup waits for
+ * another, every element written once: bitwise reproducible.
+ * EA_E_BADARG: x, w, targets, lse, d, g, gt NULL; x, w, g or gt not 16-byte aligned, targets not 8-byte, lse or d not 4-byte
+ * aligned; the dtype rules and the stride rules of ea_vocab_score for x and w; M < 1, K < 1; v0 < 0, Vc < 1, v0 + Vc > V
+ * (with V >= 1), v0 no multiple of EA_VOCAB_SCORE_SL; ldg < Vc, ldm < M, ldg or ldm no multiple of 64.  EA_E_UNSUPPORTED:
+ * K % 32 != 0, V < 1, more than 2^23 workgroups (ceil(M / BM) ceil(Vc / SL)).  Bad arguments first, all before the launch.
+ * ea_gemm_nt16, one launch, the same tile loop as a plain GEMM:  out[m, n] (+)= sum_k a[m, k] b[n, k], fp32 sums of exact
+ * products; a [M, lda] and b [N, ldb] of dtype = EA_BF16 | EA_F16, out [M, ldo] fp32; accumulate = 0 stores (out is not
+ * read: NaNs in it are gone), 1 reads, adds once and stores.  Per chunk of the backward:
+ *   dX += G_c W_c         a = g [M, ldg],   b = W_c^T [K, ldg] (pad columns zeros), contracting over ldg, accumulate
+ *   dW[v0 ..] = G_c^T X   a = gt [Vc, ldm], b = X^T [K, ldm] (pad columns zeros), contracting over ldm, a plain store
+ * EA_E_BADARG: a, b, out NULL; a or b not 16-byte aligned, out not 4-byte aligned; dtype not a 16-bit type; M, N, K < 1;
+ * lda < K, ldb < K, ldo < N; lda or ldb no multiple of 8 elements; accumulate outside {0, 1}.  EA_E_UNSUPPORTED: K % 32 != 0,
+ * more than 2^23 workgroups (ceil(M / BM) ceil(N / BN)).
+ * ea_vocab_nll_ws(M, K, V, chunk_cols): the bytes a backward holds beyond its outputs, with Vc = min(chunk_cols, V),
+ * ldg = up64(Vc), ldm = up64(M):   2 (M ldg + Vc ldm + K ldg + K ldm)
+ * -- g, gt, W_c^T, X^T.  (The gradients are outputs and not counted; 16-bit rows get their gradient through an fp32 [M, K]
+ * accumulator, which the caller counts with them.)
+ * It does not grow with M V.  chunk_cols: a multiple of EA_VOCAB_SCORE_SL, or 0: ea_vocab_nll_chunk(M, V), the largest
+ * such width at which g and gt fit EA_VOCAB_NLL_BUDGET bytes, never below one slice and never beyond V rounded up to slices.
+ * < 0: M, K or V < 1, chunk_cols negative or no multiple of the slice, a grid beyond 2^23 workgroups. */
+#define EA_VOCAB_NLL_BUDGET 268435456 /* 256 MiB: a guess; no chunk width has been measured against another */
+int32_t ea_vocab_nll_chunk(int32_t M, int32_t V);
+int64_t ea_vocab_nll_ws(int32_t M, int32_t K, int32_t V, int32_t chunk_cols);
+int ea_vocab_nll_grad(int32_t M, int32_t K, int32_t V, const void* x, int32_t x_dtype, int64_t ldx, const void* w,
+                      int32_t w_dtype, const int64_t* targets, const float* lse, const float* d, int32_t v0, int32_t Vc,
+                      void* g, int64_t ldg, void* gt, int64_t ldm, void* stream);
+int ea_gemm_nt16(int32_t M, int32_t N, int32_t K, const void* a, int64_t lda, const void* b, int64_t ldb, int32_t dtype,
+                 float* out, int64_t ldo, int32_t accumulate, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
