@@ -32,6 +32,7 @@ struct AdaptiveScoreP {
   const char* head;           // [c0 + n, C]
   const char* proj[AS_MAX_TAILS];    // [d_i, C]
   const char* table[AS_MAX_TAILS];   // [V_i, d_i]
+  const char* hmask[AS_MAX_TAILS];   // [M, d_i] 16-bit multipliers by position, or null (ea_adaptive_score_masked): h_i = E(h_i mask)
   char* ws;
   float* logp;                // [M]
   int64_t* token_head;        // [M] or null

@@ -188,6 +188,12 @@ int adaptive_score(const AdaptiveScoreP& a, hipStream_t st) {
     q.ldx = a.ldx; q.ldl = a.dims[i]; q.M = a.M; q.K = a.C; q.V = a.dims[i]; q.dtype = a.dtype; q.x_f32 = a.x_f32;
     q.xrows = list; q.count = count + i; q.logits_only = 1;
     if (const int rc = vocab_score_rows(q, st)) return rc;
+    if (a.hmask[i]) {                                  // (ea_adaptive_score_masked: the Dropout inside the tail, one launch)
+      RowsMaskP k = {};
+      k.h = reinterpret_cast<uint16_t*>(hi); k.mask = reinterpret_cast<const uint16_t*>(a.hmask[i]); k.count = count + i;
+      k.M = a.M; k.D = a.dims[i]; k.dtype = a.dtype;
+      if (const int rc = rows_mask16(k, st)) return rc;
+    }
     // the tail: h_i as it lies, the targets through the list, c_i taken off
     VocabScoreRowsP t = {};
     t.x = hi; t.w = a.table[i]; t.targets = a.targets; t.pick = reinterpret_cast<VsPick*>(a.ws + pl.inner);

@@ -2724,11 +2724,13 @@ int64_t ea_adaptive_score_ws(int32_t M, int32_t n_tails, const int64_t* cutoffs,
   return ea::adaptive_plan(M, n_tails, cutoffs, dims, nullptr);
 }
 
-int ea_adaptive_score(int32_t M, int32_t C, int32_t n_tails, const int64_t* cutoffs, const int32_t* dims, const void* x,
-                      int32_t x_dtype, int64_t ldx, const int64_t* targets, const void* head, int32_t w_dtype,
-                      const void* const* proj, const void* const* tables, void* ws, int64_t ws_bytes, float* logp,
-                      int64_t* token_head, void* stream) {
+static int adp_score(int32_t M, int32_t C, int32_t n_tails, const int64_t* cutoffs, const int32_t* dims, const void* x,
+                     int32_t x_dtype, int64_t ldx, const int64_t* targets, const void* head, int32_t w_dtype,
+                     const void* const* proj, const void* const* tables, const void* const* hmask, void* ws, int64_t ws_bytes,
+                     float* logp, int64_t* token_head, void* stream) {
   if (!adp_cutoffs_ok(n_tails, cutoffs) || !dims || !proj || !tables) return EA_E_BADARG;
+  for (int i = 0; hmask && i < n_tails && i < EA_ADAPTIVE_MAX_TAILS; ++i)
+    if ((uintptr_t)hmask[i] % 16) return EA_E_BADARG;
   if (!dec_table_ok(M, C, x, x_dtype, ldx, head, w_dtype)) return EA_E_BADARG;
   for (int i = 0; i < n_tails && i < EA_ADAPTIVE_MAX_TAILS; ++i)
     if (dims[i] < 1 || !proj[i] || !tables[i] || (uintptr_t)proj[i] % 16 || (uintptr_t)tables[i] % 16) return EA_E_BADARG;
@@ -2744,7 +2746,79 @@ int ea_adaptive_score(int32_t M, int32_t C, int32_t n_tails, const int64_t* cuto
   p.token_head = token_head; p.ldx = ldx; p.M = M; p.C = C; p.n = n_tails; p.dtype = w_dtype; p.x_f32 = x_dtype == EA_F32;
   for (int i = 0; i <= n_tails; ++i) p.cut[i] = cutoffs[i];
   for (int i = 0; i < n_tails; ++i) { p.dims[i] = dims[i]; p.proj[i] = (const char*)proj[i]; p.table[i] = (const char*)tables[i]; }
+  for (int i = 0; hmask && i < n_tails; ++i) p.hmask[i] = (const char*)hmask[i];
   return ea::adaptive_score(p, (hipStream_t)stream);
+}
+
+int ea_adaptive_score(int32_t M, int32_t C, int32_t n_tails, const int64_t* cutoffs, const int32_t* dims, const void* x,
+                      int32_t x_dtype, int64_t ldx, const int64_t* targets, const void* head, int32_t w_dtype,
+                      const void* const* proj, const void* const* tables, void* ws, int64_t ws_bytes, float* logp,
+                      int64_t* token_head, void* stream) {
+  return adp_score(M, C, n_tails, cutoffs, dims, x, x_dtype, ldx, targets, head, w_dtype, proj, tables, nullptr, ws, ws_bytes, logp,
+                   token_head, stream);
+}
+
+// ---- the adaptive-softmax training loss (ea_adaptive_nll.hip): the masked score, the row-set gradient and GEMM, the gathered
+// transpose and the workspace query; additions to ABI 38 ---------------------------------------------------------------------------
+int ea_adaptive_score_masked(int32_t M, int32_t C, int32_t n_tails, const int64_t* cutoffs, const int32_t* dims, const void* x,
+                             int32_t x_dtype, int64_t ldx, const int64_t* targets, const void* head, int32_t w_dtype,
+                             const void* const* proj, const void* const* tables, const void* const* hmask, void* ws,
+                             int64_t ws_bytes, float* logp, int64_t* token_head, void* stream) {
+  if (!hmask) return EA_E_BADARG;
+  return adp_score(M, C, n_tails, cutoffs, dims, x, x_dtype, ldx, targets, head, w_dtype, proj, tables, hmask, ws, ws_bytes, logp,
+                   token_head, stream);
+}
+
+int64_t ea_adaptive_nll_ws(int32_t M, int32_t C, int32_t n_tails, const int64_t* cutoffs, const int32_t* dims, int32_t chunk_cols) {
+  return ea::adaptive_nll_ws(M, C, n_tails, cutoffs, dims, chunk_cols);
+}
+
+int ea_vocab_nll_grad_rows(int32_t M, int32_t K, int32_t V, const void* x, int32_t x_dtype, int64_t ldx, const void* w,
+                           int32_t w_dtype, const int64_t* targets, const float* lse, const float* d, int32_t v0, int32_t Vc,
+                           void* g, int64_t ldg, void* gt, int64_t ldm, const int32_t* trows, const int32_t* count,
+                           int64_t target_base, void* stream) {
+  if (!dec_table_ok(M, K, x, x_dtype, ldx, w, w_dtype)) return EA_E_BADARG;
+  if (!targets || !lse || !d || !g || !gt) return EA_E_BADARG;
+  if ((uintptr_t)targets % 8 || (uintptr_t)lse % 4 || (uintptr_t)d % 4 || (uintptr_t)g % 16 || (uintptr_t)gt % 16) return EA_E_BADARG;
+  if ((uintptr_t)trows % 4 || (uintptr_t)count % 4 || target_base < 0) return EA_E_BADARG;
+  if (v0 < 0 || Vc < 1 || v0 % ea::VS_SL || (V >= 1 && (int64_t)v0 + Vc > V)) return EA_E_BADARG;
+  if (ldg < Vc || ldm < M || ldg % 64 || ldm % 64) return EA_E_BADARG;
+  const int64_t grid = (((int64_t)M - 1) / ea::VS_BM + 1) * (((int64_t)Vc - 1) / ea::VS_SL + 1);
+  if (K % 32 || V < 1 || grid > ea::VS_MAX_WORKGROUPS) return EA_E_UNSUPPORTED;
+  ea::VocabNllGradRowsP p = {};
+  p.x = (const char*)x; p.w = (const char*)w; p.targets = targets; p.ldx = ldx; p.M = M; p.K = K; p.V = V; p.dtype = w_dtype;
+  p.x_f32 = x_dtype == EA_F32;
+  p.lse_in = lse; p.d = d; p.g = (uint16_t*)g; p.gt = (uint16_t*)gt; p.ldg = ldg; p.ldm = ldm; p.v0 = v0; p.Vc = Vc;
+  p.trows = trows; p.count = count; p.target_base = target_base;
+  return ea::vocab_nll_grad_rows(p, (hipStream_t)stream);
+}
+
+int ea_gemm_nt16_rows(int32_t M, int32_t N, int32_t K, const void* a, int64_t lda, const void* b, int64_t ldb, int32_t dtype,
+                      float* out, int64_t ldo, int32_t accumulate, const int32_t* orows, const int32_t* count, void* stream) {
+  if (!a || !b || !out || (uintptr_t)a % 16 || (uintptr_t)b % 16 || (uintptr_t)out % 4) return EA_E_BADARG;
+  if ((uintptr_t)orows % 4 || (uintptr_t)count % 4) return EA_E_BADARG;
+  if (dtype != EA_BF16 && dtype != EA_F16) return EA_E_BADARG;
+  if (M < 1 || N < 1 || K < 1 || lda < K || ldb < K || ldo < N || lda % 8 || ldb % 8) return EA_E_BADARG;
+  if (accumulate != 0 && accumulate != 1) return EA_E_BADARG;
+  const int64_t grid = (((int64_t)M - 1) / ea::VS_BM + 1) * (((int64_t)N - 1) / ea::VS_BN + 1);
+  if (K % 32 || grid > ea::VS_MAX_WORKGROUPS) return EA_E_UNSUPPORTED;
+  ea::GemmNt16RowsP p = {};
+  p.x = (const char*)a; p.w = (const char*)b; p.logits = (char*)out; p.ldx = lda; p.ldw = ldb; p.ldl = ldo;
+  p.M = M; p.K = K; p.V = N; p.dtype = dtype; p.l_f32 = 1; p.accumulate = accumulate; p.orows = orows; p.count = count;
+  return ea::gemm_nt16_rows(p, (hipStream_t)stream);
+}
+
+int ea_rows_transpose16(int32_t M, int32_t K, const void* src, int32_t src_dtype, int64_t ld, const int32_t* rows,
+                        const int32_t* count, void* out, int32_t out_dtype, int64_t ldm, void* stream) {
+  if (!src || !out || (uintptr_t)src % 4 || (uintptr_t)out % 2 || (uintptr_t)rows % 4 || (uintptr_t)count % 4) return EA_E_BADARG;
+  if (out_dtype != EA_BF16 && out_dtype != EA_F16) return EA_E_BADARG;
+  if (src_dtype != EA_F32 && src_dtype != out_dtype) return EA_E_BADARG;
+  if (M < 1 || K < 1 || ld < K || ldm < M || ldm % 64) return EA_E_BADARG;
+  if ((((int64_t)K - 1) / 64 + 1) > 65535 || ldm / 64 > INT32_MAX) return EA_E_UNSUPPORTED;
+  ea::RowsTransposeP p = {};
+  p.src = (const char*)src; p.rows = rows; p.count = count; p.out = (uint16_t*)out; p.ld = ld; p.ldm = ldm; p.M = M; p.K = K;
+  p.dtype = out_dtype; p.src_f32 = src_dtype == EA_F32;
+  return ea::rows_transpose16(p, (hipStream_t)stream);
 }
 
 // ---- the greedy pick from the adaptive head (ABI 34, ea_adaptive_pick.hip): ea_adaptive_score's groups in their order ----------

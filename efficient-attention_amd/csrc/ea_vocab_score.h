@@ -69,6 +69,42 @@ struct GemmNt16P : VocabScoreP {
   int accumulate;             // 1: out += , 0: out =
 };
 
+// the same two over a device-counted set of POSITIONS (the adaptive-softmax loss, ea_adaptive_nll.hip): x and lse_in are indexed
+// by position, targets and d through trows; positions >= live are written as zeros in g and gt (the GEMMs contract over them)
+struct VocabNllGradRowsP : VocabScoreRowsP {
+  const float* lse_in;        // [M] by position
+  const float* d;             // read at trows[j]
+  uint16_t* g;                // [M, ldg]
+  uint16_t* gt;               // [Vc, ldm]
+  int64_t ldg, ldm;
+  int v0, Vc;
+};
+
+// out[orows[j], :] (+)= a[j, :] b^T for j < live; positions >= live write nothing and read no list entry
+struct GemmNt16RowsP : VocabScoreRowsP {
+  const int32_t* orows;       // [M] rows of out, or null: the identity
+  int64_t ldw;
+  int accumulate;
+};
+
+// out [K, ldm] 16-bit: out[k, j] = E(src[rows[j], k]) for j < live, zeros for live <= j < ldm
+struct RowsTransposeP {
+  const char* src;            // [*, ld] fp32 or 16-bit
+  const int32_t* rows;        // [M] or null: the identity
+  const int32_t* count;       // device scalar or null: M
+  uint16_t* out;
+  int64_t ld, ldm;
+  int M, K, dtype, src_f32;
+};
+
+// h[j, :] = E(h[j, :] * mask[j, :]) for j < live, in fp32, one rounding (the Dropout inside an adaptive tail)
+struct RowsMaskP {
+  uint16_t* h;                // [M, D]
+  const uint16_t* mask;       // [M, D]
+  const int32_t* count;
+  int M, D, dtype;
+};
+
 // bytes of ws for (M, V); < 0: outside the envelope (M < 1, V < 1, more than VS_MAX_WORKGROUPS workgroups)
 int64_t vocab_score_ws(int M, int V);
 // the two launches; the C entry point has checked pointers, alignment, strides, types and the size of ws
@@ -80,5 +116,12 @@ int vocab_nll_chunk(int M, int V);
 int64_t vocab_nll_ws(int M, int K, int V, int chunk_cols);
 int vocab_nll_grad(VocabNllGradP p, hipStream_t st);
 int gemm_nt16(GemmNt16P p, hipStream_t st);
+
+// the adaptive-softmax loss (ea_adaptive_nll.hip), on arguments the C entry points have checked
+int vocab_nll_grad_rows(VocabNllGradRowsP p, hipStream_t st);
+int gemm_nt16_rows(GemmNt16RowsP p, hipStream_t st);
+int rows_transpose16(const RowsTransposeP& p, hipStream_t st);
+int rows_mask16(const RowsMaskP& p, hipStream_t st);
+int64_t adaptive_nll_ws(int M, int C, int n, const int64_t* cut, const int32_t* dims, int chunk_cols);
 
 }  // namespace ea

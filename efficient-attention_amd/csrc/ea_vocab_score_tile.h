@@ -8,10 +8,12 @@
 // logits_only skips the pick / log-sum-exp bookkeeping (the tile loop as a plain GEMM with a 16-bit store).  A workgroup
 // whose row tile starts at or beyond the live count returns before its first operand load; inside the last live tile a
 // position >= live is clamped to position live - 1 BEFORE a list is read (the clamp to row M - 1 of ROWS = false), so a list
-// entry at or beyond the count is never dereferenced; nothing is written at such a position.  With no lists, no count and
+// entry at or beyond the count is never dereferenced; nothing is written at such a position (VS_EPI_GRAD, below, writes ZEROS
+// there, from dead workgroups too: its outputs are contracted over).  With no lists, no count and
 // base 0 the arithmetic is that of ROWS = false, operation for operation: the same bits.
 //
-// EPI picks what stands behind a column block's last k stage (ABI 38, ea_vocab_nll.hip; ROWS = false only):
+// EPI picks what stands behind a column block's last k stage (ABI 38, ea_vocab_nll.hip; with ROWS = true: ea_adaptive_nll.hip,
+// where VS_EPI_GRAD writes zeros at dead positions and VS_EPI_GEMM sends its output rows through a list):
 //   VS_EPI_SCORE  the above: every `if constexpr` on EPI falls away and the kernels of ABI 30 / 33 are what they were.
 //   VS_EPI_GRAD   a VocabNllGradP: the logit tiles of the table's columns [v0, v0 + Vc) are formed again -- the same k order
 //                 per accumulator, so the same bits -- and G = d ((v == target) - expf(a - lse)) is stored in 16 bits, row-major
@@ -46,6 +48,8 @@ constexpr int VS_EPI_SCORE = 0, VS_EPI_GRAD = 1, VS_EPI_GEMM = 2;
 template <bool ROWS, int EPI> struct VsEpiParams { using type = VsParams<ROWS>; };
 template <> struct VsEpiParams<false, VS_EPI_GRAD> { using type = VocabNllGradP; };
 template <> struct VsEpiParams<false, VS_EPI_GEMM> { using type = GemmNt16P; };
+template <> struct VsEpiParams<true, VS_EPI_GRAD> { using type = VocabNllGradRowsP; };
+template <> struct VsEpiParams<true, VS_EPI_GEMM> { using type = GemmNt16RowsP; };
 
 // a takes b's place: a NaN beats every number, a larger number a smaller one, and of two equals (two NaNs, +0 and -0) the
 // lower index (the few-row entries' voc_beats).  Selects, no branches: the epilogue is straight-line code.
@@ -80,6 +84,20 @@ template <> struct VsX<false> {
   template <typename E> EA_DEV u32x4 frag() const { return v; }
 };
 
+// zeros in rows [r0, r1) x columns [c0, c1) of a 16-bit image of row stride ld, by the workgroup's threads together: the image
+// is 16-byte aligned, ld and c1 are multiples of 8; 2-byte stores up to the first multiple of 8, 16-byte stores behind it
+EA_DEV void vs_zero_block(uint16_t* img, int64_t ld, int64_t r0, int64_t r1, int64_t c0, int64_t c1, int tid) {
+  if (r1 <= r0 || c1 <= c0) return;
+  const int64_t a0 = min(c1, (c0 + 7) / 8 * 8);
+  const int64_t hn = a0 - c0, per = hn + (c1 - a0) / 8, n = per * (r1 - r0);
+  for (int64_t at = tid; at < n; at += VS_THREADS) {
+    const int64_t r = at / per, i = at - r * per;
+    uint16_t* row = img + (r0 + r) * ld;
+    if (i < hn) row[c0 + i] = 0;
+    else *reinterpret_cast<u32x4*>(row + a0 + 8 * (i - hn)) = u32x4{0u, 0u, 0u, 0u};
+  }
+}
+
 // how many of the call's M positions are live: M itself, or the device count, kept inside [0, M]
 template <bool ROWS> EA_DEV int vs_live(const VsParams<ROWS>& p) {
   if constexpr (ROWS) {
@@ -101,7 +119,6 @@ template <bool ROWS> EA_DEV int32_t vs_target(const VsParams<ROWS>& p, int m) {
 
 template <typename E, bool XF32, bool ROWS, int EPI = VS_EPI_SCORE>
 __global__ __launch_bounds__(VS_THREADS) void vocab_score_kernel(const typename VsEpiParams<ROWS, EPI>::type p) {
-  static_assert(EPI == VS_EPI_SCORE || !ROWS, "the gradient and the plain GEMM take every row of the call");
   constexpr int SL = EPI == VS_EPI_GEMM ? VS_BN : VS_SL;   // columns of one workgroup
   extern __shared__ __attribute__((aligned(16))) char vs_lds[];
   int32_t* tgts = reinterpret_cast<int32_t*>(vs_lds + VS_LDS_TGT);
@@ -112,7 +129,7 @@ __global__ __launch_bounds__(VS_THREADS) void vocab_score_kernel(const typename 
   const int slice = blockIdx.x / p.MT;
   const int m0 = (blockIdx.x - slice * p.MT) * VS_BM;
   const int live = vs_live<ROWS>(p);                   // (ROWS = false: p.M)
-  if constexpr (ROWS) {
+  if constexpr (ROWS && EPI != VS_EPI_GRAD) {
     if (m0 >= live) return;                            // (uniform: the whole workgroup, before its first operand load)
   }
   int s0 = slice * SL;                                 // (< V)
@@ -120,6 +137,19 @@ __global__ __launch_bounds__(VS_THREADS) void vocab_score_kernel(const typename 
   if constexpr (EPI == VS_EPI_GRAD) {                  // (the chunk's slices: s0 < v0 + Vc <= V)
     s0 += p.v0;
     ncols = min(SL, p.v0 + p.Vc - s0);
+  }
+  // ROWS, VS_EPI_GRAD: what the two GEMMs contract over and no live position fills, as zeros, each element by this workgroup
+  // alone: the tile's positions at or beyond the live count (rows of g, columns of gt) over this slice's columns, the pad
+  // columns Vc .. ldg - 1 of the tile's live rows (the chunk's last slice) and the pad columns M .. ldm - 1 of gt (the last
+  // row tile).  A workgroup whose whole tile is dead does this and returns before its first operand load.
+  if constexpr (ROWS && EPI == VS_EPI_GRAD) {
+    const int64_t rend = min(m0 + VS_BM, p.M), rl = min((int64_t)max(live, m0), rend);
+    const int64_t tile_end = m0 + VS_BM >= p.M ? p.ldm : m0 + VS_BM;
+    const int64_t c_lo = (int64_t)slice * SL, c_hi = slice == p.NS - 1 ? p.ldg : c_lo + ncols;
+    vs_zero_block(p.g, p.ldg, rl, rend, c_lo, c_hi, tid);
+    if (slice == p.NS - 1) vs_zero_block(p.g, p.ldg, m0, rl, p.Vc, p.ldg, tid);
+    vs_zero_block(p.gt, p.ldm, c_lo, c_lo + ncols, rl, tile_end, tid);
+    if (m0 >= live) return;                            // (uniform)
   }
   const int nblk = (ncols + VS_BN - 1) / VS_BN;
   const int KT = (p.K + VS_BK - 1) / VS_BK;
@@ -186,8 +216,18 @@ __global__ __launch_bounds__(VS_THREADS) void vocab_score_kernel(const typename 
 #pragma unroll
     for (int q = 0; q < 8; ++q) {
       const int m = m0 + wm * 32 + 16 * (q >> 2) + 4 * g + (q & 3);
-      gd[q] = m < live ? p.d[m] : 0.f;
+      if constexpr (ROWS) gd[q] = m < live ? p.d[p.trows ? (int64_t)p.trows[m] : (int64_t)m] : 0.f;
+      else gd[q] = m < live ? p.d[m] : 0.f;
       gl[q] = m < live ? p.lse_in[m] : 0.f;
+    }
+  }
+  // ROWS, VS_EPI_GEMM: the row of out that position 16 i + 4 g + r (of the wave's 32) writes, entry 4 i + r
+  [[maybe_unused]] int64_t orow[8];
+  if constexpr (ROWS && EPI == VS_EPI_GEMM) {
+#pragma unroll
+    for (int q = 0; q < 8; ++q) {
+      const int m = m0 + wm * 32 + 16 * (q >> 2) + 4 * g + (q & 3);
+      orow[q] = m < live && p.orows ? (int64_t)p.orows[m] : (int64_t)m;
     }
   }
 
@@ -296,7 +336,9 @@ __global__ __launch_bounds__(VS_THREADS) void vocab_score_kernel(const typename 
             for (int j = 0; j < 4; ++j) {
               const int cs = c0 + 16 * j;
               if (cs < ncols && m < live) {
-                float* at = reinterpret_cast<float*>(p.logits) + (int64_t)m * p.ldl + s0 + cs;
+                int64_t om = m;
+                if constexpr (ROWS) om = orow[4 * i + r];
+                float* at = reinterpret_cast<float*>(p.logits) + om * p.ldl + s0 + cs;
                 *at = p.accumulate ? *at + acc[i][j][r] : acc[i][j][r];
               }
             }
@@ -354,7 +396,7 @@ __global__ __launch_bounds__(VS_THREADS) void vocab_score_kernel(const typename 
     blk = blk_next; kt = kt_next;
     __syncthreads();
   }
-  if constexpr (EPI == VS_EPI_GRAD) {
+  if constexpr (EPI == VS_EPI_GRAD && !ROWS) {
     // the pad positions the two GEMMs contract over, as zeros: columns Vc .. ldg - 1 of this tile's rows of G by the
     // workgroups of the chunk's last slice, rows M .. ldm - 1 of this slice's rows of G^T by those of the last row tile
     if (slice == p.NS - 1) {

@@ -21,6 +21,9 @@ as WHOLE models (eager, autocast, DistributedDataParallel over RCCL) on syntheti
   vocab_loss            -- vocab_nll: the vocabulary cross-entropy of the plain tied table as one autograd Function,
                            ea_vocab_score forward and a chunked HIP backward (ea_vocab_nll_grad, ea_gemm_nt16), without
                            a [rows, V] tensor; DecoderStack.loss is the stack's forward in front of it
+  adaptive_loss         -- adaptive_nll: fairseq's adaptive-softmax criterion as one autograd Function, ea_adaptive_score
+                           forward and a HIP backward over device-counted row lists (ea_vocab_nll_grad_rows,
+                           ea_gemm_nt16_rows, ea_rows_transpose16); DecoderStack.adaptive_loss is the stack in front of it
   trainer               -- one synthetic training step (forward, loss, backward, optimizer) eagerly or
                            captured in a hipGraph, single process or one process per GPU
 

@@ -273,6 +273,7 @@ class DecoderStack(nn.Module):
     decoding state pick greedily from the held adaptive tables (ea_adaptive_pick, C ABI 34): `next_tokens`, `token_logprobs`,
     `score` and `generate` run on it.  `logits` is the slow torch route (a state without it), and
     `init_decoding(hold_vocab=True)` raises: sampled and beam decoding from the adaptive head are out of scope.
+    `adaptive_loss` is such a stack's training loss (fairseq's criterion, ea_harness/adaptive_loss.py); `loss` is the plain one's.
 
     Incremental decoding runs on the attention's static / rolling states (CausalEVAttention.init_*_decoding):
         state = stack.init_decoding(B, max_tokens, torch.bfloat16, "cuda")
@@ -789,10 +790,10 @@ class DecoderStack(nn.Module):
         loss 0 and add exact zeros to every gradient.  reduction: "mean" (over the non-pad targets, counted on the device;
         nothing is read back), "sum", or "none" (fp32 [B, T - 1]; in eval mode -`evaluate(tokens)` bit for bit).  The table
         is the tied embedding: autograd adds the lookup's gradient to the projection's by itself.
-        On an adaptive stack: NotImplementedError (the adaptive-softmax loss is a follow-up)."""
+        On an adaptive stack: NotImplementedError; the adaptive-softmax loss is `adaptive_loss`."""
         if self.is_adaptive:
-            raise NotImplementedError("loss on an adaptive stack: the adaptive-softmax training loss is a follow-up (it would "
-                                      "reuse ea_vocab_nll_grad and ea_gemm_nt16 per band); this loss takes the plain tied table")
+            raise NotImplementedError("loss on an adaptive stack: the adaptive-softmax training loss is a follow-up to this "
+                                      "method and lives in adaptive_loss(tokens, ...); loss takes the plain tied table")
         if reduction not in ("mean", "sum", "none"):
             raise ValueError("reduction must be 'mean', 'sum' or 'none', got %r" % (reduction,))
         B, T = tokens.shape
@@ -803,6 +804,42 @@ class DecoderStack(nn.Module):
         targets = tokens[:, 1:].t().contiguous()
         pad = targets.eq(self.pad_idx)
         nll = -vocab_nll(rows, self.embed_tokens.weight, targets).masked_fill(pad, 0.0)
+        if reduction == "none":
+            return nll.t().contiguous()
+        if reduction == "sum":
+            return nll.sum()
+        return nll.sum() / pad.logical_not().sum().clamp(min=1)
+
+    # ---- the adaptive-softmax training loss (ea_adaptive_score forward, ea_adaptive_nll.hip backward) ---------------------------
+    def adaptive_loss(self, tokens, key_padding_mask=None, reduction="mean"):
+        """fairseq's `adaptive_loss` criterion with a gradient, on an adaptive stack: the contract of `loss` (tokens [B, T]
+        int64 -> the negative log-likelihood of tokens[:, 1:]; pad targets have loss 0 and add exact zeros to every gradient;
+        reduction "mean" over the non-pad targets counted on the device, "sum", or "none": fp32 [B, T - 1], in eval mode
+        -`evaluate(tokens)` bit for bit).  Runs the full forward on tokens[:, :-1], then `ea_harness.adaptive_loss.adaptive_nll`
+        on the adaptive softmax's parameters: ea_adaptive_score forward, HIP kernels backward, no [rows, V], [rows, c0 + n] or
+        [rows_i, V_i] tensor and nothing read back.  The band tables and projections are tied to the adaptive input: autograd
+        adds the input side's gradients by itself.
+        In training mode with `adaptive_softmax.dropout` = p > 0 both of fairseq's dropouts apply: F.dropout on the rows in
+        front, and inside each tail a mask of {0, 1 / (1 - p)} in the tables' dtype on h_i, drawn by the framework's generator
+        (graph-safe), one row per position of the tail's list.  On a stack without `adaptive`: RuntimeError."""
+        if not self.is_adaptive:
+            raise RuntimeError("adaptive_loss needs a stack built with adaptive=dict(cutoff=...); a plain tied table trains with loss")
+        if reduction not in ("mean", "sum", "none"):
+            raise ValueError("reduction must be 'mean', 'sum' or 'none', got %r" % (reduction,))
+        B, T = tokens.shape
+        if T < 2:
+            raise ValueError("adaptive_loss needs at least two tokens per row, got %d" % T)
+        from .adaptive_loss import adaptive_nll, operand_dtype
+        sm = self.adaptive_softmax
+        rows = self(tokens[:, :-1], key_padding_mask)                        # [T - 1, B, C]
+        targets = tokens[:, 1:].t().contiguous()
+        pad = targets.eq(self.pad_idx)
+        masks = None
+        if self.training and sm.dropout > 0:
+            rows = F.dropout(rows, sm.dropout, True)
+            E = operand_dtype(rows, sm)
+            masks = [F.dropout(torch.ones(((T - 1) * B, d), dtype=E, device=rows.device), sm.dropout, True) for d in sm.band_dims()]
+        nll = -adaptive_nll(rows, sm, targets, tail_masks=masks).masked_fill(pad, 0.0)
         if reduction == "none":
             return nll.t().contiguous()
         if reduction == "sum":

@@ -278,6 +278,11 @@ SIGNATURES = {
     "ea_vocab_nll_ws": [_I, _I, _I, _I],
     "ea_vocab_nll_grad": [_I, _I, _I, _P, _I, _L, _P, _I, _P, _P, _P, _I, _I, _P, _L, _P, _L, _P],
     "ea_gemm_nt16": [_I, _I, _I, _P, _L, _P, _L, _I, _P, _L, _I, _P],
+    "ea_adaptive_nll_ws": [_I, _I, _I, _P, _P, _I],
+    "ea_vocab_nll_grad_rows": [_I, _I, _I, _P, _I, _L, _P, _I, _P, _P, _P, _I, _I, _P, _L, _P, _L, _P, _P, _L, _P],
+    "ea_gemm_nt16_rows": [_I, _I, _I, _P, _L, _P, _L, _I, _P, _L, _I, _P, _P, _P],
+    "ea_rows_transpose16": [_I, _I, _P, _I, _L, _P, _P, _P, _I, _L, _P],
+    "ea_adaptive_score_masked": [_I, _I, _I, _P, _P, _P, _I, _L, _P, _P, _I, _P, _P, _P, _P, _L, _P, _P, _P],
     "ea_adaptive_route": [_I, _I, _P, _P, _P, _P, _P, _P],
     "ea_vocab_score_rows_ws": [_I, _I],
     "ea_vocab_score_rows": [_I, _I, _I, _P, _I, _L, _P, _I, _P, _P, _I, _L, _P, _L, _P, _P, _P, _P, _P, _P, _L, _I, _P],
@@ -335,6 +340,7 @@ def lib():
         cdll.ea_vocab_score_ws.restype = ctypes.c_int64
         cdll.ea_vocab_score_rows_ws.restype = ctypes.c_int64
         cdll.ea_vocab_nll_ws.restype = ctypes.c_int64
+        cdll.ea_adaptive_nll_ws.restype = ctypes.c_int64
         cdll.ea_adaptive_score_ws.restype = ctypes.c_int64
         cdll.ea_adaptive_pick_ws.restype = ctypes.c_int64
         cdll.ea_adaptive_sample_ws.restype = ctypes.c_int64

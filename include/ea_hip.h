@@ -1623,6 +1623,68 @@ int ea_vocab_nll_grad(int32_t M, int32_t K, int32_t V, const void* x, int32_t x_
 int ea_gemm_nt16(int32_t M, int32_t N, int32_t K, const void* a, int64_t lda, const void* b, int64_t ldb, int32_t dtype,
                  float* out, int64_t ldo, int32_t accumulate, void* stream);
 
+/* ADDITIONS TO ABI 38, THE ADAPTIVE-SOFTMAX TRAINING LOSS (ea_harness.adaptive_loss.adaptive_nll, DecoderStack.adaptive_loss;
+ * ea_adaptive_nll.hip).  No existing signature changes, so the ABI number stays 38: the entries below are additions.
+ * The forward is ea_adaptive_score (or ea_adaptive_score_masked) and its workspace is kept: head_target, rows, count, lse_head,
+ * h_i and lse_i are read out of it (the layout above).  With d = dlogp (fp32 [M]):
+ *   head, every row:  ea_vocab_nll's chunk loop on the head table [c0 + n, C] with head_target and lse_head: dX, d head.
+ *   tail i, positions j < count_i:  G_i[j, u] = d[rows_i[j]] ((u == t - c_i) - exp(b_i[j, u] - lse_i[j]));  dE_i = G_i^T h_i;
+ *   dh_i = G_i E_i (fp32, summed over the chunks in table order);  dQ_i = dh_i^T x[rows_i];  dX[rows_i] += dh_i Q_i.
+ * The rounding of h_i passes the gradient straight through.  Launches per tail: ea_rows_transpose16 (h_i^T), per chunk
+ * ea_vocab_nll_grad_rows, ea_gemm_nt16_rows (dh_i) and ea_gemm_nt16 (dE_i), then ea_rows_transpose16 (x[rows_i]^T), ea_gemm_nt16
+ * (dQ_i) and ea_gemm_nt16_rows (dX).  Everything is sized for M positions per tail; the counts stay on the device.  Every
+ * kernel: ordinary vector stores, no atomics, no workgroup waits for another, every output element written by one thread of
+ * one launch: bitwise reproducible.
+ *
+ * ea_vocab_nll_grad_rows: ea_vocab_nll_grad over a device-counted set of M POSITIONS.  Its arguments, then trows (int32 [M] or
+ * NULL: targets and d are read at trows[j]; x and lse are indexed by the position j, as in the tail pass of the scorer), count
+ * (int32 device scalar or NULL: M; kept inside [0, M]) and target_base (>= 0, taken off a target before the range test).
+ * Positions at or beyond *count: their rows of g (columns 0 .. ldg - 1) and their columns of gt are WRITTEN as zeros, also by
+ * workgroups whose whole row tile is dead, which store zeros and load nothing.  Inside the last live tile a position >= *count
+ * is clamped to *count - 1 before any list is read: a stale list entry is never dereferenced; *count == 0 reads nothing through
+ * a list.  With trows = count = NULL and target_base = 0: ea_vocab_nll_grad's bits.
+ * EA_E_BADARG: ea_vocab_nll_grad's; also trows or count not 4-byte aligned, target_base < 0.  EA_E_UNSUPPORTED: its own.
+ *
+ * ea_gemm_nt16_rows: ea_gemm_nt16 over M positions of which *count are live: out[orows[j], n] (+)= sum_k a[j, k] b[n, k] for
+ * j < *count (orows int32 [M] or NULL: the identity; count NULL: M).  Positions at or beyond *count write nothing and read no
+ * list entry; a workgroup whose tile is dead returns before its first load.  The rows named by orows must be distinct.
+ * EA_E_BADARG: ea_gemm_nt16's; also orows or count not 4-byte aligned.  EA_E_UNSUPPORTED: its own.
+ *
+ * ea_rows_transpose16: out[k, j] = E(src[rows[j], k]) for j < *count and k < K, ZEROS for *count <= j < ldm: a 16-bit [K, ldm]
+ * image (E = out_dtype) of rows of src [*, ld] (src_dtype = EA_F32, rounded to nearest even, or out_dtype), through an optional
+ * int32 list (NULL: the identity) and an optional device count (NULL: M).  A row at or beyond the count is not read, whatever
+ * it holds.  EA_E_BADARG: src or out NULL, src, rows or count not 4-byte, out not 2-byte aligned; out_dtype not 16-bit,
+ * src_dtype neither EA_F32 nor out_dtype; M < 1, K < 1, ld < K, ldm < M, ldm no multiple of 64.  EA_E_UNSUPPORTED: K > 64 * 65535.
+ *
+ * ea_adaptive_score_masked: ea_adaptive_score plus hmask, a HOST array of n_tails entries: hmask[i] NULL or 16-bit multipliers
+ * [M, d_i] of w_dtype, indexed by POSITION, 16-byte aligned.  A non-NULL entry adds one elementwise launch between the
+ * projection and the tail pass of that band, h_i = E(fp32(h_i) * fp32(mask)) on the live positions -- the Dropout inside
+ * fairseq's tail[i].  With every entry NULL it is ea_adaptive_score's code path and gives its bits.  EA_E_BADARG:
+ * ea_adaptive_score's; also hmask NULL or an entry not 16-byte aligned.  EA_E_UNSUPPORTED: ea_adaptive_score's.
+ *
+ * ea_adaptive_nll_ws(M, C, n_tails, cutoffs, dims, chunk_cols): the bytes the backward holds beyond its outputs (the fp32
+ * gradients) and the saved workspace, with ldm = up64(M), V_i = c_{i+1} - c_i:
+ *   max(ea_vocab_nll_ws(M, C, c0 + n_tails, chunk_cols), max_i ea_vocab_nll_ws(M, d_i, V_i, chunk_cols))
+ *   + 2 C ldm + max_i (6 M d_i + 2 d_i ldm + 2 C d_i)
+ * -- the largest chunk pass (g, gt, the chunk's transposed table, and X^T or h_i^T), x[rows_i]^T, and of the largest tail dh_i
+ * in fp32, dh_i in 16 bits, its transpose and Q_i^T.  It does not grow with M V.  chunk_cols as in ea_vocab_nll_ws (0: each
+ * pass's default).  < 0: M < 1, C < 1, n_tails outside 1 .. EA_ADAPTIVE_MAX_TAILS, cutoffs not increasing, c0 < 1, V >= 2^31,
+ * d_i < 1, or a pass ea_vocab_nll_ws refuses.  A host-known cap on the rows per tail would shrink it; there is none. */
+int64_t ea_adaptive_nll_ws(int32_t M, int32_t C, int32_t n_tails, const int64_t* cutoffs, const int32_t* dims,
+                           int32_t chunk_cols);
+int ea_vocab_nll_grad_rows(int32_t M, int32_t K, int32_t V, const void* x, int32_t x_dtype, int64_t ldx, const void* w,
+                           int32_t w_dtype, const int64_t* targets, const float* lse, const float* d, int32_t v0, int32_t Vc,
+                           void* g, int64_t ldg, void* gt, int64_t ldm, const int32_t* trows, const int32_t* count,
+                           int64_t target_base, void* stream);
+int ea_gemm_nt16_rows(int32_t M, int32_t N, int32_t K, const void* a, int64_t lda, const void* b, int64_t ldb, int32_t dtype,
+                      float* out, int64_t ldo, int32_t accumulate, const int32_t* orows, const int32_t* count, void* stream);
+int ea_rows_transpose16(int32_t M, int32_t K, const void* src, int32_t src_dtype, int64_t ld, const int32_t* rows,
+                        const int32_t* count, void* out, int32_t out_dtype, int64_t ldm, void* stream);
+int ea_adaptive_score_masked(int32_t M, int32_t C, int32_t n_tails, const int64_t* cutoffs, const int32_t* dims, const void* x,
+                             int32_t x_dtype, int64_t ldx, const int64_t* targets, const void* head, int32_t w_dtype,
+                             const void* const* proj, const void* const* tables, const void* const* hmask, void* ws,
+                             int64_t ws_bytes, float* logp, int64_t* token_head, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
