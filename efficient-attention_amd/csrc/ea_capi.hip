@@ -650,8 +650,9 @@ int ea_performer_bwd_k(const ea_perf_geom* g, const ea_t4* k, const ea_t4* v, co
 
 // ---- fused LARA landmark pipeline ----
 static int fill_lmk(const ea_lmk_geom* g, LmkP& p) {
-  if (!g || g->BH <= 0 || g->L <= 0 || g->C <= 0 || (g->D != 32 && g->D != 64)) return EA_E_BADARG;
-  if (g->L > 64 || g->C > 64) return EA_E_UNSUPPORTED;
+  if (!g || g->BH <= 0 || g->L <= 0 || g->C <= 0 || g->D <= 0) return EA_E_BADARG;
+  // a geometry outside the second-generation kernels is well-formed but not built for (ea_hip.h; lara_lmk_dispatch says the same)
+  if (g->L > 64 || g->C > 64 || (g->D != 32 && g->D != 64)) return EA_E_UNSUPPORTED;
   if (g->C % g->L != 0 || (g->dup == 0 && g->C != g->L) || (g->dup != 0 && g->C != 2 * g->L)) return EA_E_BADARG;
   if (g->mis < 0 || g->mis > 2 || g->dup < 0 || g->dup > 2) return EA_E_BADARG;
   p.BH = g->BH; p.L = g->L; p.C = g->C; p.D = g->D;
@@ -704,7 +705,7 @@ int ea_lara_landmarks_fwd_cb(const ea_lmk_geom* g, const float* pq, const float*
 
 int64_t ea_lara_landmarks_saved_floats(const ea_lmk_geom* g) {
   LmkP p = {};
-  if (fill_lmk(g, p) != EA_OK) return EA_E_BADARG;
+  if (const int rc = fill_lmk(g, p)) return rc;
   return (int64_t)g->BH * (int64_t)lara_lmk_saved_per_bh(g->L, g->D);
 }
 

@@ -425,7 +425,8 @@ int ea_kernelized_bwd_k(const ea_kz_geom* g, const ea_t4* k, const ea_t4* v, con
                         float* p_dw, void* stream);
 
 /* ---- LARA landmark pipeline, fused (lara.py:145-198,214-238) -----------------------------------
- * One workgroup per (b,h), all matrices in LDS, exact fp32:
+ * One workgroup per (b,h); fp32 in and out, the row-wise steps (LayerNorm, softmax, norms, column sums) in fp32, every
+ * matrix product on fp16 MFMA operands with fp32 accumulation (the gradient-side ones behind a power-of-two scale):
  *   q_bar = LN(pq Wq^T + bq), k0 = LN(pk Wk^T + bk)         (has_mlp; else q_bar = pq, k0 = pk)
  *   k_bar = softmax(s k0 k0^T) k0                            (mixed; else k_bar = k0)
  *   mu = q_bar + k_bar;  omega_c = mu[c mod L] + eps_c       (dup 0: C = L; 1 antithetic: C = 2L,
@@ -438,7 +439,10 @@ int ea_kernelized_bwd_k(const ea_kz_geom* g, const ea_t4* k, const ea_t4* v, con
  * Outputs omega, qbar_rows [BH,C,D], bhv, lp [BH,C] feed ea_lara_*.  The backward takes their
  * gradients and returns d pq, d pk [BH,L,D] plus per-(b,h) partial parameter gradients
  * dW_part [BH,2,D,D] (q then k; [out][in]) and dvec_part [BH,2,3,D] (Linear bias, LN weight, LN
- * bias) which the caller sums over BH.  L, C <= 64.
+ * bias) which the caller sums over BH.  L, C <= 64 and D in {32, 64}: every entry of this block, the size
+ * query included, answers EA_E_UNSUPPORTED for a well-formed geometry outside them (D = 128, L = 65, C = 128) and
+ * EA_E_BADARG for a malformed one (C != L without dup, C != 2 L with it, mis or dup out of range, eva with dup or
+ * without the MLP), before anything is launched.
  * `saved`: workspace of ea_lara_landmarks_saved_floats(g) floats in which the forward keeps its
  * intermediates (normalised rows, LayerNorm 1/std, mixing matrix, mu) for the backward.  NULL in a
  * forward that will not be differentiated; the backward of a parametrised (has_mlp) or mixed pipeline
