@@ -283,7 +283,10 @@ FACTOR = 4.0          # 2 (what M does not model: fp32 accumulation order, v_exp
 
 
 def floor_for(name, round_to):
-    """f of the bound: half an ulp of the largest element for tensors stored in 16 bits, 2^-20 for fp32 results."""
+    """f of the bound: half an ulp of the largest element for tensors stored in 16 bits, 2^-20 for fp32 results (under fp32 I/O,
+    round_to = torch.float32, every result is one)."""
+    if round_to == torch.float32:
+        return 2.0 ** -20
     if name in ("out", "dq", "dk", "dv"):
         return 2.0 ** -9 if round_to == torch.bfloat16 else 2.0 ** -12
     return 2.0 ** -20
