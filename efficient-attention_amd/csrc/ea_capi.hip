@@ -876,8 +876,11 @@ int ea_slice_sum(int32_t BH, int32_t S, int32_t n, float scale, const float* a, 
 
 // ---- LARA 1-D landmark proposals: segment means of (LayerNorm'd) rows ----
 static int fill_seg(const ea_geom* g, SegP& p) {
-  if (!g || g->B <= 0 || g->H <= 0 || g->N <= 0 || g->L <= 0 || (g->D != 32 && g->D != 64) ||
-      (g->dtype != EA_BF16 && g->dtype != EA_F16)) return EA_E_BADARG;
+  if (!g || g->B <= 0 || g->H <= 0 || g->N <= 0 || g->L <= 0 || g->D <= 0 ||
+      (g->dtype != EA_BF16 && g->dtype != EA_F16 && g->dtype != EA_F32)) return EA_E_BADARG;
+  // a well-formed geometry the kernels are not built for (include/ea_hip.h: EA_E_UNSUPPORTED), as lara_segment_dispatch and
+  // seglin_dispatch class it themselves
+  if ((g->D != 32 && g->D != 64) || g->dtype == EA_F32) return EA_E_UNSUPPORTED;
   if (g->N <= g->L) return EA_E_UNSUPPORTED;            // the reference uses the rows themselves then
   p.B = g->B; p.H = g->H; p.N = g->N; p.L = g->L;
   p.segs = g->N / g->L;

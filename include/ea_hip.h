@@ -552,7 +552,8 @@ int ea_stream_copy(const void* src, void* dst, int64_t bytes, void* stream);
  * Segment means over the sequence, q_bar_l = mean_{n in segment l} row_n, with the reference's
  * split of N tokens into L = g->L segments (N % L == 0: equal; otherwise (segs+1)L - N segments of
  * segs = N / L tokens followed by segments of segs + 1).  Geometry: ea_geom with B, H, N, D, dtype,
- * L (other fields ignored); N > L.
+ * L (other fields ignored); N > L.  D in {32, 64} and a 16-bit dtype; another D > 0, EA_F32 and N <= L are
+ * EA_E_UNSUPPORTED (well-formed, outside the kernels), a non-positive size or an unknown dtype EA_E_BADARG.
  *   'adaptive-1d' (gq != NULL): row_n = LayerNorm(x_n + bias), x = the rows q2 / k2 [B,H,N,D]
  *   (element type) holding Linear(q) WITHOUT its bias -- the host folds that Linear into the qkv
  *   projection --, bias = bias_q/k [H,D] for ordinary tokens and mbias_q/k [D] for tokens under

@@ -5,7 +5,8 @@ recipe) vs the golden vectors of the fp32 reference.  The core-level checks -- a
 fp64 evaluation of the same operands -- live in test_gpu_window_core.py (16-bit window and EVA landmark
 kernels, bound relative to a rounding model: tests/window_reference.py), test_gpu_lara_core.py (the 16-bit LARA
 estimator passes, the same bound: tests/lara_reference.py), test_gpu_lmk_core.py (the LARA / EVA landmark pipeline,
-the same bound: tests/lmk_reference.py), test_gpu_kz_core.py (the kernelized-attention feature-map kernels and the Performer's
+the same bound: tests/lmk_reference.py), test_gpu_seg_core.py (LARA's 1-D segment kernels with and without the generator Linear,
+the fused finish and the overlapping adaptive pool, the same bound in bf16 and fp16: tests/seg_reference.py), test_gpu_kz_core.py (the kernelized-attention feature-map kernels and the Performer's
 exact-fp32 unit, the same bound at the fp32 level: tests/kz_reference.py), test_gpu_scatter_overlap.py (ScatterBrain's
 feature half) and test_gpu_f32_cores.py (the exact-fp32 cores).
 
