@@ -26,7 +26,8 @@ LIB_SOURCES = ["ea_capi.hip", "ea_window_fwd.hip", "ea_window_bwd.hip", "ea_eva_
                "ea_rows_mlp.hip", "ea_wgrad.hip", "ea_linear.hip", "ea_lmk2.hip", "ea_scatter.hip", "ea_proj_rs.hip",
                "ea_performer_f32.hip", "ea_fold.hip", "ea_lara_seglin.hip", "ea_layernorm.hip", "ea_dgrad_rs.hip", "ea_f32_attn.hip",
                "ea_kernelized.hip", "ea_ceva_decode.hip", "ea_ceva_decode_linear.hip", "ea_ceva_decode_vocab.hip", "ea_lara_xp.hip",
-               "ea_vocab_score.hip", "ea_adaptive_score.hip", "ea_adaptive_pick.hip", "ea_vocab_nll.hip", "ea_adaptive_nll.hip"]
+               "ea_vocab_score.hip", "ea_adaptive_score.hip", "ea_adaptive_pick.hip", "ea_vocab_nll.hip", "ea_adaptive_nll.hip",
+               "ea_linear_rs192.hip"]
 
 
 def _cuid(src):

@@ -1426,7 +1426,7 @@ int ea_linear_w192_prepare(int32_t dtype, const float* wq, const float* wp, void
       ((uintptr_t)w16p & 15) || ((uintptr_t)w16pT & 15))
     return EA_E_BADARG;
   if (wp && (!w16p || !w16pT)) return EA_E_BADARG;
-  return w192_prepare_dispatch(dtype, wq, wp, w16q, wq_sw, w16p, w16pT, nullptr, (hipStream_t)stream);
+  return w192_prepare_dispatch(dtype, wq, wp, w16q, wq_sw, w16p, w16pT, nullptr, nullptr, nullptr, (hipStream_t)stream);
 }
 
 int ea_linear_w192_prepare_t(int32_t dtype, const float* wq, const float* wp, void* w16q, void* wq_sw, void* w16p, void* w16pT,
@@ -1435,7 +1435,28 @@ int ea_linear_w192_prepare_t(int32_t dtype, const float* wq, const float* wp, vo
       ((uintptr_t)wq_sw & 15) || ((uintptr_t)w16p & 15) || ((uintptr_t)w16pT & 15) || ((uintptr_t)wqT_sw & 15))
     return EA_E_BADARG;
   if (wp && (!w16p || !w16pT)) return EA_E_BADARG;
-  return w192_prepare_dispatch(dtype, wq, wp, w16q, wq_sw, w16p, w16pT, wqT_sw, (hipStream_t)stream);
+  return w192_prepare_dispatch(dtype, wq, wp, w16q, wq_sw, w16p, w16pT, wqT_sw, nullptr, nullptr, (hipStream_t)stream);
+}
+
+// ... and W_proj / W_proj^T in the register order of the 192 -> 192 register-resident kernel (ea_linear_rs192.hip)
+int ea_linear_w192_prepare_rs(int32_t dtype, const float* wq, const float* wp, void* w16q, void* wq_sw, void* w16p, void* w16pT,
+                              void* wqT_sw, void* wp_rs, void* wpT_rs, void* stream) {
+  if (!wq || !wp || !w16q || !wq_sw || !w16p || !w16pT || !wqT_sw || !wp_rs || !wpT_rs) return EA_E_BADARG;
+  if (((uintptr_t)wq & 15) || ((uintptr_t)wp & 15) || ((uintptr_t)w16q & 15) || ((uintptr_t)wq_sw & 15) || ((uintptr_t)w16p & 15) ||
+      ((uintptr_t)w16pT & 15) || ((uintptr_t)wqT_sw & 15) || ((uintptr_t)wp_rs & 15) || ((uintptr_t)wpT_rs & 15))
+    return EA_E_BADARG;
+  return w192_prepare_dispatch(dtype, wq, wp, w16q, wq_sw, w16p, w16pT, wqT_sw, wp_rs, wpT_rs, (hipStream_t)stream);
+}
+
+// Y = A W^T (+ bias) at 192 -> 192 from such an image, weight resident in registers (ea_linear_rs192.hip)
+int ea_linear_rs192(int32_t dtype, const void* a, int64_t lda, const void* image, const float* bias, void* y, int64_t ldy,
+                    int32_t rows, void* stream) {
+  if (dtype != EA_BF16 && dtype != EA_F16) return EA_E_BADARG;
+  if (rows <= 0) return EA_OK;
+  if (!a || !image || !y) return EA_E_BADARG;
+  if (((uintptr_t)a & 15) || ((uintptr_t)image & 15) || ((uintptr_t)y & 15) || ((uintptr_t)bias & 15)) return EA_E_UNSUPPORTED;
+  if (!linear_rs192_supported(rows, (long)lda, (long)ldy)) return EA_E_UNSUPPORTED;
+  return linear_rs192_dispatch(dtype, a, (long)lda, image, bias, y, (long)ldy, rows, (hipStream_t)stream);
 }
 
 int ea_linear_wsw(int32_t dtype, int32_t rows, int32_t B, int32_t gh, int32_t gw, int32_t r, const void* a, int32_t a_f32, int64_t lda,

@@ -12,6 +12,11 @@ int proj_rs_dispatch(int dtype, const void* a, int a_f32, const float* w, const 
                      long lda, long ldy, hipStream_t st, int B, int gh, int gw, int r, float* pq, float* pk, void* w_cast,
                      const void* wsw);
 int w192_prepare_dispatch(int dtype, const float* wq, const float* wp, void* w16q, void* wsw, void* w16p, void* w16pT, void* wtsw,
+                          void* wp_rs, void* wpT_rs, hipStream_t st);
+// ea_linear_rs192.hip: weight row behind MFMA row li of tile j of column pair `pair` (the image's piece order)
+constexpr int rs192_row(int pair, int j, int li) { return 32 * pair + 8 * (li >> 2) + (li & 3) + 4 * j; }
+int linear_rs192_supported(int rows, long lda, long ldy);
+int linear_rs192_dispatch(int dtype, const void* a, long lda, const void* wimg, const float* bias, void* y, long ldy, int rows,
                           hipStream_t st);
 int dgrad_rs_supported(int K, int NO);
 int dgrad_fin_launch(int dtype, const void* dqkv, long ldy, const void* qkv, long ldq, const void* w, int w_f32, void* dx, int dx_f32,

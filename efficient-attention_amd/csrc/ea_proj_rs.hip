@@ -293,13 +293,16 @@ int proj_rs_pool_supported(int K, int NO, int B, int gh, int gw, int r) {
 //   w16q [576, 192] (input gradient), wsw = the same values in proj_rs_kernel<.., WSW>'s staging order, w16p [192, 192] (output
 //   projection), w16pT = its transpose (the output projection's input gradient as the same streaming kernel);
 //   wtsw (or null) = wq's values once more, in the order the input-gradient kernels (ea_dgrad_rs.hip, WT) hold W^T: piece
-//   (wave, ks, lane = (g, li)) = W[32 ks + 8 g .. + 7][16 wave + li], 12 x 18 x 64 pieces of 16 bytes.
+//   (wave, ks, lane = (g, li)) = W[32 ks + 8 g .. + 7][16 wave + li], 12 x 18 x 64 pieces of 16 bytes;
+//   wp_rs, wpT_rs (or null) = wp's rounded values twice more, W_proj and W_proj^T in the register order of lin_rs192_kernel
+//   (ea_linear_rs192.hip: piece (pair, j, ks, lane) = row rs192_row(pair, j, li), channels 32 ks + 8 g .. + 7).
 // One thread per 8-element piece; round to nearest even like every cast of the library.
 template <typename E>
 __global__ __launch_bounds__(256) void w192_prepare_kernel(const float* __restrict__ wq, const float* __restrict__ wp,
                                                             char* __restrict__ w16q, char* __restrict__ wsw,
                                                             char* __restrict__ w16p, char* __restrict__ w16pT,
-                                                            char* __restrict__ wtsw) {
+                                                            char* __restrict__ wtsw, char* __restrict__ wp_rs,
+                                                            char* __restrict__ wpT_rs) {
   constexpr int NQ = RS_WAVES * 3 * RS_KT * 64, NP = RS_K * RS_K / 8, NT = 12 * (RS_NO / 32) * 64;
   const int i = blockIdx.x * 256 + threadIdx.x;
   if (i < NQ) {
@@ -318,6 +321,11 @@ __global__ __launch_bounds__(256) void w192_prepare_kernel(const float* __restri
     const float f[8] = {lo[0], lo[1], lo[2], lo[3], hi[0], hi[1], hi[2], hi[3]};
     const u32x4 w8 = pack8<E>(f);
     stg16(w16p + e * 2, w8);
+    if (wp_rs) {
+      // the same chunk in lin_rs192_kernel's register order: row = rs192_row(pair, j, li), chunk c = 4 ks + g
+      const int r = row & 31, li = 4 * (r >> 3) + (r & 3);
+      stg16(wp_rs + ((size_t)(((row >> 5) * 2 + ((r >> 2) & 1)) * RS_KT + (c >> 2)) * 64 + 16 * (c & 3) + li) * 16, w8);
+    }
     uint16_t* t = reinterpret_cast<uint16_t*>(w16pT);
 #pragma unroll
     for (int q = 0; q < 4; ++q) {
@@ -332,15 +340,26 @@ __global__ __launch_bounds__(256) void w192_prepare_kernel(const float* __restri
 #pragma unroll
     for (int q = 0; q < 8; ++q) f[q] = src[(size_t)q * RS_K];
     stg16(wtsw + (size_t)k * 16, pack8<E>(f));
+  } else if (i >= NQ + NP + NT && i < NQ + NP + NT + NP && wpT_rs) {
+    // W_proj^T in lin_rs192_kernel's register order: piece (pair, j, ks, lane) = wp[32 ks + 8 g .. + 7][rs192_row(pair, j, li)],
+    // eight elements down a column, rounded as w16p / w16pT round them
+    const int k = i - NQ - NP - NT, lane = k & 63, pc = k >> 6, ks = pc % RS_KT, pj = pc / RS_KT;
+    const int g = lane >> 4, li = lane & 15;
+    const float* src = wp + (size_t)(32 * ks + 8 * g) * RS_K + rs192_row(pj >> 1, pj & 1, li);
+    float f[8];
+#pragma unroll
+    for (int q = 0; q < 8; ++q) f[q] = src[(size_t)q * RS_K];
+    stg16(wpT_rs + (size_t)k * 16, pack8<E>(f));
   }
 }
 
 int w192_prepare_dispatch(int dtype, const float* wq, const float* wp, void* w16q, void* wsw, void* w16p, void* w16pT,
-                          void* wtsw, hipStream_t st) {
-  const int N = RS_WAVES * 3 * RS_KT * 64 + RS_K * RS_K / 8 + (wtsw ? 12 * (RS_NO / 32) * 64 : 0);
+                          void* wtsw, void* wp_rs, void* wpT_rs, hipStream_t st) {
+  const int N = RS_WAVES * 3 * RS_KT * 64 + RS_K * RS_K / 8 + ((wtsw || wpT_rs) ? 12 * (RS_NO / 32) * 64 : 0) +
+                (wpT_rs ? RS_K * RS_K / 8 : 0);
   const dim3 g((N + 255) / 256), b(256);
-  if (dtype == EA_BF16) hipLaunchKernelGGL(w192_prepare_kernel<BF16>, g, b, 0, st, wq, wp, (char*)w16q, (char*)wsw, (char*)w16p, (char*)w16pT, (char*)wtsw);
-  else if (dtype == EA_F16) hipLaunchKernelGGL(w192_prepare_kernel<F16>, g, b, 0, st, wq, wp, (char*)w16q, (char*)wsw, (char*)w16p, (char*)w16pT, (char*)wtsw);
+  if (dtype == EA_BF16) hipLaunchKernelGGL(w192_prepare_kernel<BF16>, g, b, 0, st, wq, wp, (char*)w16q, (char*)wsw, (char*)w16p, (char*)w16pT, (char*)wtsw, (char*)wp_rs, (char*)wpT_rs);
+  else if (dtype == EA_F16) hipLaunchKernelGGL(w192_prepare_kernel<F16>, g, b, 0, st, wq, wp, (char*)w16q, (char*)wsw, (char*)w16p, (char*)w16pT, (char*)wtsw, (char*)wp_rs, (char*)wpT_rs);
   else return EA_E_BADARG;
   return (int)hipGetLastError();
 }

@@ -178,6 +178,8 @@ SIGNATURES = {
     "ea_multi_cast": [_I, _I, _P, _P, _P, _P],
     "ea_linear_w192_prepare": [_I, _P, _P, _P, _P, _P, _P, _P],
     "ea_linear_w192_prepare_t": [_I, _P, _P, _P, _P, _P, _P, _P, _P],
+    "ea_linear_w192_prepare_rs": [_I] + [_P] * 10,
+    "ea_linear_rs192": [_I, _P, _L, _P, _P, _P, _L, _I, _P],
     "ea_linear_wsw": [_I, _I, _I, _I, _I, _I, _P, _I, _L, _P, _P, _P, _L, _P, _P, _P, _P],
     "ea_table_bias_bwd": [_I, _I, _I, _I, _I, _I, _F, _P, _P, _P, _P],
     "ea_linear_supported": [_I, _I],

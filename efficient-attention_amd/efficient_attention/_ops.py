@@ -1720,6 +1720,47 @@ def prepare_w192_t(wq, wp, cdtype):
     return _prepare_w192(wq, wp, cdtype, True)
 
 
+# The 192 -> 192 products of a prepared layer (output projection, its input gradient) on the register-resident kernel
+# (ea_linear_rs192); EA_LIN_RS192=0 (dev switch) keeps them on ea_linear and the prepare launch at five images.
+USE_LIN_RS192 = os.environ.get("EA_LIN_RS192", "1") == "1"
+
+
+def prepare_w192_rs(wq, wp, cdtype):
+    """prepare_w192_t with two more images from the same launch (ea_linear_w192_prepare_rs): W_proj and W_proj^T -- the bits of
+    w16p and w16pT -- in the register order of ea_linear_rs192: 16-byte piece ((pair * 2 + j) * 6 + ks) * 64 + 16 g + li =
+    W[32 pair + 8 (li >> 2) + (li & 3) + 4 j, 32 ks + 8 g .. + 7].  With EA_LIN_RS192=0 the two are None (prepare_w192_t's launch)."""
+    if not USE_LIN_RS192:
+        return _prepare_w192(wq, wp, cdtype, True) + (None, None)
+    dev = wq.device
+    w16q = torch.empty((576, 192), dtype=cdtype, device=dev)
+    wsw = torch.empty((576 * 192,), dtype=cdtype, device=dev)
+    wtsw = torch.empty((576 * 192,), dtype=cdtype, device=dev)
+    w16p, w16pT, wp_rs, wpT_rs = torch.empty((4, 192, 192), dtype=cdtype, device=dev).unbind(0)
+    nv.call("ea_linear_w192_prepare_rs", _ELEM[cdtype], nv.ptr(wq.detach()), nv.ptr(wp.detach()), nv.ptr(w16q), nv.ptr(wsw),
+            nv.ptr(w16p), nv.ptr(w16pT), nv.ptr(wtsw), nv.ptr(wp_rs), nv.ptr(wpT_rs), nv.stream())
+    return w16q, wsw, w16p, w16pT, wtsw, wp_rs.view(-1), wpT_rs.view(-1)
+
+
+def _rs192_rows_ok(a2, cdtype):
+    """What ea_linear_rs192 serves: _lin_rows_ok rows of the compute dtype, 192 wide, with a row stride of at least 192 (a
+    broadcast row, stride 0, passes _lin_rows_ok and stays on ea_linear)."""
+    return a2.dtype == cdtype and _lin_rows_ok(a2, cdtype) and a2.shape[1] == 192 and a2.stride(0) >= 192
+
+
+def linear_rs192(a2, image, bias32, cdtype):
+    """y = a2 @ W.T (+ bias) at 192 -> 192 from an image of prepare_w192_rs: the weight resident in registers (ea_linear_rs192),
+    ea_linear's bits.  a2 [rows, 192] in cdtype as _rs192_rows_ok asks."""
+    rows = a2.shape[0]
+    y = torch.empty((rows, 192), dtype=cdtype, device=a2.device)
+    label = "ea_linear_rs192"
+    if nv.KERNEL_TIMER.enabled:
+        label = "ea_linear_rs192[192->192,16->16]"
+        _note_bytes(label, rows * (192 * 2 + 192 * 2))
+    nv.call_as(label, "ea_linear_rs192", _ELEM[cdtype], nv.ptr(a2), a2.stride(0), nv.ptr(image), nv.ptr(bias32), nv.ptr(y), 192,
+               rows, nv.stream())
+    return y
+
+
 def _prepare_w192(wq, wp, cdtype, with_t):
     dev = wq.device
     w16q = torch.empty((576, 192), dtype=cdtype, device=dev)
@@ -2065,8 +2106,9 @@ class CoreModuleFn(torch.autograd.Function):
         want = x2.dtype == torch.float32 and need[1]
         lib = module_proj_lib(C)
         w16q = w16p = b16p = None
-        w192 = prepare_w192_t(wq, wp, cdtype) if (not lib and w192_usable(wq, wp, cdtype)) else None
+        w192 = prepare_w192_rs(wq, wp, cdtype) if (not lib and w192_usable(wq, wp, cdtype)) else None
         w16pT = None if w192 is None else w192[3]
+        wpT_rs = None if w192 is None else w192[6]
         if lib:
             w16q, b16q, w16p, b16p = lib_casts(wq, bq, wp, bp, cdtype)
             y, xc = lib_project(x2, wq, bq32, w16q, b16q, cdtype)
@@ -2094,13 +2136,15 @@ class CoreModuleFn(torch.autograd.Function):
         elif lib:
             with torch.autocast(device_type="cuda", enabled=False):
                 y2 = F.linear(o2, w16p, b16p)
+        elif w192 is not None and w192[5] is not None and _rs192_rows_ok(o2, cdtype):
+            y2 = linear_rs192(o2, w192[5], bp32, cdtype)
         elif w192 is not None:
             y2 = ea_linear(o2, w192[2], bp32, cdtype)[0]
         else:
             y2 = lin(o2, wp, bp32, elem, False, False, False)[0]
         # the prepared W^T goes with the rounded weight it was made from
         wqT = w192[4] if (w192 is not None and w16q is w192[0]) else None
-        ctx.save_for_backward(xl, qkv5, o2, wq, wp, w16q, w16p, w16pT, wqT, *saved)
+        ctx.save_for_backward(xl, qkv5, o2, wq, wp, w16q, w16p, w16pT, wqT, wpT_rs, *saved)
         ctx.core = core
         ctx.meta = (x.shape, x.dtype, cdtype, None if bq is None else bq.dtype, None if bp is None else bp.dtype, wq.dtype, wp.dtype,
                     heads, [None if t is None else t.dtype for t in inputs])
@@ -2108,7 +2152,7 @@ class CoreModuleFn(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, dy):
-        xl, qkv5, o2, wq, wp, w16q, w16p, w16pT, wqT, *saved = ctx.saved_tensors
+        xl, qkv5, o2, wq, wp, w16q, w16p, w16pT, wqT, wpT_rs, *saved = ctx.saved_tensors
         xshape, xdtype, cdtype, bqd, bpd, wqd, wpd, heads, in_dtypes = ctx.meta
         core = ctx.core
         C = xshape[-1]
@@ -2125,6 +2169,8 @@ class CoreModuleFn(torch.autograd.Function):
         if w16p is not None:
             dy2 = dy2 if dy2.is_contiguous() else dy2.contiguous()
             d_o2 = dy2 @ w16p
+        elif wpT_rs is not None and _rs192_rows_ok(dy2, cdtype):
+            d_o2 = linear_rs192(dy2, wpT_rs, None, cdtype)
         elif w16pT is not None and _lin_rows_ok(dy2, cdtype):
             d_o2 = ea_linear(dy2, w16pT, None, cdtype)[0]
         else:

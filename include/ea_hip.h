@@ -1690,6 +1690,27 @@ int ea_adaptive_score_masked(int32_t M, int32_t C, int32_t n_tails, const int64_
                              const void* const* proj, const void* const* tables, const void* const* hmask, void* ws,
                              int64_t ws_bytes, float* logp, int64_t* token_head, void* stream);
 
+/* ADDITIONS TO ABI 38, THE 192 -> 192 PROJECTION WITH ITS WEIGHT IN REGISTERS (ea_linear_rs192.hip).  No existing signature
+ * changes, so the ABI number stays 38: the two entries below are additions.
+ *
+ * ea_linear_rs192: Y[t][o] = sum_k A[t][k] W[o][k] (+ bias[o]) for K = out = 192, `rows` rows, A and Y in the EA dtype (bf16 /
+ * fp16) with row strides lda / ldy elements, `image` = the weight in the kernel's register order (below), bias fp32 [192] or
+ * NULL (rounded to the EA dtype before it is added, the sum rounded once).  One 12-wave workgroup per CU keeps the weight in
+ * registers for the whole launch and streams the rows through LDS once.  Y has the bits ea_linear gives on the same operands
+ * (its MFMA, its k-slots, its order of accumulation, its rounding of the bias).
+ *   image: 4608 pieces of 16 bytes; piece ((pair * 2 + j) * 6 + ks) * 64 + lane, with lane = 16 g + li, pair 0 .. 5, j 0 .. 1,
+ *   ks 0 .. 5, holds W[32 pair + 8 (li >> 2) + (li & 3) + 4 j][32 ks + 8 g .. 32 ks + 8 g + 7].
+ * rows <= 0: EA_OK, nothing launched.  EA_E_BADARG: dtype not 16-bit; a, image or y NULL.  EA_E_UNSUPPORTED, before any launch:
+ * a, image, y or bias not 16-byte aligned; lda or ldy below 192 or no multiple of 8; rows above 2^30 or rows * ld >= 2^40.
+ *
+ * ea_linear_w192_prepare_rs: ea_linear_w192_prepare_t (every pointer required, wp included) with two more images from the SAME
+ * launch, 192 * 192 elements each: wp_rs = W_proj (the bits of w16p) and wpT_rs = W_proj^T (the bits of w16pT) in
+ * ea_linear_rs192's image order -- the output projection and its input gradient.  EA_E_BADARG: a NULL or misaligned pointer. */
+int ea_linear_rs192(int32_t dtype, const void* a, int64_t lda, const void* image, const float* bias, void* y, int64_t ldy,
+                    int32_t rows, void* stream);
+int ea_linear_w192_prepare_rs(int32_t dtype, const float* wq, const float* wp, void* w16q, void* wq_sw, void* w16p, void* w16pT,
+                              void* wqT_sw, void* wp_rs, void* wpT_rs, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

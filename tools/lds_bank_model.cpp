@@ -8,6 +8,7 @@
 #include <stdio.h>
 #include <algorithm>
 #include <set>
+#include <string>
 #include <vector>
 #include "ea_lds_swizzle.h"
 
@@ -135,9 +136,37 @@ void model(const char* swz, OffFn off) {
   rw.print("rmw_write", swz);
 }
 
+// lin_rs192_kernel (ea_linear_rs192.hip): a tile of 32 tokens x 192 channels, three slabs of 32 128-byte rows.
+//   reads: wave (pair, half), k-step ks: lane (g, li) reads chunk 4 (ks & 1) + g of row 16 half + li of slab ks >> 1;
+//   commit: thread tid parks chunk tid % 24 of token tid / 24.
+void model_rs192(const char* swz, OffFn off) {
+  int a[64];
+  Acc rd, st;
+  for (int half = 0; half < 32; half += 16)
+    for (int ks = 0; ks < 6; ++ks) {
+      for (int l = 0; l < 64; ++l) a[l] = (ks >> 1) * SLAB + off(half + (l & 15), 4 * (ks & 1) + (l >> 4));
+      rd.add(cycles(READ_B128, a));
+    }
+  for (int wave = 0; wave < 12; ++wave) {
+    for (int l = 0; l < 64; ++l) {
+      const int s = 64 * wave + l, t = s / 24, c = s % 24;
+      a[l] = (c >> 3) * SLAB + off(t, c & 7);
+    }
+    st.add(cycles(WRITE_B128, a));
+  }
+  rd.print("rs192_row_read", swz);
+  st.print("rs192_commit_store", swz);
+}
+
 }  // namespace
 
-int main() {
+// no argument: the 32-token tiles of ea_proj_rs.hip / ea_dgrad_rs.hip; "rs192": the tiles of ea_linear_rs192.hip
+int main(int argc, char** argv) {
+  if (argc > 1 && std::string(argv[1]) == "rs192") {
+    model_rs192("phi2", ea::swz_off2);
+    model_rs192("psi", ea::swz_off3);
+    return 0;
+  }
   model("phi2", ea::swz_off2);
   model("psi", ea::swz_off3);
   return 0;

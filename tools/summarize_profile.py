@@ -17,7 +17,7 @@ KERNEL_TO_ENTRY = [
     ("lmk2_kernel<64, false>", "ea_lara_landmarks_fwd"), ("lmk2_kernel<64, true>", "ea_lara_landmarks_bwd"),
     ("wgrad_kernel<", "ea_wgrad"), ("part_sum_kernel", "ea_part_sum"), ("multi_sum_kernel", "ea_multi_sum"),
     ("stream_copy_kernel", "ea_stream_copy"),
-    ("lin_kernel<ea::BF16, 6, 2, true", "ea_linear[fp32 in]"), ("lin_kernel<", "ea_linear"),
+    ("lin_rs192_kernel<", "ea_linear_rs192"), ("lin_kernel<ea::BF16, 6, 2, true", "ea_linear[fp32 in]"), ("lin_kernel<", "ea_linear"),
     ("colsum_f32_kernel", "ea_colsum_f32 / ea_bias_grad(finish)"),
     ("lara_sample_kernel<", "ea_lara_sample"), ("pool2d_", "ea_adaptive_pool2d"),
     ("sb_fwd_kernel<", "ea_scatter_fwd"), ("sb_bwd_kernel<ea::BF16, false>", "ea_scatter_bwd_window"),
@@ -36,6 +36,9 @@ KERNEL_TO_ENTRY = [
     ("chunk_mean_fwd_r_kernel<", "ea_eva_chunk_mean_fwd"), ("chunk_mean_bwd_r_kernel<", "ea_eva_chunk_mean_bwd"),
     ("beta_fwd_r_kernel<", "ea_eva_beta_fwd"), ("beta_bwd_r_kernel<", "ea_eva_beta_bwd"),
     ("proj_rs_kernel<", "ea_linear[fp32 in]"), ("dgrad_rs_kernel<", "ea_linear_dgrad"), ("dgrad_fin_kernel<", "ea_linear_dgrad_finish"),
+    # the same two bodies fed by the prepared W^T image, the forward combine with the output projection inside, the prepare launch
+    ("dgrad_rs_wt_kernel<", "ea_linear_dgrad"), ("dgrad_fin_wt_kernel<", "ea_linear_dgrad_finish"),
+    ("lara_xp_kernel<", "ea_lara_out_proj_fwd"), ("w192_prepare_kernel<", "ea_linear_w192_prepare"),
     ("chunk_mean_fwd_kernel<", "ea_eva_chunk_mean_fwd"), ("chunk_mean_bwd_kernel<", "ea_eva_chunk_mean_bwd"),
     ("beta_fwd_kernel<", "ea_eva_beta_fwd"), ("beta_bwd_kernel<", "ea_eva_beta_bwd"),
     ("sm_fwd_kernel<ea::BF16, 64", "ea_softmax_attn_fwd"), ("sm_bwd_dq_kernel<ea::BF16, 64", "ea_softmax_attn_bwd(dq)"),
