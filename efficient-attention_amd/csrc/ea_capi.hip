@@ -2540,6 +2540,66 @@ int ea_ceva_sdecode_vocab_sample_logprob(int32_t M, int32_t K, int32_t V, const 
   return ea::ceva_sdecode_vocab_sample_logprob(p, s, (hipStream_t)stream);
 }
 
+// ---- full-vocabulary and nucleus sampling: ea_ceva_sdecode_vocab_sample's operands without top_k and the selection's
+// reports, with the nucleus' own reports in their place ------------------------------------------------------------------
+int64_t ea_ceva_sdecode_vocab_sample_full_ws(int32_t M, int32_t V) { return ea::ceva_sdecode_vocab_nucleus_ws(M, V); }
+
+// the sampler's state, the nucleus' optional reports and the two scalars
+static bool dec_nucleus_ok(float top_p, float temperature, const int64_t* ctr, const int32_t* sid, const int32_t* kept,
+                           const int32_t* thr_idx, const float* thr_val, const int64_t* mass) {
+  if (!ctr || !sid || (uintptr_t)ctr % 8 || (uintptr_t)sid % 4) return false;
+  if ((uintptr_t)kept % 4 || (uintptr_t)thr_idx % 4 || (uintptr_t)thr_val % 4 || (uintptr_t)mass % 8) return false;
+  return top_p > 0.f && top_p <= 1.f && std::isfinite(temperature) && temperature > 0.f;
+}
+
+static ea::DecNucleusP dec_nucleus_fill(int V, const void* ws, float* logits, int64_t ldl, float top_p, float temperature,
+                                        uint64_t seed, int64_t* ctr, const int32_t* sid, int64_t* token, int32_t* kept,
+                                        int32_t* thr_idx, float* thr_val, int64_t* mass) {
+  ea::DecNucleusP s = {};
+  s.ws = (const ea::VocPick*)ws; s.logits = logits; s.token = token; s.ctr = ctr; s.sid = sid; s.kept = kept;
+  s.thr_idx = thr_idx; s.thr_val = thr_val; s.mass = mass; s.ldl = ldl; s.V = V; s.top_p = top_p;
+  s.temperature = temperature; s.seed_lo = (uint32_t)seed; s.seed_hi = (uint32_t)(seed >> 32);
+  return s;
+}
+
+// (the logits are required and fp32)
+int ea_ceva_sdecode_vocab_sample_full(int32_t M, int32_t K, int32_t V, const void* x, int32_t x_dtype, int64_t ldx,
+                                      const void* w, int32_t w_dtype, float* logits, int64_t ldl, void* ws,
+                                      int64_t ws_bytes, float top_p, float temperature, uint64_t seed, int64_t* ctr,
+                                      const int32_t* sid, int64_t* token, int32_t* kept, int32_t* thr_idx, float* thr_val,
+                                      int64_t* mass, void* stream) {
+  if (!dec_table_ok(M, K, x, x_dtype, ldx, w, w_dtype) || !logits || !dec_logits_ok(V, logits, EA_F32, ldl, w_dtype) ||
+      !dec_pick_ok(M, V, ws, ws_bytes, token, nullptr) ||
+      !dec_nucleus_ok(top_p, temperature, ctr, sid, kept, thr_idx, thr_val, mass)) return EA_E_BADARG;
+  if (V > ea::VOC_NUCLEUS_MAX_V || !dec_vocab_geometry_ok(M, K, V)) return EA_E_UNSUPPORTED;
+  ea::DecVocabP p = {};
+  dec_vocab_fill(&p, M, K, V, x, x_dtype, ldx, w, w_dtype, logits, EA_F32, ldl, ws);
+  const ea::DecNucleusP s = dec_nucleus_fill(V, ws, logits, ldl, top_p, temperature, seed, ctr, sid, token, kept, thr_idx,
+                                             thr_val, mass);
+  return ea::ceva_sdecode_vocab_nucleus(p, s, (hipStream_t)stream);
+}
+
+// (the logits are required and fp32; the scorer reads the drawn tokens, not targets)
+int ea_ceva_sdecode_vocab_sample_full_logprob(int32_t M, int32_t K, int32_t V, const void* x, int32_t x_dtype, int64_t ldx,
+                                              const void* w, int32_t w_dtype, float* logits, int64_t ldl, void* ws,
+                                              int64_t ws_bytes, float top_p, float temperature, uint64_t seed,
+                                              int64_t* ctr, const int32_t* sid, int64_t* token, int32_t* kept,
+                                              int32_t* thr_idx, float* thr_val, int64_t* mass, void* lws,
+                                              int64_t lws_bytes, float* lse, float* logp, void* stream) {
+  if (!dec_table_ok(M, K, x, x_dtype, ldx, w, w_dtype) || !logits || !dec_logits_ok(V, logits, EA_F32, ldl, w_dtype) ||
+      !dec_pick_ok(M, V, ws, ws_bytes, token, nullptr) ||
+      !dec_nucleus_ok(top_p, temperature, ctr, sid, kept, thr_idx, thr_val, mass) ||
+      !dec_scorer_ok(M, V, lws, lws_bytes, nullptr, lse, logp)) return EA_E_BADARG;
+  if (V > ea::VOC_NUCLEUS_MAX_V || !dec_vocab_geometry_ok(M, K, V)) return EA_E_UNSUPPORTED;
+  ea::DecLseP p = {};
+  dec_vocab_fill(&p, M, K, V, x, x_dtype, ldx, w, w_dtype, logits, EA_F32, ldl, ws);
+  dec_scorer_fill(&p, lws, lse, logp);
+  p.token_in = token;
+  const ea::DecNucleusP s = dec_nucleus_fill(V, ws, logits, ldl, top_p, temperature, seed, ctr, sid, token, kept, thr_idx,
+                                             thr_val, mass);
+  return ea::ceva_sdecode_vocab_nucleus_logprob(p, s, (hipStream_t)stream);
+}
+
 // ---- the beam step (ABI 32): the table operands, the logits, the workspace, then the beam's state and outputs; the
 // geometry last -------------------------------------------------------------------------------------------------------------
 int64_t ea_ceva_sdecode_vocab_beam_ws(int32_t M, int32_t V, int32_t W) { return ea::ceva_sdecode_vocab_beam_ws(M, V, W); }

@@ -47,6 +47,26 @@ struct DecSampleP {
   uint32_t seed_lo, seed_hi;
 };
 
+// full-vocabulary and nucleus sampling (ceva_vocab_nucleus_kernel, ea_ceva_decode_nucleus.hip): the launch behind the table pass of
+// ea_ceva_sdecode_vocab_sample_full; a block of its own: the others stay what they are
+struct DecNucleusP {
+  const VocPick* ws;          // [M, ceil(V / 16)] candidates of the first launch
+  const float* logits;        // [M, ldl] fp32 logits of the first launch
+  int64_t* token;             // [M]
+  int64_t* ctr;               // [M] draw counters, read and advanced by one
+  const int32_t* sid;         // [M] stream ids
+  int32_t* kept;              // [M], or null
+  int32_t* thr_idx;           // [M] the weakest kept pair, or null
+  float* thr_val;             // [M], or null
+  int64_t* mass;              // [M, 2] (C_kept, Z), or null
+  int64_t ldl;
+  int V;
+  float top_p, temperature;
+  uint32_t seed_lo, seed_hi;
+};
+
+constexpr int VOC_NUCLEUS_MAX_V = 1 << 24;  // columns of a row the nucleus kernel takes (Z < 2^56)
+
 // token log-probabilities (ABI 28): the parameter block of ceva_rows_kernel as the table pass that also writes one
 // sum exp(logit - tile maximum) per tile, and of ceva_vocab_pick_kernel as the pick with the log-sum-exp and the
 // log-probability; a block of its own: DecVocabP and DecSampleP stay what they are.
@@ -153,6 +173,15 @@ int64_t ceva_sdecode_vocab_ws(int M, int V);
 int ceva_sdecode_vocab_argmax(const DecVocabP& p, hipStream_t st);
 // the first launch on p (token and top are not read), the second on s
 int ceva_sdecode_vocab_sample(const DecVocabP& p, const DecSampleP& s, hipStream_t st);
+
+// bytes of ws for the nucleus entries: the candidates alone; < 0: outside the envelope (V > VOC_NUCLEUS_MAX_V too)
+int64_t ceva_sdecode_vocab_nucleus_ws(int M, int V);
+// ceva_vocab_nucleus_kernel alone, one workgroup per row, on what a table pass has left (ea_ceva_decode_nucleus.hip)
+int ceva_vocab_nucleus_launch(const DecNucleusP& s, int M, hipStream_t st);
+// the first launch on p (token and top are not read), ceva_vocab_nucleus_kernel on s
+int ceva_sdecode_vocab_nucleus(const DecVocabP& p, const DecNucleusP& s, hipStream_t st);
+// the table pass with tile sums on p, ceva_vocab_nucleus_kernel on s, then lse and logp of the drawn tokens (p.token_in = s.token)
+int ceva_sdecode_vocab_nucleus_logprob(const DecLseP& p, const DecNucleusP& s, hipStream_t st);
 
 // bytes of lws and tlogit together for (M, V); < 0: outside the envelope
 int64_t ceva_sdecode_vocab_lse_ws(int M, int V);

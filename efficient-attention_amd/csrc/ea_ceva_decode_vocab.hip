@@ -398,6 +398,14 @@ bool voc_sampler_ok(const P& p, const DecSampleP& s) {
   return s.top_k >= 1 && s.top_p > 0.f && s.top_p <= 1.f && s.temperature > 0.f && s.temperature - s.temperature == 0.f;
 }
 
+// the same for the nucleus kernel's block
+template <typename P>
+bool voc_nucleus_ok(const P& p, const DecNucleusP& s) {
+  if (!s.token || !s.ctr || !s.sid || !p.logits || !p.l_f32 || (const char*)s.logits != p.logits || s.ldl != p.ldl ||
+      s.ws != p.ws || s.V != p.V) return false;
+  return s.top_p > 0.f && s.top_p <= 1.f && s.temperature > 0.f && s.temperature - s.temperature == 0.f;
+}
+
 }  // namespace
 
 int64_t ceva_sdecode_vocab_ws(int M, int V) {
@@ -437,6 +445,24 @@ int ceva_sdecode_vocab_sample_logprob(const DecLseP& p, const DecSampleP& s, hip
   if (!voc_sampler_ok(p, s) || p.token_in != s.token || p.targets) return EA_E_BADARG;
   int rc = voc_table_pass(p, s.top_k, st);
   if (rc == 0) rc = voc_row_pass(ceva_vocab_sample_kernel, SMP_THREADS, s, p.M, st);
+  return rc != 0 ? rc : voc_row_pass(ceva_vocab_pick_kernel<DecLseP>, PICK_THREADS, p, p.M, st);
+}
+
+// ---- full-vocabulary and nucleus sampling ----
+int64_t ceva_sdecode_vocab_nucleus_ws(int M, int V) { return V > VOC_NUCLEUS_MAX_V ? -1 : ceva_sdecode_vocab_ws(M, V); }
+
+int ceva_sdecode_vocab_nucleus(const DecVocabP& p, const DecNucleusP& s, hipStream_t st) {
+  if (!voc_nucleus_ok(p, s)) return EA_E_BADARG;
+  if (p.V > VOC_NUCLEUS_MAX_V) return EA_E_UNSUPPORTED;
+  const int rc = voc_table_pass(p, 0, st);
+  return rc != 0 ? rc : ceva_vocab_nucleus_launch(s, p.M, st);
+}
+
+int ceva_sdecode_vocab_nucleus_logprob(const DecLseP& p, const DecNucleusP& s, hipStream_t st) {
+  if (!voc_nucleus_ok(p, s) || p.token_in != s.token || p.targets) return EA_E_BADARG;
+  if (p.V > VOC_NUCLEUS_MAX_V) return EA_E_UNSUPPORTED;
+  int rc = voc_table_pass(p, 0, st);
+  if (rc == 0) rc = ceva_vocab_nucleus_launch(s, p.M, st);
   return rc != 0 ? rc : voc_row_pass(ceva_vocab_pick_kernel<DecLseP>, PICK_THREADS, p, p.M, st);
 }
 

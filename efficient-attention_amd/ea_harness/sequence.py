@@ -527,7 +527,7 @@ class DecoderStack(nn.Module):
         what it would draw decoded alone with its (seed, sid), whatever batch it sits in.
         Attaches `state.sampler` (a Sampler: fp32 logits [batch_size, V], ctr, sid, the scalars; 4 B V + 12 B bytes; the
         pick's workspace is `vocab_ws`) and returns the state.  Values outside the envelope raise ValueError before anything
-        is allocated; full-vocabulary sampling stays with `next_tokens(return_logits=True)`.
+        is allocated; full-vocabulary sampling is `init_nucleus_sampling`.
         On a state with an adaptive pick (`init_adaptive_decoding`) the list is the `top_k` largest JOINT log-probabilities of
         the adaptive softmax and the temperature acts on them -- ea_adaptive_sample, include/ea_hip.h (ABI 35); fairseq
         divides the features by it instead.  The Sampler then holds `ws`, that entry's workspace for batch_size rows (every
@@ -560,6 +560,40 @@ class DecoderStack(nn.Module):
                                 torch.arange(B, dtype=torch.int32, device=device), seed, top_k, top_p, temperature, ws=ws)
         return state
 
+    def init_nucleus_sampling(self, state, seed, top_p=1.0, temperature=1.0):
+        """Make `state` (made with hold_vocab=True) sample its tokens from the WHOLE vocabulary: at top_p = 1 plain ancestral
+        sampling at `temperature` (> 0), at 0 < top_p < 1 from the nucleus, the smallest head of the row -- in the greedy
+        pick's total order over all V columns -- whose mass reaches top_p of the row's; no top-k list anywhere
+        (`init_sampling` is the one with a list) -- ea_ceva_sdecode_vocab_sample_full, include/ea_hip.h.  The weights are
+        INTEGERS, trunc(expf((l - max) / temperature) 2^32), so the nucleus and the draw are exact and a row's tokens are what
+        it would draw decoded alone with its (seed, sid), whatever batch it sits in.  Streams, counters, reorders and resets:
+        as `init_sampling` has them.  `sample_tokens`, `sample_tokens_logprobs` (with `init_logprobs`) and `generate` (with
+        return_logprobs too) run on it, device launches only.
+        Attaches `state.sampler` (a Sampler whose top_k is 0: fp32 logits [batch_size, V], ctr, sid, the scalars; the pick's
+        workspace is `vocab_ws`) and returns the state.  Values outside the envelope raise ValueError before anything is
+        allocated.  An adaptive pick has no [batch_size, V] row to draw from: NotImplementedError."""
+        if state.adaptive is not None:
+            raise NotImplementedError("init_nucleus_sampling on an adaptive pick: full-vocabulary sampling from the adaptive "
+                                      "head is not implemented (init_sampling draws from its top_k list)")
+        if state.vocab is None:
+            raise RuntimeError("init_nucleus_sampling needs a decoding state that holds the vocabulary table: "
+                               "init_decoding(..., hold_vocab=True)")
+        seed, top_p, temperature = int(seed), float(top_p), float(temperature)
+        if not 0.0 < top_p <= 1.0:
+            raise ValueError("top_p must be in (0, 1], got %r" % top_p)
+        if not (math.isfinite(temperature) and temperature > 0.0):
+            raise ValueError("temperature must be finite and > 0, got %r" % temperature)
+        if not 0 <= seed < 1 << 64:
+            raise ValueError("seed must be in 0 .. 2^64 - 1, got %d" % seed)
+        B, V, device = state.options["batch_size"], state.vocab.shape[0], state.vocab.device
+        from efficient_attention import _native as nv
+        if nv.lib().ea_ceva_sdecode_vocab_sample_full_ws(min(B, _FUSED_MAX_ROWS), V) < 0:
+            raise ValueError("a table of %d rows is outside ea_ceva_sdecode_vocab_sample_full's envelope" % V)
+        state.sampler = Sampler(torch.empty((B, V), dtype=torch.float32, device=device),
+                                torch.zeros(B, dtype=torch.long, device=device),
+                                torch.arange(B, dtype=torch.int32, device=device), seed, 0, top_p, temperature)
+        return state
+
     def sample_tokens(self, rows, state, out=None, return_details=False):
         """The sampled pick on a state with a sampler (`init_sampling`): rows [1, B, C] (final-layer rows of a single-token
         step, B <= 64 and at most the state's batch size) -> int64 [1, B], one draw per row from ea_ceva_sdecode_vocab_sample on
@@ -568,9 +602,15 @@ class DecoderStack(nn.Module):
         order (entries from min(top_k, V) on are not written; log-probabilities follow from sel_val), and how many of it the
         nucleus kept (0: a row whose best logit is NaN or infinite, which gets the greedy pick).  Device launches only.
         On a state with an adaptive pick the draw is ea_adaptive_sample's: sel_idx are vocabulary indices, sel_val their
-        joint log-probabilities."""
+        joint log-probabilities.
+        On a state made to sample the whole vocabulary (`init_nucleus_sampling`) the draw is
+        ea_ceva_sdecode_vocab_sample_full's and return_details=True gives (tokens, kept int32 [B], thr_idx int32 [B], thr_val
+        fp32 [B], mass int64 [B, 2]): how many columns the nucleus kept, its weakest pair with the stored bits, and the
+        integer masses (C_kept, Z)."""
         if state.sampler is None:
             raise RuntimeError("sample_tokens needs a decoding state with a sampler: init_sampling(state, seed, top_k, ...)")
+        if state.sampler.top_k == 0:
+            return tp.HeldNucleus(self, state).run(rows, out, return_details)
         if state.adaptive is not None:
             got = tp.AdaptiveSampled(self, state).run(rows, out, None, return_details)
             return (got[0],) + got[2:] if return_details else got[0]
@@ -656,6 +696,10 @@ class DecoderStack(nn.Module):
         if state.sampler is None or state.scorer is None:
             raise RuntimeError("sample_tokens_logprobs needs a decoding state with a sampler and a scorer: "
                                "init_sampling(state, seed, top_k, ...) and init_logprobs(state)")
+        if state.sampler.top_k == 0:                     # (`init_nucleus_sampling`: the scorer's static buffers are written)
+            tp.single_step(rows, min(_FUSED_MAX_ROWS, state.sampler.ctr.numel()), "a sampled pick")
+            tokens, logp, _ = tp.HeldNucleus(self, state, rows.shape[1]).run(rows, out, False)
+            return tokens, logp.clone()
         tokens, logp, _ = tp.HeldSampledLogprob(self, state).run(rows, out, None, None)
         return tokens, logp
 

@@ -8,7 +8,8 @@
                       follows a `reorder`, a `reset_rows` and a `refresh` of the state; `DecodingState.attachments()` lists those a
                       state has, so that the stack's four lifecycle methods name none of them.
   picks            -- one class per launch: `HeldGreedy` (ea_ceva_sdecode_vocab_argmax), `HeldSampled` (.._sample),
-                      `HeldGreedyLogprob` (.._logprob), `HeldSampledLogprob` (.._sample_logprob), `AdaptiveGreedy`
+                      `HeldGreedyLogprob` (.._logprob), `HeldSampledLogprob` (.._sample_logprob), `HeldNucleus`
+                      (.._sample_full, .._sample_full_logprob), `AdaptiveGreedy`
                       (ea_adaptive_pick), `AdaptiveSampled` (ea_adaptive_sample), `BeamStep` (.._beam; .._beam_c on a Beam with a constraint),
                       `AdaptiveBeamStep` (ea_adaptive_beam, ea_adaptive_beam_c), and `FrameworkGreedy`, `logits(rows).argmax(-1)`.  `run` is the
                       launch behind the stack's public method of that mode; calling the pick, `pick(rows, out=None) -> tokens`,
@@ -26,6 +27,8 @@ VOCAB = "ea_ceva_sdecode_vocab_argmax"
 SAMPLE = "ea_ceva_sdecode_vocab_sample"
 LOGPROB = "ea_ceva_sdecode_vocab_logprob"
 SAMPLE_LOGPROB = "ea_ceva_sdecode_vocab_sample_logprob"
+SAMPLE_FULL = "ea_ceva_sdecode_vocab_sample_full"
+SAMPLE_FULL_LOGPROB = "ea_ceva_sdecode_vocab_sample_full_logprob"
 ADAPTIVE_PICK = "ea_adaptive_pick"
 BEAM = "ea_ceva_sdecode_vocab_beam"
 ADAPTIVE_SAMPLE = "ea_adaptive_sample"
@@ -149,7 +152,8 @@ class Sampler(Attachment):
     """What `DecoderStack.init_sampling` attaches to a DecodingState: the fp32 `logits` buffer [batch_size, V] of the sampled
     pick, the draw counters `ctr` (int64 [B]: draw n of a row is made at ctr = n) and the stream ids `sid` (int32 [B]), both
     on the device, the host scalars `seed`, `top_k`, `top_p`, `temperature`, and `next_sid`, the first stream id no row of
-    this state has had.  On a state with an adaptive pick there is no [batch_size, V] row: `logits` is None and `ws` is the
+    this state has had.  `top_k` = 0 (`DecoderStack.init_nucleus_sampling`): no list, the whole vocabulary or its nucleus --
+    ea_ceva_sdecode_vocab_sample_full.  On a state with an adaptive pick there is no [batch_size, V] row: `logits` is None and `ws` is the
     workspace of ea_adaptive_sample for batch_size rows (bytes; it holds every band's fp32 logits, about 4 B V)."""
 
     def __init__(self, logits, ctr, sid, seed, top_k, top_p, temperature, ws=None):
@@ -362,6 +366,9 @@ def select_pick(stack, state, B, return_logprobs=False):
             raise RuntimeError("generate(return_logprobs=True) needs a decoding state with a scorer: init_logprobs(state)")
         if B > state.scorer.logp.numel():
             raise ValueError("a prompt of %d rows on a scorer made for %d" % (B, state.scorer.logp.numel()))
+    if state is not None and state.sampler is not None and state.sampler.top_k == 0:
+        return HeldNucleus(stack, state, B if return_logprobs else None)
+    if return_logprobs:
         return (HeldGreedyLogprob if state.sampler is None else HeldSampledLogprob)(stack, state, B)
     if state is None or state.vocab is None:
         return FrameworkGreedy(stack)
@@ -514,6 +521,40 @@ class HeldSampledLogprob(HeldSampled):
         nv.call(SAMPLE_LOGPROB, *args, *self._draw(out), None, None, None, nv.ptr(lws), lws.numel(), nv.ptr(lse), nv.ptr(logp),
                 nv.stream())
         return out, logp, lse
+
+
+class HeldNucleus(HeldSampled):
+    """ea_ceva_sdecode_vocab_sample_full on the held table and a sampler without a top-k list (`init_nucleus_sampling`):
+    `sample_tokens`; made for a loop over B rows with a scorer it is ea_ceva_sdecode_vocab_sample_full_logprob instead and
+    writes into the first B entries of the scorer's static `logp` and `lse`: `sample_tokens_logprobs`."""
+
+    def _static(self, B):
+        HeldGreedyLogprob._static(self, B)
+        self.who = "a sampled pick"
+
+    def __call__(self, rows, out=None):
+        got = self.run(rows, out, False)
+        return got if self.logp is None else got[0]
+
+    def run(self, rows, out, return_details):
+        """-> tokens int64 [1, B]; with return_details (tokens, kept, thr_idx, thr_val, mass); made with a scorer's static
+        views (tokens, logp, lse)."""
+        nv, sm, ws = _native(), self.state.sampler, self.state.vocab_ws
+        x2, args = self._operands(rows)
+        B, dev = x2.shape[0], x2.device
+        out = checked_out(out, (1, B), torch.long, dev)
+        details = (None,) * 4
+        if return_details:
+            details = (torch.empty((B,), dtype=torch.int32, device=dev), torch.empty((B,), dtype=torch.int32, device=dev),
+                       torch.empty((B,), dtype=torch.float32, device=dev), torch.empty((B, 2), dtype=torch.long, device=dev))
+        draw = [nv.ptr(ws), ws.numel(), sm.top_p, sm.temperature, sm.seed, nv.ptr(sm.ctr), nv.ptr(sm.sid), nv.ptr(out)] \
+            + [None if t is None else nv.ptr(t) for t in details]
+        if self.logp is None:
+            nv.call(SAMPLE_FULL, *args, *draw, nv.stream())
+            return (out,) + details if return_details else out
+        lws = self.state.scorer.ws
+        nv.call(SAMPLE_FULL_LOGPROB, *args, *draw, nv.ptr(lws), lws.numel(), nv.ptr(self.lse), nv.ptr(self.logp), nv.stream())
+        return out, self.logp, self.lse
 
 
 class AdaptiveGreedy(Pick):

@@ -269,6 +269,11 @@ SIGNATURES = {
     "ea_ceva_sdecode_vocab_logprob": [_I, _I, _I, _P, _I, _L, _P, _I, _P, _I, _L, _P, _L, _P, _P, _P, _L, _P, _P, _P, _P],
     "ea_ceva_sdecode_vocab_sample_logprob": [_I, _I, _I, _P, _I, _L, _P, _I, _P, _L, _P, _L, _I, _F, _F, _U64, _P, _P, _P, _P,
                                              _P, _P, _P, _L, _P, _P, _P],
+    "ea_ceva_sdecode_vocab_sample_full_ws": [_I, _I],
+    "ea_ceva_sdecode_vocab_sample_full": [_I, _I, _I, _P, _I, _L, _P, _I, _P, _L, _P, _L, _F, _F, _U64, _P, _P, _P, _P, _P, _P,
+                                          _P, _P],
+    "ea_ceva_sdecode_vocab_sample_full_logprob": [_I, _I, _I, _P, _I, _L, _P, _I, _P, _L, _P, _L, _F, _F, _U64, _P, _P, _P, _P,
+                                                  _P, _P, _P, _P, _L, _P, _P, _P],
     "ea_ceva_sdecode_vocab_beam_ws": [_I, _I, _I],
     "ea_ceva_sdecode_vocab_beam": [_I, _I, _I, _P, _I, _L, _P, _I, _P, _L, _P, _L, _I, _I, _I, _P, _P, _P, _P, _P, _P, _P, _P,
                                    _P, _P, _P, _P, _P, _P, _P, _P],
@@ -338,6 +343,7 @@ def lib():
         cdll.ea_ceva_sdecode_vocab_ws.restype = ctypes.c_int64
         cdll.ea_ceva_sdecode_vocab_sample_ws.restype = ctypes.c_int64
         cdll.ea_ceva_sdecode_vocab_lse_ws.restype = ctypes.c_int64
+        cdll.ea_ceva_sdecode_vocab_sample_full_ws.restype = ctypes.c_int64
         cdll.ea_ceva_sdecode_vocab_beam_ws.restype = ctypes.c_int64
         cdll.ea_vocab_score_ws.restype = ctypes.c_int64
         cdll.ea_vocab_score_rows_ws.restype = ctypes.c_int64

@@ -1197,6 +1197,53 @@ int ea_ceva_sdecode_vocab_sample_logprob(int32_t M, int32_t K, int32_t V, const 
                                          int64_t* ctr, const int32_t* sid, int64_t* token, int32_t* sel_idx, float* sel_val,
                                          int32_t* kept, void* lws, int64_t lws_bytes, float* lse, float* logp, void* stream);
 
+/* FULL-VOCABULARY and NUCLEUS sampling on that table (additions to ABI 38; ea_harness DecoderStack.init_nucleus_sampling;
+ * ea_ceva_decode_nucleus.hip): a token drawn from the WHOLE row at a temperature (top_p = 1, fairseq's --sampling), or from
+ * its nucleus (--sampling-topp), with no top-k anywhere.  ea_ceva_sdecode_vocab_sample_full, two launches.  The first is
+ * ea_ceva_sdecode_vocab_argmax's first: fp32 logits l[0 .. V) into logits [M, ldl] (required; that entry's bits) and one
+ * candidate per 16-column tile into ws.  The second, one workgroup of 512 threads per row m; pairs are ordered as the greedy
+ * pick orders them -- the larger value first, equal values (+0 and -0 too) by the lower index, NaN above every number:
+ *   1. (val_0, idx_0) = the best pair, from the candidates.  val_0 NaN or infinite: token[m] = idx_0, kept = 0, thr = that
+ *      pair, mass = (0, 0), ctr[m] += 1; nothing below runs.
+ *   2. w_v = expf((l_v - val_0) / temperature) in fp32 (an IEEE difference and quotient, the library's expf);
+ *      q_v = (uint64) trunc(w_v 2^32): q_{idx_0} = 2^32, a logit of -inf has mass 0 (so has every column more than 22.2
+ *      temperatures below val_0).  From here on every quantity is an INTEGER.  Z = sum_v q_v.
+ *   3. target = ceil(double(top_p) double(Z)), one IEEE multiplication.  With the pairs in order and C_n the mass of the
+ *      first n, kept = the smallest n >= 1 with C_n >= target, (thr_val, thr_idx) = the n-th pair, and the kept set is every
+ *      pair that beats or equals it: ties in value at the boundary are cut by index.  C_kept = C_n at that n.  top_p = 1:
+ *      kept = V, the threshold pair is the one every other beats, C_kept = Z (columns of mass 0 are kept and never drawn).
+ *   4. n = ctr[m]; Philox4x32-10 under ea_ceva_sdecode_vocab_sample's key and counter layout; U = word 0 >> 8;
+ *      r = ((2 U + 1) C_kept) >> 25 of the full product, so r < C_kept; token[m] = the first KEPT column in VOCABULARY order
+ *      whose inclusive running kept mass exceeds r; ctr[m] = n + 1.
+ * Integer sums do not depend on their order: token is a function of the row's logits, (seed, ctr[m], sid[m]) and the two
+ * scalars alone, the same on every run and in every batch.  Integer LDS atomics only, no atomics on memory, no workgroup
+ * waits for another.  The kernel streams the row (from L2) three times at top_p < 1, once at top_p = 1, plus the one block
+ * the draw falls in: a histogram of 384 buckets of 1/16 nat finds the boundary bucket, whose keys are selected exactly in an
+ * LDS pool of 4096 (a larger bucket -- a row of equal logits -- by radix passes over the streamed row).
+ * Optional reports: kept [M] int32, thr_idx [M] int32, thr_val [M] fp32 (the stored logit's bits), mass [M, 2] int64
+ * (C_kept, Z).  top_p, temperature and seed are host scalars: a capture fixes them.  ws:
+ * ea_ceva_sdecode_vocab_sample_full_ws(M, V) bytes, which is ea_ceva_sdecode_vocab_ws(M, V); < 0 also for V > 2^24.
+ * ea_ceva_sdecode_vocab_sample_full_logprob, three launches: ea_ceva_sdecode_vocab_logprob's first (the table pass that also
+ * writes the tile sums), the second above unchanged, then ea_ceva_sdecode_vocab_sample_logprob's third:
+ * logp[m] = l[token[m]] - lse[m], the RAW distribution at temperature 1.
+ * EA_E_BADARG: what ea_ceva_sdecode_vocab_argmax answers with it (pointers, alignment, types, strides, ws_bytes); logits, ctr
+ * or sid NULL; logits, sid, kept, thr_idx or thr_val not 4-byte, ctr or mass not 8-byte aligned; top_p outside (0, 1];
+ * temperature not finite or <= 0; the _logprob entry: what ea_ceva_sdecode_vocab_logprob answers for lws, lse, logp.
+ * EA_E_UNSUPPORTED: M > 64, K % 32 != 0, V < 1, V > 2^24.  Bad arguments are decided before the geometry, everything before
+ * any launch. */
+int64_t ea_ceva_sdecode_vocab_sample_full_ws(int32_t M, int32_t V);
+int ea_ceva_sdecode_vocab_sample_full(int32_t M, int32_t K, int32_t V, const void* x, int32_t x_dtype, int64_t ldx,
+                                      const void* w, int32_t w_dtype, float* logits, int64_t ldl, void* ws,
+                                      int64_t ws_bytes, float top_p, float temperature, uint64_t seed, int64_t* ctr,
+                                      const int32_t* sid, int64_t* token, int32_t* kept, int32_t* thr_idx, float* thr_val,
+                                      int64_t* mass, void* stream);
+int ea_ceva_sdecode_vocab_sample_full_logprob(int32_t M, int32_t K, int32_t V, const void* x, int32_t x_dtype, int64_t ldx,
+                                              const void* w, int32_t w_dtype, float* logits, int64_t ldl, void* ws,
+                                              int64_t ws_bytes, float top_p, float temperature, uint64_t seed,
+                                              int64_t* ctr, const int32_t* sid, int64_t* token, int32_t* kept,
+                                              int32_t* thr_idx, float* thr_val, int64_t* mass, void* lws,
+                                              int64_t lws_bytes, float* lse, float* logp, void* stream);
+
 /* ABI 29, the LARA forward combine with the OUTPUT PROJECTION inside (ea_lara_xp.hip): for a model of three heads of 64
  * channels, y = out W_proj^T + bias is formed by the pass that forms `out`, from registers and LDS -- one launch instead of
  * ea_lara_out_fwd_merge + ea_linear[192->192], `out` written once (the weight gradient reads it) and not read back.
