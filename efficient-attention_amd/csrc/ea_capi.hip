@@ -21,6 +21,7 @@
 #include "ea_proj.h"
 #include "ea_fold.h"
 #include "ea_lara_seglin.h"
+#include "ea_ceva_lm.h"
 
 using namespace ea;
 
@@ -134,6 +135,73 @@ int ea_window_attn_bwd(const ea_geom* g, const ea_t4* q, const ea_t4* k, const e
   p.dlk_part = dlk_part; p.dlv_part = dlv_part; p.dbias_part = dbias_part;
   p.dk32 = dk_acc; p.dv32 = dv_acc;
   return window_bwd_dispatch(p, *g, mk(out), bias ? bias_t : nullptr, g->dtype, g->D, (hipStream_t)stream);
+}
+
+// ---- causal EVA past 64 chunks: the landmark columns apart from the window half (ea_ceva_lm.hip) ----
+static int fill_clm(const ea_geom* g, CevaLmP& p) {
+  if (!geom_ok(g) || g->chunk <= 0 || g->L <= 0 || g->attn_2d || g->causal != 2) return EA_E_BADARG;
+  if (g->D != 64 && g->D != 128) return EA_E_UNSUPPORTED;
+  p.B = g->B; p.H = g->H; p.N = g->N; p.L = g->L; p.Lp = clm_lp(g->L); p.r = g->chunk; p.lm_base = g->lm_base;
+  p.nQT = (g->N + CLM_TILE - 1) / CLM_TILE;
+  p.scale = g->scale; p.scale_log2 = g->scale * LOG2E;
+  return EA_OK;
+}
+static int clm_keep(CevaLmP& p, const uint8_t* keep, int32_t keep_ld, float keep_scale) {
+  if (keep && (keep_ld < p.L || keep_ld % 16 || (uintptr_t)keep % 4)) return EA_E_BADARG;
+  p.keep = keep; p.keep_ld = keep_ld; p.keep_scale = keep_scale;
+  return EA_OK;
+}
+
+int ea_ceva_lm_prepare(const ea_geom* g, const float* lk, const float* lv, void* lk16, void* lv16, void* stream) {
+  CevaLmP p = {};
+  if (const int rc = fill_clm(g, p)) return rc;
+  if (!lk || !lv || !lk16 || !lv16 || (uintptr_t)lk % 16 || (uintptr_t)lv % 16 || (uintptr_t)lk16 % 16 || (uintptr_t)lv16 % 16)
+    return EA_E_BADARG;
+  p.lk = lk; p.lv = lv; p.lk16 = (const char*)lk16; p.lv16 = (const char*)lv16;
+  return ceva_lm_dispatch(0, p, g->dtype, g->D, (hipStream_t)stream);
+}
+
+int ea_ceva_lm_fwd(const ea_geom* g, const ea_t4* q, const void* lk16, const void* lv16, const ea_t4* o_loc,
+                   const float* lse_loc, const uint8_t* keep, int32_t keep_ld, float keep_scale, const ea_t4* out,
+                   float* zl, void* stream) {
+  CevaLmP p = {};
+  if (const int rc = fill_clm(g, p)) return rc;
+  if (const int rc = clm_keep(p, keep, keep_ld, keep_scale)) return rc;
+  if (!view_ok(q, g->D, 2) || !view_ok(o_loc, g->D, 2) || !view_ok(out, g->D, 2) || !lk16 || !lv16 || !lse_loc || !zl ||
+      (uintptr_t)lk16 % 16 || (uintptr_t)lv16 % 16 || (uintptr_t)zl % 8) return EA_E_BADARG;
+  p.q = mk(q); p.oloc = mk(o_loc); p.out = mk(out);
+  p.lk16 = (const char*)lk16; p.lv16 = (const char*)lv16; p.lse_loc = lse_loc; p.zl = zl;
+  return ceva_lm_dispatch(1, p, g->dtype, g->D, (hipStream_t)stream);
+}
+
+int ea_ceva_lm_bwd_q(const ea_geom* g, const ea_t4* q, const void* lk16, const void* lv16, const ea_t4* o_loc,
+                     const float* lse_loc, const uint8_t* keep, int32_t keep_ld, float keep_scale, const ea_t4* out,
+                     const ea_t4* dout, const float* zl, const ea_t4* do_loc, float* dlse_loc, float* dq, float* delta,
+                     int32_t* flags, void* stream) {
+  CevaLmP p = {};
+  if (const int rc = fill_clm(g, p)) return rc;
+  if (const int rc = clm_keep(p, keep, keep_ld, keep_scale)) return rc;
+  if (!view_ok(q, g->D, 2) || !view_ok(o_loc, g->D, 2) || !view_ok(out, g->D, 2) || !view_ok(dout, g->D, 2) ||
+      !view_ok(do_loc, g->D, 2) || !lk16 || !lv16 || !lse_loc || !zl || !dlse_loc || !dq || !delta || !flags ||
+      (uintptr_t)lk16 % 16 || (uintptr_t)lv16 % 16 || (uintptr_t)dq % 16) return EA_E_BADARG;
+  p.q = mk(q); p.oloc = mk(o_loc); p.out = mk(out); p.dout = mk(dout); p.doloc = mk(do_loc);
+  p.lk16 = (const char*)lk16; p.lv16 = (const char*)lv16; p.lse_loc = lse_loc; p.zl = const_cast<float*>(zl);
+  p.dlse_loc = dlse_loc; p.dq = dq; p.delta = delta; p.flags = flags;
+  return ceva_lm_dispatch(2, p, g->dtype, g->D, (hipStream_t)stream);
+}
+
+int ea_ceva_lm_bwd_k(const ea_geom* g, const ea_t4* q, const void* lk16, const void* lv16, const uint8_t* keep,
+                     int32_t keep_ld, float keep_scale, const ea_t4* dout, const float* zl, const float* delta,
+                     const int32_t* flags, float* dlk, float* dlv, void* stream) {
+  CevaLmP p = {};
+  if (const int rc = fill_clm(g, p)) return rc;
+  if (const int rc = clm_keep(p, keep, keep_ld, keep_scale)) return rc;
+  if (!view_ok(q, g->D, 2) || !view_ok(dout, g->D, 2) || !lk16 || !lv16 || !zl || !delta || !flags || !dlk || !dlv ||
+      (uintptr_t)lk16 % 16 || (uintptr_t)lv16 % 16 || (uintptr_t)dlk % 16 || (uintptr_t)dlv % 16) return EA_E_BADARG;
+  p.q = mk(q); p.dout = mk(dout);
+  p.lk16 = (const char*)lk16; p.lv16 = (const char*)lv16; p.zl = const_cast<float*>(zl);
+  p.delta = const_cast<float*>(delta); p.flags = const_cast<int32_t*>(flags); p.dlk = dlk; p.dlv = dlv;
+  return ceva_lm_dispatch(3, p, g->dtype, g->D, (hipStream_t)stream);
 }
 
 // ---- EVA landmark statistics ----

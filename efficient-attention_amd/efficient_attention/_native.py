@@ -135,6 +135,10 @@ SIGNATURES = {
     "ea_window_attn_fwd": [_G, _T, _T, _T, _P, _P, _P, _P, _T, _P, _P, _F, _P],
     "ea_window_attn_bwd": [_G, _T, _T, _T, _P, _P, _P, _P, _T, _T, _P, _T, _T, _T, _P, _P, _P, _P, _P, _P, _P, _F, _P, _P],
     "ea_window_keep_ld": [_G],
+    "ea_ceva_lm_prepare": [_G, _P, _P, _P, _P, _P],
+    "ea_ceva_lm_fwd": [_G, _T, _P, _P, _T, _P, _P, _I, _F, _T, _P, _P],
+    "ea_ceva_lm_bwd_q": [_G, _T, _P, _P, _T, _P, _P, _I, _F, _T, _T, _P, _T, _P, _P, _P, _P, _P],
+    "ea_ceva_lm_bwd_k": [_G, _T, _P, _P, _P, _I, _F, _T, _P, _P, _P, _P, _P, _P],
     "ea_rows_mlp_parts": [_I, _I],
     "ea_rows_mlp_fwd": [_I] * 4 + [_P] * 15,
     "ea_rows_mlp_bwd": [_I] * 4 + [_P] * 15,

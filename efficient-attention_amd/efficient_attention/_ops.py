@@ -545,6 +545,86 @@ def _eva_cfg(qkv5, cfg):
     return geom, _eva_fused_mu(cfg, d)
 
 
+# causal EVA past 64 chunks on the 16-bit kernels (csrc/ea_ceva_lm.hip); EA_CEVA_LONG=0: the fp32 gathered-attention route
+USE_CEVA_LONG = os.environ.get("EA_CEVA_LONG", "1") == "1"
+
+
+def ceva_long_applies(cfg, d):
+    return USE_CEVA_LONG and cfg.causal == 2 and not cfg.attn_2d and cfg.L > 64 and d in (64, 128)
+
+
+def _ceva_long_setup(cfg, qkv5, keep):
+    """-> (geometry of the window half: no landmark columns; geometry of the landmark half; keep mask of the local columns, of
+    the landmark columns -- the two runs of CausalEVAttention._dropout_keep's kernel layout, each with its own rows)."""
+    B, N, _, h, d = qkv5.shape
+    mk = lambda L: nv.make_geom(B, h, N, d, nv.io_dtype(qkv5), False, cfg.seq_shape, cfg.window, cfg.ext, cfg.chunk, L, 2)
+    keep_loc = keep_lm = None
+    if keep is not None:
+        ld_local = -(-(cfg.window + cfg.ext) // 16) * 16
+        keep_loc, keep_lm = keep[..., :ld_local].contiguous(), keep[..., ld_local:].contiguous()
+    return mk(0), mk(cfg.L), keep_loc, keep_lm
+
+
+def ceva_lm_fwd(g, q, lk, lv, o_loc, lse_loc, keep_lm, keep_scale):
+    """The landmark half of causal EVA's softmax and its join with the window half (ea_ceva_lm_prepare / _fwd).  g: ea_geom with
+    causal = 2 and L landmarks; q [B,h,N,d] 16-bit view; lk, lv fp32 [B,h,L,d] contiguous; o_loc [B,N,h,d], lse_loc [B,h,N] of
+    the window half; keep_lm uint8 [B,h,N,16 ceil(L/16)] or None -> out (o_loc's layout), zl [B,h,N,2] = (Z, lse_lm), the
+    16-bit landmark images [2, B h, 64 ceil(L/64), d]."""
+    B, h, N, d = q.shape
+    img = torch.empty((2, B * h, -(-g.L // 64) * 64, d), dtype=q.dtype, device=q.device)
+    nv.call("ea_ceva_lm_prepare", ctypes.byref(g), nv.ptr(lk), nv.ptr(lv), nv.ptr(img[0]), nv.ptr(img[1]), nv.stream())
+    out = torch.empty_like(o_loc)
+    zl = torch.empty((B, h, N, 2), dtype=torch.float32, device=q.device)
+    tq, tol, to = nv.t4(q), nv.t4(o_loc.permute(0, 2, 1, 3)), nv.t4(out.permute(0, 2, 1, 3))
+    nv.call("ea_ceva_lm_fwd", ctypes.byref(g), ctypes.byref(tq), nv.ptr(img[0]), nv.ptr(img[1]), ctypes.byref(tol), nv.ptr(lse_loc),
+            nv.ptr(keep_lm), 0 if keep_lm is None else keep_lm.shape[-1], float(keep_scale), ctypes.byref(to), nv.ptr(zl),
+            nv.stream())
+    return out, zl, img
+
+
+def ceva_lm_bwd(g, q, img, o_loc, lse_loc, keep_lm, keep_scale, out, dout, zl):
+    """Backward of ceva_lm_fwd (ea_ceva_lm_bwd_q, then _bwd_k) -> d o_loc (I/O dtype, o_loc's layout), d lse_loc [B,h,N],
+    dq [B,N,h,d] fp32 (the landmark columns' share), d lk, d lv [B,h,L,d] fp32."""
+    B, h, N, d = q.shape
+    dev = q.device
+    keep_ld = 0 if keep_lm is None else keep_lm.shape[-1]
+    do_loc = torch.empty_like(o_loc)
+    dlse = torch.empty((B, h, N), dtype=torch.float32, device=dev)
+    delta = torch.empty_like(dlse)
+    dq_lm = torch.empty((B, N, h, d), dtype=torch.float32, device=dev)
+    flags = torch.empty((B * h, -(-N // 64)), dtype=torch.int32, device=dev)
+    dl = torch.empty((2, B, h, g.L, d), dtype=torch.float32, device=dev)
+    ts = [nv.t4(t) for t in (q, o_loc.permute(0, 2, 1, 3), out.permute(0, 2, 1, 3), dout.permute(0, 2, 1, 3),
+                             do_loc.permute(0, 2, 1, 3))]
+    nv.call("ea_ceva_lm_bwd_q", ctypes.byref(g), ctypes.byref(ts[0]), nv.ptr(img[0]), nv.ptr(img[1]), ctypes.byref(ts[1]),
+            nv.ptr(lse_loc), nv.ptr(keep_lm), keep_ld, float(keep_scale), ctypes.byref(ts[2]), ctypes.byref(ts[3]), nv.ptr(zl),
+            ctypes.byref(ts[4]), nv.ptr(dlse), nv.ptr(dq_lm), nv.ptr(delta), nv.ptr(flags), nv.stream())
+    nv.call("ea_ceva_lm_bwd_k", ctypes.byref(g), ctypes.byref(ts[0]), nv.ptr(img[0]), nv.ptr(img[1]), nv.ptr(keep_lm), keep_ld,
+            float(keep_scale), ctypes.byref(ts[3]), nv.ptr(zl), nv.ptr(delta), nv.ptr(flags), nv.ptr(dl[0]), nv.ptr(dl[1]),
+            nv.stream())
+    return do_loc, dlse, dq_lm, dl[0], dl[1]
+
+
+def _ceva_long_fwd(cfg, qkv5, lk, lv, bias_p, mask_u8, keep):
+    """Causal EVA's joint softmax with L > 64 landmark columns -> out, lse_loc, [o_loc, (Z, lse_lm), 16-bit landmark images]:
+    the window kernels on the local columns alone (L = 0), then the landmark columns and the join (ceva_lm_fwd)."""
+    g0, g, keep_loc, keep_lm = _ceva_long_setup(cfg, qkv5, keep)
+    o_loc, lse_loc = _window_fwd(g0, qkv5, None, None, bias_p, mask_u8, keep_loc, cfg.keep_scale)
+    out, zl, img = ceva_lm_fwd(g, _qkv_views(qkv5)[0], lk, lv, o_loc, lse_loc, keep_lm, cfg.keep_scale)
+    return out, lse_loc, [o_loc, zl, img]
+
+
+def _ceva_long_bwd(cfg, qkv5, bias_p, mask_u8, keep, out, dout, lse_loc, more, dqkv5):
+    """Backward of _ceva_long_fwd: writes dq, dk, dv into dqkv5 -> d rf_k_bar, d beta [B,h,L,d] fp32, dbias_padded."""
+    o_loc, zl, img = more
+    g0, g, keep_loc, keep_lm = _ceva_long_setup(cfg, qkv5, keep)
+    do_loc, dlse, dq_lm, dlk, dlv = ceva_lm_bwd(g, _qkv_views(qkv5)[0], img, o_loc, lse_loc, keep_lm, cfg.keep_scale, out, dout, zl)
+    _, _, dbias = _window_bwd(g0, qkv5, None, None, bias_p, mask_u8, o_loc, do_loc, lse_loc, dqkv5, keep_loc, cfg.keep_scale,
+                              dlse=dlse)
+    dqkv5[:, :, 0].add_(dq_lm)                     # (fp32 sum, rounded once more into the I/O dtype)
+    return dlk, dlv, dbias
+
+
 def _eva_fused_mu(cfg, d):
     return cfg.adaptive_proj == "default" and cfg.L <= 64 and d in (32, 64) and cfg.mu_scale == 0.5
 
@@ -694,9 +774,14 @@ def eva_fwd_impl(qkv5, bias, noise, mask_u8, keep, icfg, fcfg, adaptive_proj, ml
     nv.call("ea_eva_beta_fwd", ctypes.byref(geom), ctypes.byref(tk), ctypes.byref(tv),
             nv.ptr(mask_u8), nv.ptr(omega), nv.ptr(beta), nv.stream())
     bias_p = _bias_padded(bias, geom)
-    out, lse = _window_fwd(geom, qkv5, rf_k_bar, beta, bias_p, mask_u8, keep, cfg.keep_scale)
+    more = []
+    if ceva_long_applies(cfg, d):
+        # more than 64 chunks: window half and landmark half apart, joined through their log-sum-exps (lse = the window half's)
+        out, lse, more = _ceva_long_fwd(cfg, qkv5, rf_k_bar, beta, bias_p, mask_u8, keep)
+    else:
+        out, lse = _window_fwd(geom, qkv5, rf_k_bar, beta, bias_p, mask_u8, keep, cfg.keep_scale)
     e = lse
-    return [out, _e(bias_p, e), lse, qmean, kmean, omega, beta, rf_k_bar, _e(saved, e), _e(zhat, e), _e(rstd, e)]
+    return [out, _e(bias_p, e), lse, qmean, kmean, omega, beta, rf_k_bar, _e(saved, e), _e(zhat, e), _e(rstd, e)] + more
 
 
 def eva_bwd_impl(dout, qkv5, mask_u8, keep, noise, out, saved_list, icfg, fcfg, adaptive_proj, bias_cols, mlp_params):
@@ -750,9 +835,13 @@ def _eva_backward(dout, qkv5, mask_u8, keep, noise, out, saved_list, cfg, bias_c
         raise RuntimeError("eva_bwd: defer_chunk_mean needs the composite entry points")
     geom, fused_mu = _eva_cfg(qkv5, cfg)
     L, mu_scale = cfg.L, cfg.mu_scale
-    bias_p, lse, qmean, kmean, omega, beta, rf_k_bar, saved, zhat, rstd = [_opt(t) for t in saved_list]
-    d_rfk, d_beta, dbias = _window_bwd(geom, qkv5, rf_k_bar, beta, bias_p, mask_u8, out,
-                                       _rows_contiguous(dout), lse, dqkv5, keep, cfg.keep_scale)
+    bias_p, lse, qmean, kmean, omega, beta, rf_k_bar, saved, zhat, rstd = [_opt(t) for t in saved_list[:10]]
+    if len(saved_list) > 10:                       # the forward took the split of _ceva_long_fwd
+        d_rfk, d_beta, dbias = _ceva_long_bwd(cfg, qkv5, bias_p, mask_u8, keep, out, _rows_contiguous(dout), lse,
+                                              saved_list[10:], dqkv5)
+    else:
+        d_rfk, d_beta, dbias = _window_bwd(geom, qkv5, rf_k_bar, beta, bias_p, mask_u8, out,
+                                           _rows_contiguous(dout), lse, dqkv5, keep, cfg.keep_scale)
     q, k, v = _qkv_views(qkv5)
     dq, dk, dv = _qkv_views(dqkv5)
     tk, tv, tdq, tdk, tdv = nv.t4(k), nv.t4(v), nv.t4(dq), nv.t4(dk), nv.t4(dv)

@@ -221,9 +221,12 @@ class CausalEVAttention(CevaDecoding, _ops.DerivedCacheOwner, nn.Module):
         assert N % r == 0, "sequence length %d is not a multiple of the chunk size %d" % (N, r)
         L = N // r
         bias = None
+        # more than 64 chunks on the fp32 route below; a training step on 16-bit activations keeps the 16-bit kernels instead
+        # (_ops._ceva_long_fwd: window half and landmark half apart)
+        f32_long = L > 64 and _f32.ENABLED and not self._ceva_long_ok(qkv5.dtype, x.is_cuda)
         # (the 16-bit kernel branch below takes the table itself: decided here so that the dense bias is not built twice)
         tb_ok = bool(self.use_t5_rpe and _ops.USE_TABLE_BIAS and x.is_cuda and qkv5.dtype != torch.float32
-                     and not (L > 64 and _f32.ENABLED) and _ops._DIRECT and not torch.compiler.is_compiling()
+                     and not f32_long and _ops._DIRECT and not torch.compiler.is_compiling()
                      and torch._C._len_torch_dispatch_stack() == 0)
         if self.use_t5_rpe and not tb_ok:
             bias = self.rel_pos_bias.dense(w, w + e, x.device).expand(h, w, w + e)
@@ -238,7 +241,7 @@ class CausalEVAttention(CevaDecoding, _ops.DerivedCacheOwner, nn.Module):
             # precision the reference computes it), the mu networks as the module's own layers
             out = _f32.causal_eva_core(qkv5, bias, noise, _ops._mask_u8(mask, B, N, x.device), w, e, r, bool(self.causal), mu_fn,
                                        *self._dropout_keep(B, h, N, w + e, L, x.device, raw=True))
-        elif L > 64 and _f32.ENABLED:
+        elif f32_long:
             # more chunks than the 16-bit window kernels hold landmark rows (64; the recipe's 512-token samples have exactly
             # 64): the generic fp32 kernels on the 16-bit activations -- the reference takes any length (causal_eva.py:680-700)
             with torch.autocast(device_type="cuda", enabled=False):
@@ -260,6 +263,12 @@ class CausalEVAttention(CevaDecoding, _ops.DerivedCacheOwner, nn.Module):
         if N != tgt_len:
             y = y[:tgt_len]
         return y.contiguous(), None
+
+    def _ceva_long_ok(self, dtype, is_cuda):
+        """Past 64 chunks the 16-bit core splits the softmax at the landmark columns (csrc/ea_ceva_lm.hip): causal masks, 16-bit
+        activations, head dim 64 / 128, autograd on -- a torch.no_grad() forward keeps the fp32 route."""
+        return bool(_ops.USE_CEVA_LONG and self.causal and is_cuda and dtype in (torch.bfloat16, torch.float16)
+                    and self.head_dim in (64, 128) and torch.is_grad_enabled())
 
     def _core_cfg(self, B, N, r, L, device):
         """-> (the _ops.EvaCfg of this module's core: 1-D windows, causal or not, mu = rq + rk; the attention dropout's keep mask
@@ -283,14 +292,16 @@ class CausalEVAttention(CevaDecoding, _ops.DerivedCacheOwner, nn.Module):
         causal EVA core -> output projection as one autograd node (_ops.CoreModuleFn around an _ops.GraphCore that records the
         core's own Function), so that both projections' weight gradients leave in one launch and their partial sums in one
         more -- the three-node path below pays two of each.  Returns None when it does not apply (fp32 activations, more than
-        64 chunks, quantization noise in training -- its draws keep the reference's order on the three-node path --, tracing)."""
+        64 chunks where _ceva_long_ok() says no, quantization noise in training -- its draws keep the reference's order on the three-node path --, tracing)."""
         w, e, h, d = self.window_size, self.ext_size, self.num_heads, self.head_dim
         if not (_ops.USE_CAUSAL_MODULE_FN and torch.is_autocast_enabled() and torch.is_grad_enabled() and x.is_cuda
                 and not (self.training and self.q_noise > 0)):
             return None
         cdtype = torch.get_autocast_dtype("cuda")
         r = self.chunk_size if self.chunk_size is not None else int(N // max(int(self.num_chunks or 1), 1))
-        if cdtype not in (torch.bfloat16, torch.float16) or r <= 0 or r >= N or N % r != 0 or N // r > 64:
+        if cdtype not in (torch.bfloat16, torch.float16) or r <= 0 or r >= N or N % r != 0:
+            return None
+        if N // r > 64 and not self._ceva_long_ok(cdtype, True):
             return None
         L = N // r
         ws = [self.q_proj.weight, self.k_proj.weight, self.v_proj.weight]

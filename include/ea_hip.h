@@ -95,6 +95,36 @@ int ea_eva_beta_bwd(const ea_geom* g, const ea_t4* k, const ea_t4* v, const uint
                     const float* omega, const float* beta, const float* dbeta,
                     const ea_t4* dk, const ea_t4* dv, float* domega, void* stream);
 
+/* ---- causal EVA past 64 chunks: landmark columns apart from the window half (ea_ceva_lm.hip) --------------------------
+ * Additive entries of ABI 38 (no existing signature changes, so the number stays).  The joint softmax of causal_eva.py:716-783
+ * over [ local columns | landmark columns ] is split at the landmark columns and joined through the two log-sum-exps:
+ *     Z = logaddexp(lse_loc, lse_lm),  out = e^(lse_loc - Z) o_loc + e^(lse_lm - Z) o_lm.
+ * The window half (o_loc, lse_loc) comes from ea_window_attn_fwd with L = 0 and ea_geom.causal = 2; these entries serve
+ * the landmark half for any L: landmark c is visible to token t iff c < lm_base + t / chunk, every other landmark column
+ * holds the fill -5e4 (zero gradient).  g: 1-D, causal = 2, chunk > 0, L > 0, D in {64, 128}; N <= 65536.
+ *   ea_ceva_lm_prepare: lk16, lv16 = 16-bit images [B*H, 64 ceil(L/64), D] of the fp32 lk, lv [B*H, L, D] (rf_k_bar, beta),
+ *     zero rows past L.
+ *   ea_ceva_lm_fwd: out and zl fp32 [B*H, N, 2] = (Z, lse_lm) per query (lse_lm over the landmark tiles the query's 64-query
+ *     tile walks -- the fills of later tiles weigh nothing in fp32 --, -inf when it walks none).  keep: uint8 [B*H, N, keep_ld]
+ *     keep mask of the landmark columns (column c = landmark c, keep_ld a multiple of 16, >= L) or NULL; kept
+ *     probabilities are scaled by keep_scale, the normaliser keeps every column.
+ *   ea_ceva_lm_bwd_q: do_loc = e^(lse_loc - Z) dout (I/O dtype), dlse_loc [B*H, N] = e^(lse_loc - Z) (dout . o_loc - delta),
+ *     dq fp32 [B, N, H, D] = scale dS . lk (the caller adds it to the window backward's dq), delta [B*H, N] =
+ *     rowsum(dout out), flags int32 [B*H, ceil(N/64)] (query tiles that hold a row of fills only).
+ *   ea_ceva_lm_bwd_k: dlk, dlv fp32 [B*H, L, D], every row stored once (no atomics: bit-reproducible); reads what
+ *     ea_ceva_lm_bwd_q wrote (delta, flags). */
+int ea_ceva_lm_prepare(const ea_geom* g, const float* lk, const float* lv, void* lk16, void* lv16, void* stream);
+int ea_ceva_lm_fwd(const ea_geom* g, const ea_t4* q, const void* lk16, const void* lv16, const ea_t4* o_loc,
+                   const float* lse_loc, const uint8_t* keep, int32_t keep_ld, float keep_scale, const ea_t4* out,
+                   float* zl, void* stream);
+int ea_ceva_lm_bwd_q(const ea_geom* g, const ea_t4* q, const void* lk16, const void* lv16, const ea_t4* o_loc,
+                     const float* lse_loc, const uint8_t* keep, int32_t keep_ld, float keep_scale, const ea_t4* out,
+                     const ea_t4* dout, const float* zl, const ea_t4* do_loc, float* dlse_loc, float* dq, float* delta,
+                     int32_t* flags, void* stream);
+int ea_ceva_lm_bwd_k(const ea_geom* g, const ea_t4* q, const void* lk16, const void* lv16, const uint8_t* keep,
+                     int32_t keep_ld, float keep_scale, const ea_t4* dout, const float* zl, const float* delta,
+                     const int32_t* flags, float* dlk, float* dlv, void* stream);
+
 /* ---- window attention with control-variate columns -----------------------------------------
  * One joint softmax per query over [ local window keys | L landmark keys ]:
  *     logits_local = s q.k_j + bias[h,i,j], masked_fill(-5e4)   (eva.py:204-218,
