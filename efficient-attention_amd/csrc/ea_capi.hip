@@ -22,6 +22,7 @@
 #include "ea_fold.h"
 #include "ea_lara_seglin.h"
 #include "ea_ceva_lm.h"
+#include "ea_eva_lm.h"
 
 using namespace ea;
 
@@ -202,6 +203,89 @@ int ea_ceva_lm_bwd_k(const ea_geom* g, const ea_t4* q, const void* lk16, const v
   p.lk16 = (const char*)lk16; p.lv16 = (const char*)lv16; p.zl = const_cast<float*>(zl);
   p.delta = const_cast<float*>(delta); p.flags = const_cast<int32_t*>(flags); p.dlk = dlk; p.dlv = dlv;
   return ceva_lm_dispatch(3, p, g->dtype, g->D, (hipStream_t)stream);
+}
+
+// ---- non-causal EVA past 64 landmarks: the dense landmark columns apart from the window half (ea_eva_lm.hip) ----
+static int fill_elm(const ea_geom* g, EvaLmP& p, int32_t slices = 0) {
+  if (!geom_ok(g) || g->causal != 0 || g->L <= 0 || slices < 0) return EA_E_BADARG;
+  if ((g->D != 64 && g->D != 128) || g->L < ELM_MIN_L || g->L > ELM_MAX_L || g->N > ELM_MAX_N || slices > ELM_MAX_SLICES ||
+      (int64_t)g->B * g->H * g->L * g->D >= ((int64_t)1 << 31)) return EA_E_UNSUPPORTED;
+  p.B = g->B; p.H = g->H; p.N = g->N; p.L = g->L;
+  p.nLT = (g->L + ELM_TILE - 1) / ELM_TILE; p.Lp = p.nLT * ELM_TILE;
+  p.nQT = (g->N + ELM_TILE - 1) / ELM_TILE;
+  p.scale = g->scale; p.scale_log2 = g->scale * LOG2E;
+  const int cus = ea_device_cus();
+  elm_plan_query(p, g->D, cus);
+  elm_plan_key(p, cus, slices);
+  return EA_OK;
+}
+static bool elm_img_ok(const void* lk16, const void* lv16) {
+  return lk16 && lv16 && (uintptr_t)lk16 % 16 == 0 && (uintptr_t)lv16 % 16 == 0;
+}
+
+int32_t ea_eva_lm_query_tiles(const ea_geom* g) {
+  EvaLmP p = {};
+  if (const int rc = fill_elm(g, p)) return rc;
+  return p.walk;
+}
+int32_t ea_eva_lm_key_slices(const ea_geom* g) {
+  EvaLmP p = {};
+  if (const int rc = fill_elm(g, p)) return rc;
+  return p.S;
+}
+
+int ea_eva_lm_prepare(const ea_geom* g, const float* lk, const float* lv, void* lk16, void* lv16, void* stream) {
+  EvaLmP p = {};
+  if (const int rc = fill_elm(g, p)) return rc;
+  if (!lk || !lv || (uintptr_t)lk % 16 || (uintptr_t)lv % 16 || !elm_img_ok(lk16, lv16)) return EA_E_BADARG;
+  p.lk = lk; p.lv = lv; p.lk16 = (const char*)lk16; p.lv16 = (const char*)lv16;
+  return eva_lm_dispatch(0, p, g->dtype, g->D, (hipStream_t)stream);
+}
+
+int ea_eva_lm_fwd(const ea_geom* g, const ea_t4* q, const void* lk16, const void* lv16, const ea_t4* o_loc,
+                  const float* lse_loc, const ea_t4* out, float* zl, void* stream) {
+  EvaLmP p = {};
+  if (const int rc = fill_elm(g, p)) return rc;
+  if (!view_ok(q, g->D, 2) || !view_ok(o_loc, g->D, 2) || !view_ok(out, g->D, 2) || !elm_img_ok(lk16, lv16) || !lse_loc ||
+      !zl || (uintptr_t)zl % 8) return EA_E_BADARG;
+  p.q = mk(q); p.oloc = mk(o_loc); p.out = mk(out);
+  p.lk16 = (const char*)lk16; p.lv16 = (const char*)lv16; p.lse_loc = lse_loc; p.zl = zl;
+  return eva_lm_dispatch(1, p, g->dtype, g->D, (hipStream_t)stream);
+}
+
+int ea_eva_lm_bwd_q(const ea_geom* g, const ea_t4* q, const void* lk16, const void* lv16, const ea_t4* o_loc,
+                    const float* lse_loc, const ea_t4* out, const ea_t4* dout, const float* zl, const ea_t4* do_loc,
+                    float* dlse_loc, float* dq, float* delta, void* stream) {
+  EvaLmP p = {};
+  if (const int rc = fill_elm(g, p)) return rc;
+  if (!view_ok(q, g->D, 2) || !view_ok(o_loc, g->D, 2) || !view_ok(out, g->D, 2) || !view_ok(dout, g->D, 2) ||
+      !view_ok(do_loc, g->D, 2) || !elm_img_ok(lk16, lv16) || !lse_loc || !zl || !dlse_loc || !dq || !delta ||
+      (uintptr_t)dq % 16) return EA_E_BADARG;
+  p.q = mk(q); p.oloc = mk(o_loc); p.out = mk(out); p.dout = mk(dout); p.doloc = mk(do_loc);
+  p.lk16 = (const char*)lk16; p.lv16 = (const char*)lv16; p.lse_loc = lse_loc; p.zl = const_cast<float*>(zl);
+  p.dlse_loc = dlse_loc; p.dq = dq; p.delta = delta;
+  return eva_lm_dispatch(2, p, g->dtype, g->D, (hipStream_t)stream);
+}
+
+int ea_eva_lm_bwd_k(const ea_geom* g, const ea_t4* q, const void* lk16, const void* lv16, const ea_t4* dout,
+                    const float* zl, const float* delta, int32_t slices, float* part, float* dlk, float* dlv, void* stream) {
+  EvaLmP p = {};
+  if (const int rc = fill_elm(g, p, slices)) return rc;
+  if (!view_ok(q, g->D, 2) || !view_ok(dout, g->D, 2) || !elm_img_ok(lk16, lv16) || !zl || !delta || !dlk || !dlv ||
+      (uintptr_t)dlk % 16 || (uintptr_t)dlv % 16 || (p.S > 1 && (!part || (uintptr_t)part % 16))) return EA_E_BADARG;
+  p.q = mk(q); p.dout = mk(dout);
+  p.lk16 = (const char*)lk16; p.lv16 = (const char*)lv16; p.zl = const_cast<float*>(zl); p.delta = const_cast<float*>(delta);
+  const int n = g->B * g->H * g->L * g->D;                  // floats of one slice plane
+  p.dlk = p.S > 1 ? part : dlk;
+  p.dlv = p.S > 1 ? part + (size_t)p.S * n : dlv;
+  if (const int rc = eva_lm_dispatch(3, p, g->dtype, g->D, (hipStream_t)stream)) return rc;
+  if (p.S == 1) return EA_OK;
+  // the slice planes, added up in multi_sum_kernel's fixed order: the same bits on every run
+  const float* parts[2] = {p.dlk, p.dlv};
+  float* outs[2] = {dlk, dlv};
+  const int S2[2] = {p.S, p.S}, n2[2] = {n, n};
+  const long long ld2[2] = {n, n};
+  return multi_sum_dispatch(2, parts, S2, n2, ld2, outs, (hipStream_t)stream);
 }
 
 // ---- EVA landmark statistics ----

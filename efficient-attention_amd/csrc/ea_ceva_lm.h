@@ -3,10 +3,10 @@
 #pragma once
 #include "ea_common.h"
 #include "ea_t4.h"
+#include "ea_lm_frag.h"
 
 namespace ea {
 
-constexpr int CLM_TILE = 64;             // queries per workgroup / landmark rows per streamed tile
 constexpr int CLM_MAX_QT = 1024;         // query tiles per (b, h) the key-side kernel lists in LDS (N <= 65536)
 constexpr float CLM_DEGENERATE = -4e4f;  // a row whose joint lse lies below this has nothing but -5e4 fills: they all count
 

@@ -139,6 +139,12 @@ SIGNATURES = {
     "ea_ceva_lm_fwd": [_G, _T, _P, _P, _T, _P, _P, _I, _F, _T, _P, _P],
     "ea_ceva_lm_bwd_q": [_G, _T, _P, _P, _T, _P, _P, _I, _F, _T, _T, _P, _T, _P, _P, _P, _P, _P],
     "ea_ceva_lm_bwd_k": [_G, _T, _P, _P, _P, _I, _F, _T, _P, _P, _P, _P, _P, _P],
+    "ea_eva_lm_query_tiles": [_G],
+    "ea_eva_lm_key_slices": [_G],
+    "ea_eva_lm_prepare": [_G, _P, _P, _P, _P, _P],
+    "ea_eva_lm_fwd": [_G, _T, _P, _P, _T, _P, _T, _P, _P],
+    "ea_eva_lm_bwd_q": [_G, _T, _P, _P, _T, _P, _T, _T, _P, _T, _P, _P, _P, _P],
+    "ea_eva_lm_bwd_k": [_G, _T, _P, _P, _T, _P, _P, _I, _P, _P, _P, _P],
     "ea_rows_mlp_parts": [_I, _I],
     "ea_rows_mlp_fwd": [_I] * 4 + [_P] * 15,
     "ea_rows_mlp_bwd": [_I] * 4 + [_P] * 15,

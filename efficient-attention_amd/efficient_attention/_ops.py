@@ -625,6 +625,81 @@ def _ceva_long_bwd(cfg, qkv5, bias_p, mask_u8, keep, out, dout, lse_loc, more, d
     return dlk, dlv, dbias
 
 
+# EVA past 64 landmarks on the 16-bit kernels (csrc/ea_eva_lm.hip); EA_EVA_LONG=0: the fp32 gathered-attention route
+USE_EVA_LONG = os.environ.get("EA_EVA_LONG", "1") == "1"
+
+
+def eva_long_applies(cfg, d):
+    """Non-causal EVA whose chunks tile the sequence exactly, more landmarks than the window kernels hold, head dim 64 or 128."""
+    r = int(cfg.chunk)
+    return (USE_EVA_LONG and cfg.causal == 0 and 64 < cfg.L <= 8192 and d in (64, 128) and r > 0
+            and all(int(s) % r == 0 for s in cfg.seq_shape))
+
+
+def eva_lm_fwd(g, q, lk, lv, o_loc, lse_loc):
+    """The dense landmark half of EVA's softmax and its join with the window half (ea_eva_lm_prepare / _fwd).  g: ea_geom with
+    causal = 0 and L > 64 landmarks; q [B,h,N,d] 16-bit view; lk, lv fp32 [B,h,L,d] contiguous; o_loc [B,N,h,d], lse_loc [B,h,N]
+    of the window half -> out (o_loc's layout), zl [B,h,N,2] = (Z, lse_lm), the 16-bit landmark images [2, B h, 64 ceil(L/64), d]."""
+    B, h, N, d = q.shape
+    img = torch.empty((2, B * h, -(-g.L // 64) * 64, d), dtype=q.dtype, device=q.device)
+    nv.call("ea_eva_lm_prepare", ctypes.byref(g), nv.ptr(lk), nv.ptr(lv), nv.ptr(img[0]), nv.ptr(img[1]), nv.stream())
+    out = torch.empty_like(o_loc)
+    zl = torch.empty((B, h, N, 2), dtype=torch.float32, device=q.device)
+    tq, tol, to = nv.t4(q), nv.t4(o_loc.permute(0, 2, 1, 3)), nv.t4(out.permute(0, 2, 1, 3))
+    nv.call("ea_eva_lm_fwd", ctypes.byref(g), ctypes.byref(tq), nv.ptr(img[0]), nv.ptr(img[1]), ctypes.byref(tol), nv.ptr(lse_loc),
+            ctypes.byref(to), nv.ptr(zl), nv.stream())
+    return out, zl, img
+
+
+def eva_lm_bwd(g, q, img, o_loc, lse_loc, out, dout, zl, slices=None):
+    """Backward of eva_lm_fwd (ea_eva_lm_bwd_q, then _bwd_k) -> d o_loc (I/O dtype, o_loc's layout), d lse_loc [B,h,N],
+    dq [B,N,h,d] fp32 (the landmark columns' share), d lk, d lv [B,h,L,d] fp32.  slices: the query slices of the key-side
+    kernel (None: the planner's, ea_eva_lm_key_slices)."""
+    B, h, N, d = q.shape
+    dev = q.device
+    S = nv.query("ea_eva_lm_key_slices", g) if slices is None else int(slices)
+    do_loc = torch.empty_like(o_loc)
+    dlse = torch.empty((B, h, N), dtype=torch.float32, device=dev)
+    delta = torch.empty_like(dlse)
+    dq_lm = torch.empty((B, N, h, d), dtype=torch.float32, device=dev)
+    dl = torch.empty((2, B, h, g.L, d), dtype=torch.float32, device=dev)
+    part = torch.empty((2, S, B, h, g.L, d), dtype=torch.float32, device=dev) if S > 1 else None
+    ts = [nv.t4(t) for t in (q, o_loc.permute(0, 2, 1, 3), out.permute(0, 2, 1, 3), dout.permute(0, 2, 1, 3),
+                             do_loc.permute(0, 2, 1, 3))]
+    nv.call("ea_eva_lm_bwd_q", ctypes.byref(g), ctypes.byref(ts[0]), nv.ptr(img[0]), nv.ptr(img[1]), ctypes.byref(ts[1]),
+            nv.ptr(lse_loc), ctypes.byref(ts[2]), ctypes.byref(ts[3]), nv.ptr(zl), ctypes.byref(ts[4]), nv.ptr(dlse),
+            nv.ptr(dq_lm), nv.ptr(delta), nv.stream())
+    nv.call("ea_eva_lm_bwd_k", ctypes.byref(g), ctypes.byref(ts[0]), nv.ptr(img[0]), nv.ptr(img[1]), ctypes.byref(ts[3]),
+            nv.ptr(zl), nv.ptr(delta), S, nv.ptr(part), nv.ptr(dl[0]), nv.ptr(dl[1]), nv.stream())
+    return do_loc, dlse, dq_lm, dl[0], dl[1]
+
+
+def _eva_long_geoms(cfg, qkv5):
+    """-> (geometry of the window half: no landmark columns; geometry of the dense landmark half)."""
+    B, N, _, h, d = qkv5.shape
+    mk = lambda chunk, L: nv.make_geom(B, h, N, d, nv.io_dtype(qkv5), cfg.attn_2d, cfg.seq_shape, cfg.window, cfg.ext, chunk, L, 0)
+    return mk(0, 0), mk(cfg.chunk, cfg.L)
+
+
+def _eva_long_fwd(cfg, qkv5, lk, lv, bias_p, mask_u8):
+    """EVA's joint softmax with L > 64 landmark columns -> out, lse_loc, [o_loc, (Z, lse_lm), 16-bit landmark images]: the
+    window kernels on the local columns alone (L = 0), then the dense landmark columns and the join (eva_lm_fwd)."""
+    g0, g = _eva_long_geoms(cfg, qkv5)
+    o_loc, lse_loc = _window_fwd(g0, qkv5, None, None, bias_p, mask_u8)
+    out, zl, img = eva_lm_fwd(g, _qkv_views(qkv5)[0], lk, lv, o_loc, lse_loc)
+    return out, lse_loc, [o_loc, zl, img]
+
+
+def _eva_long_bwd(cfg, qkv5, bias_p, mask_u8, out, dout, lse_loc, more, dqkv5):
+    """Backward of _eva_long_fwd: writes dq, dk, dv into dqkv5 -> d rf_k_bar, d beta [B,h,L,d] fp32, dbias_padded."""
+    o_loc, zl, img = more
+    g0, g = _eva_long_geoms(cfg, qkv5)
+    do_loc, dlse, dq_lm, dlk, dlv = eva_lm_bwd(g, _qkv_views(qkv5)[0], img, o_loc, lse_loc, out, dout, zl)
+    _, _, dbias = _window_bwd(g0, qkv5, None, None, bias_p, mask_u8, o_loc, do_loc, lse_loc, dqkv5, dlse=dlse)
+    dqkv5[:, :, 0].add_(dq_lm)                     # (fp32 sum, rounded once more into the I/O dtype)
+    return dlk, dlv, dbias
+
+
 def _eva_fused_mu(cfg, d):
     return cfg.adaptive_proj == "default" and cfg.L <= 64 and d in (32, 64) and cfg.mu_scale == 0.5
 
@@ -778,6 +853,9 @@ def eva_fwd_impl(qkv5, bias, noise, mask_u8, keep, icfg, fcfg, adaptive_proj, ml
     if ceva_long_applies(cfg, d):
         # more than 64 chunks: window half and landmark half apart, joined through their log-sum-exps (lse = the window half's)
         out, lse, more = _ceva_long_fwd(cfg, qkv5, rf_k_bar, beta, bias_p, mask_u8, keep)
+    elif eva_long_applies(cfg, d):
+        # more than 64 landmarks: the same split with the dense landmark half of csrc/ea_eva_lm.hip
+        out, lse, more = _eva_long_fwd(cfg, qkv5, rf_k_bar, beta, bias_p, mask_u8)
     else:
         out, lse = _window_fwd(geom, qkv5, rf_k_bar, beta, bias_p, mask_u8, keep, cfg.keep_scale)
     e = lse
@@ -836,7 +914,9 @@ def _eva_backward(dout, qkv5, mask_u8, keep, noise, out, saved_list, cfg, bias_c
     geom, fused_mu = _eva_cfg(qkv5, cfg)
     L, mu_scale = cfg.L, cfg.mu_scale
     bias_p, lse, qmean, kmean, omega, beta, rf_k_bar, saved, zhat, rstd = [_opt(t) for t in saved_list[:10]]
-    if len(saved_list) > 10:                       # the forward took the split of _ceva_long_fwd
+    if len(saved_list) > 10 and cfg.causal == 0:   # the forward took the split of _eva_long_fwd
+        d_rfk, d_beta, dbias = _eva_long_bwd(cfg, qkv5, bias_p, mask_u8, out, _rows_contiguous(dout), lse, saved_list[10:], dqkv5)
+    elif len(saved_list) > 10:                     # ... of _ceva_long_fwd
         d_rfk, d_beta, dbias = _ceva_long_bwd(cfg, qkv5, bias_p, mask_u8, keep, out, _rows_contiguous(dout), lse,
                                               saved_list[10:], dqkv5)
     else:

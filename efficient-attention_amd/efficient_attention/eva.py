@@ -241,9 +241,13 @@ class EVA(LocalAttention):
         if qkv5.dtype == torch.float32:
             # fp32 outside autocast (round 5): the core on the fp32-faithful kernels, the mu networks as the module's own layers
             out = _f32.eva_core(qkv5, bias, noise, mask, self.attn_2d, tuple(seq_shape), w, e, r, self._mu_f32)
+        elif L > 64 and qkv5.is_cuda and _ops.eva_long_applies(cfg, d):
+            # more landmarks than the 16-bit window kernels hold (64): window half and dense landmark half apart, joined through
+            # their log-sum-exps (csrc/ea_eva_lm.hip); EA_EVA_LONG=0 restores the fp32 route below
+            out = _ops.EvaAttnFn.apply(qkv5, bias, noise, mask, cfg, None, *self._mu_params())
         elif L > 64 and _f32.ENABLED:
-            # more landmarks than the 16-bit window kernels hold (64): the generic fp32 kernels on the 16-bit activations
-            # (exact in fp32) -- the reference takes any --num-landmarks (eva.py:155-164)
+            # ... outside that route's envelope (d = 32, chunks that do not tile the grid): the generic fp32 kernels on the 16-bit
+            # activations (exact in fp32) -- the reference takes any --num-landmarks (eva.py:155-164)
             with torch.autocast(device_type="cuda", enabled=False):
                 out = _f32.eva_core(qkv5.float(), None if bias is None else bias.float(), noise, mask, self.attn_2d,
                                     tuple(seq_shape), w, e, r, self._mu_f32).to(qkv5.dtype)

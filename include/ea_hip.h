@@ -125,6 +125,35 @@ int ea_ceva_lm_bwd_k(const ea_geom* g, const ea_t4* q, const void* lk16, const v
                      int32_t keep_ld, float keep_scale, const ea_t4* dout, const float* zl, const float* delta,
                      const int32_t* flags, float* dlk, float* dlv, void* stream);
 
+/* ---- EVA past 64 landmarks: dense landmark columns apart from the window half (ea_eva_lm.hip) --------------------------
+ * Additive entries of ABI 38.  The joint softmax of eva.py:200-227 over [ local columns | all L landmark columns ] is split at
+ * the landmark columns and joined through the two log-sum-exps:
+ *     s_tc = scale q_t . lk_c,  lse_lm = LSE_c s_tc,  Z = logaddexp(lse_loc, lse_lm),
+ *     out = e^(lse_loc - Z) o_loc + sum_c e^(s_tc - Z) lv_c            (no visibility rule, no fill columns, no dropout).
+ * The window half (o_loc, lse_loc) comes from ea_window_attn_fwd with L = 0.  g: causal = 0, 1-D or 2-D (only B, H, N, D, L,
+ * dtype and scale are read), D in {64, 128}, 65 <= L <= 8192, N <= 2^20, B H L D < 2^31; EA_E_UNSUPPORTED outside.
+ *   ea_eva_lm_query_tiles: consecutive 64-query tiles a workgroup of _fwd / _bwd_q walks (1 .. 8; 1 where the 16-bit images
+ *     do not both fit 128 KB of LDS and stream instead).
+ *   ea_eva_lm_key_slices: S, the slices _bwd_k splits the query range into when `slices` = 0 (1 .. min(32, ceil(N / 64))).
+ *   ea_eva_lm_prepare: lk16, lv16 = 16-bit images [B*H, 64 ceil(L/64), D] of the fp32 lk, lv [B*H, L, D], zero rows past L.
+ *   ea_eva_lm_fwd: out (I/O dtype) and zl fp32 [B*H, N, 2] = (Z, lse_lm) per query.
+ *   ea_eva_lm_bwd_q: do_loc = e^(lse_loc - Z) dout (I/O dtype), dlse_loc [B*H, N] = e^(lse_loc - Z) (dout . o_loc - delta),
+ *     dq fp32 [B, N, H, D] = scale dS . lk with dS = p (dout . lv - delta) (the caller adds it to the window backward's dq),
+ *     delta [B*H, N] = rowsum(dout out).
+ *   ea_eva_lm_bwd_k: dlk = scale dS^T . q, dlv = P^T . dout, fp32 [B*H, L, D]; reads the delta _bwd_q wrote.  slices: 0 = the
+ *     planner's S, else 1 .. 32; part: fp32 [2, S, B*H, L, D] scratch (may be NULL when S = 1).  Slice partials are stored
+ *     once and added in a fixed order (no atomics: bit-reproducible). */
+int32_t ea_eva_lm_query_tiles(const ea_geom* g);
+int32_t ea_eva_lm_key_slices(const ea_geom* g);
+int ea_eva_lm_prepare(const ea_geom* g, const float* lk, const float* lv, void* lk16, void* lv16, void* stream);
+int ea_eva_lm_fwd(const ea_geom* g, const ea_t4* q, const void* lk16, const void* lv16, const ea_t4* o_loc,
+                  const float* lse_loc, const ea_t4* out, float* zl, void* stream);
+int ea_eva_lm_bwd_q(const ea_geom* g, const ea_t4* q, const void* lk16, const void* lv16, const ea_t4* o_loc,
+                    const float* lse_loc, const ea_t4* out, const ea_t4* dout, const float* zl, const ea_t4* do_loc,
+                    float* dlse_loc, float* dq, float* delta, void* stream);
+int ea_eva_lm_bwd_k(const ea_geom* g, const ea_t4* q, const void* lk16, const void* lv16, const ea_t4* dout,
+                    const float* zl, const float* delta, int32_t slices, float* part, float* dlk, float* dlv, void* stream);
+
 /* ---- window attention with control-variate columns -----------------------------------------
  * One joint softmax per query over [ local window keys | L landmark keys ]:
  *     logits_local = s q.k_j + bias[h,i,j], masked_fill(-5e4)   (eva.py:204-218,
