@@ -23,6 +23,7 @@
 #include "ea_lara_seglin.h"
 #include "ea_ceva_lm.h"
 #include "ea_eva_lm.h"
+#include "ea_lara_lm.h"
 
 using namespace ea;
 
@@ -364,10 +365,12 @@ int ea_eva_beta_bwd(const ea_geom* g, const ea_t4* k, const ea_t4* v, const uint
 // ---- LARA ----
 static int lara_nsub(int NCT) { return NCT == 1 ? 4 : (NCT == 2 ? 2 : 1); }
 // X passes: blocks per (b,h) and tokens per block; Y passes: sequence splits
-static int fill_lara(const ea_lara_geom* g, LaraP& p, bool ypass) {
+// long: the token-row passes (ea_lara_y.hip put their 16-sample tiles on grid.y) also take the C <= 512 at D = 64 whose
+// token-column passes are ea_lara_lm.hip's
+static int fill_lara(const ea_lara_geom* g, LaraP& p, bool ypass, bool long_ok = false) {
   if (!g || g->B <= 0 || g->H <= 0 || g->N <= 0 || (g->D != 32 && g->D != 64) || g->C <= 0 ||
       (g->dtype != EA_BF16 && g->dtype != EA_F16) || g->mis < 0 || g->mis > 2) return EA_E_BADARG;
-  if (g->C > 128) return EA_E_UNSUPPORTED;
+  if (g->C > ((long_ok && ypass && g->D == 64) ? LLM_MAX_C : 128)) return EA_E_UNSUPPORTED;
   p.B = g->B; p.H = g->H; p.N = g->N; p.D = g->D; p.C = g->C; p.NCT = (g->C + 15) / 16;
   p.mis = g->mis; p.kappa = g->kappa; p.scale = g->scale; p.scale_log2 = g->scale * LOG2E;
   p.norm_coef2 = 0.5f * g->scale * LOG2E;      // s |k|^2 / 2 in the log2 domain
@@ -396,25 +399,73 @@ static int fill_lara(const ea_lara_geom* g, LaraP& p, bool ypass) {
   return EA_OK;
 }
 
-extern "C" {
-
-int32_t ea_lara_parts(const ea_lara_geom* g) {
+// the token-row entries, shared by ea_lara_* (C <= 128) and ea_lara_lm_* (long_ok: C <= 512 at D = 64)
+static int32_t lara_parts(const ea_lara_geom* g, bool long_ok) {
   LaraP p = {};
-  if (const int rc = fill_lara(g, p, true)) return rc;      // (C > 128 is an unsupported geometry, not a bad argument)
+  if (const int rc = fill_lara(g, p, true, long_ok)) return rc;      // (C > 128 is an unsupported geometry, not a bad argument)
   return p.nsplit * lara_nsub(p.NCT);
 }
 
-int ea_lara_stats_fwd(const ea_lara_geom* g, const ea_t4* q, const ea_t4* k, const ea_t4* v,
-                      const uint8_t* mask, const float* omega, const float* qbar,
-                      float* p_ml, float* p_kv, void* stream) {
+static int lara_stats_fwd(const ea_lara_geom* g, const ea_t4* q, const ea_t4* k, const ea_t4* v,
+                          const uint8_t* mask, const float* omega, const float* qbar,
+                          float* p_ml, float* p_kv, void* stream, bool long_ok) {
   LaraP p = {};
-  int rc = fill_lara(g, p, true);
+  int rc = fill_lara(g, p, true, long_ok);
   if (rc != EA_OK) return rc;
   if (!view_ok(q, g->D, 2) || !view_ok(k, g->D, 2) || !view_ok(v, g->D, 2) || !omega || !p_ml || !p_kv ||
       (g->mis == EA_MIS_OPT && !qbar)) return EA_E_BADARG;
   p.q = mk(q); p.k = mk(k); p.v = mk(v); p.mask = mask; p.omega = omega; p.qbar = qbar;
   p.p_ml = p_ml; p.p_acc0 = p_kv;
   return lara_y_dispatch(LY_FWD, p, g->dtype, (hipStream_t)stream);
+}
+
+static int lara_bwd_qstats(const ea_lara_geom* g, const ea_t4* q, const ea_t4* dout, const float* omega,
+                           const float* qbar, const float* kv, const float* lse_t, const float* bhv,
+                           const float* cst, const float* lseZ, const float* tmean, const float* rowdot,
+                           const float* sda, float* p_ml, float* p_dkv, float* p_dom, float* p_m1,
+                           float* p_m2, void* stream, bool long_ok) {
+  LaraP p = {};
+  int rc = fill_lara(g, p, true, long_ok);
+  if (rc != EA_OK) return rc;
+  if (!view_ok(q, g->D, 2) || !view_ok(dout, g->D, 2) || !omega || !kv || !cst || !lseZ || !tmean ||
+      !rowdot || !sda || !p_ml || !p_dkv || !p_dom) return EA_E_BADARG;
+  if (g->mis == EA_MIS_OPT && (!qbar || !lse_t || !bhv || !p_m1 || !p_m2)) return EA_E_BADARG;
+  if (g->mis == EA_MIS_BIASED && !qbar) return EA_E_BADARG;
+  p.q = mk(q); p.dout = mk(dout); p.omega = omega; p.qbar = qbar; p.kv = kv; p.lse_t = lse_t;
+  p.bhv = bhv; p.cst = cst;
+  p.lseZ = const_cast<float*>(lseZ); p.tmean = const_cast<float*>(tmean);
+  p.rowdot = const_cast<float*>(rowdot); p.sda = const_cast<float*>(sda);
+  p.p_ml = p_ml; p.p_acc0 = p_dkv; p.p_acc1 = p_dom; p.p_acc2 = p_m1; p.p_acc3 = p_m2;
+  return lara_y_dispatch(LY_BWDQ, p, g->dtype, (hipStream_t)stream);
+}
+
+static int lara_bwd_kstats(const ea_lara_geom* g, const ea_t4* k, const ea_t4* v, const uint8_t* mask,
+                           const float* omega, const float* dkv, const float* lse_k, const float* dkk,
+                           const float* rsum, float* p_dom, void* stream, bool long_ok) {
+  LaraP p = {};
+  int rc = fill_lara(g, p, true, long_ok);
+  if (rc != EA_OK) return rc;
+  if (!view_ok(k, g->D, 2) || !view_ok(v, g->D, 2) || !omega || !dkv || !lse_k || !dkk || !rsum || !p_dom)
+    return EA_E_BADARG;
+  p.k = mk(k); p.v = mk(v); p.mask = mask; p.omega = omega; p.dkv = dkv; p.lse_k = lse_k;
+  p.dkk = dkk; p.rsum = rsum; p.p_acc0 = p_dom;
+  return lara_y_dispatch(LY_BWDK, p, g->dtype, (hipStream_t)stream);
+}
+
+extern "C" {
+
+int32_t ea_lara_parts(const ea_lara_geom* g) { return lara_parts(g, false); }
+int32_t ea_lara_lm_parts(const ea_lara_geom* g) { return lara_parts(g, true); }
+
+int ea_lara_stats_fwd(const ea_lara_geom* g, const ea_t4* q, const ea_t4* k, const ea_t4* v,
+                      const uint8_t* mask, const float* omega, const float* qbar,
+                      float* p_ml, float* p_kv, void* stream) {
+  return lara_stats_fwd(g, q, k, v, mask, omega, qbar, p_ml, p_kv, stream, false);
+}
+int ea_lara_lm_stats_fwd(const ea_lara_geom* g, const ea_t4* q, const ea_t4* k, const ea_t4* v,
+                         const uint8_t* mask, const float* omega, const float* qbar,
+                         float* p_ml, float* p_kv, void* stream) {
+  return lara_stats_fwd(g, q, k, v, mask, omega, qbar, p_ml, p_kv, stream, true);
 }
 
 int ea_lara_out_fwd(const ea_lara_geom* g, const ea_t4* q, const float* omega, const float* qbar,
@@ -454,19 +505,16 @@ int ea_lara_bwd_qstats(const ea_lara_geom* g, const ea_t4* q, const ea_t4* dout,
                        const float* cst, const float* lseZ, const float* tmean, const float* rowdot,
                        const float* sda, float* p_ml, float* p_dkv, float* p_dom, float* p_m1,
                        float* p_m2, void* stream) {
-  LaraP p = {};
-  int rc = fill_lara(g, p, true);
-  if (rc != EA_OK) return rc;
-  if (!view_ok(q, g->D, 2) || !view_ok(dout, g->D, 2) || !omega || !kv || !cst || !lseZ || !tmean ||
-      !rowdot || !sda || !p_ml || !p_dkv || !p_dom) return EA_E_BADARG;
-  if (g->mis == EA_MIS_OPT && (!qbar || !lse_t || !bhv || !p_m1 || !p_m2)) return EA_E_BADARG;
-  if (g->mis == EA_MIS_BIASED && !qbar) return EA_E_BADARG;
-  p.q = mk(q); p.dout = mk(dout); p.omega = omega; p.qbar = qbar; p.kv = kv; p.lse_t = lse_t;
-  p.bhv = bhv; p.cst = cst;
-  p.lseZ = const_cast<float*>(lseZ); p.tmean = const_cast<float*>(tmean);
-  p.rowdot = const_cast<float*>(rowdot); p.sda = const_cast<float*>(sda);
-  p.p_ml = p_ml; p.p_acc0 = p_dkv; p.p_acc1 = p_dom; p.p_acc2 = p_m1; p.p_acc3 = p_m2;
-  return lara_y_dispatch(LY_BWDQ, p, g->dtype, (hipStream_t)stream);
+  return lara_bwd_qstats(g, q, dout, omega, qbar, kv, lse_t, bhv, cst, lseZ, tmean, rowdot, sda, p_ml, p_dkv, p_dom, p_m1, p_m2,
+                         stream, false);
+}
+int ea_lara_lm_bwd_qstats(const ea_lara_geom* g, const ea_t4* q, const ea_t4* dout, const float* omega,
+                          const float* qbar, const float* kv, const float* lse_t, const float* bhv,
+                          const float* cst, const float* lseZ, const float* tmean, const float* rowdot,
+                          const float* sda, float* p_ml, float* p_dkv, float* p_dom, float* p_m1,
+                          float* p_m2, void* stream) {
+  return lara_bwd_qstats(g, q, dout, omega, qbar, kv, lse_t, bhv, cst, lseZ, tmean, rowdot, sda, p_ml, p_dkv, p_dom, p_m1, p_m2,
+                         stream, true);
 }
 
 int ea_lara_bwd_k(const ea_lara_geom* g, const ea_t4* k, const ea_t4* v, const uint8_t* mask,
@@ -485,14 +533,12 @@ int ea_lara_bwd_k(const ea_lara_geom* g, const ea_t4* k, const ea_t4* v, const u
 int ea_lara_bwd_kstats(const ea_lara_geom* g, const ea_t4* k, const ea_t4* v, const uint8_t* mask,
                        const float* omega, const float* dkv, const float* lse_k, const float* dkk,
                        const float* rsum, float* p_dom, void* stream) {
-  LaraP p = {};
-  int rc = fill_lara(g, p, true);
-  if (rc != EA_OK) return rc;
-  if (!view_ok(k, g->D, 2) || !view_ok(v, g->D, 2) || !omega || !dkv || !lse_k || !dkk || !rsum || !p_dom)
-    return EA_E_BADARG;
-  p.k = mk(k); p.v = mk(v); p.mask = mask; p.omega = omega; p.dkv = dkv; p.lse_k = lse_k;
-  p.dkk = dkk; p.rsum = rsum; p.p_acc0 = p_dom;
-  return lara_y_dispatch(LY_BWDK, p, g->dtype, (hipStream_t)stream);
+  return lara_bwd_kstats(g, k, v, mask, omega, dkv, lse_k, dkk, rsum, p_dom, stream, false);
+}
+int ea_lara_lm_bwd_kstats(const ea_lara_geom* g, const ea_t4* k, const ea_t4* v, const uint8_t* mask,
+                          const float* omega, const float* dkv, const float* lse_k, const float* dkk,
+                          const float* rsum, float* p_dom, void* stream) {
+  return lara_bwd_kstats(g, k, v, mask, omega, dkv, lse_k, dkk, rsum, p_dom, stream, true);
 }
 
 // ---- fused backward (ea_lara_f.hip): one pass per side + one finish pass ----
@@ -632,6 +678,102 @@ int ea_lara_bwd_qcorr(const ea_lara_geom* g, const ea_t4* q, const float* qbar, 
   if (!view_ok(q, g->D, 2) || !view_ok(dq, g->D, 2) || !qbar || !uq || !lse_t) return EA_E_BADARG;
   p.q = mk(q); p.dq = mk(dq); p.qbar = qbar; p.uq = uq; p.lse_t = lse_t;
   return lara_x_dispatch(LX_QCORR, p, g->dtype, (hipStream_t)stream);
+}
+
+}  // extern "C"
+
+// ---- LARA past 128 samples: the token-column passes as a loop over 64-sample groups (ea_lara_lm.hip) ----
+static int fill_llm(const ea_lara_geom* g, LaraLmP& p, int mode, int32_t plan) {
+  if (!g || g->B <= 0 || g->H <= 0 || g->N <= 0 || g->C <= 0 || (g->dtype != EA_BF16 && g->dtype != EA_F16) || g->mis < 0 ||
+      g->mis > 2 || plan < LLM_PLAN_AUTO || plan > LLM_PLAN_STREAMED) return EA_E_BADARG;
+  if (g->D != 64 || g->C < LLM_MIN_C || g->C > LLM_MAX_C || (int64_t)g->B * g->H * ((g->N + 63) / 64) >= ((int64_t)1 << 31))
+    return EA_E_UNSUPPORTED;
+  p.B = g->B; p.H = g->H; p.N = g->N; p.C = g->C; p.NG = (g->C + LLM_GROUP - 1) / LLM_GROUP; p.Cp = p.NG * LLM_GROUP;
+  p.mis = g->mis; p.kappa = g->kappa; p.scale = g->scale; p.scale_log2 = g->scale * LOG2E;
+  if (mode >= 0 && !llm_plan(p, mode, plan, ea_device_cus())) return EA_E_UNSUPPORTED;
+  return EA_OK;
+}
+static bool llm_img(LaraLmP& p, const void* img, const float* scal, bool i0, bool i1) {
+  if (!img || (uintptr_t)img % 16 || !scal || (uintptr_t)scal % 16) return false;
+  const size_t plane = (size_t)p.B * p.H * p.Cp * 64 * 2;
+  p.img[0] = i0 ? (const char*)img : nullptr;
+  p.img[1] = i1 ? (const char*)img + plane : nullptr;
+  p.img[2] = (const char*)img + 2 * plane;
+  p.sc = scal;
+  return true;
+}
+
+extern "C" {
+
+int32_t ea_lara_lm_plan(const ea_lara_geom* g, int32_t pass, int32_t plan) {
+  LaraLmP p = {};
+  if (pass < LLM_FWD || pass > LLM_QCORR) return EA_E_BADARG;
+  if (const int rc = fill_llm(g, p, pass, plan)) return rc;
+  return p.resident ? LLM_PLAN_RESIDENT : LLM_PLAN_STREAMED;
+}
+
+int ea_lara_lm_prepare(const ea_lara_geom* g, int32_t kind, const float* m0, const float* m1, const float* m2, const float* s0,
+                       const float* s1, const float* s2, void* img, float* scal, void* stream) {
+  LaraLmP p = {};
+  if (const int rc = fill_llm(g, p, -1, 0)) return rc;
+  if (kind < 0 || kind > 1 || !img || (uintptr_t)img % 16 || !scal || (uintptr_t)scal % 16) return EA_E_BADARG;
+  const float* m[3] = {m0, m1, m2};
+  const size_t plane = (size_t)p.B * p.H * p.Cp * 64 * 2;
+  for (int j = 0; j < 3; ++j) {
+    if ((uintptr_t)m[j] % 16) return EA_E_BADARG;
+    p.src[j] = m[j];
+    p.dst[j] = m[j] ? (char*)img + j * plane : nullptr;
+  }
+  p.ssrc[0] = s0; p.ssrc[1] = s1; p.ssrc[2] = s2; p.sdst = scal;
+  if (kind == 0) {          // (cst, lse_t, bhv)
+    p.smul[0] = LOG2E; p.smul[1] = LOG2E; p.smul[2] = 1.f;
+    p.spad[0] = -INFINITY; p.spad[1] = INFINITY; p.spad[2] = 1.f;
+  } else {                  // (lse_k, dkk, r)
+    p.smul[0] = LOG2E; p.smul[1] = 1.f; p.smul[2] = 1.f;
+    p.spad[0] = INFINITY; p.spad[1] = 0.f; p.spad[2] = 0.f;
+  }
+  return lara_lm_dispatch(-1, p, g->dtype, (hipStream_t)stream);
+}
+
+int ea_lara_lm_out_fwd(const ea_lara_geom* g, const ea_t4* q, const void* img, const float* scal, const ea_t4* out, float* lseZ,
+                       float* tmean, int32_t plan, void* stream) {
+  LaraLmP p = {};
+  if (const int rc = fill_llm(g, p, LLM_FWD, plan)) return rc;
+  if (!view_ok(q, 64, 2) || !view_ok(out, 64, 2) || (lseZ == nullptr) != (tmean == nullptr) ||
+      !llm_img(p, img, scal, true, g->mis != EA_MIS_BH)) return EA_E_BADARG;
+  p.q = mk(q); p.o = mk(out); p.lseZ = lseZ; p.tmean = tmean;
+  return lara_lm_dispatch(LLM_FWD, p, g->dtype, (hipStream_t)stream);
+}
+
+int ea_lara_lm_bwd_q(const ea_lara_geom* g, const ea_t4* q, const ea_t4* dout, const void* img, const float* scal,
+                     const float* lseZ, const float* tmean, const ea_t4* dq, float* rowdot, float* sda, int32_t plan,
+                     void* stream) {
+  LaraLmP p = {};
+  if (const int rc = fill_llm(g, p, LLM_BWDQ, plan)) return rc;
+  if (!view_ok(q, 64, 2) || !view_ok(dout, 64, 2) || !view_ok(dq, 64, 2) || !lseZ || !tmean || !rowdot || !sda ||
+      !llm_img(p, img, scal, true, g->mis != EA_MIS_BH)) return EA_E_BADARG;
+  p.q = mk(q); p.dout = mk(dout); p.dq = mk(dq);
+  p.lseZ = const_cast<float*>(lseZ); p.tmean = const_cast<float*>(tmean); p.rowdot = rowdot; p.sda = sda;
+  return lara_lm_dispatch(LLM_BWDQ, p, g->dtype, (hipStream_t)stream);
+}
+
+int ea_lara_lm_bwd_k(const ea_lara_geom* g, const ea_t4* k, const ea_t4* v, const uint8_t* mask, const void* img,
+                     const float* scal, const ea_t4* dk, const ea_t4* dv, int32_t plan, void* stream) {
+  LaraLmP p = {};
+  if (const int rc = fill_llm(g, p, LLM_BWDK, plan)) return rc;
+  if (!view_ok(k, 64, 2) || !view_ok(v, 64, 2) || !view_ok(dk, 64, 2) || !view_ok(dv, 64, 2) ||
+      !llm_img(p, img, scal, true, false)) return EA_E_BADARG;
+  p.k = mk(k); p.v = mk(v); p.dk = mk(dk); p.dv = mk(dv); p.mask = mask;
+  return lara_lm_dispatch(LLM_BWDK, p, g->dtype, (hipStream_t)stream);
+}
+
+int ea_lara_lm_bwd_qcorr(const ea_lara_geom* g, const ea_t4* q, const void* img, const float* scal, const ea_t4* dq,
+                         int32_t plan, void* stream) {
+  LaraLmP p = {};
+  if (const int rc = fill_llm(g, p, LLM_QCORR, plan)) return rc;
+  if (g->mis != EA_MIS_OPT || !view_ok(q, 64, 2) || !view_ok(dq, 64, 2) || !llm_img(p, img, scal, false, true)) return EA_E_BADARG;
+  p.q = mk(q); p.dq = mk(dq);
+  return lara_lm_dispatch(LLM_QCORR, p, g->dtype, (hipStream_t)stream);
 }
 
 }  // extern "C"
@@ -939,12 +1081,12 @@ int ea_lara_landmarks_bwd_cb(const ea_lmk_geom* g, const float* pq, const float*
 
 }  // extern "C"
 
-// ---- LARA partial merges ----
-extern "C" {
+// ---- LARA partial merges (ea_lara_merge_*: C <= 128; ea_lara_lm_merge_*: the same kernels up to 512 samples at D = 64) ----
 
-int ea_lara_merge_fwd(int32_t BH, int32_t S, int32_t C, int32_t D, int32_t has_t,
-                      const float* p_ml, const float* p_kv, const float* lp,
-                      float* kv, float* lse_k, float* lse_t, float* cst, void* stream) {
+static int lara_merge_fwd(int32_t BH, int32_t S, int32_t C, int32_t D, int32_t has_t,
+                          const float* p_ml, const float* p_kv, const float* lp,
+                          float* kv, float* lse_k, float* lse_t, float* cst, void* stream, int maxC) {
+  if (C > maxC) return EA_E_UNSUPPORTED;
   if (BH <= 0 || S <= 0 || C <= 0 || D <= 0 || !p_ml || !p_kv || !lp || !kv || !lse_k || !cst ||
       (has_t && !lse_t)) return EA_E_BADARG;
   MergeP p = {};
@@ -953,11 +1095,12 @@ int ea_lara_merge_fwd(int32_t BH, int32_t S, int32_t C, int32_t D, int32_t has_t
   return lara_merge_dispatch(false, p, (hipStream_t)stream);
 }
 
-int ea_lara_merge_bwd(int32_t BH, int32_t S, int32_t C, int32_t D, int32_t has_t, float scale,
-                      const float* p_ml, const float* p_dkv, const float* p_dom, const float* p_m1,
-                      const float* p_m2, const float* kv, const float* qbar,
-                      float* r, float* dbh, float* dlp, float* dkk, float* dkv, float* domq,
-                      float* dqbar, float* uq, void* stream) {
+static int lara_merge_bwd(int32_t BH, int32_t S, int32_t C, int32_t D, int32_t has_t, float scale,
+                          const float* p_ml, const float* p_dkv, const float* p_dom, const float* p_m1,
+                          const float* p_m2, const float* kv, const float* qbar,
+                          float* r, float* dbh, float* dlp, float* dkk, float* dkv, float* domq,
+                          float* dqbar, float* uq, void* stream, int maxC) {
+  if (C > maxC) return EA_E_UNSUPPORTED;
   if (BH <= 0 || S <= 0 || C <= 0 || D <= 0 || !p_ml || !p_dkv || !p_dom || !kv || !r || !dkk ||
       !dkv || !domq) return EA_E_BADARG;
   if (has_t && (!p_m1 || !p_m2 || !qbar || !dqbar || !uq)) return EA_E_BADARG;
@@ -967,6 +1110,37 @@ int ea_lara_merge_bwd(int32_t BH, int32_t S, int32_t C, int32_t D, int32_t has_t
   p.kv = const_cast<float*>(kv); p.qbar = qbar;
   p.r = r; p.dbh = dbh; p.dlp = dlp; p.dkk = dkk; p.dkv = dkv; p.domq = domq; p.dqbar = dqbar; p.uq = uq;
   return lara_merge_dispatch(true, p, (hipStream_t)stream);
+}
+
+extern "C" {
+
+int ea_lara_merge_fwd(int32_t BH, int32_t S, int32_t C, int32_t D, int32_t has_t,
+                      const float* p_ml, const float* p_kv, const float* lp,
+                      float* kv, float* lse_k, float* lse_t, float* cst, void* stream) {
+  return lara_merge_fwd(BH, S, C, D, has_t, p_ml, p_kv, lp, kv, lse_k, lse_t, cst, stream, 128);
+}
+int ea_lara_lm_merge_fwd(int32_t BH, int32_t S, int32_t C, int32_t D, int32_t has_t,
+                         const float* p_ml, const float* p_kv, const float* lp,
+                         float* kv, float* lse_k, float* lse_t, float* cst, void* stream) {
+  if (D != 64) return EA_E_UNSUPPORTED;
+  return lara_merge_fwd(BH, S, C, D, has_t, p_ml, p_kv, lp, kv, lse_k, lse_t, cst, stream, LLM_MAX_C);
+}
+int ea_lara_merge_bwd(int32_t BH, int32_t S, int32_t C, int32_t D, int32_t has_t, float scale,
+                      const float* p_ml, const float* p_dkv, const float* p_dom, const float* p_m1,
+                      const float* p_m2, const float* kv, const float* qbar,
+                      float* r, float* dbh, float* dlp, float* dkk, float* dkv, float* domq,
+                      float* dqbar, float* uq, void* stream) {
+  return lara_merge_bwd(BH, S, C, D, has_t, scale, p_ml, p_dkv, p_dom, p_m1, p_m2, kv, qbar, r, dbh, dlp, dkk, dkv, domq, dqbar, uq,
+                        stream, 128);
+}
+int ea_lara_lm_merge_bwd(int32_t BH, int32_t S, int32_t C, int32_t D, int32_t has_t, float scale,
+                         const float* p_ml, const float* p_dkv, const float* p_dom, const float* p_m1,
+                         const float* p_m2, const float* kv, const float* qbar,
+                         float* r, float* dbh, float* dlp, float* dkk, float* dkv, float* domq,
+                         float* dqbar, float* uq, void* stream) {
+  if (D != 64) return EA_E_UNSUPPORTED;
+  return lara_merge_bwd(BH, S, C, D, has_t, scale, p_ml, p_dkv, p_dom, p_m1, p_m2, kv, qbar, r, dbh, dlp, dkk, dkv, domq, dqbar, uq,
+                        stream, LLM_MAX_C);
 }
 
 }  // extern "C"

@@ -1,6 +1,6 @@
 // ea_lara_merge.hip -- merge the per-slice partial results of the LARA token-row passes
 // (ea_lara_y.hip) into the per-landmark tensors the token-column passes consume.  One workgroup
-// per (b,h); everything is [C, D] fp32 with C <= 128 -- tiny, but it replaces ~20 torch kernels
+// per (b,h) and 256 row quarters; everything is [C, D] fp32 with C <= 512 -- tiny, but it replaces ~20 torch kernels
 // (amax / exp / mul / sum / log / div ...) per direction.
 #include "ea_common.h"
 #include "ea_lara_merge.h"
@@ -193,7 +193,7 @@ __global__ __launch_bounds__(256) void lara_merge_bwd_kernel(const MergeP p) {
 }
 
 int lara_merge_dispatch(bool bwd, const MergeP& p, hipStream_t st) {
-  if (p.C > 128) return EA_E_UNSUPPORTED;
+  if (p.C > 512) return EA_E_UNSUPPORTED;      // (the landmark rows are on grid.y: nothing in the kernels depends on C)
   const dim3 grid((unsigned)p.BH, (unsigned)((p.C * p.D / 4 + 255) / 256));
   const dim3 grid_b((unsigned)p.BH, (unsigned)((p.C * p.D / 4 + 63) / 64));       // 64 columns x 4 slice lanes per block
   if (bwd && p.S > 4) hipLaunchKernelGGL(lara_merge_bwd_kernel<4>, grid_b, dim3(256), 0, st, p);

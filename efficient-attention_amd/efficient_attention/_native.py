@@ -175,6 +175,18 @@ SIGNATURES = {
     "ea_lara_bwd_k": [_LG, _T, _T, _P, _P, _P, _P, _P, _P, _T, _T, _P],
     "ea_lara_bwd_kstats": [_LG, _T, _T] + [_P] * 8,
     "ea_lara_bwd_qcorr": [_LG, _T, _P, _P, _P, _T, _P],
+    "ea_lara_lm_parts": [_LG],
+    "ea_lara_lm_stats_fwd": [_LG, _T, _T, _T, _P, _P, _P, _P, _P, _P],
+    "ea_lara_lm_bwd_qstats": [_LG, _T, _T] + [_P] * 16,
+    "ea_lara_lm_bwd_kstats": [_LG, _T, _T] + [_P] * 8,
+    "ea_lara_lm_merge_fwd": [_I] * 5 + [_P] * 8,
+    "ea_lara_lm_merge_bwd": [_I] * 5 + [_F] + [_P] * 16,
+    "ea_lara_lm_plan": [_LG, _I, _I],
+    "ea_lara_lm_prepare": [_LG, _I] + [_P] * 9,
+    "ea_lara_lm_out_fwd": [_LG, _T, _P, _P, _T, _P, _P, _I, _P],
+    "ea_lara_lm_bwd_q": [_LG, _T, _T, _P, _P, _P, _P, _T, _P, _P, _I, _P],
+    "ea_lara_lm_bwd_k": [_LG, _T, _T, _P, _P, _P, _T, _T, _I, _P],
+    "ea_lara_lm_bwd_qcorr": [_LG, _T, _P, _P, _T, _I, _P],
     "ea_lara_fused_parts": [_LG],
     "ea_lara_bwd_q_fused": [_LG, _T, _T, _P, _P, _P, _P, _P, _P, _P, _P, _T, _P, _P, _P, _P, _P, _P],
     "ea_lara_bwd_k_fused": [_LG, _T, _T, _P, _P, _P, _P, _P, _P, _T, _T, _P, _P],

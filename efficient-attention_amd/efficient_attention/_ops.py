@@ -1343,6 +1343,33 @@ class AdaptivePoolFn(torch.autograd.Function):
         return (buf if own else None), None, None, None, None, None
 
 
+# LARA past 128 samples on the 16-bit kernels (csrc/ea_lara_lm.hip: the token-column passes as a loop over 64-sample groups; the
+# token-row passes and the merges take the larger C as they are); EA_LARA_LONG=0: LinearRA keeps the fp32 gathered-attention route
+USE_LARA_LONG = os.environ.get("EA_LARA_LONG", "1") == "1"
+LARA_LONG_MAX = 512
+# plan of the ea_lara_lm_* passes: 0 the planner's, 1 resident images, 2 streamed 64-row groups (tests force the streamed one
+# at a sample count the planner keeps resident)
+LARA_LONG_PLAN = 0
+
+
+def lara_long_supported(C, d, dtype):
+    """The envelope of the 16-bit estimator passes past 128 samples (what ea_lara_lm_* accept; decided before any launch)."""
+    return USE_LARA_LONG and d == 64 and 128 < C <= LARA_LONG_MAX and dtype in (torch.bfloat16, torch.float16)
+
+
+def _lara_lm_prepare(geom, kind, mats, cols, dtype, img=None):
+    """ea_lara_lm_prepare: the 16-bit images [3, BH, Cp, 64] of up to three fp32 landmark matrices (None: that plane stays as it
+    is) and the padded scalar columns [BH, 3, Cp] of one pass -> (img, scal)."""
+    BH, Cp = geom.B * geom.H, (geom.C + 63) // 64 * 64
+    dev = next(t for t in mats if t is not None).device
+    if img is None:
+        img = torch.empty((3, BH, Cp, 64), dtype=dtype, device=dev)
+    scal = torch.empty((BH, 3, Cp), dtype=torch.float32, device=dev)
+    nv.call("ea_lara_lm_prepare", ctypes.byref(geom), kind, nv.ptr(mats[0]), nv.ptr(mats[1]), nv.ptr(mats[2]), nv.ptr(cols[0]),
+            nv.ptr(cols[1]), nv.ptr(cols[2]), nv.ptr(img), nv.ptr(scal), nv.stream())
+    return img, scal
+
+
 def lara_fold(C, S):
     """Round 5: the merge launches between the LARA token passes are folded into their consumers (C <= 64 samples, S <= 4
     slices): ea_lara_out_fwd_merge, ea_lara_bwd_k_fused_merge, ea_lara_landmarks_bwd_parts.  EA_LARA_FOLD=0 keeps the merge
@@ -1369,10 +1396,13 @@ def _lara_fwd_core(geom, qkv5, mask_u8, omega, qbar_c, bhv_c, lp_c, want_tokst=T
     C, BH, dev, mis = geom.C, B * h, qkv5.device, geom.mis
     q, k, v = _qkv_views(qkv5)
     tq, tk, tv = nv.t4(q), nv.t4(k), nv.t4(v)
-    S = nv.lib().ea_lara_parts(ctypes.byref(geom))
+    lm = "_lm" if C > 128 else ""           # past 128 samples: the ea_lara_lm_* entries (same token-row kernels and merges)
+    S = getattr(nv.lib(), "ea_lara%s_parts" % lm)(ctypes.byref(geom))
+    if S <= 0:
+        raise RuntimeError("ea_lara%s_parts: %d (C = %d, d = %d)" % (lm, S, C, d))
     p_ml = torch.empty((BH, S, C, 4), dtype=torch.float32, device=dev)
     p_kv = torch.empty((BH, S, C, d), dtype=torch.float32, device=dev)
-    nv.call("ea_lara_stats_fwd", ctypes.byref(geom), ctypes.byref(tq), ctypes.byref(tk),
+    nv.call("ea_lara%s_stats_fwd" % lm, ctypes.byref(geom), ctypes.byref(tq), ctypes.byref(tk),
             ctypes.byref(tv), nv.ptr(mask_u8), nv.ptr(omega), nv.ptr(qbar_c), nv.ptr(p_ml),
             nv.ptr(p_kv), nv.stream())
     kv = torch.empty((BH, C, d), dtype=torch.float32, device=dev)
@@ -1382,7 +1412,7 @@ def _lara_fwd_core(geom, qkv5, mask_u8, omega, qbar_c, bhv_c, lp_c, want_tokst=T
     out = torch.empty((B, N, h, d), dtype=qkv5.dtype, device=dev)
     to = nv.t4(out.permute(0, 2, 1, 3))
     # per-token softmax statistics (lse_Z in log2 units, mean_c t) for the fused backward: 8 bytes per token-head
-    tokst = torch.empty((2, BH, N), dtype=torch.float32, device=dev) if (want_tokst and C <= 64) else None
+    tokst = torch.empty((2, BH, N), dtype=torch.float32, device=dev) if (want_tokst and (C <= 64 or C > 128)) else None
     if proj is not None and lara_fold(C, S):
         label = "ea_lara_out_proj_fwd"
         if nv.KERNEL_TIMER.enabled:
@@ -1401,8 +1431,16 @@ def _lara_fwd_core(geom, qkv5, mask_u8, omega, qbar_c, bhv_c, lp_c, want_tokst=T
             _lara_proj_fallback(out, proj)
         return out, (cst, kv, lse_k, lse_t, tokst)
     # merge the sequence slices: log-sum-exp merge of the online-softmax partials (one tiny kernel)
-    nv.call("ea_lara_merge_fwd", BH, S, C, d, 1 if mis == 0 else 0, nv.ptr(p_ml), nv.ptr(p_kv),
+    nv.call("ea_lara%s_merge_fwd" % lm, BH, S, C, d, 1 if mis == 0 else 0, nv.ptr(p_ml), nv.ptr(p_kv),
             nv.ptr(lp_c), nv.ptr(kv), nv.ptr(lse_k), nv.ptr(lse_t), nv.ptr(cst), nv.stream())
+    if C > 128:
+        # past 128 samples: the combine pass loops over 64-sample groups of the prepared 16-bit images (ea_lara_lm.hip)
+        img, scal = _lara_lm_prepare(geom, 0, (omega, qbar_c, kv), (cst, lse_t, bhv_c), qkv5.dtype)
+        nv.call("ea_lara_lm_out_fwd", ctypes.byref(geom), ctypes.byref(tq), nv.ptr(img), nv.ptr(scal), ctypes.byref(to),
+                nv.ptr(tokst), None if tokst is None else nv.ptr(tokst[1]), LARA_LONG_PLAN, nv.stream())
+        if proj is not None:
+            _lara_proj_fallback(out, proj)
+        return out, (cst, kv, lse_k, lse_t, tokst)
     nv.call("ea_lara_out_fwd", ctypes.byref(geom), ctypes.byref(tq), nv.ptr(omega), nv.ptr(qbar_c),
             nv.ptr(kv), nv.ptr(lse_t), nv.ptr(bhv_c), nv.ptr(cst), ctypes.byref(to),
             nv.ptr(tokst), None if tokst is None else nv.ptr(tokst[1]), nv.stream())
@@ -1416,7 +1454,7 @@ def _lara_bwd_core(geom, qkv5, mask_u8, dout, dqkv5, omega, qbar, bhv, cst, kv, 
     Writes dq (uncorrected), dk, dv into dqkv5; returns d_omega [BH,C,d], d_qbar, d_bhv, d_lp and uq
     (the u_c q_bar_c rows of the correction, mis-opt only).
     C <= 64: one fused pass per side (ea_lara_bwd_q_fused / ea_lara_bwd_k_fused); larger sample counts
-    take the round-1 two-pass kernels."""
+    take the round-1 two-pass kernels, past 128 samples with the token-column passes of ea_lara_lm.hip."""
     B, N, _, h, d = qkv5.shape
     C, BH, dev, mis = geom.C, B * h, qkv5.device, geom.mis
     scale = geom.scale
@@ -1425,12 +1463,15 @@ def _lara_bwd_core(geom, qkv5, mask_u8, dout, dqkv5, omega, qbar, bhv, cst, kv, 
     tq, tk, tv, tdo = nv.t4(q), nv.t4(k), nv.t4(v), nv.t4(dout.permute(0, 2, 1, 3))
     tdq, tdk, tdv = nv.t4(dq), nv.t4(dk), nv.t4(dv)
     fused = C <= 64
+    lm = "_lm" if C > 128 else ""
     if fused:
         S = nv.lib().ea_lara_fused_parts(ctypes.byref(geom))
         if S <= 0:
             raise RuntimeError("ea_lara_fused_parts: %d" % S)
     else:
-        S = nv.lib().ea_lara_parts(ctypes.byref(geom))
+        S = getattr(nv.lib(), "ea_lara%s_parts" % lm)(ctypes.byref(geom))
+        if S <= 0:
+            raise RuntimeError("ea_lara%s_parts: %d (C = %d, d = %d)" % (lm, S, C, d))
     p_ml = torch.empty((BH, S, C, 4), dtype=torch.float32, device=dev)
     p_acc = torch.empty((4, BH, S, C, d), dtype=torch.float32, device=dev)
     if fused:
@@ -1441,12 +1482,21 @@ def _lara_bwd_core(geom, qkv5, mask_u8, dout, dqkv5, omega, qbar, bhv, cst, kv, 
                 ctypes.byref(tdq),
                 nv.ptr(p_ml), nv.ptr(p_acc[0]), nv.ptr(p_acc[1]), nv.ptr(p_acc[2]), nv.ptr(p_acc[3]), nv.stream())
     else:
+        long = C > 128
         tok = torch.empty((4, BH, N), dtype=torch.float32, device=dev)
         lseZ, tmean, rowdot, sda = tok[0], tok[1], tok[2], tok[3]
-        nv.call("ea_lara_bwd_q", ctypes.byref(geom), ctypes.byref(tq), ctypes.byref(tdo), nv.ptr(omega),
-                nv.ptr(qbar), nv.ptr(kv), nv.ptr(lse_t), nv.ptr(bhv), nv.ptr(cst), ctypes.byref(tdq),
-                nv.ptr(lseZ), nv.ptr(tmean), nv.ptr(rowdot), nv.ptr(sda), nv.stream())
-        nv.call("ea_lara_bwd_qstats", ctypes.byref(geom), ctypes.byref(tq), ctypes.byref(tdo),
+        if long:
+            if tokst is None:
+                raise RuntimeError("ea_lara_lm_bwd_q needs the forward's per-token statistics (lse_Z, mean t)")
+            lseZ, tmean = tokst[0], tokst[1]
+            img, scal = _lara_lm_prepare(geom, 0, (omega, qbar, kv), (cst, lse_t, bhv), qkv5.dtype)
+            nv.call("ea_lara_lm_bwd_q", ctypes.byref(geom), ctypes.byref(tq), ctypes.byref(tdo), nv.ptr(img), nv.ptr(scal),
+                    nv.ptr(lseZ), nv.ptr(tmean), ctypes.byref(tdq), nv.ptr(rowdot), nv.ptr(sda), LARA_LONG_PLAN, nv.stream())
+        else:
+            nv.call("ea_lara_bwd_q", ctypes.byref(geom), ctypes.byref(tq), ctypes.byref(tdo), nv.ptr(omega),
+                    nv.ptr(qbar), nv.ptr(kv), nv.ptr(lse_t), nv.ptr(bhv), nv.ptr(cst), ctypes.byref(tdq),
+                    nv.ptr(lseZ), nv.ptr(tmean), nv.ptr(rowdot), nv.ptr(sda), nv.stream())
+        nv.call("ea_lara%s_bwd_qstats" % lm, ctypes.byref(geom), ctypes.byref(tq), ctypes.byref(tdo),
                 nv.ptr(omega), nv.ptr(qbar), nv.ptr(kv), nv.ptr(lse_t), nv.ptr(bhv), nv.ptr(cst),
                 nv.ptr(lseZ), nv.ptr(tmean), nv.ptr(rowdot), nv.ptr(sda), nv.ptr(p_ml),
                 nv.ptr(p_acc[0]), nv.ptr(p_acc[1]), nv.ptr(p_acc[2]), nv.ptr(p_acc[3]), nv.stream())
@@ -1473,7 +1523,7 @@ def _lara_bwd_core(geom, qkv5, mask_u8, dout, dqkv5, omega, qbar, bhv, cst, kv, 
         d_omega = torch.empty((BH, C, d), dtype=torch.float32, device=dev)
         nv.call("ea_slice_sum", BH, S, C * d, float(scale), nv.ptr(dom_q), nv.ptr(p_domk), nv.ptr(d_omega), nv.stream())
         return d_omega, d_qbar, d_bhv, dlp_m, (uq if mis == 0 else None)
-    nv.call("ea_lara_merge_bwd", BH, S, C, d, 1 if mis == 0 else 0, float(scale), nv.ptr(p_ml),
+    nv.call("ea_lara%s_merge_bwd" % lm, BH, S, C, d, 1 if mis == 0 else 0, float(scale), nv.ptr(p_ml),
             nv.ptr(p_acc[0]), nv.ptr(p_acc[1]), nv.ptr(p_acc[2]), nv.ptr(p_acc[3]), nv.ptr(kv), nv.ptr(qbar),
             nv.ptr(r), nv.ptr(dbh), nv.ptr(dlp_m), nv.ptr(dkk), nv.ptr(dkv), nv.ptr(dom_q),
             nv.ptr(dqbar_m) if want_dqbar else None, nv.ptr(uq) if mis == 0 else None, nv.stream())
@@ -1483,10 +1533,16 @@ def _lara_bwd_core(geom, qkv5, mask_u8, dout, dqkv5, omega, qbar, bhv, cst, kv, 
                 nv.ptr(omega), nv.ptr(dkv), nv.ptr(lse_k), nv.ptr(dkk), nv.ptr(r), ctypes.byref(tdk),
                 ctypes.byref(tdv), nv.ptr(p_domk), nv.stream())
     else:
-        nv.call("ea_lara_bwd_k", ctypes.byref(geom), ctypes.byref(tk), ctypes.byref(tv), nv.ptr(mask_u8),
-                nv.ptr(omega), nv.ptr(dkv), nv.ptr(lse_k), nv.ptr(dkk), nv.ptr(r), ctypes.byref(tdk),
-                ctypes.byref(tdv), nv.stream())
-        nv.call("ea_lara_bwd_kstats", ctypes.byref(geom), ctypes.byref(tk), ctypes.byref(tv),
+        if long:
+            # the omega plane of the query side's images stays; the third plane becomes d kv
+            _, scal_k = _lara_lm_prepare(geom, 1, (None, None, dkv), (lse_k, dkk, r), qkv5.dtype, img=img)
+            nv.call("ea_lara_lm_bwd_k", ctypes.byref(geom), ctypes.byref(tk), ctypes.byref(tv), nv.ptr(mask_u8), nv.ptr(img),
+                    nv.ptr(scal_k), ctypes.byref(tdk), ctypes.byref(tdv), LARA_LONG_PLAN, nv.stream())
+        else:
+            nv.call("ea_lara_bwd_k", ctypes.byref(geom), ctypes.byref(tk), ctypes.byref(tv), nv.ptr(mask_u8),
+                    nv.ptr(omega), nv.ptr(dkv), nv.ptr(lse_k), nv.ptr(dkk), nv.ptr(r), ctypes.byref(tdk),
+                    ctypes.byref(tdv), nv.stream())
+        nv.call("ea_lara%s_bwd_kstats" % lm, ctypes.byref(geom), ctypes.byref(tk), ctypes.byref(tv),
                 nv.ptr(mask_u8), nv.ptr(omega), nv.ptr(dkv), nv.ptr(lse_k), nv.ptr(dkk), nv.ptr(r),
                 nv.ptr(p_domk), nv.stream())
     d_omega = torch.empty((BH, C, d), dtype=torch.float32, device=dev)
@@ -1509,7 +1565,11 @@ def _lara_finish(geom, qkv5, dqkv5, qbar, uq, lse_t, dpq=None, dpk=None, pool=No
         nv.call("ea_lara_bwd_finish", ctypes.byref(geom), ctypes.byref(tq), nv.ptr(qbar), nv.ptr(uq), nv.ptr(lse_t),
                 nv.ptr(dpq), nv.ptr(dpk), int(r), int(H), int(W), ctypes.byref(tdq), ctypes.byref(tdk), nv.stream())
         return
-    if uq is not None:
+    if uq is not None and geom.C > 128:
+        img, scal = _lara_lm_prepare(geom, 0, (None, qbar, uq), (None, lse_t, None), qkv5.dtype)
+        nv.call("ea_lara_lm_bwd_qcorr", ctypes.byref(geom), ctypes.byref(tq), nv.ptr(img), nv.ptr(scal), ctypes.byref(tdq),
+                LARA_LONG_PLAN, nv.stream())
+    elif uq is not None:
         nv.call("ea_lara_bwd_qcorr", ctypes.byref(geom), ctypes.byref(tq), nv.ptr(qbar), nv.ptr(uq),
                 nv.ptr(lse_t), ctypes.byref(tdq), nv.stream())
     if pool is not None:
@@ -2624,26 +2684,28 @@ def lara_attention(qkv5, mask_u8, q_bar, mu, noise, mis_type, alpha_coeff, mode,
     if mu.is_cuda and _sample_fits(L, L * (2 if dup else 1), d):
         omega, qbar_rows, bhv, lp = LaraSampleFn.apply(q_bar, mu, noise, mis, mode, float(scale))
         return LaraAttnFn.apply(qkv5, mask_u8, omega, qbar_rows, bhv, lp, mis, float(alpha_coeff), slot)
-    if noise is None:
-        omega = mu
-    elif mode == 2:
-        omega = mu.repeat(1, 1, 2, 1) + noise.float()
-    elif mode == 1:
-        omega = torch.cat([mu + noise.float(), mu - noise.float()], dim=-2)
-    else:
-        omega = mu + noise.float()
-    rep = (lambda t: t.repeat(1, 1, 2, 1)) if dup else (lambda t: t)
-    qbar_rows = bhv = None
-    if mis == 0:
-        lpmu = _prm(rep(mu), omega, scale)                               # [B,h,C,C]
-        lp = torch.diagonal(lpmu, dim1=-1, dim2=-2)
-        bhv = torch.exp(lp - torch.logsumexp(lpmu, dim=-1))
-        qbar_rows = rep(q_bar)
-    elif mis == 1:
-        lp = torch.logsumexp(_prm(mu, omega, scale), dim=-1)            # [B,h,C]
-        qbar_rows = rep(mu)
-    else:
-        lp = torch.logsumexp(_prm(mu, omega, scale), dim=-1)
+    # (outside autocast: these are fp32 tensors, and under autocast the einsum of _prm would round the density logits to 16 bits)
+    with torch.autocast(device_type=mu.device.type, enabled=False):
+        if noise is None:
+            omega = mu
+        elif mode == 2:
+            omega = mu.repeat(1, 1, 2, 1) + noise.float()
+        elif mode == 1:
+            omega = torch.cat([mu + noise.float(), mu - noise.float()], dim=-2)
+        else:
+            omega = mu + noise.float()
+        rep = (lambda t: t.repeat(1, 1, 2, 1)) if dup else (lambda t: t)
+        qbar_rows = bhv = None
+        if mis == 0:
+            lpmu = _prm(rep(mu), omega, scale)                               # [B,h,C,C]
+            lp = torch.diagonal(lpmu, dim1=-1, dim2=-2)
+            bhv = torch.exp(lp - torch.logsumexp(lpmu, dim=-1))
+            qbar_rows = rep(q_bar)
+        elif mis == 1:
+            lp = torch.logsumexp(_prm(mu, omega, scale), dim=-1)            # [B,h,C]
+            qbar_rows = rep(mu)
+        else:
+            lp = torch.logsumexp(_prm(mu, omega, scale), dim=-1)
     return LaraAttnFn.apply(qkv5, mask_u8, omega, qbar_rows, bhv, lp, mis, float(alpha_coeff), slot)
 
 

@@ -7,6 +7,7 @@ argparse flags.  The O(N L d) estimator -- random-feature projections of q and k
 per-landmark softmax statistics over the sequence, the importance weights and the final
 combine -- runs in libea_hip.so (_ops.LaraAttnFn).
 """
+import contextlib
 import math
 
 import torch
@@ -53,10 +54,12 @@ class LinearRA(_ops.DerivedCacheOwner, MultiheadAttention):
         self.apply(self._init_weights)
 
     # ---- landmark proposals (tiny [B,h,L,d] tensors; pooling reads q,k once) -------------
-    def _proposal_gen_2d(self, qkv5, H, W, slot=None, mix=True, pooled=None):
+    def _proposal_gen_2d(self, qkv5, H, W, slot=None, mix=True, pooled=None, gen_f32=False):
         """Adaptive 2-D average pool of q,k -> [Linear+LN] -> optional softmax mixing of k_bar
         (reference :129-175).  Returns q_bar, k_bar [B,h,L,d] fp32 and the '-vmixed' column bias of the
-        mixing logits (or None); with mix=False the mixing itself is left to the landmark kernel."""
+        mixing logits (or None); with mix=False the mixing itself is left to the landmark kernel.
+        gen_f32: the 'light' generators' Linear + LayerNorm on the fp32 pooled rows and the softmax mixing run outside
+        autocast (fp32, as on the fp32 route), not as 16-bit GEMMs of [B h L, d] rows."""
         B, N, _, h, d = qkv5.shape
         side = int(math.sqrt(self.num_landmarks))
         gen = self.proposal_gen
@@ -72,17 +75,19 @@ class LinearRA(_ops.DerivedCacheOwner, MultiheadAttention):
                     return z.reshape(B, side * side, h, d).permute(0, 2, 1, 3)
                 q_bar, k_bar = dense(pq, self.q_bar_gen), dense(pk, self.k_bar_gen)
             else:
-                q_bar = self.q_bar_gen[3](self.q_bar_gen[2](pq))
-                k_bar = self.k_bar_gen[3](self.k_bar_gen[2](pk))
+                with (torch.autocast(device_type="cuda", enabled=False) if gen_f32 else contextlib.nullcontext()):
+                    q_bar = self.q_bar_gen[3](self.q_bar_gen[2](pq))
+                    k_bar = self.k_bar_gen[3](self.k_bar_gen[2](pk))
         else:
             q_bar, k_bar = pq, pk
         q_bar, k_bar = q_bar.float(), k_bar.float()
         colbias = torch.log(pv.float().norm(dim=-1) + 1e-4) if gen.endswith('-vmixed') else None      # [B,h,L]
         if gen.endswith('mixed') and mix:
-            logits = self.scale * torch.einsum('bhpd,bhcd->bhpc', k_bar, k_bar)
-            if colbias is not None:
-                logits = logits + colbias.unsqueeze(-2)
-            k_bar = torch.einsum('bhpc,bhcd->bhpd', torch.softmax(logits, dim=-1), k_bar)
+            with (torch.autocast(device_type="cuda", enabled=False) if gen_f32 else contextlib.nullcontext()):
+                logits = self.scale * torch.einsum('bhpd,bhcd->bhpc', k_bar, k_bar)
+                if colbias is not None:
+                    logits = logits + colbias.unsqueeze(-2)
+                k_bar = torch.einsum('bhpc,bhcd->bhpd', torch.softmax(logits, dim=-1), k_bar)
         return q_bar, k_bar, colbias
 
     def _proposal_gen_1d(self, qkv5, key_padding_mask):
@@ -268,14 +273,18 @@ class LinearRA(_ops.DerivedCacheOwner, MultiheadAttention):
         side = int(math.sqrt(L))
         n_lm = side * side if len(seq_shape) == 2 else min(L, N)
         over128 = n_lm * (2 if dup else 1) > 128
-        if over128 and not (_f32.ENABLED and x.is_cuda and d in (32, 64, 128)):
+        # 129 .. 512 samples at d = 64 on 16-bit activations: the 16-bit estimator passes of csrc/ea_lara_lm.hip through the
+        # non-fused path below (EA_LARA_LONG=0: the fp32 route)
+        io = torch.get_autocast_dtype("cuda") if torch.is_autocast_enabled() else x.dtype
+        long_ok = over128 and x.is_cuda and _ops.lara_long_supported(n_lm * (2 if dup else 1), d, io)
+        if over128 and not long_ok and not (_f32.ENABLED and x.is_cuda and d in (32, 64, 128)):
             raise NotImplementedError(
                 "LinearRA: %d samples exceed the 128 the 16-bit estimator kernels hold and the generic fp32 kernels are "
                 "%s" % (n_lm * (2 if dup else 1), "switched off (EA_F32_CORES=0)" if not _f32.ENABLED else
                         "not available for head_dim %d / this device" % d))
         qkv5 = None
         if over128:
-            fold_1d = module_fn = False
+            fold_1d = module_fn = seglin = False
         # 'adaptive-1d' on the segment kernels as ONE autograd node as well (round 6, _ops.GraphCore inside CoreModuleFn): the
         # projections of the three-node path ran two weight-gradient launches and two partial sums of their own
         fits_fused = n_lm * (2 if dup else 1) <= 64
@@ -295,7 +304,7 @@ class LinearRA(_ops.DerivedCacheOwner, MultiheadAttention):
         mask = _ops._mask_u8(key_padding_mask, B, N, x.device)
 
         # ---- landmark proposals.  Fused HIP pipeline whenever the sample count fits (C <= 64) ----
-        if over128:
+        if over128 and not (long_ok and _ops.lara_long_supported(n_lm * (2 if dup else 1), d, qkv5.dtype)):
             # the generic fp32 kernels on the 16-bit activations (exact in fp32) -- the reference takes any --num-landmarks
             # (lara.py:188-196)
             return self._forward_f32(x, key_padding_mask, qkv5=qkv5)
@@ -324,7 +333,9 @@ class LinearRA(_ops.DerivedCacheOwner, MultiheadAttention):
         mixed_k = colbias = None
         if len(seq_shape) == 2:
             # the softmax mixing of k_bar runs inside the landmark kernel whenever that kernel is used
-            pq, pk, colbias = self._proposal_gen_2d(qkv5, seq_shape[0], seq_shape[1], slot, mix=not fused_b)
+            # (past 128 samples the generators stay in fp32: their weight gradients are sums over B h L rows of pooled means,
+            # which a 16-bit GEMM of those rows left 2e-2 in rms from the fp32 route's)
+            pq, pk, colbias = self._proposal_gen_2d(qkv5, seq_shape[0], seq_shape[1], slot, mix=not fused_b, gen_f32=over128)
             mixed_k = fused_b and gen.endswith('mixed')
         elif seglin:
             if key_padding_mask is not None:           # padded tokens: q = k = v = 0 for the generator AND the estimator (:93-96)

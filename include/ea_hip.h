@@ -238,7 +238,7 @@ int ea_window_attn_bwd(const ea_geom* g, const ea_t4* q, const ea_t4* k, const e
 typedef struct {
   int32_t B, H, N, D;
   int32_t dtype;             /* EA_BF16 | EA_F16 */
-  int32_t C;                 /* landmark samples, <= 128 */
+  int32_t C;                 /* landmark samples, <= 128 (<= 512 at D = 64 with the ea_lara_lm_* entries) */
   int32_t mis;               /* EA_MIS_* */
   float   kappa;             /* alpha_coeff (lara.py:231) */
   float   scale;             /* D^-0.5 */
@@ -270,6 +270,58 @@ int ea_lara_bwd_kstats(const ea_lara_geom* g, const ea_t4* k, const ea_t4* v, co
                        const float* rsum, float* p_dom, void* stream);
 int ea_lara_bwd_qcorr(const ea_lara_geom* g, const ea_t4* q, const float* qbar, const float* uq,
                       const float* lse_t, const ea_t4* dq, void* stream);
+
+/* 128 < C <= 512 samples, D = 64 (ea_lara_lm.hip; the ABI number is unchanged: no existing signature moved).
+ * Every ea_lara_* entry above keeps C <= 128; the larger counts have entries of their own.  The token-ROW kernels and the
+ * merges carry any C (their 16-sample tiles / landmark rows are on the grid): ea_lara_lm_parts, _stats_fwd, _bwd_qstats,
+ * _bwd_kstats and ea_lara_lm_merge_fwd / _bwd are ea_lara_parts .. ea_lara_merge_bwd with the same arguments and C <= 512.
+ * The token-COLUMN work (out_fwd, bwd_q, bwd_k, bwd_qcorr) is new kernels that loop over 64-sample groups of prepared 16-bit
+ * images.  EA_E_UNSUPPORTED for D != 64 or C > 512 (token-column entries: also C < 129), before anything is launched.
+ *   ea_lara_lm_prepare: img = 16-bit images [3, B*H, Cp, 64] (Cp = 64 ceil(C / 64), zero rows past C) of the fp32 m0, m1, m2
+ *     [B*H, C, 64] (a NULL matrix leaves its plane untouched) and scal fp32 [B*H, 3, Cp] = the columns s0, s1, s2 [B*H, C]
+ *     scaled and padded for the passes: kind 0 (cst log2e | -inf, lse_t log2e | +inf, bhv | 1) for out_fwd / bwd_q / bwd_qcorr,
+ *     kind 1 (lse_k log2e | +inf, dkk | 0, r | 0) for bwd_k; a NULL column holds its pad value everywhere.  A pad slot gets
+ *     weight exactly 0 in every pass and mean_c t divides by C.
+ *   ea_lara_lm_out_fwd: planes (omega, qbar, kv); out and, when given, lseZ (log2 units) / tmean [B*H, N].
+ *   ea_lara_lm_bwd_q: planes (omega, qbar, kv); reads the forward's lseZ / tmean; writes dq (before the correction) and
+ *     rowdot = dout . out, sda = sum_c d alpha [B*H, N] for ea_lara_bwd_qstats.
+ *   ea_lara_lm_bwd_k: planes (omega, -, d kv); dk, dv (exactly 0 on padded keys).
+ *   ea_lara_lm_bwd_qcorr: planes (-, qbar, u qbar), kind-0 columns (lse_t); dq -= s sum_c t (u qbar)_c, mis-opt only.
+ *   plan: 0 = the planner's, 1 = resident (the pass's images staged once per workgroup; EA_E_UNSUPPORTED where they do not fit
+ *     144 KB of LDS), 2 = streamed (64-row groups through two LDS slots).  ea_lara_lm_plan(g, pass, plan) -> 1 | 2: the plan
+ *     pass 0 out_fwd, 1 bwd_q, 2 bwd_k, 3 bwd_qcorr would take. */
+int32_t ea_lara_lm_parts(const ea_lara_geom* g);
+int ea_lara_lm_stats_fwd(const ea_lara_geom* g, const ea_t4* q, const ea_t4* k, const ea_t4* v,
+                         const uint8_t* mask, const float* omega, const float* qbar,
+                         float* p_ml, float* p_kv, void* stream);
+int ea_lara_lm_bwd_qstats(const ea_lara_geom* g, const ea_t4* q, const ea_t4* dout, const float* omega,
+                          const float* qbar, const float* kv, const float* lse_t, const float* bhv,
+                          const float* cst, const float* lseZ, const float* tmean, const float* rowdot,
+                          const float* sda, float* p_ml, float* p_dkv, float* p_dom, float* p_m1,
+                          float* p_m2, void* stream);
+int ea_lara_lm_bwd_kstats(const ea_lara_geom* g, const ea_t4* k, const ea_t4* v, const uint8_t* mask,
+                          const float* omega, const float* dkv, const float* lse_k, const float* dkk,
+                          const float* rsum, float* p_dom, void* stream);
+int ea_lara_lm_merge_fwd(int32_t BH, int32_t S, int32_t C, int32_t D, int32_t has_t,
+                         const float* p_ml, const float* p_kv, const float* lp,
+                         float* kv, float* lse_k, float* lse_t, float* cst, void* stream);
+int ea_lara_lm_merge_bwd(int32_t BH, int32_t S, int32_t C, int32_t D, int32_t has_t, float scale,
+                         const float* p_ml, const float* p_dkv, const float* p_dom, const float* p_m1,
+                         const float* p_m2, const float* kv, const float* qbar,
+                         float* r, float* dbh, float* dlp, float* dkk, float* dkv, float* domq,
+                         float* dqbar, float* uq, void* stream);
+int32_t ea_lara_lm_plan(const ea_lara_geom* g, int32_t pass, int32_t plan);
+int ea_lara_lm_prepare(const ea_lara_geom* g, int32_t kind, const float* m0, const float* m1, const float* m2, const float* s0,
+                       const float* s1, const float* s2, void* img, float* scal, void* stream);
+int ea_lara_lm_out_fwd(const ea_lara_geom* g, const ea_t4* q, const void* img, const float* scal, const ea_t4* out, float* lseZ,
+                       float* tmean, int32_t plan, void* stream);
+int ea_lara_lm_bwd_q(const ea_lara_geom* g, const ea_t4* q, const ea_t4* dout, const void* img, const float* scal,
+                     const float* lseZ, const float* tmean, const ea_t4* dq, float* rowdot, float* sda, int32_t plan,
+                     void* stream);
+int ea_lara_lm_bwd_k(const ea_lara_geom* g, const ea_t4* k, const ea_t4* v, const uint8_t* mask, const void* img,
+                     const float* scal, const ea_t4* dk, const ea_t4* dv, int32_t plan, void* stream);
+int ea_lara_lm_bwd_qcorr(const ea_lara_geom* g, const ea_t4* q, const void* img, const float* scal, const ea_t4* dq,
+                         int32_t plan, void* stream);
 
 /* Fused backward (round 2): the elementwise stage of the estimator is evaluated once per side and its
  * [C x N] weight matrices are transposed through LDS, so q/dout and k/v are each read ONCE
