@@ -2444,6 +2444,7 @@ int ea_layernorm_bwd(int32_t xtype, int32_t rows, int32_t C, const void* x, cons
 
 // ---- causal EVA, incremental decoding (ea_ceva_decode.hip) ----
 #include "ea_ceva_decode.h"
+#include "ea_ceva_decode_mm.h"
 #include "ea_ceva_decode_linear.h"
 #include "ea_ceva_decode_vocab.h"
 #include "ea_vocab_score.h"
@@ -2539,6 +2540,16 @@ static int dec_attn(const DecG& g, const ea_t4* q, const ea_t4* k, const ea_t4* 
   const int rc = dec_fill_attn(g, q, k, v, pad, bias, lk, lv, out, p);
   return rc != EA_OK ? rc : ea::ceva_decode_launch(ea::DEC_ATTN, p, (hipStream_t)stream, g.l16);
 }
+// attn on the matrix cores (ea_ceva_decode_mm.hip).  What it has no instance for is decided first, for both entries alike:
+// fp32 rows, a head dim outside {64, 128}, a window that is no multiple of 16; every other refusal is attn's.
+static int dec_attn_mm(const ea_ceva_sdec_geom* g, bool l16, const ea_t4* q, const ea_t4* k, const ea_t4* v, const uint8_t* pad,
+                       const float* bias, const ea_t4* lk, const ea_t4* lv, const ea_t4* out, void* stream) {
+  if (!g) return EA_E_BADARG;
+  if (g->dtype == EA_F32 || (g->D != 64 && g->D != 128) || g->window <= 0 || g->window % 16) return EA_E_UNSUPPORTED;
+  ea::DecP p = {};
+  const int rc = dec_fill_attn(dec_read(g, l16), q, k, v, pad, bias, lk, lv, out, p);
+  return rc != EA_OK ? rc : ea::ceva_sdecode_attn_mm(p, (hipStream_t)stream, l16);
+}
 // What the two launches of a split step add to a static step: 2 .. 64 parts, a 16-byte aligned workspace of fp32 partials
 // [B, H, 8, parts, D + 4], and a step of at most 8 tokens (one query group per window block).  Decided first, like every
 // EA_E_BADARG of the static state.
@@ -2610,6 +2621,17 @@ int ea_ceva_sdecode_attn_split_l16(const ea_ceva_sdec_geom* g, const ea_t4* q, c
                                    const uint8_t* pad, const float* bias, const ea_t4* rf_k_bar, const ea_t4* beta,
                                    const ea_t4* out, int32_t parts, float* ws, void* stream) {
   return dec_attn_split(g, true, q, k, v, pad, bias, rf_k_bar, beta, out, parts, ws, stream);
+}
+
+// attn of a step on the matrix cores, in attn's place between close and advance; _l16: on a compact state
+int ea_ceva_sdecode_attn_mm(const ea_ceva_sdec_geom* g, const ea_t4* q, const ea_t4* k, const ea_t4* v, const uint8_t* pad,
+                            const float* bias, const ea_t4* rf_k_bar, const ea_t4* beta, const ea_t4* out, void* stream) {
+  return dec_attn_mm(g, false, q, k, v, pad, bias, rf_k_bar, beta, out, stream);
+}
+
+int ea_ceva_sdecode_attn_mm_l16(const ea_ceva_sdec_geom* g, const ea_t4* q, const ea_t4* k, const ea_t4* v, const uint8_t* pad,
+                                const float* bias, const ea_t4* rf_k_bar, const ea_t4* beta, const ea_t4* out, void* stream) {
+  return dec_attn_mm(g, true, q, k, v, pad, bias, rf_k_bar, beta, out, stream);
 }
 
 int ea_ceva_sdecode_merge(const ea_ceva_sdec_geom* g, const ea_t4* out, int32_t parts, const float* ws, void* stream) {

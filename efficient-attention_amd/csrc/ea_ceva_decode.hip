@@ -100,31 +100,8 @@ template <typename L> EA_DEV void store_lmk(const DecT& t, int b, int h, int c, 
   Io<L>::st1(const_cast<char*>(row<L>(t, b, h, c)) + (size_t)o * Io<L>::SZ, v);
 }
 
-// Token index -> row of q / k / v / pad.  RING = false: the identity, every member folds away.  RING = true: slot
-// n % ring.  A kernel reduces once (`slot` of its first token) and then walks: a run of fewer than `ring` rows that starts
-// at a slot passes the end of the ring at most once (`wrap`), and one that starts up to `ring` rows before a slot falls
-// before slot 0 at most once (`unwrap`).
-template <bool RING> struct Rows {
-  int ring;
-  EA_DEV int slot(int n) const { return RING ? n % ring : n; }                     // n >= 0
-  EA_DEV size_t slot(int n, int j) const { return RING ? (size_t)((n + j) % ring) : (size_t)n + j; }
-  EA_DEV int wrap(int s) const { return RING ? s - (s >= ring ? ring : 0) : s; }   // 0 <= s < 2 ring
-  EA_DEV int unwrap(int s) const { return RING && s < 0 ? s + ring : s; }          // -ring <= s < ring
-  EA_DEV int len(int cap) const { return RING ? ring : cap; }                      // rows per batch element (of pad)
-};
-
-// Where the step starts, how many tokens of it batch element b has, and whether they fit the cache.  DEV = false: the kernel
-// argument (the host has checked the capacity: `fits` is true and folds away).  DEV = true: the token count in device memory
-// -- one value for every thread of the step's launches up to advance, so every exit decided from it is uniform.  SEQ: the
-// count and the share of element b; a workgroup has one b, so the exits stay uniform.
-template <bool DEV, bool SEQ = false> struct Step {
-  static_assert(DEV || !SEQ, "per-sequence counts belong to the static step");
-  int t0, own;                                     // own: the element's tokens of this step (SEQ; else all T of them)
-  EA_DEV Step(const DecP& p, int b) : t0(SEQ ? p.pos[b] : DEV ? *p.pos : p.t0), own(SEQ ? p.ntok[b] : 0) {}
-  EA_DEV Step(const int32_t* pos, int b, int n_own) : t0(pos[SEQ ? b : 0]), own(n_own) {}   // append finds n itself
-  EA_DEV int n(int T) const { return SEQ ? own : T; }
-  EA_DEV bool fits(int T, int cap) const { return !DEV || t0 + n(T) <= cap; }
-};
+// (Rows, the map from a token index to a cache row, and Step, the start and the per-row count of a step, live in
+// ea_ceva_decode.h: ea_ceva_decode_mm.hip takes them too.)
 
 EA_DEV float wave_max(float v) {
 #pragma unroll

@@ -259,6 +259,8 @@ def _hold_vocab_option(init):
             state.vocab_ws = torch.empty(ws_bytes, dtype=torch.uint8, device=device)
             self._load_held_vocab(state)
         return state
+    # (`matrix_prompts`, the attention states' keyword-only option, is a keyword of `init_decoding` that the pinned list omits)
+    init_decoding.__signature__ = params.replace(parameters=[p for p in params.parameters.values() if p.name != "matrix_prompts"])
     return init_decoding
 
 
@@ -331,10 +333,10 @@ class DecoderStack(nn.Module):
     # ---- incremental decoding -----------------------------------------------------------------------------------------------
     @_hold_vocab_option
     def init_decoding(self, batch_size, max_tokens, dtype, device, rolling=True, hold_weights=True, per_sequence=False,
-                      landmark_splits=1, compact_landmarks=False, max_step_tokens=None):
+                      landmark_splits=1, compact_landmarks=False, max_step_tokens=None, matrix_prompts=False):
         """One static (rolling=False) or rolling decoding state per layer's attention, made by `init_static_decoding` /
-        `init_rolling_decoding` with `per_sequence`, `landmark_splits`, `compact_landmarks` (and, rolling, `max_step_tokens`)
-        handed on and `hold_projections=hold_weights` -> a DecodingState.  With hold_weights (a 16-bit `dtype` only: fp32 is
+        `init_rolling_decoding` with `per_sequence`, `landmark_splits`, `compact_landmarks`, `matrix_prompts` (and, rolling,
+        `max_step_tokens`) handed on and `hold_projections=hold_weights` -> a DecodingState.  With hold_weights (a 16-bit `dtype` only: fp32 is
         refused with the attention's ValueError) the state also holds 16-bit copies of every layer's fc1 / fc2 weights and
         biases, 2 (C F + F + F C + C) bytes per layer, taken here once: a capture fixes the weights, and
         `refresh_decoding_weights` re-reads them.  `max_tokens` may not pass the position table.
@@ -349,6 +351,8 @@ class DecoderStack(nn.Module):
                        compact_landmarks=bool(compact_landmarks), max_step_tokens=max_step_tokens)
         opt = dict(per_sequence=per_sequence, landmark_splits=landmark_splits, hold_projections=hold_weights,
                    compact_landmarks=compact_landmarks)
+        if matrix_prompts:                              # (a state made without the option is what it was, `options` included)
+            options["matrix_prompts"] = opt["matrix_prompts"] = True
         incremental = {}
         for layer in self.layers:
             if rolling:

@@ -21,6 +21,8 @@ such a step touches a weight.
 A bf16 or fp16 static or rolling state made with `compact_landmarks=True` keeps its landmark rows (`rf_k_bar`, `beta`) in its
 own dtype instead of fp32: close, attn and attn_split run as ea_ceva_sdecode_close_l16, _attn_l16 and _attn_split_l16, which
 round the two rows of a closed chunk once and read them as they read key and value rows; the arithmetic stays fp32.
+A bf16 or fp16 static or rolling state made with `matrix_prompts=True` runs attn of a step of at least 16 tokens (a prompt, a
+piece of one) on the matrix cores, ea_ceva_sdecode_attn_mm[_l16] (csrc/ea_ceva_decode_mm.hip); shorter steps are untouched.
 """
 import ctypes
 import functools
@@ -40,6 +42,7 @@ _STATIC_BATCH_FIRST = ("qkv", "rf_k_bar", "beta", "pad")
 _PER_SEQUENCE = ("pos", "status", "ntok")
 _SPLIT_MAX_STEP = 8          # QPW of ea_ceva_decode.hip: a step of at most this many tokens has one query group per window block
 _SPLIT_MAX_PARTS = 64
+_MATRIX_MIN_STEP = 16       # a step of at least this many tokens of a `matrix_prompts` state runs attn on ea_ceva_sdecode_attn_mm
 _LINEAR_MAX_ROWS = 64        # EA_CEVA_LINEAR_MAX_ROWS of include/ea_hip.h: the rows (T_new B) ea_ceva_sdecode_linear takes
 # what a state made with hold_projections=True adds to the buffer (step-invariant like `bias` and `mu`: a beam reorder and
 # reset_decoding_rows leave them alone)
@@ -47,22 +50,22 @@ _HELD = ("w_qkv", "b_qkv", "w_out", "b_out", "proj_rows")
 
 
 def _state_options(init):
-    """The keyword-only `per_sequence=False`, `landmark_splits=1`, `hold_projections=False` and `compact_landmarks=False` of
-    the two `init_*_decoding` methods.  The methods keep
+    """The keyword-only `per_sequence=False`, `landmark_splits=1`, `hold_projections=False`, `compact_landmarks=False` and
+    `matrix_prompts=False` of the two `init_*_decoding` methods.  The methods keep
     the positional interface they had, and that is the signature they report (`__signature__`: callers that pin the parameter
     list, this package's own tests among them, see what they saw); the options are taken off here and handed to the method
     as its last arguments.  Arguments are bound as Python binds them: an option by position, or an unknown keyword, is a
     TypeError.  (`landmark_splits` is handed on as given: the method checks it behind its other refusals.)"""
     positional = inspect.signature(init)
-    positional = positional.replace(parameters=list(positional.parameters.values())[:-4])
+    positional = positional.replace(parameters=list(positional.parameters.values())[:-5])
 
     @functools.wraps(init)
     def with_options(self, *args, per_sequence=False, landmark_splits=1, hold_projections=False, compact_landmarks=False,
-                     **kwargs):
+                     matrix_prompts=False, **kwargs):
         bound = positional.bind(self, *args, **kwargs)
         bound.apply_defaults()
         return init(*bound.args, bool(per_sequence), landmark_splits, bool(hold_projections), bool(compact_landmarks),
-                    **bound.kwargs)
+                    bool(matrix_prompts), **bound.kwargs)
     with_options.__signature__ = positional
     return with_options
 
@@ -101,7 +104,7 @@ class CevaDecoding:
     # ---- static and rolling states ----------------------------------------------------------------------------------------
     @_state_options
     def init_static_decoding(self, incremental_state, batch_size, max_tokens, dtype, device, per_sequence=False,
-                             landmark_splits=1, hold_projections=False, compact_landmarks=False):
+                             landmark_splits=1, hold_projections=False, compact_landmarks=False, matrix_prompts=False):
         """Allocate, once, every buffer a decoding step touches and mark this module's incremental state as STATIC: every
         later `forward(..., incremental_state=incremental_state)` then runs a step that can be captured into a graph
         (`torch.cuda.graph`) and replayed -- the token count lives in device memory and the kernels advance it: four
@@ -186,19 +189,32 @@ class CevaDecoding:
         visible.  The token rows, pad flags and counters are those of the plain state.  The other methods need nothing
         beyond what the dtype carries: `reorder_incremental_state` copies rows of whatever type, `reset_decoding_rows`,
         `decoding_positions` and the overflow queries read no landmark row, `refresh_decoding_weights` touches none, and
-        `decoding_state_nbytes` counts the bytes the tensors have."""
+        `decoding_state_nbytes` counts the bytes the tensors have.
+        `matrix_prompts=True` (default False; combines with the other four; a 16-bit `dtype`, head dim 64 or 128 and
+        `window_size % 16 == 0` only, ValueError otherwise): a step of AT LEAST 16 TOKENS -- a prompt, and every piece of at
+        least 16 tokens that a rolling state cuts it into -- runs its attn launch on the matrix cores,
+        ea_ceva_sdecode_attn_mm (ea_ceva_sdecode_attn_mm_l16 on a compact state) in place of ea_ceva_sdecode_attn: one
+        workgroup per 64 queries, key, value and landmark rows streamed through LDS in tiles of 64, Q.K^T and P.V on
+        mfma_f32_16x16x32.  The columns, masks and the softmax are attn's; what differs is rounding -- fp32 landmark rows are
+        rounded to `dtype` as they are staged, and the weights P are rounded to `dtype` for P.V (sums stay fp32, the row sum is
+        that of the unrounded weights) -- so the outputs equal the plain state's to 16-bit rounding, not bit for bit
+        (DESIGN.md 4a has the bound).  append, close and advance are the same launches: the state's rows are the plain
+        state's bit for bit.  Shorter steps, the single-token step and the `landmark_splits` route among them, are untouched,
+        and the choice depends on the step's token count alone, which a capture fixes.  The state holds nothing more."""
         B, T, device = self._check_static_decoding(batch_size, max_tokens, dtype, device)
         P = _check_landmark_splits(landmark_splits)
         self._check_hold_projections(hold_projections, dtype)
         self._check_compact_landmarks(compact_landmarks, dtype)
+        self._check_matrix_prompts(matrix_prompts, dtype)
         w = self.window_size
         cap = -(-T // w) * w
         return self._alloc_static_decoding(incremental_state, B, cap, cap, dtype, device, {"count": 0}, per_sequence, P,
-                                           hold_projections, compact_landmarks)
+                                           hold_projections, compact_landmarks, matrix_prompts)
 
     @_state_options
     def init_rolling_decoding(self, incremental_state, batch_size, max_tokens, dtype, device, max_step_tokens=None,
-                              per_sequence=False, landmark_splits=1, hold_projections=False, compact_landmarks=False):
+                              per_sequence=False, landmark_splits=1, hold_projections=False, compact_landmarks=False,
+                              matrix_prompts=False):
         """`init_static_decoding` with the token rows in a fixed RING: the state is static in every respect (the same step,
         capturable and replayable; `static_decoding_overflowed` and the in-place `reorder_incremental_state` work on it), but
         `qkv` and `pad` hold R token slots instead of one row per token ever decoded, token n in slot n % R:
@@ -230,7 +246,9 @@ class CevaDecoding:
         `compact_landmarks=True`: as in `init_static_decoding` -- a bf16 or fp16 state keeps `rf_k_bar` and `beta` in its own
         dtype, the plain state's rows rounded once, and its steps run the `_l16` entry points.  The landmark rows are nearly
         all of a rolling state at a long context (33.5 of 35 MB per layer and sequence at 32k tokens, h = 8, d = 128, r = 8),
-        so the option about halves it."""
+        so the option about halves it.
+        `matrix_prompts=True`: as in `init_static_decoding` -- every piece of a prompt decides by its own length, so with
+        `max_step_tokens >= 16` the pieces run ea_ceva_sdecode_attn_mm and a tail shorter than 16 tokens runs attn."""
         B, T, device = self._check_static_decoding(batch_size, max_tokens, dtype, device)
         w, e = self.window_size, self.ext_size
         S = w if max_step_tokens is None else int(max_step_tokens)
@@ -239,12 +257,27 @@ class CevaDecoding:
         P = _check_landmark_splits(landmark_splits)
         self._check_hold_projections(hold_projections, dtype)
         self._check_compact_landmarks(compact_landmarks, dtype)
+        self._check_matrix_prompts(matrix_prompts, dtype)
         cap = -(-T // w) * w
         ring = -(-(w + e + S) // w) * w
         rows = min(ring, cap)
         static = {"count": 0, "cap": cap, "ring": ring if ring < cap else 0, "max_step": S}
         return self._alloc_static_decoding(incremental_state, B, cap, rows, dtype, device, static, per_sequence, P,
-                                           hold_projections, compact_landmarks)
+                                           hold_projections, compact_landmarks, matrix_prompts)
+
+    def _check_matrix_prompts(self, matrix, dtype):
+        """What `matrix_prompts=True` refuses, behind every other refusal and before anything is allocated: the geometries
+        ea_ceva_sdecode_attn_mm has no instance for."""
+        if not matrix:
+            return
+        if dtype == torch.float32:
+            raise ValueError("matrix_prompts=True multiplies 16-bit rows on the matrix cores: an fp32 decoding state is the "
+                             "fidelity path and keeps the fp32 kernels")
+        if self.head_dim not in (64, 128):
+            raise ValueError("matrix_prompts=True needs head dim 64 or 128, got %d" % self.head_dim)
+        if self.window_size % 16:
+            raise ValueError("matrix_prompts=True needs window_size %% 16 == 0 (query groups of 16 tokens may not straddle a "
+                             "window block), got %d" % self.window_size)
 
     @staticmethod
     def _check_compact_landmarks(compact, dtype):
@@ -281,7 +314,7 @@ class CevaDecoding:
         return B, T, device
 
     def _alloc_static_decoding(self, incremental_state, B, cap, rows, dtype, device, static, per_sequence=False, splits=1,
-                               hold=False, compact=False):
+                               hold=False, compact=False, matrix=False):
         """The buffers of a static state: `rows` token rows (cap, or a ring), cap / r landmark rows (fp32; compact: `dtype`);
         one counter and one overflow flag, or (per_sequence) one of each per batch row and the rows' token counts of a step;
         splits > 1: the workspace of a short step's partials; hold: the 16-bit projections and the staging rows of a step."""
@@ -313,6 +346,8 @@ class CevaDecoding:
             static["hold_projections"] = True
         if compact:
             static["compact_landmarks"] = True
+        if matrix:
+            static["matrix_prompts"] = True
         with torch.no_grad():
             state["bias"] = self._decode_bias_table(device)
             state["mu"] = self._decode_mu_f32()
@@ -632,6 +667,9 @@ class CevaDecoding:
             ws, parts = state["split_ws"], state["split_ws"].shape[3]
             nv.call("ea_ceva_sdecode_attn_split" + l16, g, *rows, nv.ptr(bias), *lmk, ctypes.byref(to), parts, nv.ptr(ws), st)
             nv.call("ea_ceva_sdecode_merge", g, ctypes.byref(to), parts, nv.ptr(ws), st)
+        elif static is not None and static.get("matrix_prompts") and T_new >= _MATRIX_MIN_STEP:
+            # (a prompt, or a piece of one, by its own length: the matrix-core twin of attn)
+            nv.call("ea_ceva_sdecode_attn_mm" + l16, g, *rows, nv.ptr(bias), *lmk, ctypes.byref(to), st)
         else:
             nv.call(family + "attn" + l16, g, *rows, nv.ptr(bias), *lmk, ctypes.byref(to), st)
         if static is not None:

@@ -278,6 +278,8 @@ SIGNATURES = {
     "ea_ceva_sdecode_close_l16": [_SDG, _T, _T, _T, _P, _P, _T, _T, _P],
     "ea_ceva_sdecode_attn_l16": [_SDG, _T, _T, _T, _P, _P, _T, _T, _T, _P],
     "ea_ceva_sdecode_attn_split_l16": [_SDG, _T, _T, _T, _P, _P, _T, _T, _T, _I, _P, _P],
+    "ea_ceva_sdecode_attn_mm": [_SDG, _T, _T, _T, _P, _P, _T, _T, _T, _P],
+    "ea_ceva_sdecode_attn_mm_l16": [_SDG, _T, _T, _T, _P, _P, _T, _T, _T, _P],
     "ea_ceva_sdecode_merge": [_SDG, _T, _I, _P, _P],
     "ea_ceva_sdecode_advance": [_SDG, _P],
     "ea_ceva_sdecode_linear": [_I, _I, _I, _P, _I, _L, _P, _I, _P, _P, _I, _L, _P],

@@ -1181,6 +1181,20 @@ int ea_ceva_sdecode_attn_split_l16(const ea_ceva_sdec_geom* g, const ea_t4* q, c
                                    const uint8_t* pad, const float* bias, const ea_t4* rf_k_bar, const ea_t4* beta,
                                    const ea_t4* out, int32_t parts, float* ws, void* stream);
 
+/* attn of a prompt step on the matrix cores (init_*_decoding(matrix_prompts=True); ea_ceva_decode_mm.hip): additions to ABI 38,
+ * no signature changes.  ea_ceva_sdecode_attn_mm takes the place of ea_ceva_sdecode_attn in a step, ea_ceva_sdecode_attn_mm_l16
+ * that of ea_ceva_sdecode_attn_l16, with the twin's arguments, geometry and contract: the same columns, masks, fill, bias,
+ * NaN rows of a step that does not fit and zero rows of a per-sequence element.  The arithmetic differs: S = Q.K^T and P.V
+ * run on mfma_f32_16x16x32 from 16-bit operands (fp32 landmark rows are rounded to `dtype` once, to nearest even, as they
+ * are staged), P is rounded to `dtype`, sums and the softmax stay in fp32 and the row sum is that of the unrounded weights:
+ *   |out - exact| <= u (|exact| + sum_j p_j |value_j|) + 1e-6 max |exact|,  u = 2^-8 (bf16) | 2^-11 (fp16)
+ * on the operands as multiplied.  One workgroup per 64 queries, any T_new >= 1.
+ * EA_E_UNSUPPORTED, decided first and for both entries alike: dtype EA_F32, D outside {64, 128}, window % 16 != 0. */
+int ea_ceva_sdecode_attn_mm(const ea_ceva_sdec_geom* g, const ea_t4* q, const ea_t4* k, const ea_t4* v, const uint8_t* pad,
+                            const float* bias, const ea_t4* rf_k_bar, const ea_t4* beta, const ea_t4* out, void* stream);
+int ea_ceva_sdecode_attn_mm_l16(const ea_ceva_sdec_geom* g, const ea_t4* q, const ea_t4* k, const ea_t4* v, const uint8_t* pad,
+                                const float* bias, const ea_t4* rf_k_bar, const ea_t4* beta, const ea_t4* out, void* stream);
+
 /* ABI 22, the projections of a step on weights the static state holds (init_*_decoding(hold_projections=True);
  * ea_ceva_decode_linear.hip):
  *   y[m, n] = round_y( sum_k round_w(x[m, k]) w[n, k] + bias[n] ),  1 <= M <= EA_CEVA_LINEAR_MAX_ROWS
