@@ -7,6 +7,7 @@
 #include "ea_landmark_params.h"
 #include "ea_lara.h"
 #include "ea_softmax.h"
+#include "ea_softmax_causal.h"
 #include "ea_lara_lmk.h"
 #include "ea_lara_merge.h"
 #include "ea_layernorm.h"
@@ -842,6 +843,58 @@ int32_t ea_softmax_tiles(int32_t which, int32_t B, int32_t H, int32_t N, int32_t
   if (rc != EA_OK) return rc;
   if ((which != 0 && which != 1) || cus < 0) return EA_E_BADARG;
   return softmax_tiles(which, (long)B * H, N, D, has_keep != 0, cus > 0 ? cus : ea_device_cus());
+}
+
+}  // extern "C"
+
+// ---- causal softmax (ea_softmax_causal.hip): the decoder's softmax baseline ----
+#define SMC_SET(dst, src) do { p.dst.p = (char*)(src)->ptr; p.dst.sb = (src)->sb; p.dst.sh = (src)->sh; p.dst.sn = (src)->sn; } while (0)
+// every refusal of the causal entries, before any launch
+static int fill_smc(int which, int B, int H, int N, int D, int dtype, float scale, const uint8_t* keep, float keep_scale, int tiles,
+                    SmcP& p) {
+  if (B <= 0 || H <= 0 || N <= 0 || (D != 32 && D != 64 && D != 128) || (dtype != EA_BF16 && dtype != EA_F16))
+    return EA_E_BADARG;
+  if (tiles < 0 || (tiles > 0 && !softmax_causal_tiles_ok(which, tiles, D, keep != nullptr))) return EA_E_BADARG;
+  p.B = B; p.H = H; p.N = N; p.scale = scale; p.scale_log2 = scale * LOG2E;
+  p.keep = keep; p.keep_scale = keep_scale; p.keep_ld = (N + 63) / 64 * 64;
+  return EA_OK;
+}
+
+extern "C" {
+
+int ea_softmax_causal_fwd(int32_t B, int32_t H, int32_t N, int32_t D, int32_t dtype, float scale,
+                          const ea_t4* q, const ea_t4* k, const ea_t4* v, const uint8_t* mask,
+                          const ea_t4* out, float* lse, const uint8_t* keep, float keep_scale,
+                          int32_t tiles, void* stream) {
+  SmcP p = {};
+  int rc = fill_smc(0, B, H, N, D, dtype, scale, keep, keep_scale, tiles, p);
+  if (rc != EA_OK) return rc;
+  if (!view_ok(q, D, 2) || !view_ok(k, D, 2) || !view_ok(v, D, 2) || !view_ok(out, D, 2) || !lse) return EA_E_BADARG;
+  SMC_SET(q, q); SMC_SET(k, k); SMC_SET(v, v); SMC_SET(o, out);
+  p.mask = mask; p.lse = lse;
+  return softmax_causal_dispatch(0, p, dtype, D, tiles, (hipStream_t)stream);
+}
+
+int ea_softmax_causal_bwd(int32_t B, int32_t H, int32_t N, int32_t D, int32_t dtype, float scale,
+                          const ea_t4* q, const ea_t4* k, const ea_t4* v, const uint8_t* mask,
+                          const ea_t4* out, const ea_t4* dout, const float* lse, float* delta,
+                          const ea_t4* dq, const ea_t4* dk, const ea_t4* dv,
+                          const uint8_t* keep, float keep_scale, int32_t tiles, void* stream) {
+  SmcP p = {};
+  int rc = fill_smc(1, B, H, N, D, dtype, scale, keep, keep_scale, tiles, p);
+  if (rc != EA_OK) return rc;
+  if (!view_ok(q, D, 2) || !view_ok(k, D, 2) || !view_ok(v, D, 2) || !view_ok(out, D, 2) || !view_ok(dout, D, 2) ||
+      !view_ok(dq, D, 2) || !view_ok(dk, D, 2) || !view_ok(dv, D, 2) || !lse || !delta) return EA_E_BADARG;
+  SMC_SET(q, q); SMC_SET(k, k); SMC_SET(v, v); SMC_SET(o, out); SMC_SET(dout, dout);
+  SMC_SET(dq, dq); SMC_SET(dk, dk); SMC_SET(dv, dv);
+  p.mask = mask; p.lse = const_cast<float*>(lse); p.delta = delta;
+  return softmax_causal_dispatch(1, p, dtype, D, tiles, (hipStream_t)stream);
+}
+
+int32_t ea_softmax_causal_tiles(int32_t which, int32_t B, int32_t H, int32_t N, int32_t D, int32_t has_keep, int32_t cus) {
+  if (B <= 0 || H <= 0 || N <= 0 || (D != 32 && D != 64 && D != 128)) return EA_E_BADARG;
+  if ((which != 0 && which != 1) || cus < 0) return EA_E_BADARG;
+  return softmax_causal_tiles(which, (long)B * H, N, D, has_keep != 0, cus > 0 ? cus : ea_device_cus());
 }
 
 }  // extern "C"

@@ -35,7 +35,7 @@ import torch
 import torch.nn as nn
 import torch.nn.functional as F
 
-from efficient_attention import AttentionFactory, CausalEVAttention
+from efficient_attention import AttentionFactory, CausalEVAttention, CausalSoftmaxAttention
 
 from . import token_pick as tp
 from .token_pick import (AdaptivePick, AdaptiveTables, Beam, DecodingState, Sampler, Scorer,    # noqa: F401  (they lived here)
@@ -162,8 +162,7 @@ class DecoderLayer(nn.Module):
         self.embed_dim, self.ffn_dim = embed_dim, ffn_dim
         if not isinstance(attn_args, argparse.Namespace):
             attn_args = argparse.Namespace(**dict(attn_args or {}))
-        self.self_attn = CausalEVAttention(embed_dim, num_heads, dropout=attention_dropout, self_attention=True,
-                                           q_noise=0.0, qn_block_size=8, attn_args=attn_args)
+        self.self_attn = self.build_self_attention(embed_dim, num_heads, attention_dropout, attn_args)
         self.dropout_module = nn.Dropout(dropout)
         self.activation_dropout_module = nn.Dropout(activation_dropout)
         self.normalize_before = normalize_before
@@ -171,6 +170,11 @@ class DecoderLayer(nn.Module):
         self.fc1 = nn.Linear(embed_dim, ffn_dim)
         self.fc2 = nn.Linear(ffn_dim, embed_dim)
         self.final_layer_norm = nn.LayerNorm(embed_dim)
+
+    def build_self_attention(self, embed_dim, num_heads, attention_dropout, attn_args):
+        """fairseq's hook (transformer_layer.py:295-321): the layer's self-attention module; a subclass builds another one."""
+        return CausalEVAttention(embed_dim, num_heads, dropout=attention_dropout, self_attention=True,
+                                 q_noise=0.0, qn_block_size=8, attn_args=attn_args)
 
     def forward(self, x, key_padding_mask=None):
         """The full causal path: x [T, B, C], key_padding_mask [B, T] (1 = pad) -> [T, B, C]."""
@@ -217,6 +221,17 @@ class DecoderLayer(nn.Module):
                 h = F.relu(F.linear(x.to(w1.dtype), w1, b1))
                 x = res + F.linear(h, w2, b2)
         return x if self.normalize_before else self.final_layer_norm(x)
+
+
+class SoftmaxDecoderLayer(DecoderLayer):
+    """DecoderLayer around fairseq's stock causal softmax attention (CausalSoftmaxAttention), the baseline of the comparison:
+    the same members and keys but for `self_attn`, which has the four projections only.  `attn_args` is not read."""
+
+    def build_self_attention(self, embed_dim, num_heads, attention_dropout, attn_args):
+        return CausalSoftmaxAttention(embed_dim, num_heads, dropout=attention_dropout, self_attention=True)
+
+
+_DECODER_LAYERS = {"causal_eva": DecoderLayer, "softmax": SoftmaxDecoderLayer}
 
 
 # ---- decoding states, what they carry and the picks made on them: token_pick.py -----------------------------------------------
@@ -284,8 +299,11 @@ class DecoderStack(nn.Module):
 
     def __init__(self, vocab, embed_dim, ffn_dim, num_heads, layers, attn_args=None, dropout=0.1, attention_dropout=0.0,
                  activation_dropout=0.0, normalize_before=True, final_norm=False, max_positions=4096, pad_idx=1,
-                 adaptive=None):
+                 adaptive=None, attn_name="causal_eva"):
         super().__init__()
+        if attn_name not in _DECODER_LAYERS:
+            raise ValueError("attn_name must be one of %s, got %r" % (sorted(_DECODER_LAYERS), attn_name))
+        self.attn_name = attn_name
         self.embed_dim, self.pad_idx = embed_dim, pad_idx
         if adaptive is None:
             self.embed_tokens = nn.Embedding(vocab, embed_dim, padding_idx=pad_idx)
@@ -303,8 +321,9 @@ class DecoderStack(nn.Module):
                                                     self.embed_tokens if opt["tie_weights"] else None, opt["tie_proj"])
         self.register_buffer("positions", EncoderStack._sinusoid(max_positions, embed_dim), persistent=False)
         self.dropout = nn.Dropout(dropout)
-        self.layers = nn.ModuleList([DecoderLayer(embed_dim, ffn_dim, num_heads, attn_args, dropout, attention_dropout,
-                                                  activation_dropout, normalize_before) for _ in range(layers)])
+        layer_cls = _DECODER_LAYERS[attn_name]
+        self.layers = nn.ModuleList([layer_cls(embed_dim, ffn_dim, num_heads, attn_args, dropout, attention_dropout,
+                                               activation_dropout, normalize_before) for _ in range(layers)])
         self.layer_norm = nn.LayerNorm(embed_dim) if final_norm else None
 
     def forward(self, tokens, key_padding_mask=None):                      # tokens [B, T] int64, mask [B, T] (1 = pad)
@@ -340,7 +359,12 @@ class DecoderStack(nn.Module):
         refused with the attention's ValueError) the state also holds 16-bit copies of every layer's fc1 / fc2 weights and
         biases, 2 (C F + F + F C + C) bytes per layer, taken here once: a capture fixes the weights, and
         `refresh_decoding_weights` re-reads them.  `max_tokens` may not pass the position table.
-        Keyword-only, on top of these: `hold_vocab=False` (see `_hold_vocab_option`)."""
+        Keyword-only, on top of these: `hold_vocab=False` (see `_hold_vocab_option`).
+        On a stack built with attn_name="softmax": NotImplementedError, as for everything that needs a decoding state."""
+        if self.attn_name == "softmax":
+            raise NotImplementedError("softmax decoding is not built: a DecoderStack(attn_name='softmax') has no decoding state "
+                                      "(KV-cache decoding is a follow-up); forward, evaluate, loss, adaptive_loss and "
+                                      "rows_logprobs run on it")
         if hold_weights:
             self.layers[0].self_attn._check_hold_projections(True, dtype)
         if int(max_tokens) > self.positions.shape[0]:

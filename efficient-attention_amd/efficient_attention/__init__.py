@@ -61,6 +61,7 @@ from .kernelized_attention import KernelizedAttention  # noqa: E402
 from .lara import LinearRA  # noqa: E402
 from .eva import EVA  # noqa: E402
 from .causal_eva import CausalEVAttention  # noqa: E402
+from .causal_softmax import CausalSoftmaxAttention  # noqa: E402
 from .randomized_attention import RandomizedAttention  # noqa: E402
 from .scatterbrain_attention import ScatterBrain  # noqa: E402
 
@@ -93,4 +94,5 @@ class AttentionFactory(object):
 
 __all__ = ["AttentionFactory", "NestedNamespace", "add_nested_argument", "remove_argument",
            "remove_prefix", "MultiheadAttention", "LocalAttention", "KernelizedAttention",
-           "LinearRA", "EVA", "RandomizedAttention", "ScatterBrain", "CausalEVAttention"]
+           "LinearRA", "EVA", "RandomizedAttention", "ScatterBrain", "CausalEVAttention",
+           "CausalSoftmaxAttention"]

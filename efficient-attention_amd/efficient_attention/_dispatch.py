@@ -8,6 +8,7 @@ on the current stream (include/ea_hip.h); there is no CPU kernel -- a CPU tensor
 implementation (no fallback).  The autograd Functions of _ops.py are thin shells over these ops.
 
     ea::softmax_fwd / softmax_bwd        abstract_attention.py:120-133
+    ea::softmax_causal_fwd / _bwd        fairseq's causal MultiheadAttention (the decoder's softmax baseline)
     ea::local_fwd / local_bwd            local_attention.py:134-182
     ea::eva_fwd / eva_bwd                eva.py:145-227 (and causal_eva.py:666-788)
     ea::lara_fwd / lara_bwd              lara.py:129-175,187-246 (2-D pooled proposals)
@@ -27,6 +28,8 @@ _LIB = torch.library.Library("ea", "DEF")
 _SCHEMAS = {
     "softmax_fwd": "(Tensor qkv, Tensor? mask, Tensor? keep, float keep_scale) -> Tensor[]",
     "softmax_bwd": "(Tensor dout, Tensor qkv, Tensor? mask, Tensor out, Tensor lse, Tensor? keep, float keep_scale) -> Tensor",
+    "softmax_causal_fwd": "(Tensor qkv, Tensor? mask, Tensor? keep, float keep_scale) -> Tensor[]",
+    "softmax_causal_bwd": "(Tensor dout, Tensor qkv, Tensor? mask, Tensor out, Tensor lse, Tensor? keep, float keep_scale) -> Tensor",
     "local_fwd": "(Tensor qkv, Tensor? bias, Tensor? mask, int[] geo) -> Tensor[]",
     "local_bwd": "(Tensor dout, Tensor? dlse, Tensor qkv, Tensor? bias_p, Tensor? mask, Tensor out, Tensor lse, "
                  "int[] geo, int bias_cols) -> Tensor[]",
@@ -48,6 +51,7 @@ _SCHEMAS = {
 }
 _IMPLS = {
     "softmax_fwd": _ops.softmax_fwd_impl, "softmax_bwd": _ops.softmax_bwd_impl,
+    "softmax_causal_fwd": _ops.softmax_causal_fwd_impl, "softmax_causal_bwd": _ops.softmax_causal_bwd_impl,
     "local_fwd": _ops.local_fwd_impl, "local_bwd": _ops.local_bwd_impl,
     "performer_fwd": _ops.performer_fwd_impl, "performer_bwd": _ops.performer_bwd_impl,
     "kernelized_fwd": _kernelized.kernelized_fwd_impl, "kernelized_bwd": _kernelized.kernelized_bwd_impl,
@@ -95,6 +99,17 @@ def _(qkv, mask, keep, keep_scale):
 
 
 @torch.library.register_fake("ea::softmax_bwd")
+def _(dout, qkv, mask, out, lse, keep, keep_scale):
+    return torch.empty_like(qkv)
+
+
+@torch.library.register_fake("ea::softmax_causal_fwd")
+def _(qkv, mask, keep, keep_scale):
+    B, N, _, h, d = qkv.shape
+    return [qkv.new_empty((B, N, h, d)), _f32(qkv, B * h, N)]
+
+
+@torch.library.register_fake("ea::softmax_causal_bwd")
 def _(dout, qkv, mask, out, lse, keep, keep_scale):
     return torch.empty_like(qkv)
 

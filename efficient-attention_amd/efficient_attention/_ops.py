@@ -85,6 +85,8 @@ KERNEL_ALGO_UNITS = {
     "ea_eva_beta_bwd": 6,         # read k,v; read+write dk,dv
     "ea_softmax_attn_fwd": 4,     # read q,k,v; write out
     "ea_softmax_attn_bwd": 8,     # read q,k,v,out,dout; write dq,dk,dv (two passes)
+    "ea_softmax_causal_fwd": 4,   # read q,k,v; write out
+    "ea_softmax_causal_bwd": 8,   # read q,k,v,out,dout; write dq,dk,dv (two passes)
     "ea_performer_kmax": 1,       # read k
     "ea_performer_kv": 2,         # read k,v
     "ea_performer_out": 2,        # read q; write out
@@ -2758,6 +2760,56 @@ class SoftmaxAttnFn(torch.autograd.Function):
     def backward(ctx, dout):
         qkv5, mask_u8, out, lse, keep = ctx.saved_tensors
         return _ea_op("softmax_bwd", softmax_bwd_impl, dout, qkv5, mask_u8, out, lse, keep, ctx.keep_scale), None, None, None
+
+
+# causal softmax: the decoder's softmax baseline (fairseq's causal MultiheadAttention; csrc/ea_softmax_causal.hip)
+def softmax_causal_fwd_impl(qkv5, mask_u8, keep, keep_scale):
+    """torch.ops.ea.softmax_causal_fwd -> [out [B,N,h,d], lse [B*h,N]]; query i attends keys j <= i."""
+    nv.require_cuda(qkv5, "qkv")
+    B, N, _, h, d = qkv5.shape
+    q, k, v = _qkv_views(qkv5)
+    out = torch.empty((B, N, h, d), dtype=qkv5.dtype, device=qkv5.device)
+    lse = torch.empty((B * h, N), dtype=torch.float32, device=qkv5.device)
+    tq, tk, tv, to = nv.t4(q), nv.t4(k), nv.t4(v), nv.t4(out.permute(0, 2, 1, 3))
+    nv.call("ea_softmax_causal_fwd", B, h, N, d, nv.io_dtype(qkv5), float(d) ** -0.5, ctypes.byref(tq),
+            ctypes.byref(tk), ctypes.byref(tv), nv.ptr(mask_u8), ctypes.byref(to), nv.ptr(lse),
+            nv.ptr(keep), float(keep_scale), 0, nv.stream())
+    return [out, lse]
+
+
+def softmax_causal_bwd_impl(dout, qkv5, mask_u8, out, lse, keep, keep_scale):
+    """torch.ops.ea.softmax_causal_bwd -> dqkv [B,N,3,h,d]."""
+    B, N, _, h, d = qkv5.shape
+    dout = dout.contiguous()
+    dqkv5 = torch.empty_like(qkv5)
+    delta = torch.empty_like(lse)
+    q, k, v = _qkv_views(qkv5)
+    dq, dk, dv = _qkv_views(dqkv5)
+    ts = [nv.t4(t) for t in (q, k, v, out.permute(0, 2, 1, 3), dout.permute(0, 2, 1, 3), dq, dk, dv)]
+    nv.call("ea_softmax_causal_bwd", B, h, N, d, nv.io_dtype(qkv5), float(d) ** -0.5, ctypes.byref(ts[0]),
+            ctypes.byref(ts[1]), ctypes.byref(ts[2]), nv.ptr(mask_u8), ctypes.byref(ts[3]),
+            ctypes.byref(ts[4]), nv.ptr(lse), nv.ptr(delta), ctypes.byref(ts[5]), ctypes.byref(ts[6]),
+            ctypes.byref(ts[7]), nv.ptr(keep), float(keep_scale), 0, nv.stream())
+    return dqkv5
+
+
+class CausalSoftmaxAttnFn(torch.autograd.Function):
+    """out[B,N,h,d] = dropout(softmax(s QK^T, -inf above the diagonal and on padded keys)) V on a fused qkv tensor; keep: None
+    or the uint8 keep decisions [B,h,N,64*ceil(N/64)] of the attention dropout, scaled by keep_scale
+    (torch.ops.ea.softmax_causal_fwd / softmax_causal_bwd)."""
+
+    @staticmethod
+    def forward(ctx, qkv5, mask_u8, keep=None, keep_scale=1.0):
+        out, lse = _ea_op("softmax_causal_fwd", softmax_causal_fwd_impl, qkv5, mask_u8, keep, float(keep_scale))
+        ctx.save_for_backward(qkv5, mask_u8, out, lse, keep)
+        ctx.keep_scale = float(keep_scale)
+        return out
+
+    @staticmethod
+    def backward(ctx, dout):
+        qkv5, mask_u8, out, lse, keep = ctx.saved_tensors
+        return (_ea_op("softmax_causal_bwd", softmax_causal_bwd_impl, dout, qkv5, mask_u8, out, lse, keep, ctx.keep_scale),
+                None, None, None)
 
 
 class SoftmaxQKVFn(torch.autograd.Function):

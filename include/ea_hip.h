@@ -372,6 +372,34 @@ int ea_softmax_attn_bwd(int32_t B, int32_t H, int32_t N, int32_t D, int32_t dtyp
  * -> 1, 2 or 4, or a negative EA_E* code for a geometry ea_softmax_attn_fwd refuses (B, H, N <= 0, D not 32 / 64 / 128) and
  * for which not 0 / 1 or cus < 0. */
 int32_t ea_softmax_tiles(int32_t which, int32_t B, int32_t H, int32_t N, int32_t D, int32_t has_keep, int32_t cus);
+/* ---- causal softmax: the decoder's softmax baseline (fairseq's causal MultiheadAttention; ea_softmax_causal.hip) ----
+ * Additive entries of ABI 38.  One sequence of N queries over the same N keys, query i sees keys j <= i:
+ *   out = dropout(softmax(s Q K^T, -inf above the diagonal and on padded keys)) V, streamed with a triangular schedule.
+ * The arguments are ea_softmax_attn_fwd / _bwd's without key_norm_bias: mask uint8 [B, N] (1 = padded key) or NULL; lse and
+ * delta fp32 [B*H, N] (natural log; delta = dout . out, written by the query-side pass and read by the key-side pass); keep
+ * uint8 [B,H,N, 64*ceil(N/64)] with keep_scale, the dense kernels' contract (dropped entries leave the numerator, dP and the P
+ * of dV; the normaliser is the full visible row's; entries above the diagonal are never read), or NULL.  dk and dv of padded
+ * keys are exactly 0; the backward has no atomics, two runs agree bit for bit.  A query whose visible keys are all padded
+ * (left padding) has an empty softmax and a NaN out, as in the reference and in ea_softmax_attn_fwd.
+ * tiles: the 16-token tiles per wave -- 0: ea_softmax_causal_tiles' rule decides; forward 1, 2 or 4 (4: D <= 64 without a
+ * keep mask), backward 1 or 2 (2: D <= 64); any other value is EA_E_BADARG.  B, H, N <= 0 or D not 32 / 64 / 128 or a dtype
+ * other than EA_BF16 / EA_F16 is EA_E_BADARG; every refusal comes before any launch. */
+int ea_softmax_causal_fwd(int32_t B, int32_t H, int32_t N, int32_t D, int32_t dtype, float scale,
+                          const ea_t4* q, const ea_t4* k, const ea_t4* v, const uint8_t* mask,
+                          const ea_t4* out, float* lse, const uint8_t* keep, float keep_scale,
+                          int32_t tiles, void* stream);
+int ea_softmax_causal_bwd(int32_t B, int32_t H, int32_t N, int32_t D, int32_t dtype, float scale,
+                          const ea_t4* q, const ea_t4* k, const ea_t4* v, const uint8_t* mask,
+                          const ea_t4* out, const ea_t4* dout, const float* lse, float* delta,
+                          const ea_t4* dq, const ea_t4* dk, const ea_t4* dv,
+                          const uint8_t* keep, float keep_scale, int32_t tiles, void* stream);
+/* The tile count the causal launcher takes for tiles = 0; which 0 = forward, 1 = backward; cus > 0: for a device of that many
+ * compute units, 0: the current device.  A workgroup's work grows linearly with its position in the sequence, so the
+ * nb = ceil(N / (64 t)) workgroups of a sequence count as (nb + 1) / 2 of the heaviest one: the largest t the direction and
+ * geometry allow with B H (nb + 1) / 2 >= 2 cus, else 1.  Pure: no environment knob.
+ * -> 1, 2 or 4, or EA_E_BADARG for a geometry the entries refuse, which not 0 / 1, or cus < 0. */
+int32_t ea_softmax_causal_tiles(int32_t which, int32_t B, int32_t H, int32_t N, int32_t D, int32_t has_keep, int32_t cus);
+
 /* Randomized attention (randomized_attention.py:21-52) is two passes of the kernels above:
  *   mu = q + softmax(s q k^T) k (num_samples = -1) or q + k[index] with one index per query drawn
  *   from softmax(s q k^T) (ea_softmax_sample: Gumbel-max with counter-based noise from the 64-bit
