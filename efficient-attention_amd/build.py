@@ -28,12 +28,12 @@ LIB_SOURCES = ["ea_capi.hip", "ea_window_fwd.hip", "ea_window_bwd.hip", "ea_eva_
                "ea_kernelized.hip", "ea_ceva_decode.hip", "ea_ceva_decode_linear.hip", "ea_ceva_decode_vocab.hip", "ea_lara_xp.hip",
                "ea_vocab_score.hip", "ea_adaptive_score.hip", "ea_adaptive_pick.hip", "ea_vocab_nll.hip", "ea_adaptive_nll.hip",
                "ea_linear_rs192.hip", "ea_ceva_decode_nucleus.hip", "ea_ceva_lm.hip", "ea_eva_lm.hip",
-               "ea_lara_lm.hip", "ea_ceva_decode_mm.hip", "ea_softmax_causal.hip"]
+               "ea_lara_lm.hip", "ea_ceva_decode_mm.hip", "ea_softmax_causal.hip", "ea_softmax_decode.hip"]
 # ea_ceva_decode_nucleus.hip's integer masses are trunc(expf(..) 2^32) of every column, recomputed in several passes that must
 # agree to the bit: its fp32 operations stay scalar per lane, the compiler pairs none into packed instructions.
 _NO_PK = ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"]
 UNIT_FLAGS = {"ea_ceva_decode_nucleus.hip": _NO_PK, "ea_ceva_lm.hip": _NO_PK, "ea_eva_lm.hip": _NO_PK, "ea_lara_lm.hip": _NO_PK,
-              "ea_ceva_decode_mm.hip": _NO_PK, "ea_softmax_causal.hip": _NO_PK}
+              "ea_ceva_decode_mm.hip": _NO_PK, "ea_softmax_causal.hip": _NO_PK, "ea_softmax_decode.hip": _NO_PK}
 
 
 def _cuid(src):

@@ -8,6 +8,7 @@
 #include "ea_lara.h"
 #include "ea_softmax.h"
 #include "ea_softmax_causal.h"
+#include "ea_softmax_decode.h"
 #include "ea_lara_lmk.h"
 #include "ea_lara_merge.h"
 #include "ea_layernorm.h"
@@ -895,6 +896,88 @@ int32_t ea_softmax_causal_tiles(int32_t which, int32_t B, int32_t H, int32_t N, 
   if (B <= 0 || H <= 0 || N <= 0 || (D != 32 && D != 64 && D != 128)) return EA_E_BADARG;
   if ((which != 0 && which != 1) || cus < 0) return EA_E_BADARG;
   return softmax_causal_tiles(which, (long)B * H, N, D, has_keep != 0, cus > 0 ? cus : ea_device_cus());
+}
+
+}  // extern "C"
+
+// ---- causal softmax decoding against a static KV cache (ea_softmax_decode.hip) ----
+static ea::DecT sdec_mk(const ea_t4* t) { return {(const char*)t->ptr, t->sb, t->sh, t->sn}; }
+// every refusal a step's launches share, before any launch
+static int sdec_check(const ea_softmax_sdec_geom* g) {
+  if (!g || !g->pos || !g->status || (uintptr_t)g->pos % 4 || (uintptr_t)g->status % 4) return EA_E_BADARG;
+  if (g->B <= 0 || g->H <= 0 || g->T_new <= 0 || g->cap < g->T_new || (g->dtype != EA_BF16 && g->dtype != EA_F16))
+    return EA_E_BADARG;
+  return g->D == 32 || g->D == 64 || g->D == 128 ? EA_OK : EA_E_UNSUPPORTED;
+}
+static int sdec_split_check(const ea_softmax_sdec_geom* g, int parts, int least, const void* ws) {
+  if (!g || parts < least || parts > 64 || g->T_new > ea::SDEC_QMAX) return EA_E_BADARG;
+  return parts > 1 && (!ws || (uintptr_t)ws % 16) ? EA_E_BADARG : EA_OK;
+}
+static int sdec_fill(const ea_softmax_sdec_geom* g, const ea_t4* q, const ea_t4* k, const ea_t4* v, const uint8_t* pad,
+                     const ea_t4* out, ea::SdecP& p) {
+  const int rc = sdec_check(g);
+  if (rc != EA_OK) return rc;
+  if (!view_ok(q, g->D, 2) || !view_ok(k, g->D, 2) || !view_ok(v, g->D, 2) || !view_ok(out, g->D, 2) || !pad) return EA_E_BADARG;
+  p.q = sdec_mk(q); p.k = sdec_mk(k); p.v = sdec_mk(v); p.o = sdec_mk(out);
+  p.pad = pad; p.pos = g->pos;
+  p.B = g->B; p.H = g->H; p.D = g->D; p.dtype = g->dtype; p.T = g->T_new; p.cap = g->cap;
+  p.scale = (float)(1.0 / sqrt((double)g->D));
+  p.parts = 1;
+  return EA_OK;
+}
+
+extern "C" {
+
+int ea_softmax_sdecode_append(const ea_softmax_sdec_geom* g, const void* qkv_new, const uint8_t* new_pad, const ea_t4* k,
+                              const ea_t4* v, uint8_t* pad, void* stream) {
+  const int rc = sdec_check(g);
+  if (rc != EA_OK) return rc;
+  if (!qkv_new || (uintptr_t)qkv_new % 16 || !view_ok(k, g->D, 2) || !view_ok(v, g->D, 2) || !pad) return EA_E_BADARG;
+  ea::SdecAppP p = {};
+  p.src = (const char*)qkv_new; p.src_pad = new_pad; p.k = sdec_mk(k); p.v = sdec_mk(v); p.pad = pad;
+  p.pos = g->pos; p.status = g->status;
+  p.B = g->B; p.H = g->H; p.D = g->D; p.T = g->T_new; p.cap = g->cap;
+  return ea::softmax_sdecode_append(p, (hipStream_t)stream);
+}
+
+int ea_softmax_sdecode_attn_split(const ea_softmax_sdec_geom* g, const ea_t4* q, const ea_t4* k, const ea_t4* v,
+                                  const uint8_t* pad, const ea_t4* out, int32_t parts, float* ws, void* stream) {
+  if (sdec_split_check(g, parts, 1, ws) != EA_OK) return EA_E_BADARG;
+  ea::SdecP p = {};
+  const int rc = sdec_fill(g, q, k, v, pad, out, p);
+  if (rc != EA_OK) return rc;
+  p.parts = parts; p.ws = ws;
+  return ea::softmax_sdecode_attn_split(p, (hipStream_t)stream);
+}
+
+// the parts of ea_softmax_sdecode_attn_split folded by the causal EVA step's merge kernel: one workspace layout, one arithmetic
+int ea_softmax_sdecode_merge(const ea_softmax_sdec_geom* g, const ea_t4* out, int32_t parts, const float* ws, void* stream) {
+  if (sdec_split_check(g, parts, 2, ws) != EA_OK) return EA_E_BADARG;
+  const int rc = sdec_check(g);
+  if (rc != EA_OK) return rc;
+  if (!view_ok(out, g->D, 2)) return EA_E_BADARG;
+  ea::DecMergeP p = {};
+  p.o = sdec_mk(out); p.ws = ws; p.pos = g->pos; p.ntok = nullptr;
+  p.H = g->H; p.T = g->T_new; p.cap = g->cap; p.parts = parts;
+  return ea::ceva_sdecode_merge(p, g->D, g->dtype, g->B * g->H, (hipStream_t)stream);
+}
+
+int ea_softmax_sdecode_attn_mm(const ea_softmax_sdec_geom* g, const ea_t4* q, const ea_t4* k, const ea_t4* v,
+                               const uint8_t* pad, const ea_t4* out, void* stream) {
+  ea::SdecP p = {};
+  const int rc = sdec_fill(g, q, k, v, pad, out, p);
+  return rc != EA_OK ? rc : ea::softmax_sdecode_attn_mm(p, (hipStream_t)stream);
+}
+
+int ea_softmax_sdecode_advance(const ea_softmax_sdec_geom* g, void* stream) {
+  const int rc = sdec_check(g);
+  if (rc != EA_OK) return rc;
+  return ea::ceva_sdecode_advance(const_cast<int32_t*>(g->pos), nullptr, g->B, g->T_new, g->cap, (hipStream_t)stream);
+}
+
+int32_t ea_softmax_sdecode_parts(int32_t B, int32_t H, int32_t cap, int32_t cus) {
+  if (B <= 0 || H <= 0 || cap <= 0 || cus < 0) return EA_E_BADARG;
+  return ea::softmax_sdecode_parts((long)B * H, cap, cus > 0 ? cus : ea_device_cus());
 }
 
 }  // extern "C"

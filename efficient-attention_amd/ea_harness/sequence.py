@@ -360,11 +360,10 @@ class DecoderStack(nn.Module):
         biases, 2 (C F + F + F C + C) bytes per layer, taken here once: a capture fixes the weights, and
         `refresh_decoding_weights` re-reads them.  `max_tokens` may not pass the position table.
         Keyword-only, on top of these: `hold_vocab=False` (see `_hold_vocab_option`).
-        On a stack built with attn_name="softmax": NotImplementedError, as for everything that needs a decoding state."""
+        On a stack built with attn_name="softmax": NotImplementedError; that stack's state is made by `init_kv_decoding`."""
         if self.attn_name == "softmax":
-            raise NotImplementedError("softmax decoding is not built: a DecoderStack(attn_name='softmax') has no decoding state "
-                                      "(KV-cache decoding is a follow-up); forward, evaluate, loss, adaptive_loss and "
-                                      "rows_logprobs run on it")
+            raise NotImplementedError("softmax decoding is not built by init_decoding: its parameters are causal EVA's; the "
+                                      "state of a DecoderStack(attn_name='softmax') is a KV cache, made by init_kv_decoding")
         if hold_weights:
             self.layers[0].self_attn._check_hold_projections(True, dtype)
         if int(max_tokens) > self.positions.shape[0]:
@@ -391,6 +390,47 @@ class DecoderStack(nn.Module):
         state = DecodingState(incremental, ffn, options)
         self._load_held_ffn(state)
         return state
+
+    @_hold_vocab_option
+    def init_kv_decoding(self, batch_size, max_tokens, dtype, device, hold_weights=True, kv_splits=0):
+        """The decoding state of a stack built with attn_name="softmax": one static KV cache per layer's attention, made by
+        `CausalSoftmaxAttention.init_kv_cache` with `kv_splits` handed on and `hold_projections=hold_weights`, and with
+        hold_weights the 16-bit fc1 / fc2 copies `init_decoding` holds -> a DecodingState.  `decode`, `generate`, the held
+        picks, sampling, `score` and `beam_search` run on it as on a causal EVA state; its `options` record that this
+        constructor made it (`made_by`), which is how scratch states are rebuilt.  bf16 / fp16 only; one token count for the
+        whole batch.  Keyword-only, on top of these: `hold_vocab=False` (see `_hold_vocab_option`).
+        On a causal_eva stack: NotImplementedError; that stack's state is made by `init_decoding`."""
+        if self.attn_name != "softmax":
+            raise NotImplementedError("init_kv_decoding makes the KV caches of a DecoderStack(attn_name='softmax'); the state "
+                                      "of a %s stack is made by init_decoding" % self.attn_name)
+        if int(max_tokens) > self.positions.shape[0]:
+            raise ValueError("max_tokens %d passes the %d positions of the table (max_positions)"
+                             % (int(max_tokens), self.positions.shape[0]))
+        incremental = {}
+        for layer in self.layers:
+            layer.self_attn.init_kv_cache(incremental, batch_size, max_tokens, dtype, device, kv_splits=kv_splits,
+                                          hold_projections=hold_weights)
+        ffn = None
+        if hold_weights:
+            ffn = [tuple(torch.empty(p.shape, dtype=dtype, device=device)
+                         for p in (layer.fc1.weight, layer.fc1.bias, layer.fc2.weight, layer.fc2.bias)) for layer in self.layers]
+        options = dict(batch_size=int(batch_size), max_tokens=int(max_tokens), dtype=dtype, device=device,
+                       hold_weights=bool(hold_weights), kv_splits=kv_splits, per_sequence=False, made_by="init_kv_decoding")
+        state = DecodingState(incremental, ffn, options)
+        self._load_held_ffn(state)
+        return state
+    init_kv_decoding.__signature__ = inspect.signature(init_kv_decoding).replace(parameters=list(
+        inspect.signature(init_kv_decoding).parameters.values()) + [inspect.Parameter("hold_vocab", inspect.Parameter.KEYWORD_ONLY,
+                                                                                       default=False)])
+
+    def _make_decoding(self, *args, **options):
+        """A state made on this stack's behalf -- inside `score`, `generate` and `beam_search`, and the scratch states rebuilt
+        from another state's `options` -- by the constructor the stack's attention has: `init_decoding` with the arguments as
+        given, or `init_kv_decoding` with those of them it takes."""
+        if self.attn_name != "softmax":
+            return self.init_decoding(*args, **options)
+        takes = ("batch_size", "max_tokens", "dtype", "device", "hold_weights", "kv_splits", "hold_vocab")
+        return self.init_kv_decoding(*args, **{k: v for k, v in options.items() if k in takes})
 
     def _load_held_ffn(self, state):
         if state.ffn is None:
@@ -747,9 +787,9 @@ class DecoderStack(nn.Module):
         with torch.no_grad(), ctx:
             if state is None:
                 if self.is_adaptive:
-                    state = self.init_adaptive_decoding(self.init_decoding(B, T - 1, dtype, tokens.device))
+                    state = self.init_adaptive_decoding(self._make_decoding(B, T - 1, dtype, tokens.device))
                 else:
-                    state = self.init_logprobs(self.init_decoding(B, T - 1, dtype, tokens.device, hold_vocab=True))
+                    state = self.init_logprobs(self._make_decoding(B, T - 1, dtype, tokens.device, hold_vocab=True))
             elif state.scorer is None and state.adaptive is None:
                 raise RuntimeError("score needs a decoding state with a scorer: init_logprobs(state)")
             fed = tokens[:, :-1]
@@ -1155,9 +1195,9 @@ class DecoderStack(nn.Module):
         with torch.no_grad(), ctx:
             if state is None:
                 if self.is_adaptive:
-                    state = self.init_adaptive_decoding(self.init_decoding(M, P + max(max_new, 1), dtype, prompt.device))
+                    state = self.init_adaptive_decoding(self._make_decoding(M, P + max(max_new, 1), dtype, prompt.device))
                 else:
-                    state = self.init_decoding(M, P + max(max_new, 1), dtype, prompt.device, hold_vocab=True)
+                    state = self._make_decoding(M, P + max(max_new, 1), dtype, prompt.device, hold_vocab=True)
             if state.beam is None:
                 self.init_beam_search(state, W, eos_idx, max_new, len_penalty)
                 if limits is not None and any(limits):
@@ -1188,7 +1228,7 @@ class DecoderStack(nn.Module):
                 self.reorder_decoding_state(st, st.beam.parent)
 
             def scratch():                                                   # (the table is shared, the beam buffers are not)
-                st = self.init_decoding(**dict(state.options, max_tokens=1, hold_vocab=False))
+                st = self._make_decoding(**dict(state.options, max_tokens=1, hold_vocab=False))
                 st.vocab, st.vocab_ws, st.adaptive = state.vocab, state.vocab_ws, state.adaptive
                 self.init_beam_search(st, W, eos_idx, max_new, len_penalty)
                 if bm.constraint is None:
@@ -1241,7 +1281,7 @@ class DecoderStack(nn.Module):
         ctx, dtype = self._decoding_context()
         with torch.no_grad(), ctx:
             if state is None:
-                state = self.init_decoding(B, P + n_new, dtype, prompt.device, hold_weights=dtype != torch.float32)
+                state = self._make_decoding(B, P + n_new, dtype, prompt.device, hold_weights=dtype != torch.float32)
             last = self._prefill(prompt, state)
             tok_in = pick(last)                                              # [1, B]: the step's static input
             out = torch.empty((B, n_new), dtype=torch.long, device=prompt.device)
@@ -1262,7 +1302,7 @@ class DecoderStack(nn.Module):
                 return y
 
             def scratch():
-                return self.init_decoding(**dict(state.options, max_tokens=1, hold_vocab=False))
+                return self._make_decoding(**dict(state.options, max_tokens=1, hold_vocab=False))
             self._run_steps(step, state, n_new, graph, tok_in, scratch, pick, record)
         if logps is not None:
             return (out, rows, logps) if return_rows else (out, logps)

@@ -126,6 +126,14 @@ _FA = ctypes.POINTER(ea_f32_attn)
 _DG = ctypes.POINTER(ea_ceva_dec_geom)
 _SDG = ctypes.POINTER(ea_ceva_sdec_geom)
 
+
+class ea_softmax_sdec_geom(ctypes.Structure):
+    _fields_ = [("B", ctypes.c_int32), ("H", ctypes.c_int32), ("D", ctypes.c_int32), ("dtype", ctypes.c_int32),
+                ("T_new", ctypes.c_int32), ("cap", ctypes.c_int32), ("pos", ctypes.c_void_p), ("status", ctypes.c_void_p)]
+
+
+_SMG = ctypes.POINTER(ea_softmax_sdec_geom)
+
 # name -> argtypes; every symbol include/ea_hip.h declares (tests check the list is complete)
 SIGNATURES = {
     "ea_eva_chunk_mean_fwd": [_G, _T, _T, _P, _P, _P, _P],
@@ -341,6 +349,12 @@ SIGNATURES = {
     "ea_softmax_causal_fwd": [_I, _I, _I, _I, _I, _F, _T, _T, _T, _P, _T, _P, _P, _F, _I, _P],
     "ea_softmax_causal_bwd": [_I, _I, _I, _I, _I, _F, _T, _T, _T, _P, _T, _T, _P, _P, _T, _T, _T, _P, _F, _I, _P],
     "ea_softmax_causal_tiles": [_I, _I, _I, _I, _I, _I, _I],
+    "ea_softmax_sdecode_append": [_SMG, _P, _P, _T, _T, _P, _P],
+    "ea_softmax_sdecode_attn_split": [_SMG, _T, _T, _T, _P, _T, _I, _P, _P],
+    "ea_softmax_sdecode_merge": [_SMG, _T, _I, _P, _P],
+    "ea_softmax_sdecode_attn_mm": [_SMG, _T, _T, _T, _P, _T, _P],
+    "ea_softmax_sdecode_advance": [_SMG, _P],
+    "ea_softmax_sdecode_parts": [_I, _I, _I, _I],
     "ea_window_bias_ld": [_G],
     "ea_window_bwd_parts": [_G],
     "ea_window_bwd_needs_bias_t": [_G],

@@ -8,16 +8,24 @@ its initialisation, time-first `forward(query, key, value, key_padding_mask=None
 
 The core runs in libea_hip.so (csrc/ea_softmax_causal.hip through `_ops.CausalSoftmaxAttnFn`): causality is built into the
 kernels' schedule, no [T, T] mask or score tensor exists, attention dropout is a keep mask drawn here and applied in the kernels.
-There is no CPU fallback.  Not built (NotImplementedError): token-by-token decoding with an incremental state, quantization
-noise, cross attention, fp32 activations outside autocast.  A query whose visible keys are all padded (left padding) gives NaN,
+There is no CPU fallback.  Incremental decoding runs on a static, graph-capturable KV cache made by `init_kv_cache`
+(csrc/ea_softmax_decode.hip); an incremental state without one raises.  Not built (NotImplementedError): quantization
+noise, cross attention, fp32 activations outside autocast, and for decoding per-sequence token counts, a rolling or windowed
+cache and fp32 caches (follow-ups).  A query whose visible keys are all padded (left padding) gives NaN,
 as in the reference.
 """
+import ctypes
 import math
+import numbers
+import uuid
 
 import torch
 import torch.nn as nn
 
 from . import _ops
+from ._ceva_decode import CevaDecoding, _LINEAR_MAX_ROWS, _SPLIT_MAX_PARTS, _SPLIT_MAX_STEP
+
+_KV_BATCH_FIRST = ("kv", "pad")      # what a beam reorder permutes; the counters are shared and the rest is step-invariant
 
 
 class CausalSoftmaxAttention(nn.Module):
@@ -37,6 +45,7 @@ class CausalSoftmaxAttention(nn.Module):
         self.out_proj = nn.Linear(embed_dim, embed_dim, bias=bias)
         self.reset_parameters()
         self._keep_mask_fn = None                       # tests: the keep decisions of a fixture instead of bernoulli_
+        self._incremental_state_id = str(uuid.uuid4())  # fairseq's protocol: this module's own key of an incremental state
 
     def reset_parameters(self):
         """CausalEVAttention's (fairseq's, for equal q / k / v sizes): xavier with gain 1 / sqrt(2) on q / k / v."""
@@ -90,8 +99,11 @@ class CausalSoftmaxAttention(nn.Module):
         attn_mask: None or the standard future mask (causality is built in; anything else raises).
         Returns (out [T, B, C], None)."""
         if incremental_state is not None:
-            raise NotImplementedError("softmax decoding is not built: CausalSoftmaxAttention has no incremental state "
-                                      "(KV-cache decoding); run the full causal path")
+            buf = self._get_input_buffer(incremental_state)
+            if "kv" not in buf:
+                raise NotImplementedError("softmax decoding is not built for an incremental state without a KV cache: "
+                                          "CausalSoftmaxAttention has no grown-on-demand state; make it with init_kv_cache")
+            return self._decode(query, key, value, key_padding_mask, incremental_state, buf, need_weights, attn_mask)
         if self.q_noise > 0:
             raise NotImplementedError("quantization noise (q_noise > 0) is not built for CausalSoftmaxAttention")
         if not self.self_attention or (key is not None and key is not query) or (value is not None and value is not query):
@@ -118,3 +130,211 @@ class CausalSoftmaxAttention(nn.Module):
         if not torch.is_autocast_enabled() and y.dtype != query.dtype:
             y = y.to(query.dtype)
         return y.contiguous(), None
+
+    # ---- incremental decoding on a static KV cache ------------------------------------------------------------------------------
+    def _get_input_buffer(self, incremental_state):
+        found = (incremental_state or {}).get(self._incremental_state_id + ".kv_state")
+        return {} if found is None else found
+
+    def _kv_buffer(self, incremental_state, what):
+        buf = self._get_input_buffer(incremental_state)
+        if "kv" not in buf:
+            raise RuntimeError("%s needs a KV cache (init_kv_cache); this incremental state holds none" % what)
+        return buf
+
+    # what a state that holds its projections shares with CausalEVAttention's: the checks, the copies and the two launches
+    _check_hold_projections = CevaDecoding._check_hold_projections
+    _load_held_projections = CevaDecoding._load_held_projections
+    _held_x = staticmethod(CevaDecoding._held_x)
+    _held_linear = CevaDecoding._held_linear
+    _held_gemm = CevaDecoding._held_gemm
+    decoding_state_nbytes = CevaDecoding.decoding_state_nbytes
+    static_decoding_overflowed = CevaDecoding.static_decoding_overflowed
+
+    def init_kv_cache(self, incremental_state, batch_size, max_tokens, dtype, device, kv_splits=0, hold_projections=False):
+        """Allocate, once, every buffer a decoding step touches, under this module's key of `incremental_state`: every later
+        `forward(..., incremental_state=incremental_state)` is then a decoding step of T_new tokens -- a prompt, a piece of one,
+        a single token -- that can be captured into a graph and replayed: the token count lives in device memory, the kernels
+        read and advance it, nothing is read back and nothing is allocated but the step's outputs.
+            kv        [B, 2, h, cap, d]   `dtype` (bf16 or fp16), cap = max_tokens: a head's keys, and its values, are one stream
+            pad       [B, cap]            uint8, 1 = padded key
+            pos       [1]                 int32 on the device: tokens decoded so far (one count for the whole batch)
+            status    [1]                 int32 on the device: 1 once a step would have passed cap
+            split_ws  [B, h, 8, P, d + 4] fp32, with P > 1: the partials of a step of at most 8 tokens (scratch)
+        A step is the projection, ea_softmax_sdecode_append, the attention, ea_softmax_sdecode_advance and out_proj.  The
+        attention of a step of at most 8 tokens is ea_softmax_sdecode_attn_split, P workgroups per (b, h) sharing the cache's
+        64-key tiles (with P > 1 followed by ea_softmax_sdecode_merge); a longer step runs ea_softmax_sdecode_attn_mm on the
+        matrix cores.  `kv_splits` is P: 0 takes ea_softmax_sdecode_parts' choice for this device, an int in [1, 64] fixes it.
+        The last T_new columns of `key_padding_mask`, in either of fairseq's shapes, are the step's flags.  A step that does
+        not fit writes nothing, sets `status` and returns NaN rows (`static_decoding_overflowed`); eagerly it raises first.
+        `hold_projections=True`: the state also holds 16-bit `w_qkv`, `b_qkv`, `w_out`, `b_out` and `proj_rows [64, 3 C]`, as
+        CausalEVAttention's states do; a step of at most 64 rows runs both projections on ea_ceva_sdecode_linear, a larger
+        one the library GEMM on the held operands; `refresh_decoding_weights` re-reads them.
+        Refuses fp32 caches, CPU devices, training mode, q_noise > 0 and head dims outside 32 / 64 / 128.  Per-sequence token
+        counts, a rolling or windowed cache and fp32 decoding are follow-ups."""
+        nv = _ops.nv
+        if not self.self_attention:
+            raise NotImplementedError("incremental decoding of encoder-decoder attention")
+        if self.training:
+            raise NotImplementedError("incremental decoding in training mode")
+        if self.q_noise > 0:
+            raise NotImplementedError("quantization noise (q_noise > 0) is not built for CausalSoftmaxAttention")
+        if self.head_dim not in (32, 64, 128):
+            raise NotImplementedError("head dim %d: the softmax decoding kernels are built for 32, 64 and 128" % self.head_dim)
+        if dtype == torch.float32:
+            raise NotImplementedError("fp32 decoding is not built for CausalSoftmaxAttention (a follow-up): the KV cache holds "
+                                      "bf16 or fp16 rows")
+        if dtype not in (torch.bfloat16, torch.float16):
+            raise ValueError("the KV cache holds bf16 or fp16 rows, not %s" % (dtype,))
+        device = torch.device(device)
+        nv.require_cuda(torch.empty(0, device=device), "the KV cache")
+        B, cap = int(batch_size), int(max_tokens)
+        if B <= 0 or cap <= 0:
+            raise ValueError("the KV cache needs batch_size > 0 and max_tokens > 0, got %d, %d" % (B, cap))
+        P = kv_splits
+        if isinstance(P, bool) or not isinstance(P, numbers.Integral) or not 0 <= P <= _SPLIT_MAX_PARTS:
+            raise ValueError("kv_splits must be 0 (the planner's choice) or an int in [1, %d], got %r" % (_SPLIT_MAX_PARTS, P))
+        self._check_hold_projections(hold_projections, dtype)
+        h, d, C = self.num_heads, self.head_dim, self.embed_dim
+        if P == 0:
+            with torch.cuda.device(device):
+                P = nv.lib().ea_softmax_sdecode_parts(B, h, cap, 0)
+            if P < 1:
+                raise RuntimeError("ea_softmax_sdecode_parts refused (%d, %d, %d): %d" % (B, h, cap, P))
+        state = {
+            "kv": torch.zeros((B, 2, h, cap, d), dtype=dtype, device=device),
+            "pad": torch.zeros((B, cap), dtype=torch.uint8, device=device),
+            "pos": torch.zeros((1,), dtype=torch.int32, device=device),
+            "status": torch.zeros((1,), dtype=torch.int32, device=device),
+        }
+        if P > 1:
+            state["split_ws"] = torch.zeros((B, h, _SPLIT_MAX_STEP, P, d + 4), dtype=torch.float32, device=device)
+        if hold_projections:
+            qkv_b, out_b = self.q_proj.bias is not None, self.out_proj.bias is not None
+            state["proj_rows"] = torch.zeros((_LINEAR_MAX_ROWS, 3 * C), dtype=dtype, device=device)
+            state["w_qkv"] = torch.empty((3 * C, C), dtype=dtype, device=device)
+            state["b_qkv"] = torch.empty((3 * C,), dtype=dtype, device=device) if qkv_b else None
+            state["w_out"] = torch.empty((C, C), dtype=dtype, device=device)
+            state["b_out"] = torch.empty((C,), dtype=dtype, device=device) if out_b else None
+            self._load_held_projections(state)
+        incremental_state[self._incremental_state_id + ".kv_state"] = state
+        # host side: the shadow count of EAGER steps (a replay advances only the device count), for the eager overflow check
+        incremental_state[self._incremental_state_id + ".kv_static"] = {"count": 0, "kv_splits": P}
+        return incremental_state
+
+    def refresh_decoding_weights(self, incremental_state):
+        """Re-read the projection parameters into what a state made with `hold_projections=True` holds of them, in place and by
+        device ops only: a step captured before sees the new weights.  A state that holds none has nothing to refresh."""
+        buf = self._kv_buffer(incremental_state, "refresh_decoding_weights")
+        if "w_qkv" in buf:
+            self._load_held_projections(buf)
+        return incremental_state
+
+    def reorder_incremental_state(self, incremental_state, new_order):
+        """Permute the batch rows of `kv` and `pad`, in place: the pointers a captured step holds stay valid."""
+        buf = self._get_input_buffer(incremental_state)
+        for k in _KV_BATCH_FIRST if "kv" in buf else ():
+            buf[k].copy_(buf[k].index_select(0, new_order))
+        return incremental_state
+
+    def reset_decoding_rows(self, incremental_state, rows):
+        """Restart the state: with one token count for the whole batch that is all rows or none.  `rows` must name every batch
+        row (`pos` and `status` back to 0, by device ops; no cache byte is cleared, nothing at or past the count is read) or
+        be empty; a subset needs per-sequence counts, which are a follow-up."""
+        buf = self._kv_buffer(incremental_state, "reset_decoding_rows")
+        idx = sorted(set(torch.as_tensor(rows).reshape(-1).tolist()))
+        if not idx:
+            return incremental_state
+        if idx != list(range(buf["kv"].shape[0])):
+            raise NotImplementedError("reset_decoding_rows of a subset of the batch: the KV cache has one token count for the "
+                                      "whole batch (per-sequence counts are a follow-up)")
+        buf["pos"].zero_()
+        buf["status"].zero_()
+        incremental_state[self._incremental_state_id + ".kv_static"]["count"] = 0
+        return incremental_state
+
+    def decoding_positions(self, incremental_state):
+        """The tokens decoded so far per batch row, a [B] int32 copy on the host (the one count repeated).  Reads back."""
+        buf = self._kv_buffer(incremental_state, "decoding_positions")
+        return buf["pos"].expand(buf["kv"].shape[0]).cpu().clone()
+
+    def decoding_positions_tensor(self, incremental_state):
+        """The device tensor the state counts in, `pos [1]` int32, itself: no read-back, a captured step may index with it."""
+        return self._kv_buffer(incremental_state, "decoding_positions_tensor")["pos"]
+
+    def _decode(self, query, key, value, key_padding_mask, incremental_state, state, need_weights, attn_mask):
+        """One decoding step on the state of `init_kv_cache`: query [T_new, B, C] -> (out [T_new, B, C], None)."""
+        nv = _ops.nv
+        if self.training:
+            raise NotImplementedError("incremental decoding in training mode")
+        if not self.self_attention or (key is not None and key is not query) or (value is not None and value is not query):
+            raise NotImplementedError("incremental decoding of encoder-decoder attention")
+        if need_weights:
+            raise NotImplementedError("need_weights: the decoding kernels never form the attention weights")
+        if attn_mask is not None:
+            raise ValueError("attn_mask in a decoding step: causality against the cache is built into the kernels")
+        nv.require_cuda(query, "query")
+        T_new, B, C = query.shape
+        kv, pad = state["kv"], state["pad"]
+        h, d, cap = self.num_heads, self.head_dim, kv.shape[3]
+        if kv.shape[0] != B:
+            raise RuntimeError("the KV cache holds batch %d, the step has %d" % (kv.shape[0], B))
+        if key_padding_mask is not None and (key_padding_mask.dim() != 2 or key_padding_mask.shape[0] != B
+                                             or key_padding_mask.shape[1] < T_new):
+            raise ValueError("key_padding_mask %s does not cover the %d new positions of a batch of %d"
+                             % (tuple(key_padding_mask.shape), T_new, B))
+        static = incremental_state[self._incremental_state_id + ".kv_static"]
+        capturing = torch.cuda.is_current_stream_capturing()
+        if not capturing and static["count"] + T_new > cap:
+            raise RuntimeError("the KV cache is full: %d of its %d tokens decoded, the step adds %d "
+                               "(init_kv_cache(max_tokens=...))" % (static["count"], cap, T_new))
+        dev = query.device
+        held = "w_qkv" in state
+        held_rows = held and T_new * B <= _LINEAR_MAX_ROWS
+        if held_rows:
+            qkv_new = self._held_linear(query.reshape(T_new * B, C), state["w_qkv"], state["b_qkv"], state["proj_rows"])
+        elif held:
+            qkv_new = self._held_gemm(query, state["w_qkv"], state["b_qkv"]).contiguous()
+        else:
+            with torch.no_grad():
+                qkv_new = self._project(query)
+            if qkv_new.dtype != kv.dtype:                          # (an fp32 step outside autocast: rounded, with the one-time warning)
+                qkv_new = _ops.to_io_dtype(qkv_new).to(kv.dtype)
+            qkv_new = qkv_new.contiguous()
+        step_pad = None
+        if key_padding_mask is not None:
+            step_pad = key_padding_mask[:, -T_new:].to(device=dev, dtype=torch.uint8).contiguous()
+        geom = nv.ea_softmax_sdec_geom(B, h, d, nv.io_dtype(kv), T_new, cap, state["pos"].data_ptr(), state["status"].data_ptr())
+        g = ctypes.byref(geom)
+        rows = qkv_new.view(-1)[:T_new * B * 3 * C].view(T_new, B, 3, h, d)      # (proj_rows: the step's rows lead the buffer)
+        tq = nv.t4(rows[:, :, 0].permute(1, 2, 0, 3))              # [B, h, T_new, d] view of the time-first rows
+        tk, tv = nv.t4(kv[:, 0]), nv.t4(kv[:, 1])
+        out = torch.empty((T_new, B, h, d), dtype=kv.dtype, device=dev)
+        to = nv.t4(out.permute(1, 2, 0, 3))
+        views = (ctypes.byref(tq), ctypes.byref(tk), ctypes.byref(tv), nv.ptr(pad), ctypes.byref(to))
+        st = nv.stream()
+        nv.call("ea_softmax_sdecode_append", g, nv.ptr(rows), nv.ptr(step_pad), views[1], views[2], nv.ptr(pad), st)
+        if T_new <= _SPLIT_MAX_STEP:
+            ws = state.get("split_ws")
+            parts = 1 if ws is None else ws.shape[3]
+            nv.call("ea_softmax_sdecode_attn_split", g, *views, parts, nv.ptr(ws), st)
+            if parts > 1:
+                nv.call("ea_softmax_sdecode_merge", g, views[4], parts, nv.ptr(ws), st)
+        else:
+            nv.call("ea_softmax_sdecode_attn_mm", g, *views, st)
+        nv.call("ea_softmax_sdecode_advance", g, st)
+        if not capturing:                                          # (a replay advances only the device count)
+            static["count"] += T_new
+        ydtype = torch.get_autocast_dtype("cuda") if torch.is_autocast_enabled() else query.dtype
+        if held_rows:
+            ytype = ydtype if ydtype in (kv.dtype, torch.float32) else torch.float32
+            y = torch.empty((T_new, B, C), dtype=ytype, device=dev)
+            self._held_linear(out.view(T_new * B, C), state["w_out"], state["b_out"], y.view(T_new * B, C))
+        elif held:
+            y = self._held_gemm(out.view(T_new, B, C), state["w_out"], state["b_out"])
+        else:
+            with torch.no_grad():
+                y = _ops.linear(out.view(T_new, B, C), self.out_proj)
+            if torch.is_autocast_enabled():
+                return y.contiguous(), None
+        return (y if y.dtype == ydtype else y.to(ydtype)).contiguous(), None

@@ -400,6 +400,47 @@ int ea_softmax_causal_bwd(int32_t B, int32_t H, int32_t N, int32_t D, int32_t dt
  * -> 1, 2 or 4, or EA_E_BADARG for a geometry the entries refuse, which not 0 / 1, or cus < 0. */
 int32_t ea_softmax_causal_tiles(int32_t which, int32_t B, int32_t H, int32_t N, int32_t D, int32_t has_keep, int32_t cus);
 
+/* ---- causal softmax, decoding against a static KV cache (CausalSoftmaxAttention.init_kv_cache; ea_softmax_decode.hip) ----
+ * Additive entries of ABI 38.  The cache is k, v [B, H, cap, D] rows of `dtype` (EA_BF16 | EA_F16; D 32, 64 or 128), handed
+ * over as ea_t4 views (the two halves of kv [B, 2, H, cap, D]), pad uint8 [B, cap] (1 = padded key) and the token count
+ * *pos, device int32 [1], which every launch of a step reads itself: a step can be captured into a graph and replayed.
+ * A step of T_new tokens is append, attention, advance, in that order on one stream:
+ *   ea_softmax_sdecode_append: rows *pos .. *pos + T_new - 1 of k and v from qkv_new [T_new * B, 3, H, D] (time-first rows,
+ *     read in place), and of pad from new_pad [B, T_new] (NULL: zeros).
+ *   attention: out[b, h, t] = softmax(q_t . k_j / sqrt(D) : j <= *pos + t, j not padded) v_j, fp32 softmax and accumulation;
+ *     q and out are [B, H, T_new, D] views.  A query whose visible keys are all padded gives NaN.
+ *     ea_softmax_sdecode_attn_split, T_new <= 8: grid (parts, B H); wave s of part p owns the 64-key tiles 4 p + s, + 4 parts, ..
+ *       of [0, *pos + T_new); vector arithmetic.  parts == 1: writes out.  parts > 1: writes, for every query, the unnormalised
+ *       (acc[D], max, sum) to ws, fp32 [B, H, 8, parts, D + 4], 16-byte aligned (a part without a tile: max = -inf, sum = 0),
+ *       and ea_softmax_sdecode_merge folds the parts into out with the arithmetic of ea_ceva_sdecode_merge.
+ *     ea_softmax_sdecode_attn_mm, any T_new >= 1: 64 queries per workgroup on mfma_f32_16x16x32; P is rounded to `dtype` for
+ *       P.V, the row sum is that of the unrounded weights; the error bound is ea_ceva_sdecode_attn_mm's.
+ *   ea_softmax_sdecode_advance: *pos += T_new.
+ * A step with *pos + T_new > cap writes no cache byte: *status = 1, its out rows are NaN, *pos stays.
+ * Every refusal comes before any launch.  EA_E_BADARG: g, a view, pad, pos or status NULL or misaligned; B, H, T_new or
+ * cap <= 0; cap < T_new; a dtype other than EA_BF16 / EA_F16; parts outside [1, 64] ([2, 64] for merge); ws NULL or not 16-byte
+ * aligned with parts > 1; T_new > 8 for attn_split and merge.  EA_E_UNSUPPORTED: D not 32 / 64 / 128. */
+typedef struct {
+  int32_t B, H, D;
+  int32_t dtype;             /* EA_BF16 | EA_F16: the cache rows, q and out */
+  int32_t T_new;             /* tokens per step: fixed for a captured step */
+  int32_t cap;               /* cache capacity in tokens */
+  const int32_t* pos;        /* device */
+  int32_t* status;           /* device */
+} ea_softmax_sdec_geom;
+int ea_softmax_sdecode_append(const ea_softmax_sdec_geom* g, const void* qkv_new, const uint8_t* new_pad, const ea_t4* k,
+                              const ea_t4* v, uint8_t* pad, void* stream);
+int ea_softmax_sdecode_attn_split(const ea_softmax_sdec_geom* g, const ea_t4* q, const ea_t4* k, const ea_t4* v,
+                                  const uint8_t* pad, const ea_t4* out, int32_t parts, float* ws, void* stream);
+int ea_softmax_sdecode_merge(const ea_softmax_sdec_geom* g, const ea_t4* out, int32_t parts, const float* ws, void* stream);
+int ea_softmax_sdecode_attn_mm(const ea_softmax_sdec_geom* g, const ea_t4* q, const ea_t4* k, const ea_t4* v,
+                               const uint8_t* pad, const ea_t4* out, void* stream);
+int ea_softmax_sdecode_advance(const ea_softmax_sdec_geom* g, void* stream);
+/* The parts ea_softmax_sdecode_attn_split takes by default; cus > 0: for a device of that many compute units, 0: the current
+ * device.  The smallest P with B H P >= 2 cus, clamped to [1, min(64, ceil(cap / 64))].  Pure: no environment knob.
+ * -> the count, or EA_E_BADARG for B, H, cap <= 0 or cus < 0. */
+int32_t ea_softmax_sdecode_parts(int32_t B, int32_t H, int32_t cap, int32_t cus);
+
 /* Randomized attention (randomized_attention.py:21-52) is two passes of the kernels above:
  *   mu = q + softmax(s q k^T) k (num_samples = -1) or q + k[index] with one index per query drawn
  *   from softmax(s q k^T) (ea_softmax_sample: Gumbel-max with counter-based noise from the 64-bit
