@@ -926,53 +926,105 @@ static int sdec_fill(const ea_softmax_sdec_geom* g, const ea_t4* q, const ea_t4*
   return EA_OK;
 }
 
-extern "C" {
-
-int ea_softmax_sdecode_append(const ea_softmax_sdec_geom* g, const void* qkv_new, const uint8_t* new_pad, const ea_t4* k,
-                              const ea_t4* v, uint8_t* pad, void* stream) {
+// One body per launch; ntok = NULL: the shared-count entry.  The _seq entries refuse a NULL or misaligned ntok themselves.
+static int sdec_append(const ea_softmax_sdec_geom* g, const void* qkv_new, const uint8_t* new_pad, const ea_t4* k,
+                       const ea_t4* v, uint8_t* pad, int32_t* ntok, void* stream) {
   const int rc = sdec_check(g);
   if (rc != EA_OK) return rc;
   if (!qkv_new || (uintptr_t)qkv_new % 16 || !view_ok(k, g->D, 2) || !view_ok(v, g->D, 2) || !pad) return EA_E_BADARG;
   ea::SdecAppP p = {};
   p.src = (const char*)qkv_new; p.src_pad = new_pad; p.k = sdec_mk(k); p.v = sdec_mk(v); p.pad = pad;
-  p.pos = g->pos; p.status = g->status;
+  p.pos = g->pos; p.status = g->status; p.ntok = ntok;
   p.B = g->B; p.H = g->H; p.D = g->D; p.T = g->T_new; p.cap = g->cap;
   return ea::softmax_sdecode_append(p, (hipStream_t)stream);
 }
 
-int ea_softmax_sdecode_attn_split(const ea_softmax_sdec_geom* g, const ea_t4* q, const ea_t4* k, const ea_t4* v,
-                                  const uint8_t* pad, const ea_t4* out, int32_t parts, float* ws, void* stream) {
+static int sdec_attn_split(const ea_softmax_sdec_geom* g, const ea_t4* q, const ea_t4* k, const ea_t4* v, const uint8_t* pad,
+                           const ea_t4* out, int32_t parts, float* ws, const int32_t* ntok, void* stream) {
   if (sdec_split_check(g, parts, 1, ws) != EA_OK) return EA_E_BADARG;
   ea::SdecP p = {};
   const int rc = sdec_fill(g, q, k, v, pad, out, p);
   if (rc != EA_OK) return rc;
-  p.parts = parts; p.ws = ws;
+  p.parts = parts; p.ws = ws; p.ntok = ntok;
   return ea::softmax_sdecode_attn_split(p, (hipStream_t)stream);
 }
 
 // the parts of ea_softmax_sdecode_attn_split folded by the causal EVA step's merge kernel: one workspace layout, one arithmetic
-int ea_softmax_sdecode_merge(const ea_softmax_sdec_geom* g, const ea_t4* out, int32_t parts, const float* ws, void* stream) {
+static int sdec_merge(const ea_softmax_sdec_geom* g, const ea_t4* out, int32_t parts, const float* ws, const int32_t* ntok,
+                      void* stream) {
   if (sdec_split_check(g, parts, 2, ws) != EA_OK) return EA_E_BADARG;
   const int rc = sdec_check(g);
   if (rc != EA_OK) return rc;
   if (!view_ok(out, g->D, 2)) return EA_E_BADARG;
   ea::DecMergeP p = {};
-  p.o = sdec_mk(out); p.ws = ws; p.pos = g->pos; p.ntok = nullptr;
+  p.o = sdec_mk(out); p.ws = ws; p.pos = g->pos; p.ntok = ntok;
   p.H = g->H; p.T = g->T_new; p.cap = g->cap; p.parts = parts;
   return ea::ceva_sdecode_merge(p, g->D, g->dtype, g->B * g->H, (hipStream_t)stream);
 }
 
-int ea_softmax_sdecode_attn_mm(const ea_softmax_sdec_geom* g, const ea_t4* q, const ea_t4* k, const ea_t4* v,
-                               const uint8_t* pad, const ea_t4* out, void* stream) {
+static int sdec_attn_mm(const ea_softmax_sdec_geom* g, const ea_t4* q, const ea_t4* k, const ea_t4* v, const uint8_t* pad,
+                        const ea_t4* out, const int32_t* ntok, void* stream) {
   ea::SdecP p = {};
   const int rc = sdec_fill(g, q, k, v, pad, out, p);
+  p.ntok = ntok;
   return rc != EA_OK ? rc : ea::softmax_sdecode_attn_mm(p, (hipStream_t)stream);
 }
 
-int ea_softmax_sdecode_advance(const ea_softmax_sdec_geom* g, void* stream) {
+static int sdec_advance(const ea_softmax_sdec_geom* g, const int32_t* ntok, void* stream) {
   const int rc = sdec_check(g);
   if (rc != EA_OK) return rc;
-  return ea::ceva_sdecode_advance(const_cast<int32_t*>(g->pos), nullptr, g->B, g->T_new, g->cap, (hipStream_t)stream);
+  return ea::ceva_sdecode_advance(const_cast<int32_t*>(g->pos), ntok, g->B, g->T_new, g->cap, (hipStream_t)stream);
+}
+
+static bool sdec_ntok_bad(const int32_t* ntok) { return !ntok || (uintptr_t)ntok % 4; }
+
+extern "C" {
+
+int ea_softmax_sdecode_append(const ea_softmax_sdec_geom* g, const void* qkv_new, const uint8_t* new_pad, const ea_t4* k,
+                              const ea_t4* v, uint8_t* pad, void* stream) {
+  return sdec_append(g, qkv_new, new_pad, k, v, pad, nullptr, stream);
+}
+
+int ea_softmax_sdecode_attn_split(const ea_softmax_sdec_geom* g, const ea_t4* q, const ea_t4* k, const ea_t4* v,
+                                  const uint8_t* pad, const ea_t4* out, int32_t parts, float* ws, void* stream) {
+  return sdec_attn_split(g, q, k, v, pad, out, parts, ws, nullptr, stream);
+}
+
+int ea_softmax_sdecode_merge(const ea_softmax_sdec_geom* g, const ea_t4* out, int32_t parts, const float* ws, void* stream) {
+  return sdec_merge(g, out, parts, ws, nullptr, stream);
+}
+
+int ea_softmax_sdecode_attn_mm(const ea_softmax_sdec_geom* g, const ea_t4* q, const ea_t4* k, const ea_t4* v,
+                               const uint8_t* pad, const ea_t4* out, void* stream) {
+  return sdec_attn_mm(g, q, k, v, pad, out, nullptr, stream);
+}
+
+int ea_softmax_sdecode_advance(const ea_softmax_sdec_geom* g, void* stream) { return sdec_advance(g, nullptr, stream); }
+
+// ---- per-sequence counts: g->pos and g->status are [B], ntok [B] is written by append and read by the rest ----
+int ea_softmax_sdecode_append_seq(const ea_softmax_sdec_geom* g, const void* qkv_new, const uint8_t* new_pad, const ea_t4* k,
+                                  const ea_t4* v, uint8_t* pad, int32_t* ntok, void* stream) {
+  return sdec_ntok_bad(ntok) ? EA_E_BADARG : sdec_append(g, qkv_new, new_pad, k, v, pad, ntok, stream);
+}
+
+int ea_softmax_sdecode_attn_split_seq(const ea_softmax_sdec_geom* g, const ea_t4* q, const ea_t4* k, const ea_t4* v,
+                                      const uint8_t* pad, const ea_t4* out, int32_t parts, float* ws, const int32_t* ntok,
+                                      void* stream) {
+  return sdec_ntok_bad(ntok) ? EA_E_BADARG : sdec_attn_split(g, q, k, v, pad, out, parts, ws, ntok, stream);
+}
+
+int ea_softmax_sdecode_merge_seq(const ea_softmax_sdec_geom* g, const ea_t4* out, int32_t parts, const float* ws,
+                                 const int32_t* ntok, void* stream) {
+  return sdec_ntok_bad(ntok) ? EA_E_BADARG : sdec_merge(g, out, parts, ws, ntok, stream);
+}
+
+int ea_softmax_sdecode_attn_mm_seq(const ea_softmax_sdec_geom* g, const ea_t4* q, const ea_t4* k, const ea_t4* v,
+                                   const uint8_t* pad, const ea_t4* out, const int32_t* ntok, void* stream) {
+  return sdec_ntok_bad(ntok) ? EA_E_BADARG : sdec_attn_mm(g, q, k, v, pad, out, ntok, stream);
+}
+
+int ea_softmax_sdecode_advance_seq(const ea_softmax_sdec_geom* g, const int32_t* ntok, void* stream) {
+  return sdec_ntok_bad(ntok) ? EA_E_BADARG : sdec_advance(g, ntok, stream);
 }
 
 int32_t ea_softmax_sdecode_parts(int32_t B, int32_t H, int32_t cap, int32_t cus) {

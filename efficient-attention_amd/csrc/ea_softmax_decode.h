@@ -17,6 +17,8 @@ struct SdecP {                // a step of T tokens at *pos on the cache k, v [B
   float scale;
   float* ws;                  // attn_split, parts > 1: fp32 [B,H,8,parts,D+4] partials (acc[D], max, sum, 2 unused), natural log
   int parts;
+  const int32_t* ntok;        // per-sequence counts: pos is [B] and ntok [B] holds each row's tokens of this step (written by
+                              // append); null = one shared count, every row takes all T tokens
 };
 
 struct SdecAppP {             // append: the step's K and V rows, and its pad flags, into the cache at rows *pos ..
@@ -27,8 +29,11 @@ struct SdecAppP {             // append: the step's K and V rows, and its pad fl
   const int32_t* pos;
   int32_t* status;            // set to 1 when the step would pass cap (nothing is written)
   int B, H, D, T, cap;
+  int32_t* ntok;              // per-sequence: [B], row b's tokens of this step = the positions before its first flag in src_pad;
+                              // pos and status are [B] then, and nothing is stored for the flagged positions.  null = shared
 };
 
+// every launch: ntok != null selects the per-sequence instance of its kernel
 int softmax_sdecode_append(const SdecAppP& p, hipStream_t st);
 // T <= 8; parts == 1: normalises and writes out itself; parts > 1: partials to ws, ceva_sdecode_merge folds them
 int softmax_sdecode_attn_split(const SdecP& p, hipStream_t st);

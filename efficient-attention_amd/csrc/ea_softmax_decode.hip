@@ -26,6 +26,14 @@
 // row sum is that of the unrounded weights.  A block's keys are [0, *pos + its last row]; a wave skips the tiles past its own
 // last query and compares key against query only in the tiles that pass its first query.  Step rows, not absolute positions,
 // are what is grouped by 16, so *pos is free.
+//
+// Per-sequence counts (SEQ, a compile-time flag of the three kernels, chosen by ntok != null; the shared-count instances are
+// the code they were): pos, status and ntok are [B].  Of the step's T positions row b takes the n_b before its first flag in
+// the step's pad columns (append finds n_b and writes ntok[b]); nothing is stored for the others and their out rows are zero;
+// query t < n_b sees keys j <= pos[b] + t; a row with pos[b] + n_b > cap alone writes nothing, gets status[b] = 1 and NaN rows,
+// and keeps pos[b].  Step<true, SEQ> (ea_ceva_decode.h) carries these rules; a workgroup has one b, so every exit is uniform.
+// A row's arithmetic is what it is decoded alone: its tiles, its wave and part assignment and its order of summation depend on
+// (pos[b], n_b) only.
 #include "ea_softmax_decode.h"
 #include "ea_lm_frag.h"
 
@@ -39,6 +47,17 @@ EA_DEV const char* sd_row(const DecT& t, int b, int h, int n) {
   return t.p + ((size_t)b * t.sb + (size_t)h * t.sh + (size_t)n * t.sn) * 2;
 }
 
+// rows lo .. hi - 1 of the output of (b, h) = x, by the whole workgroup
+template <typename E>
+EA_DEV void sd_fill(const SdecP& p, int b, int h, int lo, int hi, float x) {
+  const uint32_t w = pack2<E>(x, x);
+  const int cpr = p.D / 8;
+  for (int idx = (int)threadIdx.x; idx < (hi - lo) * cpr; idx += SD_NT) {
+    const int i = idx / cpr, c = idx - i * cpr;
+    stg16(const_cast<char*>(sd_row(p.o, b, h, lo + i)) + c * 16, u32x4{w, w, w, w});
+  }
+}
+
 // the T output rows of (b, h) = NaN: a step that does not fit
 template <typename E>
 EA_DEV void sd_refuse(const SdecP& p, int b, int h) {
@@ -50,14 +69,58 @@ EA_DEV void sd_refuse(const SdecP& p, int b, int h) {
   }
 }
 
+// The first flagged position of a row of T step flags (T when there is none): n_b.  Wave w takes the 16-byte loads
+// w 64 + lane, + 256, .. of the aligned middle of the row -- 1 KB per wave and load -- and stops at its first load with a
+// flag in it (a ballot: the exit is uniform over the wave, and what it has not read lies further on); the row's two ends,
+// up to 15 bytes each (a row of [B, T] starts at any address), go byte by byte.  Then a minimum over the wave by lane
+// exchanges and over the four waves through LDS (red: 4 ints).
+EA_DEV int sd_first_flag(const uint8_t* f, int T, int* red) {
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int head = min(T, (int)((16 - ((uintptr_t)f & 15)) & 15));
+  const int nvec = (T - head) / 16, tail = head + nvec * 16;
+  int first = T;
+  if (tid < head && f[tid]) first = tid;
+  if (tid < T - tail && f[tail + tid]) first = min(first, tail + tid);
+  for (int i0 = wave * 64; i0 < nvec; i0 += SD_NT) {                  // (i0 and nvec are uniform over the wave)
+    const int i = i0 + lane;
+    int at = 16;
+    if (i < nvec) {
+      const u32x4 u = ldg16(f + head + (size_t)i * 16);
+#pragma unroll
+      for (int c = 3; c >= 0; --c)
+        if (u[c]) at = c * 4 + (__builtin_ctz(u[c]) >> 3);
+    }
+    if (at < 16) first = min(first, head + i * 16 + at);
+    if (__ballot(at < 16)) break;
+  }
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) first = min(first, __shfl_xor(first, o));
+  if (lane == 0) red[wave] = first;
+  __syncthreads();
+  return min(min(red[0], red[1]), min(red[2], red[3]));
+}
+
 // ---- append: one workgroup per (step token, b) ----
+// SEQ: every workgroup of row b finds n_b from the row's flags itself (sd_first_flag: one 16-byte load per thread up to 4096
+// step tokens), so none waits for another and the step needs no launch in front of it; the one of t = 0 publishes it, also
+// when the row does not fit -- the attention kernels and advance decide that from pos[b] + ntok[b] as this kernel does.
+// The tokens it stores are unflagged by construction: their pad flag is 0.
+template <bool SEQ>
 __global__ __launch_bounds__(SD_NT) void sdec_append_kernel(const SdecAppP p) {
   const int t = (int)blockIdx.x, b = (int)blockIdx.y, tid = threadIdx.x;
-  const int t0 = *p.pos;
-  if (t0 + p.T > p.cap) {
-    if (t == 0 && b == 0 && tid == 0) *p.status = 1;
+  int own = p.T;
+  if constexpr (SEQ) {
+    __shared__ int red[SD_NT / 64];
+    if (p.src_pad) own = sd_first_flag(p.src_pad + (size_t)b * p.T, p.T, red);
+    if (t == 0 && tid == 0) p.ntok[b] = own;
+  }
+  const Step<true, SEQ> step(p.pos, b, own);
+  const int t0 = step.t0;
+  if (!step.fits(p.T, p.cap)) {
+    if (t == 0 && (SEQ || b == 0) && tid == 0) p.status[SEQ ? b : 0] = 1;
     return;
   }
+  if (SEQ && t >= own) return;                     // (uniform: one b per workgroup)
   const int cpr = p.D / 8, n = p.H * cpr;          // 16-byte pieces of a head's row, of a token's K (or V) row
   const char* src = p.src + ((size_t)t * p.B + b) * 3 * n * 16;
   for (int idx = tid; idx < 2 * n; idx += SD_NT) {
@@ -65,7 +128,7 @@ __global__ __launch_bounds__(SD_NT) void sdec_append_kernel(const SdecAppP p) {
     const u32x4 x = ldg16(src + ((size_t)(1 + kv) * n + hc) * 16);
     stg16(const_cast<char*>(sd_row(kv ? p.v : p.k, b, h, t0 + t)) + c * 16, x);
   }
-  if (tid == 0) p.pad[(size_t)b * p.cap + t0 + t] = p.src_pad ? (p.src_pad[(size_t)b * p.T + t] ? 1 : 0) : 0;
+  if (tid == 0) p.pad[(size_t)b * p.cap + t0 + t] = !SEQ && p.src_pad ? (p.src_pad[(size_t)b * p.T + t] ? 1 : 0) : 0;
 }
 
 // ---- attn_split ----
@@ -74,7 +137,11 @@ template <int U> struct SdBatch {                  // U rows of a lane: its 16-b
   uint32_t f[U];
 };
 
-template <typename E, int D, int TQ>
+// SEQ: t0 = pos[b], the row's nq = ntok[b] queries against its own tiles [0, pos[b] + nq); queries nq .. T - 1 are neither loaded
+// nor accumulated (the loops over t end at nq: a uniform branch) and their out rows are zero.  Part 0 writes the zero and the
+// NaN rows whatever `parts` is: ceva_merge_kernel leaves both alone and reads the workspace rows of t < nq only, which every
+// part writes -- (max = -inf, sum = 0) where it has no tile of this row.
+template <typename E, int D, int TQ, bool SEQ>
 __global__ __launch_bounds__(SD_NT) void sdec_split_kernel(const SdecP p) {
   constexpr int G = D / 8, R = 64 / G, U = 4, NB = SDEC_TILE / (R * U);      // lanes per row, rows per load, batches per tile
   __shared__ __attribute__((aligned(16))) float mo[4][TQ][D];
@@ -82,17 +149,22 @@ __global__ __launch_bounds__(SD_NT) void sdec_split_kernel(const SdecP p) {
   const int tid = threadIdx.x, lane = tid & 63, c = lane % G, r = lane / G;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int part = (int)blockIdx.x, b = (int)blockIdx.y / p.H, h = (int)blockIdx.y - b * p.H;
-  const int t0 = *p.pos;
-  if (t0 + p.T > p.cap) {                          // (one value for every thread of the step: uniform)
+  const Step<true, SEQ> step(p.pos, b, SEQ ? p.ntok[b] : 0);
+  const int t0 = step.t0, nq = step.n(p.T);        // (one value for every thread of the workgroup: every exit is uniform)
+  if (!step.fits(p.T, p.cap)) {
     if (part == 0) sd_refuse<E>(p, b, h);
     return;
   }
-  const int kend = t0 + p.T, ntiles = (kend + SDEC_TILE - 1) / SDEC_TILE;
+  if constexpr (SEQ) {
+    if (part == 0) sd_fill<E>(p, b, h, nq, p.T, 0.f);
+    if (nq == 0) return;                           // a row that sits the step out
+  }
+  const int kend = t0 + nq, ntiles = (kend + SDEC_TILE - 1) / SDEC_TILE;
   const float scale2 = p.scale * LOG2E;
   float q[TQ][8], m[TQ], l[TQ], acc[TQ][8];
 #pragma unroll
   for (int t = 0; t < TQ; ++t) {
-    const bool live = t < p.T;
+    const bool live = t < nq;
     const u32x4 w = ldg16(sd_row(p.q, b, h, live ? t : 0) + c * 16);
     unpack8<E>(live ? w : u32x4{0u, 0u, 0u, 0u}, q[t]);
     m[t] = -INFINITY; l[t] = 0.f;
@@ -127,6 +199,7 @@ __global__ __launch_bounds__(SD_NT) void sdec_split_kernel(const SdecP p) {
       const bool dead = j >= kend || x.f[u] != 0;
 #pragma unroll
       for (int t = 0; t < TQ; ++t) {
+        if (SEQ && t >= nq) break;
         float d = 0.f;
 #pragma unroll
         for (int e = 0; e < 8; ++e) d = fmaf(q[t][e], kf[e], d);
@@ -136,6 +209,7 @@ __global__ __launch_bounds__(SD_NT) void sdec_split_kernel(const SdecP p) {
     }
 #pragma unroll
     for (int t = 0; t < TQ; ++t) {
+      if (SEQ && t >= nq) break;
       float mb = s[t][0];
 #pragma unroll
       for (int u = 1; u < U; ++u) mb = fmaxf(mb, s[t][u]);
@@ -158,9 +232,11 @@ __global__ __launch_bounds__(SD_NT) void sdec_split_kernel(const SdecP p) {
       float vf[8];
       unpack8<E>(x.v[u], vf);
 #pragma unroll
-      for (int t = 0; t < TQ; ++t)
+      for (int t = 0; t < TQ; ++t) {
+        if (SEQ && t >= nq) break;
 #pragma unroll
         for (int e = 0; e < 8; ++e) acc[t][e] = fmaf(s[t][u], vf[e], acc[t][e]);
+      }
     }
   };
   SdBatch<U> xa, xb;
@@ -191,7 +267,7 @@ __global__ __launch_bounds__(SD_NT) void sdec_split_kernel(const SdecP p) {
   // ... and the four waves: thread = (query, four channels)
   constexpr int G4 = D / 4;
   const int t = tid / G4, c4 = (tid - t * G4) * 4;
-  if (t >= p.T || t >= TQ) return;
+  if (t >= nq || t >= TQ) return;
   float mx = ml[0][t][0];
 #pragma unroll
   for (int v = 1; v < 4; ++v) mx = fmaxf(mx, ml[v][t][0]);
@@ -216,7 +292,11 @@ __global__ __launch_bounds__(SD_NT) void sdec_split_kernel(const SdecP p) {
 }
 
 // ---- attn_mm ----
-template <typename E, int D>
+// SEQ: t0 = pos[b] and the row has nq = ntok[b] of the step's T rows.  The block first zeroes its rows from nq on -- all of
+// them when base >= nq, and then it exits before any tile is staged -- its keys end at pos[b] + min(nq, base + 64), a wave
+// whose 16 rows start at or past nq does no MFMA work, and the final store is guarded by i < nq.  The grid stays qt-descending:
+// heaviest-first by a row's true work (pos[b] + nq) would need a device-side sort of (qt, b), which is not built.
+template <typename E, int D, bool SEQ>
 __global__ __launch_bounds__(SD_NT, 2) void sdec_mm_kernel(const SdecP p) {
   constexpr int ROWB = D * 2, KS = D / 32, DT = D / 16, DQ = D / 4, TB = SDEC_TILE * ROWB;
   constexpr int CPR = D / 8, NCH = SDEC_TILE * CPR / SD_NT;
@@ -229,20 +309,25 @@ __global__ __launch_bounds__(SD_NT, 2) void sdec_mm_kernel(const SdecP p) {
   const int BH = p.B * p.H, nqt = (p.T + SDEC_TILE - 1) / SDEC_TILE;
   const int qt = nqt - 1 - (int)(blockIdx.x / BH), bh = (int)(blockIdx.x % BH);
   const int b = bh / p.H, h = bh - b * p.H;
-  const int t0 = *p.pos;
-  if (t0 + p.T > p.cap) {
+  const Step<true, SEQ> step(p.pos, b, SEQ ? p.ntok[b] : 0);
+  const int t0 = step.t0, nq = step.n(p.T);                            // (uniform over the workgroup: one b)
+  if (!step.fits(p.T, p.cap)) {
     if (qt == 0) sd_refuse<E>(p, b, h);
     return;
   }
   const int base = qt * SDEC_TILE;                                     // the block's first step row
-  const int kend = t0 + min(p.T, base + SDEC_TILE);                    // its keys are [0, kend)
+  if constexpr (SEQ) {
+    sd_fill<E>(p, b, h, max(base, nq), min(p.T, base + SDEC_TILE), 0.f);
+    if (base >= nq) return;
+  }
+  const int kend = t0 + min(nq, base + SDEC_TILE);                     // its keys are [0, kend)
   const int nt = (kend + SDEC_TILE - 1) / SDEC_TILE;
   const int ia = base + wave * 16;                                     // the wave's 16 step rows
-  const bool active = ia < p.T;
+  const bool active = ia < nq;
   const int i = ia + li;
-  const bool qv = i < p.T;
+  const bool qv = i < nq;
   const int tq = t0 + i;
-  const int wave_lo = t0 + ia, wave_hi = t0 + min(ia + 16, p.T) - 1;   // positions of its first and last query
+  const int wave_lo = t0 + ia, wave_hi = t0 + min(ia + 16, nq) - 1;    // positions of its first and last query
   typename E::x8 qf[KS];
   load_frag<E, KS>(qf, sd_row(p.q, b, h, qv ? i : 0), g, qv);
   const char* kb = sd_row(p.k, b, h, 0);
@@ -396,16 +481,20 @@ __global__ __launch_bounds__(SD_NT, 2) void sdec_mm_kernel(const SdecP p) {
 
 using SdKernel = void (*)(const SdecP);
 
-template <typename E, int D> SdKernel split_of(int T) {
-  return T <= 1 ? sdec_split_kernel<E, D, 1> : T <= 2 ? sdec_split_kernel<E, D, 2> : T <= 4 ? sdec_split_kernel<E, D, 4>
-                                                                                            : sdec_split_kernel<E, D, 8>;
+template <typename E, int D, bool SEQ> SdKernel split_of(int T) {
+  return T <= 1   ? sdec_split_kernel<E, D, 1, SEQ>
+         : T <= 2 ? sdec_split_kernel<E, D, 2, SEQ>
+         : T <= 4 ? sdec_split_kernel<E, D, 4, SEQ>
+                  : sdec_split_kernel<E, D, 8, SEQ>;
 }
-template <typename E> SdKernel split_of(int D, int T) {
-  return D == 32 ? split_of<E, 32>(T) : D == 64 ? split_of<E, 64>(T) : split_of<E, 128>(T);
+template <typename E, bool SEQ> SdKernel split_of(int D, int T) {
+  return D == 32 ? split_of<E, 32, SEQ>(T) : D == 64 ? split_of<E, 64, SEQ>(T) : split_of<E, 128, SEQ>(T);
 }
-template <typename E> SdKernel mm_of(int D) {
-  return D == 32 ? sdec_mm_kernel<E, 32> : D == 64 ? sdec_mm_kernel<E, 64> : sdec_mm_kernel<E, 128>;
+template <typename E> SdKernel split_of(int D, int T, bool seq) { return seq ? split_of<E, true>(D, T) : split_of<E, false>(D, T); }
+template <typename E, bool SEQ> SdKernel mm_of(int D) {
+  return D == 32 ? sdec_mm_kernel<E, 32, SEQ> : D == 64 ? sdec_mm_kernel<E, 64, SEQ> : sdec_mm_kernel<E, 128, SEQ>;
 }
+template <typename E> SdKernel mm_of(int D, bool seq) { return seq ? mm_of<E, true>(D) : mm_of<E, false>(D); }
 
 bool sd_geom_ok(const SdecP& p) {
   return (p.dtype == EA_BF16 || p.dtype == EA_F16) && (p.D == 32 || p.D == 64 || p.D == 128);
@@ -413,16 +502,17 @@ bool sd_geom_ok(const SdecP& p) {
 
 }  // namespace
 
-// (The C entry points have checked the pointers, the views and the geometry.)
+// (The C entry points have checked the pointers, the views and the geometry.)  SEQ follows the state: p.ntok != null.
 int softmax_sdecode_append(const SdecAppP& p, hipStream_t st) {
-  hipLaunchKernelGGL(sdec_append_kernel, dim3((unsigned)p.T, (unsigned)p.B), dim3(SD_NT), 0, st, p);
+  void (*kernel)(const SdecAppP) = p.ntok ? sdec_append_kernel<true> : sdec_append_kernel<false>;
+  hipLaunchKernelGGL(kernel, dim3((unsigned)p.T, (unsigned)p.B), dim3(SD_NT), 0, st, p);
   return (int)hipGetLastError();
 }
 
 int softmax_sdecode_attn_split(const SdecP& p, hipStream_t st) {
   if (!p.pos || !p.pad || p.parts < 1 || p.parts > 64 || p.T < 1 || p.T > SDEC_QMAX || (p.parts > 1 && !p.ws)) return EA_E_BADARG;
   if (!sd_geom_ok(p)) return EA_E_UNSUPPORTED;
-  const SdKernel kernel = p.dtype == EA_BF16 ? split_of<BF16>(p.D, p.T) : split_of<F16>(p.D, p.T);
+  const SdKernel kernel = p.dtype == EA_BF16 ? split_of<BF16>(p.D, p.T, p.ntok != nullptr) : split_of<F16>(p.D, p.T, p.ntok != nullptr);
   hipLaunchKernelGGL(kernel, dim3((unsigned)p.parts, (unsigned)(p.B * p.H)), dim3(SD_NT), 0, st, p);
   return (int)hipGetLastError();
 }
@@ -430,7 +520,7 @@ int softmax_sdecode_attn_split(const SdecP& p, hipStream_t st) {
 int softmax_sdecode_attn_mm(const SdecP& p, hipStream_t st) {
   if (!p.pos || !p.pad || p.T < 1) return EA_E_BADARG;
   if (!sd_geom_ok(p)) return EA_E_UNSUPPORTED;
-  const SdKernel kernel = p.dtype == EA_BF16 ? mm_of<BF16>(p.D) : mm_of<F16>(p.D);
+  const SdKernel kernel = p.dtype == EA_BF16 ? mm_of<BF16>(p.D, p.ntok != nullptr) : mm_of<F16>(p.D, p.ntok != nullptr);
   const size_t lds = (size_t)4 * SDEC_TILE * p.D * 2 + 2 * SDEC_TILE;
   if (const int e = ea_lds_limit(reinterpret_cast<const void*>(kernel), lds)) return e;
   const int nqt = (p.T + SDEC_TILE - 1) / SDEC_TILE;

@@ -392,13 +392,15 @@ class DecoderStack(nn.Module):
         return state
 
     @_hold_vocab_option
-    def init_kv_decoding(self, batch_size, max_tokens, dtype, device, hold_weights=True, kv_splits=0):
+    def init_kv_decoding(self, batch_size, max_tokens, dtype, device, hold_weights=True, kv_splits=0, *, per_sequence=False):
         """The decoding state of a stack built with attn_name="softmax": one static KV cache per layer's attention, made by
         `CausalSoftmaxAttention.init_kv_cache` with `kv_splits` handed on and `hold_projections=hold_weights`, and with
         hold_weights the 16-bit fc1 / fc2 copies `init_decoding` holds -> a DecodingState.  `decode`, `generate`, the held
         picks, sampling, `score` and `beam_search` run on it as on a causal EVA state; its `options` record that this
-        constructor made it (`made_by`), which is how scratch states are rebuilt.  bf16 / fp16 only; one token count for the
-        whole batch.  Keyword-only, on top of these: `hold_vocab=False` (see `_hold_vocab_option`).
+        constructor made it (`made_by`), which is how scratch states are rebuilt.  bf16 / fp16 only.  Keyword-only, on top of
+        the reported parameters: `hold_vocab=False` (see `_hold_vocab_option`) and `per_sequence=False`, handed on to every
+        layer's cache and recorded in `options`: True gives every batch row its own token count, and `generate`, `score` and
+        `beam_search` then take ragged right-padded rows as on a per-sequence causal EVA state.
         On a causal_eva stack: NotImplementedError; that stack's state is made by `init_decoding`."""
         if self.attn_name != "softmax":
             raise NotImplementedError("init_kv_decoding makes the KV caches of a DecoderStack(attn_name='softmax'); the state "
@@ -409,19 +411,21 @@ class DecoderStack(nn.Module):
         incremental = {}
         for layer in self.layers:
             layer.self_attn.init_kv_cache(incremental, batch_size, max_tokens, dtype, device, kv_splits=kv_splits,
-                                          hold_projections=hold_weights)
+                                          hold_projections=hold_weights, per_sequence=per_sequence)
         ffn = None
         if hold_weights:
             ffn = [tuple(torch.empty(p.shape, dtype=dtype, device=device)
                          for p in (layer.fc1.weight, layer.fc1.bias, layer.fc2.weight, layer.fc2.bias)) for layer in self.layers]
         options = dict(batch_size=int(batch_size), max_tokens=int(max_tokens), dtype=dtype, device=device,
-                       hold_weights=bool(hold_weights), kv_splits=kv_splits, per_sequence=False, made_by="init_kv_decoding")
+                       hold_weights=bool(hold_weights), kv_splits=kv_splits, per_sequence=per_sequence,
+                       made_by="init_kv_decoding")
         state = DecodingState(incremental, ffn, options)
         self._load_held_ffn(state)
         return state
+    # (the reported list: the positional interface and hold_vocab, what callers that pin it saw before per_sequence)
     init_kv_decoding.__signature__ = inspect.signature(init_kv_decoding).replace(parameters=list(
-        inspect.signature(init_kv_decoding).parameters.values()) + [inspect.Parameter("hold_vocab", inspect.Parameter.KEYWORD_ONLY,
-                                                                                       default=False)])
+        inspect.signature(init_kv_decoding).parameters.values())[:-1] + [inspect.Parameter("hold_vocab", inspect.Parameter.KEYWORD_ONLY,
+                                                                                            default=False)])
 
     def _make_decoding(self, *args, **options):
         """A state made on this stack's behalf -- inside `score`, `generate` and `beam_search`, and the scratch states rebuilt
@@ -429,7 +433,7 @@ class DecoderStack(nn.Module):
         given, or `init_kv_decoding` with those of them it takes."""
         if self.attn_name != "softmax":
             return self.init_decoding(*args, **options)
-        takes = ("batch_size", "max_tokens", "dtype", "device", "hold_weights", "kv_splits", "hold_vocab")
+        takes = ("batch_size", "max_tokens", "dtype", "device", "hold_weights", "kv_splits", "hold_vocab", "per_sequence")
         return self.init_kv_decoding(*args, **{k: v for k, v in options.items() if k in takes})
 
     def _load_held_ffn(self, state):

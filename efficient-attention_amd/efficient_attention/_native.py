@@ -355,6 +355,11 @@ SIGNATURES = {
     "ea_softmax_sdecode_attn_mm": [_SMG, _T, _T, _T, _P, _T, _P],
     "ea_softmax_sdecode_advance": [_SMG, _P],
     "ea_softmax_sdecode_parts": [_I, _I, _I, _I],
+    "ea_softmax_sdecode_append_seq": [_SMG, _P, _P, _T, _T, _P, _P, _P],
+    "ea_softmax_sdecode_attn_split_seq": [_SMG, _T, _T, _T, _P, _T, _I, _P, _P, _P],
+    "ea_softmax_sdecode_merge_seq": [_SMG, _T, _I, _P, _P, _P],
+    "ea_softmax_sdecode_attn_mm_seq": [_SMG, _T, _T, _T, _P, _T, _P, _P],
+    "ea_softmax_sdecode_advance_seq": [_SMG, _P, _P],
     "ea_window_bias_ld": [_G],
     "ea_window_bwd_parts": [_G],
     "ea_window_bwd_needs_bias_t": [_G],

@@ -10,11 +10,12 @@ The core runs in libea_hip.so (csrc/ea_softmax_causal.hip through `_ops.CausalSo
 kernels' schedule, no [T, T] mask or score tensor exists, attention dropout is a keep mask drawn here and applied in the kernels.
 There is no CPU fallback.  Incremental decoding runs on a static, graph-capturable KV cache made by `init_kv_cache`
 (csrc/ea_softmax_decode.hip); an incremental state without one raises.  Not built (NotImplementedError): quantization
-noise, cross attention, fp32 activations outside autocast, and for decoding per-sequence token counts, a rolling or windowed
-cache and fp32 caches (follow-ups).  A query whose visible keys are all padded (left padding) gives NaN,
+noise, cross attention, fp32 activations outside autocast, and for decoding a rolling or windowed cache and fp32 caches
+(follow-ups).  A query whose visible keys are all padded (left padding) gives NaN,
 as in the reference.
 """
 import ctypes
+import inspect
 import math
 import numbers
 import uuid
@@ -25,7 +26,9 @@ import torch.nn as nn
 from . import _ops
 from ._ceva_decode import CevaDecoding, _LINEAR_MAX_ROWS, _SPLIT_MAX_PARTS, _SPLIT_MAX_STEP
 
-_KV_BATCH_FIRST = ("kv", "pad")      # what a beam reorder permutes; the counters are shared and the rest is step-invariant
+# what a beam reorder permutes: the rest is step-invariant, and so are the counters unless the state counts per row
+_KV_BATCH_FIRST = ("kv", "pad")
+_PER_SEQUENCE = ("pos", "status", "ntok")
 
 
 class CausalSoftmaxAttention(nn.Module):
@@ -151,7 +154,8 @@ class CausalSoftmaxAttention(nn.Module):
     decoding_state_nbytes = CevaDecoding.decoding_state_nbytes
     static_decoding_overflowed = CevaDecoding.static_decoding_overflowed
 
-    def init_kv_cache(self, incremental_state, batch_size, max_tokens, dtype, device, kv_splits=0, hold_projections=False):
+    def init_kv_cache(self, incremental_state, batch_size, max_tokens, dtype, device, kv_splits=0, hold_projections=False, *,
+                      per_sequence=False):
         """Allocate, once, every buffer a decoding step touches, under this module's key of `incremental_state`: every later
         `forward(..., incremental_state=incremental_state)` is then a decoding step of T_new tokens -- a prompt, a piece of one,
         a single token -- that can be captured into a graph and replayed: the token count lives in device memory, the kernels
@@ -160,6 +164,7 @@ class CausalSoftmaxAttention(nn.Module):
             pad       [B, cap]            uint8, 1 = padded key
             pos       [1]                 int32 on the device: tokens decoded so far (one count for the whole batch)
             status    [1]                 int32 on the device: 1 once a step would have passed cap
+            ntok      [B]                 int32, per_sequence only: the tokens each row took from the last step (written by it)
             split_ws  [B, h, 8, P, d + 4] fp32, with P > 1: the partials of a step of at most 8 tokens (scratch)
         A step is the projection, ea_softmax_sdecode_append, the attention, ea_softmax_sdecode_advance and out_proj.  The
         attention of a step of at most 8 tokens is ea_softmax_sdecode_attn_split, P workgroups per (b, h) sharing the cache's
@@ -170,8 +175,16 @@ class CausalSoftmaxAttention(nn.Module):
         `hold_projections=True`: the state also holds 16-bit `w_qkv`, `b_qkv`, `w_out`, `b_out` and `proj_rows [64, 3 C]`, as
         CausalEVAttention's states do; a step of at most 64 rows runs both projections on ea_ceva_sdecode_linear, a larger
         one the library GEMM on the held operands; `refresh_decoding_weights` re-reads them.
-        Refuses fp32 caches, CPU devices, training mode, q_noise > 0 and head dims outside 32 / 64 / 128.  Per-sequence token
-        counts, a rolling or windowed cache and fp32 decoding are follow-ups."""
+        `per_sequence=True` (keyword-only; combines with `kv_splits` and `hold_projections`): `pos` and `status` are [B], every
+        batch row has its own count, as in CausalEVAttention's per-sequence states.  Of a step's T_new positions a row takes
+        those before its first flag in the step's `key_padding_mask` columns -- all without one, none when the first is
+        flagged: the row sits the step out -- so ragged prompts are prefilled right-padded, a finished row idles, and
+        `reset_decoding_rows` hands a row to a new sequence while a captured step keeps replaying.  Nothing is stored for the
+        other positions and their output rows are zero (before out_proj: its bias alone behind it).  Overflow is per row and
+        reported by `status` only: the host does not know the counts, so an eager step does not raise.  A row's outputs are
+        bit for bit those of the row decoded alone.  The step issues the `_seq` entry points.
+        Refuses fp32 caches, CPU devices, training mode, q_noise > 0 and head dims outside 32 / 64 / 128.  A rolling or
+        windowed cache and fp32 decoding are follow-ups."""
         nv = _ops.nv
         if not self.self_attention:
             raise NotImplementedError("incremental decoding of encoder-decoder attention")
@@ -186,6 +199,8 @@ class CausalSoftmaxAttention(nn.Module):
                                       "bf16 or fp16 rows")
         if dtype not in (torch.bfloat16, torch.float16):
             raise ValueError("the KV cache holds bf16 or fp16 rows, not %s" % (dtype,))
+        if not isinstance(per_sequence, bool):
+            raise TypeError("per_sequence must be a bool, got %r" % (per_sequence,))
         device = torch.device(device)
         nv.require_cuda(torch.empty(0, device=device), "the KV cache")
         B, cap = int(batch_size), int(max_tokens)
@@ -204,9 +219,11 @@ class CausalSoftmaxAttention(nn.Module):
         state = {
             "kv": torch.zeros((B, 2, h, cap, d), dtype=dtype, device=device),
             "pad": torch.zeros((B, cap), dtype=torch.uint8, device=device),
-            "pos": torch.zeros((1,), dtype=torch.int32, device=device),
-            "status": torch.zeros((1,), dtype=torch.int32, device=device),
+            "pos": torch.zeros((B if per_sequence else 1,), dtype=torch.int32, device=device),
+            "status": torch.zeros((B if per_sequence else 1,), dtype=torch.int32, device=device),
         }
+        if per_sequence:
+            state["ntok"] = torch.zeros((B,), dtype=torch.int32, device=device)
         if P > 1:
             state["split_ws"] = torch.zeros((B, h, _SPLIT_MAX_STEP, P, d + 4), dtype=torch.float32, device=device)
         if hold_projections:
@@ -219,8 +236,16 @@ class CausalSoftmaxAttention(nn.Module):
             self._load_held_projections(state)
         incremental_state[self._incremental_state_id + ".kv_state"] = state
         # host side: the shadow count of EAGER steps (a replay advances only the device count), for the eager overflow check
-        incremental_state[self._incremental_state_id + ".kv_static"] = {"count": 0, "kv_splits": P}
+        # (a per-sequence state: the host does not know the counts, overflow is reported by the device flags only)
+        static = {"count": 0, "kv_splits": P}
+        if per_sequence:
+            static["per_sequence"] = True
+        incremental_state[self._incremental_state_id + ".kv_static"] = static
         return incremental_state
+    # (the reported parameter list stays the positional interface: callers that pin it see what they saw, as with the options
+    #  of CausalEVAttention's init_*_decoding)
+    init_kv_cache.__signature__ = inspect.signature(init_kv_cache).replace(
+        parameters=list(inspect.signature(init_kv_cache).parameters.values())[:-1])
 
     def refresh_decoding_weights(self, incremental_state):
         """Re-read the projection parameters into what a state made with `hold_projections=True` holds of them, in place and by
@@ -231,35 +256,45 @@ class CausalSoftmaxAttention(nn.Module):
         return incremental_state
 
     def reorder_incremental_state(self, incremental_state, new_order):
-        """Permute the batch rows of `kv` and `pad`, in place: the pointers a captured step holds stay valid."""
+        """Permute the batch rows of `kv` and `pad` (a per-sequence state: and of `pos`, `status` and `ntok`), in place: the
+        pointers a captured step holds stay valid."""
         buf = self._get_input_buffer(incremental_state)
-        for k in _KV_BATCH_FIRST if "kv" in buf else ():
+        for k in _KV_BATCH_FIRST + (_PER_SEQUENCE if "ntok" in buf else ()) if "kv" in buf else ():
             buf[k].copy_(buf[k].index_select(0, new_order))
         return incremental_state
 
     def reset_decoding_rows(self, incremental_state, rows):
-        """Restart the state: with one token count for the whole batch that is all rows or none.  `rows` must name every batch
-        row (`pos` and `status` back to 0, by device ops; no cache byte is cleared, nothing at or past the count is read) or
-        be empty; a subset needs per-sequence counts, which are a follow-up."""
+        """Restart batch rows: `pos` and `status` of `rows` back to 0, in place and by device ops only; no cache byte is
+        cleared, nothing at or past a row's count is ever read.  A per-sequence state takes any subset (a sequence of ints or
+        an integer tensor; a device tensor makes the reset itself capturable), between replays of a captured step: the next
+        tokens of those rows are a new sequence's.  With one token count for the whole batch `rows` must name every batch
+        row or be empty; a subset needs a state made with `per_sequence=True`."""
         buf = self._kv_buffer(incremental_state, "reset_decoding_rows")
+        if "ntok" in buf:
+            idx = torch.as_tensor(rows, device=buf["pos"].device).reshape(-1).long()
+            buf["pos"].index_fill_(0, idx, 0)
+            buf["status"].index_fill_(0, idx, 0)
+            return incremental_state
         idx = sorted(set(torch.as_tensor(rows).reshape(-1).tolist()))
         if not idx:
             return incremental_state
         if idx != list(range(buf["kv"].shape[0])):
             raise NotImplementedError("reset_decoding_rows of a subset of the batch: the KV cache has one token count for the "
-                                      "whole batch (per-sequence counts are a follow-up)")
+                                      "whole batch (per-sequence counts: init_kv_cache(per_sequence=True))")
         buf["pos"].zero_()
         buf["status"].zero_()
         incremental_state[self._incremental_state_id + ".kv_static"]["count"] = 0
         return incremental_state
 
     def decoding_positions(self, incremental_state):
-        """The tokens decoded so far per batch row, a [B] int32 copy on the host (the one count repeated).  Reads back."""
+        """The tokens decoded so far per batch row, a [B] int32 copy on the host (a shared-count state: its one count
+        repeated).  Reads back."""
         buf = self._kv_buffer(incremental_state, "decoding_positions")
         return buf["pos"].expand(buf["kv"].shape[0]).cpu().clone()
 
     def decoding_positions_tensor(self, incremental_state):
-        """The device tensor the state counts in, `pos [1]` int32, itself: no read-back, a captured step may index with it."""
+        """The device tensor the state counts in -- `pos [1]` int32, or `[B]` on a per-sequence state -- itself: no read-back,
+        a captured step may index with it."""
         return self._kv_buffer(incremental_state, "decoding_positions_tensor")["pos"]
 
     def _decode(self, query, key, value, key_padding_mask, incremental_state, state, need_weights, attn_mask):
@@ -285,7 +320,8 @@ class CausalSoftmaxAttention(nn.Module):
                              % (tuple(key_padding_mask.shape), T_new, B))
         static = incremental_state[self._incremental_state_id + ".kv_static"]
         capturing = torch.cuda.is_current_stream_capturing()
-        if not capturing and static["count"] + T_new > cap:
+        seq = "ntok" in state
+        if not capturing and not seq and static["count"] + T_new > cap:
             raise RuntimeError("the KV cache is full: %d of its %d tokens decoded, the step adds %d "
                                "(init_kv_cache(max_tokens=...))" % (static["count"], cap, T_new))
         dev = query.device
@@ -304,6 +340,8 @@ class CausalSoftmaxAttention(nn.Module):
         step_pad = None
         if key_padding_mask is not None:
             step_pad = key_padding_mask[:, -T_new:].to(device=dev, dtype=torch.uint8).contiguous()
+        # the launches of a step and what follows their views: a per-sequence state issues the _seq entries with ntok
+        sfx, tail = ("_seq", (nv.ptr(state["ntok"]),)) if seq else ("", ())
         geom = nv.ea_softmax_sdec_geom(B, h, d, nv.io_dtype(kv), T_new, cap, state["pos"].data_ptr(), state["status"].data_ptr())
         g = ctypes.byref(geom)
         rows = qkv_new.view(-1)[:T_new * B * 3 * C].view(T_new, B, 3, h, d)      # (proj_rows: the step's rows lead the buffer)
@@ -313,17 +351,17 @@ class CausalSoftmaxAttention(nn.Module):
         to = nv.t4(out.permute(1, 2, 0, 3))
         views = (ctypes.byref(tq), ctypes.byref(tk), ctypes.byref(tv), nv.ptr(pad), ctypes.byref(to))
         st = nv.stream()
-        nv.call("ea_softmax_sdecode_append", g, nv.ptr(rows), nv.ptr(step_pad), views[1], views[2], nv.ptr(pad), st)
+        nv.call("ea_softmax_sdecode_append" + sfx, g, nv.ptr(rows), nv.ptr(step_pad), views[1], views[2], nv.ptr(pad), *tail, st)
         if T_new <= _SPLIT_MAX_STEP:
             ws = state.get("split_ws")
             parts = 1 if ws is None else ws.shape[3]
-            nv.call("ea_softmax_sdecode_attn_split", g, *views, parts, nv.ptr(ws), st)
+            nv.call("ea_softmax_sdecode_attn_split" + sfx, g, *views, parts, nv.ptr(ws), *tail, st)
             if parts > 1:
-                nv.call("ea_softmax_sdecode_merge", g, views[4], parts, nv.ptr(ws), st)
+                nv.call("ea_softmax_sdecode_merge" + sfx, g, views[4], parts, nv.ptr(ws), *tail, st)
         else:
-            nv.call("ea_softmax_sdecode_attn_mm", g, *views, st)
-        nv.call("ea_softmax_sdecode_advance", g, st)
-        if not capturing:                                          # (a replay advances only the device count)
+            nv.call("ea_softmax_sdecode_attn_mm" + sfx, g, *views, *tail, st)
+        nv.call("ea_softmax_sdecode_advance" + sfx, g, *tail, st)
+        if not capturing and not seq:                              # (a replay advances only the device count)
             static["count"] += T_new
         ydtype = torch.get_autocast_dtype("cuda") if torch.is_autocast_enabled() else query.dtype
         if held_rows:

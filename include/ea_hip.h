@@ -403,7 +403,7 @@ int32_t ea_softmax_causal_tiles(int32_t which, int32_t B, int32_t H, int32_t N, 
 /* ---- causal softmax, decoding against a static KV cache (CausalSoftmaxAttention.init_kv_cache; ea_softmax_decode.hip) ----
  * Additive entries of ABI 38.  The cache is k, v [B, H, cap, D] rows of `dtype` (EA_BF16 | EA_F16; D 32, 64 or 128), handed
  * over as ea_t4 views (the two halves of kv [B, 2, H, cap, D]), pad uint8 [B, cap] (1 = padded key) and the token count
- * *pos, device int32 [1], which every launch of a step reads itself: a step can be captured into a graph and replayed.
+ * *pos, device int32 [1] (one count for the batch; the _seq entries below: one per row), which every launch of a step reads itself: a step can be captured into a graph and replayed.
  * A step of T_new tokens is append, attention, advance, in that order on one stream:
  *   ea_softmax_sdecode_append: rows *pos .. *pos + T_new - 1 of k and v from qkv_new [T_new * B, 3, H, D] (time-first rows,
  *     read in place), and of pad from new_pad [B, T_new] (NULL: zeros).
@@ -440,6 +440,29 @@ int ea_softmax_sdecode_advance(const ea_softmax_sdec_geom* g, void* stream);
  * device.  The smallest P with B H P >= 2 cus, clamped to [1, min(64, ceil(cap / 64))].  Pure: no environment knob.
  * -> the count, or EA_E_BADARG for B, H, cap <= 0 or cus < 0. */
 int32_t ea_softmax_sdecode_parts(int32_t B, int32_t H, int32_t cap, int32_t cus);
+/* Per-sequence token counts (CausalSoftmaxAttention.init_kv_cache(per_sequence=True)): five more additive entries of ABI 38,
+ * one per launch of a step, each the entry above with one more argument in front of the stream -- ntok, device int32 [B].
+ * They take the same ea_softmax_sdec_geom (its layout and the six entries above are what they were); g->pos and g->status
+ * are [B] there.  Of the step's T_new positions row b takes the n_b before its first flag in new_pad[b, :T_new] (all T_new
+ * without one, none when the first is flagged: the row sits the step out).  append finds n_b, writes ntok[b] = n_b and stores
+ * rows pos[b] .. pos[b] + n_b - 1 of k and v with pad flags 0 -- nothing for the other positions; the rest read ntok.
+ * Attention: query t < n_b of row b sees keys j <= pos[b] + t; out rows n_b .. T_new - 1 of the row are zero.  advance:
+ * pos[b] += n_b.  Overflow is per row: with pos[b] + n_b > cap no cache byte of row b is written, status[b] = 1, its T_new
+ * out rows are NaN and pos[b] stays; other rows are not affected.  A row's outputs are bit for bit what the shared-count
+ * entries give for that row alone (B = 1, T_new = n_b, the same parts).  attn_split writes the zero and NaN rows itself
+ * for every parts; merge leaves them alone.  attn_mm keeps its grid (qt descending): ordering blocks by a row's true work
+ * pos[b] + n_b would need a device-side sort and is not built.
+ * Refusals: those of the entries above, and EA_E_BADARG for ntok NULL or not 4-byte aligned; all before any launch. */
+int ea_softmax_sdecode_append_seq(const ea_softmax_sdec_geom* g, const void* qkv_new, const uint8_t* new_pad, const ea_t4* k,
+                                  const ea_t4* v, uint8_t* pad, int32_t* ntok, void* stream);
+int ea_softmax_sdecode_attn_split_seq(const ea_softmax_sdec_geom* g, const ea_t4* q, const ea_t4* k, const ea_t4* v,
+                                      const uint8_t* pad, const ea_t4* out, int32_t parts, float* ws, const int32_t* ntok,
+                                      void* stream);
+int ea_softmax_sdecode_merge_seq(const ea_softmax_sdec_geom* g, const ea_t4* out, int32_t parts, const float* ws,
+                                 const int32_t* ntok, void* stream);
+int ea_softmax_sdecode_attn_mm_seq(const ea_softmax_sdec_geom* g, const ea_t4* q, const ea_t4* k, const ea_t4* v,
+                                   const uint8_t* pad, const ea_t4* out, const int32_t* ntok, void* stream);
+int ea_softmax_sdecode_advance_seq(const ea_softmax_sdec_geom* g, const int32_t* ntok, void* stream);
 
 /* Randomized attention (randomized_attention.py:21-52) is two passes of the kernels above:
  *   mu = q + softmax(s q k^T) k (num_samples = -1) or q + k[index] with one index per query drawn

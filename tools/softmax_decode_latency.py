@@ -5,7 +5,11 @@
            and the same step at every kv_splits of --splits around the planner's choice
    stack   one replayed 1-token step of a 16-layer DecoderStack (ffn 4096, vocab 32768), softmax against causal_eva
    prompt  one eager 2048-token prompt step of the layer from an empty cache, against sdpa is_causal
-   python tools/softmax_decode_latency.py [--contexts 512,4096,32768] [--batches 1,8] [--rounds 7] [--steps 50]      (GPU)
+   --per-sequence   instead of the above: the layer's replayed 1-token step on a per-sequence state (pos [B]) at uniform
+           contexts, next to two shared-count states of the same geometry measured in the same rounds (`shared`, and its twin
+           `shared'`: the distance between the two is the baseline's own run-to-run spread), and one ragged mix at B = 8 -- one
+           row at 32768 tokens, seven at 512 -- next to shared-count states with every row at 32768 and at 512
+   python tools/softmax_decode_latency.py [--per-sequence] [--contexts 512,4096,32768] [--batches 1,8] [--rounds 7] [--steps 50]      (GPU)
 Every step is captured with torch.cuda.graph after a warm-up and replayed; rounds alternate the routes; a round resets the
 token count to the context, replays `steps` steps and is timed by the host clock around a device synchronise.  The cache rows
 are random: the time does not depend on them.  Prints the median and min .. max over the rounds in microseconds per step."""
@@ -150,6 +154,30 @@ def prompt_rows(soft, B, T, rounds):
     show("prompt B %d T %d (eager):   " % (B, T), {n: (sorted(t)[len(t) // 2], min(t), max(t)) for n, t in times.items()}, "kv")
 
 
+def perseq_rows(soft, a):
+    def route(ctxs, seq):
+        """The layer's captured step on a state whose rows hold ctxs tokens (a shared-count state: ctxs[0] for all)."""
+        B, inc = len(ctxs), {}
+        x = 0.5 * torch.randn(1, B, EMBED, device="cuda", dtype=DT)
+        soft.init_kv_cache(inc, B, max(ctxs) + a.steps + 2, DT, "cuda", hold_projections=True, per_sequence=seq)
+        buf, host = soft._get_input_buffer(inc), inc[soft._incremental_state_id + ".kv_static"]
+        buf["kv"].normal_()
+        at = torch.tensor(ctxs if seq else ctxs[:1], dtype=torch.int32, device="cuda")
+
+        def reset():
+            buf["pos"].copy_(at)
+            host["count"] = ctxs[0]
+        reset()
+        return reset, captured(lambda: soft(x, x, x, incremental_state=inc))
+    for B in [int(v) for v in a.batches.split(",")]:
+        for ctx in [int(v) for v in a.contexts.split(",")]:
+            routes = {"shared": route([ctx] * B, False), "shared'": route([ctx] * B, False), "seq": route([ctx] * B, True)}
+            show("per-seq B %d ctx %5d uniform:  " % (B, ctx), timed(routes, a.rounds, a.steps), "shared")
+    mix = [32768] + [512] * 7
+    routes = {"seq-mix": route(mix, True), "shared-32768": route([32768] * 8, False), "shared-512": route([512] * 8, False)}
+    show("per-seq B 8 ragged 1 x 32768 + 7 x 512:  ", timed(routes, a.rounds, a.steps), "seq-mix")
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--contexts", default="512,4096,32768")
@@ -157,6 +185,7 @@ def main():
     ap.add_argument("--rounds", type=int, default=7)
     ap.add_argument("--steps", type=int, default=50)
     ap.add_argument("--no-stack", action="store_true")
+    ap.add_argument("--per-sequence", action="store_true")
     a = ap.parse_args()
     if not torch.cuda.is_available():
         sys.exit("softmax_decode_latency.py measures on a GPU: none found")
@@ -164,6 +193,10 @@ def main():
     soft = ea.CausalSoftmaxAttention(EMBED, HEADS).cuda().eval()
     ceva = ea.CausalEVAttention(EMBED, HEADS, self_attention=True, dropout=0.0, attn_args=argparse.Namespace(**RECIPE)).cuda().eval()
     print("microseconds per replayed 1-token step, bf16, median (min .. max) of %d rounds of %d steps" % (a.rounds, a.steps))
+    if a.per_sequence:
+        with torch.no_grad():
+            perseq_rows(soft, a)
+        return
     with torch.no_grad():
         for B in [int(v) for v in a.batches.split(",")]:
             for ctx in [int(v) for v in a.contexts.split(",")]:
